@@ -1,6 +1,6 @@
 """bench.py — the SpMM hot path on MI355X, BASELINE.json's metric.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5] [--dump-outputs DIR]
 
 A step is one pass of the hot path over the whole synthetic matrix:
 C = A_csr · B through `custom_mm.naive_spmm` (row-split HIP kernel).  N = 1 runs
@@ -21,6 +21,12 @@ Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (C3:
 spmm_wave_row_panel_kernel, two launches per product), from HIP events on the launch
 stream inside the timed region; `cpu_baseline` times the oracle (a CPU port of the
 reference's algorithm — test infrastructure) on the host cores after the timed region.
+
+`--dump-outputs DIR` writes, after the timed region, what the timed path handed its caller in
+the last step as DIR/<name>.npy (float32): C for c3 / c2, the two products and the four
+gradients for c5.  An output beyond its share of the budget (DUMP_BUDGET_BYTES in all) is cut
+to a fixed sample of its rows, chosen by a seeded generator from the shape alone, so that two
+builds of the project can be compared output for output on the same seeded inputs.
 """
 import argparse
 import hashlib
@@ -50,6 +56,39 @@ WORKLOADS = {
     "c3": (1 << 20, 1 << 20, 1e-4, 256, "CSR 1M x 1M at 0.01% nnz x dense 1M x 256 fp32 (BASELINE.json configs[2])"),
     "c2": (1 << 16, 1 << 16, 1e-3, 128, "CSR 64k x 64k at 0.1% nnz x dense 64k x 128 fp32 (BASELINE.json configs[1])"),
 }
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all files of one --dump-outputs together (under 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: each device tensor of `outputs` ({name: tensor}) as out_dir/<name>.npy in float32.  A tensor larger
+    than its equal share of DUMP_BUDGET_BYTES is viewed as rows (leading dims flattened) and cut to a sorted sample of them
+    drawn by PCG64(DUMP_SAMPLE_SEED): the same rows for the same shape in every run and every build.  Returns
+    {name: description} for the log."""
+    import torch
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(outputs))
+    written, desc = 0, {}
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() * 4 <= share:
+            host = t.float().cpu().numpy()
+            desc[name] = f"whole {tuple(t.shape)}"
+        else:
+            rows = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+            n = share // (rows.shape[1] * 4)
+            assert n >= 1, (name, tuple(t.shape))
+            idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(rows.shape[0], n, replace=False))
+            host = rows.index_select(0, torch.from_numpy(idx).to(rows.device)).float().cpu().numpy()
+            desc[name] = f"{n} of the {rows.shape[0]} rows of {tuple(t.shape)} as {tuple(rows.shape)} (PCG64 seed {DUMP_SAMPLE_SEED})"
+        path = out_dir / f"{name}.npy"
+        np.save(path, np.ascontiguousarray(host, dtype=np.float32))
+        written += path.stat().st_size
+    assert written <= 64_000_000, written
+    return desc
 
 
 def algorithmic_bytes(nnz, M, N):
@@ -344,6 +383,8 @@ def self_launch(args):
            "--exchange", args.exchange]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", str(Path(args.dump_outputs).resolve())]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: RCCL needs it on this pool
     env.setdefault("OMP_NUM_THREADS", "4")
@@ -378,8 +419,11 @@ def bench_c5(args):
     def step():
         for t in (q, k, v, probs):
             t.grad = None
-        matmuls.cublasTransbMM.apply(q, k).backward(d_scores)
-        matmuls.cublasMM.apply(probs, v).backward(d_ctx)
+        scores = matmuls.cublasTransbMM.apply(q, k)
+        scores.backward(d_scores)
+        ctx = matmuls.cublasMM.apply(probs, v)
+        ctx.backward(d_ctx)
+        return scores, ctx
 
     for _ in range(args.warmup):
         step()
@@ -388,10 +432,15 @@ def bench_c5(args):
     t0 = time.perf_counter()
     ev[0].record()
     for i in range(args.steps):
-        step()
+        last = step()
         ev[i + 1].record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        scores, ctx = last
+        dumped = dump_outputs(args.dump_outputs, {"scores": scores, "ctx": ctx, "q_grad": q.grad, "k_grad": k.grad,
+                                                  "probs_grad": probs.grad, "v_grad": v.grad})
+        print(f"dumped to {args.dump_outputs}: {dumped}", file=sys.stderr, flush=True)
     flops = 6 * 2.0 * Bz * H * S * S * D
     step_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps)]
     kern_ms = ev[0].elapsed_time(ev[-1]) / args.steps
@@ -442,7 +491,12 @@ def main():
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="N = 1: do not measure roofline.traffic in this run (two rocprofv3 --pmc child passes behind the timed "
                          "region, ~20 s each); the committed record of the same sources is quoted instead, or null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed step computed as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of rows where an output is larger than its share of 48 MiB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         if args.workload == "c5":
@@ -601,6 +655,9 @@ def main():
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax)
+    if args.dump_outputs and rank == 0:  # before any later leg writes C again
+        dumped = dump_outputs(args.dump_outputs, {"C": C[:M]})
+        print(f"dumped to {args.dump_outputs}: {dumped}", file=sys.stderr, flush=True)
     compute_only_ms = gather_only_ms = None
     if world > 1:
         # the same steps without the all-gather: what the row shards alone cost (reported beside the

@@ -183,15 +183,21 @@ def test_self_launch_builds_a_torchrun_child_and_relays_rank0(monkeypatch, capsy
     monkeypatch.setattr(bench.subprocess, "run", fake_run)
     monkeypatch.delitem(sys.modules, "torch", raising=False)
     args = argparse.Namespace(gpus=4, steps=7, warmup=2, workload="c3", chunks=0, split="rows", exchange="auto",
-                              no_cpu_baseline=True)
+                              no_cpu_baseline=True, dump_outputs=None)
     assert bench.self_launch(args) == 0
     cmd = seen["cmd"]
     assert cmd[:3] == [sys.executable, "-m", "torch.distributed.run"]
     assert "--nproc-per-node=4" in cmd and cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     tail = cmd[cmd.index(str(PROFILES.parent / "bench.py")) + 1:]
     assert tail[:6] == ["--gpus", "4", "--steps", "7", "--warmup", "2"] and "--no-cpu-baseline" in tail
+    assert "--dump-outputs" not in tail
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     assert capsys.readouterr().out.strip() == '{"metric": "x", "n_gpus": 4}'
+    # --dump-outputs reaches the ranks as an absolute path (rank 0 writes it)
+    assert bench.self_launch(argparse.Namespace(**{**vars(args), "dump_outputs": "dumps"})) == 0
+    tail = seen["cmd"][seen["cmd"].index(str(PROFILES.parent / "bench.py")) + 1:]
+    assert tail[tail.index("--dump-outputs") + 1] == str(Path("dumps").resolve())
+    capsys.readouterr()
 
     def failing_run(cmd, env=None, stdout=None, text=None):
         return subprocess.CompletedProcess(cmd, 3, stdout="")
@@ -274,3 +280,34 @@ def test_ranks_get_rank0s_inputs_with_or_without_room_for_the_files(tmp_path, no
         got = np.load(tmp_path / f"in_{r}.npz")
         assert all(np.array_equal(got[k], w) for k, w in (("rowptr", rowptr), ("col", col), ("val", val), ("B", B)))
         assert str(got["kind"]) == ("generated" if (r == 0 or no_room) else "mapped")
+
+
+# --- --dump-outputs: what the timed path computed, whole or as a fixed sample of rows, within the budget ----------------
+
+def test_dump_outputs_whole_or_a_fixed_row_sample_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1 << 20)
+    g = torch.Generator().manual_seed(5)
+    small = torch.rand(64, 32, generator=g)
+    big = torch.rand(3, 2048, 128, generator=g)           # 3 MiB: beyond its 512 KiB share
+    bench.dump_outputs(tmp_path / "a", {"small": small, "big": big})
+    got = np.load(tmp_path / "a" / "small.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    rows = np.load(tmp_path / "a" / "big.npy")
+    assert rows.dtype == np.float32 and rows.shape == ((512 << 10) // (128 * 4), 128)
+    flat = big.reshape(-1, 128).numpy()
+    idx = [int(np.flatnonzero((flat == r).all(axis=1))[0]) for r in rows[:8]]
+    assert idx == sorted(idx)                             # sorted rows of the flattened leading dims
+    # the same shape gives the same rows in a second run (another build compares output for output)
+    bench.dump_outputs(tmp_path / "b", {"small": small * 2, "big": big * 2})
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), rows * 2)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= (1 << 20) + 1024
+
+
+def test_steps_below_one_are_refused_before_anything_runs():
+    import subprocess
+    proc = subprocess.run([sys.executable, str(PROFILES.parent / "bench.py"), "--steps", "0"], capture_output=True,
+                          text=True, timeout=120)
+    assert proc.returncode == 2 and "--steps must be >= 1" in proc.stderr
