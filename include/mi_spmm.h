@@ -587,6 +587,48 @@ int mi_coo_to_csr_host(int32_t M, int64_t nnz, const int32_t* coo_row,
  *   mi_ipc_open_count : opens not yet closed in this process (tests: nothing is left mapped)
  * ------------------------------------------------------------------------ */
 #define MI_IPC_HANDLE_BYTES 64
+/* ------------------------------------------------------------------------ *
+ * Reductions other than sum over a row's products: torch.sparse.mm(A, B, reduce=...)
+ * (aten::_sparse_mm_reduce_impl), which torch implements for CSR on the CPU only.  The reference's Reducer
+ * (src/naive_reducer.cuh:23-101) has MIN / MAX branches, but its wrapper pins reduce = "sum"
+ * (src/naive_sparse_mm.cu:119).
+ *   MI_REDUCE_SUM   the bits of mi_spmm_csr_ws_f32 with the same workspace;
+ *   MI_REDUCE_MEAN  those bits divided by the row's entry count (correctly rounded); an empty row gives +0;
+ *   MI_REDUCE_AMAX  with p_e = val[e] · B[col[e], j] (one fp32 multiply): the sequential scan "start at (-inf, nnz),
+ *                   take (p_e, e) iff p_e > cur || isnan(p_e)", i.e. the largest e with a NaN product if there is one,
+ *                   else the smallest e attaining the maximum (-0 == +0 is a tie; the output keeps p_e's sign), else
+ *                   (-inf, nnz); an empty row gives (+0, nnz);
+ *   MI_REDUCE_AMIN  the same with <.
+ * arg (int32, [M, ldarg], may be NULL; only for AMAX / AMIN) receives the selected entry index e (nnz: none).
+ * With a workspace of mi_spmm_csr_reduce_workspace_bytes(nnz, N) bytes (16-byte aligned), rows with more than 8192
+ * entries are cut into max(1, len / 16384) chunks, one workgroup each (AMAX / AMIN: same result — the selection does
+ * not depend on the split; SUM / MEAN: mi_spmm_csr_ws_f32's long-row order).  NULL: every row is one wave's.
+ * Validation before any HIP call: an unknown code, or arg with SUM / MEAN → MI_EINVAL; M == 0 or N == 0 → MI_OK;
+ * nnz ≥ 2³¹ → MI_ERANGE; a NULL required pointer → MI_EINVAL.  No host synchronisation: graph-capturable.
+ * ------------------------------------------------------------------------ */
+enum { MI_REDUCE_SUM = 0, MI_REDUCE_MEAN = 1, MI_REDUCE_AMAX = 2, MI_REDUCE_AMIN = 3 };
+size_t mi_spmm_csr_reduce_workspace_bytes(int64_t nnz, int32_t N);
+int mi_spmm_csr_reduce_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t nnz,
+                           int32_t M, int32_t K, int32_t N, const float* B, int64_t ldb, float* C,
+                           int64_t ldc, int32_t* arg, int64_t ldarg, int reduce, void* workspace,
+                           size_t workspace_bytes, mi_stream_t stream);
+/* out[i, :] = in[i, :] / (rowptr[i+1] − rowptr[i]), correctly rounded; rows without entries are copied.
+ * in == out is allowed (the mean's epilogue; its gradient g / count out of place). */
+int mi_spmm_rows_divide_f32(const int32_t* rowptr, int32_t M, int32_t N, const float* in, int64_t ldin,
+                            float* out, int64_t ldout, mi_stream_t stream);
+/* Gradients of AMAX / AMIN given the forward's arg, without float atomics (deterministic):
+ *   grad_val[e] = Σ_j [arg[i, j] == e] · G[i, j] · B[col[e], j]      (one wave per row, j ascending, then a xor tree)
+ *   grad_B[k, j] = Σ_t [arg[i, j] == perm[t]] · val[perm[t]] · G[i, j] (i = t_col[t]; over row k of Aᵀ in order)
+ * grad_B runs on Aᵀ's pattern (t_rowptr [K+1], t_col = original rows) and the permutation perm that carries an entry of
+ * Aᵀ to its index in A (what mi_csr_transpose_f32 gives for the values 0, 1, 2, …). */
+int mi_spmm_reduce_grad_val_f32(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M, int32_t K,
+                                int32_t N, const float* B, int64_t ldb, const float* G, int64_t ldg,
+                                const int32_t* arg, int64_t ldarg, float* grad_val, mi_stream_t stream);
+int mi_spmm_reduce_grad_b_f32(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm,
+                              const float* val, int64_t nnz, int32_t M, int32_t K, int32_t N, const float* G,
+                              int64_t ldg, const int32_t* arg, int64_t ldarg, float* grad_b, int64_t ldgb,
+                              mi_stream_t stream);
+
 int mi_ipc_export(const void* dev_ptr, void* handle_out, int64_t* offset_out, int64_t* alloc_bytes_out);
 int mi_ipc_open(const void* handle, void** base_out);
 int mi_ipc_close(const void* handle);

@@ -1,0 +1,568 @@
+// CSR × dense with a max / min / mean reduction over each row's products, and the gradients of max / min, for gfx950
+// (MI355X), fp32.  Contract: include/mi_spmm.h (mi_spmm_csr_reduce_f32 and the entries after it); the semantics are those
+// of torch.sparse.mm(A, B, reduce=...) (aten::_sparse_mm_reduce_impl), which torch implements for CSR on the CPU only.
+//
+// amax (amin mirrors it with <): p_e = val[e] · B[col[e], j] (one fp32 multiply).  The result is the sequential scan
+// "start at (-inf, nnz), take (p_e, e) iff p_e > cur || isnan(p_e)".  That scan equals an order-independent selection —
+// the largest e with a NaN product if there is one, else the smallest e attaining the maximum (-0 == +0 is a tie; the
+// output keeps p_arg's sign), else (-inf, nnz) — so a row may be split and its partial results combined (`pick`).
+// An empty row gives (+0, nnz).  fmaxf / v_max_f32 drop NaN and do not order ±0: every step is compare-and-select.
+//
+// The reference's Reducer (src/naive_reducer.cuh) has MIN / MAX branches but its wrapper pins reduce = "sum"
+// (src/naive_sparse_mm.cu:119); it would start from lowest() instead of -inf and never select a NaN.  This file follows
+// torch instead.
+//
+// Kernels:
+//  * reduce_rows_kernel: G lanes per row (G = 64: one wave, col / val through the scalar unit), W = 4 columns per lane
+//    (dword-aligned 16-byte loads; a row's last, partial quad is shifted back over its neighbour — max / min are
+//    idempotent, the shared columns are scanned twice and stored twice with the same bits) or W = 1 for N < 4.  U gathers
+//    in flight per lane; the batch at a row's end repeats its last entry instead of branching (idempotent again).
+//    With a workspace, rows beyond kHubRow entries are skipped and listed (as spmm_device.h's long_list_append does).
+//  * reduce_hub_kernel: a listed row cut into S = max(1, len / kHubChunk) chunks, a 16-wave workgroup per chunk and
+//    64·W columns, waves combined through LDS; S = 1 writes the result, else a partial (value, arg) row.
+//  * reduce_hub_combine_kernel: the S partials of a row, combined in order (the order does not matter: `pick` is exact).
+//  * rows_divide_kernel: out[i, :] = in[i, :] / count(i), correctly rounded (mean, and its gradient g / count).
+//  * reduce_grad_val_kernel / reduce_grad_b_kernel: the gradients of max / min (below).  No float atomics: every
+//    result is one fixed-order chain.
+#include "mi_common.h"
+
+namespace {
+
+constexpr int kHubRow = 8192;     // rows with more entries are split when the caller gave a workspace
+constexpr int kHubChunk = 16384;  // entries per workgroup of a split row (S = max(1, len / kHubChunk))
+constexpr int kHubWaves = 16;
+constexpr int kU = 8;             // gathers in flight per lane
+
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+typedef int i32x4u __attribute__((ext_vector_type(4), aligned(4)));
+
+template <int W>
+struct Cols;
+template <>
+struct Cols<4> {
+  typedef f32x4u F;
+  typedef i32x4u I;
+};
+template <>
+struct Cols<1> {
+  typedef float F;
+  typedef int I;
+};
+
+template <int W>
+__device__ __forceinline__ float& at(typename Cols<W>::F& v, int k) {
+  if constexpr (W == 1) return v;
+  else return reinterpret_cast<float*>(&v)[k];
+}
+template <int W>
+__device__ __forceinline__ int& at(typename Cols<W>::I& v, int k) {
+  if constexpr (W == 1) return v;
+  else return reinterpret_cast<int*>(&v)[k];
+}
+
+// One step of the sequential scan.
+template <bool MAX>
+__device__ __forceinline__ void scan(float p, int e, float& cur, int& arg) {
+  const bool take = (MAX ? p > cur : p < cur) || __builtin_isnan(p);
+  cur = take ? p : cur;
+  arg = take ? e : arg;
+}
+
+// (cur, arg) ← the selection over the union of two scans of disjoint entry sets (order-independent).
+template <bool MAX>
+__device__ __forceinline__ void pick(float v, int a, float& cur, int& arg) {
+  const bool vn = __builtin_isnan(v), cn = __builtin_isnan(cur);
+  const bool take = vn ? (!cn || a > arg) : (!cn && ((MAX ? v > cur : v < cur) || (v == cur && a < arg)));
+  cur = take ? v : cur;
+  arg = take ? a : arg;
+}
+
+template <bool MAX>
+__device__ __forceinline__ float scan_start() {
+  return MAX ? -__builtin_inff() : __builtin_inff();
+}
+
+// Workspace (ints): [0] rows listed, [1] chunk slots handed out, [2] partial rows handed out, [3] –; cap_e entries of
+// {row, slot base, S, partial base}; cap_s slot → entry; then (16-B aligned) cap_p × N floats and cap_p × N ints.
+struct HubArg {
+  int* ws;  // nullptr: no row is split
+  int cap_e, cap_s, cap_p;
+};
+
+__device__ __forceinline__ void hub_append(const HubArg& h, int row, int len) {
+  int* ws = h.ws;
+  const int S = len / kHubChunk < 1 ? 1 : len / kHubChunk;
+  const int e = atomicAdd(&ws[0], 1);
+  const int sb = atomicAdd(&ws[1], S);
+  const int pb = S > 1 ? atomicAdd(&ws[2], S) : 0;
+  // the caps hold for any rowptr consistent with nnz; a lying rowptr must not write out of bounds
+  if (e >= h.cap_e) return;
+  const bool fits = sb + S <= h.cap_s && (S <= 1 || pb + S <= h.cap_p);
+  int* ent = ws + 4 + 4 * (long)e;
+  ent[0] = row;
+  ent[1] = sb;
+  ent[2] = fits ? S : 0;
+  ent[3] = pb;
+  if (!fits) return;
+  int* owner = ws + 4 + 4 * (long)h.cap_e;
+  for (int g = 0; g < S; ++g) owner[sb + g] = e;
+}
+
+// Scan entries [p, end) of one row for the W columns at Bl (= B + first column).  The batch at the end repeats entry
+// end − 1 instead of branching: a repeated (p_e, e) never changes the scan's state.
+template <int W, bool MAX>
+__device__ __forceinline__ void scan_range(const int* __restrict__ col, const float* __restrict__ val, const float* Bl,
+                                           long ldb, int p, int end, typename Cols<W>::F& cur, typename Cols<W>::I& arg) {
+  using F = typename Cols<W>::F;
+  for (; p < end; p += kU) {
+    int c[kU];
+    float v[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int q = p + u < end ? p + u : end - 1;
+      c[u] = col[q];
+      v[u] = val[q];
+    }
+    F x[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) x[u] = *reinterpret_cast<const F*>(Bl + (long)c[u] * ldb);
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int e = p + u < end ? p + u : end - 1;
+#pragma unroll
+      for (int k = 0; k < W; ++k) scan<MAX>(v[u] * at<W>(x[u], k), e, at<W>(cur, k), at<W>(arg, k));
+    }
+  }
+}
+
+// First column of lane group position gl in pass c0, or -1 when the lane has no columns there.
+template <int W>
+__device__ __forceinline__ int lane_column(int c0, int gl, int N) {
+  int q = c0 + gl * W;
+  if (q >= N) return -1;
+  if (W > 1 && q + W > N) q = N - W;  // the last, partial quad: shifted back over its neighbour
+  return q;
+}
+
+// ---------------------------------------------------------------------------
+// G lanes per row, 256 / G rows per workgroup.  grid = ⌈M / (256/G)⌉, block = 256.
+// ---------------------------------------------------------------------------
+template <int G, int W, bool MAX, bool ARG>
+__global__ __launch_bounds__(256) void reduce_rows_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                          const float* __restrict__ val, const float* __restrict__ B,
+                                                          float* __restrict__ C, int* __restrict__ argout, int M, int N,
+                                                          long ldb, long ldc, long ldarg, int nnz, HubArg hub) {
+  using F = typename Cols<W>::F;
+  using I = typename Cols<W>::I;
+  long row = ((long)blockIdx.x * 256 + threadIdx.x) / G;
+  if constexpr (G == 64) row = __builtin_amdgcn_readfirstlane((int)row);
+  const int gl = threadIdx.x % G;
+  if (row >= M) return;
+  const int p0 = rowptr[row];
+  const int end = rowptr[row + 1];
+  if (hub.ws != nullptr && end - p0 > kHubRow) {
+    if (gl == 0) hub_append(hub, (int)row, end - p0);
+    return;
+  }
+  for (int c0 = 0; c0 < N; c0 += G * W) {
+    const int q = lane_column<W>(c0, gl, N);
+    if (q < 0) break;
+    F cur;
+    I arg;
+#pragma unroll
+    for (int k = 0; k < W; ++k) at<W>(cur, k) = scan_start<MAX>(), at<W>(arg, k) = nnz;
+    scan_range<W, MAX>(col, val, B + q, ldb, p0, end, cur, arg);
+    if (end == p0) {
+#pragma unroll
+      for (int k = 0; k < W; ++k) at<W>(cur, k) = 0.f;
+    }
+    __builtin_nontemporal_store(cur, reinterpret_cast<F*>(C + row * ldc + q));
+    if constexpr (ARG) __builtin_nontemporal_store(arg, reinterpret_cast<I*>(argout + row * ldarg + q));
+  }
+}
+
+// ---------------------------------------------------------------------------
+// One chunk of a listed row × 64·W columns.  grid = (cap_s, ⌈N / 64W⌉), block = 1024 (16 waves, each a contiguous
+// sixteenth of the chunk), LDS = 16 · 64 · W · 8 bytes.
+// ---------------------------------------------------------------------------
+template <int W, bool MAX>
+__global__ __launch_bounds__(1024) void reduce_hub_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                         const float* __restrict__ val, const float* __restrict__ B,
+                                                         float* __restrict__ C, int* __restrict__ argout, int N, long ldb,
+                                                         long ldc, long ldarg, int nnz, const int* __restrict__ ws,
+                                                         int cap_e, float* __restrict__ part_val,
+                                                         int* __restrict__ part_arg) {
+  using F = typename Cols<W>::F;
+  using I = typename Cols<W>::I;
+  __shared__ float s_val[kHubWaves][64 * W];
+  __shared__ int s_arg[kHubWaves][64 * W];
+  const int slot = blockIdx.x;
+  if (slot >= __builtin_amdgcn_readfirstlane(ws[1])) return;
+  const int e = ws[4 + 4 * (long)cap_e + slot];
+  if (e < 0 || e >= cap_e) return;  // (a rowptr inconsistent with nnz: a slot nobody owns)
+  const int* ent = ws + 4 + 4 * (long)e;
+  const int row = ent[0], sb = ent[1], S = ent[2], pb = ent[3];
+  if (S == 0) return;
+  const int g = slot - sb;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int start = rowptr[row];
+  const long len = rowptr[row + 1] - start;
+  const int lo = start + (int)(len * g / S), hi = start + (int)(len * (g + 1) / S);
+  const int wlo = lo + (int)((long)(hi - lo) * wave / kHubWaves), whi = lo + (int)((long)(hi - lo) * (wave + 1) / kHubWaves);
+  const int q = lane_column<W>(blockIdx.y * 64 * W, lane, N);
+  F cur;
+  I arg;
+#pragma unroll
+  for (int k = 0; k < W; ++k) at<W>(cur, k) = scan_start<MAX>(), at<W>(arg, k) = nnz;
+  if (q >= 0) scan_range<W, MAX>(col, val, B + q, ldb, wlo, whi, cur, arg);
+#pragma unroll
+  for (int k = 0; k < W; ++k) s_val[wave][lane * W + k] = at<W>(cur, k), s_arg[wave][lane * W + k] = at<W>(arg, k);
+  __syncthreads();
+  if (wave != 0 || q < 0) return;
+  for (int w = 1; w < kHubWaves; ++w) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) pick<MAX>(s_val[w][lane * W + k], s_arg[w][lane * W + k], at<W>(cur, k), at<W>(arg, k));
+  }
+  if (S == 1) {
+    *reinterpret_cast<F*>(C + (long)row * ldc + q) = cur;
+    if (argout) *reinterpret_cast<I*>(argout + (long)row * ldarg + q) = arg;
+  } else {
+    *reinterpret_cast<F*>(part_val + (long)(pb + g) * N + q) = cur;
+    *reinterpret_cast<I*>(part_arg + (long)(pb + g) * N + q) = arg;
+  }
+}
+
+// The S > 1 rows: partials g = 0 … S−1 combined per column.  grid = (cap_e, ⌈N / 256⌉), block = 256.
+template <bool MAX>
+__global__ __launch_bounds__(256) void reduce_hub_combine_kernel(float* __restrict__ C, int* __restrict__ argout, int N,
+                                                                 long ldc, long ldarg, const int* __restrict__ ws,
+                                                                 const float* __restrict__ part_val,
+                                                                 const int* __restrict__ part_arg) {
+  const int e = blockIdx.x;
+  if (e >= __builtin_amdgcn_readfirstlane(ws[0])) return;
+  const int* ent = ws + 4 + 4 * (long)e;
+  const int row = ent[0], S = ent[2], pb = ent[3];
+  const int j = blockIdx.y * 256 + threadIdx.x;
+  if (S <= 1 || j >= N) return;
+  float cur = part_val[(long)pb * N + j];
+  int arg = part_arg[(long)pb * N + j];
+  for (int g = 1; g < S; ++g) pick<MAX>(part_val[(long)(pb + g) * N + j], part_arg[(long)(pb + g) * N + j], cur, arg);
+  C[(long)row * ldc + j] = cur;
+  if (argout) argout[(long)row * ldarg + j] = arg;
+}
+
+// out[i, j] = in[i, j] / count(i) (correctly rounded); rows without entries are copied.  One wave per row, block = 256.
+__global__ __launch_bounds__(256) void rows_divide_kernel(const int* __restrict__ rowptr, int M, int N,
+                                                          const float* in, long ldin, float* out, long ldout) {
+  const long row = __builtin_amdgcn_readfirstlane((int)(((long)blockIdx.x * 256 + threadIdx.x) >> 6));
+  if (row >= M) return;
+  const int cnt = rowptr[row + 1] - rowptr[row];
+  const float d = (float)cnt;
+  for (int j = threadIdx.x & 63; j < N; j += 64) {
+    const float x = in[row * ldin + j];
+    out[row * ldout + j] = cnt > 0 ? __fdiv_rn(x, d) : x;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// grad_val[e] = Σ_j [arg[i, j] == e] · g[i, j] · B[col[e], j] for the entries e of row i.  One wave per row; lane l
+// keeps columns 64t + l of the row's arg and g in registers (T chunks; T = 0: N > 1024, read per entry from the
+// caches).  Per entry, a B load only where arg == e, an fmaf chain over t ascending, a xor tree (32 … 1) across the
+// wave.  block = 256 (4 rows).
+// ---------------------------------------------------------------------------
+template <int T>
+__global__ __launch_bounds__(256) void reduce_grad_val_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                              int M, int N, const float* __restrict__ B, long ldb,
+                                                              const float* __restrict__ G, long ldg,
+                                                              const int* __restrict__ argin, long ldarg,
+                                                              float* __restrict__ grad_val) {
+  const long row = __builtin_amdgcn_readfirstlane((int)(((long)blockIdx.x * 256 + threadIdx.x) >> 6));
+  if (row >= M) return;
+  const int lane = threadIdx.x & 63;
+  const int p0 = rowptr[row], end = rowptr[row + 1];
+  const float* Gr = G + row * ldg;
+  const int* Ar = argin + row * ldarg;
+  constexpr int TR = T > 0 ? T : 1;
+  float gk[TR];
+  int ak[TR];
+  if constexpr (T > 0) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      const int j = 64 * t + lane;
+      ak[t] = j < N ? Ar[j] : -1;
+      gk[t] = j < N ? Gr[j] : 0.f;
+    }
+  }
+  for (int e = p0; e < end; ++e) {
+    const float* Bc = B + (long)col[e] * ldb;
+    float acc = 0.f;
+    if constexpr (T > 0) {
+#pragma unroll
+      for (int t = 0; t < T; ++t)
+        if (ak[t] == e) acc = __builtin_fmaf(gk[t], Bc[64 * t + lane], acc);
+    } else {
+      for (int j = lane; j < N; j += 64)
+        if (Ar[j] == e) acc = __builtin_fmaf(Gr[j], Bc[j], acc);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if (lane == 0) grad_val[e] = acc;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// grad_B[k, j] = Σ_{t in row k of Aᵀ} [arg[i, j] == perm[t]] · val[perm[t]] · g[i, j],  i = t_col[t], in Aᵀ order (one fmaf
+// chain per element).  G lanes per row of Aᵀ, W columns per lane (the forward's layout; shifted-back quads compute the
+// same chain twice).  grid = ⌈K / (256/G)⌉, block = 256.
+// ---------------------------------------------------------------------------
+template <int G, int W>
+__global__ __launch_bounds__(256) void reduce_grad_b_kernel(const int* __restrict__ t_rowptr, const int* __restrict__ t_col,
+                                                            const int* __restrict__ perm, const float* __restrict__ val,
+                                                            int K, int N, const float* __restrict__ Gm, long ldg,
+                                                            const int* __restrict__ argin, long ldarg,
+                                                            float* __restrict__ grad_b, long ldgb) {
+  using F = typename Cols<W>::F;
+  using I = typename Cols<W>::I;
+  long row = ((long)blockIdx.x * 256 + threadIdx.x) / G;
+  if constexpr (G == 64) row = __builtin_amdgcn_readfirstlane((int)row);
+  const int gl = threadIdx.x % G;
+  if (row >= K) return;
+  const int p0 = t_rowptr[row], end = t_rowptr[row + 1];
+  for (int c0 = 0; c0 < N; c0 += G * W) {
+    const int q = lane_column<W>(c0, gl, N);
+    if (q < 0) break;
+    F acc;
+#pragma unroll
+    for (int k = 0; k < W; ++k) at<W>(acc, k) = 0.f;
+    for (int p = p0; p < end; p += kU) {
+      int e[kU], i[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const int t = p + u < end ? p + u : end - 1;
+        e[u] = perm[t];
+        i[u] = t_col[t];
+      }
+      I a[kU];
+#pragma unroll
+      for (int u = 0; u < kU; ++u) a[u] = *reinterpret_cast<const I*>(argin + (long)i[u] * ldarg + q);
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        if (p + u >= end) break;
+        const float v = val[e[u]];
+#pragma unroll
+        for (int k = 0; k < W; ++k)
+          if (at<W>(a[u], k) == e[u]) at<W>(acc, k) = __builtin_fmaf(v, Gm[(long)i[u] * ldg + q + k], at<W>(acc, k));
+      }
+    }
+    *reinterpret_cast<F*>(grad_b + row * ldgb + q) = acc;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+struct HubWs {
+  long cap_e, cap_s, cap_p;
+  size_t part_val_off, part_arg_off, bytes;
+};
+HubWs hub_ws_layout(int64_t nnz, int32_t N) {
+  HubWs w;
+  w.cap_e = nnz / kHubRow + 1;
+  w.cap_p = nnz / kHubChunk;
+  w.cap_s = w.cap_e + w.cap_p;
+  const size_t ints = 4 + 4 * (size_t)w.cap_e + (size_t)w.cap_s;
+  w.part_val_off = (ints * sizeof(int) + 15) / 16 * 16;
+  w.part_arg_off = w.part_val_off + (size_t)w.cap_p * (size_t)N * sizeof(float);
+  w.bytes = w.part_arg_off + (size_t)w.cap_p * (size_t)N * sizeof(int);
+  return w;
+}
+
+// lanes per row for a width: a power of two with G·W ≥ N, at most a wave
+template <int W>
+int lanes_for(int32_t N) {
+  const int need = (N + W - 1) / W;
+  return need >= 64 ? 64 : mi::pow2_ceil(need);
+}
+
+template <int W, bool MAX, bool ARG>
+int launch_rows_w(int G, const int32_t* rowptr, const int32_t* col, const float* val, const float* B, float* C, int32_t* arg,
+                  int32_t M, int32_t N, int64_t ldb, int64_t ldc, int64_t ldarg, int32_t nnz, const HubArg& hub,
+                  hipStream_t s) {
+  const dim3 grid((unsigned)(((int64_t)M * G + 255) / 256));
+#define MI_REDUCE_ROWS(GG)                                                                                                  \
+  case GG:                                                                                                                 \
+    hipLaunchKernelGGL((reduce_rows_kernel<GG, W, MAX, ARG>), grid, dim3(256), 0, s, rowptr, col, val, B, C, arg, M, N, ldb, \
+                       ldc, ldarg, nnz, hub);                                                                              \
+    break;
+  switch (G) {
+    MI_REDUCE_ROWS(1)
+    MI_REDUCE_ROWS(2)
+    MI_REDUCE_ROWS(4)
+    MI_REDUCE_ROWS(8)
+    MI_REDUCE_ROWS(16)
+    MI_REDUCE_ROWS(32)
+    MI_REDUCE_ROWS(64)
+    default:
+      return MI_EINVAL;
+  }
+#undef MI_REDUCE_ROWS
+  return mi::check_launch();
+}
+
+template <bool MAX>
+int launch_reduce(const int32_t* rowptr, const int32_t* col, const float* val, int64_t nnz, int32_t M, int32_t N,
+                  const float* B, int64_t ldb, float* C, int64_t ldc, int32_t* arg, int64_t ldarg, void* workspace,
+                  hipStream_t s) {
+  HubArg hub = {nullptr, 0, 0, 0};
+  const HubWs hw = hub_ws_layout(nnz, N);
+  const bool split = workspace != nullptr && nnz > kHubRow;
+  int* ws = static_cast<int*>(workspace);
+  if (split) {
+    MI_HIP_TRY(hipMemsetAsync(ws, 0, 16, s));
+    hub = {ws, (int)hw.cap_e, (int)hw.cap_s, (int)hw.cap_p};
+  }
+  int st;
+  if (N >= 4) {
+    const int G = lanes_for<4>(N);
+    st = arg ? launch_rows_w<4, MAX, true>(G, rowptr, col, val, B, C, arg, M, N, ldb, ldc, ldarg, (int)nnz, hub, s)
+             : launch_rows_w<4, MAX, false>(G, rowptr, col, val, B, C, arg, M, N, ldb, ldc, ldarg, (int)nnz, hub, s);
+  } else {
+    const int G = lanes_for<1>(N);
+    st = arg ? launch_rows_w<1, MAX, true>(G, rowptr, col, val, B, C, arg, M, N, ldb, ldc, ldarg, (int)nnz, hub, s)
+             : launch_rows_w<1, MAX, false>(G, rowptr, col, val, B, C, arg, M, N, ldb, ldc, ldarg, (int)nnz, hub, s);
+  }
+  if (st != MI_OK || !split) return st;
+  float* part_val = reinterpret_cast<float*>(static_cast<char*>(workspace) + hw.part_val_off);
+  int* part_arg = reinterpret_cast<int*>(static_cast<char*>(workspace) + hw.part_arg_off);
+  if (N >= 4)
+    hipLaunchKernelGGL((reduce_hub_kernel<4, MAX>), dim3((unsigned)hw.cap_s, (unsigned)((N + 255) / 256)), dim3(1024), 0, s,
+                       rowptr, col, val, B, C, arg, N, (long)ldb, (long)ldc, (long)ldarg, (int)nnz, ws, (int)hw.cap_e,
+                       part_val, part_arg);
+  else
+    hipLaunchKernelGGL((reduce_hub_kernel<1, MAX>), dim3((unsigned)hw.cap_s, 1u), dim3(1024), 0, s, rowptr, col, val, B, C,
+                       arg, N, (long)ldb, (long)ldc, (long)ldarg, (int)nnz, ws, (int)hw.cap_e, part_val, part_arg);
+  st = mi::check_launch();
+  if (st != MI_OK) return st;
+  hipLaunchKernelGGL((reduce_hub_combine_kernel<MAX>), dim3((unsigned)hw.cap_e, (unsigned)((N + 255) / 256)), dim3(256), 0,
+                     s, C, arg, N, (long)ldc, (long)ldarg, ws, part_val, part_arg);
+  return mi::check_launch();
+}
+
+int launch_divide(const int32_t* rowptr, int32_t M, int32_t N, const float* in, int64_t ldin, float* out, int64_t ldout,
+                  hipStream_t s) {
+  hipLaunchKernelGGL(rows_divide_kernel, dim3((unsigned)(((int64_t)M + 3) / 4)), dim3(256), 0, s, rowptr, M, N, in,
+                     (long)ldin, out, (long)ldout);
+  return mi::check_launch();
+}
+
+bool grid_fits(int64_t rows, int lanes) { return (rows * lanes + 255) / 256 <= 0x7fffffffLL; }
+
+}  // namespace
+
+extern "C" {
+
+size_t mi_spmm_csr_reduce_workspace_bytes(int64_t nnz, int32_t N) {
+  if (nnz <= 0 || N <= 0) return 0;
+  const size_t hub = hub_ws_layout(nnz, N).bytes, sum = mi_spmm_csr_workspace_bytes(nnz, N);
+  return hub > sum ? hub : sum;
+}
+
+int mi_spmm_csr_reduce_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t nnz, int32_t M, int32_t K,
+                           int32_t N, const float* B, int64_t ldb, float* C, int64_t ldc, int32_t* arg, int64_t ldarg,
+                           int reduce, void* workspace, size_t workspace_bytes, mi_stream_t stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (reduce < MI_REDUCE_SUM || reduce > MI_REDUCE_AMIN) return MI_EINVAL;
+  const bool selects = reduce == MI_REDUCE_AMAX || reduce == MI_REDUCE_AMIN;
+  if (arg != nullptr && !selects) return MI_EINVAL;
+  if (M < 0 || K < 0 || N < 0 || nnz < 0) return MI_EINVAL;
+  if (nnz > 0x7fffffffLL) return MI_ERANGE;
+  if (M == 0 || N == 0) return MI_OK;
+  if (!rowptr || !C || (nnz > 0 && (!col || !val || !B))) return MI_EINVAL;
+  if (ldb < N || ldc < N || (arg != nullptr && ldarg < N)) return MI_EINVAL;
+  if (!selects) {
+    int st = mi_spmm_csr_ws_f32(rowptr, col, val, nnz, M, K, N, B, ldb, nullptr, C, ldc, workspace, workspace_bytes, stream);
+    if (st != MI_OK || reduce == MI_REDUCE_SUM) return st;
+    return launch_divide(rowptr, M, N, C, ldc, C, ldc, s);
+  }
+  if (workspace != nullptr && nnz > kHubRow) {
+    if (workspace_bytes < hub_ws_layout(nnz, N).bytes) return MI_ENOMEM;
+    if (!mi::aligned16(workspace)) return MI_EINVAL;
+  }
+  if (!grid_fits(M, 64)) return MI_ERANGE;
+  return reduce == MI_REDUCE_AMAX ? launch_reduce<true>(rowptr, col, val, nnz, M, N, B, ldb, C, ldc, arg, ldarg, workspace, s)
+                                  : launch_reduce<false>(rowptr, col, val, nnz, M, N, B, ldb, C, ldc, arg, ldarg, workspace, s);
+}
+
+int mi_spmm_rows_divide_f32(const int32_t* rowptr, int32_t M, int32_t N, const float* in, int64_t ldin, float* out,
+                            int64_t ldout, mi_stream_t stream) {
+  if (M < 0 || N < 0) return MI_EINVAL;
+  if (M == 0 || N == 0) return MI_OK;
+  if (!rowptr || !in || !out || ldin < N || ldout < N) return MI_EINVAL;
+  return launch_divide(rowptr, M, N, in, ldin, out, ldout, static_cast<hipStream_t>(stream));
+}
+
+int mi_spmm_reduce_grad_val_f32(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M, int32_t K, int32_t N,
+                                const float* B, int64_t ldb, const float* G, int64_t ldg, const int32_t* arg,
+                                int64_t ldarg, float* grad_val, mi_stream_t stream) {
+  if (M < 0 || K < 0 || N < 0 || nnz < 0) return MI_EINVAL;
+  if (nnz > 0x7fffffffLL) return MI_ERANGE;
+  if (M == 0 || nnz == 0) return MI_OK;
+  if (!rowptr || !col || !grad_val || (N > 0 && (!B || !G || !arg))) return MI_EINVAL;
+  if (ldb < N || ldg < N || ldarg < N) return MI_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)(((int64_t)M + 3) / 4));
+  const int T = N <= 64 ? 1 : N <= 128 ? 2 : N <= 256 ? 4 : N <= 512 ? 8 : N <= 1024 ? 16 : 0;
+#define MI_GRAD_VAL(TT)                                                                                                  \
+  case TT:                                                                                                               \
+    hipLaunchKernelGGL(reduce_grad_val_kernel<TT>, grid, dim3(256), 0, s, rowptr, col, M, N, B, (long)ldb, G, (long)ldg, \
+                       arg, (long)ldarg, grad_val);                                                                      \
+    break;
+  switch (T) {
+    MI_GRAD_VAL(0)
+    MI_GRAD_VAL(1)
+    MI_GRAD_VAL(2)
+    MI_GRAD_VAL(4)
+    MI_GRAD_VAL(8)
+    MI_GRAD_VAL(16)
+  }
+#undef MI_GRAD_VAL
+  return mi::check_launch();
+}
+
+int mi_spmm_reduce_grad_b_f32(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm, const float* val,
+                              int64_t nnz, int32_t M, int32_t K, int32_t N, const float* G, int64_t ldg,
+                              const int32_t* arg, int64_t ldarg, float* grad_b, int64_t ldgb, mi_stream_t stream) {
+  if (M < 0 || K < 0 || N < 0 || nnz < 0) return MI_EINVAL;
+  if (nnz > 0x7fffffffLL) return MI_ERANGE;
+  if (K == 0 || N == 0) return MI_OK;
+  if (!t_rowptr || !grad_b || (nnz > 0 && (!t_col || !perm || !val || !G || !arg))) return MI_EINVAL;
+  if (ldg < N || ldarg < N || ldgb < N) return MI_EINVAL;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (N >= 4) {
+    const int Gl = lanes_for<4>(N);
+    const dim3 grid((unsigned)(((int64_t)K * Gl + 255) / 256));
+#define MI_GRAD_B(GG)                                                                                                   \
+  case GG:                                                                                                              \
+    hipLaunchKernelGGL((reduce_grad_b_kernel<GG, 4>), grid, dim3(256), 0, s, t_rowptr, t_col, perm, val, K, N, G,       \
+                       (long)ldg, arg, (long)ldarg, grad_b, (long)ldgb);                                                \
+    break;
+    switch (Gl) {
+      MI_GRAD_B(1)
+      MI_GRAD_B(2)
+      MI_GRAD_B(4)
+      MI_GRAD_B(8)
+      MI_GRAD_B(16)
+      MI_GRAD_B(32)
+      MI_GRAD_B(64)
+    }
+#undef MI_GRAD_B
+  } else {
+    const dim3 grid((unsigned)(((int64_t)K * 4 + 255) / 256));
+    hipLaunchKernelGGL((reduce_grad_b_kernel<4, 1>), grid, dim3(256), 0, s, t_rowptr, t_col, perm, val, K, N, G, (long)ldg,
+                       arg, (long)ldarg, grad_b, (long)ldgb);
+  }
+  return mi::check_launch();
+}
+
+}  // extern "C"

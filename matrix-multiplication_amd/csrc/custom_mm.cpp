@@ -42,6 +42,7 @@ namespace {
 #include "custom_mm_reference.inc"
 #include "custom_mm_extras.inc"
 #include "custom_mm_inspect.inc"
+#include "custom_mm_reduce.inc"
 
 // ---- handle init / destroy (reference custom_mm.cpp:361-391) ----------------
 // There are no vendor handles on this path; init checks that the C-ABI library
@@ -153,6 +154,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ipc_close", &ipc_close, "drop one open of a peer handle");
   m.def("ipc_open_count", []() { return mi_ipc_open_count(); }, "peer mappings not yet closed in this process");
   m.def("long_row_threshold", &long_row_threshold, "rows with more non-zeros are 'long' (split rule)");
+  m.def("naive_spmm_reduce", &naive_spmm_reduce, py::arg("A_values"), py::arg("A_columns"), py::arg("A_offsets"),
+        py::arg("nnzA"), py::arg("A_rows"), py::arg("A_cols"), py::arg("B"), py::arg("C"), py::arg("reduce"),
+        py::arg("arg") = py::none(),
+        "CSR x dense with reduce = sum / mean / amax / amin (torch.sparse.mm); amax / amin write the selected entries to arg");
+  m.def("spmm_rows_divide", &spmm_rows_divide, "out = in / (entries of the row), per row (mean and its gradient)");
+  m.def("spmm_reduce_grad_val", &spmm_reduce_grad_val, "amax / amin: gradient of A's stored values from the forward's arg");
+  m.def("spmm_reduce_grad_b", &spmm_reduce_grad_b, "amax / amin: gradient of B on A^T's pattern and permutation");
   // Handles and automatic schedules own HIP streams and events: they are released while the interpreter — and with it the HIP
   // runtime — is still up (left to the destructors of the statics they segfaulted at process exit after the runtime had gone:
   // a program that never called cusparse_clean / auto_schedule_clear ended with exit code 139 AFTER its last line of output).

@@ -1,0 +1,156 @@
+// custom_mm — CSR × dense with reduce = sum / mean / amax / amin (torch.sparse.mm's `reduce`) and the gradients of amax / amin
+// Part of the `custom_mm` extension: included by custom_mm.cpp inside its anonymous namespace (one translation unit; the
+// split is for readers).  Not compiled on its own.  Contract: include/mi_spmm.h, mi_spmm_csr_reduce_f32.
+
+int reduce_code(const std::string& reduce, const char* what) {
+  if (reduce == "sum") return MI_REDUCE_SUM;
+  if (reduce == "mean") return MI_REDUCE_MEAN;
+  if (reduce == "amax") return MI_REDUCE_AMAX;
+  if (reduce == "amin") return MI_REDUCE_AMIN;
+  throw std::invalid_argument(std::string(what) + ": reduce must be one of sum, mean, amax, amin; got '" + reduce + "'");
+}
+
+// C = A ⊙_reduce B.  sum: exactly naive_spmm; mean: naive_spmm, then each row divided by its count in place; amax / amin:
+// the selection kernels, the selected entry indices into `arg` (int32 [A_rows, N]) when it is given.
+torch::Tensor naive_spmm_reduce(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor A_offsets, int64_t nnzA,
+                                int64_t A_rows, int64_t A_cols, torch::Tensor B, torch::Tensor C, const std::string& reduce,
+                                c10::optional<torch::Tensor> arg) {
+  const char* what = "naive_spmm_reduce";
+  const int code = reduce_code(reduce, what);
+  const bool selects = code == MI_REDUCE_AMAX || code == MI_REDUCE_AMIN;
+  TORCH_CHECK(!(arg.has_value() && arg->defined()) || selects, what, ": arg is only defined for amax / amin");
+  TORCH_CHECK(nnzA < (int64_t)1 << 31, what, ": nnzA does not fit int32 indices");
+  if (!selects) {
+    spmm_impl(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, what, nullptr, MI_LONG_ROWS_AUTO, nullptr,
+              MI_SPMM_AUTO, true);
+    if (code == MI_REDUCE_MEAN && C.numel() > 0) {
+      c10::hip::HIPGuard guard(C.device().index());
+      check_status(mi_spmm_rows_divide_f32(A_offsets.data_ptr<int32_t>(), (int32_t)A_rows, (int32_t)C.size(1),
+                                           C.data_ptr<float>(), C.size(1), C.data_ptr<float>(), C.size(1), stream_of(C)),
+                   what);
+    }
+    return C;
+  }
+  check_device_f32(A_values, "A_values");
+  check_device_i32(A_columns, "A_columns");
+  check_device_i32(A_offsets, "A_offsets");
+  check_device_f32(B, "B");
+  check_device_f32(C, "C");
+  check_same_device(A_values, C, what);
+  check_same_device(A_columns, C, what);
+  check_same_device(A_offsets, C, what);
+  check_same_device(B, C, what);
+  TORCH_CHECK(A_rows >= 0 && A_cols >= 0 && nnzA >= 0, what, ": negative size");
+  TORCH_CHECK(A_rows <= INT32_MAX && A_cols <= INT32_MAX, what, ": dimension too large");
+  TORCH_CHECK(A_values.is_contiguous() && A_columns.is_contiguous() && A_offsets.is_contiguous(), what,
+              ": CSR arrays must be contiguous");
+  TORCH_CHECK(A_values.numel() >= nnzA && A_columns.numel() >= nnzA, what, ": nnzA exceeds the CSR arrays");
+  TORCH_CHECK(A_offsets.numel() == A_rows + 1, what, ": A_offsets must have A_rows + 1 entries");
+  TORCH_CHECK(B.dim() == 2 && C.dim() == 2 && B.size(0) == A_cols && C.size(0) == A_rows && C.size(1) == B.size(1), what,
+              ": B must be [A_cols, N] and C [A_rows, N]");
+  TORCH_CHECK(C.is_contiguous(), what, ": C must be contiguous");
+  const int64_t N = B.size(1);
+  TORCH_CHECK(N <= INT32_MAX, what, ": N too large");
+  int32_t* arg_ptr = nullptr;
+  if (arg.has_value() && arg->defined()) {
+    check_device_i32(*arg, "arg");
+    check_same_device(*arg, C, what);
+    TORCH_CHECK(arg->dim() == 2 && arg->size(0) == A_rows && arg->size(1) == N && arg->is_contiguous(), what,
+                ": arg must be a contiguous int32 [A_rows, N]");
+    arg_ptr = arg->data_ptr<int32_t>();
+  }
+  torch::Tensor Bc = B.contiguous();
+  c10::hip::HIPGuard guard(C.device().index());
+  // the hub-row list and partial rows (a fresh block of the caching allocator: capturable; the entry zeroes its header)
+  torch::Tensor ws;
+  if (nnzA > mi_spmm_long_row_threshold() && N > 0)
+    ws = torch::empty({(int64_t)mi_spmm_csr_reduce_workspace_bytes(nnzA, (int32_t)N)}, torch::dtype(torch::kUInt8).device(C.device()));
+  check_status(mi_spmm_csr_reduce_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(), A_values.data_ptr<float>(),
+                                      nnzA, (int32_t)A_rows, (int32_t)A_cols, (int32_t)N, Bc.data_ptr<float>(),
+                                      std::max<int64_t>(N, 1), C.data_ptr<float>(), std::max<int64_t>(N, 1), arg_ptr,
+                                      std::max<int64_t>(N, 1), code, ws.defined() ? ws.data_ptr() : nullptr,
+                                      ws.defined() ? (size_t)ws.numel() : 0, stream_of(C)),
+               what);
+  return C;
+}
+
+// out = in / count(row) per row (rows without entries copied); out may be in.
+torch::Tensor spmm_rows_divide(torch::Tensor A_offsets, int64_t A_rows, torch::Tensor in, torch::Tensor out) {
+  const char* what = "spmm_rows_divide";
+  check_device_i32(A_offsets, "A_offsets");
+  check_device_f32(in, "in");
+  check_device_f32(out, "out");
+  check_same_device(A_offsets, out, what);
+  check_same_device(in, out, what);
+  TORCH_CHECK(A_offsets.is_contiguous() && A_offsets.numel() == A_rows + 1, what, ": A_offsets must have A_rows + 1 entries");
+  TORCH_CHECK(in.dim() == 2 && in.size(0) == A_rows && out.sizes() == in.sizes(), what, ": in and out must be [A_rows, N]");
+  TORCH_CHECK(in.is_contiguous() && out.is_contiguous(), what, ": in and out must be contiguous");
+  c10::hip::HIPGuard guard(out.device().index());
+  const int64_t N = in.size(1);
+  check_status(mi_spmm_rows_divide_f32(A_offsets.data_ptr<int32_t>(), (int32_t)A_rows, (int32_t)N, in.data_ptr<float>(),
+                                       std::max<int64_t>(N, 1), out.data_ptr<float>(), std::max<int64_t>(N, 1), stream_of(out)),
+               what);
+  return out;
+}
+
+// grad of the stored values for amax / amin: [nnzA], entry e gets Σ_j [arg[i, j] == e] G[i, j] B[col[e], j]
+torch::Tensor spmm_reduce_grad_val(torch::Tensor A_columns, torch::Tensor A_offsets, int64_t nnzA, int64_t A_rows,
+                                   int64_t A_cols, torch::Tensor B, torch::Tensor G, torch::Tensor arg) {
+  const char* what = "spmm_reduce_grad_val";
+  check_device_i32(A_columns, "A_columns");
+  check_device_i32(A_offsets, "A_offsets");
+  check_device_f32(B, "B");
+  check_device_f32(G, "G");
+  check_device_i32(arg, "arg");
+  check_same_device(A_columns, G, what);
+  check_same_device(A_offsets, G, what);
+  check_same_device(B, G, what);
+  check_same_device(arg, G, what);
+  TORCH_CHECK(A_columns.is_contiguous() && A_offsets.is_contiguous() && A_offsets.numel() == A_rows + 1 &&
+                  A_columns.numel() >= nnzA,
+              what, ": CSR array sizes do not match");
+  TORCH_CHECK(G.dim() == 2 && B.dim() == 2 && G.size(0) == A_rows && B.size(0) == A_cols && G.size(1) == B.size(1) &&
+                  arg.sizes() == G.sizes() && arg.is_contiguous(),
+              what, ": G and arg must be [A_rows, N] and B [A_cols, N]");
+  torch::Tensor Gc = G.contiguous(), Bc = B.contiguous();
+  const int64_t N = Bc.size(1);
+  c10::hip::HIPGuard guard(G.device().index());
+  torch::Tensor out = torch::empty({nnzA}, Gc.options());
+  check_status(mi_spmm_reduce_grad_val_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(), nnzA, (int32_t)A_rows,
+                                           (int32_t)A_cols, (int32_t)N, Bc.data_ptr<float>(), std::max<int64_t>(N, 1),
+                                           Gc.data_ptr<float>(), std::max<int64_t>(N, 1), arg.data_ptr<int32_t>(),
+                                           std::max<int64_t>(N, 1), out.data_ptr<float>(), stream_of(Gc)),
+               what);
+  return out;
+}
+
+// grad of B for amax / amin: [A_cols, N] over the rows of Aᵀ (t_offsets [A_cols+1], t_columns = rows of A, perm = entry of
+// Aᵀ → index in A)
+torch::Tensor spmm_reduce_grad_b(torch::Tensor t_offsets, torch::Tensor t_columns, torch::Tensor perm, torch::Tensor A_values,
+                                 int64_t nnzA, int64_t A_rows, int64_t A_cols, torch::Tensor G, torch::Tensor arg) {
+  const char* what = "spmm_reduce_grad_b";
+  check_device_i32(t_offsets, "t_offsets");
+  check_device_i32(t_columns, "t_columns");
+  check_device_i32(perm, "perm");
+  check_device_f32(A_values, "A_values");
+  check_device_f32(G, "G");
+  check_device_i32(arg, "arg");
+  for (const torch::Tensor* t : {&t_offsets, &t_columns, &perm, &A_values, &arg}) check_same_device(*t, G, what);
+  TORCH_CHECK(t_offsets.is_contiguous() && t_columns.is_contiguous() && perm.is_contiguous() && A_values.is_contiguous() &&
+                  t_offsets.numel() == A_cols + 1 && t_columns.numel() >= nnzA && perm.numel() >= nnzA &&
+                  A_values.numel() >= nnzA,
+              what, ": CSR array sizes do not match");
+  TORCH_CHECK(G.dim() == 2 && G.size(0) == A_rows && arg.sizes() == G.sizes() && arg.is_contiguous(), what,
+              ": G and arg must be [A_rows, N]");
+  torch::Tensor Gc = G.contiguous();
+  const int64_t N = Gc.size(1);
+  c10::hip::HIPGuard guard(G.device().index());
+  torch::Tensor out = torch::empty({A_cols, N}, Gc.options());
+  check_status(mi_spmm_reduce_grad_b_f32(t_offsets.data_ptr<int32_t>(), t_columns.data_ptr<int32_t>(), perm.data_ptr<int32_t>(),
+                                         A_values.data_ptr<float>(), nnzA, (int32_t)A_rows, (int32_t)A_cols, (int32_t)N,
+                                         Gc.data_ptr<float>(), std::max<int64_t>(N, 1), arg.data_ptr<int32_t>(),
+                                         std::max<int64_t>(N, 1), out.data_ptr<float>(), std::max<int64_t>(N, 1),
+                                         stream_of(Gc)),
+               what);
+  return out;
+}

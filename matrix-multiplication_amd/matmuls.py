@@ -967,3 +967,95 @@ class naiveSpMM(InplaceFunction):
     @staticmethod
     def backward(ctx, grad_output):
         return _sparse_backward(ctx, grad_output)
+
+
+# --------------------------------------------------------------------------- #
+# reductions other than sum: torch.sparse.mm(mat1, mat2, reduce=...)
+# --------------------------------------------------------------------------- #
+
+REDUCTIONS = ('sum', 'mean', 'amax', 'amin')
+
+
+def _check_reduce_operands(m1, m2, reduce):
+    '''The inputs sparse_mm_reduce takes: a 2-d CSR mat1 and a 2-d dense fp32 mat2, both on one device (no CPU path).'''
+    if reduce not in REDUCTIONS:
+        raise ValueError(f'sparse_mm_reduce: reduce must be one of {", ".join(REDUCTIONS)}; got {reduce!r}')
+    if not isinstance(m1, torch.Tensor) or m1.layout != torch.sparse_csr or m1.dim() != 2:
+        raise ValueError('sparse_mm_reduce: mat1 must be a 2-d (unbatched) CSR tensor')
+    if not isinstance(m2, torch.Tensor) or m2.layout != torch.strided or m2.dim() != 2 or m2.dtype != torch.float32:
+        raise ValueError('sparse_mm_reduce: mat2 must be a 2-d dense float32 tensor')
+    if not (m1.is_cuda and m2.is_cuda) or m1.device != m2.device:
+        raise RuntimeError(f'sparse_mm_reduce: mat1 and mat2 must be device (HIP) tensors on one device, got {m1.device} '
+                           f'and {m2.device}; custom_mm has no CPU path')
+    if m1.shape[1] != m2.shape[0]:
+        raise ValueError(f'sparse_mm_reduce: shapes {tuple(m1.shape)} and {tuple(m2.shape)} cannot be multiplied')
+
+
+def _transposed_perm(m1):
+    '''(t_offsets, t_columns, perm) of m1ᵀ: the pattern _csr_cached keeps on the tensor, with the int32 permutation that
+    carries an entry of m1ᵀ to its index in m1.'''
+    (values, columns, offsets, nnz, rows, cols), (_, t_col, t_off) = _csr_cached(m1)
+    hit = getattr(m1, '_mi_csr_cache', None)
+    if hit is not None and hit[2] is t_col:
+        return t_off, t_col, hit[1]
+    iota = torch.arange(nnz, device=values.device, dtype=torch.int32).view(torch.float32)
+    t_perm, t_col, t_off = custom_mm.csr_transpose(iota, columns, offsets, nnz, rows, cols)
+    return t_off, t_col, t_perm.view(torch.int32)
+
+
+class naiveSpMMReduce(InplaceFunction):
+    '''C[i, j] = reduce over the entries e of row i of val[e]·m2[col[e], j] — torch.sparse.mm(m1, m2, reduce) for a 2-d
+    device CSR m1 (torch implements `reduce` for CSR on the CPU only).  sum: naiveSpMM's product and backward; mean: that
+    product divided by the row's entry count (the gradient divided likewise, then sum's backward); amax / amin: the
+    selection kernels, which record the selected entry per output element only when a gradient is needed, and route
+    each gradient element through it.  grad of m1 is a CSR tensor on m1's pattern.'''
+
+    @staticmethod
+    def forward(ctx, m1, m2, reduce):
+        _check_reduce_operands(m1, m2, reduce)
+        ctx.reduce = reduce
+        if reduce == 'sum':
+            ctx.save_for_backward(m1, m2)
+            return naive_matmul(m1, m2)
+        m2 = m2.contiguous()
+        values, columns, offsets, nnz, rows, cols = _csr_props_cached(m1)
+        out = torch.empty((rows, m2.shape[1]), device=m2.device, dtype=torch.float32)
+        arg = None
+        if reduce in ('amax', 'amin') and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            arg = torch.empty((rows, m2.shape[1]), device=m2.device, dtype=torch.int32)
+        custom_mm.naive_spmm_reduce(values, columns, offsets, nnz, rows, cols, m2, out, reduce, arg)
+        if arg is None:
+            ctx.save_for_backward(m1, m2)
+        else:
+            ctx.save_for_backward(m1, m2, arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        g = grad_output.contiguous()
+        if ctx.reduce in ('sum', 'mean'):
+            if ctx.reduce == 'mean':
+                m1 = ctx.saved_tensors[0]
+                offsets, rows = _csr_props_cached(m1)[2], m1.shape[0]
+                g = custom_mm.spmm_rows_divide(offsets, rows, g, torch.empty_like(g))
+            return (*_sparse_backward(ctx, g), None)
+        m1, m2, arg = ctx.saved_tensors
+        values, columns, offsets, nnz, rows, cols = _csr_props_cached(m1)
+        grad_m1 = grad_m2 = None
+        if ctx.needs_input_grad[0]:
+            gvals = custom_mm.spmm_reduce_grad_val(columns, offsets, nnz, rows, cols, m2, g, arg)
+            grad_m1 = torch.sparse_csr_tensor(torch.Tensor.crow_indices(m1), torch.Tensor.col_indices(m1),
+                                              gvals.to(m1.device), size=m1.shape)
+        if ctx.needs_input_grad[1]:
+            t_off, t_col, perm = _transposed_perm(m1)
+            grad_m2 = custom_mm.spmm_reduce_grad_b(t_off, t_col, perm, values, nnz, rows, cols, g, arg)
+        return grad_m1, grad_m2, None
+
+
+def sparse_mm_reduce(mat1: torch.Tensor, mat2: torch.Tensor, reduce: str = 'sum') -> torch.Tensor:
+    '''torch.sparse.mm(mat1, mat2, reduce) on the device: mat1 a 2-d CSR tensor (int32 or int64 indices), mat2 a 2-d
+    dense float32 tensor; reduce one of "sum", "mean", "amax", "amin".  Differentiable in both operands.'''
+    _check_reduce_operands(mat1, mat2, reduce)
+    if reduce == 'sum':
+        return naiveSpMM.apply(mat1, mat2)
+    return naiveSpMMReduce.apply(mat1, mat2, reduce)
