@@ -9,7 +9,8 @@
  *
  * Each entry cites the reference interface (relative to the reference repo
  * smoorjani/matrix-multiplication) it replaces.  All device pointers must be
- * valid for the sizes stated; index arrays are int32, values are float32.
+ * valid for the sizes stated; index arrays are int32, values are float32 (bfloat16 / float16 in the
+ * low-precision entries, which say so).
  */
 #ifndef MI_SPMM_H_
 #define MI_SPMM_H_
@@ -547,6 +548,46 @@ int mi_sddmm_csr_batched_f32(const int32_t* rowptr, const int32_t* col, int64_t 
  * permutation mi_csr_transpose_* produced for the values 0, 1, 2, … (matmuls' backward; replaces the reference-side
  * `index_select`).  perm entries must lie in [0, length of src). */
 int mi_gather_f32(const float* src, const int32_t* perm, int64_t n, float* dst, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * Low precision: CSR × dense in bfloat16 / float16 (values, B and C all of the entry's type T; stored as uint16_t bit
+ * patterns), every sum in fp32.  With up() the exact widening to fp32 and rne_T the round-to-nearest-even narrowing
+ * that torch's Tensor.to(T) does, the product writes
+ *     C = rne_T(C32),   C32 = what mi_spmm_csr_ex_f32 writes for up(val), up(B) with MI_LONG_ROWS_SPLIT:
+ * the plain CSR-order fmaf chain for rows of up to mi_spmm_long_row_threshold() entries, the split order of the K1
+ * section for longer rows, the xor-butterfly order for N < 4 — and ONE rounding per element, at the store.  NaN stays
+ * NaN (its payload is not part of the contract); every other value, ±0, ±inf, overflow (fp16 above 65504) and results
+ * in T's subnormal range included, is exactly rne_T of the fp32 result.
+ *   long_rows: MI_LONG_ROWS_AUTO, _AUTO_ZEROED and _SPLIT all mean SPLIT here, whatever the fp32 plan would be (its SLAB
+ *   and NARROW plans do not split; this path has no plan-dependent exception).  _NONE: every row keeps the plain chain
+ *   (one launch; the same bits when no row exceeds the threshold).  _PREPARED → MI_EINVAL (no inspector handles here).
+ *   workspace: mi_spmm_csr_workspace_bytes(nnz, N) bytes, 16-byte aligned, required when nnz exceeds the threshold,
+ *   N ≥ 4 and the mode splits (else MI_EINVAL; too small: MI_ENOMEM).  The partial rows of split rows are fp32.
+ *   _AUTO_ZEROED keeps the zero-header contract of the fp32 entries, so one workspace per stream serves both.
+ *   B and C: any 2-byte-aligned pointer, any ldb ≥ N and ldc ≥ N (odd values and column-offset views included).
+ * Checked before any HIP call: negative sizes, ldb < N, ldc < N, the mode, null pointers (col / val / B may be NULL
+ * only when nnz == 0) → MI_EINVAL; M == 0 or N == 0 → MI_OK.  No host read-back, no float atomics: graph-capturable.
+ * A product is the main kernel plus, when it may split, one follow-up launch that sums the listed rows (or finds none).
+ * No counterpart in the reference (float32 only: src/naive_sparse_mm.cu:24-136). */
+int mi_spmm_csr_ex_bf16(const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz,
+                        int32_t M, int32_t K, int32_t N, const uint16_t* B, int64_t ldb,
+                        uint16_t* C, int64_t ldc, int long_rows, void* workspace, size_t workspace_bytes,
+                        mi_stream_t stream);
+int mi_spmm_csr_ex_f16(const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz,
+                       int32_t M, int32_t K, int32_t N, const uint16_t* B, int64_t ldb,
+                       uint16_t* C, int64_t ldc, int long_rows, void* workspace, size_t workspace_bytes,
+                       mi_stream_t stream);
+/* SDDMM in low precision: out_val[p] = rne_T(mi_sddmm_csr_f32 on up(dC), up(B)) — the same fp32 order (lane l of 64
+ * chains columns 256t + 4l + c, then the xor tree), one rounding.  Same argument rules as mi_sddmm_csr_f32; dC and B
+ * 2-byte aligned with any lddc, ldb ≥ N. */
+int mi_sddmm_csr_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M, int32_t K, int32_t N,
+                      const uint16_t* dC, int64_t lddc, const uint16_t* B, int64_t ldb, uint16_t* out_val,
+                      mi_stream_t stream);
+int mi_sddmm_csr_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M, int32_t K, int32_t N,
+                     const uint16_t* dC, int64_t lddc, const uint16_t* B, int64_t ldb, uint16_t* out_val,
+                     mi_stream_t stream);
+/* mi_gather_f32 for 2-byte values (bf16 / fp16 bit patterns moved untouched): dst[p] = src[perm[p]], p < n. */
+int mi_gather_b16(const uint16_t* src, const int32_t* perm, int64_t n, uint16_t* dst, mi_stream_t stream);
 
 /* Column sums dst[j] = Σ_r src[r, j] (src rows×n, leading dimension ld): the bias gradient of
  * the FC layers (autograd of `output += self.bias`, reference benchmarks/cublas_fc_layer.py:44-45).

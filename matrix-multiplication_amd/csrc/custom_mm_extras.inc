@@ -496,6 +496,7 @@ bool sddmm_batched(torch::Tensor A_columns, torch::Tensor A_offsets, int64_t nnz
 // out[p] = <dC[row(p), :], B[col[p], :]> on A's pattern: d(A·B)/d(A values).
 torch::Tensor sddmm(torch::Tensor A_columns, torch::Tensor A_offsets, int64_t nnzA, int64_t A_rows,
                     int64_t A_cols, torch::Tensor dC, torch::Tensor B) {
+  if (lowp_operands({&dC, &B})) return sddmm_lowp(A_columns, A_offsets, nnzA, A_rows, A_cols, dC, B);
   const char* what = "sddmm";
   check_device_i32(A_columns, "A_columns");
   check_device_i32(A_offsets, "A_offsets");

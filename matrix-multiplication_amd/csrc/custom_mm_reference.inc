@@ -344,11 +344,15 @@ torch::Tensor spmm_impl(const torch::Tensor& A_values, const torch::Tensor& A_co
 
 torch::Tensor naive_spmm(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor A_offsets,
                          int nnzA, int A_rows, int A_cols, torch::Tensor B, torch::Tensor C) {
+  if (lowp_operands({&A_values, &B, &C}))
+    return spmm_lowp(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "naive_spmm", MI_LONG_ROWS_AUTO);
   return spmm_impl(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "naive_spmm", nullptr, MI_LONG_ROWS_AUTO, nullptr, MI_SPMM_AUTO, true);
 }
 
 torch::Tensor cusparse_mmul(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor A_offsets,
                             int nnzA, int A_rows, int A_cols, torch::Tensor B, torch::Tensor C) {
+  if (lowp_operands({&A_values, &B, &C}))
+    return spmm_lowp(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "cusparse_mmul", MI_LONG_ROWS_AUTO);
   return spmm_impl(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "cusparse_mmul", nullptr, MI_LONG_ROWS_AUTO, nullptr, MI_SPMM_AUTO, true);
 }
 
@@ -375,6 +379,8 @@ torch::Tensor naive_spmm_ex(torch::Tensor A_values, torch::Tensor A_columns, tor
                             int long_rows) {
   if (long_rows < MI_LONG_ROWS_AUTO || long_rows > MI_LONG_ROWS_SPLIT)
     throw std::invalid_argument("naive_spmm_ex: long_rows must be -1, 0 or 1");
+  if (lowp_operands({&A_values, &B, &C}))  // (-1 and 1 are the same rule there: long rows split)
+    return spmm_lowp(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "naive_spmm_ex", long_rows);
   return spmm_impl(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "naive_spmm_ex", nullptr, long_rows);
 }
 
@@ -459,6 +465,7 @@ torch::Tensor column_sums(torch::Tensor src) {
 // values[perm] as a new tensor (perm int32, values f32, both contiguous and on one device); what torch's index_select
 // does, without its index conversion (bound by one line request per value either way: tools/probes/gather_bench.py)
 torch::Tensor gather_perm(torch::Tensor values, torch::Tensor perm) {
+  if (is_lowp(values)) return gather_perm_lowp(values, perm);  // 2-byte values (bf16 / fp16)
   check_device_f32(values, "values");
   check_device_i32(perm, "perm");
   check_same_device(values, perm, "gather_perm");

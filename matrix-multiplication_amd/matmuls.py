@@ -378,7 +378,7 @@ def _csr_product(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, mm_op, defau
     props = _csr_of(a, est)
     # an ESTIMATED count may only meet rule 0 (no long-row workspace is sized from it: include/mi_spmm.h, K1 section)
     assert est is None or one_launch
-    if a.is_sparse_csr and mm_op is default_op and b.dim() == 2:
+    if a.is_sparse_csr and mm_op is default_op and b.dim() == 2 and a.dtype not in _LOWP:
         # a CSR tensor that has been multiplied before (a static sparse operand: weights, an adjacency matrix): its row schedule
         sched = _row_schedule(a, '_mi_csr_sched', _csr_key(a)[1:3] + _csr_key(a)[4:], props[2], props[3], props[4], b.shape[-1], props[1], props[5])
         if sched is not None:
@@ -668,6 +668,8 @@ def _spmm_dispatch(a: torch.Tensor, b: torch.Tensor, mm_op, default_op, dense_ro
     c_rows, c_cols = a_shape[-2], b_shape[-1]
     if a_shape[-1] != b_shape[-2]:
         raise RuntimeError(f'sparse matmul: inner dimensions differ ({a_shape[-1]} vs {b_shape[-2]})')
+    if a.dtype in _LOWP or b.dtype in _LOWP:
+        return _lowp_product(a, b, mm_op, default_op)
     dev = b.device if b.is_cuda else a.device
 
     fused = mm_op is default_op and not a.is_sparse_csr  # dense A + stock kernel: skip zeros in the kernel
@@ -735,6 +737,39 @@ def _spmm_dispatch(a: torch.Tensor, b: torch.Tensor, mm_op, default_op, dense_ro
         for i in range(nb):
             mm_op(*_csr_of(_a[i]), _b[i], c[i])
     return c.view(batch + (c_rows, c_cols))
+
+
+# bfloat16 / float16: a 2-d CSR mat1 and a dense mat2 of the same dtype, summed in fp32 and rounded once per output element
+# (include/mi_spmm.h, low-precision section: the fp32 product of the widened operands with long rows split, narrowed)
+_LOWP = (torch.bfloat16, torch.float16)
+
+
+def _lowp_product(a: torch.Tensor, b: torch.Tensor, mm_op, default_op) -> torch.Tensor:
+    '''a @ b for a 2-d CSR a with bf16 / fp16 values and a dense b ([K, N] or [..., K, N]) of the same dtype; the output
+    has that dtype.  No row schedules, no dense route: the stock kernels' low-precision forms through _csr_product (its
+    one-launch shortcut included: rule 0 and the split rule give the same bits where no row can be long).  Batched CSR
+    and a dense mat1 are not covered in low precision, nor are mixed dtypes.'''
+    if b.dtype != a.dtype:
+        raise RuntimeError(f'sparse matmul: mat1 is {a.dtype} but mat2 is {b.dtype}: both operands must have one dtype '
+                           f'(float32, bfloat16 or float16)')
+    if not a.is_sparse_csr:
+        raise RuntimeError(f'sparse matmul: a dense {a.dtype} mat1 is not supported (in bfloat16 / float16 mat1 must be a '
+                           f'2-d CSR tensor; a dense mat1 is sparsified on the fly in float32 only)')
+    if a.dim() != 2:
+        raise RuntimeError(f'sparse matmul: a batched {a.dtype} CSR mat1 ({a.dim()}-d) is not supported (float32 only)')
+    if b.layout != torch.strided:
+        raise RuntimeError(f'sparse matmul: mat2 must be a dense {b.dtype} tensor, got layout {b.layout}')
+    rows, cols, n = a.shape[-2], a.shape[-1], b.shape[-1]
+    dev = b.device if b.is_cuda else a.device
+    if b.dim() == 2:
+        c = torch.empty((rows, n), device=dev, dtype=b.dtype)
+        return _csr_product(a, b, c, mm_op, default_op, a)
+    # one CSR × a batch of B: C[i] = A·B[i]  ==  A · [K, batch·N]
+    batch = tuple(b.shape[:-2])
+    _b = b.reshape((-1,) + tuple(b.shape[-2:])).permute(1, 0, 2).reshape(cols, -1)
+    c = torch.empty((rows, _b.shape[1]), device=dev, dtype=b.dtype)
+    c = _csr_product(a, _b, c, mm_op, default_op, a)
+    return c.view(rows, -1, n).permute(1, 0, 2).reshape(batch + (rows, n))
 
 
 def sparse_matmul(a: torch.Tensor,
@@ -916,10 +951,10 @@ def _sparse_backward(ctx, grad_output):
             grad_m1 = torch.sparse_csr_tensor(torch.Tensor.crow_indices(m1), torch.Tensor.col_indices(m1),
                                               gvals.to(m1.device), size=m1.shape)
         if ctx.needs_input_grad[1]:
-            gb = torch.empty((cols, g.shape[-1]), device=g.device, dtype=torch.float32)
+            gb = torch.empty((cols, g.shape[-1]), device=g.device, dtype=values.dtype)
             # m1ᵀ's pattern is cached on m1: so is its row schedule (the transpose of a skewed matrix is as skewed)
             sched = _row_schedule(m1, '_mi_csr_sched_t', _csr_key(m1)[1:3] + _csr_key(m1)[4:], t_off, nnz, cols, g.shape[-1], t_col, rows) \
-                if g.is_contiguous() else None
+                if g.is_contiguous() and values.dtype not in _LOWP else None
             if sched is not None:
                 gb = custom_mm.naive_spmm_scheduled(sched, t_val, t_col, t_off, nnz, cols, rows, g, gb)
             else:
