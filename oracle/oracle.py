@@ -12,7 +12,7 @@ from pathlib import Path
 import numpy as np
 
 __all__ = ["build", "lib", "gemm_split_count", "spmm_csr", "spmm_csr_omp", "spmm_csr_long", "spmm_csr_chain", "spmm_csr_batched", "spmm_csr_colmajor", "gemm",
-           "coo_to_csr", "dense_to_csr", "csr_transpose", "sddmm", "make_csr"]
+           "coo_to_csr", "dense_to_csr", "csr_transpose", "sddmm", "reduce_grad_val", "reduce_grad_b", "make_csr"]
 
 _DIR = Path(__file__).resolve().parent
 _SO = _DIR / "_build" / "liboracle.so"
@@ -58,6 +58,10 @@ def lib():
         L.oracle_csr_transpose.restype = None
         L.oracle_sddmm_csr_f32.argtypes = [_i32, _i32, _c32, _c32, _f32, _c64, _f32, _c64, _f32]
         L.oracle_sddmm_csr_f32.restype = None
+        L.oracle_reduce_grad_val_f32.argtypes = [_i32, _i32, _c32, _c32, _f32, _c64, _f32, _c64, _i32, _c64, _f32]
+        L.oracle_reduce_grad_val_f32.restype = None
+        L.oracle_reduce_grad_b_f32.argtypes = [_i32, _i32, _f32, _c32, _c32, _c32, _f32, _c64, _i32, _c64, _f32, _c64]
+        L.oracle_reduce_grad_b_f32.restype = None
         _lib = L
     return _lib
 
@@ -205,6 +209,31 @@ def sddmm(rowptr, col, M, dC, B):
     lib().oracle_sddmm_csr_f32(_i(rowptr), _pad1(col, np.int32), M, N, _pad1(dC, np.float32), max(N, 1),
                                _pad1(B, np.float32), max(N, 1), out)
     return out[:len(col)]
+
+
+def reduce_grad_val(rowptr, col, M, B, G, arg):
+    """amax / amin: gradient of A's stored values from the forward's arg ([M, N] selected entry per element), in the
+    order of reduce_grad_val_kernel (64 lane chains over j = 64t + l, then the xor tree 32 … 1)."""
+    B, G = _f(B), _f(G)
+    N = B.shape[1]
+    assert G.shape == (M, N) and np.shape(arg) == (M, N), (G.shape, np.shape(arg), M, N)
+    out = np.zeros(max(len(col), 1), np.float32)
+    lib().oracle_reduce_grad_val_f32(_i(rowptr), _pad1(col, np.int32), M, N, _pad1(B, np.float32), max(N, 1),
+                                     _pad1(G, np.float32), max(N, 1), _pad1(arg, np.int32), max(N, 1), out)
+    return out[:len(col)]
+
+
+def reduce_grad_b(rowptr, col, val, M, K, G, arg):
+    """amax / amin: gradient of B [K, N], one fmaf chain per element over the entries of Aᵀ's row in stable-transpose
+    order (reduce_grad_b_kernel); empty columns of A give +0 rows."""
+    G = _f(G)
+    N = G.shape[1]
+    assert G.shape == (M, N) and np.shape(arg) == (M, N), (G.shape, np.shape(arg), M, N)
+    out = np.empty((K, N), np.float32)
+    lib().oracle_reduce_grad_b_f32(_i(rowptr), _pad1(col, np.int32), _pad1(val, np.float32), M, K, N,
+                                   _pad1(G, np.float32), max(N, 1), _pad1(arg, np.int32), max(N, 1),
+                                   out if out.size else np.zeros(1, np.float32), max(N, 1))
+    return out
 
 
 def make_csr(M, K, density, seed):

@@ -9,7 +9,9 @@ import torch
 
 RTOL, ATOL = 1e-5, 1e-8
 
-__all__ = ['RTOL', 'ATOL', 't', 'torch_cpu_csr_matmul', 'assert_matches_reference_expression', 'run_spmm', '_random_rows_csr', '_transpose_through_the_c_abi', 'gemm_ref', '_dense_of', 'fwd_bwd_device', '_panel_sorted', '_sub_csr', '_moderately_dense_with_hub_rows']
+__all__ = ['RTOL', 'ATOL', 't', 'torch_cpu_csr_matmul', 'assert_matches_reference_expression', 'run_spmm', '_random_rows_csr', '_transpose_through_the_c_abi', 'gemm_ref', '_dense_of', 'fwd_bwd_device', '_panel_sorted', '_sub_csr', '_moderately_dense_with_hub_rows',
+           'assert_same_bits', 'gamma', 'assert_within_gamma_bound',
+           'sum_grads_f64', 'select_grads_f64']
 
 
 def t(x, dev):
@@ -131,3 +133,89 @@ def _moderately_dense_with_hub_rows(M, K, density, hubs, seed):
     rows, col = np.nonzero(mask)
     rowptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=M))]).astype(np.int32)
     return rowptr, col.astype(np.int32), g.random(len(col), dtype=np.float32) - 0.5
+
+
+def assert_same_bits(got, want, what=""):
+    """Bit-for-bit equality of two float tensors / arrays (float32, bfloat16 or float16): NaN by position, every other value
+    by its bits (−0 and ±inf included)."""
+    got = torch.as_tensor(got).detach().cpu()
+    want = torch.as_tensor(want).detach().cpu()
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.shape} {got.dtype} vs {want.shape} {want.dtype}"
+    gn, wn = torch.isnan(got.float()), torch.isnan(want.float())
+    assert torch.equal(gn, wn), f"{what}: NaN positions differ ({torch.nonzero(gn != wn)[:5].tolist()})"
+    ib = torch.int32 if got.element_size() == 4 else torch.int16
+    gb, wb = got.view(ib)[~gn], want.view(ib)[~wn]
+    bad = torch.nonzero(gb != wb).flatten()
+    assert bad.numel() == 0, (f"{what}: {bad.numel()} of {gb.numel()} values differ, first at {bad[:5].tolist()}: got "
+                              f"{got[~gn][bad[:5]].tolist()} want {want[~wn][bad[:5]].tolist()}")
+
+
+def gamma(n, u=2.0 ** -24):
+    """γ_n = n·u / (1 − n·u): the rounding-error factor of any summation of n (fused) products in precision u."""
+    return n * u / (1 - n * u)
+
+
+def assert_within_gamma_bound(got, ref64, abs64, n, what="", store_u=0.0, store_abs=0.0):
+    """|got − ref| ≤ γ_n·Σ|terms| (+ the store rounding store_u·|ref| + store_abs of a narrowing to 16 bits), elementwise,
+    against a float64 reference `ref64` whose terms' absolute values sum to `abs64`; non-finite references are skipped
+    (specials are checked bit for bit elsewhere).  Catches a wrong formula that a kernel and an order-restating oracle
+    could share (a transposed gradient, a wrong divisor)."""
+    got = np.asarray(torch.as_tensor(got).detach().cpu().double().numpy(), np.float64)
+    ref64, abs64 = np.asarray(ref64, np.float64), np.asarray(abs64, np.float64)
+    assert got.shape == ref64.shape == abs64.shape, (what, got.shape, ref64.shape, abs64.shape)
+    fin = np.isfinite(ref64) & np.isfinite(abs64)
+    tol = gamma(n) * abs64 * (1 + store_u) + store_u * np.abs(ref64) + store_abs
+    err = np.abs(got - ref64)
+    bad = fin & ~(err <= tol)
+    assert not bad.any(), (f"{what}: {int(bad.sum())} values outside γ_{n}·Σ|terms| of the float64 reference; first "
+                           f"{np.argwhere(bad)[:3].tolist()} got {got[bad][:3].tolist()} ref {ref64[bad][:3].tolist()} "
+                           f"tol {tol[bad][:3].tolist()}")
+
+
+def _rows_of(rowptr):
+    return np.repeat(np.arange(len(rowptr) - 1), np.diff(np.asarray(rowptr, np.int64)))
+
+
+def sum_grads_f64(rowptr, col, val, M, K, B, G):
+    """Float64 gradients of C = A·B (A CSR, duplicates and unsorted columns allowed), each with the sum of its terms'
+    absolute values: (grad_val, Σ|terms| of grad_val, grad_B, Σ|terms| of grad_B).  grad_val[e] = Σ_j G[row(e), j]·B[col[e], j]
+    (numpy, float64, in chunks); grad_B = Aᵀ·G through a torch-CPU float64 sparse product."""
+    B64, G64 = np.asarray(B, np.float64), np.asarray(G, np.float64)
+    rows, col = _rows_of(rowptr), np.asarray(col, np.int64)
+    gv, gva = np.zeros(len(col)), np.zeros(len(col))
+    step = max(1, (1 << 21) // max(B64.shape[1], 1))
+    for s0 in range(0, len(col), step):
+        r, c = rows[s0:s0 + step], col[s0:s0 + step]
+        gv[s0:s0 + len(r)] = np.einsum("ij,ij->i", G64[r], B64[c])
+        gva[s0:s0 + len(r)] = np.einsum("ij,ij->i", np.abs(G64[r]), np.abs(B64[c]))
+
+    def at_g(v, g):
+        idx = torch.from_numpy(np.stack([col, rows])) if len(col) else torch.zeros((2, 0), dtype=torch.int64)
+        at = torch.sparse_coo_tensor(idx, torch.from_numpy(np.asarray(v, np.float64)), (K, M))
+        return torch.sparse.mm(at, torch.from_numpy(g)).numpy()
+
+    v64 = np.asarray(val, np.float64)
+    return gv, gva, at_g(v64, G64), at_g(np.abs(v64), np.abs(G64))
+
+
+def select_grads_f64(rowptr, col, val, M, K, B, G, arg):
+    """Float64 gradients of amax / amin from the forward's selected entry per output element (`arg`, nnz where none):
+    grad_val[e] = Σ_{j: arg[i,j] = e} G[i,j]·B[col[e],j], grad_B[col[e], j] = Σ_{i: arg[i,j] = e} val[e]·G[i,j]; with the
+    sums of the terms' absolute values, as sum_grads_f64.  (Row blocks at a time: the 10⁶-row cases stay small.)"""
+    nnz, N = len(col), np.shape(arg)[1]
+    col = np.asarray(col, np.int64)
+    gv, gva, gb, gba = np.zeros(nnz), np.zeros(nnz), np.zeros(K * N), np.zeros(K * N)
+    step = max(1, (1 << 21) // max(N, 1))
+    for r0 in range(0, M, step):
+        a = np.asarray(arg[r0:r0 + step], np.int64)
+        i, j = np.nonzero((a >= 0) & (a < nnz))
+        e = a[i, j]
+        i = i + r0
+        g = np.asarray(G[i, j], np.float64)
+        b = np.asarray(B[col[e], j], np.float64)
+        v = np.asarray(val, np.float64)[e]
+        gv += np.bincount(e, weights=g * b, minlength=nnz)
+        gva += np.bincount(e, weights=np.abs(g * b), minlength=nnz)
+        gb += np.bincount(col[e] * N + j, weights=v * g, minlength=K * N)
+        gba += np.bincount(col[e] * N + j, weights=np.abs(v * g), minlength=K * N)
+    return gv, gva, gb.reshape(K, N), gba.reshape(K, N)

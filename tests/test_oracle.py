@@ -246,3 +246,70 @@ def test_gemm_split_k_order_matches_the_v2_golden(oracle_mod):
         for got in (split, chain):
             assert np.allclose(got, data[name + "/c"], rtol=1e-5, atol=1e-8), name
             assert np.allclose(got, data[name + "/c_fp64"], rtol=1e-5, atol=1e-8), name
+
+
+# ---- the gradient restatements of amax / amin (oracle.reduce_grad_val / reduce_grad_b) -------------------------------
+
+def _reduce_case(M, K, N, seed, integer=False):
+    """A CSR with empty rows, empty columns, rows of 1 … 150 entries and a few duplicate / unsorted columns; B, G."""
+    g = np.random.Generator(np.random.PCG64(seed))
+    lens = g.integers(0, 150, M)
+    lens[::5] = 0
+    lens[1] = 1
+    used = np.arange(K)[g.random(K) < 0.8]  # the other columns stay empty: their rows of grad B must be +0
+    col = np.concatenate([g.choice(used, int(n)) for n in lens]).astype(np.int32)  # with replacement: duplicates
+    rowptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    if integer:  # nonzero small integers: every product and every partial sum is exact in fp32
+        pick = lambda *s: (g.integers(1, 4, s) * g.choice([-1, 1], s)).astype(np.float32)  # noqa: E731
+        val, B, G = pick(len(col)), pick(K, N), pick(M, N)
+    else:
+        val = g.standard_normal(len(col), dtype=np.float32)
+        B, G = g.standard_normal((K, N), dtype=np.float32), g.standard_normal((M, N), dtype=np.float32)
+    return rowptr, col, val, B, G
+
+
+def _torch_csr(rowptr, col, val, M, K):
+    return torch.sparse_csr_tensor(torch.from_numpy(rowptr.astype(np.int64)), torch.from_numpy(col.astype(np.int64)),
+                                   torch.from_numpy(val), (M, K))
+
+
+@pytest.mark.parametrize("reduce", ["amax", "amin"])
+@pytest.mark.parametrize("N", [1, 3, 5, 64, 65, 130, 1100])
+def test_reduce_grad_restatements_within_float64_bound(oracle_mod, reduce, N):
+    from gpu_helpers import assert_within_gamma_bound, select_grads_f64
+    M, K = 120, 90
+    rowptr, col, val, B, G = _reduce_case(M, K, N, seed=N)
+    _, arg = torch.ops.aten._sparse_mm_reduce_impl(_torch_csr(rowptr, col, val, M, K).requires_grad_(),
+                                                  torch.from_numpy(B), reduce)
+    arg = arg.numpy()
+    gv = oracle_mod.reduce_grad_val(rowptr, col, M, B, G, arg)
+    gb = oracle_mod.reduce_grad_b(rowptr, col, val, M, K, G, arg)
+    ref_v, abs_v, ref_b, abs_b = select_grads_f64(rowptr, col, val, M, K, B, G, arg)
+    assert_within_gamma_bound(gv, ref_v, abs_v, N, f"{reduce} N={N} grad_val")
+    assert_within_gamma_bound(gb, ref_b, abs_b, int(np.bincount(col, minlength=K).max()), f"{reduce} N={N} grad_B")
+    empty = np.bincount(col, minlength=K) == 0
+    assert empty.any() and np.all(gb[empty].view(np.int32) == 0), "empty columns of A give +0 rows of grad B"
+
+
+@pytest.mark.parametrize("reduce", ["sum", "amax", "amin"])
+@pytest.mark.parametrize("N", [1, 3, 64, 65, 130, 1100])
+def test_gradient_restatements_equal_torch_autograd_on_exact_integers(oracle_mod, reduce, N):
+    """On nonzero small-integer operands every sum is exact, whatever its order: the restatements (amax / amin) and the
+    sum's composition (SDDMM; the product on the stable transpose) must give torch-CPU autograd's bits exactly."""
+    from gpu_helpers import assert_same_bits
+    M, K = 120, 90
+    rowptr, col, val, B, G = _reduce_case(M, K, N, seed=100 + N, integer=True)
+    a = _torch_csr(rowptr, col, val, M, K).requires_grad_()
+    b = torch.from_numpy(B).requires_grad_()
+    torch.sparse.mm(a, b, reduce=reduce).backward(torch.from_numpy(G))
+    if reduce == "sum":
+        gv = oracle_mod.sddmm(rowptr, col, M, G, B)
+        t_rp, t_col, t_val = oracle_mod.csr_transpose(rowptr, col, val, M, K)
+        gb = oracle_mod.spmm_csr_long(t_rp, t_col, t_val, K, M, G)
+    else:
+        _, arg = torch.ops.aten._sparse_mm_reduce_impl(_torch_csr(rowptr, col, val, M, K).requires_grad_(),
+                                                  torch.from_numpy(B), reduce)
+        gv = oracle_mod.reduce_grad_val(rowptr, col, M, B, G, arg.numpy())
+        gb = oracle_mod.reduce_grad_b(rowptr, col, val, M, K, G, arg.numpy())
+    assert_same_bits(gv, a.grad.values().detach(), f"{reduce} N={N} grad_val")
+    assert_same_bits(gb, b.grad, f"{reduce} N={N} grad_B")
