@@ -212,7 +212,7 @@ const char* mi_spmm_variant_name(int variant);
  *   Products on one schedule must be ordered on one stream (they share its fork / join events).  The side stream itself is ONE per
  *   device for every schedule of the process (a stream per schedule ran out of hardware queues): unrelated products may see a
  *   false order between their ordinary launches, nothing else.
- *   mi_spmm_schedule_info: info[12] = {rows, heavy slots, heavy length, non-empty classes, lower bound of the longest row,
+ *   mi_spmm_schedule_info: info[MI_SPMM_SCHEDULE_INFO_LEN] = {rows, heavy slots, heavy length, non-empty classes, lower bound of the longest row,
  *     flags (1: has a side stream; 2: ACTIVE — an order costs the locality of consecutive rows, so a matrix of short, alike
  *     rows keeps its products unscheduled: active with heavy rows, with a locality order, or mean ≥ 16 entries with ≥ 2 % of the
  *     entries in rows of ≥ 1.5 × the mean; 4: locality order), nnz, N, a window's footprint in natural order / in this order (‰ of B), mean row span (‰ of
@@ -239,6 +239,7 @@ int mi_spmm_schedule_create(const int32_t* rowptr, const int32_t* col, int32_t M
                             int32_t* order, void* workspace, size_t workspace_bytes, mi_stream_t stream,
                             mi_spmm_schedule_t** out);
 int mi_spmm_schedule_destroy(mi_spmm_schedule_t* schedule);
+#define MI_SPMM_SCHEDULE_INFO_LEN 12 /* entries mi_spmm_schedule_info writes */
 int mi_spmm_schedule_info(const mi_spmm_schedule_t* schedule, int64_t* info);
 int mi_spmm_schedule_set_heavy(mi_spmm_schedule_t* schedule, int32_t heavy_len, int use_side_stream);
 int mi_spmm_csr_scheduled_f32(const mi_spmm_schedule_t* schedule, int variant, const int32_t* rowptr, const int32_t* col,

@@ -611,7 +611,7 @@ int mi_spmm_csr_colmajor_sched_f32(const mi_spmm_schedule_t* schedule, const int
   // operands stays (a long row is ordinary work there), the fused-output kernel (16 consecutive rows per workgroup) does not
   bool scheduled = false;
   if (schedule != nullptr) {
-    int64_t info[8];
+    int64_t info[MI_SPMM_SCHEDULE_INFO_LEN];
     if (mi_spmm_schedule_info(schedule, info) == MI_OK) scheduled = (info[5] & 2) != 0 && info[0] == M;
   }
   if (M < 0 || K < 0 || N < 0 || nnz < 0) return MI_EINVAL;

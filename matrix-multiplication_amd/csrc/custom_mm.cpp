@@ -27,6 +27,7 @@
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <array>
 #include <cstdlib>
 #include <initializer_list>
 #include <map>
@@ -35,26 +36,16 @@
 #include <string>
 #include <tuple>
 #include <unordered_map>
+#include <utility>
 
 #include "mi_spmm.h"
 
 namespace {
 #include "custom_mm_helpers.inc"
-// bf16 / fp16 operands: naive_spmm, cusparse_mmul, naive_spmm_ex, sddmm and gather_perm hand the call to these
-// (custom_mm_lowp.inc, included last: it uses the per-stream workspace of custom_mm_reference.inc)
-bool is_lowp(const torch::Tensor& t);
-bool lowp_operands(std::initializer_list<const torch::Tensor*> ts);
-torch::Tensor spmm_lowp(const torch::Tensor& A_values, const torch::Tensor& A_columns, const torch::Tensor& A_offsets,
-                        int64_t nnzA, int64_t A_rows, int64_t A_cols, const torch::Tensor& B, torch::Tensor C,
-                        const char* what, int long_rows);
-torch::Tensor sddmm_lowp(const torch::Tensor& A_columns, const torch::Tensor& A_offsets, int64_t nnzA, int64_t A_rows,
-                         int64_t A_cols, const torch::Tensor& dC, const torch::Tensor& B);
-torch::Tensor gather_perm_lowp(const torch::Tensor& values, const torch::Tensor& perm);
 #include "custom_mm_reference.inc"
 #include "custom_mm_extras.inc"
 #include "custom_mm_inspect.inc"
 #include "custom_mm_reduce.inc"
-#include "custom_mm_lowp.inc"
 
 // ---- handle init / destroy (reference custom_mm.cpp:361-391) ----------------
 // There are no vendor handles on this path; init checks that the C-ABI library

@@ -29,7 +29,7 @@ torch::Tensor dense_row_offsets(torch::Tensor dense) {
   auto iopt = torch::dtype(torch::kInt32).device(d.device());
   torch::Tensor offsets = torch::empty({batch, rows + 1}, iopt);
   const size_t ws_bytes = mi_dense_to_csr_workspace_bytes((int32_t)batch, (int32_t)rows);
-  torch::Tensor ws = torch::empty({(int64_t)std::max<size_t>(ws_bytes, 1)}, torch::dtype(torch::kUInt8).device(d.device()));
+  torch::Tensor ws = byte_workspace(d.device(), ws_bytes, 1);
   check_status(mi_dense_to_csr_count(d.data_ptr<float>(), (int32_t)batch, (int32_t)rows, (int32_t)cols, cols,
                                      rows * cols, offsets.data_ptr<int32_t>(), ws.data_ptr(), ws_bytes,
                                      stream_of(d)),
@@ -42,7 +42,7 @@ torch::Tensor dense_row_offsets(torch::Tensor dense) {
 std::tuple<torch::Tensor, torch::Tensor> dense_to_csr_fill(torch::Tensor dense, torch::Tensor offsets, int64_t nnz) {
   check_device_f32(dense, "dense");
   check_device_i32(offsets, "offsets");
-  check_same_device(dense, offsets, "dense_to_csr_fill");
+  check_same_device("dense_to_csr_fill", dense.device(), {&offsets});
   TORCH_CHECK(dense.dim() >= 2 && nnz >= 0 && nnz <= dense.numel(), "dense_to_csr_fill: bad arguments");
   torch::Tensor d = dense.contiguous();
   const int64_t rows = d.size(-2), cols = d.size(-1);
@@ -74,37 +74,18 @@ torch::Tensor naive_spmm_batched(torch::Tensor A_values, torch::Tensor A_columns
                                  int64_t nnzA, int64_t batch, int64_t A_rows, int64_t A_cols,
                                  torch::Tensor B, torch::Tensor C) {
   const char* what = "naive_spmm_batched";
-  check_device_f32(A_values, "A_values");
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_device_f32(B, "B");
-  check_device_f32(C, "C");
-  check_same_device(A_values, C, what);
-  check_same_device(A_columns, C, what);
-  check_same_device(A_offsets, C, what);
-  check_same_device(B, C, what);
-  TORCH_CHECK(batch >= 0 && A_rows >= 0 && A_cols >= 0 && nnzA >= 0, what, ": negative size");
+  value_dtype(what, {{"A_values", &A_values}, {"B", &B}, {"C", &C}});
+  const Csr a = csr_arrays(what, &A_values, &A_columns, A_offsets, nnzA, A_rows, A_cols, batch);
+  check_same_device(what, a.device, {&B, &C});
   TORCH_CHECK(batch <= 65535, what, ": at most 65535 items per launch");
-  TORCH_CHECK(A_values.is_contiguous() && A_columns.is_contiguous() && A_offsets.is_contiguous(), what,
-              ": CSR arrays must be contiguous");
-  TORCH_CHECK(A_offsets.numel() == batch * (A_rows + 1), what, ": A_offsets must be [batch, A_rows + 1]");
-  TORCH_CHECK(A_values.numel() >= nnzA && A_columns.numel() >= nnzA, what, ": nnzA exceeds the CSR arrays");
   TORCH_CHECK(C.dim() == 3 && C.is_contiguous() && C.size(0) == batch && C.size(1) == A_rows, what,
               ": C must be contiguous [batch, A_rows, N]");
   const int64_t N = C.size(2);
-  torch::Tensor Bc = B.contiguous();
-  int64_t strideB = 0;
-  if (Bc.dim() == 3) {
-    TORCH_CHECK(Bc.size(0) == batch && Bc.size(1) == A_cols && Bc.size(2) == N, what, ": B must be [batch, A_cols, N]");
-    strideB = A_cols * N;
-  } else {
-    TORCH_CHECK(Bc.dim() == 2 && Bc.size(0) == A_cols && Bc.size(1) == N, what, ": B must be [A_cols, N]");
-  }
+  check_sizes(what, {N});
+  const auto b = batched_b(what, B, batch, A_cols, N);
   c10::hip::HIPGuard guard(C.device().index());
-  check_status(mi_spmm_csr_batched_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(),
-                                       A_values.data_ptr<float>(), nnzA, (int32_t)batch, (int32_t)A_rows,
-                                       (int32_t)A_cols, (int32_t)N, Bc.data_ptr<float>(), std::max<int64_t>(N, 1),
-                                       strideB, C.data_ptr<float>(), std::max<int64_t>(N, 1), A_rows * N,
+  check_status(mi_spmm_csr_batched_f32(a.offsets, a.columns, a.f32(), nnzA, a.batch, a.rows, a.cols, (int32_t)N,
+                                       b.first.data_ptr<float>(), ld1(N), b.second, C.data_ptr<float>(), ld1(N), A_rows * N,
                                        stream_of(C)),
                what);
   return C;
@@ -117,41 +98,19 @@ bool naive_spmm_batched_perm(torch::Tensor A_values, torch::Tensor perm, torch::
                              int64_t nnzA, int64_t batch, int64_t A_rows, int64_t A_cols, torch::Tensor B,
                              torch::Tensor C) {
   const char* what = "naive_spmm_batched_perm";
-  check_device_f32(A_values, "A_values");
-  check_device_i32(perm, "perm");
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_device_f32(B, "B");
-  check_device_f32(C, "C");
-  check_same_device(A_values, C, what);
-  check_same_device(perm, C, what);
-  check_same_device(A_columns, C, what);
-  check_same_device(A_offsets, C, what);
-  check_same_device(B, C, what);
-  TORCH_CHECK(batch >= 0 && A_rows >= 0 && A_cols >= 0 && nnzA >= 0, what, ": negative size");
+  value_dtype(what, {{"A_values", &A_values}, {"B", &B}, {"C", &C}});
+  const Csr a = csr_arrays(what, &A_values, &A_columns, A_offsets, nnzA, A_rows, A_cols, batch, &perm);
+  check_same_device(what, a.device, {&B, &C});
   TORCH_CHECK(batch <= 65535, what, ": at most 65535 items per launch");
-  TORCH_CHECK(A_values.is_contiguous() && perm.is_contiguous() && A_columns.is_contiguous() && A_offsets.is_contiguous(),
-              what, ": CSR arrays must be contiguous");
-  TORCH_CHECK(A_offsets.numel() == batch * (A_rows + 1), what, ": A_offsets must be [batch, A_rows + 1]");
-  TORCH_CHECK(perm.numel() >= nnzA && A_columns.numel() >= nnzA && A_values.numel() >= nnzA, what,
-              ": nnzA exceeds the CSR arrays");
   TORCH_CHECK(C.dim() == 3 && C.is_contiguous() && C.size(0) == batch && C.size(1) == A_rows, what,
               ": C must be contiguous [batch, A_rows, N]");
   const int64_t N = C.size(2);
-  torch::Tensor Bc = B.contiguous();
-  int64_t strideB = 0;
-  if (Bc.dim() == 3) {
-    TORCH_CHECK(Bc.size(0) == batch && Bc.size(1) == A_cols && Bc.size(2) == N, what, ": B must be [batch, A_cols, N]");
-    strideB = A_cols * N;
-  } else {
-    TORCH_CHECK(Bc.dim() == 2 && Bc.size(0) == A_cols && Bc.size(1) == N, what, ": B must be [A_cols, N]");
-  }
+  check_sizes(what, {N});
+  const auto b = batched_b(what, B, batch, A_cols, N);
   c10::hip::HIPGuard guard(C.device().index());
-  const int st = mi_spmm_csr_batched_perm_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(),
-                                              A_values.data_ptr<float>(), perm.data_ptr<int32_t>(), nnzA, (int32_t)batch,
-                                              (int32_t)A_rows, (int32_t)A_cols, (int32_t)N, Bc.data_ptr<float>(),
-                                              std::max<int64_t>(N, 1), strideB, C.data_ptr<float>(),
-                                              std::max<int64_t>(N, 1), A_rows * N, stream_of(C));
+  const int st = mi_spmm_csr_batched_perm_f32(a.offsets, a.columns, a.f32(), a.perm, nnzA, a.batch, a.rows, a.cols, (int32_t)N,
+                                              b.first.data_ptr<float>(), ld1(N), b.second, C.data_ptr<float>(), ld1(N),
+                                              A_rows * N, stream_of(C));
   if (st == 1) return false;
   check_status(st, what);
   return true;
@@ -163,31 +122,19 @@ bool naive_spmm_batched_perm(torch::Tensor A_values, torch::Tensor perm, torch::
 bool naive_spmm_batched_at(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor A_offsets, int64_t nnzA,
                            int64_t batch, int64_t A_rows, int64_t A_cols, torch::Tensor X, torch::Tensor C) {
   const char* what = "naive_spmm_batched_at";
-  check_device_f32(A_values, "A_values");
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_device_f32(X, "X");
-  check_device_f32(C, "C");
-  check_same_device(A_values, C, what);
-  check_same_device(A_columns, C, what);
-  check_same_device(A_offsets, C, what);
-  check_same_device(X, C, what);
-  TORCH_CHECK(batch >= 0 && A_rows >= 0 && A_cols >= 0 && nnzA >= 0, what, ": negative size");
-  TORCH_CHECK(A_rows <= INT32_MAX && A_cols <= INT32_MAX && batch <= INT32_MAX, what, ": dimension too large");
-  TORCH_CHECK(A_values.is_contiguous() && A_columns.is_contiguous() && A_offsets.is_contiguous(), what,
-              ": CSR arrays must be contiguous");
-  TORCH_CHECK(A_offsets.numel() == batch * (A_rows + 1), what, ": A_offsets must be [batch, A_rows + 1]");
-  TORCH_CHECK(A_columns.numel() >= nnzA && A_values.numel() >= nnzA, what, ": nnzA exceeds the CSR arrays");
+  value_dtype(what, {{"A_values", &A_values}, {"X", &X}, {"C", &C}});
+  const Csr a = csr_arrays(what, &A_values, &A_columns, A_offsets, nnzA, A_rows, A_cols, batch);
+  check_same_device(what, a.device, {&X, &C});
   TORCH_CHECK(C.dim() == 3 && C.is_contiguous() && C.size(0) == batch && C.size(1) == A_cols, what,
               ": C must be contiguous [batch, A_cols, N]");
   const int64_t N = C.size(2);
+  check_sizes(what, {N});
   TORCH_CHECK(X.dim() == 3 && X.size(0) == batch && X.size(1) == A_rows && X.size(2) == N, what, ": X must be [batch, A_rows, N]");
   torch::Tensor Xc = X.contiguous();
   c10::hip::HIPGuard guard(C.device().index());
-  const int st = mi_spmm_csr_batched_at_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(),
-                                            A_values.data_ptr<float>(), nnzA, (int32_t)batch, (int32_t)A_rows, (int32_t)A_cols,
-                                            (int32_t)N, Xc.data_ptr<float>(), std::max<int64_t>(N, 1), A_rows * N,
-                                            C.data_ptr<float>(), std::max<int64_t>(N, 1), A_cols * N, stream_of(C));
+  const int st = mi_spmm_csr_batched_at_f32(a.offsets, a.columns, a.f32(), nnzA, a.batch, a.rows, a.cols, (int32_t)N,
+                                            Xc.data_ptr<float>(), ld1(N), A_rows * N, C.data_ptr<float>(), ld1(N), A_cols * N,
+                                            stream_of(C));
   if (st == 1) return false;
   check_status(st, what);
   return true;
@@ -202,7 +149,7 @@ std::tuple<torch::Tensor, torch::Tensor> batched_csr_narrow(torch::Tensor crow, 
   TORCH_CHECK(crow.dim() == 2 && col.dim() == 2 && crow.size(0) == col.size(0) && crow.size(1) >= 1, what,
               ": crow [batch, rows + 1] and col [batch, per_item] expected");
   TORCH_CHECK(crow.is_contiguous() && col.is_contiguous(), what, ": contiguous index tensors expected");
-  check_same_device(crow, col, what);
+  check_same_device(what, crow.device(), {&col});
   const int64_t batch = crow.size(0), rows = crow.size(1) - 1, per_item = col.size(1);
   TORCH_CHECK(batch <= INT32_MAX && rows <= INT32_MAX && batch * per_item <= INT32_MAX, what, ": too large for int32 indices");
   c10::hip::HIPGuard guard(crow.device().index());
@@ -219,11 +166,8 @@ std::tuple<torch::Tensor, torch::Tensor> batched_csr_narrow(torch::Tensor crow, 
 // caller can take the dense_to_csr + naive_spmm_batched route instead.
 bool spmm_dense_impl(const torch::Tensor& A, const torch::Tensor& B, const torch::Tensor* bias, torch::Tensor C,
                      const char* what) {
-  check_device_f32(A, "A");
-  check_device_f32(B, "B");
-  check_device_f32(C, "C");
-  check_same_device(A, C, what);
-  check_same_device(B, C, what);
+  value_dtype(what, {{"A", &A}, {"B", &B}, {"C", &C}});
+  check_same_device(what, C.device(), {&A, &B});
   TORCH_CHECK(A.dim() >= 2 && C.dim() == A.dim(), what, ": A and C must have the same rank (>= 2)");
   TORCH_CHECK(C.is_contiguous(), what, ": C must be contiguous");
   torch::Tensor Ac = A.contiguous(), Bc = B.contiguous();
@@ -239,16 +183,9 @@ bool spmm_dense_impl(const torch::Tensor& A, const torch::Tensor& B, const torch
     strideB = K * N;
   }
   TORCH_CHECK(C.numel() == batch * M * N, what, ": C must be [batch…, ", M, ", ", N, "]");
-  TORCH_CHECK(M <= INT32_MAX && K <= INT32_MAX && N <= INT32_MAX, what, ": dimension too large");
-  const float* bias_ptr = nullptr;
-  torch::Tensor bias_keep;
-  if (bias != nullptr && bias->defined()) {
-    check_device_f32(*bias, "bias");
-    check_same_device(*bias, C, what);
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == N, what, ": bias must have ", N, " entries");
-    bias_keep = bias->contiguous();
-    bias_ptr = bias_keep.data_ptr<float>();
-  }
+  check_sizes(what, {M, K, N, batch});
+  const torch::Tensor bias_keep = bias_of(what, bias, N, C);
+  const float* bias_ptr = f32_or_null(bias_keep);
   if (batch == 0 || M == 0 || N == 0) return true;
   // The kernel covers up to 256 columns; wider products (up to 1024 columns) run as column tiles of
   // 256 — every column of C is its own chain, so the bits are the same — at the price of scanning A once
@@ -263,7 +200,7 @@ bool spmm_dense_impl(const torch::Tensor& A, const torch::Tensor& B, const torch
       return false;
   c10::hip::HIPGuard guard(C.device().index());
   for (int64_t n0 = 0; n0 < N; n0 += kTile)
-    check_status(mi_spmm_dense_skip_f32(Ac.data_ptr<float>(), std::max<int64_t>(K, 1), M * K, (int32_t)batch,
+    check_status(mi_spmm_dense_skip_f32(Ac.data_ptr<float>(), ld1(K), M * K, (int32_t)batch,
                                         (int32_t)M, (int32_t)K, (int32_t)std::min(kTile, N - n0),
                                         Bc.data_ptr<float>() + n0, N, strideB, bias_ptr ? bias_ptr + n0 : nullptr,
                                         C.data_ptr<float>() + n0, N, M * N, stream_of(C)),
@@ -285,10 +222,7 @@ bool naive_spmm_dense_bias(torch::Tensor A, torch::Tensor B, torch::Tensor bias,
 bool cublas_bmm_pair(torch::Tensor dC, torch::Tensor B, torch::Tensor A, torch::Tensor dA, torch::Tensor dB) {
   const char* what = "cublas_bmm_pair";
   for (const torch::Tensor* t : {&dC, &B, &A, &dA, &dB}) check_device_f32(*t, "operand");
-  check_same_device(dC, dA, what);
-  check_same_device(B, dA, what);
-  check_same_device(A, dA, what);
-  check_same_device(dB, dA, what);
+  check_same_device(what, dA.device(), {&dC, &B, &A, &dB});
   if (dC.dim() < 2 || B.dim() != dC.dim() || A.dim() != dC.dim() || dA.dim() != dC.dim() || dB.dim() != dC.dim()) return false;
   const int64_t m = dC.size(-2), k = dC.size(-1), n = B.size(-1);
   const int64_t batch = m * k > 0 ? dC.numel() / (m * k) : 0;
@@ -327,8 +261,7 @@ bool naive_spmm_dense_gated(torch::Tensor A, torch::Tensor B, torch::Tensor C, t
   check_device_f32(A, "A");
   check_device_f32(B, "B");
   check_device_f32(C, "C");
-  check_same_device(A, C, what);
-  check_same_device(B, C, what);
+  check_same_device(what, C.device(), {&A, &B});
   TORCH_CHECK(A.dim() >= 2 && C.dim() == A.dim(), what, ": A and C must have the same rank (>= 2)");
   TORCH_CHECK(C.is_contiguous(), what, ": C must be contiguous");
   const int64_t M = A.size(-2), K = A.size(-1), N = C.size(-1);
@@ -369,29 +302,19 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> csr_transpose(torch::Ten
                                                                       torch::Tensor A_offsets, int64_t nnzA,
                                                                       int64_t A_rows, int64_t A_cols) {
   const char* what = "csr_transpose";
-  check_device_f32(A_values, "A_values");
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_same_device(A_values, A_columns, what);
-  check_same_device(A_values, A_offsets, what);
-  TORCH_CHECK(A_rows >= 0 && A_cols >= 0 && nnzA >= 0 && A_rows <= INT32_MAX && A_cols <= INT32_MAX, what, ": bad size");
-  TORCH_CHECK(A_values.is_contiguous() && A_columns.is_contiguous() && A_offsets.is_contiguous(), what,
-              ": CSR arrays must be contiguous");
-  TORCH_CHECK(A_offsets.numel() == A_rows + 1 && A_values.numel() >= nnzA && A_columns.numel() >= nnzA, what,
-              ": CSR array sizes do not match");
+  value_dtype(what, {{"A_values", &A_values}});
+  const Csr a = csr_arrays(what, &A_values, &A_columns, A_offsets, nnzA, A_rows, A_cols);
   c10::hip::HIPGuard guard(A_values.device().index());
   auto iopt = torch::dtype(torch::kInt32).device(A_values.device());
   torch::Tensor t_off = torch::empty({A_cols + 1}, iopt);
   torch::Tensor t_col = torch::empty({nnzA}, iopt);
   torch::Tensor t_val = torch::empty({nnzA}, A_values.options());
-  const size_t ws_bytes = mi_csr_transpose_workspace_bytes((int32_t)A_rows, (int32_t)A_cols, nnzA);
-  torch::Tensor ws = torch::empty({(int64_t)std::max<size_t>(ws_bytes, 1)}, torch::dtype(torch::kUInt8).device(A_values.device()));
+  const size_t ws_bytes = mi_csr_transpose_workspace_bytes(a.rows, a.cols, nnzA);
+  torch::Tensor ws = byte_workspace(a.device, ws_bytes, 1);
   const mi_stream_t stream = stream_of(A_values);
   auto run = [&]() {
-    check_status(mi_csr_transpose_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(),
-                                      A_values.data_ptr<float>(), nnzA, (int32_t)A_rows, (int32_t)A_cols,
-                                      t_off.data_ptr<int32_t>(), t_col.data_ptr<int32_t>(), t_val.data_ptr<float>(),
-                                      ws.data_ptr(), ws_bytes, stream),
+    check_status(mi_csr_transpose_f32(a.offsets, a.columns, a.f32(), nnzA, a.rows, a.cols, t_off.data_ptr<int32_t>(),
+                                      t_col.data_ptr<int32_t>(), t_val.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream),
                  what);
   };
   run();
@@ -400,8 +323,8 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> csr_transpose(torch::Ten
   // here for a tensor's or a handle's lifetime, so the flag is read here (one synchronisation behind a ≥ 1 ms launch; not
   // under stream capture, where nothing may be read back) and a give-up re-runs the transpose on the table plan
   // (advisor, round 4).
-  if (mi_csr_transpose_auto_takes_one_sweep(1, (int32_t)A_rows, (int32_t)A_cols, nnzA) == 1 && !stream_is_capturing(stream) &&
-      mi_csr_transpose_check(ws.data_ptr(), ws_bytes, 1, (int32_t)A_rows, (int32_t)A_cols, nnzA, stream) != MI_OK) {
+  if (mi_csr_transpose_auto_takes_one_sweep(1, a.rows, a.cols, nnzA) == 1 && !stream_is_capturing(stream) &&
+      mi_csr_transpose_check(ws.data_ptr(), ws_bytes, 1, a.rows, a.cols, nnzA, stream) != MI_OK) {
     mi_csr_transpose_set_plan(MI_TRANSPOSE_PLAN_TABLES);
     try {
       run();
@@ -422,72 +345,43 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> csr_transpose_batched(to
                                                                               int64_t batch, int64_t A_rows,
                                                                               int64_t A_cols) {
   const char* what = "csr_transpose_batched";
-  check_device_f32(A_values, "A_values");
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_same_device(A_values, A_columns, what);
-  check_same_device(A_values, A_offsets, what);
-  TORCH_CHECK(batch >= 0 && A_rows >= 0 && A_cols >= 0 && nnzA >= 0 && A_rows <= INT32_MAX && A_cols <= INT32_MAX &&
-                  batch <= INT32_MAX,
-              what, ": bad size");
-  TORCH_CHECK(A_values.is_contiguous() && A_columns.is_contiguous() && A_offsets.is_contiguous(), what,
-              ": CSR arrays must be contiguous");
-  TORCH_CHECK(A_offsets.numel() == batch * (A_rows + 1) && A_values.numel() >= nnzA && A_columns.numel() >= nnzA, what,
-              ": CSR array sizes do not match");
+  value_dtype(what, {{"A_values", &A_values}});
+  const Csr a = csr_arrays(what, &A_values, &A_columns, A_offsets, nnzA, A_rows, A_cols, batch);
   c10::hip::HIPGuard guard(A_values.device().index());
   auto iopt = torch::dtype(torch::kInt32).device(A_values.device());
   torch::Tensor t_off = torch::empty({batch, A_cols + 1}, iopt);
   torch::Tensor t_col = torch::empty({nnzA}, iopt);
   torch::Tensor t_val = torch::empty({nnzA}, A_values.options());
   // (the one-workgroup-per-item plan of small items uses no workspace)
-  const size_t ws_bytes = mi_csr_transpose_batched_in_lds(nnzA, (int32_t)batch, (int32_t)A_rows, (int32_t)A_cols) == 1
-                              ? 0 : mi_csr_transpose_batched_workspace_bytes((int32_t)batch, (int32_t)A_rows, (int32_t)A_cols, nnzA);
-  torch::Tensor ws = torch::empty({(int64_t)std::max<size_t>(ws_bytes, 1)}, torch::dtype(torch::kUInt8).device(A_values.device()));
-  check_status(mi_csr_transpose_batched_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(),
-                                            A_values.data_ptr<float>(), nnzA, (int32_t)batch, (int32_t)A_rows,
-                                            (int32_t)A_cols, t_off.data_ptr<int32_t>(), t_col.data_ptr<int32_t>(),
-                                            t_val.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream_of(A_values)),
+  const size_t ws_bytes = mi_csr_transpose_batched_in_lds(nnzA, a.batch, a.rows, a.cols) == 1
+                              ? 0 : mi_csr_transpose_batched_workspace_bytes(a.batch, a.rows, a.cols, nnzA);
+  torch::Tensor ws = byte_workspace(a.device, ws_bytes, 1);
+  check_status(mi_csr_transpose_batched_f32(a.offsets, a.columns, a.f32(), nnzA, a.batch, a.rows, a.cols, t_off.data_ptr<int32_t>(),
+                                            t_col.data_ptr<int32_t>(), t_val.data_ptr<float>(), ws.data_ptr(), ws_bytes,
+                                            stream_of(A_values)),
                what);
   return std::make_tuple(t_val, t_col, t_off);
 }
 
-// The same on a batched CSR pattern (offsets [batch, A_rows + 1], global), dC [batch, A_rows, N], B [batch, A_cols, N] or
+// The same on a batched CSR pattern (offsets [batch, rows + 1], global), dC [batch, A_rows, N], B [batch, A_cols, N] or
 // [A_cols, N] (shared), into the caller's out [nnzA]; False (nothing launched) when the LDS-resident form does not take
 // the problem: run sddmm on the block-diagonal matrix of the batch instead (same bits).
 bool sddmm_batched(torch::Tensor A_columns, torch::Tensor A_offsets, int64_t nnzA, int64_t batch, int64_t A_rows,
                    int64_t A_cols, torch::Tensor dC, torch::Tensor B, torch::Tensor out) {
   const char* what = "sddmm_batched";
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_device_f32(dC, "dC");
-  check_device_f32(B, "B");
-  check_device_f32(out, "out");
-  check_same_device(A_columns, out, what);
-  check_same_device(A_offsets, out, what);
-  check_same_device(dC, out, what);
-  check_same_device(B, out, what);
-  TORCH_CHECK(batch >= 0 && A_rows >= 0 && A_cols >= 0 && nnzA >= 0 && batch <= INT32_MAX && A_rows <= INT32_MAX &&
-                  A_cols <= INT32_MAX,
-              what, ": bad size");
-  TORCH_CHECK(A_columns.is_contiguous() && A_offsets.is_contiguous() && out.is_contiguous(), what,
-              ": CSR arrays and out must be contiguous");
-  TORCH_CHECK(A_offsets.numel() == batch * (A_rows + 1) && A_columns.numel() >= nnzA && out.numel() >= nnzA, what,
-              ": CSR array sizes do not match");
+  value_dtype(what, {{"dC", &dC}, {"B", &B}, {"out", &out}});
+  const Csr a = csr_arrays(what, nullptr, &A_columns, A_offsets, nnzA, A_rows, A_cols, batch);
+  check_same_device(what, a.device, {&dC, &B, &out});
+  TORCH_CHECK(out.is_contiguous() && out.numel() >= nnzA, what, ": out must be contiguous with nnzA entries");
   TORCH_CHECK(dC.dim() == 3 && dC.size(0) == batch && dC.size(1) == A_rows, what, ": dC must be [batch, A_rows, N]");
   const int64_t N = dC.size(2);
-  torch::Tensor dCc = dC.contiguous(), Bc = B.contiguous();
-  int64_t strideB = 0;
-  if (Bc.dim() == 3) {
-    TORCH_CHECK(Bc.size(0) == batch && Bc.size(1) == A_cols && Bc.size(2) == N, what, ": B must be [batch, A_cols, N]");
-    strideB = A_cols * N;
-  } else {
-    TORCH_CHECK(Bc.dim() == 2 && Bc.size(0) == A_cols && Bc.size(1) == N, what, ": B must be [A_cols, N]");
-  }
+  check_sizes(what, {N});
+  const auto b = batched_b(what, B, batch, A_cols, N);
+  torch::Tensor dCc = dC.contiguous();
   c10::hip::HIPGuard guard(out.device().index());
-  const int st = mi_sddmm_csr_batched_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(), nnzA, (int32_t)batch,
-                                          (int32_t)A_rows, (int32_t)A_cols, (int32_t)N, dCc.data_ptr<float>(),
-                                          std::max<int64_t>(N, 1), A_rows * N, Bc.data_ptr<float>(),
-                                          std::max<int64_t>(N, 1), strideB, out.data_ptr<float>(), stream_of(out));
+  const int st = mi_sddmm_csr_batched_f32(a.offsets, a.columns, nnzA, a.batch, a.rows, a.cols, (int32_t)N, dCc.data_ptr<float>(),
+                                          ld1(N), A_rows * N, b.first.data_ptr<float>(), ld1(N), b.second, out.data_ptr<float>(),
+                                          stream_of(out));
   if (st == 1) return false;
   check_status(st, what);
   return true;
@@ -496,29 +390,26 @@ bool sddmm_batched(torch::Tensor A_columns, torch::Tensor A_offsets, int64_t nnz
 // out[p] = <dC[row(p), :], B[col[p], :]> on A's pattern: d(A·B)/d(A values).
 torch::Tensor sddmm(torch::Tensor A_columns, torch::Tensor A_offsets, int64_t nnzA, int64_t A_rows,
                     int64_t A_cols, torch::Tensor dC, torch::Tensor B) {
-  if (lowp_operands({&dC, &B})) return sddmm_lowp(A_columns, A_offsets, nnzA, A_rows, A_cols, dC, B);
   const char* what = "sddmm";
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_device_f32(dC, "dC");
-  check_device_f32(B, "B");
-  check_same_device(A_columns, dC, what);
-  check_same_device(A_offsets, dC, what);
-  check_same_device(B, dC, what);
-  TORCH_CHECK(A_columns.is_contiguous() && A_offsets.is_contiguous(), what, ": CSR arrays must be contiguous");
-  TORCH_CHECK(A_offsets.numel() == A_rows + 1 && A_columns.numel() >= nnzA, what, ": CSR array sizes do not match");
+  const torch::ScalarType dt = value_dtype(what, {{"dC", &dC}, {"B", &B}}, true);
+  const Csr a = csr_arrays(what, nullptr, &A_columns, A_offsets, nnzA, A_rows, A_cols);
+  check_same_device(what, a.device, {&dC, &B});
   TORCH_CHECK(dC.dim() == 2 && B.dim() == 2 && dC.size(0) == A_rows && B.size(0) == A_cols &&
                   dC.size(1) == B.size(1),
               what, ": dC must be [A_rows, N] and B [A_cols, N]");
+  const int64_t N = B.size(1);
+  check_sizes(what, {N});
   torch::Tensor dCc = dC.contiguous(), Bc = B.contiguous();
-  const int64_t N = Bc.size(1);
   c10::hip::HIPGuard guard(dC.device().index());
   torch::Tensor out = torch::empty({nnzA}, dCc.options());
-  check_status(mi_sddmm_csr_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(), nnzA,
-                                (int32_t)A_rows, (int32_t)A_cols, (int32_t)N, dCc.data_ptr<float>(),
-                                std::max<int64_t>(N, 1), Bc.data_ptr<float>(), std::max<int64_t>(N, 1),
-                                out.data_ptr<float>(), stream_of(dCc)),
-               what);
+  const int st =
+      dt == torch::kFloat32
+          ? mi_sddmm_csr_f32(a.offsets, a.columns, nnzA, a.rows, a.cols, (int32_t)N, dCc.data_ptr<float>(), ld1(N),
+                             Bc.data_ptr<float>(), ld1(N), out.data_ptr<float>(), stream_of(dCc))
+          : (dt == torch::kBFloat16 ? mi_sddmm_csr_bf16 : mi_sddmm_csr_f16)(
+                a.offsets, a.columns, nnzA, a.rows, a.cols, (int32_t)N, static_cast<const uint16_t*>(dCc.data_ptr()), ld1(N),
+                static_cast<const uint16_t*>(Bc.data_ptr()), ld1(N), static_cast<uint16_t*>(out.data_ptr()), stream_of(dCc));
+  check_status(st, what);
   return out;
 }
 

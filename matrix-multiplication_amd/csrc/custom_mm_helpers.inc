@@ -20,9 +20,123 @@ void check_device_i32(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be int32, got ", t.scalar_type());
 }
 
-void check_same_device(const torch::Tensor& a, const torch::Tensor& b, const char* what) {
-  TORCH_CHECK(a.device() == b.device(), what, ": tensors are on different devices (", a.device(),
-              " vs ", b.device(), ")");
+void check_same_device(const char* what, const torch::Device& dev, std::initializer_list<const torch::Tensor*> ts) {
+  for (const torch::Tensor* t : ts)
+    TORCH_CHECK(t->device() == dev, what, ": tensors are on different devices (", t->device(), " vs ", dev, ")");
+}
+
+// Sizes the C-ABI takes as int32_t; nnz (an int64_t there) only has to be non-negative.
+void check_sizes(const char* what, std::initializer_list<int64_t> int32_sizes, int64_t nnz = 0) {
+  bool negative = nnz < 0, too_large = false;
+  for (const int64_t v : int32_sizes) {
+    negative = negative || v < 0;
+    too_large = too_large || v > INT32_MAX;
+  }
+  TORCH_CHECK(!negative, what, ": negative size");
+  TORCH_CHECK(!too_large, what, ": dimension too large for the int32 sizes of the C-ABI");
+}
+
+int64_t ld1(int64_t n) { return std::max<int64_t>(n, 1); }
+
+bool is_lowp(torch::ScalarType t) { return t == torch::kBFloat16 || t == torch::kHalf; }
+
+// The dtype of an entry point's value operands: one dtype for all of them (checked first, so that mixed dtypes are named
+// even for host tensors), then the device (no CPU path), then the dtype itself — float32, or with `lowp` also bfloat16 /
+// float16.
+using Named = std::pair<const char*, const torch::Tensor*>;
+torch::ScalarType value_dtype(const char* what, std::initializer_list<Named> ts, bool lowp = false) {
+  const Named& first = *ts.begin();
+  const torch::ScalarType dt = first.second->scalar_type();
+  for (const Named& nt : ts)
+    TORCH_CHECK(nt.second->scalar_type() == dt, what, ": ", first.first, " is ", dt, " but ", nt.first, " is ",
+                nt.second->scalar_type(), ": all operands must share one dtype (",
+                lowp ? "float32, bfloat16 or float16" : "float32", ")");
+  for (const Named& nt : ts)
+    TORCH_CHECK(nt.second->is_cuda(), nt.first, " must be a device (HIP) tensor; custom_mm has no CPU path");
+  TORCH_CHECK(dt == torch::kFloat32 || (lowp && is_lowp(dt)), first.first, " must be float32",
+              lowp ? ", bfloat16 or float16" : "", ", got ", dt);
+  return dt;
+}
+
+// A CSR matrix (or, given `batch`, that many: offsets [batch, rows + 1], global over the batch) as the C-ABI takes it:
+// pointers, int32 sizes, the device.  `values` may be null (a pattern) and has passed value_dtype; `columns` may be null
+// where the callee reads the offsets only; `perm` (int32) indexes the values.  One check order, one set of messages.
+struct CsrNames {
+  const char *values = "A_values", *columns = "A_columns", *offsets = "A_offsets";
+};
+struct Csr {
+  const int32_t* offsets;
+  const int32_t* columns;
+  const void* values;
+  const int32_t* perm;
+  int64_t nnz;
+  int32_t rows, cols, batch;
+  torch::Device device;
+  const float* f32() const { return static_cast<const float*>(values); }
+  const uint16_t* b16() const { return static_cast<const uint16_t*>(values); }
+};
+Csr csr_arrays(const char* what, const torch::Tensor* values, const torch::Tensor* columns, const torch::Tensor& offsets,
+               int64_t nnz, int64_t rows, int64_t cols, c10::optional<int64_t> batch = c10::nullopt,
+               const torch::Tensor* perm = nullptr,
+               const CsrNames& names = CsrNames()) {
+  if (columns != nullptr) check_device_i32(*columns, names.columns);
+  check_device_i32(offsets, names.offsets);
+  if (perm != nullptr) check_device_i32(*perm, "perm");
+  const torch::Device dev = offsets.device();
+  for (const torch::Tensor* t : {values, columns, perm})
+    if (t != nullptr) check_same_device(what, dev, {t});
+  check_sizes(what, {rows, cols, batch.value_or(0)}, nnz);
+  bool contiguous = offsets.is_contiguous(), holds_nnz = true;
+  for (const torch::Tensor* t : {values, columns, perm})
+    if (t != nullptr) {
+      contiguous = contiguous && t->is_contiguous();
+      holds_nnz = holds_nnz && t->numel() >= nnz;
+    }
+  TORCH_CHECK(contiguous, what, ": CSR arrays must be contiguous");
+  TORCH_CHECK(holds_nnz, what, ": nnzA exceeds the CSR arrays");
+  const int64_t entries = batch.value_or(1) * (rows + 1);
+  TORCH_CHECK(offsets.numel() == entries, what, ": ", names.offsets, " must have ", batch ? "batch · " : "",
+              "(A_rows + 1) = ", entries, " entries, got ", offsets.numel());
+  return Csr{offsets.data_ptr<int32_t>(), columns != nullptr ? columns->data_ptr<int32_t>() : nullptr,
+             values != nullptr ? values->data_ptr() : nullptr, perm != nullptr ? perm->data_ptr<int32_t>() : nullptr,
+             nnz, (int32_t)rows, (int32_t)cols, (int32_t)batch.value_or(1), dev};
+}
+
+// B [K, N] of a row-major product: a row-major view with any leading dimension (column-offset views included) is taken
+// as it is, anything else copied.
+struct RowMajorB {
+  torch::Tensor keep;
+  int64_t ld;
+};
+RowMajorB row_major_b(const torch::Tensor& B) {
+  const int64_t N = B.size(1);
+  torch::Tensor Bc = (B.stride(1) == 1 || N == 1) && (B.stride(0) >= N || B.size(0) <= 1) ? B : B.contiguous();
+  return {Bc, Bc.size(0) > 1 ? Bc.stride(0) : ld1(N)};
+}
+
+// B of a batched product: [batch, K, N] (one per item) or [K, N] (shared by every item), contiguous, and its item stride.
+std::pair<torch::Tensor, int64_t> batched_b(const char* what, const torch::Tensor& B, int64_t batch, int64_t K, int64_t N) {
+  if (B.dim() == 3) {
+    TORCH_CHECK(B.size(0) == batch && B.size(1) == K && B.size(2) == N, what, ": B must be [batch, A_cols, N]");
+    return {B.contiguous(), K * N};
+  }
+  TORCH_CHECK(B.dim() == 2 && B.size(0) == K && B.size(1) == N, what, ": B must be [A_cols, N]");
+  return {B.contiguous(), 0};
+}
+
+// The float32 bias [N] of a fused epilogue, contiguous (undefined when there is none).
+torch::Tensor bias_of(const char* what, const torch::Tensor* bias, int64_t N, const torch::Tensor& C) {
+  if (bias == nullptr || !bias->defined()) return torch::Tensor();
+  check_device_f32(*bias, "bias");
+  check_same_device(what, C.device(), {bias});
+  TORCH_CHECK(bias->dim() == 1 && bias->size(0) == N, what, ": bias must have ", N, " entries");
+  return bias->contiguous();
+}
+const float* f32_or_null(const torch::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
+
+// A device byte buffer of at least `min_bytes` (C-ABI workspaces; some entries want a non-null pointer even for 0 bytes).
+torch::Tensor byte_workspace(const torch::Device& dev, size_t bytes, size_t min_bytes = 0) {
+  return torch::empty({(int64_t)std::max(bytes, min_bytes)}, torch::dtype(torch::kUInt8).device(dev));
 }
 
 mi_stream_t stream_of(const torch::Tensor& t) {
@@ -107,8 +221,7 @@ torch::Tensor gemm_impl(const torch::Tensor& A, const torch::Tensor& B, torch::T
   check_device_f32(A, "A");
   check_device_f32(B, "B");
   check_device_f32(C, "C");
-  check_same_device(A, B, what);
-  check_same_device(A, C, what);
+  check_same_device(what, C.device(), {&A, &B});
   TORCH_CHECK(C.is_contiguous(), what, ": C must be contiguous");
   TORCH_CHECK(C.dim() == nbatch_dims + 2, what, ": C has the wrong rank");
   for (int i = 0; i < nbatch_dims; ++i)
@@ -121,26 +234,18 @@ torch::Tensor gemm_impl(const torch::Tensor& A, const torch::Tensor& B, torch::T
   TORCH_CHECK(ka == kb, what, ": inner dimensions differ (", ka, " vs ", kb, ")");
   TORCH_CHECK(C.size(-2) == m && C.size(-1) == n, what, ": C must be ", m, "x", n, ", got ",
               C.size(-2), "x", C.size(-1));
-  TORCH_CHECK(m <= INT32_MAX && n <= INT32_MAX && ka <= INT32_MAX, what, ": dimension too large");
   const int64_t batch = batch_count(C, nbatch_dims);
-  const float* bias_ptr = nullptr;
-  torch::Tensor bias_keep;
-  if (bias != nullptr && bias->defined()) {
-    check_device_f32(*bias, "bias");
-    check_same_device(*bias, C, what);
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == n, what, ": bias must have ", n, " entries");
-    bias_keep = bias->contiguous();
-    bias_ptr = bias_keep.data_ptr<float>();
-  }
+  check_sizes(what, {m, n, ka, batch});
+  const torch::Tensor bias_keep = bias_of(what, bias, n, C);
   c10::hip::HIPGuard guard(C.device().index());
   // few output tiles and a long k: the fixed split of include/mi_spmm.h ("Deterministic split-k") needs room for its partial sums
   const size_t ws_bytes = mi_gemm_workspace_bytes((int32_t)m, (int32_t)n, (int32_t)ka, (int32_t)batch);
   torch::Tensor ws;
-  if (ws_bytes > 0) ws = torch::empty({(int64_t)ws_bytes}, torch::dtype(torch::kUInt8).device(C.device()));
+  if (ws_bytes > 0) ws = byte_workspace(C.device(), ws_bytes);
   const int st = mi_gemm_ws_f32(transa != a.stored_transposed, transb != b.stored_transposed,
                                 (int32_t)m, (int32_t)n, (int32_t)ka, a.ptr, a.ld, a.batch_stride,
-                                b.ptr, b.ld, b.batch_stride, bias_ptr, C.data_ptr<float>(),
-                                std::max<int64_t>(n, 1), m * n, (int32_t)batch, ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes,
+                                b.ptr, b.ld, b.batch_stride, f32_or_null(bias_keep), C.data_ptr<float>(),
+                                ld1(n), m * n, (int32_t)batch, ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes,
                                 stream_of(C));
   check_status(st, what);
   return C;

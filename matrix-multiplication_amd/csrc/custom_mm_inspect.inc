@@ -45,18 +45,19 @@ void prepare_side(CsrSide& side, int64_t nnz, int64_t N, const char* what) {
   if (side.rows > 1 && nnz > 0 && N > 0) side.sched = make_schedule(side.rowptr, nnz, side.rows, N, false, what, &side.col, side.cols);
   if (side.max_row > mi_spmm_long_row_threshold() && N > 0) {
     const size_t bytes = mi_spmm_csr_workspace_bytes(nnz, (int32_t)N);
-    side.long_ws = torch::empty({(int64_t)bytes}, torch::dtype(torch::kUInt8).device(side.val.device()));
+    side.long_ws = byte_workspace(side.val.device(), bytes);
     check_status(mi_spmm_long_rows_prepare(side.rowptr.data_ptr<int32_t>(), (int32_t)side.rows, nnz, (int32_t)N,
                                            side.long_ws.data_ptr(), bytes, stream_of(side.val)),
                  what);
   }
 }
 
-// Shared inspector: device CSR (already int32 / float32, contiguous) → a complete handle.
+// Shared inspector: device CSR → a complete handle.
 CsrHandle build_handle(int64_t M, int64_t K, int64_t N, int64_t nnz, torch::Tensor rowptr, torch::Tensor col,
                        torch::Tensor val, const char* what) {
-  check_same_device(rowptr, val, what);
-  check_same_device(col, val, what);
+  value_dtype(what, {{"value", &val}});
+  const Csr a = csr_arrays(what, &val, &col, rowptr, nnz, M, K, c10::nullopt, nullptr, {"value", "colindex", "displ"});
+  check_sizes(what, {N});
   c10::hip::HIPGuard guard(val.device().index());
   // validate once what every later product trusts (the kernels index B with these columns)
   if (M > 0) {
@@ -87,18 +88,16 @@ CsrHandle build_handle(int64_t M, int64_t K, int64_t N, int64_t nnz, torch::Tens
   h.at.col = torch::empty({nnz}, iopt);
   h.at.val = torch::empty({nnz}, val.options());
   {
-    const size_t bytes = mi_csr_transpose_workspace_bytes((int32_t)M, (int32_t)K, nnz);
-    torch::Tensor tws = torch::empty({(int64_t)std::max<size_t>(bytes, 1)}, torch::dtype(torch::kUInt8).device(val.device()));
-    check_status(mi_csr_transpose_f32(h.a.rowptr.data_ptr<int32_t>(), h.a.col.data_ptr<int32_t>(), h.a.val.data_ptr<float>(),
-                                      nnz, (int32_t)M, (int32_t)K, h.at.rowptr.data_ptr<int32_t>(),
+    const size_t bytes = mi_csr_transpose_workspace_bytes(a.rows, a.cols, nnz);
+    torch::Tensor tws = byte_workspace(a.device, bytes, 1);
+    check_status(mi_csr_transpose_f32(a.offsets, a.columns, a.f32(), nnz, a.rows, a.cols, h.at.rowptr.data_ptr<int32_t>(),
                                       h.at.col.data_ptr<int32_t>(), h.at.val.data_ptr<float>(), tws.data_ptr(), bytes,
                                       stream_of(val)),
                  what);
   }
   prepare_side(h.a, nnz, N, what);
   prepare_side(h.at, nnz, N, what);
-  const size_t ws_bytes = mi_spmm_colmajor_workspace_bytes((int32_t)M, (int32_t)K, (int32_t)N);
-  h.ws = torch::empty({(int64_t)std::max<size_t>(ws_bytes, 16)}, torch::dtype(torch::kUInt8).device(val.device()));
+  h.ws = byte_workspace(a.device, mi_spmm_colmajor_workspace_bytes(a.rows, a.cols, (int32_t)N), 16);
   return h;
 }
 
@@ -107,10 +106,8 @@ CsrHandle build_handle(int64_t M, int64_t K, int64_t N, int64_t nnz, torch::Tens
 // right element count are accepted, as in the reference (raw data_ptr()).
 void colmajor_mm(const CsrHandle& h, bool transposed, const torch::Tensor& B, torch::Tensor& C, const char* what) {
   const CsrSide& s = transposed ? h.at : h.a;
-  check_device_f32(B, "B");
-  check_device_f32(C, "C");
-  check_same_device(B, C, what);
-  check_same_device(s.val, C, what);
+  value_dtype(what, {{"B", &B}, {"C", &C}});
+  check_same_device(what, s.val.device(), {&B, &C});
   TORCH_CHECK(B.is_contiguous() && C.is_contiguous(), what, ": B and C must be contiguous");
   TORCH_CHECK(B.numel() == s.cols * h.N, what, ": B must hold ", s.cols * h.N, " elements, got ", B.numel());
   TORCH_CHECK(C.numel() == s.rows * h.N, what, ": C must hold ", s.rows * h.N, " elements, got ", C.numel());
@@ -144,12 +141,6 @@ const CsrHandle& lookup(const std::unordered_map<std::string, CsrHandle>& reg,
 // A is M×K, dense operand width N (custom_mm.cpp:266-267 passes M, K, then K, N).
 void cusparse_inspect(torch::Tensor displ, torch::Tensor colindex, torch::Tensor value, int nnz,
                       int M, int N, int K, std::string layer) {
-  check_device_i32(displ, "displ");
-  check_device_i32(colindex, "colindex");
-  check_device_f32(value, "value");
-  TORCH_CHECK(M >= 0 && N >= 0 && K >= 0 && nnz >= 0, "cusparse_inspect: negative size");
-  TORCH_CHECK(displ.numel() == (int64_t)M + 1, "cusparse_inspect: displ must have M + 1 entries");
-  TORCH_CHECK(colindex.numel() >= nnz && value.numel() >= nnz, "cusparse_inspect: nnz exceeds the CSR arrays");
   CsrHandle h = build_handle(M, K, N, nnz, displ.contiguous(), colindex.contiguous(), value.contiguous(), "cusparse_inspect");
   std::lock_guard<std::mutex> lock(g_registry_mutex);
   g_cusparse_layers[layer] = std::move(h);
@@ -228,7 +219,7 @@ void tiledspmm_inspect_csr(int M, int N, int K, torch::Tensor displ, torch::Tens
   check_host(displ, torch::kInt64, "displ");
   check_host(colindex, torch::kInt64, "colindex");
   check_host(value, torch::kFloat32, "value");
-  TORCH_CHECK(M >= 0 && N >= 0 && K >= 0, "tiledspmm_inspect_csr: negative size");
+  check_sizes("tiledspmm_inspect_csr", {M, N, K});
   TORCH_CHECK(displ.numel() == (int64_t)M + 1, "tiledspmm_inspect_csr: displ must have M + 1 entries");
   torch::Tensor d = displ.contiguous(), c = colindex.contiguous(), v = value.contiguous();
   const int64_t nnz = M > 0 ? d.data_ptr<int64_t>()[M] : 0;
@@ -249,7 +240,7 @@ void tiledspmm_inspect_coo(int M, int N, int K, int64_t nnz, torch::Tensor rowid
   check_host(rowidx, torch::kInt32, "rowidx");
   check_host(colidx, torch::kInt32, "colidx");
   check_host(value, torch::kFloat32, "value");
-  TORCH_CHECK(M >= 0 && N >= 0 && K >= 0 && nnz >= 0, "tiledspmm_inspect_coo: negative size");
+  check_sizes("tiledspmm_inspect_coo", {M, N, K}, nnz);
   TORCH_CHECK(rowidx.numel() >= nnz && colidx.numel() >= nnz && value.numel() >= nnz,
               "tiledspmm_inspect_coo: nnz exceeds the COO arrays");
   torch::Tensor r = rowidx.contiguous(), c = colidx.contiguous(), v = value.contiguous();

@@ -31,30 +31,18 @@ torch::Tensor naive_spmm_reduce(torch::Tensor A_values, torch::Tensor A_columns,
     }
     return C;
   }
-  check_device_f32(A_values, "A_values");
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_device_f32(B, "B");
-  check_device_f32(C, "C");
-  check_same_device(A_values, C, what);
-  check_same_device(A_columns, C, what);
-  check_same_device(A_offsets, C, what);
-  check_same_device(B, C, what);
-  TORCH_CHECK(A_rows >= 0 && A_cols >= 0 && nnzA >= 0, what, ": negative size");
-  TORCH_CHECK(A_rows <= INT32_MAX && A_cols <= INT32_MAX, what, ": dimension too large");
-  TORCH_CHECK(A_values.is_contiguous() && A_columns.is_contiguous() && A_offsets.is_contiguous(), what,
-              ": CSR arrays must be contiguous");
-  TORCH_CHECK(A_values.numel() >= nnzA && A_columns.numel() >= nnzA, what, ": nnzA exceeds the CSR arrays");
-  TORCH_CHECK(A_offsets.numel() == A_rows + 1, what, ": A_offsets must have A_rows + 1 entries");
+  value_dtype(what, {{"A_values", &A_values}, {"B", &B}, {"C", &C}});
+  const Csr a = csr_arrays(what, &A_values, &A_columns, A_offsets, nnzA, A_rows, A_cols);
+  check_same_device(what, a.device, {&B, &C});
   TORCH_CHECK(B.dim() == 2 && C.dim() == 2 && B.size(0) == A_cols && C.size(0) == A_rows && C.size(1) == B.size(1), what,
               ": B must be [A_cols, N] and C [A_rows, N]");
   TORCH_CHECK(C.is_contiguous(), what, ": C must be contiguous");
   const int64_t N = B.size(1);
-  TORCH_CHECK(N <= INT32_MAX, what, ": N too large");
+  check_sizes(what, {N});
   int32_t* arg_ptr = nullptr;
   if (arg.has_value() && arg->defined()) {
     check_device_i32(*arg, "arg");
-    check_same_device(*arg, C, what);
+    check_same_device(what, C.device(), {&*arg});
     TORCH_CHECK(arg->dim() == 2 && arg->size(0) == A_rows && arg->size(1) == N && arg->is_contiguous(), what,
                 ": arg must be a contiguous int32 [A_rows, N]");
     arg_ptr = arg->data_ptr<int32_t>();
@@ -64,12 +52,11 @@ torch::Tensor naive_spmm_reduce(torch::Tensor A_values, torch::Tensor A_columns,
   // the hub-row list and partial rows (a fresh block of the caching allocator: capturable; the entry zeroes its header)
   torch::Tensor ws;
   if (nnzA > mi_spmm_long_row_threshold() && N > 0)
-    ws = torch::empty({(int64_t)mi_spmm_csr_reduce_workspace_bytes(nnzA, (int32_t)N)}, torch::dtype(torch::kUInt8).device(C.device()));
-  check_status(mi_spmm_csr_reduce_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(), A_values.data_ptr<float>(),
-                                      nnzA, (int32_t)A_rows, (int32_t)A_cols, (int32_t)N, Bc.data_ptr<float>(),
-                                      std::max<int64_t>(N, 1), C.data_ptr<float>(), std::max<int64_t>(N, 1), arg_ptr,
-                                      std::max<int64_t>(N, 1), code, ws.defined() ? ws.data_ptr() : nullptr,
-                                      ws.defined() ? (size_t)ws.numel() : 0, stream_of(C)),
+    ws = byte_workspace(C.device(), mi_spmm_csr_reduce_workspace_bytes(nnzA, (int32_t)N));
+  check_status(mi_spmm_csr_reduce_f32(a.offsets, a.columns, a.f32(), nnzA, a.rows, a.cols, (int32_t)N, Bc.data_ptr<float>(),
+                                      ld1(N), C.data_ptr<float>(), ld1(N), arg_ptr, ld1(N), code,
+                                      ws.defined() ? ws.data_ptr() : nullptr, ws.defined() ? (size_t)ws.numel() : 0,
+                                      stream_of(C)),
                what);
   return C;
 }
@@ -77,18 +64,16 @@ torch::Tensor naive_spmm_reduce(torch::Tensor A_values, torch::Tensor A_columns,
 // out = in / count(row) per row (rows without entries copied); out may be in.
 torch::Tensor spmm_rows_divide(torch::Tensor A_offsets, int64_t A_rows, torch::Tensor in, torch::Tensor out) {
   const char* what = "spmm_rows_divide";
-  check_device_i32(A_offsets, "A_offsets");
-  check_device_f32(in, "in");
-  check_device_f32(out, "out");
-  check_same_device(A_offsets, out, what);
-  check_same_device(in, out, what);
-  TORCH_CHECK(A_offsets.is_contiguous() && A_offsets.numel() == A_rows + 1, what, ": A_offsets must have A_rows + 1 entries");
+  value_dtype(what, {{"in", &in}, {"out", &out}});
+  const Csr a = csr_arrays(what, nullptr, nullptr, A_offsets, 0, A_rows, 0);
+  check_same_device(what, a.device, {&in, &out});
   TORCH_CHECK(in.dim() == 2 && in.size(0) == A_rows && out.sizes() == in.sizes(), what, ": in and out must be [A_rows, N]");
   TORCH_CHECK(in.is_contiguous() && out.is_contiguous(), what, ": in and out must be contiguous");
-  c10::hip::HIPGuard guard(out.device().index());
   const int64_t N = in.size(1);
-  check_status(mi_spmm_rows_divide_f32(A_offsets.data_ptr<int32_t>(), (int32_t)A_rows, (int32_t)N, in.data_ptr<float>(),
-                                       std::max<int64_t>(N, 1), out.data_ptr<float>(), std::max<int64_t>(N, 1), stream_of(out)),
+  check_sizes(what, {N});
+  c10::hip::HIPGuard guard(out.device().index());
+  check_status(mi_spmm_rows_divide_f32(a.offsets, a.rows, (int32_t)N, in.data_ptr<float>(), ld1(N), out.data_ptr<float>(), ld1(N),
+                                       stream_of(out)),
                what);
   return out;
 }
@@ -97,29 +82,21 @@ torch::Tensor spmm_rows_divide(torch::Tensor A_offsets, int64_t A_rows, torch::T
 torch::Tensor spmm_reduce_grad_val(torch::Tensor A_columns, torch::Tensor A_offsets, int64_t nnzA, int64_t A_rows,
                                    int64_t A_cols, torch::Tensor B, torch::Tensor G, torch::Tensor arg) {
   const char* what = "spmm_reduce_grad_val";
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_device_f32(B, "B");
-  check_device_f32(G, "G");
+  value_dtype(what, {{"B", &B}, {"G", &G}});
+  const Csr a = csr_arrays(what, nullptr, &A_columns, A_offsets, nnzA, A_rows, A_cols);
   check_device_i32(arg, "arg");
-  check_same_device(A_columns, G, what);
-  check_same_device(A_offsets, G, what);
-  check_same_device(B, G, what);
-  check_same_device(arg, G, what);
-  TORCH_CHECK(A_columns.is_contiguous() && A_offsets.is_contiguous() && A_offsets.numel() == A_rows + 1 &&
-                  A_columns.numel() >= nnzA,
-              what, ": CSR array sizes do not match");
+  check_same_device(what, a.device, {&B, &G, &arg});
   TORCH_CHECK(G.dim() == 2 && B.dim() == 2 && G.size(0) == A_rows && B.size(0) == A_cols && G.size(1) == B.size(1) &&
                   arg.sizes() == G.sizes() && arg.is_contiguous(),
               what, ": G and arg must be [A_rows, N] and B [A_cols, N]");
+  const int64_t N = B.size(1);
+  check_sizes(what, {N});
   torch::Tensor Gc = G.contiguous(), Bc = B.contiguous();
-  const int64_t N = Bc.size(1);
   c10::hip::HIPGuard guard(G.device().index());
   torch::Tensor out = torch::empty({nnzA}, Gc.options());
-  check_status(mi_spmm_reduce_grad_val_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(), nnzA, (int32_t)A_rows,
-                                           (int32_t)A_cols, (int32_t)N, Bc.data_ptr<float>(), std::max<int64_t>(N, 1),
-                                           Gc.data_ptr<float>(), std::max<int64_t>(N, 1), arg.data_ptr<int32_t>(),
-                                           std::max<int64_t>(N, 1), out.data_ptr<float>(), stream_of(Gc)),
+  check_status(mi_spmm_reduce_grad_val_f32(a.offsets, a.columns, nnzA, a.rows, a.cols, (int32_t)N, Bc.data_ptr<float>(), ld1(N),
+                                           Gc.data_ptr<float>(), ld1(N), arg.data_ptr<int32_t>(), ld1(N), out.data_ptr<float>(),
+                                           stream_of(Gc)),
                what);
   return out;
 }
@@ -129,28 +106,22 @@ torch::Tensor spmm_reduce_grad_val(torch::Tensor A_columns, torch::Tensor A_offs
 torch::Tensor spmm_reduce_grad_b(torch::Tensor t_offsets, torch::Tensor t_columns, torch::Tensor perm, torch::Tensor A_values,
                                  int64_t nnzA, int64_t A_rows, int64_t A_cols, torch::Tensor G, torch::Tensor arg) {
   const char* what = "spmm_reduce_grad_b";
-  check_device_i32(t_offsets, "t_offsets");
-  check_device_i32(t_columns, "t_columns");
-  check_device_i32(perm, "perm");
-  check_device_f32(A_values, "A_values");
-  check_device_f32(G, "G");
+  value_dtype(what, {{"A_values", &A_values}, {"G", &G}});
+  // the CSR of Aᵀ (A_cols × A_rows) with A's values read through perm
+  const Csr t = csr_arrays(what, &A_values, &t_columns, t_offsets, nnzA, A_cols, A_rows, c10::nullopt, &perm,
+                           {"A_values", "t_columns", "t_offsets"});
   check_device_i32(arg, "arg");
-  for (const torch::Tensor* t : {&t_offsets, &t_columns, &perm, &A_values, &arg}) check_same_device(*t, G, what);
-  TORCH_CHECK(t_offsets.is_contiguous() && t_columns.is_contiguous() && perm.is_contiguous() && A_values.is_contiguous() &&
-                  t_offsets.numel() == A_cols + 1 && t_columns.numel() >= nnzA && perm.numel() >= nnzA &&
-                  A_values.numel() >= nnzA,
-              what, ": CSR array sizes do not match");
+  check_same_device(what, t.device, {&G, &arg});
   TORCH_CHECK(G.dim() == 2 && G.size(0) == A_rows && arg.sizes() == G.sizes() && arg.is_contiguous(), what,
               ": G and arg must be [A_rows, N]");
+  const int64_t N = G.size(1);
+  check_sizes(what, {N});
   torch::Tensor Gc = G.contiguous();
-  const int64_t N = Gc.size(1);
   c10::hip::HIPGuard guard(G.device().index());
   torch::Tensor out = torch::empty({A_cols, N}, Gc.options());
-  check_status(mi_spmm_reduce_grad_b_f32(t_offsets.data_ptr<int32_t>(), t_columns.data_ptr<int32_t>(), perm.data_ptr<int32_t>(),
-                                         A_values.data_ptr<float>(), nnzA, (int32_t)A_rows, (int32_t)A_cols, (int32_t)N,
-                                         Gc.data_ptr<float>(), std::max<int64_t>(N, 1), arg.data_ptr<int32_t>(),
-                                         std::max<int64_t>(N, 1), out.data_ptr<float>(), std::max<int64_t>(N, 1),
-                                         stream_of(Gc)),
+  check_status(mi_spmm_reduce_grad_b_f32(t.offsets, t.columns, t.perm, t.f32(), nnzA, t.cols, t.rows, (int32_t)N,
+                                         Gc.data_ptr<float>(), ld1(N), arg.data_ptr<int32_t>(), ld1(N), out.data_ptr<float>(),
+                                         ld1(N), stream_of(Gc)),
                what);
   return out;
 }

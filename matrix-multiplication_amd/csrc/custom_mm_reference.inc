@@ -56,6 +56,13 @@ void drop_stream_workspace(const torch::Device& dev, mi_stream_t stream) {
   g_stream_ws.erase(std::make_pair((int)dev.index(), stream));
 }
 
+// mi_spmm_schedule_info (include/mi_spmm.h) as an array
+std::array<int64_t, MI_SPMM_SCHEDULE_INFO_LEN> schedule_info(const mi_spmm_schedule_t* sc, const char* what) {
+  std::array<int64_t, MI_SPMM_SCHEDULE_INFO_LEN> v{};
+  check_status(mi_spmm_schedule_info(sc, v.data()), what);
+  return v;
+}
+
 // ---- row schedules (include/mi_spmm.h "Row schedules": the inspector's format for degree-skewed matrices) --------------------
 // One per matrix (per CSR pattern): the order in which rows are handed to waves — longest first, like lengths together,
 // the heavy rows in a launch of their own.  Same bits as the unscheduled entry points.  Products on one schedule must be
@@ -72,8 +79,7 @@ struct PySchedule {
   int64_t long_rows = -1;  // rows beyond the long-row threshold (counted when the list was prepared; -1: not looked at)
   ~PySchedule() { mi_spmm_schedule_destroy(sc); }
   py::dict info() const {
-    int64_t v[12] = {0};
-    check_status(mi_spmm_schedule_info(sc, v), "SpmmSchedule.info");
+    const auto v = schedule_info(sc, "SpmmSchedule.info");
     py::dict d;
     d["rows"] = v[0];
     d["heavy_rows"] = v[1];
@@ -167,8 +173,7 @@ std::shared_ptr<PySchedule> auto_schedule(const torch::Tensor& A_offsets, const 
       e.failed = true;
       return nullptr;
     }
-    int64_t v[12] = {0};
-    (void)mi_spmm_schedule_info(out->sc, v);
+    const auto v = schedule_info(out->sc, "auto_schedule");
     out->rows = A_rows;
     out->nnz = nnzA;
     out->order_keep = e.order_buf;
@@ -186,8 +191,7 @@ std::shared_ptr<PySchedule> auto_schedule(const torch::Tensor& A_offsets, const 
     try {
       auto iopt = torch::dtype(torch::kInt32).device(A_offsets.device());
       e.order_buf = torch::empty({2 * A_rows}, iopt);
-      const size_t ws_bytes = mi_spmm_schedule_workspace_bytes((int32_t)A_rows);
-      e.ws = torch::empty({(int64_t)ws_bytes}, torch::dtype(torch::kUInt8).device(A_offsets.device()));
+      e.ws = byte_workspace(A_offsets.device(), mi_spmm_schedule_workspace_bytes((int32_t)A_rows));
       e.host = torch::empty({MI_SCHEDULE_HOST_INTS}, torch::dtype(torch::kInt32).pinned_memory(true));
       e.pending = true;  // (the launch itself happens in auto_schedule_launch, after the product)
     } catch (...) {
@@ -254,106 +258,90 @@ void auto_schedule_clear() {
   g_auto.clear();
 }
 
+// C = A·B (+ bias) for A in CSR.  float32, or with `lowp` bfloat16 / float16 (C-ABI low-precision section: fp32 sums,
+// one rounding at the store; no bias, row schedules or variants there).
 torch::Tensor spmm_impl(const torch::Tensor& A_values, const torch::Tensor& A_columns,
                         const torch::Tensor& A_offsets, int64_t nnzA, int64_t A_rows,
                         int64_t A_cols, const torch::Tensor& B, torch::Tensor C, const char* what,
                         const torch::Tensor* bias = nullptr, int long_rows = MI_LONG_ROWS_AUTO,
-                        const PySchedule* schedule = nullptr, int variant = MI_SPMM_AUTO, bool allow_auto = false) {
-  check_device_f32(A_values, "A_values");
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_device_f32(B, "B");
-  check_device_f32(C, "C");
-  check_same_device(A_values, C, what);
-  check_same_device(A_columns, C, what);
-  check_same_device(A_offsets, C, what);
-  check_same_device(B, C, what);
-  TORCH_CHECK(A_rows >= 0 && A_cols >= 0 && nnzA >= 0, what, ": negative size");
-  TORCH_CHECK(A_rows <= INT32_MAX && A_cols <= INT32_MAX, what, ": dimension too large");
-  TORCH_CHECK(A_values.is_contiguous() && A_columns.is_contiguous() && A_offsets.is_contiguous(),
-              what, ": CSR arrays must be contiguous");
-  TORCH_CHECK(A_values.numel() >= nnzA && A_columns.numel() >= nnzA, what,
-              ": nnzA exceeds the CSR arrays");
-  TORCH_CHECK(A_offsets.numel() == A_rows + 1, what, ": A_offsets must have A_rows + 1 entries");
+                        const PySchedule* schedule = nullptr, int variant = MI_SPMM_AUTO, bool allow_auto = false,
+                        bool lowp = false) {
+  const torch::ScalarType dt = value_dtype(what, {{"A_values", &A_values}, {"B", &B}, {"C", &C}}, lowp);
+  const Csr a = csr_arrays(what, &A_values, &A_columns, A_offsets, nnzA, A_rows, A_cols);
+  check_same_device(what, a.device, {&B, &C});
   TORCH_CHECK(B.dim() == 2 && C.dim() == 2, what, ": B and C must be 2-d");
   TORCH_CHECK(B.size(0) == A_cols, what, ": B must have A_cols = ", A_cols, " rows, got ", B.size(0));
   TORCH_CHECK(C.size(0) == A_rows && C.size(1) == B.size(1), what, ": C must be ", A_rows, "x",
               B.size(1));
   TORCH_CHECK(C.is_contiguous(), what, ": C must be contiguous");
-  torch::Tensor Bc = (B.stride(1) == 1 || B.size(1) == 1) && (B.stride(0) >= B.size(1) || B.size(0) <= 1)
-                         ? B
-                         : B.contiguous();
   const int64_t N = B.size(1);
-  const int64_t ldb = Bc.size(0) > 1 ? Bc.stride(0) : std::max<int64_t>(N, 1);
-  const float* bias_ptr = nullptr;
-  torch::Tensor bias_keep;
-  if (bias != nullptr && bias->defined()) {
-    check_device_f32(*bias, "bias");
-    check_same_device(*bias, C, what);
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == N, what, ": bias must have ", N, " entries");
-    bias_keep = bias->contiguous();
-    bias_ptr = bias_keep.data_ptr<float>();
-  }
+  check_sizes(what, {N});
+  const RowMajorB b = row_major_b(B);
+  const torch::Tensor bias_keep = bias_of(what, bias, N, C);
+  const bool f32 = dt == torch::kFloat32;
   c10::hip::HIPGuard guard(C.device().index());
-  // workspace for the over-long rows (list + partial rows of the split ones);
-  // none when the caller pins "no row is split" (MI_LONG_ROWS_NONE: one launch, nothing else)
-  const size_t ws_bytes = long_rows == MI_LONG_ROWS_NONE ? 0 : mi_spmm_csr_workspace_bytes(nnzA, (int32_t)N);
+  // workspace for the over-long rows (list + partial rows of the split ones); none when the caller pins "no row is split"
+  // (MI_LONG_ROWS_NONE: one launch, nothing else).  bf16 / fp16: only where a row may be split (N < 4 keeps the narrow
+  // order: never split).
+  const bool may_split = long_rows != MI_LONG_ROWS_NONE && (f32 || (N >= 4 && nnzA > mi_spmm_long_row_threshold()));
+  const size_t ws_bytes = may_split ? mi_spmm_csr_workspace_bytes(nnzA, (int32_t)N) : 0;
   torch::Tensor ws;
   int mode = long_rows;
   const mi_stream_t stream = stream_of(C);
   std::shared_ptr<PySchedule> auto_keep;  // a schedule the extension built by itself for arrays it has seen before (see auto_schedule)
-  if (allow_auto && schedule == nullptr && long_rows == MI_LONG_ROWS_AUTO) {
+  if (f32 && allow_auto && schedule == nullptr && long_rows == MI_LONG_ROWS_AUTO) {
     auto_keep = auto_schedule(A_offsets, A_columns, nnzA, A_rows, A_cols, N, stream);
     schedule = auto_keep.get();
   }
   if (ws_bytes > 0 && schedule != nullptr && long_rows == MI_LONG_ROWS_AUTO && schedule->long_ws.defined() &&
       schedule->long_ws_width == N && schedule->nnz == nnzA &&
-      mi_spmm_auto_splits_long_rows(nnzA, (int32_t)A_rows, (int32_t)A_cols, (int32_t)N, Bc.data_ptr<float>(), ldb,
-                                    C.data_ptr<float>(), std::max<int64_t>(N, 1)) == 1) {
+      mi_spmm_auto_splits_long_rows(nnzA, a.rows, a.cols, (int32_t)N, b.keep.data_ptr<float>(), b.ld,
+                                    C.data_ptr<float>(), ld1(N)) == 1) {
     ws = schedule->long_ws;  // the prepared list: the same split rule, its kernel launched first, beside the rest
     mode = MI_LONG_ROWS_PREPARED;
   } else if (ws_bytes > 0 && schedule != nullptr && schedule->long_rows == 0 && schedule->nnz == nnzA && long_rows == MI_LONG_ROWS_AUTO) {
     mode = MI_LONG_ROWS_NONE;  // the inspector counted: no row is beyond the threshold — nothing to list, nothing to follow up
   } else if (ws_bytes > 0) {
     if (long_rows == MI_LONG_ROWS_AUTO && !stream_is_capturing(stream)) {
-      // the plain entry points: one workspace per (device, stream), kept with a zero header between products, so a
-      // product is the main kernel (which lists the rows it skips) + one follow-up launch — no memset, no scan
+      // the plain entry points (every dtype): one workspace per (device, stream), kept with a zero header between products,
+      // so a product is the main kernel (which lists the rows it skips) + one follow-up launch — no memset, no scan
       ws = zeroed_stream_workspace(C.device(), stream, ws_bytes);
       mode = MI_LONG_ROWS_AUTO_ZEROED;
     } else {
-      ws = torch::empty({(int64_t)ws_bytes}, torch::dtype(torch::kUInt8).device(C.device()));  // caching allocator
+      ws = byte_workspace(C.device(), ws_bytes);  // caching allocator
     }
   }
-  const int st =
-      schedule != nullptr
-          ? mi_spmm_csr_scheduled_f32(schedule->sc, variant, A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(),
-                                      A_values.data_ptr<float>(), nnzA, (int32_t)A_rows, (int32_t)A_cols, (int32_t)N,
-                                      Bc.data_ptr<float>(), ldb, bias_ptr, C.data_ptr<float>(), std::max<int64_t>(N, 1), mode,
-                                      ws.defined() ? ws.data_ptr() : nullptr, ws.defined() ? (size_t)ws.numel() : 0, stream)
-          : mi_spmm_csr_ex_f32(A_offsets.data_ptr<int32_t>(), A_columns.data_ptr<int32_t>(),
-                               A_values.data_ptr<float>(), nnzA, (int32_t)A_rows, (int32_t)A_cols,
-                               (int32_t)N, Bc.data_ptr<float>(), ldb, bias_ptr, C.data_ptr<float>(),
-                               std::max<int64_t>(N, 1), mode, ws_bytes > 0 ? ws.data_ptr() : nullptr,
-                               ws_bytes > 0 ? (size_t)ws.numel() : 0, stream);
+  void* const ws_ptr = ws.defined() ? ws.data_ptr() : nullptr;
+  const size_t ws_size = ws.defined() ? (size_t)ws.numel() : 0;
+  int st;
+  if (schedule != nullptr)
+    st = mi_spmm_csr_scheduled_f32(schedule->sc, variant, a.offsets, a.columns, a.f32(), nnzA, a.rows, a.cols, (int32_t)N,
+                                   b.keep.data_ptr<float>(), b.ld, f32_or_null(bias_keep), C.data_ptr<float>(), ld1(N), mode,
+                                   ws_ptr, ws_size, stream);
+  else if (f32)
+    st = mi_spmm_csr_ex_f32(a.offsets, a.columns, a.f32(), nnzA, a.rows, a.cols, (int32_t)N, b.keep.data_ptr<float>(), b.ld,
+                            f32_or_null(bias_keep), C.data_ptr<float>(), ld1(N), mode, ws_ptr, ws_size, stream);
+  else
+    st = (dt == torch::kBFloat16 ? mi_spmm_csr_ex_bf16 : mi_spmm_csr_ex_f16)(
+        a.offsets, a.columns, a.b16(), nnzA, a.rows, a.cols, (int32_t)N, static_cast<const uint16_t*>(b.keep.data_ptr()),
+        b.ld, static_cast<uint16_t*>(C.data_ptr()), ld1(N), mode, ws_ptr, ws_size, stream);
   if (st != MI_OK && mode == MI_LONG_ROWS_AUTO_ZEROED) drop_stream_workspace(C.device(), stream);  // its header may be dirty
   check_status(st, what);
-  if (allow_auto && long_rows == MI_LONG_ROWS_AUTO && auto_keep == nullptr)
+  if (f32 && allow_auto && long_rows == MI_LONG_ROWS_AUTO && auto_keep == nullptr)
     auto_schedule_launch(A_offsets, A_columns, nnzA, A_rows, A_cols, N, stream);  // (does something on the second product of a key only)
   return C;
 }
 
 torch::Tensor naive_spmm(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor A_offsets,
                          int nnzA, int A_rows, int A_cols, torch::Tensor B, torch::Tensor C) {
-  if (lowp_operands({&A_values, &B, &C}))
-    return spmm_lowp(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "naive_spmm", MI_LONG_ROWS_AUTO);
-  return spmm_impl(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "naive_spmm", nullptr, MI_LONG_ROWS_AUTO, nullptr, MI_SPMM_AUTO, true);
+  return spmm_impl(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "naive_spmm", nullptr, MI_LONG_ROWS_AUTO, nullptr,
+                   MI_SPMM_AUTO, true, true);
 }
 
 torch::Tensor cusparse_mmul(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor A_offsets,
                             int nnzA, int A_rows, int A_cols, torch::Tensor B, torch::Tensor C) {
-  if (lowp_operands({&A_values, &B, &C}))
-    return spmm_lowp(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "cusparse_mmul", MI_LONG_ROWS_AUTO);
-  return spmm_impl(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "cusparse_mmul", nullptr, MI_LONG_ROWS_AUTO, nullptr, MI_SPMM_AUTO, true);
+  return spmm_impl(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "cusparse_mmul", nullptr, MI_LONG_ROWS_AUTO,
+                   nullptr, MI_SPMM_AUTO, true, true);
 }
 
 // Fused FC-layer forms (additions): C = op(A)·op(B) + bias and C = A_csr·B + bias, bias[n]
@@ -379,9 +367,9 @@ torch::Tensor naive_spmm_ex(torch::Tensor A_values, torch::Tensor A_columns, tor
                             int long_rows) {
   if (long_rows < MI_LONG_ROWS_AUTO || long_rows > MI_LONG_ROWS_SPLIT)
     throw std::invalid_argument("naive_spmm_ex: long_rows must be -1, 0 or 1");
-  if (lowp_operands({&A_values, &B, &C}))  // (-1 and 1 are the same rule there: long rows split)
-    return spmm_lowp(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "naive_spmm_ex", long_rows);
-  return spmm_impl(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "naive_spmm_ex", nullptr, long_rows);
+  // (bf16 / fp16: -1 and 1 are the same rule, long rows split)
+  return spmm_impl(A_values, A_columns, A_offsets, nnzA, A_rows, A_cols, B, C, "naive_spmm_ex", nullptr, long_rows, nullptr,
+                   MI_SPMM_AUTO, false, true);
 }
 
 // … and with the fused bias (fc_layers: activations converted from a dense matrix have no row longer than
@@ -397,13 +385,12 @@ torch::Tensor naive_spmm_bias_ex(torch::Tensor A_values, torch::Tensor A_columns
 // (variant id, kernel name, launches per product, splits_long_rows) of the AUTO plan for
 // C[M,N] = A[M,K]·B with nnz non-zeros and these operand buffers — no GPU work.
 std::tuple<int, std::string, int, bool> spmm_plan(int64_t nnz, int64_t M, int64_t K, torch::Tensor B, torch::Tensor C) {
-  check_device_f32(B, "B");
-  check_device_f32(C, "C");
+  value_dtype("spmm_plan", {{"B", &B}, {"C", &C}});
   TORCH_CHECK(B.dim() == 2 && C.dim() == 2 && B.size(1) == C.size(1), "spmm_plan: B [K,N] and C [M,N] expected");
-  TORCH_CHECK(M <= INT32_MAX && K <= INT32_MAX, "spmm_plan: dimension too large");
   const int64_t N = B.size(1);
-  const int64_t ldb = B.size(0) > 1 ? B.stride(0) : std::max<int64_t>(N, 1);
-  const int64_t ldc = C.size(0) > 1 ? C.stride(0) : std::max<int64_t>(N, 1);
+  check_sizes("spmm_plan", {M, K, N}, nnz);
+  const int64_t ldb = B.size(0) > 1 ? B.stride(0) : ld1(N);
+  const int64_t ldc = C.size(0) > 1 ? C.stride(0) : ld1(N);
   const int v = mi_spmm_csr_f32_plan(nnz, (int32_t)M, (int32_t)K, (int32_t)N, B.data_ptr<float>(), ldb,
                                      C.data_ptr<float>(), ldc);
   check_status(v < 0 ? v : MI_OK, "spmm_plan");
@@ -422,14 +409,8 @@ int long_row_threshold() { return mi_spmm_long_row_threshold(); }
 void validate_csr(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor A_offsets, int64_t nnzA,
                   int64_t A_rows, int64_t A_cols) {
   const char* what = "validate_csr";
-  check_device_f32(A_values, "A_values");
-  check_device_i32(A_columns, "A_columns");
-  check_device_i32(A_offsets, "A_offsets");
-  check_same_device(A_values, A_columns, what);
-  check_same_device(A_values, A_offsets, what);
-  TORCH_CHECK(A_rows >= 0 && A_cols >= 0 && nnzA >= 0, what, ": negative size");
-  TORCH_CHECK(A_offsets.numel() == A_rows + 1, what, ": A_offsets must have A_rows + 1 entries");
-  TORCH_CHECK(A_values.numel() >= nnzA && A_columns.numel() >= nnzA, what, ": nnzA exceeds the CSR arrays");
+  value_dtype(what, {{"A_values", &A_values}});
+  csr_arrays(what, &A_values, &A_columns, A_offsets, nnzA, A_rows, A_cols);
   torch::Tensor off = A_offsets.reshape({-1});
   if (A_rows > 0) {
     TORCH_CHECK(off[0].item<int32_t>() == 0 && off[A_rows].item<int32_t>() == nnzA, what,
@@ -447,71 +428,67 @@ void validate_csr(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor
 
 // Column sums of a 2-d tensor (bias gradient of the FC layers): returns a [n] tensor.
 torch::Tensor column_sums(torch::Tensor src) {
-  check_device_f32(src, "src");
+  value_dtype("column_sums", {{"src", &src}});
   TORCH_CHECK(src.dim() == 2, "column_sums: expected a 2-d tensor");
-  torch::Tensor x = src.stride(1) == 1 && src.stride(0) >= src.size(1) ? src : src.contiguous();
-  const int64_t rows = x.size(0), n = x.size(1);
-  TORCH_CHECK(rows <= INT32_MAX && n <= INT32_MAX, "column_sums: dimension too large");
+  const int64_t rows = src.size(0), n = src.size(1);
+  check_sizes("column_sums", {rows, n});
+  torch::Tensor x = src.stride(1) == 1 && src.stride(0) >= n ? src : src.contiguous();
   c10::hip::HIPGuard guard(x.device().index());
   torch::Tensor out = torch::empty({n}, x.options());
   const size_t ws_bytes = mi_colsum_workspace_bytes((int32_t)rows, (int32_t)n);
-  torch::Tensor ws = torch::empty({(int64_t)std::max<size_t>(ws_bytes, 4)}, torch::dtype(torch::kUInt8).device(x.device()));
-  check_status(mi_colsum_f32(x.data_ptr<float>(), (int32_t)rows, (int32_t)n, rows > 1 ? x.stride(0) : std::max<int64_t>(n, 1),
+  torch::Tensor ws = byte_workspace(x.device(), ws_bytes, 4);
+  check_status(mi_colsum_f32(x.data_ptr<float>(), (int32_t)rows, (int32_t)n, rows > 1 ? x.stride(0) : ld1(n),
                              out.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream_of(x)),
                "column_sums");
   return out;
 }
 
-// values[perm] as a new tensor (perm int32, values f32, both contiguous and on one device); what torch's index_select
-// does, without its index conversion (bound by one line request per value either way: tools/probes/gather_bench.py)
+// values[perm] as a new tensor (perm int32, values f32 / bf16 / fp16, both contiguous and on one device); what torch's
+// index_select does, without its index conversion (bound by one line request per value either way: tools/probes/gather_bench.py)
 torch::Tensor gather_perm(torch::Tensor values, torch::Tensor perm) {
-  if (is_lowp(values)) return gather_perm_lowp(values, perm);  // 2-byte values (bf16 / fp16)
-  check_device_f32(values, "values");
+  const char* what = "gather_perm";
+  const torch::ScalarType dt = value_dtype(what, {{"values", &values}}, true);
   check_device_i32(perm, "perm");
-  check_same_device(values, perm, "gather_perm");
+  check_same_device(what, values.device(), {&perm});
   TORCH_CHECK(values.dim() == 1 && perm.dim() == 1 && values.is_contiguous() && perm.is_contiguous(),
               "gather_perm: expected contiguous 1-d tensors");
   c10::hip::HIPGuard guard(values.device().index());
   torch::Tensor out = torch::empty({perm.numel()}, values.options());
-  check_status(mi_gather_f32(values.data_ptr<float>(), perm.data_ptr<int32_t>(), perm.numel(), out.data_ptr<float>(),
-                             stream_of(values)),
-               "gather_perm");
+  const int st = dt == torch::kFloat32
+                     ? mi_gather_f32(values.data_ptr<float>(), perm.data_ptr<int32_t>(), perm.numel(), out.data_ptr<float>(),
+                                     stream_of(values))
+                     : mi_gather_b16(static_cast<const uint16_t*>(values.data_ptr()), perm.data_ptr<int32_t>(), perm.numel(),
+                                     static_cast<uint16_t*>(out.data_ptr()), stream_of(values));
+  check_status(st, what);
   return out;
 }
 
 std::shared_ptr<PySchedule> make_schedule(torch::Tensor A_offsets, int64_t nnzA, int64_t A_rows, int64_t N, bool list_long_rows,
                                           const char* what, const torch::Tensor* A_columns = nullptr, int64_t A_cols = 0) {
-  check_device_i32(A_offsets, "A_offsets");
-  TORCH_CHECK(A_offsets.is_contiguous() && A_offsets.numel() == A_rows + 1, what, ": A_offsets must be contiguous with A_rows + 1 entries");
-  TORCH_CHECK(A_rows >= 0 && A_rows <= INT32_MAX && nnzA >= 0 && N >= 0 && N <= INT32_MAX, what, ": bad size");
+  if (A_columns != nullptr && !A_columns->defined()) A_columns = nullptr;
+  const Csr a = csr_arrays(what, nullptr, A_columns, A_offsets, nnzA, A_rows, A_cols);
+  check_sizes(what, {N});
   c10::hip::HIPGuard guard(A_offsets.device().index());
   auto out = std::make_shared<PySchedule>();
   out->rows = A_rows;
   out->nnz = nnzA;
-  torch::Tensor order_buf = torch::empty({(A_columns != nullptr && A_columns->defined() ? 2 : 1) * A_rows}, A_offsets.options());
-  const size_t ws_bytes = mi_spmm_schedule_workspace_bytes((int32_t)A_rows);
-  torch::Tensor ws = torch::empty({(int64_t)ws_bytes}, torch::dtype(torch::kUInt8).device(A_offsets.device()));
-  const int32_t* colp = nullptr;
-  if (A_columns != nullptr && A_columns->defined()) {
-    check_device_i32(*A_columns, "A_columns");
-    check_same_device(*A_columns, A_offsets, what);
-    TORCH_CHECK(A_columns->is_contiguous() && A_columns->numel() >= nnzA && A_cols >= 0 && A_cols <= INT32_MAX, what,
-                ": A_columns must be contiguous with nnzA entries");
-    colp = A_columns->data_ptr<int32_t>();
-  }
-  check_status(mi_spmm_schedule_create(A_offsets.data_ptr<int32_t>(), colp, (int32_t)A_rows, (int32_t)A_cols, nnzA, (int32_t)N,
-                                       order_buf.data_ptr<int32_t>(), ws.data_ptr(), ws_bytes, stream_of(A_offsets), &out->sc),
+  torch::Tensor order_buf = torch::empty({(A_columns != nullptr ? 2 : 1) * A_rows}, A_offsets.options());
+  const size_t ws_bytes = mi_spmm_schedule_workspace_bytes(a.rows);
+  torch::Tensor ws = byte_workspace(a.device, ws_bytes);
+  check_status(mi_spmm_schedule_create(a.offsets, a.columns, a.rows, a.cols, nnzA, (int32_t)N, order_buf.data_ptr<int32_t>(),
+                                       ws.data_ptr(), ws_bytes, stream_of(A_offsets), &out->sc),
                what);
-  int64_t v[12] = {0};
-  check_status(mi_spmm_schedule_info(out->sc, v), what);
+  const auto v = schedule_info(out->sc, what);
   out->order_keep = order_buf;  // both candidate orders; `order` is the half the schedule points at
   out->order = (v[5] & 4) ? order_buf.narrow(0, A_rows, A_rows) : order_buf.narrow(0, 0, A_rows);
   // the longest class starts at v[4] entries and is ≈ 12 % wide: list the long rows when it may reach beyond the threshold
-  if (list_long_rows && N > 0 && v[4] + v[4] / 8 + 1 > mi_spmm_long_row_threshold()) {
+  // (and nnz does: below that, mi_spmm_long_rows_prepare writes no list)
+  const int64_t threshold = mi_spmm_long_row_threshold();
+  if (list_long_rows && N > 0 && nnzA > threshold && v[4] + v[4] / 8 + 1 > threshold) {
     const size_t lbytes = mi_spmm_csr_workspace_bytes(nnzA, (int32_t)N);
-    out->long_ws = torch::empty({(int64_t)std::max<size_t>(lbytes, 16)}, torch::dtype(torch::kUInt8).device(A_offsets.device()));
-    check_status(mi_spmm_long_rows_prepare(A_offsets.data_ptr<int32_t>(), (int32_t)A_rows, nnzA, (int32_t)N, out->long_ws.data_ptr(),
-                                           lbytes, stream_of(A_offsets)),
+    out->long_ws = byte_workspace(a.device, lbytes, 16);
+    check_status(mi_spmm_long_rows_prepare(a.offsets, a.rows, nnzA, (int32_t)N, out->long_ws.data_ptr(), lbytes,
+                                           stream_of(A_offsets)),
                  what);
     out->long_ws_width = N;
     out->long_rows = out->long_ws.view(torch::kInt32)[0].item<int32_t>();  // (inspection time: one more read-back)
@@ -534,7 +511,7 @@ torch::Tensor naive_spmm_scheduled(std::shared_ptr<PySchedule> schedule, torch::
   const char* what = "naive_spmm_scheduled";
   TORCH_CHECK(schedule && schedule->sc, what, ": no schedule");
   TORCH_CHECK(schedule->rows == A_rows, what, ": the schedule was built for ", schedule->rows, " rows, A has ", A_rows);
-  check_same_device(schedule->order, C, what);
+  check_same_device(what, C.device(), {&schedule->order});
   if (long_rows < MI_LONG_ROWS_AUTO || long_rows > MI_LONG_ROWS_SPLIT)
     throw std::invalid_argument("naive_spmm_scheduled: long_rows must be -1, 0 or 1");
   const torch::Tensor* b = bias.has_value() && bias->defined() ? &*bias : nullptr;

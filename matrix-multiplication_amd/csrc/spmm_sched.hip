@@ -443,18 +443,11 @@ int mi_spmm_schedule_destroy(mi_spmm_schedule_t* sc) {
 
 int mi_spmm_schedule_info(const mi_spmm_schedule_t* sc, int64_t* info) {
   if (!sc || !info) return MI_EINVAL;
-  info[0] = sc->rs.rows;
-  info[1] = sc->rs.heavy;
-  info[2] = sc->rs.heavy_len;
-  info[3] = sc->classes;
-  info[4] = sc->longest;
-  info[5] = (sc->rs.side != nullptr ? 1 : 0) | (sc->rs.active ? 2 : 0) | (sc->locality ? 4 : 0);
-  info[6] = sc->nnz;
-  info[7] = sc->n_width;
-  info[8] = sc->span_natural;
-  info[9] = sc->span_scheduled;
-  info[10] = sc->span_row;
-  info[11] = 0;
+  const int64_t v[MI_SPMM_SCHEDULE_INFO_LEN] = {
+      sc->rs.rows, sc->rs.heavy, sc->rs.heavy_len, sc->classes, sc->longest,
+      (sc->rs.side != nullptr ? 1 : 0) | (sc->rs.active ? 2 : 0) | (sc->locality ? 4 : 0),
+      sc->nnz, sc->n_width, sc->span_natural, sc->span_scheduled, sc->span_row, 0};
+  for (int i = 0; i < MI_SPMM_SCHEDULE_INFO_LEN; ++i) info[i] = v[i];
   return MI_OK;
 }
 

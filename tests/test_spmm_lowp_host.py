@@ -156,3 +156,31 @@ def test_matmuls_refuses_what_low_precision_does_not_cover(built, dtype):
             f(torch.rand(4, 5).to_sparse_csr(), b)
         with pytest.raises(RuntimeError, match=rf"batched.*{name}"):
             f(torch.rand(2, 4, 5).to_sparse_csr().to(dtype), b)
+
+
+def test_float32_only_entries_refuse_host_tensors_and_name_mixed_dtypes(built):
+    """The entries without a bf16 / fp16 form apply the same dtype rule: one dtype for every value operand (named when mixed,
+    before the device is looked at), then device tensors, then float32."""
+    import custom_mm
+    vals, cols, offs, nnz, M, K, B, C = csr_args(torch.float32)
+    both = r"(?s)(?=.*\bFloat\b)(?=.*\bBFloat16\b)"
+    bias = torch.rand(3)
+    with pytest.raises(RuntimeError, match=both):
+        custom_mm.naive_spmm_bias(vals, cols, offs, nnz, M, K, B.bfloat16(), bias, C)
+    with pytest.raises(RuntimeError, match=both):
+        custom_mm.naive_spmm_batched(vals, cols, offs, nnz, 1, M, K, B.bfloat16(), C[None])
+    with pytest.raises(RuntimeError, match=both):
+        custom_mm.naive_spmm_dense(torch.rand(M, K), B.bfloat16(), C)
+    with pytest.raises(RuntimeError, match=both):
+        custom_mm.spmm_plan(nnz, M, K, B.bfloat16(), C)
+    for dtype in LOWP:
+        with pytest.raises(RuntimeError, match="device"):
+            custom_mm.naive_spmm_bias(vals.to(dtype), cols, offs, nnz, M, K, B.to(dtype), bias, C.to(dtype))
+        with pytest.raises(RuntimeError, match="device"):
+            custom_mm.csr_transpose(vals.to(dtype), cols, offs, nnz, M, K)
+    with pytest.raises(RuntimeError, match="device"):
+        custom_mm.validate_csr(vals, cols, offs, nnz, M, K)
+    with pytest.raises(RuntimeError, match="device"):
+        custom_mm.column_sums(C)
+    with pytest.raises(RuntimeError, match="device"):
+        custom_mm.gather_perm(vals, torch.arange(nnz, dtype=torch.int32))

@@ -132,3 +132,27 @@ def test_sparse_mm_reduce_refuses_what_it_cannot_run(built):
             matmuls.sparse_mm_reduce(torch.rand(2, 4, 5).to_sparse_csr(), b, r)
         with pytest.raises(ValueError, match="mat2"):
             matmuls.sparse_mm_reduce(a, b.double(), r)
+
+
+def test_reduce_bindings_refuse_host_tensors_and_name_mixed_dtypes(built):
+    import custom_mm
+    a = torch.rand(2, 3).to_sparse_csr()
+    vals, cols, offs = a.values(), a.col_indices().int(), a.crow_indices().int()
+    B, G, arg, perm = torch.rand(3, 4), torch.rand(2, 4), torch.zeros(2, 4, dtype=torch.int32), torch.arange(6, dtype=torch.int32)
+    t_offs = torch.tensor([0, 2, 4, 6], dtype=torch.int32)
+    with pytest.raises(RuntimeError, match="device"):
+        custom_mm.spmm_rows_divide(offs, 2, G, torch.empty(2, 4))
+    with pytest.raises(RuntimeError, match="device"):
+        custom_mm.spmm_reduce_grad_val(cols, offs, 6, 2, 3, B, G, arg)
+    with pytest.raises(RuntimeError, match="device"):
+        custom_mm.spmm_reduce_grad_b(t_offs, cols, perm, vals, 6, 2, 3, G, arg)
+    both = r"(?s)(?=.*\bFloat\b)(?=.*\bBFloat16\b)"  # checked before the device, so host tensors show it too
+    for r in ("sum", "mean", "amax", "amin"):
+        with pytest.raises(RuntimeError, match=both):
+            custom_mm.naive_spmm_reduce(vals, cols, offs, 6, 2, 3, B.bfloat16(), torch.zeros(2, 4), r)
+    with pytest.raises(RuntimeError, match=both):
+        custom_mm.spmm_rows_divide(offs, 2, G, torch.empty(2, 4, dtype=torch.bfloat16))
+    with pytest.raises(RuntimeError, match=both):
+        custom_mm.spmm_reduce_grad_val(cols, offs, 6, 2, 3, B, G.bfloat16(), arg)
+    with pytest.raises(RuntimeError, match=both):
+        custom_mm.spmm_reduce_grad_b(t_offs, cols, perm, vals, 6, 2, 3, G.bfloat16(), arg)
