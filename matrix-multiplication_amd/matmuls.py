@@ -56,6 +56,15 @@ def _sum_to_shape(grad, shape):
     return grad
 
 
+def _matrix_forms(a: torch.Tensor, b: torch.Tensor, what: str):
+    '''torch.matmul's matrix-vector forms: (a, b, dims) with a 1-d `a` taken as a [1, K] matrix and a 1-d `b` as [K, 1];
+    `dims` are the dims this adds to their product ([..., M, N]), to be squeezed out of it.'''
+    if a.dim() == 0 or b.dim() == 0:
+        raise ValueError(f'{what}: both arguments need to be at least 1-d')
+    dims = (-2,) * (a.dim() == 1) + (-1,) * (b.dim() == 1)
+    return (a.unsqueeze(0) if a.dim() == 1 else a), (b.unsqueeze(-1) if b.dim() == 1 else b), dims
+
+
 # the HIP-backed extension (tests/fake_custom_mm.py — the oracle-backed stand-in the host-logic tests import instead — is a
 # plain Python module: with it every call goes through the dispatch code, which is what those tests are for)
 _REAL_EXTENSION = str(getattr(custom_mm, '__file__', '')).endswith('.so')
@@ -96,18 +105,9 @@ def custom_matmul(a: torch.Tensor,
         return (a.transpose(-1, -2) if transa and a.dim() > 1 else a) @ (b.transpose(-1, -2) if transb and b.dim() > 1 else b)
     # matrix-vector forms: promote the vector to a matrix, as torch.matmul does.
     if a.dim() == 1 or b.dim() == 1:
-        if a.dim() == 0 or b.dim() == 0:
-            raise ValueError('custom_matmul: both arguments need to be at least 1-d')
-        a2 = a.unsqueeze(0) if a.dim() == 1 else a
-        b2 = b.unsqueeze(-1) if b.dim() == 1 else b
-        c = custom_matmul(a2, b2, mm_op, bmm_op,
-                          transa if a.dim() > 1 else False,
-                          transb if b.dim() > 1 else False)
-        if b.dim() == 1:
-            c = c.squeeze(-1)
-        if a.dim() == 1:
-            c = c.squeeze(-2 if b.dim() > 1 else -1)
-        return c
+        a2, b2, dims = _matrix_forms(a, b, 'custom_matmul')
+        return custom_matmul(a2, b2, mm_op, bmm_op, transa if a.dim() > 1 else False,
+                             transb if b.dim() > 1 else False).squeeze(dims)
 
     batch, c_rows, c_cols = _out_shape(a.shape, b.shape, transa, transb)
     # create tensor C to store results in (beta = 0: no need to pre-zero it)
@@ -152,15 +152,12 @@ def _dense_backward(ctx, grad_output, transa, transb):
     m1, m2 = ctx.saved_tensors
     grad_m1 = grad_m2 = None
     v1, v2 = m1.dim() == 1, m2.dim() == 1
-    a = m1.unsqueeze(0) if v1 else m1
-    b = m2.unsqueeze(-1) if v2 else m2
+    a, b, dims = _matrix_forms(m1, m2, 'matmul backward')
     ta = transa and not v1
     tb = transb and not v2
     g = grad_output
-    if v2:
-        g = g.unsqueeze(-1)
-    if v1:
-        g = g.unsqueeze(-2)
+    for d in reversed(dims):  # dC of the product of the matrix forms
+        g = g.unsqueeze(d)
 
     if (_fused_pair and not ta and tb and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and a.dim() >= 3 and
             tuple(a.shape[:-2]) == tuple(b.shape[:-2]) == tuple(g.shape[:-2]) and hasattr(custom_mm, 'cublas_bmm_pair')):
@@ -277,52 +274,92 @@ def _csr_key(a: torch.Tensor):
             tuple(a.shape), vals.numel())
 
 
-def _csr_props_cached(a: torch.Tensor):
-    '''(values, columns i32, offsets i32, nnz, rows, cols) of a CSR tensor, kept ON the tensor object between
-    calls (keyed on the component tensors' storage and version counters; it dies with the tensor): a static sparse
+class _CsrState:
+    '''What matmuls keeps ON a CSR tensor object between calls (attribute `_mi_state`; it dies with the tensor), so that
+    a static sparse operand pays its index work once, not on every product.  Its fields, and when they are rebuilt:
+      props       (values, columns i32, offsets i32, nnz, rows, cols) of a 2-d tensor — when anything in _csr_key changes;
+      transposed  (t_perm, t_col, t_off) of a 2-d tensor's Aᵀ (_transposed_pattern) — when the pattern changes (the
+                  index tensors' storage or versions, the shape, nnz);
+      sched       {dense width: 'seen' | schedule} of A, and sched_t of Aᵀ (_row_schedule) — when the pattern changes;
+      batched     (offsets, columns) of a batched tensor, narrowed for the device batched_dev (_batched_pattern), and
+      batched_t   its transposed part (_batched_transposed) — when the pattern changes or another device asks for them;
+      backwards   the number of batched backward passes of this tensor object — never.
+    Values are never kept: Aᵀ's values are gathered through the permutation on every call (one pass over nnz), so a
+    write to the values that no version counter sees (`a.values().data.mul_(3)`, a kernel writing through data_ptr)
+    can never leave a stale copy behind.'''
+    key = props = transposed = sched = sched_t = batched = batched_dev = batched_t = None
+    backwards = 0
+
+
+def _csr_state(a: torch.Tensor) -> _CsrState:
+    '''The _CsrState of a CSR tensor, without the fields its current key makes stale.'''
+    key = _csr_key(a)
+    st = getattr(a, '_mi_state', None)
+    if st is None:
+        st = _CsrState()
+        try:
+            a._mi_state = st
+        except (AttributeError, RuntimeError):
+            pass  # a tensor type that takes no attributes: a record for this call only
+    if st.key != key:
+        if st.key is None or st.key[1:3] + st.key[4:] != key[1:3] + key[4:]:  # a new pattern
+            st.transposed = st.batched = st.batched_t = None
+            st.sched, st.sched_t = {}, {}
+        st.key, st.props = key, None
+    return st
+
+
+def _csr_props_cached(a: torch.Tensor, st: _CsrState = None):
+    '''(values, columns i32, offsets i32, nnz, rows, cols) of a 2-d CSR tensor, kept in its _CsrState: a static sparse
     operand is narrowed to int32 once instead of on every product (two passes over the indices: 0.3 ms at the
     1M × 1M config).  Nothing is read back to the host (round 2 read the longest row back to decide whether the
     long-row helpers were needed: since round 3 the plain entry points cost the main kernel + one empty follow-up
     launch, so the question no longer pays for a synchronisation — and the call stays graph-capturable).'''
-    key = _csr_key(a)
-    hit = getattr(a, '_mi_csr_props', None)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    props = get_sparse_tensor_properties(a)
-    try:
-        a._mi_csr_props = (key, props)
-    except (AttributeError, RuntimeError):
-        pass  # a tensor type that takes no attributes: just no caching
-    return props
+    st = _csr_state(a) if st is None else st
+    if st.props is None:
+        st.props = get_sparse_tensor_properties(a)
+    return st.props
 
 
-def _row_schedule(holder: torch.Tensor, slot: str, key, offsets: torch.Tensor, nnz: int, rows: int, width: int, columns=None, cols: int = 0):
+def _transposed_pattern(a: torch.Tensor, st: _CsrState = None):
+    '''(t_perm, t_col, t_off) of a 2-d CSR tensor, kept in its _CsrState: the pattern of Aᵀ and the int32 permutation
+    (4 B per non-zero) that carries A's values into it — in a training loop the pattern is static and the device
+    transpose (1.7 ms at the 1M × 1M config) would otherwise be paid on every backward.  No values (_gather_perm).'''
+    st = _csr_state(a) if st is None else st
+    if st.transposed is None:
+        values, columns, offsets, nnz, rows, cols = _csr_props_cached(a, st)
+        # the transpose moves 4-byte values untouched: transposing 0, 1, 2, … gives the permutation
+        iota = torch.arange(nnz, device=values.device, dtype=torch.int32).view(torch.float32)
+        t_perm, t_col, t_off = custom_mm.csr_transpose(iota, columns, offsets, nnz, rows, cols)
+        st.transposed = (t_perm.view(torch.int32), t_col, t_off)
+    return st.transposed
+
+
+def _gather_perm(values: torch.Tensor, perm: torch.Tensor) -> torch.Tensor:
+    '''values[perm]: the values of Aᵀ (or of a batch's transposes) through a kept permutation.'''
+    if hasattr(custom_mm, 'gather_perm') and values.is_contiguous():
+        return custom_mm.gather_perm(values, perm)
+    return values.index_select(0, perm)
+
+
+def _row_schedule(book: dict, offsets: torch.Tensor, nnz: int, rows: int, width: int, columns=None, cols: int = 0):
     '''The inspector's row schedule (custom_mm.spmm_schedule: rows handed to waves longest first, like lengths together,
     heavy rows in a launch of their own — the same bits as the plain product) for a CSR pattern that is being used AGAIN:
-    kept on the tensor object `holder` under `slot`, per dense width, keyed like the other per-tensor caches (index
-    tensors' storage and version counters).  The first product of a pattern runs plain and only leaves a mark — building
-    a schedule reads 1 KiB back (it synchronises), which a one-shot operand should not pay for; from the second product
-    on the schedule is there.  Never built under stream capture.  Returns None when there is none (yet), or when the
-    inspector found no skew worth an indirection (short, alike rows).  Counterpart of the reference's inspect-once /
-    multiply-many pair (src/sparse_mm.cu:137-385), without asking the caller to name a layer.'''
+    kept in `book` (_CsrState.sched or .sched_t), per dense width.  The first product of a pattern runs plain and only
+    leaves a mark — building a schedule reads 1 KiB back (it synchronises), which a one-shot operand should not pay for;
+    from the second product on the schedule is there.  Never built under stream capture.  Returns None when there is
+    none (yet), or when the inspector found no skew worth an indirection (short, alike rows).  Counterpart of the
+    reference's inspect-once / multiply-many pair (src/sparse_mm.cu:137-385), without asking the caller to name a layer.'''
     if not hasattr(custom_mm, 'spmm_schedule') or not offsets.is_cuda or rows < 2 or nnz < 4096:
         return None
-    book = getattr(holder, slot, None)
-    if book is None or book[0] != key:
-        book = (key, {})
-        try:
-            setattr(holder, slot, book)
-        except (AttributeError, RuntimeError):
-            return None  # a tensor type that takes no attributes: no schedule
-    ent = book[1].get(width)
+    ent = book.get(width)
     if ent is None:
-        book[1][width] = 'seen'
+        book[width] = 'seen'
         return None
     if ent == 'seen':
         if torch.cuda.is_current_stream_capturing():
             return None
-        ent = custom_mm.spmm_schedule(offsets, nnz, rows, width, columns, cols)
-        book[1][width] = ent
+        ent = book[width] = custom_mm.spmm_schedule(offsets, nnz, rows, width, columns, cols)
     return ent if ent.info()['active'] else None
 
 
@@ -354,9 +391,7 @@ _NO_READBACK_MAX_ELEMS = 1 << 27
 
 
 def _csr_of(a: torch.Tensor, est_density=None):
-    '''(values, columns, offsets, nnz, rows, cols) of a 2-d dense or CSR tensor.'''
-    if a.is_sparse_csr:
-        return _csr_props_cached(a)
+    '''(values, columns, offsets, nnz, rows, cols) of a 2-d dense tensor.'''
     values, columns, offsets, nnz = _dense_to_csr(a, est_density)
     return values, columns, offsets.view(-1), nnz, a.shape[-2], a.shape[-1]
 
@@ -375,14 +410,18 @@ def _csr_product(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, mm_op, defau
     est = None
     if one_launch and not a.is_sparse_csr and a.is_cuda and a.numel() > 0 and not torch.cuda.is_current_stream_capturing():
         est = sampled_density(a, (tuple(a.shape), tuple(b.shape), a.device.index), a.shape[-1], owner)
-    props = _csr_of(a, est)
+    if a.is_sparse_csr:
+        st = _csr_state(a)
+        props = _csr_props_cached(a, st)
+        if mm_op is default_op and b.dim() == 2 and a.dtype not in _LOWP:
+            # a CSR tensor that has been multiplied before (a static sparse operand: weights, an adjacency matrix): its row schedule
+            sched = _row_schedule(st.sched, props[2], props[3], props[4], b.shape[-1], props[1], props[5])
+            if sched is not None:
+                return custom_mm.naive_spmm_scheduled(sched, *props, b, c, None, 0 if one_launch else -1)
+    else:
+        props = _csr_of(a, est)
     # an ESTIMATED count may only meet rule 0 (no long-row workspace is sized from it: include/mi_spmm.h, K1 section)
     assert est is None or one_launch
-    if a.is_sparse_csr and mm_op is default_op and b.dim() == 2 and a.dtype not in _LOWP:
-        # a CSR tensor that has been multiplied before (a static sparse operand: weights, an adjacency matrix): its row schedule
-        sched = _row_schedule(a, '_mi_csr_sched', _csr_key(a)[1:3] + _csr_key(a)[4:], props[2], props[3], props[4], b.shape[-1], props[1], props[5])
-        if sched is not None:
-            return custom_mm.naive_spmm_scheduled(sched, *props, b, c, None, 0 if one_launch else -1)
     if one_launch:
         return custom_mm.naive_spmm_ex(*props, b, c, 0)
     return mm_op(*props, b, c)
@@ -404,61 +443,71 @@ def fused_skip_pays(items: int, rows: int, cols: int, width: int = 256) -> bool:
     return cols <= 3072
 
 
-def _batched_csr_pattern(a: torch.Tensor, dev, transposed: bool = False):
-    '''The index side of a batched CSR tensor ([..., M, K], equal non-zero counts per item) as the batched kernels
-    want it, kept ON the tensor object between calls (keyed on the index tensors' storage and version counters):
-    `offsets` int32 [batch, M + 1] with every item's base added ("rowptr of rowptrs"), `columns` int32 [nnz]; with
-    `transposed`, also what the backward needs — the flat offsets [batch·M + 1] and block-diagonal columns (item i
-    shifted by i·K) of the whole batch as ONE matrix, and the pattern of every item's transpose with the permutation
-    that carries the values into it (one batched device transpose of 0, 1, 2, …: the kernels move 4-byte values
-    untouched).  A training loop with a static pattern pays the narrowing and the transpose once; values are never
-    cached (see _csr_cached).'''
-    rows, cols = a.shape[-2], a.shape[-1]
-    crow = torch.Tensor.crow_indices(a).reshape(-1, rows + 1)
-    col = torch.Tensor.col_indices(a)
-    nb, per_item = crow.shape[0], col.shape[-1]
-    total = nb * per_item
-    key = (crow.data_ptr(), col.data_ptr(), crow._version, col._version, tuple(a.shape), per_item, str(dev))
-    hit = getattr(a, '_mi_batched_pattern', None)
-    if hit is None or hit[0] != key:
-        if total >= 2 ** 31 or nb * max(rows, cols) >= 2 ** 31:
+_MAX_ITEMS = 65535  # items one batched launch takes (its grid's y dimension)
+
+
+def _item_chunks(nb: int):
+    '''(lo, hi) of consecutive runs of at most _MAX_ITEMS items covering a batch of nb.'''
+    return [(lo, min(nb, lo + _MAX_ITEMS)) for lo in range(0, nb, _MAX_ITEMS)]
+
+
+def _transpose_items(values, columns, offsets, per_item: int, lo: int, hi: int, rows: int, cols: int):
+    '''csr_transpose_batched of items lo … hi - 1 on their own slices of the arrays (offsets rebased to the slice):
+    (t_values, t_columns, t_offsets) of the slice.'''
+    p0, p1 = lo * per_item, hi * per_item
+    return custom_mm.csr_transpose_batched(values[p0:p1], columns[p0:p1], offsets[lo:hi] if lo == 0 else offsets[lo:hi] - p0,
+                                           p1 - p0, hi - lo, rows, cols)
+
+
+def _batched_pattern(a: torch.Tensor, dev, st: _CsrState = None):
+    '''(offsets, columns): the index side of a batched CSR tensor ([..., M, K], equal non-zero counts per item) as the
+    batched kernels want it, kept in its _CsrState: `offsets` int32 [batch, M + 1] with every item's base added
+    ("rowptr of rowptrs"), `columns` int32 [nnz].  A training loop with a static pattern pays the narrowing once.'''
+    st = _csr_state(a) if st is None else st
+    if st.batched is None or st.batched_dev != str(dev):
+        rows, cols = a.shape[-2], a.shape[-1]
+        crow = torch.Tensor.crow_indices(a).reshape(-1, rows + 1)
+        col = torch.Tensor.col_indices(a)
+        nb, per_item = crow.shape[0], col.shape[-1]
+        if nb * per_item >= 2 ** 31 or nb * max(rows, cols) >= 2 ** 31:
             raise ValueError('sparse matmul: the batch holds too many non-zeros / rows for int32 indices')
         if (hasattr(custom_mm, 'batched_csr_narrow') and crow.is_cuda and crow.device == torch.device(dev) and per_item > 0
                 and crow.dtype == torch.int64 and col.dtype == torch.int64):
             # ONE launch for both index tensors (round 5: attention probabilities are a new pattern on every step, so
             # this narrowing is per-step work, not a one-off — it used to be five torch kernels)
-            off32, col32 = custom_mm.batched_csr_narrow(crow.contiguous(), col.reshape(nb, per_item).contiguous())
-            hit = [key, off32, col32, None]
+            st.batched = custom_mm.batched_csr_narrow(crow.contiguous(), col.reshape(nb, per_item).contiguous())
         else:
             base = torch.arange(nb, device=crow.device, dtype=crow.dtype).unsqueeze(1) * per_item
-            hit = [key, (crow + base).to(device=dev, dtype=torch.int32).contiguous(),
-                   col.reshape(-1).to(device=dev, dtype=torch.int32).contiguous(), None]
-        try:
-            a._mi_batched_pattern = hit
-        except (AttributeError, RuntimeError):
-            pass  # a tensor type that takes no attributes: just no caching
-    if transposed and hit[3] is None:
-        offsets, columns = hit[1], hit[2]
+            st.batched = ((crow + base).to(device=dev, dtype=torch.int32).contiguous(),
+                          col.reshape(-1).to(device=dev, dtype=torch.int32).contiguous())
+        st.batched_dev, st.batched_t = str(dev), None
+    return st.batched
+
+
+def _batched_transposed(a: torch.Tensor, dev, st: _CsrState = None):
+    '''(flat_off, diag_columns, t_perm, t_col, t_off): what the backward of a batched CSR tensor needs beyond
+    _batched_pattern, kept in its _CsrState — the flat offsets [batch·M + 1] and block-diagonal columns (item i shifted
+    by i·K) of the whole batch as ONE matrix, and the pattern of every item's transpose with the permutation that
+    carries the values into it (one batched device transpose of 0, 1, 2, …: the kernels move 4-byte values untouched).'''
+    st = _csr_state(a) if st is None else st
+    offsets, columns = _batched_pattern(a, dev, st)
+    if st.batched_t is None:
+        rows, cols = a.shape[-2], a.shape[-1]
+        nb = offsets.shape[0]
+        total = columns.numel()
+        per_item = total // nb
         flat_off = torch.cat([offsets[:, :-1].reshape(-1), offsets[-1:, -1]]).contiguous()
         shift = (torch.arange(nb, device=dev, dtype=torch.int32) * cols).repeat_interleave(per_item)
         iota = torch.arange(total, device=dev, dtype=torch.int32).view(torch.float32)
-        if nb <= 65535:
-            t_perm, t_col, t_off = custom_mm.csr_transpose_batched(iota, columns, offsets, total, nb, rows, cols)
-        else:
-            # more items than one launch takes: transpose chunks of ≤ 65535 items on their own slices of the arrays
-            # (offsets rebased to the slice, then put back) — the values are 0, 1, 2, … of the WHOLE batch, so the
-            # permutation stays global
-            parts = []
-            for lo in range(0, nb, 65535):
-                hi = min(nb, lo + 65535)
-                p0, p1 = lo * per_item, hi * per_item
-                tp, tc, to = custom_mm.csr_transpose_batched(iota[p0:p1], columns[p0:p1], (offsets[lo:hi] - p0).contiguous(),
-                                                             p1 - p0, hi - lo, rows, cols)
-                parts.append((tp, tc, to + p0))
-            t_perm, t_col, t_off = (torch.cat([x[i] for x in parts]) for i in range(3))
-        t_perm = t_perm.view(torch.int32)
-        hit[3] = (flat_off, columns + shift, t_perm, t_col, t_off)
-    return hit[1], hit[2], hit[3]
+        # more items than one launch takes: the chunks' offsets are put back — the values are 0, 1, 2, … of the WHOLE
+        # batch, so the permutation stays global
+        parts = []
+        for lo, hi in _item_chunks(nb):
+            tp, tc, to = _transpose_items(iota, columns, offsets, per_item, lo, hi, rows, cols)
+            parts.append((tp, tc, to if lo == 0 else to + lo * per_item))
+        t_perm, t_col, t_off = parts[0] if len(parts) == 1 else (torch.cat(x) for x in zip(*parts))
+        st.batched_t = (flat_off, columns + shift, t_perm.view(torch.int32), t_col, t_off)
+    return st.batched_t
 
 
 def _batched_csr_product(a: torch.Tensor, b: torch.Tensor, mm_op, default_op) -> torch.Tensor:
@@ -483,10 +532,9 @@ def _batched_csr_product(a: torch.Tensor, b: torch.Tensor, mm_op, default_op) ->
     _b = (b.reshape(nb, cols, n) if b.dim() > 2 else b).to(dev)  # a 2-d b is shared by every item
     c = torch.empty((nb, rows, n), device=dev, dtype=torch.float32)
     if mm_op is default_op:
-        offsets, columns, _ = _batched_csr_pattern(a, dev)
+        offsets, columns = _batched_pattern(a, dev)
         values = val.reshape(-1).to(dev).contiguous()
-        for lo in range(0, nb, 65535):
-            hi = min(nb, lo + 65535)
+        for lo, hi in _item_chunks(nb):
             custom_mm.naive_spmm_batched(values, columns, offsets[lo:hi].contiguous(), total, hi - lo, rows, cols,
                                          _b[lo:hi].contiguous() if _b.dim() > 2 else _b.contiguous(), c[lo:hi])
     else:
@@ -653,16 +701,8 @@ def _spmm_dispatch(a: torch.Tensor, b: torch.Tensor, mm_op, default_op, dense_ro
     if _host_operands(a, b):
         return a @ b  # config C1: dense host operands — the reference's own expression (matmuls.py:279,302); see custom_matmul
     if a.dim() == 1 or b.dim() == 1:
-        if a.dim() == 0 or b.dim() == 0:
-            raise ValueError('sparse matmul: both arguments need to be at least 1-d')
-        a2 = a.unsqueeze(0) if a.dim() == 1 else a
-        b2 = b.unsqueeze(-1) if b.dim() == 1 else b
-        c = _spmm_dispatch(a2, b2, mm_op, default_op, dense_route)
-        if b.dim() == 1:
-            c = c.squeeze(-1)
-        if a.dim() == 1:
-            c = c.squeeze(-2 if b.dim() > 1 else -1)
-        return c
+        a2, b2, dims = _matrix_forms(a, b, 'sparse matmul')
+        return _spmm_dispatch(a2, b2, mm_op, default_op, dense_route).squeeze(dims)
 
     a_shape, b_shape = a.shape, b.shape
     c_rows, c_cols = a_shape[-2], b_shape[-1]
@@ -727,8 +767,7 @@ def _spmm_dispatch(a: torch.Tensor, b: torch.Tensor, mm_op, default_op, dense_ro
         est = None
         if _a.is_cuda and not capturing and _a.numel() > 0:  # (the batched entry has no long-row workspace: an estimate is a legal count)
             est = sampled_density(_a, (tuple(_a.shape), tuple(_b.shape), _a.device.index), a_shape[-1], a)
-        for lo in range(0, nb, 65535):
-            hi = min(nb, lo + 65535)
+        for lo, hi in _item_chunks(nb):
             values, columns, offsets, nnz = _dense_to_csr(_a[lo:hi], est)
             custom_mm.naive_spmm_batched(values, columns, offsets, nnz, hi - lo,
                                          c_rows, a_shape[-1], _b[lo:hi], c[lo:hi])
@@ -805,32 +844,6 @@ def naive_matmul(a: torch.Tensor,
     return _spmm_dispatch(a, b, mm_op, custom_mm.naive_spmm, dense_route)
 
 
-def _csr_cached(m1: torch.Tensor):
-    '''(values, columns i32, offsets i32, nnz, rows, cols) and the CSR of m1ᵀ for a CSR tensor.  What is kept ON the
-    tensor object between calls is the PATTERN of the transpose — its columns, its offsets and the permutation that
-    carries m1's values into it — because in a training loop the pattern is static and the device transpose (1.7 ms
-    at the 1M × 1M config) would otherwise be paid on every backward.  The VALUES of m1ᵀ are gathered through the
-    permutation on every call (one pass over nnz), so a write to m1's values that no version counter sees
-    (`a.values().data.mul_(3)`, a kernel writing through data_ptr) can never leave a stale copy behind.  The entry is
-    keyed on the index tensors' storage and version counters; it dies with the tensor.'''
-    key = _csr_key(m1)[1:3] + _csr_key(m1)[4:]
-    props = _csr_props_cached(m1)
-    values, columns, offsets, nnz, rows, cols = props
-    hit = getattr(m1, '_mi_csr_cache', None)
-    if hit is None or hit[0] != key:
-        # the transpose moves 4-byte values untouched: transposing 0, 1, 2, … gives the permutation
-        iota = torch.arange(nnz, device=values.device, dtype=torch.int32).view(torch.float32)
-        t_perm, t_col, t_off = custom_mm.csr_transpose(iota, columns, offsets, nnz, rows, cols)
-        hit = (key, t_perm.view(torch.int32), t_col, t_off)  # int32 permutation: 4 B per non-zero
-        try:
-            m1._mi_csr_cache = hit
-        except (AttributeError, RuntimeError):
-            pass  # a tensor type that takes no attributes: just no caching
-    t_val = custom_mm.gather_perm(values, hit[1]) if hasattr(custom_mm, 'gather_perm') and values.is_contiguous() \
-        else values.index_select(0, hit[1])
-    return props, (t_val, hit[2], hit[3])
-
-
 def _batched_csr_backward(ctx, m1, m2, grad_output):
     '''Both gradients of C[i] = m1[i] @ m2[i] for a batched CSR m1 ([..., M, K], equal non-zero counts per item — what
     torch builds) in a handful of launches for the whole batch (the reference has no backward for this input,
@@ -849,10 +862,11 @@ def _batched_csr_backward(ctx, m1, m2, grad_output):
     total = val.numel()
     per_item = total // max(nb, 1)
     dev = grad_output.device
-    # the transposed pattern (a batched device transpose + its permutation + the block-diagonal index arrays) is built only
-    # when a step below needs it: for pruned attention (n ≤ 64, an item's m2 in LDS) neither gradient does (round 5)
-    offsets, columns, _ = _batched_csr_pattern(m1, dev)
-    transposed = lambda: _batched_csr_pattern(m1, dev, transposed=True)[2]  # noqa: E731  (flat_off, diag_columns, t_perm, t_col, t_off)
+    # the transposed part (_batched_transposed: a batched device transpose + its permutation + the block-diagonal index
+    # arrays) is built only when a step below needs it: for pruned attention (n ≤ 64, an item's m2 in LDS) neither
+    # gradient does (round 5)
+    st = _csr_state(m1)
+    offsets, columns = _batched_pattern(m1, dev, st)
     g = grad_output.reshape(nb, rows, n).contiguous()
     shared = m2.dim() == 2
     grad_m1 = grad_m2 = None
@@ -863,18 +877,19 @@ def _batched_csr_backward(ctx, m1, m2, grad_output):
         if not (hasattr(custom_mm, 'sddmm_batched') and
                 custom_mm.sddmm_batched(columns, offsets, total, nb, rows, cols, g,
                                         m2.to(dev) if shared else m2.reshape(nb, cols, n).to(dev), gvals)):
-            flat_off, diag_columns = transposed()[:2]
+            flat_off, diag_columns = _batched_transposed(m1, dev, st)[:2]
             b_stack = (m2.unsqueeze(0).expand(nb, cols, n) if shared else m2.reshape(nb, cols, n)).reshape(nb * cols, n)
             gvals = custom_mm.sddmm(diag_columns, flat_off, total, nb * rows, nb * cols, g.reshape(nb * rows, n),
                                     b_stack.contiguous())
         grad_m1 = torch.sparse_csr_tensor(torch.Tensor.crow_indices(m1), torch.Tensor.col_indices(m1),
                                           gvals.to(val.device).reshape(val.shape), size=m1.shape)
     if ctx.needs_input_grad[1]:
-        # m1[i]ᵀ·dC[i] on the cached transposed pattern; the values travel through the cached permutation INSIDE the
+        # m1[i]ᵀ·dC[i] on the kept transposed pattern; the values travel through the kept permutation INSIDE the
         # kernel where its plan allows (the LDS-resident-B kernel: pruned attention), else as one gathered copy
         flat_val = val.reshape(-1).to(dev).contiguous()
-        t_val = None
         gb = torch.empty((nb, cols, n), device=dev, dtype=torch.float32)
+        chunks = _item_chunks(nb)  # (items per launch, as in the forward)
+        seen, st.backwards = st.backwards, st.backwards + 1
         # A tensor object seen for the FIRST time (attention probabilities: a new pattern on every step) gets its values
         # transposed directly where the one-workgroup-per-item LDS transpose takes the batch: nothing is kept, no
         # permutation, no block-diagonal index arrays are built (round 5: those cost a fresh pattern 0.39 ms per step,
@@ -883,37 +898,22 @@ def _batched_csr_backward(ctx, m1, m2, grad_output):
         # through the permutation inside the product kernel, as before.  (The transpose-free product,
         # custom_mm.naive_spmm_batched_at, was built and measured too: 0.54 ms at 10 % kept — its register-indexed FMA
         # per entry and the 16-fold scan of the indices lose to transposing; it stays available as an entry point.)
-        launches = range(0, nb, 65535)  # (items per launch, as in the forward)
-        hit = getattr(m1, '_mi_batched_pattern', None)
-        seen = getattr(m1, '_mi_batched_backwards', 0)
-        try:
-            m1._mi_batched_backwards = seen + 1
-        except (AttributeError, RuntimeError):
-            pass
-        direct = seen == 0 and (hit is None or hit[3] is None) and hasattr(custom_mm, 'csr_transpose_in_lds') and \
-            all(custom_mm.csr_transpose_in_lds((min(nb, lo + 65535) - lo) * per_item, min(nb, lo + 65535) - lo, rows, cols)
-                for lo in launches)
-        if direct:
-            for lo in launches:
-                hi = min(nb, lo + 65535)
-                p0, p1 = lo * per_item, hi * per_item
-                tv, tc, to = custom_mm.csr_transpose_batched(flat_val[p0:p1], columns[p0:p1],
-                                                             offsets[lo:hi] if lo == 0 else (offsets[lo:hi] - p0).contiguous(),
-                                                             p1 - p0, hi - lo, rows, cols)
-                custom_mm.naive_spmm_batched(tv, tc, to, p1 - p0, hi - lo, cols, rows, g[lo:hi], gb[lo:hi])
-            launches = range(0)
+        if seen == 0 and st.batched_t is None and hasattr(custom_mm, 'csr_transpose_in_lds') and \
+                all(custom_mm.csr_transpose_in_lds((hi - lo) * per_item, hi - lo, rows, cols) for lo, hi in chunks):
+            for lo, hi in chunks:
+                tv, tc, to = _transpose_items(flat_val, columns, offsets, per_item, lo, hi, rows, cols)
+                custom_mm.naive_spmm_batched(tv, tc, to, (hi - lo) * per_item, hi - lo, cols, rows, g[lo:hi], gb[lo:hi])
         else:
-            _, _, t_perm, t_col, t_off = transposed()
-        for lo in launches:
-            hi = min(nb, lo + 65535)
-            off_c, g_c = t_off[lo:hi].contiguous(), g[lo:hi]
-            if hasattr(custom_mm, 'naive_spmm_batched_perm') and \
-                    custom_mm.naive_spmm_batched_perm(flat_val, t_perm, t_col, off_c, total, hi - lo, cols, rows, g_c, gb[lo:hi]):
-                continue
-            if t_val is None:
-                t_val = custom_mm.gather_perm(flat_val, t_perm) if hasattr(custom_mm, 'gather_perm') \
-                    else flat_val.index_select(0, t_perm)
-            custom_mm.naive_spmm_batched(t_val, t_col, off_c, total, hi - lo, cols, rows, g_c, gb[lo:hi])
+            _, _, t_perm, t_col, t_off = _batched_transposed(m1, dev, st)
+            t_val = None
+            for lo, hi in chunks:
+                off_c, g_c = t_off[lo:hi].contiguous(), g[lo:hi]
+                if hasattr(custom_mm, 'naive_spmm_batched_perm') and \
+                        custom_mm.naive_spmm_batched_perm(flat_val, t_perm, t_col, off_c, total, hi - lo, cols, rows, g_c, gb[lo:hi]):
+                    continue
+                if t_val is None:
+                    t_val = _gather_perm(flat_val, t_perm)
+                custom_mm.naive_spmm_batched(t_val, t_col, off_c, total, hi - lo, cols, rows, g_c, gb[lo:hi])
         grad_m2 = gb.sum(0) if shared else gb.reshape(m2.shape)
         if vec:
             grad_m2 = grad_m2.squeeze(-1)
@@ -931,54 +931,41 @@ def _sparse_backward(ctx, grad_output):
     on the same flattened operands — grad_m2[i] = m1ᵀ·dC[i] is one product with N·batch columns, and
     the SDDMM sums over every item's columns, which is exactly Σ_i dC[i]·m2[i]ᵀ on the pattern.'''
     m1, m2 = ctx.saved_tensors
+    if not m1.is_sparse_csr:
+        # dense m1 (sparsified on the fly in forward): both gradients are dense products
+        return _dense_backward(ctx, grad_output, False, False)
+    if m1.dim() > 2:
+        return _batched_csr_backward(ctx, m1, m2, grad_output)
     grad_m1 = grad_m2 = None
-
-    if m1.is_sparse_csr:
-        if m1.dim() > 2:
-            return _batched_csr_backward(ctx, m1, m2, grad_output)
-        (values, columns, offsets, nnz, rows, cols), (t_val, t_col, t_off) = _csr_cached(m1)
-        if m2.dim() == 1:
-            g, b = grad_output.reshape(rows, 1), m2.unsqueeze(-1)
-        elif m2.dim() == 2:
-            g, b = grad_output, m2
-        else:
-            # [..., K, N] → [K, batch·N] and [..., M, N] → [M, batch·N], item-major columns
-            n = m2.shape[-1]
-            b = m2.reshape(-1, cols, n).permute(1, 0, 2).reshape(cols, -1)
-            g = grad_output.reshape(-1, rows, n).permute(1, 0, 2).reshape(rows, -1)
-        if ctx.needs_input_grad[0]:
-            gvals = custom_mm.sddmm(columns, offsets, nnz, rows, cols, g, b)
-            grad_m1 = torch.sparse_csr_tensor(torch.Tensor.crow_indices(m1), torch.Tensor.col_indices(m1),
-                                              gvals.to(m1.device), size=m1.shape)
-        if ctx.needs_input_grad[1]:
-            gb = torch.empty((cols, g.shape[-1]), device=g.device, dtype=values.dtype)
-            # m1ᵀ's pattern is cached on m1: so is its row schedule (the transpose of a skewed matrix is as skewed)
-            sched = _row_schedule(m1, '_mi_csr_sched_t', _csr_key(m1)[1:3] + _csr_key(m1)[4:], t_off, nnz, cols, g.shape[-1], t_col, rows) \
-                if g.is_contiguous() and values.dtype not in _LOWP else None
-            if sched is not None:
-                gb = custom_mm.naive_spmm_scheduled(sched, t_val, t_col, t_off, nnz, cols, rows, g, gb)
-            else:
-                gb = custom_mm.naive_spmm(t_val, t_col, t_off, nnz, cols, rows, g, gb)
-            if m2.dim() > 2:
-                gb = gb.view(cols, -1, m2.shape[-1]).permute(1, 0, 2)
-            grad_m2 = gb.reshape(m2.shape)
-        return grad_m1, grad_m2
-
-    # dense m1 (sparsified on the fly in forward): both gradients are dense products
-    v1, v2 = m1.dim() == 1, m2.dim() == 1
-    a = m1.unsqueeze(0) if v1 else m1
-    b = m2.unsqueeze(-1) if v2 else m2
-    g = grad_output
-    if v2:
-        g = g.unsqueeze(-1)
-    if v1:
-        g = g.unsqueeze(-2)
+    st = _csr_state(m1)
+    values, columns, offsets, nnz, rows, cols = _csr_props_cached(m1, st)
+    if m2.dim() == 1:
+        g, b = grad_output.reshape(rows, 1), m2.unsqueeze(-1)
+    elif m2.dim() == 2:
+        g, b = grad_output, m2
+    else:
+        # [..., K, N] → [K, batch·N] and [..., M, N] → [M, batch·N], item-major columns
+        n = m2.shape[-1]
+        b = m2.reshape(-1, cols, n).permute(1, 0, 2).reshape(cols, -1)
+        g = grad_output.reshape(-1, rows, n).permute(1, 0, 2).reshape(rows, -1)
     if ctx.needs_input_grad[0]:
-        ga = _sum_to_shape(custom_matmul(g, b, transb=True), a.shape)
-        grad_m1 = ga.squeeze(0) if v1 else ga
+        gvals = custom_mm.sddmm(columns, offsets, nnz, rows, cols, g, b)
+        grad_m1 = torch.sparse_csr_tensor(torch.Tensor.crow_indices(m1), torch.Tensor.col_indices(m1),
+                                          gvals.to(m1.device), size=m1.shape)
     if ctx.needs_input_grad[1]:
-        gb = _sum_to_shape(custom_matmul(a, g, transa=True), b.shape)
-        grad_m2 = gb.squeeze(-1) if v2 else gb
+        t_perm, t_col, t_off = _transposed_pattern(m1, st)
+        t_val = _gather_perm(values, t_perm)
+        gb = torch.empty((cols, g.shape[-1]), device=g.device, dtype=values.dtype)
+        # m1ᵀ's pattern is kept on m1: so is its row schedule (the transpose of a skewed matrix is as skewed)
+        sched = _row_schedule(st.sched_t, t_off, nnz, cols, g.shape[-1], t_col, rows) \
+            if g.is_contiguous() and values.dtype not in _LOWP else None
+        if sched is not None:
+            gb = custom_mm.naive_spmm_scheduled(sched, t_val, t_col, t_off, nnz, cols, rows, g, gb)
+        else:
+            gb = custom_mm.naive_spmm(t_val, t_col, t_off, nnz, cols, rows, g, gb)
+        if m2.dim() > 2:
+            gb = gb.view(cols, -1, m2.shape[-1]).permute(1, 0, 2)
+        grad_m2 = gb.reshape(m2.shape)
     return grad_m1, grad_m2
 
 
@@ -1026,18 +1013,6 @@ def _check_reduce_operands(m1, m2, reduce):
         raise ValueError(f'sparse_mm_reduce: shapes {tuple(m1.shape)} and {tuple(m2.shape)} cannot be multiplied')
 
 
-def _transposed_perm(m1):
-    '''(t_offsets, t_columns, perm) of m1ᵀ: the pattern _csr_cached keeps on the tensor, with the int32 permutation that
-    carries an entry of m1ᵀ to its index in m1.'''
-    (values, columns, offsets, nnz, rows, cols), (_, t_col, t_off) = _csr_cached(m1)
-    hit = getattr(m1, '_mi_csr_cache', None)
-    if hit is not None and hit[2] is t_col:
-        return t_off, t_col, hit[1]
-    iota = torch.arange(nnz, device=values.device, dtype=torch.int32).view(torch.float32)
-    t_perm, t_col, t_off = custom_mm.csr_transpose(iota, columns, offsets, nnz, rows, cols)
-    return t_off, t_col, t_perm.view(torch.int32)
-
-
 class naiveSpMMReduce(InplaceFunction):
     '''C[i, j] = reduce over the entries e of row i of val[e]·m2[col[e], j] — torch.sparse.mm(m1, m2, reduce) for a 2-d
     device CSR m1 (torch implements `reduce` for CSR on the CPU only).  sum: naiveSpMM's product and backward; mean: that
@@ -1075,15 +1050,16 @@ class naiveSpMMReduce(InplaceFunction):
                 g = custom_mm.spmm_rows_divide(offsets, rows, g, torch.empty_like(g))
             return (*_sparse_backward(ctx, g), None)
         m1, m2, arg = ctx.saved_tensors
-        values, columns, offsets, nnz, rows, cols = _csr_props_cached(m1)
+        st = _csr_state(m1)
+        values, columns, offsets, nnz, rows, cols = _csr_props_cached(m1, st)
         grad_m1 = grad_m2 = None
         if ctx.needs_input_grad[0]:
             gvals = custom_mm.spmm_reduce_grad_val(columns, offsets, nnz, rows, cols, m2, g, arg)
             grad_m1 = torch.sparse_csr_tensor(torch.Tensor.crow_indices(m1), torch.Tensor.col_indices(m1),
                                               gvals.to(m1.device), size=m1.shape)
         if ctx.needs_input_grad[1]:
-            t_off, t_col, perm = _transposed_perm(m1)
-            grad_m2 = custom_mm.spmm_reduce_grad_b(t_off, t_col, perm, values, nnz, rows, cols, g, arg)
+            t_perm, t_col, t_off = _transposed_pattern(m1, st)
+            grad_m2 = custom_mm.spmm_reduce_grad_b(t_off, t_col, t_perm, values, nnz, rows, cols, g, arg)
         return grad_m1, grad_m2, None
 
 

@@ -383,7 +383,7 @@ def test_vector_and_batched_mat2(cmm, mm, dev, oracle_mod, dtype, shape):
 # ---- 7. repeats: plain, then the Aᵀ schedule is built, then it is used ---------------------------------------------------
 
 @pytest.mark.parametrize("name", ["hub_cols", "hub_rows"])
-def test_three_passes_on_one_tensor(cmm, mm, dev, oracle_mod, monkeypatch, name):
+def test_three_passes_on_one_tensor_share_its_csr_state(cmm, mm, dev, oracle_mod, monkeypatch, name):
     """Pass 1 runs plain and marks the pattern; pass 2 builds the Aᵀ row schedule; pass 3 finds it kept on the tensor.  On
     hub_cols (Aᵀ rows of up to 10⁵ entries) the schedule is active, so grad B of passes 2 and 3 comes from
     naive_spmm_scheduled; on hub_rows (Aᵀ rows of a few entries) the inspector finds no skew and the plain product runs.
@@ -410,16 +410,17 @@ def test_three_passes_on_one_tensor(cmm, mm, dev, oracle_mod, monkeypatch, name)
         assert_same_bits(a.grad.values(), torch.from_numpy(want_v), f"{name} pass {rep} grad_val")
         assert_same_bits(b.grad, torch.from_numpy(want_b), f"{name} pass {rep} grad_B")
         check_bound_sum(P, Bn, Gn, a.grad.values().cpu().numpy(), b.grad.cpu().numpy(), f"{name} pass {rep}")
-        hit = getattr(a, "_mi_csr_cache", None)
-        assert hit is not None, "the transposed pattern is kept on the tensor"
-        assert cache is None or hit[2] is cache, "later passes reuse the kept transposed pattern"
-        cache = hit[2]
-        book = getattr(a, "_mi_csr_sched_t", None)
-        assert book is not None and N in book[1]
+        state = getattr(a, "_mi_state", None)
+        assert state is not None and state.transposed is not None, "the transposed pattern is kept on the tensor"
+        _, t_col, _ = state.transposed
+        assert cache is None or t_col is cache, "later passes reuse the kept transposed pattern"
+        cache = t_col
+        book = state.sched_t
+        assert N in book
         if rep == 0:
-            assert book[1][N] == "seen" and not scheduled_grad_b, "the first backward runs plain"
+            assert book[N] == "seen" and not scheduled_grad_b, "the first backward runs plain"
             continue
-        ent = book[1][N]
+        ent = book[N]
         assert ent != "seen", "the second backward builds the Aᵀ schedule"
         if name == "hub_cols":
             assert ent.info()["active"], "hub columns: the Aᵀ schedule is active"

@@ -17,7 +17,7 @@ from gpu_helpers import *  # noqa: F401,F403
 pytestmark = pytest.mark.gpu
 
 
-def test_matmuls_csr_times_batched_operand_on_device(mm, dev):
+def test_matmuls_csr_times_batched_operand_keeps_its_transpose_on_device(mm, dev):
     """naiveSpMM / cusparseMM with a CSR m1 and a batched m2: forward + both gradients vs torch
     autograd of the dense product; the cached transpose is reused across backward passes."""
     g = torch.Generator().manual_seed(5)
@@ -39,7 +39,7 @@ def test_matmuls_csr_times_batched_operand_on_device(mm, dev):
             ref.backward(dc)
             assert torch.allclose(b2.grad, b1.grad.cpu(), rtol=RTOL, atol=1e-5)
             assert torch.allclose(a2.grad * (a != 0), a_csr.grad.to_dense().cpu(), rtol=RTOL, atol=1e-5)
-            assert getattr(a_csr, "_mi_csr_cache", None) is not None
+            assert a_csr._mi_state.transposed is not None
 
 
 def test_matmuls_dense_classes_on_device(mm, dev):

@@ -215,7 +215,7 @@ def test_inspector_handles_run_skewed_matrices_on_their_schedule(cmm, dev, oracl
         cmm.tiledspmm_clean()
 
 
-def test_matmuls_keeps_a_schedule_on_a_csr_tensor_that_is_used_again(mm, cmm, dev, oracle_mod):
+def test_matmuls_keeps_a_schedule_in_the_csr_state_of_a_tensor_used_again(mm, cmm, dev, oracle_mod):
     """cusparseMM.apply(A_csr, b): the first product of a pattern runs plain and leaves a mark, the second builds the row
     schedule and keeps it on the tensor (per dense width), later ones reuse it; the backward's Aᵀ·dC does the same on the
     cached transposed pattern.  Forward values equal the oracle bit for bit every time, gradients equal torch autograd's."""
@@ -234,16 +234,16 @@ def test_matmuls_keeps_a_schedule_on_a_csr_tensor_that_is_used_again(mm, cmm, de
         out = mm.cusparseMM.apply(a, b)
         assert np.array_equal(out.detach().cpu().numpy().view(np.uint32), want.view(np.uint32)), i
         out.backward(t(dC, dev))
-        book = a._mi_csr_sched[1]
+        book = a._mi_state.sched
         assert (book[N] == 'seen') if i == 0 else (book[N].info()["active"] and book[N].info()["heavy_rows"] > 0), (i, book)
-        book_t = a._mi_csr_sched_t[1]
+        book_t = a._mi_state.sched_t
         assert (book_t[N] == 'seen') if i == 0 else (book_t[N].info()["rows"] == K)
         t_rp, t_col, t_val = oracle_mod.csr_transpose(rowptr, col, val, M, K)
         assert np.array_equal(b.grad.cpu().numpy().view(np.uint32), oracle_mod.spmm_csr(t_rp, t_col, t_val, K, M, dC).view(np.uint32)), i
     # another width: its own entry
     b2 = t(g.random((K, 32), dtype=np.float32), dev)
     mm.cusparseMM.apply(a, b2)
-    assert a._mi_csr_sched[1][32] == 'seen' and a._mi_csr_sched[1][N] != 'seen'
+    assert a._mi_state.sched[32] == 'seen' and a._mi_state.sched[N] != 'seen'
 
 
 def test_locality_order_is_taken_where_it_measurably_helps_and_changes_no_bit(cmm, dev, oracle_mod):

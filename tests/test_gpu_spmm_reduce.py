@@ -220,6 +220,23 @@ def test_autograd_vs_torch_cpu_and_deterministic(dev, reduce, N):
         assert_same_bits(x, y, f"{reduce}: second run")
 
 
+def test_amax_backward_gathers_no_values(mm, cmm, dev, monkeypatch):
+    """grad B of amax reads A's values through the kept permutation inside its kernel: the backward takes Aᵀ's pattern
+    alone and gathers no copy of Aᵀ's values (the sum backward, which multiplies by them, does)."""
+    M, K, N = 180, 260, 64
+    rowptr, col, val = csr_rows(M, K, mixed_lengths(M, N), seed=9, sort=True)
+    a = torch.sparse_csr_tensor(torch.from_numpy(rowptr.astype(np.int64)), torch.from_numpy(col.astype(np.int64)),
+                                torch.from_numpy(val), (M, K), device=dev).requires_grad_()
+    b = torch.randn(K, N, device=dev, requires_grad=True)
+    gathers = []
+    real = cmm.gather_perm
+    monkeypatch.setattr(cmm, "gather_perm", lambda *args: (gathers.append(1), real(*args))[1])
+    mm.sparse_mm_reduce(a, b, "amax").sum().backward()
+    assert a.grad is not None and b.grad is not None and not gathers
+    mm.sparse_mm_reduce(a, b, "sum").sum().backward()
+    assert len(gathers) == 1
+
+
 def test_int32_indices_and_grad_of_one_operand(dev):
     import matmuls
     M, K, N = 50, 80, 16

@@ -436,3 +436,61 @@ def test_csr_operand_is_narrowed_once_and_skips_the_long_row_machinery(mm, monke
     fake.calls.clear()
     matmuls.naiveSpMM.apply(a, b)
     assert [c[0] for c in fake.calls if c[0].startswith("naive_spmm")] == ["naive_spmm"]
+
+
+def test_tensor_that_keeps_no_state_gives_the_same_results(mm, monkeypatch):
+    """A CSR tensor that takes no `_mi_state` record (its store raises AttributeError) keeps nothing between calls: forward
+    and both gradients still equal torch autograd's, and every backward transposes once — for a 2-d and a batched
+    tensor."""
+    matmuls, fake = mm
+    real = torch.Tensor.__setattr__
+
+    def refuse(self, name, value):
+        if name == "_mi_state":
+            raise AttributeError(name)
+        real(self, name, value)
+
+    monkeypatch.setattr(torch.Tensor, "__setattr__", refuse)
+    g = torch.Generator().manual_seed(41)
+    keep = torch.zeros(3, 7 * 9, dtype=torch.bool)
+    for i in range(3):  # torch's batched CSR wants the same number of non-zeros in every item
+        keep[i, torch.randperm(7 * 9, generator=g)[:20]] = True
+    for dense, b, transpose in ((sparsify(g, 9, 14), rand(g, 14, 6), "csr_transpose"),
+                                (rand(g, 3, 7, 9) * keep.reshape(3, 7, 9), rand(g, 3, 9, 5), "csr_transpose_batched")):
+        a = dense.to_sparse_csr().requires_grad_(True)
+        fake.calls.clear()
+        for rep in range(1, 3):
+            a.grad = None
+            b1 = b.clone().requires_grad_(True)
+            out = matmuls.naiveSpMM.apply(a, b1)
+            a2, b2 = dense.clone().requires_grad_(True), b.clone().requires_grad_(True)
+            ref = torch.matmul(a2, b2)
+            assert torch.allclose(ref, out, rtol=RTOL, atol=1e-6)
+            dc = rand(g, *ref.shape)
+            out.backward(dc)
+            ref.backward(dc)
+            assert torch.allclose(b2.grad, b1.grad, rtol=RTOL, atol=1e-6)
+            assert torch.allclose(a2.grad * (dense != 0), a.grad.to_dense(), rtol=RTOL, atol=1e-6)
+            assert sum(c[0] == transpose for c in fake.calls) == rep
+        assert getattr(a, "_mi_state", None) is None
+
+
+def test_transposed_pattern_gathers_no_values(mm, oracle_mod, monkeypatch):
+    """_transposed_pattern gives Aᵀ's pattern and the permutation that carries A's values into it — the oracle's
+    transpose — with one device transpose per pattern and without gathering any values."""
+    matmuls, fake = mm
+    gathers = []
+    monkeypatch.setattr(fake, "gather_perm", lambda v, p: gathers.append("gather_perm"), raising=False)
+    real = torch.Tensor.index_select
+    monkeypatch.setattr(torch.Tensor, "index_select", lambda *a, **k: (gathers.append("index_select"), real(*a, **k))[1])
+    g = torch.Generator().manual_seed(42)
+    M, K = 11, 17
+    a = sparsify(g, M, K).to_sparse_csr()
+    fake.calls.clear()
+    t_perm, t_col, t_off = matmuls._transposed_pattern(a)
+    assert matmuls._transposed_pattern(a)[0] is t_perm                    # kept: the same tensors, no second transpose
+    assert [c[0] for c in fake.calls] == ["csr_transpose"] and not gathers
+    val, col, rowptr = (x.numpy() for x in (a.values(), a.col_indices().int(), a.crow_indices().int()))
+    want_off, want_col, want_val = oracle_mod.csr_transpose(rowptr, col, val, M, K)
+    assert t_perm.dtype == torch.int32 and np.array_equal(t_off.numpy(), want_off) and np.array_equal(t_col.numpy(), want_col)
+    assert np.array_equal(val[t_perm.numpy()], want_val)

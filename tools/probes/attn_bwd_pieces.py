@@ -28,7 +28,8 @@ probs = ((torch.rand(items, S * S, device=dev) * 0.9 + 0.1) * mask).reshape(item
 a = probs.to_sparse_csr()
 v = torch.rand(items, S, D, device=dev)
 g = torch.rand(items, S, D, device=dev)
-offsets, columns, (flat_off, diag_columns, t_perm, t_col, t_off) = matmuls._batched_csr_pattern(a, dev, transposed=True)
+offsets, columns = matmuls._batched_pattern(a, dev)
+flat_off, diag_columns, t_perm, t_col, t_off = matmuls._batched_transposed(a, dev)
 val = a.values().reshape(-1)
 total = val.numel()
 gb = torch.empty(items, S, D, device=dev)

@@ -1,5 +1,5 @@
-"""Where a fresh-pattern backward of the pruned-attention leg spends its time: each piece of matmuls._batched_csr_pattern /
-_batched_csr_backward timed alone (384 x 512 x 512 at MI_KEPT, D = 64).   python tools/probes/attn_fresh_pieces.py"""
+"""Where a fresh-pattern backward of the pruned-attention leg spends its time: each piece of matmuls._batched_pattern /
+_batched_transposed / _batched_csr_backward timed alone (384 x 512 x 512 at MI_KEPT, D = 64).   python tools/probes/attn_fresh_pieces.py"""
 import os
 import sys
 from pathlib import Path
