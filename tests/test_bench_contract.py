@@ -183,20 +183,24 @@ def test_self_launch_builds_a_torchrun_child_and_relays_rank0(monkeypatch, capsy
     monkeypatch.setattr(bench.subprocess, "run", fake_run)
     monkeypatch.delitem(sys.modules, "torch", raising=False)
     args = argparse.Namespace(gpus=4, steps=7, warmup=2, workload="c3", chunks=0, split="rows", exchange="auto",
-                              no_cpu_baseline=True, dump_outputs=None)
+                              no_cpu_baseline=True, full=False, dump_outputs=None)
     assert bench.self_launch(args) == 0
     cmd = seen["cmd"]
     assert cmd[:3] == [sys.executable, "-m", "torch.distributed.run"]
     assert "--nproc-per-node=4" in cmd and cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     tail = cmd[cmd.index(str(PROFILES.parent / "bench.py")) + 1:]
     assert tail[:6] == ["--gpus", "4", "--steps", "7", "--warmup", "2"] and "--no-cpu-baseline" in tail
-    assert "--dump-outputs" not in tail
+    assert "--dump-outputs" not in tail and "--full" not in tail
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     assert capsys.readouterr().out.strip() == '{"metric": "x", "n_gpus": 4}'
     # --dump-outputs reaches the ranks as an absolute path (rank 0 writes it)
     assert bench.self_launch(argparse.Namespace(**{**vars(args), "dump_outputs": "dumps"})) == 0
     tail = seen["cmd"][seen["cmd"].index(str(PROFILES.parent / "bench.py")) + 1:]
     assert tail[tail.index("--dump-outputs") + 1] == str(Path("dumps").resolve())
+    capsys.readouterr()
+    # --full reaches the ranks too (the legs it adds run on every rank)
+    assert bench.self_launch(argparse.Namespace(**{**vars(args), "full": True})) == 0
+    assert "--full" in seen["cmd"][seen["cmd"].index(str(PROFILES.parent / "bench.py")) + 1:]
     capsys.readouterr()
 
     def failing_run(cmd, env=None, stdout=None, text=None):

@@ -130,7 +130,7 @@ def test_bench_multi_gpu_path_rehearsal(dev):
     repo = Path(__file__).resolve().parent.parent
     env = dict(os.environ, MI_BENCH_REHEARSE="1")
     proc = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                           "--workload", "c2"], capture_output=True, text=True, timeout=600, env=env)
+                           "--workload", "c2", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1
@@ -153,6 +153,9 @@ def test_bench_multi_gpu_path_rehearsal(dev):
     assert proc.returncode == 0, proc.stderr[-3000:]
     cfg = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith('{"metric"')][0])["config"]
     assert cfg["p2p_probe_ok"] is True  # probed in its own group before the trial
+    # a run without --full times the steps and stops: no compute-only, gather-only or single-GPU leg
+    assert cfg["compute_only_ms_per_step"] is None and cfg["gather_only_ms_per_step"] is None
+    assert cfg["single_gpu_ms_on_rank0"] is None and cfg["gathered_C_equals_single_gpu_product"] is None
     assert set(cfg["chunk_trials_ms_per_step"]) == {"allgather/2", "allgather/4", "p2p/2", "p2p/4"}
     assert cfg["exchange"] in ("allgather", "p2p")
     # the IPC push exchange in the trial (round 5): CUDA IPC works between the two processes on this GPU
@@ -181,7 +184,7 @@ def test_bench_multi_gpu_path_rehearsal(dev):
     # their blocks straight into it; bench.py's own checks (a peer's block recomputed locally, the gathered C against rank
     # 0's single-GPU product) hold bit for bit
     proc = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                           "--workload", "c2", "--chunks", "2", "--exchange", "push"],
+                           "--workload", "c2", "--chunks", "2", "--exchange", "push", "--full"],
                           capture_output=True, text=True, timeout=600, env=env)
     assert proc.returncode == 0, proc.stderr[-3000:]
     rec = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith('{"metric"')][0])
