@@ -590,6 +590,35 @@ int mi_sddmm_csr_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int
 /* mi_gather_f32 for 2-byte values (bf16 / fp16 bit patterns moved untouched): dst[p] = src[perm[p]], p < n. */
 int mi_gather_b16(const uint16_t* src, const int32_t* perm, int64_t n, uint16_t* dst, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Low precision: dense products in bfloat16 / float16 on the matrix cores.  The arguments mirror mi_gemm_f32's
+ *   C[b] (m×n) = op(A[b]) · op(B[b]),   A, B and C all of the entry's type T, stored as uint16_t bit patterns;
+ * transposes, leading dimensions and item strides (0 broadcasts) as there; alpha = 1, beta = 0.
+ * Every sum is fp32 and each element is rounded ONCE, at the store (round-to-nearest-even, the narrowing torch's
+ * Tensor.to(T) does).  NaN stays NaN (its payload is not part of the contract); fp16 results beyond 65504 in magnitude
+ * round to ±inf (from 65520 up) or to ±65504 (below it), as that narrowing does.
+ * One order for the whole family: every output element is accumulated from +0 by v_mfma_f32_16x16x32_{bf16,f16} over
+ * the k-steps 0–31, 32–63, … in ascending order, a ragged last step zero-padded.  So the bits of C[i, j] depend only on
+ * row i of op(A), column j of op(B), k and T — not on m, n, the batch size or position, the tile the element lands in,
+ * the storage transposes or the kernel the entry picks.  (Not the fp32 entries' fmaf chain: the MFMA sums 32 products
+ * per step.)
+ * A, B and C: any 2-byte-aligned pointer, any lda / ldb / ldc at least the stored row length (odd values and
+ * column-offset views included; 16-byte-aligned operands with leading dimensions and strides that are multiples of 8
+ * take the vector loads and stores).
+ * Checked before any HIP call: negative sizes or strides, a leading dimension shorter than its row, null or odd
+ * pointers (A and B may be NULL when k == 0) → MI_EINVAL; m == 0, n == 0 or batch == 0 → MI_OK (nothing launched);
+ * k == 0 writes zeros.
+ * mi_gemm_set_plan does not apply to these entries (there is one kernel family).  No float atomics, no split-k, no host
+ * read-back: graph-capturable.  No counterpart in the reference (float32 only: src/baseline_mm.cu:52-155). */
+int mi_gemm_bf16(int transa, int transb, int32_t m, int32_t n, int32_t k,
+                 const uint16_t* A, int64_t lda, int64_t strideA, const uint16_t* B,
+                 int64_t ldb, int64_t strideB, uint16_t* C, int64_t ldc,
+                 int64_t strideC, int32_t batch, mi_stream_t stream);
+int mi_gemm_f16(int transa, int transb, int32_t m, int32_t n, int32_t k,
+                const uint16_t* A, int64_t lda, int64_t strideA, const uint16_t* B,
+                int64_t ldb, int64_t strideB, uint16_t* C, int64_t ldc,
+                int64_t strideC, int32_t batch, mi_stream_t stream);
+
 /* Column sums dst[j] = Σ_r src[r, j] (src rows×n, leading dimension ld): the bias gradient of
  * the FC layers (autograd of `output += self.bias`, reference benchmarks/cublas_fc_layer.py:44-45).
  * Fixed summation order (per row chunk: 4 waves × 4 interleaved row chains, added in a fixed

@@ -143,11 +143,11 @@ mi_stream_t stream_of(const torch::Tensor& t) {
   return static_cast<mi_stream_t>(c10::hip::getCurrentHIPStream(t.device().index()).stream());
 }
 
-// A dense operand as the C-ABI wants it: pointer, leading dimension, batch
+// A dense operand as the C-ABI wants it: pointer (of the tensor's own dtype), leading dimension, batch
 // stride, and whether the stored matrix is the transpose of the logical one.
 struct Operand {
   torch::Tensor keep;  // owns the memory for the duration of the call
-  const float* ptr;
+  const void* ptr;
   int64_t ld;
   int64_t batch_stride;
   bool stored_transposed;
@@ -201,7 +201,7 @@ Operand as_operand(const torch::Tensor& t, int nbatch_dims) {
     TORCH_INTERNAL_ASSERT(layout_of(x, transposed, ld) && batch_stride_of(x, bstride));
   }
   o.keep = x;
-  o.ptr = x.data_ptr<float>();
+  o.ptr = x.data_ptr();
   o.stored_transposed = transposed;
   o.ld = ld;
   o.batch_stride = bstride;
@@ -214,13 +214,19 @@ int64_t batch_count(const torch::Tensor& t, int nbatch_dims) {
   return b;
 }
 
-// C = op(A)·op(B) for `nbatch_dims` leading batch dims.
+// C = op(A)·op(B) for `nbatch_dims` leading batch dims.  float32, or (without a bias) A, B and C all bfloat16 or all
+// float16: the C-ABI's low-precision dense entries (fp32 sums, one rounding per element).
 torch::Tensor gemm_impl(const torch::Tensor& A, const torch::Tensor& B, torch::Tensor C,
                         int nbatch_dims, bool transa, bool transb, const char* what,
                         const torch::Tensor* bias = nullptr) {
-  check_device_f32(A, "A");
-  check_device_f32(B, "B");
-  check_device_f32(C, "C");
+  torch::ScalarType dt = torch::kFloat32;
+  if (bias != nullptr) {  // the fused bias epilogue is float32 only
+    check_device_f32(A, "A");
+    check_device_f32(B, "B");
+    check_device_f32(C, "C");
+  } else {
+    dt = value_dtype(what, {{"A", &A}, {"B", &B}, {"C", &C}}, true);
+  }
   check_same_device(what, C.device(), {&A, &B});
   TORCH_CHECK(C.is_contiguous(), what, ": C must be contiguous");
   TORCH_CHECK(C.dim() == nbatch_dims + 2, what, ": C has the wrong rank");
@@ -238,13 +244,21 @@ torch::Tensor gemm_impl(const torch::Tensor& A, const torch::Tensor& B, torch::T
   check_sizes(what, {m, n, ka, batch});
   const torch::Tensor bias_keep = bias_of(what, bias, n, C);
   c10::hip::HIPGuard guard(C.device().index());
+  if (is_lowp(dt)) {  // no split-k in low precision: one kernel family, one order (include/mi_spmm.h)
+    const auto entry = dt == torch::kBFloat16 ? mi_gemm_bf16 : mi_gemm_f16;
+    const int st = entry(transa != a.stored_transposed, transb != b.stored_transposed, (int32_t)m, (int32_t)n, (int32_t)ka,
+                         static_cast<const uint16_t*>(a.ptr), a.ld, a.batch_stride, static_cast<const uint16_t*>(b.ptr), b.ld,
+                         b.batch_stride, static_cast<uint16_t*>(C.data_ptr()), ld1(n), m * n, (int32_t)batch, stream_of(C));
+    check_status(st, what);
+    return C;
+  }
   // few output tiles and a long k: the fixed split of include/mi_spmm.h ("Deterministic split-k") needs room for its partial sums
   const size_t ws_bytes = mi_gemm_workspace_bytes((int32_t)m, (int32_t)n, (int32_t)ka, (int32_t)batch);
   torch::Tensor ws;
   if (ws_bytes > 0) ws = byte_workspace(C.device(), ws_bytes);
   const int st = mi_gemm_ws_f32(transa != a.stored_transposed, transb != b.stored_transposed,
-                                (int32_t)m, (int32_t)n, (int32_t)ka, a.ptr, a.ld, a.batch_stride,
-                                b.ptr, b.ld, b.batch_stride, f32_or_null(bias_keep), C.data_ptr<float>(),
+                                (int32_t)m, (int32_t)n, (int32_t)ka, static_cast<const float*>(a.ptr), a.ld, a.batch_stride,
+                                static_cast<const float*>(b.ptr), b.ld, b.batch_stride, f32_or_null(bias_keep), C.data_ptr<float>(),
                                 ld1(n), m * n, (int32_t)batch, ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes,
                                 stream_of(C));
   check_status(st, what);

@@ -1,0 +1,306 @@
+// Dense products in bfloat16 and float16 on the matrix cores: C[b] = op(A[b]) · op(B[b]), A, B and C all of one type
+// T ∈ {bf16, fp16} (2-byte bit patterns at the C-ABI), every sum in fp32, one rounding per output element at the store.
+//
+// What it computes (contract of include/mi_spmm.h, mi_gemm_bf16 / _f16 — DESIGN.md §3.9):
+//  * ONE instruction for the whole family: v_mfma_f32_16x16x32_{bf16,f16}.  Each output element is one accumulator,
+//    started at +0 and carried through the k-steps 0–31, 32–63, … in ascending order; a ragged last step is zero-padded
+//    in both operands (zeros written to LDS, nothing read past an operand).  The bits of C[i, j] therefore depend on
+//    row i of op(A), column j of op(B), k and T only — never on m, n, the batch, the tile, the storage transposes or
+//    which tile shape the launcher picks.
+//  * The store narrows once: static_cast to __bf16 / _Float16 (v_cvt_pk_bf16_f32 / v_cvt_f16_f32: NaN stays NaN,
+//    fp16 overflow becomes ±inf).  No integer rounding on the bits.
+//
+// Kernel: a 256-thread workgroup owns a BM × BN tile of one batch item (BM = 128; BN = 128, or 64 for narrow products
+// and for grids too small to fill the chip); 4 waves in 2 × 2, each 16 × 16 MFMA tiles over a 64-deep k-tile.  Both
+// operands are staged through registers into LDS images with k contiguous ([rows][64 + 8] elements: the 144-byte row
+// puts the 16 rows a fragment read touches on 16 different 16-byte bank slots), double-buffered: the global loads of
+// k-tile t + 1 are in flight while the MFMAs of tile t run, one barrier per k-tile.  An operand stored with k
+// contiguous (A plain, B transposed) moves as 16-byte pieces; one stored k-strided (A transposed, B plain) is read as
+// 4 k-rows × 8 elements and transposed in registers into 8-byte LDS writes.  The MFMA takes the B fragment as its first
+// operand, so a lane's four results are four adjacent output COLUMNS of one row; the B rows of a fragment pair are
+// interleaved so that a lane holds eight adjacent columns and stores them as one 16-byte piece.
+// Alignment: the VEC form (operands 16-byte aligned, leading dimensions and item strides multiples of 8 elements, C
+// likewise) uses 16-byte loads and stores wherever a piece lies inside the operand; the checked form (any 2-byte
+// aligned operand, any leading dimension) reads and writes element by element.  Edges are checked in both.
+// No float atomics, no split-k, no host read-back: graph-capturable.
+#include "mi_common.h"
+
+namespace {
+
+using mi::f32x4;
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kBK = 64;        // k per LDS tile (two MFMA k-steps)
+constexpr int kStr = kBK + 8;  // LDS row stride in elements (144 bytes)
+
+struct Bf16 {
+  static __device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ unsigned pack2(float a, float b) {
+    return (unsigned)__builtin_bit_cast(unsigned short, static_cast<__bf16>(a)) |
+           ((unsigned)__builtin_bit_cast(unsigned short, static_cast<__bf16>(b)) << 16);
+  }
+  static __device__ __forceinline__ unsigned short down(float f) { return __builtin_bit_cast(unsigned short, static_cast<__bf16>(f)); }
+};
+struct F16 {
+  static __device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ unsigned pack2(float a, float b) {
+    return (unsigned)__builtin_bit_cast(unsigned short, static_cast<_Float16>(a)) |
+           ((unsigned)__builtin_bit_cast(unsigned short, static_cast<_Float16>(b)) << 16);
+  }
+  static __device__ __forceinline__ unsigned short down(float f) { return __builtin_bit_cast(unsigned short, static_cast<_Float16>(f)); }
+};
+
+struct GemmArgs {
+  const uint16_t* A;
+  const uint16_t* B;
+  uint16_t* C;
+  int m, n, k, batch;
+  long lda, ldb, ldc, sA, sB, sC;
+  int tiles_n;
+};
+
+// 8 contiguous elements p[0 … 7], of which the first `avail` exist (zeros for the rest; nothing read when avail ≤ 0).
+template <bool VEC>
+__device__ __forceinline__ uint4 load8(const uint16_t* p, int avail) {
+  if (VEC && avail >= 8) return *reinterpret_cast<const uint4*>(p);
+  unsigned short e[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) e[j] = j < avail ? p[j] : (unsigned short)0;
+  return uint4{e[0] | ((unsigned)e[1] << 16), e[2] | ((unsigned)e[3] << 16), e[4] | ((unsigned)e[5] << 16),
+               e[6] | ((unsigned)e[7] << 16)};
+}
+
+__device__ __forceinline__ unsigned half_of(uint4 v, int i) {
+  const unsigned w = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
+  return (i & 1) ? (w >> 16) : (w & 0xffffu);
+}
+
+// One operand's R × kBK tile (R rows of the output side, kBK values of k) in registers.
+//  KC (k contiguous: element (r, k) at P[r·ld + k]): R·8 pieces of 8 k-values, R/32 per thread, 8 threads per row.
+//  RC (rows contiguous: element (r, k) at P[k·ld + r]): 2R units of 4 k-rows × 8 rows, one per thread (R = 64: half the
+//  threads), 4 pieces each.  The 16 k-quads of a row group go to 16 consecutive lanes: a wave's 8-byte LDS writes of one
+//  transposed row then fall on 32 different 8-byte bank slots (2-way, the least 512 bytes allow) — with the row groups on
+//  consecutive lanes instead, rows 8 apart sit 1152 ≡ 128 (mod 256) bytes apart and the writes were 8-way.
+template <int R, bool KC>
+struct Stage {
+  static constexpr int kPieces = KC ? R / 32 : 4;
+  uint4 v[kPieces];
+};
+
+template <int R, bool KC, bool VEC>
+__device__ __forceinline__ void load_tile(Stage<R, KC>& s, const uint16_t* P, long ld, int row0, int rows, int k0, int K,
+                                          int tid) {
+  if constexpr (KC) {
+#pragma unroll
+    for (int i = 0; i < Stage<R, KC>::kPieces; ++i) {
+      const int c = tid + i * 256, r = row0 + (c >> 3), kk = k0 + (c & 7) * 8;
+      const int avail = r < rows ? K - kk : 0;
+      s.v[i] = load8<VEC>(P + (long)r * ld + kk, avail);
+    }
+  } else {
+    const int u = tid, r = row0 + (u >> 4) * 8, kk = k0 + (u & 15) * 4;
+    const bool active = u < 2 * R;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int avail = active && kk + q < K ? rows - r : 0;
+      s.v[q] = load8<VEC>(P + (long)(kk + q) * ld + r, avail);
+    }
+  }
+}
+
+template <int R, bool KC>
+__device__ __forceinline__ void store_tile(const Stage<R, KC>& s, unsigned short* S, int tid) {
+  if constexpr (KC) {
+#pragma unroll
+    for (int i = 0; i < Stage<R, KC>::kPieces; ++i) {
+      const int c = tid + i * 256;
+      *reinterpret_cast<uint4*>(S + (c >> 3) * kStr + (c & 7) * 8) = s.v[i];
+    }
+  } else {
+    const int u = tid;
+    if (u < 2 * R) {
+      const int r = (u >> 4) * 8, kk = (u & 15) * 4;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const uint2 w = {half_of(s.v[0], i) | (half_of(s.v[1], i) << 16), half_of(s.v[2], i) | (half_of(s.v[3], i) << 16)};
+        *reinterpret_cast<uint2*>(S + (r + i) * kStr + kk) = w;
+      }
+    }
+  }
+}
+
+template <class T, bool TA, bool TB, int BM, int BN, bool VEC>
+__global__ __launch_bounds__(256) void gemm_lowp_kernel(GemmArgs g) {
+  constexpr int WM = BM / 2, WN = BN / 2, FM = WM / 16, FN = WN / 16;
+  static_assert(FN % 2 == 0, "B fragments go in pairs (interleaved rows: 16-byte stores)");
+  constexpr bool KCA = !TA, KCB = TB;
+  __shared__ __attribute__((aligned(16))) unsigned short smem[2 * (BM + BN) * kStr];
+
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wm = wid >> 1, wn = wid & 1;
+  const int li = lane & 15, lg = lane >> 4;
+  // XCD remap (bijective): consecutive tiles, which share A rows, on one XCD's L2
+  const unsigned total = gridDim.x, bid = blockIdx.x, q8 = total / 8, rem = total % 8, xcd = bid % 8;
+  const unsigned w = xcd * q8 + (xcd < rem ? xcd : rem) + bid / 8;
+  const int m0 = (int)(w / g.tiles_n) * BM, n0 = (int)(w % g.tiles_n) * BN;
+  const int nt = (g.k + kBK - 1) / kBK;
+
+  for (int b = blockIdx.y; b < g.batch; b += gridDim.y) {
+    const uint16_t* A = g.A + (long)b * g.sA;
+    const uint16_t* B = g.B + (long)b * g.sB;
+    f32x4 acc[FM][FN];
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    Stage<BM, KCA> sa;
+    Stage<BN, KCB> sb;
+    load_tile<BM, KCA, VEC>(sa, A, g.lda, m0, g.m, 0, g.k, tid);
+    load_tile<BN, KCB, VEC>(sb, B, g.ldb, n0, g.n, 0, g.k, tid);
+    store_tile<BM, KCA>(sa, smem, tid);
+    store_tile<BN, KCB>(sb, smem + BM * kStr, tid);
+    __syncthreads();
+
+    for (int t = 0; t < nt; ++t) {
+      const bool more = t + 1 < nt;
+      if (more) {
+        load_tile<BM, KCA, VEC>(sa, A, g.lda, m0, g.m, (t + 1) * kBK, g.k, tid);
+        load_tile<BN, KCB, VEC>(sb, B, g.ldb, n0, g.n, (t + 1) * kBK, g.k, tid);
+      }
+      const unsigned short* As = smem + (t & 1) * (BM + BN) * kStr;
+      const unsigned short* Bs = As + BM * kStr;
+#pragma unroll
+      for (int ks = 0; ks < kBK / 32; ++ks) {
+        const int kofs = ks * 32 + 8 * lg;
+        uint4 af[FM], bf[FN];
+#pragma unroll
+        for (int i = 0; i < FM; ++i) af[i] = *reinterpret_cast<const uint4*>(As + (wm * WM + i * 16 + li) * kStr + kofs);
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {
+          // fragment pair j/2: row li of fragment j holds column 32(j/2) + 8(li/4) + 4(j%2) + li%4 of the wave's tile
+          const int col = wn * WN + (j >> 1) * 32 + 8 * (li >> 2) + 4 * (j & 1) + (li & 3);
+          bf[j] = *reinterpret_cast<const uint4*>(Bs + col * kStr + kofs);
+        }
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j) acc[i][j] = T::mfma(bf[j], af[i], acc[i][j]);
+      }
+      if (more) {
+        unsigned short* Sn = smem + ((t + 1) & 1) * (BM + BN) * kStr;
+        store_tile<BM, KCA>(sa, Sn, tid);
+        store_tile<BN, KCB>(sb, Sn + BM * kStr, tid);
+      }
+      __syncthreads();
+    }
+
+    // store: lane (li, lg) holds row li of each 16-row fragment and columns 8·lg … 8·lg + 7 of each fragment pair
+    uint16_t* C = g.C + (long)b * g.sC;
+#pragma unroll
+    for (int i = 0; i < FM; ++i) {
+      const int r = m0 + wm * WM + i * 16 + li;
+      if (r >= g.m) continue;
+#pragma unroll
+      for (int p = 0; p < FN / 2; ++p) {
+        const int c = n0 + wn * WN + p * 32 + 8 * lg;
+        const f32x4 x = acc[i][2 * p], y = acc[i][2 * p + 1];
+        uint16_t* dst = C + (long)r * g.ldc + c;
+        if (VEC && c + 8 <= g.n) {
+          *reinterpret_cast<uint4*>(dst) =
+              uint4{T::pack2(x[0], x[1]), T::pack2(x[2], x[3]), T::pack2(y[0], y[1]), T::pack2(y[2], y[3])};
+        } else {
+          const float v[8] = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (c + e < g.n) dst[e] = T::down(v[e]);
+        }
+      }
+    }
+  }
+}
+
+// k == 0: C = 0 (beta = 0 semantics)
+__global__ void zero_b16_kernel(uint16_t* C, int m, int n, long ldc, long strideC, int batch) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)m * n) return;
+  for (int b = blockIdx.y; b < batch; b += gridDim.y) C[b * strideC + (idx / n) * ldc + (idx % n)] = 0;
+}
+
+template <class T, bool TA, bool TB, int BM, int BN>
+int launch(const GemmArgs& g, bool vec, hipStream_t s) {
+  const long tiles = (long)((g.m + BM - 1) / BM) * ((g.n + BN - 1) / BN);
+  if (tiles > 0x7fffffffL) return MI_ERANGE;
+  GemmArgs a = g;
+  a.tiles_n = (g.n + BN - 1) / BN;
+  const dim3 grid((unsigned)tiles, (unsigned)(g.batch < 65535 ? g.batch : 65535));
+  if (vec)
+    hipLaunchKernelGGL((gemm_lowp_kernel<T, TA, TB, BM, BN, true>), grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((gemm_lowp_kernel<T, TA, TB, BM, BN, false>), grid, dim3(256), 0, s, a);
+  return mi::check_launch();
+}
+
+// The tile shape: 128 × 128 while that fills the chip, else 128 × 64 (and always for n ≤ 64: the attention
+// context product probs·V and the like).  Same bits either way.
+template <class T, bool TA, bool TB>
+int pick(const GemmArgs& g, bool vec, hipStream_t s) {
+  const long wide = (long)((g.m + 127) / 128) * ((g.n + 127) / 128) * g.batch;
+  if (g.n <= 64 || wide < 512) return launch<T, TA, TB, 128, 64>(g, vec, s);
+  return launch<T, TA, TB, 128, 128>(g, vec, s);
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+template <class T>
+int gemm_lowp(int transa, int transb, int32_t m, int32_t n, int32_t k, const uint16_t* A, int64_t lda, int64_t strideA,
+              const uint16_t* B, int64_t ldb, int64_t strideB, uint16_t* C, int64_t ldc, int64_t strideC, int32_t batch,
+              hipStream_t s) {
+  // every check before the first HIP call
+  if (m < 0 || n < 0 || k < 0 || batch < 0) return MI_EINVAL;
+  if (strideA < 0 || strideB < 0 || strideC < 0) return MI_EINVAL;
+  if (lda < (transa ? m : k) || ldb < (transb ? k : n) || ldc < n) return MI_EINVAL;
+  if (m == 0 || n == 0 || batch == 0) return MI_OK;
+  if (!C || (k > 0 && (!A || !B))) return MI_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) & 1u)
+    return MI_EINVAL;
+  if (lda > 0x7fffffffL || ldb > 0x7fffffffL || ldc > 0x7fffffffL) return MI_ERANGE;
+  if (k == 0) {
+    const long total = (long)m * n, blocks = (total + 255) / 256;
+    if (blocks > 0x7fffffffL) return MI_ERANGE;
+    hipLaunchKernelGGL(zero_b16_kernel, dim3((unsigned)blocks, (unsigned)(batch < 65535 ? batch : 65535)), dim3(256), 0, s, C,
+                       m, n, (long)ldc, (long)strideC, batch);
+    return mi::check_launch();
+  }
+  const bool vec = aligned16(A) && aligned16(B) && aligned16(C) && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0 &&
+                   strideA % 8 == 0 && strideB % 8 == 0 && strideC % 8 == 0;
+  const GemmArgs g = {A, B, C, m, n, k, batch, (long)lda, (long)ldb, (long)ldc, (long)strideA, (long)strideB, (long)strideC, 0};
+  if (!transa && !transb) return pick<T, false, false>(g, vec, s);
+  if (!transa && transb) return pick<T, false, true>(g, vec, s);
+  if (transa && !transb) return pick<T, true, false>(g, vec, s);
+  return pick<T, true, true>(g, vec, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_gemm_bf16(int transa, int transb, int32_t m, int32_t n, int32_t k, const uint16_t* A, int64_t lda, int64_t strideA,
+                 const uint16_t* B, int64_t ldb, int64_t strideB, uint16_t* C, int64_t ldc, int64_t strideC, int32_t batch,
+                 mi_stream_t stream) {
+  return gemm_lowp<Bf16>(transa, transb, m, n, k, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, batch,
+                         static_cast<hipStream_t>(stream));
+}
+
+int mi_gemm_f16(int transa, int transb, int32_t m, int32_t n, int32_t k, const uint16_t* A, int64_t lda, int64_t strideA,
+                const uint16_t* B, int64_t ldb, int64_t strideB, uint16_t* C, int64_t ldc, int64_t strideC, int32_t batch,
+                mi_stream_t stream) {
+  return gemm_lowp<F16>(transa, transb, m, n, k, A, lda, strideA, B, ldb, strideB, C, ldc, strideC, batch,
+                        static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

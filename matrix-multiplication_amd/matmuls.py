@@ -76,6 +76,20 @@ def _host_operands(a: torch.Tensor, b: torch.Tensor) -> bool:
             and a.dim() >= 1 and b.dim() >= 1)
 
 
+_LOWP = (torch.bfloat16, torch.float16)
+
+
+def _dense_out_dtype(a: torch.Tensor, b: torch.Tensor, what: str) -> torch.dtype:
+    '''The dtype of a dense product's output: bfloat16 / float16 when both operands are of it, float32 for every other
+    pair of one dtype; a low-precision operand with an operand of another dtype is refused, naming both.'''
+    if a.dtype in _LOWP or b.dtype in _LOWP:
+        if a.dtype != b.dtype:
+            raise RuntimeError(f'{what}: a is {a.dtype} but b is {b.dtype}: a low-precision product needs both operands '
+                               'in one dtype (bfloat16 or float16)')
+        return a.dtype
+    return torch.float32
+
+
 def custom_matmul(a: torch.Tensor,
                   b: torch.Tensor,
                   mm_op=custom_mm.cublas_mmul,
@@ -97,6 +111,7 @@ def custom_matmul(a: torch.Tensor,
     :param transb: transpose B
     :returns: Matrix multiplication output
     '''
+    out_dtype = _dense_out_dtype(a, b, 'custom_matmul')
     if _host_operands(a, b):
         # BASELINE.json configs[0] as written ("torch.mm dense 8×64 @ 64×8 on CPU via the matmuls.py wrapper"): both operands are
         # dense HOST tensors, nothing asks for the GPU — the reference's own expression for the ranks its kernels do not take,
@@ -110,8 +125,10 @@ def custom_matmul(a: torch.Tensor,
                              transb if b.dim() > 1 else False).squeeze(dims)
 
     batch, c_rows, c_cols = _out_shape(a.shape, b.shape, transa, transb)
-    # create tensor C to store results in (beta = 0: no need to pre-zero it)
-    c = torch.empty(batch + (c_rows, c_cols), device=a.device, dtype=torch.float32)
+    # create tensor C to store results in (beta = 0: no need to pre-zero it): in the operands' dtype when both are
+    # bfloat16 or both float16 (fp32 sums, one rounding per element), float32 otherwise (custom_mm refuses what it
+    # does not take)
+    c = torch.empty(batch + (c_rows, c_cols), device=a.device, dtype=out_dtype)
 
     if len(batch) == 0:
         return mm_op(a, b, c, transa, transb)
@@ -160,10 +177,11 @@ def _dense_backward(ctx, grad_output, transa, transb):
         g = g.unsqueeze(d)
 
     if (_fused_pair and not ta and tb and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and a.dim() >= 3 and
+            a.dtype == b.dtype == g.dtype == torch.float32 and
             tuple(a.shape[:-2]) == tuple(b.shape[:-2]) == tuple(g.shape[:-2]) and hasattr(custom_mm, 'cublas_bmm_pair')):
         # C = A·Bᵀ (the BERT drop-in scores = cublasTransbMM.apply(q, k), README.md:69-77): dA = dC·B and dB = dCᵀ·A both
         # stream dC — one fused launch reads it once (custom_mm.cublas_bmm_pair; same bits as the two plain products,
-        # False when the shapes are not its)
+        # False when the shapes are not its).  float32 only: bfloat16 / float16 run the two plain products below
         gc, ac, bc = g.contiguous(), a.contiguous(), b.contiguous()
         ga, gb = torch.empty_like(ac), torch.empty_like(bc)
         if custom_mm.cublas_bmm_pair(gc, bc, ac, ga, gb):
