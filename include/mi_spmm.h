@@ -608,8 +608,9 @@ int mi_gather_b16(const uint16_t* src, const int32_t* perm, int64_t n, uint16_t*
  * Checked before any HIP call: negative sizes or strides, a leading dimension shorter than its row, null or odd
  * pointers (A and B may be NULL when k == 0) → MI_EINVAL; m == 0, n == 0 or batch == 0 → MI_OK (nothing launched);
  * k == 0 writes zeros.
- * mi_gemm_set_plan does not apply to these entries (there is one kernel family).  No float atomics, no split-k, no host
- * read-back: graph-capturable.  No counterpart in the reference (float32 only: src/baseline_mm.cu:52-155). */
+ * mi_gemm_set_plan does not apply to these entries (there is one kernel family).  No float atomics, no split-k (that is
+ * mi_gemm_ws_bf16 / _f16 below), no host read-back: graph-capturable.  No counterpart in the reference (float32 only:
+ * src/baseline_mm.cu:52-155). */
 int mi_gemm_bf16(int transa, int transb, int32_t m, int32_t n, int32_t k,
                  const uint16_t* A, int64_t lda, int64_t strideA, const uint16_t* B,
                  int64_t ldb, int64_t strideB, uint16_t* C, int64_t ldc,
@@ -619,6 +620,54 @@ int mi_gemm_f16(int transa, int transb, int32_t m, int32_t n, int32_t k,
                 int64_t ldb, int64_t strideB, uint16_t* C, int64_t ldc,
                 int64_t strideC, int32_t batch, mi_stream_t stream);
 
+/* The fused FC epilogue in low precision: mi_gemm_bf16 / _f16 with a bias of the same type T,
+ *   C[b][i, j] = rne_T(acc[i, j] + up(bias[j])),
+ * acc the fp32 accumulator the plain entry would narrow (same k-loop, same order), up() the exact widening of bias[j],
+ * one fp32 add, ONE rounding per element.  bias: n elements, any 2-byte-aligned pointer (16-byte aligned for the vector
+ * form), or NULL — then the entry IS the plain one (same kernel, same bits).  Checked before any HIP call as there, an
+ * odd bias pointer included → MI_EINVAL; k == 0 writes the bias into every row (zeros without one).  Never splits k. */
+int mi_gemm_bias_bf16(int transa, int transb, int32_t m, int32_t n, int32_t k,
+                      const uint16_t* A, int64_t lda, int64_t strideA, const uint16_t* B,
+                      int64_t ldb, int64_t strideB, const uint16_t* bias, uint16_t* C, int64_t ldc,
+                      int64_t strideC, int32_t batch, mi_stream_t stream);
+int mi_gemm_bias_f16(int transa, int transb, int32_t m, int32_t n, int32_t k,
+                     const uint16_t* A, int64_t lda, int64_t strideA, const uint16_t* B,
+                     int64_t ldb, int64_t strideB, const uint16_t* bias, uint16_t* C, int64_t ldc,
+                     int64_t strideC, int32_t batch, mi_stream_t stream);
+
+/* Deterministic split-k in low precision, for products with a long k and few output tiles (the FC weight gradient
+ * dYᵀ·x over thousands of tokens), which leave most of the chip idle as one accumulator per element.
+ * mi_gemm_lowp_split_count(m, n, k, batch) is a function of the SHAPE alone: 1 unless batch == 1, k ≥ 2048 and at most
+ * 576 output tiles of 128 × 128; else S = the largest power of two ≤ min(2048 / tiles, k / 256, 32), halved until
+ * k % (32·S) == 0 (whole MFMA k-steps per range).  (Not mi_gemm_split_count: another tile, sixteen times the MFMA rate.)
+ * With S > 1, k is cut into S equal ranges; range s runs the family order of mi_gemm_bf16 from +0 into an fp32 partial
+ * P[s] (not narrowed), and
+ *   C[i, j] = rne_T((((P[0] + P[1]) + P[2]) + …) + up(bias[j]))
+ * with fp32 round-to-nearest adds in index order, the bias (optional) last: one rounding to T per element, no float
+ * atomics, no host read-back, graph-capturable, the same bits on every run.  S == 1 calls mi_gemm_bias_*: its bits.
+ * workspace ≥ mi_gemm_lowp_workspace_bytes (S·m·n·4 for S > 1, else 0), 16-byte aligned: NULL or unaligned with S > 1
+ * → MI_EINVAL, too small → MI_ENOMEM, never a silent unsplit product (the order is part of the result).  Other checks
+ * as mi_gemm_bias_*, all before any HIP call.
+ * mi_gemm_split_bf16 / _f16 take the number of ranges from the caller (one product; splits ≥ 1, k % (32·splits) == 0,
+ * else MI_EINVAL; workspace ≥ splits·m·n·4): what mi_gemm_ws_* run with splits = mi_gemm_lowp_split_count, and how the
+ * rule's grid is measured (tools/bench_gemm_lowp_split.py). */
+int mi_gemm_lowp_split_count(int32_t m, int32_t n, int32_t k, int32_t batch);
+size_t mi_gemm_lowp_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t batch);
+int mi_gemm_ws_bf16(int transa, int transb, int32_t m, int32_t n, int32_t k,
+                    const uint16_t* A, int64_t lda, int64_t strideA, const uint16_t* B,
+                    int64_t ldb, int64_t strideB, const uint16_t* bias, uint16_t* C, int64_t ldc,
+                    int64_t strideC, int32_t batch, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_gemm_ws_f16(int transa, int transb, int32_t m, int32_t n, int32_t k,
+                   const uint16_t* A, int64_t lda, int64_t strideA, const uint16_t* B,
+                   int64_t ldb, int64_t strideB, const uint16_t* bias, uint16_t* C, int64_t ldc,
+                   int64_t strideC, int32_t batch, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_gemm_split_bf16(int transa, int transb, int32_t m, int32_t n, int32_t k, const uint16_t* A, int64_t lda,
+                       const uint16_t* B, int64_t ldb, const uint16_t* bias, uint16_t* C, int64_t ldc, int32_t splits,
+                       void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_gemm_split_f16(int transa, int transb, int32_t m, int32_t n, int32_t k, const uint16_t* A, int64_t lda,
+                      const uint16_t* B, int64_t ldb, const uint16_t* bias, uint16_t* C, int64_t ldc, int32_t splits,
+                      void* workspace, size_t workspace_bytes, mi_stream_t stream);
+
 /* Column sums dst[j] = Σ_r src[r, j] (src rows×n, leading dimension ld): the bias gradient of
  * the FC layers (autograd of `output += self.bias`, reference benchmarks/cublas_fc_layer.py:44-45).
  * Fixed summation order (per row chunk: 4 waves × 4 interleaved row chains, added in a fixed
@@ -626,6 +675,15 @@ int mi_gemm_f16(int transa, int transb, int32_t m, int32_t n, int32_t k,
  * workspace ≥ mi_colsum_workspace_bytes(rows, n). */
 size_t mi_colsum_workspace_bytes(int32_t rows, int32_t n);
 int mi_colsum_f32(const float* src, int32_t rows, int32_t n, int64_t ld, float* dst,
+                  void* workspace, size_t workspace_bytes, mi_stream_t stream);
+/* … of bfloat16 / float16 values (the bias gradient of a low-precision layer): widened on load, the SAME fp32 order and
+ * fp32 partials in the same workspace (mi_colsum_workspace_bytes serves all three), one rounding at the store:
+ *   mi_colsum_T(src) == rne_T(mi_colsum_f32(up(src)))   bit for bit.
+ * src, dst: 2-byte aligned (odd → MI_EINVAL); 8-byte loads of 4 columns when n and ld are multiples of 4 and src is
+ * 8-byte aligned, 2-byte elements otherwise (odd ld, column-offset views). */
+int mi_colsum_bf16(const uint16_t* src, int32_t rows, int32_t n, int64_t ld, uint16_t* dst,
+                   void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_colsum_f16(const uint16_t* src, int32_t rows, int32_t n, int64_t ld, uint16_t* dst,
                   void* workspace, size_t workspace_bytes, mi_stream_t stream);
 
 /* Dense 2-D transpose  dst[cols, rows] = src[rows, cols]ᵀ (row-major, ld's). */

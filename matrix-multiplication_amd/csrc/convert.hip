@@ -255,9 +255,39 @@ int colsum_chunk_rows(int rows) {
   return c;
 }
 
-// VEC: lane ↔ 4 consecutive columns (16-B loads, 256 columns per wave and row); else lane ↔ column.
-template <bool VEC>
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ src, int rows, int n,
+// Element types of the column sums: float, or a 2-byte type widened on load (exactly) and rounded once at the store
+// (round-to-nearest-even: the narrowing of gemm_lowp.hip).  The fp32 summation order does not depend on the type.
+struct ColF32 {
+  using elem = float;
+  static __device__ __forceinline__ float up(float v) { return v; }
+  static __device__ __forceinline__ float down(float v) { return v; }
+  static __device__ __forceinline__ mi::f32x4 load4(const float* p) { return *reinterpret_cast<const mi::f32x4*>(p); }
+};
+struct ColBf16 {
+  using elem = uint16_t;
+  static __device__ __forceinline__ float up(uint16_t h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
+  static __device__ __forceinline__ uint16_t down(float v) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(v)); }
+  static __device__ __forceinline__ mi::f32x4 load4(const uint16_t* p) {
+    const uint2 w = *reinterpret_cast<const uint2*>(p);
+    return mi::f32x4{__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
+                     __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u)};
+  }
+};
+struct ColF16 {
+  using elem = uint16_t;
+  static __device__ __forceinline__ float up(uint16_t h) { return static_cast<float>(__builtin_bit_cast(_Float16, h)); }
+  static __device__ __forceinline__ uint16_t down(float v) { return __builtin_bit_cast(uint16_t, static_cast<_Float16>(v)); }
+  static __device__ __forceinline__ mi::f32x4 load4(const uint16_t* p) {
+    const uint2 w = *reinterpret_cast<const uint2*>(p);
+    return mi::f32x4{up((uint16_t)(w.x & 0xffffu)), up((uint16_t)(w.x >> 16)), up((uint16_t)(w.y & 0xffffu)),
+                     up((uint16_t)(w.y >> 16))};
+  }
+};
+
+// VEC: lane ↔ 4 consecutive columns (one 16-B load of floats or 8-B load of 2-byte values; 256 columns per wave and
+// row); else lane ↔ column.
+template <class E, bool VEC>
+__global__ __launch_bounds__(256) void colsum_partial_kernel(const typename E::elem* __restrict__ src, int rows, int n,
                                                              long ld, int chunk_rows, float* __restrict__ partial) {
   constexpr int W = VEC ? 4 : 1;
   __shared__ float part[4][64 * W];
@@ -276,15 +306,15 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
       for (int u = 0; u < 4; ++u) {
         const int rr = r + 4 * u;
         if (rr < r1) {
-          const float* p = src + (long)rr * ld + colj;
+          const typename E::elem* p = src + (long)rr * ld + colj;
           if constexpr (VEC) {
-            const mi::f32x4 v = *reinterpret_cast<const mi::f32x4*>(p);
+            const mi::f32x4 v = E::load4(p);
             acc[u][0] += v.x;
             acc[u][1] += v.y;
             acc[u][2] += v.z;
             acc[u][3] += v.w;
           } else {
-            acc[u][0] += p[0];
+            acc[u][0] += E::up(p[0]);
           }
         }
       }
@@ -303,8 +333,9 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __rest
 }
 
 // dst[j] = Σ_c partial[c][j]: 64 columns per workgroup, the 4 waves take chunks w, w+4, …
+template <class E>
 __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restrict__ partial, int chunks, int n,
-                                                           float* __restrict__ dst) {
+                                                           typename E::elem* __restrict__ dst) {
   __shared__ float part[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = blockIdx.x * 64 + lane;
@@ -319,7 +350,7 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
   }
   part[wave][lane] = a0 + a1;
   __syncthreads();
-  if (wave == 0 && j < n) dst[j] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
+  if (wave == 0 && j < n) dst[j] = E::down(((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]);
 }
 
 // SDDMM on A's pattern (the gradient of C = A·B with respect to A's stored values):
@@ -546,6 +577,35 @@ __global__ __launch_bounds__(256) void gather_perm_kernel(const float* __restric
   }
 }
 
+// The column sums of every element type; the 4-column loads need n and ld multiples of 4 and src aligned to 4 elements.
+template <class E>
+int colsum_any(const typename E::elem* src, int32_t rows, int32_t n, int64_t ld, typename E::elem* dst, void* workspace,
+               size_t workspace_bytes, hipStream_t s) {
+  using elem = typename E::elem;
+  if (rows < 0 || n < 0) return MI_EINVAL;
+  if (n == 0) return MI_OK;
+  if (!dst) return MI_EINVAL;
+  if (sizeof(elem) == 2 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 1u)) return MI_EINVAL;
+  if (rows == 0) {
+    MI_HIP_TRY(hipMemsetAsync(dst, 0, sizeof(elem) * (size_t)n, s));
+    return MI_OK;
+  }
+  if (!src || ld < n || !workspace) return MI_EINVAL;
+  if (workspace_bytes < mi_colsum_workspace_bytes(rows, n)) return MI_ENOMEM;
+  const int cr = colsum_chunk_rows(rows);
+  const int chunks = (rows + cr - 1) / cr;
+  if (chunks > 65535) return MI_ERANGE;
+  float* partial = static_cast<float*>(workspace);
+  if (n % 4 == 0 && ld % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & (4 * sizeof(elem) - 1)) == 0)
+    hipLaunchKernelGGL((colsum_partial_kernel<E, true>), dim3((unsigned)((n + 255) / 256), (unsigned)chunks), dim3(256), 0,
+                       s, src, rows, n, (long)ld, cr, partial);
+  else
+    hipLaunchKernelGGL((colsum_partial_kernel<E, false>), dim3((unsigned)((n + 63) / 64), (unsigned)chunks), dim3(256), 0,
+                       s, src, rows, n, (long)ld, cr, partial);
+  hipLaunchKernelGGL(colsum_final_kernel<E>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, partial, chunks, n, dst);
+  return mi::check_launch();
+}
+
 }  // namespace
 
 
@@ -725,28 +785,17 @@ size_t mi_colsum_workspace_bytes(int32_t rows, int32_t n) {
 
 int mi_colsum_f32(const float* src, int32_t rows, int32_t n, int64_t ld, float* dst, void* workspace,
                   size_t workspace_bytes, mi_stream_t stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (rows < 0 || n < 0) return MI_EINVAL;
-  if (n == 0) return MI_OK;
-  if (!dst) return MI_EINVAL;
-  if (rows == 0) {
-    MI_HIP_TRY(hipMemsetAsync(dst, 0, sizeof(float) * (size_t)n, s));
-    return MI_OK;
-  }
-  if (!src || ld < n || !workspace) return MI_EINVAL;
-  if (workspace_bytes < mi_colsum_workspace_bytes(rows, n)) return MI_ENOMEM;
-  const int cr = colsum_chunk_rows(rows);
-  const int chunks = (rows + cr - 1) / cr;
-  if (chunks > 65535) return MI_ERANGE;
-  float* partial = static_cast<float*>(workspace);
-  if (n % 4 == 0 && ld % 4 == 0 && mi::aligned16(src))
-    hipLaunchKernelGGL(colsum_partial_kernel<true>, dim3((unsigned)((n + 255) / 256), (unsigned)chunks), dim3(256), 0,
-                       s, src, rows, n, (long)ld, cr, partial);
-  else
-    hipLaunchKernelGGL(colsum_partial_kernel<false>, dim3((unsigned)((n + 63) / 64), (unsigned)chunks), dim3(256), 0,
-                       s, src, rows, n, (long)ld, cr, partial);
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, partial, chunks, n, dst);
-  return mi::check_launch();
+  return colsum_any<ColF32>(src, rows, n, ld, dst, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int mi_colsum_bf16(const uint16_t* src, int32_t rows, int32_t n, int64_t ld, uint16_t* dst, void* workspace,
+                   size_t workspace_bytes, mi_stream_t stream) {
+  return colsum_any<ColBf16>(src, rows, n, ld, dst, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int mi_colsum_f16(const uint16_t* src, int32_t rows, int32_t n, int64_t ld, uint16_t* dst, void* workspace,
+                  size_t workspace_bytes, mi_stream_t stream) {
+  return colsum_any<ColF16>(src, rows, n, ld, dst, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int mi_gather_f32(const float* src, const int32_t* perm, int64_t n, float* dst, mi_stream_t stream) {

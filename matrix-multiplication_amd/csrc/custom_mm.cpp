@@ -132,6 +132,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("naive_spmm_dense_gated", &naive_spmm_dense_gated,
         "naive_spmm_dense as a launch that runs only when flag[0] != 0 on the device; (A, B, C, flag, dry_run) -> covered?");
   m.def("cublas_mmul_bias", &cublas_mmul_bias, "op(A) op(B) + bias, fused epilogue");
+  m.def("cublas_mmul_splitk", &cublas_mmul_splitk, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("transa"), py::arg("transb"),
+        py::arg("bias") = py::none(), py::arg("splits") = 0,
+        "bfloat16 / float16 op(A) op(B) (+ bias) with the deterministic split of k (splits = 0: the rule of gemm_lowp_split_count)");
+  m.def("gemm_lowp_split_count", &gemm_lowp_split_count, "ranges cublas_mmul_splitk cuts k into for an m x n x k product (shape only)");
   m.def("column_sums", &column_sums, "sum over rows of a 2-d tensor (bias gradient)");
   m.def("naive_spmm_bias", &naive_spmm_bias, "CSR x dense + bias, fused epilogue");
   m.def("naive_spmm_ex", &naive_spmm_ex, "naive_spmm with the long-row rule pinned (-1 auto, 0 none, 1 split)");

@@ -124,15 +124,24 @@ std::pair<torch::Tensor, int64_t> batched_b(const char* what, const torch::Tenso
   return {B.contiguous(), 0};
 }
 
-// The float32 bias [N] of a fused epilogue, contiguous (undefined when there is none).
-torch::Tensor bias_of(const char* what, const torch::Tensor* bias, int64_t N, const torch::Tensor& C) {
+// The bias [N] of a fused epilogue, contiguous (undefined when there is none): float32, or — where the entry's operands
+// are bfloat16 / float16 (`dt`, the dense epilogue only) — of the operands' dtype.
+torch::Tensor bias_of(const char* what, const torch::Tensor* bias, int64_t N, const torch::Tensor& C,
+                      torch::ScalarType dt = torch::kFloat32) {
   if (bias == nullptr || !bias->defined()) return torch::Tensor();
-  check_device_f32(*bias, "bias");
+  if (is_lowp(dt)) {
+    TORCH_CHECK(bias->scalar_type() == dt, what, ": C is ", dt, " but bias is ", bias->scalar_type(),
+                ": the bias must share the operands' dtype");
+    TORCH_CHECK(bias->is_cuda(), "bias must be a device (HIP) tensor; custom_mm has no CPU path");
+  } else {
+    check_device_f32(*bias, "bias");
+  }
   check_same_device(what, C.device(), {bias});
   TORCH_CHECK(bias->dim() == 1 && bias->size(0) == N, what, ": bias must have ", N, " entries");
   return bias->contiguous();
 }
 const float* f32_or_null(const torch::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
+const uint16_t* b16_or_null(const torch::Tensor& t) { return t.defined() ? static_cast<const uint16_t*>(t.data_ptr()) : nullptr; }
 
 // A device byte buffer of at least `min_bytes` (C-ABI workspaces; some entries want a non-null pointer even for 0 bytes).
 torch::Tensor byte_workspace(const torch::Device& dev, size_t bytes, size_t min_bytes = 0) {
@@ -214,19 +223,18 @@ int64_t batch_count(const torch::Tensor& t, int nbatch_dims) {
   return b;
 }
 
-// C = op(A)·op(B) for `nbatch_dims` leading batch dims.  float32, or (without a bias) A, B and C all bfloat16 or all
+// C = op(A)·op(B) (+ bias) for `nbatch_dims` leading batch dims.  float32, or A, B, C (and the bias) all bfloat16 or all
 // float16: the C-ABI's low-precision dense entries (fp32 sums, one rounding per element).
+// `lowp_splits` (low precision, one product): < 0 never splits k — cublas_mmul / cublas_bmm / cublas_mmul_bias, whose bits
+// do not depend on m and n; 0 splits by the rule of mi_gemm_lowp_split_count; > 0 into that many ranges.
 torch::Tensor gemm_impl(const torch::Tensor& A, const torch::Tensor& B, torch::Tensor C,
                         int nbatch_dims, bool transa, bool transb, const char* what,
-                        const torch::Tensor* bias = nullptr) {
-  torch::ScalarType dt = torch::kFloat32;
-  if (bias != nullptr) {  // the fused bias epilogue is float32 only
-    check_device_f32(A, "A");
-    check_device_f32(B, "B");
-    check_device_f32(C, "C");
-  } else {
-    dt = value_dtype(what, {{"A", &A}, {"B", &B}, {"C", &C}}, true);
-  }
+                        const torch::Tensor* bias = nullptr, int64_t lowp_splits = -1) {
+  // (a bias beside low-precision operands is one of them: a mismatch names both dtypes, before the device check; beside
+  // float32 operands it keeps the messages of bias_of, which the sparse bias entries share)
+  const bool lowp_bias = bias != nullptr && bias->defined() && is_lowp(A.scalar_type());
+  const torch::ScalarType dt = lowp_bias ? value_dtype(what, {{"A", &A}, {"B", &B}, {"C", &C}, {"bias", bias}}, true)
+                                         : value_dtype(what, {{"A", &A}, {"B", &B}, {"C", &C}}, true);
   check_same_device(what, C.device(), {&A, &B});
   TORCH_CHECK(C.is_contiguous(), what, ": C must be contiguous");
   TORCH_CHECK(C.dim() == nbatch_dims + 2, what, ": C has the wrong rank");
@@ -242,13 +250,32 @@ torch::Tensor gemm_impl(const torch::Tensor& A, const torch::Tensor& B, torch::T
               C.size(-2), "x", C.size(-1));
   const int64_t batch = batch_count(C, nbatch_dims);
   check_sizes(what, {m, n, ka, batch});
-  const torch::Tensor bias_keep = bias_of(what, bias, n, C);
+  const torch::Tensor bias_keep = bias_of(what, bias, n, C, dt);
   c10::hip::HIPGuard guard(C.device().index());
-  if (is_lowp(dt)) {  // no split-k in low precision: one kernel family, one order (include/mi_spmm.h)
-    const auto entry = dt == torch::kBFloat16 ? mi_gemm_bf16 : mi_gemm_f16;
-    const int st = entry(transa != a.stored_transposed, transb != b.stored_transposed, (int32_t)m, (int32_t)n, (int32_t)ka,
-                         static_cast<const uint16_t*>(a.ptr), a.ld, a.batch_stride, static_cast<const uint16_t*>(b.ptr), b.ld,
-                         b.batch_stride, static_cast<uint16_t*>(C.data_ptr()), ld1(n), m * n, (int32_t)batch, stream_of(C));
+  const int ta = transa != a.stored_transposed, tb = transb != b.stored_transposed;
+  if (is_lowp(dt)) {
+    const bool bf = dt == torch::kBFloat16;
+    const uint16_t* pa = static_cast<const uint16_t*>(a.ptr);
+    const uint16_t* pb = static_cast<const uint16_t*>(b.ptr);
+    uint16_t* pc = static_cast<uint16_t*>(C.data_ptr());
+    int st;
+    if (lowp_splits >= 0) {  // one product (nbatch_dims == 0), k cut into a fixed number of ranges
+      const int64_t S = lowp_splits > 0 ? lowp_splits : mi_gemm_lowp_split_count((int32_t)m, (int32_t)n, (int32_t)ka, 1);
+      TORCH_CHECK(S <= 1024, what, ": at most 1024 ranges");
+      const size_t ws_bytes = S > 1 ? (size_t)S * m * n * sizeof(float) : 0;
+      torch::Tensor ws;
+      if (ws_bytes > 0) ws = byte_workspace(C.device(), ws_bytes);
+      st = (bf ? mi_gemm_split_bf16 : mi_gemm_split_f16)(ta, tb, (int32_t)m, (int32_t)n, (int32_t)ka, pa, a.ld, pb, b.ld,
+                                                         b16_or_null(bias_keep), pc, ld1(n), (int32_t)S,
+                                                         ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, stream_of(C));
+    } else if (bias_keep.defined()) {
+      st = (bf ? mi_gemm_bias_bf16 : mi_gemm_bias_f16)(ta, tb, (int32_t)m, (int32_t)n, (int32_t)ka, pa, a.ld, a.batch_stride, pb,
+                                                       b.ld, b.batch_stride, b16_or_null(bias_keep), pc, ld1(n), m * n,
+                                                       (int32_t)batch, stream_of(C));
+    } else {  // no split-k here: one kernel family, one order (include/mi_spmm.h)
+      st = (bf ? mi_gemm_bf16 : mi_gemm_f16)(ta, tb, (int32_t)m, (int32_t)n, (int32_t)ka, pa, a.ld, a.batch_stride, pb, b.ld,
+                                             b.batch_stride, pc, ld1(n), m * n, (int32_t)batch, stream_of(C));
+    }
     check_status(st, what);
     return C;
   }
@@ -256,7 +283,7 @@ torch::Tensor gemm_impl(const torch::Tensor& A, const torch::Tensor& B, torch::T
   const size_t ws_bytes = mi_gemm_workspace_bytes((int32_t)m, (int32_t)n, (int32_t)ka, (int32_t)batch);
   torch::Tensor ws;
   if (ws_bytes > 0) ws = byte_workspace(C.device(), ws_bytes);
-  const int st = mi_gemm_ws_f32(transa != a.stored_transposed, transb != b.stored_transposed,
+  const int st = mi_gemm_ws_f32(ta, tb,
                                 (int32_t)m, (int32_t)n, (int32_t)ka, static_cast<const float*>(a.ptr), a.ld, a.batch_stride,
                                 static_cast<const float*>(b.ptr), b.ld, b.batch_stride, f32_or_null(bias_keep), C.data_ptr<float>(),
                                 ld1(n), m * n, (int32_t)batch, ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes,

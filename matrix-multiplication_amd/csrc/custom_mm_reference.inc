@@ -352,6 +352,26 @@ torch::Tensor cublas_mmul_bias(torch::Tensor A, torch::Tensor B, torch::Tensor b
   return gemm_impl(A, B, C, 0, transa, transb, "cublas_mmul_bias", &bias);
 }
 
+// The deterministic split-k of the low-precision dense product (include/mi_spmm.h, mi_gemm_ws_bf16 / _f16): one 2-d product
+// of bfloat16 / float16 operands, k cut by the rule of gemm_lowp_split_count (or into `splits` ranges), an optional bias of
+// the same dtype in the combine.  cublas_mmul never takes this path; float32 products split inside cublas_mmul itself.
+torch::Tensor cublas_mmul_splitk(torch::Tensor A, torch::Tensor B, torch::Tensor C, bool transa, bool transb,
+                                 c10::optional<torch::Tensor> bias, int64_t splits) {
+  const char* what = "cublas_mmul_splitk";
+  const bool all_f32 = A.scalar_type() == torch::kFloat32 && B.scalar_type() == torch::kFloat32 && C.scalar_type() == torch::kFloat32;
+  TORCH_CHECK(!all_f32, what, ": bfloat16 / float16 operands only; float32 products go through cublas_mmul, which splits k by "
+              "its own rule");
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && C.dim() == 2, what, ": 2-d operands only");
+  TORCH_CHECK(splits >= 0, what, ": splits must be 0 (the rule) or the number of ranges");
+  const torch::Tensor* bp = bias.has_value() && bias->defined() ? &*bias : nullptr;
+  return gemm_impl(A, B, C, 0, transa, transb, what, bp, splits);
+}
+
+int64_t gemm_lowp_split_count(int64_t m, int64_t n, int64_t k) {
+  check_sizes("gemm_lowp_split_count", {m, n, k});
+  return mi_gemm_lowp_split_count((int32_t)m, (int32_t)n, (int32_t)k, 1);
+}
+
 torch::Tensor naive_spmm_bias(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor A_offsets,
                               int64_t nnzA, int64_t A_rows, int64_t A_cols, torch::Tensor B,
                               torch::Tensor bias, torch::Tensor C) {
@@ -426,9 +446,10 @@ void validate_csr(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor
   }
 }
 
-// Column sums of a 2-d tensor (bias gradient of the FC layers): returns a [n] tensor.
+// Column sums of a 2-d tensor (bias gradient of the FC layers): returns a [n] tensor of src's dtype (float32, or bfloat16 /
+// float16: fp32 sums in the float32 order, rounded once).
 torch::Tensor column_sums(torch::Tensor src) {
-  value_dtype("column_sums", {{"src", &src}});
+  const torch::ScalarType dt = value_dtype("column_sums", {{"src", &src}}, true);
   TORCH_CHECK(src.dim() == 2, "column_sums: expected a 2-d tensor");
   const int64_t rows = src.size(0), n = src.size(1);
   check_sizes("column_sums", {rows, n});
@@ -437,9 +458,16 @@ torch::Tensor column_sums(torch::Tensor src) {
   torch::Tensor out = torch::empty({n}, x.options());
   const size_t ws_bytes = mi_colsum_workspace_bytes((int32_t)rows, (int32_t)n);
   torch::Tensor ws = byte_workspace(x.device(), ws_bytes, 4);
-  check_status(mi_colsum_f32(x.data_ptr<float>(), (int32_t)rows, (int32_t)n, rows > 1 ? x.stride(0) : ld1(n),
-                             out.data_ptr<float>(), ws.data_ptr(), ws_bytes, stream_of(x)),
-               "column_sums");
+  const int64_t ld = rows > 1 ? x.stride(0) : ld1(n);
+  int st;
+  if (is_lowp(dt))
+    st = (dt == torch::kBFloat16 ? mi_colsum_bf16 : mi_colsum_f16)(static_cast<const uint16_t*>(x.data_ptr()), (int32_t)rows,
+                                                                    (int32_t)n, ld, static_cast<uint16_t*>(out.data_ptr()),
+                                                                    ws.data_ptr(), ws_bytes, stream_of(x));
+  else
+    st = mi_colsum_f32(x.data_ptr<float>(), (int32_t)rows, (int32_t)n, ld, out.data_ptr<float>(), ws.data_ptr(), ws_bytes,
+                       stream_of(x));
+  check_status(st, "column_sums");
   return out;
 }
 

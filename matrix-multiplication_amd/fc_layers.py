@@ -14,6 +14,11 @@ kernels: grad_inp = dY·W, grad_W = dYᵀ·inp, grad_bias = 1ᵀ·dY.
 
 `cusparseLinear` treats the *activations* as the sparse operand, exactly like the reference
 (`cusparseMM.apply(inp, weight.t())`: exact zeros of `inp` are dropped, e.g. after a ReLU).
+
+bfloat16 / float16: a layer moved with `.to(torch.bfloat16)` takes inputs of that dtype and
+returns it, forward and backward — the product on the matrix cores with the bias in its epilogue, the weight
+gradient through the deterministic split-k (`custom_mm.cublas_mmul_splitk`), the bias gradient by
+`custom_mm.column_sums`; fp32 sums, each element rounded once.  The input and the parameters must share one dtype.
 '''
 
 import math
@@ -31,19 +36,44 @@ def _column_sums(g2d):
     return custom_mm.column_sums(g2d)
 
 
+_LOWP = (torch.bfloat16, torch.float16)
+
+
+def _check_dtypes(inp, weight, bias):
+    '''One dtype for the input and the parameters, named before anything runs (the rule of custom_matmul).'''
+    for name, p in (('weight', weight), ('bias', bias)):
+        if p is not None and p.dtype != inp.dtype:
+            raise RuntimeError('fc_layers: the input is {} but the layer\'s {} is {}: convert one of them '
+                               '(layer.to(dtype) or input.to(dtype))'.format(inp.dtype, name, p.dtype))
+
+
+def _dense_forward(x2, weight, bias, out):
+    if bias is not None:
+        custom_mm.cublas_mmul_bias(x2, weight, bias, out, False, True)
+    else:
+        custom_mm.cublas_mmul(x2, weight, out, False, True)
+
+
+def _weight_grad(g2, x2):
+    '''dYᵀ·x.  bfloat16 / float16: a long k (the tokens) over few output tiles — the deterministic split-k; a shape the
+    rule does not split gets the plain product's bits by construction.'''
+    if g2.dtype in _LOWP:
+        gw = torch.empty((g2.shape[1], x2.shape[1]), device=g2.device, dtype=g2.dtype)
+        return custom_mm.cublas_mmul_splitk(g2, x2, gw, True, False)
+    return custom_matmul(g2, x2, transa=True)
+
+
 class _LinearBias(InplaceFunction):
     '''y = x·Wᵀ (+ bias) with the dense kernel; x [..., in], W [out, in].'''
 
     @staticmethod
     def forward(ctx, inp, weight, bias):
+        _check_dtypes(inp, weight, bias)
         ctx.save_for_backward(inp, weight)
         ctx.has_bias = bias is not None
         x2 = inp.reshape(-1, inp.shape[-1])
-        out = torch.empty((x2.shape[0], weight.shape[0]), device=inp.device, dtype=torch.float32)
-        if bias is not None:
-            custom_mm.cublas_mmul_bias(x2, weight, bias, out, False, True)
-        else:
-            custom_mm.cublas_mmul(x2, weight, out, False, True)
+        out = torch.empty((x2.shape[0], weight.shape[0]), device=inp.device, dtype=inp.dtype)
+        _dense_forward(x2, weight, bias, out)
         return out.view(tuple(inp.shape[:-1]) + (weight.shape[0],))
 
     @staticmethod
@@ -55,7 +85,7 @@ class _LinearBias(InplaceFunction):
         if ctx.needs_input_grad[0]:
             grad_inp = custom_matmul(g2, weight).view(inp.shape)       # dY·W
         if ctx.needs_input_grad[1]:
-            grad_w = custom_matmul(g2, x2, transa=True)                 # dYᵀ·x
+            grad_w = _weight_grad(g2, x2)                               # dYᵀ·x
         if ctx.has_bias and ctx.needs_input_grad[2]:
             grad_b = _column_sums(g2)
         return grad_inp, grad_w, grad_b
@@ -101,16 +131,18 @@ class _SparseLinearBias(InplaceFunction):
 
     @staticmethod
     def forward(ctx, inp, weight, bias):
+        _check_dtypes(inp, weight, bias)
         ctx.has_bias = bias is not None
         x2 = inp.reshape(-1, inp.shape[-1])
         tokens, fin, fout = x2.shape[0], x2.shape[1], weight.shape[0]
-        out = torch.empty((tokens, fout), device=inp.device, dtype=torch.float32)
+        out = torch.empty((tokens, fout), device=inp.device, dtype=inp.dtype)
         csr = None
         capturing = inp.is_cuda and torch.cuda.is_current_stream_capturing()
         ctx.x_density = 1.0
         nnz_arg = 0
         ctx.exact_csr = True
-        if not capturing and x2.numel() > 0 and worth_sampling(tokens, fin, fout):
+        lowp = inp.dtype in _LOWP  # always the dense route: no sample, no conversion (class docstring of cusparseLinear)
+        if not lowp and not capturing and x2.numel() > 0 and worth_sampling(tokens, fin, fout):
             est = sampled_density(x2, ('fc', tuple(x2.shape), fout, inp.device.index), fin, owner=inp,
                                   sample_rows=_SAMPLE_ROWS)
             ctx.x_density = est
@@ -142,10 +174,8 @@ class _SparseLinearBias(InplaceFunction):
                 custom_mm.naive_spmm_bias_ex(csr[0], csr[1], csr[2], nnz_arg, tokens, fin, wt, bias, out, rule)
             else:
                 custom_mm.naive_spmm_ex(csr[0], csr[1], csr[2], nnz_arg, tokens, fin, wt, out, rule)
-        elif bias is not None:
-            custom_mm.cublas_mmul_bias(x2, weight, bias, out, False, True)
         else:
-            custom_mm.cublas_mmul(x2, weight, out, False, True)
+            _dense_forward(x2, weight, bias, out)
         ctx.has_csr = csr is not None
         ctx.save_for_backward(inp, weight, *(csr or ()))
         return out.view(tuple(inp.shape[:-1]) + (fout,))
@@ -163,7 +193,7 @@ class _SparseLinearBias(InplaceFunction):
             # workgroups): the dense product sums the same terms in the same token order, the
             # skipped ones being exact zeros.  Measured at 16384 tokens, 3072 → 768, half zeros:
             # forward + backward 9.1 → 3.6 ms (tools/bench_fc.py).
-            grad_w = custom_matmul(g2, x2, transa=True)
+            grad_w = _weight_grad(g2, x2)
         elif ctx.needs_input_grad[1]:
             # dYᵀ·x = (xᵀ·dY)ᵀ with x sparse: the CSR kept from forward, transposed, then the row-split kernel
             values, columns, offsets = ctx.saved_tensors[2:]
@@ -219,4 +249,11 @@ class cublasLinear(_LinearBase):
 
 
 class cusparseLinear(_LinearBase):
+    '''The layer whose activations' exact zeros are skipped when that pays (float32).
+
+    In bfloat16 / float16 the layer takes the dense route unconditionally — no density sample, no conversion — and so
+    returns exactly what `cublasLinear` returns for the same parameters, forward and backward.  In those dtypes the
+    two routes would sum in different orders (the MFMA's 32-deep k-steps against the CSR kernels' fmaf chain), so
+    "the route never changes the result", which the float32 layer guarantees, could not hold; and a sparse route
+    would need a bias epilogue in the low-precision CSR kernels and a 2-byte dense → CSR conversion.'''
     _fn = _SparseLinearBias
