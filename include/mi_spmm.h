@@ -758,6 +758,58 @@ int mi_spmm_reduce_grad_b_f32(const int32_t* t_rowptr, const int32_t* t_col, con
                               int64_t ldg, const int32_t* arg, int64_t ldarg, float* grad_b, int64_t ldgb,
                               mi_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * The reductions in bfloat16 / float16 (T): val, B, C, G and both gradients of the entry's type T, stored as uint16_t bit
+ * patterns, any 2-byte-aligned pointer (an odd one → MI_EINVAL) and any leading dimension ≥ N (odd values and
+ * column-offset views included); arg stays int32, the workspace that of mi_spmm_csr_reduce_workspace_bytes (its
+ * (value, arg) partials stay fp32 / int32: one size for every dtype).  The rule of the low-precision section above: the
+ * fp32 result of the exactly widened operands (up), narrowed ONCE, at the store (rne_T; NaN stays NaN, its payload is not
+ * part of the contract; fp16 overflow goes to ±inf).  Each entry takes the argument list of its _f32 twin and validates it
+ * the same way, before any HIP call.
+ *   MI_REDUCE_SUM   the bits of mi_spmm_csr_ex_T (MI_LONG_ROWS_SPLIT with a workspace, MI_LONG_ROWS_NONE without).
+ *   MI_REDUCE_MEAN  C = rne_T(C32 / count): C32 the fp32 sum of mi_spmm_csr_ex_T's contract (long rows split, the
+ *                   CSR-order fmaf chain, the butterfly for N < 4), "/" the correctly rounded fp32 division of
+ *                   mi_spmm_rows_divide_f32, an empty row +0.  ONE narrowing: the sum is NOT narrowed to T and then
+ *                   divided (that is a second rounding and other bits).  The division is the epilogue of the sum kernels.
+ *   MI_REDUCE_AMAX / _AMIN  p_e = up(val[e]) · up(B[col[e], j]), one fp32 multiply (exact for both types wherever it
+ *                   neither overflows nor underflows fp32); the selection rule of mi_spmm_csr_reduce_f32 applied to these
+ *                   fp32 products; C = rne_T(p_arg) and arg the fp32 path's arg for the widened operands — never a choice
+ *                   among values that only tie after narrowing.  fp16: a selected product beyond 65504 is stored as ±inf
+ *                   while arg stays the fp32 choice.
+ * mi_spmm_rows_divide_T: out = rne_T(up(in) / count), rows without entries copied; in == out allowed.
+ * mi_spmm_reduce_grad_val_T = rne_T(mi_spmm_reduce_grad_val_f32(up(B), up(G), arg)) and mi_spmm_reduce_grad_b_T =
+ * rne_T(mi_spmm_reduce_grad_b_f32(up(val), up(G), arg)): the fp32 kernels' summation orders, no float atomics.
+ * The gradient of MEAN (matmuls.sparse_mm_reduce): g' = rne_T(up(g) / count) is materialised in T by
+ * mi_spmm_rows_divide_T, then the T sum backward runs on g' (mi_sddmm_csr_T; mi_spmm_csr_ex_T on Aᵀ) — this extra rounding
+ * of g' is part of the contract.
+ * ------------------------------------------------------------------------ */
+int mi_spmm_csr_reduce_bf16(const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz,
+                            int32_t M, int32_t K, int32_t N, const uint16_t* B, int64_t ldb, uint16_t* C,
+                            int64_t ldc, int32_t* arg, int64_t ldarg, int reduce, void* workspace,
+                            size_t workspace_bytes, mi_stream_t stream);
+int mi_spmm_csr_reduce_f16(const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz,
+                           int32_t M, int32_t K, int32_t N, const uint16_t* B, int64_t ldb, uint16_t* C,
+                           int64_t ldc, int32_t* arg, int64_t ldarg, int reduce, void* workspace,
+                           size_t workspace_bytes, mi_stream_t stream);
+int mi_spmm_rows_divide_bf16(const int32_t* rowptr, int32_t M, int32_t N, const uint16_t* in, int64_t ldin,
+                             uint16_t* out, int64_t ldout, mi_stream_t stream);
+int mi_spmm_rows_divide_f16(const int32_t* rowptr, int32_t M, int32_t N, const uint16_t* in, int64_t ldin,
+                            uint16_t* out, int64_t ldout, mi_stream_t stream);
+int mi_spmm_reduce_grad_val_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M, int32_t K,
+                                 int32_t N, const uint16_t* B, int64_t ldb, const uint16_t* G, int64_t ldg,
+                                 const int32_t* arg, int64_t ldarg, uint16_t* grad_val, mi_stream_t stream);
+int mi_spmm_reduce_grad_val_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M, int32_t K,
+                                int32_t N, const uint16_t* B, int64_t ldb, const uint16_t* G, int64_t ldg,
+                                const int32_t* arg, int64_t ldarg, uint16_t* grad_val, mi_stream_t stream);
+int mi_spmm_reduce_grad_b_bf16(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm,
+                               const uint16_t* val, int64_t nnz, int32_t M, int32_t K, int32_t N,
+                               const uint16_t* G, int64_t ldg, const int32_t* arg, int64_t ldarg,
+                               uint16_t* grad_b, int64_t ldgb, mi_stream_t stream);
+int mi_spmm_reduce_grad_b_f16(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm,
+                              const uint16_t* val, int64_t nnz, int32_t M, int32_t K, int32_t N,
+                              const uint16_t* G, int64_t ldg, const int32_t* arg, int64_t ldarg,
+                              uint16_t* grad_b, int64_t ldgb, mi_stream_t stream);
+
 int mi_ipc_export(const void* dev_ptr, void* handle_out, int64_t* offset_out, int64_t* alloc_bytes_out);
 int mi_ipc_open(const void* handle, void** base_out);
 int mi_ipc_close(const void* handle);

@@ -15,6 +15,7 @@
 // elements: a lane owns 4 columns (one 8-byte load per gather), and the wide form keeps twice the gathers in flight
 // (U = 16 at N = 256: 16 × 512 B per wave, the fp32 kernel's 8 × 1 KiB).
 // No float atomics; no host read-back (graph-capturable).  Nothing here is shared with the fp32 plans.
+#include "lowp_device.h"
 #include "spmm_device.h"
 #include "spmm_internal.h"
 
@@ -23,55 +24,11 @@ namespace {
 using mi::f32x4;
 using mi::LongArg;
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// The two element types: exact widening of a stored 16-bit pattern, round-to-nearest-even narrowing at the store
-// (gfx950: v_cvt_pk_bf16_f32 / v_cvt_f16_f32; NaN stays NaN, overflow goes to ±inf — DESIGN.md §3.8).
-struct Bf16 {
-  static __device__ __forceinline__ float lo(unsigned w) { return __uint_as_float(w << 16); }
-  static __device__ __forceinline__ float hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-  static __device__ __forceinline__ unsigned short down(float f) { return __builtin_bit_cast(unsigned short, static_cast<__bf16>(f)); }
-};
-struct F16 {
-  static __device__ __forceinline__ float lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
-  static __device__ __forceinline__ float hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
-  static __device__ __forceinline__ unsigned short down(float f) { return __builtin_bit_cast(unsigned short, static_cast<_Float16>(f)); }
-};
-
-template <class T>
-__device__ __forceinline__ float up(unsigned short h) { return T::lo(h); }
-
-template <class T>
-__device__ __forceinline__ unsigned pack2(float a, float b) { return (unsigned)T::down(a) | ((unsigned)T::down(b) << 16); }
-
-// four consecutive elements: one 8-byte load (VEC: 8-byte aligned, all four inside the row) or four 2-byte loads
-// guarded by j < N (zeros beyond: never part of a stored chain)
-template <class T, bool VEC>
-__device__ __forceinline__ f32x4 load4(const unsigned short* p, int j, int N) {
-  if constexpr (VEC) {
-    const u32x2 w = *reinterpret_cast<const u32x2*>(p);
-    return f32x4{T::lo(w.x), T::hi(w.x), T::lo(w.y), T::hi(w.y)};
-  } else {
-    f32x4 r = {0.f, 0.f, 0.f, 0.f};
-    if (j + 0 < N) r.x = up<T>(p[0]);
-    if (j + 1 < N) r.y = up<T>(p[1]);
-    if (j + 2 < N) r.z = up<T>(p[2]);
-    if (j + 3 < N) r.w = up<T>(p[3]);
-    return r;
-  }
-}
-
-template <class T, bool VEC>
-__device__ __forceinline__ void store4(unsigned short* p, int j, int N, f32x4 v) {
-  if constexpr (VEC) {
-    const u32x2 w = {pack2<T>(v.x, v.y), pack2<T>(v.z, v.w)};
-    __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(p));
-  } else {
-    if (j + 0 < N) p[0] = T::down(v.x);
-    if (j + 1 < N) p[1] = T::down(v.y);
-    if (j + 2 < N) p[2] = T::down(v.z);
-    if (j + 3 < N) p[3] = T::down(v.w);
-  }
+// The mean's epilogue (MEAN instantiations only): the fp32 sum divided by the row's entry count, correctly rounded
+// (mi_spmm_rows_divide_f32's division), before the one narrowing of the store.  A row without entries keeps its +0.
+__device__ __forceinline__ float mean_of(float sum, int cnt) { return cnt > 0 ? __fdiv_rn(sum, (float)cnt) : sum; }
+__device__ __forceinline__ f32x4 mean_of(f32x4 sum, int cnt) {
+  return f32x4{mean_of(sum.x, cnt), mean_of(sum.y, cnt), mean_of(sum.z, cnt), mean_of(sum.w, cnt)};
 }
 
 // ---------------------------------------------------------------------------
@@ -80,7 +37,7 @@ __device__ __forceinline__ void store4(unsigned short* p, int j, int N, f32x4 v)
 // FMA consumes one; the last < U entries go as one guarded batch (loads together, FMAs in entry order).
 // grid = ⌈M/4⌉, block = 256.
 // ---------------------------------------------------------------------------
-template <class T, int TT, int U>
+template <class T, int TT, int U, bool MEAN = false>
 __global__ __launch_bounds__(256) void lowp_wave_row_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                             const unsigned short* __restrict__ val,
                                                             const unsigned short* __restrict__ B, unsigned short* __restrict__ C,
@@ -90,6 +47,7 @@ __global__ __launch_bounds__(256) void lowp_wave_row_kernel(const int* __restric
   if (row >= M) return;
   int p = rowptr[row];
   const int end = rowptr[row + 1];
+  const int cnt = end - p;
   if (end - p > la.thresh) {  // left to the follow-up launch
     if (lane == 0) long_list_append(la, (int)row, end - p);
     return;
@@ -134,7 +92,7 @@ __global__ __launch_bounds__(256) void lowp_wave_row_kernel(const int* __restric
   }
   unsigned short* Cl = C + row * ldc + lane * 4;
 #pragma unroll
-  for (int t = 0; t < TT; ++t) store4<T, true>(Cl + t * 256, 0, 0, acc[t]);
+  for (int t = 0; t < TT; ++t) store4<T, true>(Cl + t * 256, 0, 0, MEAN ? mean_of(acc[t], cnt) : acc[t]);
 }
 
 // ---------------------------------------------------------------------------
@@ -145,7 +103,7 @@ __global__ __launch_bounds__(256) void lowp_wave_row_kernel(const int* __restric
 // otherwise 2-byte elements at any alignment and any ldb (offset views, odd leading dimensions).
 // grid = ⌈M / (4·64/G)⌉, block = 256.
 // ---------------------------------------------------------------------------
-template <class T, int G, int TT, bool VEC>
+template <class T, int G, int TT, bool VEC, bool MEAN = false>
 __global__ __launch_bounds__(256) void lowp_group_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                          const unsigned short* __restrict__ val,
                                                          const unsigned short* __restrict__ B, unsigned short* __restrict__ C,
@@ -217,7 +175,7 @@ __global__ __launch_bounds__(256) void lowp_group_kernel(const int* __restrict__
       unsigned short* dst = C + row * ldc;
 #pragma unroll
       for (int t = 0; t < TT; ++t)
-        if (on[t]) store4<T, VEC>(dst + coff[t], coff[t], N, acc[t]);
+        if (on[t]) store4<T, VEC>(dst + coff[t], coff[t], N, MEAN ? mean_of(acc[t], end - start) : acc[t]);
     }
   }
 }
@@ -226,7 +184,7 @@ __global__ __launch_bounds__(256) void lowp_group_kernel(const int* __restrict__
 // N < 4: one wave per row, lane l chains the entries l, l+64, …, the 64 partial sums added by the xor-butterfly
 // 32, 16, …, 1 — spmm_narrow_kernel's order, for every row length.  grid = ⌈M/4⌉.
 // ---------------------------------------------------------------------------
-template <class T>
+template <class T, bool MEAN = false>
 __global__ __launch_bounds__(256) void lowp_narrow_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                           const unsigned short* __restrict__ val,
                                                           const unsigned short* __restrict__ B, unsigned short* __restrict__ C,
@@ -249,7 +207,7 @@ __global__ __launch_bounds__(256) void lowp_narrow_kernel(const int* __restrict_
       float s = acc[j];
 #pragma unroll
       for (int w = 32; w >= 1; w >>= 1) s += __shfl_xor(s, w, 64);
-      if (lane == 0) C[row * ldc + j] = T::down(s);
+      if (lane == 0) C[row * ldc + j] = T::down(MEAN ? mean_of(s, end - start) : s);
     }
   }
 }
@@ -270,7 +228,7 @@ struct LowpLongWs {
   long partial_off;  // bytes
 };
 
-template <class T, bool VEC>
+template <class T, bool VEC, bool MEAN = false>
 __global__ __launch_bounds__(1024) void lowp_long_rows_kernel(int* __restrict__ ws, LowpLongWs lw,
                                                               const int* __restrict__ rowptr, const int* __restrict__ col,
                                                               const unsigned short* __restrict__ val,
@@ -323,7 +281,7 @@ __global__ __launch_bounds__(1024) void lowp_long_rows_kernel(int* __restrict__ 
         float sum = red[0][tid];
 #pragma unroll
         for (int q = 1; q < kLongWaves; ++q) sum += red[q][tid];
-        if (S == 1) C[(long)row * ldc + n0 + tid] = T::down(sum);
+        if (S == 1) C[(long)row * ldc + n0 + tid] = T::down(MEAN ? mean_of(sum, end - start) : sum);
         else partial[(long)(pb + g) * N + n0 + tid] = sum;
       }
       __syncthreads();
@@ -342,7 +300,7 @@ __global__ __launch_bounds__(1024) void lowp_long_rows_kernel(int* __restrict__ 
           const float* pr = partial + (long)pb * N + c;
           float tot = __builtin_nontemporal_load(pr);
           for (int q = 1; q < S; ++q) tot += __builtin_nontemporal_load(pr + (long)q * N);
-          C[(long)row * ldc + c] = T::down(tot);
+          C[(long)row * ldc + c] = T::down(MEAN ? mean_of(tot, end - start) : tot);
         }
       }
       __syncthreads();
@@ -441,25 +399,23 @@ __global__ __launch_bounds__(256) void gather_b16_kernel(const unsigned short* _
   }
 }
 
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
-template <class T, int G, int TT, bool VEC>
+template <class T, int G, int TT, bool VEC, bool MEAN>
 int launch_group(const int* rowptr, const int* col, const unsigned short* val, const unsigned short* B, unsigned short* C,
                  int M, int N, long ldb, long ldc, const LongArg& la, hipStream_t s) {
   constexpr int rows_per_block = 4 * (64 / G);
   const long blocks = ((long)M + rows_per_block - 1) / rows_per_block;
   if (blocks > 0x7fffffffL) return MI_ERANGE;
-  hipLaunchKernelGGL((lowp_group_kernel<T, G, TT, VEC>), dim3((unsigned)blocks), dim3(256), 0, s, rowptr, col, val, B, C, M,
+  hipLaunchKernelGGL((lowp_group_kernel<T, G, TT, VEC, MEAN>), dim3((unsigned)blocks), dim3(256), 0, s, rowptr, col, val, B, C, M,
                      N, ldb, ldc, la);
   return mi::check_launch();
 }
 
-template <class T, bool VEC>
+template <class T, bool VEC, bool MEAN>
 int dispatch_group(const int* rowptr, const int* col, const unsigned short* val, const unsigned short* B, unsigned short* C,
                    int M, int N, long ldb, long ldc, const LongArg& la, hipStream_t s) {
   const int nq = (N + 3) / 4;  // column quads
   const int G = nq >= 64 ? 64 : mi::pow2_ceil(nq);
-#define MI_LOWP_GROUP(G_, TT_) return launch_group<T, G_, TT_, VEC>(rowptr, col, val, B, C, M, N, ldb, ldc, la, s)
+#define MI_LOWP_GROUP(G_, TT_) return launch_group<T, G_, TT_, VEC, MEAN>(rowptr, col, val, B, C, M, N, ldb, ldc, la, s)
   switch (G) {
     case 1: MI_LOWP_GROUP(1, 1);
     case 2: MI_LOWP_GROUP(2, 1);
@@ -476,7 +432,7 @@ int dispatch_group(const int* rowptr, const int* col, const unsigned short* val,
 #undef MI_LOWP_GROUP
 }
 
-template <class T>
+template <class T, bool MEAN = false>
 int spmm_lowp(const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz, int32_t M, int32_t K, int32_t N,
               const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, int long_rows, void* workspace,
               size_t workspace_bytes, hipStream_t s) {
@@ -501,7 +457,7 @@ int spmm_lowp(const int32_t* rowptr, const int32_t* col, const uint16_t* val, in
   if (N < 4) {
     const long blocks = ((long)M + 3) / 4;
     if (blocks > 0x7fffffffL) return MI_ERANGE;
-    hipLaunchKernelGGL(lowp_narrow_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, rowptr, col, val, B, C, M, N, (long)ldb,
+    hipLaunchKernelGGL((lowp_narrow_kernel<T, MEAN>), dim3((unsigned)blocks), dim3(256), 0, s, rowptr, col, val, B, C, M, N, (long)ldb,
                        (long)ldc);
     return mi::check_launch();
   }
@@ -519,7 +475,7 @@ int spmm_lowp(const int32_t* rowptr, const int32_t* col, const uint16_t* val, in
     const long blocks = ((long)M + 3) / 4;
     if (blocks > 0x7fffffffL) return MI_ERANGE;
 #define MI_LOWP_WAVE(TT_, U_)                                                                                          \
-  hipLaunchKernelGGL((lowp_wave_row_kernel<T, TT_, U_>), dim3((unsigned)blocks), dim3(256), 0, s, rowptr, col, val, B, C, M, \
+  hipLaunchKernelGGL((lowp_wave_row_kernel<T, TT_, U_, MEAN>), dim3((unsigned)blocks), dim3(256), 0, s, rowptr, col, val, B, C, M, \
                      (long)ldb, (long)ldc, la)
     if (N == 256) MI_LOWP_WAVE(1, 16);
     else if (N == 512) MI_LOWP_WAVE(2, 8);
@@ -527,9 +483,9 @@ int spmm_lowp(const int32_t* rowptr, const int32_t* col, const uint16_t* val, in
 #undef MI_LOWP_WAVE
     st = mi::check_launch();
   } else if (vec) {
-    st = dispatch_group<T, true>(rowptr, col, val, B, C, M, N, ldb, ldc, la, s);
+    st = dispatch_group<T, true, MEAN>(rowptr, col, val, B, C, M, N, ldb, ldc, la, s);
   } else {
-    st = dispatch_group<T, false>(rowptr, col, val, B, C, M, N, ldb, ldc, la, s);
+    st = dispatch_group<T, false, MEAN>(rowptr, col, val, B, C, M, N, ldb, ldc, la, s);
   }
   if (st != MI_OK || !split) return st;
   // one follow-up launch: sums the listed rows (or finds none) and resets the counters
@@ -537,10 +493,10 @@ int spmm_lowp(const int32_t* rowptr, const int32_t* col, const uint16_t* val, in
   const unsigned grid = (unsigned)(lw.cap_s < 512 ? lw.cap_s : 512);
   const bool lvec = ldb % 4 == 0 && aligned8(B);
   if (lvec)
-    hipLaunchKernelGGL((lowp_long_rows_kernel<T, true>), dim3(grid), dim3(1024), 0, s, ws, lws, rowptr, col, val, B, C, N,
+    hipLaunchKernelGGL((lowp_long_rows_kernel<T, true, MEAN>), dim3(grid), dim3(1024), 0, s, ws, lws, rowptr, col, val, B, C, N,
                        (long)ldb, (long)ldc);
   else
-    hipLaunchKernelGGL((lowp_long_rows_kernel<T, false>), dim3(grid), dim3(1024), 0, s, ws, lws, rowptr, col, val, B, C, N,
+    hipLaunchKernelGGL((lowp_long_rows_kernel<T, false, MEAN>), dim3(grid), dim3(1024), 0, s, ws, lws, rowptr, col, val, B, C, N,
                        (long)ldb, (long)ldc);
   return mi::check_launch();
 }
@@ -567,6 +523,17 @@ int sddmm_lowp(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M
 }
 
 }  // namespace
+
+namespace mi {
+
+int spmm_lowp_mean(bool bf16, const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz, int32_t M, int32_t K,
+                   int32_t N, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, int long_rows, void* workspace,
+                   size_t workspace_bytes, hipStream_t s) {
+  return bf16 ? spmm_lowp<Bf16, true>(rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, long_rows, workspace, workspace_bytes, s)
+              : spmm_lowp<F16, true>(rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, long_rows, workspace, workspace_bytes, s);
+}
+
+}  // namespace mi
 
 extern "C" {
 

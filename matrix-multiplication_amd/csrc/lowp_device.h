@@ -1,0 +1,68 @@
+// Device-side pieces shared by the bfloat16 / float16 translation units of the CSR product (csr_lowp.hip: sum, mean, SDDMM;
+// csr_reduce_lowp.hip: amax / amin and their gradients).  Not installed.  Everything here has internal linkage (an
+// anonymous namespace per including unit).
+#ifndef MI_LOWP_DEVICE_H_
+#define MI_LOWP_DEVICE_H_
+
+#include "mi_common.h"
+
+namespace {
+
+using mi::f32x4;
+
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// The two element types: exact widening of a stored 16-bit pattern, round-to-nearest-even narrowing at the store
+// (gfx950: v_cvt_pk_bf16_f32 / v_cvt_f16_f32; NaN stays NaN, overflow goes to ±inf — DESIGN.md §3.8).
+struct Bf16 {
+  static __device__ __forceinline__ float lo(unsigned w) { return __uint_as_float(w << 16); }
+  static __device__ __forceinline__ float hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+  static __device__ __forceinline__ unsigned short down(float f) { return __builtin_bit_cast(unsigned short, static_cast<__bf16>(f)); }
+};
+struct F16 {
+  static __device__ __forceinline__ float lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+  static __device__ __forceinline__ float hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+  static __device__ __forceinline__ unsigned short down(float f) { return __builtin_bit_cast(unsigned short, static_cast<_Float16>(f)); }
+};
+
+template <class T>
+__device__ __forceinline__ float up(unsigned short h) { return T::lo(h); }
+
+template <class T>
+__device__ __forceinline__ unsigned pack2(float a, float b) { return (unsigned)T::down(a) | ((unsigned)T::down(b) << 16); }
+
+// four consecutive elements: one 8-byte load (VEC: 8-byte aligned, all four inside the row) or four 2-byte loads
+// guarded by j < N (zeros beyond: never part of a stored chain)
+template <class T, bool VEC>
+__device__ __forceinline__ f32x4 load4(const unsigned short* p, int j, int N) {
+  if constexpr (VEC) {
+    const u32x2 w = *reinterpret_cast<const u32x2*>(p);
+    return f32x4{T::lo(w.x), T::hi(w.x), T::lo(w.y), T::hi(w.y)};
+  } else {
+    f32x4 r = {0.f, 0.f, 0.f, 0.f};
+    if (j + 0 < N) r.x = up<T>(p[0]);
+    if (j + 1 < N) r.y = up<T>(p[1]);
+    if (j + 2 < N) r.z = up<T>(p[2]);
+    if (j + 3 < N) r.w = up<T>(p[3]);
+    return r;
+  }
+}
+
+template <class T, bool VEC>
+__device__ __forceinline__ void store4(unsigned short* p, int j, int N, f32x4 v) {
+  if constexpr (VEC) {
+    const u32x2 w = {pack2<T>(v.x, v.y), pack2<T>(v.z, v.w)};
+    __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(p));
+  } else {
+    if (j + 0 < N) p[0] = T::down(v.x);
+    if (j + 1 < N) p[1] = T::down(v.y);
+    if (j + 2 < N) p[2] = T::down(v.z);
+    if (j + 3 < N) p[3] = T::down(v.w);
+  }
+}
+
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+}  // namespace
+
+#endif  // MI_LOWP_DEVICE_H_

@@ -41,6 +41,13 @@ int launch_long_rows_staged(int* ws, const LongWs& lw, const int32_t* rowptr, co
                             const float* B, float* C, int32_t N, int64_t ldb, int64_t ldc, const float* bias, bool reset,
                             hipStream_t s);
 
+// ---- bfloat16 / float16 (csr_lowp.hip) --------------------------------------------------------------------------------
+// mi_spmm_csr_ex_bf16 / _f16 with the mean's epilogue: the same kernels, the fp32 sum of every row divided by its entry count
+// (correctly rounded; an empty row keeps +0) before the one narrowing of the store (mi_spmm_csr_reduce_bf16 / _f16)
+int spmm_lowp_mean(bool bf16, const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz, int32_t M, int32_t K,
+                   int32_t N, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, int long_rows, void* workspace,
+                   size_t workspace_bytes, hipStream_t s);
+
 // ---- column-panel passes (spmm_panels.hip) -------------------------------------------------------------------------
 int launch_locality_probe(const int32_t* rowptr, const int32_t* col, int32_t M, int64_t ldb, double b_bytes, int* verdicts,
                           const int32_t* order, hipStream_t s);  // order (may be null): a schedule's slot → row map

@@ -1017,13 +1017,18 @@ REDUCTIONS = ('sum', 'mean', 'amax', 'amin')
 
 
 def _check_reduce_operands(m1, m2, reduce):
-    '''The inputs sparse_mm_reduce takes: a 2-d CSR mat1 and a 2-d dense fp32 mat2, both on one device (no CPU path).'''
+    '''The inputs sparse_mm_reduce takes: a 2-d CSR mat1 and a 2-d dense mat2 of one dtype (float32, bfloat16 or float16),
+    both on one device (no CPU path).'''
     if reduce not in REDUCTIONS:
         raise ValueError(f'sparse_mm_reduce: reduce must be one of {", ".join(REDUCTIONS)}; got {reduce!r}')
     if not isinstance(m1, torch.Tensor) or m1.layout != torch.sparse_csr or m1.dim() != 2:
         raise ValueError('sparse_mm_reduce: mat1 must be a 2-d (unbatched) CSR tensor')
-    if not isinstance(m2, torch.Tensor) or m2.layout != torch.strided or m2.dim() != 2 or m2.dtype != torch.float32:
-        raise ValueError('sparse_mm_reduce: mat2 must be a 2-d dense float32 tensor')
+    if not isinstance(m2, torch.Tensor) or m2.layout != torch.strided or m2.dim() != 2 or \
+            m2.dtype not in (torch.float32, *_LOWP):
+        raise ValueError('sparse_mm_reduce: mat2 must be a 2-d dense float32, bfloat16 or float16 tensor')
+    if m1.dtype != m2.dtype:
+        raise RuntimeError(f'sparse_mm_reduce: mat1 is {m1.dtype} but mat2 is {m2.dtype}: both operands must share one '
+                           f'dtype (float32, bfloat16 or float16)')
     if not (m1.is_cuda and m2.is_cuda) or m1.device != m2.device:
         raise RuntimeError(f'sparse_mm_reduce: mat1 and mat2 must be device (HIP) tensors on one device, got {m1.device} '
                            f'and {m2.device}; custom_mm has no CPU path')
@@ -1036,7 +1041,10 @@ class naiveSpMMReduce(InplaceFunction):
     device CSR m1 (torch implements `reduce` for CSR on the CPU only).  sum: naiveSpMM's product and backward; mean: that
     product divided by the row's entry count (the gradient divided likewise, then sum's backward); amax / amin: the
     selection kernels, which record the selected entry per output element only when a gradient is needed, and route
-    each gradient element through it.  grad of m1 is a CSR tensor on m1's pattern.'''
+    each gradient element through it.  grad of m1 is a CSR tensor on m1's pattern.
+    bfloat16 / float16 operands (both of one dtype): the output and both gradients are of that dtype, every sum and
+    comparison is fp32 on the widened operands and each element is rounded once; the mean's backward
+    divides the gradient in that dtype, then runs the low-precision sum backward.'''
 
     @staticmethod
     def forward(ctx, m1, m2, reduce):
@@ -1047,7 +1055,7 @@ class naiveSpMMReduce(InplaceFunction):
             return naive_matmul(m1, m2)
         m2 = m2.contiguous()
         values, columns, offsets, nnz, rows, cols = _csr_props_cached(m1)
-        out = torch.empty((rows, m2.shape[1]), device=m2.device, dtype=torch.float32)
+        out = torch.empty((rows, m2.shape[1]), device=m2.device, dtype=m2.dtype)
         arg = None
         if reduce in ('amax', 'amin') and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             arg = torch.empty((rows, m2.shape[1]), device=m2.device, dtype=torch.int32)
@@ -1083,7 +1091,8 @@ class naiveSpMMReduce(InplaceFunction):
 
 def sparse_mm_reduce(mat1: torch.Tensor, mat2: torch.Tensor, reduce: str = 'sum') -> torch.Tensor:
     '''torch.sparse.mm(mat1, mat2, reduce) on the device: mat1 a 2-d CSR tensor (int32 or int64 indices), mat2 a 2-d
-    dense float32 tensor; reduce one of "sum", "mean", "amax", "amin".  Differentiable in both operands.'''
+    dense tensor, both float32, both bfloat16 or both float16; reduce one of "sum", "mean", "amax", "amin".  The output has
+    the operands' dtype.  Differentiable in both operands.'''
     _check_reduce_operands(mat1, mat2, reduce)
     if reduce == 'sum':
         return naiveSpMM.apply(mat1, mat2)

@@ -1,6 +1,6 @@
 """CSR × dense with reduce = sum / mean / amax / amin (torch.sparse.mm's `reduce`) on the shapes the sum path is measured on.
 
-    python tools/bench_spmm_reduce.py [--only TAG] [--log FILE]
+    python tools/bench_spmm_reduce.py [--only TAG] [--log FILE] [--dtype float32|bfloat16|float16]
 
 Shapes: C2 (64 K x 64 K at 0.1 % x 128), C3 (1 M x 1 M at 0.01 % x 256), tools/bench_skew.py's hub-row matrix (100 K rows
 of 100 entries plus rows of 10^5, 3·10^5 and 10^6 entries, K = 1 M, N = 256) and the three GNN-like shapes of
@@ -9,6 +9,9 @@ sum (custom_mm.naive_spmm), mean, amax and amin without arg, amax with arg, and 
 matmuls.sparse_mm_reduce for sum / mean / amax; the ratios the targets are stated in; algorithmic GB/s of amax
 (nnz·(4N+8) + 4(M+1) + 4MN, + 4MN with arg).  Sampled rows (the longest included) of mean and of amax with arg are
 compared with torch-CPU's aten::_sparse_mm_reduce_impl on their sub-CSR: amax bit for bit (arg included), mean to 1e-5.
+--dtype bfloat16 / float16 runs every entry on operands of that type (bytes nnz·(2N+6) + 4(M+1) + 2MN), times the float32
+amax beside them in the same interleaved rounds (the `T/f32` ratio) and checks the sampled rows against torch-CPU on the
+widened operands, narrowed.
 """
 import argparse
 import sys
@@ -64,18 +67,20 @@ def check_rows(rowptr, col, val, B, C_mean, C_max, arg, n=48, seed=0):
     uniq, inv = torch.unique(col[idx], return_inverse=True)
     rp = torch.zeros(len(rows) + 1, dtype=torch.int64)
     rp[1:] = torch.cumsum(ls.cpu(), 0)
-    a = torch.sparse_csr_tensor(rp, inv.long().cpu(), val[idx].cpu(), (len(rows), len(uniq))).requires_grad_()
-    Bs = B[uniq.long()].cpu()
+    a = torch.sparse_csr_tensor(rp, inv.long().cpu(), val[idx].float().cpu(), (len(rows), len(uniq))).requires_grad_()
+    Bs = B[uniq.long()].float().cpu()
     want_max, want_arg = torch.ops.aten._sparse_mm_reduce_impl(a, Bs, "amax")
     want_mean, _ = torch.ops.aten._sparse_mm_reduce_impl(a, Bs, "mean")
-    want_max = want_max.detach()
+    lowp = C_max.dtype != torch.float32
+    want_max = want_max.detach().to(C_max.dtype).float()  # (narrowed once: the low-precision contract)
     nnz = col.numel()
     mapped = torch.where(want_arg == idx.numel(), torch.tensor(nnz),
                          starts.cpu()[:, None] + (want_arg - rp[:-1][:, None]))
-    got_max, got_arg = C_max[rows_d].cpu(), arg[rows_d].cpu().long()
+    got_max, got_arg = C_max[rows_d].float().cpu(), arg[rows_d].cpu().long()
     same_max = torch.equal(torch.isnan(got_max), torch.isnan(want_max)) and \
         torch.equal(got_max.nan_to_num().view(torch.int32), want_max.nan_to_num().view(torch.int32))
-    close_mean = torch.allclose(C_mean[rows_d].cpu(), want_mean.detach(), rtol=1e-5, atol=1e-6)
+    tol = torch.finfo(C_mean.dtype).eps if lowp else 1e-5
+    close_mean = torch.allclose(C_mean[rows_d].float().cpu(), want_mean.detach(), rtol=tol, atol=tol if lowp else 1e-6)
     return same_max and torch.equal(got_arg, mapped), close_mean, len(rows)
 
 
@@ -86,13 +91,17 @@ def fwd_bwd(a, b, reduce, G):
     return step
 
 
-def run(name, out):
+def run(name, out, dtype=torch.float32):
     t0 = time.time()
     M, K, N, rowptr, col, val = shape_csr(name)
     nnz = col.numel()
     g = torch.Generator(device=dev).manual_seed(7)
     B = torch.randn(K, N, device=dev, generator=g)
-    C = {k: torch.empty(M, N, device=dev) for k in ("sum", "mean", "amax", "amin", "amax_arg")}
+    lowp = dtype != torch.float32
+    if lowp:
+        val32, B32, C32 = val, B, torch.empty(M, N, device=dev)
+        val, B = val.to(dtype), B.to(dtype)
+    C = {k: torch.empty(M, N, device=dev, dtype=dtype) for k in ("sum", "mean", "amax", "amin", "amax_arg")}
     arg = torch.empty(M, N, device=dev, dtype=torch.int32)
     ent = {
         "sum": lambda: custom_mm.naive_spmm(val, col, rowptr, nnz, M, K, B, C["sum"]),
@@ -101,14 +110,17 @@ def run(name, out):
         "amin": lambda: custom_mm.naive_spmm_reduce(val, col, rowptr, nnz, M, K, B, C["amin"], "amin"),
         "amax_arg": lambda: custom_mm.naive_spmm_reduce(val, col, rowptr, nnz, M, K, B, C["amax_arg"], "amax", arg),
     }
+    if lowp:
+        ent["amax_f32"] = lambda: custom_mm.naive_spmm_reduce(val32, col, rowptr, nnz, M, K, B32, C32, "amax")
     t = time_interleaved(ent)
     ok_max, ok_mean, nrows = check_rows(rowptr, col, val, B, C["mean"], C["amax_arg"], arg)
-    same_noarg = torch.equal(C["amax"].view(torch.int32), C["amax_arg"].view(torch.int32))
+    same_noarg = torch.equal(C["amax"].view(torch.int16 if lowp else torch.int32),
+                             C["amax_arg"].view(torch.int16 if lowp else torch.int32))
     a = torch.sparse_csr_tensor(rowptr, col, val, (M, K)).requires_grad_()
     b = B.clone().requires_grad_()
-    Gd = torch.randn(M, N, device=dev, generator=g)
+    Gd = torch.randn(M, N, device=dev, generator=g).to(dtype)
     tb = time_interleaved({r: fwd_bwd(a, b, r, Gd) for r in ("sum", "mean", "amax")}, rounds=2)
-    byts = nnz * (4 * N + 8) + 4 * (M + 1) + 4 * M * N
+    byts = nnz * (2 * N + 6) + 4 * (M + 1) + 2 * M * N if lowp else nnz * (4 * N + 8) + 4 * (M + 1) + 4 * M * N
     longest = int((rowptr[1:] - rowptr[:-1]).max())
     line = (f"{name:9s} M={M} K={K} N={N} nnz={nnz} longest={longest} | ms: sum {t['sum']:.3f} mean {t['mean']:.3f} "
             f"amax {t['amax']:.3f} amin {t['amin']:.3f} amax+arg {t['amax_arg']:.3f} | amax/sum {t['amax'] / t['sum']:.2f} "
@@ -117,6 +129,8 @@ def run(name, out):
             f"amax {tb['amax']:.2f} | {nrows} rows vs torch-CPU: amax+arg bits {'ok' if ok_max else 'FAIL'}, "
             f"mean {'ok' if ok_mean else 'FAIL'}; amax without arg = with arg {'ok' if same_noarg else 'FAIL'} "
             f"[{time.time() - t0:.0f} s]")
+    if lowp:
+        line += f" | float32 amax {t['amax_f32']:.3f} ms, T/f32 {t['amax'] / t['amax_f32']:.2f}"
     print(line, flush=True)
     out.append(line)
     del a, b, Gd, C, arg, B, rowptr, col, val
@@ -128,15 +142,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     ap.add_argument("--log", default="")
+    ap.add_argument("--dtype", default="float32", choices=("float32", "bfloat16", "float16"))
     a = ap.parse_args()
     head = (f"# device {torch.cuda.get_device_name(0)}; interleaved medians, ms per call; algorithmic bytes "
             f"nnz·(4N+8)+4(M+1)+4MN (+4MN arg)")
+    if a.dtype != "float32":
+        head = (f"# device {torch.cuda.get_device_name(0)}; {a.dtype}; interleaved medians, ms per call; algorithmic bytes "
+                f"nnz·(2N+6)+4(M+1)+2MN (+4MN arg)")
     print(head, flush=True)
     out, ok = [head], True
     for name in ("C2", "C3", "hub", "arxiv", "reddit", "products"):
         if a.only and a.only != name:
             continue
-        ok = run(name, out) and ok
+        ok = run(name, out, getattr(torch, a.dtype)) and ok
     if a.log:
         Path(a.log).parent.mkdir(parents=True, exist_ok=True)
         Path(a.log).write_text("\n".join(out) + "\n")
