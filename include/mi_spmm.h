@@ -810,6 +810,55 @@ int mi_spmm_reduce_grad_b_f16(const int32_t* t_rowptr, const int32_t* t_col, con
                               const uint16_t* G, int64_t ldg, const int32_t* arg, int64_t ldarg,
                               uint16_t* grad_b, int64_t ldgb, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * CSR row softmax — NEW relative to the reference: torch.sparse.softmax(A, dim = -1) for a CSR tensor (torch implements it
+ * for COO only; DGL / PyG call it "edge softmax"), and its backward.  The softmax runs over the STORED entries of each
+ * row: explicit zeros are entries like any other, duplicate columns are separate entries, an empty row writes nothing.
+ * The columns are never read, so the entries take the offsets and the values only.
+ *   rowptr  int32 [batch, M + 1], item i's offsets with its base added (the "rowptr of rowptrs" layout of
+ *           mi_spmm_csr_batched_f32): row r of item i is rowptr[i·(M+1) + r] … rowptr[i·(M+1) + r + 1].  batch = 1: a 2-d CSR.
+ *   nnz     the number of stored entries (an upper bound is enough: it only picks the lane-group width)
+ *   forward   y_p  = e_p / Σ_q e_q,  e_p = exp(t_p − max_q t_q),  t_p = fl32(scale · x_p)
+ *   backward  dx_p = scale · y_p · (dy_p − Σ_q dy_q · y_q)   from the forward's OUTPUT y
+ * Arithmetic and order (the bits of a row depend on that row's entries and `scale` alone — not on the lane-group width
+ * the launch took, on neighbouring rows, or on batch / M): t_p is one fp32 multiply, never fused; the maximum is exact and
+ * skips NaN; e_p = E + E·lo with E = expf(hi) (the accurate exponential) and hi + lo = t_p − m exactly (two-sum: the
+ * subtraction's rounding, half an ulp of a difference of up to 64, would otherwise dominate the error); entry p goes into chain p mod 64, a chain starts at +0 and
+ * adds in increasing p; the 64 chains are combined by the xor tree c_i ← c_i + c_(i xor d), d = 32, 16, 8, 4, 2, 1;
+ * y_p = fl(e_p · fl(1 / s)).  Backward: the chains take fmaf(dy_p, y_p, chain), the same tree gives d, and
+ * dx_p = fl(scale · fl(y_p · fl(dy_p − d))).  No float atomics; the same bits on every run.
+ * Special values follow that arithmetic, as torch.softmax of the row's entries: an explicit −inf entry gives 0; a row
+ * holding a NaN or a +inf gives NaN in every entry; a row of only −inf gives NaN.
+ * bfloat16 / float16 (T; uint16_t bit patterns, 2-byte aligned — an odd pointer → MI_EINVAL): the rule of the
+ * low-precision section: entries widened exactly, every operation in fp32, one rounding at the store —
+ *   mi_csr_softmax_T(x) == rne_T(mi_csr_softmax_f32(up(x)))  and
+ *   mi_csr_softmax_backward_T(y, dy) == rne_T(mi_csr_softmax_backward_f32(up(y), up(dy)))   bit for bit.
+ * In place is allowed: y may be x, dx may be dy (or y).
+ * Rows of any length (10⁶ entries and more) are served by the one launch: up to 8 entries per lane of a row's lane group
+ * in registers (read once, written once), up to 4096 (backward: 2048) entries through one workgroup's LDS (read once,
+ * written once), longer ones streamed by that workgroup (three reads, one write).
+ * mi_csr_softmax_workspace_bytes is 0: no entry uses a workspace; `workspace` / `workspace_bytes` are accepted for the
+ * uniform argument list and ignored.  No host synchronisation, no read-back: graph-capturable.
+ * Validation before any HIP call: negative nnz / batch / M → MI_EINVAL; nnz ≥ 2³¹ or batch·(M+1) ≥ 2³¹ → MI_ERANGE;
+ * nnz == 0, batch == 0 or M == 0 → MI_OK, nothing touched; a NULL rowptr / x / y / dy / dx with work to do → MI_EINVAL.
+ * ------------------------------------------------------------------------ */
+size_t mi_csr_softmax_workspace_bytes(int64_t nnz, int32_t batch, int32_t M);
+int mi_csr_softmax_f32(const int32_t* rowptr, int64_t nnz, int32_t batch, int32_t M, const float* x, float scale,
+                       float* y, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_csr_softmax_bf16(const int32_t* rowptr, int64_t nnz, int32_t batch, int32_t M, const uint16_t* x, float scale,
+                        uint16_t* y, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_csr_softmax_f16(const int32_t* rowptr, int64_t nnz, int32_t batch, int32_t M, const uint16_t* x, float scale,
+                       uint16_t* y, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_csr_softmax_backward_f32(const int32_t* rowptr, int64_t nnz, int32_t batch, int32_t M, const float* y,
+                                const float* dy, float scale, float* dx, void* workspace, size_t workspace_bytes,
+                                mi_stream_t stream);
+int mi_csr_softmax_backward_bf16(const int32_t* rowptr, int64_t nnz, int32_t batch, int32_t M, const uint16_t* y,
+                                 const uint16_t* dy, float scale, uint16_t* dx, void* workspace, size_t workspace_bytes,
+                                 mi_stream_t stream);
+int mi_csr_softmax_backward_f16(const int32_t* rowptr, int64_t nnz, int32_t batch, int32_t M, const uint16_t* y,
+                                const uint16_t* dy, float scale, uint16_t* dx, void* workspace, size_t workspace_bytes,
+                                mi_stream_t stream);
+
 int mi_ipc_export(const void* dev_ptr, void* handle_out, int64_t* offset_out, int64_t* alloc_bytes_out);
 int mi_ipc_open(const void* handle, void** base_out);
 int mi_ipc_close(const void* handle);

@@ -46,6 +46,7 @@ namespace {
 #include "custom_mm_extras.inc"
 #include "custom_mm_inspect.inc"
 #include "custom_mm_reduce.inc"
+#include "custom_mm_softmax.inc"
 
 // ---- handle init / destroy (reference custom_mm.cpp:361-391) ----------------
 // There are no vendor handles on this path; init checks that the C-ABI library
@@ -168,6 +169,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("spmm_rows_divide", &spmm_rows_divide, "out = in / (entries of the row), per row (mean and its gradient)");
   m.def("spmm_reduce_grad_val", &spmm_reduce_grad_val, "amax / amin: gradient of A's stored values from the forward's arg");
   m.def("spmm_reduce_grad_b", &spmm_reduce_grad_b, "amax / amin: gradient of B on A^T's pattern and permutation");
+  m.def("csr_softmax", &csr_softmax,
+        "(values, offsets [batch, rows+1], nnz, batch, rows, scale, out): softmax over the stored entries of every CSR row");
+  m.def("csr_softmax_backward", &csr_softmax_backward,
+        "(y, dy, offsets, nnz, batch, rows, scale, out): out = scale * y * (dy - sum over the row of dy * y)");
   // Handles and automatic schedules own HIP streams and events: they are released while the interpreter — and with it the HIP
   // runtime — is still up (left to the destructors of the statics they segfaulted at process exit after the runtime had gone:
   // a program that never called cusparse_clean / auto_schedule_clear ended with exit code 139 AFTER its last line of output).

@@ -1097,3 +1097,257 @@ def sparse_mm_reduce(mat1: torch.Tensor, mat2: torch.Tensor, reduce: str = 'sum'
     if reduce == 'sum':
         return naiveSpMM.apply(mat1, mat2)
     return naiveSpMMReduce.apply(mat1, mat2, reduce)
+
+
+# --------------------------------------------------------------------------- #
+# sparse attention: sampled product → softmax over the stored entries of each row → CSR × dense
+# --------------------------------------------------------------------------- #
+
+_VALUE_DTYPES = (torch.float32, *_LOWP)
+
+
+def _check_on_device(what, **tensors):
+    '''No CPU path: with the HIP extension loaded every operand is a device tensor, all on one device.'''
+    if not _REAL_EXTENSION:
+        return  # (the plain-Python stand-in of the host-logic tests computes on host tensors)
+    devs = {name: t.device for name, t in tensors.items()}
+    if not all(d.type == 'cuda' for d in devs.values()) or len(set(devs.values())) != 1:
+        raise RuntimeError(f'{what}: ' + ', '.join(tensors) + ' must be device (HIP) tensors on one device, got ' +
+                           ', '.join(str(d) for d in devs.values()) + '; custom_mm has no CPU path')
+
+
+def _check_value_dtype(what, name, t):
+    if _REAL_EXTENSION and t.dtype not in _VALUE_DTYPES:
+        raise ValueError(f'{what}: {name} must be float32, bfloat16 or float16, got {t.dtype}')
+
+
+def _check_csr(what, name, a):
+    if not isinstance(a, torch.Tensor) or a.layout != torch.sparse_csr:
+        raise ValueError(f'{what}: {name} must be a CSR tensor (2-d, or batched with equal entry counts per item)')
+
+
+_PATTERN_FIELDS = ('transposed', 'sched', 'sched_t', 'batched', 'batched_dev', 'batched_t')
+
+
+class _SharedPatternState(_CsrState):
+    '''The _CsrState of a CSR tensor built on ANOTHER tensor's index tensors: what is kept about the pattern lives in
+    the owner's record (read and written through), so whichever of the tensors first needs the narrowed indices or the
+    transposed pattern builds them for all; key, props and the backward count are this tensor's own.'''
+
+    def __init__(self, owner: _CsrState):
+        self._owner = getattr(owner, '_owner', owner)
+
+
+for _name in _PATTERN_FIELDS:
+    setattr(_SharedPatternState, _name, property(lambda self, _n=_name: getattr(self._owner, _n),
+                                                 lambda self, value, _n=_name: setattr(self._owner, _n, value)))
+
+
+def _share_pattern(src: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    '''`out` is a CSR tensor on `src`'s own index tensors: give it a record that shares what `src` keeps about the
+    PATTERN (the narrowed index arrays, the transposed pattern with its permutation, the row schedules), so that a chain
+    of operations on one static pattern (sampled_matmul → sparse_softmax → naive_matmul, and their gradients) narrows
+    and transposes it once, not once per result tensor.  Values are never part of that.'''
+    sst = _csr_state(src)
+    key = _csr_key(out)
+    if key[1:3] + key[6:] != sst.key[1:3] + sst.key[6:]:  # not the same index storage, shape and entry count
+        return out
+    st = _SharedPatternState(sst)
+    st.key = key
+    if sst.props is not None and out.dim() == 2:
+        vals = torch.Tensor.values(out)
+        if vals.device == sst.props[1].device:
+            st.props = (vals.contiguous(),) + tuple(sst.props[1:])
+    try:
+        out._mi_state = st
+    except (AttributeError, RuntimeError):
+        pass
+    return out
+
+
+def _on_pattern(a: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
+    '''A CSR tensor with `values` on a's own index tensors (as the gradients on a pattern are built).'''
+    vals = torch.Tensor.values(a)
+    out = torch.sparse_csr_tensor(torch.Tensor.crow_indices(a), torch.Tensor.col_indices(a),
+                                  values.to(vals.device).reshape(vals.shape), size=a.shape)
+    return _share_pattern(a, out)
+
+
+def _softmax_offsets(a: torch.Tensor):
+    '''(offsets int32 [batch, M + 1] with the items' bases, nnz, batch, M) of a 2-d or batched CSR tensor, from what it
+    keeps (_csr_props_cached / _batched_pattern): a static pattern is narrowed once.'''
+    rows = a.shape[-2]
+    if a.dim() == 2:
+        offsets, nnz = _csr_props_cached(a)[2:4]
+        return offsets, nnz, 1, rows
+    vals = torch.Tensor.values(a)
+    offsets = _batched_pattern(a, vals.device)[0]
+    return offsets, vals.numel(), offsets.shape[0], rows
+
+
+def _grad_values(grad, like: torch.Tensor, what: str) -> torch.Tensor:
+    '''The values [nnz] of a gradient that arrives for a CSR output on `like`'s pattern.'''
+    if grad.layout != torch.sparse_csr:
+        raise RuntimeError(f'{what}: the gradient of a CSR result must be a CSR tensor on its pattern, got layout {grad.layout}')
+    gv = torch.Tensor.values(grad)
+    if gv.numel() != torch.Tensor.values(like).numel():
+        raise RuntimeError(f'{what}: the gradient holds {gv.numel()} entries, the pattern {torch.Tensor.values(like).numel()}')
+    return gv.reshape(-1).contiguous()
+
+
+def _check_softmax_operand(a):
+    _check_csr('sparse_softmax', 'a', a)
+    _check_value_dtype('sparse_softmax', 'a', a)
+    _check_on_device('sparse_softmax', a=torch.Tensor.values(a))
+
+
+class sparseSoftmax(InplaceFunction):
+    '''softmax(scale · a) over the STORED entries of every row of a 2-d or batched CSR tensor (torch.sparse.softmax(a, -1),
+    which torch implements for COO only): one streaming kernel forward, one backward.  The result and
+    the gradient are CSR tensors on a's own index tensors.'''
+
+    @staticmethod
+    def forward(ctx, a, scale=1.0):
+        _check_softmax_operand(a)
+        offsets, nnz, batch, rows = _softmax_offsets(a)
+        x = torch.Tensor.values(a).reshape(-1).contiguous()
+        y = custom_mm.csr_softmax(x, offsets, nnz, batch, rows, float(scale), torch.empty_like(x))
+        ctx.scale = float(scale)
+        ctx.save_for_backward(a, y)
+        return _on_pattern(a, y)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        a, y = ctx.saved_tensors
+        offsets, nnz, batch, rows = _softmax_offsets(a)
+        dy = _grad_values(grad_output, a, 'sparse_softmax backward').to(y.dtype)
+        dx = custom_mm.csr_softmax_backward(y, dy, offsets, nnz, batch, rows, ctx.scale, torch.empty_like(y))
+        return _on_pattern(a, dx), None
+
+
+def sparse_softmax(a: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    '''torch.sparse.softmax(scale · a, dim=-1) for a device CSR tensor `a`, 2-d or batched (≥ 3-d), float32, bfloat16 or
+    float16: the softmax over each row's stored entries (explicit zeros are entries; empty rows stay empty).  Returns a
+    CSR tensor on a's index tensors.  Differentiable in a.'''
+    _check_softmax_operand(a)
+    return sparseSoftmax.apply(a, scale)
+
+
+def _check_sampled_operands(pattern, m1, m2t, what='sampled_matmul', device=True):
+    _check_csr(what, 'pattern', pattern)
+    for name, m in (('m1', m1), ('m2t', m2t)):
+        if not isinstance(m, torch.Tensor) or m.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be a dense tensor')
+        _check_value_dtype(what, name, m)
+    if m1.dtype != m2t.dtype:
+        raise RuntimeError(f'{what}: m1 is {m1.dtype} but m2t is {m2t.dtype}: both operands must have one dtype '
+                           f'(float32, bfloat16 or float16)')
+    if m1.dim() != pattern.dim() or m2t.dim() != pattern.dim():
+        raise ValueError(f'{what}: a {pattern.dim()}-d pattern needs {pattern.dim()}-d m1 and m2t, got {m1.dim()}-d and '
+                         f'{m2t.dim()}-d')
+    lead = tuple(pattern.shape[:-2])
+    if tuple(m1.shape[:-1]) != lead + (pattern.shape[-2],) or tuple(m2t.shape[:-1]) != lead + (pattern.shape[-1],) or \
+            m1.shape[-1] != m2t.shape[-1]:
+        raise ValueError(f'{what}: a pattern of shape {tuple(pattern.shape)} needs m1 {lead + (pattern.shape[-2], "N")} and m2t '
+                         f'{lead + (pattern.shape[-1], "N")}, got {tuple(m1.shape)} and {tuple(m2t.shape)}')
+    if m1.dtype in _LOWP and pattern.dim() != 2:
+        raise RuntimeError(f'{what}: a batched {m1.dtype} CSR pattern ({pattern.dim()}-d) is not supported (float32 only)')
+    if device:
+        _check_on_device(what, pattern=torch.Tensor.values(pattern), m1=m1, m2t=m2t)
+
+
+def _batched_sddmm(pattern, st, dev, g, b):
+    '''values[p] = ⟨g[i, row(p), :], b[i, col(p), :]⟩ on a batched pattern (g [nb, M, N], b [nb, K, N]): the LDS-resident
+    batched form where it takes the problem, else ONE SDDMM on the block-diagonal matrix of the batch — the choice and
+    the bits of _batched_csr_backward.'''
+    offsets, columns = _batched_pattern(pattern, dev, st)
+    nb, rows, n = g.shape
+    cols, total = b.shape[1], columns.numel()
+    out = torch.empty(total, device=dev, dtype=g.dtype)
+    if hasattr(custom_mm, 'sddmm_batched') and custom_mm.sddmm_batched(columns, offsets, total, nb, rows, cols, g, b, out):
+        return out
+    flat_off, diag_columns = _batched_transposed(pattern, dev, st)[:2]
+    return custom_mm.sddmm(diag_columns, flat_off, total, nb * rows, nb * cols, g.reshape(nb * rows, n), b.reshape(nb * cols, n))
+
+
+class sampledMM(InplaceFunction):
+    '''values[p] = ⟨m1[row(p), :], m2t[col(p), :]⟩ on a CSR pattern (torch.sparse.sampled_addmm with β = 0, mat2 given
+    transposed): the SDDMM kernels forward; backward two CSR × dense products with the incoming values on the pattern —
+    grad m1 = G·m2t, grad m2t = Gᵀ·m1 on the kept transposed pattern.'''
+
+    @staticmethod
+    def forward(ctx, pattern, m1, m2t):
+        _check_sampled_operands(pattern, m1, m2t)
+        ctx.save_for_backward(pattern, m1, m2t)
+        st = _csr_state(pattern)
+        if pattern.dim() == 2:
+            _, columns, offsets, nnz, rows, cols = _csr_props_cached(pattern, st)
+            vals = custom_mm.sddmm(columns, offsets, nnz, rows, cols, m1.contiguous(), m2t.contiguous())
+        else:
+            rows, cols, n = pattern.shape[-2], pattern.shape[-1], m1.shape[-1]
+            vals = _batched_sddmm(pattern, st, m1.device, m1.reshape(-1, rows, n).contiguous(),
+                                  m2t.reshape(-1, cols, n).contiguous())
+        return _on_pattern(pattern, vals)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        pattern, m1, m2t = ctx.saved_tensors
+        st = _csr_state(pattern)
+        gv = _grad_values(grad_output, pattern, 'sampled_matmul backward').to(m1.dtype)
+        rows, cols, n = pattern.shape[-2], pattern.shape[-1], m1.shape[-1]
+        grad_m1 = grad_m2t = None
+        if pattern.dim() == 2:
+            _, columns, offsets, nnz, _, _ = _csr_props_cached(pattern, st)
+            if ctx.needs_input_grad[1]:
+                grad_m1 = custom_mm.naive_spmm(gv, columns, offsets, nnz, rows, cols, m2t.contiguous(), torch.empty_like(m1))
+            if ctx.needs_input_grad[2]:
+                t_perm, t_col, t_off = _transposed_pattern(pattern, st)
+                grad_m2t = custom_mm.naive_spmm(_gather_perm(gv, t_perm), t_col, t_off, nnz, cols, rows, m1.contiguous(),
+                                                torch.empty_like(m2t))
+            return None, grad_m1, grad_m2t
+        dev = m1.device
+        offsets, columns = _batched_pattern(pattern, dev, st)
+        nb, total = offsets.shape[0], columns.numel()
+        a3, b3 = m1.reshape(nb, rows, n).contiguous(), m2t.reshape(nb, cols, n).contiguous()
+        chunks = _item_chunks(nb)
+        if ctx.needs_input_grad[1]:
+            ga = torch.empty_like(a3)
+            for lo, hi in chunks:
+                custom_mm.naive_spmm_batched(gv, columns, offsets[lo:hi].contiguous(), total, hi - lo, rows, cols, b3[lo:hi], ga[lo:hi])
+            grad_m1 = ga.reshape(m1.shape)
+        if ctx.needs_input_grad[2]:
+            _, _, t_perm, t_col, t_off = _batched_transposed(pattern, dev, st)
+            t_val = _gather_perm(gv, t_perm)
+            gb = torch.empty_like(b3)
+            for lo, hi in chunks:
+                custom_mm.naive_spmm_batched(t_val, t_col, t_off[lo:hi].contiguous(), total, hi - lo, cols, rows, a3[lo:hi], gb[lo:hi])
+            grad_m2t = gb.reshape(m2t.shape)
+        return None, grad_m1, grad_m2t
+
+
+def sampled_matmul(pattern: torch.Tensor, m1: torch.Tensor, m2t: torch.Tensor) -> torch.Tensor:
+    '''The product m1 · m2tᵀ evaluated ONLY at the stored positions of `pattern` (its values are ignored):
+    torch.sparse.sampled_addmm(pattern, m1, m2tᵀ, beta=0), with the second operand as [K, N] — the form attention has it
+    in (scores = q · kᵀ).  pattern: a device CSR tensor [M, K] or batched [..., M, K]; m1 [..., M, N], m2t [..., K, N],
+    float32 (2-d and batched) or both bfloat16 / both float16 (2-d).  Returns a CSR tensor of m1's dtype on the pattern's
+    index tensors.  Differentiable in m1 and m2t.'''
+    _check_sampled_operands(pattern, m1, m2t)
+    return sampledMM.apply(pattern, m1, m2t)
+
+
+def sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pattern: torch.Tensor, scale=None) -> torch.Tensor:
+    '''softmax(scale · q·kᵀ restricted to `pattern`) · v without any dense S × S tensor:
+    naive_matmul(sparse_softmax(sampled_matmul(pattern, q, k), scale), v).  q, k, v: [S, D] with a 2-d CSR pattern
+    [S, S], or [..., S, D] with a batched pattern of the same leading dimensions; scale defaults to 1/√D.  Rows of the
+    pattern without entries give zero rows.  Differentiable in q, k and v.'''
+    _check_sampled_operands(pattern, q, k, 'sparse_attention', device=False)
+    if not isinstance(v, torch.Tensor) or v.layout != torch.strided or v.dim() != q.dim() or \
+            tuple(v.shape[:-1]) != tuple(k.shape[:-1]):
+        raise ValueError(f'sparse_attention: v must be a dense tensor with k\'s leading shape {tuple(k.shape[:-1])}')
+    if v.dtype != q.dtype:
+        raise RuntimeError(f'sparse_attention: q is {q.dtype} but v is {v.dtype}: all operands must have one dtype')
+    _check_on_device('sparse_attention', pattern=torch.Tensor.values(pattern), q=q, k=k, v=v)
+    if scale is None:
+        scale = 1.0 / float(q.shape[-1]) ** 0.5
+    scores = sampledMM.apply(pattern, q, k)
+    return naiveSpMM.apply(sparseSoftmax.apply(scores, scale), v)
