@@ -859,6 +859,76 @@ int mi_csr_softmax_backward_f16(const int32_t* rowptr, int64_t nnz, int32_t batc
                                 const uint16_t* dy, float scale, uint16_t* dx, void* workspace, size_t workspace_bytes,
                                 mi_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Fused sparse attention — NEW relative to the reference: out = softmax(scale · q·kᵀ restricted to a CSR pattern) · v in
+ * ONE launch, and the row side of its backward in ONE launch; no score or probability array is written forward.  The
+ * result has the bits of the three entries it replaces, run one after the other (mi_sddmm_csr_T → mi_csr_softmax_T →
+ * mi_spmm_csr_T), and the backward those of their backward entries:
+ *   rowptr  int32 [batch, M + 1] with the items' bases (the layout of mi_csr_softmax_T; batch = 1: a 2-d pattern);
+ *   col     int32 [nnz], item-local columns in [0, K), any order, duplicates allowed (entries like any other);
+ *   q [batch][M][D], k and v [batch][K][D], out [batch][M][D]: leading dimension ld ≥ D and item stride in elements; rows
+ *           16-byte aligned (T: 8-byte) — base, ld and stride; D a multiple of 4 (T: of 8) in 8 … 128, else MI_EINVAL;
+ *   stats   float [batch·M][2] = (m, 1 / s) of every row (forward: written, may be NULL; backward: read, required).
+ * Order, per row r with entries p in CSR order:
+ *   s_p   = the SDDMM order of mi_sddmm_csr_f32: lane l of 64 chains columns 4l + c (c = 0 … 3) with fmaf from +0, lanes
+ *           beyond D / 4 hold +0, xor tree 32 … 1 (the steps that meet only empty lanes add +0 and are kept);
+ *   t_p   = fl(scale · s_p), never fused; m = max t_p; e_p = the two-sum exponential of mi_csr_softmax_f32; chain p mod 64
+ *           from +0 in increasing p, xor tree 32 … 1 → s; y_p = fl(e_p · fl(1 / s));
+ *   out[r, j] = ONE fmaf chain from +0 over the row's entries in CSR order, for every row length — the plain order of
+ *           mi_spmm_csr_f32 / mi_spmm_csr_batched_f32.  mi_spmm_csr_f32 itself splits rows beyond
+ *           mi_spmm_long_row_threshold() (8192) entries under its AUTO rule: such rows differ from the 2-d composition;
+ *   backward  t_p, y_p as above (recomputed from q, k and the row's stats: the same bits); dP_p = the SDDMM order on
+ *           (dO[r, :], v[col_p, :]); d = the chains fmaf(dP_p, y_p, ·) p mod 64 and their tree;
+ *           dS_p = fl(scale · fl(y_p · fl(dP_p − d))); dq[r, :] = the CSR-order fmaf chain of dS_p · k[col_p, :].
+ *           y [nnz] and dS [nnz] are written in CSR order for the column-side products dv = Pᵀ·dO and dk = dSᵀ·q, which
+ *           run on the transposed pattern through mi_spmm_csr_T / mi_spmm_csr_batched_f32.
+ * bfloat16 / float16 (T): every stage in fp32 on exactly widened inputs, narrowed (rne) once per stage — s, y, dP and dS
+ * in registers between the stages, out, dq, y and dS at the store: the 2-d composition in T, bit for bit, for any batch.
+ * Special values follow the arithmetic: a −inf score gives probability 0; a NaN or +inf score gives a NaN row; a row whose
+ * scores are all −inf gives NaN.  A row without entries gives a zero row of out and dq.
+ * Row lengths: up to 2048 entries (backward: 1024) stay in the wave's LDS slice; longer rows are streamed by the same
+ * wave with recomputation (forward three score passes, backward two).  Any length, one launch, no read-back.
+ * mi_sparse_attention_workspace_bytes is 0; `workspace` / `workspace_bytes` are accepted and ignored.  No atomics, no host
+ * synchronisation: graph-capturable; the same bits on every run, whatever the neighbouring rows or the batch.
+ * Validation before any HIP call: a negative size → MI_EINVAL; nnz ≥ 2³¹ or batch·(M+1) ≥ 2³¹ → MI_ERANGE; an unsupported
+ * D → MI_EINVAL; batch == 0 or M == 0 → MI_OK, nothing touched (nnz == 0 with rows: zero rows are written); a NULL or
+ * misaligned pointer, ld < D, or K == 0 with entries → MI_EINVAL.
+ * ------------------------------------------------------------------------ */
+size_t mi_sparse_attention_workspace_bytes(int64_t nnz, int32_t batch, int32_t M, int32_t D);
+int mi_sparse_attention_f32(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t batch, int32_t M, int32_t K,
+                            int32_t D, const float* q, int64_t ldq, int64_t strideQ, const float* k, int64_t ldk,
+                            int64_t strideK, const float* v, int64_t ldv, int64_t strideV, float scale, float* out,
+                            int64_t ldo, int64_t strideO, float* stats, void* workspace, size_t workspace_bytes,
+                            mi_stream_t stream);
+int mi_sparse_attention_backward_f32(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t batch, int32_t M,
+                                     int32_t K, int32_t D, const float* q, int64_t ldq, int64_t strideQ, const float* k,
+                                     int64_t ldk, int64_t strideK, const float* v, int64_t ldv, int64_t strideV,
+                                     const float* dout, int64_t lddo, int64_t strideDO, const float* stats, float scale,
+                                     float* dq, int64_t lddq, int64_t strideDQ, float* y, float* ds, void* workspace,
+                                     size_t workspace_bytes, mi_stream_t stream);
+int mi_sparse_attention_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t batch, int32_t M, int32_t K,
+                            int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k, int64_t ldk,
+                            int64_t strideK, const uint16_t* v, int64_t ldv, int64_t strideV, float scale, uint16_t* out,
+                            int64_t ldo, int64_t strideO, float* stats, void* workspace, size_t workspace_bytes,
+                            mi_stream_t stream);
+int mi_sparse_attention_backward_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t batch, int32_t M,
+                                     int32_t K, int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k,
+                                     int64_t ldk, int64_t strideK, const uint16_t* v, int64_t ldv, int64_t strideV,
+                                     const uint16_t* dout, int64_t lddo, int64_t strideDO, const float* stats, float scale,
+                                     uint16_t* dq, int64_t lddq, int64_t strideDQ, uint16_t* y, uint16_t* ds, void* workspace,
+                                     size_t workspace_bytes, mi_stream_t stream);
+int mi_sparse_attention_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t batch, int32_t M, int32_t K,
+                            int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k, int64_t ldk,
+                            int64_t strideK, const uint16_t* v, int64_t ldv, int64_t strideV, float scale, uint16_t* out,
+                            int64_t ldo, int64_t strideO, float* stats, void* workspace, size_t workspace_bytes,
+                            mi_stream_t stream);
+int mi_sparse_attention_backward_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t batch, int32_t M,
+                                     int32_t K, int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k,
+                                     int64_t ldk, int64_t strideK, const uint16_t* v, int64_t ldv, int64_t strideV,
+                                     const uint16_t* dout, int64_t lddo, int64_t strideDO, const float* stats, float scale,
+                                     uint16_t* dq, int64_t lddq, int64_t strideDQ, uint16_t* y, uint16_t* ds, void* workspace,
+                                     size_t workspace_bytes, mi_stream_t stream);
+
 int mi_ipc_export(const void* dev_ptr, void* handle_out, int64_t* offset_out, int64_t* alloc_bytes_out);
 int mi_ipc_open(const void* handle, void** base_out);
 int mi_ipc_close(const void* handle);

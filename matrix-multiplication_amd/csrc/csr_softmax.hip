@@ -31,64 +31,13 @@
 
 #pragma clang fp contract(off)
 
+#include "csr_softmax_device.h"
+
 namespace {
 
 constexpr int kBlock = 256;        // threads of a workgroup
 constexpr int kRegs = 8;           // entries per lane of the register form
 constexpr int kLdsEntries = 4096;  // floats of the workgroup forms' buffer (16 KiB: does not limit the register form's occupancy)
-
-// down(f, z): the stored form of the fp32 result f.  z is a zero the compiler cannot see (the kernels derive it from an
-// argument): for fp16 hipcc otherwise fuses the multiply that produces f with the narrowing into ONE mixed-precision fma
-// (v_fma_mixlo_f16) — a single rounding of the exact product, and a +0 addend that turns −0 into +0 — which is not
-// rne_T(fl32(product)), the contract.  Passing f's bits through `xor z` keeps the two roundings apart.
-struct Fp32 {
-  typedef float S;
-  static __device__ __forceinline__ float up(float v) { return v; }
-  static __device__ __forceinline__ float down(float v, unsigned) { return v; }
-};
-template <class T>
-struct Lowp {
-  typedef unsigned short S;
-  static __device__ __forceinline__ float up(unsigned short h) { return T::lo(h); }
-  static __device__ __forceinline__ unsigned short down(float f, unsigned z) {
-    return T::down(__uint_as_float(__float_as_uint(f) ^ z));
-  }
-};
-
-// the xor tree over the lanes of a group of G (d = G/2 … 1); every lane ends with the result
-template <int G>
-__device__ __forceinline__ float tree_sum(float v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v = v + __shfl_xor(v, d);
-  return v;
-}
-template <int G>
-__device__ __forceinline__ float tree_max(float v) {
-#pragma unroll
-  for (int d = G / 2; d >= 1; d >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, d));
-  return v;
-}
-// the tree's steps d = 32 … G on the NA = 64 / G chains a lane holds (chain index l + G·k ↔ acc[k])
-template <int NA>
-__device__ __forceinline__ float fold_chains(float (&acc)[NA]) {
-#pragma unroll
-  for (int h = NA / 2; h >= 1; h >>= 1)
-#pragma unroll
-    for (int k = 0; k < h; ++k) acc[k] = acc[k] + acc[k + h];
-  return acc[0];
-}
-
-// exp(t − m) without the rounding of the subtraction: t − m = hi + lo exactly (two-sum), exp(hi + lo) = E + E·lo with
-// E = expf(hi) up to lo² ≤ 2⁻³⁸.  (Rounding t − m alone costs half an ulp OF THE DIFFERENCE — 1.9e-6 relative in e at a
-// spread of 32 … 64 — which is sixteen times the exponential's own error.)  A non-finite difference has no low part:
-// −inf gives 0, NaN stays NaN.
-__device__ __forceinline__ float exp_shifted(float t, float m) {
-  const float hi = t - m;
-  const float bb = hi - t;
-  const float lo = (t - (hi - bb)) + (-m - bb);
-  const float e = expf(hi);
-  return __builtin_isfinite(hi) ? __builtin_fmaf(e, lo, e) : e;
-}
 
 // the maximum over the workgroup of one value per thread (red: 4 floats of LDS)
 __device__ __forceinline__ float block_max(float v, float* red) {
@@ -99,17 +48,6 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   return __builtin_fmaxf(__builtin_fmaxf(red[0], red[1]), __builtin_fmaxf(red[2], red[3]));
 }
 
-// (start, length) of global row g of a batch of M-row items; offsets [batch, M + 1] with global bases
-__device__ __forceinline__ void row_span(const int32_t* __restrict__ rowptr, long g, int M, long rows, int& start, int& len) {
-  start = 0;
-  len = 0;
-  if (g < rows) {
-    const long item = g / M, at = g + item;  // item·(M + 1) + (g − item·M)
-    start = rowptr[at];
-    len = rowptr[at + 1] - start;
-    if (len < 0) len = 0;
-  }
-}
 
 // ---------------------------------------------------------------------------
 // forward

@@ -47,6 +47,7 @@ namespace {
 #include "custom_mm_inspect.inc"
 #include "custom_mm_reduce.inc"
 #include "custom_mm_softmax.inc"
+#include "custom_mm_attention.inc"
 
 // ---- handle init / destroy (reference custom_mm.cpp:361-391) ----------------
 // There are no vendor handles on this path; init checks that the C-ABI library
@@ -173,6 +174,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(values, offsets [batch, rows+1], nnz, batch, rows, scale, out): softmax over the stored entries of every CSR row");
   m.def("csr_softmax_backward", &csr_softmax_backward,
         "(y, dy, offsets, nnz, batch, rows, scale, out): out = scale * y * (dy - sum over the row of dy * y)");
+  m.def("sparse_attention_fwd", &sparse_attention_fwd,
+        "(offsets [batch, rows+1], columns, nnz, batch, rows, cols, q, k, v, scale, out, stats [batch*rows, 2]): "
+        "out = softmax(scale * q k^T on the pattern) v in one launch");
+  m.def("sparse_attention_bwd", &sparse_attention_bwd,
+        "(offsets, columns, nnz, batch, rows, cols, q, k, v, dout, stats, scale, dq, y, ds): dq, and y, ds [nnz] in CSR order");
   // Handles and automatic schedules own HIP streams and events: they are released while the interpreter — and with it the HIP
   // runtime — is still up (left to the destructors of the statics they segfaulted at process exit after the runtime had gone:
   // a program that never called cusparse_clean / auto_schedule_clear ended with exit code 139 AFTER its last line of output).

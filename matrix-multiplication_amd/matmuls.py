@@ -1233,7 +1233,7 @@ def sparse_softmax(a: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
     return sparseSoftmax.apply(a, scale)
 
 
-def _check_sampled_operands(pattern, m1, m2t, what='sampled_matmul', device=True):
+def _check_sampled_operands(pattern, m1, m2t, what='sampled_matmul', device=True, batched_lowp=False):
     _check_csr(what, 'pattern', pattern)
     for name, m in (('m1', m1), ('m2t', m2t)):
         if not isinstance(m, torch.Tensor) or m.layout != torch.strided:
@@ -1250,7 +1250,7 @@ def _check_sampled_operands(pattern, m1, m2t, what='sampled_matmul', device=True
             m1.shape[-1] != m2t.shape[-1]:
         raise ValueError(f'{what}: a pattern of shape {tuple(pattern.shape)} needs m1 {lead + (pattern.shape[-2], "N")} and m2t '
                          f'{lead + (pattern.shape[-1], "N")}, got {tuple(m1.shape)} and {tuple(m2t.shape)}')
-    if m1.dtype in _LOWP and pattern.dim() != 2:
+    if m1.dtype in _LOWP and pattern.dim() != 2 and not batched_lowp:  # (only the fused attention kernels take such a batch)
         raise RuntimeError(f'{what}: a batched {m1.dtype} CSR pattern ({pattern.dim()}-d) is not supported (float32 only)')
     if device:
         _check_on_device(what, pattern=torch.Tensor.values(pattern), m1=m1, m2t=m2t)
@@ -1351,3 +1351,152 @@ def sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pattern:
         scale = 1.0 / float(q.shape[-1]) ** 0.5
     scores = sampledMM.apply(pattern, q, k)
     return naiveSpMM.apply(sparseSoftmax.apply(scores, scale), v)
+
+
+# --------------------------------------------------------------------------- #
+# fused sparse attention: one row kernel forward, one backward
+# --------------------------------------------------------------------------- #
+
+def fused_attention_takes(dtype, D: int) -> bool:
+    '''Whether the fused row kernels take head size D in `dtype` — a function of (dtype, D) alone: every multiple of 4
+    (float32) or of 8 (bfloat16 / float16) from 8 to 128.  For any other D fused_sparse_attention runs the composed stages
+    (the same bits by definition).'''
+    if dtype == torch.float32:
+        return 8 <= D <= 128 and D % 4 == 0
+    if dtype in _LOWP:
+        return 8 <= D <= 128 and D % 8 == 0
+    return False
+
+
+def _check_attention_operands(what, q, k, v, pattern, batched_lowp: bool):
+    '''The checks of sparse_attention, under the name `what`; batched_lowp: a batched bfloat16 / float16 pattern passes.'''
+    _check_sampled_operands(pattern, q, k, what, device=False, batched_lowp=batched_lowp)
+    if not isinstance(v, torch.Tensor) or v.layout != torch.strided or v.dim() != q.dim() or \
+            tuple(v.shape[:-1]) != tuple(k.shape[:-1]):
+        raise ValueError(f'{what}: v must be a dense tensor with k\'s leading shape {tuple(k.shape[:-1])}')
+    if v.dtype != q.dtype:
+        raise RuntimeError(f'{what}: q is {q.dtype} but v is {v.dtype}: all operands must have one dtype')
+    _check_on_device(what, pattern=torch.Tensor.values(pattern), q=q, k=k, v=v)
+
+
+def _attention_pattern(pattern, dev, st):
+    '''(offsets int32 [batch, M + 1] with the items' bases, columns int32 item-local, nnz, batch) of a 2-d or batched pattern.'''
+    if pattern.dim() == 2:
+        _, columns, offsets, nnz, _, _ = _csr_props_cached(pattern, st)
+        return offsets, columns, nnz, 1
+    offsets, columns = _batched_pattern(pattern, dev, st)
+    return offsets, columns, columns.numel(), offsets.shape[0]
+
+
+def _block_diagonal_transposed(pattern, dev, st):
+    '''(t_perm, t_col, t_off) of the transpose of the batch's block-diagonal matrix [nb·K, nb·M], from _batched_transposed:
+    the items' transposed columns shifted by item · M, the offsets flattened — ONE 2-d pattern whose rows hold exactly
+    the items' transposed rows, in their order.  Kept beside the batched transpose it is made from.'''
+    bt = _batched_transposed(pattern, dev, st)
+    kept = getattr(st, 'diag_t', None)
+    if kept is None or kept[0] is not bt:
+        t_perm, t_col, t_off = bt[2:]
+        nb, rows = t_off.shape[0], pattern.shape[-2]
+        if nb * max(rows, pattern.shape[-1]) >= 2 ** 31:
+            raise ValueError('fused_sparse_attention: batch · S does not fit the int32 columns of the block-diagonal matrix')
+        per_item = t_col.numel() // nb
+        shift = (torch.arange(nb, device=dev, dtype=torch.int32) * rows).repeat_interleave(per_item)
+        flat_off = torch.cat([t_off[:, :-1].reshape(-1), t_off[-1:, -1]]).contiguous()
+        kept = (bt, t_perm, t_col + shift, flat_off)
+        st.diag_t = kept
+    return kept[1:]
+
+
+class fusedSparseAttention(InplaceFunction):
+    '''softmax(scale · q·kᵀ on the pattern) · v in ONE launch (custom_mm.sparse_attention_fwd), saving q, k, v, the pattern
+    and two floats per row.  Backward: ONE row kernel (custom_mm.sparse_attention_bwd) recomputes the probabilities and
+    writes dq and, in CSR order, y and dS; dv = Pᵀ·dO and dk = dSᵀ·q are CSR × dense products on the kept transposed
+    pattern — a bfloat16 / float16 batch as ONE 2-d product each on the block-diagonal matrix of the batch.'''
+
+    @staticmethod
+    def forward(ctx, q, k, v, pattern, scale):
+        st = _csr_state(pattern)
+        offsets, columns, nnz, nb = _attention_pattern(pattern, q.device, st)
+        rows, cols, n = pattern.shape[-2], pattern.shape[-1], q.shape[-1]
+        q3, k3, v3 = q.reshape(nb, rows, n).contiguous(), k.reshape(nb, cols, n).contiguous(), v.reshape(nb, cols, n).contiguous()
+        out = torch.empty_like(q3)
+        stats = torch.empty((nb * rows, 2), device=q.device, dtype=torch.float32)
+        custom_mm.sparse_attention_fwd(offsets, columns, nnz, nb, rows, cols, q3, k3, v3, float(scale), out, stats)
+        ctx.scale = float(scale)
+        ctx.save_for_backward(q, k, v, pattern, stats)
+        return out.reshape(q.shape)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        q, k, v, pattern, stats = ctx.saved_tensors
+        st = _csr_state(pattern)
+        dev = q.device
+        offsets, columns, nnz, nb = _attention_pattern(pattern, dev, st)
+        rows, cols, n = pattern.shape[-2], pattern.shape[-1], q.shape[-1]
+        q3, k3, v3 = q.reshape(nb, rows, n).contiguous(), k.reshape(nb, cols, n).contiguous(), v.reshape(nb, cols, n).contiguous()
+        g3 = grad_output.to(q.dtype).reshape(nb, rows, n).contiguous()
+        dq = torch.empty_like(q3)
+        y = torch.empty(nnz, device=dev, dtype=q.dtype)
+        ds = torch.empty(nnz, device=dev, dtype=q.dtype)
+        custom_mm.sparse_attention_bwd(offsets, columns, nnz, nb, rows, cols, q3, k3, v3, g3, stats, ctx.scale, dq, y, ds)
+        dk = dv = None
+        need_k, need_v = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if pattern.dim() == 2:
+            if need_k or need_v:
+                t_perm, t_col, t_off = _transposed_pattern(pattern, st)
+            if need_v:
+                dv = custom_mm.naive_spmm(_gather_perm(y, t_perm), t_col, t_off, nnz, cols, rows, g3[0], torch.empty_like(v3[0]))
+            if need_k:
+                dk = custom_mm.naive_spmm(_gather_perm(ds, t_perm), t_col, t_off, nnz, cols, rows, q3[0], torch.empty_like(k3[0]))
+        elif q.dtype in _LOWP:
+            # no batched low-precision product: each gradient is ONE 2-d product on the block-diagonal matrix of the batch
+            if need_k or need_v:
+                t_perm, t_col, t_off = _block_diagonal_transposed(pattern, dev, st)
+            if need_v:
+                dv = custom_mm.naive_spmm(_gather_perm(y, t_perm), t_col, t_off, nnz, nb * cols, nb * rows,
+                                          g3.reshape(nb * rows, n), torch.empty((nb * cols, n), device=dev, dtype=q.dtype))
+            if need_k:
+                dk = custom_mm.naive_spmm(_gather_perm(ds, t_perm), t_col, t_off, nnz, nb * cols, nb * rows,
+                                          q3.reshape(nb * rows, n), torch.empty((nb * cols, n), device=dev, dtype=q.dtype))
+        else:
+            if need_k or need_v:
+                _, _, t_perm, t_col, t_off = _batched_transposed(pattern, dev, st)
+            for need, vals, dense, name in ((need_v, y, g3, 'v'), (need_k, ds, q3, 'k')):
+                if not need:
+                    continue
+                t_val = _gather_perm(vals, t_perm)
+                gb = torch.empty_like(k3)
+                for lo, hi in _item_chunks(nb):
+                    custom_mm.naive_spmm_batched(t_val, t_col, t_off[lo:hi].contiguous(), nnz, hi - lo, cols, rows, dense[lo:hi], gb[lo:hi])
+                if name == 'v':
+                    dv = gb
+                else:
+                    dk = gb
+        return (dq.reshape(q.shape) if ctx.needs_input_grad[0] else None,
+                dk.reshape(k.shape) if dk is not None else None, dv.reshape(v.shape) if dv is not None else None, None, None)
+
+
+def fused_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pattern: torch.Tensor, scale=None) -> torch.Tensor:
+    '''sparse_attention(q, k, v, pattern, scale) — softmax(scale · q·kᵀ restricted to `pattern`) · v, scale 1/√D by default —
+    as ONE kernel forward and ONE row kernel backward: no score or probability tensor is written forward, and autograd
+    keeps q, k, v, the pattern and two floats per row.  float32, bfloat16 or float16; 2-d patterns, or batched ones with any
+    leading dimensions — in all three dtypes (sparse_attention refuses a batched bfloat16 / float16 pattern).
+
+    The bits are sparse_attention's, forward and gradients; a bfloat16 / float16 batch equals the 2-d sparse_attention
+    applied item by item.  One exception: the output is one fmaf chain per element over the row's entries in CSR order for
+    EVERY row length, while the 2-d sparse_attention splits rows beyond mi_spmm_long_row_threshold() (8192) entries.
+    Head sizes the kernels do not take (see fused_attention_takes) run the composed stages; a batched bfloat16 / float16
+    call with such a head size raises.  Differentiable in q, k and v.'''
+    _check_attention_operands('fused_sparse_attention', q, k, v, pattern, batched_lowp=True)
+    n = q.shape[-1]
+    if scale is None:
+        scale = 1.0 / float(n) ** 0.5
+    # (the plain-Python stand-in of the host-logic tests takes every head size and dtype)
+    if _REAL_EXTENSION and not fused_attention_takes(q.dtype, n):
+        if q.dtype in _LOWP and pattern.dim() != 2:
+            raise RuntimeError(f'fused_sparse_attention: a batched {q.dtype} pattern needs a head size that is a multiple of 8 '
+                               f'from 8 to 128, got {n} (the composed stages have no batched {q.dtype} form)')
+        return naiveSpMM.apply(sparseSoftmax.apply(sampledMM.apply(pattern, q, k), scale), v)
+    if torch.Tensor.values(pattern).numel() >= 2 ** 31:
+        raise ValueError('fused_sparse_attention: nnz does not fit int32 indices')
+    return fusedSparseAttention.apply(q, k, v, pattern, scale)
