@@ -929,6 +929,58 @@ int mi_sparse_attention_backward_f16(const int32_t* rowptr, const int32_t* col, 
                                      uint16_t* dq, int64_t lddq, int64_t strideDQ, uint16_t* y, uint16_t* ds, void* workspace,
                                      size_t workspace_bytes, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Block-sparse attention on the matrix cores — NEW relative to the reference: out = softmax(scale · q·kᵀ + mask) · v in
+ * bfloat16 / float16 (T, 2-byte bit patterns), where the mask keeps the 64 × 64 blocks a CSR block layout lists and,
+ * with causal != 0, the positions j ≤ i; and its backward:
+ *   rowptr   int32 [layouts][Sq/64 + 1] with the layouts' bases, col int32 [nnz] layout-local key blocks in any order
+ *            (a duplicate block is unsupported: it would count twice); item i of the batch uses layout i mod layouts;
+ *   t_rowptr int32 [layouts][Sk/64 + 1], t_col [nnz]: the transposed lists (backward: key block → its query blocks);
+ *   q, out, dout, dq [batch][Sq][D]; k, v, dk, dv [batch][Sk][D]: leading dimension ld ≥ D and item stride in elements,
+ *            base 16-byte aligned, ld and stride multiples of 8; D ∈ {32, 64, 96, 128}; Sq, Sk multiples of 64;
+ *   lse      float [batch][Sq], 16-byte aligned: m + ln Σ exp(t − m) of every query row, −inf for a row that sees nothing
+ *            (forward: written; backward: read);
+ *   workspace (backward) mi_block_attention_workspace_bytes(batch, Sq) bytes, 16-byte aligned: δ = rowsum(dO ∘ O).
+ * Arithmetic: every product is v_mfma_f32_16x16x32_T with fp32 accumulators; scores, maxima, sums, lse and δ stay fp32;
+ * P is narrowed to T only as the operand of P·V / dOᵀ·P, dS only as the operand of dS·K / dSᵀ·Q; out, dq, dk, dv are
+ * rounded once at the store.  A query block walks its list in CSR order with the online softmax (running maximum and
+ * sum); the backward recomputes P = exp(t − lse) per tile (a −inf lse gives 0); dk and dv are summed per key block over
+ * the transposed list in its order.  Blocks outside the list are never read; causal skips listed blocks above the
+ * diagonal (needs Sq == Sk).  A row that sees nothing gives zero rows of out and dq, a key nobody sees zero rows of dk
+ * and dv.  No atomics, no host synchronisation: graph-capturable; the bits of an output depend on its item and its
+ * layout only.  A listed block outside the grid is skipped, offsets are clamped to [0, nnz].
+ * Validation before any HIP call: a negative size, an unsupported D, Sq or Sk not a multiple of 64, causal with
+ * Sq != Sk → MI_EINVAL; nnz ≥ 2³¹ → MI_ERANGE; batch == 0 or Sq == 0 → MI_OK, nothing touched; layouts == 0, a NULL or
+ * misaligned pointer, ld < D, Sk == 0 with entries → MI_EINVAL; a short workspace → MI_ENOMEM.
+ * ------------------------------------------------------------------------ */
+size_t mi_block_attention_workspace_bytes(int32_t batch, int32_t Sq);
+int mi_block_attention_fwd_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t batch,
+                                int32_t Sq, int32_t Sk, int32_t D, int32_t causal, const uint16_t* q, int64_t ldq,
+                                int64_t strideQ, const uint16_t* k, int64_t ldk, int64_t strideK, const uint16_t* v,
+                                int64_t ldv, int64_t strideV, float scale, uint16_t* out, int64_t ldo, int64_t strideO,
+                                float* lse, mi_stream_t stream);
+int mi_block_attention_fwd_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t batch,
+                               int32_t Sq, int32_t Sk, int32_t D, int32_t causal, const uint16_t* q, int64_t ldq,
+                               int64_t strideQ, const uint16_t* k, int64_t ldk, int64_t strideK, const uint16_t* v,
+                               int64_t ldv, int64_t strideV, float scale, uint16_t* out, int64_t ldo, int64_t strideO,
+                               float* lse, mi_stream_t stream);
+int mi_block_attention_bwd_bf16(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col,
+                                int64_t nnz, int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk, int32_t D,
+                                int32_t causal, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k,
+                                int64_t ldk, int64_t strideK, const uint16_t* v, int64_t ldv, int64_t strideV,
+                                const uint16_t* out, int64_t ldo, int64_t strideO, const uint16_t* dout, int64_t lddo,
+                                int64_t strideDO, const float* lse, float scale, uint16_t* dq, int64_t lddq,
+                                int64_t strideDQ, uint16_t* dk, int64_t lddk, int64_t strideDK, uint16_t* dv, int64_t lddv,
+                                int64_t strideDV, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_block_attention_bwd_f16(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col,
+                               int64_t nnz, int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk, int32_t D,
+                               int32_t causal, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k,
+                               int64_t ldk, int64_t strideK, const uint16_t* v, int64_t ldv, int64_t strideV,
+                               const uint16_t* out, int64_t ldo, int64_t strideO, const uint16_t* dout, int64_t lddo,
+                               int64_t strideDO, const float* lse, float scale, uint16_t* dq, int64_t lddq,
+                               int64_t strideDQ, uint16_t* dk, int64_t lddk, int64_t strideDK, uint16_t* dv, int64_t lddv,
+                               int64_t strideDV, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+
 int mi_ipc_export(const void* dev_ptr, void* handle_out, int64_t* offset_out, int64_t* alloc_bytes_out);
 int mi_ipc_open(const void* handle, void** base_out);
 int mi_ipc_close(const void* handle);

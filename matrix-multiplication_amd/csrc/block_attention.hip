@@ -1,0 +1,560 @@
+// Block-sparse attention in bfloat16 and float16 on the matrix cores: out = softmax(scale · q·kᵀ + mask) · v, where the mask
+// keeps the 64 × 64 blocks a CSR block layout lists (and, causal, the positions j ≤ i), with its backward.  q, k, v, out
+// and the gradients are all of one type T ∈ {bf16, fp16} (2-byte bit patterns at the C-ABI).
+//
+// What it computes (contract of include/mi_spmm.h, mi_block_attention_{fwd,bwd}_{bf16,f16} — DESIGN.md §3.14):
+//  * ONE instruction for every product: v_mfma_f32_16x16x32_{bf16,f16}, fp32 accumulators.  Scores, row maxima, row sums,
+//    the log-sum-exp and δ = rowsum(dO ∘ O) stay in fp32; P is narrowed to T only as the operand of P·V (and of dOᵀ·P),
+//    dS only as the operand of dS·K and dSᵀ·Q; out, dq, dk and dv are rounded once, at the store.
+//  * Order: a query block walks its kept key blocks in the order of the CSR list, a key block (backward) the query blocks
+//    of the TRANSPOSED list in its order; every output element is one accumulator of one wave.  The bits of an output
+//    depend on its own item and its layout only — never on the batch, the neighbours or the launch.  No atomics, no host
+//    read-back: graph-capturable.
+//  * A block outside the list is never loaded.  causal: a listed block strictly above the diagonal is skipped, the
+//    diagonal block masked by position.  A query row that sees nothing gives a zero row of out and dq and −inf as its
+//    log-sum-exp; a key nobody sees zero rows of dk and dv.  A listed column outside [0, blocks) is skipped, offsets are
+//    clamped to the list: a malformed layout cannot make a kernel read outside the operands.
+//
+// Kernels: a 256-thread workgroup owns one 64-row block of one item; wave w its rows 16w … 16w + 15 ("own" rows), held
+// as MFMA B fragments in registers for the whole walk.  Each listed block of the other side ("walk" rows, 64 of them)
+// is staged through registers into LDS (the global loads of the next block are in flight while this one is computed):
+// a row image [64][D + 8] for the products that sum over d, and a transposed image [D][64 + 8] for those that sum over
+// the walk rows.  With the walk rows as the MFMA A operand a score tile arrives with the OWN row on the lane (lane & 15)
+// and 16 walk rows in its registers (16f + 4(lane >> 4) + r): the softmax constants of an own row are lane scalars, a row
+// reduction is 15 in-register steps and two cross-lane ones, and the tile, packed, is already the B operand of the
+// product that sums over the walk rows (k-slot (lane >> 4, j) of step s ↦ walk row 32s + 16(j >> 2) + 4(lane >> 4) + (j & 3);
+// the transposed image is read in the same permuted order).  Results arrive as [d][own row]: four adjacent d per lane.
+//  * forward: own = q; walk = k (scores), vᵀ (P·V); online softmax (running maximum and sum, rescale).
+//  * backward, query blocks: own = q, dO; walk = k (S), v (dP), kᵀ (dQ += dS·K); δ computed in the prologue and written
+//    for the key-block kernel; P = exp(scale·S − lse).
+//  * backward, key blocks over the transposed layout: own = k, v; walk = q (Sᵀ), dO (dPᵀ), dOᵀ (dV += Pᵀ·dO),
+//    qᵀ (dK += dSᵀ·Q); lse and δ of the walk rows are read per tile.
+#include "lowp_device.h"
+
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+template <class T>
+__device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c);
+template <>
+__device__ __forceinline__ f32x4 mfma<Bf16>(uint4 a, uint4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+template <>
+__device__ __forceinline__ f32x4 mfma<F16>(uint4 a, uint4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
+constexpr int kB = 64;         // rows of a block: the kernels' tile on both sides
+constexpr int kTStr = kB + 8;  // row stride of a transposed image in elements (144 bytes)
+
+struct Dense {  // a [batch][rows][D] operand: leading dimension and item stride in elements
+  uint16_t* p;
+  long ld, stride;
+};
+
+struct Args {
+  const int32_t* rowptr;  // [layouts][own blocks + 1], with the layouts' bases
+  const int32_t* col;     // [nnz], layout-local block columns
+  long nnz;
+  int layouts, batch, own_blocks, walk_blocks;
+  long own_rows;  // rows of an item on the own side (lse, δ: [batch][own_rows]; walk side: walk_rows)
+  long walk_rows;
+  float scale;
+  Dense q, k, v, o, dout, dq, dk, dv;
+  float* lse;    // [batch][Sq]
+  float* delta;  // [batch][Sq]
+};
+
+__device__ __forceinline__ unsigned half_of(uint4 v, int i) {
+  const unsigned w = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
+  return (i & 1) ? (w >> 16) : (w & 0xffffu);
+}
+
+// One 64 × D block in registers: unit u = tid < 2D holds rows 4(u & 15) … + 3, columns 8(u >> 4) … + 7.
+template <int D>
+struct Tile {
+  uint4 v[4];
+  __device__ __forceinline__ void load(const uint16_t* src, long ld, int tid) {
+    if (tid < 2 * D) {
+      const uint16_t* p = src + (long)(4 * (tid & 15)) * ld + 8 * (tid >> 4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const uint4*>(p + i * ld);
+    }
+  }
+  // the row image [64][D + 8]
+  __device__ __forceinline__ void store_rows(unsigned short* R, int tid) const {
+    if (tid < 2 * D) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(R + (4 * (tid & 15) + i) * (D + 8) + 8 * (tid >> 4)) = v[i];
+    }
+  }
+  // the transposed image [D][64 + 8]
+  __device__ __forceinline__ void store_transposed(unsigned short* Tt, int tid) const {
+    if (tid < 2 * D) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const uint2 w = {half_of(v[0], e) | (half_of(v[1], e) << 16), half_of(v[2], e) | (half_of(v[3], e) << 16)};
+        *reinterpret_cast<uint2*>(Tt + (8 * (tid >> 4) + e) * kTStr + 4 * (tid & 15)) = w;
+      }
+    }
+  }
+};
+
+// The wave's 16 own rows as B fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of row li.
+template <int D>
+__device__ __forceinline__ void load_own(uint4 (&f)[D / 32], const uint16_t* rows, long ld, int li, int lg) {
+#pragma unroll
+  for (int s = 0; s < D / 32; ++s) f[s] = *reinterpret_cast<const uint4*>(rows + (long)li * ld + 32 * s + 8 * lg);
+}
+
+// acc[f][r] = ⟨walk row 16f + 4lg + r, own row li⟩ over d, from the row image R of the walk block
+template <class T, int D>
+__device__ __forceinline__ void score(f32x4 (&acc)[4], const unsigned short* R, const uint4 (&own)[D / 32], int li, int lg) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s) {
+      const uint4 a = *reinterpret_cast<const uint4*>(R + (16 * f + li) * (D + 8) + 32 * s + 8 * lg);
+      acc[f] = mfma<T>(a, own[s], acc[f]);
+    }
+  }
+}
+
+// a score-shaped tile narrowed to T as the B operand of the two k-steps over the walk rows
+template <class T>
+__device__ __forceinline__ void pack_tile(uint4 (&b)[2], const f32x4 (&x)[4]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+    b[s] = uint4{pack2<T>(x[2 * s][0], x[2 * s][1]), pack2<T>(x[2 * s][2], x[2 * s][3]), pack2<T>(x[2 * s + 1][0], x[2 * s + 1][1]),
+                 pack2<T>(x[2 * s + 1][2], x[2 * s + 1][3])};
+}
+
+// out[fd][r] += Σ over the walk rows of Tt[d = 16fd + 4lg + r][walk row] · b[walk row][own row li]
+template <class T, int D>
+__device__ __forceinline__ void accumulate(f32x4 (&out)[D / 16], const unsigned short* Tt, const uint4 (&b)[2], int li, int lg) {
+#pragma unroll
+  for (int fd = 0; fd < D / 16; ++fd)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const unsigned short* p = Tt + (16 * fd + li) * kTStr + 32 * s + 4 * lg;
+      const uint2 lo = *reinterpret_cast<const uint2*>(p), hi = *reinterpret_cast<const uint2*>(p + 16);
+      out[fd] = mfma<T>(uint4{lo.x, lo.y, hi.x, hi.y}, b[s], out[fd]);
+    }
+}
+
+// rows [d][own row li] → own row li, columns 16fd + 4lg … + 3, each value times `mul`, rounded once
+template <class T, int D>
+__device__ __forceinline__ void store_own(const f32x4 (&acc)[D / 16], float mul, uint16_t* rows, long ld, int li, int lg) {
+#pragma unroll
+  for (int fd = 0; fd < D / 16; ++fd) {
+    const f32x4 x = acc[fd];
+    *reinterpret_cast<uint2*>(rows + (long)li * ld + 16 * fd + 4 * lg) =
+        uint2{pack2<T>(x[0] * mul, x[1] * mul), pack2<T>(x[2] * mul, x[3] * mul)};
+  }
+}
+
+// the next listed block at or after p that is computed: inside the grid and, causal, not beyond the own block's diagonal.
+// own_first: the own side is the query side (skip walk blocks J > I); else the key side (skip walk blocks I < J).
+template <bool CAUSAL, bool OWN_IS_QUERY>
+__device__ __forceinline__ int next_block(const int32_t* col, int p, int end, int own_block, int walk_blocks) {
+  for (; p < end; ++p) {
+    const int j = col[p];
+    if ((unsigned)j >= (unsigned)walk_blocks) continue;
+    if (CAUSAL && (OWN_IS_QUERY ? j > own_block : j < own_block)) continue;
+    break;
+  }
+  return p;
+}
+
+__device__ __forceinline__ float group_max(float x) {  // over the four lanes li, li + 16, li + 32, li + 48
+  x = fmaxf(x, __shfl_xor(x, 16));
+  return fmaxf(x, __shfl_xor(x, 32));
+}
+__device__ __forceinline__ float group_sum(float x) {
+  x = x + __shfl_xor(x, 16);
+  return x + __shfl_xor(x, 32);
+}
+
+struct Walk {  // the part of a layout's list one workgroup walks
+  const int32_t* col;
+  int beg, end;
+};
+__device__ __forceinline__ Walk walk_of(const Args& a, int item, int own_block) {
+  const int lay = item % a.layouts;
+  const int32_t* rp = a.rowptr + (long)lay * (a.own_blocks + 1);
+  long beg = rp[own_block], end = rp[own_block + 1];
+  beg = beg < 0 ? 0 : beg;
+  end = end > a.nnz ? a.nnz : end;
+  return Walk{a.col, (int)beg, (int)end};
+}
+
+template <class T, int D, bool CAUSAL>
+__global__ __launch_bounds__(256) void block_attention_fwd_kernel(Args a) {
+  __shared__ __attribute__((aligned(16))) unsigned short Ks[kB * (D + 8)];
+  __shared__ __attribute__((aligned(16))) unsigned short Vt[D * kTStr];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
+  const int I = blockIdx.x;
+  for (int b = blockIdx.y; b < a.batch; b += gridDim.y) {
+    const Walk wk = walk_of(a, b, I);
+    const uint16_t* K = a.k.p + (long)b * a.k.stride;
+    const uint16_t* V = a.v.p + (long)b * a.v.stride;
+    const long row0 = (long)I * kB + 16 * w;
+    uint4 qf[D / 32];
+    load_own<D>(qf, a.q.p + (long)b * a.q.stride + row0 * a.q.ld, a.q.ld, li, lg);
+    f32x4 o[D / 16];
+#pragma unroll
+    for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+
+    Tile<D> tk, tv;
+    int p = next_block<CAUSAL, true>(wk.col, wk.beg, wk.end, I, a.walk_blocks);
+    if (p < wk.end) {
+      tk.load(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid);
+      tv.load(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid);
+    }
+    while (p < wk.end) {
+      const int J = wk.col[p];
+      __syncthreads();  // the previous block's reads are done
+      tk.store_rows(Ks, tid);
+      tv.store_transposed(Vt, tid);
+      __syncthreads();
+      p = next_block<CAUSAL, true>(wk.col, p + 1, wk.end, I, a.walk_blocks);
+      if (p < wk.end) {
+        tk.load(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid);
+        tv.load(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid);
+      }
+      f32x4 s[4];
+      score<T, D>(s, Ks, qf, li, lg);
+      float mt = -INFINITY;
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float t = s[f][r] * a.scale;
+          if (CAUSAL && J == I && 16 * f + 4 * lg + r > 16 * w + li) t = -INFINITY;
+          s[f][r] = t;
+          mt = fmaxf(mt, t);
+        }
+      const float mn = fmaxf(m, group_max(mt));
+      const float alpha = m == mn ? 1.f : __expf(m - mn);  // (−inf stays: nothing seen yet)
+      float sum = 0.f;
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = s[f][r] == -INFINITY ? 0.f : __expf(s[f][r] - mn);
+          s[f][r] = e;
+          sum += e;
+        }
+      l = l * alpha + sum;  // this lane's share of the row sum; the four shares meet after the walk
+      m = mn;
+#pragma unroll
+      for (int fd = 0; fd < D / 16; ++fd)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[fd][r] *= alpha;
+      uint4 pb[2];
+      pack_tile<T>(pb, s);
+      accumulate<T, D>(o, Vt, pb, li, lg);
+    }
+    l = group_sum(l);
+    const float inv = l == 0.f ? 0.f : 1.f / l;
+    store_own<T, D>(o, inv, a.o.p + (long)b * a.o.stride + row0 * a.o.ld, a.o.ld, li, lg);
+    if (lg == 0) a.lse[(long)b * a.own_rows + row0 + li] = l == 0.f ? -INFINITY : m + __logf(l);
+    __syncthreads();  // the next item restages
+  }
+}
+
+// P of a score tile from the rows' log-sum-exp: own row on the lane (lse a lane scalar)
+__device__ __forceinline__ float prob(float t, float lse) {
+  return (lse == -INFINITY || t == -INFINITY) ? 0.f : __expf(t - lse);
+}
+
+// dQ over the layout; own = q and dO.  Also writes δ = rowsum(dO ∘ O) of its rows.
+template <class T, int D, bool CAUSAL>
+__global__ __launch_bounds__(256) void block_attention_dq_kernel(Args a) {
+  __shared__ __attribute__((aligned(16))) unsigned short Ks[kB * (D + 8)];
+  __shared__ __attribute__((aligned(16))) unsigned short Vs[kB * (D + 8)];
+  __shared__ __attribute__((aligned(16))) unsigned short Kt[D * kTStr];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
+  const int I = blockIdx.x;
+  for (int b = blockIdx.y; b < a.batch; b += gridDim.y) {
+    const Walk wk = walk_of(a, b, I);
+    const uint16_t* K = a.k.p + (long)b * a.k.stride;
+    const uint16_t* V = a.v.p + (long)b * a.v.stride;
+    const long row0 = (long)I * kB + 16 * w;
+    uint4 qf[D / 32], gf[D / 32], of[D / 32];
+    load_own<D>(qf, a.q.p + (long)b * a.q.stride + row0 * a.q.ld, a.q.ld, li, lg);
+    load_own<D>(gf, a.dout.p + (long)b * a.dout.stride + row0 * a.dout.ld, a.dout.ld, li, lg);
+    load_own<D>(of, a.o.p + (long)b * a.o.stride + row0 * a.o.ld, a.o.ld, li, lg);
+    float delta = 0.f;
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) delta = fmaf(up<T>((unsigned short)half_of(gf[s], e)), up<T>((unsigned short)half_of(of[s], e)), delta);
+    delta = group_sum(delta);
+    const float lse = a.lse[(long)b * a.own_rows + row0 + li];
+    if (lg == 0) a.delta[(long)b * a.own_rows + row0 + li] = delta;
+    f32x4 dq[D / 16];
+#pragma unroll
+    for (int fd = 0; fd < D / 16; ++fd) dq[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    Tile<D> tk, tv;
+    int p = next_block<CAUSAL, true>(wk.col, wk.beg, wk.end, I, a.walk_blocks);
+    if (p < wk.end) {
+      tk.load(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid);
+      tv.load(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid);
+    }
+    while (p < wk.end) {
+      const int J = wk.col[p];
+      __syncthreads();
+      tk.store_rows(Ks, tid);
+      tk.store_transposed(Kt, tid);
+      tv.store_rows(Vs, tid);
+      __syncthreads();
+      p = next_block<CAUSAL, true>(wk.col, p + 1, wk.end, I, a.walk_blocks);
+      if (p < wk.end) {
+        tk.load(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid);
+        tv.load(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid);
+      }
+      f32x4 s[4], dp[4];
+      score<T, D>(s, Ks, qf, li, lg);
+      score<T, D>(dp, Vs, gf, li, lg);
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float t = s[f][r] * a.scale;
+          if (CAUSAL && J == I && 16 * f + 4 * lg + r > 16 * w + li) t = -INFINITY;
+          const float pr = prob(t, lse);
+          s[f][r] = pr == 0.f ? 0.f : pr * (dp[f][r] - delta);
+        }
+      uint4 db[2];
+      pack_tile<T>(db, s);
+      accumulate<T, D>(dq, Kt, db, li, lg);
+    }
+    store_own<T, D>(dq, a.scale, a.dq.p + (long)b * a.dq.stride + row0 * a.dq.ld, a.dq.ld, li, lg);
+    __syncthreads();
+  }
+}
+
+// dK and dV over the transposed layout; own = k and v (a.rowptr / a.col are the transposed list, own_* the key side).
+template <class T, int D, bool CAUSAL>
+__global__ __launch_bounds__(256) void block_attention_dkv_kernel(Args a) {
+  __shared__ __attribute__((aligned(16))) unsigned short Qs[kB * (D + 8)];
+  __shared__ __attribute__((aligned(16))) unsigned short Gs[kB * (D + 8)];
+  __shared__ __attribute__((aligned(16))) unsigned short Qt[D * kTStr];
+  __shared__ __attribute__((aligned(16))) unsigned short Gt[D * kTStr];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
+  const int J = blockIdx.x;
+  for (int b = blockIdx.y; b < a.batch; b += gridDim.y) {
+    const Walk wk = walk_of(a, b, J);
+    const uint16_t* Q = a.q.p + (long)b * a.q.stride;
+    const uint16_t* G = a.dout.p + (long)b * a.dout.stride;
+    const float* lse = a.lse + (long)b * a.walk_rows;
+    const float* delta = a.delta + (long)b * a.walk_rows;
+    const long row0 = (long)J * kB + 16 * w;
+    uint4 kf[D / 32], vf[D / 32];
+    load_own<D>(kf, a.k.p + (long)b * a.k.stride + row0 * a.k.ld, a.k.ld, li, lg);
+    load_own<D>(vf, a.v.p + (long)b * a.v.stride + row0 * a.v.ld, a.v.ld, li, lg);
+    f32x4 dk[D / 16], dv[D / 16];
+#pragma unroll
+    for (int fd = 0; fd < D / 16; ++fd) dk[fd] = dv[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    Tile<D> tq, tg;
+    int p = next_block<CAUSAL, false>(wk.col, wk.beg, wk.end, J, a.walk_blocks);
+    if (p < wk.end) {
+      tq.load(Q + (long)wk.col[p] * kB * a.q.ld, a.q.ld, tid);
+      tg.load(G + (long)wk.col[p] * kB * a.dout.ld, a.dout.ld, tid);
+    }
+    while (p < wk.end) {
+      const int I = wk.col[p];
+      __syncthreads();
+      tq.store_rows(Qs, tid);
+      tq.store_transposed(Qt, tid);
+      tg.store_rows(Gs, tid);
+      tg.store_transposed(Gt, tid);
+      __syncthreads();
+      p = next_block<CAUSAL, false>(wk.col, p + 1, wk.end, J, a.walk_blocks);
+      if (p < wk.end) {
+        tq.load(Q + (long)wk.col[p] * kB * a.q.ld, a.q.ld, tid);
+        tg.load(G + (long)wk.col[p] * kB * a.dout.ld, a.dout.ld, tid);
+      }
+      f32x4 s[4], dp[4];
+      score<T, D>(s, Qs, kf, li, lg);   // s[f][r]: query 16f + 4lg + r of block I against key li of the wave
+      score<T, D>(dp, Gs, vf, li, lg);
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        const f32x4 ls = *reinterpret_cast<const f32x4*>(lse + (long)I * kB + 16 * f + 4 * lg);
+        const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + (long)I * kB + 16 * f + 4 * lg);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float t = s[f][r] * a.scale;
+          if (CAUSAL && I == J && 16 * w + li > 16 * f + 4 * lg + r) t = -INFINITY;
+          const float pr = prob(t, ls[r]);
+          s[f][r] = pr;
+          dp[f][r] = pr == 0.f ? 0.f : pr * (dp[f][r] - dl[r]);
+        }
+      }
+      uint4 pb[2], db[2];
+      pack_tile<T>(pb, s);
+      pack_tile<T>(db, dp);
+      accumulate<T, D>(dv, Gt, pb, li, lg);
+      accumulate<T, D>(dk, Qt, db, li, lg);
+    }
+    store_own<T, D>(dv, 1.f, a.dv.p + (long)b * a.dv.stride + row0 * a.dv.ld, a.dv.ld, li, lg);
+    store_own<T, D>(dk, a.scale, a.dk.p + (long)b * a.dk.stride + row0 * a.dk.ld, a.dk.ld, li, lg);
+    __syncthreads();
+  }
+}
+
+bool takes_width(int32_t D) { return D == 32 || D == 64 || D == 96 || D == 128; }
+
+// a [batch][rows][D] operand whose rows move as 16-byte pieces
+bool dense_ok(const uint16_t* p, int64_t ld, int64_t stride, int32_t D) {
+  return p != nullptr && mi::aligned16(p) && ld >= D && ld % 8 == 0 && stride >= 0 && stride % 8 == 0;
+}
+
+// The checks every entry makes before its first HIP call.  MI_OK with *empty set: nothing to compute.
+int validate(int64_t nnz, int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk, int32_t D, int32_t causal, bool* empty) {
+  *empty = false;
+  if (nnz < 0 || layouts < 0 || batch < 0 || Sq < 0 || Sk < 0 || D < 0) return MI_EINVAL;
+  if (nnz > 0x7fffffffLL) return MI_ERANGE;
+  if (!takes_width(D) || Sq % kB != 0 || Sk % kB != 0) return MI_EINVAL;
+  if (causal && Sq != Sk) return MI_EINVAL;
+  if (batch == 0 || Sq == 0) {
+    *empty = true;
+    return MI_OK;
+  }
+  if (layouts == 0 || (nnz > 0 && Sk == 0)) return MI_EINVAL;
+  return MI_OK;
+}
+
+template <class T, int D>
+int launch_fwd(const Args& a, bool causal, hipStream_t s) {
+  const dim3 grid((unsigned)a.own_blocks, (unsigned)(a.batch < 65535 ? a.batch : 65535));
+  if (causal)
+    hipLaunchKernelGGL((block_attention_fwd_kernel<T, D, true>), grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((block_attention_fwd_kernel<T, D, false>), grid, dim3(256), 0, s, a);
+  return mi::check_launch();
+}
+
+template <class T, int D>
+int launch_bwd(const Args& aq, const Args& ak, bool causal, hipStream_t s) {
+  const unsigned gy = (unsigned)(aq.batch < 65535 ? aq.batch : 65535);
+  if (causal)
+    hipLaunchKernelGGL((block_attention_dq_kernel<T, D, true>), dim3((unsigned)aq.own_blocks, gy), dim3(256), 0, s, aq);
+  else
+    hipLaunchKernelGGL((block_attention_dq_kernel<T, D, false>), dim3((unsigned)aq.own_blocks, gy), dim3(256), 0, s, aq);
+  const int st = mi::check_launch();
+  if (st != MI_OK || ak.own_blocks == 0) return st;
+  if (causal)
+    hipLaunchKernelGGL((block_attention_dkv_kernel<T, D, true>), dim3((unsigned)ak.own_blocks, gy), dim3(256), 0, s, ak);
+  else
+    hipLaunchKernelGGL((block_attention_dkv_kernel<T, D, false>), dim3((unsigned)ak.own_blocks, gy), dim3(256), 0, s, ak);
+  return mi::check_launch();
+}
+
+Dense dense(const uint16_t* p, int64_t ld, int64_t stride) { return Dense{const_cast<uint16_t*>(p), (long)ld, (long)stride}; }
+
+template <class T>
+int forward_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk,
+                  int32_t D, int32_t causal, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k, int64_t ldk,
+                  int64_t strideK, const uint16_t* v, int64_t ldv, int64_t strideV, float scale, uint16_t* out, int64_t ldo,
+                  int64_t strideO, float* lse, hipStream_t s) {
+  bool empty;
+  const int st = validate(nnz, layouts, batch, Sq, Sk, D, causal, &empty);
+  if (st != MI_OK || empty) return st;
+  if (!rowptr || !lse || (nnz > 0 && !col) || (reinterpret_cast<uintptr_t>(lse) & 3u)) return MI_EINVAL;
+  if (!dense_ok(q, ldq, strideQ, D) || !dense_ok(out, ldo, strideO, D)) return MI_EINVAL;
+  if (nnz > 0 && (!dense_ok(k, ldk, strideK, D) || !dense_ok(v, ldv, strideV, D))) return MI_EINVAL;
+  Args a = {};
+  a.rowptr = rowptr, a.col = col, a.nnz = nnz, a.layouts = layouts, a.batch = batch;
+  a.own_blocks = Sq / kB, a.walk_blocks = Sk / kB, a.own_rows = Sq, a.walk_rows = Sk, a.scale = scale;
+  a.q = dense(q, ldq, strideQ), a.k = dense(k, ldk, strideK), a.v = dense(v, ldv, strideV), a.o = dense(out, ldo, strideO);
+  a.lse = lse;
+  switch (D) {
+    case 32: return launch_fwd<T, 32>(a, causal != 0, s);
+    case 64: return launch_fwd<T, 64>(a, causal != 0, s);
+    case 96: return launch_fwd<T, 96>(a, causal != 0, s);
+    default: return launch_fwd<T, 128>(a, causal != 0, s);
+  }
+}
+
+template <class T>
+int backward_entry(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col, int64_t nnz,
+                   int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk, int32_t D, int32_t causal, const uint16_t* q,
+                   int64_t ldq, int64_t strideQ, const uint16_t* k, int64_t ldk, int64_t strideK, const uint16_t* v, int64_t ldv,
+                   int64_t strideV, const uint16_t* out, int64_t ldo, int64_t strideO, const uint16_t* dout, int64_t lddo,
+                   int64_t strideDO, const float* lse, float scale, uint16_t* dq, int64_t lddq, int64_t strideDQ, uint16_t* dk,
+                   int64_t lddk, int64_t strideDK, uint16_t* dv, int64_t lddv, int64_t strideDV, void* workspace,
+                   size_t workspace_bytes, hipStream_t s) {
+  bool empty;
+  const int st = validate(nnz, layouts, batch, Sq, Sk, D, causal, &empty);
+  if (st != MI_OK || empty) return st;
+  if (!rowptr || !t_rowptr || !lse || (nnz > 0 && (!col || !t_col)) || !mi::aligned16(lse)) return MI_EINVAL;
+  if (!dense_ok(q, ldq, strideQ, D) || !dense_ok(out, ldo, strideO, D) || !dense_ok(dout, lddo, strideDO, D) ||
+      !dense_ok(dq, lddq, strideDQ, D))
+    return MI_EINVAL;
+  if (Sk > 0 && (!dense_ok(k, ldk, strideK, D) || !dense_ok(v, ldv, strideV, D) || !dense_ok(dk, lddk, strideDK, D) ||
+                 !dense_ok(dv, lddv, strideDV, D)))
+    return MI_EINVAL;
+  if (!workspace || !mi::aligned16(workspace)) return MI_EINVAL;
+  if (workspace_bytes < mi_block_attention_workspace_bytes(batch, Sq)) return MI_ENOMEM;
+  Args aq = {};
+  aq.rowptr = rowptr, aq.col = col, aq.nnz = nnz, aq.layouts = layouts, aq.batch = batch;
+  aq.own_blocks = Sq / kB, aq.walk_blocks = Sk / kB, aq.own_rows = Sq, aq.walk_rows = Sk, aq.scale = scale;
+  aq.q = dense(q, ldq, strideQ), aq.k = dense(k, ldk, strideK), aq.v = dense(v, ldv, strideV), aq.o = dense(out, ldo, strideO);
+  aq.dout = dense(dout, lddo, strideDO), aq.dq = dense(dq, lddq, strideDQ), aq.dk = dense(dk, lddk, strideDK);
+  aq.dv = dense(dv, lddv, strideDV);
+  aq.lse = const_cast<float*>(lse), aq.delta = static_cast<float*>(workspace);
+  Args ak = aq;  // the key side owns: the transposed list, lse and δ indexed by the walk (query) rows
+  ak.rowptr = t_rowptr, ak.col = t_col;
+  ak.own_blocks = Sk / kB, ak.walk_blocks = Sq / kB, ak.own_rows = Sk, ak.walk_rows = Sq;
+  switch (D) {
+    case 32: return launch_bwd<T, 32>(aq, ak, causal != 0, s);
+    case 64: return launch_bwd<T, 64>(aq, ak, causal != 0, s);
+    case 96: return launch_bwd<T, 96>(aq, ak, causal != 0, s);
+    default: return launch_bwd<T, 128>(aq, ak, causal != 0, s);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mi_block_attention_workspace_bytes(int32_t batch, int32_t Sq) {
+  return batch > 0 && Sq > 0 ? (size_t)batch * (size_t)Sq * sizeof(float) : 0;
+}
+
+#define MI_BLOCK_FWD_ARGS                                                                                                    \
+  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk, int32_t D,  \
+      int32_t causal, const uint16_t *q, int64_t ldq, int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t strideK,      \
+      const uint16_t *v, int64_t ldv, int64_t strideV, float scale, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, \
+      mi_stream_t stream
+#define MI_BLOCK_FWD_PASS \
+  rowptr, col, nnz, layouts, batch, Sq, Sk, D, causal, q, ldq, strideQ, k, ldk, strideK, v, ldv, strideV, scale, out, ldo, strideO, lse
+
+int mi_block_attention_fwd_bf16(MI_BLOCK_FWD_ARGS) { return forward_entry<Bf16>(MI_BLOCK_FWD_PASS, static_cast<hipStream_t>(stream)); }
+int mi_block_attention_fwd_f16(MI_BLOCK_FWD_ARGS) { return forward_entry<F16>(MI_BLOCK_FWD_PASS, static_cast<hipStream_t>(stream)); }
+
+#define MI_BLOCK_BWD_ARGS                                                                                                      \
+  const int32_t *rowptr, const int32_t *col, const int32_t *t_rowptr, const int32_t *t_col, int64_t nnz, int32_t layouts,       \
+      int32_t batch, int32_t Sq, int32_t Sk, int32_t D, int32_t causal, const uint16_t *q, int64_t ldq, int64_t strideQ,       \
+      const uint16_t *k, int64_t ldk, int64_t strideK, const uint16_t *v, int64_t ldv, int64_t strideV, const uint16_t *out,   \
+      int64_t ldo, int64_t strideO, const uint16_t *dout, int64_t lddo, int64_t strideDO, const float *lse, float scale,       \
+      uint16_t *dq, int64_t lddq, int64_t strideDQ, uint16_t *dk, int64_t lddk, int64_t strideDK, uint16_t *dv, int64_t lddv, \
+      int64_t strideDV, void *workspace, size_t workspace_bytes, mi_stream_t stream
+#define MI_BLOCK_BWD_PASS                                                                                                       \
+  rowptr, col, t_rowptr, t_col, nnz, layouts, batch, Sq, Sk, D, causal, q, ldq, strideQ, k, ldk, strideK, v, ldv, strideV, out, \
+      ldo, strideO, dout, lddo, strideDO, lse, scale, dq, lddq, strideDQ, dk, lddk, strideDK, dv, lddv, strideDV, workspace,    \
+      workspace_bytes
+
+int mi_block_attention_bwd_bf16(MI_BLOCK_BWD_ARGS) { return backward_entry<Bf16>(MI_BLOCK_BWD_PASS, static_cast<hipStream_t>(stream)); }
+int mi_block_attention_bwd_f16(MI_BLOCK_BWD_ARGS) { return backward_entry<F16>(MI_BLOCK_BWD_PASS, static_cast<hipStream_t>(stream)); }
+
+}  // extern "C"

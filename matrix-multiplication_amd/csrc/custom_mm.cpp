@@ -48,6 +48,7 @@ namespace {
 #include "custom_mm_reduce.inc"
 #include "custom_mm_softmax.inc"
 #include "custom_mm_attention.inc"
+#include "custom_mm_block_attention.inc"
 
 // ---- handle init / destroy (reference custom_mm.cpp:361-391) ----------------
 // There are no vendor handles on this path; init checks that the C-ABI library
@@ -179,6 +180,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out = softmax(scale * q k^T on the pattern) v in one launch");
   m.def("sparse_attention_bwd", &sparse_attention_bwd,
         "(offsets, columns, nnz, batch, rows, cols, q, k, v, dout, stats, scale, dq, y, ds): dq, and y, ds [nnz] in CSR order");
+  m.def("block_attention_forward", &block_attention_forward,
+        "(offsets [layouts, Sq/64+1], columns, nnz, q, k, v, scale, causal, out, lse [batch, Sq]): "
+        "out = softmax(scale * q k^T + block mask) v on the matrix cores, bfloat16 / float16");
+  m.def("block_attention_backward", &block_attention_backward,
+        "(offsets, columns, t_offsets, t_columns, nnz, q, k, v, out, dout, lse, scale, causal, dq, dk, dv): (dq, dk, dv)");
   // Handles and automatic schedules own HIP streams and events: they are released while the interpreter — and with it the HIP
   // runtime — is still up (left to the destructors of the statics they segfaulted at process exit after the runtime had gone:
   // a program that never called cusparse_clean / auto_schedule_clear ended with exit code 139 AFTER its last line of output).

@@ -1500,3 +1500,206 @@ def fused_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pa
     if torch.Tensor.values(pattern).numel() >= 2 ** 31:
         raise ValueError('fused_sparse_attention: nnz does not fit int32 indices')
     return fusedSparseAttention.apply(q, k, v, pattern, scale)
+
+
+# --------------------------------------------------------------------------- #
+# block-sparse attention on the matrix cores
+# --------------------------------------------------------------------------- #
+
+_BLOCK_TILE = 64                     # keys (and queries) of the kernels' tile
+_BLOCK_HEAD_SIZES = (32, 64, 96, 128)
+_BLOCK_SIZES_TEXT = ('bfloat16 or float16 operands, head size D in {32, 64, 96, 128}, block a multiple of 64, '
+                     'Sq and Sk multiples of block')
+
+
+def block_attention_takes(dtype, D: int, block: int) -> bool:
+    '''Whether block_sparse_attention takes head size D and block size `block` in `dtype` — a function of (dtype, D, block)
+    alone: bfloat16 / float16, D ∈ {32, 64, 96, 128}, block a positive multiple of 64.  Anything else raises there.'''
+    return dtype in _LOWP and D in _BLOCK_HEAD_SIZES and isinstance(block, int) and not isinstance(block, bool) and \
+        block > 0 and block % _BLOCK_TILE == 0
+
+
+def _expand_block_layout(crow: torch.Tensor, col: torch.Tensor, f: int):
+    '''A block layout in blocks of f·64 as one in 64-blocks, in sub-block order: crow [L, nb + 1] (layout-local) and col
+    [L, n] become crow' [L, nb·f + 1] and col' [L, n·f²]; sub-row a of block row I lists, for the entries c of row I in
+    their order, the columns c·f, c·f + 1, …, c·f + f − 1.  torch ops on the tensors' device, nothing read back.'''
+    crow, col = crow.to(torch.int64), col.to(torch.int64)
+    if f == 1:
+        return crow, col
+    L, nb, n = crow.shape[0], crow.shape[1] - 1, col.shape[1]
+    dev = crow.device
+    cnt = crow[:, 1:] - crow[:, :-1]
+    new_crow = torch.zeros((L, nb * f + 1), dtype=torch.int64, device=dev)
+    new_crow[:, 1:] = (cnt.repeat_interleave(f, dim=1) * f).cumsum(1)
+    new_col = torch.zeros((L, n * f * f), dtype=torch.int64, device=dev)
+    if n == 0 or nb == 0:
+        return new_crow, new_col
+    idx = torch.arange(n, device=dev).expand(L, n)
+    row = torch.searchsorted(crow[:, 1:].contiguous(), idx.contiguous(), right=True).clamp_(max=nb - 1)  # the row of every entry
+    start, rcnt = torch.gather(crow, 1, row), torch.gather(cnt, 1, row)
+    sub = torch.arange(f, device=dev)
+    a, b = sub.view(1, 1, f, 1), sub.view(1, 1, 1, f)
+    pos = (f * f * start + (idx - start) * f)[..., None, None] + a * (rcnt * f)[..., None, None] + b
+    val = ((col * f)[..., None, None] + b).expand(L, n, f, f)
+    new_col.scatter_(1, pos.reshape(L, -1).clamp_(0, n * f * f - 1), val.reshape(L, -1))
+    return new_crow, new_col
+
+
+def _block_layout(layout: torch.Tensor, dev, f: int, st: _CsrState):
+    '''What the block attention kernels read of a layout, kept in its _CsrState per (device, f) for as long as the pattern
+    stays: {'fwd': (offsets int32 [L, Sq/64 + 1] with the layouts' bases, columns int32 [L·n], nnz, L), 't': None or the
+    transposed lists (_block_layout_transposed)} — the layout expanded by f into 64-blocks and narrowed, once.'''
+    pat = st.key[1:3] + st.key[4:]
+    kept = getattr(st, 'block_layouts', None)
+    if kept is None or kept[0] != pat:
+        kept = (pat, {})
+        st.block_layouts = kept
+    rec = kept[1].get((str(dev), f))
+    if rec is None:
+        nb = layout.shape[-2]
+        crow = torch.Tensor.crow_indices(layout).reshape(-1, nb + 1).to(dev)
+        col = torch.Tensor.col_indices(layout).reshape(crow.shape[0], -1).to(dev)
+        crow, col = _expand_block_layout(crow, col, f)
+        L, n = col.shape
+        base = torch.arange(L, device=crow.device, dtype=torch.int64).unsqueeze(1) * n
+        rec = {'fwd': ((crow + base).to(torch.int32).contiguous(), col.reshape(-1).to(torch.int32).contiguous(), L * n, L),
+               't': None}
+        kept[1][(str(dev), f)] = rec
+    return rec
+
+
+def _block_layout_transposed(rec: dict, rows: int, cols: int):
+    '''(t_offsets int32 [L, cols + 1] with the layouts' bases, t_columns int32 [L·n]) of a _block_layout record with
+    rows × cols 64-blocks: key block → the query blocks that see it, by the device transposes (csr_transpose /
+    csr_transpose_batched on the block-level pattern), each list then put in ascending order — the order dk and dv are
+    summed in is a property of the layout, not of the transpose plan.  Kept in the record: a static layout pays once.'''
+    if rec['t'] is None:
+        offsets, columns, nnz, L = rec['fwd']
+        dev = offsets.device
+        if nnz == 0:
+            rec['t'] = (torch.zeros((L, cols + 1), dtype=torch.int32, device=dev), columns)
+            return rec['t']
+        n = nnz // L
+        zeros = torch.zeros(nnz, device=dev, dtype=torch.float32)  # (the transposes carry values; a layout has none)
+        if L == 1:
+            _, t_col, t_off = custom_mm.csr_transpose(zeros, columns, offsets.reshape(-1), nnz, rows, cols)
+            t_off = t_off.reshape(1, cols + 1)
+        else:
+            parts = []
+            for lo, hi in _item_chunks(L):
+                _, tc, to = _transpose_items(zeros, columns, offsets, n, lo, hi, rows, cols)
+                parts.append((tc, to if lo == 0 else to + lo * n))
+            t_col, t_off = parts[0] if len(parts) == 1 else (torch.cat(x) for x in zip(*parts))
+        t_off = t_off.to(device=dev, dtype=torch.int32).reshape(L, cols + 1).contiguous()
+        t_col = t_col.to(device=dev, dtype=torch.int64).reshape(L, n)
+        local = t_off.to(torch.int64) - torch.arange(L, device=dev, dtype=torch.int64).unsqueeze(1) * n
+        idx = torch.arange(n, device=dev).expand(L, n).contiguous()
+        row = torch.searchsorted(local[:, 1:].contiguous(), idx, right=True)
+        t_col = (row * rows + t_col).sort(dim=1).values % rows
+        rec['t'] = (t_off, t_col.reshape(-1).to(torch.int32).contiguous())
+    return rec['t']
+
+
+class blockSparseAttention(InplaceFunction):
+    '''softmax(scale · q·kᵀ + block mask) · v on the matrix cores (custom_mm.block_attention_forward), saving q, k, v, the
+    layout, out and ONE float per query row (the log-sum-exp) — nothing of size Sq × Sk, nothing per kept block.  Backward:
+    custom_mm.block_attention_backward recomputes P per tile; dq over the layout, dk and dv per key block over the
+    transposed layout kept in the layout tensor's _CsrState.  No atomics, no read-back.'''
+
+    @staticmethod
+    def forward(ctx, q, k, v, layout, f, scale, causal):
+        rec = _block_layout(layout, q.device, f, _csr_state(layout))
+        offsets, columns, nnz, _ = rec['fwd']
+        Sq, Sk, D = q.shape[-2], k.shape[-2], q.shape[-1]
+        q3, k3, v3 = q.reshape(-1, Sq, D).contiguous(), k.reshape(-1, Sk, D).contiguous(), v.reshape(-1, Sk, D).contiguous()
+        out = torch.empty_like(q3)
+        lse = torch.empty((q3.shape[0], Sq), device=q.device, dtype=torch.float32)
+        if out.numel() > 0:
+            custom_mm.block_attention_forward(offsets, columns, nnz, q3, k3, v3, float(scale), bool(causal), out, lse)
+        ctx.block_args = (f, float(scale), bool(causal))
+        ctx.save_for_backward(q, k, v, layout, out, lse)
+        return out.reshape(q.shape)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        q, k, v, layout, out, lse = ctx.saved_tensors
+        f, scale, causal = ctx.block_args
+        Sq, Sk, D = q.shape[-2], k.shape[-2], q.shape[-1]
+        q3, k3, v3 = q.reshape(-1, Sq, D).contiguous(), k.reshape(-1, Sk, D).contiguous(), v.reshape(-1, Sk, D).contiguous()
+        if out.numel() == 0:
+            dq, dk, dv = torch.zeros_like(q3), torch.zeros_like(k3), torch.zeros_like(v3)
+        else:
+            rec = _block_layout(layout, q.device, f, _csr_state(layout))
+            offsets, columns, nnz, _ = rec['fwd']
+            t_off, t_col = _block_layout_transposed(rec, Sq // _BLOCK_TILE, Sk // _BLOCK_TILE)
+            g3 = grad_output.to(q.dtype).reshape(-1, Sq, D).contiguous()
+            dq, dk, dv = torch.empty_like(q3), torch.empty_like(k3), torch.empty_like(v3)
+            custom_mm.block_attention_backward(offsets, columns, t_off, t_col, nnz, q3, k3, v3, out, g3, lse, scale, causal,
+                                               dq, dk, dv)
+        need = ctx.needs_input_grad
+        return (dq.reshape(q.shape) if need[0] else None, dk.reshape(k.shape) if need[1] else None,
+                dv.reshape(v.shape) if need[2] else None, None, None, None, None)
+
+
+def _check_block_attention_operands(what, q, k, v, layout, block, causal):
+    '''Every refusal of block_sparse_attention, before the first device call: ValueError for what an operand is (layout,
+    dtype, sizes, shapes), RuntimeError for operands that do not go together (mixed dtypes, host tensors / devices).'''
+    _check_csr(what, 'layout', layout)
+    for name, t in (('q', q), ('k', k), ('v', v)):
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be a dense tensor')
+        if t.dtype not in _VALUE_DTYPES or t.dtype == torch.float32:
+            raise ValueError(f'{what}: {name} must be bfloat16 or float16, got {t.dtype} (accepted: {_BLOCK_SIZES_TEXT})')
+    for name, t in (('k', k), ('v', v)):
+        if t.dtype != q.dtype:
+            raise RuntimeError(f'{what}: q is {q.dtype} but {name} is {t.dtype}: all operands must have one dtype '
+                               f'(bfloat16 or float16)')
+    if isinstance(block, bool) or not isinstance(block, int) or block <= 0 or block % _BLOCK_TILE != 0:
+        raise ValueError(f'{what}: block must be a positive multiple of 64, got {block!r} (accepted: {_BLOCK_SIZES_TEXT})')
+    if q.dim() < 2 or k.dim() != q.dim() or v.dim() != q.dim():
+        raise ValueError(f'{what}: q, k and v must be [..., S, D] tensors of one rank, got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
+    D = q.shape[-1]
+    if D not in _BLOCK_HEAD_SIZES:
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_BLOCK_SIZES_TEXT})')
+    lead, Sq, Sk = tuple(q.shape[:-2]), q.shape[-2], k.shape[-2]
+    if tuple(k.shape[:-2]) != lead or k.shape[-1] != D:
+        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs k {lead + ("Sk", D)}, got {tuple(k.shape)}')
+    if tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f'{what}: v must be a dense tensor with k\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
+    if Sq % block != 0 or Sk % block != 0:
+        raise ValueError(f'{what}: Sq = {Sq} and Sk = {Sk} must be multiples of block = {block}: ragged lengths are not '
+                         f'supported (accepted: {_BLOCK_SIZES_TEXT})')
+    l_lead = tuple(layout.shape[:-2])
+    if tuple(layout.shape[-2:]) != (Sq // block, Sk // block) or len(l_lead) > len(lead) or \
+            l_lead != lead[len(lead) - len(l_lead):]:
+        raise ValueError(f'{what}: the layout must have shape [*l_lead, Sq/block, Sk/block] = [*l_lead, {Sq // block}, '
+                         f'{Sk // block}] with l_lead empty or a trailing part of {lead}, got {tuple(layout.shape)}')
+    if causal and Sq != Sk:
+        raise ValueError(f'{what}: causal=True needs Sq == Sk, got {Sq} and {Sk}')
+    if torch.Tensor.values(layout).numel() * (block // _BLOCK_TILE) ** 2 >= 2 ** 31:
+        raise ValueError(f'{what}: the layout in 64-blocks does not fit int32 indices')
+    _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k=k, v=v)
+
+
+def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, block: int = 64, scale=None,
+                           causal: bool = False) -> torch.Tensor:
+    '''out = softmax(scale · q·kᵀ + mask) · v on the matrix cores, the mask given in BLOCKS: q [*lead, Sq, D], k and v
+    [*lead, Sk, D], dense device tensors, all bfloat16 or all float16; `layout` a CSR tensor [*l_lead, Sq/block, Sk/block]
+    whose stored entry (I, J) lets query block I see key block J (values ignored, any dtype; int32 or int64 indices; columns
+    of a block row in any order; a block stored twice is NOT supported — it would count twice).  l_lead is empty (one
+    layout for all) or a trailing part of lead ([H, …] against q [B, H, S, D]): item i of the flattened batch uses layout
+    i mod L; a batched layout has equal entry counts per item, as torch builds it.  scale defaults to 1/√D.  causal=True
+    (Sq == Sk) also hides j > i: kept blocks strictly above the diagonal contribute nothing.
+
+    The softmax runs over the visible positions of a row; a row that sees nothing is a zero row of out (and dq), a key
+    nobody sees a zero row of dk and dv.  Positions outside the kept blocks are never read.  Sizes: D ∈ {32, 64, 96, 128},
+    block a multiple of 64, Sq and Sk multiples of block — anything else raises (block_attention_takes).  The kernels' tile is 64
+    keys: a larger block is served by expanding the layout into 64-blocks in sub-block order on the device, and the result
+    is by definition the bits of that expanded call.  Products on the MFMA with fp32 accumulators; scores, maxima, sums and
+    the log-sum-exp in fp32; one rounding at the store.  Autograd keeps q, k, v, out and one float per query row, and
+    recomputes P per tile; no atomics, no read-back; the bits of an output depend on its own item and layout only.
+    Differentiable in q, k and v.'''
+    _check_block_attention_operands('block_sparse_attention', q, k, v, layout, block, causal)
+    if scale is None:
+        scale = 1.0 / float(q.shape[-1]) ** 0.5
+    return blockSparseAttention.apply(q, k, v, layout, block // _BLOCK_TILE, float(scale), bool(causal))
