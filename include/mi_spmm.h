@@ -981,6 +981,57 @@ int mi_block_attention_bwd_f16(const int32_t* rowptr, const int32_t* col, const 
                                int64_t strideDQ, uint16_t* dk, int64_t lddk, int64_t strideDK, uint16_t* dv, int64_t lddv,
                                int64_t strideDV, void* workspace, size_t workspace_bytes, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in
+ * bfloat16 / float16 (T, 2-byte bit patterns) with A given as the kept 64 × 64 blocks of a CSR block list, shared by
+ * every item of the batch, and the sampled product on the same list:
+ *   rowptr   int32 [rows/64 + 1], col int32 [nnz]: for each 64-row block of C the blocks of A it sums over — col is the
+ *            64-block of the inner dimension (the 64 rows of B) the entry meets.  trans_a == 0: the block rows of A and
+ *            their block columns; trans_a != 0: the TRANSPOSED list (block columns of A and their block rows), every
+ *            block used transposed.  A duplicate block is unsupported (it would count twice);
+ *   entry_id int32 [nnz] or NULL: entry p reads (sddmm: writes) block entry_id[p] of values; NULL: block p;
+ *   values   [nvalues][64][64], row-major blocks, 16-byte aligned;
+ *   B [batch][inner][N], C [batch][rows][N]: leading dimension ≥ N and item stride in elements, any 2-byte alignment
+ *            (16-byte aligned bases with leading dimensions and strides multiples of 8 run the 16-byte form);
+ *   sddmm:   entry_row, col int32 [nnz]: block row and block column of entry p; dC [batch][M][N], B [batch][K][N];
+ *            dvalues [nvalues][64][64], 16-byte aligned: dvalues[e] = Σ over the items of dC[I-rows, :] · B[J-rows, :]ᵀ.
+ * Arithmetic (all three products): every product is v_mfma_f32_16x16x32_T with fp32 accumulators, in the k-slots of
+ * mi_gemm_T; every output element is ONE accumulator started at +0 and rounded once at the store, by the static_cast
+ * narrowing of mi_gemm_T; the bits do not depend on the launch shape, the column tile, the position in the batch or the
+ * alignment form.
+ *   C = A·B:     element (i, j) walks the entries of its block row in the order of the list (the caller gives it in
+ *                ascending block column) and, within a block, the two 32-deep k-steps ascending;
+ *   dB = Aᵀ·dC:  element (k, j) walks the transposed list of block column k/64 (ascending block row), each block used
+ *                transposed;
+ *   dvalues[e]:  the sum runs over the flattened width k' = item · N + j (item-major, items ascending) in ascending
+ *                32-steps, a ragged last step zero-padded in both operands.
+ * For finite operands and ascending lists these are, bit for bit, mi_gemm_T(A_dense, B), mi_gemm_T(transa, A_dense, dC)
+ * and the kept blocks of mi_gemm_T(transb, dC, B) on the flattened operands: the same instruction in the same order, an
+ * unkept block contributing only exact zero products to the dense run.  A block outside the list is never loaded, nor
+ * the rows of B it would meet: NaN or inf there reaches no output.  An empty list stores zeros.  A listed column outside
+ * the grid or an entry id outside [0, nvalues) is skipped (sddmm: the block is zero / not written), offsets are clamped
+ * to [0, nnz].  No atomics, no workspace, no host synchronisation: graph-capturable.
+ * Validation before any HIP call: a negative size or stride, rows / inner / M / K not a multiple of 64, ld < N,
+ * nvalues < nnz without entry ids → MI_EINVAL; nnz, nvalues or batch · N (sddmm) ≥ 2³¹ → MI_ERANGE; rows, N or batch
+ * == 0 (sddmm: nnz == 0) → MI_OK, nothing touched; a NULL, odd or (values, dvalues) not 16-byte aligned pointer → MI_EINVAL.
+ * ------------------------------------------------------------------------ */
+int mi_bsr_mm_bf16(const int32_t* rowptr, const int32_t* col, const int32_t* entry_id, int64_t nnz, int32_t trans_a,
+                   int32_t rows, int32_t inner, int32_t N, int32_t batch, const uint16_t* values, int64_t nvalues,
+                   const uint16_t* B, int64_t ldb, int64_t strideB, uint16_t* C, int64_t ldc, int64_t strideC,
+                   mi_stream_t stream);
+int mi_bsr_mm_f16(const int32_t* rowptr, const int32_t* col, const int32_t* entry_id, int64_t nnz, int32_t trans_a,
+                  int32_t rows, int32_t inner, int32_t N, int32_t batch, const uint16_t* values, int64_t nvalues,
+                  const uint16_t* B, int64_t ldb, int64_t strideB, uint16_t* C, int64_t ldc, int64_t strideC,
+                  mi_stream_t stream);
+int mi_bsr_sddmm_bf16(const int32_t* entry_row, const int32_t* col, const int32_t* entry_id, int64_t nnz, int32_t M,
+                      int32_t K, int32_t N, int32_t batch, const uint16_t* dC, int64_t lddc, int64_t strideDC,
+                      const uint16_t* B, int64_t ldb, int64_t strideB, uint16_t* dvalues, int64_t nvalues,
+                      mi_stream_t stream);
+int mi_bsr_sddmm_f16(const int32_t* entry_row, const int32_t* col, const int32_t* entry_id, int64_t nnz, int32_t M,
+                     int32_t K, int32_t N, int32_t batch, const uint16_t* dC, int64_t lddc, int64_t strideDC,
+                     const uint16_t* B, int64_t ldb, int64_t strideB, uint16_t* dvalues, int64_t nvalues,
+                     mi_stream_t stream);
+
 int mi_ipc_export(const void* dev_ptr, void* handle_out, int64_t* offset_out, int64_t* alloc_bytes_out);
 int mi_ipc_open(const void* handle, void** base_out);
 int mi_ipc_close(const void* handle);

@@ -49,6 +49,7 @@ namespace {
 #include "custom_mm_softmax.inc"
 #include "custom_mm_attention.inc"
 #include "custom_mm_block_attention.inc"
+#include "custom_mm_bsr.inc"
 
 // ---- handle init / destroy (reference custom_mm.cpp:361-391) ----------------
 // There are no vendor handles on this path; init checks that the C-ABI library
@@ -185,6 +186,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out = softmax(scale * q k^T + block mask) v on the matrix cores, bfloat16 / float16");
   m.def("block_attention_backward", &block_attention_backward,
         "(offsets, columns, t_offsets, t_columns, nnz, q, k, v, out, dout, lse, scale, causal, dq, dk, dv): (dq, dk, dv)");
+  m.def("bsr_mm", &bsr_mm,
+        "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
+        "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");
+  m.def("bsr_sddmm", &bsr_sddmm,
+        "(entry_row, columns, entry_ids or None, nnz, dC [batch, M, N], B [batch, K, N], dvalues [n, 64, 64]): "
+        "dvalues[e] = sum over the items of dC[I-rows] B[J-rows]^T on the kept blocks");
   // Handles and automatic schedules own HIP streams and events: they are released while the interpreter — and with it the HIP
   // runtime — is still up (left to the destructors of the statics they segfaulted at process exit after the runtime had gone:
   // a program that never called cusparse_clean / auto_schedule_clear ended with exit code 139 AFTER its last line of output).

@@ -23,6 +23,7 @@ math = `torch.matmul` and its autograd (SURVEY.md §8a "known defects"):
     Python recursion with one to_sparse_csr() per slice (reference :289-297).
 '''
 
+import math
 import os
 import weakref
 
@@ -1703,3 +1704,189 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, la
     if scale is None:
         scale = 1.0 / float(q.shape[-1]) ** 0.5
     return blockSparseAttention.apply(q, k, v, layout, block // _BLOCK_TILE, float(scale), bool(causal))
+
+
+# --------------------------------------------------------------------------- #
+# block-sparse (BSR) × dense products on the matrix cores
+# --------------------------------------------------------------------------- #
+
+_BSR_SIZES_TEXT = 'bfloat16 or float16 operands, block = 64, M and K multiples of 64'
+
+
+def block_mm_takes(dtype, block) -> bool:
+    '''Whether block_sparse_mm takes blocks of `block` × `block` in `dtype` — a function of (dtype, block) alone: bfloat16 /
+    float16 and block == 64.  Anything else raises there.'''
+    return dtype in _LOWP and isinstance(block, int) and not isinstance(block, bool) and block == _BLOCK_TILE
+
+
+def _sorted_lists(offsets: torch.Tensor, columns: torch.Tensor, ids: torch.Tensor, rows: int, cols: int):
+    '''A CSR list (offsets int64 [rows + 1], columns int64 [n], column < cols) with every row's columns in ascending order:
+    (sorted columns int32, ids carried along int32, row of every entry int32).  torch ops on the device, nothing read back.'''
+    n = columns.numel()
+    idx = torch.arange(n, device=columns.device)
+    row = torch.searchsorted(offsets[1:].contiguous(), idx, right=True).clamp_(max=max(rows - 1, 0))  # the row of every entry
+    key, order = (row * cols + columns).sort()
+    return (key % cols).to(torch.int32).contiguous(), ids[order].to(torch.int32).contiguous(), row.to(torch.int32).contiguous()
+
+
+def _bsr_layout(layout: torch.Tensor, dev, st: _CsrState):
+    '''What the block product kernels read of a 2-d layout [M/64, K/64], kept in its _CsrState per device for as long as
+    the pattern stays: {'fwd': (offsets int32 [M/64 + 1], columns int32 [n] ascending within a block row, entry ids int32
+    [n] — sorted position → stored entry, entry_row int32 [n], n), 't': None or the transposed lists
+    (_bsr_layout_transposed)} — narrowed and sorted once.'''
+    pat = st.key[1:3] + st.key[4:]
+    kept = getattr(st, 'bsr_layouts', None)
+    if kept is None or kept[0] != pat:
+        kept = (pat, {})
+        st.bsr_layouts = kept
+    rec = kept[1].get(str(dev))
+    if rec is None:
+        rows, cols = layout.shape
+        crow = torch.Tensor.crow_indices(layout).to(dev).to(torch.int64)
+        col = torch.Tensor.col_indices(layout).to(dev).to(torch.int64)
+        n = col.numel()
+        columns, ids, entry_row = _sorted_lists(crow, col, torch.arange(n, device=col.device), rows, cols)
+        rec = {'fwd': (crow.to(torch.int32).contiguous(), columns, ids, entry_row, n), 't': None}
+        kept[1][str(dev)] = rec
+    return rec
+
+
+def _bsr_layout_transposed(rec: dict, rows: int, cols: int):
+    '''(t_offsets int32 [cols + 1], t_columns int32 [n], t_ids int32 [n]) of a _bsr_layout record with rows × cols blocks:
+    block column → the block rows that keep it, by the device transpose of an iota (as _transposed_pattern), each list then
+    put in ascending block row with the stored entry ids carried along — the order d b is summed in is a property of the
+    layout, not of the transpose plan.  Kept in the record: a static weight pays once.'''
+    if rec['t'] is None:
+        offsets, columns, ids, _, n = rec['fwd']
+        dev = offsets.device
+        if n == 0:
+            rec['t'] = (torch.zeros(cols + 1, dtype=torch.int32, device=dev), columns, ids)
+            return rec['t']
+        iota = torch.arange(n, device=dev, dtype=torch.int32).view(torch.float32)
+        t_perm, t_col, t_off = custom_mm.csr_transpose(iota, columns, offsets, n, rows, cols)
+        t_ids = ids.to(torch.int64)[t_perm.view(torch.int32).to(torch.int64)]
+        t_columns, t_ids, _ = _sorted_lists(t_off.to(device=dev, dtype=torch.int64), t_col.to(device=dev, dtype=torch.int64),
+                                            t_ids, cols, rows)
+        rec['t'] = (t_off.to(device=dev, dtype=torch.int32).contiguous(), t_columns, t_ids)
+    return rec['t']
+
+
+class blockSparseMM(InplaceFunction):
+    '''out = A·b with A the 64 × 64 blocks `values` on the block list of `layout` (custom_mm.bsr_mm), saving values, the
+    layout and b — nothing of size M × K.  Backward: d values on the pattern by custom_mm.bsr_sddmm (summed over the items),
+    d b = Aᵀ·dC by custom_mm.bsr_mm over the transposed lists kept in the layout tensor's _CsrState.  No atomics, no
+    workspace, no read-back.'''
+
+    @staticmethod
+    def forward(ctx, values, layout, b):
+        rec = _bsr_layout(layout, b.device, _csr_state(layout))
+        offsets, columns, ids, _, n = rec['fwd']
+        M, K, N = layout.shape[0] * _BLOCK_TILE, b.shape[-2], b.shape[-1]
+        b3 = b.reshape(math.prod(b.shape[:-2]), K, N)
+        if n == 0 or b3.numel() == 0:
+            out = torch.zeros((b3.shape[0], M, N), device=b.device, dtype=b.dtype)
+        else:
+            out = torch.empty((b3.shape[0], M, N), device=b.device, dtype=b.dtype)
+            custom_mm.bsr_mm(offsets, columns, ids, n, values, b3, out, False)
+        ctx.save_for_backward(values, layout, b)
+        return out.reshape(b.shape[:-2] + (M, N))
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        values, layout, b = ctx.saved_tensors
+        M, K, N = layout.shape[0] * _BLOCK_TILE, b.shape[-2], b.shape[-1]
+        b3 = b.reshape(math.prod(b.shape[:-2]), K, N)
+        need = ctx.needs_input_grad
+        dvalues = db = None
+        rec = _bsr_layout(layout, b.device, _csr_state(layout))
+        offsets, columns, ids, entry_row, n = rec['fwd']
+        empty = n == 0 or b3.numel() == 0
+        g3 = grad_output.to(b.dtype).reshape(b3.shape[0], M, N)
+        if need[2] and not empty:
+            # first, before any gradient is allocated: the one-off device transpose brings its own fixed workspace (2 MiB)
+            t_off, t_col, t_ids = _bsr_layout_transposed(rec, M // _BLOCK_TILE, K // _BLOCK_TILE)
+        if need[0]:
+            if empty:
+                dvalues = torch.zeros_like(values)
+            else:
+                dvalues = torch.empty_like(values)
+                custom_mm.bsr_sddmm(entry_row, columns, ids, n, g3, b3, dvalues)
+        if need[2]:
+            if empty:
+                db = torch.zeros(b.shape, device=b.device, dtype=b.dtype)
+            else:
+                db = torch.empty((b3.shape[0], K, N), device=b.device, dtype=b.dtype)
+                custom_mm.bsr_mm(t_off, t_col, t_ids, n, values, g3, db, True)
+                db = db.reshape(b.shape)
+        return dvalues, None, db
+
+
+def _check_block_mm_operands(what, values, layout, b, block):
+    '''Every refusal of block_sparse_mm, before the first device call: ValueError for what an operand is (layout, dtype,
+    block, shapes), RuntimeError for operands that do not go together (mixed dtypes, host tensors / devices).'''
+    _check_csr(what, 'layout', layout)
+    if layout.dim() != 2:
+        raise ValueError(f'{what}: the layout must be a 2-d CSR tensor [M/64, K/64], got {layout.dim()}-d: A is shared by '
+                         f'every item of the batch, a batched layout is not supported')
+    for name, t in (('values', values), ('b', b)):
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be a dense tensor')
+        if t.dtype not in _LOWP:
+            raise ValueError(f'{what}: {name} must be bfloat16 or float16, got {t.dtype} (accepted: {_BSR_SIZES_TEXT})')
+    if b.dtype != values.dtype:
+        raise RuntimeError(f'{what}: values is {values.dtype} but b is {b.dtype}: all operands must have one dtype '
+                           f'(bfloat16 or float16)')
+    if isinstance(block, bool) or not isinstance(block, int) or block != _BLOCK_TILE:
+        raise ValueError(f'{what}: block must be 64, got {block!r} (accepted: {_BSR_SIZES_TEXT})')
+    n = torch.Tensor.values(layout).numel()
+    if values.dim() != 3 or tuple(values.shape[1:]) != (block, block):
+        raise ValueError(f'{what}: values must be [n, {block}, {block}], got {tuple(values.shape)}')
+    if values.shape[0] != n:
+        raise ValueError(f'{what}: values holds {values.shape[0]} blocks but the layout stores {n} entries')
+    if not values.is_contiguous():
+        raise ValueError(f'{what}: values must be contiguous')
+    if b.dim() < 2:
+        raise ValueError(f'{what}: b must be a [..., K, N] tensor, got {b.dim()}-d')
+    K = b.shape[-2]
+    if K % block != 0 or K // block != layout.shape[1]:
+        raise ValueError(f'{what}: b of shape {tuple(b.shape)} has K = {K} rows, the layout {tuple(layout.shape)} needs '
+                         f'K = {layout.shape[1]} · {block} = {layout.shape[1] * block}: M and K must be multiples of block, '
+                         f'ragged sizes are not supported (accepted: {_BSR_SIZES_TEXT})')
+    if n >= 2 ** 31:
+        raise ValueError(f'{what}: the layout does not fit int32 indices')
+    _check_on_device(what, layout=torch.Tensor.values(layout), values=values, b=b)
+
+
+def block_sparse_mm(values: torch.Tensor, layout: torch.Tensor, b: torch.Tensor, block: int = 64) -> torch.Tensor:
+    '''out = A·b on the matrix cores with A [M, K] given in BLOCKS: `layout` a 2-d CSR tensor [M/64, K/64] whose stored
+    entry (I, J) keeps block (I, J) of A (values ignored, any dtype; int32 or int64 indices; columns of a block row in any
+    order; a block stored twice is NOT supported — it would count twice); `values` [n, 64, 64] contiguous, values[e] the
+    row-major block of the e-th stored entry — the values() of a torch.sparse_bsr tensor (bsr_parts); b [*lead, K, N] dense,
+    any N ≥ 1; all bfloat16 or all float16, device tensors.  out is [*lead, M, N]; A is shared by every item of the batch.
+
+    Products on the MFMA with fp32 accumulators, one accumulator per output element, one rounding at the store; a block
+    row walks its kept blocks in ascending block column whatever the order of the layout, so for finite operands the result
+    is, bit for bit, cublas_mmul(A_dense, b) of this package — but a block outside the layout is never read: NaN or inf in
+    the rows of b that only unkept blocks meet reach nothing.  A block row that keeps nothing is a zero row block.
+    Differentiable in values (a dense [n, 64, 64] gradient, sampled on the pattern and summed over the batch) and in b
+    (Aᵀ·dC over the transposed lists, built once per layout tensor); the same bits as cublas_mmul(dC, b, transb=True) on the
+    kept blocks and cublas_mmul(A_dense, dC, transa=True).  No atomics, no workspace, no read-back.  float32, other block
+    sizes, a batched layout and ragged M or K raise (block_mm_takes).'''
+    _check_block_mm_operands('block_sparse_mm', values, layout, b, block)
+    return blockSparseMM.apply(values, layout, b)
+
+
+def bsr_parts(a: torch.Tensor):
+    '''(values, layout) of a 2-d torch.sparse_bsr tensor with 64 × 64 blocks, as block_sparse_mm takes them: its values()
+    [n, 64, 64] and a CSR layout tensor [M/64, K/64] on its own crow_indices() / col_indices() — no copy of the blocks or
+    the indices, nothing read back.  Keep the layout tensor: the sorted and transposed lists live on it.'''
+    if not isinstance(a, torch.Tensor) or a.layout != torch.sparse_bsr:
+        raise ValueError('bsr_parts: a must be a torch.sparse_bsr tensor')
+    values = torch.Tensor.values(a)
+    if a.dim() != 2 or tuple(values.shape[-2:]) != (_BLOCK_TILE, _BLOCK_TILE):
+        raise ValueError(f'bsr_parts: a must be a 2-d BSR tensor with 64 × 64 blocks, got {a.dim()}-d with blocks '
+                         f'{tuple(values.shape[-2:])}')
+    crow, col = torch.Tensor.crow_indices(a), torch.Tensor.col_indices(a)
+    marks = torch.ones(col.shape[0], dtype=torch.float32, device=col.device)  # (a CSR tensor carries values; ignored)
+    layout = torch.sparse_csr_tensor(crow, col, marks, size=(a.shape[0] // _BLOCK_TILE, a.shape[1] // _BLOCK_TILE))
+    return values, layout
