@@ -1032,6 +1032,67 @@ int mi_bsr_sddmm_f16(const int32_t* entry_row, const int32_t* col, const int32_t
                      const uint16_t* B, int64_t ldb, int64_t strideB, uint16_t* dvalues, int64_t nvalues,
                      mi_stream_t stream);
 
+/* ------------------------------------------------------------------------ *
+ * Block-sparse linear layer on the matrix cores — NEW relative to the reference: Y = X·Wᵀ (+ bias) in bfloat16 / float16
+ * (T, 2-byte bit patterns) with the weight W [outer-of-the-forward = out, in] given as its kept 64 × 64 blocks, the tokens
+ * X [tokens, in] row-major; dX = dY·W on the same kernel; the weight gradient on the kept blocks.
+ *
+ * mi_bsr_linear_T:  Y[t, 64·P + c] = Σ over the entries p of list row P, in list order, Σ_k X[t, 64·col[p] + k] · Wblk(c, k)
+ *   rowptr   int32 [outer/64 + 1], col int32 [nnz]: for each 64-column block P of Y the 64-column blocks of X it sums over;
+ *   entry_id int32 [nnz] or NULL: entry p reads block entry_id[p] of values; NULL: block p;
+ *   trans_w == 0 (the forward): P a block row of W, the list its kept block columns, Wblk(c, k) = values[e][c][k];
+ *   trans_w != 0 (dX = dY·W):   P a block column of W, the list the block rows that keep it (the TRANSPOSED list),
+ *                               Wblk(c, k) = values[e][k][c]; X is dY;
+ *   values   [nvalues][64][64], row-major blocks of W, 16-byte aligned;
+ *   X [tokens][inner], Y [tokens][outer]: leading dimensions ldx ≥ inner, ldy ≥ outer in elements, any 2-byte alignment
+ *            (16-byte aligned bases with leading dimensions multiples of 8 run the 16-byte form); any tokens ≥ 0;
+ *   bias     [outer] or NULL, any 2-byte alignment: Y = rne_T(acc + up(bias[64·P + c])) — one fp32 add of the exactly
+ *            widened bias, one rounding (the epilogue of mi_gemm_bias_T).
+ * mi_bsr_wgrad_T:   dvalues[entry_id[p]][o][i] = Σ_t dY[t, 64·entry_row[p] + o] · X[t, 64·col[p] + i]
+ *   entry_row, col int32 [nnz]: block row (of `out`) and block column (of `in`) of entry p; entry_id as above (written);
+ *   dY [tokens][out], X [tokens][in] with lddy ≥ out, ldx ≥ in; dvalues [nvalues][64][64], 16-byte aligned;
+ *   splits   the number S of equal token ranges (0: mi_bsr_wgrad_split_count(nnz, tokens)); S > 1 needs
+ *            tokens % (32·S) == 0 and a 16-byte aligned workspace of mi_bsr_wgrad_workspace_bytes(nnz, S) =
+ *            S·nnz·64·64·4 bytes (smaller: MI_ENOMEM — never a silent unsplit product).
+ * mi_bsr_wgrad_split_count(nnz, tokens) is a function of those two numbers alone: 1 below 2048 tokens, else the largest
+ *   power of two ≤ min(1024 / nnz, tokens / 512, 32) (at least 1), halved until tokens % (32·S) == 0.
+ *
+ * Arithmetic: every product is v_mfma_f32_16x16x32_T with fp32 accumulators in the k-slots of mi_gemm_T; every output
+ * element is ONE accumulator started at +0, carried through its list in the order given (the caller gives it ascending)
+ * and, within a block, through the two 32-deep k-steps ascending, and rounded once at the store (static_cast narrowing).
+ * The bits do not depend on the token tile, the workgroup numbering, the position of a token, the alignment form or the
+ * order of the layout the lists were sorted from.  The weight gradient sums the tokens of a range in ascending 32-steps
+ * from +0, a ragged last step zero-padded in both operands; with S > 1 range s goes to an fp32 partial P[s][p][64][64],
+ * not narrowed, and a combine kernel stores rne_T((((P[0] + P[1]) + P[2]) + …)) with fp32 adds in index order.
+ * For finite operands and ascending lists these are, bit for bit, mi_gemm_bias_T / mi_gemm_T(transb, X, W_dense),
+ * mi_gemm_T(dY, W_dense) and the kept blocks of mi_gemm_split_T(transa, dY, X, splits = S) (S = 1: mi_gemm_T(transa)):
+ * the same instruction in the same order, an unkept block contributing only exact zero products to the dense run.
+ * A block outside the list is never loaded, nor the columns of X (of dY) it would meet: NaN or inf there reaches no
+ * output.  An empty list row stores +0, or the bias.  A listed column outside the grid or an entry id outside
+ * [0, nvalues) is skipped (wgrad: the block is zero / not written), offsets are clamped to [0, nnz].  No float atomics,
+ * no host synchronisation: graph-capturable.
+ * Validation before any HIP call: a negative size, inner / outer / out / in not a multiple of 64, ld below the width,
+ * nvalues < nnz without entry ids, splits < 0 or tokens not a multiple of 32·splits → MI_EINVAL; nnz, nvalues or a
+ * leading dimension ≥ 2³¹ → MI_ERANGE; tokens or outer == 0 (wgrad: nnz == 0) → MI_OK, nothing touched; a NULL or odd
+ * pointer, values / dvalues / workspace not 16-byte aligned → MI_EINVAL; a workspace too small → MI_ENOMEM.
+ * ------------------------------------------------------------------------ */
+int mi_bsr_linear_bf16(const int32_t* rowptr, const int32_t* col, const int32_t* entry_id, int64_t nnz, int32_t trans_w,
+                       int32_t tokens, int32_t inner, int32_t outer, const uint16_t* values, int64_t nvalues,
+                       const uint16_t* X, int64_t ldx, const uint16_t* bias, uint16_t* Y, int64_t ldy, mi_stream_t stream);
+int mi_bsr_linear_f16(const int32_t* rowptr, const int32_t* col, const int32_t* entry_id, int64_t nnz, int32_t trans_w,
+                      int32_t tokens, int32_t inner, int32_t outer, const uint16_t* values, int64_t nvalues,
+                      const uint16_t* X, int64_t ldx, const uint16_t* bias, uint16_t* Y, int64_t ldy, mi_stream_t stream);
+int mi_bsr_wgrad_bf16(const int32_t* entry_row, const int32_t* col, const int32_t* entry_id, int64_t nnz, int32_t tokens,
+                      int32_t out, int32_t in, const uint16_t* dY, int64_t lddy, const uint16_t* X, int64_t ldx,
+                      uint16_t* dvalues, int64_t nvalues, int32_t splits, void* workspace, size_t workspace_bytes,
+                      mi_stream_t stream);
+int mi_bsr_wgrad_f16(const int32_t* entry_row, const int32_t* col, const int32_t* entry_id, int64_t nnz, int32_t tokens,
+                     int32_t out, int32_t in, const uint16_t* dY, int64_t lddy, const uint16_t* X, int64_t ldx,
+                     uint16_t* dvalues, int64_t nvalues, int32_t splits, void* workspace, size_t workspace_bytes,
+                     mi_stream_t stream);
+int mi_bsr_wgrad_split_count(int64_t nnz, int64_t tokens);
+size_t mi_bsr_wgrad_workspace_bytes(int64_t nnz, int32_t splits);
+
 int mi_ipc_export(const void* dev_ptr, void* handle_out, int64_t* offset_out, int64_t* alloc_bytes_out);
 int mi_ipc_open(const void* handle, void** base_out);
 int mi_ipc_close(const void* handle);

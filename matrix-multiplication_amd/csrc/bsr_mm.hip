@@ -33,26 +33,9 @@
 // No atomics, no workspace, no host read-back: graph-capturable.
 #include <type_traits>
 
-#include "lowp_device.h"
+#include "bsr_device.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <class T>
-__device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma<Bf16>(uint4 a, uint4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma<F16>(uint4 a, uint4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-constexpr int kB = 64;        // rows and columns of a block: the k-tile of every kernel here
-constexpr int kStr = kB + 8;  // LDS row stride in elements (144 bytes: 16 rows of a fragment read on 16 bank slots)
 
 struct MmArgs {
   const int32_t* rowptr;  // [own_blocks + 1]
@@ -78,64 +61,6 @@ struct SddmmArgs {
   long ldg, ldb, sG, sB;
 };
 
-__device__ __forceinline__ unsigned half_of(uint4 v, int i) {
-  const unsigned w = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
-  return (i & 1) ? (w >> 16) : (w & 0xffffu);
-}
-
-__device__ __forceinline__ uint4 pack8(const unsigned short (&e)[8]) {
-  return uint4{e[0] | ((unsigned)e[1] << 16), e[2] | ((unsigned)e[3] << 16), e[4] | ((unsigned)e[5] << 16),
-               e[6] | ((unsigned)e[7] << 16)};
-}
-
-// 8 contiguous elements p[0 … 7], of which the first `avail` exist (zeros for the rest; nothing read when avail ≤ 0).
-template <bool VEC>
-__device__ __forceinline__ uint4 load8(const uint16_t* p, int avail) {
-  if (VEC && avail >= 8) return *reinterpret_cast<const uint4*>(p);
-  unsigned short e[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) e[j] = j < avail ? p[j] : (unsigned short)0;
-  return pack8(e);
-}
-
-// A 64 × 64 value block, k contiguous as stored (element (r, k) at P[64r + k]): 512 pieces of 8, two per thread.
-struct BlockKC {
-  uint4 lo, hi;  // pieces tid and tid + 256 (two members, not an array: they stay in registers)
-  __device__ __forceinline__ void load(const uint16_t* P, int tid) {
-    lo = *reinterpret_cast<const uint4*>(P + (long)tid * 8);
-    hi = *reinterpret_cast<const uint4*>(P + (long)(tid + 256) * 8);
-  }
-  __device__ __forceinline__ void store(unsigned short* S, int tid) const {
-    *reinterpret_cast<uint4*>(S + (tid >> 3) * kStr + (tid & 7) * 8) = lo;
-    *reinterpret_cast<uint4*>(S + ((tid >> 3) + 32) * kStr + (tid & 7) * 8) = hi;
-  }
-};
-
-// R output-side rows × 64 values of k of an operand stored rows-contiguous (element (r, k) at P[k·ld + r]): 2R units of
-// 4 k-rows × 8 rows, one per thread, transposed in registers into 8-byte LDS writes.  The 16 k-quads of a row group go
-// to 16 consecutive lanes (the 8-byte writes of one transposed row then fall on 32 different bank slots).
-template <int R>
-struct TileRC {
-  uint4 v[4];
-  template <bool VEC>
-  __device__ __forceinline__ void load(const uint16_t* P, long ld, int row0, int rows, int tid) {
-    const int r = row0 + (tid >> 4) * 8, kk = (tid & 15) * 4;
-    const int avail = tid < 2 * R ? rows - r : 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = load8<VEC>(P + (long)(kk + q) * ld + r, avail);
-  }
-  __device__ __forceinline__ void store(unsigned short* S, int tid) const {
-    if (tid < 2 * R) {
-      const int r = (tid >> 4) * 8, kk = (tid & 15) * 4;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const uint2 w = {half_of(v[0], i) | (half_of(v[1], i) << 16), half_of(v[2], i) | (half_of(v[3], i) << 16)};
-        *reinterpret_cast<uint2*>(S + (r + i) * kStr + kk) = w;
-      }
-    }
-  }
-};
-
 // the next entry at or after p that is computed: its column inside the grid, its values inside the buffer
 __device__ __forceinline__ int next_entry(const MmArgs& g, int p, int end) {
   for (; p < end; ++p) {
@@ -145,56 +70,6 @@ __device__ __forceinline__ int next_entry(const MmArgs& g, int p, int end) {
     break;
   }
   return p;
-}
-
-// The 2 × FN accumulators of a wave over one staged 64-deep k-tile: As [64][kStr] the output rows, Bs [BN][kStr] the
-// output columns.  Fragment pair j/2: row li of fragment j holds column 32(j/2) + 8(li/4) + 4(j%2) + li%4 of the wave's
-// tile, so that a lane ends with eight adjacent columns of one row (gemm_lowp.hip).
-template <class T, int FN>
-__device__ __forceinline__ void tile_mfma(f32x4 (&acc)[2][FN], const unsigned short* As, const unsigned short* Bs, int wm, int wn,
-                                          int li, int lg) {
-#pragma unroll
-  for (int ks = 0; ks < kB / 32; ++ks) {
-    const int kofs = ks * 32 + 8 * lg;
-    uint4 af[2], bf[FN];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const uint4*>(As + (wm * 32 + i * 16 + li) * kStr + kofs);
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      const int c = wn * (FN * 16) + (j >> 1) * 32 + 8 * (li >> 2) + 4 * (j & 1) + (li & 3);
-      bf[j] = *reinterpret_cast<const uint4*>(Bs + c * kStr + kofs);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j) acc[i][j] = mfma<T>(bf[j], af[i], acc[i][j]);
-  }
-}
-
-// lane (li, lg) holds row li of each 16-row fragment and columns 8·lg … 8·lg + 7 of each fragment pair
-template <class T, int FN, bool VEC>
-__device__ __forceinline__ void store_acc(const f32x4 (&acc)[2][FN], uint16_t* C, long ldc, int n0, int n, int wm, int wn, int li,
-                                          int lg) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int r = wm * 32 + i * 16 + li;
-#pragma unroll
-    for (int p = 0; p < FN / 2; ++p) {
-      const int c = n0 + wn * (FN * 16) + p * 32 + 8 * lg;
-      const f32x4 x = acc[i][2 * p], y = acc[i][2 * p + 1];
-      uint16_t* dst = C + (long)r * ldc + c;
-      if (VEC && c + 8 <= n) {
-        *reinterpret_cast<uint4*>(dst) =
-            uint4{pack2<T>(x[0], x[1]), pack2<T>(x[2], x[3]), pack2<T>(y[0], y[1]), pack2<T>(y[2], y[3])};
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (c + e < n) dst[e] = T::down(x[e]);
-          if (c + 4 + e < n) dst[4 + e] = T::down(y[e]);
-        }
-      }
-    }
-  }
 }
 
 // One listed entry in registers on its way to LDS: the value block and the 64 × BN tile of the dense operand.

@@ -50,6 +50,7 @@ namespace {
 #include "custom_mm_attention.inc"
 #include "custom_mm_block_attention.inc"
 #include "custom_mm_bsr.inc"
+#include "custom_mm_bsr_linear.inc"
 
 // ---- handle init / destroy (reference custom_mm.cpp:361-391) ----------------
 // There are no vendor handles on this path; init checks that the C-ABI library
@@ -192,6 +193,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bsr_sddmm", &bsr_sddmm,
         "(entry_row, columns, entry_ids or None, nnz, dC [batch, M, N], B [batch, K, N], dvalues [n, 64, 64]): "
         "dvalues[e] = sum over the items of dC[I-rows] B[J-rows]^T on the kept blocks");
+  m.def("bsr_linear", &bsr_linear,
+        "(offsets [outer/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], X [T, inner], bias [outer] or None, Y [T, outer], "
+        "trans_w): Y = X op(W)^T (+ bias) with W in 64 x 64 blocks on the matrix cores, bfloat16 / float16");
+  m.def("bsr_wgrad", &bsr_wgrad, py::arg("entry_row"), py::arg("columns"), py::arg("entry_ids"), py::arg("nnz"), py::arg("dY"),
+        py::arg("X"), py::arg("dvalues"), py::arg("splits") = 0,
+        "dvalues[e] = dY[:, O-columns]^T X[:, I-columns] on the kept blocks, the tokens cut into `splits` ranges (0: the rule)");
+  m.def("bsr_wgrad_split_count", &bsr_wgrad_split_count, "ranges bsr_wgrad cuts the tokens into for (kept blocks, tokens)");
   // Handles and automatic schedules own HIP streams and events: they are released while the interpreter — and with it the HIP
   // runtime — is still up (left to the destructors of the statics they segfaulted at process exit after the runtime had gone:
   // a program that never called cusparse_clean / auto_schedule_clear ended with exit code 139 AFTER its last line of output).

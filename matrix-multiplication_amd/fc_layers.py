@@ -19,6 +19,9 @@ bfloat16 / float16: a layer moved with `.to(torch.bfloat16)` 
 returns it, forward and backward — the product on the matrix cores with the bias in its epilogue, the weight
 gradient through the deterministic split-k (`custom_mm.cublas_mmul_splitk`), the bias gradient by
 `custom_mm.column_sums`; fp32 sums, each element rounded once.  The input and the parameters must share one dtype.
+
+`blockSparseLinear` (an addition) is the layer with a block-pruned WEIGHT: the kept 64 × 64 blocks of
+`weight` are its parameter, the layout a pair of buffers; bfloat16 / float16 only (`matmuls.block_sparse_linear`).
 '''
 
 import math
@@ -28,7 +31,7 @@ import torch.nn as nn
 from torch.autograd.function import InplaceFunction
 
 import custom_mm
-from matmuls import custom_matmul, sampled_density
+from matmuls import block_sparse_linear, custom_matmul, sampled_density
 
 
 def _column_sums(g2d):
@@ -257,3 +260,93 @@ class cusparseLinear(_LinearBase):
     "the route never changes the result", which the float32 layer guarantees, could not hold; and a sparse route
     would need a bias epilogue in the low-precision CSR kernels and a 2-byte dense → CSR conversion.'''
     _fn = _SparseLinearBias
+
+
+def _block_rows(crow):
+    '''The block row of every stored entry of a CSR layout.'''
+    rows = crow.numel() - 1
+    return torch.repeat_interleave(torch.arange(rows, device=crow.device), (crow[1:] - crow[:-1]).to(torch.int64))
+
+
+def _kept_blocks(weight, crow, col):
+    '''[n, 64, 64]: the blocks of a dense [out, in] weight at the stored entries of the layout, in stored-entry order.'''
+    out_f, in_f = weight.shape
+    blocks = weight.reshape(out_f // 64, 64, in_f // 64, 64).permute(0, 2, 1, 3)
+    return blocks[_block_rows(crow), col.to(torch.int64)].contiguous()
+
+
+class blockSparseLinear(nn.Module):
+    '''y = inp @ W.t() + bias with a block-pruned weight: `layout` a 2-d CSR tensor [out_features/64, in_features/64]
+    whose stored entries are the kept 64 × 64 blocks of W (matmuls.block_sparse_linear; bfloat16 / float16 — move the layer
+    with `.to(device, dtype)`).  Parameters: `values` [n, 64, 64], the kept blocks in stored-entry order, and `bias`; the
+    layout's `crow_indices` / `col_indices` are buffers, so they move, save and load with the module.  The CSR layout
+    tensor the kernels' sorted and transposed lists live on is rebuilt from the buffers only when they move or are
+    overwritten, and kept on the module otherwise.
+
+    Initialisation is `cublasLinear`'s — the same seed, the same kaiming_uniform_ on a dense [out, in] weight, the same
+    bias — with the kept blocks taken from that weight: a full layout starts with exactly `cublasLinear`'s parameters.'''
+
+    def __init__(self, in_features, out_features, layout, bias=True):
+        super().__init__()
+        torch.manual_seed(0)  # as _LinearBase
+        if in_features % 64 != 0 or out_features % 64 != 0:
+            raise ValueError('blockSparseLinear: in_features and out_features must be multiples of 64, got {} and {}'.format(
+                in_features, out_features))
+        if not isinstance(layout, torch.Tensor) or layout.layout != torch.sparse_csr or layout.dim() != 2 or \
+                tuple(layout.shape) != (out_features // 64, in_features // 64):
+            raise ValueError('blockSparseLinear: the layout must be a 2-d CSR tensor [out_features/64, in_features/64] = '
+                             '[{}, {}]'.format(out_features // 64, in_features // 64))
+        self.in_features = in_features
+        self.out_features = out_features
+        self.register_buffer('crow_indices', layout.crow_indices().detach().clone())
+        self.register_buffer('col_indices', layout.col_indices().detach().clone())
+        weight = torch.empty(out_features, in_features)
+        nn.init.kaiming_uniform_(weight, a=math.sqrt(5))
+        self.values = nn.Parameter(_kept_blocks(weight, self.crow_indices.cpu(), self.col_indices.cpu()))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_features))
+            bound = 1 / math.sqrt(in_features)  # fan_in of the dense weight
+            nn.init.uniform_(self.bias, -bound, bound)
+        else:
+            self.register_parameter('bias', None)
+        self._layout = self._layout_key = None
+
+    @classmethod
+    def from_dense(cls, weight, layout, bias=None):
+        '''The layer whose kept blocks are those of the dense `weight` [out, in] (what lies outside the layout is dropped)
+        and whose bias is `bias`, in the dtype and on the device of `weight`.'''
+        layer = cls(weight.shape[1], weight.shape[0], layout, bias=bias is not None).to(device=weight.device, dtype=weight.dtype)
+        with torch.no_grad():
+            layer.values.copy_(_kept_blocks(weight.detach(), layer.crow_indices, layer.col_indices))
+            if bias is not None:
+                layer.bias.copy_(bias.detach())
+        return layer
+
+    def layout(self):
+        '''The CSR layout tensor [out/64, in/64] on the buffers as they are now (no copy of the indices).'''
+        crow, col = self.crow_indices, self.col_indices
+        key = (crow.data_ptr(), col.data_ptr(), str(crow.device), crow._version, col._version)
+        if self._layout is None or self._layout_key != key:
+            marks = torch.ones(col.numel(), dtype=torch.float32, device=col.device)
+            self._layout = torch.sparse_csr_tensor(crow, col, marks, size=(self.out_features // 64, self.in_features // 64))
+            self._layout_key = key
+        return self._layout
+
+    def dense_weight(self):
+        '''W [out, in] with zeros outside the layout (differentiable in `values`).'''
+        rows, cols = self.out_features // 64, self.in_features // 64
+        blocks = self.values.new_zeros((rows, cols, 64, 64))
+        blocks = blocks.index_put((_block_rows(self.crow_indices), self.col_indices.to(torch.int64)), self.values)
+        return blocks.permute(0, 2, 1, 3).reshape(self.out_features, self.in_features)
+
+    def forward(self, inp):
+        if inp.shape[-1] != self.in_features:
+            print('Invalid dimensions')  # reference behaviour (cublas_fc_layer.py:37-40)
+            return 0
+        _check_dtypes(inp, self.values, self.bias)
+        return block_sparse_linear(inp, self.values, self.layout(), self.bias)
+
+    def extra_repr(self):
+        return 'in_features={}, out_features={}, kept_blocks={} of {}, bias={}'.format(
+            self.in_features, self.out_features, self.values.shape[0], (self.in_features // 64) * (self.out_features // 64),
+            self.bias is not None)

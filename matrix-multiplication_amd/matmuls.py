@@ -1890,3 +1890,142 @@ def bsr_parts(a: torch.Tensor):
     marks = torch.ones(col.shape[0], dtype=torch.float32, device=col.device)  # (a CSR tensor carries values; ignored)
     layout = torch.sparse_csr_tensor(crow, col, marks, size=(a.shape[0] // _BLOCK_TILE, a.shape[1] // _BLOCK_TILE))
     return values, layout
+
+
+# --------------------------------------------------------------------------- #
+# block-sparse linear layer on the matrix cores: y = x·Wᵀ + bias over kept 64-blocks
+# --------------------------------------------------------------------------- #
+
+_BSR_LINEAR_SIZES_TEXT = 'bfloat16 or float16 operands, block = 64, in and out multiples of 64'
+
+
+def block_linear_takes(dtype, block) -> bool:
+    '''Whether block_sparse_linear takes blocks of `block` × `block` in `dtype` — a function of (dtype, block) alone:
+    bfloat16 / float16 and block == 64.  Anything else raises there.'''
+    return dtype in _LOWP and isinstance(block, int) and not isinstance(block, bool) and block == _BLOCK_TILE
+
+
+class blockSparseLinearFn(InplaceFunction):
+    '''y = x·Wᵀ (+ bias) with W [out, in] the 64 × 64 blocks `values` on the block list of `layout`
+    (custom_mm.bsr_linear), saving x, values and the layout — nothing of size out × in, no transposed copy of the
+    activations.  Backward: d x = dY·W by custom_mm.bsr_linear over the transposed lists kept in the layout tensor's
+    _CsrState (shared with block_sparse_mm), d values on the pattern by custom_mm.bsr_wgrad (the deterministic split of
+    the tokens), d bias by custom_mm.column_sums.  No atomics, no read-back.'''
+
+    @staticmethod
+    def forward(ctx, x, values, layout, bias):
+        rec = _bsr_layout(layout, x.device, _csr_state(layout))
+        offsets, columns, ids, _, n = rec['fwd']
+        fin, fout = x.shape[-1], layout.shape[0] * _BLOCK_TILE
+        x2 = x.reshape(-1, fin)
+        tokens = x2.shape[0]
+        if tokens == 0:
+            out = torch.empty((0, fout), device=x.device, dtype=x.dtype)
+        elif n == 0:
+            out = torch.zeros((tokens, fout), device=x.device, dtype=x.dtype)
+            if bias is not None:
+                out += bias
+        else:
+            out = torch.empty((tokens, fout), device=x.device, dtype=x.dtype)
+            custom_mm.bsr_linear(offsets, columns, ids, n, values, x2, bias, out, False)
+        ctx.save_for_backward(x, values, layout)
+        ctx.has_bias = bias is not None
+        return out.reshape(tuple(x.shape[:-1]) + (fout,))
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        x, values, layout = ctx.saved_tensors
+        fin, fout = x.shape[-1], layout.shape[0] * _BLOCK_TILE
+        x2 = x.reshape(-1, fin)
+        tokens = x2.shape[0]
+        need = ctx.needs_input_grad
+        dx = dvalues = dbias = None
+        rec = _bsr_layout(layout, x.device, _csr_state(layout))
+        offsets, columns, ids, entry_row, n = rec['fwd']
+        empty = n == 0 or tokens == 0
+        g2 = grad_output.to(x.dtype).reshape(-1, fout)
+        if need[0] and not empty:
+            # first, before any gradient is allocated: the one-off device transpose brings its own fixed workspace (2 MiB)
+            t_off, t_col, t_ids = _bsr_layout_transposed(rec, fout // _BLOCK_TILE, fin // _BLOCK_TILE)
+        if need[0]:
+            if empty:
+                dx = torch.zeros(x.shape, device=x.device, dtype=x.dtype)
+            else:
+                dx = torch.empty((tokens, fin), device=x.device, dtype=x.dtype)
+                custom_mm.bsr_linear(t_off, t_col, t_ids, n, values, g2, None, dx, True)
+                dx = dx.reshape(x.shape)
+        if need[1]:
+            if empty:
+                dvalues = torch.zeros_like(values)
+            else:
+                dvalues = torch.empty_like(values)
+                custom_mm.bsr_wgrad(entry_row, columns, ids, n, g2, x2, dvalues)
+        if ctx.has_bias and need[3]:
+            dbias = custom_mm.column_sums(g2) if tokens > 0 else torch.zeros(fout, device=x.device, dtype=x.dtype)
+        return dx, dvalues, None, dbias
+
+
+def _check_block_linear_operands(what, x, values, layout, bias, block):
+    '''Every refusal of block_sparse_linear, before the first device call, with the exception types of
+    _check_block_mm_operands: ValueError for what an operand is (layout, dtype, block, shapes), RuntimeError for operands
+    that do not go together (mixed dtypes, host tensors / devices).'''
+    _check_csr(what, 'layout', layout)
+    if layout.dim() != 2:
+        raise ValueError(f'{what}: the layout must be a 2-d CSR tensor [out/64, in/64], got {layout.dim()}-d: W is shared by '
+                         f'every token, a batched layout is not supported')
+    operands = (('x', x), ('values', values)) + ((('bias', bias),) if bias is not None else ())
+    for name, t in operands:
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be a dense tensor')
+        if t.dtype not in _LOWP:
+            raise ValueError(f'{what}: {name} must be bfloat16 or float16, got {t.dtype} (accepted: {_BSR_LINEAR_SIZES_TEXT})')
+    for name, t in operands[1:]:
+        if t.dtype != x.dtype:
+            raise RuntimeError(f'{what}: x is {x.dtype} but {name} is {t.dtype}: all operands must have one dtype '
+                               f'(bfloat16 or float16)')
+    if isinstance(block, bool) or not isinstance(block, int) or block != _BLOCK_TILE:
+        raise ValueError(f'{what}: block must be 64, got {block!r} (accepted: {_BSR_LINEAR_SIZES_TEXT})')
+    n = torch.Tensor.values(layout).numel()
+    if values.dim() != 3 or tuple(values.shape[1:]) != (block, block):
+        raise ValueError(f'{what}: values must be [n, {block}, {block}], got {tuple(values.shape)}')
+    if values.shape[0] != n:
+        raise ValueError(f'{what}: values holds {values.shape[0]} blocks but the layout stores {n} entries')
+    if not values.is_contiguous():
+        raise ValueError(f'{what}: values must be contiguous')
+    if x.dim() < 1:
+        raise ValueError(f'{what}: x must be a [..., in] tensor, got {x.dim()}-d')
+    fin, fout = x.shape[-1], layout.shape[0] * block
+    if fin % block != 0 or fin // block != layout.shape[1]:
+        raise ValueError(f'{what}: x of shape {tuple(x.shape)} has in = {fin} features, the layout {tuple(layout.shape)} needs '
+                         f'in = {layout.shape[1]} · {block} = {layout.shape[1] * block}: in and out must be multiples of '
+                         f'block, ragged sizes are not supported (accepted: {_BSR_LINEAR_SIZES_TEXT})')
+    if bias is not None and tuple(bias.shape) != (fout,):
+        raise ValueError(f'{what}: bias must be [out] = [{fout}], got {tuple(bias.shape)}')
+    if n >= 2 ** 31:
+        raise ValueError(f'{what}: the layout does not fit int32 indices')
+    named = dict(layout=torch.Tensor.values(layout), x=x, values=values)
+    if bias is not None:
+        named['bias'] = bias
+    _check_on_device(what, **named)
+
+
+def block_sparse_linear(x: torch.Tensor, values: torch.Tensor, layout: torch.Tensor, bias=None, block: int = 64) -> torch.Tensor:
+    '''y = x·Wᵀ + bias on the matrix cores with the weight W [out, in] given in BLOCKS — the operands of block_sparse_mm:
+    `layout` a 2-d CSR tensor [out/64, in/64] whose stored entry (O, I) keeps block (O, I) of W (values ignored; int32 or
+    int64 indices; the columns of a block row in any order; a block stored twice is NOT supported), `values` [n, 64, 64]
+    contiguous in stored-entry order (bsr_parts of a torch.sparse_bsr weight); x [*lead, in], the leading dimensions
+    flattened to tokens (any count, zero included); bias [out] or None; all bfloat16 or all float16, device tensors.
+    y is [*lead, out].
+
+    Products on the MFMA with fp32 accumulators, one accumulator per output element from +0 through the kept blocks in
+    ascending block order whatever the order of the layout, the bias added in fp32, one rounding at the store: for finite
+    operands, bit for bit, cublas_mmul_bias(x, W_dense, bias, transb=True) of this package — but a block outside the layout
+    is never read, nor the columns of x it would meet.  A block row that keeps nothing gives the bias (or +0).
+    Differentiable in x (dY·W over the transposed lists, built once per layout tensor and shared with block_sparse_mm: the
+    bits of cublas_mmul(dY, W_dense)), in values (a dense [n, 64, 64] gradient on the pattern, the tokens cut into ranges
+    by custom_mm.bsr_wgrad_split_count and combined in fp32 in a fixed order: the kept blocks of cublas_mmul_splitk(dY, x,
+    transa=True) at the same count) and in bias (custom_mm.column_sums).  No transposed copy of the activations, no float
+    atomics, no read-back.  float32, other block sizes, a batched layout and ragged in or out raise
+    (block_linear_takes).'''
+    _check_block_linear_operands('block_sparse_linear', x, values, layout, bias, block)
+    return blockSparseLinearFn.apply(x, values, layout, bias)
