@@ -11,7 +11,9 @@ RTOL, ATOL = 1e-5, 1e-8
 
 __all__ = ['RTOL', 'ATOL', 't', 'torch_cpu_csr_matmul', 'assert_matches_reference_expression', 'run_spmm', '_random_rows_csr', '_transpose_through_the_c_abi', 'gemm_ref', '_dense_of', 'fwd_bwd_device', '_panel_sorted', '_sub_csr', '_moderately_dense_with_hub_rows',
            'assert_same_bits', 'gamma', 'assert_within_gamma_bound',
-           'sum_grads_f64', 'select_grads_f64']
+           'sum_grads_f64', 'select_grads_f64', 'Padded', 'padded', 'SENTINEL', 'assert_outside_untouched', '_sparse_attention_through_the_c_abi',
+           '_sparse_attention_backward_through_the_c_abi', '_block_attention_fwd_through_the_c_abi',
+           '_block_attention_bwd_through_the_c_abi']
 
 
 def t(x, dev):
@@ -81,6 +83,111 @@ def _transpose_through_the_c_abi(capi, dev, rowptr, col, val, M, K, plan):
     assert st == 0, st
     assert capi.mi_csr_transpose_check(ws.data_ptr(), ws_bytes, 1, M, K, nnz, stream) == 0, "a look-back poll gave up"
     return t_rp.cpu().numpy(), t_col.cpu().numpy(), t_val.cpu().numpy()
+
+
+class Padded:
+    """A dense operand [batch, rows, D] of the attention entries inside a larger buffer of its own: `buf` (1-d), the logical
+    view `x` on it, the leading dimension `ld` and the item stride `stride` in elements."""
+
+    def __init__(self, buf, x, ld, stride):
+        self.buf, self.x, self.ld, self.stride = buf, x, ld, stride
+
+    def args(self, stride=None):
+        return [self.buf.data_ptr(), self.ld, self.stride if stride is None else stride]
+
+    def outside(self):
+        """The buffer's elements outside the logical [batch][rows][:D]."""
+        inside = torch.zeros(self.buf.shape, dtype=torch.bool, device=self.buf.device)
+        inside.as_strided(self.x.shape, self.x.stride()).fill_(True)
+        return self.buf[~inside]
+
+
+def padded(x, number, fill, step=8):
+    """Operand number `number` of a call as a Padded: leading dimension D + step·(number + 1), item stride rows·ld +
+    step·(number + 1) — different from every other operand's and from the packed ones; with step = 8 rows are 16-byte
+    aligned for every dtype, with step = 4 a 2-byte dtype's rows of the even-numbered operands sit on 8-byte boundaries
+    only (what the fused bfloat16 / float16 entries ask for) —, everything outside the logical region set to `fill` (NaN
+    for an input: it stays out of the results only if nothing outside is read; SENTINEL for an output, checked afterwards
+    with assert_outside_untouched)."""
+    batch, rows, D = x.shape
+    ld = D + step * (number + 1)
+    stride = rows * ld + step * (number + 1)
+    buf = torch.full((batch * stride + 8,), fill, dtype=x.dtype, device=x.device)
+    view = buf.as_strided((batch, rows, D), (stride, ld, 1))
+    view.copy_(x)
+    return Padded(buf, view, ld, stride)
+
+
+SENTINEL = -7.5  # around the outputs of a padded call: finite, exact in float32, bfloat16 and float16
+
+
+def assert_outside_untouched(p, what):
+    """The call left every element of the Padded output `p` outside its logical region at SENTINEL."""
+    rest = p.outside()
+    assert_same_bits(rest, torch.full_like(rest, SENTINEL), f"{what}: outside the logical region")
+
+
+def _attention_entry(capi, name):
+    """A fused / block attention entry of the C ABI with its argument types (include/mi_spmm.h)."""
+    vp, i64, i32, f32, sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_size_t
+    dense = [vp, i64, i64]
+    fn = getattr(capi, name)
+    if name.startswith("mi_sparse_attention_backward_"):
+        fn.argtypes = [vp, vp, i64, i32, i32, i32, i32] + 4 * dense + [vp, f32] + dense + [vp, vp, vp, sz, vp]
+    elif name.startswith("mi_sparse_attention_"):
+        fn.argtypes = [vp, vp, i64, i32, i32, i32, i32] + 3 * dense + [f32] + dense + [vp, vp, sz, vp]
+    elif name.startswith("mi_block_attention_fwd_"):
+        fn.argtypes = [vp, vp, i64] + 6 * [i32] + 3 * dense + [f32] + dense + [vp, vp]
+    else:
+        fn.argtypes = [vp, vp, vp, vp, i64] + 6 * [i32] + 5 * dense + [vp, f32] + 3 * dense + [vp, sz, vp]
+    fn.restype = ctypes.c_int
+    return fn
+
+
+_SUFFIX = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}
+
+
+def _sparse_attention_through_the_c_abi(capi, dtype, offsets, columns, batch, M, K, D, q, k, v, scale, out, stats,
+                                        kv_stride=None):
+    """mi_sparse_attention_T on Padded operands (kv_stride: the item stride passed for k and v instead of their own);
+    returns the status."""
+    fn = _attention_entry(capi, f"mi_sparse_attention_{_SUFFIX[dtype]}")
+    stream = torch.cuda.current_stream().cuda_stream
+    return fn(offsets.data_ptr(), columns.data_ptr(), columns.numel(), batch, M, K, D, *q.args(), *k.args(kv_stride),
+              *v.args(kv_stride), scale, *out.args(), stats.data_ptr(), None, 0, stream)
+
+
+def _sparse_attention_backward_through_the_c_abi(capi, dtype, offsets, columns, batch, M, K, D, q, k, v, dout, stats, scale,
+                                                 dq, y, ds, kv_stride=None):
+    """mi_sparse_attention_backward_T on Padded operands (y, ds: plain [nnz] tensors); returns the status."""
+    fn = _attention_entry(capi, f"mi_sparse_attention_backward_{_SUFFIX[dtype]}")
+    stream = torch.cuda.current_stream().cuda_stream
+    return fn(offsets.data_ptr(), columns.data_ptr(), columns.numel(), batch, M, K, D, *q.args(), *k.args(kv_stride),
+              *v.args(kv_stride), *dout.args(), stats.data_ptr(), scale, *dq.args(), y.data_ptr(), ds.data_ptr(), None, 0, stream)
+
+
+def _block_attention_fwd_through_the_c_abi(capi, dtype, offsets, columns, nnz, layouts, batch, Sq, Sk, D, causal, q, k, v,
+                                           scale, out, lse, kv_stride=None):
+    """mi_block_attention_fwd_T on Padded operands; returns the status."""
+    fn = _attention_entry(capi, f"mi_block_attention_fwd_{_SUFFIX[dtype]}")
+    stream = torch.cuda.current_stream().cuda_stream
+    return fn(offsets.data_ptr(), columns.data_ptr(), nnz, layouts, batch, Sq, Sk, D, causal, *q.args(), *k.args(kv_stride),
+              *v.args(kv_stride), scale, *out.args(), lse.data_ptr(), stream)
+
+
+def _block_attention_bwd_through_the_c_abi(capi, dtype, offsets, columns, t_offsets, t_columns, nnz, layouts, batch, Sq, Sk, D,
+                                           causal, q, k, v, out, dout, lse, scale, dq, dk, dv, kv_stride=None):
+    """mi_block_attention_bwd_T on Padded operands, with a workspace of mi_block_attention_workspace_bytes; returns the
+    status."""
+    fn = _attention_entry(capi, f"mi_block_attention_bwd_{_SUFFIX[dtype]}")
+    capi.mi_block_attention_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
+    capi.mi_block_attention_workspace_bytes.restype = ctypes.c_size_t
+    ws_bytes = capi.mi_block_attention_workspace_bytes(batch, Sq)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=lse.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    return fn(offsets.data_ptr(), columns.data_ptr(), t_offsets.data_ptr(), t_columns.data_ptr(), nnz, layouts, batch, Sq, Sk, D,
+              causal, *q.args(), *k.args(kv_stride), *v.args(kv_stride), *out.args(), *dout.args(), lse.data_ptr(), scale,
+              *dq.args(), *dk.args(), *dv.args(), ws.data_ptr(), ws_bytes, stream)
 
 
 def gemm_ref(oracle_mod, a, b, ta, tb):

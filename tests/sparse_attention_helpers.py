@@ -1,6 +1,7 @@
-"""Shared by tests/test_gpu_csr_softmax.py and tests/test_gpu_sparse_attention.py: input builders, the float64 / float32
-torch-CPU references and the e_dev ≤ 8 · e_ref rule.  The measured pairs are printed and appended to
-profiles/r12_csr_softmax.log when MI_SOFTMAX_LOG names a file."""
+"""Shared by tests/test_gpu_csr_softmax.py, tests/test_gpu_sparse_attention.py, tests/test_gpu_fused_attention.py and
+tests/test_gpu_block_attention.py: input builders, the float64 / float32 torch-CPU references (dense_step: dense masked
+attention, optionally narrowed once per stage) and the e_dev ≤ 8 · e_ref rule, for a whole tensor and per class of rows.
+The measured pairs are printed and appended to the file MI_SOFTMAX_LOG names, when it names one."""
 import os
 
 import numpy as np
@@ -22,6 +23,50 @@ def record(what, e_ref, e_dev):
 def assert_under_rule(what, e_ref, e_dev):
     record(what, e_ref, e_dev)
     assert e_dev <= FACTOR * e_ref, f"{what}: e_dev {e_dev:.3e} > {FACTOR:g} · e_ref {e_ref:.3e}"
+
+
+def _f64(x):
+    return np.asarray(torch.as_tensor(x).detach().cpu().double().numpy(), np.float64)
+
+
+def assert_tensor_under_rule(what, got, yard, ref):
+    """The rule on one whole tensor: `got` the device result, `yard` the yardstick's, `ref` the float64 one."""
+    got, yard, ref = _f64(got), _f64(yard), _f64(ref)
+    assert got.shape == yard.shape == ref.shape, (what, got.shape, yard.shape, ref.shape)
+    assert_under_rule(what, scaled_err(yard, ref), scaled_err(got, ref))
+
+
+def assert_under_rule_by_rows(what, got, yard, ref, classes):
+    """The rule on the whole row-indexed tensor [rows, D] (out, dq), then on each class of rows alone: `classes` maps a
+    name to row indices, scaled_err is taken over those rows only — a long row's small outputs are measured against their
+    own maximum, not against the short rows' — and the bound is FACTOR · max(e_ref of the class, e_ref of the whole
+    tensor): the floor keeps a class of few elements from failing on a lucky yardstick.  `yard` is the yardstick's result,
+    `ref` the float64 one."""
+    got, yard, ref = _f64(got), _f64(yard), _f64(ref)
+    assert got.ndim == 2, (what, got.shape)
+    assert_tensor_under_rule(f"{what}, all rows", got, yard, ref)
+    e_all = scaled_err(yard, ref)
+    for name, rows in classes.items():
+        rows = np.asarray(rows, np.int64)
+        e_class = scaled_err(yard[rows], ref[rows])
+        assert_under_rule(f"{what}, rows {name} ({len(rows)} rows, their own e_ref {e_class:.3e})", max(e_class, e_all),
+                          scaled_err(got[rows], ref[rows]))
+
+
+def dense_step(q, k, v, w, mask, scale, wide, narrow=None):
+    """Dense masked attention on the CPU in `wide`, with autograd: (out, dq, dk, dv) for the incoming gradient w; rows of
+    the mask that see nothing give zero rows.  `narrow` (T) rounds the scores, the probabilities and the product to T and
+    widens them again — with wide = float32 the yardstick of a bfloat16 / float16 device result; for a float32 device
+    result the yardstick is the plain expression in float32 (narrow=None), the reference the one in float64."""
+    rnd = (lambda t: t) if narrow is None else (lambda t: t.to(narrow).to(wide))
+    rq, rk, rv = (t.detach().cpu().to(wide).requires_grad_(True) for t in (q, k, v))
+    s = rnd(scale * (rq @ rk.transpose(-1, -2)))
+    empty = ~mask.any(-1, keepdim=True)
+    p = torch.softmax(s.masked_fill(~mask & ~empty, -float("inf")), -1)
+    p = rnd(torch.where(empty, torch.zeros_like(p), p))
+    out = rnd(p @ rv)
+    grads = torch.autograd.grad(out, (rq, rk, rv), grad_outputs=w.detach().cpu().to(wide))
+    return (out.detach(),) + tuple(g.detach() for g in grads)
 
 
 def rel_err(y, y64):

@@ -4,12 +4,15 @@ nothing are zero), held to the project's rule e_dev ≤ 8 · e_ref on scaled_err
 computation with every stage in fp32 on widened inputs, narrowed to T after the scores, after the softmax and after the
 product, with autograd through it.  Beside the rule: exact zeros for rows that see nothing and keys nobody sees, bits
 that do not depend on the batch or the layout's form, causal skipping, NaN outside the kept blocks, block = 128 as its
-expansion, determinism, and the memory autograd keeps."""
+expansion, determinism, and the memory autograd keeps.  A rectangular batch (Sq ≠ Sk: q's item stride differs from k's)
+under the rule and item by item; and through the C ABI every dense operand with a leading dimension and an item stride of
+its own, NaN around the inputs and a sentinel around the outputs, and k, v shared by the batch (item stride 0)."""
 import pytest
 import torch
 
-from gpu_helpers import assert_same_bits
-from sparse_attention_helpers import assert_under_rule, device_pattern, scaled_err
+from gpu_helpers import (SENTINEL, assert_outside_untouched, assert_same_bits, padded, _block_attention_bwd_through_the_c_abi,
+                         _block_attention_fwd_through_the_c_abi)
+from sparse_attention_helpers import assert_tensor_under_rule, dense_step, device_pattern
 
 pytestmark = pytest.mark.gpu
 
@@ -51,28 +54,13 @@ def step(mm, q, k, v, layout, w, **kw):
     return (out.detach(),) + torch.autograd.grad(out, (q, k, v), grad_outputs=w)
 
 
-def dense_step(q, k, v, w, mask, scale, wide, narrow=None):
-    """Dense masked attention on the CPU in `wide`, with autograd; `narrow` (T) rounds the scores, the probabilities and
-    the product to T and widens them again (the yardstick)."""
-    rnd = (lambda t: t) if narrow is None else (lambda t: t.to(narrow).to(wide))
-    rq, rk, rv = (t.detach().cpu().to(wide).requires_grad_(True) for t in (q, k, v))
-    s = rnd(scale * (rq @ rk.transpose(-1, -2)))
-    empty = ~mask.any(-1, keepdim=True)
-    p = torch.softmax(s.masked_fill(~mask & ~empty, -float("inf")), -1)
-    p = rnd(torch.where(empty, torch.zeros_like(p), p))
-    out = rnd(p @ rv)
-    grads = torch.autograd.grad(out, (rq, rk, rv), grad_outputs=w.detach().cpu().to(wide))
-    return (out.detach(),) + tuple(g.detach() for g in grads)
-
-
 def check_rule(what, got, q, k, v, w, mask, scale=None):
     scale = 1.0 / q.shape[-1] ** 0.5 if scale is None else scale
     ref = dense_step(q, k, v, w, mask, scale, torch.float64)
     yard = dense_step(q, k, v, w, mask, scale, torch.float32, narrow=q.dtype)
     for name, g, r, y in zip(NAMES, got, ref, yard):
         assert g.dtype == q.dtype and g.shape == r.shape, (what, name)
-        assert_under_rule(f"block attention {what} {name}", scaled_err(y.double().numpy(), r.numpy()),
-                          scaled_err(g.double().cpu().numpy(), r.numpy()))
+        assert_tensor_under_rule(f"block attention {what} {name}", g, y, r)
 
 
 def assert_same_step(got, want, what):
@@ -224,3 +212,91 @@ def test_8_memory(mm, dev):
           f"(dense scores {items * S * S * 2}, design {4 * items * S * D * 2 + 2 * items * S * 4})")
     assert used < items * S * S * 2
     assert all(torch.isfinite(g.float()).all() for g in grads)
+
+
+# Sq = 128, Sk = 192: 2 × 3 blocks.  Per item: equal entry counts, as torch builds a batch; item 1 has an empty block row
+# and a block column nobody keeps.
+RECT_PER_ITEM = [[[1], [2]], [[], [2, 0]], [[2], [0]]]
+RECT_SHARED = [[2, 0], [0, 1, 2]]
+
+
+def rect_layouts(dev, form):
+    """(layout, the items' 2-d layouts) of the rectangular batch of 3."""
+    items = [layout_from_rows(r, 3, dev) for r in (RECT_PER_ITEM if form == "per item" else [RECT_SHARED] * 3)]
+    if form == "shared":
+        return items[0], items
+    crow = torch.stack([l.crow_indices() for l in items])
+    col = torch.stack([l.col_indices() for l in items])
+    return torch.sparse_csr_tensor(crow, col, torch.ones(col.shape, device=dev), size=(3, 2, 3)), items
+
+
+@pytest.mark.parametrize("dtype,D", [(torch.bfloat16, 32), (torch.float16, 96)])
+@pytest.mark.parametrize("form", ["per item", "shared"])
+def test_9_rectangular_batch(mm, dev, dtype, D, form):
+    nb, Sq, Sk = 3, 128, 192
+    layout, items = rect_layouts(dev, form)
+    q, k, v, w = operands(dev, (nb,), Sq, Sk, D, dtype, 41 + D)
+    got = step(mm, q, k, v, layout, w)
+    mask = torch.stack([block_mask(l, 64) for l in items])
+    check_rule(f"rectangular batch ({form}) {dtype} D={D}", got, q, k, v, w, mask)
+    for i in range(nb):
+        assert_same_step([g[i] for g in got], step(mm, q[i], k[i], v[i], items[i], w[i]), f"rectangular batch ({form}), item {i}")
+    if form == "per item":
+        assert (got[0][1, :64] == 0).all() and (got[1][1, :64] == 0).all()        # item 1's empty block row
+        assert (got[2][1, 64:128] == 0).all() and (got[3][1, 64:128] == 0).all()  # item 1's block column nobody keeps
+        assert got[2][1, :64].abs().sum() > 0 and got[3][1, 128:].abs().sum() > 0
+
+
+@pytest.mark.parametrize("dtype,D", [(torch.bfloat16, 32), (torch.float16, 96)])
+def test_10_leading_dimensions_and_strides(mm, cmm, capi, dev, dtype, D):
+    """The per-item rectangular batch through the C ABI: each of the eight dense operands in a buffer of its own with its
+    own leading dimension and item stride (operand number i: ld = D + 8(i + 1), stride = rows · ld + 8(i + 1)), NaN around
+    the inputs, a sentinel around the outputs; every logical output has the bits of the packed call through custom_mm.
+    Then k, v shared by the batch: item stride 0 on one item equals the packed call on that item expanded."""
+    nb, Sq, Sk = 3, 128, 192
+    nan = float("nan")
+    layout, _ = rect_layouts(dev, "per item")
+    rec = mm._block_layout(layout, dev, 1, mm._csr_state(layout))
+    offsets, columns, nnz, L = rec["fwd"]
+    t_off, t_col = mm._block_layout_transposed(rec, Sq // 64, Sk // 64)
+    assert L == nb and nnz == 6
+    q, k, v, w = operands(dev, (nb,), Sq, Sk, D, dtype, 51 + D)
+    scale = 1.0 / D ** 0.5
+
+    def packed(k3, v3):
+        out, dq = torch.full_like(q, nan), torch.full_like(q, nan)
+        dk, dv = torch.full_like(k3, nan), torch.full_like(k3, nan)
+        lse = torch.full((nb, Sq), nan, device=dev)
+        cmm.block_attention_forward(offsets, columns, nnz, q, k3, v3, scale, False, out, lse)
+        cmm.block_attention_backward(offsets, columns, t_off, t_col, nnz, q, k3, v3, out, w, lse, scale, False, dq, dk, dv)
+        return out, lse, dq, dk, dv
+
+    def strided(k3, v3, kv_stride, what):
+        pq, pk, pv, pw = padded(q, 0, nan), padded(k3, 1, nan), padded(v3, 2, nan), padded(w, 4, nan)
+        pout = padded(torch.full_like(q, SENTINEL), 3, SENTINEL)
+        lse = torch.full((nb, Sq), nan, device=dev)
+        st = _block_attention_fwd_through_the_c_abi(capi, dtype, offsets, columns, nnz, L, nb, Sq, Sk, D, 0, pq, pk, pv, scale, pout,
+                                                    lse, kv_stride)
+        assert st == 0, (what, st)
+        torch.cuda.synchronize()
+        assert_outside_untouched(pout, f"{what}: out")
+        pout_in = padded(pout.x.contiguous(), 3, nan)  # the backward reads out
+        outs = [padded(torch.full((nb, rows, D), SENTINEL, device=dev, dtype=dtype), i, SENTINEL)
+                for i, rows in ((5, Sq), (6, Sk), (7, Sk))]
+        st = _block_attention_bwd_through_the_c_abi(capi, dtype, offsets, columns, t_off, t_col, nnz, L, nb, Sq, Sk, D, 0, pq, pk, pv,
+                                                    pout_in, pw, lse, scale, *outs, kv_stride)
+        assert st == 0, (what, st)
+        torch.cuda.synchronize()
+        for name, p in zip(("dq", "dk", "dv"), outs):
+            assert_outside_untouched(p, f"{what}: {name}")
+        return (pout.x, lse) + tuple(p.x for p in outs)
+
+    def compare(got, want, what):
+        for name, g, x in zip(("out", "lse", "dq", "dk", "dv"), got, want):
+            assert_same_bits(g, x, f"{what}: {name}")
+            assert not torch.isnan(g.float()).any(), (what, name)
+
+    compare(strided(k, v, None, "own ld and strides"), packed(k, v), f"{dtype} D={D}, own ld and strides")
+    k1, v1 = k[1:2], v[1:2]  # one k, v for the whole batch
+    compare(strided(k1, v1, 0, "shared k, v"), packed(k1.expand(nb, Sk, D).contiguous(), v1.expand(nb, Sk, D).contiguous()),
+            f"{dtype} D={D}, strideK = strideV = 0")
