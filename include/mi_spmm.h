@@ -982,6 +982,58 @@ int mi_block_attention_bwd_f16(const int32_t* rowptr, const int32_t* col, const 
                                int64_t strideDV, void* workspace, size_t workspace_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * Block-sparse attention with grouped-query heads and per-item lengths: the entries above with four more
+ * arguments in front of the stream.  Everything said there holds; in addition:
+ *   group      ≥ 1: query items per k / v item.  batch counts QUERY items (q, out, dout, dq, lse, the workspace and the
+ *              layouts — item i uses layout i mod layouts — are indexed by them); k, v, dk and dv have batch / group items
+ *              and query item i reads k / v item i / group (heads of a group adjacent: torch's enable_gqa convention).
+ *              dk and dv of a k / v item are summed over its group's query items in ascending order and, within each,
+ *              over that item's transposed list in its order — one fp32 accumulator of one wave, rounded once;
+ *   q_lens,
+ *   k_lens     int32 [lens_count] on the device, 4-byte aligned, each nullable (NULL: every position of that side exists);
+ *              query item i has the lengths of entry i / (batch / lens_count).  A length is clamped to [0, Sq] / [0, Sk]
+ *              where it is read.  Query position r exists iff r < q_len, key position j iff j < k_len: the softmax of a row
+ *              runs over the visible AND existing keys; a query row at or beyond q_len gives a zero row of out and dq and
+ *              −inf as its lse (δ in the workspace: 0) and adds nothing to dk / dv; a key at or beyond k_len gets zero
+ *              rows of dk / dv.  A listed block wholly beyond a length is skipped like an unlisted one; in a block that
+ *              straddles a length the rows beyond it enter no product, whatever memory holds there (NaN included);
+ *   lens_count the entries of q_lens / k_lens; ignored when both are NULL.
+ * Validation before any HIP call, beside the plain entries': group < 1, batch % group != 0; with a length array:
+ * lens_count < 1, batch % lens_count != 0, (batch / lens_count) % group != 0 (the heads of a group share one length), a
+ * misaligned length pointer → MI_EINVAL.  The plain entries are the group = 1, q_lens = k_lens = NULL case of these.
+ * ------------------------------------------------------------------------ */
+int mi_block_attention_fwd_ex_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t batch,
+                                   int32_t Sq, int32_t Sk, int32_t D, int32_t causal, const uint16_t* q, int64_t ldq,
+                                   int64_t strideQ, const uint16_t* k, int64_t ldk, int64_t strideK, const uint16_t* v,
+                                   int64_t ldv, int64_t strideV, float scale, uint16_t* out, int64_t ldo, int64_t strideO,
+                                   float* lse, int32_t group, const int32_t* q_lens, const int32_t* k_lens,
+                                   int32_t lens_count, mi_stream_t stream);
+int mi_block_attention_fwd_ex_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t batch,
+                                  int32_t Sq, int32_t Sk, int32_t D, int32_t causal, const uint16_t* q, int64_t ldq,
+                                  int64_t strideQ, const uint16_t* k, int64_t ldk, int64_t strideK, const uint16_t* v,
+                                  int64_t ldv, int64_t strideV, float scale, uint16_t* out, int64_t ldo, int64_t strideO,
+                                  float* lse, int32_t group, const int32_t* q_lens, const int32_t* k_lens,
+                                  int32_t lens_count, mi_stream_t stream);
+int mi_block_attention_bwd_ex_bf16(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col,
+                                   int64_t nnz, int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk, int32_t D,
+                                   int32_t causal, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k,
+                                   int64_t ldk, int64_t strideK, const uint16_t* v, int64_t ldv, int64_t strideV,
+                                   const uint16_t* out, int64_t ldo, int64_t strideO, const uint16_t* dout, int64_t lddo,
+                                   int64_t strideDO, const float* lse, float scale, uint16_t* dq, int64_t lddq,
+                                   int64_t strideDQ, uint16_t* dk, int64_t lddk, int64_t strideDK, uint16_t* dv, int64_t lddv,
+                                   int64_t strideDV, void* workspace, size_t workspace_bytes, int32_t group,
+                                   const int32_t* q_lens, const int32_t* k_lens, int32_t lens_count, mi_stream_t stream);
+int mi_block_attention_bwd_ex_f16(const int32_t* rowptr, const int32_t* col, const int32_t* t_rowptr, const int32_t* t_col,
+                                  int64_t nnz, int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk, int32_t D,
+                                  int32_t causal, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k,
+                                  int64_t ldk, int64_t strideK, const uint16_t* v, int64_t ldv, int64_t strideV,
+                                  const uint16_t* out, int64_t ldo, int64_t strideO, const uint16_t* dout, int64_t lddo,
+                                  int64_t strideDO, const float* lse, float scale, uint16_t* dq, int64_t lddq,
+                                  int64_t strideDQ, uint16_t* dk, int64_t lddk, int64_t strideDK, uint16_t* dv, int64_t lddv,
+                                  int64_t strideDV, void* workspace, size_t workspace_bytes, int32_t group,
+                                  const int32_t* q_lens, const int32_t* k_lens, int32_t lens_count, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in
  * bfloat16 / float16 (T, 2-byte bit patterns) with A given as the kept 64 × 64 blocks of a CSR block list, shared by
  * every item of the batch, and the sampled product on the same list:

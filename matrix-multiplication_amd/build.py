@@ -42,6 +42,7 @@ def ext_path() -> Path:
 
 
 def _run(cmd, verbose):
+    """Runs a build step; returns what it wrote to stderr (warnings, remarks)."""
     if verbose:
         print("+", " ".join(shlex.quote(str(c)) for c in cmd), flush=True)
     proc = subprocess.run([str(c) for c in cmd], capture_output=True, text=True)
@@ -51,6 +52,32 @@ def _run(cmd, verbose):
         raise RuntimeError("build step failed: " + " ".join(str(c) for c in cmd))
     if verbose and proc.stderr.strip():
         sys.stderr.write(proc.stderr)
+    return proc.stderr
+
+
+# Units whose kernels sit at the edge of the register file: compiled with the compiler's resource-usage remarks, which are
+# kept as build/<unit>.resources.txt (one line per kernel instantiation); a vector-register spill fails the build.
+RESOURCE_REPORTS = ("block_attention",)
+_RESOURCE_FIELDS = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill", "LDS Size [bytes/block]",
+                    "Occupancy [waves/SIMD]")
+
+
+def resource_report(remarks: str):
+    """[(mangled kernel name, {field: value})] of -Rpass-analysis=kernel-resource-usage output."""
+    rows = []
+    for block in remarks.split("Function Name: ")[1:]:
+        name = block.split()[0]
+        rows.append((name, {f: int(re.search(re.escape(f) + r": (\d+)", block).group(1)) for f in _RESOURCE_FIELDS}))
+    return rows
+
+
+def _write_resource_report(src: Path, remarks: str):
+    rows = resource_report(remarks)
+    lines = [f"{name}  " + "  ".join(f"{f}: {v[f]}" for f in _RESOURCE_FIELDS) for name, v in sorted(rows)]
+    (OBJ_DIR / (src.stem + ".resources.txt")).write_text("\n".join(lines) + "\n")
+    spilled = [name for name, v in rows if v["VGPRs Spill"] > 0]
+    if not rows or spilled:
+        raise RuntimeError(f"{src.name}: " + ("no resource-usage remarks" if not rows else f"vector-register spills in {spilled}"))
 
 
 def _digest(paths, extra=""):
@@ -82,7 +109,10 @@ def build_library(force=False, verbose=False) -> Path:
         included = [CSRC / m for m in re.findall(r'#include "([\w.]+\.hip)"', src.read_text()) if (CSRC / m).exists()]
         digest = _digest([src, *included], hdr_digest)
         if force or _stale(obj, stamp, digest):
-            _run([HIPCC, *flags, "-c", src, "-o", obj], verbose)
+            if src.stem in RESOURCE_REPORTS:
+                _write_resource_report(src, _run([HIPCC, *flags, "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj], False))
+            else:
+                _run([HIPCC, *flags, "-c", src, "-o", obj], verbose)
             stamp.write_text(digest)
             return obj, True
         return obj, False

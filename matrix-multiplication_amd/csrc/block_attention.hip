@@ -15,6 +15,12 @@
 //    log-sum-exp; a key nobody sees zero rows of dk and dv.  A listed column outside [0, blocks) is skipped, offsets are
 //    clamped to the list: a malformed layout cannot make a kernel read outside the operands.
 //
+//  * Grouped-query heads and per-item lengths (the _ex entries — DESIGN.md §3.17): query item b reads k / v item b / group,
+//    and a key block sums dk, dv over its group's query items (g ascending, each over its own transposed list) in the same
+//    accumulators.  With lengths (LENS, a compile-time form: a call without them runs kernels without any of it) a
+//    position at or beyond its item's length does not exist: blocks wholly beyond are skipped, rows beyond are staged as
+//    zeros and never enter an MFMA, scores / probabilities are masked by position, their outputs are zero rows.
+//
 // Kernels: a 256-thread workgroup owns one 64-row block of one item; wave w its rows 16w … 16w + 15 ("own" rows), held
 // as MFMA B fragments in registers for the whole walk.  Each listed block of the other side ("walk" rows, 64 of them)
 // is staged through registers into LDS (the global loads of the next block are in flight while this one is computed):
@@ -66,7 +72,19 @@ struct Args {
   Dense q, k, v, o, dout, dq, dk, dv;
   float* lse;    // [batch][Sq]
   float* delta;  // [batch][Sq]
+  int group;     // query items per k / v item: query item b reads (and dk, dv sum into) k / v item b / group
+  int lens_div;  // query items per length entry: query item b has lengths q_lens[b / lens_div], k_lens[b / lens_div]
+  const int32_t* q_lens;  // [batch / lens_div] or null (every query position exists); clamped to [0, Sq] where read
+  const int32_t* k_lens;  // [batch / lens_div] or null; clamped to [0, Sk]
 };
+
+// the length of an item on a side of `rows` positions, clamped to [0, rows]; without LENS (or without the array) `rows`
+template <bool LENS>
+__device__ __forceinline__ int length_of(const int32_t* lens, int entry, long rows) {
+  if (!LENS || lens == nullptr) return (int)rows;
+  const int n = lens[entry];
+  return n < 0 ? 0 : n > rows ? (int)rows : n;
+}
 
 __device__ __forceinline__ unsigned half_of(uint4 v, int i) {
   const unsigned w = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
@@ -77,11 +95,18 @@ __device__ __forceinline__ unsigned half_of(uint4 v, int i) {
 template <int D>
 struct Tile {
   uint4 v[4];
-  __device__ __forceinline__ void load(const uint16_t* src, long ld, int tid) {
+  // LIMIT: rows at or beyond `limit` (the part of the block beyond an item's length) are zero rows, whatever memory holds
+  template <bool LIMIT>
+  __device__ __forceinline__ void load(const uint16_t* src, long ld, int tid, int limit) {
     if (tid < 2 * D) {
       const uint16_t* p = src + (long)(4 * (tid & 15)) * ld + 8 * (tid >> 4);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const uint4*>(p + i * ld);
+      for (int i = 0; i < 4; ++i) {
+        if (!LIMIT || 4 * (tid & 15) + i < limit)
+          v[i] = *reinterpret_cast<const uint4*>(p + i * ld);
+        else
+          v[i] = uint4{0u, 0u, 0u, 0u};
+      }
     }
   }
   // the row image [64][D + 8]
@@ -108,6 +133,11 @@ template <int D>
 __device__ __forceinline__ void load_own(uint4 (&f)[D / 32], const uint16_t* rows, long ld, int li, int lg) {
 #pragma unroll
   for (int s = 0; s < D / 32; ++s) f[s] = *reinterpret_cast<const uint4*>(rows + (long)li * ld + 32 * s + 8 * lg);
+}
+template <int D>
+__device__ __forceinline__ void zero_own(uint4 (&f)[D / 32]) {
+#pragma unroll
+  for (int s = 0; s < D / 32; ++s) f[s] = uint4{0u, 0u, 0u, 0u};
 }
 
 // acc[f][r] = ⟨walk row 16f + 4lg + r, own row li⟩ over d, from the row image R of the walk block
@@ -157,8 +187,21 @@ __device__ __forceinline__ void store_own(const f32x4 (&acc)[D / 16], float mul,
   }
 }
 
+// own row li, columns 16fd + 4lg … + 3: zeros
+template <int D>
+__device__ __forceinline__ void store_zero(uint16_t* rows, long ld, int li, int lg) {
+#pragma unroll
+  for (int fd = 0; fd < D / 16; ++fd) *reinterpret_cast<uint2*>(rows + (long)li * ld + 16 * fd + 4 * lg) = uint2{0u, 0u};
+}
+template <int D>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[D / 16]) {
+#pragma unroll
+  for (int fd = 0; fd < D / 16; ++fd) acc[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 // the next listed block at or after p that is computed: inside the grid and, causal, not beyond the own block's diagonal.
 // own_first: the own side is the query side (skip walk blocks J > I); else the key side (skip walk blocks I < J).
+// walk_blocks is the grid cut to the walk side's length: a block wholly beyond it is skipped like one outside the list.
 template <bool CAUSAL, bool OWN_IS_QUERY>
 __device__ __forceinline__ int next_block(const int32_t* col, int p, int end, int own_block, int walk_blocks) {
   for (; p < end; ++p) {
@@ -192,7 +235,7 @@ __device__ __forceinline__ Walk walk_of(const Args& a, int item, int own_block) 
   return Walk{a.col, (int)beg, (int)end};
 }
 
-template <class T, int D, bool CAUSAL>
+template <class T, int D, bool CAUSAL, bool LENS>
 __global__ __launch_bounds__(256) void block_attention_fwd_kernel(Args a) {
   __shared__ __attribute__((aligned(16))) unsigned short Ks[kB * (D + 8)];
   __shared__ __attribute__((aligned(16))) unsigned short Vt[D * kTStr];
@@ -200,21 +243,32 @@ __global__ __launch_bounds__(256) void block_attention_fwd_kernel(Args a) {
   const int I = blockIdx.x;
   for (int b = blockIdx.y; b < a.batch; b += gridDim.y) {
     const Walk wk = walk_of(a, b, I);
-    const uint16_t* K = a.k.p + (long)b * a.k.stride;
-    const uint16_t* V = a.v.p + (long)b * a.v.stride;
+    const int c = b / a.group;
+    const uint16_t* K = a.k.p + (long)c * a.k.stride;
+    const uint16_t* V = a.v.p + (long)c * a.v.stride;
     const long row0 = (long)I * kB + 16 * w;
+    uint16_t* orows = a.o.p + (long)b * a.o.stride + row0 * a.o.ld;
+    const int qlen = length_of<LENS>(a.q_lens, b / a.lens_div, a.own_rows);
+    const int klen = length_of<LENS>(a.k_lens, b / a.lens_div, a.walk_rows);
+    const int kblocks = LENS ? (klen + kB - 1) / kB : a.walk_blocks;
+    if (LENS && (long)I * kB >= qlen) {  // the whole block is beyond the item's length
+      store_zero<D>(orows, a.o.ld, li, lg);
+      if (lg == 0) a.lse[(long)b * a.own_rows + row0 + li] = -INFINITY;
+      continue;
+    }
+    const bool dead = LENS && row0 + li >= qlen;  // an own row beyond the length: never an MFMA operand
     uint4 qf[D / 32];
     load_own<D>(qf, a.q.p + (long)b * a.q.stride + row0 * a.q.ld, a.q.ld, li, lg);
+    if (dead) zero_own<D>(qf);
     f32x4 o[D / 16];
-#pragma unroll
-    for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc<D>(o);
     float m = -INFINITY, l = 0.f;
 
     Tile<D> tk, tv;
-    int p = next_block<CAUSAL, true>(wk.col, wk.beg, wk.end, I, a.walk_blocks);
+    int p = next_block<CAUSAL, true>(wk.col, wk.beg, wk.end, I, kblocks);
     if (p < wk.end) {
-      tk.load(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid);
-      tv.load(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid);
+      tk.template load<LENS>(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid, klen - wk.col[p] * kB);
+      tv.template load<LENS>(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid, klen - wk.col[p] * kB);
     }
     while (p < wk.end) {
       const int J = wk.col[p];
@@ -222,11 +276,12 @@ __global__ __launch_bounds__(256) void block_attention_fwd_kernel(Args a) {
       tk.store_rows(Ks, tid);
       tv.store_transposed(Vt, tid);
       __syncthreads();
-      p = next_block<CAUSAL, true>(wk.col, p + 1, wk.end, I, a.walk_blocks);
+      p = next_block<CAUSAL, true>(wk.col, p + 1, wk.end, I, kblocks);
       if (p < wk.end) {
-        tk.load(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid);
-        tv.load(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid);
+        tk.template load<LENS>(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid, klen - wk.col[p] * kB);
+        tv.template load<LENS>(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid, klen - wk.col[p] * kB);
       }
+      const int kleft = klen - J * kB;  // keys of this block that exist
       f32x4 s[4];
       score<T, D>(s, Ks, qf, li, lg);
       float mt = -INFINITY;
@@ -236,6 +291,7 @@ __global__ __launch_bounds__(256) void block_attention_fwd_kernel(Args a) {
         for (int r = 0; r < 4; ++r) {
           float t = s[f][r] * a.scale;
           if (CAUSAL && J == I && 16 * f + 4 * lg + r > 16 * w + li) t = -INFINITY;
+          if (LENS && 16 * f + 4 * lg + r >= kleft) t = -INFINITY;
           s[f][r] = t;
           mt = fmaxf(mt, t);
         }
@@ -261,8 +317,12 @@ __global__ __launch_bounds__(256) void block_attention_fwd_kernel(Args a) {
       accumulate<T, D>(o, Vt, pb, li, lg);
     }
     l = group_sum(l);
+    if (dead) {
+      l = 0.f;
+      zero_acc<D>(o);
+    }
     const float inv = l == 0.f ? 0.f : 1.f / l;
-    store_own<T, D>(o, inv, a.o.p + (long)b * a.o.stride + row0 * a.o.ld, a.o.ld, li, lg);
+    store_own<T, D>(o, inv, orows, a.o.ld, li, lg);
     if (lg == 0) a.lse[(long)b * a.own_rows + row0 + li] = l == 0.f ? -INFINITY : m + __logf(l);
     __syncthreads();  // the next item restages
   }
@@ -273,8 +333,8 @@ __device__ __forceinline__ float prob(float t, float lse) {
   return (lse == -INFINITY || t == -INFINITY) ? 0.f : __expf(t - lse);
 }
 
-// dQ over the layout; own = q and dO.  Also writes δ = rowsum(dO ∘ O) of its rows.
-template <class T, int D, bool CAUSAL>
+// dQ over the layout; own = q and dO.  Also writes δ = rowsum(dO ∘ O) of its rows (0 for a row beyond the length).
+template <class T, int D, bool CAUSAL, bool LENS>
 __global__ __launch_bounds__(256) void block_attention_dq_kernel(Args a) {
   __shared__ __attribute__((aligned(16))) unsigned short Ks[kB * (D + 8)];
   __shared__ __attribute__((aligned(16))) unsigned short Vs[kB * (D + 8)];
@@ -283,30 +343,46 @@ __global__ __launch_bounds__(256) void block_attention_dq_kernel(Args a) {
   const int I = blockIdx.x;
   for (int b = blockIdx.y; b < a.batch; b += gridDim.y) {
     const Walk wk = walk_of(a, b, I);
-    const uint16_t* K = a.k.p + (long)b * a.k.stride;
-    const uint16_t* V = a.v.p + (long)b * a.v.stride;
+    const int c = b / a.group;
+    const uint16_t* K = a.k.p + (long)c * a.k.stride;
+    const uint16_t* V = a.v.p + (long)c * a.v.stride;
     const long row0 = (long)I * kB + 16 * w;
+    uint16_t* dqrows = a.dq.p + (long)b * a.dq.stride + row0 * a.dq.ld;
+    const int qlen = length_of<LENS>(a.q_lens, b / a.lens_div, a.own_rows);
+    const int klen = length_of<LENS>(a.k_lens, b / a.lens_div, a.walk_rows);
+    const int kblocks = LENS ? (klen + kB - 1) / kB : a.walk_blocks;
+    if (LENS && (long)I * kB >= qlen) {  // the whole block is beyond the item's length
+      store_zero<D>(dqrows, a.dq.ld, li, lg);
+      if (lg == 0) a.delta[(long)b * a.own_rows + row0 + li] = 0.f;
+      continue;
+    }
+    const bool dead = LENS && row0 + li >= qlen;
     uint4 qf[D / 32], gf[D / 32], of[D / 32];
     load_own<D>(qf, a.q.p + (long)b * a.q.stride + row0 * a.q.ld, a.q.ld, li, lg);
     load_own<D>(gf, a.dout.p + (long)b * a.dout.stride + row0 * a.dout.ld, a.dout.ld, li, lg);
     load_own<D>(of, a.o.p + (long)b * a.o.stride + row0 * a.o.ld, a.o.ld, li, lg);
+    if (dead) {
+      zero_own<D>(qf);
+      zero_own<D>(gf);
+      zero_own<D>(of);
+    }
     float delta = 0.f;
 #pragma unroll
     for (int s = 0; s < D / 32; ++s)
 #pragma unroll
       for (int e = 0; e < 8; ++e) delta = fmaf(up<T>((unsigned short)half_of(gf[s], e)), up<T>((unsigned short)half_of(of[s], e)), delta);
     delta = group_sum(delta);
-    const float lse = a.lse[(long)b * a.own_rows + row0 + li];
+    float lse = a.lse[(long)b * a.own_rows + row0 + li];
+    if (dead) lse = -INFINITY;
     if (lg == 0) a.delta[(long)b * a.own_rows + row0 + li] = delta;
     f32x4 dq[D / 16];
-#pragma unroll
-    for (int fd = 0; fd < D / 16; ++fd) dq[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc<D>(dq);
 
     Tile<D> tk, tv;
-    int p = next_block<CAUSAL, true>(wk.col, wk.beg, wk.end, I, a.walk_blocks);
+    int p = next_block<CAUSAL, true>(wk.col, wk.beg, wk.end, I, kblocks);
     if (p < wk.end) {
-      tk.load(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid);
-      tv.load(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid);
+      tk.template load<LENS>(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid, klen - wk.col[p] * kB);
+      tv.template load<LENS>(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid, klen - wk.col[p] * kB);
     }
     while (p < wk.end) {
       const int J = wk.col[p];
@@ -315,11 +391,12 @@ __global__ __launch_bounds__(256) void block_attention_dq_kernel(Args a) {
       tk.store_transposed(Kt, tid);
       tv.store_rows(Vs, tid);
       __syncthreads();
-      p = next_block<CAUSAL, true>(wk.col, p + 1, wk.end, I, a.walk_blocks);
+      p = next_block<CAUSAL, true>(wk.col, p + 1, wk.end, I, kblocks);
       if (p < wk.end) {
-        tk.load(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid);
-        tv.load(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid);
+        tk.template load<LENS>(K + (long)wk.col[p] * kB * a.k.ld, a.k.ld, tid, klen - wk.col[p] * kB);
+        tv.template load<LENS>(V + (long)wk.col[p] * kB * a.v.ld, a.v.ld, tid, klen - wk.col[p] * kB);
       }
+      const int kleft = klen - J * kB;
       f32x4 s[4], dp[4];
       score<T, D>(s, Ks, qf, li, lg);
       score<T, D>(dp, Vs, gf, li, lg);
@@ -329,20 +406,37 @@ __global__ __launch_bounds__(256) void block_attention_dq_kernel(Args a) {
         for (int r = 0; r < 4; ++r) {
           float t = s[f][r] * a.scale;
           if (CAUSAL && J == I && 16 * f + 4 * lg + r > 16 * w + li) t = -INFINITY;
-          const float pr = prob(t, lse);
-          s[f][r] = pr == 0.f ? 0.f : pr * (dp[f][r] - delta);
+          float pr = prob(t, lse);
+          if (LENS && 16 * f + 4 * lg + r >= kleft) pr = 0.f;  // (the probability, not the score: the arithmetic above is
+          s[f][r] = pr == 0.f ? 0.f : pr * (dp[f][r] - delta);  //  the no-lengths form's, operation for operation)
         }
       uint4 db[2];
       pack_tile<T>(db, s);
       accumulate<T, D>(dq, Kt, db, li, lg);
     }
-    store_own<T, D>(dq, a.scale, a.dq.p + (long)b * a.dq.stride + row0 * a.dq.ld, a.dq.ld, li, lg);
+    if (dead) zero_acc<D>(dq);
+    store_own<T, D>(dq, a.scale, dqrows, a.dq.ld, li, lg);
     __syncthreads();
   }
 }
 
-// dK and dV over the transposed layout; own = k and v (a.rowptr / a.col are the transposed list, own_* the key side).
-template <class T, int D, bool CAUSAL>
+// The walk of a key block over the query heads of its group: (g, p) is entry p of the transposed list of query item
+// c · group + g, `end` that list's end.  Moves (g, p) to the next computed block at or after it, over the boundary between
+// two heads' lists; p == end afterwards (with g == group − 1): the walk is over.
+template <bool CAUSAL>
+__device__ __forceinline__ void next_walk(const Args& a, int c, int J, int qblocks, int& g, int& p, int& end) {
+  for (;;) {
+    p = next_block<CAUSAL, false>(a.col, p, end, J, qblocks);
+    if (p < end || g + 1 >= a.group) return;
+    ++g;
+    const Walk wk = walk_of(a, c * a.group + g, J);
+    p = wk.beg, end = wk.end;
+  }
+}
+
+// dK and dV over the transposed layout; own = k and v (a.rowptr / a.col are the transposed list, own_* the key side) of
+// k / v item c, summed over the group's query items c · group + g, g ascending, each over its own transposed list.
+template <class T, int D, bool CAUSAL, bool LENS>
 __global__ __launch_bounds__(256) void block_attention_dkv_kernel(Args a) {
   __shared__ __attribute__((aligned(16))) unsigned short Qs[kB * (D + 8)];
   __shared__ __attribute__((aligned(16))) unsigned short Gs[kB * (D + 8)];
@@ -350,51 +444,76 @@ __global__ __launch_bounds__(256) void block_attention_dkv_kernel(Args a) {
   __shared__ __attribute__((aligned(16))) unsigned short Gt[D * kTStr];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
   const int J = blockIdx.x;
-  for (int b = blockIdx.y; b < a.batch; b += gridDim.y) {
-    const Walk wk = walk_of(a, b, J);
-    const uint16_t* Q = a.q.p + (long)b * a.q.stride;
-    const uint16_t* G = a.dout.p + (long)b * a.dout.stride;
-    const float* lse = a.lse + (long)b * a.walk_rows;
-    const float* delta = a.delta + (long)b * a.walk_rows;
+  const int items = a.batch / a.group;
+  for (int c = blockIdx.y; c < items; c += gridDim.y) {
     const long row0 = (long)J * kB + 16 * w;
+    uint16_t* dkrows = a.dk.p + (long)c * a.dk.stride + row0 * a.dk.ld;
+    uint16_t* dvrows = a.dv.p + (long)c * a.dv.stride + row0 * a.dv.ld;
+    const int entry = (c * a.group) / a.lens_div;  // the heads of a group share one length
+    const int qlen = length_of<LENS>(a.q_lens, entry, a.walk_rows);
+    const int klen = length_of<LENS>(a.k_lens, entry, a.own_rows);
+    const int qblocks = LENS ? (qlen + kB - 1) / kB : a.walk_blocks;
+    if (LENS && (long)J * kB >= klen) {  // the whole block is beyond the item's length
+      store_zero<D>(dvrows, a.dv.ld, li, lg);
+      store_zero<D>(dkrows, a.dk.ld, li, lg);
+      continue;
+    }
+    const bool dead = LENS && row0 + li >= klen;
     uint4 kf[D / 32], vf[D / 32];
-    load_own<D>(kf, a.k.p + (long)b * a.k.stride + row0 * a.k.ld, a.k.ld, li, lg);
-    load_own<D>(vf, a.v.p + (long)b * a.v.stride + row0 * a.v.ld, a.v.ld, li, lg);
+    load_own<D>(kf, a.k.p + (long)c * a.k.stride + row0 * a.k.ld, a.k.ld, li, lg);
+    load_own<D>(vf, a.v.p + (long)c * a.v.stride + row0 * a.v.ld, a.v.ld, li, lg);
+    if (dead) {
+      zero_own<D>(kf);
+      zero_own<D>(vf);
+    }
     f32x4 dk[D / 16], dv[D / 16];
-#pragma unroll
-    for (int fd = 0; fd < D / 16; ++fd) dk[fd] = dv[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc<D>(dk);
+    zero_acc<D>(dv);
 
     Tile<D> tq, tg;
-    int p = next_block<CAUSAL, false>(wk.col, wk.beg, wk.end, J, a.walk_blocks);
-    if (p < wk.end) {
-      tq.load(Q + (long)wk.col[p] * kB * a.q.ld, a.q.ld, tid);
-      tg.load(G + (long)wk.col[p] * kB * a.dout.ld, a.dout.ld, tid);
+    int g = 0, p, end;
+    {
+      const Walk wk = walk_of(a, c * a.group, J);
+      p = wk.beg, end = wk.end;
     }
-    while (p < wk.end) {
-      const int I = wk.col[p];
+    next_walk<CAUSAL>(a, c, J, qblocks, g, p, end);
+    if (p < end) {
+      const long b = (long)c * a.group + g;
+      tq.template load<LENS>(a.q.p + b * a.q.stride + (long)a.col[p] * kB * a.q.ld, a.q.ld, tid, qlen - a.col[p] * kB);
+      tg.template load<LENS>(a.dout.p + b * a.dout.stride + (long)a.col[p] * kB * a.dout.ld, a.dout.ld, tid, qlen - a.col[p] * kB);
+    }
+    while (p < end) {
+      const int I = a.col[p];
+      const long bq = (long)c * a.group + g;  // the query item of this tile
       __syncthreads();
       tq.store_rows(Qs, tid);
       tq.store_transposed(Qt, tid);
       tg.store_rows(Gs, tid);
       tg.store_transposed(Gt, tid);
       __syncthreads();
-      p = next_block<CAUSAL, false>(wk.col, p + 1, wk.end, J, a.walk_blocks);
-      if (p < wk.end) {
-        tq.load(Q + (long)wk.col[p] * kB * a.q.ld, a.q.ld, tid);
-        tg.load(G + (long)wk.col[p] * kB * a.dout.ld, a.dout.ld, tid);
+      ++p;
+      next_walk<CAUSAL>(a, c, J, qblocks, g, p, end);
+      if (p < end) {  // the next tile's loads are in flight, across the boundary between two heads' lists too
+        const long b = (long)c * a.group + g;
+        tq.template load<LENS>(a.q.p + b * a.q.stride + (long)a.col[p] * kB * a.q.ld, a.q.ld, tid, qlen - a.col[p] * kB);
+        tg.template load<LENS>(a.dout.p + b * a.dout.stride + (long)a.col[p] * kB * a.dout.ld, a.dout.ld, tid, qlen - a.col[p] * kB);
       }
+      const float* lse = a.lse + bq * a.walk_rows + (long)I * kB;
+      const float* delta = a.delta + bq * a.walk_rows + (long)I * kB;
+      const int qleft = qlen - I * kB;  // queries of this block that exist
       f32x4 s[4], dp[4];
       score<T, D>(s, Qs, kf, li, lg);   // s[f][r]: query 16f + 4lg + r of block I against key li of the wave
       score<T, D>(dp, Gs, vf, li, lg);
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
-        const f32x4 ls = *reinterpret_cast<const f32x4*>(lse + (long)I * kB + 16 * f + 4 * lg);
-        const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + (long)I * kB + 16 * f + 4 * lg);
+        const f32x4 ls = *reinterpret_cast<const f32x4*>(lse + 16 * f + 4 * lg);
+        const f32x4 dl = *reinterpret_cast<const f32x4*>(delta + 16 * f + 4 * lg);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float t = s[f][r] * a.scale;
           if (CAUSAL && I == J && 16 * w + li > 16 * f + 4 * lg + r) t = -INFINITY;
-          const float pr = prob(t, ls[r]);
+          float pr = prob(t, ls[r]);
+          if (LENS && (dead || 16 * f + 4 * lg + r >= qleft)) pr = 0.f;  // (the probability, not the score: as in dq)
           s[f][r] = pr;
           dp[f][r] = pr == 0.f ? 0.f : pr * (dp[f][r] - dl[r]);
         }
@@ -405,8 +524,12 @@ __global__ __launch_bounds__(256) void block_attention_dkv_kernel(Args a) {
       accumulate<T, D>(dv, Gt, pb, li, lg);
       accumulate<T, D>(dk, Qt, db, li, lg);
     }
-    store_own<T, D>(dv, 1.f, a.dv.p + (long)b * a.dv.stride + row0 * a.dv.ld, a.dv.ld, li, lg);
-    store_own<T, D>(dk, a.scale, a.dk.p + (long)b * a.dk.stride + row0 * a.dk.ld, a.dk.ld, li, lg);
+    if (dead) {
+      zero_acc<D>(dk);
+      zero_acc<D>(dv);
+    }
+    store_own<T, D>(dv, 1.f, dvrows, a.dv.ld, li, lg);
+    store_own<T, D>(dk, a.scale, dkrows, a.dk.ld, li, lg);
     __syncthreads();
   }
 }
@@ -433,30 +556,53 @@ int validate(int64_t nnz, int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk
   return MI_OK;
 }
 
+// group and lengths of the _ex entries, checked before any HIP call (batch > 0): the k / v items and the length entries
+// divide the query items, and the heads of a group share one length entry
+int validate_ex(int32_t batch, int32_t group, const int32_t* q_lens, const int32_t* k_lens, int32_t lens_count) {
+  if (group < 1 || batch % group != 0) return MI_EINVAL;
+  if (q_lens == nullptr && k_lens == nullptr) return MI_OK;
+  if (lens_count < 1 || batch % lens_count != 0 || (batch / lens_count) % group != 0) return MI_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(q_lens) & 3u) || (reinterpret_cast<uintptr_t>(k_lens) & 3u)) return MI_EINVAL;
+  return MI_OK;
+}
+
+void set_ex(Args& a, int32_t group, const int32_t* q_lens, const int32_t* k_lens, int32_t lens_count) {
+  const bool lens = q_lens != nullptr || k_lens != nullptr;
+  a.group = group, a.q_lens = q_lens, a.k_lens = k_lens, a.lens_div = lens ? a.batch / lens_count : a.batch;
+}
+
+// LENS is a compile-time form: a call without lengths runs kernels that hold no length arithmetic at all
+template <class T, int D, bool CAUSAL, bool LENS>
+int launch_fwd_form(const Args& a, hipStream_t s) {
+  const dim3 grid((unsigned)a.own_blocks, (unsigned)(a.batch < 65535 ? a.batch : 65535));
+  hipLaunchKernelGGL((block_attention_fwd_kernel<T, D, CAUSAL, LENS>), grid, dim3(256), 0, s, a);
+  return mi::check_launch();
+}
+
 template <class T, int D>
 int launch_fwd(const Args& a, bool causal, hipStream_t s) {
-  const dim3 grid((unsigned)a.own_blocks, (unsigned)(a.batch < 65535 ? a.batch : 65535));
-  if (causal)
-    hipLaunchKernelGGL((block_attention_fwd_kernel<T, D, true>), grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((block_attention_fwd_kernel<T, D, false>), grid, dim3(256), 0, s, a);
+  const bool lens = a.q_lens != nullptr || a.k_lens != nullptr;
+  if (causal) return lens ? launch_fwd_form<T, D, true, true>(a, s) : launch_fwd_form<T, D, true, false>(a, s);
+  return lens ? launch_fwd_form<T, D, false, true>(a, s) : launch_fwd_form<T, D, false, false>(a, s);
+}
+
+template <class T, int D, bool CAUSAL, bool LENS>
+int launch_bwd_form(const Args& aq, const Args& ak, hipStream_t s) {
+  const unsigned gy = (unsigned)(aq.batch < 65535 ? aq.batch : 65535);
+  hipLaunchKernelGGL((block_attention_dq_kernel<T, D, CAUSAL, LENS>), dim3((unsigned)aq.own_blocks, gy), dim3(256), 0, s, aq);
+  const int st = mi::check_launch();
+  if (st != MI_OK || ak.own_blocks == 0) return st;
+  const int items = ak.batch / ak.group;  // a workgroup owns a key block of a k / v item
+  const unsigned gk = (unsigned)(items < 65535 ? items : 65535);
+  hipLaunchKernelGGL((block_attention_dkv_kernel<T, D, CAUSAL, LENS>), dim3((unsigned)ak.own_blocks, gk), dim3(256), 0, s, ak);
   return mi::check_launch();
 }
 
 template <class T, int D>
 int launch_bwd(const Args& aq, const Args& ak, bool causal, hipStream_t s) {
-  const unsigned gy = (unsigned)(aq.batch < 65535 ? aq.batch : 65535);
-  if (causal)
-    hipLaunchKernelGGL((block_attention_dq_kernel<T, D, true>), dim3((unsigned)aq.own_blocks, gy), dim3(256), 0, s, aq);
-  else
-    hipLaunchKernelGGL((block_attention_dq_kernel<T, D, false>), dim3((unsigned)aq.own_blocks, gy), dim3(256), 0, s, aq);
-  const int st = mi::check_launch();
-  if (st != MI_OK || ak.own_blocks == 0) return st;
-  if (causal)
-    hipLaunchKernelGGL((block_attention_dkv_kernel<T, D, true>), dim3((unsigned)ak.own_blocks, gy), dim3(256), 0, s, ak);
-  else
-    hipLaunchKernelGGL((block_attention_dkv_kernel<T, D, false>), dim3((unsigned)ak.own_blocks, gy), dim3(256), 0, s, ak);
-  return mi::check_launch();
+  const bool lens = aq.q_lens != nullptr || aq.k_lens != nullptr;
+  if (causal) return lens ? launch_bwd_form<T, D, true, true>(aq, ak, s) : launch_bwd_form<T, D, true, false>(aq, ak, s);
+  return lens ? launch_bwd_form<T, D, false, true>(aq, ak, s) : launch_bwd_form<T, D, false, false>(aq, ak, s);
 }
 
 Dense dense(const uint16_t* p, int64_t ld, int64_t stride) { return Dense{const_cast<uint16_t*>(p), (long)ld, (long)stride}; }
@@ -465,10 +611,13 @@ template <class T>
 int forward_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk,
                   int32_t D, int32_t causal, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k, int64_t ldk,
                   int64_t strideK, const uint16_t* v, int64_t ldv, int64_t strideV, float scale, uint16_t* out, int64_t ldo,
-                  int64_t strideO, float* lse, hipStream_t s) {
+                  int64_t strideO, float* lse, int32_t group, const int32_t* q_lens, const int32_t* k_lens, int32_t lens_count,
+                  hipStream_t s) {
+  if (group < 1) return MI_EINVAL;
   bool empty;
   const int st = validate(nnz, layouts, batch, Sq, Sk, D, causal, &empty);
   if (st != MI_OK || empty) return st;
+  if (validate_ex(batch, group, q_lens, k_lens, lens_count) != MI_OK) return MI_EINVAL;
   if (!rowptr || !lse || (nnz > 0 && !col) || (reinterpret_cast<uintptr_t>(lse) & 3u)) return MI_EINVAL;
   if (!dense_ok(q, ldq, strideQ, D) || !dense_ok(out, ldo, strideO, D)) return MI_EINVAL;
   if (nnz > 0 && (!dense_ok(k, ldk, strideK, D) || !dense_ok(v, ldv, strideV, D))) return MI_EINVAL;
@@ -477,6 +626,7 @@ int forward_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_
   a.own_blocks = Sq / kB, a.walk_blocks = Sk / kB, a.own_rows = Sq, a.walk_rows = Sk, a.scale = scale;
   a.q = dense(q, ldq, strideQ), a.k = dense(k, ldk, strideK), a.v = dense(v, ldv, strideV), a.o = dense(out, ldo, strideO);
   a.lse = lse;
+  set_ex(a, group, q_lens, k_lens, lens_count);
   switch (D) {
     case 32: return launch_fwd<T, 32>(a, causal != 0, s);
     case 64: return launch_fwd<T, 64>(a, causal != 0, s);
@@ -492,10 +642,13 @@ int backward_entry(const int32_t* rowptr, const int32_t* col, const int32_t* t_r
                    int64_t strideV, const uint16_t* out, int64_t ldo, int64_t strideO, const uint16_t* dout, int64_t lddo,
                    int64_t strideDO, const float* lse, float scale, uint16_t* dq, int64_t lddq, int64_t strideDQ, uint16_t* dk,
                    int64_t lddk, int64_t strideDK, uint16_t* dv, int64_t lddv, int64_t strideDV, void* workspace,
-                   size_t workspace_bytes, hipStream_t s) {
+                   size_t workspace_bytes, int32_t group, const int32_t* q_lens, const int32_t* k_lens, int32_t lens_count,
+                   hipStream_t s) {
+  if (group < 1) return MI_EINVAL;
   bool empty;
   const int st = validate(nnz, layouts, batch, Sq, Sk, D, causal, &empty);
   if (st != MI_OK || empty) return st;
+  if (validate_ex(batch, group, q_lens, k_lens, lens_count) != MI_OK) return MI_EINVAL;
   if (!rowptr || !t_rowptr || !lse || (nnz > 0 && (!col || !t_col)) || !mi::aligned16(lse)) return MI_EINVAL;
   if (!dense_ok(q, ldq, strideQ, D) || !dense_ok(out, ldo, strideO, D) || !dense_ok(dout, lddo, strideDO, D) ||
       !dense_ok(dq, lddq, strideDQ, D))
@@ -512,6 +665,7 @@ int backward_entry(const int32_t* rowptr, const int32_t* col, const int32_t* t_r
   aq.dout = dense(dout, lddo, strideDO), aq.dq = dense(dq, lddq, strideDQ), aq.dk = dense(dk, lddk, strideDK);
   aq.dv = dense(dv, lddv, strideDV);
   aq.lse = const_cast<float*>(lse), aq.delta = static_cast<float*>(workspace);
+  set_ex(aq, group, q_lens, k_lens, lens_count);
   Args ak = aq;  // the key side owns: the transposed list, lse and δ indexed by the walk (query) rows
   ak.rowptr = t_rowptr, ak.col = t_col;
   ak.own_blocks = Sk / kB, ak.walk_blocks = Sq / kB, ak.own_rows = Sk, ak.walk_rows = Sq;
@@ -534,13 +688,19 @@ size_t mi_block_attention_workspace_bytes(int32_t batch, int32_t Sq) {
 #define MI_BLOCK_FWD_ARGS                                                                                                    \
   const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t batch, int32_t Sq, int32_t Sk, int32_t D,  \
       int32_t causal, const uint16_t *q, int64_t ldq, int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t strideK,      \
-      const uint16_t *v, int64_t ldv, int64_t strideV, float scale, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, \
-      mi_stream_t stream
+      const uint16_t *v, int64_t ldv, int64_t strideV, float scale, uint16_t *out, int64_t ldo, int64_t strideO, float *lse
 #define MI_BLOCK_FWD_PASS \
   rowptr, col, nnz, layouts, batch, Sq, Sk, D, causal, q, ldq, strideQ, k, ldk, strideK, v, ldv, strideV, scale, out, ldo, strideO, lse
 
-int mi_block_attention_fwd_bf16(MI_BLOCK_FWD_ARGS) { return forward_entry<Bf16>(MI_BLOCK_FWD_PASS, static_cast<hipStream_t>(stream)); }
-int mi_block_attention_fwd_f16(MI_BLOCK_FWD_ARGS) { return forward_entry<F16>(MI_BLOCK_FWD_PASS, static_cast<hipStream_t>(stream)); }
+// the plain entries are the group = 1, no-lengths case of the _ex ones
+#define MI_BLOCK_PLAIN 1, nullptr, nullptr, 0, static_cast<hipStream_t>(stream)
+#define MI_BLOCK_EX group, q_lens, k_lens, lens_count, static_cast<hipStream_t>(stream)
+#define MI_BLOCK_EX_ARGS int32_t group, const int32_t *q_lens, const int32_t *k_lens, int32_t lens_count, mi_stream_t stream
+
+int mi_block_attention_fwd_bf16(MI_BLOCK_FWD_ARGS, mi_stream_t stream) { return forward_entry<Bf16>(MI_BLOCK_FWD_PASS, MI_BLOCK_PLAIN); }
+int mi_block_attention_fwd_f16(MI_BLOCK_FWD_ARGS, mi_stream_t stream) { return forward_entry<F16>(MI_BLOCK_FWD_PASS, MI_BLOCK_PLAIN); }
+int mi_block_attention_fwd_ex_bf16(MI_BLOCK_FWD_ARGS, MI_BLOCK_EX_ARGS) { return forward_entry<Bf16>(MI_BLOCK_FWD_PASS, MI_BLOCK_EX); }
+int mi_block_attention_fwd_ex_f16(MI_BLOCK_FWD_ARGS, MI_BLOCK_EX_ARGS) { return forward_entry<F16>(MI_BLOCK_FWD_PASS, MI_BLOCK_EX); }
 
 #define MI_BLOCK_BWD_ARGS                                                                                                      \
   const int32_t *rowptr, const int32_t *col, const int32_t *t_rowptr, const int32_t *t_col, int64_t nnz, int32_t layouts,       \
@@ -548,13 +708,15 @@ int mi_block_attention_fwd_f16(MI_BLOCK_FWD_ARGS) { return forward_entry<F16>(MI
       const uint16_t *k, int64_t ldk, int64_t strideK, const uint16_t *v, int64_t ldv, int64_t strideV, const uint16_t *out,   \
       int64_t ldo, int64_t strideO, const uint16_t *dout, int64_t lddo, int64_t strideDO, const float *lse, float scale,       \
       uint16_t *dq, int64_t lddq, int64_t strideDQ, uint16_t *dk, int64_t lddk, int64_t strideDK, uint16_t *dv, int64_t lddv, \
-      int64_t strideDV, void *workspace, size_t workspace_bytes, mi_stream_t stream
+      int64_t strideDV, void *workspace, size_t workspace_bytes
 #define MI_BLOCK_BWD_PASS                                                                                                       \
   rowptr, col, t_rowptr, t_col, nnz, layouts, batch, Sq, Sk, D, causal, q, ldq, strideQ, k, ldk, strideK, v, ldv, strideV, out, \
       ldo, strideO, dout, lddo, strideDO, lse, scale, dq, lddq, strideDQ, dk, lddk, strideDK, dv, lddv, strideDV, workspace,    \
       workspace_bytes
 
-int mi_block_attention_bwd_bf16(MI_BLOCK_BWD_ARGS) { return backward_entry<Bf16>(MI_BLOCK_BWD_PASS, static_cast<hipStream_t>(stream)); }
-int mi_block_attention_bwd_f16(MI_BLOCK_BWD_ARGS) { return backward_entry<F16>(MI_BLOCK_BWD_PASS, static_cast<hipStream_t>(stream)); }
+int mi_block_attention_bwd_bf16(MI_BLOCK_BWD_ARGS, mi_stream_t stream) { return backward_entry<Bf16>(MI_BLOCK_BWD_PASS, MI_BLOCK_PLAIN); }
+int mi_block_attention_bwd_f16(MI_BLOCK_BWD_ARGS, mi_stream_t stream) { return backward_entry<F16>(MI_BLOCK_BWD_PASS, MI_BLOCK_PLAIN); }
+int mi_block_attention_bwd_ex_bf16(MI_BLOCK_BWD_ARGS, MI_BLOCK_EX_ARGS) { return backward_entry<Bf16>(MI_BLOCK_BWD_PASS, MI_BLOCK_EX); }
+int mi_block_attention_bwd_ex_f16(MI_BLOCK_BWD_ARGS, MI_BLOCK_EX_ARGS) { return backward_entry<F16>(MI_BLOCK_BWD_PASS, MI_BLOCK_EX); }
 
 }  // extern "C"

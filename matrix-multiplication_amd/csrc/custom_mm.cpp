@@ -187,6 +187,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "out = softmax(scale * q k^T + block mask) v on the matrix cores, bfloat16 / float16");
   m.def("block_attention_backward", &block_attention_backward,
         "(offsets, columns, t_offsets, t_columns, nnz, q, k, v, out, dout, lse, scale, causal, dq, dk, dv): (dq, dk, dv)");
+  m.def("block_attention_forward_ex", &block_attention_forward_ex,
+        "(offsets, columns, nnz, q [batch, Sq, D], k, v [batch / group, Sk, D], scale, causal, out, lse, q_lens or None, k_lens or None): "
+        "block_attention_forward with grouped-query heads (query item i reads k / v item i / group) and per-item lengths (int32)");
+  m.def("block_attention_backward_ex", &block_attention_backward_ex,
+        "(offsets, columns, t_offsets, t_columns, nnz, q, k, v, out, dout, lse, scale, causal, dq, dk, dv, q_lens or None, "
+        "k_lens or None): (dq, dk, dv); dk, dv [batch / group, Sk, D] summed over the group in one accumulator");
   m.def("bsr_mm", &bsr_mm,
         "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
         "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");

@@ -95,3 +95,108 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> block_attention_backward
   check_status(st, what);
   return std::make_tuple(dq, dk, dv);
 }
+
+// ---- grouped-query heads and per-item lengths (include/mi_spmm.h, the _ex entries; DESIGN.md §3.17) ----------------------
+// q, out, dout, dq [batch, Sq, D] and lse [batch, Sq] count QUERY items; k, v, dk, dv [batch / group, Sk, D] with the group
+// inferred from the two batch sizes; q_lens / k_lens None or int32 device tensors of one count that divides batch / group.
+
+struct BlockLens {
+  const int32_t* q;
+  const int32_t* k;
+  int64_t count;
+};
+
+BlockLens block_lens(const char* what, const c10::optional<torch::Tensor>& q_lens, const c10::optional<torch::Tensor>& k_lens,
+                     int64_t batch, int64_t group, const torch::Device& dev) {
+  BlockLens r = {nullptr, nullptr, 0};
+  const std::pair<const char*, const c10::optional<torch::Tensor>*> both[] = {{"q_lens", &q_lens}, {"k_lens", &k_lens}};
+  for (const auto& [name, t] : both) {
+    if (!t->has_value() || !(*t)->defined()) continue;
+    check_device_i32(**t, name);
+    check_same_device(what, dev, {&**t});
+    TORCH_CHECK((*t)->is_contiguous() && (*t)->numel() > 0, what, ": ", name, " must be a contiguous, non-empty int32 tensor");
+    TORCH_CHECK(r.count == 0 || r.count == (*t)->numel(), what, ": q_lens and k_lens must have one count, got ", r.count, " and ",
+                (*t)->numel());
+    r.count = (*t)->numel();
+    (name[0] == 'q' ? r.q : r.k) = (*t)->data_ptr<int32_t>();
+  }
+  TORCH_CHECK(r.count == 0 || (batch % r.count == 0 && (batch / r.count) % group == 0), what, ": ", r.count,
+              " lengths do not divide ", batch, " query items in groups of ", group);
+  return r;
+}
+
+int64_t block_group(const char* what, const torch::Tensor& q, const torch::Tensor& k) {
+  TORCH_CHECK(q.dim() == 3 && k.dim() == 3, what, ": q must be [batch, Sq, D] and k [batch / group, Sk, D]");
+  TORCH_CHECK(k.size(0) > 0 ? q.size(0) % k.size(0) == 0 : q.size(0) == 0, what, ": ", q.size(0), " query items are not a multiple of ",
+              k.size(0), " k / v items");
+  return k.size(0) > 0 ? std::max<int64_t>(q.size(0) / k.size(0), 1) : 1;
+}
+
+torch::Tensor block_attention_forward_ex(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q, torch::Tensor k,
+                                         torch::Tensor v, double scale, bool causal, torch::Tensor out, torch::Tensor lse,
+                                         c10::optional<torch::Tensor> q_lens, c10::optional<torch::Tensor> k_lens) {
+  const char* what = "block_attention_forward_ex";
+  const torch::ScalarType dt = value_dtype(what, {{"q", &q}, {"k", &k}, {"v", &v}, {"out", &out}}, true);
+  const bool bf = is_lowp_dtype(what, dt);
+  const int64_t group = block_group(what, q, k);
+  const int64_t batch = q.size(0), Sq = q.size(1), D = q.size(2), Sk = k.size(1), items = k.size(0);
+  const BlockLayout lay = block_layout(what, offsets, columns, nnz, Sq, Sk);
+  check_same_device(what, lay.list.device, {&q, &k, &v, &out, &lse});
+  check_device_f32(lse, "lse");
+  check_attention_dense(what, "q", q, batch, Sq, D);
+  check_attention_dense(what, "k", k, items, Sk, D);
+  check_attention_dense(what, "v", v, items, Sk, D);
+  check_attention_dense(what, "out", out, batch, Sq, D);
+  TORCH_CHECK(lse.is_contiguous() && lse.numel() == batch * Sq, what, ": lse must be a contiguous [batch, Sq] tensor");
+  TORCH_CHECK(!causal || Sq == Sk, what, ": causal needs Sq == Sk, got ", Sq, " and ", Sk);
+  check_sizes(what, {batch, Sq, Sk, D});
+  const BlockLens lens = block_lens(what, q_lens, k_lens, batch, group, lay.list.device);
+  c10::hip::HIPGuard guard(out.device().index());
+  auto p = [](const torch::Tensor& t) { return static_cast<uint16_t*>(t.data_ptr()); };
+  const int st = (bf ? mi_block_attention_fwd_ex_bf16 : mi_block_attention_fwd_ex_f16)(
+      lay.list.offsets, lay.list.columns, nnz, (int32_t)lay.layouts, (int32_t)batch, (int32_t)Sq, (int32_t)Sk, (int32_t)D,
+      causal ? 1 : 0, p(q), D, Sq * D, p(k), D, Sk * D, p(v), D, Sk * D, (float)scale, p(out), D, Sq * D, lse.data_ptr<float>(),
+      (int32_t)group, lens.q, lens.k, (int32_t)lens.count, stream_of(out));
+  check_status(st, what);
+  return out;
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> block_attention_backward_ex(
+    torch::Tensor offsets, torch::Tensor columns, torch::Tensor t_offsets, torch::Tensor t_columns, int64_t nnz, torch::Tensor q,
+    torch::Tensor k, torch::Tensor v, torch::Tensor out, torch::Tensor dout, torch::Tensor lse, double scale, bool causal,
+    torch::Tensor dq, torch::Tensor dk, torch::Tensor dv, c10::optional<torch::Tensor> q_lens, c10::optional<torch::Tensor> k_lens) {
+  const char* what = "block_attention_backward_ex";
+  const torch::ScalarType dt = value_dtype(
+      what, {{"q", &q}, {"k", &k}, {"v", &v}, {"out", &out}, {"dout", &dout}, {"dq", &dq}, {"dk", &dk}, {"dv", &dv}}, true);
+  const bool bf = is_lowp_dtype(what, dt);
+  const int64_t group = block_group(what, q, k);
+  const int64_t batch = q.size(0), Sq = q.size(1), D = q.size(2), Sk = k.size(1), items = k.size(0);
+  const BlockLayout lay = block_layout(what, offsets, columns, nnz, Sq, Sk);
+  const BlockLayout tlay = block_layout(what, t_offsets, t_columns, nnz, Sk, Sq);
+  TORCH_CHECK(lay.layouts == tlay.layouts, what, ": the layouts and their transposes differ in number");
+  check_same_device(what, lay.list.device, {&t_offsets, &t_columns, &q, &k, &v, &out, &dout, &lse, &dq, &dk, &dv});
+  check_device_f32(lse, "lse");
+  check_attention_dense(what, "q", q, batch, Sq, D);
+  check_attention_dense(what, "k", k, items, Sk, D);
+  check_attention_dense(what, "v", v, items, Sk, D);
+  check_attention_dense(what, "out", out, batch, Sq, D);
+  check_attention_dense(what, "dout", dout, batch, Sq, D);
+  check_attention_dense(what, "dq", dq, batch, Sq, D);
+  check_attention_dense(what, "dk", dk, items, Sk, D);
+  check_attention_dense(what, "dv", dv, items, Sk, D);
+  TORCH_CHECK(lse.is_contiguous() && lse.numel() == batch * Sq, what, ": lse must be a contiguous [batch, Sq] tensor");
+  TORCH_CHECK(!causal || Sq == Sk, what, ": causal needs Sq == Sk, got ", Sq, " and ", Sk);
+  check_sizes(what, {batch, Sq, Sk, D});
+  const BlockLens lens = block_lens(what, q_lens, k_lens, batch, group, lay.list.device);
+  c10::hip::HIPGuard guard(dq.device().index());
+  const size_t ws_bytes = mi_block_attention_workspace_bytes((int32_t)batch, (int32_t)Sq);
+  torch::Tensor ws = byte_workspace(dq.device(), ws_bytes, 16);
+  auto p = [](const torch::Tensor& t) { return static_cast<uint16_t*>(t.data_ptr()); };
+  const int st = (bf ? mi_block_attention_bwd_ex_bf16 : mi_block_attention_bwd_ex_f16)(
+      lay.list.offsets, lay.list.columns, tlay.list.offsets, tlay.list.columns, nnz, (int32_t)lay.layouts, (int32_t)batch,
+      (int32_t)Sq, (int32_t)Sk, (int32_t)D, causal ? 1 : 0, p(q), D, Sq * D, p(k), D, Sk * D, p(v), D, Sk * D, p(out), D, Sq * D,
+      p(dout), D, Sq * D, lse.data_ptr<float>(), (float)scale, p(dq), D, Sq * D, p(dk), D, Sk * D, p(dv), D, Sk * D, ws.data_ptr(),
+      ws_bytes, (int32_t)group, lens.q, lens.k, (int32_t)lens.count, stream_of(dq));
+  check_status(st, what);
+  return std::make_tuple(dq, dk, dv);
+}

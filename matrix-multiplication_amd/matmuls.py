@@ -1642,9 +1642,82 @@ class blockSparseAttention(InplaceFunction):
                 dv.reshape(v.shape) if need[2] else None, None, None, None, None)
 
 
-def _check_block_attention_operands(what, q, k, v, layout, block, causal):
+class blockSparseAttentionGrouped(InplaceFunction):
+    '''blockSparseAttention with grouped-query heads and per-item lengths (custom_mm.block_attention_forward_ex /
+    block_attention_backward_ex): k and v have one item per `group` query items, q_lens / k_lens are None
+    or contiguous int32 device tensors of one count.  Saves what blockSparseAttention saves plus the two length tensors —
+    nothing of size Sq × Sk, nothing per kept block.  dk and dv come back in k's shape: the group's sum is taken inside
+    the key-block kernel, in one accumulator.'''
+
+    @staticmethod
+    def forward(ctx, q, k, v, layout, f, scale, causal, q_lens, k_lens):
+        rec = _block_layout(layout, q.device, f, _csr_state(layout))
+        offsets, columns, nnz, _ = rec['fwd']
+        Sq, Sk, D = q.shape[-2], k.shape[-2], q.shape[-1]
+        q3, k3, v3 = q.reshape(-1, Sq, D).contiguous(), k.reshape(-1, Sk, D).contiguous(), v.reshape(-1, Sk, D).contiguous()
+        out = torch.empty_like(q3)
+        lse = torch.empty((q3.shape[0], Sq), device=q.device, dtype=torch.float32)
+        if out.numel() > 0:
+            custom_mm.block_attention_forward_ex(offsets, columns, nnz, q3, k3, v3, float(scale), bool(causal), out, lse,
+                                                 q_lens, k_lens)
+        ctx.block_args = (f, float(scale), bool(causal), q_lens is not None, k_lens is not None)
+        ctx.save_for_backward(q, k, v, layout, out, lse, *(t for t in (q_lens, k_lens) if t is not None))
+        return out.reshape(q.shape)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        q, k, v, layout, out, lse, *lens = ctx.saved_tensors
+        f, scale, causal, has_q, has_k = ctx.block_args
+        q_lens = lens.pop(0) if has_q else None
+        k_lens = lens.pop(0) if has_k else None
+        Sq, Sk, D = q.shape[-2], k.shape[-2], q.shape[-1]
+        q3, k3, v3 = q.reshape(-1, Sq, D).contiguous(), k.reshape(-1, Sk, D).contiguous(), v.reshape(-1, Sk, D).contiguous()
+        if out.numel() == 0:
+            dq, dk, dv = torch.zeros_like(q3), torch.zeros_like(k3), torch.zeros_like(v3)
+        else:
+            rec = _block_layout(layout, q.device, f, _csr_state(layout))
+            offsets, columns, nnz, _ = rec['fwd']
+            t_off, t_col = _block_layout_transposed(rec, Sq // _BLOCK_TILE, Sk // _BLOCK_TILE)
+            g3 = grad_output.to(q.dtype).reshape(-1, Sq, D).contiguous()
+            dq, dk, dv = torch.empty_like(q3), torch.empty_like(k3), torch.empty_like(v3)
+            custom_mm.block_attention_backward_ex(offsets, columns, t_off, t_col, nnz, q3, k3, v3, out, g3, lse, scale, causal,
+                                                  dq, dk, dv, q_lens, k_lens)
+        need = ctx.needs_input_grad
+        return (dq.reshape(q.shape) if need[0] else None, dk.reshape(k.shape) if need[1] else None,
+                dv.reshape(v.shape) if need[2] else None, None, None, None, None, None, None)
+
+
+def _check_block_lens(what, q_lens, k_lens, common):
+    '''The ValueErrors of block_sparse_attention's q_lens / k_lens: each None or a dense integer tensor whose shape is a
+    leading part of `common`, the lead dimensions q and k share.'''
+    for name, t in (('q_lens', q_lens), ('k_lens', k_lens)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be a dense tensor or None')
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f'{what}: {name} must be an int32 or int64 tensor, got {t.dtype}')
+        if tuple(t.shape) != common[:t.dim()]:
+            raise ValueError(f'{what}: {name} must have a shape that is a leading part of {common}, the lead dimensions q and k '
+                             f'share ([B] against q [B, H, S, D]), got {tuple(t.shape)}')
+
+
+def _block_lens(q_lens, k_lens, common):
+    '''(q_lens, k_lens) as the kernels read them: None, or contiguous int32 on the tensors\' own device, both of one count (the
+    shorter shape broadcast over the longer one's further dimensions).  torch ops on the device; nothing is read back.'''
+    dims = max(t.dim() for t in (q_lens, k_lens) if t is not None)
+    out = []
+    for t in (q_lens, k_lens):
+        if t is not None:
+            t = t.reshape(tuple(t.shape) + (1,) * (dims - t.dim())).expand(common[:dims]).to(torch.int32).contiguous().reshape(-1)
+        out.append(t)
+    return out
+
+
+def _check_block_attention_operands(what, q, k, v, layout, block, causal, q_lens=None, k_lens=None):
     '''Every refusal of block_sparse_attention, before the first device call: ValueError for what an operand is (layout,
-    dtype, sizes, shapes), RuntimeError for operands that do not go together (mixed dtypes, host tensors / devices).'''
+    dtype, sizes, shapes, lengths), RuntimeError for operands that do not go together (mixed dtypes, host tensors / devices).
+    Returns the group: query heads per k / v head.'''
     _check_csr(what, 'layout', layout)
     for name, t in (('q', q), ('k', k), ('v', v)):
         if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
@@ -1663,8 +1736,13 @@ def _check_block_attention_operands(what, q, k, v, layout, block, causal):
     if D not in _BLOCK_HEAD_SIZES:
         raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_BLOCK_SIZES_TEXT})')
     lead, Sq, Sk = tuple(q.shape[:-2]), q.shape[-2], k.shape[-2]
-    if tuple(k.shape[:-2]) != lead or k.shape[-1] != D:
-        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs k {lead + ("Sk", D)}, got {tuple(k.shape)}')
+    k_lead = tuple(k.shape[:-2])
+    grouped = len(lead) > 0 and k_lead[:-1] == lead[:-1] and k_lead[-1] > 0 and lead[-1] % k_lead[-1] == 0
+    if (k_lead != lead and not grouped) or k.shape[-1] != D:
+        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs k {lead + ("Sk", D)}' +
+                         (f' or, grouped, {lead[:-1] + ("Hkv", "Sk", D)} with Hkv a divisor of {lead[-1]}' if lead else '') +
+                         f', got {tuple(k.shape)}')
+    group = lead[-1] // k_lead[-1] if k_lead != lead else 1
     if tuple(v.shape) != tuple(k.shape):
         raise ValueError(f'{what}: v must be a dense tensor with k\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
     if Sq % block != 0 or Sk % block != 0:
@@ -1679,11 +1757,14 @@ def _check_block_attention_operands(what, q, k, v, layout, block, causal):
         raise ValueError(f'{what}: causal=True needs Sq == Sk, got {Sq} and {Sk}')
     if torch.Tensor.values(layout).numel() * (block // _BLOCK_TILE) ** 2 >= 2 ** 31:
         raise ValueError(f'{what}: the layout in 64-blocks does not fit int32 indices')
-    _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k=k, v=v)
+    _check_block_lens(what, q_lens, k_lens, lead if group == 1 else lead[:-1])
+    _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k=k, v=v,
+                     **{name: t for name, t in (('q_lens', q_lens), ('k_lens', k_lens)) if t is not None})
+    return group
 
 
 def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, block: int = 64, scale=None,
-                           causal: bool = False) -> torch.Tensor:
+                           causal: bool = False, *, q_lens=None, k_lens=None) -> torch.Tensor:
     '''out = softmax(scale · q·kᵀ + mask) · v on the matrix cores, the mask given in BLOCKS: q [*lead, Sq, D], k and v
     [*lead, Sk, D], dense device tensors, all bfloat16 or all float16; `layout` a CSR tensor [*l_lead, Sq/block, Sk/block]
     whose stored entry (I, J) lets query block I see key block J (values ignored, any dtype; int32 or int64 indices; columns
@@ -1699,11 +1780,30 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, la
     is by definition the bits of that expanded call.  Products on the MFMA with fp32 accumulators; scores, maxima, sums and
     the log-sum-exp in fp32; one rounding at the store.  Autograd keeps q, k, v, out and one float per query row, and
     recomputes P per tile; no atomics, no read-back; the bits of an output depend on its own item and layout only.
-    Differentiable in q, k and v.'''
-    _check_block_attention_operands('block_sparse_attention', q, k, v, layout, block, causal)
+    Differentiable in q, k and v.
+
+    Grouped-query heads: k and v may be [*lead[:-1], Hkv, Sk, D] against q [*lead[:-1], Hq, Sq, D] with
+    Hq = G · Hkv; query head h reads k / v head h // G (torch SDPA's enable_gqa convention: the result is that of the call
+    on k.repeat_interleave(G, -3)), the layout is indexed by the QUERY item as before, and dk, dv have k's shape — the sum
+    over the group's G query heads (g ascending, each over its transposed list in its order) is taken in one accumulator
+    and rounded once.
+
+    Lengths: q_lens / k_lens are None or int32 / int64 device tensors whose shape is a leading part of the lead dimensions
+    q and k share ([B] against q [B, H, S, D]); they are narrowed to int32 on the device and never read back.  Query
+    position i of an item exists iff i < q_len, key position j iff j < k_len (a length is clamped to [0, S]).  The softmax
+    runs over the visible AND existing keys; a query row at or beyond q_len is a zero row of out and dq and adds nothing
+    to dk, dv; a key at or beyond k_len gets zero rows of dk, dv; a kept block wholly beyond a length is skipped; and
+    whatever the padding of q, k, v or the incoming gradient holds — NaN included — reaches no output.  Sq and Sk
+    themselves stay multiples of block.  With equal leads and no lengths this is exactly the call described above.'''
+    what = 'block_sparse_attention'
+    group = _check_block_attention_operands(what, q, k, v, layout, block, causal, q_lens, k_lens)
     if scale is None:
         scale = 1.0 / float(q.shape[-1]) ** 0.5
-    return blockSparseAttention.apply(q, k, v, layout, block // _BLOCK_TILE, float(scale), bool(causal))
+    if group == 1 and q_lens is None and k_lens is None:
+        return blockSparseAttention.apply(q, k, v, layout, block // _BLOCK_TILE, float(scale), bool(causal))
+    if q_lens is not None or k_lens is not None:
+        q_lens, k_lens = _block_lens(q_lens, k_lens, tuple(q.shape[:-2]) if group == 1 else tuple(q.shape[:-3]))
+    return blockSparseAttentionGrouped.apply(q, k, v, layout, block // _BLOCK_TILE, float(scale), bool(causal), q_lens, k_lens)
 
 
 # --------------------------------------------------------------------------- #
