@@ -9,7 +9,8 @@ store — the instruction and the order of this package's dense low-precision pr
   3. a long list (1, 2, 3, 40 kept blocks in one block row) within |C − E| ≤ u_T·|E| + k·2⁻²³·(|A|·|B|) (+ 2⁻²⁵ for fp16);
   4. invariance: batch position, the item-major flattening of d values, the checked alignment form, the order of the
      layout, repeated runs;
-  5. unkept blocks are never read; 6. graph capture; 7. memory.
+  5. unkept blocks are never read; 6. graph capture; 7. memory;
+  8. 65 538 items, exact as in 1: the second pass of bsr_mm's item loop behind the 65 535-item grid cap.
 """
 import pytest
 import torch
@@ -283,3 +284,28 @@ def test_7_nothing_of_size_m_by_k_is_allocated(mm, dev):
     # fixed 2 MiB workspace, alive beside `out` alone, exceeds the two gradients by — far below 1 MiB
     assert results <= peak <= results + (1 << 20), (peak, results)
     assert peak < (nb * B) ** 2 * 2
+
+
+# ---- 8. beyond 65 535 items -----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dtype", LOWP)
+def test_8_beyond_65535_items_is_exact(mm, dev, dtype):
+    """65 538 items of b [128, 8]: bsr_mm's grid holds 65 535 of them, the rest come in the second pass of its item loop
+    (forward and d b); d values sums over every item.  Operands in {−1, 0, 1}: the 524 304-term sums of d values stay exact
+    in fp32, so contract 1 holds — the float64 results (on the device: 0.54 GB per operand) narrowed to T, bit for bit."""
+    rows, cols, items, N = [[1], [0, 1]], 2, 65538, 8
+    layout = layout_from_rows(rows, cols, dev)
+    g = torch.Generator(device=dev).manual_seed(81)
+    draw = lambda *shape: torch.randint(-1, 2, shape, device=dev, generator=g).to(dtype)  # noqa: E731
+    values, b, w = draw(len(entries(rows)), B, B), draw(items, cols * B, N), draw(items, len(rows) * B, N)
+    got = step(mm, values, layout, b, w)
+    a = densify(values.double(), rows, cols)
+    b64, w64 = b.double(), w.double()
+    by_rows = lambda x: x.permute(1, 0, 2).reshape(x.shape[1], -1)  # noqa: E731  [rows, items · N]
+    by_items = lambda x: x.reshape(x.shape[0], items, N).permute(1, 0, 2).contiguous()  # noqa: E731  and back
+    b64, w64 = by_rows(b64), by_rows(w64)
+    want = (by_items(a @ b64) + 0.0, kept_blocks(w64 @ b64.T, rows) + 0.0, by_items(a.T @ w64) + 0.0)
+    for name, r, x in zip(NAMES, got, want):
+        assert r.shape == x.shape, name
+        assert torch.equal(r.view(torch.int16), x.to(dtype).view(torch.int16)), f"{dtype} {name} of {items} items"
+    assert got[1].abs().max() > 256  # sums long enough for the store's rounding to matter

@@ -3,7 +3,8 @@
 The contract (include/mi_spmm.h, mi_gemm_bf16 / _f16): fp32 sums, one rounding per element at the store, and one order
 for the whole family — the bits of C[i, j] depend on row i of op(A), column j of op(B), k and the dtype only.
   1. exact: integer operands in [−8, 8] keep every fp32 partial sum exact, so the product is (A·B in float64).to(T)
-     whatever the order inside the MFMA — bit for bit, in every transpose, batch and broadcast form;
+     whatever the order inside the MFMA — bit for bit, in every transpose, batch and broadcast form, and with 65 538 items
+     (the second pass of the item loops behind the 65 535-item grid cap, the k = 0 fill included);
   2. invariance: sub-products, batch position, storage transposes, unaligned views and repeated runs give the same bits;
   3. accuracy: |C − E| ≤ u_T·|E| + k·2⁻²³·(|A|·|B|) (+ 2⁻²⁵ for fp16) against the float64 product E;
   4. non-finite values; 5. autograd through the four dense classes; 6. graph capture.
@@ -111,6 +112,22 @@ def test_exact_batched_and_broadcast(cmm, dev, dtype):
         C = nan_c((2, bsz, m, n), dev, dtype)
         cmm.cublas_bmm(a4, b4, C, 4, False, True)
         assert_same_bits(C, exact(a4, b4, False, True, dtype), f"{dtype} 4-d")
+
+
+@pytest.mark.parametrize("dtype", LOWP)
+def test_exact_beyond_65535_items(cmm, dev, dtype):
+    '''65 538 items of 8 × 32 · 32 × 8: the grid holds 65 535 of them, the rest come in the second pass of the item loop of
+    gemm_lowp_kernel — plain and with A stored transposed — and, with k = 0, of fill_b16_kernel.'''
+    bsz, m, n, k = 65538, 8, 8, 32
+    a, b = ints((bsz, m, k), dev, dtype, 6), ints((bsz, k, n), dev, dtype, 7)
+    want = exact(a, b, False, False, dtype)
+    for a_op, ta, what in ((a, False, "plain"), (a.transpose(1, 2).contiguous(), True, "A stored transposed")):
+        C = nan_c((bsz, m, n), dev, dtype)
+        cmm.cublas_bmm(a_op, b, C, 3, ta, False)
+        assert_same_bits(C, want, f"{dtype} {bsz} items, {what}")
+    C = nan_c((bsz, m, n), dev, dtype)
+    cmm.cublas_bmm(a[:, :, :0], b[:, :0], C, 3, False, False)
+    assert_same_bits(C, torch.zeros_like(C), f"{dtype} {bsz} items, k = 0")
 
 
 def test_exact_rounding_edges(cmm, dev):
