@@ -302,12 +302,20 @@ class _CsrState:
       sched       {dense width: 'seen' | schedule} of A, and sched_t of Aᵀ (_row_schedule) — when the pattern changes;
       batched     (offsets, columns) of a batched tensor, narrowed for the device batched_dev (_batched_pattern), and
       batched_t   its transposed part (_batched_transposed) — when the pattern changes or another device asks for them;
+      block_layouts  {(device, f): record} of a block attention layout (_block_layout) and
+      bsr_layouts    {device: record} of a block product layout (_bsr_layout), each record the narrowed lists with their
+                  transposes — when the pattern changes; this tensor's own, never shared through _share_pattern;
       backwards   the number of batched backward passes of this tensor object — never.
     Values are never kept: Aᵀ's values are gathered through the permutation on every call (one pass over nnz), so a
     write to the values that no version counter sees (`a.values().data.mul_(3)`, a kernel writing through data_ptr)
     can never leave a stale copy behind.'''
-    key = props = transposed = sched = sched_t = batched = batched_dev = batched_t = None
+    key = props = transposed = sched = sched_t = batched = batched_dev = batched_t = block_layouts = bsr_layouts = None
     backwards = 0
+
+
+def _pattern_key(key):
+    '''The part of a _csr_key that names the pattern: the index tensors' storage and versions, the shape, nnz.'''
+    return key[1:3] + key[4:]
 
 
 def _csr_state(a: torch.Tensor) -> _CsrState:
@@ -321,9 +329,10 @@ def _csr_state(a: torch.Tensor) -> _CsrState:
         except (AttributeError, RuntimeError):
             pass  # a tensor type that takes no attributes: a record for this call only
     if st.key != key:
-        if st.key is None or st.key[1:3] + st.key[4:] != key[1:3] + key[4:]:  # a new pattern
+        if st.key is None or _pattern_key(st.key) != _pattern_key(key):  # a new pattern
             st.transposed = st.batched = st.batched_t = None
             st.sched, st.sched_t = {}, {}
+            st.block_layouts, st.bsr_layouts = {}, {}
         st.key, st.props = key, None
     return st
 
@@ -799,7 +808,6 @@ def _spmm_dispatch(a: torch.Tensor, b: torch.Tensor, mm_op, default_op, dense_ro
 
 # bfloat16 / float16: a 2-d CSR mat1 and a dense mat2 of the same dtype, summed in fp32 and rounded once per output element
 # (include/mi_spmm.h, low-precision section: the fp32 product of the widened operands with long rows split, narrowed)
-_LOWP = (torch.bfloat16, torch.float16)
 
 
 def _lowp_product(a: torch.Tensor, b: torch.Tensor, mm_op, default_op) -> torch.Tensor:
@@ -1133,10 +1141,11 @@ _PATTERN_FIELDS = ('transposed', 'sched', 'sched_t', 'batched', 'batched_dev', '
 class _SharedPatternState(_CsrState):
     '''The _CsrState of a CSR tensor built on ANOTHER tensor's index tensors: what is kept about the pattern lives in
     the owner's record (read and written through), so whichever of the tensors first needs the narrowed indices or the
-    transposed pattern builds them for all; key, props and the backward count are this tensor's own.'''
+    transposed pattern builds them for all; key, props, the backward count and the block lists are this tensor's own.'''
 
     def __init__(self, owner: _CsrState):
         self._owner = getattr(owner, '_owner', owner)
+        self.block_layouts, self.bsr_layouts = {}, {}  # (_share_pattern sets the key itself: _csr_state sees no new pattern)
 
 
 for _name in _PATTERN_FIELDS:
@@ -1550,12 +1559,7 @@ def _block_layout(layout: torch.Tensor, dev, f: int, st: _CsrState):
     '''What the block attention kernels read of a layout, kept in its _CsrState per (device, f) for as long as the pattern
     stays: {'fwd': (offsets int32 [L, Sq/64 + 1] with the layouts' bases, columns int32 [L·n], nnz, L), 't': None or the
     transposed lists (_block_layout_transposed)} — the layout expanded by f into 64-blocks and narrowed, once.'''
-    pat = st.key[1:3] + st.key[4:]
-    kept = getattr(st, 'block_layouts', None)
-    if kept is None or kept[0] != pat:
-        kept = (pat, {})
-        st.block_layouts = kept
-    rec = kept[1].get((str(dev), f))
+    rec = st.block_layouts.get((str(dev), f))
     if rec is None:
         nb = layout.shape[-2]
         crow = torch.Tensor.crow_indices(layout).reshape(-1, nb + 1).to(dev)
@@ -1565,7 +1569,7 @@ def _block_layout(layout: torch.Tensor, dev, f: int, st: _CsrState):
         base = torch.arange(L, device=crow.device, dtype=torch.int64).unsqueeze(1) * n
         rec = {'fwd': ((crow + base).to(torch.int32).contiguous(), col.reshape(-1).to(torch.int32).contiguous(), L * n, L),
                't': None}
-        kept[1][(str(dev), f)] = rec
+        st.block_layouts[(str(dev), f)] = rec
     return rec
 
 
@@ -1601,77 +1605,47 @@ def _block_layout_transposed(rec: dict, rows: int, cols: int):
     return rec['t']
 
 
+def _block_items(q, k, v):
+    '''q, k and v [*lead, S, D] as the kernels read them: contiguous [items, S, D].'''
+    return tuple(t.reshape(-1, t.shape[-2], t.shape[-1]).contiguous() for t in (q, k, v))
+
+
 class blockSparseAttention(InplaceFunction):
-    '''softmax(scale · q·kᵀ + block mask) · v on the matrix cores (custom_mm.block_attention_forward), saving q, k, v, the
-    layout, out and ONE float per query row (the log-sum-exp) — nothing of size Sq × Sk, nothing per kept block.  Backward:
-    custom_mm.block_attention_backward recomputes P per tile; dq over the layout, dk and dv per key block over the
-    transposed layout kept in the layout tensor's _CsrState.  No atomics, no read-back.'''
-
-    @staticmethod
-    def forward(ctx, q, k, v, layout, f, scale, causal):
-        rec = _block_layout(layout, q.device, f, _csr_state(layout))
-        offsets, columns, nnz, _ = rec['fwd']
-        Sq, Sk, D = q.shape[-2], k.shape[-2], q.shape[-1]
-        q3, k3, v3 = q.reshape(-1, Sq, D).contiguous(), k.reshape(-1, Sk, D).contiguous(), v.reshape(-1, Sk, D).contiguous()
-        out = torch.empty_like(q3)
-        lse = torch.empty((q3.shape[0], Sq), device=q.device, dtype=torch.float32)
-        if out.numel() > 0:
-            custom_mm.block_attention_forward(offsets, columns, nnz, q3, k3, v3, float(scale), bool(causal), out, lse)
-        ctx.block_args = (f, float(scale), bool(causal))
-        ctx.save_for_backward(q, k, v, layout, out, lse)
-        return out.reshape(q.shape)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        q, k, v, layout, out, lse = ctx.saved_tensors
-        f, scale, causal = ctx.block_args
-        Sq, Sk, D = q.shape[-2], k.shape[-2], q.shape[-1]
-        q3, k3, v3 = q.reshape(-1, Sq, D).contiguous(), k.reshape(-1, Sk, D).contiguous(), v.reshape(-1, Sk, D).contiguous()
-        if out.numel() == 0:
-            dq, dk, dv = torch.zeros_like(q3), torch.zeros_like(k3), torch.zeros_like(v3)
-        else:
-            rec = _block_layout(layout, q.device, f, _csr_state(layout))
-            offsets, columns, nnz, _ = rec['fwd']
-            t_off, t_col = _block_layout_transposed(rec, Sq // _BLOCK_TILE, Sk // _BLOCK_TILE)
-            g3 = grad_output.to(q.dtype).reshape(-1, Sq, D).contiguous()
-            dq, dk, dv = torch.empty_like(q3), torch.empty_like(k3), torch.empty_like(v3)
-            custom_mm.block_attention_backward(offsets, columns, t_off, t_col, nnz, q3, k3, v3, out, g3, lse, scale, causal,
-                                               dq, dk, dv)
-        need = ctx.needs_input_grad
-        return (dq.reshape(q.shape) if need[0] else None, dk.reshape(k.shape) if need[1] else None,
-                dv.reshape(v.shape) if need[2] else None, None, None, None, None)
-
-
-class blockSparseAttentionGrouped(InplaceFunction):
-    '''blockSparseAttention with grouped-query heads and per-item lengths (custom_mm.block_attention_forward_ex /
-    block_attention_backward_ex): k and v have one item per `group` query items, q_lens / k_lens are None
-    or contiguous int32 device tensors of one count.  Saves what blockSparseAttention saves plus the two length tensors —
-    nothing of size Sq × Sk, nothing per kept block.  dk and dv come back in k's shape: the group's sum is taken inside
-    the key-block kernel, in one accumulator.'''
+    '''softmax(scale · q·kᵀ + block mask) · v on the matrix cores, saving q, k, v, the layout, out and ONE float per query
+    row (the log-sum-exp), then the length tensors that exist — nothing of size Sq × Sk, nothing per kept block.  Backward:
+    P is recomputed per tile; dq over the layout, dk and dv per key block over the transposed layout kept in the layout
+    tensor's _CsrState.  No atomics, no read-back.  With equal leads of q and k and no lengths the calls are
+    custom_mm.block_attention_forward / block_attention_backward; grouped-query heads (k and v with one item per `group`
+    query items) and per-item lengths (q_lens / k_lens None or contiguous int32 device tensors of one count) go through
+    block_attention_forward_ex / block_attention_backward_ex, and dk and dv come back in k's shape: the
+    group's sum is taken inside the key-block kernel, in one accumulator.'''
 
     @staticmethod
     def forward(ctx, q, k, v, layout, f, scale, causal, q_lens, k_lens):
         rec = _block_layout(layout, q.device, f, _csr_state(layout))
         offsets, columns, nnz, _ = rec['fwd']
-        Sq, Sk, D = q.shape[-2], k.shape[-2], q.shape[-1]
-        q3, k3, v3 = q.reshape(-1, Sq, D).contiguous(), k.reshape(-1, Sk, D).contiguous(), v.reshape(-1, Sk, D).contiguous()
+        q3, k3, v3 = _block_items(q, k, v)
         out = torch.empty_like(q3)
-        lse = torch.empty((q3.shape[0], Sq), device=q.device, dtype=torch.float32)
+        lse = torch.empty(q3.shape[:2], device=q.device, dtype=torch.float32)
+        plain = q.shape[:-2] == k.shape[:-2] and q_lens is None and k_lens is None
         if out.numel() > 0:
-            custom_mm.block_attention_forward_ex(offsets, columns, nnz, q3, k3, v3, float(scale), bool(causal), out, lse,
-                                                 q_lens, k_lens)
-        ctx.block_args = (f, float(scale), bool(causal), q_lens is not None, k_lens is not None)
+            if plain:
+                custom_mm.block_attention_forward(offsets, columns, nnz, q3, k3, v3, float(scale), bool(causal), out, lse)
+            else:
+                custom_mm.block_attention_forward_ex(offsets, columns, nnz, q3, k3, v3, float(scale), bool(causal), out, lse,
+                                                     q_lens, k_lens)
+        ctx.block_args = (f, float(scale), bool(causal), plain, q_lens is not None, k_lens is not None)
         ctx.save_for_backward(q, k, v, layout, out, lse, *(t for t in (q_lens, k_lens) if t is not None))
         return out.reshape(q.shape)
 
     @staticmethod
     def backward(ctx, grad_output):
         q, k, v, layout, out, lse, *lens = ctx.saved_tensors
-        f, scale, causal, has_q, has_k = ctx.block_args
+        f, scale, causal, plain, has_q, has_k = ctx.block_args
         q_lens = lens.pop(0) if has_q else None
         k_lens = lens.pop(0) if has_k else None
         Sq, Sk, D = q.shape[-2], k.shape[-2], q.shape[-1]
-        q3, k3, v3 = q.reshape(-1, Sq, D).contiguous(), k.reshape(-1, Sk, D).contiguous(), v.reshape(-1, Sk, D).contiguous()
+        q3, k3, v3 = _block_items(q, k, v)
         if out.numel() == 0:
             dq, dk, dv = torch.zeros_like(q3), torch.zeros_like(k3), torch.zeros_like(v3)
         else:
@@ -1680,11 +1654,29 @@ class blockSparseAttentionGrouped(InplaceFunction):
             t_off, t_col = _block_layout_transposed(rec, Sq // _BLOCK_TILE, Sk // _BLOCK_TILE)
             g3 = grad_output.to(q.dtype).reshape(-1, Sq, D).contiguous()
             dq, dk, dv = torch.empty_like(q3), torch.empty_like(k3), torch.empty_like(v3)
-            custom_mm.block_attention_backward_ex(offsets, columns, t_off, t_col, nnz, q3, k3, v3, out, g3, lse, scale, causal,
-                                                  dq, dk, dv, q_lens, k_lens)
+            args = (offsets, columns, t_off, t_col, nnz, q3, k3, v3, out, g3, lse, scale, causal, dq, dk, dv)
+            if plain:
+                custom_mm.block_attention_backward(*args)
+            else:
+                custom_mm.block_attention_backward_ex(*args, q_lens, k_lens)
         need = ctx.needs_input_grad
         return (dq.reshape(q.shape) if need[0] else None, dk.reshape(k.shape) if need[1] else None,
                 dv.reshape(v.shape) if need[2] else None, None, None, None, None, None, None)
+
+
+def _check_lowp_operands(what, operands, sizes_text):
+    '''What every block-sparse front end asks of its dense operands, (name, tensor) pairs: each a dense bfloat16 / float16
+    tensor (ValueError), then all of the first one's dtype (RuntimeError).'''
+    for name, t in operands:
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be a dense tensor')
+        if t.dtype not in _LOWP:
+            raise ValueError(f'{what}: {name} must be bfloat16 or float16, got {t.dtype} (accepted: {sizes_text})')
+    first, t0 = operands[0]
+    for name, t in operands[1:]:
+        if t.dtype != t0.dtype:
+            raise RuntimeError(f'{what}: {first} is {t0.dtype} but {name} is {t.dtype}: all operands must have one dtype '
+                               f'(bfloat16 or float16)')
 
 
 def _check_block_lens(what, q_lens, k_lens, common):
@@ -1719,15 +1711,7 @@ def _check_block_attention_operands(what, q, k, v, layout, block, causal, q_lens
     dtype, sizes, shapes, lengths), RuntimeError for operands that do not go together (mixed dtypes, host tensors / devices).
     Returns the group: query heads per k / v head.'''
     _check_csr(what, 'layout', layout)
-    for name, t in (('q', q), ('k', k), ('v', v)):
-        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
-            raise ValueError(f'{what}: {name} must be a dense tensor')
-        if t.dtype not in _VALUE_DTYPES or t.dtype == torch.float32:
-            raise ValueError(f'{what}: {name} must be bfloat16 or float16, got {t.dtype} (accepted: {_BLOCK_SIZES_TEXT})')
-    for name, t in (('k', k), ('v', v)):
-        if t.dtype != q.dtype:
-            raise RuntimeError(f'{what}: q is {q.dtype} but {name} is {t.dtype}: all operands must have one dtype '
-                               f'(bfloat16 or float16)')
+    _check_lowp_operands(what, (('q', q), ('k', k), ('v', v)), _BLOCK_SIZES_TEXT)
     if isinstance(block, bool) or not isinstance(block, int) or block <= 0 or block % _BLOCK_TILE != 0:
         raise ValueError(f'{what}: block must be a positive multiple of 64, got {block!r} (accepted: {_BLOCK_SIZES_TEXT})')
     if q.dim() < 2 or k.dim() != q.dim() or v.dim() != q.dim():
@@ -1799,11 +1783,9 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, la
     group = _check_block_attention_operands(what, q, k, v, layout, block, causal, q_lens, k_lens)
     if scale is None:
         scale = 1.0 / float(q.shape[-1]) ** 0.5
-    if group == 1 and q_lens is None and k_lens is None:
-        return blockSparseAttention.apply(q, k, v, layout, block // _BLOCK_TILE, float(scale), bool(causal))
     if q_lens is not None or k_lens is not None:
         q_lens, k_lens = _block_lens(q_lens, k_lens, tuple(q.shape[:-2]) if group == 1 else tuple(q.shape[:-3]))
-    return blockSparseAttentionGrouped.apply(q, k, v, layout, block // _BLOCK_TILE, float(scale), bool(causal), q_lens, k_lens)
+    return blockSparseAttention.apply(q, k, v, layout, block // _BLOCK_TILE, float(scale), bool(causal), q_lens, k_lens)
 
 
 # --------------------------------------------------------------------------- #
@@ -1813,10 +1795,14 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, la
 _BSR_SIZES_TEXT = 'bfloat16 or float16 operands, block = 64, M and K multiples of 64'
 
 
+def _bsr_takes(dtype, block) -> bool:
+    return dtype in _LOWP and isinstance(block, int) and not isinstance(block, bool) and block == _BLOCK_TILE
+
+
 def block_mm_takes(dtype, block) -> bool:
     '''Whether block_sparse_mm takes blocks of `block` × `block` in `dtype` — a function of (dtype, block) alone: bfloat16 /
     float16 and block == 64.  Anything else raises there.'''
-    return dtype in _LOWP and isinstance(block, int) and not isinstance(block, bool) and block == _BLOCK_TILE
+    return _bsr_takes(dtype, block)
 
 
 def _sorted_lists(offsets: torch.Tensor, columns: torch.Tensor, ids: torch.Tensor, rows: int, cols: int):
@@ -1834,12 +1820,7 @@ def _bsr_layout(layout: torch.Tensor, dev, st: _CsrState):
     the pattern stays: {'fwd': (offsets int32 [M/64 + 1], columns int32 [n] ascending within a block row, entry ids int32
     [n] — sorted position → stored entry, entry_row int32 [n], n), 't': None or the transposed lists
     (_bsr_layout_transposed)} — narrowed and sorted once.'''
-    pat = st.key[1:3] + st.key[4:]
-    kept = getattr(st, 'bsr_layouts', None)
-    if kept is None or kept[0] != pat:
-        kept = (pat, {})
-        st.bsr_layouts = kept
-    rec = kept[1].get(str(dev))
+    rec = st.bsr_layouts.get(str(dev))
     if rec is None:
         rows, cols = layout.shape
         crow = torch.Tensor.crow_indices(layout).to(dev).to(torch.int64)
@@ -1847,7 +1828,7 @@ def _bsr_layout(layout: torch.Tensor, dev, st: _CsrState):
         n = col.numel()
         columns, ids, entry_row = _sorted_lists(crow, col, torch.arange(n, device=col.device), rows, cols)
         rec = {'fwd': (crow.to(torch.int32).contiguous(), columns, ids, entry_row, n), 't': None}
-        kept[1][str(dev)] = rec
+        st.bsr_layouts[str(dev)] = rec
     return rec
 
 
@@ -1921,23 +1902,18 @@ class blockSparseMM(InplaceFunction):
         return dvalues, None, db
 
 
-def _check_block_mm_operands(what, values, layout, b, block):
-    '''Every refusal of block_sparse_mm, before the first device call: ValueError for what an operand is (layout, dtype,
-    block, shapes), RuntimeError for operands that do not go together (mixed dtypes, host tensors / devices).'''
+def _check_bsr_operands(what, values, layout, operands, block, dims, shared, sizes_text, shape_error):
+    '''Every refusal of block_sparse_mm and block_sparse_linear, before the first device call: ValueError for what an
+    operand is (layout, dtype, block, shapes), RuntimeError for operands that do not go together (mixed dtypes, host
+    tensors / devices).  `operands` are the dense (name, tensor) pairs in the order the messages name them; `dims`, `shared`
+    and `sizes_text` are the function's own words; shape_error() gives the text of its own shape refusal, or None.'''
     _check_csr(what, 'layout', layout)
     if layout.dim() != 2:
-        raise ValueError(f'{what}: the layout must be a 2-d CSR tensor [M/64, K/64], got {layout.dim()}-d: A is shared by '
-                         f'every item of the batch, a batched layout is not supported')
-    for name, t in (('values', values), ('b', b)):
-        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
-            raise ValueError(f'{what}: {name} must be a dense tensor')
-        if t.dtype not in _LOWP:
-            raise ValueError(f'{what}: {name} must be bfloat16 or float16, got {t.dtype} (accepted: {_BSR_SIZES_TEXT})')
-    if b.dtype != values.dtype:
-        raise RuntimeError(f'{what}: values is {values.dtype} but b is {b.dtype}: all operands must have one dtype '
-                           f'(bfloat16 or float16)')
+        raise ValueError(f'{what}: the layout must be a 2-d CSR tensor {dims}, got {layout.dim()}-d: {shared}, a batched '
+                         f'layout is not supported')
+    _check_lowp_operands(what, operands, sizes_text)
     if isinstance(block, bool) or not isinstance(block, int) or block != _BLOCK_TILE:
-        raise ValueError(f'{what}: block must be 64, got {block!r} (accepted: {_BSR_SIZES_TEXT})')
+        raise ValueError(f'{what}: block must be 64, got {block!r} (accepted: {sizes_text})')
     n = torch.Tensor.values(layout).numel()
     if values.dim() != 3 or tuple(values.shape[1:]) != (block, block):
         raise ValueError(f'{what}: values must be [n, {block}, {block}], got {tuple(values.shape)}')
@@ -1945,16 +1921,27 @@ def _check_block_mm_operands(what, values, layout, b, block):
         raise ValueError(f'{what}: values holds {values.shape[0]} blocks but the layout stores {n} entries')
     if not values.is_contiguous():
         raise ValueError(f'{what}: values must be contiguous')
-    if b.dim() < 2:
-        raise ValueError(f'{what}: b must be a [..., K, N] tensor, got {b.dim()}-d')
-    K = b.shape[-2]
-    if K % block != 0 or K // block != layout.shape[1]:
-        raise ValueError(f'{what}: b of shape {tuple(b.shape)} has K = {K} rows, the layout {tuple(layout.shape)} needs '
-                         f'K = {layout.shape[1]} · {block} = {layout.shape[1] * block}: M and K must be multiples of block, '
-                         f'ragged sizes are not supported (accepted: {_BSR_SIZES_TEXT})')
+    text = shape_error()
+    if text is not None:
+        raise ValueError(f'{what}: {text}')
     if n >= 2 ** 31:
         raise ValueError(f'{what}: the layout does not fit int32 indices')
-    _check_on_device(what, layout=torch.Tensor.values(layout), values=values, b=b)
+    _check_on_device(what, layout=torch.Tensor.values(layout), **dict(operands))
+
+
+def _check_block_mm_operands(what, values, layout, b, block):
+    '''Every refusal of block_sparse_mm (_check_bsr_operands), with its own words and its shape check of b.'''
+    def shape_error():
+        if b.dim() < 2:
+            return f'b must be a [..., K, N] tensor, got {b.dim()}-d'
+        K = b.shape[-2]
+        if K % block != 0 or K // block != layout.shape[1]:
+            return (f'b of shape {tuple(b.shape)} has K = {K} rows, the layout {tuple(layout.shape)} needs '
+                    f'K = {layout.shape[1]} · {block} = {layout.shape[1] * block}: M and K must be multiples of block, '
+                    f'ragged sizes are not supported (accepted: {_BSR_SIZES_TEXT})')
+
+    _check_bsr_operands(what, values, layout, (('values', values), ('b', b)), block, '[M/64, K/64]',
+                        'A is shared by every item of the batch', _BSR_SIZES_TEXT, shape_error)
 
 
 def block_sparse_mm(values: torch.Tensor, layout: torch.Tensor, b: torch.Tensor, block: int = 64) -> torch.Tensor:
@@ -2002,7 +1989,7 @@ _BSR_LINEAR_SIZES_TEXT = 'bfloat16 or float16 operands, block = 64, in and out m
 def block_linear_takes(dtype, block) -> bool:
     '''Whether block_sparse_linear takes blocks of `block` × `block` in `dtype` — a function of (dtype, block) alone:
     bfloat16 / float16 and block == 64.  Anything else raises there.'''
-    return dtype in _LOWP and isinstance(block, int) and not isinstance(block, bool) and block == _BLOCK_TILE
+    return _bsr_takes(dtype, block)
 
 
 class blockSparseLinearFn(InplaceFunction):
@@ -2066,47 +2053,21 @@ class blockSparseLinearFn(InplaceFunction):
 
 
 def _check_block_linear_operands(what, x, values, layout, bias, block):
-    '''Every refusal of block_sparse_linear, before the first device call, with the exception types of
-    _check_block_mm_operands: ValueError for what an operand is (layout, dtype, block, shapes), RuntimeError for operands
-    that do not go together (mixed dtypes, host tensors / devices).'''
-    _check_csr(what, 'layout', layout)
-    if layout.dim() != 2:
-        raise ValueError(f'{what}: the layout must be a 2-d CSR tensor [out/64, in/64], got {layout.dim()}-d: W is shared by '
-                         f'every token, a batched layout is not supported')
+    '''Every refusal of block_sparse_linear (_check_bsr_operands), with its own words and its shape checks of x and bias.'''
+    def shape_error():
+        if x.dim() < 1:
+            return f'x must be a [..., in] tensor, got {x.dim()}-d'
+        fin, fout = x.shape[-1], layout.shape[0] * block
+        if fin % block != 0 or fin // block != layout.shape[1]:
+            return (f'x of shape {tuple(x.shape)} has in = {fin} features, the layout {tuple(layout.shape)} needs '
+                    f'in = {layout.shape[1]} · {block} = {layout.shape[1] * block}: in and out must be multiples of '
+                    f'block, ragged sizes are not supported (accepted: {_BSR_LINEAR_SIZES_TEXT})')
+        if bias is not None and tuple(bias.shape) != (fout,):
+            return f'bias must be [out] = [{fout}], got {tuple(bias.shape)}'
+
     operands = (('x', x), ('values', values)) + ((('bias', bias),) if bias is not None else ())
-    for name, t in operands:
-        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
-            raise ValueError(f'{what}: {name} must be a dense tensor')
-        if t.dtype not in _LOWP:
-            raise ValueError(f'{what}: {name} must be bfloat16 or float16, got {t.dtype} (accepted: {_BSR_LINEAR_SIZES_TEXT})')
-    for name, t in operands[1:]:
-        if t.dtype != x.dtype:
-            raise RuntimeError(f'{what}: x is {x.dtype} but {name} is {t.dtype}: all operands must have one dtype '
-                               f'(bfloat16 or float16)')
-    if isinstance(block, bool) or not isinstance(block, int) or block != _BLOCK_TILE:
-        raise ValueError(f'{what}: block must be 64, got {block!r} (accepted: {_BSR_LINEAR_SIZES_TEXT})')
-    n = torch.Tensor.values(layout).numel()
-    if values.dim() != 3 or tuple(values.shape[1:]) != (block, block):
-        raise ValueError(f'{what}: values must be [n, {block}, {block}], got {tuple(values.shape)}')
-    if values.shape[0] != n:
-        raise ValueError(f'{what}: values holds {values.shape[0]} blocks but the layout stores {n} entries')
-    if not values.is_contiguous():
-        raise ValueError(f'{what}: values must be contiguous')
-    if x.dim() < 1:
-        raise ValueError(f'{what}: x must be a [..., in] tensor, got {x.dim()}-d')
-    fin, fout = x.shape[-1], layout.shape[0] * block
-    if fin % block != 0 or fin // block != layout.shape[1]:
-        raise ValueError(f'{what}: x of shape {tuple(x.shape)} has in = {fin} features, the layout {tuple(layout.shape)} needs '
-                         f'in = {layout.shape[1]} · {block} = {layout.shape[1] * block}: in and out must be multiples of '
-                         f'block, ragged sizes are not supported (accepted: {_BSR_LINEAR_SIZES_TEXT})')
-    if bias is not None and tuple(bias.shape) != (fout,):
-        raise ValueError(f'{what}: bias must be [out] = [{fout}], got {tuple(bias.shape)}')
-    if n >= 2 ** 31:
-        raise ValueError(f'{what}: the layout does not fit int32 indices')
-    named = dict(layout=torch.Tensor.values(layout), x=x, values=values)
-    if bias is not None:
-        named['bias'] = bias
-    _check_on_device(what, **named)
+    _check_bsr_operands(what, values, layout, operands, block, '[out/64, in/64]', 'W is shared by every token',
+                        _BSR_LINEAR_SIZES_TEXT, shape_error)
 
 
 def block_sparse_linear(x: torch.Tensor, values: torch.Tensor, layout: torch.Tensor, bias=None, block: int = 64) -> torch.Tensor:
