@@ -1034,6 +1034,48 @@ int mi_block_attention_bwd_ex_f16(const int32_t* rowptr, const int32_t* col, con
                                   const int32_t* q_lens, const int32_t* k_lens, int32_t lens_count, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * Block-sparse attention for decoding: the T newest tokens of every item against a key / value cache,
+ * forward only, in bfloat16 / float16 (2-byte bit patterns).  Token t of k / v item c stands at pos = k_len − T + t and
+ * sees key j iff j ≤ pos and the layout lists 64-block (pos / 64, j / 64); a token with pos < 0, or one that sees nothing,
+ * gives a zero row of out and −inf as its lse.
+ *   rowptr, col, nnz, layouts   the block lists of mi_block_attention_fwd_* over Smax/64 × Smax/64 blocks; k / v item c
+ *              uses layout c mod layouts — the `group` query heads of a k / v head share its layout;
+ *   items, heads   items = B · heads k / v items; item c is head c % heads of batch item c / heads.  items, T ≤ 65535;
+ *   q, out     query item c · group + g (g < group), token t: q + (c · group + g) · strideQ + t · ldq, D elements; out
+ *              likewise with ldo, strideO; 16-byte aligned, ld ≥ D, ld and stride multiples of 8;
+ *   k, v       the cache, never copied: key j of item c at k + (c / heads) · batchK + (c % heads) · headK + j · ldk; 16-byte
+ *              aligned, ldk ≥ D, every stride a multiple of 8 elements ([B, heads, Smax, D] and [B, Smax, heads, D] both fit);
+ *   k_lens     int32 [lens_count] on the device, required; item c has entry c / (items / lens_count); clamped to [0, Smax];
+ *   group      query heads per k / v head, 1 … 16: the own rows of ONE 16-row MFMA tile, a k / v tile read once for all;
+ *   chunk      ≥ 1: the list of layout row pos / 64 is cut into chunks of `chunk` consecutive entries by list position
+ *              (skipped entries do not move the cut); one workgroup per chunk, its four waves taking entries w, w + 4, …;
+ *              partials (maximum, sum, fp32 accumulator) are merged in ascending wave order, then in ascending chunk order
+ *              by a second launch (none when Smax/64 ≤ chunk); out is rounded once.  The bits of a row depend on its own
+ *              item's operands, its list, pos and chunk only.  No atomics, no read-back: graph-capturable;
+ *   lse        float32 [items · group][T];
+ *   workspace  mi_block_attention_decode_workspace_bytes(...) bytes, 16-byte aligned: `group` rows of D + 2 floats per
+ *              (item, token, chunk); 0 bytes (may be NULL) when there is one chunk.
+ * Validation before any HIP call: group outside [1, 16], D ∉ {32, 64, 96, 128}, chunk < 1, Smax not a multiple of 64, items or
+ * T > 65535, items % heads != 0, lens_count < 1 or items % lens_count != 0, a NULL / misaligned pointer, a stride that is
+ * not a multiple of 8 or a leading dimension < D → MI_EINVAL; a short workspace → MI_ENOMEM; items == 0 or T == 0 → MI_OK,
+ * nothing touched.  Offsets are clamped to nnz and a column outside the grid is skipped.
+ * ------------------------------------------------------------------------ */
+size_t mi_block_attention_decode_workspace_bytes(int32_t items, int32_t T, int32_t group, int32_t D, int32_t Smax,
+                                                 int32_t chunk);
+int mi_block_attention_decode_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items,
+                                   int32_t heads, int32_t T, int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq,
+                                   int64_t strideQ, const uint16_t* k, int64_t ldk, int64_t headK, int64_t batchK,
+                                   const uint16_t* v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t* k_lens,
+                                   int32_t lens_count, int32_t group, int32_t chunk, float scale, uint16_t* out, int64_t ldo,
+                                   int64_t strideO, float* lse, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_block_attention_decode_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items,
+                                  int32_t heads, int32_t T, int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq,
+                                  int64_t strideQ, const uint16_t* k, int64_t ldk, int64_t headK, int64_t batchK,
+                                  const uint16_t* v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t* k_lens,
+                                  int32_t lens_count, int32_t group, int32_t chunk, float scale, uint16_t* out, int64_t ldo,
+                                  int64_t strideO, float* lse, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in
  * bfloat16 / float16 (T, 2-byte bit patterns) with A given as the kept 64 × 64 blocks of a CSR block list, shared by
  * every item of the batch, and the sampled product on the same list:

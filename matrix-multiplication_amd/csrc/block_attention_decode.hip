@@ -1,0 +1,430 @@
+// Block-sparse attention for decoding in bfloat16 and float16 on the matrix cores: the T newest tokens of every item
+// against a key / value cache, out = softmax(scale · q·kᵀ + mask) · v, where token t of an item of length k_len stands at
+// pos = k_len − T + t and sees key j iff j ≤ pos and the CSR block layout lists 64-block (pos / 64, j / 64).  Forward
+// only.  q, k, v and out are of one type T ∈ {bf16, fp16} (2-byte bit patterns at the C-ABI).
+//
+// What it computes (contract of include/mi_spmm.h, mi_block_attention_decode_{bf16,f16} — DESIGN.md §3.18):
+//  * The arithmetic of block_attention_fwd_kernel (block_attention.hip): v_mfma_f32_16x16x32_{bf16,f16} with fp32
+//    accumulators, scores, maxima and sums in fp32 as lane scalars, P narrowed to T only as the operand of P·V, out rounded
+//    once at the final store.  The own rows of a workgroup are the `group` query heads of one (item, k / v head, token) in
+//    ONE 16-row tile (rows ≥ group are zero fragments and never stored): a k / v tile is read once for the whole group.
+//  * The order of summation: the list of layout row pos / 64 is cut into chunks of `chunk` consecutive entries BY LIST
+//    POSITION (entry p belongs to chunk (p − beg) / chunk; an entry outside the grid or wholly beyond pos is skipped inside
+//    its chunk and does not move the cut).  A workgroup owns one chunk; wave w walks its entries w, w + 4, … in order, and
+//    the four waves' partials (running maximum m, sum l, unnormalised fp32 accumulator) are merged in ascending wave order:
+//    M = max m_i, l = Σ l_i·exp(m_i − M), o likewise; an empty partial is (−inf, 0, 0).  The chunks' partials are merged the
+//    same way in ascending chunk order by block_attention_decode_combine_kernel — or, with one chunk, stored at once by
+//    the first kernel with the same arithmetic.  The bits of an output row depend on its own item's operands, its list,
+//    pos and chunk only: never on the batch, the neighbours or the launch.  No atomics, no read-back: graph-capturable.
+//  * Nothing outside is read: the cache is read through its own row, head and batch strides; a block outside the list, a
+//    key beyond pos (so every key at or beyond k_len) and everything between the rows are never loaded; the rows of a
+//    straddling block beyond pos are staged as zeros, their scores masked to −inf.  Offsets are clamped to nnz, a column
+//    outside the grid is skipped: a malformed layout reads nothing outside the operands.
+//
+// Kernel: grid (chunks, items, T), 256 threads.  No workgroup barrier inside the walk.  A wave loads the k tile of an
+// entry as 16-byte global loads straight into MFMA A fragments (lane (li, lg): row 16f + li, columns 32s + 8lg … + 7), the v
+// tile into registers and from there into a wave-private transposed LDS image [D][64 + 8] (a wave-level fence between its
+// writes and reads); the next entry's loads are issued before this one's softmax and P·V.  The device pieces (mfma,
+// score, pack_tile, accumulate, group_max / group_sum) are private copies of block_attention.hip's, adapted to one wave.
+#include "lowp_device.h"
+
+namespace {
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+template <class T>
+__device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c);
+template <>
+__device__ __forceinline__ f32x4 mfma<Bf16>(uint4 a, uint4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+template <>
+__device__ __forceinline__ f32x4 mfma<F16>(uint4 a, uint4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
+constexpr int kB = 64;          // keys of a block: the kernel's tile
+constexpr int kTStr = kB + 8;   // row stride of the transposed image in elements (144 bytes)
+constexpr int kWaves = 4;       // waves of a workgroup: wave w walks entries w, w + 4, … of the chunk
+constexpr int kMaxGroup = 16;   // own rows of the one MFMA tile
+
+struct Args {
+  const int32_t* rowptr;  // [layouts][blocks + 1], with the layouts' bases
+  const int32_t* col;     // [nnz], layout-local block columns
+  long nnz;
+  int layouts, blocks;    // blocks = Smax / 64
+  int heads;              // k / v heads per batch item: k / v item c is head c % heads of batch item c / heads
+  int group, T, chunk, chunks;
+  long smax;
+  const uint16_t* q;      // query item c · group + g, token t: q + (c · group + g) · strideQ + t · ldq
+  long ldq, strideQ;
+  const uint16_t *k, *v;  // key j of k / v item c: k + (c / heads) · batchK + (c % heads) · headK + j · ldk
+  long ldk, headK, batchK, ldv, headV, batchV;
+  const int32_t* k_lens;  // [items / lens_div], clamped to [0, Smax] where read
+  int lens_div;
+  float scale;
+  uint16_t* out;
+  long ldo, strideO;
+  float* lse;  // [items · group][T]
+  float* ws;   // [items][T][chunks][group][D + 2]: m, l, o[D] — read and written only with chunks > 1
+};
+
+__device__ __forceinline__ unsigned half_of(uint4 v, int i) {
+  const unsigned w = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
+  return (i & 1) ? (w >> 16) : (w & 0xffffu);
+}
+
+__device__ __forceinline__ void fence_wave() {  // LDS writes of this wave before, its reads after
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The k tile of a block as A fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of row 16f + li; rows at or beyond
+// `limit` (keys beyond pos) are zero fragments, whatever memory holds
+template <int D>
+__device__ __forceinline__ void load_k(uint4 (&kf)[4][D / 32], const uint16_t* src, long ld, int li, int lg, int limit) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f)
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s) {
+      if (16 * f + li < limit)
+        kf[f][s] = *reinterpret_cast<const uint4*>(src + (long)(16 * f + li) * ld + 32 * s + 8 * lg);
+      else
+        kf[f][s] = uint4{0u, 0u, 0u, 0u};
+    }
+}
+
+// The v tile of a block in one wave's registers: lane (li, lg) holds rows 4li … + 3, columns 8(lg + 4i) … + 7
+template <int D>
+__device__ __forceinline__ void load_v(uint4 (&vr)[D / 32][4], const uint16_t* src, long ld, int li, int lg, int limit) {
+#pragma unroll
+  for (int i = 0; i < D / 32; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (4 * li + r < limit)
+        vr[i][r] = *reinterpret_cast<const uint4*>(src + (long)(4 * li + r) * ld + 8 * (lg + 4 * i));
+      else
+        vr[i][r] = uint4{0u, 0u, 0u, 0u};
+    }
+}
+
+// … into the wave's transposed image [D][64 + 8]
+template <int D>
+__device__ __forceinline__ void store_transposed(unsigned short* Tt, const uint4 (&vr)[D / 32][4], int li, int lg) {
+#pragma unroll
+  for (int i = 0; i < D / 32; ++i)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint2 w = {half_of(vr[i][0], e) | (half_of(vr[i][1], e) << 16), half_of(vr[i][2], e) | (half_of(vr[i][3], e) << 16)};
+      *reinterpret_cast<uint2*>(Tt + (8 * (lg + 4 * i) + e) * kTStr + 4 * li) = w;
+    }
+}
+
+// acc[f][r] = ⟨key 16f + 4lg + r of the block, own row li⟩ over d
+template <class T, int D>
+__device__ __forceinline__ void score(f32x4 (&acc)[4], const uint4 (&kf)[4][D / 32], const uint4 (&own)[D / 32]) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s) acc[f] = mfma<T>(kf[f][s], own[s], acc[f]);
+  }
+}
+
+// a score-shaped tile narrowed to T as the B operand of the two k-steps over the keys
+template <class T>
+__device__ __forceinline__ void pack_tile(uint4 (&b)[2], const f32x4 (&x)[4]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+    b[s] = uint4{pack2<T>(x[2 * s][0], x[2 * s][1]), pack2<T>(x[2 * s][2], x[2 * s][3]), pack2<T>(x[2 * s + 1][0], x[2 * s + 1][1]),
+                 pack2<T>(x[2 * s + 1][2], x[2 * s + 1][3])};
+}
+
+// out[fd][r] += Σ over the keys of Tt[d = 16fd + 4lg + r][key] · b[key][own row li]
+template <class T, int D>
+__device__ __forceinline__ void accumulate(f32x4 (&out)[D / 16], const unsigned short* Tt, const uint4 (&b)[2], int li, int lg) {
+#pragma unroll
+  for (int fd = 0; fd < D / 16; ++fd)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const unsigned short* p = Tt + (16 * fd + li) * kTStr + 32 * s + 4 * lg;
+      const uint2 lo = *reinterpret_cast<const uint2*>(p), hi = *reinterpret_cast<const uint2*>(p + 16);
+      out[fd] = mfma<T>(uint4{lo.x, lo.y, hi.x, hi.y}, b[s], out[fd]);
+    }
+}
+
+__device__ __forceinline__ float group_max(float x) {  // over the four lanes li, li + 16, li + 32, li + 48
+  x = fmaxf(x, __shfl_xor(x, 16));
+  return fmaxf(x, __shfl_xor(x, 32));
+}
+__device__ __forceinline__ float group_sum(float x) {
+  x = x + __shfl_xor(x, 16);
+  return x + __shfl_xor(x, 32);
+}
+
+// the next entry of this wave at or after p (in steps of the workgroup's waves) that is computed: inside the grid and
+// not wholly beyond pos
+__device__ __forceinline__ int next_entry(const int32_t* col, int p, int end, int pos, int blocks) {
+  for (; p < end; p += kWaves) {
+    const int j = col[p];
+    if ((unsigned)j >= (unsigned)blocks || (long)j * kB > pos) continue;
+    break;
+  }
+  return p;
+}
+
+// the weight of a partial with maximum m in a merge to the maximum M (an empty partial, m = −inf, weighs nothing)
+__device__ __forceinline__ float merge_weight(float m, float M) { return m == -INFINITY ? 0.f : __expf(m - M); }
+
+// element d of the row of query head g of (c, t): normalised, rounded once; the row's log-sum-exp with its element 0
+template <class T>
+__device__ __forceinline__ void finish(const Args& a, int c, int t, int g, int d, float M, float L, float O) {
+  const float inv = L == 0.f ? 0.f : 1.f / L;
+  const long item = (long)c * a.group + g;
+  a.out[item * a.strideO + (long)t * a.ldo + d] = T::down(O * inv);
+  if (d == 0) a.lse[item * a.T + t] = L == 0.f ? -INFINITY : M + __logf(L);
+}
+
+template <class T, int D>
+__global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
+  constexpr int kPStr = D + 4;  // a wave's partial in its own image: [16][D + 4] floats — o[D], m, l
+  __shared__ __attribute__((aligned(16))) unsigned short Vt[kWaves][D * kTStr];
+  static_assert(kMaxGroup * kPStr * 4 <= D * kTStr * 2, "the partial fits the image");
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
+  const int ch = blockIdx.x, c = blockIdx.y, t = blockIdx.z;
+  const int G = a.group;
+  int klen = a.k_lens[c / a.lens_div];
+  klen = klen < 0 ? 0 : klen > a.smax ? (int)a.smax : klen;
+  const int pos = klen - a.T + t;  // the token's position: it sees keys j ≤ pos of the blocks its layout row lists
+  int beg = 0, end = 0;            // this chunk's part of the list
+  if (pos >= 0) {
+    const int32_t* rp = a.rowptr + (long)(c % a.layouts) * (a.blocks + 1);
+    long lo = rp[pos / kB], hi = rp[pos / kB + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > a.nnz ? a.nnz : hi;
+    lo += (long)ch * a.chunk;
+    hi = hi < lo + a.chunk ? hi : lo + a.chunk;
+    if (lo < hi) beg = (int)lo, end = (int)hi;
+  }
+  if (beg == end) {  // no token, or the chunk lies beyond the list's end: the empty partial (−inf, 0, 0), and leave
+    for (int e = tid; e < G * D; e += 256) {
+      const int g = e / D, d = e - g * D;
+      if (a.chunks == 1) {
+        finish<T>(a, c, t, g, d, -INFINITY, 0.f, 0.f);
+      } else {
+        float* row = a.ws + ((((long)c * a.T + t) * a.chunks + ch) * G + g) * (D + 2);
+        row[2 + d] = 0.f;
+        if (d == 0) row[0] = -INFINITY, row[1] = 0.f;
+      }
+    }
+    return;
+  }
+  const uint16_t* K = a.k + (long)(c / a.heads) * a.batchK + (long)(c % a.heads) * a.headK;
+  const uint16_t* V = a.v + (long)(c / a.heads) * a.batchV + (long)(c % a.heads) * a.headV;
+  unsigned short* Vw = Vt[w];
+
+  uint4 qf[D / 32];  // the own rows as B fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of query head li
+#pragma unroll
+  for (int s = 0; s < D / 32; ++s) qf[s] = uint4{0u, 0u, 0u, 0u};
+  int p = next_entry(a.col, beg + w, end, pos, a.blocks);
+  if (li < G && p < end) {
+    const uint16_t* row = a.q + ((long)c * G + li) * a.strideQ + (long)t * a.ldq;
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s) qf[s] = *reinterpret_cast<const uint4*>(row + 32 * s + 8 * lg);
+  }
+  f32x4 o[D / 16];
+#pragma unroll
+  for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+
+  uint4 kf[4][D / 32], vr[D / 32][4];
+  if (p < end) {
+    const int J = a.col[p];
+    load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB);
+    load_v<D>(vr, V + (long)J * kB * a.ldv, a.ldv, li, lg, pos + 1 - J * kB);
+  }
+  while (p < end) {
+    const int visible = pos + 1 - a.col[p] * kB;  // keys of this block the token sees (≥ 1; 64 or more: all)
+    fence_wave();  // the previous entry's reads of the image are done
+    store_transposed<D>(Vw, vr, li, lg);
+    fence_wave();
+    f32x4 s[4];
+    score<T, D>(s, kf, qf);
+    p = next_entry(a.col, p + kWaves, end, pos, a.blocks);
+    if (p < end) {  // the next entry's loads are in flight while this one is computed
+      const int J = a.col[p];
+      load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB);
+      load_v<D>(vr, V + (long)J * kB * a.ldv, a.ldv, li, lg, pos + 1 - J * kB);
+    }
+    float mt = -INFINITY;
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float x = s[f][r] * a.scale;
+        if (16 * f + 4 * lg + r >= visible) x = -INFINITY;
+        s[f][r] = x;
+        mt = fmaxf(mt, x);
+      }
+    const float mn = fmaxf(m, group_max(mt));
+    const float alpha = m == mn ? 1.f : __expf(m - mn);  // (−inf stays: nothing seen yet)
+    float sum = 0.f;
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float e = s[f][r] == -INFINITY ? 0.f : __expf(s[f][r] - mn);
+        s[f][r] = e;
+        sum += e;
+      }
+    l = l * alpha + sum;  // this lane's share of the row sum; the four shares meet after the walk
+    m = mn;
+#pragma unroll
+    for (int fd = 0; fd < D / 16; ++fd)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[fd][r] *= alpha;
+    uint4 pb[2];
+    pack_tile<T>(pb, s);
+    accumulate<T, D>(o, Vw, pb, li, lg);
+  }
+  l = group_sum(l);
+
+  // the four waves' partials meet through LDS, each in its own image, and are merged in wave order
+  fence_wave();
+  float* P = reinterpret_cast<float*>(Vw);
+  if (li < G) {
+#pragma unroll
+    for (int fd = 0; fd < D / 16; ++fd) *reinterpret_cast<f32x4*>(P + li * kPStr + 16 * fd + 4 * lg) = o[fd];
+    if (lg == 0) P[li * kPStr + D] = m, P[li * kPStr + D + 1] = l;
+  }
+  __syncthreads();
+  for (int e = tid; e < G * D; e += 256) {
+    const int g = e / D, d = e - g * D;
+    float M = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < kWaves; ++i) M = fmaxf(M, reinterpret_cast<const float*>(Vt[i])[g * kPStr + D]);
+    float L = 0.f, O = 0.f;
+#pragma unroll
+    for (int i = 0; i < kWaves; ++i) {
+      const float* Pi = reinterpret_cast<const float*>(Vt[i]) + g * kPStr;
+      const float wt = merge_weight(Pi[D], M);
+      L += Pi[D + 1] * wt;
+      O += Pi[d] * wt;
+    }
+    if (a.chunks == 1) {
+      finish<T>(a, c, t, g, d, M, L, O);
+    } else {
+      float* row = a.ws + ((((long)c * a.T + t) * a.chunks + ch) * G + g) * (D + 2);
+      row[2 + d] = O;
+      if (d == 0) row[0] = M, row[1] = L;
+    }
+  }
+}
+
+// merges the chunks' partials of the rows of (c, t) in ascending chunk order, normalises, stores out and lse
+template <class T>
+__global__ __launch_bounds__(128) void block_attention_decode_combine_kernel(Args a, int D) {
+  const int c = blockIdx.x, t = blockIdx.y, G = a.group;
+  const float* base = a.ws + (((long)c * a.T + t) * a.chunks) * G * (D + 2);
+  for (int e = threadIdx.x; e < G * D; e += 128) {
+    const int g = e / D, d = e - g * D;
+    float M = -INFINITY;
+    for (int i = 0; i < a.chunks; ++i) M = fmaxf(M, base[((long)i * G + g) * (D + 2)]);
+    float L = 0.f, O = 0.f;
+    for (int i = 0; i < a.chunks; ++i) {
+      const float* row = base + ((long)i * G + g) * (D + 2);
+      const float wt = merge_weight(row[0], M);
+      L += row[1] * wt;
+      O += row[2 + d] * wt;
+    }
+    finish<T>(a, c, t, g, d, M, L, O);
+  }
+}
+
+bool takes_width(int32_t D) { return D == 32 || D == 64 || D == 96 || D == 128; }
+
+bool stride_ok(int64_t s) { return s >= 0 && s % 8 == 0; }
+
+int chunks_of(int32_t Smax, int32_t chunk) {  // from the shape alone; a list has at most Smax / 64 entries
+  const long blocks = Smax / kB;
+  const long n = (blocks + chunk - 1) / chunk;
+  return (int)(n < 1 ? 1 : n);
+}
+
+template <class T, int D>
+int launch(const Args& a, int items, hipStream_t s) {
+  hipLaunchKernelGGL((block_attention_decode_kernel<T, D>), dim3((unsigned)a.chunks, (unsigned)items, (unsigned)a.T), dim3(256), 0, s, a);
+  const int st = mi::check_launch();
+  if (st != MI_OK || a.chunks == 1) return st;
+  hipLaunchKernelGGL((block_attention_decode_combine_kernel<T>), dim3((unsigned)items, (unsigned)a.T), dim3(128), 0, s, a, D);
+  return mi::check_launch();
+}
+
+// Every check comes before the first HIP call.
+template <class T>
+int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T_,
+                 int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k, int64_t ldk,
+                 int64_t headK, int64_t batchK, const uint16_t* v, int64_t ldv, int64_t headV, int64_t batchV,
+                 const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale, uint16_t* out, int64_t ldo,
+                 int64_t strideO, float* lse, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  if (group < 1 || group > kMaxGroup || chunk < 1 || !takes_width(D)) return MI_EINVAL;
+  if (nnz < 0 || layouts < 0 || items < 0 || heads < 0 || T_ < 0 || Smax < 0 || Smax % kB != 0) return MI_EINVAL;
+  if (nnz > 0x7fffffffLL) return MI_ERANGE;
+  if (items > 65535 || T_ > 65535) return MI_EINVAL;  // the grid's y and z: no item loop
+  if (items == 0 || T_ == 0) return MI_OK;
+  if (layouts == 0 || heads == 0 || items % heads != 0 || lens_count < 1 || items % lens_count != 0) return MI_EINVAL;
+  if (!rowptr || (nnz > 0 && !col) || !k_lens || (reinterpret_cast<uintptr_t>(k_lens) & 3u)) return MI_EINVAL;
+  if (!lse || (reinterpret_cast<uintptr_t>(lse) & 3u)) return MI_EINVAL;
+  if (!q || !mi::aligned16(q) || ldq < D || !stride_ok(ldq) || !stride_ok(strideQ)) return MI_EINVAL;
+  if (!out || !mi::aligned16(out) || ldo < D || !stride_ok(ldo) || !stride_ok(strideO)) return MI_EINVAL;
+  if (nnz > 0 && Smax > 0) {
+    if (!k || !mi::aligned16(k) || ldk < D || !stride_ok(ldk) || !stride_ok(headK) || !stride_ok(batchK)) return MI_EINVAL;
+    if (!v || !mi::aligned16(v) || ldv < D || !stride_ok(ldv) || !stride_ok(headV) || !stride_ok(batchV)) return MI_EINVAL;
+  }
+  const int chunks = chunks_of(Smax, chunk);
+  if (chunks > 1) {
+    if (!workspace || !mi::aligned16(workspace)) return MI_EINVAL;
+    if (workspace_bytes < mi_block_attention_decode_workspace_bytes(items, T_, group, D, Smax, chunk)) return MI_ENOMEM;
+  }
+  Args a = {};
+  a.rowptr = rowptr, a.col = col, a.nnz = nnz, a.layouts = layouts, a.blocks = Smax / kB, a.heads = heads, a.group = group;
+  a.T = T_, a.chunk = chunk, a.chunks = chunks, a.smax = Smax;
+  a.q = q, a.ldq = ldq, a.strideQ = strideQ;
+  a.k = k, a.ldk = ldk, a.headK = headK, a.batchK = batchK, a.v = v, a.ldv = ldv, a.headV = headV, a.batchV = batchV;
+  a.k_lens = k_lens, a.lens_div = items / lens_count, a.scale = scale;
+  a.out = out, a.ldo = ldo, a.strideO = strideO, a.lse = lse, a.ws = static_cast<float*>(workspace);
+  switch (D) {
+    case 32: return launch<T, 32>(a, items, s);
+    case 64: return launch<T, 64>(a, items, s);
+    case 96: return launch<T, 96>(a, items, s);
+    default: return launch<T, 128>(a, items, s);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mi_block_attention_decode_workspace_bytes(int32_t items, int32_t T, int32_t group, int32_t D, int32_t Smax, int32_t chunk) {
+  if (items <= 0 || T <= 0 || group <= 0 || D <= 0 || Smax < 0 || chunk < 1) return 0;
+  const int chunks = chunks_of(Smax, chunk);
+  if (chunks == 1) return 0;  // the walk stores out itself
+  return (size_t)items * (size_t)T * (size_t)chunks * (size_t)group * (size_t)(D + 2) * sizeof(float);
+}
+
+#define MI_DECODE_ARGS                                                                                                          \
+  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T,             \
+      int32_t Smax, int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t headK,  \
+      int64_t batchK, const uint16_t *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, \
+      int32_t group, int32_t chunk, float scale, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace,      \
+      size_t workspace_bytes, mi_stream_t stream
+#define MI_DECODE_PASS                                                                                                         \
+  rowptr, col, nnz, layouts, items, heads, T, Smax, D, q, ldq, strideQ, k, ldk, headK, batchK, v, ldv, headV, batchV, k_lens, \
+      lens_count, group, chunk, scale, out, ldo, strideO, lse, workspace, workspace_bytes, static_cast<hipStream_t>(stream)
+
+int mi_block_attention_decode_bf16(MI_DECODE_ARGS) { return decode_entry<Bf16>(MI_DECODE_PASS); }
+int mi_block_attention_decode_f16(MI_DECODE_ARGS) { return decode_entry<F16>(MI_DECODE_PASS); }
+
+}  // extern "C"

@@ -49,6 +49,7 @@ namespace {
 #include "custom_mm_softmax.inc"
 #include "custom_mm_attention.inc"
 #include "custom_mm_block_attention.inc"
+#include "custom_mm_block_attention_decode.inc"
 #include "custom_mm_bsr.inc"
 #include "custom_mm_bsr_linear.inc"
 
@@ -193,6 +194,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("block_attention_backward_ex", &block_attention_backward_ex,
         "(offsets, columns, t_offsets, t_columns, nnz, q, k, v, out, dout, lse, scale, causal, dq, dk, dv, q_lens or None, "
         "k_lens or None): (dq, dk, dv); dk, dv [batch / group, Sk, D] summed over the group in one accumulator");
+  m.def("block_attention_decode", &block_attention_decode,
+        "(offsets [layouts, Smax/64+1], columns, nnz, q [B, Hq, T, D], k, v [B, Hkv, Smax, D] through their own strides, "
+        "k_lens int32 [B] or [1], scale, chunk, out, lse [B, Hq, T]): the T newest tokens against the cache, the list cut into "
+        "chunks of `chunk` entries and merged in order");
   m.def("bsr_mm", &bsr_mm,
         "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
         "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");

@@ -1789,6 +1789,151 @@ def block_sparse_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, la
 
 
 # --------------------------------------------------------------------------- #
+# block-sparse attention for decoding: split key walks over a KV cache
+# --------------------------------------------------------------------------- #
+
+_DECODE_MAX_GROUP = 16   # query heads per k / v head: the own rows of one 16-row MFMA tile
+_DECODE_MAX_GRID = 65535  # B·Hkv and T are grid dimensions: no item loop
+_DECODE_CHUNK = 16       # list entries per workgroup when chunk=None: a constant — never a function of the batch — to be
+#                          fitted over (Smax, D) by tools/bench_block_attention_decode.py; not measured yet
+_DECODE_SIZES_TEXT = ('bfloat16 or float16 operands, head size D in {32, 64, 96, 128}, block a multiple of 64, Smax a multiple '
+                      'of block, 1 to 16 query heads per k / v head')
+
+
+def block_attention_decode_takes(dtype, D: int, block: int, group: int) -> bool:
+    '''Whether block_sparse_attention_decode takes head size D, block size `block` and `group` query heads per k / v head
+    in `dtype` — a function of these alone: block_attention_takes(dtype, D, block) and 1 ≤ group ≤ 16.'''
+    return block_attention_takes(dtype, D, block) and isinstance(group, int) and not isinstance(group, bool) and \
+        1 <= group <= _DECODE_MAX_GROUP
+
+
+def _decode_chunk(Smax: int, D: int) -> int:
+    '''The list entries one workgroup walks when the caller names no chunk: a function of (Smax, D) only.'''
+    return _DECODE_CHUNK
+
+
+def _check_cache_strides(what, name, t, D):
+    '''The cache is read through its own strides and never copied: the ValueError names the stride that does not fit.'''
+    B, H, S, _ = t.shape
+    sb, sh, sr, sd = t.stride()
+    if sd != 1:
+        raise ValueError(f'{what}: {name} must have a last stride of 1, got {sd} (the cache is never copied)')
+    if S > 1 and (sr < D or sr % 8 != 0):
+        raise ValueError(f'{what}: {name}\'s row stride must be a multiple of 8 elements and at least D = {D}, got {sr} '
+                         f'(the cache is never copied)')
+    if H > 1 and (sh < 0 or sh % 8 != 0):
+        raise ValueError(f'{what}: {name}\'s head stride must be a multiple of 8 elements, got {sh} (the cache is never copied)')
+    if B > 1 and (sb < 0 or sb % 8 != 0):
+        raise ValueError(f'{what}: {name}\'s batch stride must be a multiple of 8 elements, got {sb} (the cache is never copied)')
+    if t.data_ptr() % 16 != 0:
+        raise ValueError(f'{what}: {name}\'s data pointer must be 16-byte aligned (the cache is never copied)')
+
+
+def _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block, chunk):
+    '''Every refusal of block_sparse_attention_decode, before the first device call, split as
+    _check_block_attention_operands splits them: ValueError for what an operand is, RuntimeError for operands that do not go
+    together (mixed dtypes, host tensors / devices).  Returns the group: query heads per k / v head.'''
+    _check_csr(what, 'layout', layout)
+    _check_lowp_operands(what, (('q', q), ('k', k), ('v', v)), _DECODE_SIZES_TEXT)
+    if isinstance(block, bool) or not isinstance(block, int) or block <= 0 or block % _BLOCK_TILE != 0:
+        raise ValueError(f'{what}: block must be a positive multiple of 64, got {block!r} (accepted: {_DECODE_SIZES_TEXT})')
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1 or chunk >= 2 ** 31):
+        raise ValueError(f'{what}: chunk must be None or a positive int, got {chunk!r}')
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError(f'{what}: q must be [B, Hq, T, D] and k, v [B, Hkv, Smax, D], got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
+    B, Hq, T, D = q.shape
+    if D not in _BLOCK_HEAD_SIZES:
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_DECODE_SIZES_TEXT})')
+    Hkv, Smax = k.shape[1], k.shape[2]
+    if k.shape[0] != B or k.shape[3] != D or Hkv < 1 or Hq % Hkv != 0:
+        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs k {(B, "Hkv", "Smax", D)} with Hkv a divisor of {Hq}, '
+                         f'got {tuple(k.shape)}')
+    group = Hq // Hkv
+    if not 1 <= group <= _DECODE_MAX_GROUP:
+        raise ValueError(f'{what}: {Hq} query heads over {Hkv} k / v heads is a group of {group}; 1 to {_DECODE_MAX_GROUP} are '
+                         f'taken (accepted: {_DECODE_SIZES_TEXT})')
+    if tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f'{what}: v must be a dense tensor with k\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
+    if T < 1:
+        raise ValueError(f'{what}: q must hold T >= 1 new tokens, got T = {T}')
+    if Smax % block != 0:
+        raise ValueError(f'{what}: Smax = {Smax} must be a multiple of block = {block} (accepted: {_DECODE_SIZES_TEXT})')
+    l_lead = tuple(layout.shape[:-2])
+    if tuple(layout.shape[-2:]) != (Smax // block, Smax // block) or l_lead not in ((), (Hkv,), (B, Hkv)):
+        raise ValueError(f'{what}: the layout must have shape [*l_lead, Smax/block, Smax/block] = [*l_lead, {Smax // block}, '
+                         f'{Smax // block}] with l_lead empty, ({Hkv},) or ({B}, {Hkv}) — indexed by the k / v item —, got '
+                         f'{tuple(layout.shape)}')
+    if torch.Tensor.values(layout).numel() * (block // _BLOCK_TILE) ** 2 >= 2 ** 31:
+        raise ValueError(f'{what}: the layout in 64-blocks does not fit int32 indices')
+    if B * Hkv > _DECODE_MAX_GRID or T > _DECODE_MAX_GRID:
+        raise ValueError(f'{what}: B·Hkv = {B * Hkv} and T = {T} must each be at most {_DECODE_MAX_GRID} (they are grid dimensions)')
+    if not isinstance(k_lens, torch.Tensor) or k_lens.layout != torch.strided:
+        raise ValueError(f'{what}: k_lens is required and must be a dense tensor')
+    if k_lens.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'{what}: k_lens must be an int32 or int64 tensor, got {k_lens.dtype}')
+    if tuple(k_lens.shape) not in ((), (B,)):
+        raise ValueError(f'{what}: k_lens must have shape ({B},) — one length per batch item — or be 0-d, got {tuple(k_lens.shape)}')
+    _check_cache_strides(what, 'k', k, D)
+    _check_cache_strides(what, 'v', v, D)
+    _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k=k, v=v, k_lens=k_lens)
+    return group
+
+
+def block_sparse_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
+                                  block: int = 64, scale=None, *, chunk=None, return_lse: bool = False):
+    '''Block-sparse attention of the T ≥ 1 newest tokens of every item against its key / value cache, on the matrix cores:
+    q [B, Hq, T, D] (contiguous or made so: it is small), k and v [B, Hkv, Smax, D] — the cache, with the new tokens' keys
+    and values already written —, all bfloat16 or all float16, Hq = G · Hkv with 1 ≤ G ≤ 16 (query head h reads k / v head
+    h // G, torch SDPA's enable_gqa convention), D ∈ {32, 64, 96, 128}, Smax a multiple of block, block a multiple of 64
+    (block_attention_decode_takes).  THE CACHE IS NEVER COPIED: k and v are read through their own strides — last stride 1,
+    row stride ≥ D, row, head and batch strides multiples of 8 elements, a 16-byte aligned data pointer — so [B, Hkv, Smax, D]
+    and a [B, Smax, Hkv, D].transpose(1, 2) view both work; anything else raises ValueError naming the stride.
+
+    k_lens (required) is an int32 / int64 device tensor [B], or 0-d for one length; it is narrowed to int32 on the device,
+    never read back, and clamped to [0, Smax] by the kernel.  Token t of item b stands at pos = k_lens[b] − T + t and sees
+    key j iff j ≤ pos and the layout lists block (pos // block, j // block).  A token with pos < 0 does not exist: its out
+    row is zero and its lse −inf; so are those of a token that sees nothing.  Positions outside the listed blocks, beyond
+    pos, or between the rows of a strided cache are never read.
+
+    `layout` is the layout of block_sparse_attention, a CSR tensor [*l_lead, Smax/block, Smax/block] — the same tensor
+    serves prefill and decode, and its expansion into 64-blocks is the one record both calls keep on it.  l_lead is empty,
+    (Hkv,) or (B, Hkv): k / v item c of the flattened [B, Hkv] uses layout c mod L, and the G query heads of a group SHARE
+    their k / v head's layout.  This differs from block_sparse_attention, which indexes the layout by the QUERY item;
+    per-query-head layouts inside a group are not supported here.
+
+    The order of summation is part of the contract.  The 64-block list of layout row pos // 64 is cut into chunks of `chunk`
+    consecutive list entries by list position (an entry outside the grid or wholly beyond pos is skipped inside its chunk
+    and does not move the cut); a chunk gives one partial per row — running maximum, sum, unnormalised fp32 accumulator —,
+    its entries dealt to four waves (wave w takes entries w, w + 4, …) whose partials are merged in ascending wave order;
+    the chunks' partials are merged in ascending chunk order; out is rounded once, at the final store.  The bits of an
+    output row depend on its own item's operands, its list, pos and chunk only — never on B, the neighbours, the launch, or
+    whether the layout came shared or per item.  chunk=None takes a constant of the module (a function of (Smax, D) at
+    most, never of the batch).  No atomics and no read-back: the call can be captured in a graph and replayed after k_lens
+    and the cache were updated in place.
+
+    Returns out [B, Hq, T, D] in q's dtype, or with return_lse=True (out, lse) with lse float32 [B, Hq, T].  There is NO
+    autograd: the result does not require grad whatever the operands do.  scale defaults to 1/√D.'''
+    what = 'block_sparse_attention_decode'
+    group = _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block, chunk)
+    B, Hq, T, D = q.shape
+    Smax = k.shape[2]
+    if scale is None:
+        scale = 1.0 / float(D) ** 0.5
+    if chunk is None:
+        chunk = _decode_chunk(Smax, D)
+    with torch.no_grad():
+        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
+        offsets, columns, nnz, _ = rec['fwd']
+        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
+        qc = q.detach().contiguous()
+        out = torch.empty_like(qc)
+        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
+        if out.numel() > 0:
+            custom_mm.block_attention_decode(offsets, columns, nnz, qc, k.detach(), v.detach(), lens, float(scale), int(chunk), out, lse)
+    return (out, lse) if return_lse else out
+
+
+# --------------------------------------------------------------------------- #
 # block-sparse (BSR) × dense products on the matrix cores (DESIGN.md §3.15)
 # --------------------------------------------------------------------------- #
 
