@@ -1076,6 +1076,44 @@ int mi_block_attention_decode_f16(const int32_t* rowptr, const int32_t* col, int
                                   int64_t strideO, float* lse, void* workspace, size_t workspace_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * … over a paged cache: mi_block_attention_decode_* with k and v given as ONE POOL OF PAGES and a block
+ * table per batch item.  The arguments are those of mi_block_attention_decode_* except:
+ *   k_pages, v_pages   the pool, never copied: row r of head h of pool page e at k_pages + e · pageK + h · headK + r · ldk
+ *              (v likewise); 16-byte aligned, ldk ≥ D, every stride a multiple of 8 elements ([P, heads, page, D] and
+ *              [P, page, heads, D] both fit).  With pages == 0 the pool is never read and may be NULL;
+ *   block_table, table_ld   int32 on the device, 4-byte aligned: row c / heads, table_ld ≥ Smax / page entries apart, holds
+ *              the pool page of each of the item's Smax / page logical pages — all heads of a batch item share its row.
+ *              Key j of k / v item c is row j % page of head c % heads of pool page block_table[(c / heads) · table_ld +
+ *              j / page].  An entry outside [0, pages) makes the keys of its logical page INVISIBLE: nothing is loaded,
+ *              their scores are −inf.  Entries of pages wholly beyond pos or only in unlisted blocks are never read;
+ *   pages      pool pages P ≥ 0;
+ *   page       keys per page: a power of two ≥ 16.  Smax, the logical length, is a multiple of page (and of 64).
+ * For a pool and table whose seen entries are in range, out and lse have the bits of mi_block_attention_decode_* with the
+ * same chunk on the gathered cache — independent of pages, of where the pages lie and of page.  The workspace is that of
+ * mi_block_attention_decode_workspace_bytes.  No atomics, no read-back: graph-capturable while k_lens, the pool and the
+ * table are updated in place.
+ * Validation before any HIP call: everything mi_block_attention_decode_* refuses, page < 16 or not a power of two,
+ * Smax % page != 0, pages < 0, a NULL or misaligned block_table (with Smax > 0), table_ld < Smax / page, a NULL / misaligned
+ * pool pointer or a bad pool stride (with pages > 0) → MI_EINVAL; a short workspace → MI_ENOMEM.
+ * ------------------------------------------------------------------------ */
+int mi_block_attention_decode_paged_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items,
+                                         int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table, int64_t table_ld,
+                                         int32_t pages, int32_t page, int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ,
+                                         const uint16_t* k_pages, int64_t ldk, int64_t headK, int64_t pageK,
+                                         const uint16_t* v_pages, int64_t ldv, int64_t headV, int64_t pageV,
+                                         const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale,
+                                         uint16_t* out, int64_t ldo, int64_t strideO, float* lse, void* workspace,
+                                         size_t workspace_bytes, mi_stream_t stream);
+int mi_block_attention_decode_paged_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items,
+                                        int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table, int64_t table_ld,
+                                        int32_t pages, int32_t page, int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ,
+                                        const uint16_t* k_pages, int64_t ldk, int64_t headK, int64_t pageK,
+                                        const uint16_t* v_pages, int64_t ldv, int64_t headV, int64_t pageV,
+                                        const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale,
+                                        uint16_t* out, int64_t ldo, int64_t strideO, float* lse, void* workspace,
+                                        size_t workspace_bytes, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in
  * bfloat16 / float16 (T, 2-byte bit patterns) with A given as the kept 64 × 64 blocks of a CSR block list, shared by
  * every item of the batch, and the sampled product on the same list:

@@ -21,6 +21,11 @@
 //    straddling block beyond pos are staged as zeros, their scores masked to −inf.  Offsets are clamped to nnz, a column
 //    outside the grid is skipped: a malformed layout reads nothing outside the operands.
 //
+//  * Paged caches (mi_block_attention_decode_paged_{bf16,f16}): k and v are one pool of pages of 2^s ≥ 16 keys
+//    and a block table per batch item names the pool page of each logical page; the walk's tile addressing is a compile-time
+//    form of the kernel (contiguous / pages ≥ 64 keys / pages of 16 or 32 keys), everything else is shared.  A table entry
+//    outside the pool hides its page's keys: nothing is loaded for them, zeros are staged, their scores are −inf.
+//
 // Kernel: grid (chunks, items, T), 256 threads.  No workgroup barrier inside the walk.  A wave loads the k tile of an
 // entry as 16-byte global loads straight into MFMA A fragments (lane (li, lg): row 16f + li, columns 32s + 8lg … + 7), the v
 // tile into registers and from there into a wave-private transposed LDS image [D][64 + 8] (a wave-level fence between its
@@ -68,7 +73,18 @@ struct Args {
   long ldo, strideO;
   float* lse;  // [items · group][T]
   float* ws;   // [items][T][chunks][group][D + 2]: m, l, o[D] — read and written only with chunks > 1
+  // the paged forms: k and v are pools of pages of 1 << page_shift keys; key j of k / v item c lies at
+  // k + table[(c / heads) · table_ld + (j >> page_shift)] · pageK + (c % heads) · headK + (j & (page − 1)) · ldk
+  const int32_t* table;  // [items / heads][table_ld]; an entry outside [0, pages) hides the keys of its logical page
+  long table_ld;
+  int pages, page_shift;
+  long pageK, pageV;
 };
+
+// How the walk finds the 64 keys of a list entry: a compile-time form of the kernel, as LENS is in block_attention.hip
+constexpr int kContiguous = 0;  // one [Smax][D] run per k / v item behind fixed strides
+constexpr int kPaged = 1;       // a pool of pages ≥ 64 keys: the tile lies inside one page — one table entry per tile
+constexpr int kPagedSmall = 2;  // pages of 16 or 32 keys: the tile spans 64 / page whole pages — one entry per page
 
 __device__ __forceinline__ unsigned half_of(uint4 v, int i) {
   const unsigned w = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
@@ -105,6 +121,65 @@ __device__ __forceinline__ void load_v(uint4 (&vr)[D / 32][4], const uint16_t* s
     for (int r = 0; r < 4; ++r) {
       if (4 * li + r < limit)
         vr[i][r] = *reinterpret_cast<const uint4*>(src + (long)(4 * li + r) * ld + 8 * (lg + 4 * i));
+      else
+        vr[i][r] = uint4{0u, 0u, 0u, 0u};
+    }
+}
+
+// The table entries of the logical pages of tile J of a paged cache, one per 16-row fragment f of the tile (fragment f lies
+// inside logical page (64J + 16f) >> page_shift because 16 divides the page): with pages ≥ 64 keys all four are the tile's
+// one page.  J < Smax / 64, so the index stays below Smax / page ≤ table_ld.
+template <int FORM>
+__device__ __forceinline__ void read_pages(int (&e)[4], const int32_t* trow, int J, int shift) {
+  if constexpr (FORM == kPaged) {
+    e[0] = e[1] = e[2] = e[3] = trow[(J * kB) >> shift];
+  } else {
+#pragma unroll
+    for (int f = 0; f < 4; ++f) e[f] = trow[(J * kB + 16 * f) >> shift];
+  }
+}
+
+// bit f: fragment f of the tile lies in a page of the pool; the rows of the others are invisible and never loaded
+__device__ __forceinline__ unsigned valid_pages(const int (&e)[4], int pages) {
+  unsigned ok = 0;
+#pragma unroll
+  for (int f = 0; f < 4; ++f) ok |= ((unsigned)e[f] < (unsigned)pages ? 1u : 0u) << f;
+  return ok;
+}
+
+// load_k over pages of 16 or 32 keys: fragment f (rows 16f … 16f + 15 of the tile) starts at row (16f) & (page − 1) of its
+// own page e[f]; a fragment of an invalid page is zero, whatever its entry holds
+template <int D>
+__device__ __forceinline__ void load_k_pages(uint4 (&kf)[4][D / 32], const uint16_t* pool, long ld, long pageStride, const int (&e)[4],
+                                             unsigned ok, int in_page, int li, int lg, int limit) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const uint16_t* src = pool + (long)e[f] * pageStride + (long)(((16 * f) & in_page) + li) * ld + 8 * lg;
+    const bool take = ((ok >> f) & 1u) && 16 * f + li < limit;
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s) {
+      if (take)
+        kf[f][s] = *reinterpret_cast<const uint4*>(src + 32 * s);
+      else
+        kf[f][s] = uint4{0u, 0u, 0u, 0u};
+    }
+  }
+}
+
+// load_v over pages of 16 or 32 keys: the lane's rows 4li … 4li + 3 lie in fragment li / 4, so in one page (4 divides 16)
+template <int D>
+__device__ __forceinline__ void load_v_pages(uint4 (&vr)[D / 32][4], const uint16_t* pool, long ld, long pageStride, const int (&e)[4],
+                                             unsigned ok, int in_page, int li, int lg, int limit) {
+  const int f = li >> 2;
+  const int mine = f == 0 ? e[0] : f == 1 ? e[1] : f == 2 ? e[2] : e[3];
+  const uint16_t* src = pool + (long)mine * pageStride + (long)((4 * li) & in_page) * ld + 8 * lg;
+  const bool valid = (ok >> f) & 1u;
+#pragma unroll
+  for (int i = 0; i < D / 32; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (valid && 4 * li + r < limit)
+        vr[i][r] = *reinterpret_cast<const uint4*>(src + (long)r * ld + 32 * i);
       else
         vr[i][r] = uint4{0u, 0u, 0u, 0u};
     }
@@ -187,12 +262,19 @@ __device__ __forceinline__ void finish(const Args& a, int c, int t, int g, int d
   if (d == 0) a.lse[item * a.T + t] = L == 0.f ? -INFINITY : M + __logf(L);
 }
 
-template <class T, int D>
+// The walk of one chunk and the merge of its four waves, in the three forms of tile addressing (FORM).  The paged forms
+// differ from the contiguous one in where a tile's rows are loaded from and in the validity of a page, which joins the
+// position mask — the summation, the chunking and the merge are the same statements, so a paged call has the bits of the
+// contiguous call on the gathered cache.
+template <class T, int D, int FORM>
 __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   constexpr int kPStr = D + 4;  // a wave's partial in its own image: [16][D + 4] floats — o[D], m, l
   __shared__ __attribute__((aligned(16))) unsigned short Vt[kWaves][D * kTStr];
   static_assert(kMaxGroup * kPStr * 4 <= D * kTStr * 2, "the partial fits the image");
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lg = lane >> 4;
+  // the paged forms say that the wave's number is uniform: list positions, columns and table entries stay in scalar
+  // registers, and the page bases cost the vector file nothing
+  const int w = FORM == kContiguous ? tid >> 6 : __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ch = blockIdx.x, c = blockIdx.y, t = blockIdx.z;
   const int G = a.group;
   int klen = a.k_lens[c / a.lens_div];
@@ -221,8 +303,9 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
     }
     return;
   }
-  const uint16_t* K = a.k + (long)(c / a.heads) * a.batchK + (long)(c % a.heads) * a.headK;
-  const uint16_t* V = a.v + (long)(c / a.heads) * a.batchV + (long)(c % a.heads) * a.headV;
+  // (a pool has no batch stride: the item's pages come from its table row)
+  const uint16_t* K = a.k + (FORM == kContiguous ? (long)(c / a.heads) * a.batchK : 0L) + (long)(c % a.heads) * a.headK;
+  const uint16_t* V = a.v + (FORM == kContiguous ? (long)(c / a.heads) * a.batchV : 0L) + (long)(c % a.heads) * a.headV;
   unsigned short* Vw = Vt[w];
 
   uint4 qf[D / 32];  // the own rows as B fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of query head li
@@ -240,23 +323,74 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   float m = -INFINITY, l = 0.f;
 
   uint4 kf[4][D / 32], vr[D / 32][4];
-  if (p < end) {
-    const int J = a.col[p];
-    load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB);
-    load_v<D>(vr, V + (long)J * kB * a.ldv, a.ldv, li, lg, pos + 1 - J * kB);
+  // Paged forms: the tile whose loads are in flight (J, its table entries e, their validity ok) and the entry after it
+  // (pn, Jn, en).  The chain col[p] → table → tile is cut in two: the column and the table entries of an entry are read
+  // ONE ITERATION EARLY, right after the loads of the entry before it were issued, and have that entry's softmax and P·V
+  // to arrive — so the tile loads are issued right after the score MFMAs from values that are already there.
+  int J = 0, Jn = 0, pn = end, e[4] = {0, 0, 0, 0}, en[4] = {0, 0, 0, 0};
+  unsigned ok = 0;
+  const int32_t* trow = nullptr;
+  const int in_page = FORM == kContiguous ? 0 : (1 << a.page_shift) - 1;
+  auto issue = [&]() {  // the loads of tile J of the pool; an invalid page loads nothing and stages zeros
+    const int limit = pos + 1 - J * kB;
+    if constexpr (FORM == kPaged) {
+      const long row = (J * kB) & in_page;
+      load_k<D>(kf, K + (long)e[0] * a.pageK + row * a.ldk, a.ldk, li, lg, ok ? limit : 0);
+      load_v<D>(vr, V + (long)e[0] * a.pageV + row * a.ldv, a.ldv, li, lg, ok ? limit : 0);
+    } else {
+      load_k_pages<D>(kf, K, a.ldk, a.pageK, e, ok, in_page, li, lg, limit);
+      load_v_pages<D>(vr, V, a.ldv, a.pageV, e, ok, in_page, li, lg, limit);
+    }
+  };
+  auto look_ahead = [&](int from) {  // the next computed entry at or after `from`, its column and its table entries
+    pn = next_entry(a.col, from, end, pos, a.blocks);
+    if (pn < end) {
+      Jn = a.col[pn];
+      read_pages<FORM>(en, trow, Jn, a.page_shift);
+    }
+  };
+  if constexpr (FORM == kContiguous) {
+    if (p < end) {
+      const int J = a.col[p];
+      load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB);
+      load_v<D>(vr, V + (long)J * kB * a.ldv, a.ldv, li, lg, pos + 1 - J * kB);
+    }
+  } else {
+    trow = a.table + (long)(c / a.heads) * a.table_ld;
+    if (p < end) {
+      J = a.col[p];
+      read_pages<FORM>(e, trow, J, a.page_shift);
+      ok = valid_pages(e, a.pages);
+      issue();
+      look_ahead(p + kWaves);
+    }
   }
   while (p < end) {
-    const int visible = pos + 1 - a.col[p] * kB;  // keys of this block the token sees (≥ 1; 64 or more: all)
+    // keys of this block the token sees (≥ 1; 64 or more: all)
+    const int visible = pos + 1 - (FORM == kContiguous ? a.col[p] : J) * kB;
+    const unsigned seen = ok;  // … and the fragments of it that lie in a page (paged forms)
     fence_wave();  // the previous entry's reads of the image are done
     store_transposed<D>(Vw, vr, li, lg);
     fence_wave();
     f32x4 s[4];
     score<T, D>(s, kf, qf);
-    p = next_entry(a.col, p + kWaves, end, pos, a.blocks);
-    if (p < end) {  // the next entry's loads are in flight while this one is computed
-      const int J = a.col[p];
-      load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB);
-      load_v<D>(vr, V + (long)J * kB * a.ldv, a.ldv, li, lg, pos + 1 - J * kB);
+    if constexpr (FORM == kContiguous) {
+      p = next_entry(a.col, p + kWaves, end, pos, a.blocks);
+      if (p < end) {  // the next entry's loads are in flight while this one is computed
+        const int J = a.col[p];
+        load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB);
+        load_v<D>(vr, V + (long)J * kB * a.ldv, a.ldv, li, lg, pos + 1 - J * kB);
+      }
+    } else {
+      p = pn;
+      if (p < end) {  // … from the column and the table entries read an iteration ago; then the look-ahead moves on
+        J = Jn;
+#pragma unroll
+        for (int f = 0; f < 4; ++f) e[f] = en[f];
+        ok = valid_pages(e, a.pages);
+        issue();
+        look_ahead(p + kWaves);
+      }
     }
     float mt = -INFINITY;
 #pragma unroll
@@ -265,6 +399,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
       for (int r = 0; r < 4; ++r) {
         float x = s[f][r] * a.scale;
         if (16 * f + 4 * lg + r >= visible) x = -INFINITY;
+        if (FORM != kContiguous && !((seen >> f) & 1u)) x = -INFINITY;  // a key of an invalid page
         s[f][r] = x;
         mt = fmaxf(mt, x);
       }
@@ -355,21 +490,32 @@ int chunks_of(int32_t Smax, int32_t chunk) {  // from the shape alone; a list ha
 
 template <class T, int D>
 int launch(const Args& a, int items, hipStream_t s) {
-  hipLaunchKernelGGL((block_attention_decode_kernel<T, D>), dim3((unsigned)a.chunks, (unsigned)items, (unsigned)a.T), dim3(256), 0, s, a);
+  const dim3 grid((unsigned)a.chunks, (unsigned)items, (unsigned)a.T);
+  if (!a.table)
+    hipLaunchKernelGGL((block_attention_decode_kernel<T, D, kContiguous>), grid, dim3(256), 0, s, a);
+  else if (a.page_shift >= 6)
+    hipLaunchKernelGGL((block_attention_decode_kernel<T, D, kPaged>), grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((block_attention_decode_kernel<T, D, kPagedSmall>), grid, dim3(256), 0, s, a);
   const int st = mi::check_launch();
   if (st != MI_OK || a.chunks == 1) return st;
   hipLaunchKernelGGL((block_attention_decode_combine_kernel<T>), dim3((unsigned)items, (unsigned)a.T), dim3(128), 0, s, a, D);
   return mi::check_launch();
 }
 
-// Every check comes before the first HIP call.
+// Every check comes before the first HIP call.  page == 0: the contiguous cache, `outerK` / `outerV` its batch strides and
+// no table; page > 0: a pool of `pages` pages of `page` keys, `outerK` / `outerV` its page strides, Smax = the table's
+// logical pages · page.
 template <class T>
 int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T_,
                  int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k, int64_t ldk,
-                 int64_t headK, int64_t batchK, const uint16_t* v, int64_t ldv, int64_t headV, int64_t batchV,
+                 int64_t headK, int64_t outerK, const uint16_t* v, int64_t ldv, int64_t headV, int64_t outerV,
                  const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale, uint16_t* out, int64_t ldo,
-                 int64_t strideO, float* lse, void* workspace, size_t workspace_bytes, hipStream_t s) {
+                 int64_t strideO, float* lse, void* workspace, size_t workspace_bytes, hipStream_t s, const int32_t* table = nullptr,
+                 int64_t table_ld = 0, int32_t pages = 0, int32_t page = 0) {
   if (group < 1 || group > kMaxGroup || chunk < 1 || !takes_width(D)) return MI_EINVAL;
+  const bool paged = page != 0;
+  if (paged && (page < 16 || (page & (page - 1)) != 0 || pages < 0 || Smax % page != 0)) return MI_EINVAL;
   if (nnz < 0 || layouts < 0 || items < 0 || heads < 0 || T_ < 0 || Smax < 0 || Smax % kB != 0) return MI_EINVAL;
   if (nnz > 0x7fffffffLL) return MI_ERANGE;
   if (items > 65535 || T_ > 65535) return MI_EINVAL;  // the grid's y and z: no item loop
@@ -379,9 +525,10 @@ int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t
   if (!lse || (reinterpret_cast<uintptr_t>(lse) & 3u)) return MI_EINVAL;
   if (!q || !mi::aligned16(q) || ldq < D || !stride_ok(ldq) || !stride_ok(strideQ)) return MI_EINVAL;
   if (!out || !mi::aligned16(out) || ldo < D || !stride_ok(ldo) || !stride_ok(strideO)) return MI_EINVAL;
-  if (nnz > 0 && Smax > 0) {
-    if (!k || !mi::aligned16(k) || ldk < D || !stride_ok(ldk) || !stride_ok(headK) || !stride_ok(batchK)) return MI_EINVAL;
-    if (!v || !mi::aligned16(v) || ldv < D || !stride_ok(ldv) || !stride_ok(headV) || !stride_ok(batchV)) return MI_EINVAL;
+  if (paged && Smax > 0 && (!table || (reinterpret_cast<uintptr_t>(table) & 3u) || table_ld < Smax / page)) return MI_EINVAL;
+  if (nnz > 0 && Smax > 0 && (!paged || pages > 0)) {  // (an empty pool is never read: every entry of the table is invalid)
+    if (!k || !mi::aligned16(k) || ldk < D || !stride_ok(ldk) || !stride_ok(headK) || !stride_ok(outerK)) return MI_EINVAL;
+    if (!v || !mi::aligned16(v) || ldv < D || !stride_ok(ldv) || !stride_ok(headV) || !stride_ok(outerV)) return MI_EINVAL;
   }
   const int chunks = chunks_of(Smax, chunk);
   if (chunks > 1) {
@@ -392,7 +539,13 @@ int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t
   a.rowptr = rowptr, a.col = col, a.nnz = nnz, a.layouts = layouts, a.blocks = Smax / kB, a.heads = heads, a.group = group;
   a.T = T_, a.chunk = chunk, a.chunks = chunks, a.smax = Smax;
   a.q = q, a.ldq = ldq, a.strideQ = strideQ;
-  a.k = k, a.ldk = ldk, a.headK = headK, a.batchK = batchK, a.v = v, a.ldv = ldv, a.headV = headV, a.batchV = batchV;
+  a.k = k, a.ldk = ldk, a.headK = headK, a.v = v, a.ldv = ldv, a.headV = headV;
+  if (paged && Smax > 0) {  // (Smax == 0: no list has an entry, the contiguous form stores the zero rows)
+    a.table = table, a.table_ld = table_ld, a.pages = pages, a.page_shift = __builtin_ctz((unsigned)page);
+    a.pageK = outerK, a.pageV = outerV;
+  } else {
+    a.batchK = outerK, a.batchV = outerV;
+  }
   a.k_lens = k_lens, a.lens_div = items / lens_count, a.scale = scale;
   a.out = out, a.ldo = ldo, a.strideO = strideO, a.lse = lse, a.ws = static_cast<float*>(workspace);
   switch (D) {
@@ -426,5 +579,23 @@ size_t mi_block_attention_decode_workspace_bytes(int32_t items, int32_t T, int32
 
 int mi_block_attention_decode_bf16(MI_DECODE_ARGS) { return decode_entry<Bf16>(MI_DECODE_PASS); }
 int mi_block_attention_decode_f16(MI_DECODE_ARGS) { return decode_entry<F16>(MI_DECODE_PASS); }
+
+#define MI_DECODE_PAGED_ARGS                                                                                                  \
+  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T,           \
+      int32_t Smax, const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page, int32_t D, const uint16_t *q,  \
+      int64_t ldq, int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t headK, int64_t batchK, const uint16_t *v,         \
+      int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group, int32_t chunk,    \
+      float scale, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes,          \
+      mi_stream_t stream
+// (k, batchK and v, batchV stand for k_pages, pageK and v_pages, pageV of the header)  A page of 0 keys would name the
+// contiguous form: it is refused here like every page that is no power of two ≥ 16.
+#define MI_DECODE_PAGED_PASS MI_DECODE_PASS, block_table, table_ld, pages, page
+
+int mi_block_attention_decode_paged_bf16(MI_DECODE_PAGED_ARGS) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16>(MI_DECODE_PAGED_PASS);
+}
+int mi_block_attention_decode_paged_f16(MI_DECODE_PAGED_ARGS) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16>(MI_DECODE_PAGED_PASS);
+}
 
 }  // extern "C"

@@ -50,6 +50,7 @@ namespace {
 #include "custom_mm_attention.inc"
 #include "custom_mm_block_attention.inc"
 #include "custom_mm_block_attention_decode.inc"
+#include "custom_mm_block_attention_decode_paged.inc"
 #include "custom_mm_bsr.inc"
 #include "custom_mm_bsr_linear.inc"
 
@@ -198,6 +199,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(offsets [layouts, Smax/64+1], columns, nnz, q [B, Hq, T, D], k, v [B, Hkv, Smax, D] through their own strides, "
         "k_lens int32 [B] or [1], scale, chunk, out, lse [B, Hq, T]): the T newest tokens against the cache, the list cut into "
         "chunks of `chunk` entries and merged in order");
+  m.def("block_attention_decode_paged", &block_attention_decode_paged,
+        "(offsets [layouts, Smax/64+1], columns, nnz, q [B, Hq, T, D], k_pages, v_pages [P, Hkv, page, D] through their own strides, "
+        "block_table int32 [B, W] (Smax = W * page; last stride 1, any row stride >= W), k_lens int32 [B] or [1], scale, chunk, out, "
+        "lse [B, Hq, T]): block_attention_decode over a pool of pages; an entry outside [0, P) hides its page's keys");
   m.def("bsr_mm", &bsr_mm,
         "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
         "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");

@@ -1812,8 +1812,9 @@ def _decode_chunk(Smax: int, D: int) -> int:
     return _DECODE_CHUNK
 
 
-def _check_cache_strides(what, name, t, D):
-    '''The cache is read through its own strides and never copied: the ValueError names the stride that does not fit.'''
+def _check_cache_strides(what, name, t, D, outer='batch'):
+    '''The cache is read through its own strides and never copied: the ValueError names the stride that does not fit
+    (`outer` names the first one: the batch stride of a cache, the page stride of a pool).'''
     B, H, S, _ = t.shape
     sb, sh, sr, sd = t.stride()
     if sd != 1:
@@ -1824,36 +1825,32 @@ def _check_cache_strides(what, name, t, D):
     if H > 1 and (sh < 0 or sh % 8 != 0):
         raise ValueError(f'{what}: {name}\'s head stride must be a multiple of 8 elements, got {sh} (the cache is never copied)')
     if B > 1 and (sb < 0 or sb % 8 != 0):
-        raise ValueError(f'{what}: {name}\'s batch stride must be a multiple of 8 elements, got {sb} (the cache is never copied)')
+        raise ValueError(f'{what}: {name}\'s {outer} stride must be a multiple of 8 elements, got {sb} (the cache is never copied)')
     if t.data_ptr() % 16 != 0:
         raise ValueError(f'{what}: {name}\'s data pointer must be 16-byte aligned (the cache is never copied)')
 
 
-def _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block, chunk):
-    '''Every refusal of block_sparse_attention_decode, before the first device call, split as
-    _check_block_attention_operands splits them: ValueError for what an operand is, RuntimeError for operands that do not go
-    together (mixed dtypes, host tensors / devices).  Returns the group: query heads per k / v head.'''
+def _check_decode_call(what, names, q, k, v, layout, block, chunk):
+    '''What block_sparse_attention_decode and its paged form refuse before they look at a shape: the layout's and the
+    operands' kinds, block, chunk.  `names` are the two cache operands' names in the messages.'''
     _check_csr(what, 'layout', layout)
-    _check_lowp_operands(what, (('q', q), ('k', k), ('v', v)), _DECODE_SIZES_TEXT)
+    _check_lowp_operands(what, (('q', q), (names[0], k), (names[1], v)), _DECODE_SIZES_TEXT)
     if isinstance(block, bool) or not isinstance(block, int) or block <= 0 or block % _BLOCK_TILE != 0:
         raise ValueError(f'{what}: block must be a positive multiple of 64, got {block!r} (accepted: {_DECODE_SIZES_TEXT})')
     if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1 or chunk >= 2 ** 31):
         raise ValueError(f'{what}: chunk must be None or a positive int, got {chunk!r}')
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError(f'{what}: q must be [B, Hq, T, D] and k, v [B, Hkv, Smax, D], got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
-    B, Hq, T, D = q.shape
-    if D not in _BLOCK_HEAD_SIZES:
-        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_DECODE_SIZES_TEXT})')
-    Hkv, Smax = k.shape[1], k.shape[2]
-    if k.shape[0] != B or k.shape[3] != D or Hkv < 1 or Hq % Hkv != 0:
-        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs k {(B, "Hkv", "Smax", D)} with Hkv a divisor of {Hq}, '
-                         f'got {tuple(k.shape)}')
+
+
+def _check_decode_group(what, Hq, Hkv):
     group = Hq // Hkv
     if not 1 <= group <= _DECODE_MAX_GROUP:
         raise ValueError(f'{what}: {Hq} query heads over {Hkv} k / v heads is a group of {group}; 1 to {_DECODE_MAX_GROUP} are '
                          f'taken (accepted: {_DECODE_SIZES_TEXT})')
-    if tuple(v.shape) != tuple(k.shape):
-        raise ValueError(f'{what}: v must be a dense tensor with k\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
+    return group
+
+
+def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, k_lens, block):
+    '''The refusals of the decode calls that follow from (B, Hkv, T, Smax) alone, however the cache is stored.'''
     if T < 1:
         raise ValueError(f'{what}: q must hold T >= 1 new tokens, got T = {T}')
     if Smax % block != 0:
@@ -1873,6 +1870,26 @@ def _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block,
         raise ValueError(f'{what}: k_lens must be an int32 or int64 tensor, got {k_lens.dtype}')
     if tuple(k_lens.shape) not in ((), (B,)):
         raise ValueError(f'{what}: k_lens must have shape ({B},) — one length per batch item — or be 0-d, got {tuple(k_lens.shape)}')
+
+
+def _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block, chunk):
+    '''Every refusal of block_sparse_attention_decode, before the first device call, split as
+    _check_block_attention_operands splits them: ValueError for what an operand is, RuntimeError for operands that do not go
+    together (mixed dtypes, host tensors / devices).  Returns the group: query heads per k / v head.'''
+    _check_decode_call(what, ('k', 'v'), q, k, v, layout, block, chunk)
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError(f'{what}: q must be [B, Hq, T, D] and k, v [B, Hkv, Smax, D], got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
+    B, Hq, T, D = q.shape
+    if D not in _BLOCK_HEAD_SIZES:
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_DECODE_SIZES_TEXT})')
+    Hkv, Smax = k.shape[1], k.shape[2]
+    if k.shape[0] != B or k.shape[3] != D or Hkv < 1 or Hq % Hkv != 0:
+        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs k {(B, "Hkv", "Smax", D)} with Hkv a divisor of {Hq}, '
+                         f'got {tuple(k.shape)}')
+    group = _check_decode_group(what, Hq, Hkv)
+    if tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f'{what}: v must be a dense tensor with k\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
+    _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, k_lens, block)
     _check_cache_strides(what, 'k', k, D)
     _check_cache_strides(what, 'v', v, D)
     _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k=k, v=v, k_lens=k_lens)
@@ -1930,6 +1947,113 @@ def block_sparse_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Ten
         lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
         if out.numel() > 0:
             custom_mm.block_attention_decode(offsets, columns, nnz, qc, k.detach(), v.detach(), lens, float(scale), int(chunk), out, lse)
+    return (out, lse) if return_lse else out
+
+
+# --------------------------------------------------------------------------- #
+# … over a paged KV cache: a pool of pages and a block table per item
+# --------------------------------------------------------------------------- #
+
+_DECODE_MIN_PAGE = 16    # keys of the smallest page: a 16-row MFMA fragment of a k tile never straddles two pages
+_DECODE_PAGED_SIZES_TEXT = _DECODE_SIZES_TEXT + ', pages of a power of two >= 16 keys'
+
+
+def _page_ok(page) -> bool:
+    return isinstance(page, int) and not isinstance(page, bool) and page >= _DECODE_MIN_PAGE and page & (page - 1) == 0
+
+
+def block_attention_decode_paged_takes(dtype, D: int, block: int, group: int, page: int) -> bool:
+    '''Whether block_sparse_attention_decode_paged takes head size D, block size `block`, `group` query heads per k / v
+    head and pages of `page` keys in `dtype` — a function of these alone: block_attention_decode_takes(dtype, D, block,
+    group) and page a power of two ≥ 16.'''
+    return block_attention_decode_takes(dtype, D, block, group) and _page_ok(page)
+
+
+def _check_block_attention_decode_paged_operands(what, q, k_pages, v_pages, block_table, layout, k_lens, block, chunk):
+    '''Every refusal of block_sparse_attention_decode_paged before the first device call: those of the contiguous call
+    (the same functions, Smax = W · page) and the pool's and the table's own.  Returns the group.'''
+    _check_decode_call(what, ('k_pages', 'v_pages'), q, k_pages, v_pages, layout, block, chunk)
+    if q.dim() != 4 or k_pages.dim() != 4 or v_pages.dim() != 4:
+        raise ValueError(f'{what}: q must be [B, Hq, T, D] and k_pages, v_pages [P, Hkv, page, D], got {q.dim()}-d, '
+                         f'{k_pages.dim()}-d and {v_pages.dim()}-d')
+    B, Hq, T, D = q.shape
+    if D not in _BLOCK_HEAD_SIZES:
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_DECODE_PAGED_SIZES_TEXT})')
+    P, Hkv, page = k_pages.shape[0], k_pages.shape[1], k_pages.shape[2]
+    if k_pages.shape[3] != D or Hkv < 1 or Hq % Hkv != 0:
+        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs k_pages {("P", "Hkv", "page", D)} with Hkv a divisor of '
+                         f'{Hq}, got {tuple(k_pages.shape)}')
+    group = _check_decode_group(what, Hq, Hkv)
+    if tuple(v_pages.shape) != tuple(k_pages.shape):
+        raise ValueError(f'{what}: v_pages must be a dense tensor with k_pages\' shape {tuple(k_pages.shape)}, got '
+                         f'{tuple(v_pages.shape)}')
+    if not _page_ok(page):
+        raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} keys, got page = {page} '
+                         f'(accepted: {_DECODE_PAGED_SIZES_TEXT})')
+    if not isinstance(block_table, torch.Tensor) or block_table.layout != torch.strided:
+        raise ValueError(f'{what}: block_table is required and must be a dense tensor')
+    if block_table.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'{what}: block_table must be an int32 or int64 tensor, got {block_table.dtype}')
+    if block_table.dim() != 2 or block_table.shape[0] != B:
+        raise ValueError(f'{what}: block_table must have shape ({B}, W) — a row of logical pages per batch item —, got '
+                         f'{tuple(block_table.shape)}')
+    W = block_table.shape[1]
+    if W > 1 and block_table.stride(1) != 1:
+        raise ValueError(f'{what}: block_table must have a last stride of 1, got {block_table.stride(1)}')
+    if B > 1 and block_table.stride(0) < W:
+        raise ValueError(f'{what}: block_table\'s row stride must be at least W = {W}, got {block_table.stride(0)}')
+    _check_decode_layout_and_lens(what, B, Hkv, T, W * page, layout, k_lens, block)
+    _check_cache_strides(what, 'k_pages', k_pages, D, 'page')
+    _check_cache_strides(what, 'v_pages', v_pages, D, 'page')
+    _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k_pages=k_pages, v_pages=v_pages, block_table=block_table,
+                     k_lens=k_lens)
+    return group
+
+
+def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                                        layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *, chunk=None,
+                                        return_lse: bool = False):
+    '''block_sparse_attention_decode over a PAGED cache: k_pages and v_pages [P, Hkv, page, D] are one pool of pages of
+    `page` keys (a power of two ≥ 16, taken from the pool's shape) and block_table [B, W] maps the logical pages of every
+    item to pool pages: key j of batch item b, k / v head h, is row j % page of head h of pool page block_table[b, j // page].
+    The logical length is Smax = W · page (a multiple of block); all k / v heads of an item share its table row, and items
+    may share pages.  q, layout, k_lens, block, scale, chunk, return_lse, the visibility rule, the group of at most 16 and
+    every refusal are those of block_sparse_attention_decode with that Smax (block_attention_decode_paged_takes).
+
+    THE POOL IS NEVER COPIED: it is read through its own strides — last stride 1, row stride ≥ D, row, head and page
+    strides multiples of 8 elements, a 16-byte aligned data pointer — so [P, Hkv, page, D] and a
+    [P, page, Hkv, D].transpose(1, 2) view both work; anything else raises ValueError naming the stride.  P = 0 is allowed.
+    block_table is an int32 or int64 device tensor with a last stride of 1 and any row stride ≥ W (a [B, Wmax][:, :W] slice
+    works); an int32 table is handed to the kernel as it is, an int64 table is narrowed on the device; it is never read back.
+    A table entry outside [0, P) — the −1 of an unallocated slot — makes the keys of its logical page INVISIBLE: nothing is
+    loaded for them and their scores are −inf.  Entries of pages wholly beyond pos, or only in unlisted blocks, are never
+    consulted.
+
+    Bits: for a pool and a table whose seen entries are in range, out and lse are bit for bit those of
+    block_sparse_attention_decode with the same chunk on the cache gathered to [B, Hkv, Smax, D] — so they do not depend
+    on P, on where the pages lie, or on `page`.  No atomics, no read-back: graph-capturable, and one captured graph keeps
+    serving while k_lens, the pool and the block table are updated in place.  NO autograd.'''
+    what = 'block_sparse_attention_decode_paged'
+    _check_block_attention_decode_paged_operands(what, q, k_pages, v_pages, block_table, layout, k_lens, block, chunk)
+    B, Hq, T, D = q.shape
+    Smax = block_table.shape[1] * k_pages.shape[2]
+    if scale is None:
+        scale = 1.0 / float(D) ** 0.5
+    if chunk is None:
+        chunk = _decode_chunk(Smax, D)
+    with torch.no_grad():
+        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
+        offsets, columns, nnz, _ = rec['fwd']
+        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
+        table = block_table.detach()
+        if table.dtype != torch.int32:
+            table = table.to(torch.int32)
+        qc = q.detach().contiguous()
+        out = torch.empty_like(qc)
+        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
+        if out.numel() > 0:
+            custom_mm.block_attention_decode_paged(offsets, columns, nnz, qc, k_pages.detach(), v_pages.detach(), table, lens,
+                                                   float(scale), int(chunk), out, lse)
     return (out, lse) if return_lse else out
 
 
