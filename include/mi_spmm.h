@@ -1114,6 +1114,65 @@ int mi_block_attention_decode_paged_f16(const int32_t* rowptr, const int32_t* co
                                         size_t workspace_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * … over an FP8 cache: mi_block_attention_decode_* and mi_block_attention_decode_paged_* with k and v (or
+ * the pool) stored as OCP e4m3fn bytes — gfx950's native 8-bit float; not the FNUZ encoding, not e5m2 — and a float32 scale
+ * per k / v head.  q, out, lse and every other argument are the parents'; the differences:
+ *   k, v / k_pages, v_pages   bytes, never copied; the strides are in elements (= bytes): 16-byte aligned, ldk ≥ D, every
+ *              stride a multiple of 16;
+ *   k_scale, k_scale_count, v_scale, v_scale_count   float32 on the device, 4-byte aligned, read by the kernels and never
+ *              read back; a count of 1: one scale for all heads, a count of `heads`: head c % heads has its own; NULL: 1.
+ *              The real key is k8 · k_scale[h], the real value v8 · v_scale[h].  Non-finite or non-positive scales are the
+ *              caller's business.
+ * Arithmetic: every byte is widened to T in registers — exact: each finite e4m3fn code is a bfloat16 and a float16 — and the
+ * statements of the parents follow, with two differences: a score is multiplied by scale · k_scale[h], ONE fp32 product taken
+ * once per workgroup, in the place of scale; the stored element is narrow((O / L) · v_scale[h]), one rounding.  lse is that
+ * of the real scores.  So with both scales NULL, out and lse have the bits of the parent on the widened cache with the same
+ * chunk; with k_scale = s for all heads and v_scale = 2^n, out has the parent's bits at scale' = fl32(scale · s), times 2^n,
+ * and lse the parent's bits; and the paged call has the bits of the contiguous one on the gathered cache.  P is never
+ * narrowed to fp8 and no fp8 MFMA is used.  Nothing beyond pos, in an unlisted block, between the rows or in an invalid page
+ * is loaded: a NaN byte (0x7F / 0xFF) there reaches no output.  Workspace: mi_block_attention_decode_workspace_bytes.
+ * Graph-capturable while k_lens, the cache, the table and the scales are updated in place.
+ * Validation before any HIP call: everything the parents refuse (with 16 for 8 in the cache's strides), a scale count other
+ * than 1 or heads, a misaligned scale pointer → MI_EINVAL; a short workspace → MI_ENOMEM.
+ * ------------------------------------------------------------------------ */
+int mi_block_attention_decode_fp8_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts,
+                                       int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, const uint16_t* q,
+                                       int64_t ldq, int64_t strideQ, const uint8_t* k, int64_t ldk, int64_t headK,
+                                       int64_t batchK, const uint8_t* v, int64_t ldv, int64_t headV, int64_t batchV,
+                                       const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale,
+                                       const float* k_scale, int32_t k_scale_count, const float* v_scale,
+                                       int32_t v_scale_count, uint16_t* out, int64_t ldo, int64_t strideO, float* lse,
+                                       void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_block_attention_decode_fp8_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts,
+                                      int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, const uint16_t* q,
+                                      int64_t ldq, int64_t strideQ, const uint8_t* k, int64_t ldk, int64_t headK,
+                                      int64_t batchK, const uint8_t* v, int64_t ldv, int64_t headV, int64_t batchV,
+                                      const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale,
+                                      const float* k_scale, int32_t k_scale_count, const float* v_scale,
+                                      int32_t v_scale_count, uint16_t* out, int64_t ldo, int64_t strideO, float* lse,
+                                      void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_block_attention_decode_paged_fp8_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts,
+                                             int32_t items, int32_t heads, int32_t T, int32_t Smax,
+                                             const int32_t* block_table, int64_t table_ld, int32_t pages, int32_t page,
+                                             int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ,
+                                             const uint8_t* k_pages, int64_t ldk, int64_t headK, int64_t pageK,
+                                             const uint8_t* v_pages, int64_t ldv, int64_t headV, int64_t pageV,
+                                             const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk,
+                                             float scale, const float* k_scale, int32_t k_scale_count, const float* v_scale,
+                                             int32_t v_scale_count, uint16_t* out, int64_t ldo, int64_t strideO, float* lse,
+                                             void* workspace, size_t workspace_bytes, mi_stream_t stream);
+int mi_block_attention_decode_paged_fp8_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts,
+                                            int32_t items, int32_t heads, int32_t T, int32_t Smax,
+                                            const int32_t* block_table, int64_t table_ld, int32_t pages, int32_t page,
+                                            int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ,
+                                            const uint8_t* k_pages, int64_t ldk, int64_t headK, int64_t pageK,
+                                            const uint8_t* v_pages, int64_t ldv, int64_t headV, int64_t pageV,
+                                            const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk,
+                                            float scale, const float* k_scale, int32_t k_scale_count, const float* v_scale,
+                                            int32_t v_scale_count, uint16_t* out, int64_t ldo, int64_t strideO, float* lse,
+                                            void* workspace, size_t workspace_bytes, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in
  * bfloat16 / float16 (T, 2-byte bit patterns) with A given as the kept 64 × 64 blocks of a CSR block list, shared by
  * every item of the batch, and the sampled product on the same list:

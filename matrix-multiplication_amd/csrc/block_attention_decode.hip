@@ -26,11 +26,22 @@
 //    form of the kernel (contiguous / pages ≥ 64 keys / pages of 16 or 32 keys), everything else is shared.  A table entry
 //    outside the pool hides its page's keys: nothing is loaded for them, zeros are staged, their scores are −inf.
 //
+//  * fp8 caches (mi_block_attention_decode{,_paged}_fp8_{bf16,f16}): k and v (or the pool) hold OCP e4m3fn
+//    bytes and a float32 scale per k / v head (or one for all).  The cache element type is a compile-time form of the walk:
+//    a lane loads the 8 bytes of its 8 elements where the 2-byte walk loads 16, and widens them to T in registers
+//    (v_cvt_scalef32_pk_{bf16,f16}_fp8 at scale 1: exact, every finite e4m3fn code is a T) — k right before the score
+//    MFMAs, v on its way into the transposed image, which holds T as before.  From there the statements are the same, but
+//    for two: a score is multiplied by scale · k_scale[h] (ONE fp32 product, taken once per workgroup) and the stored
+//    element is T::down((O · inv) · v_scale[h]).  So without scales the call has the bits of the 2-byte call on the widened
+//    cache.  The scales are read from device memory by the kernels: never read back, graph-capturable.
+//
 // Kernel: grid (chunks, items, T), 256 threads.  No workgroup barrier inside the walk.  A wave loads the k tile of an
 // entry as 16-byte global loads straight into MFMA A fragments (lane (li, lg): row 16f + li, columns 32s + 8lg … + 7), the v
 // tile into registers and from there into a wave-private transposed LDS image [D][64 + 8] (a wave-level fence between its
 // writes and reads); the next entry's loads are issued before this one's softmax and P·V.  The device pieces (mfma,
 // score, pack_tile, accumulate, group_max / group_sum) are private copies of block_attention.hip's, adapted to one wave.
+#include <type_traits>
+
 #include "lowp_device.h"
 
 namespace {
@@ -64,7 +75,8 @@ struct Args {
   long smax;
   const uint16_t* q;      // query item c · group + g, token t: q + (c · group + g) · strideQ + t · ldq
   long ldq, strideQ;
-  const uint16_t *k, *v;  // key j of k / v item c: k + (c / heads) · batchK + (c % heads) · headK + j · ldk
+  const void *k, *v;      // key j of k / v item c: k + (c / heads) · batchK + (c % heads) · headK + j · ldk (in elements:
+                          // 2-byte patterns of T, or e4m3fn bytes in the fp8 forms)
   long ldk, headK, batchK, ldv, headV, batchV;
   const int32_t* k_lens;  // [items / lens_div], clamped to [0, Smax] where read
   int lens_div;
@@ -79,7 +91,74 @@ struct Args {
   long table_ld;
   int pages, page_shift;
   long pageK, pageV;
+  // the fp8 forms: the real key is k8 · k_scale[h], the real value v8 · v_scale[h]; a null pointer is 1,
+  // a count of 1 one scale for all heads, else one per k / v head
+  const float *k_scale, *v_scale;
+  int k_scale_count, v_scale_count;
 };
+
+// The cache element as a compile-time form of the walk: Fp8<T> names q's and out's type T over a cache of e4m3fn bytes
+template <class T>
+struct Fp8 {};
+template <class TC>
+struct Operand {
+  typedef TC type;
+  static constexpr bool fp8 = false;
+};
+template <class T>
+struct Operand<Fp8<T>> {
+  typedef T type;
+  static constexpr bool fp8 = true;
+};
+
+// … and what a lane loads for its 8 consecutive elements
+template <bool FP8>
+struct Cache {
+  typedef uint16_t elem;
+  typedef uint4 frag;
+};
+template <>
+struct Cache<true> {
+  typedef uint8_t elem;
+  typedef uint2 frag;
+};
+
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+// two e4m3fn (OCP) bytes of w — the low pair, or with HI the high pair — as two T, in their order: exact
+template <class T, bool HI>
+__device__ __forceinline__ unsigned widen2(unsigned w);
+template <>
+__device__ __forceinline__ unsigned widen2<Bf16, false>(unsigned w) {
+  return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
+}
+template <>
+__device__ __forceinline__ unsigned widen2<Bf16, true>(unsigned w) {
+  return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true));
+}
+template <>
+__device__ __forceinline__ unsigned widen2<F16, false>(unsigned w) {
+  return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false));
+}
+template <>
+__device__ __forceinline__ unsigned widen2<F16, true>(unsigned w) {
+  return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true));
+}
+
+// a lane's 8 elements as the 16 bytes of T the MFMA takes: as they are, or 8 e4m3fn bytes widened
+template <class T>
+__device__ __forceinline__ uint4 widen(uint4 x) { return x; }
+template <class T>
+__device__ __forceinline__ uint4 widen(uint2 x) {
+  return uint4{widen2<T, false>(x.x), widen2<T, true>(x.x), widen2<T, false>(x.y), widen2<T, true>(x.y)};
+}
+
+template <class F> __device__ __forceinline__ F zero_frag();
+template <> __device__ __forceinline__ uint4 zero_frag<uint4>() { return uint4{0u, 0u, 0u, 0u}; }
+template <> __device__ __forceinline__ uint2 zero_frag<uint2>() { return uint2{0u, 0u}; }
+// the scale of k / v head h of the fp8 forms
+__device__ __forceinline__ float head_scale(const float* s, int count, int h) { return s ? s[count == 1 ? 0 : h] : 1.f; }
 
 // How the walk finds the 64 keys of a list entry: a compile-time form of the kernel, as LENS is in block_attention.hip
 constexpr int kContiguous = 0;  // one [Smax][D] run per k / v item behind fixed strides
@@ -99,30 +178,30 @@ __device__ __forceinline__ void fence_wave() {  // LDS writes of this wave befor
 
 // The k tile of a block as A fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of row 16f + li; rows at or beyond
 // `limit` (keys beyond pos) are zero fragments, whatever memory holds
-template <int D>
-__device__ __forceinline__ void load_k(uint4 (&kf)[4][D / 32], const uint16_t* src, long ld, int li, int lg, int limit) {
+template <int D, class F, class E>
+__device__ __forceinline__ void load_k(F (&kf)[4][D / 32], const E* src, long ld, int li, int lg, int limit) {
 #pragma unroll
   for (int f = 0; f < 4; ++f)
 #pragma unroll
     for (int s = 0; s < D / 32; ++s) {
       if (16 * f + li < limit)
-        kf[f][s] = *reinterpret_cast<const uint4*>(src + (long)(16 * f + li) * ld + 32 * s + 8 * lg);
+        kf[f][s] = *reinterpret_cast<const F*>(src + (long)(16 * f + li) * ld + 32 * s + 8 * lg);
       else
-        kf[f][s] = uint4{0u, 0u, 0u, 0u};
+        kf[f][s] = zero_frag<F>();
     }
 }
 
 // The v tile of a block in one wave's registers: lane (li, lg) holds rows 4li … + 3, columns 8(lg + 4i) … + 7
-template <int D>
-__device__ __forceinline__ void load_v(uint4 (&vr)[D / 32][4], const uint16_t* src, long ld, int li, int lg, int limit) {
+template <int D, class F, class E>
+__device__ __forceinline__ void load_v(F (&vr)[D / 32][4], const E* src, long ld, int li, int lg, int limit) {
 #pragma unroll
   for (int i = 0; i < D / 32; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (4 * li + r < limit)
-        vr[i][r] = *reinterpret_cast<const uint4*>(src + (long)(4 * li + r) * ld + 8 * (lg + 4 * i));
+        vr[i][r] = *reinterpret_cast<const F*>(src + (long)(4 * li + r) * ld + 8 * (lg + 4 * i));
       else
-        vr[i][r] = uint4{0u, 0u, 0u, 0u};
+        vr[i][r] = zero_frag<F>();
     }
 }
 
@@ -149,44 +228,44 @@ __device__ __forceinline__ unsigned valid_pages(const int (&e)[4], int pages) {
 
 // load_k over pages of 16 or 32 keys: fragment f (rows 16f … 16f + 15 of the tile) starts at row (16f) & (page − 1) of its
 // own page e[f]; a fragment of an invalid page is zero, whatever its entry holds
-template <int D>
-__device__ __forceinline__ void load_k_pages(uint4 (&kf)[4][D / 32], const uint16_t* pool, long ld, long pageStride, const int (&e)[4],
+template <int D, class F, class E>
+__device__ __forceinline__ void load_k_pages(F (&kf)[4][D / 32], const E* pool, long ld, long pageStride, const int (&e)[4],
                                              unsigned ok, int in_page, int li, int lg, int limit) {
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
-    const uint16_t* src = pool + (long)e[f] * pageStride + (long)(((16 * f) & in_page) + li) * ld + 8 * lg;
+    const E* src = pool + (long)e[f] * pageStride + (long)(((16 * f) & in_page) + li) * ld + 8 * lg;
     const bool take = ((ok >> f) & 1u) && 16 * f + li < limit;
 #pragma unroll
     for (int s = 0; s < D / 32; ++s) {
       if (take)
-        kf[f][s] = *reinterpret_cast<const uint4*>(src + 32 * s);
+        kf[f][s] = *reinterpret_cast<const F*>(src + 32 * s);
       else
-        kf[f][s] = uint4{0u, 0u, 0u, 0u};
+        kf[f][s] = zero_frag<F>();
     }
   }
 }
 
 // load_v over pages of 16 or 32 keys: the lane's rows 4li … 4li + 3 lie in fragment li / 4, so in one page (4 divides 16)
-template <int D>
-__device__ __forceinline__ void load_v_pages(uint4 (&vr)[D / 32][4], const uint16_t* pool, long ld, long pageStride, const int (&e)[4],
+template <int D, class F, class E>
+__device__ __forceinline__ void load_v_pages(F (&vr)[D / 32][4], const E* pool, long ld, long pageStride, const int (&e)[4],
                                              unsigned ok, int in_page, int li, int lg, int limit) {
   const int f = li >> 2;
   const int mine = f == 0 ? e[0] : f == 1 ? e[1] : f == 2 ? e[2] : e[3];
-  const uint16_t* src = pool + (long)mine * pageStride + (long)((4 * li) & in_page) * ld + 8 * lg;
+  const E* src = pool + (long)mine * pageStride + (long)((4 * li) & in_page) * ld + 8 * lg;
   const bool valid = (ok >> f) & 1u;
 #pragma unroll
   for (int i = 0; i < D / 32; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (valid && 4 * li + r < limit)
-        vr[i][r] = *reinterpret_cast<const uint4*>(src + (long)r * ld + 32 * i);
+        vr[i][r] = *reinterpret_cast<const F*>(src + (long)r * ld + 32 * i);
       else
-        vr[i][r] = uint4{0u, 0u, 0u, 0u};
+        vr[i][r] = zero_frag<F>();
     }
 }
 
 // … into the wave's transposed image [D][64 + 8]
-template <int D>
+template <class T, int D>
 __device__ __forceinline__ void store_transposed(unsigned short* Tt, const uint4 (&vr)[D / 32][4], int li, int lg) {
 #pragma unroll
   for (int i = 0; i < D / 32; ++i)
@@ -196,15 +275,28 @@ __device__ __forceinline__ void store_transposed(unsigned short* Tt, const uint4
       *reinterpret_cast<uint2*>(Tt + (8 * (lg + 4 * i) + e) * kTStr + 4 * li) = w;
     }
 }
+// … of e4m3fn bytes: widened on the way, so the image holds T either way
+template <class T, int D>
+__device__ __forceinline__ void store_transposed(unsigned short* Tt, const uint2 (&vr)[D / 32][4], int li, int lg) {
+#pragma unroll
+  for (int i = 0; i < D / 32; ++i) {
+    const uint4 x[4] = {widen<T>(vr[i][0]), widen<T>(vr[i][1]), widen<T>(vr[i][2]), widen<T>(vr[i][3])};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const uint2 w = {half_of(x[0], e) | (half_of(x[1], e) << 16), half_of(x[2], e) | (half_of(x[3], e) << 16)};
+      *reinterpret_cast<uint2*>(Tt + (8 * (lg + 4 * i) + e) * kTStr + 4 * li) = w;
+    }
+  }
+}
 
 // acc[f][r] = ⟨key 16f + 4lg + r of the block, own row li⟩ over d
-template <class T, int D>
-__device__ __forceinline__ void score(f32x4 (&acc)[4], const uint4 (&kf)[4][D / 32], const uint4 (&own)[D / 32]) {
+template <class T, int D, class F>
+__device__ __forceinline__ void score(f32x4 (&acc)[4], const F (&kf)[4][D / 32], const uint4 (&own)[D / 32]) {
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
     acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int s = 0; s < D / 32; ++s) acc[f] = mfma<T>(kf[f][s], own[s], acc[f]);
+    for (int s = 0; s < D / 32; ++s) acc[f] = mfma<T>(widen<T>(kf[f][s]), own[s], acc[f]);
   }
 }
 
@@ -253,12 +345,16 @@ __device__ __forceinline__ int next_entry(const int32_t* col, int p, int end, in
 // the weight of a partial with maximum m in a merge to the maximum M (an empty partial, m = −inf, weighs nothing)
 __device__ __forceinline__ float merge_weight(float m, float M) { return m == -INFINITY ? 0.f : __expf(m - M); }
 
-// element d of the row of query head g of (c, t): normalised, rounded once; the row's log-sum-exp with its element 0
-template <class T>
-__device__ __forceinline__ void finish(const Args& a, int c, int t, int g, int d, float M, float L, float O) {
+// element d of the row of query head g of (c, t): normalised, rounded once; the row's log-sum-exp with its element 0.
+// SCALED: `vs`, the fp8 forms' v_scale of the item's head (value_scale: read once at the kernel's start, 1 for a null
+// pointer — every 2-byte call), multiplies the normalised element; the 2-byte walk, which never has one, does not look.
+template <class T, bool SCALED>
+__device__ __forceinline__ void finish(const Args& a, int c, int t, int g, int d, float M, float L, float O, float vs) {
   const float inv = L == 0.f ? 0.f : 1.f / L;
   const long item = (long)c * a.group + g;
-  a.out[item * a.strideO + (long)t * a.ldo + d] = T::down(O * inv);
+  float x = O * inv;
+  if constexpr (SCALED) x *= vs;
+  a.out[item * a.strideO + (long)t * a.ldo + d] = T::down(x);
   if (d == 0) a.lse[item * a.T + t] = L == 0.f ? -INFINITY : M + __logf(L);
 }
 
@@ -266,8 +362,14 @@ __device__ __forceinline__ void finish(const Args& a, int c, int t, int g, int d
 // differ from the contiguous one in where a tile's rows are loaded from and in the validity of a page, which joins the
 // position mask — the summation, the chunking and the merge are the same statements, so a paged call has the bits of the
 // contiguous call on the gathered cache.
-template <class T, int D, int FORM>
+// The cache element is part of the kernel's first parameter: T itself (k and v hold T), or Fp8<T> — the cache holds e4m3fn
+// bytes: the loads, the widening and the two scales differ, nothing else.
+template <class TC, int D, int FORM>
 __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
+  typedef typename Operand<TC>::type T;
+  constexpr bool FP8 = Operand<TC>::fp8;
+  typedef typename Cache<FP8>::elem E;
+  typedef typename Cache<FP8>::frag F;
   constexpr int kPStr = D + 4;  // a wave's partial in its own image: [16][D + 4] floats — o[D], m, l
   __shared__ __attribute__((aligned(16))) unsigned short Vt[kWaves][D * kTStr];
   static_assert(kMaxGroup * kPStr * 4 <= D * kTStr * 2, "the partial fits the image");
@@ -294,7 +396,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
     for (int e = tid; e < G * D; e += 256) {
       const int g = e / D, d = e - g * D;
       if (a.chunks == 1) {
-        finish<T>(a, c, t, g, d, -INFINITY, 0.f, 0.f);
+        finish<T, FP8>(a, c, t, g, d, -INFINITY, 0.f, 0.f, 1.f);
       } else {
         float* row = a.ws + ((((long)c * a.T + t) * a.chunks + ch) * G + g) * (D + 2);
         row[2 + d] = 0.f;
@@ -304,9 +406,13 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
     return;
   }
   // (a pool has no batch stride: the item's pages come from its table row)
-  const uint16_t* K = a.k + (FORM == kContiguous ? (long)(c / a.heads) * a.batchK : 0L) + (long)(c % a.heads) * a.headK;
-  const uint16_t* V = a.v + (FORM == kContiguous ? (long)(c / a.heads) * a.batchV : 0L) + (long)(c % a.heads) * a.headV;
+  const E* K = static_cast<const E*>(a.k) + (FORM == kContiguous ? (long)(c / a.heads) * a.batchK : 0L) + (long)(c % a.heads) * a.headK;
+  const E* V = static_cast<const E*>(a.v) + (FORM == kContiguous ? (long)(c / a.heads) * a.batchV : 0L) + (long)(c % a.heads) * a.headV;
   unsigned short* Vw = Vt[w];
+  // what multiplies a score: scale, or in the fp8 forms scale · k_scale[h] — one fp32 product per workgroup
+  const float sc = FP8 ? a.scale * head_scale(a.k_scale, a.k_scale_count, c % a.heads) : a.scale;
+  // … and the stored element (only a one-chunk walk stores): read here, long before it is used
+  const float vs = FP8 && a.chunks == 1 ? head_scale(a.v_scale, a.v_scale_count, c % a.heads) : 1.f;
 
   uint4 qf[D / 32];  // the own rows as B fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of query head li
 #pragma unroll
@@ -322,7 +428,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
 
-  uint4 kf[4][D / 32], vr[D / 32][4];
+  F kf[4][D / 32], vr[D / 32][4];
   // Paged forms: the tile whose loads are in flight (J, its table entries e, their validity ok) and the entry after it
   // (pn, Jn, en).  The chain col[p] → table → tile is cut in two: the column and the table entries of an entry are read
   // ONE ITERATION EARLY, right after the loads of the entry before it were issued, and have that entry's softmax and P·V
@@ -370,7 +476,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
     const int visible = pos + 1 - (FORM == kContiguous ? a.col[p] : J) * kB;
     const unsigned seen = ok;  // … and the fragments of it that lie in a page (paged forms)
     fence_wave();  // the previous entry's reads of the image are done
-    store_transposed<D>(Vw, vr, li, lg);
+    store_transposed<T, D>(Vw, vr, li, lg);
     fence_wave();
     f32x4 s[4];
     score<T, D>(s, kf, qf);
@@ -397,7 +503,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
     for (int f = 0; f < 4; ++f)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        float x = s[f][r] * a.scale;
+        float x = s[f][r] * sc;
         if (16 * f + 4 * lg + r >= visible) x = -INFINITY;
         if (FORM != kContiguous && !((seen >> f) & 1u)) x = -INFINITY;  // a key of an invalid page
         s[f][r] = x;
@@ -449,7 +555,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
       O += Pi[d] * wt;
     }
     if (a.chunks == 1) {
-      finish<T>(a, c, t, g, d, M, L, O);
+      finish<T, FP8>(a, c, t, g, d, M, L, O, vs);
     } else {
       float* row = a.ws + ((((long)c * a.T + t) * a.chunks + ch) * G + g) * (D + 2);
       row[2 + d] = O;
@@ -462,6 +568,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
 template <class T>
 __global__ __launch_bounds__(128) void block_attention_decode_combine_kernel(Args a, int D) {
   const int c = blockIdx.x, t = blockIdx.y, G = a.group;
+  const float vs = head_scale(a.v_scale, a.v_scale_count, c % a.heads);  // (null in every 2-byte call: 1)
   const float* base = a.ws + (((long)c * a.T + t) * a.chunks) * G * (D + 2);
   for (int e = threadIdx.x; e < G * D; e += 128) {
     const int g = e / D, d = e - g * D;
@@ -474,13 +581,14 @@ __global__ __launch_bounds__(128) void block_attention_decode_combine_kernel(Arg
       L += row[1] * wt;
       O += row[2 + d] * wt;
     }
-    finish<T>(a, c, t, g, d, M, L, O);
+    finish<T, true>(a, c, t, g, d, M, L, O, vs);
   }
 }
 
 bool takes_width(int32_t D) { return D == 32 || D == 64 || D == 96 || D == 128; }
 
-bool stride_ok(int64_t s) { return s >= 0 && s % 8 == 0; }
+// a stride in elements: a multiple of 16 bytes — 8 elements of T, 16 e4m3fn bytes
+bool stride_ok(int64_t s, int64_t unit = 8) { return s >= 0 && s % unit == 0; }
 
 int chunks_of(int32_t Smax, int32_t chunk) {  // from the shape alone; a list has at most Smax / 64 entries
   const long blocks = Smax / kB;
@@ -488,15 +596,16 @@ int chunks_of(int32_t Smax, int32_t chunk) {  // from the shape alone; a list ha
   return (int)(n < 1 ? 1 : n);
 }
 
-template <class T, int D>
+template <class T, int D, bool FP8>
 int launch(const Args& a, int items, hipStream_t s) {
   const dim3 grid((unsigned)a.chunks, (unsigned)items, (unsigned)a.T);
+  typedef std::conditional_t<FP8, Fp8<T>, T> TC;  // the cache element type is part of the kernel's first parameter
   if (!a.table)
-    hipLaunchKernelGGL((block_attention_decode_kernel<T, D, kContiguous>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, kContiguous>), grid, dim3(256), 0, s, a);
   else if (a.page_shift >= 6)
-    hipLaunchKernelGGL((block_attention_decode_kernel<T, D, kPaged>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, kPaged>), grid, dim3(256), 0, s, a);
   else
-    hipLaunchKernelGGL((block_attention_decode_kernel<T, D, kPagedSmall>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, kPagedSmall>), grid, dim3(256), 0, s, a);
   const int st = mi::check_launch();
   if (st != MI_OK || a.chunks == 1) return st;
   hipLaunchKernelGGL((block_attention_decode_combine_kernel<T>), dim3((unsigned)items, (unsigned)a.T), dim3(128), 0, s, a, D);
@@ -505,14 +614,24 @@ int launch(const Args& a, int items, hipStream_t s) {
 
 // Every check comes before the first HIP call.  page == 0: the contiguous cache, `outerK` / `outerV` its batch strides and
 // no table; page > 0: a pool of `pages` pages of `page` keys, `outerK` / `outerV` its page strides, Smax = the table's
-// logical pages · page.
-template <class T>
+// logical pages · page.  FP8: k and v are e4m3fn bytes (their strides multiples of 16) with the two scales of `scales`.
+struct Scales {
+  const float* k = nullptr;
+  int k_count = 1;
+  const float* v = nullptr;
+  int v_count = 1;
+};
+
+template <class T, bool FP8 = false>
 int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T_,
-                 int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ, const uint16_t* k, int64_t ldk,
-                 int64_t headK, int64_t outerK, const uint16_t* v, int64_t ldv, int64_t headV, int64_t outerV,
+                 int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ, const void* k, int64_t ldk,
+                 int64_t headK, int64_t outerK, const void* v, int64_t ldv, int64_t headV, int64_t outerV,
                  const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale, uint16_t* out, int64_t ldo,
                  int64_t strideO, float* lse, void* workspace, size_t workspace_bytes, hipStream_t s, const int32_t* table = nullptr,
-                 int64_t table_ld = 0, int32_t pages = 0, int32_t page = 0) {
+                 int64_t table_ld = 0, int32_t pages = 0, int32_t page = 0, const Scales& scales = Scales()) {
+  constexpr int64_t unit = FP8 ? 16 : 8;  // cache elements in 16 bytes
+  if (FP8 && ((scales.k_count != 1 && scales.k_count != heads) || (scales.v_count != 1 && scales.v_count != heads))) return MI_EINVAL;
+  if (FP8 && ((reinterpret_cast<uintptr_t>(scales.k) & 3u) || (reinterpret_cast<uintptr_t>(scales.v) & 3u))) return MI_EINVAL;
   if (group < 1 || group > kMaxGroup || chunk < 1 || !takes_width(D)) return MI_EINVAL;
   const bool paged = page != 0;
   if (paged && (page < 16 || (page & (page - 1)) != 0 || pages < 0 || Smax % page != 0)) return MI_EINVAL;
@@ -527,15 +646,17 @@ int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t
   if (!out || !mi::aligned16(out) || ldo < D || !stride_ok(ldo) || !stride_ok(strideO)) return MI_EINVAL;
   if (paged && Smax > 0 && (!table || (reinterpret_cast<uintptr_t>(table) & 3u) || table_ld < Smax / page)) return MI_EINVAL;
   if (nnz > 0 && Smax > 0 && (!paged || pages > 0)) {  // (an empty pool is never read: every entry of the table is invalid)
-    if (!k || !mi::aligned16(k) || ldk < D || !stride_ok(ldk) || !stride_ok(headK) || !stride_ok(outerK)) return MI_EINVAL;
-    if (!v || !mi::aligned16(v) || ldv < D || !stride_ok(ldv) || !stride_ok(headV) || !stride_ok(outerV)) return MI_EINVAL;
+    if (!k || !mi::aligned16(k) || ldk < D || !stride_ok(ldk, unit) || !stride_ok(headK, unit) || !stride_ok(outerK, unit))
+      return MI_EINVAL;
+    if (!v || !mi::aligned16(v) || ldv < D || !stride_ok(ldv, unit) || !stride_ok(headV, unit) || !stride_ok(outerV, unit))
+      return MI_EINVAL;
   }
   const int chunks = chunks_of(Smax, chunk);
   if (chunks > 1) {
     if (!workspace || !mi::aligned16(workspace)) return MI_EINVAL;
     if (workspace_bytes < mi_block_attention_decode_workspace_bytes(items, T_, group, D, Smax, chunk)) return MI_ENOMEM;
   }
-  Args a = {};
+  Args a = {};  // (zeroed: the 2-byte entries leave k_scale / v_scale null, which finish and the combine kernel read as 1)
   a.rowptr = rowptr, a.col = col, a.nnz = nnz, a.layouts = layouts, a.blocks = Smax / kB, a.heads = heads, a.group = group;
   a.T = T_, a.chunk = chunk, a.chunks = chunks, a.smax = Smax;
   a.q = q, a.ldq = ldq, a.strideQ = strideQ;
@@ -548,11 +669,12 @@ int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t
   }
   a.k_lens = k_lens, a.lens_div = items / lens_count, a.scale = scale;
   a.out = out, a.ldo = ldo, a.strideO = strideO, a.lse = lse, a.ws = static_cast<float*>(workspace);
+  if (FP8) a.k_scale = scales.k, a.k_scale_count = scales.k_count, a.v_scale = scales.v, a.v_scale_count = scales.v_count;
   switch (D) {
-    case 32: return launch<T, 32>(a, items, s);
-    case 64: return launch<T, 64>(a, items, s);
-    case 96: return launch<T, 96>(a, items, s);
-    default: return launch<T, 128>(a, items, s);
+    case 32: return launch<T, 32, FP8>(a, items, s);
+    case 64: return launch<T, 64, FP8>(a, items, s);
+    case 96: return launch<T, 96, FP8>(a, items, s);
+    default: return launch<T, 128, FP8>(a, items, s);
   }
 }
 
@@ -596,6 +718,36 @@ int mi_block_attention_decode_paged_bf16(MI_DECODE_PAGED_ARGS) {
 }
 int mi_block_attention_decode_paged_f16(MI_DECODE_PAGED_ARGS) {
   return page < 16 ? MI_EINVAL : decode_entry<F16>(MI_DECODE_PAGED_PASS);
+}
+
+// the fp8 caches: the parents' lists with byte caches and the two scales
+#define MI_DECODE_FP8_ARGS                                                                                                      \
+  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T,             \
+      int32_t Smax, int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const uint8_t *k, int64_t ldk, int64_t headK,   \
+      int64_t batchK, const uint8_t *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count,  \
+      int32_t group, int32_t chunk, float scale, const float *k_scale, int32_t k_scale_count, const float *v_scale,             \
+      int32_t v_scale_count, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes,  \
+      mi_stream_t stream
+#define MI_DECODE_PAGED_FP8_ARGS                                                                                               \
+  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T,            \
+      int32_t Smax, const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page, int32_t D, const uint16_t *q,   \
+      int64_t ldq, int64_t strideQ, const uint8_t *k, int64_t ldk, int64_t headK, int64_t batchK, const uint8_t *v,            \
+      int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group, int32_t chunk,     \
+      float scale, const float *k_scale, int32_t k_scale_count, const float *v_scale, int32_t v_scale_count, uint16_t *out,    \
+      int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes, mi_stream_t stream
+#define MI_DECODE_SCALES Scales{k_scale, k_scale_count, v_scale, v_scale_count}
+
+int mi_block_attention_decode_fp8_bf16(MI_DECODE_FP8_ARGS) {
+  return decode_entry<Bf16, true>(MI_DECODE_PASS, nullptr, 0, 0, 0, MI_DECODE_SCALES);
+}
+int mi_block_attention_decode_fp8_f16(MI_DECODE_FP8_ARGS) {
+  return decode_entry<F16, true>(MI_DECODE_PASS, nullptr, 0, 0, 0, MI_DECODE_SCALES);
+}
+int mi_block_attention_decode_paged_fp8_bf16(MI_DECODE_PAGED_FP8_ARGS) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16, true>(MI_DECODE_PAGED_PASS, MI_DECODE_SCALES);
+}
+int mi_block_attention_decode_paged_fp8_f16(MI_DECODE_PAGED_FP8_ARGS) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16, true>(MI_DECODE_PAGED_PASS, MI_DECODE_SCALES);
 }
 
 }  // extern "C"

@@ -51,6 +51,7 @@ namespace {
 #include "custom_mm_block_attention.inc"
 #include "custom_mm_block_attention_decode.inc"
 #include "custom_mm_block_attention_decode_paged.inc"
+#include "custom_mm_block_attention_decode_fp8.inc"
 #include "custom_mm_bsr.inc"
 #include "custom_mm_bsr_linear.inc"
 
@@ -203,6 +204,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(offsets [layouts, Smax/64+1], columns, nnz, q [B, Hq, T, D], k_pages, v_pages [P, Hkv, page, D] through their own strides, "
         "block_table int32 [B, W] (Smax = W * page; last stride 1, any row stride >= W), k_lens int32 [B] or [1], scale, chunk, out, "
         "lse [B, Hq, T]): block_attention_decode over a pool of pages; an entry outside [0, P) hides its page's keys");
+  m.def("block_attention_decode_fp8", &block_attention_decode_fp8,
+        "(offsets, columns, nnz, q [B, Hq, T, D] bfloat16 / float16, k, v [B, Hkv, Smax, D] float8_e4m3fn through their own strides "
+        "(multiples of 16), k_lens, scale, k_scale, v_scale (None or float32 device tensors of 1 or Hkv entries), chunk, out, lse): "
+        "block_attention_decode over an fp8 cache, every byte widened exactly in registers");
+  m.def("block_attention_decode_paged_fp8", &block_attention_decode_paged_fp8,
+        "(offsets, columns, nnz, q, k_pages, v_pages [P, Hkv, page, D] float8_e4m3fn, block_table int32 [B, W], k_lens, scale, "
+        "k_scale, v_scale, chunk, out, lse): block_attention_decode_paged over an fp8 pool");
   m.def("bsr_mm", &bsr_mm,
         "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
         "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");

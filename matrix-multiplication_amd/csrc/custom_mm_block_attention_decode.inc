@@ -7,15 +7,16 @@
 // or [1] on the device; lse float32 [B, Hq, T].  The workspace of the chunks' partials comes from torch's allocator.
 
 // a cache operand's strides as the kernel takes them; the message names the stride that does not fit (`outer`: the first
-// one, the batch stride of a cache or the page stride of a pool)
-void check_cache_strides(const char* what, const char* name, const torch::Tensor& t, int64_t D, const char* outer = "batch") {
+// one, the batch stride of a cache or the page stride of a pool; `unit`: the elements of 16 bytes — 8, or 16 of an fp8 cache)
+void check_cache_strides(const char* what, const char* name, const torch::Tensor& t, int64_t D, const char* outer = "batch",
+                         int64_t unit = 8) {
   TORCH_CHECK(t.stride(3) == 1 || D == 1, what, ": ", name, " must have a last stride of 1, got ", t.stride(3));
-  TORCH_CHECK(t.size(2) <= 1 || (t.stride(2) >= D && t.stride(2) % 8 == 0), what, ": ", name,
-              "'s row stride must be a multiple of 8 elements and at least D = ", D, ", got ", t.stride(2));
-  TORCH_CHECK(t.size(1) <= 1 || (t.stride(1) >= 0 && t.stride(1) % 8 == 0), what, ": ", name,
-              "'s head stride must be a multiple of 8 elements, got ", t.stride(1));
-  TORCH_CHECK(t.size(0) <= 1 || (t.stride(0) >= 0 && t.stride(0) % 8 == 0), what, ": ", name,
-              "'s ", outer, " stride must be a multiple of 8 elements, got ", t.stride(0));
+  TORCH_CHECK(t.size(2) <= 1 || (t.stride(2) >= D && t.stride(2) % unit == 0), what, ": ", name,
+              "'s row stride must be a multiple of ", unit, " elements and at least D = ", D, ", got ", t.stride(2));
+  TORCH_CHECK(t.size(1) <= 1 || (t.stride(1) >= 0 && t.stride(1) % unit == 0), what, ": ", name,
+              "'s head stride must be a multiple of ", unit, " elements, got ", t.stride(1));
+  TORCH_CHECK(t.size(0) <= 1 || (t.stride(0) >= 0 && t.stride(0) % unit == 0), what, ": ", name,
+              "'s ", outer, " stride must be a multiple of ", unit, " elements, got ", t.stride(0));
   TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, what, ": ", name, "'s data pointer must be 16-byte aligned");
 }
 

@@ -1812,29 +1812,36 @@ def _decode_chunk(Smax: int, D: int) -> int:
     return _DECODE_CHUNK
 
 
-def _check_cache_strides(what, name, t, D, outer='batch'):
+def _check_cache_strides(what, name, t, D, outer='batch', unit=8):
     '''The cache is read through its own strides and never copied: the ValueError names the stride that does not fit
-    (`outer` names the first one: the batch stride of a cache, the page stride of a pool).'''
+    (`outer` names the first one: the batch stride of a cache, the page stride of a pool; `unit`: the elements of 16 bytes —
+    8, or 16 of an fp8 cache).'''
     B, H, S, _ = t.shape
     sb, sh, sr, sd = t.stride()
     if sd != 1:
         raise ValueError(f'{what}: {name} must have a last stride of 1, got {sd} (the cache is never copied)')
-    if S > 1 and (sr < D or sr % 8 != 0):
-        raise ValueError(f'{what}: {name}\'s row stride must be a multiple of 8 elements and at least D = {D}, got {sr} '
+    if S > 1 and (sr < D or sr % unit != 0):
+        raise ValueError(f'{what}: {name}\'s row stride must be a multiple of {unit} elements and at least D = {D}, got {sr} '
                          f'(the cache is never copied)')
-    if H > 1 and (sh < 0 or sh % 8 != 0):
-        raise ValueError(f'{what}: {name}\'s head stride must be a multiple of 8 elements, got {sh} (the cache is never copied)')
-    if B > 1 and (sb < 0 or sb % 8 != 0):
-        raise ValueError(f'{what}: {name}\'s {outer} stride must be a multiple of 8 elements, got {sb} (the cache is never copied)')
+    if H > 1 and (sh < 0 or sh % unit != 0):
+        raise ValueError(f'{what}: {name}\'s head stride must be a multiple of {unit} elements, got {sh} (the cache is never copied)')
+    if B > 1 and (sb < 0 or sb % unit != 0):
+        raise ValueError(f'{what}: {name}\'s {outer} stride must be a multiple of {unit} elements, got {sb} (the cache is never '
+                         f'copied)')
     if t.data_ptr() % 16 != 0:
         raise ValueError(f'{what}: {name}\'s data pointer must be 16-byte aligned (the cache is never copied)')
 
 
-def _check_decode_call(what, names, q, k, v, layout, block, chunk):
+def _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8=False):
     '''What block_sparse_attention_decode and its paged form refuse before they look at a shape: the layout's and the
-    operands' kinds, block, chunk.  `names` are the two cache operands' names in the messages.'''
+    operands' kinds, block, chunk.  `names` are the two cache operands' names in the messages.  fp8: the cache is
+    float8_e4m3fn (_check_fp8_cache) and only q is bfloat16 / float16.'''
     _check_csr(what, 'layout', layout)
-    _check_lowp_operands(what, (('q', q), (names[0], k), (names[1], v)), _DECODE_SIZES_TEXT)
+    if fp8:
+        _check_lowp_operands(what, (('q', q),), _DECODE_SIZES_TEXT)
+        _check_fp8_cache(what, ((names[0], k), (names[1], v)))
+    else:
+        _check_lowp_operands(what, (('q', q), (names[0], k), (names[1], v)), _DECODE_SIZES_TEXT)
     if isinstance(block, bool) or not isinstance(block, int) or block <= 0 or block % _BLOCK_TILE != 0:
         raise ValueError(f'{what}: block must be a positive multiple of 64, got {block!r} (accepted: {_DECODE_SIZES_TEXT})')
     if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1 or chunk >= 2 ** 31):
@@ -1872,11 +1879,12 @@ def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, k_lens, block):
         raise ValueError(f'{what}: k_lens must have shape ({B},) — one length per batch item — or be 0-d, got {tuple(k_lens.shape)}')
 
 
-def _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block, chunk):
+def _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block, chunk, fp8=False, scales=()):
     '''Every refusal of block_sparse_attention_decode, before the first device call, split as
     _check_block_attention_operands splits them: ValueError for what an operand is, RuntimeError for operands that do not go
-    together (mixed dtypes, host tensors / devices).  Returns the group: query heads per k / v head.'''
-    _check_decode_call(what, ('k', 'v'), q, k, v, layout, block, chunk)
+    together (mixed dtypes, host tensors / devices).  Returns the group: query heads per k / v head.  fp8, scales: the
+    fp8 call's cache type and its (name, scale) pairs (_check_fp8_scales).'''
+    _check_decode_call(what, ('k', 'v'), q, k, v, layout, block, chunk, fp8)
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError(f'{what}: q must be [B, Hq, T, D] and k, v [B, Hkv, Smax, D], got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
     B, Hq, T, D = q.shape
@@ -1890,9 +1898,9 @@ def _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block,
     if tuple(v.shape) != tuple(k.shape):
         raise ValueError(f'{what}: v must be a dense tensor with k\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
     _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, k_lens, block)
-    _check_cache_strides(what, 'k', k, D)
-    _check_cache_strides(what, 'v', v, D)
-    _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k=k, v=v, k_lens=k_lens)
+    _check_cache_strides(what, 'k', k, D, unit=16 if fp8 else 8)
+    _check_cache_strides(what, 'v', v, D, unit=16 if fp8 else 8)
+    _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k=k, v=v, k_lens=k_lens, **_check_fp8_scales(what, scales, Hkv, q))
     return group
 
 
@@ -1969,10 +1977,12 @@ def block_attention_decode_paged_takes(dtype, D: int, block: int, group: int, pa
     return block_attention_decode_takes(dtype, D, block, group) and _page_ok(page)
 
 
-def _check_block_attention_decode_paged_operands(what, q, k_pages, v_pages, block_table, layout, k_lens, block, chunk):
+def _check_block_attention_decode_paged_operands(what, q, k_pages, v_pages, block_table, layout, k_lens, block, chunk, fp8=False,
+                                                 scales=()):
     '''Every refusal of block_sparse_attention_decode_paged before the first device call: those of the contiguous call
-    (the same functions, Smax = W · page) and the pool's and the table's own.  Returns the group.'''
-    _check_decode_call(what, ('k_pages', 'v_pages'), q, k_pages, v_pages, layout, block, chunk)
+    (the same functions, Smax = W · page) and the pool's and the table's own.  Returns the group.  fp8, scales: as in
+    _check_block_attention_decode_operands.'''
+    _check_decode_call(what, ('k_pages', 'v_pages'), q, k_pages, v_pages, layout, block, chunk, fp8)
     if q.dim() != 4 or k_pages.dim() != 4 or v_pages.dim() != 4:
         raise ValueError(f'{what}: q must be [B, Hq, T, D] and k_pages, v_pages [P, Hkv, page, D], got {q.dim()}-d, '
                          f'{k_pages.dim()}-d and {v_pages.dim()}-d')
@@ -2003,10 +2013,10 @@ def _check_block_attention_decode_paged_operands(what, q, k_pages, v_pages, bloc
     if B > 1 and block_table.stride(0) < W:
         raise ValueError(f'{what}: block_table\'s row stride must be at least W = {W}, got {block_table.stride(0)}')
     _check_decode_layout_and_lens(what, B, Hkv, T, W * page, layout, k_lens, block)
-    _check_cache_strides(what, 'k_pages', k_pages, D, 'page')
-    _check_cache_strides(what, 'v_pages', v_pages, D, 'page')
+    _check_cache_strides(what, 'k_pages', k_pages, D, 'page', 16 if fp8 else 8)
+    _check_cache_strides(what, 'v_pages', v_pages, D, 'page', 16 if fp8 else 8)
     _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k_pages=k_pages, v_pages=v_pages, block_table=block_table,
-                     k_lens=k_lens)
+                     k_lens=k_lens, **_check_fp8_scales(what, scales, Hkv, q))
     return group
 
 
@@ -2054,6 +2064,181 @@ def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, 
         if out.numel() > 0:
             custom_mm.block_attention_decode_paged(offsets, columns, nnz, qc, k_pages.detach(), v_pages.detach(), table, lens,
                                                    float(scale), int(chunk), out, lse)
+    return (out, lse) if return_lse else out
+
+
+# --------------------------------------------------------------------------- #
+# … over an FP8 (OCP e4m3fn) cache, contiguous and paged, with per-head scales
+# --------------------------------------------------------------------------- #
+
+_FP8_MAX = 448.0                     # the largest finite e4m3fn value
+_DECODE_FP8_SIZES_TEXT = _DECODE_SIZES_TEXT.replace('bfloat16 or float16 operands', 'bfloat16 or float16 q, a float8_e4m3fn cache')
+
+
+def _check_fp8_cache(what, operands):
+    '''The cache operands of the fp8 decode calls, (name, tensor) pairs: each a dense float8_e4m3fn tensor — another 8-bit
+    type is a ValueError that says which encoding is read —, then both of one dtype (RuntimeError).'''
+    first, t0 = operands[0]
+    for name, t in operands:
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be a dense tensor')
+    for name, t in operands[1:]:
+        if t.dtype != t0.dtype:
+            raise RuntimeError(f'{what}: {first} is {t0.dtype} but {name} is {t.dtype}: the cache must have one dtype '
+                               f'(float8_e4m3fn)')
+    for name, t in operands:
+        if t.dtype != torch.float8_e4m3fn:
+            raise ValueError(f'{what}: {name} must be float8_e4m3fn, got {t.dtype}: the OCP e4m3fn encoding is what is read '
+                             f'(not e4m3fnuz, not e5m2, not raw bytes; accepted: {_DECODE_FP8_SIZES_TEXT})')
+
+
+def _check_fp8_scales(what, scales, Hkv, q):
+    '''The scales of an fp8 decode call, (name, scale) pairs: each None, a Python float, or a float32 tensor of shape (),
+    (1,) or (Hkv,) (ValueError) on q's device (RuntimeError).  Returns the tensors among them by name, for _check_on_device.'''
+    tensors = {}
+    for name, s in scales:
+        if s is None or (isinstance(s, (float, int)) and not isinstance(s, bool)):
+            continue
+        if not isinstance(s, torch.Tensor) or s.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be None, a float or a dense float32 tensor, got {type(s).__name__}')
+        if s.dtype != torch.float32:
+            raise ValueError(f'{what}: {name} must be a float32 tensor, got {s.dtype}')
+        if tuple(s.shape) not in ((), (1,), (Hkv,)):
+            raise ValueError(f'{what}: {name} must have shape (), (1,) or ({Hkv},) — one scale, or one per k / v head —, got '
+                             f'{tuple(s.shape)}')
+        if s.device != q.device:
+            raise RuntimeError(f'{what}: {name} is on {s.device} but q is on {q.device}: a scale is read by the kernel, on q\'s device')
+        tensors[name] = s
+    return tensors
+
+
+def _fp8_scale(s, dev):
+    '''A scale as the binding takes it: None (= 1), or a contiguous float32 device tensor of 1 or Hkv entries; a Python
+    number becomes a 0-d device tensor by a fill kernel — no host copy, so the call stays capturable.'''
+    if s is None:
+        return None
+    if not isinstance(s, torch.Tensor):
+        return torch.full((), float(s), dtype=torch.float32, device=dev)
+    return s if s.is_contiguous() and not s.requires_grad else s.detach().contiguous()  # (as it is: the call is short)
+
+
+def block_attention_decode_fp8_takes(dtype, D: int, block: int, group: int) -> bool:
+    '''Whether block_sparse_attention_decode_fp8 takes head size D, block size `block` and `group` query heads per k / v
+    head with q in `dtype` (the cache is float8_e4m3fn): exactly block_attention_decode_takes.'''
+    return block_attention_decode_takes(dtype, D, block, group)
+
+
+def block_attention_decode_paged_fp8_takes(dtype, D: int, block: int, group: int, page: int) -> bool:
+    '''… and of block_sparse_attention_decode_paged_fp8: exactly block_attention_decode_paged_takes.'''
+    return block_attention_decode_paged_takes(dtype, D, block, group, page)
+
+
+def kv_to_fp8(x: torch.Tensor, scale=None):
+    '''A key / value tensor [*, Hkv, S, D] — the heads in dim 1: a cache [B, Hkv, Smax, D] or a pool [P, Hkv, page, D] — as
+    (x8, scale) for the fp8 decode calls: x8 = clamp(x / scale, −448, 448) in float8_e4m3fn and the float32 scale [Hkv], so
+    that x ≈ x8 · scale[h].  scale=None takes amax over all but dim 1, divided by 448, with a floor at the smallest normal
+    float32; a given scale is a float or a tensor of shape (), (1,) or (Hkv,).  The clamp matters: torch's cast does not
+    saturate, a value beyond 448 would become NaN.  torch ops only — not a hot path.'''
+    if not isinstance(x, torch.Tensor) or x.dim() < 2 or not x.is_floating_point():
+        raise ValueError(f'kv_to_fp8: x must be a floating-point tensor [*, Hkv, S, D] with the heads in dim 1')
+    Hkv = x.shape[1]
+    xf = x.detach().float()
+    if scale is None:
+        amax = xf.abs().amax(dim=[d for d in range(x.dim()) if d != 1]) if x.numel() > 0 else xf.new_zeros(Hkv)
+        scale = (amax / _FP8_MAX).clamp_min(torch.finfo(torch.float32).tiny)
+    else:
+        scale = torch.as_tensor(scale, dtype=torch.float32, device=x.device).reshape(-1)
+        if scale.numel() not in (1, Hkv):
+            raise ValueError(f'kv_to_fp8: scale must hold 1 or Hkv = {Hkv} entries, got {scale.numel()}')
+        scale = scale.expand(Hkv).contiguous()
+    per_head = scale.reshape((1, Hkv) + (1,) * (x.dim() - 2))
+    x8 = (xf / per_head).clamp(-_FP8_MAX, _FP8_MAX).to(torch.float8_e4m3fn)
+    return x8, scale
+
+
+def block_sparse_attention_decode_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
+                                      block: int = 64, scale=None, *, k_scale=None, v_scale=None, chunk=None,
+                                      return_lse: bool = False):
+    '''block_sparse_attention_decode over an FP8 cache: q [B, Hq, T, D] bfloat16 or float16, k and v [B, Hkv, Smax, D]
+    torch.float8_e4m3fn — the OCP encoding, gfx950's native one; float8_e4m3fnuz, float8_e5m2 and uint8 raise ValueError —
+    with the real key k8 · k_scale[h] and the real value v8 · v_scale[h].  Everything else — the visibility rule, the
+    grouped heads, the layout, k_lens, chunk, return_lse, no autograd, the graph-capturable call — is
+    block_sparse_attention_decode\'s (block_attention_decode_fp8_takes).  kv_to_fp8 makes such a cache.
+
+    THE CACHE IS NEVER COPIED: it is read through its own strides — last stride 1, row stride ≥ D, row, head and batch
+    strides multiples of 16 elements (= bytes), a 16-byte aligned data pointer — so [B, Hkv, Smax, D] and a
+    [B, Smax, Hkv, D].transpose(1, 2) view both work; anything else raises ValueError naming the stride.
+
+    k_scale, v_scale: None (= 1), a Python float, or a float32 device tensor of shape (), (1,) or (Hkv,).  They are handed
+    to the kernel as device pointers and never read back: a captured graph follows a scale tensor that is updated in
+    place (a float becomes a 0-d device tensor by a fill kernel).  Non-finite or non-positive scales are the caller\'s
+    business.
+
+    Bits: every byte is widened to q\'s type in registers, which is exact, and block_sparse_attention_decode\'s statements
+    follow with two differences: a score is multiplied by scale · k_scale[h] — one float32 product — in the place of scale,
+    and the stored element is round((O / L) · v_scale[h]).  lse is that of the real scores.  So with both scales None, out
+    and lse are bit for bit those of block_sparse_attention_decode on k.to(q.dtype), v.to(q.dtype) with the same chunk;
+    with k_scale = s for all heads and v_scale = 2^n, out is that call\'s result at scale\' = float32(scale) · float32(s)
+    times 2^n, and lse that call\'s.  Nothing beyond pos, in an unlisted block or between the rows is loaded: a NaN byte
+    there reaches no output.'''
+    what = 'block_sparse_attention_decode_fp8'
+    _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block, chunk, True,
+                                           (('k_scale', k_scale), ('v_scale', v_scale)))
+    B, Hq, T, D = q.shape
+    Smax = k.shape[2]
+    if scale is None:
+        scale = 1.0 / float(D) ** 0.5
+    if chunk is None:
+        chunk = _decode_chunk(Smax, D)
+    with torch.no_grad():
+        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
+        offsets, columns, nnz, _ = rec['fwd']
+        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
+        qc = q.detach().contiguous()
+        out = torch.empty_like(qc)
+        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
+        if out.numel() > 0:
+            custom_mm.block_attention_decode_fp8(offsets, columns, nnz, qc, k.detach(), v.detach(), lens, float(scale),
+                                                 _fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device), int(chunk), out, lse)
+    return (out, lse) if return_lse else out
+
+
+def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                                            layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *,
+                                            k_scale=None, v_scale=None, chunk=None, return_lse: bool = False):
+    '''block_sparse_attention_decode_paged over an FP8 pool: k_pages and v_pages [P, Hkv, page, D] torch.float8_e4m3fn
+    with k_scale / v_scale as in block_sparse_attention_decode_fp8, everything else — the table, the pages (a power of two
+    ≥ 16 keys), entries outside [0, P) hiding their page, the refusals — as in block_sparse_attention_decode_paged
+    (block_attention_decode_paged_fp8_takes).  The pool is never copied: its row, head and page strides are multiples of 16
+    elements, [P, Hkv, page, D] and [P, page, Hkv, D].transpose(1, 2) both work.
+
+    Bits: for in-range tables, out and lse are bit for bit those of block_sparse_attention_decode_fp8 with the same chunk
+    and scales on the gathered cache; with both scales None, those of block_sparse_attention_decode_paged on the pool
+    widened to q\'s type.  Nothing in an invalid page is loaded.  Graph-capturable while k_lens, the pool, the table and
+    the scale tensors are updated in place.'''
+    what = 'block_sparse_attention_decode_paged_fp8'
+    _check_block_attention_decode_paged_operands(what, q, k_pages, v_pages, block_table, layout, k_lens, block, chunk, True,
+                                                 (('k_scale', k_scale), ('v_scale', v_scale)))
+    B, Hq, T, D = q.shape
+    Smax = block_table.shape[1] * k_pages.shape[2]
+    if scale is None:
+        scale = 1.0 / float(D) ** 0.5
+    if chunk is None:
+        chunk = _decode_chunk(Smax, D)
+    with torch.no_grad():
+        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
+        offsets, columns, nnz, _ = rec['fwd']
+        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
+        table = block_table.detach()
+        if table.dtype != torch.int32:
+            table = table.to(torch.int32)
+        qc = q.detach().contiguous()
+        out = torch.empty_like(qc)
+        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
+        if out.numel() > 0:
+            custom_mm.block_attention_decode_paged_fp8(offsets, columns, nnz, qc, k_pages.detach(), v_pages.detach(), table, lens,
+                                                       float(scale), _fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device),
+                                                       int(chunk), out, lse)
     return (out, lse) if return_lse else out
 
 
