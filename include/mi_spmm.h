@@ -1173,6 +1173,71 @@ int mi_block_attention_decode_paged_fp8_f16(const int32_t* rowptr, const int32_t
                                             void* workspace, size_t workspace_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * The fused KV-cache append: the write side of the decode entries above.  ONE launch writes the keys AND the
+ * values of the T newest tokens of every k / v item into the cache of mi_block_attention_decode_* — contiguous or paged,
+ * 2-byte or e4m3fn bytes — at the positions the lengths name.
+ *   items, heads   as in the decode entries: items = B · heads, item c is head c % heads of batch item c / heads; items ≤ 65535;
+ *   k_new, v_new   the source, 2-byte patterns (bfloat16 or float16), never copied: token t of item c at k_new + (c / heads) ·
+ *              batchKn + (c % heads) · headKn + t · ldkn, D elements (v_new likewise); 16-byte aligned, every stride a
+ *              non-negative multiple of 8 elements — two slices of one fused projection [B, T, Hq + 2·heads, D] fit;
+ *   k, v       the destination with the strides of the decode entries: row j of item c at k + (c / heads) · batchK +
+ *              (c % heads) · headK + j · ldk; 16-byte aligned, ldk ≥ D, every stride a multiple of 8 elements (16 e4m3fn bytes);
+ *              paged (k_pages, pageK …): row r of head h of pool page e at k_pages + e · pageK + h · headK + r · ldk, with
+ *              block_table, table_ld, pages, page as in mi_block_attention_decode_paged_*; Smax = the logical pages · page;
+ *   k_lens     int32 [lens_count] on the device, the lengths AFTER the append — what the decode entry receives next; item c
+ *              has entry c / (items / lens_count).  NOT clamped.
+ * Token t of item c goes to pos = k_len − T + t.  It is written iff 0 ≤ pos < Smax and, paged, block_table[(c / heads) ·
+ * table_ld + pos / page] lies in [0, pages); otherwise it is DROPPED — nothing is stored for it anywhere, nothing wraps or
+ * moves.  Everything the rule does not write keeps its bytes (other rows, the gap between rows, unreferenced pages).  The
+ * source must not overlap the destination; two (item, token) pairs mapped to one pool row stay inside the operands, but which
+ * write lands is unspecified.
+ *   _b16       a bit copy, the same for both 2-byte types (NaN payloads and −0 kept);
+ *   _fp8_T     the stored byte is that of torch's CPU expression (float32(x) / scale[h]).clamp(−448, 448).to(float8_e4m3fn):
+ *              an IEEE float32 division, the clamp, one round-to-nearest-even into OCP e4m3fn; a NaN quotient becomes a NaN
+ *              code (byte & 0x7F == 0x7F).  k_scale, k_scale_count, v_scale, v_scale_count as in the fp8 decode entries: read
+ *              on the device, never read back; NULL is 1.
+ * No atomics, no workspace, no read-back: graph-capturable while k_lens, the table and the scales are updated in place.
+ * Validation before any HIP call: D ∉ {32, 64, 96, 128}, a negative size, items > 65535, items % heads != 0, lens_count < 1 or
+ * items % lens_count != 0, a NULL / misaligned pointer, a stride that is negative or no multiple of 8 (cache of bytes: 16), ldk
+ * < D, page < 16 or no power of two, Smax % page != 0, pages < 0, table_ld < Smax / page, a scale count other than 1 or heads
+ * → MI_EINVAL; items · T · D/8 ≥ 2³¹ → MI_ERANGE; items == 0 or T == 0 → MI_OK, nothing touched; Smax == 0 or pages == 0 →
+ * MI_OK, every token dropped (the destination may be NULL).
+ * ------------------------------------------------------------------------ */
+int mi_kv_append_b16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, const uint16_t* k_new, int64_t ldkn,
+                     int64_t headKn, int64_t batchKn, const uint16_t* v_new, int64_t ldvn, int64_t headVn, int64_t batchVn,
+                     uint16_t* k, int64_t ldk, int64_t headK, int64_t batchK, uint16_t* v, int64_t ldv, int64_t headV,
+                     int64_t batchV, const int32_t* k_lens, int32_t lens_count, mi_stream_t stream);
+int mi_kv_append_paged_b16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table, int64_t table_ld,
+                           int32_t pages, int32_t page, int32_t D, const uint16_t* k_new, int64_t ldkn, int64_t headKn,
+                           int64_t batchKn, const uint16_t* v_new, int64_t ldvn, int64_t headVn, int64_t batchVn,
+                           uint16_t* k_pages, int64_t ldk, int64_t headK, int64_t pageK, uint16_t* v_pages, int64_t ldv,
+                           int64_t headV, int64_t pageV, const int32_t* k_lens, int32_t lens_count, mi_stream_t stream);
+int mi_kv_append_fp8_bf16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, const uint16_t* k_new, int64_t ldkn,
+                          int64_t headKn, int64_t batchKn, const uint16_t* v_new, int64_t ldvn, int64_t headVn, int64_t batchVn,
+                          uint8_t* k, int64_t ldk, int64_t headK, int64_t batchK, uint8_t* v, int64_t ldv, int64_t headV,
+                          int64_t batchV, const int32_t* k_lens, int32_t lens_count, const float* k_scale, int32_t k_scale_count,
+                          const float* v_scale, int32_t v_scale_count, mi_stream_t stream);
+int mi_kv_append_fp8_f16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, const uint16_t* k_new, int64_t ldkn,
+                         int64_t headKn, int64_t batchKn, const uint16_t* v_new, int64_t ldvn, int64_t headVn, int64_t batchVn,
+                         uint8_t* k, int64_t ldk, int64_t headK, int64_t batchK, uint8_t* v, int64_t ldv, int64_t headV,
+                         int64_t batchV, const int32_t* k_lens, int32_t lens_count, const float* k_scale, int32_t k_scale_count,
+                         const float* v_scale, int32_t v_scale_count, mi_stream_t stream);
+int mi_kv_append_paged_fp8_bf16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                int64_t table_ld, int32_t pages, int32_t page, int32_t D, const uint16_t* k_new, int64_t ldkn,
+                                int64_t headKn, int64_t batchKn, const uint16_t* v_new, int64_t ldvn, int64_t headVn,
+                                int64_t batchVn, uint8_t* k_pages, int64_t ldk, int64_t headK, int64_t pageK, uint8_t* v_pages,
+                                int64_t ldv, int64_t headV, int64_t pageV, const int32_t* k_lens, int32_t lens_count,
+                                const float* k_scale, int32_t k_scale_count, const float* v_scale, int32_t v_scale_count,
+                                mi_stream_t stream);
+int mi_kv_append_paged_fp8_f16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                               int64_t table_ld, int32_t pages, int32_t page, int32_t D, const uint16_t* k_new, int64_t ldkn,
+                               int64_t headKn, int64_t batchKn, const uint16_t* v_new, int64_t ldvn, int64_t headVn,
+                               int64_t batchVn, uint8_t* k_pages, int64_t ldk, int64_t headK, int64_t pageK, uint8_t* v_pages,
+                               int64_t ldv, int64_t headV, int64_t pageV, const int32_t* k_lens, int32_t lens_count,
+                               const float* k_scale, int32_t k_scale_count, const float* v_scale, int32_t v_scale_count,
+                               mi_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in
  * bfloat16 / float16 (T, 2-byte bit patterns) with A given as the kept 64 × 64 blocks of a CSR block list, shared by
  * every item of the batch, and the sampled product on the same list:

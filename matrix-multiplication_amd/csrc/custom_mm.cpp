@@ -52,6 +52,7 @@ namespace {
 #include "custom_mm_block_attention_decode.inc"
 #include "custom_mm_block_attention_decode_paged.inc"
 #include "custom_mm_block_attention_decode_fp8.inc"
+#include "custom_mm_kv_append.inc"
 #include "custom_mm_bsr.inc"
 #include "custom_mm_bsr_linear.inc"
 
@@ -211,6 +212,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("block_attention_decode_paged_fp8", &block_attention_decode_paged_fp8,
         "(offsets, columns, nnz, q, k_pages, v_pages [P, Hkv, page, D] float8_e4m3fn, block_table int32 [B, W], k_lens, scale, "
         "k_scale, v_scale, chunk, out, lse): block_attention_decode_paged over an fp8 pool");
+  m.def("kv_append", &kv_append,
+        "(k_new, v_new [B, Hkv, T, D] bfloat16 / float16 through their own strides, k, v [B, Hkv, Smax, D] of that dtype or "
+        "float8_e4m3fn, k_lens int32 [B] or [1] — the lengths AFTER the append —, k_scale, v_scale (None or float32 device tensors "
+        "of 1 or Hkv entries)): token t of item b written at k_lens[b] - T + t, or dropped outside [0, Smax); one launch for k and v");
+  m.def("kv_append_paged", &kv_append_paged,
+        "(k_new, v_new, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, k_scale, v_scale): kv_append into a "
+        "pool of pages; a token whose table entry lies outside [0, P) is dropped");
   m.def("bsr_mm", &bsr_mm,
         "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
         "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");

@@ -2092,9 +2092,10 @@ def _check_fp8_cache(what, operands):
                              f'(not e4m3fnuz, not e5m2, not raw bytes; accepted: {_DECODE_FP8_SIZES_TEXT})')
 
 
-def _check_fp8_scales(what, scales, Hkv, q):
+def _check_fp8_scales(what, scales, Hkv, q, ref='q'):
     '''The scales of an fp8 decode call, (name, scale) pairs: each None, a Python float, or a float32 tensor of shape (),
-    (1,) or (Hkv,) (ValueError) on q's device (RuntimeError).  Returns the tensors among them by name, for _check_on_device.'''
+    (1,) or (Hkv,) (ValueError) on q's device (RuntimeError; `ref` names q in the message: the append calls have a k_new
+    there).  Returns the tensors among them by name, for _check_on_device.'''
     tensors = {}
     for name, s in scales:
         if s is None or (isinstance(s, (float, int)) and not isinstance(s, bool)):
@@ -2107,7 +2108,7 @@ def _check_fp8_scales(what, scales, Hkv, q):
             raise ValueError(f'{what}: {name} must have shape (), (1,) or ({Hkv},) — one scale, or one per k / v head —, got '
                              f'{tuple(s.shape)}')
         if s.device != q.device:
-            raise RuntimeError(f'{what}: {name} is on {s.device} but q is on {q.device}: a scale is read by the kernel, on q\'s device')
+            raise RuntimeError(f'{what}: {name} is on {s.device} but {ref} is on {q.device}: a scale is read by the kernel, on {ref}\'s device')
         tensors[name] = s
     return tensors
 
@@ -2240,6 +2241,190 @@ def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tens
                                                        float(scale), _fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device),
                                                        int(chunk), out, lse)
     return (out, lse) if return_lse else out
+
+
+# --------------------------------------------------------------------------- #
+# the fused KV-cache append: the write side of the four decode calls
+# --------------------------------------------------------------------------- #
+
+_KV_APPEND_SIZES_TEXT = ('bfloat16 or float16 k_new and v_new, a cache of their dtype or float8_e4m3fn, head size D in '
+                         '{32, 64, 96, 128}')
+
+
+def kv_cache_append_takes(dtype, cache_dtype, D) -> bool:
+    '''Whether kv_cache_append takes a source of `dtype`, a cache of `cache_dtype` and head size D — a function of these
+    alone: dtype bfloat16 / float16, cache_dtype that dtype or float8_e4m3fn, D ∈ {32, 64, 96, 128}.'''
+    return dtype in _LOWP and cache_dtype in (dtype, torch.float8_e4m3fn) and isinstance(D, int) and not isinstance(D, bool) and \
+        D in _BLOCK_HEAD_SIZES
+
+
+def kv_cache_append_paged_takes(dtype, cache_dtype, D, page) -> bool:
+    '''… and kv_cache_append_paged: kv_cache_append_takes(dtype, cache_dtype, D) and page a power of two ≥ 16.'''
+    return kv_cache_append_takes(dtype, cache_dtype, D) and _page_ok(page)
+
+
+def _check_source_strides(what, name, t):
+    '''The source of an append is read through its own strides and never copied: the ValueError names the stride that does
+    not fit.'''
+    if t.shape[3] > 1 and t.stride(3) != 1:
+        raise ValueError(f'{what}: {name} must have a last stride of 1, got {t.stride(3)} (the source is never copied)')
+    for d, dim in ((2, 'token'), (1, 'head'), (0, 'batch')):
+        if t.shape[d] > 1 and (t.stride(d) < 0 or t.stride(d) % 8 != 0):
+            raise ValueError(f'{what}: {name}\'s {dim} stride must be a multiple of 8 elements, got {t.stride(d)} (the source is '
+                             f'never copied)')
+    if t.data_ptr() % 16 != 0:
+        raise ValueError(f'{what}: {name}\'s data pointer must be 16-byte aligned (the source is never copied)')
+
+
+def _check_kv_append_operands(what, names, k_new, v_new, k, v, k_lens, scales, block_table=None):
+    '''Every refusal of kv_cache_append and kv_cache_append_paged before the first device call, split as
+    _check_block_attention_operands splits them: ValueError for what an operand is, RuntimeError for operands that do not
+    go together (mixed dtypes, host tensors / devices).  `names`: the cache operands' names; block_table: the paged form.
+    Returns whether the cache is fp8.'''
+    kn, vn = names
+    paged = kn == 'k_pages'
+    _check_lowp_operands(what, (('k_new', k_new), ('v_new', v_new)), _KV_APPEND_SIZES_TEXT)
+    for name, t in ((kn, k), (vn, v)):
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be a dense tensor')
+    fp8 = k.dtype.itemsize == 1 or v.dtype.itemsize == 1
+    if fp8:
+        _check_fp8_cache(what, ((kn, k), (vn, v)))
+    else:
+        for name, t in ((kn, k), (vn, v)):
+            if t.dtype not in _LOWP:
+                raise ValueError(f'{what}: {name} must have k_new\'s dtype or be float8_e4m3fn, got {t.dtype} (accepted: '
+                                 f'{_KV_APPEND_SIZES_TEXT})')
+            if t.dtype != k_new.dtype:
+                raise RuntimeError(f'{what}: k_new is {k_new.dtype} but {name} is {t.dtype}: a 2-byte cache is a bit copy of the '
+                                   f'source and must have its dtype')
+        for name, s in scales:
+            if s is not None:
+                raise ValueError(f'{what}: {name} goes with a float8_e4m3fn cache only, but {kn} is {k.dtype}')
+    if k_new.dim() != 4 or v_new.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError(f'{what}: k_new and v_new must be [B, Hkv, T, D] and {kn}, {vn} '
+                         f'{"[P, Hkv, page, D]" if paged else "[B, Hkv, Smax, D]"}, got {k_new.dim()}-d, {v_new.dim()}-d, '
+                         f'{k.dim()}-d and {v.dim()}-d')
+    B, Hkv, T, D = k_new.shape
+    if tuple(v_new.shape) != tuple(k_new.shape):
+        raise ValueError(f'{what}: v_new must have k_new\'s shape {tuple(k_new.shape)}, got {tuple(v_new.shape)}')
+    if D not in _BLOCK_HEAD_SIZES:
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_KV_APPEND_SIZES_TEXT})')
+    if T < 1 or Hkv < 1:
+        raise ValueError(f'{what}: k_new must hold T >= 1 new tokens of Hkv >= 1 heads, got T = {T}, Hkv = {Hkv}')
+    if (not paged and k.shape[0] != B) or k.shape[1] != Hkv or k.shape[3] != D:
+        raise ValueError(f'{what}: k_new of shape {tuple(k_new.shape)} needs {kn} '
+                         f'{("P", Hkv, "page", D) if paged else (B, Hkv, "Smax", D)}, got {tuple(k.shape)}')
+    if tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f'{what}: {vn} must be a dense tensor with {kn}\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
+    tensors = {}
+    if paged:
+        page = k.shape[2]
+        if not _page_ok(page):
+            raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} rows, got page = {page}')
+        if not isinstance(block_table, torch.Tensor) or block_table.layout != torch.strided:
+            raise ValueError(f'{what}: block_table is required and must be a dense tensor')
+        if block_table.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f'{what}: block_table must be an int32 or int64 tensor, got {block_table.dtype}')
+        if block_table.dim() != 2 or block_table.shape[0] != B:
+            raise ValueError(f'{what}: block_table must have shape ({B}, W) — a row of logical pages per batch item —, got '
+                             f'{tuple(block_table.shape)}')
+        W = block_table.shape[1]
+        if W > 1 and block_table.stride(1) != 1:
+            raise ValueError(f'{what}: block_table must have a last stride of 1, got {block_table.stride(1)}')
+        if B > 1 and block_table.stride(0) < W:
+            raise ValueError(f'{what}: block_table\'s row stride must be at least W = {W}, got {block_table.stride(0)}')
+        tensors['block_table'] = block_table
+        Smax = W * page
+    else:
+        Smax = k.shape[2]
+    if B * Hkv > _DECODE_MAX_GRID:
+        raise ValueError(f'{what}: B·Hkv = {B * Hkv} must be at most {_DECODE_MAX_GRID}, as in the decode calls')
+    if B * Hkv * T * (D // 8) >= 2 ** 31 or Smax >= 2 ** 31:
+        raise ValueError(f'{what}: B·Hkv·T·D/8 = {B * Hkv * T * (D // 8)} and Smax = {Smax} must fit int32 indices')
+    if not isinstance(k_lens, torch.Tensor) or k_lens.layout != torch.strided:
+        raise ValueError(f'{what}: k_lens is required and must be a dense tensor')
+    if k_lens.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'{what}: k_lens must be an int32 or int64 tensor, got {k_lens.dtype}')
+    if tuple(k_lens.shape) not in ((), (B,)):
+        raise ValueError(f'{what}: k_lens must have shape ({B},) — one length per batch item — or be 0-d, got {tuple(k_lens.shape)}')
+    _check_source_strides(what, 'k_new', k_new)
+    _check_source_strides(what, 'v_new', v_new)
+    outer = 'page' if paged else 'batch'
+    _check_cache_strides(what, kn, k, D, outer, 16 if fp8 else 8)
+    _check_cache_strides(what, vn, v, D, outer, 16 if fp8 else 8)
+    _check_on_device(what, k_new=k_new, v_new=v_new, **{kn: k, vn: v}, **tensors, k_lens=k_lens,
+                     **_check_fp8_scales(what, scales if fp8 else (), Hkv, k_new, 'k_new'))
+    return fp8
+
+
+def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k_lens: torch.Tensor, *,
+                    k_scale=None, v_scale=None) -> None:
+    '''Writes the keys and values of the T ≥ 1 newest tokens of every item into the cache the decode calls read, IN PLACE and
+    in one launch for k and v: k_new, v_new [B, Hkv, T, D] bfloat16 or float16 (one dtype), k and v [B, Hkv, Smax, D] — the
+    operands of block_sparse_attention_decode (the source's dtype: a bit copy) or of block_sparse_attention_decode_fp8
+    (torch.float8_e4m3fn: quantised; float8_e4m3fnuz, float8_e5m2 and uint8 raise ValueError).  D ∈ {32, 64, 96, 128}; Smax
+    needs no relation to a block size (kv_cache_append_takes).  Returns None.  NO autograd: the operands are detached.
+
+    k_lens is the decode calls' operand — an int32 / int64 device tensor [B], or 0-d, narrowed to int32 on the device, never
+    read back — and holds the lengths AFTER the append: the same tensor the decode call receives next.  Token t of item b
+    goes to pos = k_lens[b] − T + t and is written iff 0 ≤ pos < Smax; otherwise it is DROPPED and nothing is stored for it
+    anywhere.  k_lens is NOT clamped for this: a length beyond Smax drops the tokens that do not fit, it never moves them.
+    Everything the rule does not write keeps its bytes — other rows, the gaps between the rows of a padded cache.
+
+    NOTHING IS COPIED.  The source is read through its own strides — last stride 1, every other stride a multiple of 8
+    elements, a 16-byte aligned data pointer — so k_new and v_new may be slices of one fused projection
+    [B, T, Hq + 2·Hkv, D] seen through .transpose(1, 2); the cache as the decode calls read it (row stride ≥ D, strides
+    multiples of 8 elements, 16 of an fp8 cache).  Anything else raises ValueError naming the stride.  The source must not
+    overlap the cache.
+
+    Bits.  A 2-byte cache receives bit copies, NaN payloads and −0 included.  An fp8 cache receives, per element, the byte
+    of kv_to_fp8(x_new, scale)[0] as torch computes it on the CPU: float32(x) / scale[h] — an IEEE float32 division —,
+    clamped to ±448, rounded to nearest even into e4m3fn; a NaN becomes a NaN code (byte & 0x7F == 0x7F).  k_scale, v_scale:
+    None (= 1), a Python float, or a float32 device tensor of shape (), (1,) or (Hkv,), handed over as device pointers — a
+    scale tensor updated in place is followed; with a 2-byte cache a scale is a ValueError.
+
+    No read-back, no host synchronisation, no atomics: `lens += 1; kv_cache_append(…); block_sparse_attention_decode(…)`
+    can be captured in one graph and replayed.'''
+    what = 'kv_cache_append'
+    scales = (('k_scale', k_scale), ('v_scale', v_scale))
+    fp8 = _check_kv_append_operands(what, ('k', 'v'), k_new, v_new, k, v, k_lens, scales)
+    if k_new.numel() == 0 or k.numel() == 0:
+        return None
+    with torch.no_grad():
+        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
+        ks, vs = (_fp8_scale(k_scale, k_new.device), _fp8_scale(v_scale, k_new.device)) if fp8 else (None, None)
+        custom_mm.kv_append(k_new.detach(), v_new.detach(), k.detach(), v.detach(), lens, ks, vs)
+    return None
+
+
+def kv_cache_append_paged(k_new: torch.Tensor, v_new: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
+                          block_table: torch.Tensor, k_lens: torch.Tensor, *, k_scale=None, v_scale=None) -> None:
+    '''kv_cache_append into a PAGED cache: k_pages and v_pages [P, Hkv, page, D] and block_table [B, W] are the operands of
+    block_sparse_attention_decode_paged (or, float8_e4m3fn, of its fp8 form): `page` a power of two ≥ 16, the table int32 or
+    int64 with a last stride of 1 and any row stride ≥ W — an int32 table is handed over as it is, an int64 table is
+    narrowed on the device —, the logical length Smax = W · page (kv_cache_append_paged_takes).  Token t of item b goes to
+    pos = k_lens[b] − T + t, i.e. to row pos % page of pool page block_table[b, pos // page]; it is written iff
+    0 ≤ pos < Smax AND that entry lies in [0, P) — the −1 of an unallocated slot drops the token, nothing is stored for it
+    anywhere.  Unreferenced pages keep their bytes.  Source, strides (the pool's page stride in the place of the batch
+    stride), bits, scales, k_lens and the refusals are kv_cache_append\'s.
+
+    The source must not overlap the pool.  Two (item, token) pairs mapped to one pool row — items sharing a page they both
+    write — are the caller\'s business: the kernel stays inside the operands, but which write lands is unspecified.
+    Graph-capturable while k_lens, the table and the scales are updated in place.'''
+    what = 'kv_cache_append_paged'
+    scales = (('k_scale', k_scale), ('v_scale', v_scale))
+    fp8 = _check_kv_append_operands(what, ('k_pages', 'v_pages'), k_new, v_new, k_pages, v_pages, k_lens, scales, block_table)
+    if k_new.numel() == 0 or k_pages.numel() == 0 or block_table.numel() == 0:
+        return None
+    with torch.no_grad():
+        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
+        table = block_table.detach()
+        if table.dtype != torch.int32:
+            table = table.to(torch.int32)
+        ks, vs = (_fp8_scale(k_scale, k_new.device), _fp8_scale(v_scale, k_new.device)) if fp8 else (None, None)
+        custom_mm.kv_append_paged(k_new.detach(), v_new.detach(), k_pages.detach(), v_pages.detach(), table, lens, ks, vs)
+    return None
 
 
 # --------------------------------------------------------------------------- #
