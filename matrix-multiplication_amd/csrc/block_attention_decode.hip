@@ -348,12 +348,17 @@ __device__ __forceinline__ float merge_weight(float m, float M) { return m == -I
 // element d of the row of query head g of (c, t): normalised, rounded once; the row's log-sum-exp with its element 0.
 // SCALED: `vs`, the fp8 forms' v_scale of the item's head (value_scale: read once at the kernel's start, 1 for a null
 // pointer — every 2-byte call), multiplies the normalised element; the 2-byte walk, which never has one, does not look.
+// The last product is rounded to fp32 BEFORE it is narrowed, whatever T and SCALED: left alone, the compiler folds the
+// product and the narrowing to float16 into one v_fma_mixlo_f16, which rounds the exact product once — O · inv in the
+// 2-byte walk, x · vs in the other forms — and the fp8 call at scale 1 then differs from the 2-byte call on the widened
+// cache in the last bit of about one float16 element in 10⁴ (found at 64-entry lists).  The empty asm keeps them apart.
 template <class T, bool SCALED>
 __device__ __forceinline__ void finish(const Args& a, int c, int t, int g, int d, float M, float L, float O, float vs) {
   const float inv = L == 0.f ? 0.f : 1.f / L;
   const long item = (long)c * a.group + g;
   float x = O * inv;
   if constexpr (SCALED) x *= vs;
+  asm("" : "+v"(x));  // (no instruction: x is an fp32 value of its own before it is narrowed)
   a.out[item * a.strideO + (long)t * a.ldo + d] = T::down(x);
   if (d == 0) a.lse[item * a.T + t] = L == 0.f ? -INFINITY : M + __logf(L);
 }

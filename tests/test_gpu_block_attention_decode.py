@@ -6,7 +6,8 @@ for bit: a strided cache against its contiguous clone, an item of a batch agains
 against a repeated one, block = 128 against the 64-block layout expanded here, a graph replay against the eager call.
 
 Smax = 512 (8 blocks), B · Hkv ≤ 8; chunk=2 wherever the split matters: several chunks, chunks with fewer entries than
-waves, empty trailing chunks."""
+waves, empty trailing chunks.  Long lists (16 and 64 entries: three and more turns per wave, up to 64 partials) live in
+tests/test_gpu_block_attention_decode_long.py."""
 import ctypes
 
 import pytest

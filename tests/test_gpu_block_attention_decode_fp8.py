@@ -6,7 +6,8 @@ the gathered cache.  Accuracy where scales are no powers of two is the project's
 operands.  fp8 data is made from bytes on the CPU and written through uint8 views: no fp8 operator of torch runs on the
 device.  The NaN code 0x7F stands wherever nothing may be read.
 
-Smax = 512, B · Hkv ≤ 8, chunk=2 unless stated."""
+Smax = 512, B · Hkv ≤ 8, chunk=2 unless stated.  Long lists (64 entries, up to 16 turns per wave) live in
+tests/test_gpu_block_attention_decode_long.py."""
 import ctypes
 
 import pytest

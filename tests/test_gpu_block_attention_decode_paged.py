@@ -6,7 +6,8 @@ against dense masked attention in float64 (the helpers of tests/test_gpu_block_a
 invisible keys of an out-of-range table entry.
 
 Smax = 512, B · Hkv ≤ 8, chunk=2 unless stated.  Pools: P = B · W + 3 pages, the logical → physical map a seeded
-permutation (physical neighbours are not logical neighbours), unreferenced pages NaN."""
+permutation (physical neighbours are not logical neighbours), unreferenced pages NaN.  Long lists (64 entries: the tiles of
+the in-loop look-ahead, holes met in a wave's third turn and later) live in tests/test_gpu_block_attention_decode_long.py."""
 import ctypes
 
 import pytest
