@@ -1238,6 +1238,79 @@ int mi_kv_append_paged_fp8_f16(int32_t items, int32_t heads, int32_t T, int32_t 
                                mi_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * The fused rotary embedding + KV-cache append: the step in front of mi_kv_append_*, fused into it.  ONE
+ * launch rotates q and the new keys by position with the caller's cos / sin tables, writes the rotated keys and the values
+ * into the cache of mi_block_attention_decode_* — contiguous or paged, 2-byte or e4m3fn bytes — and the rotated q into q_out.
+ * items, heads, T, Smax, D, k_new, v_new, k, v (k_pages, v_pages), block_table, table_ld, pages, page, k_lens, the scales and
+ * their strides and alignments are those of mi_kv_append_*, with one difference: lens_count is 1 or B = items / heads (q has
+ * no k / v head, so a length per k / v item has no meaning here).  Added to them:
+ *   q_heads    Hq ≥ 1 query heads per batch item; no relation to `heads` is required;
+ *   q          the queries, 2-byte patterns read through their own strides like k_new: token t of head h of batch item b at
+ *              q + b · batchQ + h · headQ + t · ldq, D elements; 16-byte aligned, every stride a non-negative multiple of 8;
+ *   q_out      receives the rotated q, with strides of its own under the same rules; q_out == q (same strides) rotates in place;
+ *   k_out      NULL — the rotated k goes to the cache only — or, under the same rules, an operand [B, heads, T, D] that ALSO
+ *              receives the rotated k in the source type; k_out == k_new (same strides) rotates in place;
+ *   cos, sin   float32 [table_rows][ld] on the device, 16-byte aligned, ld ≥ rotary_dim / 2 and a multiple of 4: row p holds
+ *              the rotary_dim / 2 cosines / sines of position p.  No trigonometry is computed: the tables define the angles;
+ *   rotary_dim R, a multiple of 16 with 16 ≤ R ≤ D: elements d ≥ R of q and k are bit copies;
+ *   interleaved  0: pair i is (x[i], x[i + R/2]) — the NeoX halves; non-zero: (x[2i], x[2i + 1]) — GPT-J;
+ *   new_lens   NULL, or int32 [B] on the device: batch item b has n = clamp(new_lens[b], 0, T) new tokens, standing in the LAST
+ *              n of the T slots.  NULL: n = T.
+ * The rule.  pos = k_len − T + t in 64 bits, k_len not clamped.  Slot t of batch item b HOLDS A TOKEN iff t ≥ T − n and
+ * 0 ≤ pos < table_rows.  No token: the slot's rows of q_out, and of k_out if given, are written as zeros and nothing is stored
+ * into the cache.  A token: its q rows and its k row are rotated by table row pos; q goes to q_out, k to k_out if given; k and
+ * v are written into the cache iff mi_kv_append_*'s condition holds (0 ≤ pos < Smax and, paged, the table entry in [0, pages)),
+ * and dropped otherwise — q is still rotated.  Everything the rule does not write keeps its bytes.
+ * Bits.  With c = cos[pos · ld + i], s = sin[pos · ld + i] and the pair (a, b) widened exactly to float32:
+ *     a' = fl32(fl32(a·c) − fl32(b·s))        b' = fl32(fl32(b·c) + fl32(a·s))
+ * two products and one sum, each rounded to float32, never contracted into an fma, float32 subnormals kept; then ONE
+ * round-to-nearest-even to the source type — torch's CPU result of (a.float() * c − b.float() * s).to(T).  A NaN result is a
+ * NaN of unspecified payload.  Elements d ≥ R of q and k, and all of v, are bit copies.  An fp8 cache receives the bytes of
+ * mi_kv_append_fp8_T applied to the rotated k AFTER its rounding to the source type, and to v: all four forms leave the cache
+ * that mi_kv_append_* leaves for the rounded rotated k.
+ * No atomics, no workspace, no read-back: graph-capturable while k_lens, new_lens, the tables and the scales are updated in
+ * place.  Operands other than q_out == q and k_out == k_new must not overlap what is written.
+ * Validation before any HIP call: what mi_kv_append_* refuses, lens_count other than 1 or items / heads, q_heads < 0 (or 0 with
+ * work to do), table_rows < 0, rotary_dim < 16, > D or no multiple of 16, a NULL / misaligned q or q_out or a stride of theirs
+ * (or of a non-NULL k_out) that is negative or no multiple of 8, ld < rotary_dim / 2 or no multiple of 4, NULL / misaligned cos
+ * or sin with table_rows > 0, a new_lens that is not 4-byte aligned → MI_EINVAL; B · (q_heads + 2 · heads) · T · D/8 ≥ 2³¹ →
+ * MI_ERANGE; items == 0 or T == 0 → MI_OK, nothing touched.  Smax == 0 or pages == 0: every k / v row is dropped (the
+ * destination may be NULL), q is still rotated.
+ * ------------------------------------------------------------------------ */
+#define MI_ROPE_KV_APPEND_OPERANDS(CT)                                                                                           \
+  int32_t q_heads, const uint16_t *q, int64_t ldq, int64_t headQ, int64_t batchQ, uint16_t *q_out, int64_t ldqo, int64_t headQo, \
+      int64_t batchQo, const uint16_t *k_new, int64_t ldkn, int64_t headKn, int64_t batchKn, const uint16_t *v_new,              \
+      int64_t ldvn, int64_t headVn, int64_t batchVn, uint16_t *k_out, int64_t ldko, int64_t headKo, int64_t batchKo,             \
+      const float *cos, const float *sin, int32_t table_rows, int64_t ld, int32_t rotary_dim, int32_t interleaved, CT *k,        \
+      int64_t ldk, int64_t headK, int64_t batchK, CT *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens,      \
+      int32_t lens_count, const int32_t *new_lens
+int mi_rope_kv_append_bf16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint16_t),
+                           mi_stream_t stream);
+int mi_rope_kv_append_f16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint16_t),
+                          mi_stream_t stream);
+/* (paged: k, batchK, v, batchV of the operand list are k_pages, pageK, v_pages, pageV) */
+int mi_rope_kv_append_paged_bf16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                 int64_t table_ld, int32_t pages, int32_t page, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint16_t),
+                                 mi_stream_t stream);
+int mi_rope_kv_append_paged_f16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                int64_t table_ld, int32_t pages, int32_t page, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint16_t),
+                                mi_stream_t stream);
+int mi_rope_kv_append_fp8_bf16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint8_t),
+                               const float* k_scale, int32_t k_scale_count, const float* v_scale, int32_t v_scale_count,
+                               mi_stream_t stream);
+int mi_rope_kv_append_fp8_f16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint8_t),
+                              const float* k_scale, int32_t k_scale_count, const float* v_scale, int32_t v_scale_count,
+                              mi_stream_t stream);
+int mi_rope_kv_append_paged_fp8_bf16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                     int64_t table_ld, int32_t pages, int32_t page, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint8_t),
+                                     const float* k_scale, int32_t k_scale_count, const float* v_scale, int32_t v_scale_count,
+                                     mi_stream_t stream);
+int mi_rope_kv_append_paged_fp8_f16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                    int64_t table_ld, int32_t pages, int32_t page, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint8_t),
+                                    const float* k_scale, int32_t k_scale_count, const float* v_scale, int32_t v_scale_count,
+                                    mi_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in
  * bfloat16 / float16 (T, 2-byte bit patterns) with A given as the kept 64 × 64 blocks of a CSR block list, shared by
  * every item of the batch, and the sampled product on the same list:

@@ -53,6 +53,7 @@ namespace {
 #include "custom_mm_block_attention_decode_paged.inc"
 #include "custom_mm_block_attention_decode_fp8.inc"
 #include "custom_mm_kv_append.inc"
+#include "custom_mm_rope_kv_append.inc"
 #include "custom_mm_bsr.inc"
 #include "custom_mm_bsr_linear.inc"
 
@@ -219,6 +220,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_append_paged", &kv_append_paged,
         "(k_new, v_new, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, k_scale, v_scale): kv_append into a "
         "pool of pages; a token whose table entry lies outside [0, P) is dropped");
+  m.def("rope_kv_append", &rope_kv_append,
+        "(q [B, Hq, T, D], k_new, v_new [B, Hkv, T, D] bfloat16 / float16 through their own strides, cos, sin float32 [Pmax, R/2], "
+        "k, v [B, Hkv, Smax, D] of that dtype or float8_e4m3fn, k_lens int32 [B] or [1] — the lengths AFTER the append —, new_lens "
+        "int32 [B] or None, q_out [B, Hq, T, D], k_out [B, Hkv, T, D] or None, rotary_dim R, interleaved, k_scale, v_scale): q and "
+        "k_new rotated by table row k_lens[b] - T + t; rotated q to q_out, rotated k and v into the cache as kv_append writes them, "
+        "in one launch; returns q_out");
+  m.def("rope_kv_append_paged", &rope_kv_append_paged,
+        "(q, k_new, v_new, cos, sin, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, new_lens, q_out, k_out, "
+        "rotary_dim, interleaved, k_scale, v_scale): rope_kv_append into a pool of pages");
   m.def("bsr_mm", &bsr_mm,
         "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
         "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");

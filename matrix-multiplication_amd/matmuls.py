@@ -2428,6 +2428,188 @@ def kv_cache_append_paged(k_new: torch.Tensor, v_new: torch.Tensor, k_pages: tor
 
 
 # --------------------------------------------------------------------------- #
+# the fused rotary embedding + KV-cache append: the step in front of the append, in its launch
+# --------------------------------------------------------------------------- #
+
+_ROPE_SIZES_TEXT = ('bfloat16 or float16 q, k_new and v_new, a cache of their dtype or float8_e4m3fn, head size D in '
+                    '{32, 64, 96, 128}, rotary_dim a multiple of 16 in [16, D]')
+
+
+def _rotary_dim_ok(D, rotary_dim) -> bool:
+    return isinstance(rotary_dim, int) and not isinstance(rotary_dim, bool) and 16 <= rotary_dim <= D and rotary_dim % 16 == 0
+
+
+def rope_kv_cache_append_takes(dtype, cache_dtype, D, rotary_dim) -> bool:
+    '''Whether rope_kv_cache_append takes a source of `dtype`, a cache of `cache_dtype`, head size D and `rotary_dim`
+    rotated elements (None: D) — a function of these alone: kv_cache_append_takes(dtype, cache_dtype, D) and rotary_dim a
+    multiple of 16 with 16 ≤ rotary_dim ≤ D.'''
+    return kv_cache_append_takes(dtype, cache_dtype, D) and _rotary_dim_ok(D, D if rotary_dim is None else rotary_dim)
+
+
+def rope_kv_cache_append_paged_takes(dtype, cache_dtype, D, rotary_dim, page) -> bool:
+    '''… and rope_kv_cache_append_paged: rope_kv_cache_append_takes(dtype, cache_dtype, D, rotary_dim) and page a power of
+    two ≥ 16.'''
+    return rope_kv_cache_append_takes(dtype, cache_dtype, D, rotary_dim) and _page_ok(page)
+
+
+def _check_rope_operands(what, q, k_new, cos, sin, rotary_dim, new_lens, q_out, k_out):
+    '''What the fused call refuses beyond the append's own operands, for a k_new that is a [B, Hkv, T, D] tensor with an
+    accepted D (anything else is named by _check_kv_append_operands afterwards): ValueError for what an operand is,
+    RuntimeError for dtypes that do not go together.  Returns (rotary_dim, the tensors among the operands by name).'''
+    B, Hkv, T, D = k_new.shape
+    if q.dim() != 4 or q.shape[0] != B or q.shape[2] != T or q.shape[3] != D or q.shape[1] < 1:
+        raise ValueError(f'{what}: k_new of shape {tuple(k_new.shape)} needs q {(B, "Hq", T, D)} with Hq >= 1, got {tuple(q.shape)}')
+    Hq = q.shape[1]
+    R = D if rotary_dim is None else rotary_dim
+    if not _rotary_dim_ok(D, R):
+        raise ValueError(f'{what}: rotary_dim must be None or a multiple of 16 with 16 <= rotary_dim <= D = {D}, got {rotary_dim!r}')
+    for name, t in (('cos', cos), ('sin', sin)):
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be a dense tensor')
+        if t.dtype != torch.float32:
+            raise ValueError(f'{what}: {name} must be a float32 tensor, got {t.dtype} (the tables define the angles: they are '
+                             f'never cast)')
+    if cos.dim() != 2 or cos.shape[1] != R // 2:
+        raise ValueError(f'{what}: cos must have shape (Pmax, rotary_dim / 2 = {R // 2}) — row p for position p —, got '
+                         f'{tuple(cos.shape)}')
+    if tuple(sin.shape) != tuple(cos.shape):
+        raise ValueError(f'{what}: sin must have cos\'s shape {tuple(cos.shape)}, got {tuple(sin.shape)}')
+    Pmax = cos.shape[0]
+    for name, t in (('cos', cos), ('sin', sin)):
+        if t.stride(1) != 1:
+            raise ValueError(f'{what}: {name} must have a last stride of 1, got {t.stride(1)} (the tables are never copied)')
+        if Pmax > 1 and (t.stride(0) < R // 2 or t.stride(0) % 4 != 0):
+            raise ValueError(f'{what}: {name}\'s row stride must be a multiple of 4 elements and at least rotary_dim / 2 = '
+                             f'{R // 2}, got {t.stride(0)} (the tables are never copied)')
+        if t.data_ptr() % 16 != 0:
+            raise ValueError(f'{what}: {name}\'s data pointer must be 16-byte aligned (the tables are never copied)')
+    if Pmax > 1 and sin.stride(0) != cos.stride(0):
+        raise ValueError(f'{what}: cos and sin must have one row stride, got {cos.stride(0)} and {sin.stride(0)}')
+    if Pmax >= 2 ** 31:
+        raise ValueError(f'{what}: cos must hold fewer than 2^31 rows, got {Pmax}')
+    tensors = {'cos': cos, 'sin': sin}
+    if new_lens is not None:
+        if not isinstance(new_lens, torch.Tensor) or new_lens.layout != torch.strided:
+            raise ValueError(f'{what}: new_lens must be None or a dense tensor')
+        if new_lens.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f'{what}: new_lens must be an int32 or int64 tensor, got {new_lens.dtype}')
+        if tuple(new_lens.shape) != (B,):
+            raise ValueError(f'{what}: new_lens must have shape ({B},) — the number of new tokens of every batch item —, got '
+                             f'{tuple(new_lens.shape)}')
+        tensors['new_lens'] = new_lens
+    for name, t, like, like_name in (('q_out', q_out, q, 'q'), ('k_out', k_out, k_new, 'k_new')):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be None or a dense tensor')
+        if t.dtype not in _LOWP:
+            raise ValueError(f'{what}: {name} must be bfloat16 or float16, got {t.dtype} (accepted: {_ROPE_SIZES_TEXT})')
+        if t.dtype != like.dtype:
+            raise RuntimeError(f'{what}: {like_name} is {like.dtype} but {name} is {t.dtype}: the rotated rows are written in '
+                               f'the source\'s dtype')
+        if tuple(t.shape) != tuple(like.shape):
+            raise ValueError(f'{what}: {name} must have {like_name}\'s shape {tuple(like.shape)}, got {tuple(t.shape)}')
+        _check_source_strides(what, name, t)
+        tensors[name] = t
+    if B * (Hq + 2 * Hkv) * T * (D // 8) >= 2 ** 31:
+        raise ValueError(f'{what}: B·(Hq + 2·Hkv)·T·D/8 = {B * (Hq + 2 * Hkv) * T * (D // 8)} must fit an int32 index')
+    _check_source_strides(what, 'q', q)
+    return R, tensors
+
+
+def _rope_kv_cache_append(what, names, q, k_new, v_new, cos, sin, k, v, block_table, k_lens, interleaved, rotary_dim, new_lens,
+                          q_out, k_out, k_scale, v_scale):
+    '''Both forms of the fused call: the checks, then the one binding call.'''
+    paged = block_table is not None or names[0] == 'k_pages'
+    _check_lowp_operands(what, (('q', q), ('k_new', k_new), ('v_new', v_new)), _ROPE_SIZES_TEXT)
+    if not isinstance(interleaved, bool):
+        raise ValueError(f'{what}: interleaved must be a bool, got {interleaved!r}')
+    scales = (('k_scale', k_scale), ('v_scale', v_scale))
+    R, tensors = None, {}
+    if k_new.dim() == 4 and k_new.shape[3] in _BLOCK_HEAD_SIZES and k_new.shape[2] >= 1 and k_new.shape[1] >= 1:
+        R, tensors = _check_rope_operands(what, q, k_new, cos, sin, rotary_dim, new_lens, q_out, k_out)
+    fp8 = _check_kv_append_operands(what, names, k_new, v_new, k, v, k_lens, scales, block_table)
+    _check_on_device(what, k_new=k_new, q=q, **tensors)
+    if q.numel() == 0:
+        return torch.empty_like(q, memory_format=torch.contiguous_format) if q_out is None else q_out
+    with torch.no_grad():
+        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
+        news = None if new_lens is None else new_lens.detach().to(torch.int32).contiguous()
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device) if q_out is None else q_out
+        ks, vs = (_fp8_scale(k_scale, k_new.device), _fp8_scale(v_scale, k_new.device)) if fp8 else (None, None)
+        head = (q.detach(), k_new.detach(), v_new.detach(), cos.detach(), sin.detach(), k.detach(), v.detach())
+        tail = (lens, news, out.detach(), None if k_out is None else k_out.detach(), R, interleaved, ks, vs)
+        if paged:
+            table = block_table.detach()
+            if table.dtype != torch.int32:
+                table = table.to(torch.int32)
+            custom_mm.rope_kv_append_paged(*head, table, *tail)
+        else:
+            custom_mm.rope_kv_append(*head, *tail)
+    return out
+
+
+def rope_kv_cache_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                         k: torch.Tensor, v: torch.Tensor, k_lens: torch.Tensor, *, interleaved: bool = False, rotary_dim=None,
+                         new_lens=None, q_out=None, k_out=None, k_scale=None, v_scale=None) -> torch.Tensor:
+    '''The rotary embedding (RoPE) of q and of the new keys FUSED INTO kv_cache_append: in ONE launch q [B, Hq, T, D] and
+    k_new [B, Hkv, T, D] are rotated by position, the rotated keys and v_new [B, Hkv, T, D] are written into the cache k, v
+    [B, Hkv, Smax, D] — copied, or quantised into a float8_e4m3fn cache — and the rotated q is returned.  q, k_new, v_new:
+    bfloat16 or float16 of one dtype, D ∈ {32, 64, 96, 128}, T ≥ 1, Hq ≥ 1 with no relation to Hkv (the decode call checks
+    its own).  The cache, k_lens, k_scale and v_scale are kv_cache_append\'s operands with its checks and refusals
+    (rope_kv_cache_append_takes).  NO autograd: the operands are detached.  No read-back, no atomics:
+    `lens += 1; rope_kv_cache_append(…); block_sparse_attention_decode(…)` can be captured in one graph.
+
+    NOTHING IS COPIED.  q, k_new and v_new are read through their own strides — last stride 1, the others multiples of 8
+    elements, a 16-byte aligned data pointer —, so the three slices of one fused projection [B, T, Hq + 2·Hkv, D] seen
+    through .transpose(1, 2) work as they are.
+
+    cos, sin: float32 device tensors [Pmax, R/2], row p for position p, R = rotary_dim (None: D), a multiple of 16 with
+    16 ≤ R ≤ D; last stride 1, one row stride ≥ R/2 that is a multiple of 4, a 16-byte aligned data pointer.  The kernel
+    computes no trigonometry: the tables define the angles (scaled tables included), and a table updated in place is
+    followed by a captured graph.
+
+    The rule.  pos = k_lens[b] − T + t (64 bits; k_lens holds the lengths AFTER the append and is not clamped).  new_lens:
+    None, or an int32 / int64 device tensor [B], clamped to [0, T] by the kernel: item b has new_lens[b] new tokens,
+    standing in the LAST new_lens[b] of the T slots.  Slot t HOLDS A TOKEN iff t ≥ T − new_lens[b] (always, without
+    new_lens) and 0 ≤ pos < Pmax.
+      * No token: the slot\'s rows of q_out, and of k_out if given, are zeros; nothing is stored into the cache.
+      * A token: its q rows and its k row are rotated by table row pos.  q goes to q_out.  k and v are written into the cache
+        iff kv_cache_append\'s condition holds (0 ≤ pos < Smax), and are dropped otherwise — q is still rotated.
+      * Everything the rule does not write keeps its bytes.
+    A decode call on the same T slots gives the right rows for the slots that hold a token.
+
+    q_out: None returns a fresh contiguous [B, Hq, T, D]; a tensor of q\'s shape and dtype under the source\'s stride rules is
+    written and returned; q_out is q rotates in place.  k_out: None — the rotated k goes to the cache only — or a
+    [B, Hkv, T, D] tensor under the same rules (k_out is k_new: in place) that ALSO receives the rotated k in the source
+    dtype, for a prefill step that still needs it.  Any other overlap between operands is the caller\'s business.
+
+    Bits.  Pair i < R/2 is (a, b) = (x[i], x[i + R/2]) — the NeoX halves — or, interleaved=True, (x[2i], x[2i + 1]) — GPT-J.
+    With c = cos[pos, i], s = sin[pos, i] and the elements widened exactly to float32:
+        a\' = fl32(fl32(a·c) − fl32(b·s))        b\' = fl32(fl32(b·c) + fl32(a·s))
+    two products and one sum, each rounded to float32, never contracted into an fma, subnormals kept; then one
+    round-to-nearest-even to the source dtype: operation for operation what torch gives ON THE CPU for
+    (a.float() * c − b.float() * s).to(dtype).  A NaN result is a NaN of unspecified payload.  Elements d ≥ R of q and k, and
+    all of v, are bit copies.  An fp8 cache receives kv_cache_append\'s bytes of the rotated k after its rounding to the
+    source dtype: every cache form is byte for byte what kv_cache_append(k_rot, v_new, …) leaves.'''
+    return _rope_kv_cache_append('rope_kv_cache_append', ('k', 'v'), q, k_new, v_new, cos, sin, k, v, None, k_lens, interleaved,
+                                 rotary_dim, new_lens, q_out, k_out, k_scale, v_scale)
+
+
+def rope_kv_cache_append_paged(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                               k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor, k_lens: torch.Tensor, *,
+                               interleaved: bool = False, rotary_dim=None, new_lens=None, q_out=None, k_out=None, k_scale=None,
+                               v_scale=None) -> torch.Tensor:
+    '''rope_kv_cache_append into a PAGED cache: k_pages, v_pages [P, Hkv, page, D] and block_table [B, W] are the operands of
+    kv_cache_append_paged with its checks (rope_kv_cache_append_paged_takes).  A token\'s rotated k and its v are written to
+    row pos % page of pool page block_table[b, pos // page] iff 0 ≤ pos < W · page and that entry lies in [0, P); otherwise
+    they are dropped — q is still rotated.  Everything else — the tables, new_lens, q_out, k_out, the bits — is
+    rope_kv_cache_append\'s: bit for bit the flat call on the gathered cache.'''
+    return _rope_kv_cache_append('rope_kv_cache_append_paged', ('k_pages', 'v_pages'), q, k_new, v_new, cos, sin, k_pages, v_pages,
+                                 block_table, k_lens, interleaved, rotary_dim, new_lens, q_out, k_out, k_scale, v_scale)
+
+
+# --------------------------------------------------------------------------- #
 # block-sparse (BSR) × dense products on the matrix cores
 # --------------------------------------------------------------------------- #
 
