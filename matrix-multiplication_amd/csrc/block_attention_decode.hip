@@ -42,7 +42,7 @@
 // score, pack_tile, accumulate, group_max / group_sum) are private copies of block_attention.hip's, adapted to one wave.
 #include <type_traits>
 
-#include "lowp_device.h"
+#include "kv_cache_device.h"
 
 namespace {
 
@@ -157,8 +157,6 @@ __device__ __forceinline__ uint4 widen(uint2 x) {
 template <class F> __device__ __forceinline__ F zero_frag();
 template <> __device__ __forceinline__ uint4 zero_frag<uint4>() { return uint4{0u, 0u, 0u, 0u}; }
 template <> __device__ __forceinline__ uint2 zero_frag<uint2>() { return uint2{0u, 0u}; }
-// the scale of k / v head h of the fp8 forms
-__device__ __forceinline__ float head_scale(const float* s, int count, int h) { return s ? s[count == 1 ? 0 : h] : 1.f; }
 
 // How the walk finds the 64 keys of a list entry: a compile-time form of the kernel, as LENS is in block_attention.hip
 constexpr int kContiguous = 0;  // one [Smax][D] run per k / v item behind fixed strides
@@ -590,11 +588,6 @@ __global__ __launch_bounds__(128) void block_attention_decode_combine_kernel(Arg
   }
 }
 
-bool takes_width(int32_t D) { return D == 32 || D == 64 || D == 96 || D == 128; }
-
-// a stride in elements: a multiple of 16 bytes — 8 elements of T, 16 e4m3fn bytes
-bool stride_ok(int64_t s, int64_t unit = 8) { return s >= 0 && s % unit == 0; }
-
 int chunks_of(int32_t Smax, int32_t chunk) {  // from the shape alone; a list has at most Smax / 64 entries
   const long blocks = Smax / kB;
   const long n = (blocks + chunk - 1) / chunk;
@@ -620,13 +613,6 @@ int launch(const Args& a, int items, hipStream_t s) {
 // Every check comes before the first HIP call.  page == 0: the contiguous cache, `outerK` / `outerV` its batch strides and
 // no table; page > 0: a pool of `pages` pages of `page` keys, `outerK` / `outerV` its page strides, Smax = the table's
 // logical pages · page.  FP8: k and v are e4m3fn bytes (their strides multiples of 16) with the two scales of `scales`.
-struct Scales {
-  const float* k = nullptr;
-  int k_count = 1;
-  const float* v = nullptr;
-  int v_count = 1;
-};
-
 template <class T, bool FP8 = false>
 int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T_,
                  int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ, const void* k, int64_t ldk,
@@ -634,28 +620,20 @@ int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t
                  const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale, uint16_t* out, int64_t ldo,
                  int64_t strideO, float* lse, void* workspace, size_t workspace_bytes, hipStream_t s, const int32_t* table = nullptr,
                  int64_t table_ld = 0, int32_t pages = 0, int32_t page = 0, const Scales& scales = Scales()) {
-  constexpr int64_t unit = FP8 ? 16 : 8;  // cache elements in 16 bytes
-  if (FP8 && ((scales.k_count != 1 && scales.k_count != heads) || (scales.v_count != 1 && scales.v_count != heads))) return MI_EINVAL;
-  if (FP8 && ((reinterpret_cast<uintptr_t>(scales.k) & 3u) || (reinterpret_cast<uintptr_t>(scales.v) & 3u))) return MI_EINVAL;
+  if (!cache_form_ok(FP8, scales, heads, Smax, pages, page)) return MI_EINVAL;
   if (group < 1 || group > kMaxGroup || chunk < 1 || !takes_width(D)) return MI_EINVAL;
   const bool paged = page != 0;
-  if (paged && (page < 16 || (page & (page - 1)) != 0 || pages < 0 || Smax % page != 0)) return MI_EINVAL;
   if (nnz < 0 || layouts < 0 || items < 0 || heads < 0 || T_ < 0 || Smax < 0 || Smax % kB != 0) return MI_EINVAL;
   if (nnz > 0x7fffffffLL) return MI_ERANGE;
   if (items > 65535 || T_ > 65535) return MI_EINVAL;  // the grid's y and z: no item loop
   if (items == 0 || T_ == 0) return MI_OK;
   if (layouts == 0 || heads == 0 || items % heads != 0 || lens_count < 1 || items % lens_count != 0) return MI_EINVAL;
-  if (!rowptr || (nnz > 0 && !col) || !k_lens || (reinterpret_cast<uintptr_t>(k_lens) & 3u)) return MI_EINVAL;
-  if (!lse || (reinterpret_cast<uintptr_t>(lse) & 3u)) return MI_EINVAL;
+  if (!rowptr || (nnz > 0 && !col) || !k_lens || !aligned4(k_lens)) return MI_EINVAL;
+  if (!lse || !aligned4(lse)) return MI_EINVAL;
   if (!q || !mi::aligned16(q) || ldq < D || !stride_ok(ldq) || !stride_ok(strideQ)) return MI_EINVAL;
   if (!out || !mi::aligned16(out) || ldo < D || !stride_ok(ldo) || !stride_ok(strideO)) return MI_EINVAL;
-  if (paged && Smax > 0 && (!table || (reinterpret_cast<uintptr_t>(table) & 3u) || table_ld < Smax / page)) return MI_EINVAL;
-  if (nnz > 0 && Smax > 0 && (!paged || pages > 0)) {  // (an empty pool is never read: every entry of the table is invalid)
-    if (!k || !mi::aligned16(k) || ldk < D || !stride_ok(ldk, unit) || !stride_ok(headK, unit) || !stride_ok(outerK, unit))
-      return MI_EINVAL;
-    if (!v || !mi::aligned16(v) || ldv < D || !stride_ok(ldv, unit) || !stride_ok(headV, unit) || !stride_ok(outerV, unit))
-      return MI_EINVAL;
-  }
+  const bool reads = nnz > 0 && Smax > 0 && (!paged || pages > 0);  // (an empty pool is never read: every entry of the table is invalid)
+  if (!cache_operands_ok(FP8, reads, Smax, D, k, ldk, headK, outerK, v, ldv, headV, outerV, table, table_ld, page)) return MI_EINVAL;
   const int chunks = chunks_of(Smax, chunk);
   if (chunks > 1) {
     if (!workspace || !mi::aligned16(workspace)) return MI_EINVAL;

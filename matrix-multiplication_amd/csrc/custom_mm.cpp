@@ -49,9 +49,8 @@ namespace {
 #include "custom_mm_softmax.inc"
 #include "custom_mm_attention.inc"
 #include "custom_mm_block_attention.inc"
+#include "custom_mm_kv_cache.inc"
 #include "custom_mm_block_attention_decode.inc"
-#include "custom_mm_block_attention_decode_paged.inc"
-#include "custom_mm_block_attention_decode_fp8.inc"
 #include "custom_mm_kv_append.inc"
 #include "custom_mm_rope_kv_append.inc"
 #include "custom_mm_bsr.inc"

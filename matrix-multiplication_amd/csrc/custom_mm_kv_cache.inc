@@ -1,0 +1,126 @@
+// custom_mm — what the bindings of the KV-cache family (block_attention_decode*, kv_append*, rope_kv_append*) say about the
+// cache operands, said once (DESIGN.md §3.23)
+// Part of the `custom_mm` extension: included by custom_mm.cpp inside its anonymous namespace, ahead of the three bindings.
+// Not compiled on its own.  The cache is k, v [B, Hkv, Smax, D] or a pool k_pages, v_pages [P, Hkv, page, D] with block_table
+// int32 [B, W] (Smax = W · page), READ AND WRITTEN THROUGH ITS OWN STRIDES (last stride 1, the others multiples of 16 bytes —
+// 8 two-byte elements, 16 float8_e4m3fn bytes —, a 16-byte aligned data pointer — never copied); k_lens int32 [B] or [1] on
+// the device; k_scale, v_scale: None (= 1) or float32 device tensors of 1 or Hkv entries, handed over as pointers and never
+// read back.  Each rule is one function, so that every binding keeps the order in which it refuses; a message that differs
+// between the callers by a word (the tensors' names, "batch" | "page", "keys" | "rows") takes that word as an argument.
+
+// a cache operand's strides as the kernel takes them; the message names the stride that does not fit (`outer`: the first
+// one, the batch stride of a cache or the page stride of a pool; `unit`: the elements of 16 bytes — 8, or 16 of an fp8 cache)
+void check_cache_strides(const char* what, const char* name, const torch::Tensor& t, int64_t D, const char* outer = "batch",
+                         int64_t unit = 8) {
+  TORCH_CHECK(t.stride(3) == 1 || D == 1, what, ": ", name, " must have a last stride of 1, got ", t.stride(3));
+  TORCH_CHECK(t.size(2) <= 1 || (t.stride(2) >= D && t.stride(2) % unit == 0), what, ": ", name,
+              "'s row stride must be a multiple of ", unit, " elements and at least D = ", D, ", got ", t.stride(2));
+  TORCH_CHECK(t.size(1) <= 1 || (t.stride(1) >= 0 && t.stride(1) % unit == 0), what, ": ", name,
+              "'s head stride must be a multiple of ", unit, " elements, got ", t.stride(1));
+  TORCH_CHECK(t.size(0) <= 1 || (t.stride(0) >= 0 && t.stride(0) % unit == 0), what, ": ", name,
+              "'s ", outer, " stride must be a multiple of ", unit, " elements, got ", t.stride(0));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, what, ": ", name, "'s data pointer must be 16-byte aligned");
+}
+
+// a stride the kernel never multiplies by anything but 0 (a dimension of one entry) is handed over as a harmless 0 / D
+int64_t cache_stride(const torch::Tensor& t, int dim, int64_t fallback) { return t.size(dim) > 1 ? t.stride(dim) : fallback; }
+
+// a source operand's strides (k_new, v_new, q of the rope call and its outputs) as the kernel takes them
+void check_source_strides(const char* what, const char* name, const torch::Tensor& t) {
+  static const char* const dims[] = {"batch", "head", "token"};
+  TORCH_CHECK(t.stride(3) == 1 || t.size(3) <= 1, what, ": ", name, " must have a last stride of 1, got ", t.stride(3));
+  for (int d = 2; d >= 0; --d)
+    TORCH_CHECK(t.size(d) <= 1 || (t.stride(d) >= 0 && t.stride(d) % 8 == 0), what, ": ", name, "'s ", dims[d],
+                " stride must be a multiple of 8 elements, got ", t.stride(d));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, what, ": ", name, "'s data pointer must be 16-byte aligned");
+}
+
+// a scale operand as the C ABI takes it: (pointer or null, count)
+std::pair<const float*, int32_t> fp8_scale(const char* what, const char* name, const c10::optional<torch::Tensor>& s, int64_t Hkv,
+                                           const torch::Tensor& q) {
+  if (!s.has_value()) return {nullptr, 1};
+  const torch::Tensor& t = *s;
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.device() == q.device() && t.is_contiguous() && t.dim() <= 1 &&
+                  (t.numel() == 1 || t.numel() == Hkv),
+              what, ": ", name, " must be None or a contiguous float32 tensor on q's device of 1 or Hkv = ", Hkv, " entries");
+  return {t.data_ptr<float>(), (int32_t)t.numel()};
+}
+
+// the page rule; `noun`: what a page holds for the caller — "keys" for the reading calls, "rows" for the writing ones
+void check_page(const char* what, const char* noun, int64_t page) {
+  TORCH_CHECK(page >= 16 && (page & (page - 1)) == 0, what, ": a page must hold a power of two >= 16 ", noun, ", got ", page);
+}
+
+// the block table's shape [B, W]: returns W, the logical pages of an item
+int64_t table_width(const char* what, const torch::Tensor& table, int64_t B) {
+  TORCH_CHECK(table.dim() == 2 && table.size(0) == B, what, ": block_table must be [B, W] = [", B, ", W]");
+  return table.size(1);
+}
+
+// … its dtype and strides: it is handed over as it is
+void check_table(const char* what, const torch::Tensor& table) {
+  const int64_t B = table.size(0), W = table.size(1);
+  check_device_i32(table, "block_table");
+  TORCH_CHECK((W <= 1 || table.stride(1) == 1) && (B <= 1 || table.stride(0) >= W), what,
+              ": block_table must have a last stride of 1 and a row stride of at least W = ", W, ", got strides (", table.stride(0),
+              ", ", table.stride(1), ")");
+}
+
+void check_k_lens(const char* what, const torch::Tensor& k_lens, int64_t B) {
+  TORCH_CHECK(k_lens.is_contiguous() && (k_lens.numel() == B || k_lens.numel() == 1), what,
+              ": k_lens must be a contiguous int32 tensor of B = ", B, " entries or of one, got ", k_lens.numel());
+}
+
+// The cache operands as the C entries take them, gathered after the checks: `table` null — the contiguous cache — or the
+// block table of a pool, for which k, v are k_pages, v_pages and the outer strides the page strides.
+struct CacheOperands {
+  bool paged;
+  int64_t Smax, P, page;  // rows of an item; pool pages and rows of a page (0, 0: contiguous)
+  const int32_t* table;
+  int64_t table_ld;
+  void *k, *v;
+  int64_t ldk, headK, outerK, ldv, headV, outerV;
+};
+
+CacheOperands cache_operands(const torch::Tensor& k, const torch::Tensor& v, const torch::Tensor* table, int64_t D) {
+  CacheOperands c = {table != nullptr, k.size(2), 0, 0, nullptr, 0, k.data_ptr(), v.data_ptr(),
+                     cache_stride(k, 2, D), cache_stride(k, 1, 0), cache_stride(k, 0, 0),
+                     cache_stride(v, 2, D), cache_stride(v, 1, 0), cache_stride(v, 0, 0)};
+  if (table) {
+    const int64_t B = table->size(0), W = table->size(1);
+    c.P = k.size(0), c.page = k.size(2), c.Smax = W * c.page;
+    c.table = table->data_ptr<int32_t>(), c.table_ld = B > 1 ? table->stride(0) : W;
+  }
+  return c;
+}
+
+// the writing calls' cache: of the source's dtype `dt` (a bit copy) or float8_e4m3fn; returns whether it is fp8
+bool written_cache_is_fp8(const char* what, const char* kname, const char* vname, torch::ScalarType dt, const torch::Tensor& k,
+                          const torch::Tensor& v, const c10::optional<torch::Tensor>& k_scale,
+                          const c10::optional<torch::Tensor>& v_scale) {
+  const bool fp8 = k.scalar_type() != dt || v.scalar_type() != dt;
+  TORCH_CHECK(!fp8 || (k.scalar_type() == torch::kFloat8_e4m3fn && v.scalar_type() == torch::kFloat8_e4m3fn), what, ": ", kname,
+              " and ", vname, " must have k_new's dtype ", dt, " or be float8_e4m3fn (the OCP e4m3fn encoding is what is written), got ",
+              k.scalar_type(), " and ", v.scalar_type());
+  TORCH_CHECK(fp8 || (!k_scale.has_value() && !v_scale.has_value()), what, ": k_scale and v_scale go with a float8_e4m3fn cache only");
+  return fp8;
+}
+
+// … its shape against the source's B, Hkv and D
+void check_written_cache_shape(const char* what, const char* kname, const char* vname, const torch::Tensor& k, const torch::Tensor& v,
+                               bool paged, int64_t B, int64_t Hkv, int64_t D) {
+  TORCH_CHECK((paged || k.size(0) == B) && k.size(1) == Hkv && k.size(3) == D && v.sizes() == k.sizes(), what, ": ", kname, " and ",
+              vname, " must be ", paged ? "[P, Hkv, page, D]" : "[B, Hkv, Smax, D]", " with k_new's B = ", B, ", Hkv = ", Hkv,
+              " and D = ", D);
+}
+
+// … and its page and table, in the writing calls' order of refusals (the reading calls make the same checks between others of
+// their own); `dev`: the device of the call's first operand
+void check_written_cache_table(const char* what, const torch::Tensor& k, const torch::Tensor* table, int64_t B,
+                               const torch::Device& dev) {
+  if (!table) return;
+  check_page(what, "rows", k.size(2));
+  table_width(what, *table, B);
+  check_table(what, *table);
+  check_same_device(what, dev, {table});
+}

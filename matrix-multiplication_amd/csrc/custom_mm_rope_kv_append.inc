@@ -1,7 +1,8 @@
 // custom_mm — the fused rotary embedding + KV-cache append: q and the new keys rotated by position, the rotated keys and the
 // values written into the decode calls' cache, the rotated q into q_out, in one launch
-// Part of the `custom_mm` extension: included by custom_mm.cpp inside its anonymous namespace, after custom_mm_kv_append.inc,
-// whose source-stride check it shares with the decode bindings' cache-stride and scale checks.  Not compiled on its own.
+// Part of the `custom_mm` extension: included by custom_mm.cpp inside its anonymous namespace, after custom_mm_kv_cache.inc,
+// which owns what is said about the cache operands, the sources' strides and the scales (DESIGN.md §3.23).  Not compiled on
+// its own.
 // Contract: include/mi_spmm.h, "The fused rotary embedding + KV-cache append" (DESIGN.md §3.22): q [B, Hq, T, D], k_new and
 // v_new [B, Hkv, T, D] bfloat16 or float16 READ THROUGH THEIR OWN STRIDES; cos, sin float32 [Pmax, R/2] (last stride 1, one
 // row stride ≥ R/2 that is a multiple of 4, 16-byte aligned); the cache, block_table, k_lens and the scales as kv_append takes
@@ -18,11 +19,7 @@ torch::Tensor rope_kv_append_impl(const char* what, const char* kname, const cha
   TORCH_CHECK(is_lowp(dt), what, ": q must be bfloat16 or float16, got ", dt);
   TORCH_CHECK(!k_out.has_value() || k_out->scalar_type() == dt, what, ": k_out must have q's dtype ", dt, ", got ",
               k_out.has_value() ? k_out->scalar_type() : dt);
-  const bool fp8 = k.scalar_type() != dt || v.scalar_type() != dt;
-  TORCH_CHECK(!fp8 || (k.scalar_type() == torch::kFloat8_e4m3fn && v.scalar_type() == torch::kFloat8_e4m3fn), what, ": ", kname,
-              " and ", vname, " must have k_new's dtype ", dt, " or be float8_e4m3fn (the OCP e4m3fn encoding is what is written), got ",
-              k.scalar_type(), " and ", v.scalar_type());
-  TORCH_CHECK(fp8 || (!k_scale.has_value() && !v_scale.has_value()), what, ": k_scale and v_scale go with a float8_e4m3fn cache only");
+  const bool fp8 = written_cache_is_fp8(what, kname, vname, dt, k, v, k_scale, v_scale);
   TORCH_CHECK(q.dim() == 4 && k_new.dim() == 4 && v_new.dim() == 4 && k.dim() == 4 && v.dim() == 4, what,
               ": q must be [B, Hq, T, D], k_new and v_new [B, Hkv, T, D], ", kname, " and ", vname,
               table ? " [P, Hkv, page, D]" : " [B, Hkv, Smax, D]");
@@ -32,9 +29,7 @@ torch::Tensor rope_kv_append_impl(const char* what, const char* kname, const cha
               ", T = ", T, " and D = ", D, " and Hq >= 1");
   TORCH_CHECK(q_out.sizes() == q.sizes(), what, ": q_out must have q's shape");
   TORCH_CHECK(!k_out.has_value() || k_out->sizes() == k_new.sizes(), what, ": k_out must have k_new's shape");
-  TORCH_CHECK((table || k.size(0) == B) && k.size(1) == Hkv && k.size(3) == D && v.sizes() == k.sizes(), what, ": ", kname, " and ",
-              vname, " must be ", table ? "[P, Hkv, page, D]" : "[B, Hkv, Smax, D]", " with k_new's B = ", B, ", Hkv = ", Hkv,
-              " and D = ", D);
+  check_written_cache_shape(what, kname, vname, k, v, table != nullptr, B, Hkv, D);
   TORCH_CHECK(R >= 16 && R <= D && R % 16 == 0, what, ": rotary_dim must be a multiple of 16 in [16, D = ", D, "], got ", R);
   check_device_f32(cos, "cos");
   check_device_f32(sin, "sin");
@@ -47,22 +42,10 @@ torch::Tensor rope_kv_append_impl(const char* what, const char* kname, const cha
               cos.stride(0), ", ", cos.stride(1), ") and (", sin.stride(0), ", ", sin.stride(1), ")");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(cos.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(sin.data_ptr()) % 16 == 0, what,
               ": the data pointers of cos and sin must be 16-byte aligned");
-  int64_t Smax = k.size(2), P = 0, page = 0, W = 0;
-  if (table) {
-    P = k.size(0), page = k.size(2);
-    TORCH_CHECK(page >= 16 && (page & (page - 1)) == 0, what, ": a page must hold a power of two >= 16 rows, got ", page);
-    TORCH_CHECK(table->dim() == 2 && table->size(0) == B, what, ": block_table must be [B, W] = [", B, ", W]");
-    W = table->size(1), Smax = W * page;
-    check_device_i32(*table, "block_table");
-    TORCH_CHECK((W <= 1 || table->stride(1) == 1) && (B <= 1 || table->stride(0) >= W), what,
-                ": block_table must have a last stride of 1 and a row stride of at least W = ", W, ", got strides (",
-                table->stride(0), ", ", table->stride(1), ")");
-    check_same_device(what, q.device(), {table});
-  }
+  check_written_cache_table(what, k, table, B, q.device());
   check_same_device(what, q.device(), {&k_new, &v_new, &cos, &sin, &k, &v, &k_lens, &q_out});
   check_device_i32(k_lens, "k_lens");
-  TORCH_CHECK(k_lens.is_contiguous() && (k_lens.numel() == B || k_lens.numel() == 1), what,
-              ": k_lens must be a contiguous int32 tensor of B = ", B, " entries or of one, got ", k_lens.numel());
+  check_k_lens(what, k_lens, B);
   if (new_lens.has_value()) {
     check_same_device(what, q.device(), {&*new_lens});
     check_device_i32(*new_lens, "new_lens");
@@ -80,7 +63,8 @@ torch::Tensor rope_kv_append_impl(const char* what, const char* kname, const cha
   check_cache_strides(what, kname, k, D, outer, fp8 ? 16 : 8);
   check_cache_strides(what, vname, v, D, outer, fp8 ? 16 : 8);
   const auto ks = fp8_scale(what, "k_scale", k_scale, Hkv, q), vs = fp8_scale(what, "v_scale", v_scale, Hkv, q);
-  check_sizes(what, {B * Hkv, B * Hq, T, Smax, D, P, Pmax});
+  const CacheOperands c = cache_operands(k, v, table, D);
+  check_sizes(what, {B * Hkv, B * Hq, T, c.Smax, D, c.P, Pmax});
   if (q.numel() == 0) return q_out;
   c10::hip::HIPGuard guard(q.device().index());
   const int32_t items = (int32_t)(B * Hkv), lens_count = (int32_t)k_lens.numel();
@@ -89,13 +73,11 @@ torch::Tensor rope_kv_append_impl(const char* what, const char* kname, const cha
   auto st3 = [D](const torch::Tensor& t) {
     return std::array<int64_t, 3>{cache_stride(t, 2, D), cache_stride(t, 1, 0), cache_stride(t, 0, 0)};
   };
-  const auto sq = st3(q), sqo = st3(q_out), skn = st3(k_new), svn = st3(v_new), sk = st3(k), sv = st3(v);
+  const auto sq = st3(q), sqo = st3(q_out), skn = st3(k_new), svn = st3(v_new);
   const auto sko = k_out.has_value() ? st3(*k_out) : std::array<int64_t, 3>{D, 0, 0};
   uint16_t* ko = k_out.has_value() ? dst16(*k_out) : nullptr;
   const int32_t* lens = k_lens.data_ptr<int32_t>();
   const int32_t* nl = new_lens.has_value() ? new_lens->data_ptr<int32_t>() : nullptr;
-  const int32_t* tab = table ? table->data_ptr<int32_t>() : nullptr;
-  const int64_t table_ld = table ? (B > 1 ? table->stride(0) : W) : 0;
   const float *cp = Pmax > 0 ? cos.data_ptr<float>() : nullptr, *sp = Pmax > 0 ? sin.data_ptr<float>() : nullptr;
   const bool bf = dt == torch::kBFloat16;
   mi_stream_t stream = stream_of(q);
@@ -104,19 +86,19 @@ torch::Tensor rope_kv_append_impl(const char* what, const char* kname, const cha
 #define MI_ROPE_CALL_OPERANDS(CT)                                                                                                   \
   (int32_t) Hq, src(q), sq[0], sq[1], sq[2], dst16(q_out), sqo[0], sqo[1], sqo[2], src(k_new), skn[0], skn[1], skn[2], src(v_new),  \
       svn[0], svn[1], svn[2], ko, sko[0], sko[1], sko[2], cp, sp, (int32_t)Pmax, ld, (int32_t)R, (int32_t)interleaved,              \
-      static_cast<CT*>(k.data_ptr()), sk[0], sk[1], sk[2], static_cast<CT*>(v.data_ptr()), sv[0], sv[1], sv[2], lens, lens_count, nl
+      static_cast<CT*>(c.k), c.ldk, c.headK, c.outerK, static_cast<CT*>(c.v), c.ldv, c.headV, c.outerV, lens, lens_count, nl
   if (!fp8) {
     st = table ? (bf ? mi_rope_kv_append_paged_bf16 : mi_rope_kv_append_paged_f16)(
-                     items, (int32_t)Hkv, (int32_t)T, (int32_t)Smax, tab, table_ld, (int32_t)P, (int32_t)page, (int32_t)D,
+                     items, (int32_t)Hkv, (int32_t)T, (int32_t)c.Smax, c.table, c.table_ld, (int32_t)c.P, (int32_t)c.page, (int32_t)D,
                      MI_ROPE_CALL_OPERANDS(uint16_t), stream)
-               : (bf ? mi_rope_kv_append_bf16 : mi_rope_kv_append_f16)(items, (int32_t)Hkv, (int32_t)T, (int32_t)Smax, (int32_t)D,
+               : (bf ? mi_rope_kv_append_bf16 : mi_rope_kv_append_f16)(items, (int32_t)Hkv, (int32_t)T, (int32_t)c.Smax, (int32_t)D,
                                                                        MI_ROPE_CALL_OPERANDS(uint16_t), stream);
   } else {
     st = table ? (bf ? mi_rope_kv_append_paged_fp8_bf16 : mi_rope_kv_append_paged_fp8_f16)(
-                     items, (int32_t)Hkv, (int32_t)T, (int32_t)Smax, tab, table_ld, (int32_t)P, (int32_t)page, (int32_t)D,
+                     items, (int32_t)Hkv, (int32_t)T, (int32_t)c.Smax, c.table, c.table_ld, (int32_t)c.P, (int32_t)c.page, (int32_t)D,
                      MI_ROPE_CALL_OPERANDS(uint8_t), ks.first, ks.second, vs.first, vs.second, stream)
                : (bf ? mi_rope_kv_append_fp8_bf16 : mi_rope_kv_append_fp8_f16)(
-                     items, (int32_t)Hkv, (int32_t)T, (int32_t)Smax, (int32_t)D, MI_ROPE_CALL_OPERANDS(uint8_t), ks.first, ks.second,
+                     items, (int32_t)Hkv, (int32_t)T, (int32_t)c.Smax, (int32_t)D, MI_ROPE_CALL_OPERANDS(uint8_t), ks.first, ks.second,
                      vs.first, vs.second, stream);
   }
 #undef MI_ROPE_CALL_OPERANDS

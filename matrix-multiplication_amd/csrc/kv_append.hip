@@ -9,9 +9,9 @@
 //    length beyond Smax drops what does not fit and moves nothing.
 //  * The 2-byte forms copy bits (NaN payloads, −0).  The fp8 forms store, per element, the byte of torch's CPU expression
 //    (float32(x) / scale[h]).clamp(−448, 448).to(float8_e4m3fn): the IEEE float32 quotient (taken through a double
-//    reciprocal: `quotient` below), the clamp, ONE round-to-nearest-even into e4m3fn (v_cvt_pk_fp8_f32, the OCP encoding on
-//    gfx950).  v_med3_f32 — what the clamp compiles to — turns a NaN into ±448, so a NaN quotient is given its own path: its
-//    byte is ORed with 0x7F, a NaN code.
+//    reciprocal: `quotient` in kv_cache_device.h, which owns this rule — DESIGN.md §3.23), the clamp, ONE
+//    round-to-nearest-even into e4m3fn (v_cvt_pk_fp8_f32, the OCP encoding on gfx950).  v_med3_f32 — what the clamp compiles
+//    to — turns a NaN into ±448, so a NaN quotient is given its own path: its byte is ORed with 0x7F, a NaN code.
 //  * Everything else keeps its bytes: other rows, the gap between the rows of a padded cache, unreferenced pages.
 //
 // Kernel: one thread moves 8 consecutive elements of one k row and the same 8 of the matching v row — two 16-byte global
@@ -21,7 +21,7 @@
 // ⌈items · T · D/8 / 256⌉ workgroups of 256 threads — or of 64 while that would be fewer workgroups than the chip has CUs, so
 // that a decode step (T = 1) still spreads.  No LDS, no barrier, no atomics, plain vector stores: graph-capturable, and which
 // write lands when two (item, token) pairs are mapped to one pool row is unspecified.
-#include "lowp_device.h"
+#include "kv_cache_device.h"
 
 namespace {
 
@@ -49,46 +49,16 @@ struct Args {
   int k_scale_count, v_scale_count;
 };
 
-__device__ __forceinline__ float head_scale(const float* s, int count, int h) { return s ? s[count == 1 ? 0 : h] : 1.f; }
-
-// The IEEE float32 quotient x / s from r = fl64(1 / s), taken once per thread: float(double(x) · r).  It IS the correctly
-// rounded quotient: the double product is within 2⁻⁵² (relative) of x / s, while a quotient of two 24-bit numbers that is not
-// itself a float lies at least 2⁻⁴⁹ (relative) from every midpoint of two floats (x − s · m is a non-zero multiple of the last
-// place of a 24 × 25-bit product), so the one rounding to float falls where the division's would.  ±0, ±inf and NaN in x or s
-// come out as the division gives them (0 · inf = NaN = 0 / 0); a quotient below 2⁻¹²⁶ may differ in its last subnormal bits,
-// which is far below 2⁻¹⁰, where every value is the byte ±0.  Three instructions per element where the division takes eleven.
-__device__ __forceinline__ float quotient(float x, double r) { return (float)((double)x * r); }
-
-// two floats as two e4m3fn bytes in the low half of the result: quotient, clamp, one rounding; a NaN quotient → 0x7F | sign
-__device__ __forceinline__ unsigned fp8x2(float a, float b, double r) {
-  const float qa = quotient(a, r), qb = quotient(b, r);
-  const float ca = fminf(fmaxf(qa, -448.f), 448.f), cb = fminf(fmaxf(qb, -448.f), 448.f);
-  const unsigned w = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(ca, cb, 0, false) & 0xffffu;
-  return w | (qa != qa ? 0x7fu : 0u) | (qb != qb ? 0x7f00u : 0u);
-}
-
-// the 8 elements of one 16-byte load as 8 bytes
-template <class T>
-__device__ __forceinline__ uint2 quantise(uint4 x, double s) {
-  uint2 r;
-  r.x = fp8x2(T::lo(x.x), T::hi(x.x), s) | (fp8x2(T::lo(x.y), T::hi(x.y), s) << 16);
-  r.y = fp8x2(T::lo(x.z), T::hi(x.z), s) | (fp8x2(T::lo(x.w), T::hi(x.w), s) << 16);
-  return r;
-}
-
+// what store_cache (kv_cache_device.h) takes for a form: the source's type, which only the fp8 form looks at
 template <class TC>
 struct Form {
+  typedef void type;
   static constexpr bool fp8 = false;
-  static __device__ __forceinline__ void store(void* base, long off, uint4 x, double) {
-    *reinterpret_cast<uint4*>(static_cast<uint16_t*>(base) + off) = x;
-  }
 };
 template <class T>
 struct Form<Fp8<T>> {
+  typedef T type;
   static constexpr bool fp8 = true;
-  static __device__ __forceinline__ void store(void* base, long off, uint4 x, double s) {
-    *reinterpret_cast<uint2*>(static_cast<uint8_t*>(base) + off) = quantise<T>(x, s);
-  }
 };
 
 template <class TC, int D, bool PAGED>
@@ -120,16 +90,9 @@ __global__ __launch_bounds__(256) void kv_append_kernel(Args a) {
     ks = 1.0 / (double)head_scale(a.k_scale, a.k_scale_count, h);
     vs = 1.0 / (double)head_scale(a.v_scale, a.v_scale_count, h);
   }
-  Form<TC>::store(a.k, ko, kx, ks);
-  Form<TC>::store(a.v, vo, vx, vs);
+  store_cache<typename Form<TC>::type, Form<TC>::fp8>(a.k, ko, kx, ks);
+  store_cache<typename Form<TC>::type, Form<TC>::fp8>(a.v, vo, vx, vs);
 }
-
-bool takes_width(int32_t D) { return D == 32 || D == 64 || D == 96 || D == 128; }
-
-// a stride in elements: a multiple of 16 bytes — 8 two-byte elements, 16 e4m3fn bytes
-bool stride_ok(int64_t s, int64_t unit = 8) { return s >= 0 && s % unit == 0; }
-
-constexpr long kSpread = 256;  // fewer workgroups of 256 threads than this: workgroups of 64 (the CUs of the chip)
 
 template <class TC, int D>
 int launch(const Args& a, hipStream_t s) {
@@ -142,13 +105,6 @@ int launch(const Args& a, hipStream_t s) {
   return mi::check_launch();
 }
 
-struct Scales {
-  const float* k = nullptr;
-  int k_count = 1;
-  const float* v = nullptr;
-  int v_count = 1;
-};
-
 // Every check comes before the first HIP call.  page == 0: the contiguous cache, `outerK` / `outerV` its batch strides and no
 // table; page > 0: a pool of `pages` pages of `page` rows, `outerK` / `outerV` its page strides, Smax = the table's logical
 // pages · page.
@@ -159,27 +115,17 @@ int append_entry(int32_t items, int32_t heads, int32_t T_, int32_t Smax, int32_t
                  const int32_t* k_lens, int32_t lens_count, hipStream_t s, const int32_t* table = nullptr, int64_t table_ld = 0,
                  int32_t pages = 0, int32_t page = 0, const Scales& scales = Scales()) {
   constexpr bool FP8 = Form<TC>::fp8;
-  constexpr int64_t unit = FP8 ? 16 : 8;  // cache elements in 16 bytes
-  if (FP8 && ((scales.k_count != 1 && scales.k_count != heads) || (scales.v_count != 1 && scales.v_count != heads))) return MI_EINVAL;
-  if (FP8 && ((reinterpret_cast<uintptr_t>(scales.k) & 3u) || (reinterpret_cast<uintptr_t>(scales.v) & 3u))) return MI_EINVAL;
-  if (!takes_width(D)) return MI_EINVAL;
+  if (!cache_form_ok(FP8, scales, heads, Smax, pages, page) || !takes_width(D)) return MI_EINVAL;
   const bool paged = page != 0;
-  if (paged && (page < 16 || (page & (page - 1)) != 0 || pages < 0 || Smax % page != 0)) return MI_EINVAL;
   if (items < 0 || heads < 0 || T_ < 0 || Smax < 0) return MI_EINVAL;
   if (items > 65535) return MI_EINVAL;  // the decode calls' limit: their grid's y
   if (items == 0 || T_ == 0) return MI_OK;
   if (heads == 0 || items % heads != 0 || lens_count < 1 || items % lens_count != 0) return MI_EINVAL;
-  if (!k_lens || (reinterpret_cast<uintptr_t>(k_lens) & 3u)) return MI_EINVAL;
+  if (!k_lens || !aligned4(k_lens)) return MI_EINVAL;
   if (!k_new || !mi::aligned16(k_new) || !stride_ok(ldkn) || !stride_ok(headKn) || !stride_ok(batchKn)) return MI_EINVAL;
   if (!v_new || !mi::aligned16(v_new) || !stride_ok(ldvn) || !stride_ok(headVn) || !stride_ok(batchVn)) return MI_EINVAL;
-  if (paged && Smax > 0 && (!table || (reinterpret_cast<uintptr_t>(table) & 3u) || table_ld < Smax / page)) return MI_EINVAL;
   const bool written = Smax > 0 && (!paged || pages > 0);  // (an empty cache or pool: every token is dropped, nothing is read)
-  if (written) {
-    if (!k || !mi::aligned16(k) || ldk < D || !stride_ok(ldk, unit) || !stride_ok(headK, unit) || !stride_ok(outerK, unit))
-      return MI_EINVAL;
-    if (!v || !mi::aligned16(v) || ldv < D || !stride_ok(ldv, unit) || !stride_ok(headV, unit) || !stride_ok(outerV, unit))
-      return MI_EINVAL;
-  }
+  if (!cache_operands_ok(FP8, written, Smax, D, k, ldk, headK, outerK, v, ldv, headV, outerV, table, table_ld, page)) return MI_EINVAL;
   const long n = (long)items * T_ * (D / 8);
   if (n > 0x7fffffffL) return MI_ERANGE;
   if (!written) return MI_OK;

@@ -22,7 +22,9 @@
 // NeoX — the thread of the group at d < R/2 also takes the partner group at d + R/2 (two 16-byte loads of each of cos and
 // sin), the thread of the partner group has nothing to do; interleaved — the four pairs of its own group (one 16-byte load of
 // each table).  pos, the slot test, the table entry and the scales are taken once per thread.
-#include "lowp_device.h"
+// (in front of the pragma: the header's fp8 pieces hold a product, a clamp and a conversion, no multiply-add pair that
+// contraction could fuse, so their bits do not depend on it; the pragma covers `rotate` below, which does)
+#include "kv_cache_device.h"
 
 #pragma clang fp contract(off)
 
@@ -57,37 +59,6 @@ struct Args {
   const float *k_scale, *v_scale;  // the fp8 forms: null is 1, a count of 1 one scale for all heads, else one per k / v head
   int k_scale_count, v_scale_count;
 };
-
-// ---- private copies of kv_append.hip's device pieces: the bytes of an fp8 cache ----------------------------
-__device__ __forceinline__ float head_scale(const float* s, int count, int h) { return s ? s[count == 1 ? 0 : h] : 1.f; }
-
-// the IEEE float32 quotient x / s from r = fl64(1 / s): float(double(x) · r) — kv_append.hip shows why it is the division's
-__device__ __forceinline__ float quotient(float x, double r) { return (float)((double)x * r); }
-
-// two floats as two e4m3fn bytes in the low half of the result: quotient, clamp, one rounding; a NaN quotient → 0x7F | sign
-__device__ __forceinline__ unsigned fp8x2(float a, float b, double r) {
-  const float qa = quotient(a, r), qb = quotient(b, r);
-  const float ca = fminf(fmaxf(qa, -448.f), 448.f), cb = fminf(fmaxf(qb, -448.f), 448.f);
-  const unsigned w = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(ca, cb, 0, false) & 0xffffu;
-  return w | (qa != qa ? 0x7fu : 0u) | (qb != qb ? 0x7f00u : 0u);
-}
-
-// the 8 elements of one 16-byte load as 8 bytes
-template <class T>
-__device__ __forceinline__ uint2 quantise(uint4 x, double s) {
-  uint2 r;
-  r.x = fp8x2(T::lo(x.x), T::hi(x.x), s) | (fp8x2(T::lo(x.y), T::hi(x.y), s) << 16);
-  r.y = fp8x2(T::lo(x.z), T::hi(x.z), s) | (fp8x2(T::lo(x.w), T::hi(x.w), s) << 16);
-  return r;
-}
-
-template <class T, bool FP8>
-__device__ __forceinline__ void store_cache(void* base, long off, uint4 x, double s) {
-  if constexpr (FP8)
-    *reinterpret_cast<uint2*>(static_cast<uint8_t*>(base) + off) = quantise<T>(x, s);
-  else
-    *reinterpret_cast<uint4*>(static_cast<uint16_t*>(base) + off) = x;
-}
 
 // ---- the rotation -------------------------------------------------------------------------------------------------------------
 // one pair: two products and one sum each, every one rounded to float32.  Plain operators under the pragma above, NOT
@@ -212,18 +183,9 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(Args a) {
   if (two) store_cache<T, FP8>(base, co + half, y, r);
 }
 
-bool takes_width(int32_t D) { return D == 32 || D == 64 || D == 96 || D == 128; }
-
-// a stride in elements: a multiple of 16 bytes — 8 two-byte elements, 16 e4m3fn bytes
-bool stride_ok(int64_t s, int64_t unit = 8) { return s >= 0 && s % unit == 0; }
-
 bool operand_ok(const void* p, int64_t ld, int64_t head, int64_t batch) {
   return p && mi::aligned16(p) && stride_ok(ld) && stride_ok(head) && stride_ok(batch);
 }
-
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
-constexpr long kSpread = 256;  // fewer workgroups of 256 threads than this: workgroups of 64 (the CUs of the chip)
 
 template <class T, bool FP8>
 int launch(const Args& a, bool inter, hipStream_t s) {
@@ -243,13 +205,6 @@ int launch(const Args& a, bool inter, hipStream_t s) {
   return mi::check_launch();
 }
 
-struct Scales {
-  const float* k = nullptr;
-  int k_count = 1;
-  const float* v = nullptr;
-  int v_count = 1;
-};
-
 struct Rope {  // what the entries take beyond the append's arguments
   int32_t q_heads;
   Src q;
@@ -267,14 +222,10 @@ int rope_entry(int32_t items, int32_t heads, int32_t T_, int32_t Smax, int32_t D
                int64_t ldk, int64_t headK, int64_t outerK, void* v, int64_t ldv, int64_t headV, int64_t outerV, const int32_t* k_lens,
                int32_t lens_count, hipStream_t s, const int32_t* table = nullptr, int64_t table_ld = 0, int32_t pages = 0,
                int32_t page = 0, const Scales& scales = Scales()) {
-  constexpr int64_t unit = FP8 ? 16 : 8;  // cache elements in 16 bytes
-  if (FP8 && ((scales.k_count != 1 && scales.k_count != heads) || (scales.v_count != 1 && scales.v_count != heads))) return MI_EINVAL;
-  if (FP8 && (!aligned4(scales.k) || !aligned4(scales.v))) return MI_EINVAL;
-  if (!takes_width(D)) return MI_EINVAL;
+  if (!cache_form_ok(FP8, scales, heads, Smax, pages, page) || !takes_width(D)) return MI_EINVAL;
   const int32_t R = ro.rotary_dim;
   if (R < 16 || R > D || R % 16 != 0) return MI_EINVAL;
   const bool paged = page != 0;
-  if (paged && (page < 16 || (page & (page - 1)) != 0 || pages < 0 || Smax % page != 0)) return MI_EINVAL;
   if (items < 0 || heads < 0 || T_ < 0 || Smax < 0 || ro.q_heads < 0 || ro.table_rows < 0) return MI_EINVAL;
   if (items > 65535) return MI_EINVAL;  // the decode calls' limit: their grid's y
   if (items == 0 || T_ == 0) return MI_OK;
@@ -288,14 +239,8 @@ int rope_entry(int32_t items, int32_t heads, int32_t T_, int32_t Smax, int32_t D
   if (ro.k_out.p && !operand_ok(ro.k_out.p, ro.k_out.ld, ro.k_out.head, ro.k_out.batch)) return MI_EINVAL;
   if (ro.ld < R / 2 || ro.ld % 4 != 0) return MI_EINVAL;
   if (ro.table_rows > 0 && (!ro.cos || !ro.sin || !mi::aligned16(ro.cos) || !mi::aligned16(ro.sin))) return MI_EINVAL;
-  if (paged && Smax > 0 && (!table || !aligned4(table) || table_ld < Smax / page)) return MI_EINVAL;
   const bool written = Smax > 0 && (!paged || pages > 0);  // (an empty cache or pool: every k / v row is dropped; q is still rotated)
-  if (written) {
-    if (!k || !mi::aligned16(k) || ldk < D || !stride_ok(ldk, unit) || !stride_ok(headK, unit) || !stride_ok(outerK, unit))
-      return MI_EINVAL;
-    if (!v || !mi::aligned16(v) || ldv < D || !stride_ok(ldv, unit) || !stride_ok(headV, unit) || !stride_ok(outerV, unit))
-      return MI_EINVAL;
-  }
+  if (!cache_operands_ok(FP8, written, Smax, D, k, ldk, headK, outerK, v, ldv, headV, outerV, table, table_ld, page)) return MI_EINVAL;
   const long n = (long)B * ((long)ro.q_heads + 2L * heads) * T_ * (D / 8);
   if (n > 0x7fffffffL) return MI_ERANGE;
   Args a = {};

@@ -1856,8 +1856,9 @@ def _check_decode_group(what, Hq, Hkv):
     return group
 
 
-def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, k_lens, block):
-    '''The refusals of the decode calls that follow from (B, Hkv, T, Smax) alone, however the cache is stored.'''
+def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, entries, k_lens, block):
+    '''The refusals of the decode calls that follow from (B, Hkv, T, Smax) alone, however the cache is stored.  `entries`: the
+    number of the layout's stored values.'''
     if T < 1:
         raise ValueError(f'{what}: q must hold T >= 1 new tokens, got T = {T}')
     if Smax % block != 0:
@@ -1867,10 +1868,15 @@ def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, k_lens, block):
         raise ValueError(f'{what}: the layout must have shape [*l_lead, Smax/block, Smax/block] = [*l_lead, {Smax // block}, '
                          f'{Smax // block}] with l_lead empty, ({Hkv},) or ({B}, {Hkv}) — indexed by the k / v item —, got '
                          f'{tuple(layout.shape)}')
-    if torch.Tensor.values(layout).numel() * (block // _BLOCK_TILE) ** 2 >= 2 ** 31:
+    if entries * (block // _BLOCK_TILE) ** 2 >= 2 ** 31:
         raise ValueError(f'{what}: the layout in 64-blocks does not fit int32 indices')
     if B * Hkv > _DECODE_MAX_GRID or T > _DECODE_MAX_GRID:
         raise ValueError(f'{what}: B·Hkv = {B * Hkv} and T = {T} must each be at most {_DECODE_MAX_GRID} (they are grid dimensions)')
+    _check_k_lens(what, k_lens, B)
+
+
+def _check_k_lens(what, k_lens, B):
+    '''k_lens as the decode and the append calls take it: an int32 / int64 tensor [B], or 0-d for one length.'''
     if not isinstance(k_lens, torch.Tensor) or k_lens.layout != torch.strided:
         raise ValueError(f'{what}: k_lens is required and must be a dense tensor')
     if k_lens.dtype not in (torch.int32, torch.int64):
@@ -1879,29 +1885,118 @@ def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, k_lens, block):
         raise ValueError(f'{what}: k_lens must have shape ({B},) — one length per batch item — or be 0-d, got {tuple(k_lens.shape)}')
 
 
-def _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block, chunk, fp8=False, scales=()):
-    '''Every refusal of block_sparse_attention_decode, before the first device call, split as
-    _check_block_attention_operands splits them: ValueError for what an operand is, RuntimeError for operands that do not go
-    together (mixed dtypes, host tensors / devices).  Returns the group: query heads per k / v head.  fp8, scales: the
-    fp8 call's cache type and its (name, scale) pairs (_check_fp8_scales).'''
-    _check_decode_call(what, ('k', 'v'), q, k, v, layout, block, chunk, fp8)
+def _check_block_table(what, block_table, B):
+    '''The block table of a paged cache as the decode and the append calls take it: an int32 / int64 tensor [B, W] with a last
+    stride of 1 and any row stride ≥ W.  Returns W, the logical pages of an item.'''
+    if not isinstance(block_table, torch.Tensor) or block_table.layout != torch.strided:
+        raise ValueError(f'{what}: block_table is required and must be a dense tensor')
+    if block_table.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'{what}: block_table must be an int32 or int64 tensor, got {block_table.dtype}')
+    if block_table.dim() != 2 or block_table.shape[0] != B:
+        raise ValueError(f'{what}: block_table must have shape ({B}, W) — a row of logical pages per batch item —, got '
+                         f'{tuple(block_table.shape)}')
+    W = block_table.shape[1]
+    if W > 1 and block_table.stride(1) != 1:
+        raise ValueError(f'{what}: block_table must have a last stride of 1, got {block_table.stride(1)}')
+    if B > 1 and block_table.stride(0) < W:
+        raise ValueError(f'{what}: block_table\'s row stride must be at least W = {W}, got {block_table.stride(0)}')
+    return W
+
+
+def _lens_i32(k_lens):
+    '''k_lens as the bindings take it: narrowed to int32 on the device, one contiguous dimension.'''
+    return k_lens.detach().to(torch.int32).reshape(-1).contiguous()
+
+
+def _table_i32(block_table):
+    '''A block table as the bindings take it: an int32 table as it is, an int64 table narrowed on the device.'''
+    table = block_table.detach()
+    return table if table.dtype == torch.int32 else table.to(torch.int32)
+
+
+_DECODE_MIN_PAGE = 16    # keys of the smallest page: a 16-row MFMA fragment of a k tile never straddles two pages
+_DECODE_PAGED_SIZES_TEXT = _DECODE_SIZES_TEXT + ', pages of a power of two >= 16 keys'
+
+
+def _page_ok(page) -> bool:
+    return isinstance(page, int) and not isinstance(page, bool) and page >= _DECODE_MIN_PAGE and page & (page - 1) == 0
+
+
+def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8=False, scales=(),
+                                           block_table=None):
+    '''Every refusal of the four decode calls, before the first device call, split as _check_block_attention_operands splits
+    them: ValueError for what an operand is, RuntimeError for operands that do not go together (mixed dtypes, host tensors /
+    devices).  `names`: the cache operands' names — ('k_pages', 'v_pages') is the paged form, whose k and v are the pool
+    [P, Hkv, page, D] and whose Smax is W · page of block_table [B, W].  fp8, scales: the fp8 calls' cache type and their
+    (name, scale) pairs (_check_fp8_scales).'''
+    kn, vn = names
+    paged = kn == 'k_pages'
+    sizes_text = _DECODE_PAGED_SIZES_TEXT if paged else _DECODE_SIZES_TEXT
+    _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8)
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError(f'{what}: q must be [B, Hq, T, D] and k, v [B, Hkv, Smax, D], got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
+        raise ValueError(f'{what}: q must be [B, Hq, T, D] and {kn}, {vn} {"[P, Hkv, page, D]" if paged else "[B, Hkv, Smax, D]"}, '
+                         f'got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
     B, Hq, T, D = q.shape
     if D not in _BLOCK_HEAD_SIZES:
-        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_DECODE_SIZES_TEXT})')
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {sizes_text})')
     Hkv, Smax = k.shape[1], k.shape[2]
-    if k.shape[0] != B or k.shape[3] != D or Hkv < 1 or Hq % Hkv != 0:
-        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs k {(B, "Hkv", "Smax", D)} with Hkv a divisor of {Hq}, '
+    if (not paged and k.shape[0] != B) or k.shape[3] != D or Hkv < 1 or Hq % Hkv != 0:
+        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs {kn} '
+                         f'{("P", "Hkv", "page", D) if paged else (B, "Hkv", "Smax", D)} with Hkv a divisor of {Hq}, '
                          f'got {tuple(k.shape)}')
-    group = _check_decode_group(what, Hq, Hkv)
+    _check_decode_group(what, Hq, Hkv)
     if tuple(v.shape) != tuple(k.shape):
-        raise ValueError(f'{what}: v must be a dense tensor with k\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
-    _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, k_lens, block)
-    _check_cache_strides(what, 'k', k, D, unit=16 if fp8 else 8)
-    _check_cache_strides(what, 'v', v, D, unit=16 if fp8 else 8)
-    _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k=k, v=v, k_lens=k_lens, **_check_fp8_scales(what, scales, Hkv, q))
-    return group
+        owner = "k_pages'" if paged else "k's"
+        raise ValueError(f'{what}: {vn} must be a dense tensor with {owner} shape {tuple(k.shape)}, got {tuple(v.shape)}')
+    values = torch.Tensor.values(layout)  # (taken once: a new tensor every time)
+    operands = {'layout': values, 'q': q, kn: k, vn: v}  # in the order the device check names them
+    if paged:
+        page = k.shape[2]
+        if not _page_ok(page):
+            raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} keys, got page = {page} '
+                             f'(accepted: {_DECODE_PAGED_SIZES_TEXT})')
+        Smax = _check_block_table(what, block_table, B) * page
+        operands['block_table'] = block_table
+    _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, values.numel(), k_lens, block)
+    outer, unit = ('page' if paged else 'batch'), (16 if fp8 else 8)
+    _check_cache_strides(what, kn, k, D, outer, unit)
+    _check_cache_strides(what, vn, v, D, outer, unit)
+    operands['k_lens'] = k_lens
+    if fp8:
+        operands.update(_check_fp8_scales(what, scales, Hkv, q))
+    _check_on_device(what, **operands)
+    return Smax
+
+
+_DECODE_BINDINGS = (('block_attention_decode', 'block_attention_decode_fp8'),  # [paged][fp8]
+                    ('block_attention_decode_paged', 'block_attention_decode_paged_fp8'))
+
+
+def _decode(what, names, q, k, v, block_table, layout, k_lens, block, scale, chunk, k_scale, v_scale, fp8, return_lse):
+    '''The one body of the four decode calls: the checks, the defaults, the operands as the binding takes them, one binding
+    call.  `names` as in _check_block_attention_decode_operands; block_table, k_scale and v_scale are looked at by the paged
+    and the fp8 forms only.'''
+    paged = names[0] == 'k_pages'
+    scales = (('k_scale', k_scale), ('v_scale', v_scale)) if fp8 else ()
+    Smax = _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8, scales, block_table)
+    B, Hq, T, D = q.shape
+    if scale is None:
+        scale = 1.0 / float(D) ** 0.5
+    if chunk is None:
+        chunk = _decode_chunk(Smax, D)
+    with torch.no_grad():
+        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
+        offsets, columns, nnz, _ = rec['fwd']
+        lens = _lens_i32(k_lens)
+        table = (_table_i32(block_table),) if paged else ()
+        qc = q.detach().contiguous()
+        out = torch.empty_like(qc)
+        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
+        if out.numel() > 0:
+            binding = getattr(custom_mm, _DECODE_BINDINGS[paged][fp8])
+            fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
+            binding(offsets, columns, nnz, qc, k.detach(), v.detach(), *table, lens, float(scale), *fp8_scales, int(chunk), out, lse)
+    return (out, lse) if return_lse else out
 
 
 def block_sparse_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
@@ -1938,86 +2033,19 @@ def block_sparse_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Ten
 
     Returns out [B, Hq, T, D] in q's dtype, or with return_lse=True (out, lse) with lse float32 [B, Hq, T].  There is NO
     autograd: the result does not require grad whatever the operands do.  scale defaults to 1/√D.'''
-    what = 'block_sparse_attention_decode'
-    group = _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block, chunk)
-    B, Hq, T, D = q.shape
-    Smax = k.shape[2]
-    if scale is None:
-        scale = 1.0 / float(D) ** 0.5
-    if chunk is None:
-        chunk = _decode_chunk(Smax, D)
-    with torch.no_grad():
-        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
-        offsets, columns, nnz, _ = rec['fwd']
-        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
-        qc = q.detach().contiguous()
-        out = torch.empty_like(qc)
-        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
-        if out.numel() > 0:
-            custom_mm.block_attention_decode(offsets, columns, nnz, qc, k.detach(), v.detach(), lens, float(scale), int(chunk), out, lse)
-    return (out, lse) if return_lse else out
+    return _decode('block_sparse_attention_decode', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, chunk, None, None, False,
+                   return_lse)
 
 
 # --------------------------------------------------------------------------- #
 # … over a paged KV cache: a pool of pages and a block table per item (DESIGN.md §3.19)
 # --------------------------------------------------------------------------- #
 
-_DECODE_MIN_PAGE = 16    # keys of the smallest page: a 16-row MFMA fragment of a k tile never straddles two pages
-_DECODE_PAGED_SIZES_TEXT = _DECODE_SIZES_TEXT + ', pages of a power of two >= 16 keys'
-
-
-def _page_ok(page) -> bool:
-    return isinstance(page, int) and not isinstance(page, bool) and page >= _DECODE_MIN_PAGE and page & (page - 1) == 0
-
-
 def block_attention_decode_paged_takes(dtype, D: int, block: int, group: int, page: int) -> bool:
     '''Whether block_sparse_attention_decode_paged takes head size D, block size `block`, `group` query heads per k / v
     head and pages of `page` keys in `dtype` — a function of these alone: block_attention_decode_takes(dtype, D, block,
     group) and page a power of two ≥ 16.'''
     return block_attention_decode_takes(dtype, D, block, group) and _page_ok(page)
-
-
-def _check_block_attention_decode_paged_operands(what, q, k_pages, v_pages, block_table, layout, k_lens, block, chunk, fp8=False,
-                                                 scales=()):
-    '''Every refusal of block_sparse_attention_decode_paged before the first device call: those of the contiguous call
-    (the same functions, Smax = W · page) and the pool's and the table's own.  Returns the group.  fp8, scales: as in
-    _check_block_attention_decode_operands.'''
-    _check_decode_call(what, ('k_pages', 'v_pages'), q, k_pages, v_pages, layout, block, chunk, fp8)
-    if q.dim() != 4 or k_pages.dim() != 4 or v_pages.dim() != 4:
-        raise ValueError(f'{what}: q must be [B, Hq, T, D] and k_pages, v_pages [P, Hkv, page, D], got {q.dim()}-d, '
-                         f'{k_pages.dim()}-d and {v_pages.dim()}-d')
-    B, Hq, T, D = q.shape
-    if D not in _BLOCK_HEAD_SIZES:
-        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_DECODE_PAGED_SIZES_TEXT})')
-    P, Hkv, page = k_pages.shape[0], k_pages.shape[1], k_pages.shape[2]
-    if k_pages.shape[3] != D or Hkv < 1 or Hq % Hkv != 0:
-        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs k_pages {("P", "Hkv", "page", D)} with Hkv a divisor of '
-                         f'{Hq}, got {tuple(k_pages.shape)}')
-    group = _check_decode_group(what, Hq, Hkv)
-    if tuple(v_pages.shape) != tuple(k_pages.shape):
-        raise ValueError(f'{what}: v_pages must be a dense tensor with k_pages\' shape {tuple(k_pages.shape)}, got '
-                         f'{tuple(v_pages.shape)}')
-    if not _page_ok(page):
-        raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} keys, got page = {page} '
-                         f'(accepted: {_DECODE_PAGED_SIZES_TEXT})')
-    if not isinstance(block_table, torch.Tensor) or block_table.layout != torch.strided:
-        raise ValueError(f'{what}: block_table is required and must be a dense tensor')
-    if block_table.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f'{what}: block_table must be an int32 or int64 tensor, got {block_table.dtype}')
-    if block_table.dim() != 2 or block_table.shape[0] != B:
-        raise ValueError(f'{what}: block_table must have shape ({B}, W) — a row of logical pages per batch item —, got '
-                         f'{tuple(block_table.shape)}')
-    W = block_table.shape[1]
-    if W > 1 and block_table.stride(1) != 1:
-        raise ValueError(f'{what}: block_table must have a last stride of 1, got {block_table.stride(1)}')
-    if B > 1 and block_table.stride(0) < W:
-        raise ValueError(f'{what}: block_table\'s row stride must be at least W = {W}, got {block_table.stride(0)}')
-    _check_decode_layout_and_lens(what, B, Hkv, T, W * page, layout, k_lens, block)
-    _check_cache_strides(what, 'k_pages', k_pages, D, 'page', 16 if fp8 else 8)
-    _check_cache_strides(what, 'v_pages', v_pages, D, 'page', 16 if fp8 else 8)
-    _check_on_device(what, layout=torch.Tensor.values(layout), q=q, k_pages=k_pages, v_pages=v_pages, block_table=block_table,
-                     k_lens=k_lens, **_check_fp8_scales(what, scales, Hkv, q))
-    return group
 
 
 def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
@@ -2043,28 +2071,8 @@ def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, 
     block_sparse_attention_decode with the same chunk on the cache gathered to [B, Hkv, Smax, D] — so they do not depend
     on P, on where the pages lie, or on `page`.  No atomics, no read-back: graph-capturable, and one captured graph keeps
     serving while k_lens, the pool and the block table are updated in place.  NO autograd.'''
-    what = 'block_sparse_attention_decode_paged'
-    _check_block_attention_decode_paged_operands(what, q, k_pages, v_pages, block_table, layout, k_lens, block, chunk)
-    B, Hq, T, D = q.shape
-    Smax = block_table.shape[1] * k_pages.shape[2]
-    if scale is None:
-        scale = 1.0 / float(D) ** 0.5
-    if chunk is None:
-        chunk = _decode_chunk(Smax, D)
-    with torch.no_grad():
-        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
-        offsets, columns, nnz, _ = rec['fwd']
-        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
-        table = block_table.detach()
-        if table.dtype != torch.int32:
-            table = table.to(torch.int32)
-        qc = q.detach().contiguous()
-        out = torch.empty_like(qc)
-        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
-        if out.numel() > 0:
-            custom_mm.block_attention_decode_paged(offsets, columns, nnz, qc, k_pages.detach(), v_pages.detach(), table, lens,
-                                                   float(scale), int(chunk), out, lse)
-    return (out, lse) if return_lse else out
+    return _decode('block_sparse_attention_decode_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens, block,
+                   scale, chunk, None, None, False, return_lse)
 
 
 # --------------------------------------------------------------------------- #
@@ -2182,26 +2190,8 @@ def block_sparse_attention_decode_fp8(q: torch.Tensor, k: torch.Tensor, v: torch
     with k_scale = s for all heads and v_scale = 2^n, out is that call\'s result at scale\' = float32(scale) · float32(s)
     times 2^n, and lse that call\'s.  Nothing beyond pos, in an unlisted block or between the rows is loaded: a NaN byte
     there reaches no output.'''
-    what = 'block_sparse_attention_decode_fp8'
-    _check_block_attention_decode_operands(what, q, k, v, layout, k_lens, block, chunk, True,
-                                           (('k_scale', k_scale), ('v_scale', v_scale)))
-    B, Hq, T, D = q.shape
-    Smax = k.shape[2]
-    if scale is None:
-        scale = 1.0 / float(D) ** 0.5
-    if chunk is None:
-        chunk = _decode_chunk(Smax, D)
-    with torch.no_grad():
-        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
-        offsets, columns, nnz, _ = rec['fwd']
-        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
-        qc = q.detach().contiguous()
-        out = torch.empty_like(qc)
-        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
-        if out.numel() > 0:
-            custom_mm.block_attention_decode_fp8(offsets, columns, nnz, qc, k.detach(), v.detach(), lens, float(scale),
-                                                 _fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device), int(chunk), out, lse)
-    return (out, lse) if return_lse else out
+    return _decode('block_sparse_attention_decode_fp8', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, chunk, k_scale, v_scale,
+                   True, return_lse)
 
 
 def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
@@ -2217,30 +2207,8 @@ def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tens
     and scales on the gathered cache; with both scales None, those of block_sparse_attention_decode_paged on the pool
     widened to q\'s type.  Nothing in an invalid page is loaded.  Graph-capturable while k_lens, the pool, the table and
     the scale tensors are updated in place.'''
-    what = 'block_sparse_attention_decode_paged_fp8'
-    _check_block_attention_decode_paged_operands(what, q, k_pages, v_pages, block_table, layout, k_lens, block, chunk, True,
-                                                 (('k_scale', k_scale), ('v_scale', v_scale)))
-    B, Hq, T, D = q.shape
-    Smax = block_table.shape[1] * k_pages.shape[2]
-    if scale is None:
-        scale = 1.0 / float(D) ** 0.5
-    if chunk is None:
-        chunk = _decode_chunk(Smax, D)
-    with torch.no_grad():
-        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
-        offsets, columns, nnz, _ = rec['fwd']
-        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
-        table = block_table.detach()
-        if table.dtype != torch.int32:
-            table = table.to(torch.int32)
-        qc = q.detach().contiguous()
-        out = torch.empty_like(qc)
-        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
-        if out.numel() > 0:
-            custom_mm.block_attention_decode_paged_fp8(offsets, columns, nnz, qc, k_pages.detach(), v_pages.detach(), table, lens,
-                                                       float(scale), _fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device),
-                                                       int(chunk), out, lse)
-    return (out, lse) if return_lse else out
+    return _decode('block_sparse_attention_decode_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens,
+                   block, scale, chunk, k_scale, v_scale, True, return_lse)
 
 
 # --------------------------------------------------------------------------- #
@@ -2322,32 +2290,15 @@ def _check_kv_append_operands(what, names, k_new, v_new, k, v, k_lens, scales, b
         page = k.shape[2]
         if not _page_ok(page):
             raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} rows, got page = {page}')
-        if not isinstance(block_table, torch.Tensor) or block_table.layout != torch.strided:
-            raise ValueError(f'{what}: block_table is required and must be a dense tensor')
-        if block_table.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f'{what}: block_table must be an int32 or int64 tensor, got {block_table.dtype}')
-        if block_table.dim() != 2 or block_table.shape[0] != B:
-            raise ValueError(f'{what}: block_table must have shape ({B}, W) — a row of logical pages per batch item —, got '
-                             f'{tuple(block_table.shape)}')
-        W = block_table.shape[1]
-        if W > 1 and block_table.stride(1) != 1:
-            raise ValueError(f'{what}: block_table must have a last stride of 1, got {block_table.stride(1)}')
-        if B > 1 and block_table.stride(0) < W:
-            raise ValueError(f'{what}: block_table\'s row stride must be at least W = {W}, got {block_table.stride(0)}')
+        Smax = _check_block_table(what, block_table, B) * page
         tensors['block_table'] = block_table
-        Smax = W * page
     else:
         Smax = k.shape[2]
     if B * Hkv > _DECODE_MAX_GRID:
         raise ValueError(f'{what}: B·Hkv = {B * Hkv} must be at most {_DECODE_MAX_GRID}, as in the decode calls')
     if B * Hkv * T * (D // 8) >= 2 ** 31 or Smax >= 2 ** 31:
         raise ValueError(f'{what}: B·Hkv·T·D/8 = {B * Hkv * T * (D // 8)} and Smax = {Smax} must fit int32 indices')
-    if not isinstance(k_lens, torch.Tensor) or k_lens.layout != torch.strided:
-        raise ValueError(f'{what}: k_lens is required and must be a dense tensor')
-    if k_lens.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f'{what}: k_lens must be an int32 or int64 tensor, got {k_lens.dtype}')
-    if tuple(k_lens.shape) not in ((), (B,)):
-        raise ValueError(f'{what}: k_lens must have shape ({B},) — one length per batch item — or be 0-d, got {tuple(k_lens.shape)}')
+    _check_k_lens(what, k_lens, B)
     _check_source_strides(what, 'k_new', k_new)
     _check_source_strides(what, 'v_new', v_new)
     outer = 'page' if paged else 'batch'
@@ -2392,7 +2343,7 @@ def kv_cache_append(k_new: torch.Tensor, v_new: torch.Tensor, k: torch.Tensor, v
     if k_new.numel() == 0 or k.numel() == 0:
         return None
     with torch.no_grad():
-        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
+        lens = _lens_i32(k_lens)
         ks, vs = (_fp8_scale(k_scale, k_new.device), _fp8_scale(v_scale, k_new.device)) if fp8 else (None, None)
         custom_mm.kv_append(k_new.detach(), v_new.detach(), k.detach(), v.detach(), lens, ks, vs)
     return None
@@ -2418,10 +2369,8 @@ def kv_cache_append_paged(k_new: torch.Tensor, v_new: torch.Tensor, k_pages: tor
     if k_new.numel() == 0 or k_pages.numel() == 0 or block_table.numel() == 0:
         return None
     with torch.no_grad():
-        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
-        table = block_table.detach()
-        if table.dtype != torch.int32:
-            table = table.to(torch.int32)
+        lens = _lens_i32(k_lens)
+        table = _table_i32(block_table)
         ks, vs = (_fp8_scale(k_scale, k_new.device), _fp8_scale(v_scale, k_new.device)) if fp8 else (None, None)
         custom_mm.kv_append_paged(k_new.detach(), v_new.detach(), k_pages.detach(), v_pages.detach(), table, lens, ks, vs)
     return None
@@ -2533,17 +2482,14 @@ def _rope_kv_cache_append(what, names, q, k_new, v_new, cos, sin, k, v, block_ta
     if q.numel() == 0:
         return torch.empty_like(q, memory_format=torch.contiguous_format) if q_out is None else q_out
     with torch.no_grad():
-        lens = k_lens.detach().to(torch.int32).reshape(-1).contiguous()
+        lens = _lens_i32(k_lens)
         news = None if new_lens is None else new_lens.detach().to(torch.int32).contiguous()
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device) if q_out is None else q_out
         ks, vs = (_fp8_scale(k_scale, k_new.device), _fp8_scale(v_scale, k_new.device)) if fp8 else (None, None)
         head = (q.detach(), k_new.detach(), v_new.detach(), cos.detach(), sin.detach(), k.detach(), v.detach())
         tail = (lens, news, out.detach(), None if k_out is None else k_out.detach(), R, interleaved, ks, vs)
         if paged:
-            table = block_table.detach()
-            if table.dtype != torch.int32:
-                table = table.to(torch.int32)
-            custom_mm.rope_kv_append_paged(*head, table, *tail)
+            custom_mm.rope_kv_append_paged(*head, _table_i32(block_table), *tail)
         else:
             custom_mm.rope_kv_append(*head, *tail)
     return out
