@@ -35,26 +35,12 @@
 //    for the key-block kernel; P = exp(scale·S − lse).
 //  * backward, key blocks over the transposed layout: own = k, v; walk = q (Sᵀ), dO (dPᵀ), dOᵀ (dV += Pᵀ·dO),
 //    qᵀ (dK += dSᵀ·Q); lse and δ of the walk rows are read per tile.
-#include "lowp_device.h"
+//
+// kB, the transposed image's stride, pack_tile, accumulate and group_max / group_sum are block_attention_device.h's, which
+// block_attention_decode.hip shares; mfma<T> and half_of are mfma_device.h's.
+#include "block_attention_device.h"
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <class T>
-__device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma<Bf16>(uint4 a, uint4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma<F16>(uint4 a, uint4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-constexpr int kB = 64;         // rows of a block: the kernels' tile on both sides
-constexpr int kTStr = kB + 8;  // row stride of a transposed image in elements (144 bytes)
 
 struct Dense {  // a [batch][rows][D] operand: leading dimension and item stride in elements
   uint16_t* p;
@@ -86,11 +72,6 @@ __device__ __forceinline__ int length_of(const int32_t* lens, int entry, long ro
   return n < 0 ? 0 : n > rows ? (int)rows : n;
 }
 
-__device__ __forceinline__ unsigned half_of(uint4 v, int i) {
-  const unsigned w = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
-  return (i & 1) ? (w >> 16) : (w & 0xffffu);
-}
-
 // One 64 × D block in registers: unit u = tid < 2D holds rows 4(u & 15) … + 3, columns 8(u >> 4) … + 7.
 template <int D>
 struct Tile {
@@ -116,15 +97,9 @@ struct Tile {
       for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(R + (4 * (tid & 15) + i) * (D + 8) + 8 * (tid >> 4)) = v[i];
     }
   }
-  // the transposed image [D][64 + 8]
+  // the transposed image [D][64 + 8]: the unit is store_rc's, the walk rows its k
   __device__ __forceinline__ void store_transposed(unsigned short* Tt, int tid) const {
-    if (tid < 2 * D) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const uint2 w = {half_of(v[0], e) | (half_of(v[1], e) << 16), half_of(v[2], e) | (half_of(v[3], e) << 16)};
-        *reinterpret_cast<uint2*>(Tt + (8 * (tid >> 4) + e) * kTStr + 4 * (tid & 15)) = w;
-      }
-    }
+    if (tid < 2 * D) store_rc(Tt, v, tid);
   }
 };
 
@@ -152,28 +127,6 @@ __device__ __forceinline__ void score(f32x4 (&acc)[4], const unsigned short* R, 
       acc[f] = mfma<T>(a, own[s], acc[f]);
     }
   }
-}
-
-// a score-shaped tile narrowed to T as the B operand of the two k-steps over the walk rows
-template <class T>
-__device__ __forceinline__ void pack_tile(uint4 (&b)[2], const f32x4 (&x)[4]) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-    b[s] = uint4{pack2<T>(x[2 * s][0], x[2 * s][1]), pack2<T>(x[2 * s][2], x[2 * s][3]), pack2<T>(x[2 * s + 1][0], x[2 * s + 1][1]),
-                 pack2<T>(x[2 * s + 1][2], x[2 * s + 1][3])};
-}
-
-// out[fd][r] += Σ over the walk rows of Tt[d = 16fd + 4lg + r][walk row] · b[walk row][own row li]
-template <class T, int D>
-__device__ __forceinline__ void accumulate(f32x4 (&out)[D / 16], const unsigned short* Tt, const uint4 (&b)[2], int li, int lg) {
-#pragma unroll
-  for (int fd = 0; fd < D / 16; ++fd)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const unsigned short* p = Tt + (16 * fd + li) * kTStr + 32 * s + 4 * lg;
-      const uint2 lo = *reinterpret_cast<const uint2*>(p), hi = *reinterpret_cast<const uint2*>(p + 16);
-      out[fd] = mfma<T>(uint4{lo.x, lo.y, hi.x, hi.y}, b[s], out[fd]);
-    }
 }
 
 // rows [d][own row li] → own row li, columns 16fd + 4lg … + 3, each value times `mul`, rounded once
@@ -211,15 +164,6 @@ __device__ __forceinline__ int next_block(const int32_t* col, int p, int end, in
     break;
   }
   return p;
-}
-
-__device__ __forceinline__ float group_max(float x) {  // over the four lanes li, li + 16, li + 32, li + 48
-  x = fmaxf(x, __shfl_xor(x, 16));
-  return fmaxf(x, __shfl_xor(x, 32));
-}
-__device__ __forceinline__ float group_sum(float x) {
-  x = x + __shfl_xor(x, 16);
-  return x + __shfl_xor(x, 32);
 }
 
 struct Walk {  // the part of a layout's list one workgroup walks

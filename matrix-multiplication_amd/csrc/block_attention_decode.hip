@@ -38,32 +38,19 @@
 // Kernel: grid (chunks, items, T), 256 threads.  No workgroup barrier inside the walk.  A wave loads the k tile of an
 // entry as 16-byte global loads straight into MFMA A fragments (lane (li, lg): row 16f + li, columns 32s + 8lg … + 7), the v
 // tile into registers and from there into a wave-private transposed LDS image [D][64 + 8] (a wave-level fence between its
-// writes and reads); the next entry's loads are issued before this one's softmax and P·V.  The device pieces (mfma,
-// score, pack_tile, accumulate, group_max / group_sum) are private copies of block_attention.hip's, adapted to one wave.
+// writes and reads); the next entry's loads are issued before this one's softmax and P·V.  kB, the image's stride,
+// pack_tile, accumulate and group_max / group_sum are block_attention_device.h's, which block_attention.hip shares (the walk
+// rows are the keys here); mfma<T> and half_of are mfma_device.h's; what is said about the cache is
+// kv_cache_device.h's (§3.23).  `score` is this unit's own: its k fragments come from registers.
 #include <type_traits>
 
+#include "block_attention_device.h"
 #include "kv_cache_device.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <class T>
-__device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma<Bf16>(uint4 a, uint4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma<F16>(uint4 a, uint4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-constexpr int kB = 64;          // keys of a block: the kernel's tile
-constexpr int kTStr = kB + 8;   // row stride of the transposed image in elements (144 bytes)
-constexpr int kWaves = 4;       // waves of a workgroup: wave w walks entries w, w + 4, … of the chunk
-constexpr int kMaxGroup = 16;   // own rows of the one MFMA tile
+constexpr int kWaves = 4;      // waves of a workgroup: wave w walks entries w, w + 4, … of the chunk
+constexpr int kMaxGroup = 16;  // own rows of the one MFMA tile
 
 struct Args {
   const int32_t* rowptr;  // [layouts][blocks + 1], with the layouts' bases
@@ -162,11 +149,6 @@ template <> __device__ __forceinline__ uint2 zero_frag<uint2>() { return uint2{0
 constexpr int kContiguous = 0;  // one [Smax][D] run per k / v item behind fixed strides
 constexpr int kPaged = 1;       // a pool of pages ≥ 64 keys: the tile lies inside one page — one table entry per tile
 constexpr int kPagedSmall = 2;  // pages of 16 or 32 keys: the tile spans 64 / page whole pages — one entry per page
-
-__device__ __forceinline__ unsigned half_of(uint4 v, int i) {
-  const unsigned w = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
-  return (i & 1) ? (w >> 16) : (w & 0xffffu);
-}
 
 __device__ __forceinline__ void fence_wave() {  // LDS writes of this wave before, its reads after
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -268,7 +250,7 @@ __device__ __forceinline__ void store_transposed(unsigned short* Tt, const uint4
 #pragma unroll
   for (int i = 0; i < D / 32; ++i)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
+    for (int e = 0; e < 8; ++e) {  // mfma_device.h's store_rc for unit li + 16(lg + 4i), written out: the call changed 48 kernels
       const uint2 w = {half_of(vr[i][0], e) | (half_of(vr[i][1], e) << 16), half_of(vr[i][2], e) | (half_of(vr[i][3], e) << 16)};
       *reinterpret_cast<uint2*>(Tt + (8 * (lg + 4 * i) + e) * kTStr + 4 * li) = w;
     }
@@ -296,37 +278,6 @@ __device__ __forceinline__ void score(f32x4 (&acc)[4], const F (&kf)[4][D / 32],
 #pragma unroll
     for (int s = 0; s < D / 32; ++s) acc[f] = mfma<T>(widen<T>(kf[f][s]), own[s], acc[f]);
   }
-}
-
-// a score-shaped tile narrowed to T as the B operand of the two k-steps over the keys
-template <class T>
-__device__ __forceinline__ void pack_tile(uint4 (&b)[2], const f32x4 (&x)[4]) {
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-    b[s] = uint4{pack2<T>(x[2 * s][0], x[2 * s][1]), pack2<T>(x[2 * s][2], x[2 * s][3]), pack2<T>(x[2 * s + 1][0], x[2 * s + 1][1]),
-                 pack2<T>(x[2 * s + 1][2], x[2 * s + 1][3])};
-}
-
-// out[fd][r] += Σ over the keys of Tt[d = 16fd + 4lg + r][key] · b[key][own row li]
-template <class T, int D>
-__device__ __forceinline__ void accumulate(f32x4 (&out)[D / 16], const unsigned short* Tt, const uint4 (&b)[2], int li, int lg) {
-#pragma unroll
-  for (int fd = 0; fd < D / 16; ++fd)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const unsigned short* p = Tt + (16 * fd + li) * kTStr + 32 * s + 4 * lg;
-      const uint2 lo = *reinterpret_cast<const uint2*>(p), hi = *reinterpret_cast<const uint2*>(p + 16);
-      out[fd] = mfma<T>(uint4{lo.x, lo.y, hi.x, hi.y}, b[s], out[fd]);
-    }
-}
-
-__device__ __forceinline__ float group_max(float x) {  // over the four lanes li, li + 16, li + 32, li + 48
-  x = fmaxf(x, __shfl_xor(x, 16));
-  return fmaxf(x, __shfl_xor(x, 32));
-}
-__device__ __forceinline__ float group_sum(float x) {
-  x = x + __shfl_xor(x, 16);
-  return x + __shfl_xor(x, 32);
 }
 
 // the next entry of this wave at or after p (in steps of the workgroup's waves) that is computed: inside the grid and

@@ -1,35 +1,18 @@
 // Device-side pieces shared by the block-sparse translation units on the matrix cores (bsr_mm.hip: A·b and the sampled
-// product; bsr_linear.hip: x·Wᵀ and the weight gradient): the MFMA wrapper, the staging of a 64 × 64 value block and of a
-// rows-contiguous tile through registers into LDS images [rows][64 + 8], the 32-row × (FN·16)-column wave tile and its
-// fragment-pair store.  Not installed.  Everything here has internal linkage (an anonymous namespace per including unit).
+// product; bsr_linear.hip: x·Wᵀ and the weight gradient): the staging of a 64 × 64 value block and of a rows-contiguous tile
+// through registers into LDS images [rows][kStr], the 32-row × (FN·16)-column wave tile and its fragment-pair store.  The
+// MFMA wrapper, half_of, the row stride kStr and the transposing store are mfma_device.h's, which gemm_lowp.hip and the
+// attention units share.  Not installed.  Everything here has internal linkage (an anonymous namespace
+// per including unit).
 #ifndef MI_BSR_DEVICE_H_
 #define MI_BSR_DEVICE_H_
 
-#include "lowp_device.h"
+#include "mfma_device.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <class T>
-__device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c);
-template <>
-__device__ __forceinline__ f32x4 mfma<Bf16>(uint4 a, uint4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <>
-__device__ __forceinline__ f32x4 mfma<F16>(uint4 a, uint4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-constexpr int kB = 64;        // rows and columns of a block: the k-tile of every kernel here
-constexpr int kStr = kB + 8;  // LDS row stride in elements (144 bytes: 16 rows of a fragment read on 16 bank slots)
-
-__device__ __forceinline__ unsigned half_of(uint4 v, int i) {
-  const unsigned w = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
-  return (i & 1) ? (w >> 16) : (w & 0xffffu);
-}
+constexpr int kB = 64;  // rows and columns of a block: the k-tile of every kernel here
+static_assert(kB == kTileK, "a block is one staged k-tile");
 
 __device__ __forceinline__ uint4 pack8(const unsigned short (&e)[8]) {
   return uint4{e[0] | ((unsigned)e[1] << 16), e[2] | ((unsigned)e[3] << 16), e[4] | ((unsigned)e[5] << 16),
@@ -37,6 +20,7 @@ __device__ __forceinline__ uint4 pack8(const unsigned short (&e)[8]) {
 }
 
 // 8 contiguous elements p[0 … 7], of which the first `avail` exist (zeros for the rest; nothing read when avail ≤ 0).
+// (gemm_lowp.hip has this function with pack8 written out: each unit's kernels change with the other's form, §3.24.)
 template <bool VEC>
 __device__ __forceinline__ uint4 load8(const uint16_t* p, int avail) {
   if (VEC && avail >= 8) return *reinterpret_cast<const uint4*>(p);
@@ -60,8 +44,7 @@ struct BlockKC {
 };
 
 // R output-side rows × 64 values of k of an operand stored rows-contiguous (element (r, k) at P[k·ld + r]): 2R units of
-// 4 k-rows × 8 rows, one per thread, transposed in registers into 8-byte LDS writes.  The 16 k-quads of a row group go
-// to 16 consecutive lanes (the 8-byte writes of one transposed row then fall on 32 different bank slots).
+// 4 k-rows × 8 rows, one per thread, transposed in registers into 8-byte LDS writes (store_rc).
 template <int R>
 struct TileRC {
   uint4 v[4];
@@ -73,20 +56,14 @@ struct TileRC {
     for (int q = 0; q < 4; ++q) v[q] = load8<VEC>(P + (long)(kk + q) * ld + r, avail);
   }
   __device__ __forceinline__ void store(unsigned short* S, int tid) const {
-    if (tid < 2 * R) {
-      const int r = (tid >> 4) * 8, kk = (tid & 15) * 4;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const uint2 w = {half_of(v[0], i) | (half_of(v[1], i) << 16), half_of(v[2], i) | (half_of(v[3], i) << 16)};
-        *reinterpret_cast<uint2*>(S + (r + i) * kStr + kk) = w;
-      }
-    }
+    if (tid < 2 * R) store_rc(S, v, tid);
   }
 };
 
 // The 2 × FN accumulators of a wave over one staged 64-deep k-tile: As [64][kStr] the output rows, Bs [BN][kStr] the
 // output columns.  Fragment pair j/2: row li of fragment j holds column 32(j/2) + 8(li/4) + 4(j%2) + li%4 of the wave's
-// tile, so that a lane ends with eight adjacent columns of one row (gemm_lowp.hip).
+// tile, so that a lane ends with eight adjacent columns of one row.  (gemm_lowp_kernel and bsr_linear_kernel have this
+// loop written out, FM × FN: called from there, with FM a parameter, it changed their kernels, §3.24.)
 template <class T, int FN>
 __device__ __forceinline__ void tile_mfma(f32x4 (&acc)[2][FN], const unsigned short* As, const unsigned short* Bs, int wm, int wn,
                                           int li, int lg) {

@@ -157,6 +157,7 @@ __global__ __launch_bounds__(256) void bsr_linear_kernel(LinArgs g) {
     if (q < end) st.load(g, q, t0, tid);
     const unsigned short* Xs = smem + buf * kBuf;
     const unsigned short* Ws = Xs + BM * kStr;
+    // bsr_device.h's tile_mfma with FM rows of fragments, written out: as a call it changed all 32 instantiations (§3.24)
 #pragma unroll
     for (int ks = 0; ks < kB / 32; ++ks) {
       const int kofs = ks * 32 + 8 * lg;
@@ -220,14 +221,7 @@ struct TokensRC {
       v[q] = load8<VEC>(P + (long)t * ld + c, t < t_end ? 8 : 0);
     }
   }
-  __device__ __forceinline__ void store(unsigned short* S, int u) const {
-    const int c = (u >> 4) * 8, kk = (u & 15) * 4;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const uint2 w = {half_of(v[0], i) | (half_of(v[1], i) << 16), half_of(v[2], i) | (half_of(v[3], i) << 16)};
-      *reinterpret_cast<uint2*>(S + (c + i) * kStr + kk) = w;
-    }
-  }
+  __device__ __forceinline__ void store(unsigned short* S, int u) const { store_rc(S, v, u); }
 };
 
 template <class T, bool VEC, bool PARTIAL>

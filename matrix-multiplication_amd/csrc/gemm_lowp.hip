@@ -12,8 +12,8 @@
 //
 // Kernel: a 256-thread workgroup owns a BM × BN tile of one batch item (BM = 128; BN = 128, or 64 for narrow products
 // and for grids too small to fill the chip); 4 waves in 2 × 2, each 16 × 16 MFMA tiles over a 64-deep k-tile.  Both
-// operands are staged through registers into LDS images with k contiguous ([rows][64 + 8] elements: the 144-byte row
-// puts the 16 rows a fragment read touches on 16 different 16-byte bank slots), double-buffered: the global loads of
+// operands are staged through registers into LDS images with k contiguous ([rows][kStr] elements: the padded row of
+// mfma_device.h), double-buffered: the global loads of
 // k-tile t + 1 are in flight while the MFMAs of tile t run, one barrier per k-tile.  An operand stored with k
 // contiguous (A plain, B transposed) moves as 16-byte pieces; one stored k-strided (A transposed, B plain) is read as
 // 4 k-rows × 8 elements and transposed in registers into 8-byte LDS writes.  The MFMA takes the B fragment as its first
@@ -32,41 +32,14 @@
 //    split-k below, which run as a batch of S items whose operands are the k-ranges (as gemm_splitk.hip does in fp32).
 // Split-k: k cut into S equal ranges of whole 32-deep MFMA steps, each range the family order from +0; the combine kernel
 // adds an element's partial sums in index order, ((P0 + P1) + P2) + …, then the bias, and rounds once.  No atomics.
-#include "mi_common.h"
+//
+// The element types are lowp_device.h's; the MFMA wrapper, half_of, the row stride kStr and the transposing store of a
+// k-strided operand are mfma_device.h's, which the block-sparse and the attention units share.
+#include "mfma_device.h"
 
 namespace {
 
-using mi::f32x4;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kBK = 64;        // k per LDS tile (two MFMA k-steps)
-constexpr int kStr = kBK + 8;  // LDS row stride in elements (144 bytes)
-
-struct Bf16 {
-  static __device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ unsigned pack2(float a, float b) {
-    return (unsigned)__builtin_bit_cast(unsigned short, static_cast<__bf16>(a)) |
-           ((unsigned)__builtin_bit_cast(unsigned short, static_cast<__bf16>(b)) << 16);
-  }
-  static __device__ __forceinline__ unsigned short down(float f) { return __builtin_bit_cast(unsigned short, static_cast<__bf16>(f)); }
-  static __device__ __forceinline__ float up(unsigned h) { return __builtin_bit_cast(float, h << 16); }
-};
-struct F16 {
-  static __device__ __forceinline__ f32x4 mfma(uint4 a, uint4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ unsigned pack2(float a, float b) {
-    return (unsigned)__builtin_bit_cast(unsigned short, static_cast<_Float16>(a)) |
-           ((unsigned)__builtin_bit_cast(unsigned short, static_cast<_Float16>(b)) << 16);
-  }
-  static __device__ __forceinline__ unsigned short down(float f) { return __builtin_bit_cast(unsigned short, static_cast<_Float16>(f)); }
-  static __device__ __forceinline__ float up(unsigned h) {
-    return static_cast<float>(__builtin_bit_cast(_Float16, (unsigned short)h));
-  }
-};
+constexpr int kBK = kTileK;  // k per LDS tile (two MFMA k-steps)
 
 enum Epilogue { kStore = 0, kBias = 1, kPartial = 2 };
 
@@ -82,6 +55,7 @@ struct GemmArgs {
 };
 
 // 8 contiguous elements p[0 … 7], of which the first `avail` exist (zeros for the rest; nothing read when avail ≤ 0).
+// (bsr_device.h has this function with the last expression as a call: each unit's kernels change with the other's form, §3.24.)
 template <bool VEC>
 __device__ __forceinline__ uint4 load8(const uint16_t* p, int avail) {
   if (VEC && avail >= 8) return *reinterpret_cast<const uint4*>(p);
@@ -92,17 +66,10 @@ __device__ __forceinline__ uint4 load8(const uint16_t* p, int avail) {
                e[6] | ((unsigned)e[7] << 16)};
 }
 
-__device__ __forceinline__ unsigned half_of(uint4 v, int i) {
-  const unsigned w = (i >> 1) == 0 ? v.x : (i >> 1) == 1 ? v.y : (i >> 1) == 2 ? v.z : v.w;
-  return (i & 1) ? (w >> 16) : (w & 0xffffu);
-}
-
 // One operand's R × kBK tile (R rows of the output side, kBK values of k) in registers.
 //  KC (k contiguous: element (r, k) at P[r·ld + k]): R·8 pieces of 8 k-values, R/32 per thread, 8 threads per row.
 //  RC (rows contiguous: element (r, k) at P[k·ld + r]): 2R units of 4 k-rows × 8 rows, one per thread (R = 64: half the
-//  threads), 4 pieces each.  The 16 k-quads of a row group go to 16 consecutive lanes: a wave's 8-byte LDS writes of one
-//  transposed row then fall on 32 different 8-byte bank slots (2-way, the least 512 bytes allow) — with the row groups on
-//  consecutive lanes instead, rows 8 apart sit 1152 ≡ 128 (mod 256) bytes apart and the writes were 8-way.
+//  threads), 4 pieces each, in the lane order of store_rc.
 template <int R, bool KC>
 struct Stage {
   static constexpr int kPieces = KC ? R / 32 : 4;
@@ -139,15 +106,7 @@ __device__ __forceinline__ void store_tile(const Stage<R, KC>& s, unsigned short
       *reinterpret_cast<uint4*>(S + (c >> 3) * kStr + (c & 7) * 8) = s.v[i];
     }
   } else {
-    const int u = tid;
-    if (u < 2 * R) {
-      const int r = (u >> 4) * 8, kk = (u & 15) * 4;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const uint2 w = {half_of(s.v[0], i) | (half_of(s.v[1], i) << 16), half_of(s.v[2], i) | (half_of(s.v[3], i) << 16)};
-        *reinterpret_cast<uint2*>(S + (r + i) * kStr + kk) = w;
-      }
-    }
+    if (tid < 2 * R) store_rc(S, s.v, tid);
   }
 }
 
@@ -200,6 +159,7 @@ __global__ __launch_bounds__(256) void gemm_lowp_kernel(GemmArgs g) {
       }
       const unsigned short* As = smem + (t & 1) * (BM + BN) * kStr;
       const unsigned short* Bs = As + BM * kStr;
+      // bsr_device.h's tile_mfma with FM rows of fragments, written out: as a call it changed all 96 instantiations (§3.24)
 #pragma unroll
       for (int ks = 0; ks < kBK / 32; ++ks) {
         const int kofs = ks * 32 + 8 * lg;
@@ -215,7 +175,7 @@ __global__ __launch_bounds__(256) void gemm_lowp_kernel(GemmArgs g) {
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
-          for (int j = 0; j < FN; ++j) acc[i][j] = T::mfma(bf[j], af[i], acc[i][j]);
+          for (int j = 0; j < FN; ++j) acc[i][j] = mfma<T>(bf[j], af[i], acc[i][j]);
       }
       if (more) {
         unsigned short* Sn = smem + ((t + 1) & 1) * (BM + BN) * kStr;
@@ -261,14 +221,14 @@ __global__ __launch_bounds__(256) void gemm_lowp_kernel(GemmArgs g) {
             const uint4 bv = bias8[p];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              x[e] = __fadd_rn(x[e], T::up(half_of(bv, e)));
-              y[e] = __fadd_rn(y[e], T::up(half_of(bv, 4 + e)));
+              x[e] = __fadd_rn(x[e], up<T>(half_of(bv, e)));
+              y[e] = __fadd_rn(y[e], up<T>(half_of(bv, 4 + e)));
             }
           }
           uint16_t* dst = C + (long)r * g.ldc + c;
           if (VEC && c + 8 <= g.n) {
             *reinterpret_cast<uint4*>(dst) =
-                uint4{T::pack2(x[0], x[1]), T::pack2(x[2], x[3]), T::pack2(y[0], y[1]), T::pack2(y[2], y[3])};
+                uint4{pack2<T>(x[0], x[1]), pack2<T>(x[2], x[3]), pack2<T>(y[0], y[1]), pack2<T>(y[2], y[3])};
           } else {
             const float v[8] = {x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
 #pragma unroll
@@ -307,13 +267,13 @@ __global__ __launch_bounds__(256) void gemm_lowp_combine_kernel(const float* __r
     }
     if (bias) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) t[e] = __fadd_rn(t[e], T::up(bias[j + e]));
+      for (int e = 0; e < 4; ++e) t[e] = __fadd_rn(t[e], up<T>(bias[j + e]));
     }
-    *reinterpret_cast<uint2*>(C + i * ldc + j) = uint2{T::pack2(t[0], t[1]), T::pack2(t[2], t[3])};
+    *reinterpret_cast<uint2*>(C + i * ldc + j) = uint2{pack2<T>(t[0], t[1]), pack2<T>(t[2], t[3])};
   } else {
     float t = P[idx];
     for (int s = 1; s < S; ++s) t = __fadd_rn(t, P[(long)s * mn + idx]);
-    if (bias) t = __fadd_rn(t, T::up(bias[j]));
+    if (bias) t = __fadd_rn(t, up<T>(bias[j]));
     C[i * ldc + j] = T::down(t);
   }
 }

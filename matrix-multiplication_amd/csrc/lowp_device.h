@@ -1,6 +1,9 @@
-// Device-side pieces shared by the bfloat16 / float16 translation units of the CSR product (csr_lowp.hip: sum, mean, SDDMM;
-// csr_reduce_lowp.hip: amax / amin and their gradients).  Not installed.  Everything here has internal linkage (an
-// anonymous namespace per including unit).
+// The two 16-bit element types, said once for every bfloat16 / float16 translation unit: Bf16 / F16 with their exact widening
+// and their one rounding, up<T>, pack2<T>, and the 4-element row pieces load4 / store4.  Included by the CSR units
+// (csr_lowp.hip, csr_reduce_lowp.hip, csr_softmax.hip through csr_softmax_device.h too, csr_attention.hip), by
+// mfma_device.h for the five matrix-core units (gemm_lowp.hip, bsr_mm.hip, bsr_linear.hip, block_attention.hip,
+// block_attention_decode.hip) and by kv_cache_device.h for the KV-cache family (kv_append.hip, rope_kv_append.hip).  Not
+// installed.  Everything here has internal linkage (an anonymous namespace per including unit).
 #ifndef MI_LOWP_DEVICE_H_
 #define MI_LOWP_DEVICE_H_
 
