@@ -99,7 +99,7 @@ def build_library(force=False, verbose=False) -> Path:
     headers = sorted(CSRC.glob("*.h")) + sorted(INCLUDE.glob("*.h"))
     flags = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", f"-I{INCLUDE}", f"-I{CSRC}",
              "-Wall", "-Wno-unused-function"]
-    flags += shlex.split(os.environ.get("MI_HIPCC_FLAGS", ""))  # developer A/B builds (-DMI_…); part of the stamp
+    flags += shlex.split(os.environ.get("MI_HIPCC_FLAGS", ""))  # extra compiler flags of a developer build; part of the stamp
     hdr_digest = _digest(headers, " ".join(flags))
 
     def compile_one(src: Path):
@@ -117,7 +117,8 @@ def build_library(force=False, verbose=False) -> Path:
             return obj, True
         return obj, False
 
-    with ThreadPoolExecutor(max_workers=min(max(2, (os.cpu_count() or 4) - 2), len(sources))) as pool:
+    # at most 16 compiles at once: a shared host reports every CPU it has, not the ones this process may use
+    with ThreadPoolExecutor(max_workers=min(max(2, (os.cpu_count() or 4) - 2), 16, len(sources))) as pool:
         results = list(pool.map(compile_one, sources))
     objs = [o for o, _ in results]
     if force or any(changed for _, changed in results) or not LIB_PATH.exists():

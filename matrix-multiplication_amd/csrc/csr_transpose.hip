@@ -41,10 +41,7 @@ constexpr int TR_THREADS = 1024;
 constexpr int TR_WAVES = TR_THREADS / 64;
 constexpr int TR_PER = TR_TILE / TR_THREADS;  // entries per thread
 constexpr int TR_GROUPS = 256;                // tile groups of the column-wise table scan
-#ifndef MI_TR_COUNT_THREADS
-#define MI_TR_COUNT_THREADS 256
-#endif
-constexpr int TR_COUNT_THREADS = MI_TR_COUNT_THREADS;  // count kernel (512: same, 1024: first pass 133 -> 187 µs)
+constexpr int TR_COUNT_THREADS = 256;         // count kernel (512: same, 1024: first pass 133 -> 187 µs)
 constexpr int TR_GRID = 256;                  // persistent scatter workgroups: one per CU of an MI355X
 // One-sweep plan: the tiles of a pass are cut into TR_LB_GROUPS contiguous groups; a group's per-digit base comes from
 // the histogram launch, offsets inside a group by decoupled look-back over at most its own tiles.  XCD x (workgroups
@@ -564,20 +561,6 @@ __global__ __launch_bounds__(256) void tr_rowptr_lb_kernel(const int* __restrict
 // next tile's entries are in flight while the current tile's stores drain.  The main path is
 // tr_scatter_staged_kernel below.
 // ---------------------------------------------------------------------------------------------
-#ifdef MI_TR_TIMING
-// per-phase cycle sums of wave 0 (tools/probes/tr_probe.cpp).  The sums are kept in scalar registers and
-// written once when the workgroup ends: an atomic per stamp sits in the same in-order memory queue as
-// the tile's loads and stores and slows exactly what is being measured.
-__device__ unsigned long long g_tr_phase[16];  // [0, 8): later passes, [8, 16): first pass
-#define TR_STAMP_INIT unsigned long long stamp_ = __builtin_readcyclecounter(), acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define TR_STAMP(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); acc_[k] += now_ - stamp_; stamp_ = now_; } while (0)
-#define TR_STAMP_FLUSH(first) do { if (threadIdx.x == 0) for (int k_ = 0; k_ < 8; ++k_) atomicAdd(&g_tr_phase[k_ + ((first) ? 8 : 0)], acc_[k_]); } while (0)
-#else
-#define TR_STAMP_INIT do {} while (0)
-#define TR_STAMP(k) do {} while (0)
-#define TR_STAMP_FLUSH(first) do {} while (0)
-#endif
-
 // An entry as the scatter kernel carries it: already in the form it leaves the pass in, plus its
 // digit — 3 registers on the main path (a 1024-thread workgroup has 128 VGPRs per lane; the first
 // form kept key, row, value, digit and rank apart and spilled to scratch inside the rank loop, which
@@ -673,12 +656,10 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_kernel(TrArgs a) {
     t_end = (xcd + 1) * per < a.ntiles ? (xcd + 1) * per : a.ntiles;
     t_step = TR_GRID / 8;
   }
-  TR_STAMP_INIT;
   if (t < t_end) fetch(t);
   for (; t < t_end; t += t_step) {
     const int cur_len = len;  // block-uniform
     if (cur_len > 0) {
-      TR_STAMP(0);
       for (int i = tid; i < TR_WAVES * nb / 2; i += TR_THREADS) reinterpret_cast<unsigned*>(cntw)[i] = 0u;
       if (tid == 0) carry_s = 0;
       if (FIRST) {
@@ -715,7 +696,6 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_kernel(TrArgs a) {
           }
         }
       }
-      TR_STAMP(1);
 
       // rank inside the wave: lanes holding the same digit ("peers") found with one ballot per digit
       // bit; a lane's rank is the wave's running count of the digit + the number of peers below it
@@ -736,9 +716,7 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_kernel(TrArgs a) {
         if (valid && below == 0) mycnt[d] = (unsigned short)(base + __builtin_popcountll(peers));
         e[c].d = d | ((unsigned)(base + below) << 16);
       }
-      TR_STAMP(2);
       __syncthreads();
-      TR_STAMP(3);
 
       // per digit: exclusive prefix over the waves (in place), tile total; then the exclusive scan of
       // the totals over the digits and the digit's global offset
@@ -783,7 +761,6 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_kernel(TrArgs a) {
         }
       }
 
-      TR_STAMP(4);
       {
         // straight from registers (wide keys / rows, 11-bit digits): correct for every size, but the
         // stores of a wave go to up to 64 different places
@@ -813,7 +790,6 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_kernel(TrArgs a) {
       if (t + t_step < t_end) fetch(t + t_step); else len = 0;
     }
   }
-  TR_STAMP_FLUSH(FIRST);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -828,7 +804,7 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_kernel(TrArgs a) {
 //       up when it was converted (first pass: its columns; the values of tile t itself are loaded one
 //       phase ahead, they are not needed before the tile is staged),
 // so loads, stores and ranking share the CU.  What it is up against (tools/probes/store_piece_probe.cpp,
-// tr_probe.cpp): the runs a tile leaves in are 32–64 bytes at arbitrary offsets, and an XCD's L2 accepts
+// profiles/r02_transpose_phases.log): the runs a tile leaves in are 32–64 bytes at arbitrary offsets, and an XCD's L2 accepts
 // such pieces at ≈5 per clock for its 32 CUs — ≈0.3 ms (first pass) and ≈0.46 ms (last pass: two 4-byte
 // arrays) for the C3 matrix whatever the kernel does; a wave whose store finds the queue full stalls
 // with its ranking work, so only the other waves' work overlaps.  Issued as blocks (all loads, then
@@ -841,25 +817,11 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_kernel(TrArgs a) {
 // vector load of a tile descriptor, turned every wait into vmcnt(0): load latency, store drain and
 // ranking one after the other.
 // ---------------------------------------------------------------------------------------------
-#ifndef MI_TR_INTERLEAVE
-#define MI_TR_INTERLEAVE 1
-#endif
 // Where slice k of the previous tile streams out: 0 = top of the tile, 1+c = after ranking step c,
 // 9 / 10 = prefix phase before its first / second barrier.  (C3 shape, whole transpose, one box: all
 // eight as one block before the ranking 2.16 ms, one per ranking step 2.04 ms, spread over the three
 // phases 1.93–1.97 ms with ≈2 % between the spreads tried; boxes differ by more than that.)
-#ifndef MI_TR_SLICE_PLAN
-#define MI_TR_SLICE_PLAN {0, 0, 3, 7, 9, 9, 10, 10}
-#endif
-#ifndef MI_TR_LB_SKEW
-#define MI_TR_LB_SKEW 0
-#endif
-#ifndef MI_TR_LB_EARLY  // 1: a tile's look-back loads are issued when it has been staged, 0: at the top of the next tile
-#define MI_TR_LB_EARLY 1
-#endif
-#ifndef MI_TR_ABL  // timing-only builds (tools/probes/tr_time.cpp): 1 = no global stores, 3 = no tile loads either
-#define MI_TR_ABL 0
-#endif
+// (the plan itself is slice_at's initialiser in the kernel)
 // LB = true: the one-sweep plan.  There is no scanned table; a tile's per-digit global offsets are found by decoupled
 // look-back inside its tile group (TR_LB_GROUPS contiguous groups per pass, each with a per-digit base from
 // tr_lb_setup_kernel).  Every digit of every tile has one 32-bit status word {flag, value} written with ONE agent-scope
@@ -929,11 +891,6 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
   auto fetch_slice = [&](int c) {
     int i = wave * (TR_TILE / TR_WAVES) + c * 64 + lane;
     i = i < n_len ? i : 0;
-    if (MI_TR_ABL & 2) {
-      rx[c] = (unsigned)(i * 2654435761u) >> 7;
-      ry[c] = 0;
-      return;
-    }
     if (FIRST) {
       rx[c] = (unsigned)a.col[n_start + i];
     } else {
@@ -947,22 +904,17 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
   auto fetch_values = [&](int c, long start, int len) {
     int i = wave * (TR_TILE / TR_WAVES) + c * 64 + lane;
     i = i < len ? i : 0;
-    if (MI_TR_ABL & 2) return;
     ry[c] = __builtin_bit_cast(unsigned, a.val[start + i]);
   };
   // slice k of the tile staged in LDS (length plen) leaves; with no such tile (plen = 0) to the dump slot
   int plen = 0;
   const int* gadj_out = gadj2;  // offsets of the tile that is streaming out
-  constexpr int slice_at[TR_PER] = MI_TR_SLICE_PLAN;
+  constexpr int slice_at[TR_PER] = {0, 0, 3, 7, 9, 9, 10, 10};
   auto store_slice = [&](int k) {
     const int i0 = k * TR_THREADS + tid;
     const int i = i0 < plen ? i0 : (plen > 0 ? plen - 1 : 0);
     const uint2 w = sorted[i];
     const long dst = (long)gadj_out[sorted_d[i] & mask] + i;
-    if (MI_TR_ABL & 1) {
-      asm volatile("" ::"v"(w.x), "v"(w.y), "v"(dst));
-      return;
-    }
     if (LAST) {
       int* pc = plen > 0 ? a.t_col + dst : reinterpret_cast<int*>(a.dump) + 4 * blockIdx.x;
       float* pv = plen > 0 ? a.t_val + dst : reinterpret_cast<float*>(a.dump) + 4 * blockIdx.x + 1;
@@ -1090,11 +1042,8 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
   int t = blockIdx.x, t_end = ntiles, t_step = gridDim.x;
   int cur_grp = 0, n1_tile = -1, n1_grp = 0;  // one-sweep last pass: the group of the tile in hand; the tile after it
   if (LB) {
-    // (MI_TR_LB_SKEW: the workgroups of a group start a fraction of a tile apart, ≈1.4 µs each, so that a tile's
-    // predecessors published their counts well before it looks back; measured: no gain — off.)
-#if MI_TR_LB_SKEW
-    for (int i = 0; i < (int)(blockIdx.x >> 5); ++i) __builtin_amdgcn_s_sleep(52);
-#endif
+    // (starting the workgroups of a group a fraction of a tile apart, ≈1.4 µs each, so that a tile's predecessors
+    // published their counts well before it looks back, measured no gain)
     if (tid == 0) {
       acquire_issue();
       acquire_finish(0);
@@ -1121,7 +1070,6 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
     t_end = (xcd + 1) * per < ntiles ? (xcd + 1) * per : ntiles;
     t_step = TR_GRID / 8;
   }
-  TR_STAMP_INIT;
   if (t < t_end) {
     fetch_meta(t);
 #pragma unroll
@@ -1135,27 +1083,21 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
     }
     asm volatile("" : "+v"(n_goff), "+v"(n_rp0), "+v"(n_rp1));
   }
-  static_assert(TR_PER == 8, "MI_TR_SLICE_PLAN places eight slices");
+  static_assert(TR_PER == 8, "slice_at places eight slices of the previous tile");
   static_assert(TR_GROUPS % 16 == 0, "tr_group_bases_kernel: sixteen waves share the groups");
   int tile_no = 0;
   for (; t < t_end && t >= 0;) {
     const int cur_len = n_len;  // block-uniform, ≥ 1: every tile below `ntiles` is in use
     const long start = n_start;
     const int row_lo = n_row_lo, row_hi = n_row_hi;
-    TR_STAMP(0);
     int* gadj = gadj2 + ((tile_no & 1) ? nb : 0);
     if (LB) {
       // (the staged tile's predecessors' words were requested when it was staged); the ticket after next
-#if !MI_TR_LB_EARLY
-      if (plen > 0) lookback_issue();
-#endif
       if (tid == 0 && n1_tile >= 0) acquire_issue();
     } else {
-#if MI_TR_INTERLEAVE
 #pragma unroll
       for (int k = 0; k < TR_PER; ++k)
         if (slice_at[k] == 0) store_slice(k);
-#endif
     }
     // every wave zeroes ITS counters (nobody else touches them between the prefix phase and here)
     for (int i = lane; i < nb / 2; i += 64) reinterpret_cast<unsigned*>(mycnt)[i] = 0u;
@@ -1178,7 +1120,6 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
     if (FIRST) __syncthreads();  // rows known
     const int next_tile = n1_tile, next_grp = n1_grp;
     if (LB && plen > 0) lookback_resolve(const_cast<int*>(gadj_out));  // the staged tile's offsets
-    TR_STAMP(7);
     Slot e[TR_PER];
 #pragma unroll
     for (int c = 0; c < TR_PER; ++c) {
@@ -1209,14 +1150,11 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
     const int goff = n_goff;
     const bool more = LB ? next_tile >= 0 : t + t_step < t_end;  // block-uniform
     if (more) fetch_meta(LB ? next_tile : t + t_step);
-    TR_STAMP(1);
     if (LB) {
       __syncthreads();  // the staged tile's offsets (gadj_out) are complete
-#if MI_TR_INTERLEAVE
 #pragma unroll
       for (int k = 0; k < TR_PER; ++k)
         if (slice_at[k] == 0) store_slice(k);
-#endif
     }
 
     // Rank inside the wave.  A lane's rank among equal digits = the wave's running count of the digit
@@ -1227,18 +1165,6 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
     // One ballot per COLLIDING digit value (≈2 per step for uniform digits) hands all its holders
     // their peer mask.  Stable (ranks follow lane order), no atomics.
     // Between the steps: one slice of the previous tile out, one slice of the next tile in.
-#if !MI_TR_INTERLEAVE
-    if (more) {
-#pragma unroll
-      for (int c = 0; c < TR_PER; ++c) fetch_slice(c);
-    }
-    if (FIRST) {
-#pragma unroll
-      for (int c = 0; c < TR_PER; ++c) fetch_values(c, start, cur_len);
-    }
-#pragma unroll
-    for (int c = 0; c < TR_PER; ++c) store_slice(c);
-#endif
 #pragma unroll
     for (int c = 0; c < TR_PER; ++c) {
       const int i = wave * (TR_TILE / TR_WAVES) + c * 64 + lane;
@@ -1267,17 +1193,13 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
       const int holders = __builtin_popcountll(peers);
       if (valid && below == 0) mycnt[d] = (unsigned short)(w0 + (holders > 1 ? holders : 1));
       e[c].d = d | ((w0 + (unsigned)below) << 16);
-#if MI_TR_INTERLEAVE
 #pragma unroll
       for (int k = 0; k < TR_PER; ++k)
         if (slice_at[k] == 1 + c) store_slice(k);
       if (more) fetch_slice(c);
       if (FIRST) fetch_values(c, start, cur_len);
-#endif
     }
-    TR_STAMP(2);
     __syncthreads();  // all counts in; every thread is past its reads of the previous tile's staging
-    TR_STAMP(3);
 
     // per digit: exclusive prefix over the waves (in place), tile total; then the exclusive scan of
     // the totals over the digits and the digit's global offset
@@ -1307,11 +1229,9 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
         if (lane >= s2) incl += v;
       }
       if (lane == 63) wsum[wave] = incl;
-#if MI_TR_INTERLEAVE
 #pragma unroll
       for (int k = 0; k < TR_PER; ++k)
         if (slice_at[k] == 9) store_slice(k);
-#endif
       __syncthreads();
       int wbase = 0;
 #pragma unroll
@@ -1324,15 +1244,12 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
         binstart[d] = bs;
         if (!LB) gadj[d] = goff - bs;
       }
-#if MI_TR_INTERLEAVE
 #pragma unroll
       for (int k = 0; k < TR_PER; ++k)
         if (slice_at[k] == 10) store_slice(k);
-#endif
       __syncthreads();
     }
 
-    TR_STAMP(4);
     // reorder the tile by digit in LDS; it streams out during the next tile's ranking
 #pragma unroll
     for (int c = 0; c < TR_PER; ++c) {
@@ -1349,9 +1266,7 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
     if (LB) {
       p_tile = t;
       p_grp = cur_grp;
-#if MI_TR_LB_EARLY
       lookback_issue();  // in flight across the barrier below and the top of the next tile
-#endif
       cur_grp = next_grp;
       t = next_tile;
       if (tid == 0) {
@@ -1366,27 +1281,21 @@ __global__ __launch_bounds__(TR_THREADS) void tr_scatter_staged_kernel(TrArgs a)
       t += t_step;
     }
     ++tile_no;
-    TR_STAMP(5);
     __syncthreads();  // the tile is staged (and, first pass: rowid may be refilled)
     if (LB) {
       n1_tile = __builtin_amdgcn_readfirstlane(s_next[0]);
       n1_grp = __builtin_amdgcn_readfirstlane(s_next[1]);
     }
-    TR_STAMP(6);
   }
   // the last tile of this workgroup
   if (plen > 0) {
     if (LB) {
-#if !MI_TR_LB_EARLY
-      lookback_issue();
-#endif
       lookback_resolve(const_cast<int*>(gadj_out));
       __syncthreads();
     }
 #pragma unroll
     for (int k = 0; k < TR_PER; ++k) store_slice(k);
   }
-  TR_STAMP_FLUSH(FIRST);
 }
 
 // Row offsets of Aᵀ, [batch][K+1] with global offsets, from the scanned tables (≤ 2 passes).
@@ -1811,16 +1720,6 @@ int mi_csr_transpose_check(const void* workspace, size_t workspace_bytes, int32_
   MI_HIP_TRY(hipStreamSynchronize(s));
   return flag == 0 ? MI_OK : MI_EHIP;
 }
-
-#ifdef MI_TR_ITEM_TIMING
-int mi_tr_item_stamps(unsigned long long* out8) {  // reads and clears the phase counters (synchronises the device)
-  MI_HIP_TRY(hipDeviceSynchronize());
-  MI_HIP_TRY(hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_tr_item_stamp), 8 * sizeof(unsigned long long)));
-  unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  MI_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_tr_item_stamp), zero, sizeof(zero)));
-  return MI_OK;
-}
-#endif
 
 int mi_csr_transpose_batched_in_lds(int64_t nnz, int32_t batch, int32_t M, int32_t K) {
   return g_tr_plan.load(std::memory_order_relaxed) == MI_TRANSPOSE_PLAN_AUTO && mi::tr_item_lds_waves(nnz, batch, M, K) > 0 ? 1 : 0;

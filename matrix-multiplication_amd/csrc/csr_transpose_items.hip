@@ -33,18 +33,6 @@ namespace {
 // loop below keeps busy enough
 __device__ __forceinline__ int wave_shr1(int x) { return __builtin_amdgcn_update_dpp(x, x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false); }
 
-#ifdef MI_TR_ITEM_TIMING  // developer probe (tools/probes/tr_item_timing.py): cycles per phase, summed over workgroups (thread 0)
-__device__ unsigned long long g_tr_item_stamp[8];
-#define TR_ITEM_STAMP(k)                                                                   \
-  do {                                                                                     \
-    const unsigned long long now_ = __builtin_readcyclecounter();                          \
-    if (threadIdx.x == 0) atomicAdd(&g_tr_item_stamp[k], now_ - stamp_);                   \
-    stamp_ = now_;                                                                         \
-  } while (0)
-#else
-#define TR_ITEM_STAMP(k) do {} while (0)
-#endif
-
 template <int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void tr_item_lds_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                                  const float* __restrict__ val, int M, int K,
@@ -71,9 +59,6 @@ __global__ __launch_bounds__(WAVES * 64) void tr_item_lds_kernel(const int* __re
   const int r0 = wave * rows_per_wave < M ? wave * rows_per_wave : M;
   const int r1 = r0 + rows_per_wave < M ? r0 + rows_per_wave : M;
   const int base = rp[0];
-#ifdef MI_TR_ITEM_TIMING
-  unsigned long long stamp_ = __builtin_readcyclecounter();
-#endif
   // The kernel is a chain of dependent trips to memory (row bounds → entries → … ) with the CU to itself, so the chain is
   // kept short: the wave's row bounds arrive as ONE vector load, the counting pass's entries and the first placement
   // group's entries are requested together right behind it.
@@ -116,7 +101,6 @@ __global__ __launch_bounds__(WAVES * 64) void tr_item_lds_kernel(const int* __re
   }
   for (int i = tid; i < WAVES * K; i += T) cnt[i] = 0;
   __syncthreads();
-  TR_ITEM_STAMP(0);  // bounds + first fetch issued, table zeroed
   int* mine = cnt + (long)wave * K;
   {  // (1) the wave's entries are contiguous: [rp[r0], rp[r1])
     const int e0 = bound(r0), e1 = bound(r1);
@@ -134,7 +118,6 @@ __global__ __launch_bounds__(WAVES * 64) void tr_item_lds_kernel(const int* __re
     }
   }
   __syncthreads();
-  TR_ITEM_STAMP(1);  // counted
   {  // (2) counters → cursors (positions relative to the item); a thread owns a contiguous range of columns
     const int cpt = (K + T - 1) / T;
     const int k_lo = tid * cpt < K ? tid * cpt : K, k_hi = k_lo + cpt < K ? k_lo + cpt : K;
@@ -176,7 +159,6 @@ __global__ __launch_bounds__(WAVES * 64) void tr_item_lds_kernel(const int* __re
     }
   }
   __syncthreads();
-  TR_ITEM_STAMP(2);  // cursors
   // (3) column passes: [ka, kb) = as many columns from ka on as fit the staging area (at least one); this workgroup
   // places pass number `seg` (and, if it is the last workgroup of the item, every pass behind it)
   int ka = 0, pass = 0;
@@ -259,7 +241,7 @@ __global__ __launch_bounds__(WAVES * 64) void tr_item_lds_kernel(const int* __re
             pos[u] = 0;
             // a plain read and a plain write (the lanes' words are distinct; the next row's read follows this row's write in
             // the wave's LDS order): a RETURNING LDS atomic measured ≈ 1 lane per cycle for the whole CU — 64 cycles per
-            // instruction, 33 k cycles per pass and workgroup, four fifths of the kernel (tools/probes/tr_item_timing.py)
+            // instruction, 33 k cycles per pass and workgroup, four fifths of the kernel (profiles/r05_transpose_item_lds_stamps.log)
             if (ok[u]) {
               pos[u] = mine[gq.c[u]];
               mine[gq.c[u]] = pos[u] + 1;
@@ -304,7 +286,6 @@ __global__ __launch_bounds__(WAVES * 64) void tr_item_lds_kernel(const int* __re
     }
     if (take && staged && pb > pa) {
       __syncthreads();  // the pass's entries are all staged
-      TR_ITEM_STAMP(3);  // placed
       // copy out: entries [pa, pb) of the item → t_col / t_val [base + pa, base + pb); 16-byte stores between aligned ends
       const int n = pb - pa;
       int* dc = t_col + base + pa - sh;    // 16-byte aligned; entry j of the staging area ↔ dc[j], j in [sh, sh + n)
@@ -333,7 +314,6 @@ __global__ __launch_bounds__(WAVES * 64) void tr_item_lds_kernel(const int* __re
         }
       }
       __syncthreads();  // the staging area is free for the next pass
-      TR_ITEM_STAMP(4);  // copied out
     }
     ka = kb;
     ++pass;

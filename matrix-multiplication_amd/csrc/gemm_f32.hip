@@ -42,23 +42,13 @@
 //
 // Translation units: the kernels of ONE transposition case are compiled per file (gemm_f32_nn.hip … _tt.hip define
 // MI_GEMM_TU_NAME / _TA / _TB and include this file: four parallel compiles instead of one 2½-minute one); this
-// file compiled on its own carries only the C-ABI entry points.  Developer probes that include it directly define
-// MI_GEMM_SINGLE_TU and get everything in one unit.
+// file compiled on its own carries only the C-ABI entry points.  A probe that includes it directly defines
+// MI_GEMM_SINGLE_TU and gets everything in one unit.  These are the file's only build switches: they arrange
+// translation units, and none selects a second code path.
 #include <atomic>
 #include <type_traits>
 
 #include "mi_common.h"
-
-#ifndef MI_GEMM_N16_ALL
-#define MI_GEMM_N16_ALL 0  // 1: the 16 × 16-block kernel for every 64 < n ≤ 96 (developer A/B; default: only where it computes fewer columns than the 96-wide tile, n ≤ 80)
-#endif
-#ifndef MI_GEMM_STORE_AUX
-#define MI_GEMM_STORE_AUX 2  // cache policy of the C stores: 2 = non-temporal, 0 = default (developer probes)
-#endif
-#ifndef MI_GEMM_ABL
-#define MI_GEMM_ABL 0  // developer probes only (tools/probes/*): 1 no C stores, 2 no MFMAs, 4 no operand loads; pipelined kernel also
-                       // 8 no LDS operand reads, 16 no LDS writes, 32 no barriers (timing only: wrong results)
-#endif
 
 #define MI_GEMM_TU_ARGS                                                                                              \
   const float *A, const float *B, float *C, int m, int n, int k, long lda, long ldb, long ldc, long sA, long sB, long sC, \
@@ -78,6 +68,7 @@ using mi::f32x4;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;
+constexpr int kStoreAux = 2;  // cache policy of the C stores: 2 = non-temporal (0 = default)
 
 // One operand's k-tile: EXT×BK elements (EXT = BM or BN), 256 threads.
 // KCONTIG: element (e, k) lives at src[e*ld + k]; else at src[k*ld + e].
@@ -312,7 +303,6 @@ __device__ __forceinline__ void gemm_epilogue_b(f32x16 (&acc)[TM][TN], float* __
           const long bytes = ((long)(m - row0 - 1) * ldc + (n - col0)) * 4;  // up to the last stored element of the block
           recs = (row0 >= m || col0 >= n) ? 0 : (bytes > 0x7fffffffL ? 0x7fffffff : (int)bytes);
         }
-        if ((MI_GEMM_ABL & 1) && MODE == 0) recs = 0;  // timing only: every store dropped by the range check
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc(C + (long)row0 * ldc + col0, 0, recs, 0x00020000);
         if (MODE == 0 || col < n) {
@@ -321,7 +311,7 @@ __device__ __forceinline__ void gemm_epilogue_b(f32x16 (&acc)[TM][TN], float* __
             float v = acc[i][j][r];
             if (HAS_BIAS) v += bv;  // after the chain: one extra rounding, like `output += bias` (never x + 0: keeps −0)
             const unsigned soff = (unsigned)((r & 3) + 8 * (r >> 2)) * c_row;
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, (int)c_lane, (int)soff, MI_GEMM_STORE_AUX /* nt */);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, (int)c_lane, (int)soff, kStoreAux);
           }
         }
       } else {
@@ -343,18 +333,8 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[TM][TN], float* __re
   else gemm_epilogue_b<BM, BN, TM, TN, MODE, false>(acc, C, m, n, ldc, m0, n0, wm, wn, lane, bias);
 }
 
-#ifdef MI_GEMM_TIMING
-__device__ unsigned long long g_gemm_phase[16];
-#define GEMM_STAMP(k) do { const unsigned long long now_ = __builtin_readcyclecounter(); if (tid == 0) atomicAdd(&g_gemm_phase[k], now_ - stamp_); stamp_ = now_; } while (0)
-#else
-#define GEMM_STAMP(k) do {} while (0)
-#endif
-
-#ifndef MI_GEMM_SHORTK_WAVES
-#define MI_GEMM_SHORTK_WAVES 3
-#endif
 template <int BM, int BN, bool TA, bool TB, bool ALIGNED>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MI_GEMM_SHORTK_WAVES, MI_GEMM_SHORTK_WAVES))) void gemm_f32_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void gemm_f32_kernel(
     const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C, int m, int n,
     int k, long lda, long ldb, long ldc, long strideA, long strideB, long strideC, int tiles_n,
     int tiles_per_item, bool vecA, bool vecB, bool vecC, const float* __restrict__ bias, int reverse) {
@@ -396,9 +376,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MI_GEMM_SHO
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-#ifdef MI_GEMM_TIMING
-  unsigned long long stamp_ = __builtin_readcyclecounter();
-#endif
   f32x4 ra[LA::VECS], rb[LB::VECS];
   const int l31 = lane & 31, lhi = lane >> 5;
   // Launch-uniform: operands whose rows are 16-byte aligned take unconditional buffer loads — on edge tiles too,
@@ -410,17 +387,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MI_GEMM_SHO
   // kernel's register count otherwise)
   // (round 5) rows off 16-byte boundaries take them too — dword-aligned 16-byte loads along k, clamped dword loads along
   // ext (TileLoader::load_clamped_dw) — as long as the 32-bit offsets hold (what vecA / vecB also stand for)
-#ifdef MI_GEMM_NO_UNALIGNED_FAST
-  const bool fast = ALIGNED || (vecA && vecB);
-#else
   const bool fast = ALIGNED || (lda < (1 << 21) && ldb < (1 << 21) && ldc < (1 << 24));
-#endif
   const bool whole = ALIGNED || (m0 + BM <= m && n0 + BN <= n);
-#ifndef MI_GEMM_KK_UNROLL
-#define MI_GEMM_KK_UNROLL 16
-#endif
   auto mfma_tile = [&]() {
-#pragma unroll MI_GEMM_KK_UNROLL
+#pragma unroll 16
     for (int kk = 0; kk < BK; kk += 2) {
       float a[TM], b[TN];
 #pragma unroll
@@ -432,7 +402,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MI_GEMM_SHO
 #pragma unroll
         for (int j = 0; j < TN; ++j)
           // accumulator block = C block: lane ↔ column n, registers ↔ rows (see gemm_epilogue)
-          if (!(MI_GEMM_ABL & 2)) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
     }
   };
   if (fast) {
@@ -448,7 +418,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MI_GEMM_SHO
       else LB::lane_offsets(b_off, ldb, tid, n - n0);
     }
     auto load_tile = [&](int k0) {  // k-tile starting at k0 < k
-      if (MI_GEMM_ABL & 4) return;
       if (ALIGNED) {
         LA::load_fast(ra, LA::origin(A, lda, m0, k0), lda, a_lane);
         LB::load_fast(rb, LB::origin(B, ldb, n0, k0), ldb, b_lane);
@@ -466,17 +435,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MI_GEMM_SHO
     for (int k0 = 0; k0 < k; k0 += BK) {
       LA::store(ra, As, tid);
       LB::store(rb, Bs, tid);
-      GEMM_STAMP(0);  // operand tile landed and written to LDS
       __syncthreads();
-      GEMM_STAMP(1);
       if (k0 + BK < k) load_tile(k0 + BK);
       // the loads stay in front of the MFMAs: hipcc otherwise sinks them (they feed nothing until the next
       // iteration) to the end of the tile, right in front of the waits on them — no prefetch left
       __builtin_amdgcn_sched_barrier(0);
       mfma_tile();
-      GEMM_STAMP(2);  // MFMAs of the tile issued
       __syncthreads();
-      GEMM_STAMP(3);
     }
   } else if (!ALIGNED) {
     LA::load(ra, A, lda, m0, 0, m, k, vecA, tid);
@@ -497,7 +462,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MI_GEMM_SHO
   if (ALIGNED || (fast && whole)) gemm_epilogue<BM, BN, TM, TN, 0>(acc, C, m, n, ldc, m0, n0, wm, wn, lane, bias);
   else if (fast) gemm_epilogue<BM, BN, TM, TN, 1>(acc, C, m, n, ldc, m0, n0, wm, wn, lane, bias);
   else gemm_epilogue<BM, BN, TM, TN, 2>(acc, C, m, n, ldc, m0, n0, wm, wn, lane, bias);
-  GEMM_STAMP(4);  // epilogue issued
 }
 
 // Pipelined form: two LDS buffers, ONE barrier per k-tile.  While the MFMAs of tile t run out of
@@ -563,7 +527,6 @@ __global__ __launch_bounds__(256) void gemm_f32_pipe_kernel(
     LB::lane_offsets(b_off, ldb, tid, n - n0);
     auto load_tile = [&](f32x4 (&ra)[LA::VECS], f32x4 (&rb)[LB::VECS], int k0) {
       const int kk = k0 < k_last ? k0 : k_last;
-      if (MI_GEMM_ABL & 4) return;
       // default cache policy: nt / sc loads measured 3-5 % slower here
       LA::load_clamped(ra, LA::origin(A, lda, m0, kk), a_off);
       LB::load_clamped(rb, LB::origin(B, ldb, n0, kk), b_off);
@@ -589,9 +552,9 @@ __global__ __launch_bounds__(256) void gemm_f32_pipe_kernel(
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
 #pragma unroll
-          for (int i = 0; i < TM; ++i) a[slot][h][i] = (MI_GEMM_ABL & 8) ? (float)(s + i) : LA::at(As, wm * (TM * 32) + i * 32 + l31, 4 * s + 2 * h + lhi);
+          for (int i = 0; i < TM; ++i) a[slot][h][i] = LA::at(As, wm * (TM * 32) + i * 32 + l31, 4 * s + 2 * h + lhi);
 #pragma unroll
-          for (int j = 0; j < TN; ++j) b[slot][h][j] = (MI_GEMM_ABL & 8) ? (float)(h + j) : LB::at(Bs, wn * (TN * 32) + j * 32 + l31, 4 * s + 2 * h + lhi);
+          for (int j = 0; j < TN; ++j) b[slot][h][j] = LB::at(Bs, wn * (TN * 32) + j * 32 + l31, 4 * s + 2 * h + lhi);
         }
       };
       read_batch(0, 0);
@@ -601,12 +564,8 @@ __global__ __launch_bounds__(256) void gemm_f32_pipe_kernel(
         if (s == 0) {
           // tile t+1: registers → the other buffer, whose last readers passed the previous
           // barrier.  After the last tile this writes a buffer nobody reads.
-          if (!(MI_GEMM_ABL & 16)) {
-            LA::store(ra, An, tid);
-            LB::store(rb, Bn, tid);
-          } else {
-            asm volatile("" :: "v"(ra[0]), "v"(rb[0]));  // keeps the loads live
-          }
+          LA::store(ra, An, tid);
+          LB::store(rb, Bn, tid);
         }
         if (s == 1) load_tile(ra, rb, k0 + 3 * BK);
 #pragma unroll
@@ -615,7 +574,7 @@ __global__ __launch_bounds__(256) void gemm_f32_pipe_kernel(
           for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < TN; ++j)
-              if (!(MI_GEMM_ABL & 2)) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s & 1][h][i], b[s & 1][h][j], acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s & 1][h][i], b[s & 1][h][j], acc[i][j], 0, 0, 0);
         // Fence the scheduler per batch: hipcc otherwise sinks the operand reads next to their
         // use and the global loads to the end of the tile (right in front of the waits on them).
         if (s == 0) {
@@ -636,7 +595,7 @@ __global__ __launch_bounds__(256) void gemm_f32_pipe_kernel(
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (!(MI_GEMM_ABL & 32)) __syncthreads();
+      __syncthreads();
     };
     for (int k0 = 0; k0 < k; k0 += 2 * BK) {
       k_tile(k0, 0, ra1, rb1);                        // even tile: tile t+1 is odd → set 1
@@ -682,7 +641,7 @@ __global__ __launch_bounds__(256) void gemm_f32_pipe_kernel(
 // CHAIN·g + CHAIN − 1), so that a tile's epilogue — 16 dword buffer stores per 32×32 block, straight from the
 // accumulator registers — is issued between the MFMAs of the NEXT tile instead of after its own.  With k = 64 a
 // wave has only 128 MFMAs per tile; in the one-tile kernel their 0.082 ms of matrix-pipe time and the staging +
-// epilogue skeleton simply add up (tools/probes/gemm_probe.cpp), because co-resident workgroups run in step.
+// epilogue skeleton simply add up (profiles/r02_gemm_ablation.log), because co-resident workgroups run in step.
 // Here the skeleton of tile T rides inside tile T + 1's MFMA stream of the SAME wave (two accumulator sets), and
 // the chain's stages form one prefetch chain through two LDS buffers (the next tile's first operands are
 // requested during this tile's last MFMAs).  Same k order per element as every other kernel here → same bits.
@@ -740,15 +699,13 @@ __global__ __launch_bounds__(256) void gemm_f32_pair_kernel(
     constexpr int q = P / 2, h = P % 2, i = q / TN, j = q % TN, SET = T % 2;
     const int col0 = (CHAIN * group_n + T) * BN + wn * (BN / 2) + j * 32;  // uniform
     const int row0 = m0 + wm * (BM / 2) + i * 32;
-    // (MI_GEMM_ABL & 1, timing only: a descriptor of zero records — the range check drops every store, the instruction
-    // stream stays as it is)
     const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(C + (long)row0 * ldc + col0, 0, (MI_GEMM_ABL & 1) ? 0 : 0x7fffffff, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(C + (long)row0 * ldc + col0, 0, 0x7fffffff, 0x00020000);
 #pragma unroll
     for (int r = 8 * h; r < 8 * h + 8; ++r) {
       const float v = acc[SET][i][j][r];
       const unsigned soff = (unsigned)((r & 3) + 8 * (r >> 2)) * c_row;
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, (int)c_lane, (int)soff, MI_GEMM_STORE_AUX /* nt */);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, (int)c_lane, (int)soff, kStoreAux);
     }
   };
 
@@ -807,9 +764,7 @@ __global__ __launch_bounds__(256) void gemm_f32_pair_kernel(
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          if (MI_GEMM_ABL & 2) {
-            if (KT == 0 && S == 0) acc[SET][i][j] = zero16;
-          } else if constexpr (KT == 0 && S == 0) {
+          if constexpr (KT == 0 && S == 0) {
             // a tile's first product starts its accumulators (set reused from tile T − 2) from zero
             acc[SET][i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[S & 1][i], b[S & 1][j], zero16, 0, 0, 0);
           } else {
@@ -838,13 +793,8 @@ __global__ __launch_bounds__(256) void gemm_f32_pair_kernel(
 // (D = Bᵀ-block × A-block), so a lane's four accumulator registers are four consecutive n: 16-byte stores.
 // Whole tiles only (m, n multiples of 96, k of 64, 16-byte aligned rows): pick_tile() checks.
 // ---------------------------------------------------------------------------------------------
-#ifndef MI_GEMM_T16_KC
-#define MI_GEMM_T16_KC 32
-#endif
-constexpr int T16_KC = MI_GEMM_T16_KC;
-#ifndef MI_GEMM_T16_WAVES
-#define MI_GEMM_T16_WAVES 12  // waves per workgroup of the 96×96 tile (4: one wave per SIMD, 0.75 ms at the BERT-base shape)
-#endif
+constexpr int T16_KC = 32;     // k rows per chunk
+constexpr int T16_WAVES = 12;  // waves per workgroup of the 96×96 tile (4: one wave per SIMD, 0.75 ms at the BERT-base shape)
 
 // TILE × TILE outputs per workgroup, 16×16 MFMA blocks dealt to WAVES waves so that every SIMD holds 2–4 waves:
 //   TILE 128, 16 waves: 32×32 (2×2 blocks) per wave — level with the 32×32-block kernels at 4096 × 1024 / 2048²
@@ -912,10 +862,6 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_f32_t16_tn_kernel(
     const __amdgpu_buffer_rsrc_t rb_src = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Bp + (long)k0 * ldb), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
     for (int i = 0; i < VECS; ++i) {
-      if (MI_GEMM_ABL & 4) {
-        ra[set][i] = rb[set][i] = f32x4{1.f, 2.f, 3.f, (float)k0};
-        continue;
-      }
       ra[set][i] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(ra_src, (int)a_lane, (int)(i * a_step), 0));
       rb[set][i] = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rb_src, (int)b_lane, (int)(i * b_step), 0));
     }
@@ -936,20 +882,12 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_f32_t16_tn_kernel(
   auto read_ops = [&](int set, int buf, int kk) {
     const float* as = &lds[buf][0][(kk * 4 + lk) * LD + m_w + lc];
     const float* bs = &lds[buf][1][(kk * 4 + lk) * LD + n_w + lc];
-    if (MI_GEMM_ABL & 8) {  // timing only: no LDS operand reads
-#pragma unroll
-      for (int i = 0; i < MB; ++i) a[set][i] = (float)(kk + i);
-#pragma unroll
-      for (int i = 0; i < NB; ++i) b[set][i] = (float)(set + i);
-      return;
-    }
 #pragma unroll
     for (int i = 0; i < MB; ++i) a[set][i] = as[16 * i];
 #pragma unroll
     for (int i = 0; i < NB; ++i) b[set][i] = bs[16 * i];
   };
   auto mfmas = [&](int set) {
-    if (MI_GEMM_ABL & 2) return;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -985,7 +923,6 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_f32_t16_tn_kernel(
     half(0, c + 2, 0, 1);                // halves lets the compiler sink the first half's loads past it)
     half(1, c + 3, 1, 0);
   }
-  if (MI_GEMM_ABL & 1) return;
   float* Cp = C + item * strideC + ((long)tile_m * TILE + m_w + lc) * ldc + (long)tile_n * TILE + n_w + 4 * lk;
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
@@ -1148,11 +1085,7 @@ int launch_n16(const float* A, const float* B, float* C, int m, int n, int k, lo
   } while (0)
   if (nb == 4) MI_N16(4);
   else if (nb == 5) MI_N16(5);
-#if MI_GEMM_N16_ALL
-  else MI_N16(6);
-#else
   else return MI_EINVAL;  // (88 / 96 columns run the 96-wide tile of 32 × 32 blocks: pick_tile)
-#endif
 #undef MI_N16
   return mi::check_launch();
 }
@@ -1170,6 +1103,9 @@ int launch_t16(const float* A, const float* B, float* C, int m, int n, int k, lo
   return mi::check_launch();
 }
 
+// long k: the pipelined kernel (its prologue and double LDS buffer pay off from ≈8 k-tiles);
+// short k (BERT q·kᵀ, k = 64): the single-buffer kernel, which keeps 3–4 workgroups per CU
+constexpr int kPipeMinTiles = 8;
 
 template <int BM, int BN, bool TA, bool TB>
 int launch(const float* A, const float* B, float* C, int m, int n, int k, long lda, long ldb,
@@ -1183,38 +1119,22 @@ int launch(const float* A, const float* B, float* C, int m, int n, int k, long l
   // upstream gradient: 403 MB of dScores at BERT-base attention, more than the 256 MiB Infinity Cache)
   // then meet its most recently read half still in the cache instead of evicting it in lock step.
   // Tile order never affects values.
-#ifdef MI_GEMM_NO_REVERSE
-  const int rev = 0;
-#else
   const int rev = (int)(mi::g_gemm_launch_counter.fetch_add(1, std::memory_order_relaxed) & 1u);
-#endif
-  // long k: the pipelined kernel (its prologue and double LDS buffer pay off from ≈8 k-tiles);
-  // short k (BERT q·kᵀ, k = 64): the single-buffer kernel, which keeps 3–4 workgroups per CU
-#ifndef MI_GEMM_PIPE_MIN_TILES
-#define MI_GEMM_PIPE_MIN_TILES 8  // developer probes may override
-#endif
   // (the pipelined kernel's fast loop wants whole k-tiles and 16-byte aligned rows; a long k that is ragged or unaligned —
   // 577 tokens — is better off in the single-buffer kernel, whose whole k-tiles take unconditional loads whatever the
   // alignment and only the ragged last one the bounds-checked loader, than in the pipelined kernel's bounds-checked loop)
-#ifdef MI_GEMM_NO_RAGGED_SHORTK
-  const bool pipe_ok = true;
-#else
   const bool pipe_ok = (vecA && vecB && k % BK == 0) || !(lda < (1 << 21) && ldb < (1 << 21) && ldc < (1 << 24));
-#endif
-  if (k >= MI_GEMM_PIPE_MIN_TILES * BK && pipe_ok)
+  if (k >= kPipeMinTiles * BK && pipe_ok)
     hipLaunchKernelGGL((gemm_f32_pipe_kernel<BM, BN, TA, TB>), dim3((unsigned)blocks), dim3(256), 0, s, A, B, C, m,
                        n, k, lda, ldb, ldc, sA, sB, sC, (int)tiles_n, (int)(tiles_m * tiles_n), vecA, vecB, vecC,
                        bias, rev);
   else if (vecA && vecB && vecC && m % BM == 0 && n % BN == 0 && k % BK == 0) {
-#ifndef MI_GEMM_NO_PAIR
-#ifndef MI_GEMM_CHAIN_MAX
-#define MI_GEMM_CHAIN_MAX 4
-#endif
+    constexpr int kChainMax = 4;  // longest chain of output tiles per workgroup
     if (BM == 128 && BN == 128 && (tiles_n % 2 == 0 || tiles_n % 3 == 0) && (k == BK || k == 2 * BK || k == 4 * BK) &&
         bias == nullptr) {
       // CHAIN output tiles of one tile row per workgroup, each tile's epilogue inside the next one's MFMAs
       // (three for tile rows of 3, 9, 15 … tiles: 384 tokens, BERT's SQuAD length)
-      const int chain = (tiles_n % 4 == 0 && MI_GEMM_CHAIN_MAX >= 4) ? 4 : (tiles_n % 2 == 0 ? 2 : 3);
+      const int chain = (tiles_n % 4 == 0 && kChainMax >= 4) ? 4 : (tiles_n % 2 == 0 ? 2 : 3);
       const unsigned gblocks = (unsigned)(blocks / chain);
       const int gn = (int)(tiles_n / chain), gpi = (int)(tiles_m * tiles_n / chain);
 #define MI_PAIR(NK_, CH_)                                                                                         \
@@ -1236,7 +1156,6 @@ int launch(const float* A, const float* B, float* C, int m, int n, int k, long l
 #undef MI_PAIR
       return mi::check_launch();
     }
-#endif
     hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, TA, TB, true>), dim3((unsigned)blocks), dim3(256), 0, s, A, B, C, m, n, k,
                        lda, ldb, ldc, sA, sB, sC, (int)tiles_n, (int)(tiles_m * tiles_n), vecA, vecB, vecC, bias, rev);
   }
@@ -1271,7 +1190,6 @@ int pick_tile(const float* A, const float* B, float* C, int m, int n, int k, lon
   // than leave CUs idle — the k order per element is the same for every tile shape.
   auto blocks_for = [&](int bm, int bn) { return (long)((m + bm - 1) / bm) * ((n + bn - 1) / bn) * batch; };
   const long want = 2L * 256;
-#ifndef MI_GEMM_NO_T16
   if (TA && !TB && bias == nullptr && vecA && vecB && vecC && k % (2 * T16_KC) == 0 && k >= 16 * T16_KC &&
       blocks_for(128, 128) < want) {
     // Aᵀ·B with few output tiles and a long k (weight gradients): tiles of 16×16 MFMA blocks, one workgroup per CU
@@ -1287,32 +1205,22 @@ int pick_tile(const float* A, const float* B, float* C, int m, int n, int k, lon
       if (eff > best_eff + 1e-9) best_eff = eff, best = tile;
     }
     if (m % 32 == 0 && n % 32 == 0 && blocks_for(64, 64) <= 64) best = 32, best_eff = 1.0;  // a tiny output: most workgroups win
-#ifndef MI_GEMM_T16_MIN_EFF
-#define MI_GEMM_T16_MIN_EFF 0.75
-#endif
+    constexpr double kT16MinEff = 0.75;  // least share of the CUs' rounds that a tile size has to fill
     // neither 96- nor 64-tiles fill the CUs' rounds (768², 1536 × 768, 1152² outputs: 0.56–0.63): 32×32 tiles give every
     // SIMD two to five one-block waves instead (round 3, tools/probes/duo_probe.cpp gw*: 768² × 16384 0.287 → 0.261 ms,
     // 1536 × 768 × 8192 0.264 → 0.216, 1152² × 8192 0.267 → 0.249; where 64-tiles give exactly one workgroup per CU they
     // stay ahead: 2048 × 512 × 8192 0.164 vs 0.188)
-    if (best_eff < MI_GEMM_T16_MIN_EFF && m % 32 == 0 && n % 32 == 0 && blocks_for(32, 32) >= 256 && blocks_for(64, 64) <= 512)
+    if (best_eff < kT16MinEff && m % 32 == 0 && n % 32 == 0 && blocks_for(32, 32) >= 256 && blocks_for(64, 64) <= 512)
       best = 32, best_eff = 1.0;
-    if (best_eff >= MI_GEMM_T16_MIN_EFF) {
+    if (best_eff >= kT16MinEff) {
       const int rev = (int)(mi::g_gemm_launch_counter.fetch_add(1, std::memory_order_relaxed) & 1u);
-      if (best == 96) return launch_t16<96, MI_GEMM_T16_WAVES>(A, B, C, m, n, k, lda, ldb, ldc, sA, sB, sC, batch, rev, s);
+      if (best == 96) return launch_t16<96, T16_WAVES>(A, B, C, m, n, k, lda, ldb, ldc, sA, sB, sC, batch, rev, s);
       if (best == 32) return launch_t16<32, 4>(A, B, C, m, n, k, lda, ldb, ldc, sA, sB, sC, batch, rev, s);
       return launch_t16<64, 8>(A, B, C, m, n, k, lda, ldb, ldc, sA, sB, sC, batch, rev, s);
     }
   }
-#endif
 #define MI_TILE(BM_, BN_) \
   return launch<BM_, BN_, TA, TB>(A, B, C, m, n, k, lda, ldb, ldc, sA, sB, sC, batch, vecA, vecB, vecC, bias, s)
-#ifdef MI_GEMM_FORCE_TILE  // developer probes only
-  if (MI_GEMM_FORCE_TILE == 1) MI_TILE(128, 128);
-  if (MI_GEMM_FORCE_TILE == 2) MI_TILE(128, 64);
-  if (MI_GEMM_FORCE_TILE == 3) MI_TILE(64, 128);
-  if (MI_GEMM_FORCE_TILE == 4) MI_TILE(64, 64);
-#endif
-#ifndef MI_GEMM_NO_N16
   // n = 64 with a LONG k (probs·V / Pᵀ·dC over 2048 tokens): the 16 × 16-block kernel's 128 × 64 tile — 8 waves of 16 rows,
   // two workgroups per CU — is ahead of the 2 × 2-wave tile of 32 × 32 blocks there (48 × 2048² × 64: 0.2375 → 0.219 ms,
   // torch 0.2305; at k = 512 / 1024 the 32 × 32 tiles stay ahead or level: tools/probes/gemm_n64_ab.py)
@@ -1320,21 +1228,16 @@ int pick_tile(const float* A, const float* B, float* C, int m, int n, int k, lon
     if (n == 64 && k >= 2048 && m % 128 == 0 && k % 64 == 0 && vecA && vecB && vecC && bias == nullptr && blocks_for(128, 64) >= 256)
       return launch_n16<TA, TB>(A, B, C, m, n, k, lda, ldb, ldc, sA, sB, sC, batch, s);
   }
-#endif
-#ifndef MI_GEMM_NO_N96
-  if (n > 64 && n <= 96 && m > 64 && k >= MI_GEMM_PIPE_MIN_TILES * BK && vecA && vecB && k % BK == 0 && blocks_for(128, 96) >= 256) {
-#ifndef MI_GEMM_NO_N16
+  if (n > 64 && n <= 96 && m > 64 && k >= kPipeMinTiles * BK && vecA && vecB && k % BK == 0 && blocks_for(128, 96) >= 256) {
     // exact 80- / 96-column tiles of 16 × 16 blocks where the shape is made of whole 128-row tiles (probs·V, Pᵀ·dC)
     if constexpr (!TB) {
       // (n ≤ 80: 384 × 512 × 80 probs·V 0.151 → 0.135 ms, × 72 0.159 → 0.142; at 88 / 96 columns the 96-wide tile of 32 × 32 blocks
       // is ahead: 0.153 vs 0.162 ms)
-      if (bias == nullptr && vecC && m % 128 == 0 && k % 64 == 0 && n % 4 == 0 && (n <= 80 || MI_GEMM_N16_ALL))
+      if (bias == nullptr && vecC && m % 128 == 0 && k % 64 == 0 && n % 4 == 0 && n <= 80)
         return launch_n16<TA, TB>(A, B, C, m, n, k, lda, ldb, ldc, sA, sB, sC, batch, s);
     }
-#endif
     return launch_n96<TA, TB>(A, B, C, m, n, k, lda, ldb, ldc, sA, sB, sC, batch, vecA, vecB, vecC, bias, s);
   }
-#endif
   if (m > 64 && n > 64 && blocks_for(128, 128) >= want) MI_TILE(128, 128);
   if (m > 64 && blocks_for(128, 64) >= want) MI_TILE(128, 64);
   if (n > 64 && blocks_for(64, 128) >= want) MI_TILE(64, 128);

@@ -38,25 +38,6 @@
 
 #include "mi_common.h"
 
-#ifndef MI_DUO_ABL
-#define MI_DUO_ABL 0  // developer probes only: 1 no C stores, 2 no MFMAs, 4 no operand loads
-#endif
-#ifndef MI_DUO_STAGE_PRIO
-#define MI_DUO_STAGE_PRIO 2  // wave priority during a stage interval (the multiplying partner runs at 0)
-#endif
-#ifndef MI_DUO_DYNAMIC_ROLES
-#define MI_DUO_DYNAMIC_ROLES 1  // 0: half = wave index / 4 (developer probes)
-#endif
-
-#ifdef MI_DUO_TIMING  // developer probes only: cycle stamps of the first events of every wave, kept in LDS (no
-                       // vector-memory operations of their own) and copied out at the end
-__device__ unsigned long long g_duo_stamps[256][8][64];
-__device__ unsigned long long g_duo_real[256][2];
-#define DUO_STAMP() do { if (lane == 0 && stamp_i_ < 64) stamp_lds_[(tid >> 6) * 64 + stamp_i_] = __builtin_amdgcn_s_memtime(); if (tid == 0 && stamp_i_ == 43) g_duo_real[blockIdx.x & 255][1] = __builtin_amdgcn_s_memrealtime(); ++stamp_i_; } while (0)
-#else
-#define DUO_STAMP() do {} while (0)
-#endif
-
 namespace {
 
 using mi::f32x4;
@@ -100,12 +81,8 @@ struct DuoOperand {
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(tile), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
     for (int v = 0; v < VECS; ++v) {
-      if (MI_DUO_ABL & 4) {
-        r[v] = f32x4{1.f, 2.f, 3.f, (float)off};
-      } else {
-        const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, (int)(v * row_step_bytes), 0);
-        r[v] = __builtin_bit_cast(f32x4, x);
-      }
+      const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off, (int)(v * row_step_bytes), 0);
+      r[v] = __builtin_bit_cast(f32x4, x);
     }
   }
 
@@ -153,7 +130,6 @@ __global__ __launch_bounds__(512) void gemm_f32_duo_kernel(const float* __restri
   // rank among the workgroup's waves on that SIMD (an LDS counter per SIMD).  If a placement other than two waves
   // per SIMD ever shows up, every wave falls back to the static roles (correct either way; speed only).
   int half = tid >> 8, wave = (tid >> 6) & 3;
-#if MI_DUO_DYNAMIC_ROLES
   {
     int* cnt = reinterpret_cast<int*>(duo_lds);
     const int simd = (int)((__builtin_amdgcn_s_getreg((2 - 1) << 11 | 4 << 6 | 4)) & 3);  // HW_ID[5:4]
@@ -166,7 +142,6 @@ __global__ __launch_bounds__(512) void gemm_f32_duo_kernel(const float* __restri
     __syncthreads();  // the counters sit where the operand buffers are about to go
     if (two_each) half = __builtin_amdgcn_readfirstlane(rank), wave = simd;
   }
-#endif
   half = __builtin_amdgcn_readfirstlane(half);
   wave = __builtin_amdgcn_readfirstlane(wave);
   const int th = wave * 64 + lane;  // thread id inside the half
@@ -222,9 +197,7 @@ __global__ __launch_bounds__(512) void gemm_f32_duo_kernel(const float* __restri
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int j = 0; j < TN; ++j) {
-            if (MI_DUO_ABL & 2) {
-              if (FIRST && g == 0 && c == 0) acc[i][j] = zero16;
-            } else if (FIRST && g == 0 && c == 0) {
+            if (FIRST && g == 0 && c == 0) {
               acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g & 1][i][c], b[g & 1][j][c], zero16, 0, 0, 0);
             } else {
               acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g & 1][i][c], b[g & 1][j][c], acc[i][j], 0, 0, 0);
@@ -252,22 +225,12 @@ __global__ __launch_bounds__(512) void gemm_f32_duo_kernel(const float* __restri
           float v = acc[i][j][r];
           if (HAS_BIAS) v += bv;  // after the chain: one extra rounding, as `output += bias` (and never x + 0: keeps −0)
           const unsigned soff = (unsigned)((r & 3) + 8 * (r >> 2)) * c_row;  // 16 scalar row offsets, shared by every block
-          if (MI_DUO_ABL & 1) {
-            if (v == 12345.678f) c0[(long)(i * 32) * ldc + soff / 4 + c_off / 4 + j * 32] = v;  // keeps the accumulators live
-          } else {
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, (int)(c_off + j * 128), (int)soff, 2 /* nt */);
-          }
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsrc, (int)(c_off + j * 128), (int)soff, 2 /* nt */);
         }
       }
     }
   };
 
-#ifdef MI_DUO_TIMING
-  int stamp_i_ = 0;
-  unsigned long long* stamp_lds_ = reinterpret_cast<unsigned long long*>(duo_lds + 2 * (LA::FLOATS + LB::FLOATS));
-  if (tid == 0) g_duo_real[blockIdx.x & 255][0] = __builtin_amdgcn_s_memrealtime();
-#endif
-  DUO_STAMP();
   if (t_begin + half < t_end) issue_loads(t_begin + half, 0);
   if (half == 1) __syncthreads();  // the stagger: half 1 runs one barrier behind half 0
   for (int ti = 0; ti < steps; ++ti) {
@@ -278,7 +241,7 @@ __global__ __launch_bounds__(512) void gemm_f32_duo_kernel(const float* __restri
       // the previous tile's stores: vmcnt retires in order, so with the stores in front the wait for the operand
       // registers would also wait for a store issued a moment ago (a full write round trip: measured 11 k cycles
       // per stage); behind the loads they have a whole period to drain before anything waits on them
-      __builtin_amdgcn_s_setprio(MI_DUO_STAGE_PRIO);
+      __builtin_amdgcn_s_setprio(2);  // a stage interval runs above the multiplying partner, which runs at 0
       if (valid) {
         LA::store(ra, a_lds);
         LB::store(rb, b_lds);
@@ -286,28 +249,20 @@ __global__ __launch_bounds__(512) void gemm_f32_duo_kernel(const float* __restri
         else if (t + 2 < t_end) issue_loads(t + 2, 0);
       }
       if (kt == 0 && ti > 0) epilogue(t - 2);  // (t − 2 is always a tile of this range)
-      DUO_STAMP();  // staged, loads issued
       __builtin_amdgcn_s_setprio(0);
       __syncthreads();
-      DUO_STAMP();  // MFMA interval begins
       // ---- MFMA interval (the other half stages)
       if (valid) {
         if (kt == 0) mfma_phase(std::true_type{});
         else mfma_phase(std::false_type{});
       }
-      DUO_STAMP();  // MFMAs issued
       if (!(half == 1 && ti == steps - 1 && kt == nk - 1)) __syncthreads();  // half 1 entered one barrier late
-      DUO_STAMP();  // stage interval begins
     }
   }
   {
     const int t_last = t_begin + 2 * (steps - 1) + half;  // the last tile's stores have nothing left to hide behind
     if (t_last < t_end) epilogue(t_last);  // (a half that owns one tile fewer stored its last one in the empty step's stage)
   }
-#ifdef MI_DUO_TIMING
-  if (lane == 0) for (int e = 0; e < 64; ++e) g_duo_stamps[blockIdx.x & 255][tid >> 6][e] = stamp_lds_[(tid >> 6) * 64 + e];
-#endif
-
 }
 
 template <int BN, bool AK, bool BKC, bool HAS_BIAS>
@@ -315,11 +270,7 @@ int launch_duo_b(const float* A, const float* B, float* C, int m, int n, int k, 
                long sB, long sC, int batch, const float* bias, hipStream_t s, int cu_count) {
   typedef DuoOperand<DBM, AK> LA;
   typedef DuoOperand<BN, BKC> LB;
-#ifdef MI_DUO_TIMING
-  constexpr int lds_bytes = 2 * (LA::FLOATS + LB::FLOATS) * (int)sizeof(float) + 8 * 64 * 8;
-#else
   constexpr int lds_bytes = 2 * (LA::FLOATS + LB::FLOATS) * (int)sizeof(float);
-#endif
   static_assert(lds_bytes <= 160 * 1024, "two halves' operand buffers must fit one CU's LDS");
   auto kern = gemm_f32_duo_kernel<BN, AK, BKC, HAS_BIAS>;
   // (per device and cheap: set on every launch rather than remembered per process)

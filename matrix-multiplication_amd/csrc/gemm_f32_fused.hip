@@ -26,7 +26,7 @@
 // half of the same item — runs on the same XCD right behind the first and finds it in that L2).
 // Waves w and w + 4 share a SIMD (MI355X_MICROARCH.md § LDS: a workgroup's waves go to the SIMDs in a cyclic order), which
 // is all the role assignment relies on, for speed only.
-// History at the C5 shape (tools/bench_fused_pair.py + MI_FUSED_ABL; the two plain products: 0.243 ms): 16 waves, C2 over
+// History at the C5 shape (tools/bench_fused_pair.py; the two plain products: 0.243 ms): 16 waves, C2 over
 // eight of them, six loader waves on the C1 SIMDs, one chunk of look-ahead, a run-time k loop 0.378 ms (the compiler
 // drained the LDS queue before every batch of MFMAs, spilled 25 registers per lane into the chunk loop, the loaders'
 // integer divisions sat on the C1 chains' SIMDs); 8 waves, templated k, 16-row chunks with B1 in LDS 0.236 ms (compute
@@ -43,12 +43,6 @@ constexpr int FN = 32;        // columns of n per unit
 constexpr int FPAD = 4;       // floats of padding per chunk row: 16-byte aligned rows, conflict-free C1 operand reads
 constexpr int FTHREADS = 512;
 constexpr int FLOADERS = 256;
-#ifndef MI_FUSED_BAHEAD  // batches of eight k-steps by which the B1 operand loads run ahead of their MFMAs
-#define MI_FUSED_BAHEAD 2
-#endif
-#ifndef MI_FUSED_ABL  // timing-only builds (tools/bench_fused_pair.py): 1 no C1 chains, 2 no C2 tiles, 4 no chunk loads / LDS writes
-#define MI_FUSED_ABL 0
-#endif
 
 template <int KT>  // k = 64 · KT
 __global__ __launch_bounds__(FTHREADS) void gemm_pair_a_at_kernel(const float* __restrict__ A, const float* __restrict__ B1,
@@ -115,15 +109,11 @@ __global__ __launch_bounds__(FTHREADS) void gemm_pair_a_at_kernel(const float* _
     load_chunk(0, 2);
     __syncthreads();
     for (int c = 0; c < chunks; c += 2) {  // (chunks is even: two chunk steps per trip keep the register sets static)
-      if (!(MI_FUSED_ABL & 4)) {
-        store_chunk(1, 1);  // chunk c + 1
-        load_chunk(1, c + 3);
-      }
+      store_chunk(1, 1);  // chunk c + 1
+      load_chunk(1, c + 3);
       __syncthreads();
-      if (!(MI_FUSED_ABL & 4)) {
-        store_chunk(0, 0);  // chunk c + 2
-        load_chunk(0, c + 4);
-      }
+      store_chunk(0, 0);  // chunk c + 2
+      load_chunk(0, c + 4);
       __syncthreads();
     }
     return;
@@ -132,67 +122,56 @@ __global__ __launch_bounds__(FTHREADS) void gemm_pair_a_at_kernel(const float* _
   if (wave < 2) {
     // ---- C1: the chunk's 32 rows × 16 columns (16·wave …): two chains of k/4 MFMAs, interleaved, sharing B1's operand ----
     __syncthreads();
-    // B1 element (k-step s, lane): row 4s + lk, column 16·wave + lc of the unit's half: buffer loads with a loop-invariant
-    // lane offset and a compile-time step (n = 64) — no vector-ALU instruction beside the MFMAs
-    const __amdgpu_buffer_rsrc_t b1_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(B1i), 0, 0x7fffffff, 0x00020000);
+    // B1 element (k-step s, lane): row 4s + lk, column 16·wave + lc of the unit's half: a loop-invariant lane offset and
+    // a compile-time step (n = 64) — no vector-ALU instruction beside the MFMAs
     const int b1_lane = (lk * (2 * FN) + 16 * wave + lc) * 4;
     constexpr int b1_step = 4 * (2 * FN) * 4;  // bytes per k-step
     // (plain global loads: B1's operands do not depend on the chunk, so the compiler hoists ALL of them out of the chunk
     // loop — the strip's k × 16 values sit in 128 registers for the whole unit and no chunk re-reads them; buffer loads
     // are not hoisted and measured 0.28 ms against 0.225, a uniform base + 32-bit lane offset 0.243)
-#ifndef MI_FUSED_B1BUF
-#define MI_FUSED_B1BUF 0
-#endif
     const float* const b1_ptr = reinterpret_cast<const float*>(reinterpret_cast<const char*>(B1i) + b1_lane);
-    const unsigned b1_lane_elems = (unsigned)b1_lane / 4u;
-    auto b1_load = [&](int step) {
-      if (MI_FUSED_B1BUF == 1) return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b1_rsrc, b1_lane, step * b1_step, 0));
-      if (MI_FUSED_B1BUF == 2) return (B1i + step * (b1_step / 4))[b1_lane_elems];  // scalar base + lane offset: no VALU per load
-      return b1_ptr[step * (b1_step / 4)];
-    };
+    auto b1_load = [&](int step) { return b1_ptr[step * (b1_step / 4)]; };
     for (int c = 0; c < chunks; ++c) {
-      if (!(MI_FUSED_ABL & 1)) {
-        const float* ap = as + ((c & 1) * FR + lc) * ld + lk;
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        constexpr int UB = 8, NB = k / 4 / UB;  // batches of eight k-steps
-        constexpr int BA = MI_FUSED_BAHEAD;
-        float a0[2][UB], a1[2][UB], bv[BA + 1][UB];  // A one batch ahead (LDS), B1 BA batches ahead (L2)
+      const float* ap = as + ((c & 1) * FR + lc) * ld + lk;
+      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+      constexpr int UB = 8, NB = k / 4 / UB;  // batches of eight k-steps
+      constexpr int BA = 2;                   // batches by which the B1 operand loads run ahead of their MFMAs
+      float a0[2][UB], a1[2][UB], bv[BA + 1][UB];  // A one batch ahead (LDS), B1 BA batches ahead (L2)
 #pragma unroll
-        for (int b = 0; b < BA; ++b)
+      for (int b = 0; b < BA; ++b)
 #pragma unroll
-          for (int j = 0; j < UB; ++j)
-            if (b < NB) bv[b][j] = b1_load(b * UB + j);
+        for (int j = 0; j < UB; ++j)
+          if (b < NB) bv[b][j] = b1_load(b * UB + j);
 #pragma unroll
-        for (int j = 0; j < UB; ++j) {
-          a0[0][j] = ap[4 * j];
-          a1[0][j] = ap[16 * ld + 4 * j];
+      for (int j = 0; j < UB; ++j) {
+        a0[0][j] = ap[4 * j];
+        a1[0][j] = ap[16 * ld + 4 * j];
+      }
+#pragma unroll
+      for (int t = 0; t < NB; ++t) {
+        if (t + BA < NB) {
+#pragma unroll
+          for (int j = 0; j < UB; ++j) bv[(t + BA) % (BA + 1)][j] = b1_load((t + BA) * UB + j);
         }
-#pragma unroll
-        for (int t = 0; t < NB; ++t) {
-          if (t + BA < NB) {
-#pragma unroll
-            for (int j = 0; j < UB; ++j) bv[(t + BA) % (BA + 1)][j] = b1_load((t + BA) * UB + j);
-          }
-          if (t + 1 < NB) {
-#pragma unroll
-            for (int j = 0; j < UB; ++j) {
-              a0[(t + 1) & 1][j] = ap[4 * ((t + 1) * UB + j)];
-              a1[(t + 1) & 1][j] = ap[16 * ld + 4 * ((t + 1) * UB + j)];
-            }
-          }
-          __builtin_amdgcn_sched_barrier(0);  // loads first: the scheduler otherwise sinks them to just before their use
+        if (t + 1 < NB) {
 #pragma unroll
           for (int j = 0; j < UB; ++j) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[t % (BA + 1)][j], a0[t & 1][j], acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[t % (BA + 1)][j], a1[t & 1][j], acc1, 0, 0, 0);
+            a0[(t + 1) & 1][j] = ap[4 * ((t + 1) * UB + j)];
+            a1[(t + 1) & 1][j] = ap[16 * ld + 4 * ((t + 1) * UB + j)];
           }
-          __builtin_amdgcn_sched_barrier(0);
         }
-        // lane (lc, lk) holds C1[row lc (+16)][16·wave + 4·lk … + 3]
-        float* cp = C1i + ((long)c * FR + lc) * n + 16 * wave + 4 * lk;
-        __builtin_nontemporal_store(acc0, reinterpret_cast<f32x4*>(cp));
-        __builtin_nontemporal_store(acc1, reinterpret_cast<f32x4*>(cp + 16L * n));
+        __builtin_amdgcn_sched_barrier(0);  // loads first: the scheduler otherwise sinks them to just before their use
+#pragma unroll
+        for (int j = 0; j < UB; ++j) {
+          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[t % (BA + 1)][j], a0[t & 1][j], acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(bv[t % (BA + 1)][j], a1[t & 1][j], acc1, 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
+      // lane (lc, lk) holds C1[row lc (+16)][16·wave + 4·lk … + 3]
+      float* cp = C1i + ((long)c * FR + lc) * n + 16 * wave + 4 * lk;
+      __builtin_nontemporal_store(acc0, reinterpret_cast<f32x4*>(cp));
+      __builtin_nontemporal_store(acc1, reinterpret_cast<f32x4*>(cp + 16L * n));
       __syncthreads();
     }
     return;
@@ -206,26 +185,24 @@ __global__ __launch_bounds__(FTHREADS) void gemm_pair_a_at_kernel(const float* _
     for (int r = 0; r < 16; ++r) acc2[u][r] = 0.f;
   __syncthreads();
   for (int c = 0; c < chunks; ++c) {
-    if (!(MI_FUSED_ABL & 2)) {
-      const float* bp = b2s + ((c & 1) * FR + lhi) * FN + l31;
-      const float* ap = as + ((c & 1) * FR + lhi) * ld + 32 * (wave - 2) + l31;
-      constexpr int KS = FR / 2;  // MFMAs per tile and chunk
-      float bv[KS], av[2][KS];
+    const float* bp = b2s + ((c & 1) * FR + lhi) * FN + l31;
+    const float* ap = as + ((c & 1) * FR + lhi) * ld + 32 * (wave - 2) + l31;
+    constexpr int KS = FR / 2;  // MFMAs per tile and chunk
+    float bv[KS], av[2][KS];
 #pragma unroll
-      for (int s = 0; s < KS; ++s) bv[s] = bp[2 * s * FN];
+    for (int s = 0; s < KS; ++s) bv[s] = bp[2 * s * FN];
 #pragma unroll
-      for (int s = 0; s < KS; ++s) av[0][s] = ap[2 * s * ld];
+    for (int s = 0; s < KS; ++s) av[0][s] = ap[2 * s * ld];
 #pragma unroll
-      for (int u = 0; u < KT; ++u) {
-        if (u + 1 < KT) {
+    for (int u = 0; u < KT; ++u) {
+      if (u + 1 < KT) {
 #pragma unroll
-          for (int s = 0; s < KS; ++s) av[(u + 1) & 1][s] = ap[2 * s * ld + 64 * (u + 1)];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int s = 0; s < KS; ++s) acc2[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][s], bv[s], acc2[u], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
+        for (int s = 0; s < KS; ++s) av[(u + 1) & 1][s] = ap[2 * s * ld + 64 * (u + 1)];
       }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < KS; ++s) acc2[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u & 1][s], bv[s], acc2[u], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();
   }

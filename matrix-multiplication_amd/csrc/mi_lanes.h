@@ -24,9 +24,6 @@ struct LaneChunk {
   static constexpr int ENTRIES = (G == 32 && SPLIT32) ? 16 : G;
 };
 
-#ifndef MI_LANES_READLANE64
-#define MI_LANES_READLANE64 1  // 0: whole-wave groups use ds_bpermute too (developer A/B)
-#endif
 // Entry I (a compile-time index) of the caller's group's chunk register, without a trip through the LDS crossbar
 // where the hardware offers one: a DPP row broadcast (row_newbcast, a modifier of a VALU move, 16-lane rows) for
 // groups of 8 and 16 lanes (and of 32 with SPLIT32) — two 8-lane groups share a row and take their halves through
@@ -52,7 +49,7 @@ __device__ __forceinline__ T group_lane(T x) {
     r = __builtin_amdgcn_update_dpp(0, bits, I | (I << 2) | ((2 + I) << 4) | ((2 + I) << 6), 0xf, 0xf, true);  // [I,I,2+I,2+I]
   } else if constexpr (G == 1) {
     r = bits;
-  } else if constexpr (G == 64 && MI_LANES_READLANE64) {
+  } else if constexpr (G == 64) {
     r = __builtin_amdgcn_readlane(bits, I);
   } else {
     r = __shfl(bits, I, G);

@@ -43,25 +43,9 @@ __device__ __forceinline__ f32x4 fma4(float a, f32x4 x, f32x4 acc) {
 
 constexpr int kWaves = 16;
 
-#ifndef MI_LDSQ_FMAC_DPP
-#define MI_LDSQ_FMAC_DPP 0
-#endif
-#ifndef MI_LDSQ_BATCH_MASK
-#define MI_LDSQ_BATCH_MASK 3  // entries whose LDS reads the scheduler may batch, minus one (A/B in one process, tools/probes/ldsb_ab.py:
-                              // 0 / 1 / 3 within 1 % of each other, 3 ahead by 0.5 %)
-#endif
-
-#ifdef MI_LDSB_TIMING
-// developer build (tools/probes/ldsb_timing.py): wave 0 of every workgroup stamps the 100 MHz wall clock at its phase
-// boundaries — entry, after each staging, after each unit, exit — into g_ldsq_stamps[workgroup][slot]
-__device__ unsigned long long g_ldsq_stamps[512][16];
-__device__ unsigned long long g_ldsq_wave_end[512][16][4];  // [workgroup][wave][unit]: when the wave left the unit's rows
-#define LDSQ_WAVE_END(unit) do { if (lane == 0 && (unit) < 4) g_ldsq_wave_end[blockIdx.x & 511][wave][unit] = wall_clock64(); } while (0)
-#define LDSQ_STAMP(slot) do { const int s_ = (slot); if (tid == 0 && s_ < 16) g_ldsq_stamps[blockIdx.x & 511][s_] = wall_clock64(); } while (0)
-#else
-#define LDSQ_STAMP(slot) do {} while (0)
-#define LDSQ_WAVE_END(unit) do {} while (0)
-#endif
+// entries whose LDS reads the scheduler may batch, minus one (A/B in one process: 0 / 1 / 3 within 1 % of each other,
+// 3 ahead by 0.5 %)
+constexpr int kLdsqBatchMask = 3;
 
 template <int G, bool PERM>
 __global__ __launch_bounds__(kWaves * 64) void spmm_ldsb_kernel(
@@ -355,8 +339,6 @@ __global__ __launch_bounds__(WAVES * 64) void spmm_ldsq_kernel(
   finish_bounds(s1, e1, k1);
 
   long staged = -1;
-  [[maybe_unused]] int stamp = 0;
-  LDSQ_STAMP(stamp++);
   for (unsigned u = u0; u < u1; ++u) {  // workgroup-uniform
     const long slice = u / (unsigned)units_per_item;
     const int part = (int)(u % (unsigned)units_per_item);
@@ -381,7 +363,6 @@ __global__ __launch_bounds__(WAVES * 64) void spmm_ldsq_kernel(
       __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the pieces have landed (expcnt / lgkmcnt left alone)
       __syncthreads();
       staged = slice;
-      LDSQ_STAMP(stamp++);
     }
     const __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(C + item * strideC + col0, 0, 0x7fffffff, 0x00020000);
     const __amdgpu_buffer_rsrc_t brsrc =
@@ -413,26 +394,13 @@ __global__ __launch_bounds__(WAVES * 64) void spmm_ldsq_kernel(
               f32x4 x[Q];
 #pragma unroll
               for (int j = 0; j < Q; ++j) x[j] = *(LdsRow)(unsigned long)(off + lb[j]);
-#if MI_LDSQ_FMAC_DPP
-              // developer A/B: the value's quad broadcast as a DPP modifier of sixteen v_fmac_f32 instead of one
-              // v_mov_b32_dpp + eight v_pk_fma_f32 — measured 15 % SLOWER (0.340 vs 0.297 ms at 100 % kept): the packed
-              // FMA issues at full rate (SQ_ACTIVE_INST_VALU counts one quad-cycle for it)
-#pragma unroll
-              for (int j = 0; j < Q; ++j) {
-                float a0 = acc[j].x, a1 = acc[j].y, a2 = acc[j].z, a3 = acc[j].w;
-                asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(a0) : "v"(r0.v[comp]), "v"(x[j].x), "n"(src));
-                asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(a1) : "v"(r0.v[comp]), "v"(x[j].y), "n"(src));
-                asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(a2) : "v"(r0.v[comp]), "v"(x[j].z), "n"(src));
-                asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[%3,%3,%3,%3] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "+v"(a3) : "v"(r0.v[comp]), "v"(x[j].w), "n"(src));
-                acc[j] = f32x4{a0, a1, a2, a3};
-              }
-#else
+              // (the value's quad broadcast as one v_mov_b32_dpp + eight v_pk_fma_f32; a DPP-modifier form of the FMA was
+              // 15 % slower: 0.340 vs 0.297 ms at 100 % kept — the packed FMA issues at full rate)
               const float v = group_lane<4, src, true>(r0.v[comp]);
 #pragma unroll
               for (int j = 0; j < Q; ++j) acc[j] = fma4(v, x[j], acc[j]);
-#endif
-              // (a fence for the scheduler every MI_LDSQ_BATCH_MASK + 1 entries: left alone it hoists sixteen entries' reads and spills)
-              if constexpr ((e & MI_LDSQ_BATCH_MASK) == MI_LDSQ_BATCH_MASK) __builtin_amdgcn_sched_barrier(0);
+              // (a fence for the scheduler every kLdsqBatchMask + 1 entries: left alone it hoists sixteen entries' reads and spills)
+              if constexpr ((e & kLdsqBatchMask) == kLdsqBatchMask) __builtin_amdgcn_sched_barrier(0);
             });
           }
         });
@@ -459,8 +427,6 @@ __global__ __launch_bounds__(WAVES * 64) void spmm_ldsq_kernel(
       s1 = s2, e1 = e2;
       finish_bounds(s1, e1, k1);
     }
-    LDSQ_WAVE_END((int)(u - u0));
-    LDSQ_STAMP(stamp++);
   }
 }
 
@@ -1004,24 +970,6 @@ int launch_sddmm_ldsb(const int32_t* rowptr, const int32_t* col, const float* dC
 }  // namespace mi
 
 extern "C" {
-
-#if defined(MI_LDSB_TIMING) || defined(MI_LDSB_PROBE)
-// developer builds of this file alone (tools/probes/ldsb_timing.py, tools/probes/ldsb_ab.py): the plan's launcher without
-// the dispatcher; stamps_out = null: no synchronisation, nothing read back
-int mi_ldsb_probe(const int32_t* rowptr, const int32_t* col, const float* val, const float* B, float* C, int32_t batch,
-                  int32_t M, int32_t K, int32_t N, int64_t nnz, void* stamps_out) {
-  const int st = mi::launch_spmm_ldsb(rowptr, col, val, B, C, batch, M, K, N, N, N, (int64_t)K * N, (int64_t)M * N, nullptr,
-                                      0x7fffffff, nullptr, nullptr, nnz);
-  if (st != MI_OK || !stamps_out) return st;
-  MI_HIP_TRY(hipDeviceSynchronize());
-#ifdef MI_LDSB_TIMING
-  MI_HIP_TRY(hipMemcpyFromSymbol(stamps_out, HIP_SYMBOL(g_ldsq_stamps), sizeof(g_ldsq_stamps)));
-  MI_HIP_TRY(hipMemcpyFromSymbol(static_cast<char*>(stamps_out) + sizeof(g_ldsq_stamps), HIP_SYMBOL(g_ldsq_wave_end),
-                                 sizeof(g_ldsq_wave_end)));
-#endif
-  return MI_OK;
-}
-#endif
 
 int mi_spmm_ldsb_set_form(int form) {
   if (form < -1 || form > 1) return MI_EINVAL;

@@ -181,9 +181,7 @@ Shape classify(int32_t N, int64_t ldb, int64_t ldc, int64_t strideB, int64_t str
   return sh;
 }
 
-#ifndef MI_SPMM_LDSB_MIN_ROW
-#define MI_SPMM_LDSB_MIN_ROW 4L  // mean non-zeros per row from which MI_SPMM_LDS_B is AUTO's choice (tools/bench_attn_csr.py)
-#endif
+constexpr long kLdsbMinRow = 4L;  // mean non-zeros per row from which MI_SPMM_LDS_B is AUTO's choice (tools/bench_attn_csr.py)
 // The kernel AUTO resolves to.
 int choose_variant(const Shape& sh, int64_t nnz, int32_t batch, int32_t M, int32_t K, int32_t N,
                    int64_t ldb) {
@@ -217,7 +215,7 @@ int choose_variant(const Shape& sh, int64_t nnz, int32_t batch, int32_t M, int32
   // 12 heads of 1024 tokens at 25 % kept 0.041 → 0.020 ms, 24 × 512² 0.024 → 0.017, tools/probes/small_batch_probe.py)
   if (sh.vec4_ok && mi::spmm_ldsb_fits(K, N) &&
       ((long)batch * M >= 16384 || ((long)batch * M >= 8192 && nnz >= 1500000)) &&
-      nnz >= MI_SPMM_LDSB_MIN_ROW * (long)batch * M)
+      nnz >= kLdsbMinRow * (long)batch * M)
     return MI_SPMM_LDS_B;
   // N = 20 … 32, up to 16 Ki rows of ≥ 32 entries: 16 lanes per row (half of them idle) instead of 8 — the launch form of the
   // column tiles with ONE tile: twice the waves for a launch that has too few — was ahead on every such shape of

@@ -1,5 +1,5 @@
 """Developer probe: the fused pair of products (dQ = dS·K, dK = dSᵀ·Q in one launch, csrc/gemm_f32_fused.hip) at the C5
-shape against the two plain products; optional ablation libraries (tools/probes/fused_probe_abl*.so, timing only).
+shape against the two plain products; optional further builds of the library (another tree's libmi_spmm.so) are timed beside them.
 
     python tools/bench_fused_pair.py [lib.so …]
 """

@@ -1,7 +1,6 @@
 // Developer probe (not part of the product): the persistent two-halves GEMM (gemm_f32_duo.hip) beside the tile
 // kernels of gemm_f32.hip on BERT-base attention's products and a few squares — bit-equality and time.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude -Imatrix-multiplication_amd/csrc tools/probes/duo_probe.cpp -o tools/probes/duo_probe
-//   (-DMI_DUO_ABL=1/2/4: no C stores / no MFMAs / no operand loads in the duo kernel — timing only)
 #include "../../matrix-multiplication_amd/csrc/mi_status.hip"
 #define MI_GEMM_SINGLE_TU  // everything in this unit
 #include "../../matrix-multiplication_amd/csrc/gemm_f32.hip"
@@ -39,7 +38,6 @@ int main(int argc, char** argv) {
       {"gw7  TN 3072x768 k16384", 1, 0, 1, 3072, 768, 16384},
   };
   const char* only = argc > 1 ? argv[1] : nullptr;
-  const bool check = MI_DUO_ABL == 0;
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (const Shape& s : shapes) {
     if (only && !strstr(s.name, only)) continue;
@@ -74,30 +72,13 @@ int main(int argc, char** argv) {
         float ms; hipEventElapsedTime(&ms, e0, e1);
         if (round >= 1) t[plan].push_back(ms / reps);
       }
-#ifdef MI_DUO_TIMING
-    {
-      static unsigned long long st_[256][8][64], re_[256][2];
-      hipMemcpyFromSymbol(st_, HIP_SYMBOL(g_duo_stamps), sizeof(st_));
-      hipMemcpyFromSymbol(re_, HIP_SYMBOL(g_duo_real), sizeof(re_));
-      for (int wg : {0, 100}) {
-        const double real_ns = (re_[wg][1] - re_[wg][0]) * 10.0;
-        printf("  wg %d: stamps 0..43 span %.1f us by s_memrealtime, %lld cycles -> shader clock %.2f GHz\n", wg, real_ns / 1e3,
-               (long long)(st_[wg][0][43] - st_[wg][0][0]), (st_[wg][0][43] - st_[wg][0][0]) / real_ns);
-        for (int wv : {0, 4}) {
-          printf("   wave %d deltas (cycles): ", wv);
-          for (int e = 1; e < 44; ++e) printf("%s%lld", (e % 4 == 1) ? " | " : " ", (long long)(st_[wg][wv][e] - st_[wg][wv][e - 1]));
-          printf("\n   total stamped cycles %lld -> clock %.2f GHz if whole body\n", (long long)(st_[wg][wv][43] - st_[wg][wv][0]), 0.0);
-        }
-      }
-    }
-#endif
     const double flop = 2.0 * s.batch * s.m * (double)s.n * s.k;
     for (int plan = 1; plan <= 2; ++plan) {
       std::sort(t[plan].begin(), t[plan].end());
       printf("%-32s %s  median %.4f ms  min %.4f ms  %.1f TFLOP/s (median)  status %d\n", s.name, plan == 1 ? "tiles" : "duo  ",
              t[plan][t[plan].size() / 2], t[plan][0], flop / t[plan][t[plan].size() / 2] / 1e9, st[plan]);
     }
-    if (check && st[1] == 0 && st[2] == 0) {
+    if (st[1] == 0 && st[2] == 0) {
       std::vector<float> h1(nc), h2(nc);
       hipMemcpy(h1.data(), C1, nc * 4, hipMemcpyDeviceToHost);
       hipMemcpy(h2.data(), C2, nc * 4, hipMemcpyDeviceToHost);

@@ -1,8 +1,8 @@
 """A/B of builds of the dense fp32 product in ONE process, beside torch.matmul, taking turns block by block:
     python tools/probes/gemm_ab.py items m n k ta tb [name=lib.so …]
-`default` is the tree's libmi_spmm.so; a probe library is a single-unit build of csrc/gemm_f32.hip, e.g.
+`default` is the tree's libmi_spmm.so; a probe library is a single-unit build of another tree's csrc/gemm_f32.hip, e.g.
     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -Imatrix-multiplication_amd/csrc -DMI_GEMM_SINGLE_TU \
-          -DMI_GEMM_FORCE_TILE=4 -shared matrix-multiplication_amd/csrc/{gemm_f32,gemm_f32_duo,mi_status}.hip -o tools/probes/gemm_t64.so
+          -shared matrix-multiplication_amd/csrc/{gemm_f32,gemm_f32_duo,mi_status}.hip -o tools/probes/gemm_other.so
 Outputs of every library are compared bit for bit with the default's."""
 import ctypes
 import sys

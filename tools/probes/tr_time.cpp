@@ -1,4 +1,5 @@
 // Developer probe: wall time of mi_csr_transpose_f32 at the C3 shape (uniform 105 non-zeros per row).
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude -Imatrix-multiplication_amd/csrc tools/probes/tr_time.cpp matrix-multiplication_amd/csrc/csr_transpose_items.hip -o tools/probes/tr_time
 #include "../../matrix-multiplication_amd/csrc/mi_status.hip"
 #include "../../matrix-multiplication_amd/csrc/csr_transpose.hip"
 #include <cstdio>
