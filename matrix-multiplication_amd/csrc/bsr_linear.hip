@@ -297,8 +297,6 @@ __global__ __launch_bounds__(256) void bsr_wgrad_combine_kernel(const float* __r
   *reinterpret_cast<uint2*>(out + e * (kB * kB) + (idx - p * (kB * kB))) = uint2{pack2<T>(t[0], t[1]), pack2<T>(t[2], t[3])};
 }
 
-bool odd(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) != 0; }
-
 template <class T, bool TRANS_W, int BM, bool BIAS>
 int launch_linear(const LinArgs& g, bool vec, hipStream_t s) {
   const long tiles = (long)g.own_blocks * ((g.tokens + BM - 1) / BM);

@@ -213,8 +213,6 @@ __global__ __launch_bounds__(256) void bsr_sddmm_kernel(SddmmArgs g) {
   store_acc<T, 2, true>(acc, g.out + e * (kB * kB), kB, 0, kB, wm, wn, li, lg);
 }
 
-bool odd(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) != 0; }
-
 template <class T, bool TRANS_A, int BN>
 int launch_mm(const MmArgs& g, bool vec, hipStream_t s) {
   MmArgs a = g;

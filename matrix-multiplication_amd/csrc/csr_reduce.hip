@@ -20,17 +20,17 @@
 //    With a workspace, rows beyond kHubRow entries are skipped and listed (as spmm_device.h's long_list_append does).
 //  * reduce_hub_kernel: a listed row cut into S = max(1, len / kHubChunk) chunks, a 16-wave workgroup per chunk and
 //    64·W columns, waves combined through LDS; S = 1 writes the result, else a partial (value, arg) row.
-//  * reduce_hub_combine_kernel: the S partials of a row, combined in order (the order does not matter: `pick` is exact).
 //  * rows_divide_kernel: out[i, :] = in[i, :] / count(i), correctly rounded (mean, and its gradient g / count).
-//  * reduce_grad_val_kernel / reduce_grad_b_kernel: the gradients of max / min (below).  No float atomics: every
-//    result is one fixed-order chain.
+//  * reduce_grad_b_kernel: the gradient of max / min for B (below).  No float atomics: every result is one fixed-order
+//    chain.
+// csr_reduce_device.h owns what this unit shares with csr_reduce_lowp.hip and instantiates here for Fp32: the selection
+// steps, the hub-row list, reduce_hub_combine_kernel (the S partials of a row), reduce_grad_val_kernel, the argument
+// checks of the four entries, launch_reduce and the launch ladders.  Forms<Fp32> below is this unit's part of the host
+// side: the choice of W, and the sum / mean route.
 #include "csr_reduce_device.h"
 #include "mi_common.h"
 
 namespace {
-
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef int i32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 template <int W>
 struct Cols;
@@ -102,6 +102,7 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const int* __restrict_
                                                           long ldb, long ldc, long ldarg, int nnz, HubArg hub) {
   using F = typename Cols<W>::F;
   using I = typename Cols<W>::I;
+  // (written out in both units: as rows_begin(), or with only the hub test in a function, every rows kernel changed: §3.26)
   long row = ((long)blockIdx.x * 256 + threadIdx.x) / G;
   if constexpr (G == 64) row = __builtin_amdgcn_readfirstlane((int)row);
   const int gl = threadIdx.x % G;
@@ -144,6 +145,7 @@ __global__ __launch_bounds__(1024) void reduce_hub_kernel(const int* __restrict_
   using I = typename Cols<W>::I;
   __shared__ float s_val[kHubWaves][64 * W];
   __shared__ int s_arg[kHubWaves][64 * W];
+  // (slot → wave range and the LDS combine: written out in both units; four forms each changed hub kernels: DESIGN.md §3.26)
   const int slot = blockIdx.x;
   if (slot >= __builtin_amdgcn_readfirstlane(ws[1])) return;
   const int e = ws[4 + 4 * (long)cap_e + slot];
@@ -181,25 +183,6 @@ __global__ __launch_bounds__(1024) void reduce_hub_kernel(const int* __restrict_
   }
 }
 
-// The S > 1 rows: partials g = 0 … S−1 combined per column.  grid = (cap_e, ⌈N / 256⌉), block = 256.
-template <bool MAX>
-__global__ __launch_bounds__(256) void reduce_hub_combine_kernel(float* __restrict__ C, int* __restrict__ argout, int N,
-                                                                 long ldc, long ldarg, const int* __restrict__ ws,
-                                                                 const float* __restrict__ part_val,
-                                                                 const int* __restrict__ part_arg) {
-  const int e = blockIdx.x;
-  if (e >= __builtin_amdgcn_readfirstlane(ws[0])) return;
-  const int* ent = ws + 4 + 4 * (long)e;
-  const int row = ent[0], S = ent[2], pb = ent[3];
-  const int j = blockIdx.y * 256 + threadIdx.x;
-  if (S <= 1 || j >= N) return;
-  float cur = part_val[(long)pb * N + j];
-  int arg = part_arg[(long)pb * N + j];
-  for (int g = 1; g < S; ++g) pick<MAX>(part_val[(long)(pb + g) * N + j], part_arg[(long)(pb + g) * N + j], cur, arg);
-  C[(long)row * ldc + j] = cur;
-  if (argout) argout[(long)row * ldarg + j] = arg;
-}
-
 // out[i, j] = in[i, j] / count(i) (correctly rounded); rows without entries are copied.  One wave per row, block = 256.
 __global__ __launch_bounds__(256) void rows_divide_kernel(const int* __restrict__ rowptr, int M, int N,
                                                           const float* in, long ldin, float* out, long ldout) {
@@ -210,52 +193,6 @@ __global__ __launch_bounds__(256) void rows_divide_kernel(const int* __restrict_
   for (int j = threadIdx.x & 63; j < N; j += 64) {
     const float x = in[row * ldin + j];
     out[row * ldout + j] = cnt > 0 ? __fdiv_rn(x, d) : x;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// grad_val[e] = Σ_j [arg[i, j] == e] · g[i, j] · B[col[e], j] for the entries e of row i.  One wave per row; lane l
-// keeps columns 64t + l of the row's arg and g in registers (T chunks; T = 0: N > 1024, read per entry from the
-// caches).  Per entry, a B load only where arg == e, an fmaf chain over t ascending, a xor tree (32 … 1) across the
-// wave.  block = 256 (4 rows).
-// ---------------------------------------------------------------------------
-template <int T>
-__global__ __launch_bounds__(256) void reduce_grad_val_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
-                                                              int M, int N, const float* __restrict__ B, long ldb,
-                                                              const float* __restrict__ G, long ldg,
-                                                              const int* __restrict__ argin, long ldarg,
-                                                              float* __restrict__ grad_val) {
-  const long row = __builtin_amdgcn_readfirstlane((int)(((long)blockIdx.x * 256 + threadIdx.x) >> 6));
-  if (row >= M) return;
-  const int lane = threadIdx.x & 63;
-  const int p0 = rowptr[row], end = rowptr[row + 1];
-  const float* Gr = G + row * ldg;
-  const int* Ar = argin + row * ldarg;
-  constexpr int TR = T > 0 ? T : 1;
-  float gk[TR];
-  int ak[TR];
-  if constexpr (T > 0) {
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-      const int j = 64 * t + lane;
-      ak[t] = j < N ? Ar[j] : -1;
-      gk[t] = j < N ? Gr[j] : 0.f;
-    }
-  }
-  for (int e = p0; e < end; ++e) {
-    const float* Bc = B + (long)col[e] * ldb;
-    float acc = 0.f;
-    if constexpr (T > 0) {
-#pragma unroll
-      for (int t = 0; t < T; ++t)
-        if (ak[t] == e) acc = __builtin_fmaf(gk[t], Bc[64 * t + lane], acc);
-    } else {
-      for (int j = lane; j < N; j += 64)
-        if (Ar[j] == e) acc = __builtin_fmaf(Gr[j], Bc[j], acc);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if (lane == 0) grad_val[e] = acc;
   }
 }
 
@@ -308,78 +245,76 @@ __global__ __launch_bounds__(256) void reduce_grad_b_kernel(const int* __restric
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// host side: the checks, launch_reduce and the ladders are csr_reduce_device.h's; here the choice of W
 // ---------------------------------------------------------------------------
 template <int W, bool MAX, bool ARG>
-int launch_rows_w(int G, const int32_t* rowptr, const int32_t* col, const float* val, const float* B, float* C, int32_t* arg,
-                  int32_t M, int32_t N, int64_t ldb, int64_t ldc, int64_t ldarg, int32_t nnz, const HubArg& hub,
-                  hipStream_t s) {
-  const dim3 grid((unsigned)(((int64_t)M * G + 255) / 256));
-#define MI_REDUCE_ROWS(GG)                                                                                                  \
-  case GG:                                                                                                                 \
-    hipLaunchKernelGGL((reduce_rows_kernel<GG, W, MAX, ARG>), grid, dim3(256), 0, s, rowptr, col, val, B, C, arg, M, N, ldb, \
-                       ldc, ldarg, nnz, hub);                                                                              \
-    break;
-  switch (G) {
-    MI_REDUCE_ROWS(1)
-    MI_REDUCE_ROWS(2)
-    MI_REDUCE_ROWS(4)
-    MI_REDUCE_ROWS(8)
-    MI_REDUCE_ROWS(16)
-    MI_REDUCE_ROWS(32)
-    MI_REDUCE_ROWS(64)
-    default:
-      return MI_EINVAL;
-  }
+int launch_rows(const ReduceCall<float>& c, const HubArg& hub, hipStream_t s) {
+  const int G = lanes_for<W>(c.N);
+  const dim3 grid((unsigned)(((int64_t)c.M * G + 255) / 256));
+#define MI_REDUCE_ROWS(GG)                                                                                                   \
+  hipLaunchKernelGGL((reduce_rows_kernel<GG, W, MAX, ARG>), grid, dim3(256), 0, s, c.rowptr, c.col, c.val, c.B, c.C, c.arg, \
+                     c.M, c.N, c.ldb, c.ldc, c.ldarg, c.nnz, hub)
+  MI_REDUCE_FOR_LANES(G, MI_REDUCE_ROWS)
 #undef MI_REDUCE_ROWS
   return mi::check_launch();
 }
 
-template <bool MAX>
-int launch_reduce(const int32_t* rowptr, const int32_t* col, const float* val, int64_t nnz, int32_t M, int32_t N,
-                  const float* B, int64_t ldb, float* C, int64_t ldc, int32_t* arg, int64_t ldarg, void* workspace,
-                  hipStream_t s) {
-  HubArg hub = {nullptr, 0, 0, 0};
-  const HubWs hw = hub_ws_layout(nnz, N);
-  const bool split = workspace != nullptr && nnz > kHubRow;
-  int* ws = static_cast<int*>(workspace);
-  if (split) {
-    MI_HIP_TRY(hipMemsetAsync(ws, 0, 16, s));
-    hub = {ws, (int)hw.cap_e, (int)hw.cap_s, (int)hw.cap_p};
+template <>
+struct Forms<Fp32> {
+  static int sum_or_mean(const int32_t* rowptr, const int32_t* col, const float* val, int64_t nnz, int32_t M, int32_t K,
+                         int32_t N, const float* B, int64_t ldb, float* C, int64_t ldc, int reduce, void* workspace,
+                         size_t workspace_bytes, hipStream_t s) {
+    int st = mi_spmm_csr_ws_f32(rowptr, col, val, nnz, M, K, N, B, ldb, nullptr, C, ldc, workspace, workspace_bytes,
+                                static_cast<mi_stream_t>(s));
+    if (st != MI_OK || reduce == MI_REDUCE_SUM) return st;
+    return divide(rowptr, M, N, C, ldc, C, ldc, s);
   }
-  int st;
-  if (N >= 4) {
-    const int G = lanes_for<4>(N);
-    st = arg ? launch_rows_w<4, MAX, true>(G, rowptr, col, val, B, C, arg, M, N, ldb, ldc, ldarg, (int)nnz, hub, s)
-             : launch_rows_w<4, MAX, false>(G, rowptr, col, val, B, C, arg, M, N, ldb, ldc, ldarg, (int)nnz, hub, s);
-  } else {
-    const int G = lanes_for<1>(N);
-    st = arg ? launch_rows_w<1, MAX, true>(G, rowptr, col, val, B, C, arg, M, N, ldb, ldc, ldarg, (int)nnz, hub, s)
-             : launch_rows_w<1, MAX, false>(G, rowptr, col, val, B, C, arg, M, N, ldb, ldc, ldarg, (int)nnz, hub, s);
-  }
-  if (st != MI_OK || !split) return st;
-  float* part_val = reinterpret_cast<float*>(static_cast<char*>(workspace) + hw.part_val_off);
-  int* part_arg = reinterpret_cast<int*>(static_cast<char*>(workspace) + hw.part_arg_off);
-  if (N >= 4)
-    hipLaunchKernelGGL((reduce_hub_kernel<4, MAX>), dim3((unsigned)hw.cap_s, (unsigned)((N + 255) / 256)), dim3(1024), 0, s,
-                       rowptr, col, val, B, C, arg, N, (long)ldb, (long)ldc, (long)ldarg, (int)nnz, ws, (int)hw.cap_e,
-                       part_val, part_arg);
-  else
-    hipLaunchKernelGGL((reduce_hub_kernel<1, MAX>), dim3((unsigned)hw.cap_s, 1u), dim3(1024), 0, s, rowptr, col, val, B, C,
-                       arg, N, (long)ldb, (long)ldc, (long)ldarg, (int)nnz, ws, (int)hw.cap_e, part_val, part_arg);
-  st = mi::check_launch();
-  if (st != MI_OK) return st;
-  hipLaunchKernelGGL((reduce_hub_combine_kernel<MAX>), dim3((unsigned)hw.cap_e, (unsigned)((N + 255) / 256)), dim3(256), 0,
-                     s, C, arg, N, (long)ldc, (long)ldarg, ws, part_val, part_arg);
-  return mi::check_launch();
-}
 
-int launch_divide(const int32_t* rowptr, int32_t M, int32_t N, const float* in, int64_t ldin, float* out, int64_t ldout,
-                  hipStream_t s) {
-  hipLaunchKernelGGL(rows_divide_kernel, dim3((unsigned)(((int64_t)M + 3) / 4)), dim3(256), 0, s, rowptr, M, N, in,
-                     (long)ldin, out, (long)ldout);
-  return mi::check_launch();
-}
+  static int form(const ReduceCall<float>& c) { return c.N >= 4 ? 4 : 1; }  // W
+
+  template <bool MAX>
+  static int rows(const ReduceCall<float>& c, int W, const HubArg& hub, hipStream_t s) {
+    if (W == 4) return c.arg ? launch_rows<4, MAX, true>(c, hub, s) : launch_rows<4, MAX, false>(c, hub, s);
+    return c.arg ? launch_rows<1, MAX, true>(c, hub, s) : launch_rows<1, MAX, false>(c, hub, s);
+  }
+
+  template <bool MAX>
+  static int hub(const ReduceCall<float>& c, int W, dim3 grid, const int* ws, int cap_e, float* part_val, int* part_arg,
+                 hipStream_t s) {
+    if (W == 4)
+      hipLaunchKernelGGL((reduce_hub_kernel<4, MAX>), grid, dim3(1024), 0, s, c.rowptr, c.col, c.val, c.B, c.C, c.arg, c.N,
+                         c.ldb, c.ldc, c.ldarg, c.nnz, ws, cap_e, part_val, part_arg);
+    else
+      hipLaunchKernelGGL((reduce_hub_kernel<1, MAX>), grid, dim3(1024), 0, s, c.rowptr, c.col, c.val, c.B, c.C, c.arg, c.N,
+                         c.ldb, c.ldc, c.ldarg, c.nnz, ws, cap_e, part_val, part_arg);
+    return mi::check_launch();
+  }
+
+  static int divide(const int32_t* rowptr, int32_t M, int32_t N, const float* in, int64_t ldin, float* out, int64_t ldout,
+                    hipStream_t s) {
+    hipLaunchKernelGGL(rows_divide_kernel, dim3((unsigned)(((int64_t)M + 3) / 4)), dim3(256), 0, s, rowptr, M, N, in,
+                       (long)ldin, out, (long)ldout);
+    return mi::check_launch();
+  }
+
+  static int grad_b(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm, const float* val, int32_t K, int32_t N,
+                    const float* G, long ldg, const int32_t* arg, long ldarg, float* grad_b, long ldgb, hipStream_t s) {
+    if (N >= 4) {
+      const int Gl = lanes_for<4>(N);
+      const dim3 grid((unsigned)(((int64_t)K * Gl + 255) / 256));
+#define MI_GRAD_B(GG)                                                                                                      \
+  hipLaunchKernelGGL((reduce_grad_b_kernel<GG, 4>), grid, dim3(256), 0, s, t_rowptr, t_col, perm, val, K, N, G, ldg, arg, \
+                     ldarg, grad_b, ldgb)
+      MI_REDUCE_FOR_LANES(Gl, MI_GRAD_B)
+#undef MI_GRAD_B
+    } else {
+      const dim3 grid((unsigned)(((int64_t)K * 4 + 255) / 256));
+      hipLaunchKernelGGL((reduce_grad_b_kernel<4, 1>), grid, dim3(256), 0, s, t_rowptr, t_col, perm, val, K, N, G, ldg, arg,
+                         ldarg, grad_b, ldgb);
+    }
+    return mi::check_launch();
+  }
+};
 
 }  // namespace
 
@@ -394,98 +329,25 @@ size_t mi_spmm_csr_reduce_workspace_bytes(int64_t nnz, int32_t N) {
 int mi_spmm_csr_reduce_f32(const int32_t* rowptr, const int32_t* col, const float* val, int64_t nnz, int32_t M, int32_t K,
                            int32_t N, const float* B, int64_t ldb, float* C, int64_t ldc, int32_t* arg, int64_t ldarg,
                            int reduce, void* workspace, size_t workspace_bytes, mi_stream_t stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (reduce < MI_REDUCE_SUM || reduce > MI_REDUCE_AMIN) return MI_EINVAL;
-  const bool selects = reduce == MI_REDUCE_AMAX || reduce == MI_REDUCE_AMIN;
-  if (arg != nullptr && !selects) return MI_EINVAL;
-  if (M < 0 || K < 0 || N < 0 || nnz < 0) return MI_EINVAL;
-  if (nnz > 0x7fffffffLL) return MI_ERANGE;
-  if (M == 0 || N == 0) return MI_OK;
-  if (!rowptr || !C || (nnz > 0 && (!col || !val || !B))) return MI_EINVAL;
-  if (ldb < N || ldc < N || (arg != nullptr && ldarg < N)) return MI_EINVAL;
-  if (!selects) {
-    int st = mi_spmm_csr_ws_f32(rowptr, col, val, nnz, M, K, N, B, ldb, nullptr, C, ldc, workspace, workspace_bytes, stream);
-    if (st != MI_OK || reduce == MI_REDUCE_SUM) return st;
-    return launch_divide(rowptr, M, N, C, ldc, C, ldc, s);
-  }
-  if (workspace != nullptr && nnz > kHubRow) {
-    if (workspace_bytes < hub_ws_layout(nnz, N).bytes) return MI_ENOMEM;
-    if (!mi::aligned16(workspace)) return MI_EINVAL;
-  }
-  if (!grid_fits(M, 64)) return MI_ERANGE;
-  return reduce == MI_REDUCE_AMAX ? launch_reduce<true>(rowptr, col, val, nnz, M, N, B, ldb, C, ldc, arg, ldarg, workspace, s)
-                                  : launch_reduce<false>(rowptr, col, val, nnz, M, N, B, ldb, C, ldc, arg, ldarg, workspace, s);
+  return reduce_entry<Fp32>(rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, arg, ldarg, reduce, workspace, workspace_bytes,
+                            stream);
 }
 
 int mi_spmm_rows_divide_f32(const int32_t* rowptr, int32_t M, int32_t N, const float* in, int64_t ldin, float* out,
                             int64_t ldout, mi_stream_t stream) {
-  if (M < 0 || N < 0) return MI_EINVAL;
-  if (M == 0 || N == 0) return MI_OK;
-  if (!rowptr || !in || !out || ldin < N || ldout < N) return MI_EINVAL;
-  return launch_divide(rowptr, M, N, in, ldin, out, ldout, static_cast<hipStream_t>(stream));
+  return divide_entry<Fp32>(rowptr, M, N, in, ldin, out, ldout, stream);
 }
 
 int mi_spmm_reduce_grad_val_f32(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M, int32_t K, int32_t N,
                                 const float* B, int64_t ldb, const float* G, int64_t ldg, const int32_t* arg,
                                 int64_t ldarg, float* grad_val, mi_stream_t stream) {
-  if (M < 0 || K < 0 || N < 0 || nnz < 0) return MI_EINVAL;
-  if (nnz > 0x7fffffffLL) return MI_ERANGE;
-  if (M == 0 || nnz == 0) return MI_OK;
-  if (!rowptr || !col || !grad_val || (N > 0 && (!B || !G || !arg))) return MI_EINVAL;
-  if (ldb < N || ldg < N || ldarg < N) return MI_EINVAL;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)(((int64_t)M + 3) / 4));
-  const int T = N <= 64 ? 1 : N <= 128 ? 2 : N <= 256 ? 4 : N <= 512 ? 8 : N <= 1024 ? 16 : 0;
-#define MI_GRAD_VAL(TT)                                                                                                  \
-  case TT:                                                                                                               \
-    hipLaunchKernelGGL(reduce_grad_val_kernel<TT>, grid, dim3(256), 0, s, rowptr, col, M, N, B, (long)ldb, G, (long)ldg, \
-                       arg, (long)ldarg, grad_val);                                                                      \
-    break;
-  switch (T) {
-    MI_GRAD_VAL(0)
-    MI_GRAD_VAL(1)
-    MI_GRAD_VAL(2)
-    MI_GRAD_VAL(4)
-    MI_GRAD_VAL(8)
-    MI_GRAD_VAL(16)
-  }
-#undef MI_GRAD_VAL
-  return mi::check_launch();
+  return grad_val_entry<Fp32>(rowptr, col, nnz, M, K, N, B, ldb, G, ldg, arg, ldarg, grad_val, stream);
 }
 
 int mi_spmm_reduce_grad_b_f32(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm, const float* val,
                               int64_t nnz, int32_t M, int32_t K, int32_t N, const float* G, int64_t ldg,
                               const int32_t* arg, int64_t ldarg, float* grad_b, int64_t ldgb, mi_stream_t stream) {
-  if (M < 0 || K < 0 || N < 0 || nnz < 0) return MI_EINVAL;
-  if (nnz > 0x7fffffffLL) return MI_ERANGE;
-  if (K == 0 || N == 0) return MI_OK;
-  if (!t_rowptr || !grad_b || (nnz > 0 && (!t_col || !perm || !val || !G || !arg))) return MI_EINVAL;
-  if (ldg < N || ldarg < N || ldgb < N) return MI_EINVAL;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (N >= 4) {
-    const int Gl = lanes_for<4>(N);
-    const dim3 grid((unsigned)(((int64_t)K * Gl + 255) / 256));
-#define MI_GRAD_B(GG)                                                                                                   \
-  case GG:                                                                                                              \
-    hipLaunchKernelGGL((reduce_grad_b_kernel<GG, 4>), grid, dim3(256), 0, s, t_rowptr, t_col, perm, val, K, N, G,       \
-                       (long)ldg, arg, (long)ldarg, grad_b, (long)ldgb);                                                \
-    break;
-    switch (Gl) {
-      MI_GRAD_B(1)
-      MI_GRAD_B(2)
-      MI_GRAD_B(4)
-      MI_GRAD_B(8)
-      MI_GRAD_B(16)
-      MI_GRAD_B(32)
-      MI_GRAD_B(64)
-    }
-#undef MI_GRAD_B
-  } else {
-    const dim3 grid((unsigned)(((int64_t)K * 4 + 255) / 256));
-    hipLaunchKernelGGL((reduce_grad_b_kernel<4, 1>), grid, dim3(256), 0, s, t_rowptr, t_col, perm, val, K, N, G, (long)ldg,
-                       arg, (long)ldarg, grad_b, (long)ldgb);
-  }
-  return mi::check_launch();
+  return grad_b_entry<Fp32>(t_rowptr, t_col, perm, val, nnz, M, K, N, G, ldg, arg, ldarg, grad_b, ldgb, stream);
 }
 
 }  // extern "C"

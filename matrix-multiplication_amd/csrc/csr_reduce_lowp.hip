@@ -11,18 +11,19 @@
 //    aligned) or four guarded 2-byte loads (any N, leading dimension and 2-byte alignment: odd N, column-offset views).
 //    The gathered words stay packed until they are multiplied, so a one-wave row keeps 16 gathers in flight per lane
 //    (16 × 512 B per wave at N = 256 — the fp32 kernel's 8 × 1 KiB); the batch at a row's end repeats its last entry.
-//  * lowp_reduce_hub_kernel / lowp_reduce_hub_combine_kernel: rows beyond kHubRow entries, listed by the rows kernel —
-//    csr_reduce.hip's split, the (value, arg) partials fp32 / int32 in the same workspace layout.
-//  * lowp_rows_divide_kernel, lowp_reduce_grad_val_kernel, lowp_reduce_grad_b_kernel: the fp32 kernels' fixed summation orders,
-//    widened on load, rounded once at the store.
+//  * lowp_reduce_hub_kernel: rows beyond kHubRow entries, listed by the rows kernel — csr_reduce.hip's split, the
+//    (value, arg) partials fp32 / int32 in the same workspace layout.
+//  * lowp_rows_divide_kernel, lowp_reduce_grad_b_kernel: the fp32 kernels' fixed summation orders, widened on load, rounded
+//    once at the store.
+// csr_reduce_device.h owns what this unit shares with csr_reduce.hip and instantiates here for Lowp<Bf16> / Lowp<F16>: the
+// selection steps, the hub-row list, reduce_hub_combine_kernel, reduce_grad_val_kernel, the argument checks of the four
+// entries (with the odd-pointer refusal of 2-byte elements), launch_reduce and the launch ladders.  Forms<Lowp<T>> below is
+// this unit's part of the host side: the choice of VEC, and the sum / mean route.
 // No float atomics; no host read-back (graph-capturable).
 #include "csr_reduce_device.h"
-#include "lowp_device.h"
 #include "spmm_internal.h"
 
 namespace {
-
-typedef int i32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 // four consecutive elements as they are stored, two per dword (zeros at and beyond column N in the element form)
 template <bool VEC>
@@ -86,6 +87,7 @@ __device__ __forceinline__ void scan_range(const int* __restrict__ col, const un
   }
 }
 
+// (the fp32 unit starts its W columns by element: one scan_init for both changed its four hub kernels)
 template <bool MAX>
 __device__ __forceinline__ void scan_init(f32x4& cur, i32x4u& arg, int nnz) {
   const float s = scan_start<MAX>();
@@ -104,6 +106,7 @@ __global__ __launch_bounds__(256) void lowp_reduce_rows_kernel(const int* __rest
                                                                unsigned short* __restrict__ C, int* __restrict__ argout, int M,
                                                                int N, long ldb, long ldc, long ldarg, int nnz, HubArg hub) {
   constexpr int U = G == 64 && VEC ? 16 : kU;
+  // (written out in both units: as rows_begin(), or with only the hub test in a function, every rows kernel changed: §3.26)
   long row = ((long)blockIdx.x * 256 + threadIdx.x) / G;
   if constexpr (G == 64) row = __builtin_amdgcn_readfirstlane((int)row);
   const int gl = threadIdx.x % G;
@@ -141,6 +144,7 @@ __global__ __launch_bounds__(1024) void lowp_reduce_hub_kernel(const int* __rest
                                                                float* __restrict__ part_val, int* __restrict__ part_arg) {
   __shared__ float s_val[kHubWaves][256];
   __shared__ int s_arg[kHubWaves][256];
+  // (slot → wave range and the LDS combine: written out in both units; four forms each changed hub kernels: DESIGN.md §3.26)
   const int slot = blockIdx.x;
   if (slot >= __builtin_amdgcn_readfirstlane(ws[1])) return;
   const int e = ws[4 + 4 * (long)cap_e + slot];
@@ -187,25 +191,6 @@ __global__ __launch_bounds__(1024) void lowp_reduce_hub_kernel(const int* __rest
   }
 }
 
-// The S > 1 rows: partials g = 0 … S−1 combined per column, narrowed.  grid = (cap_e, ⌈N / 256⌉), block = 256.
-template <class T, bool MAX>
-__global__ __launch_bounds__(256) void lowp_reduce_hub_combine_kernel(unsigned short* __restrict__ C, int* __restrict__ argout,
-                                                                      int N, long ldc, long ldarg, const int* __restrict__ ws,
-                                                                      const float* __restrict__ part_val,
-                                                                      const int* __restrict__ part_arg) {
-  const int e = blockIdx.x;
-  if (e >= __builtin_amdgcn_readfirstlane(ws[0])) return;
-  const int* ent = ws + 4 + 4 * (long)e;
-  const int row = ent[0], S = ent[2], pb = ent[3];
-  const int j = blockIdx.y * 256 + threadIdx.x;
-  if (S <= 1 || j >= N) return;
-  float cur = part_val[(long)pb * N + j];
-  int arg = part_arg[(long)pb * N + j];
-  for (int g = 1; g < S; ++g) pick<MAX>(part_val[(long)(pb + g) * N + j], part_arg[(long)(pb + g) * N + j], cur, arg);
-  C[(long)row * ldc + j] = T::down(cur);
-  if (argout) argout[(long)row * ldarg + j] = arg;
-}
-
 // out[i, j] = rne_T(up(in[i, j]) / count(i)) (the fp32 division correctly rounded); rows without entries are copied.
 // One wave per row, 4 columns per lane; block = 256.
 template <class T, bool VEC>
@@ -220,51 +205,6 @@ __global__ __launch_bounds__(256) void lowp_rows_divide_kernel(const int* __rest
     f32x4 x = load4<T, VEC>(in + row * ldin + j, j, N);
     if (cnt > 0) x = f32x4{__fdiv_rn(x.x, d), __fdiv_rn(x.y, d), __fdiv_rn(x.z, d), __fdiv_rn(x.w, d)};
     store4<T, VEC>(out + row * ldout + j, j, N, x);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// grad_val[e] = rne_T(Σ_j [arg[i, j] == e] · g[i, j] · B[col[e], j]): reduce_grad_val_kernel's order — lane l keeps columns
-// 64t + l of the row's arg and (widened) g in registers (TT chunks; TT = 0: N > 1024, read per entry from the caches), an
-// fmaf chain over t ascending, a xor tree (32 … 1) across the wave.  One wave per row, block = 256 (4 rows).
-// ---------------------------------------------------------------------------
-template <class T, int TT>
-__global__ __launch_bounds__(256) void lowp_reduce_grad_val_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
-                                                                   int M, int N, const unsigned short* __restrict__ B, long ldb,
-                                                                   const unsigned short* __restrict__ G, long ldg,
-                                                                   const int* __restrict__ argin, long ldarg,
-                                                                   unsigned short* __restrict__ grad_val) {
-  const long row = __builtin_amdgcn_readfirstlane((int)(((long)blockIdx.x * 256 + threadIdx.x) >> 6));
-  if (row >= M) return;
-  const int lane = threadIdx.x & 63;
-  const int p0 = rowptr[row], end = rowptr[row + 1];
-  const unsigned short* Gr = G + row * ldg;
-  const int* Ar = argin + row * ldarg;
-  constexpr int TR = TT > 0 ? TT : 1;
-  float gk[TR];
-  int ak[TR];
-  if constexpr (TT > 0) {
-#pragma unroll
-    for (int t = 0; t < TT; ++t) {
-      const int j = 64 * t + lane;
-      ak[t] = j < N ? Ar[j] : -1;
-      gk[t] = j < N ? up<T>(Gr[j]) : 0.f;
-    }
-  }
-  for (int e = p0; e < end; ++e) {
-    const unsigned short* Bc = B + (long)col[e] * ldb;
-    float acc = 0.f;
-    if constexpr (TT > 0) {
-#pragma unroll
-      for (int t = 0; t < TT; ++t)
-        if (ak[t] == e) acc = __builtin_fmaf(gk[t], up<T>(Bc[64 * t + lane]), acc);
-    } else {
-      for (int j = lane; j < N; j += 64)
-        if (Ar[j] == e) acc = __builtin_fmaf(up<T>(Gr[j]), up<T>(Bc[j]), acc);
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if (lane == 0) grad_val[e] = T::down(acc);
   }
 }
 
@@ -324,184 +264,88 @@ __global__ __launch_bounds__(256) void lowp_reduce_grad_b_kernel(const int* __re
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// host side: the checks, launch_reduce and the ladders are csr_reduce_device.h's; here the choice of VEC
 // ---------------------------------------------------------------------------
-inline bool odd(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) != 0; }
-
 template <class T, bool VEC, bool MAX, bool ARG>
-int launch_rows(int G, const int32_t* rowptr, const int32_t* col, const uint16_t* val, const uint16_t* B, uint16_t* C,
-                int32_t* arg, int32_t M, int32_t N, int64_t ldb, int64_t ldc, int64_t ldarg, int32_t nnz, const HubArg& hub,
-                hipStream_t s) {
-  const dim3 grid((unsigned)(((int64_t)M * G + 255) / 256));
-#define MI_REDUCE_ROWS(GG)                                                                                                   \
-  case GG:                                                                                                                  \
-    hipLaunchKernelGGL((lowp_reduce_rows_kernel<T, GG, VEC, MAX, ARG>), grid, dim3(256), 0, s, rowptr, col, val, B, C, arg, M, \
-                       N, (long)ldb, (long)ldc, (long)ldarg, nnz, hub);                                                     \
-    break;
-  switch (G) {
-    MI_REDUCE_ROWS(1)
-    MI_REDUCE_ROWS(2)
-    MI_REDUCE_ROWS(4)
-    MI_REDUCE_ROWS(8)
-    MI_REDUCE_ROWS(16)
-    MI_REDUCE_ROWS(32)
-    MI_REDUCE_ROWS(64)
-    default:
-      return MI_EINVAL;
-  }
+int launch_rows(const ReduceCall<uint16_t>& c, const HubArg& hub, hipStream_t s) {
+  const int G = lanes_for<4>(c.N);
+  const dim3 grid((unsigned)(((int64_t)c.M * G + 255) / 256));
+#define MI_REDUCE_ROWS(GG)                                                                                                  \
+  hipLaunchKernelGGL((lowp_reduce_rows_kernel<T, GG, VEC, MAX, ARG>), grid, dim3(256), 0, s, c.rowptr, c.col, c.val, c.B, \
+                     c.C, c.arg, c.M, c.N, c.ldb, c.ldc, c.ldarg, c.nnz, hub)
+  MI_REDUCE_FOR_LANES(G, MI_REDUCE_ROWS)
 #undef MI_REDUCE_ROWS
-  return mi::check_launch();
-}
-
-template <class T, bool VEC, bool MAX>
-int launch_reduce(const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz, int32_t M, int32_t N,
-                  const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, int32_t* arg, int64_t ldarg, void* workspace,
-                  hipStream_t s) {
-  HubArg hub = {nullptr, 0, 0, 0};
-  const HubWs hw = hub_ws_layout(nnz, N);
-  const bool split = workspace != nullptr && nnz > kHubRow;
-  int* ws = static_cast<int*>(workspace);
-  if (split) {
-    MI_HIP_TRY(hipMemsetAsync(ws, 0, 16, s));
-    hub = {ws, (int)hw.cap_e, (int)hw.cap_s, (int)hw.cap_p};
-  }
-  const int G = lanes_for<4>(N);
-  int st = arg ? launch_rows<T, VEC, MAX, true>(G, rowptr, col, val, B, C, arg, M, N, ldb, ldc, ldarg, (int)nnz, hub, s)
-               : launch_rows<T, VEC, MAX, false>(G, rowptr, col, val, B, C, arg, M, N, ldb, ldc, ldarg, (int)nnz, hub, s);
-  if (st != MI_OK || !split) return st;
-  float* part_val = reinterpret_cast<float*>(static_cast<char*>(workspace) + hw.part_val_off);
-  int* part_arg = reinterpret_cast<int*>(static_cast<char*>(workspace) + hw.part_arg_off);
-  hipLaunchKernelGGL((lowp_reduce_hub_kernel<T, VEC, MAX>), dim3((unsigned)hw.cap_s, (unsigned)((N + 255) / 256)), dim3(1024), 0,
-                     s, rowptr, col, val, B, C, arg, N, (long)ldb, (long)ldc, (long)ldarg, (int)nnz, ws, (int)hw.cap_e, part_val,
-                     part_arg);
-  st = mi::check_launch();
-  if (st != MI_OK) return st;
-  hipLaunchKernelGGL((lowp_reduce_hub_combine_kernel<T, MAX>), dim3((unsigned)hw.cap_e, (unsigned)((N + 255) / 256)), dim3(256),
-                     0, s, C, arg, N, (long)ldc, (long)ldarg, ws, part_val, part_arg);
-  return mi::check_launch();
-}
-
-template <class T>
-int reduce_lowp(bool bf16, const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz, int32_t M, int32_t K,
-                int32_t N, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, int32_t* arg, int64_t ldarg, int reduce,
-                void* workspace, size_t workspace_bytes, hipStream_t s) {
-  // every check before the first HIP call, in the order of mi_spmm_csr_reduce_f32
-  if (reduce < MI_REDUCE_SUM || reduce > MI_REDUCE_AMIN) return MI_EINVAL;
-  const bool selects = reduce == MI_REDUCE_AMAX || reduce == MI_REDUCE_AMIN;
-  if (arg != nullptr && !selects) return MI_EINVAL;
-  if (M < 0 || K < 0 || N < 0 || nnz < 0) return MI_EINVAL;
-  if (nnz > 0x7fffffffLL) return MI_ERANGE;
-  if (M == 0 || N == 0) return MI_OK;
-  if (!rowptr || !C || (nnz > 0 && (!col || !val || !B))) return MI_EINVAL;
-  if (ldb < N || ldc < N || (arg != nullptr && ldarg < N)) return MI_EINVAL;
-  if (odd(val) || odd(B) || odd(C)) return MI_EINVAL;
-  if (!selects) {
-    // NULL workspace: every row is one chain (as the fp32 entry); else the split order of mi_spmm_csr_ex_T
-    const int mode = workspace != nullptr ? MI_LONG_ROWS_SPLIT : MI_LONG_ROWS_NONE;
-    if (reduce == MI_REDUCE_SUM)
-      return (bf16 ? mi_spmm_csr_ex_bf16 : mi_spmm_csr_ex_f16)(rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, mode, workspace,
-                                                               workspace_bytes, static_cast<mi_stream_t>(s));
-    return mi::spmm_lowp_mean(bf16, rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, mode, workspace, workspace_bytes, s);
-  }
-  if (workspace != nullptr && nnz > kHubRow) {
-    if (workspace_bytes < hub_ws_layout(nnz, N).bytes) return MI_ENOMEM;
-    if (!mi::aligned16(workspace)) return MI_EINVAL;
-  }
-  if (!grid_fits(M, 64)) return MI_ERANGE;
-  const bool vec = N % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && aligned8(B) && aligned8(C);
-  const bool max = reduce == MI_REDUCE_AMAX;
-#define MI_REDUCE_LOWP(VEC_, MAX_) \
-  return launch_reduce<T, VEC_, MAX_>(rowptr, col, val, nnz, M, N, B, ldb, C, ldc, arg, ldarg, workspace, s)
-  if (vec && max) MI_REDUCE_LOWP(true, true);
-  if (vec) MI_REDUCE_LOWP(true, false);
-  if (max) MI_REDUCE_LOWP(false, true);
-  MI_REDUCE_LOWP(false, false);
-#undef MI_REDUCE_LOWP
-}
-
-template <class T>
-int divide_lowp(const int32_t* rowptr, int32_t M, int32_t N, const uint16_t* in, int64_t ldin, uint16_t* out, int64_t ldout,
-                hipStream_t s) {
-  if (M < 0 || N < 0) return MI_EINVAL;
-  if (M == 0 || N == 0) return MI_OK;
-  if (!rowptr || !in || !out || ldin < N || ldout < N) return MI_EINVAL;
-  if (odd(in) || odd(out)) return MI_EINVAL;
-  const dim3 grid((unsigned)(((int64_t)M + 3) / 4));
-  if (N % 4 == 0 && ldin % 4 == 0 && ldout % 4 == 0 && aligned8(in) && aligned8(out))
-    hipLaunchKernelGGL((lowp_rows_divide_kernel<T, true>), grid, dim3(256), 0, s, rowptr, M, N, in, (long)ldin, out, (long)ldout);
-  else
-    hipLaunchKernelGGL((lowp_rows_divide_kernel<T, false>), grid, dim3(256), 0, s, rowptr, M, N, in, (long)ldin, out, (long)ldout);
-  return mi::check_launch();
-}
-
-template <class T>
-int grad_val_lowp(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M, int32_t K, int32_t N, const uint16_t* B,
-                  int64_t ldb, const uint16_t* G, int64_t ldg, const int32_t* arg, int64_t ldarg, uint16_t* grad_val,
-                  hipStream_t s) {
-  if (M < 0 || K < 0 || N < 0 || nnz < 0) return MI_EINVAL;
-  if (nnz > 0x7fffffffLL) return MI_ERANGE;
-  if (M == 0 || nnz == 0) return MI_OK;
-  if (!rowptr || !col || !grad_val || (N > 0 && (!B || !G || !arg))) return MI_EINVAL;
-  if (ldb < N || ldg < N || ldarg < N) return MI_EINVAL;
-  if (odd(B) || odd(G) || odd(grad_val)) return MI_EINVAL;
-  const dim3 grid((unsigned)(((int64_t)M + 3) / 4));
-  const int TT = N <= 64 ? 1 : N <= 128 ? 2 : N <= 256 ? 4 : N <= 512 ? 8 : N <= 1024 ? 16 : 0;
-#define MI_GRAD_VAL(TT_)                                                                                                   \
-  case TT_:                                                                                                                \
-    hipLaunchKernelGGL((lowp_reduce_grad_val_kernel<T, TT_>), grid, dim3(256), 0, s, rowptr, col, M, N, B, (long)ldb, G,   \
-                       (long)ldg, arg, (long)ldarg, grad_val);                                                             \
-    break;
-  switch (TT) {
-    MI_GRAD_VAL(0)
-    MI_GRAD_VAL(1)
-    MI_GRAD_VAL(2)
-    MI_GRAD_VAL(4)
-    MI_GRAD_VAL(8)
-    MI_GRAD_VAL(16)
-  }
-#undef MI_GRAD_VAL
   return mi::check_launch();
 }
 
 template <class T, bool VEC>
 int launch_grad_b(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm, const uint16_t* val, int32_t K, int32_t N,
-                  const uint16_t* G, int64_t ldg, const int32_t* arg, int64_t ldarg, uint16_t* grad_b, int64_t ldgb,
-                  hipStream_t s) {
+                  const uint16_t* G, long ldg, const int32_t* arg, long ldarg, uint16_t* grad_b, long ldgb, hipStream_t s) {
   const int Gl = lanes_for<4>(N);
   const dim3 grid((unsigned)(((int64_t)K * Gl + 255) / 256));
-#define MI_GRAD_B(GG)                                                                                                       \
-  case GG:                                                                                                                  \
-    hipLaunchKernelGGL((lowp_reduce_grad_b_kernel<T, GG, VEC>), grid, dim3(256), 0, s, t_rowptr, t_col, perm, val, K, N, G, \
-                       (long)ldg, arg, (long)ldarg, grad_b, (long)ldgb);                                                    \
-    break;
-  switch (Gl) {
-    MI_GRAD_B(1)
-    MI_GRAD_B(2)
-    MI_GRAD_B(4)
-    MI_GRAD_B(8)
-    MI_GRAD_B(16)
-    MI_GRAD_B(32)
-    MI_GRAD_B(64)
-  }
+#define MI_GRAD_B(GG)                                                                                                          \
+  hipLaunchKernelGGL((lowp_reduce_grad_b_kernel<T, GG, VEC>), grid, dim3(256), 0, s, t_rowptr, t_col, perm, val, K, N, G, ldg, \
+                     arg, ldarg, grad_b, ldgb)
+  MI_REDUCE_FOR_LANES(Gl, MI_GRAD_B)
 #undef MI_GRAD_B
   return mi::check_launch();
 }
 
 template <class T>
-int grad_b_lowp(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm, const uint16_t* val, int64_t nnz, int32_t M,
-                int32_t K, int32_t N, const uint16_t* G, int64_t ldg, const int32_t* arg, int64_t ldarg, uint16_t* grad_b,
-                int64_t ldgb, hipStream_t s) {
-  if (M < 0 || K < 0 || N < 0 || nnz < 0) return MI_EINVAL;
-  if (nnz > 0x7fffffffLL) return MI_ERANGE;
-  if (K == 0 || N == 0) return MI_OK;
-  if (!t_rowptr || !grad_b || (nnz > 0 && (!t_col || !perm || !val || !G || !arg))) return MI_EINVAL;
-  if (ldg < N || ldarg < N || ldgb < N) return MI_EINVAL;
-  if (odd(val) || odd(G) || odd(grad_b)) return MI_EINVAL;
-  if (!grid_fits(K, 64)) return MI_ERANGE;
-  if (N % 4 == 0 && ldgb % 4 == 0 && aligned8(grad_b))
-    return launch_grad_b<T, true>(t_rowptr, t_col, perm, val, K, N, G, ldg, arg, ldarg, grad_b, ldgb, s);
-  return launch_grad_b<T, false>(t_rowptr, t_col, perm, val, K, N, G, ldg, arg, ldarg, grad_b, ldgb, s);
-}
+struct Forms<Lowp<T>> {
+  static constexpr bool kBf16 = std::is_same<T, Bf16>::value;
+
+  // NULL workspace: every row is one chain (as the fp32 entry); else the split order of mi_spmm_csr_ex_T
+  static int sum_or_mean(const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz, int32_t M, int32_t K,
+                         int32_t N, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, int reduce, void* workspace,
+                         size_t workspace_bytes, hipStream_t s) {
+    const int mode = workspace != nullptr ? MI_LONG_ROWS_SPLIT : MI_LONG_ROWS_NONE;
+    if (reduce == MI_REDUCE_SUM)
+      return (kBf16 ? mi_spmm_csr_ex_bf16 : mi_spmm_csr_ex_f16)(rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, mode, workspace,
+                                                                workspace_bytes, static_cast<mi_stream_t>(s));
+    return mi::spmm_lowp_mean(kBf16, rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, mode, workspace, workspace_bytes, s);
+  }
+
+  // VEC: one 8-byte access per four columns; else guarded elements
+  static int form(const ReduceCall<uint16_t>& c) {
+    return c.N % 4 == 0 && c.ldb % 4 == 0 && c.ldc % 4 == 0 && aligned8(c.B) && aligned8(c.C);
+  }
+
+  template <bool MAX>
+  static int rows(const ReduceCall<uint16_t>& c, int vec, const HubArg& hub, hipStream_t s) {
+    if (vec) return c.arg ? launch_rows<T, true, MAX, true>(c, hub, s) : launch_rows<T, true, MAX, false>(c, hub, s);
+    return c.arg ? launch_rows<T, false, MAX, true>(c, hub, s) : launch_rows<T, false, MAX, false>(c, hub, s);
+  }
+
+  template <bool MAX>
+  static int hub(const ReduceCall<uint16_t>& c, int vec, dim3 grid, const int* ws, int cap_e, float* part_val, int* part_arg,
+                 hipStream_t s) {
+    if (vec)
+      hipLaunchKernelGGL((lowp_reduce_hub_kernel<T, true, MAX>), grid, dim3(1024), 0, s, c.rowptr, c.col, c.val, c.B, c.C, c.arg,
+                         c.N, c.ldb, c.ldc, c.ldarg, c.nnz, ws, cap_e, part_val, part_arg);
+    else
+      hipLaunchKernelGGL((lowp_reduce_hub_kernel<T, false, MAX>), grid, dim3(1024), 0, s, c.rowptr, c.col, c.val, c.B, c.C, c.arg,
+                         c.N, c.ldb, c.ldc, c.ldarg, c.nnz, ws, cap_e, part_val, part_arg);
+    return mi::check_launch();
+  }
+
+  static int divide(const int32_t* rowptr, int32_t M, int32_t N, const uint16_t* in, int64_t ldin, uint16_t* out, int64_t ldout,
+                    hipStream_t s) {
+    const dim3 grid((unsigned)(((int64_t)M + 3) / 4));
+    if (N % 4 == 0 && ldin % 4 == 0 && ldout % 4 == 0 && aligned8(in) && aligned8(out))
+      hipLaunchKernelGGL((lowp_rows_divide_kernel<T, true>), grid, dim3(256), 0, s, rowptr, M, N, in, (long)ldin, out, (long)ldout);
+    else
+      hipLaunchKernelGGL((lowp_rows_divide_kernel<T, false>), grid, dim3(256), 0, s, rowptr, M, N, in, (long)ldin, out, (long)ldout);
+    return mi::check_launch();
+  }
+
+  static int grad_b(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm, const uint16_t* val, int32_t K, int32_t N,
+                    const uint16_t* G, long ldg, const int32_t* arg, long ldarg, uint16_t* grad_b, long ldgb, hipStream_t s) {
+    if (N % 4 == 0 && ldgb % 4 == 0 && aligned8(grad_b))
+      return launch_grad_b<T, true>(t_rowptr, t_col, perm, val, K, N, G, ldg, arg, ldarg, grad_b, ldgb, s);
+    return launch_grad_b<T, false>(t_rowptr, t_col, perm, val, K, N, G, ldg, arg, ldarg, grad_b, ldgb, s);
+  }
+};
 
 }  // namespace
 
@@ -510,51 +354,49 @@ extern "C" {
 int mi_spmm_csr_reduce_bf16(const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz, int32_t M, int32_t K,
                             int32_t N, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, int32_t* arg, int64_t ldarg,
                             int reduce, void* workspace, size_t workspace_bytes, mi_stream_t stream) {
-  return reduce_lowp<Bf16>(true, rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, arg, ldarg, reduce, workspace, workspace_bytes,
-                           static_cast<hipStream_t>(stream));
+  return reduce_entry<Lowp<Bf16>>(rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, arg, ldarg, reduce, workspace, workspace_bytes,
+                                  stream);
 }
 
 int mi_spmm_csr_reduce_f16(const int32_t* rowptr, const int32_t* col, const uint16_t* val, int64_t nnz, int32_t M, int32_t K,
                            int32_t N, const uint16_t* B, int64_t ldb, uint16_t* C, int64_t ldc, int32_t* arg, int64_t ldarg,
                            int reduce, void* workspace, size_t workspace_bytes, mi_stream_t stream) {
-  return reduce_lowp<F16>(false, rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, arg, ldarg, reduce, workspace, workspace_bytes,
-                          static_cast<hipStream_t>(stream));
+  return reduce_entry<Lowp<F16>>(rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, arg, ldarg, reduce, workspace, workspace_bytes,
+                                 stream);
 }
 
 int mi_spmm_rows_divide_bf16(const int32_t* rowptr, int32_t M, int32_t N, const uint16_t* in, int64_t ldin, uint16_t* out,
                              int64_t ldout, mi_stream_t stream) {
-  return divide_lowp<Bf16>(rowptr, M, N, in, ldin, out, ldout, static_cast<hipStream_t>(stream));
+  return divide_entry<Lowp<Bf16>>(rowptr, M, N, in, ldin, out, ldout, stream);
 }
 
 int mi_spmm_rows_divide_f16(const int32_t* rowptr, int32_t M, int32_t N, const uint16_t* in, int64_t ldin, uint16_t* out,
                             int64_t ldout, mi_stream_t stream) {
-  return divide_lowp<F16>(rowptr, M, N, in, ldin, out, ldout, static_cast<hipStream_t>(stream));
+  return divide_entry<Lowp<F16>>(rowptr, M, N, in, ldin, out, ldout, stream);
 }
 
 int mi_spmm_reduce_grad_val_bf16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M, int32_t K, int32_t N,
                                  const uint16_t* B, int64_t ldb, const uint16_t* G, int64_t ldg, const int32_t* arg,
                                  int64_t ldarg, uint16_t* grad_val, mi_stream_t stream) {
-  return grad_val_lowp<Bf16>(rowptr, col, nnz, M, K, N, B, ldb, G, ldg, arg, ldarg, grad_val, static_cast<hipStream_t>(stream));
+  return grad_val_entry<Lowp<Bf16>>(rowptr, col, nnz, M, K, N, B, ldb, G, ldg, arg, ldarg, grad_val, stream);
 }
 
 int mi_spmm_reduce_grad_val_f16(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t M, int32_t K, int32_t N,
                                 const uint16_t* B, int64_t ldb, const uint16_t* G, int64_t ldg, const int32_t* arg,
                                 int64_t ldarg, uint16_t* grad_val, mi_stream_t stream) {
-  return grad_val_lowp<F16>(rowptr, col, nnz, M, K, N, B, ldb, G, ldg, arg, ldarg, grad_val, static_cast<hipStream_t>(stream));
+  return grad_val_entry<Lowp<F16>>(rowptr, col, nnz, M, K, N, B, ldb, G, ldg, arg, ldarg, grad_val, stream);
 }
 
 int mi_spmm_reduce_grad_b_bf16(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm, const uint16_t* val,
                                int64_t nnz, int32_t M, int32_t K, int32_t N, const uint16_t* G, int64_t ldg, const int32_t* arg,
                                int64_t ldarg, uint16_t* grad_b, int64_t ldgb, mi_stream_t stream) {
-  return grad_b_lowp<Bf16>(t_rowptr, t_col, perm, val, nnz, M, K, N, G, ldg, arg, ldarg, grad_b, ldgb,
-                           static_cast<hipStream_t>(stream));
+  return grad_b_entry<Lowp<Bf16>>(t_rowptr, t_col, perm, val, nnz, M, K, N, G, ldg, arg, ldarg, grad_b, ldgb, stream);
 }
 
 int mi_spmm_reduce_grad_b_f16(const int32_t* t_rowptr, const int32_t* t_col, const int32_t* perm, const uint16_t* val,
                               int64_t nnz, int32_t M, int32_t K, int32_t N, const uint16_t* G, int64_t ldg, const int32_t* arg,
                               int64_t ldarg, uint16_t* grad_b, int64_t ldgb, mi_stream_t stream) {
-  return grad_b_lowp<F16>(t_rowptr, t_col, perm, val, nnz, M, K, N, G, ldg, arg, ldarg, grad_b, ldgb,
-                          static_cast<hipStream_t>(stream));
+  return grad_b_entry<Lowp<F16>>(t_rowptr, t_col, perm, val, nnz, M, K, N, G, ldg, arg, ldarg, grad_b, ldgb, stream);
 }
 
 }  // extern "C"

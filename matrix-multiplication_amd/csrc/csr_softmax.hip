@@ -268,8 +268,6 @@ int launch_backward(const int32_t* rowptr, int64_t nnz, int32_t batch, int32_t M
   return mi::check_launch();
 }
 
-inline bool odd(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) != 0; }
-
 template <class E>
 int forward_entry(const int32_t* rowptr, int64_t nnz, int32_t batch, int32_t M, const typename E::S* x, float scale,
                   typename E::S* y, mi_stream_t stream) {

@@ -9,24 +9,6 @@
 
 namespace {
 
-// down(f, z): the stored form of the fp32 result f.  z is a zero the compiler cannot see (the kernels derive it from an
-// argument): for fp16 hipcc otherwise fuses the multiply that produces f with the narrowing into ONE mixed-precision fma
-// (v_fma_mixlo_f16) — a single rounding of the exact product, and a +0 addend that turns −0 into +0 — which is not
-// rne_T(fl32(product)), the contract.  Passing f's bits through `xor z` keeps the two roundings apart.
-struct Fp32 {
-  typedef float S;
-  static __device__ __forceinline__ float up(float v) { return v; }
-  static __device__ __forceinline__ float down(float v, unsigned) { return v; }
-};
-template <class T>
-struct Lowp {
-  typedef unsigned short S;
-  static __device__ __forceinline__ float up(unsigned short h) { return T::lo(h); }
-  static __device__ __forceinline__ unsigned short down(float f, unsigned z) {
-    return T::down(__uint_as_float(__float_as_uint(f) ^ z));
-  }
-};
-
 // the xor tree over the lanes of a group of G (d = G/2 … 1); every lane ends with the result
 template <int G>
 __device__ __forceinline__ float tree_sum(float v) {

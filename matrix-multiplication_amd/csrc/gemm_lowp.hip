@@ -310,7 +310,6 @@ int run(int transa, int transb, const GemmArgs& g, bool vec, hipStream_t s) {
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-bool odd(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) != 0; }
 
 // The checks every entry makes before its first HIP call.  MI_OK with *empty set: nothing to compute.
 int validate(int transa, int transb, int32_t m, int32_t n, int32_t k, const uint16_t* A, int64_t lda, int64_t strideA,

@@ -1,6 +1,8 @@
 // The two 16-bit element types, said once for every bfloat16 / float16 translation unit: Bf16 / F16 with their exact widening
-// and their one rounding, up<T>, pack2<T>, and the 4-element row pieces load4 / store4.  Included by the CSR units
-// (csr_lowp.hip, csr_reduce_lowp.hip, csr_softmax.hip through csr_softmax_device.h too, csr_attention.hip), by
+// and their one rounding, up<T>, pack2<T>, the element scheme Fp32 / Lowp<T> of the units that are one template over fp32 and
+// the 16-bit types, the 4-element row pieces load4 / store4, and the host's aligned8 / odd.  Included by the CSR units
+// (csr_lowp.hip; csr_reduce.hip and csr_reduce_lowp.hip through csr_reduce_device.h; csr_softmax.hip and csr_attention.hip,
+// through csr_softmax_device.h too), by
 // mfma_device.h for the five matrix-core units (gemm_lowp.hip, bsr_mm.hip, bsr_linear.hip, block_attention.hip,
 // block_attention_decode.hip) and by kv_cache_device.h for the KV-cache family (kv_append.hip, rope_kv_append.hip).  Not
 // installed.  Everything here has internal linkage (an anonymous namespace per including unit).
@@ -30,6 +32,29 @@ struct F16 {
 
 template <class T>
 __device__ __forceinline__ float up(unsigned short h) { return T::lo(h); }
+
+// The element scheme of the units that cover fp32, bf16 and fp16 with one `template <class E>` (csr_softmax.hip,
+// csr_attention.hip, the reductions of csr_reduce_device.h): E::S the stored type, E::up its exact widening, E::down(f) the
+// one rounding at the store.
+// down(f, z): the stored form of the fp32 result f.  z is a zero the compiler cannot see (the kernels derive it from an
+// argument): for fp16 hipcc otherwise fuses the multiply that produces f with the narrowing into ONE mixed-precision fma
+// (v_fma_mixlo_f16) — a single rounding of the exact product, and a +0 addend that turns −0 into +0 — which is not
+// rne_T(fl32(product)), the contract.  Passing f's bits through `xor z` keeps the two roundings apart.
+struct Fp32 {
+  typedef float S;
+  static __device__ __forceinline__ float up(float v) { return v; }
+  static __device__ __forceinline__ float down(float v) { return v; }
+  static __device__ __forceinline__ float down(float v, unsigned) { return v; }
+};
+template <class T>
+struct Lowp {
+  typedef unsigned short S;
+  static __device__ __forceinline__ float up(unsigned short h) { return T::lo(h); }
+  static __device__ __forceinline__ unsigned short down(float f) { return T::down(f); }
+  static __device__ __forceinline__ unsigned short down(float f, unsigned z) {
+    return T::down(__uint_as_float(__float_as_uint(f) ^ z));
+  }
+};
 
 template <class T>
 __device__ __forceinline__ unsigned pack2(float a, float b) { return (unsigned)T::down(a) | ((unsigned)T::down(b) << 16); }
@@ -65,6 +90,7 @@ __device__ __forceinline__ void store4(unsigned short* p, int j, int N, f32x4 v)
 }
 
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+inline bool odd(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 1u) != 0; }  // a 2-byte element cannot start there
 
 }  // namespace
 

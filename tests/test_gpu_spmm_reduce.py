@@ -132,6 +132,17 @@ def test_hub_rows_bit_exact_vs_torch(cmm, dev, N):
     check_select(cmm, dev, rowptr, col, val, M, K, B, f"hub rows with ties N={N}")
 
 
+@pytest.mark.parametrize("N", [3, 6, 258])
+def test_hub_rows_at_partial_widths_bit_exact_vs_torch(cmm, dev, N):
+    """The hub kernels at the widths the test above does not reach: N = 3 is their one-column-per-lane form, N = 6 ends in
+    a quad shifted back over its neighbour, N = 258 has a second column block whose only quad is shifted back, in the hub
+    and in the combine kernel.  One row in one chunk, a short row, a row through the two-chunk combine, an empty row."""
+    M, K = 4, 4096
+    rowptr, col, val = csr_rows(M, K, (9000, 5, 40000, 0), seed=N, replace=True)
+    B = np.random.Generator(np.random.PCG64(N + 1)).standard_normal((K, N), dtype=np.float32)
+    check_select(cmm, dev, rowptr, col, val, M, K, B, f"hub rows N={N}")
+
+
 def test_c3_amax_with_arg_sampled_rows_vs_torch(cmm, dev):
     M = K = 1_000_000
     N, per_row = 256, 100  # 0.01 %

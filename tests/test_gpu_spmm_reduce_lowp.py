@@ -409,8 +409,8 @@ def pow2_ceil(x):
 
 
 def select_forms(N, vec, hub):
-    """The launcher of csr_reduce_lowp.hip, restated: lanes per row = pow2_ceil(⌈N / 4⌉) up to 64; rows beyond 8192 entries go to
-    the hub kernel, beyond 2 · 16384 also through the combine."""
+    """launch_reduce of csr_reduce_device.h with Forms<Lowp<T>> of csr_reduce_lowp.hip (the choice of VEC), restated: lanes per
+    row = pow2_ceil(⌈N / 4⌉) up to 64; rows beyond 8192 entries go to the hub kernel, beyond 2 · 16384 also through the combine."""
     forms = {("rows", min(64, pow2_ceil((N + 3) // 4)), vec)}
     if hub:
         forms |= {("hub", vec), ("hub combine",)}

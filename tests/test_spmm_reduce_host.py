@@ -13,7 +13,8 @@ HEADER = REPO / "include" / "mi_spmm.h"
 NEW_ENTRIES = ("mi_spmm_csr_reduce_f32", "mi_spmm_csr_reduce_workspace_bytes", "mi_spmm_rows_divide_f32",
                "mi_spmm_reduce_grad_val_f32", "mi_spmm_reduce_grad_b_f32")
 SUM, MEAN, AMAX, AMIN = 0, 1, 2, 3
-OK, EINVAL, ERANGE = 0, -1, -2
+OK, EINVAL, ERANGE, ENOMEM = 0, -1, -2, -4
+DTYPES = ("f32", "bf16", "f16")
 
 
 @pytest.fixture(scope="module")
@@ -28,6 +29,9 @@ def lib(built):
     lib.mi_spmm_rows_divide_f32.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp]
     lib.mi_spmm_reduce_grad_val_f32.argtypes = [vp, vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp]
     lib.mi_spmm_reduce_grad_b_f32.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp]
+    for sfx in DTYPES[1:]:  # the 16-bit twins take the same argument lists
+        for stem in ("mi_spmm_csr_reduce", "mi_spmm_rows_divide", "mi_spmm_reduce_grad_val", "mi_spmm_reduce_grad_b"):
+            getattr(lib, f"{stem}_{sfx}").argtypes = getattr(lib, f"{stem}_f32").argtypes
     return lib
 
 
@@ -99,6 +103,111 @@ def test_divide_and_gradient_entries_validate_before_any_hip_call(lib):
     assert gb(FAKE, FAKE, FAKE, FAKE, 2 ** 31, 4, 4, 8, FAKE, 8, FAKE, 8, FAKE, 8, None) == ERANGE
     assert gb(FAKE, FAKE, None, FAKE, 10, 4, 4, 8, FAKE, 8, FAKE, 8, FAKE, 8, None) == EINVAL
     assert gb(FAKE, FAKE, FAKE, FAKE, 10, 4, 4, 8, FAKE, 8, FAKE, 8, FAKE, 7, None) == EINVAL
+
+
+# One argument list per entry, every pointer FAKE and every size consistent; a case overrides some of them.
+def call_reduce(lib, sfx, *, reduce=AMAX, nnz=10, M=4, K=4, N=8, rowptr=FAKE, col=FAKE, val=FAKE, B=FAKE, ldb=8, C=FAKE,
+                ldc=8, arg=None, ldarg=8, ws=None, ws_bytes=0):
+    return getattr(lib, f"mi_spmm_csr_reduce_{sfx}")(rowptr, col, val, nnz, M, K, N, B, ldb, C, ldc, arg, ldarg, reduce, ws,
+                                                     ws_bytes, None)
+
+
+def call_divide(lib, sfx, *, M=4, N=8, rowptr=FAKE, src=FAKE, ldin=8, out=FAKE, ldout=8):
+    return getattr(lib, f"mi_spmm_rows_divide_{sfx}")(rowptr, M, N, src, ldin, out, ldout, None)
+
+
+def call_grad_val(lib, sfx, *, nnz=10, M=4, K=4, N=8, rowptr=FAKE, col=FAKE, B=FAKE, ldb=8, G=FAKE, ldg=8, arg=FAKE,
+                  ldarg=8, grad_val=FAKE):
+    return getattr(lib, f"mi_spmm_reduce_grad_val_{sfx}")(rowptr, col, nnz, M, K, N, B, ldb, G, ldg, arg, ldarg, grad_val, None)
+
+
+def call_grad_b(lib, sfx, *, nnz=10, M=4, K=4, N=8, t_rowptr=FAKE, t_col=FAKE, perm=FAKE, val=FAKE, G=FAKE, ldg=8, arg=FAKE,
+                ldarg=8, grad_b=FAKE, ldgb=8):
+    return getattr(lib, f"mi_spmm_reduce_grad_b_{sfx}")(t_rowptr, t_col, perm, val, nnz, M, K, N, G, ldg, arg, ldarg, grad_b,
+                                                        ldgb, None)
+
+
+BIG = 2 ** 31            # the first nnz that does not fit the kernels' 32-bit entry index
+HUB = dict(nnz=100_000)  # enough entries for the hub-row workspace to be looked at
+ROOMY = 1 << 40          # a workspace size that is enough for HUB
+# (what is wrong and what else is wrong after it, arguments, status): every case but the plain ones carries a second
+# mistake that a LATER check would answer differently, so the order of the checks shows in the status.
+SHARED_CASES = {
+    "reduce": (call_reduce, [
+        ("bad reduce code; nnz >= 2^31", dict(reduce=99, nnz=BIG), EINVAL),
+        ("bad reduce code; empty call", dict(reduce=-1, M=0), EINVAL),
+        ("arg with sum; nnz >= 2^31", dict(reduce=SUM, arg=FAKE, nnz=BIG), EINVAL),
+        ("arg with mean; empty call", dict(reduce=MEAN, arg=FAKE, M=0), EINVAL),
+        ("negative size; nnz >= 2^31", dict(K=-1, nnz=BIG), EINVAL),
+        ("negative size; empty call", dict(N=-1, M=0), EINVAL),
+        ("negative nnz; empty call", dict(nnz=-1, N=0), EINVAL),
+        ("negative size; null pointer", dict(M=-1, rowptr=None), EINVAL),
+        ("nnz >= 2^31; null pointer", dict(nnz=BIG, rowptr=None), ERANGE),
+        ("nnz >= 2^31; empty call", dict(nnz=BIG, M=0), ERANGE),
+        ("empty call (M = 0); null pointers, leading dimension below N", dict(M=0, rowptr=None, C=None, ldb=0), OK),
+        ("empty call (N = 0); null pointer, short workspace", dict(N=0, B=None, ws=FAKE, ws_bytes=16, **HUB), OK),
+        ("null pointer; short workspace", dict(col=None, ws=FAKE, ws_bytes=16, **HUB), EINVAL),
+        ("null output; short workspace", dict(C=None, ws=FAKE, ws_bytes=16, **HUB), EINVAL),
+        ("ldb below N; short workspace", dict(ldb=7, ws=FAKE, ws_bytes=16, **HUB), EINVAL),
+        ("ldc below N; short workspace", dict(ldc=7, ws=FAKE, ws_bytes=16, **HUB), EINVAL),
+        ("ldarg below N; short workspace", dict(arg=FAKE, ldarg=7, ws=FAKE, ws_bytes=16, **HUB), EINVAL),
+        ("short workspace; misaligned workspace", dict(ws=FAKE + 8, ws_bytes=16, **HUB), ENOMEM),
+        ("misaligned workspace", dict(ws=FAKE + 8, ws_bytes=ROOMY, **HUB), EINVAL),
+    ]),
+    "rows_divide": (call_divide, [
+        ("negative size; empty call", dict(N=-1, M=0), EINVAL),
+        ("negative size; null pointer", dict(M=-1, rowptr=None), EINVAL),
+        ("empty call (M = 0); null pointers, leading dimension below N", dict(M=0, rowptr=None, src=None, out=None, ldin=0), OK),
+        ("empty call (N = 0); null pointers", dict(N=0, src=None, out=None), OK),
+        ("null rowptr", dict(rowptr=None), EINVAL),
+        ("null input", dict(src=None), EINVAL),
+        ("null output", dict(out=None), EINVAL),
+        ("ldin below N", dict(ldin=7), EINVAL),
+        ("ldout below N", dict(ldout=7), EINVAL),
+    ]),
+    "reduce_grad_val": (call_grad_val, [
+        ("negative size; nnz >= 2^31", dict(N=-1, nnz=BIG), EINVAL),
+        ("negative size; empty call", dict(K=-1, M=0), EINVAL),
+        ("negative nnz; null pointer", dict(nnz=-1, rowptr=None), EINVAL),
+        ("nnz >= 2^31; null pointer", dict(nnz=BIG, col=None), ERANGE),
+        ("nnz >= 2^31; empty call", dict(nnz=BIG, M=0), ERANGE),
+        ("empty call (M = 0); null pointers, leading dimension below N", dict(M=0, rowptr=None, grad_val=None, ldb=0), OK),
+        ("empty call (nnz = 0); null pointers", dict(nnz=0, col=None, B=None), OK),
+        ("null rowptr", dict(rowptr=None), EINVAL),
+        ("null arg", dict(arg=None), EINVAL),
+        ("null output", dict(grad_val=None), EINVAL),
+        ("ldb below N", dict(ldb=7), EINVAL),
+        ("ldg below N", dict(ldg=7), EINVAL),
+        ("ldarg below N", dict(ldarg=7), EINVAL),
+    ]),
+    "reduce_grad_b": (call_grad_b, [
+        ("negative size; nnz >= 2^31", dict(M=-1, nnz=BIG), EINVAL),
+        ("negative size; empty call", dict(N=-1, K=0), EINVAL),
+        ("negative nnz; null pointer", dict(nnz=-1, t_rowptr=None), EINVAL),
+        ("nnz >= 2^31; null pointer", dict(nnz=BIG, perm=None), ERANGE),
+        ("nnz >= 2^31; empty call", dict(nnz=BIG, K=0), ERANGE),
+        ("empty call (K = 0); null pointers, leading dimension below N", dict(K=0, t_rowptr=None, grad_b=None, ldg=0), OK),
+        ("empty call (N = 0); null pointers", dict(N=0, G=None, arg=None), OK),
+        ("null t_rowptr", dict(t_rowptr=None), EINVAL),
+        ("null perm", dict(perm=None), EINVAL),
+        ("null output", dict(grad_b=None), EINVAL),
+        ("ldg below N", dict(ldg=7), EINVAL),
+        ("ldarg below N", dict(ldarg=7), EINVAL),
+        ("ldgb below N", dict(ldgb=7), EINVAL),
+    ]),
+}
+
+
+@pytest.mark.parametrize("entry", sorted(SHARED_CASES))
+def test_every_dtype_answers_a_bad_argument_alike_and_in_the_same_order(lib, entry):
+    """The float32, bfloat16 and float16 forms of an entry make the checks they share in one order: the same status for
+    the same mistake, also when a second mistake follows that a later check would answer with another status."""
+    call, cases = SHARED_CASES[entry]
+    for what, kw, want in cases:
+        # the reduce cases that name no code hold for both selections
+        for extra in ({"reduce": AMAX}, {"reduce": AMIN}) if entry == "reduce" and "reduce" not in kw else ({},):
+            got = {sfx: call(lib, sfx, **kw, **extra) for sfx in DTYPES}
+            assert got == dict.fromkeys(DTYPES, want), (entry, what, extra, got)
 
 
 def test_custom_mm_binds_the_reduce_entries(built):
