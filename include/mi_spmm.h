@@ -1173,6 +1173,66 @@ int mi_block_attention_decode_paged_fp8_f16(const int32_t* rowptr, const int32_t
                                             void* workspace, size_t workspace_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * Block-sparse prefill attention over the KV cache: the T ≥ 1 newest tokens of every item — a whole prompt
+ * or one chunk of it — against the cache of mi_block_attention_decode_* in its four forms, forward only.  The rule is the
+ * decode entries': token t of k / v item c stands at pos = clamp(k_len, 0, Smax) − T + t and sees key j iff j ≤ pos and the
+ * layout lists 64-block (pos / 64, j / 64).  The arguments are the decode entries' without `chunk` and the workspace, with:
+ *   q          read through its own strides, never copied: token t of query head g of k / v item c at q + (c / heads) · batchQ +
+ *              ((c % heads) · group + g) · headQ + t · ldq, D elements; 16-byte aligned, every stride a non-negative multiple
+ *              of 8 elements — q_out of mi_rope_kv_append_* and the q slice of a fused projection both fit;
+ *   group      query heads per k / v head, any value ≥ 1; items and T have no bound but int32 (an item loop serves what
+ *              lies beyond the grid);
+ *   new_lens, new_lens_count   NULL, or int32 on the device, 4-byte aligned, 1 or items / heads entries: batch item b has
+ *              n = clamp(new_lens[b], 0, T) new tokens, standing in the LAST n of the T slots (mi_rope_kv_append_*'s
+ *              convention).  Slot t holds a token iff t ≥ T − n and pos ≥ 0;
+ *   out, lse   out as in the decode entries, lse float32 [items · group][T].  EVERY row of both is written exactly once by
+ *              the one launch: a slot without a token, and a token that sees nothing, get a zero row and −inf.
+ * Order of summation: a workgroup owns the positions [64r, 64r + 64) ∩ [k_len − T, k_len) of one query head and walks the
+ * list of layout row r in list order, as mi_block_attention_fwd_ex_* with causal = 1 and q_lens = k_lens walks it: for a cache
+ * whose seen table entries are in range, the out and lse rows of existing tokens have the BITS of that entry on the gathered
+ * (fp8: widened) cache with q scattered to its positions and the layout repeated per query head.  So a paged call has the
+ * bits of the contiguous call on the gathered cache, an fp8 call with NULL scales those of the 2-byte call on the widened
+ * cache, a strided cache those of its contiguous clone; a row's bits depend on its item's operands, its list and pos, never
+ * on T, new_lens, the batch or the launch.  With scales: a score is multiplied by scale · k_scale[h], one fp32 product; with
+ * a non-NULL v_scale the stored element is narrow(fl32((O / L) · v_scale[h])).
+ * Never read: positions outside the listed blocks, blocks above the diagonal, positions at or beyond k_len (staged as
+ * zeros), the gaps between rows, pages whose table entry lies outside [0, pages) — such an entry hides its page's keys.
+ * No atomics, no workspace, no read-back: graph-capturable while k_lens, new_lens, the cache, the table and the scales
+ * change in place.
+ * Validation before any HIP call: what the decode entries refuse through the same cache checks (but no bound on group,
+ * items or T), a misaligned new_lens or a count other than 1 or items / heads → MI_EINVAL; items == 0 or T == 0 → MI_OK,
+ * nothing touched.
+ * ------------------------------------------------------------------------ */
+#define MI_BLOCK_ATTENTION_PREFILL_LIST \
+  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T, int32_t Smax
+#define MI_BLOCK_ATTENTION_PREFILL_TABLE const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page
+/* (paged: k, batchK, v, batchV of the operand list are k_pages, pageK, v_pages, pageV) */
+#define MI_BLOCK_ATTENTION_PREFILL_OPERANDS(CT)                                                                                \
+  const uint16_t *q, int64_t ldq, int64_t headQ, int64_t batchQ, const CT *k, int64_t ldk, int64_t headK, int64_t batchK,      \
+      const CT *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count,                      \
+      const int32_t *new_lens, int32_t new_lens_count, int32_t group, float scale
+#define MI_BLOCK_ATTENTION_PREFILL_SCALES const float *k_scale, int32_t k_scale_count, const float *v_scale, int32_t v_scale_count
+#define MI_BLOCK_ATTENTION_PREFILL_OUT uint16_t *out, int64_t ldo, int64_t strideO, float *lse, mi_stream_t stream
+int mi_block_attention_prefill_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                    MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_prefill_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                   MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_prefill_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                          MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_prefill_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                         MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_prefill_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                        MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_prefill_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                       MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_prefill_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                              MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                              MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_prefill_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                             MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                             MI_BLOCK_ATTENTION_PREFILL_OUT);
+
+/* ------------------------------------------------------------------------ *
  * The fused KV-cache append: the write side of the decode entries above.  ONE launch writes the keys AND the
  * values of the T newest tokens of every k / v item into the cache of mi_block_attention_decode_* — contiguous or paged,
  * 2-byte or e4m3fn bytes — at the positions the lengths name.

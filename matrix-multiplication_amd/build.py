@@ -57,7 +57,7 @@ def _run(cmd, verbose):
 
 # Units whose kernels sit at the edge of the register file: compiled with the compiler's resource-usage remarks, which are
 # kept as build/<unit>.resources.txt (one line per kernel instantiation); a vector-register spill fails the build.
-RESOURCE_REPORTS = ("block_attention", "block_attention_decode")
+RESOURCE_REPORTS = ("block_attention", "block_attention_decode", "block_attention_prefill")
 _RESOURCE_FIELDS = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill", "LDS Size [bytes/block]",
                     "Occupancy [waves/SIMD]")
 

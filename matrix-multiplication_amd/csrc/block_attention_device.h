@@ -1,6 +1,7 @@
-// Device-side pieces shared by the two block-sparse attention units — block_attention.hip (forward and backward over
-// workgroup tiles staged in LDS) and block_attention_decode.hip (one wave per list entry, k fragments straight from global
-// memory) — said once: the block size, the transposed image of a walk block, a score-shaped tile as the B
+// Device-side pieces shared by the three block-sparse attention units — block_attention.hip (forward and backward over
+// workgroup tiles staged in LDS), block_attention_decode.hip (one wave per list entry, k fragments straight from global
+// memory) and block_attention_prefill.hip (the forward's tiles fed through the KV cache's addressing, §3.27) — said once
+// (DESIGN.md §3.24): the block size, the transposed image of a walk block, a score-shaped tile as the B
 // operand of the product that sums over the walk rows, that product, and the reductions over a row's four lanes.  The two
 // `score` forms, the walkers and the Args stay with their units: one reads LDS, the other registers.  Not installed.
 // Everything here has internal linkage (an anonymous namespace per including unit).

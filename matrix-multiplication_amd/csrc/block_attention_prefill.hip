@@ -1,0 +1,488 @@
+// Block-sparse prefill attention over the KV cache in bfloat16 and float16 on the matrix cores: the T newest tokens of every
+// item — a whole prompt, or one chunk of it behind a prefix that is already cached — against a key / value cache in any of
+// its four forms, out = softmax(scale · q·kᵀ + mask) · v.  Token t of an item of length k_len stands at pos = k_len − T + t and
+// sees key j iff j ≤ pos and the CSR block layout lists 64-block (pos / 64, j / 64): the decode call's rule, word for word.
+// Forward only.  q and out are of one type T ∈ {bf16, fp16} (2-byte bit patterns at the C-ABI); the cache holds T or e4m3fn.
+//
+// What it computes (contract of include/mi_spmm.h, mi_block_attention_prefill_* — DESIGN.md §3.27):
+//  * The training forward, placed in the cache.  A workgroup owns one POSITION TILE of one query head: the positions
+//    [64r, 64r + 64) of layout row r that fall inside the item's [k_len − T, k_len).  Own row i of the tile is position
+//    64r + i, that is q row t = 64r + i − (k_len − T); k_len − T need not be a multiple of 64, so the first and the last tile
+//    of an item are partial.  The tile walks the list of layout row r in list order, skips listed blocks J > r, masks the
+//    diagonal block by position and the keys ≥ k_len as LENS masks them — block_attention_fwd_kernel<T, D, true, true>
+//    (block_attention.hip) statement for statement: the score MFMAs from the LDS row image, the online softmax, pack_tile,
+//    accumulate, group_max / group_sum, one accumulator per element, one rounding at the store.  For a cache whose seen
+//    table entries are in range, out and lse rows of existing tokens have the bits of that kernel with q_lens = k_lens on
+//    the gathered (widened) cache and q scattered to its positions.  The bits of a row depend on its item's operands, its
+//    list and pos: never on T, new_lens, B, the neighbours or the launch.
+//  * Slot t holds a token iff t ≥ T − clamp(new_lens[b], 0, T) and pos ≥ 0.  A slot without a token is a zero fragment, never
+//    an MFMA operand; its out row is zero and its lse −inf, as for a token that sees nothing; no walk is spent on a tile
+//    without a token.  Every row of out is written exactly once by the launch: slot t belongs to tile
+//    ⌊pos / 64⌋ − ⌊(k_len − T) / 64⌋ ∈ [0, ⌈T / 64⌉], so ⌈T / 64⌉ + 1 tiles per item from the shape alone.
+//  * Nothing outside is read: the cache through its own strides, q through its own; a block outside the list, a block above
+//    the diagonal, rows at or beyond k_len (staged as zeros), the gaps between rows and pages whose table entry lies outside
+//    [0, P) are never loaded.  Such an entry hides its page's keys (§3.19).  Offsets are clamped to nnz, a column outside
+//    the grid is skipped.
+//  * fp8 (§3.20): a lane loads the 8 bytes of its 8 elements and widens them on the way into LDS (exact); both images hold
+//    T.  A score is multiplied by scale · k_scale[h], one fp32 product taken once per workgroup; with a v_scale the stored
+//    element is T::down((O · inv) · v_scale[h]), the product an fp32 value of its own before it is narrowed (§3.20's guard).
+//    Without a v_scale the store is the training kernel's statement, so an fp8 call without scales has the bits of the
+//    2-byte call on the widened cache.
+//
+// Kernel: a 1-d grid over (k / v item, tile, query head of the group), 256 threads, an item loop beyond the grid.  The G
+// heads of one (item, k / v head, tile) walk the same tiles; they stand 8 workgroups apart (work unit u = 8G·a + 8g + s is
+// head g of slot 8a + s, a slot one (item, tile)), where the guide observes — and does not promise — a shared L2.
+// Staging is the training kernel's double-buffered tile into Ks and Vt, its rows addressed through the cache form
+// (block_attention_cache_device.h: contiguous / pages ≥ 64 / pages of 16, 32 keys — there a lane's four rows lie in one
+// page, 4 divides 16); the table is read one list entry ahead.  Tile, score, store_own and next_block are copies of
+// block_attention.hip's private pieces with the cache form added (that unit stays as it is); kB, the images' strides,
+// pack_tile, accumulate, group_max / group_sum are block_attention_device.h's; mfma<T>, half_of, store_rc mfma_device.h's.
+#include <type_traits>
+
+#include "block_attention_cache_device.h"
+
+namespace {
+
+constexpr int kSpreadHeads = 8;      // workgroups between two heads of a group on one (item, tile)
+constexpr long kMaxGrid = 1L << 16;  // workgroups of a launch: work units beyond are served by the item loop
+
+struct Args {
+  const int32_t* rowptr;  // [layouts][blocks + 1], with the layouts' bases
+  const int32_t* col;     // [nnz], layout-local block columns
+  long nnz;
+  int layouts, blocks;  // blocks = Smax / 64
+  int heads;            // k / v heads per batch item: k / v item c is head c % heads of batch item c / heads
+  int group, T, tiles;  // tiles = ⌈T / 64⌉ + 1 position tiles per item
+  long smax;
+  long slots, units;  // slots = items · tiles; units = ⌈slots / 8⌉ · 8 · group
+  const uint16_t* q;  // query head g of k / v item c, token t: q + (c / heads) · batchQ + ((c % heads) · group + g) · headQ + t · ldq
+  long ldq, headQ, batchQ;
+  const void *k, *v;  // the cache, as in block_attention_decode.hip
+  long ldk, headK, batchK, ldv, headV, batchV;
+  const int32_t* k_lens;  // [items / lens_div], clamped to [0, Smax] where read
+  int lens_div;
+  const int32_t* new_lens;  // [B] or [1], clamped to [0, T] where read; null (NEWLENS false): T
+  int new_lens_one;         // one entry for all batch items
+  float scale;
+  uint16_t* out;  // query item c · group + g, token t: out + (c · group + g) · strideO + t · ldo
+  long ldo, strideO;
+  float* lse;  // [items · group][T]
+  const int32_t* table;
+  long table_ld;
+  int pages, page_shift;
+  long pageK, pageV;
+  const float *k_scale, *v_scale;
+  int k_scale_count, v_scale_count;
+};
+
+// One 64 × D block of the cache in registers: unit u = tid < 2D holds rows 4(u & 15) … + 3, columns 8(u >> 4) … + 7 — 16 bytes
+// of T or 8 e4m3fn bytes a row.  Rows at or beyond `limit` (the part of the block beyond the item's length) and the rows of a
+// page outside the pool are zero rows, whatever memory holds.
+template <int D, class F, class E, int FORM>
+struct Tile {
+  F v[4];
+  // `src`: the cache or pool at the item's head; J: the block; e, ok: its table entries and their validity (paged forms)
+  __device__ __forceinline__ void load(const E* src, long ld, long pageStride, int J, const int (&e)[4], unsigned ok, int in_page,
+                                       int tid, int limit) {
+    if (tid < 2 * D) {
+      const int row = 4 * (tid & 15);
+      const E* p;
+      bool valid = true;
+      if constexpr (FORM == kContiguous) {
+        p = src + ((long)J * kB + row) * ld + 8 * (tid >> 4);
+      } else if constexpr (FORM == kPaged) {
+        p = src + (long)e[0] * pageStride + (long)(((J * kB) & in_page) + row) * ld + 8 * (tid >> 4);
+        valid = ok != 0;
+      } else {  // the lane's four rows lie in fragment row / 16, so in one page
+        const int f = (tid & 15) >> 2;
+        const int mine = f == 0 ? e[0] : f == 1 ? e[1] : f == 2 ? e[2] : e[3];
+        p = src + (long)mine * pageStride + (long)(row & in_page) * ld + 8 * (tid >> 4);
+        valid = (ok >> f) & 1u;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (valid && row + i < limit)
+          v[i] = *reinterpret_cast<const F*>(p + i * ld);
+        else
+          v[i] = zero_frag<F>();
+      }
+    }
+  }
+  // the row image [64][D + 8], in T
+  template <class T>
+  __device__ __forceinline__ void store_rows(unsigned short* R, int tid) const {
+    if (tid < 2 * D) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(R + (4 * (tid & 15) + i) * (D + 8) + 8 * (tid >> 4)) = widen<T>(v[i]);
+    }
+  }
+  // the transposed image [D][64 + 8], in T: the unit is store_rc's, the walk rows its k
+  template <class T>
+  __device__ __forceinline__ void store_transposed(unsigned short* Tt, int tid) const {
+    if (tid < 2 * D) {
+      const uint4 x[4] = {widen<T>(v[0]), widen<T>(v[1]), widen<T>(v[2]), widen<T>(v[3])};
+      store_rc(Tt, x, tid);
+    }
+  }
+};
+
+// acc[f][r] = ⟨walk row 16f + 4lg + r, own row li⟩ over d, from the row image R of the walk block
+template <class T, int D>
+__device__ __forceinline__ void score(f32x4 (&acc)[4], const unsigned short* R, const uint4 (&own)[D / 32], int li, int lg) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s) {
+      const uint4 a = *reinterpret_cast<const uint4*>(R + (16 * f + li) * (D + 8) + 32 * s + 8 * lg);
+      acc[f] = mfma<T>(a, own[s], acc[f]);
+    }
+  }
+}
+
+// The stored element of the training kernel's statement T::down(x · mul), AS ITS KERNELS HOLD IT.  For float16 the compiler
+// makes the product and the narrowing of block_attention_fwd_kernel ONE v_fma_mixlo_f16 — a single rounding of the exact
+// product, in all D / 4 stores of a lane (read from that unit's assembly; §3.20 met the same fold in the decode walk).  Left
+// to the compiler here, the 2-byte kernels were folded likewise but the fp8 kernels only in part (30 of 32 stores at D = 128),
+// which broke "an fp8 call without scales has the bits of the 2-byte call" in float16.  So the instruction is written out:
+// the bits do not depend on the compiler's choice in this unit.  bfloat16 has no such instruction and is never folded.
+template <class T>
+__device__ __forceinline__ unsigned down_product(float x, float mul) { return T::down(x * mul); }
+template <>
+__device__ __forceinline__ unsigned down_product<F16>(float x, float mul) {
+  unsigned r;
+  asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(r) : "v"(x), "v"(mul));  // (writes the low half only)
+  return r & 0xffffu;
+}
+
+// rows [d][own row] → the lane's own row `row`, columns 16fd + 4lg … + 3, each value times `mul`, rounded once
+template <class T, int D>
+__device__ __forceinline__ void store_own(const f32x4 (&acc)[D / 16], float mul, uint16_t* row, int lg) {
+#pragma unroll
+  for (int fd = 0; fd < D / 16; ++fd) {
+    const f32x4 x = acc[fd];
+    *reinterpret_cast<uint2*>(row + 16 * fd + 4 * lg) =
+        uint2{down_product<T>(x[0], mul) | (down_product<T>(x[1], mul) << 16), down_product<T>(x[2], mul) | (down_product<T>(x[3], mul) << 16)};
+  }
+}
+
+// … times `vs`, an fp8 cache's v_scale: the last product is an fp32 value of its own before it is narrowed (DESIGN.md §3.20:
+// left alone, the product and the narrowing to float16 become one v_fma_mixlo_f16, which rounds the exact product once)
+template <class T, int D>
+__device__ __forceinline__ void store_own_scaled(const f32x4 (&acc)[D / 16], float mul, float vs, uint16_t* row, int lg) {
+#pragma unroll
+  for (int fd = 0; fd < D / 16; ++fd) {
+    f32x4 x = acc[fd];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float y = (x[r] * mul) * vs;
+      asm("" : "+v"(y));  // (no instruction)
+      x[r] = y;
+    }
+    *reinterpret_cast<uint2*>(row + 16 * fd + 4 * lg) = uint2{pack2<T>(x[0], x[1]), pack2<T>(x[2], x[3])};
+  }
+}
+
+// the next listed block at or after p that is computed: inside the grid cut to the item's length, not above the diagonal
+__device__ __forceinline__ int next_block(const int32_t* col, int p, int end, int own_block, int walk_blocks) {
+  for (; p < end; ++p) {
+    const int j = col[p];
+    if ((unsigned)j >= (unsigned)walk_blocks) continue;
+    if (j > own_block) continue;
+    break;
+  }
+  return p;
+}
+
+template <class TC, int D, int FORM, bool NEWLENS>
+__global__ __launch_bounds__(256) void block_attention_prefill_kernel(Args a) {
+  typedef typename Operand<TC>::type T;
+  constexpr bool FP8 = Operand<TC>::fp8;
+  typedef typename Cache<FP8>::elem E;
+  typedef typename Cache<FP8>::frag F;
+  __shared__ __attribute__((aligned(16))) unsigned short Ks[kB * (D + 8)];
+  __shared__ __attribute__((aligned(16))) unsigned short Vt[D * kTStr];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
+  const int G = a.group;
+  const int in_page = FORM == kContiguous ? 0 : (1 << a.page_shift) - 1;
+  for (long u = blockIdx.x; u < a.units; u += gridDim.x) {
+    // the G heads of a slot stand 8 work units apart
+    const long slot = u / ((long)kSpreadHeads * G) * kSpreadHeads + (u & (kSpreadHeads - 1));
+    if (slot >= a.slots) continue;  // (the padding of the last eight)
+    const int g = (int)((u / kSpreadHeads) % G);
+    const int c = (int)(slot / a.tiles), x = (int)(slot - (long)c * a.tiles);
+    const int bi = c / a.heads, h = c - bi * a.heads;
+    int klen = a.k_lens[c / a.lens_div];
+    klen = klen < 0 ? 0 : klen > a.smax ? (int)a.smax : klen;
+    int n = a.T;  // the item's new tokens: they stand in the last n of the T slots
+    if (NEWLENS) {
+      n = a.new_lens[a.new_lens_one ? 0 : bi];
+      n = n < 0 ? 0 : n > a.T ? a.T : n;
+    }
+    const int start = klen - a.T;                         // the position of slot 0 (negative: slots without a token)
+    const int first = klen - n < 0 ? 0 : klen - n;        // the existing tokens stand at [first, klen)
+    const int r = (start >> 6) + x;                       // the tile's layout row: ⌊start / 64⌋ + x
+    const int pos = r * kB + 16 * w + li;                 // the own row's position …
+    const long t = (long)pos - start;                     // … and its slot
+    const bool slot_ok = t >= 0 && t < a.T;               // the row is a row of q and out
+    const bool token = slot_ok && pos >= first;           // … that holds a token (pos < k_len follows from t < T)
+    const bool any = first < klen && r * kB + kB > first && r * kB < klen;  // the tile holds a token
+    const long item = (long)c * G + g;
+    uint16_t* orow = a.out + item * a.strideO + t * a.ldo;
+    if (!any) {  // nothing to walk: the zero rows of the slots it owns, if any
+      if (slot_ok) {
+#pragma unroll
+        for (int fd = 0; fd < D / 16; ++fd) *reinterpret_cast<uint2*>(orow + 16 * fd + 4 * lg) = uint2{0u, 0u};
+        if (lg == 0) a.lse[item * a.T + t] = -INFINITY;
+      }
+      continue;
+    }
+    // (0 ≤ r < blocks from here on: 64r + 63 ≥ first ≥ 0 and 64r < k_len ≤ Smax)
+    // (a pool has no batch stride: the item's pages come from its table row)
+    const E* K = static_cast<const E*>(a.k) + (FORM == kContiguous ? (long)bi * a.batchK : 0L) + (long)h * a.headK;
+    const E* V = static_cast<const E*>(a.v) + (FORM == kContiguous ? (long)bi * a.batchV : 0L) + (long)h * a.headV;
+    const int32_t* trow = FORM == kContiguous ? nullptr : a.table + (long)bi * a.table_ld;
+    // what multiplies a score: scale, or in the fp8 forms scale · k_scale[h] — one fp32 product per workgroup
+    const float sc = FP8 ? a.scale * head_scale(a.k_scale, a.k_scale_count, h) : a.scale;
+    const int kblocks = (klen + kB - 1) / kB;
+    long beg, end;
+    {
+      const int32_t* rp = a.rowptr + (long)(c % a.layouts) * (a.blocks + 1);
+      beg = rp[r], end = rp[r + 1];
+      beg = beg < 0 ? 0 : beg;
+      end = end > a.nnz ? a.nnz : end;
+    }
+    const int pend = (int)end;
+
+    uint4 qf[D / 32];  // the wave's 16 own rows as B fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of row li
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s) qf[s] = uint4{0u, 0u, 0u, 0u};
+    if (token) {
+      const uint16_t* qrow = a.q + (long)bi * a.batchQ + ((long)h * G + g) * a.headQ + t * a.ldq;
+#pragma unroll
+      for (int s = 0; s < D / 32; ++s) qf[s] = *reinterpret_cast<const uint4*>(qrow + 32 * s + 8 * lg);
+    }
+    f32x4 o[D / 16];
+#pragma unroll
+    for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+
+    // The tile whose loads are in flight (J, its table entries e, their validity ok) and the entry after it (pn, Jn, en): the
+    // column and the table entries of an entry are read ONE ENTRY AHEAD, right after the loads of the entry before it were
+    // issued, so the chain col[p] → table → tile never stands in front of a tile's loads.
+    Tile<D, F, E, FORM> tk, tv;
+    int J = 0, Jn = 0, pn = pend, e[4] = {0, 0, 0, 0}, en[4] = {0, 0, 0, 0};
+    unsigned ok = 0xfu;
+    auto issue = [&]() {
+      tk.load(K, a.ldk, a.pageK, J, e, ok, in_page, tid, klen - J * kB);
+      tv.load(V, a.ldv, a.pageV, J, e, ok, in_page, tid, klen - J * kB);
+    };
+    auto look_ahead = [&](int from) {
+      pn = next_block(a.col, from, pend, r, kblocks);
+      if (pn < pend) {
+        Jn = a.col[pn];
+        if constexpr (FORM != kContiguous) read_pages<FORM>(en, trow, Jn, a.page_shift);
+      }
+    };
+    int p = next_block(a.col, (int)beg, pend, r, kblocks);
+    if (p < pend) {
+      J = a.col[p];
+      if constexpr (FORM != kContiguous) {
+        read_pages<FORM>(e, trow, J, a.page_shift);
+        ok = valid_pages(e, a.pages);
+      }
+      issue();
+      look_ahead(p + 1);
+    }
+    while (p < pend) {
+      const int Jc = J;           // the block computed in this turn …
+      const unsigned seen = ok;   // … and the fragments of it that lie in a page (paged forms)
+      __syncthreads();  // the previous block's reads are done
+      tk.template store_rows<T>(Ks, tid);
+      tv.template store_transposed<T>(Vt, tid);
+      __syncthreads();
+      p = pn;
+      if (p < pend) {  // the next block's loads are in flight while this one is computed
+        J = Jn;
+        if constexpr (FORM != kContiguous) {
+#pragma unroll
+          for (int f = 0; f < 4; ++f) e[f] = en[f];
+          ok = valid_pages(e, a.pages);
+        }
+        issue();
+        look_ahead(p + 1);
+      }
+      const int kleft = klen - Jc * kB;  // keys of this block that exist
+      f32x4 s[4];
+      score<T, D>(s, Ks, qf, li, lg);
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          float x = s[f][rr] * sc;
+          if (Jc == r && 16 * f + 4 * lg + rr > 16 * w + li) x = -INFINITY;
+          if (16 * f + 4 * lg + rr >= kleft) x = -INFINITY;
+          s[f][rr] = x;
+        }
+      if (FORM != kContiguous && seen != 0xfu) {  // keys of a page outside the pool (a uniform branch: tables are in range as a rule)
+#pragma unroll
+        for (int f = 0; f < 4; ++f)
+          if (!((seen >> f) & 1u)) s[f] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      }
+      float mt = -INFINITY;
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) mt = fmaxf(mt, s[f][rr]);
+      const float mn = fmaxf(m, group_max(mt));
+      const float alpha = m == mn ? 1.f : __expf(m - mn);  // (−inf stays: nothing seen yet)
+      float sum = 0.f;
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const float ex = s[f][rr] == -INFINITY ? 0.f : __expf(s[f][rr] - mn);
+          s[f][rr] = ex;
+          sum += ex;
+        }
+      l = l * alpha + sum;  // this lane's share of the row sum; the four shares meet after the walk
+      m = mn;
+#pragma unroll
+      for (int fd = 0; fd < D / 16; ++fd)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) o[fd][rr] *= alpha;
+      uint4 pb[2];
+      pack_tile<T>(pb, s);
+      accumulate<T, D>(o, Vt, pb, li, lg);
+    }
+    l = group_sum(l);
+    if (!token) {
+      l = 0.f;
+#pragma unroll
+      for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const float inv = l == 0.f ? 0.f : 1.f / l;
+    if (slot_ok) {
+      if (FP8 && a.v_scale != nullptr)
+        store_own_scaled<T, D>(o, inv, head_scale(a.v_scale, a.v_scale_count, h), orow, lg);
+      else
+        store_own<T, D>(o, inv, orow, lg);
+      if (lg == 0) a.lse[item * a.T + t] = l == 0.f ? -INFINITY : m + __logf(l);
+    }
+    __syncthreads();  // the next work unit restages
+  }
+}
+
+template <class TC, int D, int FORM>
+int launch_form(const Args& a, hipStream_t s) {
+  const dim3 grid((unsigned)(a.units < kMaxGrid ? a.units : kMaxGrid));
+  if (a.new_lens)
+    hipLaunchKernelGGL((block_attention_prefill_kernel<TC, D, FORM, true>), grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((block_attention_prefill_kernel<TC, D, FORM, false>), grid, dim3(256), 0, s, a);
+  return mi::check_launch();
+}
+
+template <class T, int D, bool FP8>
+int launch(const Args& a, hipStream_t s) {
+  typedef std::conditional_t<FP8, Fp8<T>, T> TC;  // the cache element type is part of the kernel's first parameter
+  if (!a.table) return launch_form<TC, D, kContiguous>(a, s);
+  return a.page_shift >= 6 ? launch_form<TC, D, kPaged>(a, s) : launch_form<TC, D, kPagedSmall>(a, s);
+}
+
+// Every check comes before the first HIP call.  page == 0: the contiguous cache, `outerK` / `outerV` its batch strides and
+// no table; page > 0: a pool of `pages` pages of `page` keys, `outerK` / `outerV` its page strides, Smax = the table's
+// logical pages · page.  FP8: k and v are e4m3fn bytes (their strides multiples of 16) with the two scales of `scales`.
+template <class T, bool FP8 = false>
+int prefill_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T_,
+                  int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq, int64_t headQ, int64_t batchQ, const void* k, int64_t ldk,
+                  int64_t headK, int64_t outerK, const void* v, int64_t ldv, int64_t headV, int64_t outerV, const int32_t* k_lens,
+                  int32_t lens_count, const int32_t* new_lens, int32_t new_lens_count, int32_t group, float scale, uint16_t* out,
+                  int64_t ldo, int64_t strideO, float* lse, hipStream_t s, const int32_t* table = nullptr, int64_t table_ld = 0,
+                  int32_t pages = 0, int32_t page = 0, const Scales& scales = Scales()) {
+  if (!cache_form_ok(FP8, scales, heads, Smax, pages, page)) return MI_EINVAL;
+  if (group < 1 || !takes_width(D)) return MI_EINVAL;
+  const bool paged = page != 0;
+  if (nnz < 0 || layouts < 0 || items < 0 || heads < 0 || T_ < 0 || Smax < 0 || Smax % kB != 0) return MI_EINVAL;
+  if (nnz > 0x7fffffffLL) return MI_ERANGE;
+  if (items == 0 || T_ == 0) return MI_OK;
+  if (layouts == 0 || heads == 0 || items % heads != 0 || lens_count < 1 || items % lens_count != 0) return MI_EINVAL;
+  if (!rowptr || (nnz > 0 && !col) || !k_lens || !aligned4(k_lens)) return MI_EINVAL;
+  if (new_lens && (!aligned4(new_lens) || (new_lens_count != 1 && new_lens_count != items / heads))) return MI_EINVAL;
+  if (!lse || !aligned4(lse)) return MI_EINVAL;
+  if (!q || !mi::aligned16(q) || !stride_ok(ldq) || !stride_ok(headQ) || !stride_ok(batchQ) || (T_ > 1 && ldq < D)) return MI_EINVAL;
+  if (!out || !mi::aligned16(out) || ldo < D || !stride_ok(ldo) || !stride_ok(strideO)) return MI_EINVAL;
+  const bool reads = nnz > 0 && Smax > 0 && (!paged || pages > 0);  // (an empty pool is never read: every entry of the table is invalid)
+  if (!cache_operands_ok(FP8, reads, Smax, D, k, ldk, headK, outerK, v, ldv, headV, outerV, table, table_ld, page)) return MI_EINVAL;
+  Args a = {};  // (zeroed: the 2-byte entries leave k_scale / v_scale null)
+  a.rowptr = rowptr, a.col = col, a.nnz = nnz, a.layouts = layouts, a.blocks = Smax / kB, a.heads = heads, a.group = group;
+  a.T = T_, a.tiles = (int)(((long)T_ + kB - 1) / kB + 1), a.smax = Smax;
+  a.slots = (long)items * a.tiles;
+  a.units = (a.slots + kSpreadHeads - 1) / kSpreadHeads * kSpreadHeads * group;
+  a.q = q, a.ldq = ldq, a.headQ = headQ, a.batchQ = batchQ;
+  a.k = k, a.ldk = ldk, a.headK = headK, a.v = v, a.ldv = ldv, a.headV = headV;
+  if (paged && Smax > 0) {  // (Smax == 0: no list has an entry, the contiguous form stores the zero rows)
+    a.table = table, a.table_ld = table_ld, a.pages = pages, a.page_shift = __builtin_ctz((unsigned)page);
+    a.pageK = outerK, a.pageV = outerV;
+  } else {
+    a.batchK = outerK, a.batchV = outerV;
+  }
+  a.k_lens = k_lens, a.lens_div = items / lens_count, a.new_lens = new_lens, a.new_lens_one = new_lens_count == 1, a.scale = scale;
+  a.out = out, a.ldo = ldo, a.strideO = strideO, a.lse = lse;
+  if (FP8) a.k_scale = scales.k, a.k_scale_count = scales.k_count, a.v_scale = scales.v, a.v_scale_count = scales.v_count;
+  switch (D) {
+    case 32: return launch<T, 32, FP8>(a, s);
+    case 64: return launch<T, 64, FP8>(a, s);
+    case 96: return launch<T, 96, FP8>(a, s);
+    default: return launch<T, 128, FP8>(a, s);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+#define MI_PREFILL_PASS                                                                                                       \
+  rowptr, col, nnz, layouts, items, heads, T, Smax, D, q, ldq, headQ, batchQ, k, ldk, headK, batchK, v, ldv, headV, batchV,  \
+      k_lens, lens_count, new_lens, new_lens_count, group, scale, out, ldo, strideO, lse, static_cast<hipStream_t>(stream)
+// (k, batchK and v, batchV stand for k_pages, pageK and v_pages, pageV of the header)  A page of 0 keys would name the
+// contiguous form: it is refused here like every page that is no power of two ≥ 16.
+#define MI_PREFILL_PAGED_PASS MI_PREFILL_PASS, block_table, table_ld, pages, page
+#define MI_PREFILL_SCALES Scales{k_scale, k_scale_count, v_scale, v_scale_count}
+
+int mi_block_attention_prefill_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                    MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return prefill_entry<Bf16>(MI_PREFILL_PASS);
+}
+int mi_block_attention_prefill_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                   MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return prefill_entry<F16>(MI_PREFILL_PASS);
+}
+int mi_block_attention_prefill_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                          MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<Bf16>(MI_PREFILL_PAGED_PASS);
+}
+int mi_block_attention_prefill_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                         MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<F16>(MI_PREFILL_PAGED_PASS);
+}
+int mi_block_attention_prefill_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                        MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return prefill_entry<Bf16, true>(MI_PREFILL_PASS, nullptr, 0, 0, 0, MI_PREFILL_SCALES);
+}
+int mi_block_attention_prefill_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                       MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return prefill_entry<F16, true>(MI_PREFILL_PASS, nullptr, 0, 0, 0, MI_PREFILL_SCALES);
+}
+int mi_block_attention_prefill_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                              MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                              MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<Bf16, true>(MI_PREFILL_PAGED_PASS, MI_PREFILL_SCALES);
+}
+int mi_block_attention_prefill_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                             MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                             MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_PAGED_PASS, MI_PREFILL_SCALES);
+}
+
+}  // extern "C"

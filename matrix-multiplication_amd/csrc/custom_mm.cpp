@@ -51,6 +51,7 @@ namespace {
 #include "custom_mm_block_attention.inc"
 #include "custom_mm_kv_cache.inc"
 #include "custom_mm_block_attention_decode.inc"
+#include "custom_mm_block_attention_prefill.inc"
 #include "custom_mm_kv_append.inc"
 #include "custom_mm_rope_kv_append.inc"
 #include "custom_mm_bsr.inc"
@@ -212,6 +213,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("block_attention_decode_paged_fp8", &block_attention_decode_paged_fp8,
         "(offsets, columns, nnz, q, k_pages, v_pages [P, Hkv, page, D] float8_e4m3fn, block_table int32 [B, W], k_lens, scale, "
         "k_scale, v_scale, chunk, out, lse): block_attention_decode_paged over an fp8 pool");
+  m.def("block_attention_prefill", &block_attention_prefill,
+        "(offsets [layouts, Smax/64+1], columns, nnz, q [B, Hq, T, D] through its own strides, k, v [B, Hkv, Smax, D] through "
+        "theirs, k_lens int32 [B] or [1], new_lens None or int32 [B] or [1], scale, out, lse [B, Hq, T]): the T newest tokens "
+        "against the cache in 64-row position tiles, the bits of the causal training forward placed in the cache");
+  m.def("block_attention_prefill_paged", &block_attention_prefill_paged,
+        "(offsets, columns, nnz, q, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, new_lens, scale, out, "
+        "lse): block_attention_prefill over a pool of pages; an entry outside [0, P) hides its page's keys");
+  m.def("block_attention_prefill_fp8", &block_attention_prefill_fp8,
+        "(offsets, columns, nnz, q, k, v [B, Hkv, Smax, D] float8_e4m3fn, k_lens, new_lens, scale, k_scale, v_scale (None or "
+        "float32 device tensors of 1 or Hkv entries), out, lse): block_attention_prefill over an fp8 cache");
+  m.def("block_attention_prefill_paged_fp8", &block_attention_prefill_paged_fp8,
+        "(offsets, columns, nnz, q, k_pages, v_pages [P, Hkv, page, D] float8_e4m3fn, block_table, k_lens, new_lens, scale, "
+        "k_scale, v_scale, out, lse): block_attention_prefill_paged over an fp8 pool");
   m.def("kv_append", &kv_append,
         "(k_new, v_new [B, Hkv, T, D] bfloat16 / float16 through their own strides, k, v [B, Hkv, Smax, D] of that dtype or "
         "float8_e4m3fn, k_lens int32 [B] or [1] — the lengths AFTER the append —, k_scale, v_scale (None or float32 device tensors "

@@ -1,6 +1,6 @@
-// Device-side pieces shared by the five bfloat16 / float16 units on the matrix cores — gemm_lowp.hip, bsr_mm.hip and
-// bsr_linear.hip (through bsr_device.h), block_attention.hip and block_attention_decode.hip (through
-// block_attention_device.h) — said once: the wrapper round v_mfma_f32_16x16x32_{bf16,f16}, the element
+// Device-side pieces shared by the six bfloat16 / float16 units on the matrix cores — gemm_lowp.hip, bsr_mm.hip and
+// bsr_linear.hip (through bsr_device.h), block_attention.hip, block_attention_decode.hip and block_attention_prefill.hip
+// (through block_attention_device.h) — said once: the wrapper round v_mfma_f32_16x16x32_{bf16,f16}, the element
 // of an 8-element piece, the row stride of a staged k-tile and the transposing store of a rows-contiguous operand.  The
 // element types are lowp_device.h's.  load8 and the wave's MFMA loop are NOT here: sharing them changed kernels (§3.24).
 // Not installed.  Everything here has internal linkage (an anonymous namespace per including unit).

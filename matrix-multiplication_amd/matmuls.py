@@ -1832,37 +1832,44 @@ def _check_cache_strides(what, name, t, D, outer='batch', unit=8):
         raise ValueError(f'{what}: {name}\'s data pointer must be 16-byte aligned (the cache is never copied)')
 
 
-def _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8=False):
+def _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8=False, sizes_text=None):
     '''What block_sparse_attention_decode and its paged form refuse before they look at a shape: the layout's and the
     operands' kinds, block, chunk.  `names` are the two cache operands' names in the messages.  fp8: the cache is
-    float8_e4m3fn (_check_fp8_cache) and only q is bfloat16 / float16.'''
+    float8_e4m3fn (_check_fp8_cache) and only q is bfloat16 / float16.  sizes_text: what the messages name as accepted
+    (None: the decode calls').'''
+    fp8_text, sizes_text = sizes_text, sizes_text or _DECODE_SIZES_TEXT
     _check_csr(what, 'layout', layout)
     if fp8:
-        _check_lowp_operands(what, (('q', q),), _DECODE_SIZES_TEXT)
-        _check_fp8_cache(what, ((names[0], k), (names[1], v)))
+        _check_lowp_operands(what, (('q', q),), sizes_text)
+        _check_fp8_cache(what, ((names[0], k), (names[1], v)), fp8_text)
     else:
-        _check_lowp_operands(what, (('q', q), (names[0], k), (names[1], v)), _DECODE_SIZES_TEXT)
+        _check_lowp_operands(what, (('q', q), (names[0], k), (names[1], v)), sizes_text)
     if isinstance(block, bool) or not isinstance(block, int) or block <= 0 or block % _BLOCK_TILE != 0:
-        raise ValueError(f'{what}: block must be a positive multiple of 64, got {block!r} (accepted: {_DECODE_SIZES_TEXT})')
+        raise ValueError(f'{what}: block must be a positive multiple of 64, got {block!r} (accepted: {sizes_text})')
     if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1 or chunk >= 2 ** 31):
         raise ValueError(f'{what}: chunk must be None or a positive int, got {chunk!r}')
 
 
-def _check_decode_group(what, Hq, Hkv):
+def _check_decode_group(what, Hq, Hkv, max_group=_DECODE_MAX_GROUP):
+    '''max_group None: any group ≥ 1 (the prefill calls, whose own rows are positions, not heads).'''
     group = Hq // Hkv
-    if not 1 <= group <= _DECODE_MAX_GROUP:
+    if max_group is None:
+        if group < 1:
+            raise ValueError(f'{what}: q must hold at least one query head per k / v head, got {Hq} over {Hkv}')
+        return group
+    if not 1 <= group <= max_group:
         raise ValueError(f'{what}: {Hq} query heads over {Hkv} k / v heads is a group of {group}; 1 to {_DECODE_MAX_GROUP} are '
                          f'taken (accepted: {_DECODE_SIZES_TEXT})')
     return group
 
 
-def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, entries, k_lens, block):
+def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, entries, k_lens, block, max_grid=_DECODE_MAX_GRID, sizes_text=None):
     '''The refusals of the decode calls that follow from (B, Hkv, T, Smax) alone, however the cache is stored.  `entries`: the
-    number of the layout's stored values.'''
+    number of the layout's stored values.  max_grid None: B·Hkv and T are no grid dimensions (the prefill calls).'''
     if T < 1:
         raise ValueError(f'{what}: q must hold T >= 1 new tokens, got T = {T}')
     if Smax % block != 0:
-        raise ValueError(f'{what}: Smax = {Smax} must be a multiple of block = {block} (accepted: {_DECODE_SIZES_TEXT})')
+        raise ValueError(f'{what}: Smax = {Smax} must be a multiple of block = {block} (accepted: {sizes_text or _DECODE_SIZES_TEXT})')
     l_lead = tuple(layout.shape[:-2])
     if tuple(layout.shape[-2:]) != (Smax // block, Smax // block) or l_lead not in ((), (Hkv,), (B, Hkv)):
         raise ValueError(f'{what}: the layout must have shape [*l_lead, Smax/block, Smax/block] = [*l_lead, {Smax // block}, '
@@ -1870,7 +1877,7 @@ def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, entries, k_lens
                          f'{tuple(layout.shape)}')
     if entries * (block // _BLOCK_TILE) ** 2 >= 2 ** 31:
         raise ValueError(f'{what}: the layout in 64-blocks does not fit int32 indices')
-    if B * Hkv > _DECODE_MAX_GRID or T > _DECODE_MAX_GRID:
+    if max_grid is not None and (B * Hkv > _DECODE_MAX_GRID or T > _DECODE_MAX_GRID):
         raise ValueError(f'{what}: B·Hkv = {B * Hkv} and T = {T} must each be at most {_DECODE_MAX_GRID} (they are grid dimensions)')
     _check_k_lens(what, k_lens, B)
 
@@ -1915,24 +1922,42 @@ def _table_i32(block_table):
 
 
 _DECODE_MIN_PAGE = 16    # keys of the smallest page: a 16-row MFMA fragment of a k tile never straddles two pages
-_DECODE_PAGED_SIZES_TEXT = _DECODE_SIZES_TEXT + ', pages of a power of two >= 16 keys'
+_PAGED_SIZES_SUFFIX = ', pages of a power of two >= 16 keys'  # what a paged call's accepted sizes add to its contiguous form's
 
 
 def _page_ok(page) -> bool:
     return isinstance(page, int) and not isinstance(page, bool) and page >= _DECODE_MIN_PAGE and page & (page - 1) == 0
 
 
+def _check_new_lens(what, new_lens, B):
+    '''new_lens as the rope and the prefill calls take it: None, or an int32 / int64 tensor [B].'''
+    if new_lens is None:
+        return
+    if not isinstance(new_lens, torch.Tensor) or new_lens.layout != torch.strided:
+        raise ValueError(f'{what}: new_lens must be None or a dense tensor')
+    if new_lens.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'{what}: new_lens must be an int32 or int64 tensor, got {new_lens.dtype}')
+    if tuple(new_lens.shape) != (B,):
+        raise ValueError(f'{what}: new_lens must have shape ({B},) — the number of new tokens of every batch item —, got '
+                         f'{tuple(new_lens.shape)}')
+
+
 def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8=False, scales=(),
-                                           block_table=None):
+                                           block_table=None, *, sizes_text=None, max_group=_DECODE_MAX_GROUP,
+                                           max_grid=_DECODE_MAX_GRID, q_strided=False, new_lens=None):
     '''Every refusal of the four decode calls, before the first device call, split as _check_block_attention_operands splits
     them: ValueError for what an operand is, RuntimeError for operands that do not go together (mixed dtypes, host tensors /
     devices).  `names`: the cache operands' names — ('k_pages', 'v_pages') is the paged form, whose k and v are the pool
     [P, Hkv, page, D] and whose Smax is W · page of block_table [B, W].  fp8, scales: the fp8 calls' cache type and their
-    (name, scale) pairs (_check_fp8_scales).'''
+    (name, scale) pairs (_check_fp8_scales).  The keyword parameters are what the prefill calls say differently
+    (_prefill): the accepted sizes in the messages, no bound on the group (max_group None), none on B·Hkv and T (max_grid
+    None), q read through its own strides (q_strided: _check_source_strides), and new_lens (_check_new_lens).'''
     kn, vn = names
     paged = kn == 'k_pages'
-    sizes_text = _DECODE_PAGED_SIZES_TEXT if paged else _DECODE_SIZES_TEXT
-    _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8)
+    base_text = sizes_text or _DECODE_SIZES_TEXT
+    paged_text = base_text + _PAGED_SIZES_SUFFIX
+    sizes_text = paged_text if paged else base_text
+    _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8, base_text)
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError(f'{what}: q must be [B, Hq, T, D] and {kn}, {vn} {"[P, Hkv, page, D]" if paged else "[B, Hkv, Smax, D]"}, '
                          f'got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
@@ -1944,7 +1969,7 @@ def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens,
         raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs {kn} '
                          f'{("P", "Hkv", "page", D) if paged else (B, "Hkv", "Smax", D)} with Hkv a divisor of {Hq}, '
                          f'got {tuple(k.shape)}')
-    _check_decode_group(what, Hq, Hkv)
+    _check_decode_group(what, Hq, Hkv, max_group)
     if tuple(v.shape) != tuple(k.shape):
         owner = "k_pages'" if paged else "k's"
         raise ValueError(f'{what}: {vn} must be a dense tensor with {owner} shape {tuple(k.shape)}, got {tuple(v.shape)}')
@@ -1954,14 +1979,21 @@ def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens,
         page = k.shape[2]
         if not _page_ok(page):
             raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} keys, got page = {page} '
-                             f'(accepted: {_DECODE_PAGED_SIZES_TEXT})')
+                             f'(accepted: {paged_text})')
         Smax = _check_block_table(what, block_table, B) * page
         operands['block_table'] = block_table
-    _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, values.numel(), k_lens, block)
+    _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, values.numel(), k_lens, block, max_grid, base_text)
+    if max_grid is None and max(B * Hq, T, Smax) >= 2 ** 31:
+        raise ValueError(f'{what}: B·Hq = {B * Hq}, T = {T} and Smax = {Smax} must each fit an int32')
+    _check_new_lens(what, new_lens, B)
+    if q_strided:
+        _check_source_strides(what, 'q', q)
     outer, unit = ('page' if paged else 'batch'), (16 if fp8 else 8)
     _check_cache_strides(what, kn, k, D, outer, unit)
     _check_cache_strides(what, vn, v, D, outer, unit)
     operands['k_lens'] = k_lens
+    if new_lens is not None:
+        operands['new_lens'] = new_lens
     if fp8:
         operands.update(_check_fp8_scales(what, scales, Hkv, q))
     _check_on_device(what, **operands)
@@ -2032,7 +2064,8 @@ def block_sparse_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Ten
     and the cache were updated in place.
 
     Returns out [B, Hq, T, D] in q's dtype, or with return_lse=True (out, lse) with lse float32 [B, Hq, T].  There is NO
-    autograd: the result does not require grad whatever the operands do.  scale defaults to 1/√D.'''
+    autograd: the result does not require grad whatever the operands do.  scale defaults to 1/√D.  For T beyond a few
+    tokens — a prompt, or a chunk of one — use block_sparse_attention_prefill, whose tokens share their walks.'''
     return _decode('block_sparse_attention_decode', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, chunk, None, None, False,
                    return_lse)
 
@@ -2070,7 +2103,8 @@ def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, 
     Bits: for a pool and a table whose seen entries are in range, out and lse are bit for bit those of
     block_sparse_attention_decode with the same chunk on the cache gathered to [B, Hkv, Smax, D] — so they do not depend
     on P, on where the pages lie, or on `page`.  No atomics, no read-back: graph-capturable, and one captured graph keeps
-    serving while k_lens, the pool and the block table are updated in place.  NO autograd.'''
+    serving while k_lens, the pool and the block table are updated in place.  NO autograd.  For T beyond a few tokens use
+    block_sparse_attention_prefill_paged.'''
     return _decode('block_sparse_attention_decode_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens, block,
                    scale, chunk, None, None, False, return_lse)
 
@@ -2083,7 +2117,7 @@ _FP8_MAX = 448.0                     # the largest finite e4m3fn value
 _DECODE_FP8_SIZES_TEXT = _DECODE_SIZES_TEXT.replace('bfloat16 or float16 operands', 'bfloat16 or float16 q, a float8_e4m3fn cache')
 
 
-def _check_fp8_cache(what, operands):
+def _check_fp8_cache(what, operands, sizes_text=None):
     '''The cache operands of the fp8 decode calls, (name, tensor) pairs: each a dense float8_e4m3fn tensor — another 8-bit
     type is a ValueError that says which encoding is read —, then both of one dtype (RuntimeError).'''
     first, t0 = operands[0]
@@ -2097,7 +2131,7 @@ def _check_fp8_cache(what, operands):
     for name, t in operands:
         if t.dtype != torch.float8_e4m3fn:
             raise ValueError(f'{what}: {name} must be float8_e4m3fn, got {t.dtype}: the OCP e4m3fn encoding is what is read '
-                             f'(not e4m3fnuz, not e5m2, not raw bytes; accepted: {_DECODE_FP8_SIZES_TEXT})')
+                             f'(not e4m3fnuz, not e5m2, not raw bytes; accepted: {sizes_text or _DECODE_FP8_SIZES_TEXT})')
 
 
 def _check_fp8_scales(what, scales, Hkv, q, ref='q'):
@@ -2189,7 +2223,7 @@ def block_sparse_attention_decode_fp8(q: torch.Tensor, k: torch.Tensor, v: torch
     and lse are bit for bit those of block_sparse_attention_decode on k.to(q.dtype), v.to(q.dtype) with the same chunk;
     with k_scale = s for all heads and v_scale = 2^n, out is that call\'s result at scale\' = float32(scale) · float32(s)
     times 2^n, and lse that call\'s.  Nothing beyond pos, in an unlisted block or between the rows is loaded: a NaN byte
-    there reaches no output.'''
+    there reaches no output.  For T beyond a few tokens use block_sparse_attention_prefill_fp8.'''
     return _decode('block_sparse_attention_decode_fp8', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, chunk, k_scale, v_scale,
                    True, return_lse)
 
@@ -2206,9 +2240,144 @@ def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tens
     Bits: for in-range tables, out and lse are bit for bit those of block_sparse_attention_decode_fp8 with the same chunk
     and scales on the gathered cache; with both scales None, those of block_sparse_attention_decode_paged on the pool
     widened to q\'s type.  Nothing in an invalid page is loaded.  Graph-capturable while k_lens, the pool, the table and
-    the scale tensors are updated in place.'''
+    the scale tensors are updated in place.  For T beyond a few tokens use block_sparse_attention_prefill_paged_fp8.'''
     return _decode('block_sparse_attention_decode_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens,
                    block, scale, chunk, k_scale, v_scale, True, return_lse)
+
+
+# --------------------------------------------------------------------------- #
+# block-sparse prefill attention over the KV cache: chunked prompts in 64-row position tiles (DESIGN.md §3.27)
+# --------------------------------------------------------------------------- #
+
+_PREFILL_SIZES_TEXT = _DECODE_SIZES_TEXT.replace('1 to 16 query heads per k / v head', 'Hq a multiple of Hkv')
+_PREFILL_FP8_SIZES_TEXT = _PREFILL_SIZES_TEXT.replace('bfloat16 or float16 operands', 'bfloat16 or float16 q, a float8_e4m3fn cache')
+
+
+def block_attention_prefill_takes(dtype, D: int, block: int) -> bool:
+    '''Whether block_sparse_attention_prefill takes head size D and block size `block` in `dtype` — a function of these
+    alone: exactly block_attention_takes (the group is any G ≥ 1, T any T ≥ 1).'''
+    return block_attention_takes(dtype, D, block)
+
+
+def block_attention_prefill_paged_takes(dtype, D: int, block: int, page: int) -> bool:
+    '''… and of block_sparse_attention_prefill_paged: block_attention_prefill_takes and page a power of two ≥ 16.'''
+    return block_attention_prefill_takes(dtype, D, block) and _page_ok(page)
+
+
+def block_attention_prefill_fp8_takes(dtype, D: int, block: int) -> bool:
+    '''… of block_sparse_attention_prefill_fp8 with q in `dtype` (the cache is float8_e4m3fn): block_attention_prefill_takes.'''
+    return block_attention_prefill_takes(dtype, D, block)
+
+
+def block_attention_prefill_paged_fp8_takes(dtype, D: int, block: int, page: int) -> bool:
+    '''… and of block_sparse_attention_prefill_paged_fp8: exactly block_attention_prefill_paged_takes.'''
+    return block_attention_prefill_paged_takes(dtype, D, block, page)
+
+
+_PREFILL_BINDINGS = (('block_attention_prefill', 'block_attention_prefill_fp8'),  # [paged][fp8]
+                     ('block_attention_prefill_paged', 'block_attention_prefill_paged_fp8'))
+
+
+def _prefill(what, names, q, k, v, block_table, layout, k_lens, block, scale, new_lens, k_scale, v_scale, fp8, return_lse):
+    '''The one body of the four prefill calls, beside _decode: the decode calls' checks with what differs given as
+    parameters, the defaults, the operands as the binding takes them — q AS IT IS, through its own strides —, one binding
+    call.'''
+    paged = names[0] == 'k_pages'
+    scales = (('k_scale', k_scale), ('v_scale', v_scale)) if fp8 else ()
+    _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, None, fp8, scales, block_table,
+                                           sizes_text=_PREFILL_FP8_SIZES_TEXT if fp8 else _PREFILL_SIZES_TEXT, max_group=None,
+                                           max_grid=None, q_strided=True, new_lens=new_lens)
+    B, Hq, T, D = q.shape
+    if scale is None:
+        scale = 1.0 / float(D) ** 0.5
+    with torch.no_grad():
+        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
+        offsets, columns, nnz, _ = rec['fwd']
+        lens = _lens_i32(k_lens)
+        news = None if new_lens is None else new_lens.detach().to(torch.int32).contiguous()
+        table = (_table_i32(block_table),) if paged else ()
+        out = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
+        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
+        if out.numel() > 0:
+            binding = getattr(custom_mm, _PREFILL_BINDINGS[paged][fp8])
+            fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
+            binding(offsets, columns, nnz, q.detach(), k.detach(), v.detach(), *table, lens, news, float(scale), *fp8_scales, out, lse)
+    return (out, lse) if return_lse else out
+
+
+def block_sparse_attention_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
+                                   block: int = 64, scale=None, *, new_lens=None, return_lse: bool = False):
+    '''Block-sparse attention of the T ≥ 1 newest tokens of every item — a whole prompt, or one CHUNK of it behind a prefix
+    that is already cached — against its key / value cache, on the matrix cores: the read side of `lens += new;
+    rope_kv_cache_append(…, new_lens)`.  q [B, Hq, T, D] bfloat16 or float16; k, v [B, Hkv, Smax, D] — the cache of
+    block_sparse_attention_decode, with the new tokens' keys and values already written —; Hq = G · Hkv with ANY G ≥ 1,
+    D ∈ {32, 64, 96, 128}, Smax a multiple of block, block a multiple of 64 (block_attention_prefill_takes).  Neither q nor
+    the cache is ever copied.  q is read through its own strides under rope_kv_cache_append's source rules — last stride
+    1, token, head and batch strides multiples of 8 elements, a 16-byte aligned data pointer —, so that call's q_out, or
+    the q slice of a fused projection [B, T, Hq + 2·Hkv, D] seen through .transpose(1, 2), works as it is; the cache under
+    the decode call's rules.  Anything else raises ValueError naming the stride.
+
+    The rule is block_sparse_attention_decode's, word for word: token t of item b stands at pos = clamp(k_lens[b], 0, Smax)
+    − T + t and sees key j iff j ≤ pos and the layout lists block (pos // block, j // block); layout, k_lens, block, scale
+    and every refusal are that call's (there is no bound on G, B·Hkv or T, and no chunk).  new_lens: None, or an int32 /
+    int64 device tensor [B], clamped to [0, T] by the kernel and never read back — rope_kv_cache_append's convention: the
+    item's new tokens stand in the LAST new_lens[b] of the T slots.  Slot t holds a token iff t ≥ T − new_lens[b] and
+    pos ≥ 0.  A slot without a token gets a zero row of out and lse −inf, as does a token that sees nothing.  Never read:
+    positions outside the listed blocks, positions at or beyond k_lens[b], the gaps between the rows of a strided cache.
+
+    Bits.  A workgroup owns the positions [64r, 64r + 64) ∩ [k_len − T, k_len) of one query head and walks the 64-block
+    list of layout row r in list order: the causal block_sparse_attention forward, placed in the cache.  The out and lse
+    rows of existing tokens are bit for bit those of custom_mm.block_attention_forward_ex with causal=True and q_lens =
+    k_lens = lens on the cache, q scattered to its positions in a [B·Hq, Smax, D] tensor and the layout repeated per query
+    head.  The bits of a row depend on its item's operands, its list and pos: never on T, new_lens, B, the neighbours or
+    the launch — a chunk of 100 tokens equals the same tokens given as chunks of 60 and 40.  Against
+    block_sparse_attention_decode with the same T the results agree to rounding, not bit for bit: the order of summation
+    differs (that call is the tool for T of a few tokens, and for a short chunk against a very long cache).
+
+    Returns a fresh contiguous out [B, Hq, T, D] in q's dtype, every row written exactly once by ONE launch, or with
+    return_lse=True (out, lse) with lse float32 [B, Hq, T].  NO autograd, no atomics, no read-back, no workspace: the call
+    can be captured in a graph and replayed while k_lens, new_lens and the cache change in place.  scale defaults to 1/√D.'''
+    return _prefill('block_sparse_attention_prefill', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, new_lens, None, None,
+                    False, return_lse)
+
+
+def block_sparse_attention_prefill_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                                         layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *, new_lens=None,
+                                         return_lse: bool = False):
+    '''block_sparse_attention_prefill over a PAGED cache: the pool k_pages, v_pages [P, Hkv, page, D] and block_table
+    [B, W] of block_sparse_attention_decode_paged, with that call's operand rules and refusals (Smax = W · page, pages of a
+    power of two ≥ 16 keys; block_attention_prefill_paged_takes).  A table entry outside [0, P) hides its page's keys:
+    nothing is loaded for them and their scores are −inf; entries of pages only in unlisted blocks, or wholly at or beyond
+    k_lens[b], are never consulted.  Bits: for a pool and a table whose seen entries are in range, out and lse are bit for
+    bit those of block_sparse_attention_prefill on the cache gathered to [B, Hkv, Smax, D] — independent of P, of where the
+    pages lie and of `page`.  Graph-capturable while k_lens, new_lens, the pool and the table change in place.'''
+    return _prefill('block_sparse_attention_prefill_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens,
+                    block, scale, new_lens, None, None, False, return_lse)
+
+
+def block_sparse_attention_prefill_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
+                                       block: int = 64, scale=None, *, k_scale=None, v_scale=None, new_lens=None,
+                                       return_lse: bool = False):
+    '''block_sparse_attention_prefill over an FP8 cache: k, v [B, Hkv, Smax, D] torch.float8_e4m3fn with k_scale / v_scale
+    as in block_sparse_attention_decode_fp8, whose operand rules and refusals these are (strides multiples of 16 bytes;
+    block_attention_prefill_fp8_takes).  Every byte is widened to q's type on its way into LDS, which is exact, and
+    block_sparse_attention_prefill's statements follow: a score is multiplied by scale · k_scale[h], one float32 product,
+    and with a v_scale the stored element is round(float32((O / L) · v_scale[h])).  With both scales None, out and lse are
+    bit for bit those of block_sparse_attention_prefill on k.to(q.dtype), v.to(q.dtype).  (A v_scale TENSOR equal to 1 is
+    the scaled statement: in float16 it rounds O / L to float32 first and may differ from v_scale=None in a last bit.)'''
+    return _prefill('block_sparse_attention_prefill_fp8', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, new_lens, k_scale,
+                    v_scale, True, return_lse)
+
+
+def block_sparse_attention_prefill_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
+                                             layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *,
+                                             k_scale=None, v_scale=None, new_lens=None, return_lse: bool = False):
+    '''block_sparse_attention_prefill_paged over an FP8 pool: k_pages, v_pages [P, Hkv, page, D] torch.float8_e4m3fn with
+    the scales of block_sparse_attention_prefill_fp8 (block_attention_prefill_paged_fp8_takes).  Bits: for in-range
+    tables those of block_sparse_attention_prefill_fp8 with the same scales on the gathered cache; with both scales None
+    those of block_sparse_attention_prefill_paged on the pool widened to q's type.'''
+    return _prefill('block_sparse_attention_prefill_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout,
+                    k_lens, block, scale, new_lens, k_scale, v_scale, True, return_lse)
 
 
 # --------------------------------------------------------------------------- #
@@ -2437,14 +2606,8 @@ def _check_rope_operands(what, q, k_new, cos, sin, rotary_dim, new_lens, q_out, 
     if Pmax >= 2 ** 31:
         raise ValueError(f'{what}: cos must hold fewer than 2^31 rows, got {Pmax}')
     tensors = {'cos': cos, 'sin': sin}
+    _check_new_lens(what, new_lens, B)
     if new_lens is not None:
-        if not isinstance(new_lens, torch.Tensor) or new_lens.layout != torch.strided:
-            raise ValueError(f'{what}: new_lens must be None or a dense tensor')
-        if new_lens.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f'{what}: new_lens must be an int32 or int64 tensor, got {new_lens.dtype}')
-        if tuple(new_lens.shape) != (B,):
-            raise ValueError(f'{what}: new_lens must have shape ({B},) — the number of new tokens of every batch item —, got '
-                             f'{tuple(new_lens.shape)}')
         tensors['new_lens'] = new_lens
     for name, t, like, like_name in (('q_out', q_out, q, 'q'), ('k_out', k_out, k_new, 'k_new')):
         if t is None:
