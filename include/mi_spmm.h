@@ -1233,6 +1233,56 @@ int mi_block_attention_prefill_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI
                                              MI_BLOCK_ATTENTION_PREFILL_OUT);
 
 /* ------------------------------------------------------------------------ *
+ * Split key walks for the prefill entries: a short chunk behind a long cached prefix has few position
+ * tiles, so one workgroup per (tile, query head) leaves most of the chip idle.  These entries cut the list of a tile's
+ * layout row BY LIST POSITION into parts of `split` entries — entry p of a list [beg, end) belongs to part (p − beg) / split;
+ * a skipped entry (outside the grid, above the diagonal, beyond k_len) stays in its part — and give every (tile, query
+ * head, part) to a workgroup of the first launch; a second launch merges the parts.  parts_max = ⌈(Smax / 64) / split⌉,
+ * from the shape alone; with parts_max == 1 the call IS the unsplit entry: one launch, the workspace not looked at.
+ *   split      ≥ 1, list entries of a part;
+ *   workspace, workspace_bytes   16-byte aligned device memory of at least
+ *              mi_block_attention_prefill_split_workspace_bytes(items, group, T, D, Smax, split) =
+ *              items · group · (⌈T / 64⌉ + 1) · parts_max · 64 · (D + 2) · 4 bytes (0 when parts_max ≤ 1; MI_EINVAL for arguments
+ *              the entries refuse, MI_ERANGE beyond int64).  Partial (query item, tile, part) holds o [64][D], then m [64],
+ *              then l [64], float32; only partials of parts below ⌈(end − beg) / split⌉ of tiles that hold a token are
+ *              written, by plain vector stores, and only those are read.  No memset, no atomics, no read-back.
+ * The bits.  A part gives per own row the running maximum m, the row sum l and the unnormalised fp32 accumulator o of the
+ * unsplit walk's statements over its entries in list order; a row without a token, or whose part computes nothing, gives
+ * (−inf, 0) and zeros.  Parts merge in ascending order: M = max mᵢ, L = Σ lᵢ·wᵢ, O = Σ oᵢ·wᵢ with wᵢ = 1 if mᵢ == M, else
+ * exp(mᵢ − M); the store is the unsplit entry's (narrow(O · (1 / L)), the scaled statement with a v_scale, lse = M + log L,
+ * zero and −inf when L == 0).  So a row whose list holds at most `split` entries has the bits of the unsplit entry; a
+ * row's bits depend on its item's operands, its list, pos and split, never on T, new_lens, the batch or the launch; paged
+ * equals contiguous on the gathered cache, fp8 with NULL scales the 2-byte entry on the widened cache.  Rows with more
+ * than one part agree with the unsplit entry to rounding.  Every row of out and lse is written exactly once, by the
+ * second launch.
+ * Validation before any HIP call: what the prefill entries refuse, split < 1, and (parts_max > 1) a NULL or misaligned
+ * workspace → MI_EINVAL; a short workspace → MI_ENOMEM; items == 0 or T == 0 → MI_OK, nothing touched.
+ * ------------------------------------------------------------------------ */
+int64_t mi_block_attention_prefill_split_workspace_bytes(int32_t items, int32_t group, int32_t T, int32_t D, int32_t Smax,
+                                                         int32_t split);
+#define MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT                                                                                   \
+  uint16_t *out, int64_t ldo, int64_t strideO, float *lse, int32_t split, void *workspace, size_t workspace_bytes,             \
+      mi_stream_t stream
+int mi_block_attention_prefill_split_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                          MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT);
+int mi_block_attention_prefill_split_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                         MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT);
+int mi_block_attention_prefill_split_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT);
+int mi_block_attention_prefill_split_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                               MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT);
+int mi_block_attention_prefill_split_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                              MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT);
+int mi_block_attention_prefill_split_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                             MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT);
+int mi_block_attention_prefill_split_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                    MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                                    MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT);
+int mi_block_attention_prefill_split_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                   MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                                   MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT);
+
+/* ------------------------------------------------------------------------ *
  * The fused KV-cache append: the write side of the decode entries above.  ONE launch writes the keys AND the
  * values of the T newest tokens of every k / v item into the cache of mi_block_attention_decode_* — contiguous or paged,
  * 2-byte or e4m3fn bytes — at the positions the lengths name.

@@ -37,6 +37,12 @@
 // page, 4 divides 16); the table is read one list entry ahead.  Tile, score, store_own and next_block are copies of
 // block_attention.hip's private pieces with the cache form added (that unit stays as it is); kB, the images' strides,
 // pack_tile, accumulate, group_max / group_sum are block_attention_device.h's; mfma<T>, half_of, store_rc mfma_device.h's.
+//
+// Split walks (mi_block_attention_prefill_split_* — DESIGN.md §3.28), for a short chunk behind a long cache: the list of a
+// tile's layout row is cut by list position into parts of `split` entries, block_attention_prefill_split_kernel — the walk
+// above as a sibling — gives every (work unit, part) a workgroup that stores the partial (o, m, l) of its 64 rows, and
+// block_attention_prefill_combine_kernel merges the parts in ascending order and makes the unsplit kernel's store.  The
+// unsplit kernel and its argument are untouched by it.
 #include <type_traits>
 
 #include "block_attention_cache_device.h"
@@ -373,8 +379,314 @@ __global__ __launch_bounds__(256) void block_attention_prefill_kernel(Args a) {
   }
 }
 
+// What the split launches add to Args.  The unsplit kernel's argument stays as it was.
+struct SplitArgs {
+  Args a;
+  int split, parts;  // list entries of a part; parts = ⌈blocks / split⌉ > 1, the parts of a full list
+  float* ws;         // [items · group][tiles][parts] partials of 64 · (D + 2) floats: o [64][D], then m [64], then l [64]
+};
+
+// block_attention_prefill_kernel with three differences: a work unit is (u, part) and walks the list entries
+// [beg + part · split, min(end, beg + (part + 1) · split)); it neither normalises nor stores out; its epilogue stores the
+// partial (o, m, l) of its 64 own rows.  Everything else — tile addressing, the look-ahead of the table, masking, staging, the
+// double buffer — is that kernel's text, kept a sibling because parametrising it moved the registers of the unsplit kernels.
+template <class TC, int D, int FORM, bool NEWLENS>
+__global__ __launch_bounds__(256) void block_attention_prefill_split_kernel(SplitArgs sa) {
+  const Args& a = sa.a;
+  typedef typename Operand<TC>::type T;
+  constexpr bool FP8 = Operand<TC>::fp8;
+  typedef typename Cache<FP8>::elem E;
+  typedef typename Cache<FP8>::frag F;
+  __shared__ __attribute__((aligned(16))) unsigned short Ks[kB * (D + 8)];
+  __shared__ __attribute__((aligned(16))) unsigned short Vt[D * kTStr];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
+  const int G = a.group;
+  const int in_page = FORM == kContiguous ? 0 : (1 << a.page_shift) - 1;
+  const long total = a.units * sa.parts;
+  for (long uu = blockIdx.x; uu < total; uu += gridDim.x) {
+    // the parts of a work unit stand `units` workgroups apart, so the heads of a group keep their distance of 8
+    const long u = uu % a.units;
+    const int part = (int)(uu / a.units);
+    // the G heads of a slot stand 8 work units apart
+    const long slot = u / ((long)kSpreadHeads * G) * kSpreadHeads + (u & (kSpreadHeads - 1));
+    if (slot >= a.slots) continue;  // (the padding of the last eight)
+    const int g = (int)((u / kSpreadHeads) % G);
+    const int c = (int)(slot / a.tiles), x = (int)(slot - (long)c * a.tiles);
+    const int bi = c / a.heads, h = c - bi * a.heads;
+    int klen = a.k_lens[c / a.lens_div];
+    klen = klen < 0 ? 0 : klen > a.smax ? (int)a.smax : klen;
+    int n = a.T;  // the item's new tokens: they stand in the last n of the T slots
+    if (NEWLENS) {
+      n = a.new_lens[a.new_lens_one ? 0 : bi];
+      n = n < 0 ? 0 : n > a.T ? a.T : n;
+    }
+    const int start = klen - a.T;                         // the position of slot 0 (negative: slots without a token)
+    const int first = klen - n < 0 ? 0 : klen - n;        // the existing tokens stand at [first, klen)
+    const int r = (start >> 6) + x;                       // the tile's layout row: ⌊start / 64⌋ + x
+    const int pos = r * kB + 16 * w + li;                 // the own row's position …
+    const long t = (long)pos - start;                     // … and its slot
+    const bool slot_ok = t >= 0 && t < a.T;               // the row is a row of q and out
+    const bool token = slot_ok && pos >= first;           // … that holds a token (pos < k_len follows from t < T)
+    const bool any = first < klen && r * kB + kB > first && r * kB < klen;  // the tile holds a token
+    const long item = (long)c * G + g;
+    if (!any) continue;  // nothing to walk: the combine launch writes the zero rows
+    // (0 ≤ r < blocks from here on: 64r + 63 ≥ first ≥ 0 and 64r < k_len ≤ Smax)
+    // (a pool has no batch stride: the item's pages come from its table row)
+    const E* K = static_cast<const E*>(a.k) + (FORM == kContiguous ? (long)bi * a.batchK : 0L) + (long)h * a.headK;
+    const E* V = static_cast<const E*>(a.v) + (FORM == kContiguous ? (long)bi * a.batchV : 0L) + (long)h * a.headV;
+    const int32_t* trow = FORM == kContiguous ? nullptr : a.table + (long)bi * a.table_ld;
+    // what multiplies a score: scale, or in the fp8 forms scale · k_scale[h] — one fp32 product per workgroup
+    const float sc = FP8 ? a.scale * head_scale(a.k_scale, a.k_scale_count, h) : a.scale;
+    const int kblocks = (klen + kB - 1) / kB;
+    long beg, end;
+    {
+      const int32_t* rp = a.rowptr + (long)(c % a.layouts) * (a.blocks + 1);
+      beg = rp[r], end = rp[r + 1];
+      beg = beg < 0 ? 0 : beg;
+      end = end > a.nnz ? a.nnz : end;
+    }
+    {  // the part's entries, cut by list position; a part beyond the list's end leaves before any load, barrier or store
+      const long lo = beg + (long)part * sa.split;
+      if (lo >= end) continue;
+      beg = lo;
+      end = end - lo > sa.split ? lo + sa.split : end;
+    }
+    const int pend = (int)end;
+
+    uint4 qf[D / 32];  // the wave's 16 own rows as B fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of row li
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s) qf[s] = uint4{0u, 0u, 0u, 0u};
+    if (token) {
+      const uint16_t* qrow = a.q + (long)bi * a.batchQ + ((long)h * G + g) * a.headQ + t * a.ldq;
+#pragma unroll
+      for (int s = 0; s < D / 32; ++s) qf[s] = *reinterpret_cast<const uint4*>(qrow + 32 * s + 8 * lg);
+    }
+    f32x4 o[D / 16];
+#pragma unroll
+    for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+
+    // The tile whose loads are in flight (J, its table entries e, their validity ok) and the entry after it (pn, Jn, en): the
+    // column and the table entries of an entry are read ONE ENTRY AHEAD, right after the loads of the entry before it were
+    // issued, so the chain col[p] → table → tile never stands in front of a tile's loads.
+    Tile<D, F, E, FORM> tk, tv;
+    int J = 0, Jn = 0, pn = pend, e[4] = {0, 0, 0, 0}, en[4] = {0, 0, 0, 0};
+    unsigned ok = 0xfu;
+    auto issue = [&]() {
+      tk.load(K, a.ldk, a.pageK, J, e, ok, in_page, tid, klen - J * kB);
+      tv.load(V, a.ldv, a.pageV, J, e, ok, in_page, tid, klen - J * kB);
+    };
+    auto look_ahead = [&](int from) {
+      pn = next_block(a.col, from, pend, r, kblocks);
+      if (pn < pend) {
+        Jn = a.col[pn];
+        if constexpr (FORM != kContiguous) read_pages<FORM>(en, trow, Jn, a.page_shift);
+      }
+    };
+    int p = next_block(a.col, (int)beg, pend, r, kblocks);
+    if (p < pend) {
+      J = a.col[p];
+      if constexpr (FORM != kContiguous) {
+        read_pages<FORM>(e, trow, J, a.page_shift);
+        ok = valid_pages(e, a.pages);
+      }
+      issue();
+      look_ahead(p + 1);
+    }
+    while (p < pend) {
+      const int Jc = J;           // the block computed in this turn …
+      const unsigned seen = ok;   // … and the fragments of it that lie in a page (paged forms)
+      __syncthreads();  // the previous block's reads are done
+      tk.template store_rows<T>(Ks, tid);
+      tv.template store_transposed<T>(Vt, tid);
+      __syncthreads();
+      p = pn;
+      if (p < pend) {  // the next block's loads are in flight while this one is computed
+        J = Jn;
+        if constexpr (FORM != kContiguous) {
+#pragma unroll
+          for (int f = 0; f < 4; ++f) e[f] = en[f];
+          ok = valid_pages(e, a.pages);
+        }
+        issue();
+        look_ahead(p + 1);
+      }
+      const int kleft = klen - Jc * kB;  // keys of this block that exist
+      f32x4 s[4];
+      score<T, D>(s, Ks, qf, li, lg);
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          float x = s[f][rr] * sc;
+          if (Jc == r && 16 * f + 4 * lg + rr > 16 * w + li) x = -INFINITY;
+          if (16 * f + 4 * lg + rr >= kleft) x = -INFINITY;
+          s[f][rr] = x;
+        }
+      if (FORM != kContiguous && seen != 0xfu) {  // keys of a page outside the pool (a uniform branch: tables are in range as a rule)
+#pragma unroll
+        for (int f = 0; f < 4; ++f)
+          if (!((seen >> f) & 1u)) s[f] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      }
+      float mt = -INFINITY;
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) mt = fmaxf(mt, s[f][rr]);
+      const float mn = fmaxf(m, group_max(mt));
+      const float alpha = m == mn ? 1.f : __expf(m - mn);  // (−inf stays: nothing seen yet)
+      float sum = 0.f;
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const float ex = s[f][rr] == -INFINITY ? 0.f : __expf(s[f][rr] - mn);
+          s[f][rr] = ex;
+          sum += ex;
+        }
+      l = l * alpha + sum;  // this lane's share of the row sum; the four shares meet after the walk
+      m = mn;
+#pragma unroll
+      for (int fd = 0; fd < D / 16; ++fd)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) o[fd][rr] *= alpha;
+      uint4 pb[2];
+      pack_tile<T>(pb, s);
+      accumulate<T, D>(o, Vt, pb, li, lg);
+    }
+    l = group_sum(l);
+    if (!token) {
+      l = 0.f;
+#pragma unroll
+      for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // the partial of the own row: an empty one is (−inf, 0) with a zero accumulator (o is zero wherever m is −inf)
+    float* wp = sa.ws + (((item * a.tiles + x) * sa.parts + part) * (long)(kB * (D + 2)));
+    const int row = 16 * w + li;
+#pragma unroll
+    for (int fd = 0; fd < D / 16; ++fd) *reinterpret_cast<f32x4*>(wp + row * D + 16 * fd + 4 * lg) = o[fd];
+    if (lg == 0) {
+      wp[kB * D + row] = l == 0.f ? -INFINITY : m;
+      wp[kB * D + kB + row] = l;
+    }
+    __syncthreads();  // the next work unit restages
+  }
+}
+
+
+// The second launch of a split call: one workgroup per (query item, tile), thread (w, li, lg) on own row 16w + li as in the
+// walk.  The tile's rows, its list and its number of parts are recomputed as the walk computes them; the partials of parts
+// [0, n) — exactly those a walk workgroup wrote — are merged in ascending order: M = max mᵢ, wᵢ = 1 if mᵢ == M else exp(mᵢ − M)
+// (the walk's alpha statement), L = Σ lᵢ·wᵢ, O = Σ oᵢ·wᵢ, the first part setting the sums (so one part is the walk's values,
+// bit for bit).  M and the weights are taken once per row, by the lane with lg == 0, and handed to the row's other three lanes.
+// The store is the unsplit kernel's; every out and lse row of the tile's slots is written here and nowhere else.
+template <class T, int D>
+__global__ __launch_bounds__(256) void block_attention_prefill_combine_kernel(SplitArgs sa) {
+  const Args& a = sa.a;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
+  const int G = a.group;
+  const long total = a.slots * G;
+  for (long uu = blockIdx.x; uu < total; uu += gridDim.x) {
+    const long item = uu / a.tiles;
+    const int x = (int)(uu - item * a.tiles);
+    const int c = (int)(item / G);
+    const int bi = c / a.heads, h = c - bi * a.heads;
+    int klen = a.k_lens[c / a.lens_div];
+    klen = klen < 0 ? 0 : klen > a.smax ? (int)a.smax : klen;
+    int n = a.T;
+    if (a.new_lens) {
+      n = a.new_lens[a.new_lens_one ? 0 : bi];
+      n = n < 0 ? 0 : n > a.T ? a.T : n;
+    }
+    const int start = klen - a.T;
+    const int first = klen - n < 0 ? 0 : klen - n;
+    const int r = (start >> 6) + x;
+    const int pos = r * kB + 16 * w + li;
+    const long t = (long)pos - start;
+    const bool slot_ok = t >= 0 && t < a.T;
+    const bool token = slot_ok && pos >= first;
+    const bool any = first < klen && r * kB + kB > first && r * kB < klen;
+    int parts = 0;  // the parts of the tile's list: those whose workgroup wrote a partial
+    if (any) {
+      const int32_t* rp = a.rowptr + (long)(c % a.layouts) * (a.blocks + 1);
+      long beg = rp[r], end = rp[r + 1];
+      beg = beg < 0 ? 0 : beg;
+      end = end > a.nnz ? a.nnz : end;
+      const long np = end > beg ? (end - beg + sa.split - 1) / sa.split : 0;
+      parts = (int)(np < sa.parts ? np : sa.parts);
+    }
+    const float* wp = sa.ws + (item * a.tiles + x) * sa.parts * (long)(kB * (D + 2));
+    const long pstride = (long)kB * (D + 2);
+    const int row = 16 * w + li;
+    float M = -INFINITY;
+    if (lg == 0)
+      for (int i = 0; i < parts; ++i) M = fmaxf(M, wp[i * pstride + kB * D + row]);
+    M = __shfl(M, li);
+    f32x4 o[D / 16];
+#pragma unroll
+    for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float l = 0.f;
+    for (int i = 0; i < parts; ++i) {
+      const float* pp = wp + i * pstride;
+      float wt = 0.f, lw = 0.f;
+      if (lg == 0) {
+        const float mi = pp[kB * D + row];
+        wt = mi == M ? 1.f : __expf(mi - M);
+        lw = pp[kB * D + kB + row] * wt;
+      }
+      wt = __shfl(wt, li);
+      lw = __shfl(lw, li);
+      if (i == 0) {
+        l = lw;
+#pragma unroll
+        for (int fd = 0; fd < D / 16; ++fd) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(pp + row * D + 16 * fd + 4 * lg);
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) o[fd][rr] = v[rr] * wt;
+        }
+      } else {
+        l += lw;
+#pragma unroll
+        for (int fd = 0; fd < D / 16; ++fd) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(pp + row * D + 16 * fd + 4 * lg);
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) o[fd][rr] += v[rr] * wt;
+        }
+      }
+    }
+    if (!token) {  // (its partials are empty: l is 0 already)
+      l = 0.f;
+#pragma unroll
+      for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const float inv = l == 0.f ? 0.f : 1.f / l;
+    if (slot_ok) {
+      uint16_t* orow = a.out + item * a.strideO + t * a.ldo;
+      if (a.v_scale != nullptr)
+        store_own_scaled<T, D>(o, inv, head_scale(a.v_scale, a.v_scale_count, h), orow, lg);
+      else
+        store_own<T, D>(o, inv, orow, lg);
+      if (lg == 0) a.lse[item * a.T + t] = l == 0.f ? -INFINITY : M + __logf(l);
+    }
+  }
+}
+
 template <class TC, int D, int FORM>
-int launch_form(const Args& a, hipStream_t s) {
+int launch_form(const Args& a, const SplitArgs& sp, hipStream_t s) {
+  if (sp.parts > 1) {  // the split walk, then the combine: two launches on the one stream, the kernel boundary the hand-over
+    typedef typename Operand<TC>::type T;
+    const SplitArgs sa = {a, sp.split, sp.parts, sp.ws};
+    const long walks = a.units * sp.parts, tiles = a.slots * a.group;
+    const dim3 grid((unsigned)(walks < kMaxGrid ? walks : kMaxGrid));
+    if (a.new_lens)
+      hipLaunchKernelGGL((block_attention_prefill_split_kernel<TC, D, FORM, true>), grid, dim3(256), 0, s, sa);
+    else
+      hipLaunchKernelGGL((block_attention_prefill_split_kernel<TC, D, FORM, false>), grid, dim3(256), 0, s, sa);
+    if (const int st = mi::check_launch()) return st;
+    hipLaunchKernelGGL((block_attention_prefill_combine_kernel<T, D>), dim3((unsigned)(tiles < kMaxGrid ? tiles : kMaxGrid)), dim3(256),
+                       0, s, sa);
+    return mi::check_launch();
+  }
   const dim3 grid((unsigned)(a.units < kMaxGrid ? a.units : kMaxGrid));
   if (a.new_lens)
     hipLaunchKernelGGL((block_attention_prefill_kernel<TC, D, FORM, true>), grid, dim3(256), 0, s, a);
@@ -384,24 +696,36 @@ int launch_form(const Args& a, hipStream_t s) {
 }
 
 template <class T, int D, bool FP8>
-int launch(const Args& a, hipStream_t s) {
+int launch(const Args& a, const SplitArgs& sp, hipStream_t s) {
   typedef std::conditional_t<FP8, Fp8<T>, T> TC;  // the cache element type is part of the kernel's first parameter
-  if (!a.table) return launch_form<TC, D, kContiguous>(a, s);
-  return a.page_shift >= 6 ? launch_form<TC, D, kPaged>(a, s) : launch_form<TC, D, kPagedSmall>(a, s);
+  if (!a.table) return launch_form<TC, D, kContiguous>(a, sp, s);
+  return a.page_shift >= 6 ? launch_form<TC, D, kPaged>(a, sp, s) : launch_form<TC, D, kPagedSmall>(a, sp, s);
 }
+
+// What the split entries add: the list entries of a part, and the workspace of the partials.
+struct Split {
+  bool on = false;
+  int32_t entries = 0;
+  void* workspace = nullptr;
+  size_t workspace_bytes = 0;
+};
+
+// the parts of a full list of Smax / 64 entries cut every `split`
+inline int parts_of(int32_t Smax, int32_t split) { return (int)(((long)Smax / kB + split - 1) / split); }
 
 // Every check comes before the first HIP call.  page == 0: the contiguous cache, `outerK` / `outerV` its batch strides and
 // no table; page > 0: a pool of `pages` pages of `page` keys, `outerK` / `outerV` its page strides, Smax = the table's
 // logical pages · page.  FP8: k and v are e4m3fn bytes (their strides multiples of 16) with the two scales of `scales`.
+// `split`: the split entries' cut and workspace; with one part the call is the unsplit launch.
 template <class T, bool FP8 = false>
 int prefill_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T_,
                   int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq, int64_t headQ, int64_t batchQ, const void* k, int64_t ldk,
                   int64_t headK, int64_t outerK, const void* v, int64_t ldv, int64_t headV, int64_t outerV, const int32_t* k_lens,
                   int32_t lens_count, const int32_t* new_lens, int32_t new_lens_count, int32_t group, float scale, uint16_t* out,
                   int64_t ldo, int64_t strideO, float* lse, hipStream_t s, const int32_t* table = nullptr, int64_t table_ld = 0,
-                  int32_t pages = 0, int32_t page = 0, const Scales& scales = Scales()) {
+                  int32_t pages = 0, int32_t page = 0, const Scales& scales = Scales(), const Split& split = Split()) {
   if (!cache_form_ok(FP8, scales, heads, Smax, pages, page)) return MI_EINVAL;
-  if (group < 1 || !takes_width(D)) return MI_EINVAL;
+  if (group < 1 || !takes_width(D) || (split.on && split.entries < 1)) return MI_EINVAL;
   const bool paged = page != 0;
   if (nnz < 0 || layouts < 0 || items < 0 || heads < 0 || T_ < 0 || Smax < 0 || Smax % kB != 0) return MI_EINVAL;
   if (nnz > 0x7fffffffLL) return MI_ERANGE;
@@ -414,7 +738,16 @@ int prefill_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_
   if (!out || !mi::aligned16(out) || ldo < D || !stride_ok(ldo) || !stride_ok(strideO)) return MI_EINVAL;
   const bool reads = nnz > 0 && Smax > 0 && (!paged || pages > 0);  // (an empty pool is never read: every entry of the table is invalid)
   if (!cache_operands_ok(FP8, reads, Smax, D, k, ldk, headK, outerK, v, ldv, headV, outerV, table, table_ld, page)) return MI_EINVAL;
+  const int parts = split.on ? parts_of(Smax, split.entries) : 1;
+  if (parts > 1) {  // (one part: the unsplit launch, no workspace)
+    if (!split.workspace || !mi::aligned16(split.workspace)) return MI_EINVAL;
+    const int64_t need = mi_block_attention_prefill_split_workspace_bytes(items, group, T_, D, Smax, split.entries);
+    if (need < 0) return (int)need;
+    if (split.workspace_bytes < (uint64_t)need) return MI_ENOMEM;
+  }
   Args a = {};  // (zeroed: the 2-byte entries leave k_scale / v_scale null)
+  SplitArgs sp = {};
+  if (parts > 1) sp.split = split.entries, sp.parts = parts, sp.ws = static_cast<float*>(split.workspace);
   a.rowptr = rowptr, a.col = col, a.nnz = nnz, a.layouts = layouts, a.blocks = Smax / kB, a.heads = heads, a.group = group;
   a.T = T_, a.tiles = (int)(((long)T_ + kB - 1) / kB + 1), a.smax = Smax;
   a.slots = (long)items * a.tiles;
@@ -431,10 +764,10 @@ int prefill_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_
   a.out = out, a.ldo = ldo, a.strideO = strideO, a.lse = lse;
   if (FP8) a.k_scale = scales.k, a.k_scale_count = scales.k_count, a.v_scale = scales.v, a.v_scale_count = scales.v_count;
   switch (D) {
-    case 32: return launch<T, 32, FP8>(a, s);
-    case 64: return launch<T, 64, FP8>(a, s);
-    case 96: return launch<T, 96, FP8>(a, s);
-    default: return launch<T, 128, FP8>(a, s);
+    case 32: return launch<T, 32, FP8>(a, sp, s);
+    case 64: return launch<T, 64, FP8>(a, sp, s);
+    case 96: return launch<T, 96, FP8>(a, sp, s);
+    default: return launch<T, 128, FP8>(a, sp, s);
   }
 }
 
@@ -483,6 +816,56 @@ int mi_block_attention_prefill_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI
                                              MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
                                              MI_BLOCK_ATTENTION_PREFILL_OUT) {
   return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_PAGED_PASS, MI_PREFILL_SCALES);
+}
+
+int64_t mi_block_attention_prefill_split_workspace_bytes(int32_t items, int32_t group, int32_t T, int32_t D, int32_t Smax,
+                                                         int32_t split) {
+  if (items < 0 || group < 1 || T < 0 || !takes_width(D) || Smax < 0 || Smax % kB != 0 || split < 1) return MI_EINVAL;
+  const int parts = parts_of(Smax, split);
+  if (items == 0 || T == 0 || parts <= 1) return 0;  // (one part: the walk stores out itself)
+  int64_t n = (int64_t)items * group;                // < 2^62
+  if (__builtin_mul_overflow(n, ((int64_t)T + kB - 1) / kB + 1, &n) || __builtin_mul_overflow(n, (int64_t)parts, &n) ||
+      __builtin_mul_overflow(n, (int64_t)kB * (D + 2) * (int64_t)sizeof(float), &n))
+    return MI_ERANGE;
+  return n;
+}
+
+#define MI_PREFILL_SPLIT Split{true, split, workspace, workspace_bytes}
+#define MI_PREFILL_SPLIT_OUT MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT
+
+int mi_block_attention_prefill_split_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                          MI_PREFILL_SPLIT_OUT) {
+  return prefill_entry<Bf16>(MI_PREFILL_PASS, nullptr, 0, 0, 0, Scales(), MI_PREFILL_SPLIT);
+}
+int mi_block_attention_prefill_split_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                         MI_PREFILL_SPLIT_OUT) {
+  return prefill_entry<F16>(MI_PREFILL_PASS, nullptr, 0, 0, 0, Scales(), MI_PREFILL_SPLIT);
+}
+int mi_block_attention_prefill_split_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_PREFILL_SPLIT_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<Bf16>(MI_PREFILL_PAGED_PASS, Scales(), MI_PREFILL_SPLIT);
+}
+int mi_block_attention_prefill_split_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                               MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_PREFILL_SPLIT_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<F16>(MI_PREFILL_PAGED_PASS, Scales(), MI_PREFILL_SPLIT);
+}
+int mi_block_attention_prefill_split_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                              MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_PREFILL_SPLIT_OUT) {
+  return prefill_entry<Bf16, true>(MI_PREFILL_PASS, nullptr, 0, 0, 0, MI_PREFILL_SCALES, MI_PREFILL_SPLIT);
+}
+int mi_block_attention_prefill_split_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                             MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_PREFILL_SPLIT_OUT) {
+  return prefill_entry<F16, true>(MI_PREFILL_PASS, nullptr, 0, 0, 0, MI_PREFILL_SCALES, MI_PREFILL_SPLIT);
+}
+int mi_block_attention_prefill_split_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                    MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                                    MI_PREFILL_SPLIT_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<Bf16, true>(MI_PREFILL_PAGED_PASS, MI_PREFILL_SCALES, MI_PREFILL_SPLIT);
+}
+int mi_block_attention_prefill_split_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                   MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                                   MI_PREFILL_SPLIT_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_PAGED_PASS, MI_PREFILL_SCALES, MI_PREFILL_SPLIT);
 }
 
 }  // extern "C"

@@ -226,6 +226,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("block_attention_prefill_paged_fp8", &block_attention_prefill_paged_fp8,
         "(offsets, columns, nnz, q, k_pages, v_pages [P, Hkv, page, D] float8_e4m3fn, block_table, k_lens, new_lens, scale, "
         "k_scale, v_scale, out, lse): block_attention_prefill_paged over an fp8 pool");
+  m.def("block_attention_prefill_split", &block_attention_prefill_split,
+        "(block_attention_prefill's arguments, split): the list of a tile's layout row cut by list position into parts of `split` "
+        "entries, one workgroup per (tile, query head, part), a second launch merging the parts in ascending order; the "
+        "workspace of the partials comes from torch's allocator");
+  m.def("block_attention_prefill_split_paged", &block_attention_prefill_split_paged,
+        "(block_attention_prefill_paged's arguments, split): block_attention_prefill_split over a pool of pages");
+  m.def("block_attention_prefill_split_fp8", &block_attention_prefill_split_fp8,
+        "(block_attention_prefill_fp8's arguments, split): block_attention_prefill_split over an fp8 cache");
+  m.def("block_attention_prefill_split_paged_fp8", &block_attention_prefill_split_paged_fp8,
+        "(block_attention_prefill_paged_fp8's arguments, split): block_attention_prefill_split_paged over an fp8 pool");
   m.def("kv_append", &kv_append,
         "(k_new, v_new [B, Hkv, T, D] bfloat16 / float16 through their own strides, k, v [B, Hkv, Smax, D] of that dtype or "
         "float8_e4m3fn, k_lens int32 [B] or [1] — the lengths AFTER the append —, k_scale, v_scale (None or float32 device tensors "

@@ -6,16 +6,17 @@
 // KV cache" (DESIGN.md §3.27): q [B, Hq, T, D] bfloat16 or float16 READ THROUGH ITS OWN STRIDES (check_source_strides: never
 // copied), out [B, Hq, T, D] contiguous; the cache of q's type or float8_e4m3fn; offsets int32 [layouts, Smax/64 + 1] with the
 // layouts' bases, columns int32 layout-local, in 64-blocks; new_lens None or int32 [B] / [1]; lse float32 [B, Hq, T].  No
-// workspace.
+// workspace — but for the four …_split bindings (DESIGN.md §3.28), which take `split` after the old argument list and get the
+// workspace of the parts' partials from torch's allocator.
 
 // all four forms: `table` null — the contiguous cache [B, Hkv, Smax, D] — or the block table of a pool [P, Hkv, page, D];
-// `fp8`: a cache of e4m3fn bytes with the two scales
+// `fp8`: a cache of e4m3fn bytes with the two scales; `split` 0: the unsplit entries, else the list entries of a part
 torch::Tensor block_attention_prefill_impl(const char* what, const char* kname, const char* vname, bool fp8, const torch::Tensor& offsets,
                                            const torch::Tensor& columns, int64_t nnz, const torch::Tensor& q, const torch::Tensor& k,
                                            const torch::Tensor& v, const torch::Tensor* table, const torch::Tensor& k_lens,
                                            const c10::optional<torch::Tensor>& new_lens, double scale,
                                            const c10::optional<torch::Tensor>& k_scale, const c10::optional<torch::Tensor>& v_scale,
-                                           torch::Tensor out, const torch::Tensor& lse) {
+                                           torch::Tensor out, const torch::Tensor& lse, int64_t split = 0) {
   const bool bf = fp8 ? fp8_decode_dtypes(what, q, out, kname, k, vname, v)
                       : is_lowp_dtype(what, value_dtype(what, {{"q", &q}, {kname, &k}, {vname, &v}, {"out", &out}}, true));
   TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, what, ": q must be [B, Hq, T, D], ", kname, " and ", vname,
@@ -65,6 +66,14 @@ torch::Tensor block_attention_prefill_impl(const char* what, const char* kname, 
   if (out.numel() == 0) return out;
   c10::hip::HIPGuard guard(out.device().index());
   const int64_t items = B * Hkv;
+  torch::Tensor ws;  // the partials of a split call: alive until the launches are enqueued, then the allocator's on this stream
+  int64_t ws_bytes = 0;
+  if (split != 0) {
+    ws_bytes = mi_block_attention_prefill_split_workspace_bytes((int32_t)items, (int32_t)group, (int32_t)T, (int32_t)D, (int32_t)Smax,
+                                                                (int32_t)split);
+    if (ws_bytes < 0) check_status((int)ws_bytes, what);
+    ws = byte_workspace(out.device(), (size_t)ws_bytes, 16);
+  }
   auto p = [](const torch::Tensor& t) { return static_cast<uint16_t*>(t.data_ptr()); };
 // the argument lists of the eight C entries, in pieces: [table] and [scales] are what the paged and the fp8 entries add
 #define MI_PREFILL_LIST \
@@ -76,8 +85,19 @@ torch::Tensor block_attention_prefill_impl(const char* what, const char* kname, 
       (int32_t)k_lens.numel(), nl, nl_count, (int32_t)group, (float)scale
 #define MI_PREFILL_SCALES ks.first, ks.second, vs.first, vs.second
 #define MI_PREFILL_OUT p(out), D, T* D, lse.data_ptr<float>(), stream_of(out)
+#define MI_PREFILL_SPLIT_OUT p(out), D, T* D, lse.data_ptr<float>(), (int32_t)split, ws.data_ptr(), (size_t)ws_bytes, stream_of(out)
   int st;
-  if (!fp8)
+  if (split != 0 && !fp8)
+    st = table ? (bf ? mi_block_attention_prefill_split_paged_bf16 : mi_block_attention_prefill_split_paged_f16)(
+                     MI_PREFILL_LIST, MI_PREFILL_TABLE, MI_PREFILL_OPERANDS(uint16_t), MI_PREFILL_SPLIT_OUT)
+               : (bf ? mi_block_attention_prefill_split_bf16 : mi_block_attention_prefill_split_f16)(
+                     MI_PREFILL_LIST, MI_PREFILL_OPERANDS(uint16_t), MI_PREFILL_SPLIT_OUT);
+  else if (split != 0)
+    st = table ? (bf ? mi_block_attention_prefill_split_paged_fp8_bf16 : mi_block_attention_prefill_split_paged_fp8_f16)(
+                     MI_PREFILL_LIST, MI_PREFILL_TABLE, MI_PREFILL_OPERANDS(uint8_t), MI_PREFILL_SCALES, MI_PREFILL_SPLIT_OUT)
+               : (bf ? mi_block_attention_prefill_split_fp8_bf16 : mi_block_attention_prefill_split_fp8_f16)(
+                     MI_PREFILL_LIST, MI_PREFILL_OPERANDS(uint8_t), MI_PREFILL_SCALES, MI_PREFILL_SPLIT_OUT);
+  else if (!fp8)
     st = table ? (bf ? mi_block_attention_prefill_paged_bf16 : mi_block_attention_prefill_paged_f16)(
                      MI_PREFILL_LIST, MI_PREFILL_TABLE, MI_PREFILL_OPERANDS(uint16_t), MI_PREFILL_OUT)
                : (bf ? mi_block_attention_prefill_bf16 : mi_block_attention_prefill_f16)(MI_PREFILL_LIST, MI_PREFILL_OPERANDS(uint16_t),
@@ -92,6 +112,7 @@ torch::Tensor block_attention_prefill_impl(const char* what, const char* kname, 
 #undef MI_PREFILL_OPERANDS
 #undef MI_PREFILL_SCALES
 #undef MI_PREFILL_OUT
+#undef MI_PREFILL_SPLIT_OUT
   check_status(st, what);
   return out;
 }
@@ -126,4 +147,47 @@ torch::Tensor block_attention_prefill_paged_fp8(torch::Tensor offsets, torch::Te
                                                 torch::Tensor out, torch::Tensor lse) {
   return block_attention_prefill_impl("block_attention_prefill_paged_fp8", "k_pages", "v_pages", true, offsets, columns, nnz, q,
                                       k_pages, v_pages, &block_table, k_lens, new_lens, scale, k_scale, v_scale, out, lse);
+}
+
+// the four split forms: the old argument lists with `split` at the end
+void check_split(const char* what, int64_t split) {
+  TORCH_CHECK(split >= 1 && split <= INT32_MAX, what, ": split must be a positive int32, got ", split);
+}
+
+torch::Tensor block_attention_prefill_split(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q, torch::Tensor k,
+                                            torch::Tensor v, torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens, double scale,
+                                            torch::Tensor out, torch::Tensor lse, int64_t split) {
+  check_split("block_attention_prefill_split", split);
+  return block_attention_prefill_impl("block_attention_prefill_split", "k", "v", false, offsets, columns, nnz, q, k, v, nullptr, k_lens,
+                                      new_lens, scale, c10::nullopt, c10::nullopt, out, lse, split);
+}
+
+torch::Tensor block_attention_prefill_split_paged(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q,
+                                                  torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table,
+                                                  torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens, double scale,
+                                                  torch::Tensor out, torch::Tensor lse, int64_t split) {
+  check_split("block_attention_prefill_split_paged", split);
+  return block_attention_prefill_impl("block_attention_prefill_split_paged", "k_pages", "v_pages", false, offsets, columns, nnz, q,
+                                      k_pages, v_pages, &block_table, k_lens, new_lens, scale, c10::nullopt, c10::nullopt, out, lse,
+                                      split);
+}
+
+torch::Tensor block_attention_prefill_split_fp8(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q,
+                                                torch::Tensor k, torch::Tensor v, torch::Tensor k_lens,
+                                                c10::optional<torch::Tensor> new_lens, double scale,
+                                                c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale,
+                                                torch::Tensor out, torch::Tensor lse, int64_t split) {
+  check_split("block_attention_prefill_split_fp8", split);
+  return block_attention_prefill_impl("block_attention_prefill_split_fp8", "k", "v", true, offsets, columns, nnz, q, k, v, nullptr,
+                                      k_lens, new_lens, scale, k_scale, v_scale, out, lse, split);
+}
+
+torch::Tensor block_attention_prefill_split_paged_fp8(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q,
+                                                      torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table,
+                                                      torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens, double scale,
+                                                      c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale,
+                                                      torch::Tensor out, torch::Tensor lse, int64_t split) {
+  check_split("block_attention_prefill_split_paged_fp8", split);
+  return block_attention_prefill_impl("block_attention_prefill_split_paged_fp8", "k_pages", "v_pages", true, offsets, columns, nnz, q,
+                                      k_pages, v_pages, &block_table, k_lens, new_lens, scale, k_scale, v_scale, out, lse, split);
 }

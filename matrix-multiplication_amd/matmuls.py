@@ -1832,9 +1832,9 @@ def _check_cache_strides(what, name, t, D, outer='batch', unit=8):
         raise ValueError(f'{what}: {name}\'s data pointer must be 16-byte aligned (the cache is never copied)')
 
 
-def _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8=False, sizes_text=None):
+def _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8=False, sizes_text=None, split=None):
     '''What block_sparse_attention_decode and its paged form refuse before they look at a shape: the layout's and the
-    operands' kinds, block, chunk.  `names` are the two cache operands' names in the messages.  fp8: the cache is
+    operands' kinds, block, chunk (and the prefill calls' `split`, which is what they have in chunk's place).  `names` are the two cache operands' names in the messages.  fp8: the cache is
     float8_e4m3fn (_check_fp8_cache) and only q is bfloat16 / float16.  sizes_text: what the messages name as accepted
     (None: the decode calls').'''
     fp8_text, sizes_text = sizes_text, sizes_text or _DECODE_SIZES_TEXT
@@ -1848,6 +1848,8 @@ def _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8=False, si
         raise ValueError(f'{what}: block must be a positive multiple of 64, got {block!r} (accepted: {sizes_text})')
     if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1 or chunk >= 2 ** 31):
         raise ValueError(f'{what}: chunk must be None or a positive int, got {chunk!r}')
+    if split is not None and (isinstance(split, bool) or not isinstance(split, int) or split < 1 or split >= 2 ** 31):
+        raise ValueError(f'{what}: split must be None or a positive int, got {split!r}')
 
 
 def _check_decode_group(what, Hq, Hkv, max_group=_DECODE_MAX_GROUP):
@@ -1944,20 +1946,20 @@ def _check_new_lens(what, new_lens, B):
 
 def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8=False, scales=(),
                                            block_table=None, *, sizes_text=None, max_group=_DECODE_MAX_GROUP,
-                                           max_grid=_DECODE_MAX_GRID, q_strided=False, new_lens=None):
+                                           max_grid=_DECODE_MAX_GRID, q_strided=False, new_lens=None, split=None):
     '''Every refusal of the four decode calls, before the first device call, split as _check_block_attention_operands splits
     them: ValueError for what an operand is, RuntimeError for operands that do not go together (mixed dtypes, host tensors /
     devices).  `names`: the cache operands' names — ('k_pages', 'v_pages') is the paged form, whose k and v are the pool
     [P, Hkv, page, D] and whose Smax is W · page of block_table [B, W].  fp8, scales: the fp8 calls' cache type and their
     (name, scale) pairs (_check_fp8_scales).  The keyword parameters are what the prefill calls say differently
     (_prefill): the accepted sizes in the messages, no bound on the group (max_group None), none on B·Hkv and T (max_grid
-    None), q read through its own strides (q_strided: _check_source_strides), and new_lens (_check_new_lens).'''
+    None), q read through its own strides (q_strided: _check_source_strides), new_lens (_check_new_lens) and split.'''
     kn, vn = names
     paged = kn == 'k_pages'
     base_text = sizes_text or _DECODE_SIZES_TEXT
     paged_text = base_text + _PAGED_SIZES_SUFFIX
     sizes_text = paged_text if paged else base_text
-    _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8, base_text)
+    _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8, base_text, split)
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError(f'{what}: q must be [B, Hq, T, D] and {kn}, {vn} {"[P, Hkv, page, D]" if paged else "[B, Hkv, Smax, D]"}, '
                          f'got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
@@ -2276,17 +2278,45 @@ def block_attention_prefill_paged_fp8_takes(dtype, D: int, block: int, page: int
 
 _PREFILL_BINDINGS = (('block_attention_prefill', 'block_attention_prefill_fp8'),  # [paged][fp8]
                      ('block_attention_prefill_paged', 'block_attention_prefill_paged_fp8'))
+_PREFILL_SPLIT_BINDINGS = (('block_attention_prefill_split', 'block_attention_prefill_split_fp8'),  # [paged][fp8]
+                           ('block_attention_prefill_split_paged', 'block_attention_prefill_split_paged_fp8'))
 
 
-def _prefill(what, names, q, k, v, block_table, layout, k_lens, block, scale, new_lens, k_scale, v_scale, fp8, return_lse):
+def block_attention_prefill_split(B: int, Hq: int, T: int, Smax: int, D: int):
+    '''The `split` this project suggests for block_sparse_attention_prefill and its forms at a shape — None (the unsplit
+    call) or a positive int —, a function of its five arguments alone.  Callers opt in: the four calls never consult it.
+
+    The rule, fitted on the sweep of tools/bench_block_attention_prefill_split.py
+    (profiles/r30_block_attention_prefill_split.log: bf16, D = 128, Hq = 32, Hkv = 8, B ∈ {1, 4}, T ∈ {64, 512, 2048}, k_len ∈
+    {8 K, 32 K, 128 K}, three layouts, split ∈ {16 … 512}): with W = B · Hq · (⌈T / 64⌉ + 1) unsplit workgroups,
+        D == 128, 8192 ≤ Smax ≤ 131072 and W ≤ 288   →   max(16, the power of two at or below (Smax / 64) / 32)
+        anything else                                  →   None.
+    That is 16, 16 and 64 at 8 K, 32 K and 128 K: about 32 parts of a full list.  On the grid's rows with W ≤ 288 (B = 1 with T = 64
+    or 512, B = 4 with T = 64) it takes 0.16 … 0.70 of the unsplit time when every block is kept and 0.37 … 0.81 at random
+    10 % from 32 K on; at random 10 % of 8 K and under a window of 16 blocks, whose lists are too short to cut, it costs the
+    second launch — 1.01 … 1.15 of a 50 … 80 µs call, inside those rows' own [min … max] —, so a caller who knows its lists
+    hold a few entries does not split.  At W ≥ 1056 (the grid's other shapes) no split won by more than a row's spread but
+    one (B = 4, T = 2048, 128 K, fully kept: 0.93 at split 64): None.  Not measured, hence None: other D, Smax outside
+    [8 K, 128 K], 288 < W < 1056.  (The helper cannot see the layout.)'''
+    for n in (B, Hq, T, Smax, D):
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            return None
+    units = B * Hq * (-(-T // _BLOCK_TILE) + 1)
+    if D != 128 or not 8192 <= Smax <= 131072 or units > 288:
+        return None
+    per_part = (Smax // _BLOCK_TILE) // 32
+    return max(16, 1 << (per_part.bit_length() - 1))
+
+
+def _prefill(what, names, q, k, v, block_table, layout, k_lens, block, scale, new_lens, k_scale, v_scale, fp8, return_lse, split=None):
     '''The one body of the four prefill calls, beside _decode: the decode calls' checks with what differs given as
     parameters, the defaults, the operands as the binding takes them — q AS IT IS, through its own strides —, one binding
-    call.'''
+    call: split None the unsplit binding with its own argument list, an int the split binding with that int behind it.'''
     paged = names[0] == 'k_pages'
     scales = (('k_scale', k_scale), ('v_scale', v_scale)) if fp8 else ()
     _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, None, fp8, scales, block_table,
                                            sizes_text=_PREFILL_FP8_SIZES_TEXT if fp8 else _PREFILL_SIZES_TEXT, max_group=None,
-                                           max_grid=None, q_strided=True, new_lens=new_lens)
+                                           max_grid=None, q_strided=True, new_lens=new_lens, split=split)
     B, Hq, T, D = q.shape
     if scale is None:
         scale = 1.0 / float(D) ** 0.5
@@ -2299,14 +2329,15 @@ def _prefill(what, names, q, k, v, block_table, layout, k_lens, block, scale, ne
         out = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
         lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
         if out.numel() > 0:
-            binding = getattr(custom_mm, _PREFILL_BINDINGS[paged][fp8])
+            binding = getattr(custom_mm, (_PREFILL_BINDINGS if split is None else _PREFILL_SPLIT_BINDINGS)[paged][fp8])
             fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
-            binding(offsets, columns, nnz, q.detach(), k.detach(), v.detach(), *table, lens, news, float(scale), *fp8_scales, out, lse)
+            binding(offsets, columns, nnz, q.detach(), k.detach(), v.detach(), *table, lens, news, float(scale), *fp8_scales, out, lse,
+                    *(() if split is None else (int(split),)))
     return (out, lse) if return_lse else out
 
 
 def block_sparse_attention_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
-                                   block: int = 64, scale=None, *, new_lens=None, return_lse: bool = False):
+                                   block: int = 64, scale=None, *, new_lens=None, return_lse: bool = False, split=None):
     '''Block-sparse attention of the T ≥ 1 newest tokens of every item — a whole prompt, or one CHUNK of it behind a prefix
     that is already cached — against its key / value cache, on the matrix cores: the read side of `lens += new;
     rope_kv_cache_append(…, new_lens)`.  q [B, Hq, T, D] bfloat16 or float16; k, v [B, Hkv, Smax, D] — the cache of
@@ -2332,52 +2363,78 @@ def block_sparse_attention_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Te
     head.  The bits of a row depend on its item's operands, its list and pos: never on T, new_lens, B, the neighbours or
     the launch — a chunk of 100 tokens equals the same tokens given as chunks of 60 and 40.  Against
     block_sparse_attention_decode with the same T the results agree to rounding, not bit for bit: the order of summation
-    differs (that call is the tool for T of a few tokens, and for a short chunk against a very long cache).
+    differs (that call is the tool for T of a few tokens.  For a short chunk against a very long cache — few tiles,
+    long lists — use `split` below: at T = 64 the decode call took 0.9 … 1.0 of this call's unsplit time where every block
+    of 8 K … 128 K keys is kept and B = 1, and 2.9 … 88 × it in the other measured rows, while split took 0.15 … 0.23 and
+    0.58 … 0.66 of it on the fully kept rows at B = 1 and B = 4; profiles/r30_block_attention_prefill_split.log).
 
-    Returns a fresh contiguous out [B, Hq, T, D] in q's dtype, every row written exactly once by ONE launch, or with
-    return_lse=True (out, lse) with lse float32 [B, Hq, T].  NO autograd, no atomics, no read-back, no workspace: the call
-    can be captured in a graph and replayed while k_lens, new_lens and the cache change in place.  scale defaults to 1/√D.'''
+    split (keyword only): None — this call in every respect: one launch, no workspace — or a positive
+    int s < 2³¹ (anything else: ValueError), for a SHORT CHUNK BEHIND A LONG CACHE, whose few tiles leave most of the chip
+    idle.  The 64-block list of a tile's layout row is cut by list position — entry p of a list beginning at beg belongs
+    to part (p − beg) // s; a skipped entry (outside the grid, above the diagonal, beyond k_len) stays in its part and
+    does not move the cut — and every (tile, query head, part) gets a workgroup; a second launch merges the parts.
+    parts_max = ⌈(Smax / 64) / s⌉ comes from the shape alone; at parts_max == 1 the call runs the unsplit launch.  Bits: a
+    part gives per row the running maximum m, the row sum l and the unnormalised float32 accumulator o of this call's own
+    statements over its entries in list order (a row without a token, or whose part computes nothing: (−inf, 0), its
+    accumulator never reaching out); parts merge in ascending order, M = max mᵢ, L = Σ lᵢ·wᵢ, O = Σ oᵢ·wᵢ with wᵢ = 1 where
+    mᵢ == M, else exp(mᵢ − M); the store is this call's own — round(O · (1 / L)) rounded once, lse = M + log L, zero and
+    −inf when L == 0.  So a row whose list holds at most s entries has bit for bit the unsplit out and lse, also beside
+    rows of many parts; a row's bits are a function of its item's operands, its list, pos and s — never of T, new_lens,
+    B, the neighbours or the launch: 100 tokens equal chunks of 60 and 40 at the same s; paged equals contiguous on the
+    gathered cache, fp8 without scales the 2-byte call on the widened cache, a strided cache its clone.  Rows of more
+    than one part agree with the unsplit call to rounding, not in bits.  The return value, every refusal, new_lens,
+    return_lse and graph capture are unchanged: two launches on the caller's stream, a workspace of B·Hq · (⌈T/64⌉ + 1) ·
+    parts_max · 64 · (D + 2) · 4 bytes from torch's allocator, no atomics, no read-back, no memset.
+    block_attention_prefill_split(B, Hq, T, Smax, D) is the split this project suggests for a shape (None: do not split).
+
+    Returns a fresh contiguous out [B, Hq, T, D] in q's dtype, every row written exactly once by ONE launch (split: by the
+    second of two), or with return_lse=True (out, lse) with lse float32 [B, Hq, T].  NO autograd, no atomics, no
+    read-back, no workspace without split: the call can be captured in a graph and replayed while k_lens, new_lens and
+    the cache change in place.  scale defaults to 1/√D.'''
     return _prefill('block_sparse_attention_prefill', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, new_lens, None, None,
-                    False, return_lse)
+                    False, return_lse, split)
 
 
 def block_sparse_attention_prefill_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
                                          layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *, new_lens=None,
-                                         return_lse: bool = False):
+                                         return_lse: bool = False, split=None):
     '''block_sparse_attention_prefill over a PAGED cache: the pool k_pages, v_pages [P, Hkv, page, D] and block_table
     [B, W] of block_sparse_attention_decode_paged, with that call's operand rules and refusals (Smax = W · page, pages of a
     power of two ≥ 16 keys; block_attention_prefill_paged_takes).  A table entry outside [0, P) hides its page's keys:
     nothing is loaded for them and their scores are −inf; entries of pages only in unlisted blocks, or wholly at or beyond
     k_lens[b], are never consulted.  Bits: for a pool and a table whose seen entries are in range, out and lse are bit for
     bit those of block_sparse_attention_prefill on the cache gathered to [B, Hkv, Smax, D] — independent of P, of where the
-    pages lie and of `page`.  Graph-capturable while k_lens, new_lens, the pool and the table change in place.'''
+    pages lie and of `page`.  Graph-capturable while k_lens, new_lens, the pool and the table change in place.  split: as in
+    block_sparse_attention_prefill, whose split call on the gathered cache has this one's bits.'''
     return _prefill('block_sparse_attention_prefill_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens,
-                    block, scale, new_lens, None, None, False, return_lse)
+                    block, scale, new_lens, None, None, False, return_lse, split)
 
 
 def block_sparse_attention_prefill_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
                                        block: int = 64, scale=None, *, k_scale=None, v_scale=None, new_lens=None,
-                                       return_lse: bool = False):
+                                       return_lse: bool = False, split=None):
     '''block_sparse_attention_prefill over an FP8 cache: k, v [B, Hkv, Smax, D] torch.float8_e4m3fn with k_scale / v_scale
     as in block_sparse_attention_decode_fp8, whose operand rules and refusals these are (strides multiples of 16 bytes;
     block_attention_prefill_fp8_takes).  Every byte is widened to q's type on its way into LDS, which is exact, and
     block_sparse_attention_prefill's statements follow: a score is multiplied by scale · k_scale[h], one float32 product,
     and with a v_scale the stored element is round(float32((O / L) · v_scale[h])).  With both scales None, out and lse are
     bit for bit those of block_sparse_attention_prefill on k.to(q.dtype), v.to(q.dtype).  (A v_scale TENSOR equal to 1 is
-    the scaled statement: in float16 it rounds O / L to float32 first and may differ from v_scale=None in a last bit.)'''
+    the scaled statement: in float16 it rounds O / L to float32 first and may differ from v_scale=None in a last bit.)  split:
+    as in block_sparse_attention_prefill; the merged O takes the same two stores.'''
     return _prefill('block_sparse_attention_prefill_fp8', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, new_lens, k_scale,
-                    v_scale, True, return_lse)
+                    v_scale, True, return_lse, split)
 
 
 def block_sparse_attention_prefill_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
                                              layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *,
-                                             k_scale=None, v_scale=None, new_lens=None, return_lse: bool = False):
+                                             k_scale=None, v_scale=None, new_lens=None, return_lse: bool = False, split=None):
     '''block_sparse_attention_prefill_paged over an FP8 pool: k_pages, v_pages [P, Hkv, page, D] torch.float8_e4m3fn with
     the scales of block_sparse_attention_prefill_fp8 (block_attention_prefill_paged_fp8_takes).  Bits: for in-range
     tables those of block_sparse_attention_prefill_fp8 with the same scales on the gathered cache; with both scales None
-    those of block_sparse_attention_prefill_paged on the pool widened to q's type.'''
+    those of block_sparse_attention_prefill_paged on the pool widened to q's type.  split: as in
+    block_sparse_attention_prefill, with the same equalities at the same split.'''
     return _prefill('block_sparse_attention_prefill_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout,
-                    k_lens, block, scale, new_lens, k_scale, v_scale, True, return_lse)
+                    k_lens, block, scale, new_lens, k_scale, v_scale, True, return_lse, split)
 
 
 # --------------------------------------------------------------------------- #
