@@ -1421,6 +1421,83 @@ int mi_rope_kv_append_paged_fp8_f16(int32_t items, int32_t heads, int32_t T, int
                                     mi_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * Query-aware key-block selection for decoding: per-block key bounds kept next to the cache, a selection
+ * kernel that scores every 64-key block against the newest tokens' queries and lists the K best per token, and a decode
+ * entry that walks those lists in the place of a CSR layout.  bfloat16 / float16 (2-byte bit patterns), D ∈ {32, 64, 96,
+ * 128}; items, heads, Smax, k_lens, lens_count, the cache operands and the paged arguments as in
+ * mi_block_attention_decode{,_paged}_*.  Nothing is read back, there are no atomics: every entry is graph-capturable.
+ *
+ * mi_kv_block_bounds{,_paged}_T: bounds [items][Smax/64][2][D] of T, 16-byte aligned: bounds[c][J][0][d] = min and
+ *   bounds[c][J][1][d] = max of k[c][j][d] over the SEEN keys j of block J — 64J ≤ j < min(64J + 64, clamp(k_len, 0, Smax))
+ *   and, paged, the table entry of j's logical page in [0, pages).  A block without a seen key is not written.  last == 0
+ *   refreshes every block with a seen key, last = n ≥ 1 only those holding a position of [k_len − n, k_len).  Exact, and a
+ *   function of the seen keys alone (the 16-bit patterns are compared in one total order in which −0 < +0; with NaN keys
+ *   the result is unspecified).  Rows at or beyond k_len, between the rows and behind invalid table entries are never read.
+ *   MI_EINVAL: D, Smax % 64, last < 0, items > 65535, heads / lens_count that do not divide items, null or misaligned
+ *   pointers, strides that are no multiples of 8 elements or ldk < D, the page rules.  Smax == 0 or items == 0: MI_OK.
+ *
+ * mi_block_select_T: q — head g of item c, token t at q + (c / heads)·batchQ + ((c % heads)·group + g)·headQ + t·ldq, 16-byte
+ *   aligned, strides multiples of 8 elements —, bounds as above.  Token t stands at pos = clamp(k_len, 0, Smax) − T + t; its
+ *   candidates are the blocks J ≤ pos / 64; s_g(J) = Σ_d max(q[g,d]·lo[J,d], q[g,d]·hi[J,d]) in fp32 (every product exact; the
+ *   order of the sum is fixed: block_select.hip's header), score(J) = max_g s_g(J); a NaN score ranks below every number.
+ *   The candidates among the first `sink` blocks and the `local` blocks ending at pos / 64 are always listed and count toward
+ *   K; the other slots go to the rest in (score descending, index ascending).  block_ids int32 [items][T][K] receives the list
+ *   in ASCENDING block index and −1 from block_counts[c][t] = min(K, candidates) on (0 for pos < 0); scores, if not null,
+ *   float32 [items][T][Smax/64]: the candidates' scores, −inf elsewhere.  Bounds of non-candidates are never read.
+ *   MI_EINVAL: K < 1, sink < 0, local < 1, sink + local > K, group outside 1 … 16, Smax/64 > mi_block_select_max_blocks()
+ *   (16 384: the scores of one token live in the LDS of one workgroup), D, Smax % 64, items > 65535, pointers, strides.
+ *
+ * mi_block_attention_decode_lists{,_paged}_T: mi_block_attention_decode{,_paged}_T with the list of token t of item c given
+ *   as the first clamp(block_counts[c·T + t], 0, K) entries of row c·T + t of block_ids [items][T][K] (int32, 4-byte aligned)
+ *   — in the place of row pos / 64 of a layout.  An entry outside [0, Smax/64) or wholly beyond pos is skipped inside its
+ *   chunk; a block listed twice counts twice.  The chunks — and the workspace:
+ *   mi_block_attention_decode_workspace_bytes(items, T, group, D, 64·K, chunk) — are those of K list positions.  For token t,
+ *   out and lse have the bits of mi_block_attention_decode{,_paged}_T with T = 1, k_len = pos + 1, the same chunk and a layout
+ *   whose row pos / 64 lists the same blocks in the same order.  MI_EINVAL: what that entry refuses but for the layout, K < 1
+ *   or 64·K beyond int32, null or misaligned block_ids / block_counts; MI_ERANGE: items·T·K beyond int32.
+ * ------------------------------------------------------------------------ */
+#define MI_KV_BLOCK_BOUNDS_OPERANDS                                                                                      \
+  int32_t D, const uint16_t *k, int64_t ldk, int64_t headK, int64_t batchK, const int32_t *k_lens, int32_t lens_count, \
+      int32_t last, uint16_t *bounds, mi_stream_t stream
+int mi_kv_block_bounds_bf16(int32_t items, int32_t heads, int32_t Smax, MI_KV_BLOCK_BOUNDS_OPERANDS);
+int mi_kv_block_bounds_f16(int32_t items, int32_t heads, int32_t Smax, MI_KV_BLOCK_BOUNDS_OPERANDS);
+/* (k and batchK: k_pages and its page stride) */
+int mi_kv_block_bounds_paged_bf16(int32_t items, int32_t heads, int32_t Smax, const int32_t* block_table, int64_t table_ld,
+                                  int32_t pages, int32_t page, MI_KV_BLOCK_BOUNDS_OPERANDS);
+int mi_kv_block_bounds_paged_f16(int32_t items, int32_t heads, int32_t Smax, const int32_t* block_table, int64_t table_ld,
+                                 int32_t pages, int32_t page, MI_KV_BLOCK_BOUNDS_OPERANDS);
+
+int32_t mi_block_select_max_blocks(void);
+#define MI_BLOCK_SELECT_OPERANDS                                                                                                \
+  int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, int32_t group, const uint16_t *q, int64_t ldq, int64_t headQ, \
+      int64_t batchQ, const uint16_t *bounds, const int32_t *k_lens, int32_t lens_count, int32_t K, int32_t sink, int32_t local,  \
+      int32_t *block_ids, int32_t *block_counts, float *scores, mi_stream_t stream
+int mi_block_select_bf16(MI_BLOCK_SELECT_OPERANDS);
+int mi_block_select_f16(MI_BLOCK_SELECT_OPERANDS);
+
+/* (the return type stands on a line of its own: these four take lists, not the rowptr / col / nnz / layouts head that the
+ * one-line declarations `int mi_block_attention_decode…(` of the eight layout entries share) */
+#define MI_DECODE_LISTS_OPERANDS                                                                                                \
+  int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t headK, int64_t batchK,     \
+      const uint16_t *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group,  \
+      int32_t chunk, float scale, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace,                     \
+      size_t workspace_bytes, mi_stream_t stream
+int
+mi_block_attention_decode_lists_bf16(const int32_t* block_ids, const int32_t* block_counts, int32_t K, int32_t items,
+                                         int32_t heads, int32_t T, int32_t Smax, MI_DECODE_LISTS_OPERANDS);
+int
+mi_block_attention_decode_lists_f16(const int32_t* block_ids, const int32_t* block_counts, int32_t K, int32_t items,
+                                        int32_t heads, int32_t T, int32_t Smax, MI_DECODE_LISTS_OPERANDS);
+int
+mi_block_attention_decode_lists_paged_bf16(const int32_t* block_ids, const int32_t* block_counts, int32_t K, int32_t items,
+                                               int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                               int64_t table_ld, int32_t pages, int32_t page, MI_DECODE_LISTS_OPERANDS);
+int
+mi_block_attention_decode_lists_paged_f16(const int32_t* block_ids, const int32_t* block_counts, int32_t K, int32_t items,
+                                              int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                              int64_t table_ld, int32_t pages, int32_t page, MI_DECODE_LISTS_OPERANDS);
+
+/* ------------------------------------------------------------------------ *
  * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in
  * bfloat16 / float16 (T, 2-byte bit patterns) with A given as the kept 64 × 64 blocks of a CSR block list, shared by
  * every item of the batch, and the sampled product on the same list:

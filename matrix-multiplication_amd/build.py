@@ -57,7 +57,9 @@ def _run(cmd, verbose):
 
 # Units whose kernels sit at the edge of the register file: compiled with the compiler's resource-usage remarks, which are
 # kept as build/<unit>.resources.txt (one line per kernel instantiation); a vector-register spill fails the build.
-RESOURCE_REPORTS = ("block_attention", "block_attention_decode", "block_attention_prefill")
+RESOURCE_REPORTS = ("block_attention", "block_attention_decode", "block_attention_prefill", "kv_block_bounds", "block_select")
+# … of which these have room to spare: any scratch memory fails their build too
+NO_SCRATCH = ("kv_block_bounds", "block_select")
 _RESOURCE_FIELDS = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill", "LDS Size [bytes/block]",
                     "Occupancy [waves/SIMD]")
 
@@ -78,6 +80,9 @@ def _write_resource_report(src: Path, remarks: str):
     spilled = [name for name, v in rows if v["VGPRs Spill"] > 0]
     if not rows or spilled:
         raise RuntimeError(f"{src.name}: " + ("no resource-usage remarks" if not rows else f"vector-register spills in {spilled}"))
+    scratch = [name for name, v in rows if v["ScratchSize [bytes/lane]"] > 0] if src.stem in NO_SCRATCH else []
+    if scratch:
+        raise RuntimeError(f"{src.name}: scratch memory in {scratch}")
 
 
 def _digest(paths, extra=""):

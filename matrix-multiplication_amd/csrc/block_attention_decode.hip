@@ -35,6 +35,11 @@
 //    element is T::down((O · inv) · v_scale[h]).  So without scales the call has the bits of the 2-byte call on the widened
 //    cache.  The scales are read from device memory by the kernels: never read back, graph-capturable.
 //
+//  * Lists in the place of a layout (mi_block_attention_decode_lists{,_paged}_{bf16,f16}): the list of token t of
+//    k / v item c is the first clamp(block_counts[c · T + t], 0, K) entries of row c · T + t of the caller's block_ids — what
+//    block_select.hip writes —, the chunks are counted over the K list positions, and everything after the list's two bounds is
+//    the same statements: the bits of the layout row that lists the same blocks in the same order.
+//
 // Kernel: grid (chunks, items, T), 256 threads.  No workgroup barrier inside the walk.  A wave loads the k tile of an
 // entry as 16-byte global loads straight into MFMA A fragments (lane (li, lg): row 16f + li, columns 32s + 8lg … + 7), the v
 // tile into registers and from there into a wave-private transposed LDS image [D][64 + 8] (a wave-level fence between its
@@ -51,6 +56,20 @@ namespace {
 
 constexpr int kWaves = 4;      // waves of a workgroup: wave w walks entries w, w + 4, … of the chunk
 constexpr int kMaxGroup = 16;  // own rows of the one MFMA tile
+
+// the list source as a form of the kernel's first parameter: TC itself — a CSR layout over a cache of TC — or Listed<T>
+template <class T>
+struct Listed {};
+template <class TS>
+struct Source {
+  typedef TS cache;
+  static constexpr bool lists = false;
+};
+template <class T>
+struct Source<Listed<T>> {
+  typedef T cache;
+  static constexpr bool lists = true;
+};
 
 struct Args {
   const int32_t* rowptr;  // [layouts][blocks + 1], with the layouts' bases
@@ -82,6 +101,10 @@ struct Args {
   // a count of 1 one scale for all heads, else one per k / v head
   const float *k_scale, *v_scale;
   int k_scale_count, v_scale_count;
+  // the list source of the *_lists entries: `col` is block_ids [items][T][list_k], the list of token t of
+  // item c its first clamp(counts[c · T + t], 0, list_k) entries; rowptr, nnz and layouts are not looked at
+  const int32_t* counts;
+  int list_k;
 };
 
 __device__ __forceinline__ void fence_wave() {  // LDS writes of this wave before, its reads after
@@ -231,8 +254,14 @@ __device__ __forceinline__ void finish(const Args& a, int c, int t, int g, int d
 // contiguous call on the gathered cache.
 // The cache element is part of the kernel's first parameter: T itself (k and v hold T), or Fp8<T> — the cache holds e4m3fn
 // bytes: the loads, the widening and the two scales differ, nothing else.
-template <class TC, int D, int FORM>
+// Where a token's list comes from is part of the kernel's first parameter too: row pos / 64 of the CSR layout of its k / v
+// item, or — Listed<T>, the *_lists entries, 2-byte caches only — row (c, t) of the caller's block_ids, cut
+// to block_counts.  A compile-time form of the walk: what follows the two bounds is the same statements, so a list has the
+// bits of the layout row that lists the same blocks in the same order.
+template <class TS, int D, int FORM>
 __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
+  typedef typename Source<TS>::cache TC;
+  constexpr bool LISTS = Source<TS>::lists;
   typedef typename Operand<TC>::type T;
   constexpr bool FP8 = Operand<TC>::fp8;
   typedef typename Cache<FP8>::elem E;
@@ -251,10 +280,18 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   const int pos = klen - a.T + t;  // the token's position: it sees keys j ≤ pos of the blocks its layout row lists
   int beg = 0, end = 0;            // this chunk's part of the list
   if (pos >= 0) {
-    const int32_t* rp = a.rowptr + (long)(c % a.layouts) * (a.blocks + 1);
-    long lo = rp[pos / kB], hi = rp[pos / kB + 1];
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > a.nnz ? a.nnz : hi;
+    long lo, hi;
+    if constexpr (LISTS) {
+      const long row = (long)c * a.T + t;
+      const int n = a.counts[row];
+      lo = row * a.list_k;
+      hi = lo + (n < 0 ? 0 : n > a.list_k ? a.list_k : n);
+    } else {
+      const int32_t* rp = a.rowptr + (long)(c % a.layouts) * (a.blocks + 1);
+      lo = rp[pos / kB], hi = rp[pos / kB + 1];
+      lo = lo < 0 ? 0 : lo;
+      hi = hi > a.nnz ? a.nnz : hi;
+    }
     lo += (long)ch * a.chunk;
     hi = hi < lo + a.chunk ? hi : lo + a.chunk;
     if (lo < hi) beg = (int)lo, end = (int)hi;
@@ -452,26 +489,49 @@ __global__ __launch_bounds__(128) void block_attention_decode_combine_kernel(Arg
   }
 }
 
+// the caller's lists of the *_lists entries: block_counts [items][T] and K, the entries of a row of block_ids
+struct Lists {
+  const int32_t* counts = nullptr;
+  int32_t K = 0;
+};
+
 int chunks_of(int32_t Smax, int32_t chunk) {  // from the shape alone; a list has at most Smax / 64 entries
   const long blocks = Smax / kB;
   const long n = (blocks + chunk - 1) / chunk;
   return (int)(n < 1 ? 1 : n);
 }
 
+// the walk's launch checked, then — with more than one chunk — the combine kernel
+template <class T>
+int finish_launch(const Args& a, int items, int D, hipStream_t s) {
+  const int st = mi::check_launch();
+  if (st != MI_OK || a.chunks == 1) return st;
+  hipLaunchKernelGGL((block_attention_decode_combine_kernel<T>), dim3((unsigned)items, (unsigned)a.T), dim3(128), 0, s, a, D);
+  return mi::check_launch();
+}
+
 template <class T, int D, bool FP8>
 int launch(const Args& a, int items, hipStream_t s) {
   const dim3 grid((unsigned)a.chunks, (unsigned)items, (unsigned)a.T);
   typedef std::conditional_t<FP8, Fp8<T>, T> TC;  // the cache element type is part of the kernel's first parameter
+  if constexpr (!FP8) {
+    if (a.counts) {  // the list source
+      if (!a.table)
+        hipLaunchKernelGGL((block_attention_decode_kernel<Listed<T>, D, kContiguous>), grid, dim3(256), 0, s, a);
+      else if (a.page_shift >= 6)
+        hipLaunchKernelGGL((block_attention_decode_kernel<Listed<T>, D, kPaged>), grid, dim3(256), 0, s, a);
+      else
+        hipLaunchKernelGGL((block_attention_decode_kernel<Listed<T>, D, kPagedSmall>), grid, dim3(256), 0, s, a);
+      return finish_launch<T>(a, items, D, s);
+    }
+  }
   if (!a.table)
     hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, kContiguous>), grid, dim3(256), 0, s, a);
   else if (a.page_shift >= 6)
     hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, kPaged>), grid, dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, kPagedSmall>), grid, dim3(256), 0, s, a);
-  const int st = mi::check_launch();
-  if (st != MI_OK || a.chunks == 1) return st;
-  hipLaunchKernelGGL((block_attention_decode_combine_kernel<T>), dim3((unsigned)items, (unsigned)a.T), dim3(128), 0, s, a, D);
-  return mi::check_launch();
+  return finish_launch<T>(a, items, D, s);
 }
 
 // Every check comes before the first HIP call.  page == 0: the contiguous cache, `outerK` / `outerV` its batch strides and
@@ -483,7 +543,13 @@ int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t
                  int64_t headK, int64_t outerK, const void* v, int64_t ldv, int64_t headV, int64_t outerV,
                  const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale, uint16_t* out, int64_t ldo,
                  int64_t strideO, float* lse, void* workspace, size_t workspace_bytes, hipStream_t s, const int32_t* table = nullptr,
-                 int64_t table_ld = 0, int32_t pages = 0, int32_t page = 0, const Scales& scales = Scales()) {
+                 int64_t table_ld = 0, int32_t pages = 0, int32_t page = 0, const Scales& scales = Scales(),
+                 const Lists& lists = Lists()) {
+  // the list source: `col` is block_ids, nnz its items · T · K entries; a list has at most K entries, so the chunks — and
+  // the workspace — are those of a cache of K blocks
+  const bool listed = lists.K != 0 || lists.counts;
+  if (listed && (lists.K < 1 || lists.K > 0x7fffffff / kB || !lists.counts || !aligned4(lists.counts) || !aligned4(col))) return MI_EINVAL;
+  const int32_t span = listed ? lists.K * kB : Smax;  // what the chunks are counted over
   if (!cache_form_ok(FP8, scales, heads, Smax, pages, page)) return MI_EINVAL;
   if (group < 1 || group > kMaxGroup || chunk < 1 || !takes_width(D)) return MI_EINVAL;
   const bool paged = page != 0;
@@ -492,16 +558,16 @@ int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t
   if (items > 65535 || T_ > 65535) return MI_EINVAL;  // the grid's y and z: no item loop
   if (items == 0 || T_ == 0) return MI_OK;
   if (layouts == 0 || heads == 0 || items % heads != 0 || lens_count < 1 || items % lens_count != 0) return MI_EINVAL;
-  if (!rowptr || (nnz > 0 && !col) || !k_lens || !aligned4(k_lens)) return MI_EINVAL;
+  if ((!listed && !rowptr) || (nnz > 0 && !col) || !k_lens || !aligned4(k_lens)) return MI_EINVAL;
   if (!lse || !aligned4(lse)) return MI_EINVAL;
   if (!q || !mi::aligned16(q) || ldq < D || !stride_ok(ldq) || !stride_ok(strideQ)) return MI_EINVAL;
   if (!out || !mi::aligned16(out) || ldo < D || !stride_ok(ldo) || !stride_ok(strideO)) return MI_EINVAL;
   const bool reads = nnz > 0 && Smax > 0 && (!paged || pages > 0);  // (an empty pool is never read: every entry of the table is invalid)
   if (!cache_operands_ok(FP8, reads, Smax, D, k, ldk, headK, outerK, v, ldv, headV, outerV, table, table_ld, page)) return MI_EINVAL;
-  const int chunks = chunks_of(Smax, chunk);
+  const int chunks = chunks_of(span, chunk);
   if (chunks > 1) {
     if (!workspace || !mi::aligned16(workspace)) return MI_EINVAL;
-    if (workspace_bytes < mi_block_attention_decode_workspace_bytes(items, T_, group, D, Smax, chunk)) return MI_ENOMEM;
+    if (workspace_bytes < mi_block_attention_decode_workspace_bytes(items, T_, group, D, span, chunk)) return MI_ENOMEM;
   }
   Args a = {};  // (zeroed: the 2-byte entries leave k_scale / v_scale null, which finish and the combine kernel read as 1)
   a.rowptr = rowptr, a.col = col, a.nnz = nnz, a.layouts = layouts, a.blocks = Smax / kB, a.heads = heads, a.group = group;
@@ -517,6 +583,7 @@ int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t
   a.k_lens = k_lens, a.lens_div = items / lens_count, a.scale = scale;
   a.out = out, a.ldo = ldo, a.strideO = strideO, a.lse = lse, a.ws = static_cast<float*>(workspace);
   if (FP8) a.k_scale = scales.k, a.k_scale_count = scales.k_count, a.v_scale = scales.v, a.v_scale_count = scales.v_count;
+  if (listed) a.counts = lists.counts, a.list_k = lists.K;
   switch (D) {
     case 32: return launch<T, 32, FP8>(a, items, s);
     case 64: return launch<T, 64, FP8>(a, items, s);
@@ -595,6 +662,39 @@ int mi_block_attention_decode_paged_fp8_bf16(MI_DECODE_PAGED_FP8_ARGS) {
 }
 int mi_block_attention_decode_paged_fp8_f16(MI_DECODE_PAGED_FP8_ARGS) {
   return page < 16 ? MI_EINVAL : decode_entry<F16, true>(MI_DECODE_PAGED_PASS, MI_DECODE_SCALES);
+}
+
+// the list source: the caller's block_ids / block_counts in the place of the layout
+#define MI_DECODE_LISTS_ARGS                                                                                                    \
+  const int32_t *block_ids, const int32_t *block_counts, int32_t K, int32_t items, int32_t heads, int32_t T, int32_t Smax,      \
+      int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t headK,                \
+      int64_t batchK, const uint16_t *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, \
+      int32_t group, int32_t chunk, float scale, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace,      \
+      size_t workspace_bytes, mi_stream_t stream
+#define MI_DECODE_LISTS_PAGED_ARGS                                                                                            \
+  const int32_t *block_ids, const int32_t *block_counts, int32_t K, int32_t items, int32_t heads, int32_t T, int32_t Smax,    \
+      const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page, int32_t D, const uint16_t *q, int64_t ldq,    \
+      int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t headK, int64_t batchK, const uint16_t *v, int64_t ldv,         \
+      int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale,    \
+      uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes, mi_stream_t stream
+// (a K that is no positive int32 is refused inside, before the product is looked at)
+#define MI_DECODE_LISTS_PASS                                                                                                  \
+  nullptr, block_ids, K < 1 ? 0 : (int64_t)items * T * K, 1, items, heads, T, Smax, D, q, ldq, strideQ, k, ldk, headK, batchK, v, \
+      ldv, headV, batchV, k_lens, lens_count, group, chunk, scale, out, ldo, strideO, lse, workspace, workspace_bytes,         \
+      static_cast<hipStream_t>(stream)
+#define MI_DECODE_LISTS Scales(), Lists{block_counts, K < 1 ? -1 : K}
+
+int mi_block_attention_decode_lists_bf16(MI_DECODE_LISTS_ARGS) {
+  return decode_entry<Bf16>(MI_DECODE_LISTS_PASS, nullptr, 0, 0, 0, MI_DECODE_LISTS);
+}
+int mi_block_attention_decode_lists_f16(MI_DECODE_LISTS_ARGS) {
+  return decode_entry<F16>(MI_DECODE_LISTS_PASS, nullptr, 0, 0, 0, MI_DECODE_LISTS);
+}
+int mi_block_attention_decode_lists_paged_bf16(MI_DECODE_LISTS_PAGED_ARGS) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16>(MI_DECODE_LISTS_PASS, block_table, table_ld, pages, page, MI_DECODE_LISTS);
+}
+int mi_block_attention_decode_lists_paged_f16(MI_DECODE_LISTS_PAGED_ARGS) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16>(MI_DECODE_LISTS_PASS, block_table, table_ld, pages, page, MI_DECODE_LISTS);
 }
 
 }  // extern "C"

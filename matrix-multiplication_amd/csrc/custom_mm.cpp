@@ -54,6 +54,9 @@ namespace {
 #include "custom_mm_block_attention_prefill.inc"
 #include "custom_mm_kv_append.inc"
 #include "custom_mm_rope_kv_append.inc"
+#include "custom_mm_kv_block_bounds.inc"
+#include "custom_mm_block_select.inc"
+#include "custom_mm_block_attention_decode_lists.inc"
 #include "custom_mm_bsr.inc"
 #include "custom_mm_bsr_linear.inc"
 
@@ -252,6 +255,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_kv_append_paged", &rope_kv_append_paged,
         "(q, k_new, v_new, cos, sin, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, new_lens, q_out, k_out, "
         "rotary_dim, interleaved, k_scale, v_scale): rope_kv_append into a pool of pages");
+  m.def("kv_block_bounds", &kv_block_bounds,
+        "(k [B, Hkv, Smax, D] bfloat16 / float16 through its own strides, k_lens int32 [B] or [1], last, bounds [B, Hkv, Smax/64, 2, D]): "
+        "the minimum and maximum of the seen keys of every 64-key block, in place; last = 0 every block that holds a key, n >= 1 "
+        "the blocks of the n newest positions; a block without a key is not written");
+  m.def("kv_block_bounds_paged", &kv_block_bounds_paged,
+        "(k_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, last, bounds): kv_block_bounds over a pool of pages; the "
+        "keys behind an entry outside [0, P) are left out");
+  m.def("block_select", &block_select,
+        "(q [B, Hq, T, D] through its own strides, bounds [B, Hkv, Smax/64, 2, D], k_lens, K, sink, local, block_ids int32 "
+        "[B, Hkv, T, K], block_counts int32 [B, Hkv, T], scores float32 [B, Hkv, T, Smax/64] or None): the K best candidate blocks "
+        "of every token by the bounds' upper estimate of q·k, forced sink / local blocks included, in ascending block index");
+  m.def("block_attention_decode_lists", &block_attention_decode_lists,
+        "(block_ids int32 [B, Hkv, T, K], block_counts int32 [B, Hkv, T], q [B, Hq, T, D], k, v [B, Hkv, Smax, D] through their own "
+        "strides, k_lens, scale, chunk, out, lse): block_attention_decode with the list of (k / v item, token) given as a row of "
+        "block_ids in the place of a layout row");
+  m.def("block_attention_decode_lists_paged", &block_attention_decode_lists_paged,
+        "(block_ids, block_counts, q, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, scale, chunk, out, lse): "
+        "block_attention_decode_lists over a pool of pages");
   m.def("bsr_mm", &bsr_mm,
         "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
         "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");

@@ -1,5 +1,6 @@
 // What the four units of the KV-cache family — block_attention_decode.hip and block_attention_prefill.hip (the read side),
-// kv_append.hip and rope_kv_append.hip (the write side) — say about the cache itself, said once: the scales of an fp8 cache,
+// kv_append.hip and rope_kv_append.hip (the write side) — and the selection's two, kv_block_bounds.hip and block_select.hip
+//  — say about the cache itself, said once: the scales of an fp8 cache,
 // the bytes an fp8 cache receives, and what every C entry refuses about the cache operands.  Not installed.  Everything here
 // has internal linkage (an anonymous namespace per including unit).
 #ifndef MI_KV_CACHE_DEVICE_H_

@@ -2776,6 +2776,313 @@ def rope_kv_cache_append_paged(q: torch.Tensor, k_new: torch.Tensor, v_new: torc
 
 
 # --------------------------------------------------------------------------- #
+# query-aware key-block selection for decoding: per-block key bounds, the K best blocks per token, decode over those lists
+# 
+# --------------------------------------------------------------------------- #
+
+_SELECT_MAX_BLOCKS = 16384  # blocks of one item (1 M keys): the scores of one token live in the LDS of one workgroup
+_SELECT_SIZES_TEXT = 'bfloat16 or float16 operands, head size D in {32, 64, 96, 128}, Smax a multiple of 64'
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, int) and not isinstance(x, bool)
+
+
+def key_block_bounds_takes(dtype, D: int, page=None) -> bool:
+    '''Whether key_block_bounds (page None) or key_block_bounds_paged (pages of `page` keys) takes a cache of `dtype` and
+    head size D — a function of these alone: bfloat16 / float16, D ∈ {32, 64, 96, 128}, page a power of two ≥ 16.'''
+    return dtype in _LOWP and _is_int(D) and D in _BLOCK_HEAD_SIZES and (page is None or _page_ok(page))
+
+
+def select_key_blocks_takes(dtype, D: int, group: int, blocks: int) -> bool:
+    '''Whether select_key_blocks takes q of `dtype`, head size D, `group` query heads per k / v head and `blocks` = Smax / 64
+    blocks per item — a function of these alone: bfloat16 / float16, D ∈ {32, 64, 96, 128}, 1 ≤ group ≤ 16 and
+    0 ≤ blocks ≤ 16 384 (1 M keys: one workgroup holds a token's scores in LDS).'''
+    return dtype in _LOWP and _is_int(D) and D in _BLOCK_HEAD_SIZES and _is_int(group) and 1 <= group <= _DECODE_MAX_GROUP and \
+        _is_int(blocks) and 0 <= blocks <= _SELECT_MAX_BLOCKS
+
+
+def block_attention_decode_selected_takes(dtype, D: int, group: int) -> bool:
+    '''Whether block_sparse_attention_decode_selected takes these: block_attention_decode_takes(dtype, D, 64, group).'''
+    return block_attention_decode_takes(dtype, D, _BLOCK_TILE, group)
+
+
+def block_attention_decode_selected_paged_takes(dtype, D: int, group: int, page: int) -> bool:
+    '''… and block_sparse_attention_decode_selected_paged: block_attention_decode_paged_takes(dtype, D, 64, group, page).'''
+    return block_attention_decode_paged_takes(dtype, D, _BLOCK_TILE, group, page)
+
+
+def _check_key_cache(what, kn, k, block_table):
+    '''The key cache of the bounds call, as the decode calls check theirs: shape, D, page and table, Smax a multiple of 64,
+    strides.  Returns (B, Hkv, Smax, D).'''
+    paged = kn == 'k_pages'
+    _check_lowp_operands(what, ((kn, k),), _SELECT_SIZES_TEXT)
+    if k.dim() != 4:
+        raise ValueError(f'{what}: {kn} must be {"[P, Hkv, page, D]" if paged else "[B, Hkv, Smax, D]"}, got {k.dim()}-d')
+    Hkv, D = k.shape[1], k.shape[3]
+    if D not in _BLOCK_HEAD_SIZES:
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_SELECT_SIZES_TEXT})')
+    if Hkv < 1:
+        raise ValueError(f'{what}: {kn} must hold Hkv >= 1 heads, got {tuple(k.shape)}')
+    if paged:
+        if not isinstance(block_table, torch.Tensor) or block_table.dim() != 2:
+            raise ValueError(f'{what}: block_table is required and must be a dense [B, W] tensor')
+        page = k.shape[2]
+        if not _page_ok(page):
+            raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} keys, got page = {page}')
+        B = block_table.shape[0]
+        Smax = _check_block_table(what, block_table, B) * page
+    else:
+        B, Smax = k.shape[0], k.shape[2]
+    if Smax % _BLOCK_TILE != 0:
+        raise ValueError(f'{what}: Smax = {Smax} must be a multiple of 64 (accepted: {_SELECT_SIZES_TEXT})')
+    if B * Hkv > _DECODE_MAX_GRID or Smax >= 2 ** 31:
+        raise ValueError(f'{what}: B·Hkv = {B * Hkv} must be at most {_DECODE_MAX_GRID} and Smax = {Smax} fit an int32')
+    _check_cache_strides(what, kn, k, D, 'page' if paged else 'batch')
+    return B, Hkv, Smax, D
+
+
+def _key_block_bounds(what, kn, k, block_table, k_lens, bounds, last):
+    paged = kn == 'k_pages'
+    B, Hkv, Smax, D = _check_key_cache(what, kn, k, block_table)
+    _check_k_lens(what, k_lens, B)
+    if last is not None and (not _is_int(last) or last < 1 or last >= 2 ** 31):
+        raise ValueError(f'{what}: last must be None (every block) or an int >= 1 (the tokens just appended), got {last!r}')
+    shape = (B, Hkv, Smax // _BLOCK_TILE, 2, D)
+    tensors = {kn: k}
+    if paged:
+        tensors['block_table'] = block_table
+    tensors['k_lens'] = k_lens
+    if bounds is not None:
+        if not isinstance(bounds, torch.Tensor) or bounds.layout != torch.strided or tuple(bounds.shape) != shape or \
+                not bounds.is_contiguous():
+            raise ValueError(f'{what}: bounds must be None or a contiguous dense tensor [B, Hkv, Smax/64, 2, D] = {list(shape)}')
+        if bounds.dtype != k.dtype:
+            raise RuntimeError(f'{what}: {kn} is {k.dtype} but bounds is {bounds.dtype}: the bounds are keys and have their dtype')
+        tensors['bounds'] = bounds
+    _check_on_device(what, **tensors)
+    with torch.no_grad():
+        if bounds is None:
+            bounds = torch.empty(shape, device=k.device, dtype=k.dtype)
+        if bounds.numel() > 0 and k.numel() > 0:
+            lens = _lens_i32(k_lens)
+            if paged:
+                custom_mm.kv_block_bounds_paged(k.detach(), _table_i32(block_table), lens, int(last or 0), bounds.detach())
+            else:
+                custom_mm.kv_block_bounds(k.detach(), lens, int(last or 0), bounds.detach())
+    return bounds
+
+
+def key_block_bounds(k: torch.Tensor, k_lens: torch.Tensor, bounds=None, *, last=None) -> torch.Tensor:
+    '''The per-block key bounds of a key cache, kept next to it for select_key_blocks: k [B, Hkv, Smax, D] bfloat16 or float16
+    — the cache of block_sparse_attention_decode, READ THROUGH ITS OWN STRIDES AND NEVER COPIED (its rules: last stride 1,
+    row stride ≥ D, strides multiples of 8 elements, a 16-byte aligned data pointer) —, D ∈ {32, 64, 96, 128}, Smax a multiple
+    of 64 (key_block_bounds_takes).  Returns bounds [B, Hkv, Smax/64, 2, D] in k's dtype, contiguous: allocated (uninitialised)
+    when `bounds` is None, else WRITTEN IN PLACE and returned.
+
+    bounds[b, h, J, 0, d] is the minimum and bounds[b, h, J, 1, d] the maximum of k[b, h, j, d] over the keys
+    j ∈ [64J, min(64J + 64, k_len)) of block J.  k_lens is the decode calls' operand — int32 / int64 [B] or 0-d, narrowed to
+    int32 on the device, clamped to [0, Smax] by the kernel, never read back.  A block that holds no key is NOT WRITTEN: it
+    keeps its bytes.  Rows at or beyond k_len and the gaps between the rows of a strided cache are never read.
+
+    last=None refreshes every block that holds a key.  last=T (an int ≥ 1) refreshes only the blocks that hold a position in
+    [k_len − T, k_len): the refresh after an append of T tokens — `kv_cache_append(…); key_block_bounds(k, lens, bounds,
+    last=T)`; every other block of `bounds` keeps its bytes.
+
+    Minimum and maximum are exact, and a function of the seen keys alone: they do not depend on the order of the rows, the
+    launch, or whether the cache is paged (the patterns are compared in one total order, in which −0 < +0).  With a NaN
+    among the seen keys the block's bounds are unspecified; nothing faults.  No atomics, no read-back: graph-capturable.
+    NO autograd.'''
+    return _key_block_bounds('key_block_bounds', 'k', k, None, k_lens, bounds, last)
+
+
+def key_block_bounds_paged(k_pages: torch.Tensor, block_table: torch.Tensor, k_lens: torch.Tensor, bounds=None, *,
+                           last=None) -> torch.Tensor:
+    '''key_block_bounds over a PAGED cache: k_pages [P, Hkv, page, D] and block_table [B, W] are the operands of
+    block_sparse_attention_decode_paged with its rules (page a power of two ≥ 16, an int32 table handed over as it is, an
+    int64 table narrowed on the device), Smax = W · page a multiple of 64.  The bounds are per ITEM, [B, Hkv, Smax/64, 2, D],
+    whatever pages the items share.  The keys of a logical page whose table entry lies outside [0, P) are invisible, as in
+    the decode call: they are never read and are left out of the minimum and maximum — the rest of their block is counted;
+    a block whose every seen key is invisible is not written.  Everything else is key_block_bounds': the same bits as that
+    call on the gathered cache.'''
+    return _key_block_bounds('key_block_bounds_paged', 'k_pages', k_pages, block_table, k_lens, bounds, last)
+
+
+def select_key_blocks(q: torch.Tensor, bounds: torch.Tensor, k_lens: torch.Tensor, K: int, *, sink: int = 1, local: int = 2,
+                      return_scores: bool = False):
+    '''The K key blocks worth reading for every new token, chosen on the device from the bounds of key_block_bounds — the
+    Quest upper bound: q [B, Hq, T, D] bfloat16 or float16, read through its own strides (the prefill calls' rule for q:
+    last stride 1, the others multiples of 8 elements, a 16-byte aligned data pointer), bounds [B, Hkv, Smax/64, 2, D]
+    contiguous in q's dtype, Hq = G · Hkv with 1 ≤ G ≤ 16, at most 16 384 blocks (1 M keys) per item
+    (select_key_blocks_takes).  Returns (block_ids int32 [B, Hkv, T, K], block_counts int32 [B, Hkv, T]) — the operands of
+    block_sparse_attention_decode_selected — and with return_scores=True also scores float32 [B, Hkv, T, Smax/64].
+
+    Token t of item b stands at pos = k_lens[b] − T + t (k_lens as in the decode calls: clamped to [0, Smax], never read
+    back); its CANDIDATES are the blocks J ≤ pos // 64.  In fp32, with q, lo = bounds[…, 0, :] and hi = bounds[…, 1, :]
+    widened exactly, s_g(J) = Σ_d max(q[g, d] · lo[J, d], q[g, d] · hi[J, d]) — no key of the block has a larger q·k — and
+    score(J) = max over the G query heads of the k / v head: the group shares one list, as it shares one layout in the
+    decode calls.  Every product is exact; the order of the sum over d is fixed (four partial sums over interleaved
+    8-element pieces, joined pairwise: csrc/block_select.hip).  A NaN score ranks below every number; −0 counts as +0.
+
+    FORCED blocks — the candidates among the first `sink` blocks and the `local` blocks ending at pos // 64 — are always
+    listed and count toward K.  The remaining slots go to the other candidates, highest first in (score descending, block
+    index ascending).  The list is written in ASCENDING BLOCK INDEX — the order the decode walk sums in —,
+    block_counts = min(K, candidates), the slots at or beyond it are −1, and a token with pos < 0 gets count 0.  scores holds
+    score(J) for the candidates and −inf elsewhere.  Bounds of non-candidates are never read.
+
+    ValueError before the first device call: K < 1, sink < 0, local < 1, sink + local > K, more than 16 384 blocks.  The bits
+    of a token's list depend on its own item's q, bounds, pos, K, sink and local only — never on B or the launch.  No
+    atomics, no read-back, fixed shapes: graph-capturable.  NO autograd.  K is the caller's choice; nothing picks it.'''
+    what = 'select_key_blocks'
+    _check_lowp_operands(what, (('q', q), ('bounds', bounds)), _SELECT_SIZES_TEXT)
+    for name, x in (('K', K), ('sink', sink), ('local', local)):
+        if not _is_int(x):
+            raise ValueError(f'{what}: {name} must be an int, got {x!r}')
+    if K < 1 or K >= 2 ** 31:
+        raise ValueError(f'{what}: K must be a positive int32, got {K}')
+    if sink < 0:
+        raise ValueError(f'{what}: sink must be >= 0, got {sink}')
+    if local < 1:
+        raise ValueError(f'{what}: local must be >= 1 (the token\'s own block is always read), got {local}')
+    if sink + local > K:
+        raise ValueError(f'{what}: sink + local = {sink + local} forced blocks do not fit K = {K}')
+    if q.dim() != 4 or bounds.dim() != 5:
+        raise ValueError(f'{what}: q must be [B, Hq, T, D] and bounds [B, Hkv, Smax/64, 2, D], got {q.dim()}-d and {bounds.dim()}-d')
+    B, Hq, T, D = q.shape
+    if D not in _BLOCK_HEAD_SIZES:
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_SELECT_SIZES_TEXT})')
+    Hkv, blocks = bounds.shape[1], bounds.shape[2]
+    if bounds.shape[0] != B or bounds.shape[3] != 2 or bounds.shape[4] != D or Hkv < 1 or Hq % Hkv != 0 or not bounds.is_contiguous():
+        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs contiguous bounds ({B}, "Hkv", "Smax/64", 2, {D}) with Hkv a '
+                         f'divisor of {Hq}, got {tuple(bounds.shape)}')
+    _check_decode_group(what, Hq, Hkv)
+    if T < 1:
+        raise ValueError(f'{what}: q must hold T >= 1 new tokens, got T = {T}')
+    if blocks > _SELECT_MAX_BLOCKS:
+        raise ValueError(f'{what}: {blocks} blocks per item exceed the {_SELECT_MAX_BLOCKS} (1 M keys) whose scores one workgroup '
+                         f'holds in LDS')
+    if B * Hkv > _DECODE_MAX_GRID or T > _DECODE_MAX_GRID or B * Hkv * T * max(K, blocks) >= 2 ** 31:
+        raise ValueError(f'{what}: B·Hkv = {B * Hkv} and T = {T} must each be at most {_DECODE_MAX_GRID} and B·Hkv·T·max(K, blocks) '
+                         f'fit an int32')
+    _check_k_lens(what, k_lens, B)
+    _check_source_strides(what, 'q', q)
+    _check_on_device(what, q=q, bounds=bounds, k_lens=k_lens)
+    with torch.no_grad():
+        ids = torch.empty((B, Hkv, T, K), device=q.device, dtype=torch.int32)
+        counts = torch.empty((B, Hkv, T), device=q.device, dtype=torch.int32)
+        scores = torch.empty((B, Hkv, T, blocks), device=q.device, dtype=torch.float32) if return_scores else None
+        if counts.numel() > 0:
+            custom_mm.block_select(q.detach(), bounds.detach(), _lens_i32(k_lens), int(K), int(sink), int(local), ids, counts, scores)
+    return (ids, counts, scores) if return_scores else (ids, counts)
+
+
+def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse):
+    '''The one body of the two list-source decode calls: _decode's checks minus the layout ones, the lists' own, one binding
+    call with the caller's lists as they are.'''
+    kn, vn = names
+    paged = kn == 'k_pages'
+    sizes_text = _DECODE_SIZES_TEXT + (_PAGED_SIZES_SUFFIX if paged else '')
+    _check_lowp_operands(what, (('q', q), (kn, k), (vn, v)), _DECODE_SIZES_TEXT)
+    for name, t in (('block_ids', block_ids), ('block_counts', block_counts)):
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided or t.dtype != torch.int32:
+            raise ValueError(f'{what}: {name} must be a dense int32 tensor (select_key_blocks\' output is handed over as it is)')
+    if chunk is not None and (not _is_int(chunk) or chunk < 1 or chunk >= 2 ** 31):
+        raise ValueError(f'{what}: chunk must be None or a positive int, got {chunk!r}')
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise ValueError(f'{what}: q must be [B, Hq, T, D] and {kn}, {vn} {"[P, Hkv, page, D]" if paged else "[B, Hkv, Smax, D]"}, '
+                         f'got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
+    B, Hq, T, D = q.shape
+    if D not in _BLOCK_HEAD_SIZES:
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {sizes_text})')
+    Hkv, Smax = k.shape[1], k.shape[2]
+    if (not paged and k.shape[0] != B) or k.shape[3] != D or Hkv < 1 or Hq % Hkv != 0:
+        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs {kn} '
+                         f'{("P", "Hkv", "page", D) if paged else (B, "Hkv", "Smax", D)} with Hkv a divisor of {Hq}, '
+                         f'got {tuple(k.shape)}')
+    _check_decode_group(what, Hq, Hkv)
+    if tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f'{what}: {vn} must be a dense tensor with {kn}\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
+    operands = {'q': q, kn: k, vn: v}
+    if paged:
+        page = k.shape[2]
+        if not _page_ok(page):
+            raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} keys, got page = {page} '
+                             f'(accepted: {sizes_text})')
+        Smax = _check_block_table(what, block_table, B) * page
+        operands['block_table'] = block_table
+    if T < 1:
+        raise ValueError(f'{what}: q must hold T >= 1 new tokens, got T = {T}')
+    if Smax % _BLOCK_TILE != 0:
+        raise ValueError(f'{what}: Smax = {Smax} must be a multiple of 64 (accepted: {sizes_text})')
+    if block_ids.dim() != 4 or tuple(block_ids.shape[:3]) != (B, Hkv, T) or block_ids.shape[3] < 1 or not block_ids.is_contiguous():
+        raise ValueError(f'{what}: block_ids must be a contiguous [B, Hkv, T, K] = [{B}, {Hkv}, {T}, K >= 1] tensor, got '
+                         f'{tuple(block_ids.shape)}')
+    if tuple(block_counts.shape) != (B, Hkv, T) or not block_counts.is_contiguous():
+        raise ValueError(f'{what}: block_counts must be a contiguous [B, Hkv, T] = [{B}, {Hkv}, {T}] tensor, got '
+                         f'{tuple(block_counts.shape)}')
+    K = block_ids.shape[3]
+    if B * Hkv > _DECODE_MAX_GRID or T > _DECODE_MAX_GRID:
+        raise ValueError(f'{what}: B·Hkv = {B * Hkv} and T = {T} must each be at most {_DECODE_MAX_GRID} (they are grid dimensions)')
+    if B * Hkv * T * K >= 2 ** 31 or K * _BLOCK_TILE >= 2 ** 31:
+        raise ValueError(f'{what}: B·Hkv·T·K = {B * Hkv * T * K} and 64·K must fit int32 indices')
+    _check_k_lens(what, k_lens, B)
+    outer = 'page' if paged else 'batch'
+    _check_cache_strides(what, kn, k, D, outer)
+    _check_cache_strides(what, vn, v, D, outer)
+    operands.update(block_ids=block_ids, block_counts=block_counts, k_lens=k_lens)
+    _check_on_device(what, **operands)
+    if scale is None:
+        scale = 1.0 / float(D) ** 0.5
+    if chunk is None:
+        chunk = _decode_chunk(Smax, D)
+    with torch.no_grad():
+        lens = _lens_i32(k_lens)
+        table = (_table_i32(block_table),) if paged else ()
+        qc = q.detach().contiguous()
+        out = torch.empty_like(qc)
+        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
+        if out.numel() > 0:
+            binding = custom_mm.block_attention_decode_lists_paged if paged else custom_mm.block_attention_decode_lists
+            binding(block_ids.detach(), block_counts.detach(), qc, k.detach(), v.detach(), *table, lens, float(scale), int(chunk), out, lse)
+    return (out, lse) if return_lse else out
+
+
+def block_sparse_attention_decode_selected(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
+                                           block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, chunk=None,
+                                           return_lse: bool = False):
+    '''block_sparse_attention_decode with the blocks of every token given as a LIST — the output of select_key_blocks — in the
+    place of a CSR layout: q [B, Hq, T, D], k and v [B, Hkv, Smax, D] and k_lens as in that call (64-key blocks, Smax a
+    multiple of 64, the cache read through its own strides and never copied), block_ids int32 [B, Hkv, T, K] and
+    block_counts int32 [B, Hkv, T], contiguous, HANDED TO THE KERNEL AS THEY ARE: no record is kept on them and no torch op
+    runs per call, so a step that rewrites them in place can be captured in a graph
+    (block_attention_decode_selected_takes).
+
+    The list of token t of k / v item (b, h) is the first clamp(block_counts[b, h, t], 0, K) entries of block_ids[b, h, t];
+    the G query heads of the group share it.  An entry outside [0, Smax/64) — the −1 padding — or wholly beyond
+    pos = k_lens[b] − T + t is skipped inside its chunk; keys beyond pos are never read; a block listed twice counts twice,
+    as a layout that stores a block twice does.  The list is cut into chunks of `chunk` entries by list position and summed
+    as block_sparse_attention_decode sums a layout row (chunk=None: the same constant of the module).
+
+    Bits: for token t, out and lse are bit for bit those of block_sparse_attention_decode with T = 1, k_lens = pos + 1, the
+    same chunk and a (B, Hkv) layout whose row pos // 64 lists the same blocks in the same order — a row's bits depend on
+    its list, pos and chunk only.  Returns out [B, Hq, T, D], or (out, lse) with return_lse=True.  No atomics, no read-back:
+    graph-capturable.  NO autograd.  fp8 caches are not taken.'''
+    return _decode_selected('block_sparse_attention_decode_selected', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens, scale,
+                            chunk, return_lse)
+
+
+def block_sparse_attention_decode_selected_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
+                                                 block_table: torch.Tensor, block_ids: torch.Tensor, block_counts: torch.Tensor,
+                                                 k_lens: torch.Tensor, scale=None, *, chunk=None, return_lse: bool = False):
+    '''block_sparse_attention_decode_selected over a PAGED cache: k_pages, v_pages [P, Hkv, page, D] and block_table [B, W]
+    are the operands of block_sparse_attention_decode_paged with its rules (Smax = W · page; an entry outside [0, P) hides
+    its page's keys); the lists are indexed by logical 64-key blocks, whatever `page` is.  Bit for bit the contiguous call
+    on the gathered cache (block_attention_decode_selected_paged_takes).'''
+    return _decode_selected('block_sparse_attention_decode_selected_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
+                            block_ids, block_counts, k_lens, scale, chunk, return_lse)
+
+
+# --------------------------------------------------------------------------- #
 # block-sparse (BSR) × dense products on the matrix cores
 # --------------------------------------------------------------------------- #
 
