@@ -196,7 +196,9 @@ __global__ __launch_bounds__(kThreads) void block_select_kernel(Args a) {
     const bool tie = !f && !all && !none && key == th;
     if (sure || (tie && tie_before < ties_taken)) {
       const int slot = sure_before + (tie_before < ties_taken ? tie_before : ties_taken);
-      if (slot < count) ids[slot] = J;  // (always: the guard keeps a wrong count inside the row)
+      // (always: the guard keeps a wrong count inside the row — on both sides: with more sure candidates than slots
+      // ties_taken, and with it the slot, would be negative)
+      if ((unsigned)slot < (unsigned)count) ids[slot] = J;
     }
     sure_before += sure ? 1 : 0;
     tie_before += tie ? 1 : 0;
