@@ -37,7 +37,8 @@
 //    qᵀ (dK += dSᵀ·Q); lse and δ of the walk rows are read per tile.
 //
 // kB, the transposed image's stride, pack_tile, accumulate and group_max / group_sum are block_attention_device.h's, which
-// block_attention_decode.hip shares; mfma<T> and half_of are mfma_device.h's.
+// block_attention_decode.hip shares, as is `score` from a row image, which block_attention_prefill.hip shares; mfma<T> and
+// half_of are mfma_device.h's.
 #include "block_attention_device.h"
 
 namespace {
@@ -113,20 +114,6 @@ template <int D>
 __device__ __forceinline__ void zero_own(uint4 (&f)[D / 32]) {
 #pragma unroll
   for (int s = 0; s < D / 32; ++s) f[s] = uint4{0u, 0u, 0u, 0u};
-}
-
-// acc[f][r] = ⟨walk row 16f + 4lg + r, own row li⟩ over d, from the row image R of the walk block
-template <class T, int D>
-__device__ __forceinline__ void score(f32x4 (&acc)[4], const unsigned short* R, const uint4 (&own)[D / 32], int li, int lg) {
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < D / 32; ++s) {
-      const uint4 a = *reinterpret_cast<const uint4*>(R + (16 * f + li) * (D + 8) + 32 * s + 8 * lg);
-      acc[f] = mfma<T>(a, own[s], acc[f]);
-    }
-  }
 }
 
 // rows [d][own row li] → own row li, columns 16fd + 4lg … + 3, each value times `mul`, rounded once

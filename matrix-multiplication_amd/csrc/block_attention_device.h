@@ -1,9 +1,10 @@
 // Device-side pieces shared by the three block-sparse attention units — block_attention.hip (forward and backward over
 // workgroup tiles staged in LDS), block_attention_decode.hip (one wave per list entry, k fragments straight from global
 // memory) and block_attention_prefill.hip (the forward's tiles fed through the KV cache's addressing, §3.27) — said once
-// (DESIGN.md §3.24): the block size, the transposed image of a walk block, a score-shaped tile as the B
-// operand of the product that sums over the walk rows, that product, and the reductions over a row's four lanes.  The two
-// `score` forms, the walkers and the Args stay with their units: one reads LDS, the other registers.  Not installed.
+// (DESIGN.md §3.24): the block size, the transposed image of a walk block, the scores of a walk block staged in LDS (the
+// training and the prefill walks'), a score-shaped tile as the B operand of the product that sums over the walk rows, that
+// product, and the reductions over a row's four lanes.  The decode unit's `score` from registers, the walkers and the Args
+// stay with their units.  Not installed.
 // Everything here has internal linkage (an anonymous namespace per including unit).
 #ifndef MI_BLOCK_ATTENTION_DEVICE_H_
 #define MI_BLOCK_ATTENTION_DEVICE_H_
@@ -15,6 +16,20 @@ namespace {
 constexpr int kB = 64;       // rows of a block: the kernels' tile on both sides
 constexpr int kTStr = kStr;  // row stride of a transposed image [D][64 + 8] in elements
 static_assert(kB == kTileK, "a transposed image row is one staged k-tile");
+
+// acc[f][r] = ⟨walk row 16f + 4lg + r, own row li⟩ over d, from the row image R [64][D + 8] of the walk block in LDS
+template <class T, int D>
+__device__ __forceinline__ void score(f32x4 (&acc)[4], const unsigned short* R, const uint4 (&own)[D / 32], int li, int lg) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s) {
+      const uint4 a = *reinterpret_cast<const uint4*>(R + (16 * f + li) * (D + 8) + 32 * s + 8 * lg);
+      acc[f] = mfma<T>(a, own[s], acc[f]);
+    }
+  }
+}
 
 // a score-shaped tile narrowed to T as the B operand of the two k-steps over the walk rows
 template <class T>

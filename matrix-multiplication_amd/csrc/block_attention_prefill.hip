@@ -34,15 +34,17 @@
 // head g of slot 8a + s, a slot one (item, tile)), where the guide observes — and does not promise — a shared L2.
 // Staging is the training kernel's double-buffered tile into Ks and Vt, its rows addressed through the cache form
 // (block_attention_cache_device.h: contiguous / pages ≥ 64 / pages of 16, 32 keys — there a lane's four rows lie in one
-// page, 4 divides 16); the table is read one list entry ahead.  Tile, score, store_own and next_block are copies of
-// block_attention.hip's private pieces with the cache form added (that unit stays as it is); kB, the images' strides,
-// pack_tile, accumulate, group_max / group_sum are block_attention_device.h's; mfma<T>, half_of, store_rc mfma_device.h's.
+// page, 4 divides 16); the table is read one list entry ahead.  Tile, store_own and next_block are copies of
+// block_attention.hip's private pieces with the cache form added; kB, the images' strides, score, pack_tile, accumulate,
+// group_max / group_sum are block_attention_device.h's; mfma<T>, half_of, store_rc mfma_device.h's.
 //
 // Split walks (mi_block_attention_prefill_split_* — DESIGN.md §3.28), for a short chunk behind a long cache: the list of a
-// tile's layout row is cut by list position into parts of `split` entries, block_attention_prefill_split_kernel — the walk
-// above as a sibling — gives every (work unit, part) a workgroup that stores the partial (o, m, l) of its 64 rows, and
-// block_attention_prefill_combine_kernel merges the parts in ascending order and makes the unsplit kernel's store.  The
-// unsplit kernel and its argument are untouched by it.
+// tile's layout row is cut by list position into parts of `split` entries.  There is ONE walk, prefill_walk<…, SPLIT>:
+// block_attention_prefill_kernel and block_attention_prefill_split_kernel are shells around it.  SPLIT gives every (work unit,
+// part) a workgroup over the part's entries, which leaves a tile without a token to the combine launch and stores the partial
+// (o, m, l) of its 64 rows where the unsplit walk normalises and stores out and lse.  block_attention_prefill_combine_kernel
+// merges the parts in ascending order and makes the unsplit store (store_row).  What the three kernels must agree on — the
+// tile's geometry (Geom), the clamped list range, the part count of a list — is said once, above the walk.
 #include <type_traits>
 
 #include "block_attention_cache_device.h"
@@ -132,20 +134,6 @@ struct Tile {
   }
 };
 
-// acc[f][r] = ⟨walk row 16f + 4lg + r, own row li⟩ over d, from the row image R of the walk block
-template <class T, int D>
-__device__ __forceinline__ void score(f32x4 (&acc)[4], const unsigned short* R, const uint4 (&own)[D / 32], int li, int lg) {
-#pragma unroll
-  for (int f = 0; f < 4; ++f) {
-    acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < D / 32; ++s) {
-      const uint4 a = *reinterpret_cast<const uint4*>(R + (16 * f + li) * (D + 8) + 32 * s + 8 * lg);
-      acc[f] = mfma<T>(a, own[s], acc[f]);
-    }
-  }
-}
-
 // The stored element of the training kernel's statement T::down(x · mul), AS ITS KERNELS HOLD IT.  For float16 the compiler
 // makes the product and the narrowing of block_attention_fwd_kernel ONE v_fma_mixlo_f16 — a single rounding of the exact
 // product, in all D / 4 stores of a lane (read from that unit's assembly; §3.20 met the same fold in the decode walk).  Left
@@ -200,185 +188,6 @@ __device__ __forceinline__ int next_block(const int32_t* col, int p, int end, in
   return p;
 }
 
-template <class TC, int D, int FORM, bool NEWLENS>
-__global__ __launch_bounds__(256) void block_attention_prefill_kernel(Args a) {
-  typedef typename Operand<TC>::type T;
-  constexpr bool FP8 = Operand<TC>::fp8;
-  typedef typename Cache<FP8>::elem E;
-  typedef typename Cache<FP8>::frag F;
-  __shared__ __attribute__((aligned(16))) unsigned short Ks[kB * (D + 8)];
-  __shared__ __attribute__((aligned(16))) unsigned short Vt[D * kTStr];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
-  const int G = a.group;
-  const int in_page = FORM == kContiguous ? 0 : (1 << a.page_shift) - 1;
-  for (long u = blockIdx.x; u < a.units; u += gridDim.x) {
-    // the G heads of a slot stand 8 work units apart
-    const long slot = u / ((long)kSpreadHeads * G) * kSpreadHeads + (u & (kSpreadHeads - 1));
-    if (slot >= a.slots) continue;  // (the padding of the last eight)
-    const int g = (int)((u / kSpreadHeads) % G);
-    const int c = (int)(slot / a.tiles), x = (int)(slot - (long)c * a.tiles);
-    const int bi = c / a.heads, h = c - bi * a.heads;
-    int klen = a.k_lens[c / a.lens_div];
-    klen = klen < 0 ? 0 : klen > a.smax ? (int)a.smax : klen;
-    int n = a.T;  // the item's new tokens: they stand in the last n of the T slots
-    if (NEWLENS) {
-      n = a.new_lens[a.new_lens_one ? 0 : bi];
-      n = n < 0 ? 0 : n > a.T ? a.T : n;
-    }
-    const int start = klen - a.T;                         // the position of slot 0 (negative: slots without a token)
-    const int first = klen - n < 0 ? 0 : klen - n;        // the existing tokens stand at [first, klen)
-    const int r = (start >> 6) + x;                       // the tile's layout row: ⌊start / 64⌋ + x
-    const int pos = r * kB + 16 * w + li;                 // the own row's position …
-    const long t = (long)pos - start;                     // … and its slot
-    const bool slot_ok = t >= 0 && t < a.T;               // the row is a row of q and out
-    const bool token = slot_ok && pos >= first;           // … that holds a token (pos < k_len follows from t < T)
-    const bool any = first < klen && r * kB + kB > first && r * kB < klen;  // the tile holds a token
-    const long item = (long)c * G + g;
-    uint16_t* orow = a.out + item * a.strideO + t * a.ldo;
-    if (!any) {  // nothing to walk: the zero rows of the slots it owns, if any
-      if (slot_ok) {
-#pragma unroll
-        for (int fd = 0; fd < D / 16; ++fd) *reinterpret_cast<uint2*>(orow + 16 * fd + 4 * lg) = uint2{0u, 0u};
-        if (lg == 0) a.lse[item * a.T + t] = -INFINITY;
-      }
-      continue;
-    }
-    // (0 ≤ r < blocks from here on: 64r + 63 ≥ first ≥ 0 and 64r < k_len ≤ Smax)
-    // (a pool has no batch stride: the item's pages come from its table row)
-    const E* K = static_cast<const E*>(a.k) + (FORM == kContiguous ? (long)bi * a.batchK : 0L) + (long)h * a.headK;
-    const E* V = static_cast<const E*>(a.v) + (FORM == kContiguous ? (long)bi * a.batchV : 0L) + (long)h * a.headV;
-    const int32_t* trow = FORM == kContiguous ? nullptr : a.table + (long)bi * a.table_ld;
-    // what multiplies a score: scale, or in the fp8 forms scale · k_scale[h] — one fp32 product per workgroup
-    const float sc = FP8 ? a.scale * head_scale(a.k_scale, a.k_scale_count, h) : a.scale;
-    const int kblocks = (klen + kB - 1) / kB;
-    long beg, end;
-    {
-      const int32_t* rp = a.rowptr + (long)(c % a.layouts) * (a.blocks + 1);
-      beg = rp[r], end = rp[r + 1];
-      beg = beg < 0 ? 0 : beg;
-      end = end > a.nnz ? a.nnz : end;
-    }
-    const int pend = (int)end;
-
-    uint4 qf[D / 32];  // the wave's 16 own rows as B fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of row li
-#pragma unroll
-    for (int s = 0; s < D / 32; ++s) qf[s] = uint4{0u, 0u, 0u, 0u};
-    if (token) {
-      const uint16_t* qrow = a.q + (long)bi * a.batchQ + ((long)h * G + g) * a.headQ + t * a.ldq;
-#pragma unroll
-      for (int s = 0; s < D / 32; ++s) qf[s] = *reinterpret_cast<const uint4*>(qrow + 32 * s + 8 * lg);
-    }
-    f32x4 o[D / 16];
-#pragma unroll
-    for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m = -INFINITY, l = 0.f;
-
-    // The tile whose loads are in flight (J, its table entries e, their validity ok) and the entry after it (pn, Jn, en): the
-    // column and the table entries of an entry are read ONE ENTRY AHEAD, right after the loads of the entry before it were
-    // issued, so the chain col[p] → table → tile never stands in front of a tile's loads.
-    Tile<D, F, E, FORM> tk, tv;
-    int J = 0, Jn = 0, pn = pend, e[4] = {0, 0, 0, 0}, en[4] = {0, 0, 0, 0};
-    unsigned ok = 0xfu;
-    auto issue = [&]() {
-      tk.load(K, a.ldk, a.pageK, J, e, ok, in_page, tid, klen - J * kB);
-      tv.load(V, a.ldv, a.pageV, J, e, ok, in_page, tid, klen - J * kB);
-    };
-    auto look_ahead = [&](int from) {
-      pn = next_block(a.col, from, pend, r, kblocks);
-      if (pn < pend) {
-        Jn = a.col[pn];
-        if constexpr (FORM != kContiguous) read_pages<FORM>(en, trow, Jn, a.page_shift);
-      }
-    };
-    int p = next_block(a.col, (int)beg, pend, r, kblocks);
-    if (p < pend) {
-      J = a.col[p];
-      if constexpr (FORM != kContiguous) {
-        read_pages<FORM>(e, trow, J, a.page_shift);
-        ok = valid_pages(e, a.pages);
-      }
-      issue();
-      look_ahead(p + 1);
-    }
-    while (p < pend) {
-      const int Jc = J;           // the block computed in this turn …
-      const unsigned seen = ok;   // … and the fragments of it that lie in a page (paged forms)
-      __syncthreads();  // the previous block's reads are done
-      tk.template store_rows<T>(Ks, tid);
-      tv.template store_transposed<T>(Vt, tid);
-      __syncthreads();
-      p = pn;
-      if (p < pend) {  // the next block's loads are in flight while this one is computed
-        J = Jn;
-        if constexpr (FORM != kContiguous) {
-#pragma unroll
-          for (int f = 0; f < 4; ++f) e[f] = en[f];
-          ok = valid_pages(e, a.pages);
-        }
-        issue();
-        look_ahead(p + 1);
-      }
-      const int kleft = klen - Jc * kB;  // keys of this block that exist
-      f32x4 s[4];
-      score<T, D>(s, Ks, qf, li, lg);
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          float x = s[f][rr] * sc;
-          if (Jc == r && 16 * f + 4 * lg + rr > 16 * w + li) x = -INFINITY;
-          if (16 * f + 4 * lg + rr >= kleft) x = -INFINITY;
-          s[f][rr] = x;
-        }
-      if (FORM != kContiguous && seen != 0xfu) {  // keys of a page outside the pool (a uniform branch: tables are in range as a rule)
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-          if (!((seen >> f) & 1u)) s[f] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-      }
-      float mt = -INFINITY;
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) mt = fmaxf(mt, s[f][rr]);
-      const float mn = fmaxf(m, group_max(mt));
-      const float alpha = m == mn ? 1.f : __expf(m - mn);  // (−inf stays: nothing seen yet)
-      float sum = 0.f;
-#pragma unroll
-      for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const float ex = s[f][rr] == -INFINITY ? 0.f : __expf(s[f][rr] - mn);
-          s[f][rr] = ex;
-          sum += ex;
-        }
-      l = l * alpha + sum;  // this lane's share of the row sum; the four shares meet after the walk
-      m = mn;
-#pragma unroll
-      for (int fd = 0; fd < D / 16; ++fd)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) o[fd][rr] *= alpha;
-      uint4 pb[2];
-      pack_tile<T>(pb, s);
-      accumulate<T, D>(o, Vt, pb, li, lg);
-    }
-    l = group_sum(l);
-    if (!token) {
-      l = 0.f;
-#pragma unroll
-      for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const float inv = l == 0.f ? 0.f : 1.f / l;
-    if (slot_ok) {
-      if (FP8 && a.v_scale != nullptr)
-        store_own_scaled<T, D>(o, inv, head_scale(a.v_scale, a.v_scale_count, h), orow, lg);
-      else
-        store_own<T, D>(o, inv, orow, lg);
-      if (lg == 0) a.lse[item * a.T + t] = l == 0.f ? -INFINITY : m + __logf(l);
-    }
-    __syncthreads();  // the next work unit restages
-  }
-}
-
 // What the split launches add to Args.  The unsplit kernel's argument stays as it was.
 struct SplitArgs {
   Args a;
@@ -386,13 +195,82 @@ struct SplitArgs {
   float* ws;         // [items · group][tiles][parts] partials of 64 · (D + 2) floats: o [64][D], then m [64], then l [64]
 };
 
-// block_attention_prefill_kernel with three differences: a work unit is (u, part) and walks the list entries
-// [beg + part · split, min(end, beg + (part + 1) · split)); it neither normalises nor stores out; its epilogue stores the
-// partial (o, m, l) of its 64 own rows.  Everything else — tile addressing, the look-ahead of the table, masking, staging, the
-// double buffer — is that kernel's text, kept a sibling because parametrising it moved the registers of the unsplit kernels.
-template <class TC, int D, int FORM, bool NEWLENS>
-__global__ __launch_bounds__(256) void block_attention_prefill_split_kernel(SplitArgs sa) {
-  const Args& a = sa.a;
+// Position tile x of k / v item c (of batch item bi) as thread (w, li) on own row 16w + li sees it: what the walks and the
+// combine launch must agree on, said once.
+struct Geom {
+  int klen;      // the item's length, clamped to [0, Smax]
+  int start;     // the position of slot 0 (negative: slots without a token)
+  int first;     // the existing tokens stand at [first, klen)
+  int r;         // the tile's layout row: ⌊start / 64⌋ + x
+  int pos;       // the own row's position …
+  long t;        // … and its slot
+  bool slot_ok;  // the row is a row of q and out
+  bool token;    // … that holds a token (pos < k_len follows from t < T)
+  bool any;      // the tile holds a token; then 0 ≤ r < blocks: 64r + 63 ≥ first ≥ 0 and 64r < k_len ≤ Smax
+};
+
+// `newlens`: a.new_lens is read (the walks' NEWLENS, a compile-time constant there); without it every slot ≥ −start has a token
+__device__ __forceinline__ Geom geometry(const Args& a, bool newlens, int c, int bi, int x, int w, int li) {
+  Geom g;
+  const int klen = a.k_lens[c / a.lens_div];
+  g.klen = klen < 0 ? 0 : klen > a.smax ? (int)a.smax : klen;
+  int n = a.T;  // the item's new tokens: they stand in the last n of the T slots
+  if (newlens) {
+    n = a.new_lens[a.new_lens_one ? 0 : bi];
+    n = n < 0 ? 0 : n > a.T ? a.T : n;
+  }
+  g.start = g.klen - a.T;
+  g.first = g.klen - n < 0 ? 0 : g.klen - n;
+  g.r = (g.start >> 6) + x;
+  g.pos = g.r * kB + 16 * w + li;
+  g.t = (long)g.pos - g.start;
+  g.slot_ok = g.t >= 0 && g.t < a.T;
+  g.token = g.slot_ok && g.pos >= g.first;
+  g.any = g.first < g.klen && g.r * kB + kB > g.first && g.r * kB < g.klen;
+  return g;
+}
+
+// the list of layout row r of k / v item c as positions [beg, end) of col, clamped to [0, nnz]
+struct ListRange {
+  long beg, end;
+};
+__device__ __forceinline__ ListRange list_range(const Args& a, int c, int r) {
+  const int32_t* rp = a.rowptr + (long)(c % a.layouts) * (a.blocks + 1);
+  const long beg = rp[r], end = rp[r + 1];
+  return {beg < 0 ? 0 : beg, end > a.nnz ? a.nnz : end};
+}
+
+// The parts of a list cut every `split` entries — part i holds the positions [beg + i · split, min(end, beg + (i + 1) · split))
+// — of which the first `parts` have a place in the workspace (a malformed rowptr cannot index past it).  A walk workgroup
+// whose part is not below this count leaves before any load, barrier or store; the combine launch merges exactly these.
+__device__ __forceinline__ int list_parts(const ListRange& ls, int split, int parts) {
+  if (ls.end <= ls.beg) return 0;
+  const unsigned np = (unsigned)(ls.end - ls.beg - 1) / (unsigned)split + 1u;  // (0 < end − beg ≤ nnz < 2³¹, split ≥ 1)
+  return np < (unsigned)parts ? (int)np : parts;
+}
+
+// The unsplit store of own row gm.t of query item `item` (head h of its k / v item) from the sums (o, m, l) of its walk, made
+// by the unsplit walk and by the combine launch: normalised, with `scaled` through an fp8 cache's v_scale; lse beside it.
+template <class T, int D>
+__device__ __forceinline__ void store_row(const Args& a, const Geom& gm, long item, int h, bool scaled, const f32x4 (&o)[D / 16],
+                                          float m, float l, int lg) {
+  const float inv = l == 0.f ? 0.f : 1.f / l;
+  if (gm.slot_ok) {
+    uint16_t* orow = a.out + item * a.strideO + gm.t * a.ldo;
+    if (scaled)
+      store_own_scaled<T, D>(o, inv, head_scale(a.v_scale, a.v_scale_count, h), orow, lg);
+    else
+      store_own<T, D>(o, inv, orow, lg);
+    if (lg == 0) a.lse[item * a.T + gm.t] = l == 0.f ? -INFINITY : m + __logf(l);
+  }
+}
+
+// The walk of both launches.  Without SPLIT a work unit u is one (item, tile, head) and walks its whole list; its epilogue is
+// store_row, and a tile without a token stores the zero rows of the slots it owns.  With SPLIT a work unit is (u, part) and
+// walks the list positions of its part; a tile without a token, and a part beyond the list's count, leave at once — the
+// combine launch writes those rows —, and the epilogue stores the partial (o, m, l) of the 64 own rows into `ws`.
+template <class TC, int D, int FORM, bool NEWLENS, bool SPLIT>
+__device__ __forceinline__ void prefill_walk(const Args& a, int split, int parts, float* ws) {
   typedef typename Operand<TC>::type T;
   constexpr bool FP8 = Operand<TC>::fp8;
   typedef typename Cache<FP8>::elem E;
@@ -402,35 +280,29 @@ __global__ __launch_bounds__(256) void block_attention_prefill_split_kernel(Spli
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lg = lane >> 4;
   const int G = a.group;
   const int in_page = FORM == kContiguous ? 0 : (1 << a.page_shift) - 1;
-  const long total = a.units * sa.parts;
+  const long total = SPLIT ? a.units * parts : a.units;
   for (long uu = blockIdx.x; uu < total; uu += gridDim.x) {
     // the parts of a work unit stand `units` workgroups apart, so the heads of a group keep their distance of 8
-    const long u = uu % a.units;
-    const int part = (int)(uu / a.units);
+    const long u = SPLIT ? uu % a.units : uu;
+    const int part = SPLIT ? (int)(uu / a.units) : 0;
     // the G heads of a slot stand 8 work units apart
     const long slot = u / ((long)kSpreadHeads * G) * kSpreadHeads + (u & (kSpreadHeads - 1));
     if (slot >= a.slots) continue;  // (the padding of the last eight)
     const int g = (int)((u / kSpreadHeads) % G);
     const int c = (int)(slot / a.tiles), x = (int)(slot - (long)c * a.tiles);
     const int bi = c / a.heads, h = c - bi * a.heads;
-    int klen = a.k_lens[c / a.lens_div];
-    klen = klen < 0 ? 0 : klen > a.smax ? (int)a.smax : klen;
-    int n = a.T;  // the item's new tokens: they stand in the last n of the T slots
-    if (NEWLENS) {
-      n = a.new_lens[a.new_lens_one ? 0 : bi];
-      n = n < 0 ? 0 : n > a.T ? a.T : n;
-    }
-    const int start = klen - a.T;                         // the position of slot 0 (negative: slots without a token)
-    const int first = klen - n < 0 ? 0 : klen - n;        // the existing tokens stand at [first, klen)
-    const int r = (start >> 6) + x;                       // the tile's layout row: ⌊start / 64⌋ + x
-    const int pos = r * kB + 16 * w + li;                 // the own row's position …
-    const long t = (long)pos - start;                     // … and its slot
-    const bool slot_ok = t >= 0 && t < a.T;               // the row is a row of q and out
-    const bool token = slot_ok && pos >= first;           // … that holds a token (pos < k_len follows from t < T)
-    const bool any = first < klen && r * kB + kB > first && r * kB < klen;  // the tile holds a token
+    const Geom gm = geometry(a, NEWLENS, c, bi, x, w, li);
+    const int klen = gm.klen, r = gm.r;
     const long item = (long)c * G + g;
-    if (!any) continue;  // nothing to walk: the combine launch writes the zero rows
-    // (0 ≤ r < blocks from here on: 64r + 63 ≥ first ≥ 0 and 64r < k_len ≤ Smax)
+    if (!gm.any) {  // nothing to walk: the zero rows of the slots it owns, if any
+      if (!SPLIT && gm.slot_ok) {
+        uint16_t* orow = a.out + item * a.strideO + gm.t * a.ldo;
+#pragma unroll
+        for (int fd = 0; fd < D / 16; ++fd) *reinterpret_cast<uint2*>(orow + 16 * fd + 4 * lg) = uint2{0u, 0u};
+        if (lg == 0) a.lse[item * a.T + gm.t] = -INFINITY;
+      }
+      continue;
+    }
     // (a pool has no batch stride: the item's pages come from its table row)
     const E* K = static_cast<const E*>(a.k) + (FORM == kContiguous ? (long)bi * a.batchK : 0L) + (long)h * a.headK;
     const E* V = static_cast<const E*>(a.v) + (FORM == kContiguous ? (long)bi * a.batchV : 0L) + (long)h * a.headV;
@@ -438,26 +310,19 @@ __global__ __launch_bounds__(256) void block_attention_prefill_split_kernel(Spli
     // what multiplies a score: scale, or in the fp8 forms scale · k_scale[h] — one fp32 product per workgroup
     const float sc = FP8 ? a.scale * head_scale(a.k_scale, a.k_scale_count, h) : a.scale;
     const int kblocks = (klen + kB - 1) / kB;
-    long beg, end;
-    {
-      const int32_t* rp = a.rowptr + (long)(c % a.layouts) * (a.blocks + 1);
-      beg = rp[r], end = rp[r + 1];
-      beg = beg < 0 ? 0 : beg;
-      end = end > a.nnz ? a.nnz : end;
+    ListRange ls = list_range(a, c, r);
+    if (SPLIT) {  // the part's entries, cut by list position
+      if (part >= list_parts(ls, split, parts)) continue;
+      ls.beg += (long)part * split;
+      ls.end = ls.end - ls.beg > split ? ls.beg + split : ls.end;
     }
-    {  // the part's entries, cut by list position; a part beyond the list's end leaves before any load, barrier or store
-      const long lo = beg + (long)part * sa.split;
-      if (lo >= end) continue;
-      beg = lo;
-      end = end - lo > sa.split ? lo + sa.split : end;
-    }
-    const int pend = (int)end;
+    const int pend = (int)ls.end;
 
     uint4 qf[D / 32];  // the wave's 16 own rows as B fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of row li
 #pragma unroll
     for (int s = 0; s < D / 32; ++s) qf[s] = uint4{0u, 0u, 0u, 0u};
-    if (token) {
-      const uint16_t* qrow = a.q + (long)bi * a.batchQ + ((long)h * G + g) * a.headQ + t * a.ldq;
+    if (gm.token) {
+      const uint16_t* qrow = a.q + (long)bi * a.batchQ + ((long)h * G + g) * a.headQ + gm.t * a.ldq;
 #pragma unroll
       for (int s = 0; s < D / 32; ++s) qf[s] = *reinterpret_cast<const uint4*>(qrow + 32 * s + 8 * lg);
     }
@@ -483,7 +348,7 @@ __global__ __launch_bounds__(256) void block_attention_prefill_split_kernel(Spli
         if constexpr (FORM != kContiguous) read_pages<FORM>(en, trow, Jn, a.page_shift);
       }
     };
-    int p = next_block(a.col, (int)beg, pend, r, kblocks);
+    int p = next_block(a.col, (int)ls.beg, pend, r, kblocks);
     if (p < pend) {
       J = a.col[p];
       if constexpr (FORM != kContiguous) {
@@ -555,24 +420,36 @@ __global__ __launch_bounds__(256) void block_attention_prefill_split_kernel(Spli
       accumulate<T, D>(o, Vt, pb, li, lg);
     }
     l = group_sum(l);
-    if (!token) {
+    if (!gm.token) {
       l = 0.f;
 #pragma unroll
       for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    // the partial of the own row: an empty one is (−inf, 0) with a zero accumulator (o is zero wherever m is −inf)
-    float* wp = sa.ws + (((item * a.tiles + x) * sa.parts + part) * (long)(kB * (D + 2)));
-    const int row = 16 * w + li;
+    if constexpr (SPLIT) {
+      // the partial of the own row: an empty one is (−inf, 0) with a zero accumulator (o is zero wherever m is −inf)
+      float* wp = ws + (((item * a.tiles + x) * parts + part) * (long)(kB * (D + 2)));
+      const int row = 16 * w + li;
 #pragma unroll
-    for (int fd = 0; fd < D / 16; ++fd) *reinterpret_cast<f32x4*>(wp + row * D + 16 * fd + 4 * lg) = o[fd];
-    if (lg == 0) {
-      wp[kB * D + row] = l == 0.f ? -INFINITY : m;
-      wp[kB * D + kB + row] = l;
+      for (int fd = 0; fd < D / 16; ++fd) *reinterpret_cast<f32x4*>(wp + row * D + 16 * fd + 4 * lg) = o[fd];
+      if (lg == 0) {
+        wp[kB * D + row] = l == 0.f ? -INFINITY : m;
+        wp[kB * D + kB + row] = l;
+      }
+    } else {
+      store_row<T, D>(a, gm, item, h, FP8 && a.v_scale != nullptr, o, m, l, lg);
     }
     __syncthreads();  // the next work unit restages
   }
 }
 
+template <class TC, int D, int FORM, bool NEWLENS>
+__global__ __launch_bounds__(256) void block_attention_prefill_kernel(Args a) {
+  prefill_walk<TC, D, FORM, NEWLENS, false>(a, 0, 1, nullptr);
+}
+template <class TC, int D, int FORM, bool NEWLENS>
+__global__ __launch_bounds__(256) void block_attention_prefill_split_kernel(SplitArgs sa) {
+  prefill_walk<TC, D, FORM, NEWLENS, true>(sa.a, sa.split, sa.parts, sa.ws);
+}
 
 // The second launch of a split call: one workgroup per (query item, tile), thread (w, li, lg) on own row 16w + li as in the
 // walk.  The tile's rows, its list and its number of parts are recomputed as the walk computes them; the partials of parts
@@ -591,30 +468,9 @@ __global__ __launch_bounds__(256) void block_attention_prefill_combine_kernel(Sp
     const int x = (int)(uu - item * a.tiles);
     const int c = (int)(item / G);
     const int bi = c / a.heads, h = c - bi * a.heads;
-    int klen = a.k_lens[c / a.lens_div];
-    klen = klen < 0 ? 0 : klen > a.smax ? (int)a.smax : klen;
-    int n = a.T;
-    if (a.new_lens) {
-      n = a.new_lens[a.new_lens_one ? 0 : bi];
-      n = n < 0 ? 0 : n > a.T ? a.T : n;
-    }
-    const int start = klen - a.T;
-    const int first = klen - n < 0 ? 0 : klen - n;
-    const int r = (start >> 6) + x;
-    const int pos = r * kB + 16 * w + li;
-    const long t = (long)pos - start;
-    const bool slot_ok = t >= 0 && t < a.T;
-    const bool token = slot_ok && pos >= first;
-    const bool any = first < klen && r * kB + kB > first && r * kB < klen;
-    int parts = 0;  // the parts of the tile's list: those whose workgroup wrote a partial
-    if (any) {
-      const int32_t* rp = a.rowptr + (long)(c % a.layouts) * (a.blocks + 1);
-      long beg = rp[r], end = rp[r + 1];
-      beg = beg < 0 ? 0 : beg;
-      end = end > a.nnz ? a.nnz : end;
-      const long np = end > beg ? (end - beg + sa.split - 1) / sa.split : 0;
-      parts = (int)(np < sa.parts ? np : sa.parts);
-    }
+    const Geom gm = geometry(a, a.new_lens != nullptr, c, bi, x, w, li);
+    // the parts of the tile's list: those whose workgroup wrote a partial
+    const int parts = gm.any ? list_parts(list_range(a, c, gm.r), sa.split, sa.parts) : 0;
     const float* wp = sa.ws + (item * a.tiles + x) * sa.parts * (long)(kB * (D + 2));
     const long pstride = (long)kB * (D + 2);
     const int row = 16 * w + li;
@@ -654,20 +510,12 @@ __global__ __launch_bounds__(256) void block_attention_prefill_combine_kernel(Sp
         }
       }
     }
-    if (!token) {  // (its partials are empty: l is 0 already)
+    if (!gm.token) {  // (its partials are empty: l is 0 already)
       l = 0.f;
 #pragma unroll
       for (int fd = 0; fd < D / 16; ++fd) o[fd] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    const float inv = l == 0.f ? 0.f : 1.f / l;
-    if (slot_ok) {
-      uint16_t* orow = a.out + item * a.strideO + t * a.ldo;
-      if (a.v_scale != nullptr)
-        store_own_scaled<T, D>(o, inv, head_scale(a.v_scale, a.v_scale_count, h), orow, lg);
-      else
-        store_own<T, D>(o, inv, orow, lg);
-      if (lg == 0) a.lse[item * a.T + t] = l == 0.f ? -INFINITY : M + __logf(l);
-    }
+    store_row<T, D>(a, gm, item, h, a.v_scale != nullptr, o, M, l, lg);
   }
 }
 
