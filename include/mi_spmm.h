@@ -650,8 +650,13 @@ int mi_gemm_bias_f16(int transa, int transb, int32_t m, int32_t n, int32_t k,
  * as mi_gemm_bias_*, all before any HIP call.
  * mi_gemm_split_bf16 / _f16 take the number of ranges from the caller (one product; splits ≥ 1, k % (32·splits) == 0,
  * else MI_EINVAL; workspace ≥ splits·m·n·4): what mi_gemm_ws_* run with splits = mi_gemm_lowp_split_count, and how the
- * rule's grid is measured (tools/bench_gemm_lowp_split.py). */
+ * rule's grid is measured (tools/bench_gemm_lowp_split.py).
+ * mi_gemm_lowp_tile_n(m, n, batch) is the width of the output tile every entry of this family launches for a shape — a
+ * function of the SHAPE alone: 128 (the 128 × 128 tile) when n > 64 and ceil(m/128) · ceil(n/128) · batch ≥ 512, else 64
+ * (the 128 × 64 tile; also for an empty shape).  For the partials of a split, batch is the number of ranges.  The bits of
+ * no result depend on it (see above); it is exported so that a test can tell which tile it ran. */
 int mi_gemm_lowp_split_count(int32_t m, int32_t n, int32_t k, int32_t batch);
+int mi_gemm_lowp_tile_n(int32_t m, int32_t n, int32_t batch);
 size_t mi_gemm_lowp_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t batch);
 int mi_gemm_ws_bf16(int transa, int transb, int32_t m, int32_t n, int32_t k,
                     const uint16_t* A, int64_t lda, int64_t strideA, const uint16_t* B,
@@ -1527,6 +1532,9 @@ mi_block_attention_decode_lists_paged_f16(const int32_t* block_ids, const int32_
  * the rows of B it would meet: NaN or inf there reaches no output.  An empty list stores zeros.  A listed column outside
  * the grid or an entry id outside [0, nvalues) is skipped (sddmm: the block is zero / not written), offsets are clamped
  * to [0, nnz].  No atomics, no workspace, no host synchronisation: graph-capturable.
+ * mi_bsr_mm_tile_n(rows, N, batch) is the column tile mi_bsr_mm_T launches for a shape — a function of the SHAPE alone:
+ * 128 when N > 64 and (rows/64) · ceil(N/128) · batch ≥ 512, else 64 (also for an empty shape).  The bits of C do not
+ * depend on it; it is exported so that a test can tell which tile it ran.
  * Validation before any HIP call: a negative size or stride, rows / inner / M / K not a multiple of 64, ld < N,
  * nvalues < nnz without entry ids → MI_EINVAL; nnz, nvalues or batch · N (sddmm) ≥ 2³¹ → MI_ERANGE; rows, N or batch
  * == 0 (sddmm: nnz == 0) → MI_OK, nothing touched; a NULL, odd or (values, dvalues) not 16-byte aligned pointer → MI_EINVAL.
@@ -1547,6 +1555,7 @@ int mi_bsr_sddmm_f16(const int32_t* entry_row, const int32_t* col, const int32_t
                      int32_t K, int32_t N, int32_t batch, const uint16_t* dC, int64_t lddc, int64_t strideDC,
                      const uint16_t* B, int64_t ldb, int64_t strideB, uint16_t* dvalues, int64_t nvalues,
                      mi_stream_t stream);
+int mi_bsr_mm_tile_n(int32_t rows, int32_t N, int32_t batch);
 
 /* ------------------------------------------------------------------------ *
  * Block-sparse linear layer on the matrix cores — NEW relative to the reference: Y = X·Wᵀ (+ bias) in bfloat16 / float16
@@ -1572,6 +1581,9 @@ int mi_bsr_sddmm_f16(const int32_t* entry_row, const int32_t* col, const int32_t
  *            S·nnz·64·64·4 bytes (smaller: MI_ENOMEM — never a silent unsplit product).
  * mi_bsr_wgrad_split_count(nnz, tokens) is a function of those two numbers alone: 1 below 2048 tokens, else the largest
  *   power of two ≤ min(1024 / nnz, tokens / 512, 32) (at least 1), halved until tokens % (32·S) == 0.
+ * mi_bsr_linear_tile_tokens(outer, tokens) is the token tile mi_bsr_linear_T launches for a shape — a function of the
+ *   SHAPE alone: 128 when tokens > 64 and (outer/64) · ceil(tokens/128) ≥ 512, else 64 (also for an empty shape).  The
+ *   bits of Y do not depend on it; it is exported so that a test can tell which tile it ran.
  *
  * Arithmetic: every product is v_mfma_f32_16x16x32_T with fp32 accumulators in the k-slots of mi_gemm_T; every output
  * element is ONE accumulator started at +0, carried through its list in the order given (the caller gives it ascending)
@@ -1607,6 +1619,7 @@ int mi_bsr_wgrad_f16(const int32_t* entry_row, const int32_t* col, const int32_t
                      uint16_t* dvalues, int64_t nvalues, int32_t splits, void* workspace, size_t workspace_bytes,
                      mi_stream_t stream);
 int mi_bsr_wgrad_split_count(int64_t nnz, int64_t tokens);
+int mi_bsr_linear_tile_tokens(int32_t outer, int32_t tokens);
 size_t mi_bsr_wgrad_workspace_bytes(int64_t nnz, int32_t splits);
 
 int mi_ipc_export(const void* dev_ptr, void* handle_out, int64_t* offset_out, int64_t* alloc_bytes_out);

@@ -310,10 +310,10 @@ int launch_linear(const LinArgs& g, bool vec, hipStream_t s) {
 }
 
 // The token tile: 128 while that fills the chip, else 64 (and always for T ≤ 64) — by the shape only, same bits either way.
+// mi_bsr_linear_tile_tokens is the rule, so that a caller can ask which one a shape takes.
 template <class T, bool TRANS_W, bool BIAS>
 int pick_linear(const LinArgs& g, bool vec, hipStream_t s) {
-  const long wide = (long)g.own_blocks * ((g.tokens + 127) / 128);
-  if (g.tokens <= 64 || wide < 512) return launch_linear<T, TRANS_W, 64, BIAS>(g, vec, s);
+  if (mi_bsr_linear_tile_tokens(g.own_blocks * kB, g.tokens) == 64) return launch_linear<T, TRANS_W, 64, BIAS>(g, vec, s);
   return launch_linear<T, TRANS_W, 128, BIAS>(g, vec, s);
 }
 
@@ -409,6 +409,14 @@ int mi_bsr_linear_f16(MI_BSR_LINEAR_ARGS) { return linear_entry<F16>(MI_BSR_LINE
 
 int mi_bsr_wgrad_bf16(MI_BSR_WGRAD_ARGS) { return wgrad_entry<Bf16>(MI_BSR_WGRAD_PASS, static_cast<hipStream_t>(stream)); }
 int mi_bsr_wgrad_f16(MI_BSR_WGRAD_ARGS) { return wgrad_entry<F16>(MI_BSR_WGRAD_PASS, static_cast<hipStream_t>(stream)); }
+
+// The token tile of mi_bsr_linear_T — a function of the shape alone (columns of Y, tokens): 128 when tokens > 64 and the
+// 64-column blocks of Y × 128-token tiles number at least 512, else 64.  The bits of the product do not depend on it.
+int mi_bsr_linear_tile_tokens(int32_t outer, int32_t tokens) {
+  if (outer <= 0 || tokens <= 64) return 64;
+  const long wide = (long)(outer / kB) * (((long)tokens + 127) / 128);
+  return wide < 512 ? 64 : 128;
+}
 
 // How many ranges the tokens are cut into — a function of (kept blocks, tokens) alone: the rule of
 // mi_gemm_lowp_split_count with the kept blocks in the place of the output tiles and the two constants fitted for this

@@ -228,10 +228,10 @@ int launch_mm(const MmArgs& g, bool vec, hipStream_t s) {
 }
 
 // The column tile: 128 while that fills the chip, else 64 (and always for N ≤ 64) — by the shape only, same bits either way.
+// mi_bsr_mm_tile_n is the rule, so that a caller can ask which one a shape takes.
 template <class T, bool TRANS_A>
 int pick_mm(const MmArgs& g, bool vec, hipStream_t s) {
-  const long wide = (long)g.own_blocks * ((g.n + 127) / 128) * g.batch;
-  if (g.n <= 64 || wide < 512) return launch_mm<T, TRANS_A, 64>(g, vec, s);
+  if (mi_bsr_mm_tile_n(g.own_blocks * kB, g.n, g.batch) == 64) return launch_mm<T, TRANS_A, 64>(g, vec, s);
   return launch_mm<T, TRANS_A, 128>(g, vec, s);
 }
 
@@ -302,6 +302,14 @@ int mi_bsr_mm_f16(MI_BSR_MM_ARGS) { return mm_entry<F16>(MI_BSR_MM_PASS, static_
       int32_t batch, const uint16_t *dC, int64_t lddc, int64_t strideDC, const uint16_t *B, int64_t ldb, int64_t strideB,    \
       uint16_t *dvalues, int64_t nvalues, mi_stream_t stream
 #define MI_BSR_SDDMM_PASS entry_row, col, entry_id, nnz, M, K, N, batch, dC, lddc, strideDC, B, ldb, strideB, dvalues, nvalues
+
+// The column tile of mi_bsr_mm_T — a function of the shape alone (rows of C, N, batch): 128 when N > 64 and the 64-row
+// blocks × 128-column tiles × items number at least 512, else 64.  The bits of the product do not depend on it.
+int mi_bsr_mm_tile_n(int32_t rows, int32_t N, int32_t batch) {
+  if (rows <= 0 || N <= 64 || batch <= 0) return 64;
+  const long wide = (long)(rows / kB) * (((long)N + 127) / 128) * batch;
+  return wide < 512 ? 64 : 128;
+}
 
 int mi_bsr_sddmm_bf16(MI_BSR_SDDMM_ARGS) { return sddmm_entry<Bf16>(MI_BSR_SDDMM_PASS, static_cast<hipStream_t>(stream)); }
 int mi_bsr_sddmm_f16(MI_BSR_SDDMM_ARGS) { return sddmm_entry<F16>(MI_BSR_SDDMM_PASS, static_cast<hipStream_t>(stream)); }

@@ -149,6 +149,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = py::none(), py::arg("splits") = 0,
         "bfloat16 / float16 op(A) op(B) (+ bias) with the deterministic split of k (splits = 0: the rule of gemm_lowp_split_count)");
   m.def("gemm_lowp_split_count", &gemm_lowp_split_count, "ranges cublas_mmul_splitk cuts k into for an m x n x k product (shape only)");
+  m.def("gemm_lowp_tile_n", &gemm_lowp_tile_n,
+        "(m, n, batch): 64 or 128, the width of the output tile a bfloat16 / float16 dense product launches (shape only; same bits)");
   m.def("column_sums", &column_sums, "sum over rows of a 2-d tensor (bias gradient)");
   m.def("naive_spmm_bias", &naive_spmm_bias, "CSR x dense + bias, fused epilogue");
   m.def("naive_spmm_ex", &naive_spmm_ex, "naive_spmm with the long-row rule pinned (-1 auto, 0 none, 1 split)");
@@ -286,6 +288,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("X"), py::arg("dvalues"), py::arg("splits") = 0,
         "dvalues[e] = dY[:, O-columns]^T X[:, I-columns] on the kept blocks, the tokens cut into `splits` ranges (0: the rule)");
   m.def("bsr_wgrad_split_count", &bsr_wgrad_split_count, "ranges bsr_wgrad cuts the tokens into for (kept blocks, tokens)");
+  m.def("bsr_mm_tile_n", &bsr_mm_tile_n, "(rows, N, batch): 64 or 128, the column tile bsr_mm launches (shape only; same bits)");
+  m.def("bsr_linear_tile_tokens", &bsr_linear_tile_tokens,
+        "(outer, tokens): 64 or 128, the token tile bsr_linear launches (shape only; same bits)");
   // Handles and automatic schedules own HIP streams and events: they are released while the interpreter — and with it the HIP
   // runtime — is still up (left to the destructors of the statics they segfaulted at process exit after the runtime had gone:
   // a program that never called cusparse_clean / auto_schedule_clear ended with exit code 139 AFTER its last line of output).

@@ -64,6 +64,12 @@ torch::Tensor bsr_mm(torch::Tensor offsets, torch::Tensor columns, c10::optional
   return C;
 }
 
+// the column tile (64 or 128) bsr_mm launches for C [batch, rows, N]: shape only
+int64_t bsr_mm_tile_n(int64_t rows, int64_t N, int64_t batch) {
+  check_sizes("bsr_mm_tile_n", {rows, N, batch});
+  return mi_bsr_mm_tile_n((int32_t)rows, (int32_t)N, (int32_t)batch);
+}
+
 // dvalues[entry_ids[p]] (None: dvalues[p]) = Σ over the items of dC[64·entry_row[p] …, :] · B[64·columns[p] …, :]ᵀ
 torch::Tensor bsr_sddmm(torch::Tensor entry_row, torch::Tensor columns, c10::optional<torch::Tensor> entry_ids, int64_t nnz,
                         torch::Tensor dC, torch::Tensor B, torch::Tensor dvalues) {

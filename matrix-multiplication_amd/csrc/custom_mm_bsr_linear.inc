@@ -64,6 +64,12 @@ int64_t bsr_wgrad_split_count(int64_t nnz, int64_t tokens) {
   return mi_bsr_wgrad_split_count(nnz, tokens);
 }
 
+// the token tile (64 or 128) bsr_linear launches for Y [tokens, outer]: shape only
+int64_t bsr_linear_tile_tokens(int64_t outer, int64_t tokens) {
+  check_sizes("bsr_linear_tile_tokens", {outer, tokens});
+  return mi_bsr_linear_tile_tokens((int32_t)outer, (int32_t)tokens);
+}
+
 // dvalues[entry_ids[p]] (None: dvalues[p]) = dY[:, 64·entry_row[p] …]ᵀ · X[:, 64·columns[p] …], the tokens cut into `splits`
 // ranges (0: the rule of bsr_wgrad_split_count); the fp32 workspace of a split lives until the stream has used it (the
 // caching allocator's stream order).

@@ -372,6 +372,12 @@ int64_t gemm_lowp_split_count(int64_t m, int64_t n, int64_t k) {
   return mi_gemm_lowp_split_count((int32_t)m, (int32_t)n, (int32_t)k, 1);
 }
 
+// the width (64 or 128) of the output tile a bfloat16 / float16 product of `batch` items of m × n launches: shape only
+int64_t gemm_lowp_tile_n(int64_t m, int64_t n, int64_t batch) {
+  check_sizes("gemm_lowp_tile_n", {m, n, batch});
+  return mi_gemm_lowp_tile_n((int32_t)m, (int32_t)n, (int32_t)batch);
+}
+
 torch::Tensor naive_spmm_bias(torch::Tensor A_values, torch::Tensor A_columns, torch::Tensor A_offsets,
                               int64_t nnzA, int64_t A_rows, int64_t A_cols, torch::Tensor B,
                               torch::Tensor bias, torch::Tensor C) {

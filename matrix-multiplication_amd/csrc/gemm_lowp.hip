@@ -294,10 +294,10 @@ int launch(const GemmArgs& g, bool vec, hipStream_t s) {
 
 // The tile shape: 128 × 128 while that fills the chip, else 128 × 64 (and always for n ≤ 64: the attention
 // context product probs·V and the like).  Same bits either way.  (The ranges of a split count as batch items here.)
+// mi_gemm_lowp_tile_n is the rule, so that a caller can ask which one a shape takes.
 template <class T, bool TA, bool TB, int EPI>
 int pick(const GemmArgs& g, bool vec, hipStream_t s) {
-  const long wide = (long)((g.m + 127) / 128) * ((g.n + 127) / 128) * g.batch;
-  if (g.n <= 64 || wide < 512) return launch<T, TA, TB, 128, 64, EPI>(g, vec, s);
+  if (mi_gemm_lowp_tile_n(g.m, g.n, g.batch) == 64) return launch<T, TA, TB, 128, 64, EPI>(g, vec, s);
   return launch<T, TA, TB, 128, 128, EPI>(g, vec, s);
 }
 
@@ -440,6 +440,14 @@ int mi_gemm_lowp_split_count(int32_t m, int32_t n, int32_t k, int32_t batch) {
   while (2L * S <= cap) S *= 2;
   while (S > 1 && k % (32 * S) != 0) S /= 2;
   return S;
+}
+
+// The columns of the output tile — a function of the shape alone: 128 (the 128 × 128 tile) when n > 64 and the 128 × 128
+// tiles of all items number at least 512, else 64 (the 128 × 64 tile).  The bits of the product do not depend on it.
+int mi_gemm_lowp_tile_n(int32_t m, int32_t n, int32_t batch) {
+  if (m <= 0 || n <= 64 || batch <= 0) return 64;
+  const long wide = (((long)m + 127) / 128) * (((long)n + 127) / 128) * batch;
+  return wide < 512 ? 64 : 128;
 }
 
 size_t mi_gemm_lowp_workspace_bytes(int32_t m, int32_t n, int32_t k, int32_t batch) {

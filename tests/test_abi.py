@@ -37,7 +37,8 @@ def test_header_declares_the_expected_entry_points():
     for must in ("mi_csr_transpose_batched_f32", "mi_csr_transpose_batched_workspace_bytes", "mi_spmm_long_rows_prepare",
                  "mi_spmm_csr_colmajor_ex_f32", "mi_spmm_colmajor_form", "mi_spmm_csr_ex_f32", "mi_spmm_auto_splits_long_rows", "mi_spmm_long_row_threshold", "mi_spmm_csr_f32", "mi_spmm_csr_batched_f32", "mi_spmm_csr_colmajor_f32", "mi_gemm_f32",
                  "mi_dense_to_csr_count", "mi_dense_to_csr_fill", "mi_csr_transpose_f32", "mi_sddmm_csr_f32",
-                 "mi_coo_to_csr_host", "mi_dummy_kernel"):
+                 "mi_coo_to_csr_host", "mi_dummy_kernel",
+                 "mi_gemm_lowp_tile_n", "mi_bsr_mm_tile_n", "mi_bsr_linear_tile_tokens"):
         assert must in names
 
 
@@ -314,3 +315,52 @@ def test_gemm_split_rule_is_a_function_of_the_shape_and_matches_the_oracles_rest
     assert {1, 2, 4, 8, 64} <= seen
     assert lib.mi_gemm_split_count(768, 768, 16384, 1) == 8 and lib.mi_gemm_split_count(256, 256, 65536, 1) == 64
     assert lib.mi_gemm_split_count(4096, 1024, 16384, 1) == 1   # 256 tiles: the chip is busy as it is
+
+
+def tile_rule(own_tiles, width, batch):
+    """The tile rule of the matrix-core launchers, restated: the 128-wide tile only for a width beyond 64 whose 128-wide
+    tiles, over every owner (128-row tile or 64-row block) and item, number at least 512."""
+    return 128 if width > 64 and own_tiles * -(-width // 128) * batch >= 512 else 64
+
+
+def test_tile_rules_are_functions_of_the_shape_and_match_their_restatement(lib, custom_mm):
+    """mi_gemm_lowp_tile_n, mi_bsr_mm_tile_n and mi_bsr_linear_tile_tokens — the rules the launchers themselves call
+    (include/mi_spmm.h) — against tile_rule on grids with both sides of width = 64, both sides of 511 / 512 wide tiles and
+    zero sizes; the custom_mm queries are the same functions.  The wide-tile GPU tests rest on these queries."""
+    i32 = ctypes.c_int32
+    lib.mi_gemm_lowp_tile_n.argtypes = [i32] * 3
+    lib.mi_bsr_mm_tile_n.argtypes = [i32] * 3
+    lib.mi_bsr_linear_tile_tokens.argtypes = [i32] * 2
+    widths = (0, 1, 63, 64, 65, 127, 128, 129, 197, 200, 290, 13147)
+    items = (0, 1, 2, 52, 56, 57, 63, 64, 73, 74, 511, 512, 513)
+    seen = {name: set() for name in ("gemm", "mm", "linear")}
+    for n in widths:
+        for batch in items:
+            for m in (0, 1, 127, 128, 129, 300, 896, 1024):
+                got = lib.mi_gemm_lowp_tile_n(m, n, batch)
+                assert got == tile_rule(-(-m // 128), n, batch) == custom_mm.gemm_lowp_tile_n(m, n, batch), (m, n, batch)
+                seen["gemm"].add(got)
+            for rows in (0, 64, 320, 448, 512):
+                got = lib.mi_bsr_mm_tile_n(rows, n, batch)
+                assert got == tile_rule(rows // 64, n, batch) == custom_mm.bsr_mm_tile_n(rows, n, batch), (rows, n, batch)
+                seen["mm"].add(got)
+    for tokens in widths + (128 * 73, 128 * 73 + 1, 128 * 102 + 1, 128 * 103, 128 * 511, 128 * 511 + 1, 128 * 512):
+        for outer in (0, 64, 320, 448, 64 * 7, 64 * 511, 64 * 512):
+            got = lib.mi_bsr_linear_tile_tokens(outer, tokens)
+            assert got == tile_rule(outer // 64, tokens, 1) == custom_mm.bsr_linear_tile_tokens(outer, tokens), (outer, tokens)
+            seen["linear"].add(got)
+    assert all(s == {64, 128} for s in seen.values()), seen
+    # 511 | 512 wide tiles, and 64 | 65 columns, by name
+    assert lib.mi_gemm_lowp_tile_n(896, 128, 73) == 64 and lib.mi_gemm_lowp_tile_n(1024, 128, 64) == 128      # 7·1·73 | 8·1·64
+    assert lib.mi_gemm_lowp_tile_n(128, 65, 511) == 64 and lib.mi_gemm_lowp_tile_n(128, 65, 512) == 128
+    assert lib.mi_gemm_lowp_tile_n(1 << 20, 64, 512) == 64 and lib.mi_gemm_lowp_tile_n(1 << 20, 65, 512) == 128
+    assert lib.mi_bsr_mm_tile_n(448, 128, 73) == 64 and lib.mi_bsr_mm_tile_n(512, 128, 64) == 128             # 7·1·73 | 8·1·64
+    assert lib.mi_bsr_mm_tile_n(64, 129, 255) == 64 and lib.mi_bsr_mm_tile_n(64, 129, 256) == 128             # 1·2·255 | 1·2·256
+    assert lib.mi_bsr_mm_tile_n(64 * 512, 64, 512) == 64 and lib.mi_bsr_mm_tile_n(64 * 512, 65, 1) == 128
+    assert lib.mi_bsr_linear_tile_tokens(448, 128 * 73) == 64 and lib.mi_bsr_linear_tile_tokens(448, 128 * 73 + 1) == 128  # 7·73 | 7·74
+    assert lib.mi_bsr_linear_tile_tokens(64, 128 * 511 + 1) == 128 and lib.mi_bsr_linear_tile_tokens(64, 128 * 511) == 64
+    assert lib.mi_bsr_linear_tile_tokens(64 * 512, 64) == 64 and lib.mi_bsr_linear_tile_tokens(64 * 512, 65) == 128
+    # the shapes of the wide-tile GPU tests and of their narrow twins
+    assert lib.mi_bsr_mm_tile_n(320, 197, 52) == 128 and lib.mi_bsr_mm_tile_n(448, 200, 52) == 128 and lib.mi_bsr_mm_tile_n(448, 200, 1) == 64
+    assert lib.mi_bsr_linear_tile_tokens(320, 13147) == 128 and lib.mi_bsr_linear_tile_tokens(448, 200) == 64
+    assert lib.mi_gemm_lowp_tile_n(300, 290, 60) == 128 and lib.mi_gemm_lowp_tile_n(300, 290, 1) == 64

@@ -12,6 +12,11 @@ unkept blocks left out; the weight gradient with the deterministic split of the 
   4. a long list (1, 2, 3, 40 kept blocks in one block row) within |C − E| ≤ u_T·|E| + k·2⁻²³·S (+ 2⁻²⁵ for fp16);
   5. invariance: leading dimensions, the checked alignment form, the order of the layout, repeated runs;
   6. unkept blocks are never read; 7. graph capture with the split inside; 8. memory.
+Of these only 8 at 4096 tokens reaches the 128-token tile (custom_mm.bsr_linear_tile_tokens is the rule), and it asserts memory;
+  9. the 128-token tile — 1, 3 and 5 (the position of a token, the checked form and its stores) there:
+     tests/test_gpu_lowp_wide_tiles.py;
+ 10. malformed lists — a column outside the grid, an id outside the values, offsets outside [0, nnz]:
+     tests/test_gpu_block_lists_malformed.py.
 Here a layout row is a block row of W (out) and a layout column a block column (in).
 """
 import ctypes

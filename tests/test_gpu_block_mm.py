@@ -11,6 +11,10 @@ store — the instruction and the order of this package's dense low-precision pr
      layout, repeated runs;
   5. unkept blocks are never read; 6. graph capture; 7. memory;
   8. 65 538 items, exact as in 1: the second pass of bsr_mm's item loop behind the 65 535-item grid cap.
+Every shape here stays below 512 wide tiles and so takes the 64-column tile (custom_mm.bsr_mm_tile_n is the rule);
+  9. the 128-column tile — 1, 2, 4 (items, the checked form) and 5 there: tests/test_gpu_lowp_wide_tiles.py;
+ 10. malformed lists — a column outside the grid, an id outside the values, offsets outside [0, nnz]:
+     tests/test_gpu_block_lists_malformed.py.
 """
 import pytest
 import torch
