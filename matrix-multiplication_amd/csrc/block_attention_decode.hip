@@ -47,7 +47,10 @@
 // pack_tile, accumulate and group_max / group_sum are block_attention_device.h's, which block_attention.hip shares (the walk
 // rows are the keys here); mfma<T> and half_of are mfma_device.h's; what is said about the cache is
 // kv_cache_device.h's (§3.23), what is said about a walk over it — Fp8 / Operand / Cache, widen, the forms, read_pages,
-// valid_pages — block_attention_cache_device.h's, which block_attention_prefill.hip shares (§3.27).  `score` is this unit's own: its k fragments come from registers.
+// valid_pages — block_attention_cache_device.h's, which block_attention_prefill.hip shares (§3.27).  `score` is this unit's
+// own: its k fragments come from registers.  Host side: what a reading entry checks and fills alike in both units — ReadCall,
+// read_sizes_status, read_operands_ok, fill_read_args, with_width, with_form — is that header's too (§3.31); decode_entry keeps
+// the lists' rules, group ≤ 16, chunk, the grid's bounds, q and the workspace.
 #include <type_traits>
 
 #include "block_attention_cache_device.h"
@@ -514,82 +517,48 @@ template <class T, int D, bool FP8>
 int launch(const Args& a, int items, hipStream_t s) {
   const dim3 grid((unsigned)a.chunks, (unsigned)items, (unsigned)a.T);
   typedef std::conditional_t<FP8, Fp8<T>, T> TC;  // the cache element type is part of the kernel's first parameter
-  if constexpr (!FP8) {
-    if (a.counts) {  // the list source
-      if (!a.table)
-        hipLaunchKernelGGL((block_attention_decode_kernel<Listed<T>, D, kContiguous>), grid, dim3(256), 0, s, a);
-      else if (a.page_shift >= 6)
-        hipLaunchKernelGGL((block_attention_decode_kernel<Listed<T>, D, kPaged>), grid, dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((block_attention_decode_kernel<Listed<T>, D, kPagedSmall>), grid, dim3(256), 0, s, a);
-      return finish_launch<T>(a, items, D, s);
+  with_form(a, [&](auto form) {
+    constexpr int FORM = decltype(form)::value;
+    if constexpr (!FP8) {
+      if (a.counts) {  // the list source
+        hipLaunchKernelGGL((block_attention_decode_kernel<Listed<T>, D, FORM>), grid, dim3(256), 0, s, a);
+        return 0;
+      }
     }
-  }
-  if (!a.table)
-    hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, kContiguous>), grid, dim3(256), 0, s, a);
-  else if (a.page_shift >= 6)
-    hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, kPaged>), grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, kPagedSmall>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, FORM>), grid, dim3(256), 0, s, a);
+    return 0;
+  });
   return finish_launch<T>(a, items, D, s);
 }
 
-// Every check comes before the first HIP call.  page == 0: the contiguous cache, `outerK` / `outerV` its batch strides and
-// no table; page > 0: a pool of `pages` pages of `page` keys, `outerK` / `outerV` its page strides, Smax = the table's
-// logical pages · page.  FP8: k and v are e4m3fn bytes (their strides multiples of 16) with the two scales of `scales`.
+// Every check comes before the first HIP call.  `r`: what every reading entry takes (block_attention_cache_device.h), FP8 its
+// cache type; q, chunk and the workspace are this entry's own.
 template <class T, bool FP8 = false>
-int decode_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T_,
-                 int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq, int64_t strideQ, const void* k, int64_t ldk,
-                 int64_t headK, int64_t outerK, const void* v, int64_t ldv, int64_t headV, int64_t outerV,
-                 const int32_t* k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale, uint16_t* out, int64_t ldo,
-                 int64_t strideO, float* lse, void* workspace, size_t workspace_bytes, hipStream_t s, const int32_t* table = nullptr,
-                 int64_t table_ld = 0, int32_t pages = 0, int32_t page = 0, const Scales& scales = Scales(),
-                 const Lists& lists = Lists()) {
+int decode_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t strideQ, int32_t chunk, void* workspace,
+                 size_t workspace_bytes, hipStream_t s, const Lists& lists = Lists()) {
   // the list source: `col` is block_ids, nnz its items · T · K entries; a list has at most K entries, so the chunks — and
   // the workspace — are those of a cache of K blocks
   const bool listed = lists.K != 0 || lists.counts;
-  if (listed && (lists.K < 1 || lists.K > 0x7fffffff / kB || !lists.counts || !aligned4(lists.counts) || !aligned4(col))) return MI_EINVAL;
-  const int32_t span = listed ? lists.K * kB : Smax;  // what the chunks are counted over
-  if (!cache_form_ok(FP8, scales, heads, Smax, pages, page)) return MI_EINVAL;
-  if (group < 1 || group > kMaxGroup || chunk < 1 || !takes_width(D)) return MI_EINVAL;
-  const bool paged = page != 0;
-  if (nnz < 0 || layouts < 0 || items < 0 || heads < 0 || T_ < 0 || Smax < 0 || Smax % kB != 0) return MI_EINVAL;
-  if (nnz > 0x7fffffffLL) return MI_ERANGE;
-  if (items > 65535 || T_ > 65535) return MI_EINVAL;  // the grid's y and z: no item loop
-  if (items == 0 || T_ == 0) return MI_OK;
-  if (layouts == 0 || heads == 0 || items % heads != 0 || lens_count < 1 || items % lens_count != 0) return MI_EINVAL;
-  if ((!listed && !rowptr) || (nnz > 0 && !col) || !k_lens || !aligned4(k_lens)) return MI_EINVAL;
-  if (!lse || !aligned4(lse)) return MI_EINVAL;
-  if (!q || !mi::aligned16(q) || ldq < D || !stride_ok(ldq) || !stride_ok(strideQ)) return MI_EINVAL;
-  if (!out || !mi::aligned16(out) || ldo < D || !stride_ok(ldo) || !stride_ok(strideO)) return MI_EINVAL;
-  const bool reads = nnz > 0 && Smax > 0 && (!paged || pages > 0);  // (an empty pool is never read: every entry of the table is invalid)
-  if (!cache_operands_ok(FP8, reads, Smax, D, k, ldk, headK, outerK, v, ldv, headV, outerV, table, table_ld, page)) return MI_EINVAL;
+  if (listed && (lists.K < 1 || lists.K > 0x7fffffff / kB || !lists.counts || !aligned4(lists.counts) || !aligned4(r.col))) return MI_EINVAL;
+  const int32_t span = listed ? lists.K * kB : r.Smax;  // what the chunks are counted over
+  if (r.group > kMaxGroup || chunk < 1) return MI_EINVAL;
+  if (const int st = read_sizes_status(FP8, r)) return st;
+  if (r.items > 65535 || r.T > 65535) return MI_EINVAL;  // the grid's y and z: no item loop
+  if (read_is_empty(r)) return MI_OK;
+  if (!q || !mi::aligned16(q) || ldq < r.D || !stride_ok(ldq) || !stride_ok(strideQ)) return MI_EINVAL;
+  if (!read_operands_ok(FP8, r, listed)) return MI_EINVAL;
   const int chunks = chunks_of(span, chunk);
   if (chunks > 1) {
     if (!workspace || !mi::aligned16(workspace)) return MI_EINVAL;
-    if (workspace_bytes < mi_block_attention_decode_workspace_bytes(items, T_, group, D, span, chunk)) return MI_ENOMEM;
+    if (workspace_bytes < mi_block_attention_decode_workspace_bytes(r.items, r.T, r.group, r.D, span, chunk)) return MI_ENOMEM;
   }
-  Args a = {};  // (zeroed: the 2-byte entries leave k_scale / v_scale null, which finish and the combine kernel read as 1)
-  a.rowptr = rowptr, a.col = col, a.nnz = nnz, a.layouts = layouts, a.blocks = Smax / kB, a.heads = heads, a.group = group;
-  a.T = T_, a.chunk = chunk, a.chunks = chunks, a.smax = Smax;
+  Args a = {};
+  fill_read_args(a, FP8, r);
+  a.chunk = chunk, a.chunks = chunks;
   a.q = q, a.ldq = ldq, a.strideQ = strideQ;
-  a.k = k, a.ldk = ldk, a.headK = headK, a.v = v, a.ldv = ldv, a.headV = headV;
-  if (paged && Smax > 0) {  // (Smax == 0: no list has an entry, the contiguous form stores the zero rows)
-    a.table = table, a.table_ld = table_ld, a.pages = pages, a.page_shift = __builtin_ctz((unsigned)page);
-    a.pageK = outerK, a.pageV = outerV;
-  } else {
-    a.batchK = outerK, a.batchV = outerV;
-  }
-  a.k_lens = k_lens, a.lens_div = items / lens_count, a.scale = scale;
-  a.out = out, a.ldo = ldo, a.strideO = strideO, a.lse = lse, a.ws = static_cast<float*>(workspace);
-  if (FP8) a.k_scale = scales.k, a.k_scale_count = scales.k_count, a.v_scale = scales.v, a.v_scale_count = scales.v_count;
+  a.ws = static_cast<float*>(workspace);
   if (listed) a.counts = lists.counts, a.list_k = lists.K;
-  switch (D) {
-    case 32: return launch<T, 32, FP8>(a, items, s);
-    case 64: return launch<T, 64, FP8>(a, items, s);
-    case 96: return launch<T, 96, FP8>(a, items, s);
-    default: return launch<T, 128, FP8>(a, items, s);
-  }
+  return with_width(r.D, [&](auto d) { return launch<T, decltype(d)::value, FP8>(a, r.items, s); });
 }
 
 }  // namespace
@@ -603,98 +572,71 @@ size_t mi_block_attention_decode_workspace_bytes(int32_t items, int32_t T, int32
   return (size_t)items * (size_t)T * (size_t)chunks * (size_t)group * (size_t)(D + 2) * sizeof(float);
 }
 
-#define MI_DECODE_ARGS                                                                                                          \
-  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T,             \
-      int32_t Smax, int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t headK,  \
-      int64_t batchK, const uint16_t *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, \
-      int32_t group, int32_t chunk, float scale, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace,      \
-      size_t workspace_bytes, mi_stream_t stream
-#define MI_DECODE_PASS                                                                                                         \
-  rowptr, col, nnz, layouts, items, heads, T, Smax, D, q, ldq, strideQ, k, ldk, headK, batchK, v, ldv, headV, batchV, k_lens, \
-      lens_count, group, chunk, scale, out, ldo, strideO, lse, workspace, workspace_bytes, static_cast<hipStream_t>(stream)
+// the header's parameter lists in pieces: [table] and [scales] are what the paged and the fp8 entries add
+#define MI_DECODE_LIST const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts
+#define MI_DECODE_LISTS_LIST const int32_t *block_ids, const int32_t *block_counts, int32_t K
+#define MI_DECODE_SIZES int32_t items, int32_t heads, int32_t T, int32_t Smax
+#define MI_DECODE_TABLE const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page
+#define MI_DECODE_OPERANDS(CT)                                                                                                  \
+  int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const CT *k, int64_t ldk, int64_t headK, int64_t batchK,          \
+      const CT *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group,        \
+      int32_t chunk, float scale
+#define MI_DECODE_SCALES const float *k_scale, int32_t k_scale_count, const float *v_scale, int32_t v_scale_count
+#define MI_DECODE_OUT \
+  uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes, mi_stream_t stream
+// … and what the entries pass on: the reading call, then their own.  A page of 0 keys would name the contiguous form: it is
+// refused here like every page that is no power of two ≥ 16.
+#define MI_DECODE_CALL(...) MI_READ_CALL(rowptr, col, nnz, layouts, __VA_ARGS__)
+#define MI_DECODE_OWN q, ldq, strideQ, chunk, workspace, workspace_bytes, static_cast<hipStream_t>(stream)
 
-int mi_block_attention_decode_bf16(MI_DECODE_ARGS) { return decode_entry<Bf16>(MI_DECODE_PASS); }
-int mi_block_attention_decode_f16(MI_DECODE_ARGS) { return decode_entry<F16>(MI_DECODE_PASS); }
-
-#define MI_DECODE_PAGED_ARGS                                                                                                  \
-  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T,           \
-      int32_t Smax, const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page, int32_t D, const uint16_t *q,  \
-      int64_t ldq, int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t headK, int64_t batchK, const uint16_t *v,         \
-      int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group, int32_t chunk,    \
-      float scale, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes,          \
-      mi_stream_t stream
-// (k, batchK and v, batchV stand for k_pages, pageK and v_pages, pageV of the header)  A page of 0 keys would name the
-// contiguous form: it is refused here like every page that is no power of two ≥ 16.
-#define MI_DECODE_PAGED_PASS MI_DECODE_PASS, block_table, table_ld, pages, page
-
-int mi_block_attention_decode_paged_bf16(MI_DECODE_PAGED_ARGS) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16>(MI_DECODE_PAGED_PASS);
+int mi_block_attention_decode_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
+  return decode_entry<Bf16>(MI_DECODE_CALL(), MI_DECODE_OWN);
 }
-int mi_block_attention_decode_paged_f16(MI_DECODE_PAGED_ARGS) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16>(MI_DECODE_PAGED_PASS);
+int mi_block_attention_decode_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
+  return decode_entry<F16>(MI_DECODE_CALL(), MI_DECODE_OWN);
+}
+int mi_block_attention_decode_paged_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16>(MI_DECODE_CALL(MI_READ_PAGED), MI_DECODE_OWN);
+}
+int mi_block_attention_decode_paged_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16>(MI_DECODE_CALL(MI_READ_PAGED), MI_DECODE_OWN);
 }
 
 // the fp8 caches: the parents' lists with byte caches and the two scales
-#define MI_DECODE_FP8_ARGS                                                                                                      \
-  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T,             \
-      int32_t Smax, int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const uint8_t *k, int64_t ldk, int64_t headK,   \
-      int64_t batchK, const uint8_t *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count,  \
-      int32_t group, int32_t chunk, float scale, const float *k_scale, int32_t k_scale_count, const float *v_scale,             \
-      int32_t v_scale_count, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes,  \
-      mi_stream_t stream
-#define MI_DECODE_PAGED_FP8_ARGS                                                                                               \
-  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T,            \
-      int32_t Smax, const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page, int32_t D, const uint16_t *q,   \
-      int64_t ldq, int64_t strideQ, const uint8_t *k, int64_t ldk, int64_t headK, int64_t batchK, const uint8_t *v,            \
-      int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group, int32_t chunk,     \
-      float scale, const float *k_scale, int32_t k_scale_count, const float *v_scale, int32_t v_scale_count, uint16_t *out,    \
-      int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes, mi_stream_t stream
-#define MI_DECODE_SCALES Scales{k_scale, k_scale_count, v_scale, v_scale_count}
-
-int mi_block_attention_decode_fp8_bf16(MI_DECODE_FP8_ARGS) {
-  return decode_entry<Bf16, true>(MI_DECODE_PASS, nullptr, 0, 0, 0, MI_DECODE_SCALES);
+int mi_block_attention_decode_fp8_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES, MI_DECODE_OUT) {
+  return decode_entry<Bf16, true>(MI_DECODE_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_OWN);
 }
-int mi_block_attention_decode_fp8_f16(MI_DECODE_FP8_ARGS) {
-  return decode_entry<F16, true>(MI_DECODE_PASS, nullptr, 0, 0, 0, MI_DECODE_SCALES);
+int mi_block_attention_decode_fp8_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES, MI_DECODE_OUT) {
+  return decode_entry<F16, true>(MI_DECODE_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_OWN);
 }
-int mi_block_attention_decode_paged_fp8_bf16(MI_DECODE_PAGED_FP8_ARGS) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16, true>(MI_DECODE_PAGED_PASS, MI_DECODE_SCALES);
+int mi_block_attention_decode_paged_fp8_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
+                                             MI_DECODE_SCALES, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16, true>(MI_DECODE_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_OWN);
 }
-int mi_block_attention_decode_paged_fp8_f16(MI_DECODE_PAGED_FP8_ARGS) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16, true>(MI_DECODE_PAGED_PASS, MI_DECODE_SCALES);
+int mi_block_attention_decode_paged_fp8_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
+                                            MI_DECODE_SCALES, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16, true>(MI_DECODE_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_OWN);
 }
 
-// the list source: the caller's block_ids / block_counts in the place of the layout
-#define MI_DECODE_LISTS_ARGS                                                                                                    \
-  const int32_t *block_ids, const int32_t *block_counts, int32_t K, int32_t items, int32_t heads, int32_t T, int32_t Smax,      \
-      int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t headK,                \
-      int64_t batchK, const uint16_t *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, \
-      int32_t group, int32_t chunk, float scale, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace,      \
-      size_t workspace_bytes, mi_stream_t stream
-#define MI_DECODE_LISTS_PAGED_ARGS                                                                                            \
-  const int32_t *block_ids, const int32_t *block_counts, int32_t K, int32_t items, int32_t heads, int32_t T, int32_t Smax,    \
-      const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page, int32_t D, const uint16_t *q, int64_t ldq,    \
-      int64_t strideQ, const uint16_t *k, int64_t ldk, int64_t headK, int64_t batchK, const uint16_t *v, int64_t ldv,         \
-      int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group, int32_t chunk, float scale,    \
-      uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes, mi_stream_t stream
-// (a K that is no positive int32 is refused inside, before the product is looked at)
-#define MI_DECODE_LISTS_PASS                                                                                                  \
-  nullptr, block_ids, K < 1 ? 0 : (int64_t)items * T * K, 1, items, heads, T, Smax, D, q, ldq, strideQ, k, ldk, headK, batchK, v, \
-      ldv, headV, batchV, k_lens, lens_count, group, chunk, scale, out, ldo, strideO, lse, workspace, workspace_bytes,         \
-      static_cast<hipStream_t>(stream)
-#define MI_DECODE_LISTS Scales(), Lists{block_counts, K < 1 ? -1 : K}
+// the list source: the caller's block_ids / block_counts in the place of the layout — no rowptr, block_ids as
+// col, its items · T · K entries as nnz, one layout.  (A K that is no positive int32 is refused inside, before the product is
+// looked at.)
+#define MI_DECODE_LISTS_CALL(...) MI_READ_CALL(nullptr, block_ids, K < 1 ? 0 : (int64_t)items * T * K, 1, __VA_ARGS__)
+#define MI_DECODE_LISTS_OWN MI_DECODE_OWN, Lists{block_counts, K < 1 ? -1 : K}
 
-int mi_block_attention_decode_lists_bf16(MI_DECODE_LISTS_ARGS) {
-  return decode_entry<Bf16>(MI_DECODE_LISTS_PASS, nullptr, 0, 0, 0, MI_DECODE_LISTS);
+int mi_block_attention_decode_lists_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
+  return decode_entry<Bf16>(MI_DECODE_LISTS_CALL(), MI_DECODE_LISTS_OWN);
 }
-int mi_block_attention_decode_lists_f16(MI_DECODE_LISTS_ARGS) {
-  return decode_entry<F16>(MI_DECODE_LISTS_PASS, nullptr, 0, 0, 0, MI_DECODE_LISTS);
+int mi_block_attention_decode_lists_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
+  return decode_entry<F16>(MI_DECODE_LISTS_CALL(), MI_DECODE_LISTS_OWN);
 }
-int mi_block_attention_decode_lists_paged_bf16(MI_DECODE_LISTS_PAGED_ARGS) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16>(MI_DECODE_LISTS_PASS, block_table, table_ld, pages, page, MI_DECODE_LISTS);
+int mi_block_attention_decode_lists_paged_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
+                                               MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16>(MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_OWN);
 }
-int mi_block_attention_decode_lists_paged_f16(MI_DECODE_LISTS_PAGED_ARGS) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16>(MI_DECODE_LISTS_PASS, block_table, table_ld, pages, page, MI_DECODE_LISTS);
+int mi_block_attention_decode_lists_paged_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
+                                              MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16>(MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_OWN);
 }
 
 }  // extern "C"

@@ -36,7 +36,9 @@
 // (block_attention_cache_device.h: contiguous / pages ≥ 64 / pages of 16, 32 keys — there a lane's four rows lie in one
 // page, 4 divides 16); the table is read one list entry ahead.  Tile, store_own and next_block are copies of
 // block_attention.hip's private pieces with the cache form added; kB, the images' strides, score, pack_tile, accumulate,
-// group_max / group_sum are block_attention_device.h's; mfma<T>, half_of, store_rc mfma_device.h's.
+// group_max / group_sum are block_attention_device.h's; mfma<T>, half_of, store_rc mfma_device.h's.  Host side: what a reading
+// entry checks and fills alike here and in block_attention_decode.hip is block_attention_cache_device.h's (§3.31); prefill_entry
+// keeps split, new_lens, q's strides, the workspace of the parts and the tiles' counts.
 //
 // Split walks (mi_block_attention_prefill_split_* — DESIGN.md §3.28), for a short chunk behind a long cache: the list of a
 // tile's layout row is cut by list position into parts of `split` entries.  There is ONE walk, prefill_walk<…, SPLIT>:
@@ -546,8 +548,7 @@ int launch_form(const Args& a, const SplitArgs& sp, hipStream_t s) {
 template <class T, int D, bool FP8>
 int launch(const Args& a, const SplitArgs& sp, hipStream_t s) {
   typedef std::conditional_t<FP8, Fp8<T>, T> TC;  // the cache element type is part of the kernel's first parameter
-  if (!a.table) return launch_form<TC, D, kContiguous>(a, sp, s);
-  return a.page_shift >= 6 ? launch_form<TC, D, kPaged>(a, sp, s) : launch_form<TC, D, kPagedSmall>(a, sp, s);
+  return with_form(a, [&](auto form) { return launch_form<TC, D, decltype(form)::value>(a, sp, s); });
 }
 
 // What the split entries add: the list entries of a part, and the workspace of the partials.
@@ -561,109 +562,79 @@ struct Split {
 // the parts of a full list of Smax / 64 entries cut every `split`
 inline int parts_of(int32_t Smax, int32_t split) { return (int)(((long)Smax / kB + split - 1) / split); }
 
-// Every check comes before the first HIP call.  page == 0: the contiguous cache, `outerK` / `outerV` its batch strides and
-// no table; page > 0: a pool of `pages` pages of `page` keys, `outerK` / `outerV` its page strides, Smax = the table's
-// logical pages · page.  FP8: k and v are e4m3fn bytes (their strides multiples of 16) with the two scales of `scales`.
-// `split`: the split entries' cut and workspace; with one part the call is the unsplit launch.
+// Every check comes before the first HIP call.  `r`: what every reading entry takes (block_attention_cache_device.h), FP8 its
+// cache type; q, new_lens and `split` — the split entries' cut and workspace; with one part the call is the unsplit launch —
+// are this entry's own.
 template <class T, bool FP8 = false>
-int prefill_entry(const int32_t* rowptr, const int32_t* col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T_,
-                  int32_t Smax, int32_t D, const uint16_t* q, int64_t ldq, int64_t headQ, int64_t batchQ, const void* k, int64_t ldk,
-                  int64_t headK, int64_t outerK, const void* v, int64_t ldv, int64_t headV, int64_t outerV, const int32_t* k_lens,
-                  int32_t lens_count, const int32_t* new_lens, int32_t new_lens_count, int32_t group, float scale, uint16_t* out,
-                  int64_t ldo, int64_t strideO, float* lse, hipStream_t s, const int32_t* table = nullptr, int64_t table_ld = 0,
-                  int32_t pages = 0, int32_t page = 0, const Scales& scales = Scales(), const Split& split = Split()) {
-  if (!cache_form_ok(FP8, scales, heads, Smax, pages, page)) return MI_EINVAL;
-  if (group < 1 || !takes_width(D) || (split.on && split.entries < 1)) return MI_EINVAL;
-  const bool paged = page != 0;
-  if (nnz < 0 || layouts < 0 || items < 0 || heads < 0 || T_ < 0 || Smax < 0 || Smax % kB != 0) return MI_EINVAL;
-  if (nnz > 0x7fffffffLL) return MI_ERANGE;
-  if (items == 0 || T_ == 0) return MI_OK;
-  if (layouts == 0 || heads == 0 || items % heads != 0 || lens_count < 1 || items % lens_count != 0) return MI_EINVAL;
-  if (!rowptr || (nnz > 0 && !col) || !k_lens || !aligned4(k_lens)) return MI_EINVAL;
-  if (new_lens && (!aligned4(new_lens) || (new_lens_count != 1 && new_lens_count != items / heads))) return MI_EINVAL;
-  if (!lse || !aligned4(lse)) return MI_EINVAL;
-  if (!q || !mi::aligned16(q) || !stride_ok(ldq) || !stride_ok(headQ) || !stride_ok(batchQ) || (T_ > 1 && ldq < D)) return MI_EINVAL;
-  if (!out || !mi::aligned16(out) || ldo < D || !stride_ok(ldo) || !stride_ok(strideO)) return MI_EINVAL;
-  const bool reads = nnz > 0 && Smax > 0 && (!paged || pages > 0);  // (an empty pool is never read: every entry of the table is invalid)
-  if (!cache_operands_ok(FP8, reads, Smax, D, k, ldk, headK, outerK, v, ldv, headV, outerV, table, table_ld, page)) return MI_EINVAL;
-  const int parts = split.on ? parts_of(Smax, split.entries) : 1;
+int prefill_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t headQ, int64_t batchQ, const int32_t* new_lens,
+                  int32_t new_lens_count, hipStream_t s, const Split& split = Split()) {
+  if (split.on && split.entries < 1) return MI_EINVAL;
+  if (const int st = read_sizes_status(FP8, r)) return st;
+  if (read_is_empty(r)) return MI_OK;
+  if (!read_operands_ok(FP8, r)) return MI_EINVAL;
+  if (new_lens && (!aligned4(new_lens) || (new_lens_count != 1 && new_lens_count != r.items / r.heads))) return MI_EINVAL;
+  if (!q || !mi::aligned16(q) || !stride_ok(ldq) || !stride_ok(headQ) || !stride_ok(batchQ) || (r.T > 1 && ldq < r.D)) return MI_EINVAL;
+  const int parts = split.on ? parts_of(r.Smax, split.entries) : 1;
   if (parts > 1) {  // (one part: the unsplit launch, no workspace)
     if (!split.workspace || !mi::aligned16(split.workspace)) return MI_EINVAL;
-    const int64_t need = mi_block_attention_prefill_split_workspace_bytes(items, group, T_, D, Smax, split.entries);
+    const int64_t need = mi_block_attention_prefill_split_workspace_bytes(r.items, r.group, r.T, r.D, r.Smax, split.entries);
     if (need < 0) return (int)need;
     if (split.workspace_bytes < (uint64_t)need) return MI_ENOMEM;
   }
-  Args a = {};  // (zeroed: the 2-byte entries leave k_scale / v_scale null)
+  Args a = {};
   SplitArgs sp = {};
   if (parts > 1) sp.split = split.entries, sp.parts = parts, sp.ws = static_cast<float*>(split.workspace);
-  a.rowptr = rowptr, a.col = col, a.nnz = nnz, a.layouts = layouts, a.blocks = Smax / kB, a.heads = heads, a.group = group;
-  a.T = T_, a.tiles = (int)(((long)T_ + kB - 1) / kB + 1), a.smax = Smax;
-  a.slots = (long)items * a.tiles;
-  a.units = (a.slots + kSpreadHeads - 1) / kSpreadHeads * kSpreadHeads * group;
+  fill_read_args(a, FP8, r);
+  a.tiles = (int)(((long)r.T + kB - 1) / kB + 1);
+  a.slots = (long)r.items * a.tiles;
+  a.units = (a.slots + kSpreadHeads - 1) / kSpreadHeads * kSpreadHeads * r.group;
   a.q = q, a.ldq = ldq, a.headQ = headQ, a.batchQ = batchQ;
-  a.k = k, a.ldk = ldk, a.headK = headK, a.v = v, a.ldv = ldv, a.headV = headV;
-  if (paged && Smax > 0) {  // (Smax == 0: no list has an entry, the contiguous form stores the zero rows)
-    a.table = table, a.table_ld = table_ld, a.pages = pages, a.page_shift = __builtin_ctz((unsigned)page);
-    a.pageK = outerK, a.pageV = outerV;
-  } else {
-    a.batchK = outerK, a.batchV = outerV;
-  }
-  a.k_lens = k_lens, a.lens_div = items / lens_count, a.new_lens = new_lens, a.new_lens_one = new_lens_count == 1, a.scale = scale;
-  a.out = out, a.ldo = ldo, a.strideO = strideO, a.lse = lse;
-  if (FP8) a.k_scale = scales.k, a.k_scale_count = scales.k_count, a.v_scale = scales.v, a.v_scale_count = scales.v_count;
-  switch (D) {
-    case 32: return launch<T, 32, FP8>(a, sp, s);
-    case 64: return launch<T, 64, FP8>(a, sp, s);
-    case 96: return launch<T, 96, FP8>(a, sp, s);
-    default: return launch<T, 128, FP8>(a, sp, s);
-  }
+  a.new_lens = new_lens, a.new_lens_one = new_lens_count == 1;
+  return with_width(r.D, [&](auto d) { return launch<T, decltype(d)::value, FP8>(a, sp, s); });
 }
 
 }  // namespace
 
 extern "C" {
 
-#define MI_PREFILL_PASS                                                                                                       \
-  rowptr, col, nnz, layouts, items, heads, T, Smax, D, q, ldq, headQ, batchQ, k, ldk, headK, batchK, v, ldv, headV, batchV,  \
-      k_lens, lens_count, new_lens, new_lens_count, group, scale, out, ldo, strideO, lse, static_cast<hipStream_t>(stream)
-// (k, batchK and v, batchV stand for k_pages, pageK and v_pages, pageV of the header)  A page of 0 keys would name the
-// contiguous form: it is refused here like every page that is no power of two ≥ 16.
-#define MI_PREFILL_PAGED_PASS MI_PREFILL_PASS, block_table, table_ld, pages, page
-#define MI_PREFILL_SCALES Scales{k_scale, k_scale_count, v_scale, v_scale_count}
+// what the entries pass on: the reading call, then their own.  A page of 0 keys would name the contiguous form: it is refused
+// here like every page that is no power of two ≥ 16.
+#define MI_PREFILL_CALL(...) MI_READ_CALL(rowptr, col, nnz, layouts, __VA_ARGS__)
+#define MI_PREFILL_OWN q, ldq, headQ, batchQ, new_lens, new_lens_count, static_cast<hipStream_t>(stream)
 
 int mi_block_attention_prefill_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
                                     MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<Bf16>(MI_PREFILL_PASS);
+  return prefill_entry<Bf16>(MI_PREFILL_CALL(), MI_PREFILL_OWN);
 }
 int mi_block_attention_prefill_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
                                    MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<F16>(MI_PREFILL_PASS);
+  return prefill_entry<F16>(MI_PREFILL_CALL(), MI_PREFILL_OWN);
 }
 int mi_block_attention_prefill_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
                                           MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<Bf16>(MI_PREFILL_PAGED_PASS);
+  return page < 16 ? MI_EINVAL : prefill_entry<Bf16>(MI_PREFILL_CALL(MI_READ_PAGED), MI_PREFILL_OWN);
 }
 int mi_block_attention_prefill_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
                                          MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<F16>(MI_PREFILL_PAGED_PASS);
+  return page < 16 ? MI_EINVAL : prefill_entry<F16>(MI_PREFILL_CALL(MI_READ_PAGED), MI_PREFILL_OWN);
 }
 int mi_block_attention_prefill_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
                                         MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<Bf16, true>(MI_PREFILL_PASS, nullptr, 0, 0, 0, MI_PREFILL_SCALES);
+  return prefill_entry<Bf16, true>(MI_PREFILL_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_OWN);
 }
 int mi_block_attention_prefill_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
                                        MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<F16, true>(MI_PREFILL_PASS, nullptr, 0, 0, 0, MI_PREFILL_SCALES);
+  return prefill_entry<F16, true>(MI_PREFILL_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_OWN);
 }
 int mi_block_attention_prefill_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
                                               MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
                                               MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<Bf16, true>(MI_PREFILL_PAGED_PASS, MI_PREFILL_SCALES);
+  return page < 16 ? MI_EINVAL : prefill_entry<Bf16, true>(MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_OWN);
 }
 int mi_block_attention_prefill_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
                                              MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
                                              MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_PAGED_PASS, MI_PREFILL_SCALES);
+  return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_OWN);
 }
 
 int64_t mi_block_attention_prefill_split_workspace_bytes(int32_t items, int32_t group, int32_t T, int32_t D, int32_t Smax,
@@ -683,37 +654,37 @@ int64_t mi_block_attention_prefill_split_workspace_bytes(int32_t items, int32_t 
 
 int mi_block_attention_prefill_split_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
                                           MI_PREFILL_SPLIT_OUT) {
-  return prefill_entry<Bf16>(MI_PREFILL_PASS, nullptr, 0, 0, 0, Scales(), MI_PREFILL_SPLIT);
+  return prefill_entry<Bf16>(MI_PREFILL_CALL(), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
 }
 int mi_block_attention_prefill_split_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
                                          MI_PREFILL_SPLIT_OUT) {
-  return prefill_entry<F16>(MI_PREFILL_PASS, nullptr, 0, 0, 0, Scales(), MI_PREFILL_SPLIT);
+  return prefill_entry<F16>(MI_PREFILL_CALL(), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
 }
 int mi_block_attention_prefill_split_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
                                                 MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_PREFILL_SPLIT_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<Bf16>(MI_PREFILL_PAGED_PASS, Scales(), MI_PREFILL_SPLIT);
+  return page < 16 ? MI_EINVAL : prefill_entry<Bf16>(MI_PREFILL_CALL(MI_READ_PAGED), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
 }
 int mi_block_attention_prefill_split_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
                                                MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_PREFILL_SPLIT_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<F16>(MI_PREFILL_PAGED_PASS, Scales(), MI_PREFILL_SPLIT);
+  return page < 16 ? MI_EINVAL : prefill_entry<F16>(MI_PREFILL_CALL(MI_READ_PAGED), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
 }
 int mi_block_attention_prefill_split_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
                                               MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_PREFILL_SPLIT_OUT) {
-  return prefill_entry<Bf16, true>(MI_PREFILL_PASS, nullptr, 0, 0, 0, MI_PREFILL_SCALES, MI_PREFILL_SPLIT);
+  return prefill_entry<Bf16, true>(MI_PREFILL_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
 }
 int mi_block_attention_prefill_split_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
                                              MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_PREFILL_SPLIT_OUT) {
-  return prefill_entry<F16, true>(MI_PREFILL_PASS, nullptr, 0, 0, 0, MI_PREFILL_SCALES, MI_PREFILL_SPLIT);
+  return prefill_entry<F16, true>(MI_PREFILL_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
 }
 int mi_block_attention_prefill_split_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
                                                     MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
                                                     MI_PREFILL_SPLIT_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<Bf16, true>(MI_PREFILL_PAGED_PASS, MI_PREFILL_SCALES, MI_PREFILL_SPLIT);
+  return page < 16 ? MI_EINVAL : prefill_entry<Bf16, true>(MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
 }
 int mi_block_attention_prefill_split_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
                                                    MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
                                                    MI_PREFILL_SPLIT_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_PAGED_PASS, MI_PREFILL_SCALES, MI_PREFILL_SPLIT);
+  return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
-// custom_mm — what the bindings of the KV-cache family (block_attention_decode*, kv_append*, rope_kv_append*) say about the
-// cache operands, said once (DESIGN.md §3.23)
-// Part of the `custom_mm` extension: included by custom_mm.cpp inside its anonymous namespace, ahead of the three bindings.
+// custom_mm — what the bindings of the KV-cache family (block_attention_decode*, block_attention_prefill*, kv_append*,
+// rope_kv_append*) say about the cache operands, said once (DESIGN.md §3.23), and what the reading ones say alike about the
+// whole call (§3.31)
+// Part of the `custom_mm` extension: included by custom_mm.cpp inside its anonymous namespace, ahead of those bindings.
 // Not compiled on its own.  The cache is k, v [B, Hkv, Smax, D] or a pool k_pages, v_pages [P, Hkv, page, D] with block_table
 // int32 [B, W] (Smax = W · page), READ AND WRITTEN THROUGH ITS OWN STRIDES (last stride 1, the others multiples of 16 bytes —
 // 8 two-byte elements, 16 float8_e4m3fn bytes —, a 16-byte aligned data pointer — never copied); k_lens int32 [B] or [1] on
@@ -93,6 +94,98 @@ CacheOperands cache_operands(const torch::Tensor& k, const torch::Tensor& v, con
   }
   return c;
 }
+
+// ---- a reading call: block_attention_decode*, block_attention_prefill*, block_attention_decode_lists* (DESIGN.md §3.31) --------
+// q and out [B, Hq, T, D] bfloat16 or float16, the cache of q's type or (`fp8`) float8_e4m3fn with the two scales, `table` null
+// or the block table of a pool, lse float32 [B, Hq, T].  Four pieces, between which every binding makes the checks of its own:
+// read_shape, read_smax, check_read_operands and read_cache.
+
+// q's and out's type of an fp8 call, the cache's checked on the way
+bool fp8_decode_dtypes(const char* what, const torch::Tensor& q, const torch::Tensor& out, const char* kname, const torch::Tensor& k,
+                       const char* vname, const torch::Tensor& v) {
+  TORCH_CHECK(k.scalar_type() == torch::kFloat8_e4m3fn && v.scalar_type() == torch::kFloat8_e4m3fn, what, ": ", kname, " and ", vname,
+              " must be float8_e4m3fn (the OCP e4m3fn encoding is what is read), got ", k.scalar_type(), " and ", v.scalar_type());
+  return is_lowp_dtype(what, value_dtype(what, {{"q", &q}, {"out", &out}}, true));
+}
+
+struct ReadShape {
+  bool bf;  // bfloat16, else float16
+  int64_t B, Hq, T, D, Hkv, group;
+};
+
+// the dtype rule, the 4-d shapes, the pool or the cache against q's shape, the page and the heads / group rule
+ReadShape read_shape(const char* what, const char* kname, const char* vname, bool fp8, const torch::Tensor& q, const torch::Tensor& k,
+                     const torch::Tensor& v, const torch::Tensor* table, const torch::Tensor& out) {
+  const bool bf = fp8 ? fp8_decode_dtypes(what, q, out, kname, k, vname, v)
+                      : is_lowp_dtype(what, value_dtype(what, {{"q", &q}, {kname, &k}, {vname, &v}, {"out", &out}}, true));
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, what, ": q must be [B, Hq, T, D], ", kname, " and ", vname,
+              table ? " [P, Hkv, page, D]" : " [B, Hkv, Smax, D]");
+  const int64_t B = q.size(0), Hq = q.size(1), T = q.size(2), D = q.size(3), Hkv = k.size(1);
+  if (table) {
+    TORCH_CHECK(k.size(3) == D && v.sizes() == k.sizes(), what, ": ", kname, " and ", vname,
+                " must be [P, Hkv, page, D] = [P, Hkv, page, ", D, "]");
+    check_page(what, "keys", k.size(2));
+  } else {
+    TORCH_CHECK(k.size(0) == B && k.size(3) == D && v.sizes() == k.sizes(), what, ": k and v must be [B, Hkv, Smax, D] = [", B,
+                ", Hkv, Smax, ", D, "]");
+  }
+  TORCH_CHECK(Hkv > 0 ? Hq % Hkv == 0 : Hq == 0, what, ": ", Hq, " query heads are not a multiple of ", Hkv, " k / v heads");
+  return {bf, B, Hq, T, D, Hkv, Hkv > 0 ? std::max<int64_t>(Hq / Hkv, 1) : 1};
+}
+
+// the rows of an item: the table's logical pages · page, or the cache's own
+int64_t read_smax(const char* what, const torch::Tensor& k, const torch::Tensor* table, int64_t B) {
+  return table ? table_width(what, *table, B) * k.size(2) : k.size(2);
+}
+
+// the devices (`dev`: the device of the call's lists, which the binding has checked q, k and v against), lse, k_lens and the
+// table as they are handed over, out's and lse's shapes; `q_contiguous`: q is taken contiguous (the decode calls) — else it is
+// read through its own strides, which the binding checks
+void check_read_operands(const char* what, const torch::Device& dev, bool q_contiguous, const torch::Tensor& q,
+                         const torch::Tensor* table, const torch::Tensor& k_lens, const torch::Tensor& out, const torch::Tensor& lse,
+                         const ReadShape& s) {
+  if (table) check_same_device(what, dev, {table});
+  check_same_device(what, dev, {&out, &lse, &k_lens});
+  check_device_f32(lse, "lse");
+  check_device_i32(k_lens, "k_lens");
+  if (table) check_table(what, *table);
+  TORCH_CHECK(!q_contiguous || (q.is_contiguous() && out.is_contiguous() && out.sizes() == q.sizes()), what,
+              ": q and out must be contiguous [B, Hq, T, D] tensors of one shape");
+  TORCH_CHECK(out.is_contiguous() && out.sizes() == q.sizes(), what, ": out must be a contiguous [B, Hq, T, D] tensor of q's shape");
+  TORCH_CHECK(lse.is_contiguous() && lse.numel() == s.B * s.Hq * s.T, what, ": lse must be a contiguous [B, Hq, T] tensor");
+  check_k_lens(what, k_lens, s.B);
+}
+
+// the cache's strides, the scales of an fp8 cache, the operands gathered, and the sizes the C ABI takes as int32
+struct ReadCache {
+  CacheOperands c;
+  std::pair<const float*, int32_t> ks, vs;
+};
+
+ReadCache read_cache(const char* what, const char* kname, const char* vname, bool fp8, const torch::Tensor& q, const torch::Tensor& k,
+                     const torch::Tensor& v, const torch::Tensor* table, const c10::optional<torch::Tensor>& k_scale,
+                     const c10::optional<torch::Tensor>& v_scale, const ReadShape& s) {
+  const char* outer = table ? "page" : "batch";
+  check_cache_strides(what, kname, k, s.D, outer, fp8 ? 16 : 8);
+  check_cache_strides(what, vname, v, s.D, outer, fp8 ? 16 : 8);
+  ReadCache r = {{}, {nullptr, 1}, {nullptr, 1}};
+  if (fp8) r.ks = fp8_scale(what, "k_scale", k_scale, s.Hkv, q), r.vs = fp8_scale(what, "v_scale", v_scale, s.Hkv, q);
+  r.c = cache_operands(k, v, table, s.D);
+  check_sizes(what, {s.B * s.Hkv, s.B * s.Hq, s.T, r.c.Smax, s.D, r.c.P});  // (P: 0 without a pool)
+  return r;
+}
+
+uint16_t* bits16(const torch::Tensor& t) { return static_cast<uint16_t*>(t.data_ptr()); }
+
+// The argument lists of the 28 C entries in the pieces they share (`s`: the ReadShape, `r`: the ReadCache, CT: the cache's
+// element at the C ABI): the sizes, what the paged entries add, the cache with the lengths, what the fp8 entries add, out and lse.
+#define MI_READ_SIZES (int32_t)(s.B * s.Hkv), (int32_t)s.Hkv, (int32_t)s.T, (int32_t)r.c.Smax
+#define MI_READ_TABLE r.c.table, r.c.table_ld, (int32_t)r.c.P, (int32_t)r.c.page
+#define MI_READ_CACHE(CT)                                                                                                   \
+  static_cast<const CT*>(r.c.k), r.c.ldk, r.c.headK, r.c.outerK, static_cast<const CT*>(r.c.v), r.c.ldv, r.c.headV, r.c.outerV, \
+      k_lens.data_ptr<int32_t>(), (int32_t)k_lens.numel()
+#define MI_READ_SCALES r.ks.first, r.ks.second, r.vs.first, r.vs.second
+#define MI_READ_OUT bits16(out), s.D, s.T* s.D, lse.data_ptr<float>()
 
 // the writing calls' cache: of the source's dtype `dt` (a bit copy) or float8_e4m3fn; returns whether it is fp8
 bool written_cache_is_fp8(const char* what, const char* kname, const char* vname, torch::ScalarType dt, const torch::Tensor& k,

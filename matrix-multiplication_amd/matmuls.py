@@ -1865,11 +1865,9 @@ def _check_decode_group(what, Hq, Hkv, max_group=_DECODE_MAX_GROUP):
     return group
 
 
-def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, entries, k_lens, block, max_grid=_DECODE_MAX_GRID, sizes_text=None):
-    '''The refusals of the decode calls that follow from (B, Hkv, T, Smax) alone, however the cache is stored.  `entries`: the
-    number of the layout's stored values.  max_grid None: B·Hkv and T are no grid dimensions (the prefill calls).'''
-    if T < 1:
-        raise ValueError(f'{what}: q must hold T >= 1 new tokens, got T = {T}')
+def _check_decode_layout(what, B, Hkv, Smax, layout, entries, block, sizes_text=None):
+    '''The layout half of the decode calls' refusals, from (B, Hkv, Smax) alone, however the cache is stored.  `entries`: the
+    number of the layout's stored values.'''
     if Smax % block != 0:
         raise ValueError(f'{what}: Smax = {Smax} must be a multiple of block = {block} (accepted: {sizes_text or _DECODE_SIZES_TEXT})')
     l_lead = tuple(layout.shape[:-2])
@@ -1879,9 +1877,6 @@ def _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, entries, k_lens
                          f'{tuple(layout.shape)}')
     if entries * (block // _BLOCK_TILE) ** 2 >= 2 ** 31:
         raise ValueError(f'{what}: the layout in 64-blocks does not fit int32 indices')
-    if max_grid is not None and (B * Hkv > _DECODE_MAX_GRID or T > _DECODE_MAX_GRID):
-        raise ValueError(f'{what}: B·Hkv = {B * Hkv} and T = {T} must each be at most {_DECODE_MAX_GRID} (they are grid dimensions)')
-    _check_k_lens(what, k_lens, B)
 
 
 def _check_k_lens(what, k_lens, B):
@@ -1944,28 +1939,23 @@ def _check_new_lens(what, new_lens, B):
                          f'{tuple(new_lens.shape)}')
 
 
-def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8=False, scales=(),
-                                           block_table=None, *, sizes_text=None, max_group=_DECODE_MAX_GROUP,
-                                           max_grid=_DECODE_MAX_GRID, q_strided=False, new_lens=None, split=None):
-    '''Every refusal of the four decode calls, before the first device call, split as _check_block_attention_operands splits
-    them: ValueError for what an operand is, RuntimeError for operands that do not go together (mixed dtypes, host tensors /
-    devices).  `names`: the cache operands' names — ('k_pages', 'v_pages') is the paged form, whose k and v are the pool
-    [P, Hkv, page, D] and whose Smax is W · page of block_table [B, W].  fp8, scales: the fp8 calls' cache type and their
-    (name, scale) pairs (_check_fp8_scales).  The keyword parameters are what the prefill calls say differently
-    (_prefill): the accepted sizes in the messages, no bound on the group (max_group None), none on B·Hkv and T (max_grid
-    None), q read through its own strides (q_strided: _check_source_strides), new_lens (_check_new_lens) and split.'''
+def _check_cache_shape(what, names, q, k, v, block_table, base_text=_DECODE_SIZES_TEXT, max_group=_DECODE_MAX_GROUP,
+                       pool_owner="k_pages'"):
+    '''The cache-shape half of every reading call's refusals (the decode, the prefill and the list-source calls; the other
+    half is the call's own: a layout, or lists): q, k and v 4-d, D, the cache or the pool against q's shape, the group, v's
+    shape, the page and the block table, T ≥ 1.  `names`: the cache operands' names — ('k_pages', 'v_pages') is the paged form,
+    whose k and v are the pool [P, Hkv, page, D] and whose Smax is W · page of block_table [B, W].  base_text: the accepted
+    sizes the messages name; max_group: _check_decode_group's; pool_owner: how the v-shape message of a paged call names
+    k_pages' shape (the calls word it differently).  Returns Smax.'''
     kn, vn = names
     paged = kn == 'k_pages'
-    base_text = sizes_text or _DECODE_SIZES_TEXT
     paged_text = base_text + _PAGED_SIZES_SUFFIX
-    sizes_text = paged_text if paged else base_text
-    _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8, base_text, split)
     if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
         raise ValueError(f'{what}: q must be [B, Hq, T, D] and {kn}, {vn} {"[P, Hkv, page, D]" if paged else "[B, Hkv, Smax, D]"}, '
                          f'got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
     B, Hq, T, D = q.shape
     if D not in _BLOCK_HEAD_SIZES:
-        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {sizes_text})')
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {paged_text if paged else base_text})')
     Hkv, Smax = k.shape[1], k.shape[2]
     if (not paged and k.shape[0] != B) or k.shape[3] != D or Hkv < 1 or Hq % Hkv != 0:
         raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs {kn} '
@@ -1973,18 +1963,44 @@ def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens,
                          f'got {tuple(k.shape)}')
     _check_decode_group(what, Hq, Hkv, max_group)
     if tuple(v.shape) != tuple(k.shape):
-        owner = "k_pages'" if paged else "k's"
+        owner = pool_owner if paged else "k's"
         raise ValueError(f'{what}: {vn} must be a dense tensor with {owner} shape {tuple(k.shape)}, got {tuple(v.shape)}')
-    values = torch.Tensor.values(layout)  # (taken once: a new tensor every time)
-    operands = {'layout': values, 'q': q, kn: k, vn: v}  # in the order the device check names them
     if paged:
         page = k.shape[2]
         if not _page_ok(page):
             raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} keys, got page = {page} '
                              f'(accepted: {paged_text})')
         Smax = _check_block_table(what, block_table, B) * page
+    if T < 1:
+        raise ValueError(f'{what}: q must hold T >= 1 new tokens, got T = {T}')
+    return Smax
+
+
+def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8=False, scales=(),
+                                           block_table=None, *, sizes_text=None, max_group=_DECODE_MAX_GROUP,
+                                           max_grid=_DECODE_MAX_GRID, q_strided=False, new_lens=None, split=None):
+    '''Every refusal of the four decode calls, before the first device call, split as _check_block_attention_operands splits
+    them: ValueError for what an operand is, RuntimeError for operands that do not go together (mixed dtypes, host tensors /
+    devices).  The cache-shape half is _check_cache_shape's (`names` as there), the layout half _check_decode_layout's.  fp8,
+    scales: the fp8 calls' cache type and their (name, scale) pairs (_check_fp8_scales).  The keyword parameters are what the
+    prefill calls say differently (_prefill): the accepted sizes in the messages, no bound on the group (max_group None), none
+    on B·Hkv and T (max_grid None), q read through its own strides (q_strided: _check_source_strides), new_lens
+    (_check_new_lens) and split.'''
+    kn, vn = names
+    paged = kn == 'k_pages'
+    base_text = sizes_text or _DECODE_SIZES_TEXT
+    _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8, base_text, split)
+    Smax = _check_cache_shape(what, names, q, k, v, block_table, base_text, max_group)
+    B, Hq, T, D = q.shape
+    Hkv = k.shape[1]
+    values = torch.Tensor.values(layout)  # (taken once: a new tensor every time)
+    operands = {'layout': values, 'q': q, kn: k, vn: v}  # in the order the device check names them
+    if paged:
         operands['block_table'] = block_table
-    _check_decode_layout_and_lens(what, B, Hkv, T, Smax, layout, values.numel(), k_lens, block, max_grid, base_text)
+    _check_decode_layout(what, B, Hkv, Smax, layout, values.numel(), block, base_text)
+    if max_grid is not None and (B * Hkv > _DECODE_MAX_GRID or T > _DECODE_MAX_GRID):
+        raise ValueError(f'{what}: B·Hkv = {B * Hkv} and T = {T} must each be at most {_DECODE_MAX_GRID} (they are grid dimensions)')
+    _check_k_lens(what, k_lens, B)
     if max_grid is None and max(B * Hq, T, Smax) >= 2 ** 31:
         raise ValueError(f'{what}: B·Hq = {B * Hq}, T = {T} and Smax = {Smax} must each fit an int32')
     _check_new_lens(what, new_lens, B)
@@ -2988,30 +3004,9 @@ def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts,
             raise ValueError(f'{what}: {name} must be a dense int32 tensor (select_key_blocks\' output is handed over as it is)')
     if chunk is not None and (not _is_int(chunk) or chunk < 1 or chunk >= 2 ** 31):
         raise ValueError(f'{what}: chunk must be None or a positive int, got {chunk!r}')
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise ValueError(f'{what}: q must be [B, Hq, T, D] and {kn}, {vn} {"[P, Hkv, page, D]" if paged else "[B, Hkv, Smax, D]"}, '
-                         f'got {q.dim()}-d, {k.dim()}-d and {v.dim()}-d')
+    Smax = _check_cache_shape(what, names, q, k, v, block_table, pool_owner="k_pages's")
     B, Hq, T, D = q.shape
-    if D not in _BLOCK_HEAD_SIZES:
-        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {sizes_text})')
-    Hkv, Smax = k.shape[1], k.shape[2]
-    if (not paged and k.shape[0] != B) or k.shape[3] != D or Hkv < 1 or Hq % Hkv != 0:
-        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs {kn} '
-                         f'{("P", "Hkv", "page", D) if paged else (B, "Hkv", "Smax", D)} with Hkv a divisor of {Hq}, '
-                         f'got {tuple(k.shape)}')
-    _check_decode_group(what, Hq, Hkv)
-    if tuple(v.shape) != tuple(k.shape):
-        raise ValueError(f'{what}: {vn} must be a dense tensor with {kn}\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
-    operands = {'q': q, kn: k, vn: v}
-    if paged:
-        page = k.shape[2]
-        if not _page_ok(page):
-            raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} keys, got page = {page} '
-                             f'(accepted: {sizes_text})')
-        Smax = _check_block_table(what, block_table, B) * page
-        operands['block_table'] = block_table
-    if T < 1:
-        raise ValueError(f'{what}: q must hold T >= 1 new tokens, got T = {T}')
+    Hkv = k.shape[1]
     if Smax % _BLOCK_TILE != 0:
         raise ValueError(f'{what}: Smax = {Smax} must be a multiple of 64 (accepted: {sizes_text})')
     if block_ids.dim() != 4 or tuple(block_ids.shape[:3]) != (B, Hkv, T) or block_ids.shape[3] < 1 or not block_ids.is_contiguous():
@@ -3029,6 +3024,9 @@ def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts,
     outer = 'page' if paged else 'batch'
     _check_cache_strides(what, kn, k, D, outer)
     _check_cache_strides(what, vn, v, D, outer)
+    operands = {'q': q, kn: k, vn: v}  # in the order the device check names them
+    if paged:
+        operands['block_table'] = block_table
     operands.update(block_ids=block_ids, block_counts=block_counts, k_lens=k_lens)
     _check_on_device(what, **operands)
     if scale is None:
