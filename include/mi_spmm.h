@@ -1503,6 +1503,53 @@ mi_block_attention_decode_lists_paged_f16(const int32_t* block_ids, const int32_
                                               int64_t table_ld, int32_t pages, int32_t page, MI_DECODE_LISTS_OPERANDS);
 
 /* ------------------------------------------------------------------------ *
+ * … over an FP8 (OCP e4m3fn) cache: the bounds of a cache of e4m3fn bytes and the decode entry that walks the
+ * caller's lists over one.  k (and v) are bytes, their strides count bytes and are multiples of 16; everything not said here is
+ * the entry above of the same name.
+ *
+ * mi_kv_block_bounds{,_paged}_fp8_T: mi_kv_block_bounds{,_paged}_T over a cache of e4m3fn bytes, with bounds of T — THE SUFFIX
+ *   IS THE BOUNDS' TYPE.  Every finite e4m3fn code is a T, and the widening is strictly monotone in the total order the bounds
+ *   are taken in (−0 < +0 included), so the result is, bit for bit, that of mi_kv_block_bounds{,_paged}_T on the cache widened to
+ *   T; −0 is stored as 0x8000.  The bytes are compared as they are and only the 2·D results of a block are widened.  The scales
+ *   of the cache are no operand: positive per-head scales change neither a minimum nor the ranking of the blocks of a head, and
+ *   mi_block_select_T's scores of these bounds are those of the UNSCALED widened keys (the bound of the real q·k is
+ *   score · k_scale[h]).  NaN codes (0x7f, 0xff) among the seen keys: unspecified, nothing faults.  MI_EINVAL as above, with
+ *   strides that are no multiples of 16 bytes.
+ *
+ * mi_block_attention_lists_decode{,_paged}_fp8_T: mi_block_attention_decode_lists{,_paged}_T over an fp8 cache, with the four
+ *   scale parameters of mi_block_attention_decode{,_paged}_fp8_T after `scale`.  For token t, out and lse have the bits of
+ *   mi_block_attention_decode{,_paged}_fp8_T with T = 1, k_len = pos + 1, the same chunk and scales and a layout whose row
+ *   pos / 64 lists the same blocks in the same order; without scales, those of mi_block_attention_decode_lists{,_paged}_T on the
+ *   widened cache.  MI_EINVAL: what the lists entries and the fp8 entries refuse.  (`lists` stands before `decode` in the name:
+ *   the entries `mi_block_attention_decode…` are a closed family.)
+ * ------------------------------------------------------------------------ */
+#define MI_KV_BLOCK_BOUNDS_FP8_OPERANDS                                                                                 \
+  int32_t D, const uint8_t *k, int64_t ldk, int64_t headK, int64_t batchK, const int32_t *k_lens, int32_t lens_count, \
+      int32_t last, uint16_t *bounds, mi_stream_t stream
+int mi_kv_block_bounds_fp8_bf16(int32_t items, int32_t heads, int32_t Smax, MI_KV_BLOCK_BOUNDS_FP8_OPERANDS);
+int mi_kv_block_bounds_fp8_f16(int32_t items, int32_t heads, int32_t Smax, MI_KV_BLOCK_BOUNDS_FP8_OPERANDS);
+int mi_kv_block_bounds_paged_fp8_bf16(int32_t items, int32_t heads, int32_t Smax, const int32_t* block_table, int64_t table_ld,
+                                      int32_t pages, int32_t page, MI_KV_BLOCK_BOUNDS_FP8_OPERANDS);
+int mi_kv_block_bounds_paged_fp8_f16(int32_t items, int32_t heads, int32_t Smax, const int32_t* block_table, int64_t table_ld,
+                                     int32_t pages, int32_t page, MI_KV_BLOCK_BOUNDS_FP8_OPERANDS);
+
+#define MI_LISTS_DECODE_FP8_OPERANDS                                                                                            \
+  int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const uint8_t *k, int64_t ldk, int64_t headK, int64_t batchK,      \
+      const uint8_t *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group,   \
+      int32_t chunk, float scale, const float *k_scale, int32_t k_scale_count, const float *v_scale, int32_t v_scale_count,     \
+      uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes, mi_stream_t stream
+int mi_block_attention_lists_decode_fp8_bf16(const int32_t* block_ids, const int32_t* block_counts, int32_t K, int32_t items,
+                                             int32_t heads, int32_t T, int32_t Smax, MI_LISTS_DECODE_FP8_OPERANDS);
+int mi_block_attention_lists_decode_fp8_f16(const int32_t* block_ids, const int32_t* block_counts, int32_t K, int32_t items,
+                                            int32_t heads, int32_t T, int32_t Smax, MI_LISTS_DECODE_FP8_OPERANDS);
+int mi_block_attention_lists_decode_paged_fp8_bf16(const int32_t* block_ids, const int32_t* block_counts, int32_t K, int32_t items,
+                                                   int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                                   int64_t table_ld, int32_t pages, int32_t page, MI_LISTS_DECODE_FP8_OPERANDS);
+int mi_block_attention_lists_decode_paged_fp8_f16(const int32_t* block_ids, const int32_t* block_counts, int32_t K, int32_t items,
+                                                  int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                                  int64_t table_ld, int32_t pages, int32_t page, MI_LISTS_DECODE_FP8_OPERANDS);
+
+/* ------------------------------------------------------------------------ *
  * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in
  * bfloat16 / float16 (T, 2-byte bit patterns) with A given as the kept 64 × 64 blocks of a CSR block list, shared by
  * every item of the batch, and the sampled product on the same list:

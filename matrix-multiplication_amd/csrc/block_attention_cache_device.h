@@ -126,8 +126,8 @@ struct ReadCall {
   Scales scales = Scales();
 };
 
-// … as an entry gathers it from its parameters, which the header names alike for all 28: the list (a layout's, or the caller's
-// lists: §3.29), then what the paged entries add (MI_READ_PAGED) and the scales of the fp8 ones (MI_READ_FP8).  (k, batchK and v,
+// … as an entry gathers it from its parameters, which the header names alike for all 32 (the four list entries over an fp8
+// cache, §3.32, included): the list (a layout's, or the caller's lists: §3.29), then what the paged entries add (MI_READ_PAGED) and the scales of the fp8 ones (MI_READ_FP8).  (k, batchK and v,
 // batchV stand for k_pages, pageK and v_pages, pageV of the header.)
 #define MI_READ_CALL(ROWPTR, COL, NNZ, LAYOUTS, ...)                                                                         \
   ReadCall{ROWPTR, COL, NNZ, LAYOUTS, items, heads, T, Smax, D, k, ldk, headK, batchK, v, ldv, headV, batchV, k_lens, lens_count, \

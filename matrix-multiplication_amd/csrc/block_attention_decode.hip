@@ -35,7 +35,8 @@
 //    element is T::down((O · inv) · v_scale[h]).  So without scales the call has the bits of the 2-byte call on the widened
 //    cache.  The scales are read from device memory by the kernels: never read back, graph-capturable.
 //
-//  * Lists in the place of a layout (mi_block_attention_decode_lists{,_paged}_{bf16,f16}): the list of token t of
+//  * Lists in the place of a layout (mi_block_attention_decode_lists{,_paged}_{bf16,f16}, DESIGN.md §3.29, and over an fp8 cache
+//    mi_block_attention_lists_decode{,_paged}_fp8_{bf16,f16}, §3.32): the list of token t of
 //    k / v item c is the first clamp(block_counts[c · T + t], 0, K) entries of row c · T + t of the caller's block_ids — what
 //    block_select.hip writes —, the chunks are counted over the K list positions, and everything after the list's two bounds is
 //    the same statements: the bits of the layout row that lists the same blocks in the same order.
@@ -60,17 +61,17 @@ namespace {
 constexpr int kWaves = 4;      // waves of a workgroup: wave w walks entries w, w + 4, … of the chunk
 constexpr int kMaxGroup = 16;  // own rows of the one MFMA tile
 
-// the list source as a form of the kernel's first parameter: TC itself — a CSR layout over a cache of TC — or Listed<T>
-template <class T>
+// the list source as a form of the kernel's first parameter: TC itself — a CSR layout over a cache of TC — or Listed<TC>
+template <class TC>
 struct Listed {};
 template <class TS>
 struct Source {
   typedef TS cache;
   static constexpr bool lists = false;
 };
-template <class T>
-struct Source<Listed<T>> {
-  typedef T cache;
+template <class TC>
+struct Source<Listed<TC>> {
+  typedef TC cache;
   static constexpr bool lists = true;
 };
 
@@ -258,9 +259,9 @@ __device__ __forceinline__ void finish(const Args& a, int c, int t, int g, int d
 // The cache element is part of the kernel's first parameter: T itself (k and v hold T), or Fp8<T> — the cache holds e4m3fn
 // bytes: the loads, the widening and the two scales differ, nothing else.
 // Where a token's list comes from is part of the kernel's first parameter too: row pos / 64 of the CSR layout of its k / v
-// item, or — Listed<T>, the *_lists entries, 2-byte caches only — row (c, t) of the caller's block_ids, cut
-// to block_counts.  A compile-time form of the walk: what follows the two bounds is the same statements, so a list has the
-// bits of the layout row that lists the same blocks in the same order.
+// item, or — Listed<TC>, the *_lists and *_lists_decode entries, over either cache element — row (c, t)
+// of the caller's block_ids, cut to block_counts.  A compile-time form of the walk: what follows the two bounds is the same
+// statements, so a list has the bits of the layout row that lists the same blocks in the same order.
 template <class TS, int D, int FORM>
 __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   typedef typename Source<TS>::cache TC;
@@ -519,11 +520,9 @@ int launch(const Args& a, int items, hipStream_t s) {
   typedef std::conditional_t<FP8, Fp8<T>, T> TC;  // the cache element type is part of the kernel's first parameter
   with_form(a, [&](auto form) {
     constexpr int FORM = decltype(form)::value;
-    if constexpr (!FP8) {
-      if (a.counts) {  // the list source
-        hipLaunchKernelGGL((block_attention_decode_kernel<Listed<T>, D, FORM>), grid, dim3(256), 0, s, a);
-        return 0;
-      }
+    if (a.counts) {  // the list source
+      hipLaunchKernelGGL((block_attention_decode_kernel<Listed<TC>, D, FORM>), grid, dim3(256), 0, s, a);
+      return 0;
     }
     hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, FORM>), grid, dim3(256), 0, s, a);
     return 0;
@@ -637,6 +636,25 @@ int mi_block_attention_decode_lists_paged_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_S
 int mi_block_attention_decode_lists_paged_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
                                               MI_DECODE_OUT) {
   return page < 16 ? MI_EINVAL : decode_entry<F16>(MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_OWN);
+}
+
+// … over an fp8 cache: byte caches and the two scales after `scale`, as the fp8 layout entries place them.  (The
+// names put `lists` first: `mi_block_attention_decode…` is the closed family of the entries above.)
+int mi_block_attention_lists_decode_fp8_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
+                                             MI_DECODE_OUT) {
+  return decode_entry<Bf16, true>(MI_DECODE_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LISTS_OWN);
+}
+int mi_block_attention_lists_decode_fp8_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
+                                            MI_DECODE_OUT) {
+  return decode_entry<F16, true>(MI_DECODE_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LISTS_OWN);
+}
+int mi_block_attention_lists_decode_paged_fp8_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
+                                                   MI_DECODE_SCALES, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LISTS_OWN);
+}
+int mi_block_attention_lists_decode_paged_fp8_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
+                                                  MI_DECODE_SCALES, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LISTS_OWN);
 }
 
 }  // extern "C"

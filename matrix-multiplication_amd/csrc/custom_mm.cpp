@@ -275,6 +275,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("block_attention_decode_lists_paged", &block_attention_decode_lists_paged,
         "(block_ids, block_counts, q, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, scale, chunk, out, lse): "
         "block_attention_decode_lists over a pool of pages");
+  m.def("kv_block_bounds_fp8", &kv_block_bounds_fp8,
+        "(k [B, Hkv, Smax, D] float8_e4m3fn through its own strides (multiples of 16 bytes), k_lens, last, bounds [B, Hkv, Smax/64, 2, D] "
+        "bfloat16 / float16): kv_block_bounds over an fp8 cache — the bits of kv_block_bounds on the cache widened to bounds' dtype");
+  m.def("kv_block_bounds_paged_fp8", &kv_block_bounds_paged_fp8,
+        "(k_pages [P, Hkv, page, D] float8_e4m3fn, block_table int32 [B, W], k_lens, last, bounds): kv_block_bounds_fp8 over a pool of "
+        "pages");
+  m.def("block_attention_lists_decode_fp8", &block_attention_lists_decode_fp8,
+        "(block_ids, block_counts, q, k, v [B, Hkv, Smax, D] float8_e4m3fn, k_lens, scale, k_scale, v_scale (None or float32 device "
+        "tensors of 1 or Hkv entries), chunk, out, lse): block_attention_decode_lists over an fp8 cache");
+  m.def("block_attention_lists_decode_paged_fp8", &block_attention_lists_decode_paged_fp8,
+        "(block_ids, block_counts, q, k_pages, v_pages [P, Hkv, page, D] float8_e4m3fn, block_table int32 [B, W], k_lens, scale, k_scale, "
+        "v_scale, chunk, out, lse): block_attention_lists_decode_fp8 over a pool of pages");
   m.def("bsr_mm", &bsr_mm,
         "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
         "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");

@@ -3,15 +3,19 @@
 // Part of the `custom_mm` extension: included by custom_mm.cpp inside its anonymous namespace, after
 // custom_mm_kv_cache.inc, whose reading-call pieces it shares with the decode and the prefill bindings (§3.31).  Not compiled on
 // its own.  Contract: include/mi_spmm.h, "Query-aware key-block selection": block_ids int32 [B, Hkv, T, K] and block_counts int32 [B, Hkv, T], contiguous, HANDED OVER AS THEY ARE; q and out
-// [B, Hq, T, D] contiguous, bfloat16 or float16; the cache of q's type, read through its own strides; lse float32 [B, Hq, T].
+// [B, Hq, T, D] contiguous, bfloat16 or float16; the cache of q's type or (the *_fp8 forms, §3.32) float8_e4m3fn with the two
+// scales, read through its own strides; lse float32 [B, Hq, T].
 
-// both forms: `table` null — the contiguous cache [B, Hkv, Smax, D] — or the block table of a pool [P, Hkv, page, D].  Its own:
+// all four forms: `table` null — the contiguous cache [B, Hkv, Smax, D] — or the block table of a pool [P, Hkv, page, D]; `fp8`: a
+// cache of e4m3fn bytes with the two scales.  Its own:
 // chunk, Smax % 64, the block_ids / block_counts rules, the workspace of a cache of K blocks, the C entry.
-torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kname, const char* vname, const torch::Tensor& block_ids,
-                                                const torch::Tensor& block_counts, const torch::Tensor& q, const torch::Tensor& k,
-                                                const torch::Tensor& v, const torch::Tensor* table, const torch::Tensor& k_lens,
-                                                double scale, int64_t chunk, torch::Tensor out, const torch::Tensor& lse) {
-  const ReadShape s = read_shape(what, kname, vname, false, q, k, v, table, out);
+torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kname, const char* vname, bool fp8,
+                                                const torch::Tensor& block_ids, const torch::Tensor& block_counts, const torch::Tensor& q,
+                                                const torch::Tensor& k, const torch::Tensor& v, const torch::Tensor* table,
+                                                const torch::Tensor& k_lens, double scale, const c10::optional<torch::Tensor>& k_scale,
+                                                const c10::optional<torch::Tensor>& v_scale, int64_t chunk, torch::Tensor out,
+                                                const torch::Tensor& lse) {
+  const ReadShape s = read_shape(what, kname, vname, fp8, q, k, v, table, out);
   TORCH_CHECK(chunk >= 1 && chunk <= INT32_MAX, what, ": chunk must be a positive int32, got ", chunk);
   const int64_t Smax = read_smax(what, k, table, s.B);
   TORCH_CHECK(Smax % 64 == 0, what, ": Smax = ", Smax, " must be a multiple of 64");
@@ -26,7 +30,7 @@ torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kn
   check_device_i32(block_counts, "block_counts");
   check_same_device(what, q.device(), {&block_ids, &block_counts, &k, &v});
   check_read_operands(what, q.device(), true, q, table, k_lens, out, lse, s);
-  const ReadCache r = read_cache(what, kname, vname, false, q, k, v, table, c10::nullopt, c10::nullopt, s);
+  const ReadCache r = read_cache(what, kname, vname, fp8, q, k, v, table, k_scale, v_scale, s);
   check_sizes(what, {64 * K, s.B * s.Hkv * s.T * K});
   if (out.numel() == 0) return out;
   c10::hip::HIPGuard guard(out.device().index());
@@ -35,14 +39,22 @@ torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kn
                                                                     (int32_t)(64 * K), (int32_t)chunk);
   torch::Tensor ws = byte_workspace(out.device(), ws_bytes, 16);
 #define MI_LISTS_HEAD block_ids.data_ptr<int32_t>(), block_counts.data_ptr<int32_t>(), (int32_t)K, MI_READ_SIZES
-#define MI_LISTS_OPERANDS \
-  (int32_t) s.D, bits16(q), s.D, s.T* s.D, MI_READ_CACHE(uint16_t), (int32_t)s.group, (int32_t)chunk, (float)scale, MI_READ_OUT, \
-      ws.data_ptr(), ws_bytes, stream_of(out)
-  const int st = table ? (s.bf ? mi_block_attention_decode_lists_paged_bf16 : mi_block_attention_decode_lists_paged_f16)(
-                             MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS)
-                       : (s.bf ? mi_block_attention_decode_lists_bf16 : mi_block_attention_decode_lists_f16)(MI_LISTS_HEAD, MI_LISTS_OPERANDS);
+#define MI_LISTS_OPERANDS(CT) (int32_t) s.D, bits16(q), s.D, s.T* s.D, MI_READ_CACHE(CT), (int32_t)s.group, (int32_t)chunk, (float)scale
+#define MI_LISTS_OUT MI_READ_OUT, ws.data_ptr(), ws_bytes, stream_of(out)
+  int st;
+  if (fp8)
+    st = table ? (s.bf ? mi_block_attention_lists_decode_paged_fp8_bf16 : mi_block_attention_lists_decode_paged_fp8_f16)(
+                     MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_OUT)
+               : (s.bf ? mi_block_attention_lists_decode_fp8_bf16 : mi_block_attention_lists_decode_fp8_f16)(
+                     MI_LISTS_HEAD, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_OUT);
+  else
+    st = table ? (s.bf ? mi_block_attention_decode_lists_paged_bf16 : mi_block_attention_decode_lists_paged_f16)(
+                             MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint16_t), MI_LISTS_OUT)
+               : (s.bf ? mi_block_attention_decode_lists_bf16 : mi_block_attention_decode_lists_f16)(
+                     MI_LISTS_HEAD, MI_LISTS_OPERANDS(uint16_t), MI_LISTS_OUT);
 #undef MI_LISTS_HEAD
 #undef MI_LISTS_OPERANDS
+#undef MI_LISTS_OUT
   check_status(st, what);
   return out;
 }
@@ -50,14 +62,31 @@ torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kn
 torch::Tensor block_attention_decode_lists(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q, torch::Tensor k,
                                            torch::Tensor v, torch::Tensor k_lens, double scale, int64_t chunk, torch::Tensor out,
                                            torch::Tensor lse) {
-  return block_attention_decode_lists_impl("block_attention_decode_lists", "k", "v", block_ids, block_counts, q, k, v, nullptr, k_lens,
-                                           scale, chunk, out, lse);
+  return block_attention_decode_lists_impl("block_attention_decode_lists", "k", "v", false, block_ids, block_counts, q, k, v, nullptr,
+                                           k_lens, scale, c10::nullopt, c10::nullopt, chunk, out, lse);
 }
 
 torch::Tensor block_attention_decode_lists_paged(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q,
                                                  torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table,
                                                  torch::Tensor k_lens, double scale, int64_t chunk, torch::Tensor out,
                                                  torch::Tensor lse) {
-  return block_attention_decode_lists_impl("block_attention_decode_lists_paged", "k_pages", "v_pages", block_ids, block_counts, q,
-                                           k_pages, v_pages, &block_table, k_lens, scale, chunk, out, lse);
+  return block_attention_decode_lists_impl("block_attention_decode_lists_paged", "k_pages", "v_pages", false, block_ids, block_counts, q,
+                                           k_pages, v_pages, &block_table, k_lens, scale, c10::nullopt, c10::nullopt, chunk, out, lse);
+}
+
+torch::Tensor block_attention_lists_decode_fp8(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q, torch::Tensor k,
+                                               torch::Tensor v, torch::Tensor k_lens, double scale,
+                                               c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale, int64_t chunk,
+                                               torch::Tensor out, torch::Tensor lse) {
+  return block_attention_decode_lists_impl("block_attention_lists_decode_fp8", "k", "v", true, block_ids, block_counts, q, k, v, nullptr,
+                                           k_lens, scale, k_scale, v_scale, chunk, out, lse);
+}
+
+torch::Tensor block_attention_lists_decode_paged_fp8(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q,
+                                                     torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table,
+                                                     torch::Tensor k_lens, double scale, c10::optional<torch::Tensor> k_scale,
+                                                     c10::optional<torch::Tensor> v_scale, int64_t chunk, torch::Tensor out,
+                                                     torch::Tensor lse) {
+  return block_attention_decode_lists_impl("block_attention_lists_decode_paged_fp8", "k_pages", "v_pages", true, block_ids, block_counts,
+                                           q, k_pages, v_pages, &block_table, k_lens, scale, k_scale, v_scale, chunk, out, lse);
 }

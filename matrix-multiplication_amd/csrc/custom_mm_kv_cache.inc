@@ -177,8 +177,8 @@ ReadCache read_cache(const char* what, const char* kname, const char* vname, boo
 
 uint16_t* bits16(const torch::Tensor& t) { return static_cast<uint16_t*>(t.data_ptr()); }
 
-// The argument lists of the 28 C entries in the pieces they share (`s`: the ReadShape, `r`: the ReadCache, CT: the cache's
-// element at the C ABI): the sizes, what the paged entries add, the cache with the lengths, what the fp8 entries add, out and lse.
+// The argument lists of the 32 C entries (§3.31's 28 and the four list entries over an fp8 cache of §3.32) in the pieces they
+// share (`s`: the ReadShape, `r`: the ReadCache, CT: the cache's element at the C ABI): the sizes, what the paged entries add, the cache with the lengths, what the fp8 entries add, out and lse.
 #define MI_READ_SIZES (int32_t)(s.B * s.Hkv), (int32_t)s.Hkv, (int32_t)s.T, (int32_t)r.c.Smax
 #define MI_READ_TABLE r.c.table, r.c.table_ld, (int32_t)r.c.P, (int32_t)r.c.page
 #define MI_READ_CACHE(CT)                                                                                                   \

@@ -2828,11 +2828,21 @@ def block_attention_decode_selected_paged_takes(dtype, D: int, group: int, page:
     return block_attention_decode_paged_takes(dtype, D, _BLOCK_TILE, group, page)
 
 
-def _check_key_cache(what, kn, k, block_table):
+_BOUNDS_BINDINGS = (('kv_block_bounds', 'kv_block_bounds_fp8'),  # [paged][fp8]
+                    ('kv_block_bounds_paged', 'kv_block_bounds_paged_fp8'))
+_SELECTED_BINDINGS = (('block_attention_decode_lists', 'block_attention_lists_decode_fp8'),  # [paged][fp8]
+                      ('block_attention_decode_lists_paged', 'block_attention_lists_decode_paged_fp8'))
+_SELECT_FP8_SIZES_TEXT = 'a float8_e4m3fn cache, bfloat16 or float16 bounds, head size D in {32, 64, 96, 128}, Smax a multiple of 64'
+
+
+def _check_key_cache(what, kn, k, block_table, fp8=False):
     '''The key cache of the bounds call, as the decode calls check theirs: shape, D, page and table, Smax a multiple of 64,
-    strides.  Returns (B, Hkv, Smax, D).'''
+    strides.  fp8: a float8_e4m3fn cache (_check_fp8_cache), its strides multiples of 16 bytes.  Returns (B, Hkv, Smax, D).'''
     paged = kn == 'k_pages'
-    _check_lowp_operands(what, ((kn, k),), _SELECT_SIZES_TEXT)
+    if fp8:
+        _check_fp8_cache(what, ((kn, k),), _SELECT_FP8_SIZES_TEXT)
+    else:
+        _check_lowp_operands(what, ((kn, k),), _SELECT_SIZES_TEXT)
     if k.dim() != 4:
         raise ValueError(f'{what}: {kn} must be {"[P, Hkv, page, D]" if paged else "[B, Hkv, Smax, D]"}, got {k.dim()}-d')
     Hkv, D = k.shape[1], k.shape[3]
@@ -2854,13 +2864,15 @@ def _check_key_cache(what, kn, k, block_table):
         raise ValueError(f'{what}: Smax = {Smax} must be a multiple of 64 (accepted: {_SELECT_SIZES_TEXT})')
     if B * Hkv > _DECODE_MAX_GRID or Smax >= 2 ** 31:
         raise ValueError(f'{what}: B·Hkv = {B * Hkv} must be at most {_DECODE_MAX_GRID} and Smax = {Smax} fit an int32')
-    _check_cache_strides(what, kn, k, D, 'page' if paged else 'batch')
+    _check_cache_strides(what, kn, k, D, 'page' if paged else 'batch', 16 if fp8 else 8)
     return B, Hkv, Smax, D
 
 
-def _key_block_bounds(what, kn, k, block_table, k_lens, bounds, last):
+def _key_block_bounds(what, kn, k, block_table, k_lens, bounds, last, fp8=False, dtype=None):
+    '''The one body of the four bounds calls.  fp8: the cache is float8_e4m3fn and the bounds' dtype is the caller's choice —
+    that of `bounds`, or `dtype` when the call allocates them.'''
     paged = kn == 'k_pages'
-    B, Hkv, Smax, D = _check_key_cache(what, kn, k, block_table)
+    B, Hkv, Smax, D = _check_key_cache(what, kn, k, block_table, fp8)
     _check_k_lens(what, k_lens, B)
     if last is not None and (not _is_int(last) or last < 1 or last >= 2 ** 31):
         raise ValueError(f'{what}: last must be None (every block) or an int >= 1 (the tokens just appended), got {last!r}')
@@ -2873,19 +2885,25 @@ def _key_block_bounds(what, kn, k, block_table, k_lens, bounds, last):
         if not isinstance(bounds, torch.Tensor) or bounds.layout != torch.strided or tuple(bounds.shape) != shape or \
                 not bounds.is_contiguous():
             raise ValueError(f'{what}: bounds must be None or a contiguous dense tensor [B, Hkv, Smax/64, 2, D] = {list(shape)}')
-        if bounds.dtype != k.dtype:
+        if fp8 and bounds.dtype not in _LOWP:
+            raise ValueError(f'{what}: bounds must be bfloat16 or float16, got {bounds.dtype} (accepted: {_SELECT_FP8_SIZES_TEXT})')
+        if fp8 and dtype is not None and dtype != bounds.dtype:
+            raise RuntimeError(f'{what}: dtype is {dtype} but bounds is {bounds.dtype}: the bounds given decide, leave dtype out')
+        if not fp8 and bounds.dtype != k.dtype:
             raise RuntimeError(f'{what}: {kn} is {k.dtype} but bounds is {bounds.dtype}: the bounds are keys and have their dtype')
         tensors['bounds'] = bounds
+    elif fp8 and dtype not in _LOWP:
+        raise ValueError(f'{what}: dtype must be torch.bfloat16 or torch.float16 when bounds is None — the bounds of an fp8 cache '
+                         f'are kept in q\'s dtype —, got {dtype!r}')
     _check_on_device(what, **tensors)
     with torch.no_grad():
         if bounds is None:
-            bounds = torch.empty(shape, device=k.device, dtype=k.dtype)
+            bounds = torch.empty(shape, device=k.device, dtype=dtype if fp8 else k.dtype)
         if bounds.numel() > 0 and k.numel() > 0:
             lens = _lens_i32(k_lens)
-            if paged:
-                custom_mm.kv_block_bounds_paged(k.detach(), _table_i32(block_table), lens, int(last or 0), bounds.detach())
-            else:
-                custom_mm.kv_block_bounds(k.detach(), lens, int(last or 0), bounds.detach())
+            binding = getattr(custom_mm, _BOUNDS_BINDINGS[paged][fp8])
+            table = (_table_i32(block_table),) if paged else ()
+            binding(k.detach(), *table, lens, int(last or 0), bounds.detach())
     return bounds
 
 
@@ -2908,7 +2926,7 @@ def key_block_bounds(k: torch.Tensor, k_lens: torch.Tensor, bounds=None, *, last
     Minimum and maximum are exact, and a function of the seen keys alone: they do not depend on the order of the rows, the
     launch, or whether the cache is paged (the patterns are compared in one total order, in which −0 < +0).  With a NaN
     among the seen keys the block's bounds are unspecified; nothing faults.  No atomics, no read-back: graph-capturable.
-    NO autograd.'''
+    NO autograd.  An fp8 cache is key_block_bounds_fp8's.'''
     return _key_block_bounds('key_block_bounds', 'k', k, None, k_lens, bounds, last)
 
 
@@ -2992,19 +3010,25 @@ def select_key_blocks(q: torch.Tensor, bounds: torch.Tensor, k_lens: torch.Tenso
     return (ids, counts, scores) if return_scores else (ids, counts)
 
 
-def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse):
-    '''The one body of the two list-source decode calls: _decode's checks minus the layout ones, the lists' own, one binding
-    call with the caller's lists as they are.'''
+def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse, k_scale=None,
+                     v_scale=None, fp8=False):
+    '''The one body of the four list-source decode calls: _decode's checks minus the layout ones, the lists' own, one binding
+    call with the caller's lists as they are.  fp8: a float8_e4m3fn cache with the scale operands of _decode(…, fp8=True).'''
     kn, vn = names
     paged = kn == 'k_pages'
-    sizes_text = _DECODE_SIZES_TEXT + (_PAGED_SIZES_SUFFIX if paged else '')
-    _check_lowp_operands(what, (('q', q), (kn, k), (vn, v)), _DECODE_SIZES_TEXT)
+    base_text = _DECODE_FP8_SIZES_TEXT if fp8 else _DECODE_SIZES_TEXT
+    sizes_text = base_text + (_PAGED_SIZES_SUFFIX if paged else '')
+    if fp8:
+        _check_lowp_operands(what, (('q', q),), base_text)
+        _check_fp8_cache(what, ((kn, k), (vn, v)), base_text)
+    else:
+        _check_lowp_operands(what, (('q', q), (kn, k), (vn, v)), _DECODE_SIZES_TEXT)
     for name, t in (('block_ids', block_ids), ('block_counts', block_counts)):
         if not isinstance(t, torch.Tensor) or t.layout != torch.strided or t.dtype != torch.int32:
             raise ValueError(f'{what}: {name} must be a dense int32 tensor (select_key_blocks\' output is handed over as it is)')
     if chunk is not None and (not _is_int(chunk) or chunk < 1 or chunk >= 2 ** 31):
         raise ValueError(f'{what}: chunk must be None or a positive int, got {chunk!r}')
-    Smax = _check_cache_shape(what, names, q, k, v, block_table, pool_owner="k_pages's")
+    Smax = _check_cache_shape(what, names, q, k, v, block_table, base_text, pool_owner="k_pages's")
     B, Hq, T, D = q.shape
     Hkv = k.shape[1]
     if Smax % _BLOCK_TILE != 0:
@@ -3021,13 +3045,15 @@ def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts,
     if B * Hkv * T * K >= 2 ** 31 or K * _BLOCK_TILE >= 2 ** 31:
         raise ValueError(f'{what}: B·Hkv·T·K = {B * Hkv * T * K} and 64·K must fit int32 indices')
     _check_k_lens(what, k_lens, B)
-    outer = 'page' if paged else 'batch'
-    _check_cache_strides(what, kn, k, D, outer)
-    _check_cache_strides(what, vn, v, D, outer)
+    outer, unit = ('page' if paged else 'batch'), (16 if fp8 else 8)
+    _check_cache_strides(what, kn, k, D, outer, unit)
+    _check_cache_strides(what, vn, v, D, outer, unit)
     operands = {'q': q, kn: k, vn: v}  # in the order the device check names them
     if paged:
         operands['block_table'] = block_table
     operands.update(block_ids=block_ids, block_counts=block_counts, k_lens=k_lens)
+    if fp8:
+        operands.update(_check_fp8_scales(what, (('k_scale', k_scale), ('v_scale', v_scale)), Hkv, q))
     _check_on_device(what, **operands)
     if scale is None:
         scale = 1.0 / float(D) ** 0.5
@@ -3040,8 +3066,10 @@ def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts,
         out = torch.empty_like(qc)
         lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
         if out.numel() > 0:
-            binding = custom_mm.block_attention_decode_lists_paged if paged else custom_mm.block_attention_decode_lists
-            binding(block_ids.detach(), block_counts.detach(), qc, k.detach(), v.detach(), *table, lens, float(scale), int(chunk), out, lse)
+            binding = getattr(custom_mm, _SELECTED_BINDINGS[paged][fp8])
+            fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
+            binding(block_ids.detach(), block_counts.detach(), qc, k.detach(), v.detach(), *table, lens, float(scale), *fp8_scales,
+                    int(chunk), out, lse)
     return (out, lse) if return_lse else out
 
 
@@ -3064,7 +3092,7 @@ def block_sparse_attention_decode_selected(q: torch.Tensor, k: torch.Tensor, v: 
     Bits: for token t, out and lse are bit for bit those of block_sparse_attention_decode with T = 1, k_lens = pos + 1, the
     same chunk and a (B, Hkv) layout whose row pos // 64 lists the same blocks in the same order — a row's bits depend on
     its list, pos and chunk only.  Returns out [B, Hq, T, D], or (out, lse) with return_lse=True.  No atomics, no read-back:
-    graph-capturable.  NO autograd.  fp8 caches are not taken.'''
+    graph-capturable.  NO autograd.  An fp8 cache is block_sparse_attention_decode_selected_fp8's.'''
     return _decode_selected('block_sparse_attention_decode_selected', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens, scale,
                             chunk, return_lse)
 
@@ -3078,6 +3106,92 @@ def block_sparse_attention_decode_selected_paged(q: torch.Tensor, k_pages: torch
     on the gathered cache (block_attention_decode_selected_paged_takes).'''
     return _decode_selected('block_sparse_attention_decode_selected_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
                             block_ids, block_counts, k_lens, scale, chunk, return_lse)
+
+
+# --------------------------------------------------------------------------- #
+# … over an FP8 (OCP e4m3fn) cache: bounds kept in q's dtype, decode over the lists (DESIGN.md §3.32)
+# --------------------------------------------------------------------------- #
+
+def key_block_bounds_fp8_takes(dtype, D: int, page=None) -> bool:
+    '''Whether key_block_bounds_fp8 (page None) or key_block_bounds_paged_fp8 (pages of `page` keys) writes bounds of `dtype` —
+    THE BOUNDS' dtype; the cache is float8_e4m3fn — at head size D: exactly key_block_bounds_takes(dtype, D, page).'''
+    return key_block_bounds_takes(dtype, D, page)
+
+
+def block_attention_decode_selected_fp8_takes(dtype, D: int, group: int) -> bool:
+    '''Whether block_sparse_attention_decode_selected_fp8 takes q of `dtype` (the cache is float8_e4m3fn): exactly
+    block_attention_decode_selected_takes.'''
+    return block_attention_decode_selected_takes(dtype, D, group)
+
+
+def block_attention_decode_selected_paged_fp8_takes(dtype, D: int, group: int, page: int) -> bool:
+    '''… and block_sparse_attention_decode_selected_paged_fp8: exactly block_attention_decode_selected_paged_takes.'''
+    return block_attention_decode_selected_paged_takes(dtype, D, group, page)
+
+
+def key_block_bounds_fp8(k: torch.Tensor, k_lens: torch.Tensor, bounds=None, *, dtype=None, last=None) -> torch.Tensor:
+    '''key_block_bounds over an FP8 cache: k [B, Hkv, Smax, D] torch.float8_e4m3fn — the cache of
+    block_sparse_attention_decode_fp8 with its rules (the OCP encoding; float8_e4m3fnuz, float8_e5m2 and uint8 raise
+    ValueError; read through its own strides, multiples of 16 bytes, and never copied).  THE BOUNDS ARE KEPT IN q's DTYPE:
+    [B, Hkv, Smax/64, 2, D] bfloat16 or float16, contiguous — what select_key_blocks takes as it is.  bounds=None: `dtype`
+    (torch.bfloat16 or torch.float16) is required and the tensor is allocated uninitialised; a `bounds` given is WRITTEN IN
+    PLACE and returned, and its dtype decides (a `dtype=` that disagrees is a RuntimeError)
+    (key_block_bounds_fp8_takes).
+
+    Bits: every finite e4m3fn code is a bfloat16 and a float16, and the widening is strictly monotone in the order the
+    bounds are taken in (−0 < +0 included), so the result is bit for bit key_block_bounds(k.to(dtype), …) — the kernel
+    compares the bytes and widens only the results.  Everything else is key_block_bounds' contract: seen keys only, k_len
+    clamped on the device, a block with no seen key not written, last=T refreshing the blocks of [k_len − T, k_len); NaN
+    codes (0x7F, 0xFF) among the seen keys give unspecified, non-faulting results; no atomics, no read-back,
+    graph-capturable, NO autograd.
+
+    The scales of the cache are no operand.  kv_to_fp8 makes them positive, per k / v head, so they change neither a
+    minimum or maximum nor the ranking of the blocks inside a (b, h): select_key_blocks on these bounds lists the blocks it
+    would list on the bounds of the real keys.  Its scores (return_scores=True) are those of the UNSCALED widened keys:
+    the upper bound of the real q·k is score · k_scale[h].  A non-positive or NaN k scale makes the selection meaningless;
+    that is not checked (it would need a read-back).'''
+    return _key_block_bounds('key_block_bounds_fp8', 'k', k, None, k_lens, bounds, last, True, dtype)
+
+
+def key_block_bounds_paged_fp8(k_pages: torch.Tensor, block_table: torch.Tensor, k_lens: torch.Tensor, bounds=None, *, dtype=None,
+                               last=None) -> torch.Tensor:
+    '''key_block_bounds_fp8 over a PAGED cache: k_pages [P, Hkv, page, D] torch.float8_e4m3fn and block_table [B, W], the
+    operands of block_sparse_attention_decode_paged_fp8 with its rules; hidden pages are left out as in
+    key_block_bounds_paged.  Bit for bit key_block_bounds_paged(k_pages.to(dtype), …), hence key_block_bounds_fp8 on the
+    gathered bytes.'''
+    return _key_block_bounds('key_block_bounds_paged_fp8', 'k_pages', k_pages, block_table, k_lens, bounds, last, True, dtype)
+
+
+def block_sparse_attention_decode_selected_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
+                                               block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, k_scale=None,
+                                               v_scale=None, chunk=None, return_lse: bool = False):
+    '''block_sparse_attention_decode_selected over an FP8 cache: q [B, Hq, T, D] bfloat16 or float16, k and v
+    [B, Hkv, Smax, D] torch.float8_e4m3fn with k_scale / v_scale as in block_sparse_attention_decode_fp8 — None (= 1), a
+    float, or a float32 device tensor of shape (), (1,) or (Hkv,), read by the kernel from device memory, so a captured
+    graph follows in-place updates.  block_ids, block_counts, k_lens, chunk, return_lse and every refusal are those of
+    block_sparse_attention_decode_selected; the cache rules (strides multiples of 16 bytes, never copied) those of the fp8
+    decode call (block_attention_decode_selected_fp8_takes).  The lists are handed over as they are.
+
+    Bits: for token t, out and lse are bit for bit those of block_sparse_attention_decode_fp8 with T = 1, k_lens = pos + 1,
+    the same chunk and scales and a (B, Hkv) layout whose row pos // 64 lists the same blocks in the same order.  With both
+    scales None: those of block_sparse_attention_decode_selected on k.to(q.dtype), v.to(q.dtype).
+
+    With lists from select_key_blocks over key_block_bounds_fp8: the selection ranks by the unscaled widened keys, which
+    for positive per-head k scales is the ranking of the real keys (see key_block_bounds_fp8).  No atomics, no read-back:
+    graph-capturable.  NO autograd.'''
+    return _decode_selected('block_sparse_attention_decode_selected_fp8', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens,
+                            scale, chunk, return_lse, k_scale, v_scale, True)
+
+
+def block_sparse_attention_decode_selected_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
+                                                     block_table: torch.Tensor, block_ids: torch.Tensor, block_counts: torch.Tensor,
+                                                     k_lens: torch.Tensor, scale=None, *, k_scale=None, v_scale=None, chunk=None,
+                                                     return_lse: bool = False):
+    '''block_sparse_attention_decode_selected_fp8 over a PAGED cache: k_pages, v_pages [P, Hkv, page, D] torch.float8_e4m3fn
+    and block_table [B, W] as in block_sparse_attention_decode_paged_fp8; the lists are indexed by logical 64-key blocks.
+    Bit for bit the contiguous fp8 call on the gathered bytes (block_attention_decode_selected_paged_fp8_takes).'''
+    return _decode_selected('block_sparse_attention_decode_selected_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages,
+                            block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse, k_scale, v_scale, True)
 
 
 # --------------------------------------------------------------------------- #
