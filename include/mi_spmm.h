@@ -1550,6 +1550,77 @@ int mi_block_attention_lists_decode_paged_fp8_f16(const int32_t* block_ids, cons
                                                   int64_t table_ld, int32_t pages, int32_t page, MI_LISTS_DECODE_FP8_OPERANDS);
 
 /* ------------------------------------------------------------------------ *
+ * Key-block selection per POSITION TILE for chunked prefill: mi_block_select_tiles_T scores every 64-key
+ * block against the queries of a whole 64-position tile of the chunk on the matrix cores and lists the K best per tile.
+ * q, bounds, k_lens, group, K, sink, local and the limits are mi_block_select_T's; new_lens, new_lens_count the prefill
+ * entries'.  X = ⌈T / 64⌉ + 1 tiles per item; the geometry is the prefill entries': with klen = clamp(k_len, 0, Smax),
+ * n = clamp(new_len, 0, T) (T for a NULL new_lens), tile x of item c is layout row r = ⌊(klen − T) / 64⌋ + x and its tokens the
+ * positions pos ∈ [64r, 64r + 64) ∩ [max(klen − n, 0), klen), slot pos − (klen − T).  A tile without a token: count 0, a row of
+ * −1, scores −inf.  Else the candidates are the blocks J ≤ r, and
+ *   s_{t,g}(J) = [q⁻ | q⁺] · [lo | hi]ᵀ in fp32 on the matrix cores (v_mfma_f32_16x16x32 in ascending k from +0) — the score
+ *   Σ_d max(q_d·lo_d, q_d·hi_d) of mi_block_select_T in another order of summation: q⁻ holds the elements of q whose sign bit
+ *   is set, q⁺ the others —, score(J) = max over the tile's tokens and the group's heads (a NaN term is passed over while
+ *   another is a number; a slot without a token takes no part).
+ * Forced blocks (the first `sink`, the `local` ending at r), the order (score descending, index ascending; −0 as +0; NaN
+ * lowest), count = min(K, candidates), the list in ASCENDING block index and −1 from count on are mi_block_select_T's.
+ * block_ids int32 [items][X][K], block_counts int32 [items][X], scores NULL or float32 [items][X][Smax/64] (the candidates'
+ * scores, −inf elsewhere; the selection is an exact function of them).  Bounds of non-candidates and q of slots without a
+ * token are never read.  With an inf or NaN in q or bounds the product form may give NaN (0 · inf) where mi_block_select_T
+ * has a number: then only the structure holds — the count, ascending distinct candidates, every forced block listed, no
+ * store outside the row.  No atomics, no read-back: graph-capturable.
+ * MI_EINVAL, before any HIP call: what mi_block_select_T refuses, a misaligned new_lens or a count other than 1 or
+ * items / heads.  items == 0 or T == 0: MI_OK.
+ * ------------------------------------------------------------------------ */
+#define MI_BLOCK_SELECT_TILES_OPERANDS                                                                                          \
+  int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, int32_t group, const uint16_t *q, int64_t ldq, int64_t headQ, \
+      int64_t batchQ, const uint16_t *bounds, const int32_t *k_lens, int32_t lens_count, const int32_t *new_lens,               \
+      int32_t new_lens_count, int32_t K, int32_t sink, int32_t local, int32_t *block_ids, int32_t *block_counts, float *scores, \
+      mi_stream_t stream
+int mi_block_select_tiles_bf16(MI_BLOCK_SELECT_TILES_OPERANDS);
+int mi_block_select_tiles_f16(MI_BLOCK_SELECT_TILES_OPERANDS);
+
+/* ------------------------------------------------------------------------ *
+ * Prefill over the caller's lists, mi_block_attention_lists_prefill{,_paged}{,_fp8}_T: mi_block_attention_prefill{,_paged}{,_fp8}_T with the list of POSITION
+ * TILE x of k / v item c given as a row of block_ids, in the place of a layout row.  X = ⌈T / 64⌉ + 1 tiles per item, from the
+ * shape alone; tile x of item c is layout row r = ⌊(clamp(k_len, 0, Smax) − T) / 64⌋ + x of the prefill entries and holds the
+ * slots whose pos lies in [64r, 64r + 64).
+ *   block_ids     int32 [items][X][K], 4-byte aligned; block_counts int32 [items][X]; K ≥ 1.  The list of tile x of item c
+ *                 is the first clamp(block_counts[c·X + x], 0, K) entries of row c·X + x; the group's query heads share it.
+ *                 An entry outside [0, Smax/64) — the −1 padding —, above r, or at or beyond ⌈k_len / 64⌉ is skipped; a
+ *                 block listed twice counts twice.  The row of a tile without a token is not looked at.
+ * Everything after the two bounds of the list is the prefill entries' walk, statement for statement: out and lse have the
+ * BITS of mi_block_attention_prefill{,_paged}{,_fp8}_T with a layout per k / v item whose row r lists the same blocks in the
+ * same order.  Every row of out and lse is written exactly once by the one launch.  No atomics, no workspace, no read-back:
+ * graph-capturable while the lists, k_lens, new_lens, the cache, the table and the scales change in place.
+ * Validation before any HIP call: what the prefill entry of the same form refuses but for the layout, K < 1, a null or
+ * misaligned block_ids / block_counts → MI_EINVAL; items · X · K beyond int32 → MI_ERANGE; items == 0 or T == 0 → MI_OK.
+ * There are no split forms: a list has K entries.  (`lists` stands before `prefill` in the name, as in
+ * mi_block_attention_lists_decode…: the entries `mi_block_attention_prefill…` are the closed family of the sixteen above.)
+ * ------------------------------------------------------------------------ */
+#define MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD \
+  const int32_t *block_ids, const int32_t *block_counts, int32_t K, int32_t items, int32_t heads, int32_t T, int32_t Smax
+int mi_block_attention_lists_prefill_bf16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, int32_t D,
+                                          MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_lists_prefill_f16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, int32_t D,
+                                         MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_lists_prefill_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_lists_prefill_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                               MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_lists_prefill_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, int32_t D,
+                                              MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                              MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_lists_prefill_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, int32_t D,
+                                             MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                             MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_lists_prefill_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE,
+                                                    int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                                    MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT);
+int mi_block_attention_lists_prefill_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE,
+                                                   int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                                   MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT);
+
+/* ------------------------------------------------------------------------ *
  * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in
  * bfloat16 / float16 (T, 2-byte bit patterns) with A given as the kept 64 × 64 blocks of a CSR block list, shared by
  * every item of the batch, and the sampled product on the same list:

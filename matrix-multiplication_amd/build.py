@@ -57,9 +57,10 @@ def _run(cmd, verbose):
 
 # Units whose kernels sit at the edge of the register file: compiled with the compiler's resource-usage remarks, which are
 # kept as build/<unit>.resources.txt (one line per kernel instantiation); a vector-register spill fails the build.
-RESOURCE_REPORTS = ("block_attention", "block_attention_decode", "block_attention_prefill", "kv_block_bounds", "block_select")
+RESOURCE_REPORTS = ("block_attention", "block_attention_decode", "block_attention_prefill", "kv_block_bounds", "block_select",
+                    "block_select_tiles")
 # … of which these have room to spare: any scratch memory fails their build too
-NO_SCRATCH = ("kv_block_bounds", "block_select")
+NO_SCRATCH = ("kv_block_bounds", "block_select", "block_select_tiles")
 _RESOURCE_FIELDS = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill", "LDS Size [bytes/block]",
                     "Occupancy [waves/SIMD]")
 

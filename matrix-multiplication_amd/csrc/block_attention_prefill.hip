@@ -47,6 +47,13 @@
 // (o, m, l) of its 64 rows where the unsplit walk normalises and stores out and lse.  block_attention_prefill_combine_kernel
 // merges the parts in ascending order and makes the unsplit store (store_row).  What the three kernels must agree on — the
 // tile's geometry (Geom), the clamped list range, the part count of a list — is said once, above the walk.
+//
+// Lists in the place of a layout (mi_block_attention_lists_prefill{,_paged}{,_fp8}_* — DESIGN.md §3.33): the list of tile x of
+// k / v item c is the first clamp(block_counts[c·X + x], 0, K) entries of row c·X + x of block_ids [items][X][K], X = ⌈T / 64⌉ + 1 —
+// the output of block_select_tiles.hip, or anyone's.  prefill_walk<…, LISTS> is the same walk: listed_range() stands where
+// list_range() stands, every statement after the two bounds of the list is shared, so a list has the bits of the layout row that
+// lists the same blocks in the same order.  block_attention_prefill_lists_kernel is the third shell; what it adds to Args
+// travels beside it (ListArgs).  Unsplit only: a list has K entries.
 #include <type_traits>
 
 #include "block_attention_cache_device.h"
@@ -242,6 +249,23 @@ __device__ __forceinline__ ListRange list_range(const Args& a, int c, int r) {
   return {beg < 0 ? 0 : beg, end > a.nnz ? a.nnz : end};
 }
 
+// What the list entries add to Args: the caller's lists in the place of the layout.  a.col is block_ids
+// [items][tiles][list_k], a.nnz its entries, a.rowptr null.  The unsplit kernel's argument stays as it was.
+struct ListArgs {
+  Args a;
+  const int32_t* counts;  // block_counts [items][tiles]
+  int list_k;             // K, the entries of a row of block_ids
+};
+
+// … and the list of tile x of k / v item c there: the first clamp(counts, 0, K) entries of row c · tiles + x, so inside col
+// whatever counts holds
+__device__ __forceinline__ ListRange listed_range(const Args& a, const int32_t* counts, int list_k, int c, int x) {
+  const long row = (long)c * a.tiles + x;
+  int n = counts[row];
+  n = n < 0 ? 0 : n > list_k ? list_k : n;
+  return {row * list_k, row * list_k + n};
+}
+
 // The parts of a list cut every `split` entries — part i holds the positions [beg + i · split, min(end, beg + (i + 1) · split))
 // — of which the first `parts` have a place in the workspace (a malformed rowptr cannot index past it).  A walk workgroup
 // whose part is not below this count leaves before any load, barrier or store; the combine launch merges exactly these.
@@ -271,8 +295,11 @@ __device__ __forceinline__ void store_row(const Args& a, const Geom& gm, long it
 // store_row, and a tile without a token stores the zero rows of the slots it owns.  With SPLIT a work unit is (u, part) and
 // walks the list positions of its part; a tile without a token, and a part beyond the list's count, leave at once — the
 // combine launch writes those rows —, and the epilogue stores the partial (o, m, l) of the 64 own rows into `ws`.
-template <class TC, int D, int FORM, bool NEWLENS, bool SPLIT>
-__device__ __forceinline__ void prefill_walk(const Args& a, int split, int parts, float* ws) {
+// LISTS (unsplit only): the list is the caller's, row (c, x) of block_ids, where the layout gives row r of its CSR lists —
+// the two bounds of the list are all that differs; a.new_lens is looked at when it is there, whatever NEWLENS says.
+template <class TC, int D, int FORM, bool NEWLENS, bool SPLIT, bool LISTS = false>
+__device__ __forceinline__ void prefill_walk(const Args& a, int split, int parts, float* ws, const int32_t* counts = nullptr,
+                                             int list_k = 0) {
   typedef typename Operand<TC>::type T;
   constexpr bool FP8 = Operand<TC>::fp8;
   typedef typename Cache<FP8>::elem E;
@@ -293,7 +320,7 @@ __device__ __forceinline__ void prefill_walk(const Args& a, int split, int parts
     const int g = (int)((u / kSpreadHeads) % G);
     const int c = (int)(slot / a.tiles), x = (int)(slot - (long)c * a.tiles);
     const int bi = c / a.heads, h = c - bi * a.heads;
-    const Geom gm = geometry(a, NEWLENS, c, bi, x, w, li);
+    const Geom gm = geometry(a, LISTS ? a.new_lens != nullptr : NEWLENS, c, bi, x, w, li);
     const int klen = gm.klen, r = gm.r;
     const long item = (long)c * G + g;
     if (!gm.any) {  // nothing to walk: the zero rows of the slots it owns, if any
@@ -312,7 +339,11 @@ __device__ __forceinline__ void prefill_walk(const Args& a, int split, int parts
     // what multiplies a score: scale, or in the fp8 forms scale · k_scale[h] — one fp32 product per workgroup
     const float sc = FP8 ? a.scale * head_scale(a.k_scale, a.k_scale_count, h) : a.scale;
     const int kblocks = (klen + kB - 1) / kB;
-    ListRange ls = list_range(a, c, r);
+    ListRange ls;
+    if constexpr (LISTS)
+      ls = listed_range(a, counts, list_k, c, x);
+    else
+      ls = list_range(a, c, r);
     if (SPLIT) {  // the part's entries, cut by list position
       if (part >= list_parts(ls, split, parts)) continue;
       ls.beg += (long)part * split;
@@ -453,6 +484,11 @@ __global__ __launch_bounds__(256) void block_attention_prefill_split_kernel(Spli
   prefill_walk<TC, D, FORM, NEWLENS, true>(sa.a, sa.split, sa.parts, sa.ws);
 }
 
+template <class TC, int D, int FORM>
+__global__ __launch_bounds__(256) void block_attention_prefill_lists_kernel(ListArgs la) {
+  prefill_walk<TC, D, FORM, true, false, true>(la.a, 0, 1, nullptr, la.counts, la.list_k);
+}
+
 // The second launch of a split call: one workgroup per (query item, tile), thread (w, li, lg) on own row 16w + li as in the
 // walk.  The tile's rows, its list and its number of parts are recomputed as the walk computes them; the partials of parts
 // [0, n) — exactly those a walk workgroup wrote — are merged in ascending order: M = max mᵢ, wᵢ = 1 if mᵢ == M else exp(mᵢ − M)
@@ -522,7 +558,13 @@ __global__ __launch_bounds__(256) void block_attention_prefill_combine_kernel(Sp
 }
 
 template <class TC, int D, int FORM>
-int launch_form(const Args& a, const SplitArgs& sp, hipStream_t s) {
+int launch_form(const Args& a, const SplitArgs& sp, const ListArgs& li, hipStream_t s) {
+  if (li.counts) {  // the list source: one launch, never split
+    const ListArgs la = {a, li.counts, li.list_k};
+    hipLaunchKernelGGL((block_attention_prefill_lists_kernel<TC, D, FORM>), dim3((unsigned)(a.units < kMaxGrid ? a.units : kMaxGrid)),
+                       dim3(256), 0, s, la);
+    return mi::check_launch();
+  }
   if (sp.parts > 1) {  // the split walk, then the combine: two launches on the one stream, the kernel boundary the hand-over
     typedef typename Operand<TC>::type T;
     const SplitArgs sa = {a, sp.split, sp.parts, sp.ws};
@@ -546,9 +588,9 @@ int launch_form(const Args& a, const SplitArgs& sp, hipStream_t s) {
 }
 
 template <class T, int D, bool FP8>
-int launch(const Args& a, const SplitArgs& sp, hipStream_t s) {
+int launch(const Args& a, const SplitArgs& sp, const ListArgs& li, hipStream_t s) {
   typedef std::conditional_t<FP8, Fp8<T>, T> TC;  // the cache element type is part of the kernel's first parameter
-  return with_form(a, [&](auto form) { return launch_form<TC, D, decltype(form)::value>(a, sp, s); });
+  return with_form(a, [&](auto form) { return launch_form<TC, D, decltype(form)::value>(a, sp, li, s); });
 }
 
 // What the split entries add: the list entries of a part, and the workspace of the partials.
@@ -559,19 +601,27 @@ struct Split {
   size_t workspace_bytes = 0;
 };
 
+// the caller's lists of the *_lists entries: block_counts [items][tiles] and K, the entries of a row of block_ids
+struct Lists {
+  const int32_t* counts = nullptr;
+  int32_t K = 0;
+};
+
 // the parts of a full list of Smax / 64 entries cut every `split`
 inline int parts_of(int32_t Smax, int32_t split) { return (int)(((long)Smax / kB + split - 1) / split); }
 
 // Every check comes before the first HIP call.  `r`: what every reading entry takes (block_attention_cache_device.h), FP8 its
 // cache type; q, new_lens and `split` — the split entries' cut and workspace; with one part the call is the unsplit launch —
-// are this entry's own.
+// are this entry's own, and `lists`: the list source (never with split) — `col` is block_ids, nnz its items · tiles · K entries.
 template <class T, bool FP8 = false>
 int prefill_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t headQ, int64_t batchQ, const int32_t* new_lens,
-                  int32_t new_lens_count, hipStream_t s, const Split& split = Split()) {
+                  int32_t new_lens_count, hipStream_t s, const Split& split = Split(), const Lists& lists = Lists()) {
+  const bool listed = lists.K != 0 || lists.counts;
+  if (listed && (split.on || lists.K < 1 || !lists.counts || !aligned4(lists.counts) || !aligned4(r.col))) return MI_EINVAL;
   if (split.on && split.entries < 1) return MI_EINVAL;
   if (const int st = read_sizes_status(FP8, r)) return st;
   if (read_is_empty(r)) return MI_OK;
-  if (!read_operands_ok(FP8, r)) return MI_EINVAL;
+  if (!read_operands_ok(FP8, r, listed)) return MI_EINVAL;
   if (new_lens && (!aligned4(new_lens) || (new_lens_count != 1 && new_lens_count != r.items / r.heads))) return MI_EINVAL;
   if (!q || !mi::aligned16(q) || !stride_ok(ldq) || !stride_ok(headQ) || !stride_ok(batchQ) || (r.T > 1 && ldq < r.D)) return MI_EINVAL;
   const int parts = split.on ? parts_of(r.Smax, split.entries) : 1;
@@ -583,6 +633,8 @@ int prefill_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t hea
   }
   Args a = {};
   SplitArgs sp = {};
+  ListArgs li = {};
+  if (listed) li.counts = lists.counts, li.list_k = lists.K;
   if (parts > 1) sp.split = split.entries, sp.parts = parts, sp.ws = static_cast<float*>(split.workspace);
   fill_read_args(a, FP8, r);
   a.tiles = (int)(((long)r.T + kB - 1) / kB + 1);
@@ -590,7 +642,7 @@ int prefill_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t hea
   a.units = (a.slots + kSpreadHeads - 1) / kSpreadHeads * kSpreadHeads * r.group;
   a.q = q, a.ldq = ldq, a.headQ = headQ, a.batchQ = batchQ;
   a.new_lens = new_lens, a.new_lens_one = new_lens_count == 1;
-  return with_width(r.D, [&](auto d) { return launch<T, decltype(d)::value, FP8>(a, sp, s); });
+  return with_width(r.D, [&](auto d) { return launch<T, decltype(d)::value, FP8>(a, sp, li, s); });
 }
 
 }  // namespace
@@ -685,6 +737,49 @@ int mi_block_attention_prefill_split_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LI
                                                    MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
                                                    MI_PREFILL_SPLIT_OUT) {
   return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
+}
+
+// the list source: the caller's block_ids / block_counts in the place of the layout — no rowptr, block_ids as
+// col, its items · (⌈T / 64⌉ + 1) · K entries as nnz, one layout.  (A K that is no positive int32 is refused inside, before the
+// product is looked at; T < 0 likewise by the sizes' check.)
+#define MI_PREFILL_LISTS_CALL(...) \
+  MI_READ_CALL(nullptr, block_ids, (K < 1 || T < 0) ? 0 : (int64_t)items * (((int64_t)T + kB - 1) / kB + 1) * K, 1, __VA_ARGS__)
+#define MI_PREFILL_LISTS_OWN MI_PREFILL_OWN, Split(), Lists{block_counts, K < 1 ? -1 : K}
+#define MI_PREFILL_LISTS_HEAD MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD
+
+int mi_block_attention_lists_prefill_bf16(MI_PREFILL_LISTS_HEAD, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                          MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return prefill_entry<Bf16>(MI_PREFILL_LISTS_CALL(), MI_PREFILL_LISTS_OWN);
+}
+int mi_block_attention_lists_prefill_f16(MI_PREFILL_LISTS_HEAD, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                         MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return prefill_entry<F16>(MI_PREFILL_LISTS_CALL(), MI_PREFILL_LISTS_OWN);
+}
+int mi_block_attention_lists_prefill_paged_bf16(MI_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<Bf16>(MI_PREFILL_LISTS_CALL(MI_READ_PAGED), MI_PREFILL_LISTS_OWN);
+}
+int mi_block_attention_lists_prefill_paged_f16(MI_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                               MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<F16>(MI_PREFILL_LISTS_CALL(MI_READ_PAGED), MI_PREFILL_LISTS_OWN);
+}
+int mi_block_attention_lists_prefill_fp8_bf16(MI_PREFILL_LISTS_HEAD, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                              MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return prefill_entry<Bf16, true>(MI_PREFILL_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_LISTS_OWN);
+}
+int mi_block_attention_lists_prefill_fp8_f16(MI_PREFILL_LISTS_HEAD, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                             MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return prefill_entry<F16, true>(MI_PREFILL_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_LISTS_OWN);
+}
+int mi_block_attention_lists_prefill_paged_fp8_bf16(MI_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                    MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                                    MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<Bf16, true>(MI_PREFILL_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_LISTS_OWN);
+}
+int mi_block_attention_lists_prefill_paged_fp8_f16(MI_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                   MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                                   MI_BLOCK_ATTENTION_PREFILL_OUT) {
+  return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_LISTS_OWN);
 }
 
 }  // extern "C"

@@ -21,15 +21,16 @@
 // cap of 16 384 blocks = 1 M keys; gfx950 gives a workgroup 160 KiB); the key of the last chosen unforced candidate is found
 // by a threshold search over those bits, four bits a round: a wave counts the keys at or above each of 15 trial thresholds
 // with ballots, the 16 waves' counts meet in LDS, one barrier a round.  Emission is a prefix-sum compaction over contiguous
-// index ranges — ascending order for free —, in which the ties at the threshold are taken lowest index first.
-#include "kv_cache_device.h"
+// index ranges — ascending order for free —, in which the ties at the threshold are taken lowest index first.  The search and
+// the emission are block_select_device.h's select_and_emit, shared with block_select_tiles.hip.
+#include "block_select_device.h"
 
 namespace {
 
 constexpr int kB = 64;
 constexpr int kMaxGroup = 16;
-constexpr int kThreads = 1024, kWavesWg = kThreads / 64;
-constexpr int kMaxBlocks = 16384;  // the scores of one token in LDS: 64 KiB
+constexpr int kThreads = kSelectThreads, kWavesWg = kSelectWaves;
+constexpr int kMaxBlocks = kSelectMaxBlocks;  // the scores of one token in LDS: 64 KiB
 
 struct Args {
   int heads, group, T, blocks, K, sink, local;
@@ -44,21 +45,13 @@ struct Args {
   float* scores;    // [items][T][blocks] or null
 };
 
-// a score as an unsigned key of the selection's order: NaN lowest, −0 as +0
-__device__ __forceinline__ unsigned key_of(float s) {
-  if (s != s) return 0u;
-  unsigned u = __float_as_uint(s);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 template <class T, int D>
 __global__ __launch_bounds__(kThreads) void block_select_kernel(Args a) {
   __shared__ unsigned keys[kMaxBlocks];
   __shared__ __attribute__((aligned(16))) float qs[kMaxGroup * D];
   __shared__ unsigned wcnt[2][kWavesWg][16];
   __shared__ unsigned wtot[kWavesWg];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int t = blockIdx.x, c = blockIdx.y;
   const int G = a.group, K = a.K;
   int klen = a.k_lens[c / a.lens_div];
@@ -123,86 +116,7 @@ __global__ __launch_bounds__(kThreads) void block_select_kernel(Args a) {
   }
   __syncthreads();
 
-  // ---- the threshold: the key of the last chosen unforced candidate ------------------------------------------------------
-  const int sinkN = a.sink < n ? a.sink : n;               // forced: J < sinkN …
-  const int localFrom = n - a.local > sinkN ? n - a.local : sinkN;  // … or J ≥ localFrom
-  const int forced = sinkN + (n - localFrom);
-  const int R = count - forced;  // slots of the unforced candidates (sink + local ≤ K: never negative)
-  const int U = n - forced;      // unforced candidates
-  unsigned th = 0u;              // chosen: key > th, and the lowest-index ties key == th that still fit
-  const bool all = R >= U, none = R <= 0;
-  if (!all && !none) {
-    for (int round = 0; round < 8; ++round) {
-      const int shift = 28 - 4 * round;
-      unsigned cnt[15];
-#pragma unroll
-      for (int d = 0; d < 15; ++d) cnt[d] = 0u;
-      for (int J0 = sinkN + wave * 64; J0 < localFrom; J0 += kThreads) {  // (a wave-uniform bound: every lane votes)
-        const int J = J0 + lane;
-        const bool in = J < localFrom;
-        const unsigned key = in ? keys[J] : 0u;
-#pragma unroll
-        for (int d = 0; d < 15; ++d)
-          cnt[d] += (unsigned)__popcll(__ballot(in && key >= (th | ((unsigned)(d + 1) << shift))));
-      }
-      unsigned(*buf)[16] = wcnt[round & 1];
-      if (lane == 0) {
-#pragma unroll
-        for (int d = 0; d < 15; ++d) buf[wave][d + 1] = cnt[d];
-      }
-      __syncthreads();
-      // lane d of 1 … 15 adds the waves' counts of digit d; the counts fall with d, so the lanes that reach R are a prefix
-      unsigned tot = 0u;
-      const int d = lane & 15;
-      if (d > 0)
-        for (int w = 0; w < kWavesWg; ++w) tot += buf[w][d];
-      const unsigned long long reach = __ballot(lane > 0 && lane < 16 && tot >= (unsigned)R);
-      const int digit = reach ? 63 - __clzll(reach) : 0;
-      th |= (unsigned)digit << shift;
-    }
-  }
-
-  // ---- emission: a prefix sum over contiguous index ranges -------------------------------------------------------------------
-  const int per = (n + kThreads - 1) / kThreads;
-  const int beg = tid * per < n ? tid * per : n, end = beg + per < n ? beg + per : n;
-  unsigned mine = 0u;  // chosen for certain (low half) and ties at the threshold (high half) of this thread's range
-  for (int J = beg; J < end; ++J) {
-    const bool f = J < sinkN || J >= localFrom;
-    const unsigned key = keys[J];
-    const bool sure = f || all || (!none && key > th);
-    const bool tie = !f && !all && !none && key == th;
-    mine += (sure ? 1u : 0u) + (tie ? 0x10000u : 0u);
-  }
-  unsigned incl = mine;  // (n ≤ 16 384: neither half overflows its 16 bits)
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned up = __shfl_up(incl, o);
-    if (lane >= o) incl += up;
-  }
-  if (lane == 63) wtot[wave] = incl;
-  __syncthreads();
-  unsigned before = incl - mine, total = 0u;
-  for (int w = 0; w < kWavesWg; ++w) {
-    const unsigned x = wtot[w];
-    if (w < wave) before += x;
-    total += x;
-  }
-  const int ties_taken = count - (int)(total & 0xffffu);  // ties that still fit, lowest index first
-  int sure_before = (int)(before & 0xffffu), tie_before = (int)(before >> 16);
-  for (int J = beg; J < end; ++J) {
-    const bool f = J < sinkN || J >= localFrom;
-    const unsigned key = keys[J];
-    const bool sure = f || all || (!none && key > th);
-    const bool tie = !f && !all && !none && key == th;
-    if (sure || (tie && tie_before < ties_taken)) {
-      const int slot = sure_before + (tie_before < ties_taken ? tie_before : ties_taken);
-      // (always: the guard keeps a wrong count inside the row — on both sides: with more sure candidates than slots
-      // ties_taken, and with it the slot, would be negative)
-      if ((unsigned)slot < (unsigned)count) ids[slot] = J;
-    }
-    sure_before += sure ? 1 : 0;
-    tie_before += tie ? 1 : 0;
-  }
+  select_and_emit(keys, wcnt, wtot, n, count, a.sink, a.local, ids, tid);
 }
 
 template <class T, int D>

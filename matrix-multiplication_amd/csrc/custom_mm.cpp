@@ -57,6 +57,7 @@ namespace {
 #include "custom_mm_kv_block_bounds.inc"
 #include "custom_mm_block_select.inc"
 #include "custom_mm_block_attention_decode_lists.inc"
+#include "custom_mm_block_attention_prefill_lists.inc"
 #include "custom_mm_bsr.inc"
 #include "custom_mm_bsr_linear.inc"
 
@@ -268,6 +269,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(q [B, Hq, T, D] through its own strides, bounds [B, Hkv, Smax/64, 2, D], k_lens, K, sink, local, block_ids int32 "
         "[B, Hkv, T, K], block_counts int32 [B, Hkv, T], scores float32 [B, Hkv, T, Smax/64] or None): the K best candidate blocks "
         "of every token by the bounds' upper estimate of q·k, forced sink / local blocks included, in ascending block index");
+  m.def("block_select_tiles", &block_select_tiles,
+        "(q [B, Hq, T, D] through its own strides, bounds [B, Hkv, Smax/64, 2, D], k_lens, new_lens int32 [B] / [1] or None, K, sink, "
+        "local, block_ids int32 [B, Hkv, X, K], block_counts int32 [B, Hkv, X], scores float32 [B, Hkv, X, Smax/64] or None; "
+        "X = ceil(T/64) + 1): block_select per 64-position tile of a prefill chunk, scored on the matrix cores");
   m.def("block_attention_decode_lists", &block_attention_decode_lists,
         "(block_ids int32 [B, Hkv, T, K], block_counts int32 [B, Hkv, T], q [B, Hq, T, D], k, v [B, Hkv, Smax, D] through their own "
         "strides, k_lens, scale, chunk, out, lse): block_attention_decode with the list of (k / v item, token) given as a row of "
@@ -287,6 +292,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("block_attention_lists_decode_paged_fp8", &block_attention_lists_decode_paged_fp8,
         "(block_ids, block_counts, q, k_pages, v_pages [P, Hkv, page, D] float8_e4m3fn, block_table int32 [B, W], k_lens, scale, k_scale, "
         "v_scale, chunk, out, lse): block_attention_lists_decode_fp8 over a pool of pages");
+  m.def("block_attention_lists_prefill", &block_attention_prefill_lists,
+        "(block_ids int32 [B, Hkv, ceil(T/64) + 1, K], block_counts int32 [B, Hkv, ceil(T/64) + 1], q [B, Hq, T, D], k, v "
+        "[B, Hkv, Smax, D] through their own strides, k_lens, new_lens int32 [B] / [1] or None, scale, out, lse): "
+        "block_attention_prefill with the list of (k / v item, position tile) given as a row of block_ids in the place of a layout row");
+  m.def("block_attention_lists_prefill_paged", &block_attention_prefill_lists_paged,
+        "(block_ids, block_counts, q, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, new_lens, scale, out, lse): "
+        "block_attention_lists_prefill over a pool of pages");
+  m.def("block_attention_lists_prefill_fp8", &block_attention_prefill_lists_fp8,
+        "(block_ids, block_counts, q, k, v [B, Hkv, Smax, D] float8_e4m3fn, k_lens, new_lens, scale, k_scale, v_scale (None or float32 "
+        "device tensors of 1 or Hkv entries), out, lse): block_attention_lists_prefill over an fp8 cache");
+  m.def("block_attention_lists_prefill_paged_fp8", &block_attention_prefill_lists_paged_fp8,
+        "(block_ids, block_counts, q, k_pages, v_pages [P, Hkv, page, D] float8_e4m3fn, block_table int32 [B, W], k_lens, new_lens, scale, "
+        "k_scale, v_scale, out, lse): block_attention_lists_prefill_fp8 over a pool of pages");
   m.def("bsr_mm", &bsr_mm,
         "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
         "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");

@@ -3195,6 +3195,263 @@ def block_sparse_attention_decode_selected_paged_fp8(q: torch.Tensor, k_pages: t
 
 
 # --------------------------------------------------------------------------- #
+# prefill over the caller's lists: one list per (k / v head, position tile) in the place of a layout
+# --------------------------------------------------------------------------- #
+
+def block_attention_prefill_tiles(T: int) -> int:
+    '''The position tiles X = ⌈T / 64⌉ + 1 of an item in the prefill calls — the third dimension of the lists of
+    block_sparse_attention_prefill_selected —, from T alone: a chunk of T tokens whose first position is no multiple of 64
+    touches one 64-position tile more than ⌈T / 64⌉.  Tile x of item b is layout row ⌊(k_lens[b] − T) / 64⌋ + x.'''
+    if not _is_int(T) or T < 1:
+        raise ValueError(f'block_attention_prefill_tiles: T must be an int >= 1, got {T!r}')
+    return -(-T // _BLOCK_TILE) + 1
+
+
+def select_key_blocks_tiles_takes(dtype, D: int, group: int, blocks: int) -> bool:
+    '''Whether select_key_blocks_tiles takes q of `dtype`, head size D, `group` query heads per k / v head and `blocks` =
+    Smax / 64 blocks per item: exactly select_key_blocks_takes (T is any T ≥ 1).'''
+    return select_key_blocks_takes(dtype, D, group, blocks)
+
+
+def select_key_blocks_tiles(q: torch.Tensor, bounds: torch.Tensor, k_lens: torch.Tensor, K: int, *, sink: int = 1, local: int = 2,
+                            new_lens=None, return_scores: bool = False):
+    '''select_key_blocks for a CHUNK OF A PROMPT: the K key blocks worth reading for every 64-POSITION TILE of the chunk, the
+    operands of block_sparse_attention_prefill_selected, scored on the matrix cores.  q [B, Hq, T, D] bfloat16 or float16,
+    read through its own strides under select_key_blocks' rule for q; bounds [B, Hkv, Smax/64, 2, D] contiguous in q's dtype —
+    the output of any of the four key_block_bounds* calls, fp8 caches included —; 1 ≤ G ≤ 16, D ∈ {32, 64, 96, 128}, at most
+    16 384 blocks (select_key_blocks_tiles_takes).  k_lens and new_lens follow the prefill calls' conventions: clamped in
+    the kernel, never read back.  Returns (block_ids int32 [B, Hkv, X, K], block_counts int32 [B, Hkv, X]) with
+    X = block_attention_prefill_tiles(T) = ⌈T / 64⌉ + 1, and with return_scores=True also scores float32 [B, Hkv, X, Smax/64].
+
+    Geometry: the prefill calls', word for word.  Tile x of item b is layout row r = ⌊(k_lens[b] − T) / 64⌋ + x; its tokens
+    are the slots that hold a token (t ≥ T − new_lens[b], pos ≥ 0) whose pos = k_lens[b] − T + t lies in [64r, 64r + 64).  A
+    tile without a token gets count 0 and a row of −1.  The CANDIDATES of a tile are the blocks J ≤ r.
+
+    score(J) = max over the tile's tokens and over the G heads of s_{t,g}(J), where s is select_key_blocks' upper bound
+    Σ_d max(q_d · lo_d, q_d · hi_d) = q⁻ · lo + q⁺ · hi with q⁺ = max(q, 0), q⁻ = min(q, 0), computed in float32 as ONE
+    product [q⁻ | q⁺] · [lo | hi]ᵀ of 2·D terms on the matrix cores (every product exact, the MFMAs of an accumulator in
+    ascending k from +0): no key of block J has a larger q·k with any token of the tile.  The order of the sum differs from
+    select_key_blocks', so the two calls' scores agree to rounding, not in bits.  A slot without a token takes no part; the
+    max passes over a NaN while another term is a number; −0 counts as +0; a NaN score ranks lowest.
+
+    Forced blocks — the candidates among the first `sink` blocks and the `local` blocks ending at r — order (score
+    descending, block index ascending), the list in ASCENDING BLOCK INDEX, block_counts = min(K, candidates), −1 from the
+    count on, scores −inf for non-candidates, and the ValueErrors are select_key_blocks' (plus new_lens').  Bounds of
+    non-candidates are never read.
+
+    NON-FINITE INPUTS: the contract above holds for finite q and bounds.  With an inf or NaN in q or bounds, the product
+    form 0 · inf may give NaN where select_key_blocks gives a number; then only the structure is guaranteed: the count,
+    ascending distinct candidates, every forced block listed, no store outside the row.
+
+    The bits of a tile's lists and scores depend on its own item's q, bounds, k_len, new_len, its positions, K, sink and
+    local only — never on B, T or the launch —, and the selection is an exact function of the float32 scores returned.  No
+    atomics, no read-back, fixed shapes: graph-capturable.  NO autograd.'''
+    what = 'select_key_blocks_tiles'
+    _check_lowp_operands(what, (('q', q), ('bounds', bounds)), _SELECT_SIZES_TEXT)
+    for name, x in (('K', K), ('sink', sink), ('local', local)):
+        if not _is_int(x):
+            raise ValueError(f'{what}: {name} must be an int, got {x!r}')
+    if K < 1 or K >= 2 ** 31:
+        raise ValueError(f'{what}: K must be a positive int32, got {K}')
+    if sink < 0:
+        raise ValueError(f'{what}: sink must be >= 0, got {sink}')
+    if local < 1:
+        raise ValueError(f'{what}: local must be >= 1 (the tile\'s own block is always read), got {local}')
+    if sink + local > K:
+        raise ValueError(f'{what}: sink + local = {sink + local} forced blocks do not fit K = {K}')
+    if q.dim() != 4 or bounds.dim() != 5:
+        raise ValueError(f'{what}: q must be [B, Hq, T, D] and bounds [B, Hkv, Smax/64, 2, D], got {q.dim()}-d and {bounds.dim()}-d')
+    B, Hq, T, D = q.shape
+    if D not in _BLOCK_HEAD_SIZES:
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D} (accepted: {_SELECT_SIZES_TEXT})')
+    Hkv, blocks = bounds.shape[1], bounds.shape[2]
+    if bounds.shape[0] != B or bounds.shape[3] != 2 or bounds.shape[4] != D or Hkv < 1 or Hq % Hkv != 0 or not bounds.is_contiguous():
+        raise ValueError(f'{what}: q of shape {tuple(q.shape)} needs contiguous bounds ({B}, "Hkv", "Smax/64", 2, {D}) with Hkv a '
+                         f'divisor of {Hq}, got {tuple(bounds.shape)}')
+    _check_decode_group(what, Hq, Hkv)
+    if T < 1:
+        raise ValueError(f'{what}: q must hold T >= 1 new tokens, got T = {T}')
+    if blocks > _SELECT_MAX_BLOCKS:
+        raise ValueError(f'{what}: {blocks} blocks per item exceed the {_SELECT_MAX_BLOCKS} (1 M keys) whose scores one workgroup '
+                         f'holds in LDS')
+    X = block_attention_prefill_tiles(T)
+    if B * Hkv > _DECODE_MAX_GRID or T >= 2 ** 31 or B * Hkv * X * max(K, blocks) >= 2 ** 31:
+        raise ValueError(f'{what}: B·Hkv = {B * Hkv} must be at most {_DECODE_MAX_GRID}, and T = {T} and '
+                         f'B·Hkv·(ceil(T/64) + 1)·max(K, blocks) fit an int32')
+    _check_k_lens(what, k_lens, B)
+    _check_new_lens(what, new_lens, B)
+    _check_source_strides(what, 'q', q)
+    tensors = dict(q=q, bounds=bounds, k_lens=k_lens)
+    if new_lens is not None:
+        tensors['new_lens'] = new_lens
+    _check_on_device(what, **tensors)
+    with torch.no_grad():
+        ids = torch.empty((B, Hkv, X, K), device=q.device, dtype=torch.int32)
+        counts = torch.empty((B, Hkv, X), device=q.device, dtype=torch.int32)
+        scores = torch.empty((B, Hkv, X, blocks), device=q.device, dtype=torch.float32) if return_scores else None
+        news = None if new_lens is None else new_lens.detach().to(torch.int32).contiguous()
+        if counts.numel() > 0:
+            custom_mm.block_select_tiles(q.detach(), bounds.detach(), _lens_i32(k_lens), news, int(K), int(sink), int(local), ids, counts,
+                                         scores)
+    return (ids, counts, scores) if return_scores else (ids, counts)
+
+
+def block_attention_prefill_selected_takes(dtype, D: int) -> bool:
+    '''Whether block_sparse_attention_prefill_selected takes head size D in `dtype` — a function of these alone: exactly
+    block_attention_prefill_takes(dtype, D, 64) (the group is any G ≥ 1, T any T ≥ 1, K any K ≥ 1).'''
+    return block_attention_prefill_takes(dtype, D, _BLOCK_TILE)
+
+
+def block_attention_prefill_selected_paged_takes(dtype, D: int, page: int) -> bool:
+    '''… and of block_sparse_attention_prefill_selected_paged: block_attention_prefill_paged_takes(dtype, D, 64, page).'''
+    return block_attention_prefill_paged_takes(dtype, D, _BLOCK_TILE, page)
+
+
+def block_attention_prefill_selected_fp8_takes(dtype, D: int) -> bool:
+    '''… of block_sparse_attention_prefill_selected_fp8 with q in `dtype` (the cache is float8_e4m3fn): exactly
+    block_attention_prefill_selected_takes.'''
+    return block_attention_prefill_selected_takes(dtype, D)
+
+
+def block_attention_prefill_selected_paged_fp8_takes(dtype, D: int, page: int) -> bool:
+    '''… and of block_sparse_attention_prefill_selected_paged_fp8: exactly block_attention_prefill_selected_paged_takes.'''
+    return block_attention_prefill_selected_paged_takes(dtype, D, page)
+
+
+_PREFILL_SELECTED_BINDINGS = (('block_attention_lists_prefill', 'block_attention_lists_prefill_fp8'),  # [paged][fp8]
+                              ('block_attention_lists_prefill_paged', 'block_attention_lists_prefill_paged_fp8'))
+
+
+def _prefill_selected(what, names, q, k, v, block_table, block_ids, block_counts, k_lens, scale, new_lens, return_lse, k_scale=None,
+                      v_scale=None, fp8=False):
+    '''The one body of the four list-source prefill calls, beside _decode_selected: _prefill's checks minus the layout ones —
+    no bound on the group, on B·Hkv or on T, q through its own strides, new_lens —, the lists' own with X = ⌈T / 64⌉ + 1 in
+    the place of T, one binding call with the caller's lists as they are.'''
+    kn, vn = names
+    paged = kn == 'k_pages'
+    base_text = _PREFILL_FP8_SIZES_TEXT if fp8 else _PREFILL_SIZES_TEXT
+    sizes_text = base_text + (_PAGED_SIZES_SUFFIX if paged else '')
+    if fp8:
+        _check_lowp_operands(what, (('q', q),), base_text)
+        _check_fp8_cache(what, ((kn, k), (vn, v)), base_text)
+    else:
+        _check_lowp_operands(what, (('q', q), (kn, k), (vn, v)), base_text)
+    for name, t in (('block_ids', block_ids), ('block_counts', block_counts)):
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided or t.dtype != torch.int32:
+            raise ValueError(f'{what}: {name} must be a dense int32 tensor (select_key_blocks_tiles\' output is handed over as it is)')
+    Smax = _check_cache_shape(what, names, q, k, v, block_table, base_text, None, pool_owner="k_pages's")
+    B, Hq, T, D = q.shape
+    Hkv = k.shape[1]
+    X = block_attention_prefill_tiles(T)
+    if Smax % _BLOCK_TILE != 0:
+        raise ValueError(f'{what}: Smax = {Smax} must be a multiple of 64 (accepted: {sizes_text})')
+    if block_ids.dim() != 4 or tuple(block_ids.shape[:3]) != (B, Hkv, X) or block_ids.shape[3] < 1 or not block_ids.is_contiguous():
+        raise ValueError(f'{what}: block_ids must be a contiguous [B, Hkv, ceil(T/64) + 1, K] = [{B}, {Hkv}, {X}, K >= 1] tensor, got '
+                         f'{tuple(block_ids.shape)}')
+    if tuple(block_counts.shape) != (B, Hkv, X) or not block_counts.is_contiguous():
+        raise ValueError(f'{what}: block_counts must be a contiguous [B, Hkv, ceil(T/64) + 1] = [{B}, {Hkv}, {X}] tensor, got '
+                         f'{tuple(block_counts.shape)}')
+    K = block_ids.shape[3]
+    if max(B * Hq, T, Smax) >= 2 ** 31:
+        raise ValueError(f'{what}: B·Hq = {B * Hq}, T = {T} and Smax = {Smax} must each fit an int32')
+    if B * Hkv * X * K >= 2 ** 31:
+        raise ValueError(f'{what}: B·Hkv·(ceil(T/64) + 1)·K = {B * Hkv * X * K} must fit int32 indices')
+    _check_k_lens(what, k_lens, B)
+    _check_new_lens(what, new_lens, B)
+    _check_source_strides(what, 'q', q)
+    outer, unit = ('page' if paged else 'batch'), (16 if fp8 else 8)
+    _check_cache_strides(what, kn, k, D, outer, unit)
+    _check_cache_strides(what, vn, v, D, outer, unit)
+    operands = {'q': q, kn: k, vn: v}  # in the order the device check names them
+    if paged:
+        operands['block_table'] = block_table
+    operands.update(block_ids=block_ids, block_counts=block_counts, k_lens=k_lens)
+    if new_lens is not None:
+        operands['new_lens'] = new_lens
+    if fp8:
+        operands.update(_check_fp8_scales(what, (('k_scale', k_scale), ('v_scale', v_scale)), Hkv, q))
+    _check_on_device(what, **operands)
+    if scale is None:
+        scale = 1.0 / float(D) ** 0.5
+    with torch.no_grad():
+        lens = _lens_i32(k_lens)
+        news = None if new_lens is None else new_lens.detach().to(torch.int32).contiguous()
+        table = (_table_i32(block_table),) if paged else ()
+        out = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
+        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
+        if out.numel() > 0:
+            binding = getattr(custom_mm, _PREFILL_SELECTED_BINDINGS[paged][fp8])
+            fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
+            binding(block_ids.detach(), block_counts.detach(), q.detach(), k.detach(), v.detach(), *table, lens, news, float(scale),
+                    *fp8_scales, out, lse)
+    return (out, lse) if return_lse else out
+
+
+def block_sparse_attention_prefill_selected(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
+                                            block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, new_lens=None,
+                                            return_lse: bool = False):
+    '''block_sparse_attention_prefill with the blocks of every POSITION TILE given as a LIST in the place of a CSR layout: a
+    chunk of a prompt behind a long cached prefix reads the listed blocks only.  q [B, Hq, T, D], k and v [B, Hkv, Smax, D],
+    k_lens and new_lens as in that call (64-key blocks, Smax a multiple of 64, q and the cache read through their own strides
+    and never copied; Hq = G · Hkv with any G ≥ 1); block_ids int32 [B, Hkv, X, K] and block_counts int32 [B, Hkv, X] with
+    X = block_attention_prefill_tiles(T) = ⌈T / 64⌉ + 1, contiguous, HANDED TO THE KERNEL AS THEY ARE: no record is kept on
+    them and no torch op runs per call, so a step that rewrites them in place can be captured in a graph
+    (block_attention_prefill_selected_takes).
+
+    Tile x of item b is layout row r = ⌊(k_lens[b] − T) / 64⌋ + x of block_sparse_attention_prefill: the slots with a token
+    whose pos lies in [64r, 64r + 64).  Its list — shared by the G query heads of k / v head h — is the first
+    clamp(block_counts[b, h, x], 0, K) entries of block_ids[b, h, x].  Everything behind the two ends of the list is that
+    call's walk, statement for statement: an entry outside [0, Smax/64) — the −1 padding included — is skipped, an entry above
+    r is skipped, an entry at or beyond ⌈k_len / 64⌉ is skipped, the diagonal block is masked by position, keys at or beyond
+    k_len are staged as zeros; a block listed twice counts twice.  The row of a tile without a token is never looked at.
+
+    Bits: out and lse of every row are bit for bit those of block_sparse_attention_prefill with split=None and a (B, Hkv)
+    layout whose row r lists the same blocks in the same order — so a row's bits depend on its item's operands, its list
+    and pos, never on T, new_lens, B or the launch: a chunk of 100 tokens equals chunks of 60 and 40 where the lists of the
+    shared rows agree.  Every refusal is that call's but for the layout, plus the lists' own (ValueError: not int32, not
+    contiguous, a shape other than [B, Hkv, X, K ≥ 1] / [B, Hkv, X], B·Hkv·X·K beyond int32).  There is no `split`: a list
+    has K entries.  Returns a fresh out [B, Hq, T, D], every row written exactly once by ONE launch, or (out, lse) with
+    return_lse=True.  No atomics, no workspace, no read-back: graph-capturable.  NO autograd.'''
+    return _prefill_selected('block_sparse_attention_prefill_selected', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens,
+                             scale, new_lens, return_lse)
+
+
+def block_sparse_attention_prefill_selected_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
+                                                  block_table: torch.Tensor, block_ids: torch.Tensor, block_counts: torch.Tensor,
+                                                  k_lens: torch.Tensor, scale=None, *, new_lens=None, return_lse: bool = False):
+    '''block_sparse_attention_prefill_selected over a PAGED cache: k_pages, v_pages [P, Hkv, page, D] and block_table [B, W]
+    are the operands of block_sparse_attention_prefill_paged with its rules (Smax = W · page; an entry outside [0, P) hides
+    its page's keys); the lists are indexed by logical 64-key blocks, whatever `page` is.  Bit for bit the contiguous call
+    on the gathered cache (block_attention_prefill_selected_paged_takes).'''
+    return _prefill_selected('block_sparse_attention_prefill_selected_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
+                             block_ids, block_counts, k_lens, scale, new_lens, return_lse)
+
+
+def block_sparse_attention_prefill_selected_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
+                                                block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, k_scale=None,
+                                                v_scale=None, new_lens=None, return_lse: bool = False):
+    '''block_sparse_attention_prefill_selected over an FP8 cache: k, v [B, Hkv, Smax, D] torch.float8_e4m3fn with k_scale /
+    v_scale as in block_sparse_attention_prefill_fp8, whose cache rules and statements these are
+    (block_attention_prefill_selected_fp8_takes).  Bits: those of block_sparse_attention_prefill_fp8 with the same scales and
+    a layout that lists the same blocks in the same order; with both scales None those of
+    block_sparse_attention_prefill_selected on k.to(q.dtype), v.to(q.dtype).'''
+    return _prefill_selected('block_sparse_attention_prefill_selected_fp8', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens,
+                             scale, new_lens, return_lse, k_scale, v_scale, True)
+
+
+def block_sparse_attention_prefill_selected_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
+                                                      block_table: torch.Tensor, block_ids: torch.Tensor, block_counts: torch.Tensor,
+                                                      k_lens: torch.Tensor, scale=None, *, k_scale=None, v_scale=None,
+                                                      new_lens=None, return_lse: bool = False):
+    '''block_sparse_attention_prefill_selected_fp8 over a PAGED cache: k_pages, v_pages [P, Hkv, page, D]
+    torch.float8_e4m3fn and block_table [B, W] as in block_sparse_attention_prefill_paged_fp8; the lists are indexed by
+    logical 64-key blocks.  Bit for bit the contiguous fp8 call on the gathered bytes
+    (block_attention_prefill_selected_paged_fp8_takes).'''
+    return _prefill_selected('block_sparse_attention_prefill_selected_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages,
+                             block_table, block_ids, block_counts, k_lens, scale, new_lens, return_lse, k_scale, v_scale, True)
+
+
+# --------------------------------------------------------------------------- #
 # block-sparse (BSR) × dense products on the matrix cores
 # --------------------------------------------------------------------------- #
 
