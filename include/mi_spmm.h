@@ -1550,6 +1550,122 @@ int mi_block_attention_lists_decode_paged_fp8_f16(const int32_t* block_ids, cons
                                                   int64_t table_ld, int32_t pages, int32_t page, MI_LISTS_DECODE_FP8_OPERANDS);
 
 /* ------------------------------------------------------------------------ *
+ * Tree-masked decode for speculative decoding: the sixteen decode entries above — the layout entries
+ * mi_block_attention_decode{,_paged}{,_fp8}_T and the list entries mi_block_attention_decode_lists{,_paged}_T,
+ * mi_block_attention_lists_decode{,_paged}_fp8_T — as mi_block_attention_tree_decode{,_lists}{,_paged}{,_fp8}_T, with two
+ * parameters between `scale` (or the four scale parameters) and `out`:
+ *   tree_mask  int64 words [mask_rows][T] on the device, 8-byte aligned, read by the kernel and never read back
+ *   mask_rows  1 — one row of words for the whole batch — or the batch size items / heads
+ * The T newest tokens of an item are the nodes of a drafted tree, stored in the window [base, base + T) of the cache with
+ * base = clamp(k_len, 0, Smax) − T.  Token t stands at pos = base + t, as in the parents, and sees key j iff the parent's rule
+ * holds (j ≤ pos and its list names block j / 64) AND (j < base, or j == pos, or bit j − base of tree_mask[b][t] is set).  Bits at
+ * or above t are never looked at, a token always sees itself; the word (2 << t) − 1, or all ones, gives the parent entry's bits.
+ * A hidden key is treated like a key beyond pos: never loaded, staged as zeros, its score −inf — a NaN in a hidden slot reaches
+ * no output.  Chunks, the deal to the waves, the order of the merges, the workspace, out and lse are the parent's.
+ * Validation before any HIP call: what the parent refuses; T > 64 (before the empty call is answered with MI_OK); then, for a
+ * call that is not empty, a null or misaligned tree_mask and a mask_rows that is neither 1 nor items / heads — MI_EINVAL.
+ * (`tree` stands before `decode` in the name: the entries `mi_block_attention_decode…` are a closed family.)
+ * ------------------------------------------------------------------------ */
+#define MI_TREE_DECODE_OPERANDS(CT)                                                                                             \
+  int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const CT *k, int64_t ldk, int64_t headK, int64_t batchK,           \
+      const CT *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group,        \
+      int32_t chunk, float scale
+#define MI_TREE_DECODE_SCALES const float *k_scale, int32_t k_scale_count, const float *v_scale, int32_t v_scale_count
+#define MI_TREE_DECODE_OUT                                                                                                      \
+  const int64_t *tree_mask, int32_t mask_rows, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace,        \
+      size_t workspace_bytes, mi_stream_t stream
+#define MI_TREE_DECODE_LAYOUT \
+  const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts, int32_t items, int32_t heads, int32_t T, int32_t Smax
+#define MI_TREE_DECODE_LISTS \
+  const int32_t *block_ids, const int32_t *block_counts, int32_t K, int32_t items, int32_t heads, int32_t T, int32_t Smax
+#define MI_TREE_DECODE_TABLE const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page
+int mi_block_attention_tree_decode_bf16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_OPERANDS(uint16_t), MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_f16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_OPERANDS(uint16_t), MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_paged_bf16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint16_t),
+                                              MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_paged_f16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint16_t),
+                                             MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_fp8_bf16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_OPERANDS(uint8_t), MI_TREE_DECODE_SCALES,
+                                            MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_fp8_f16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_OPERANDS(uint8_t), MI_TREE_DECODE_SCALES,
+                                           MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_paged_fp8_bf16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint8_t),
+                                                  MI_TREE_DECODE_SCALES, MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_paged_fp8_f16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint8_t),
+                                                 MI_TREE_DECODE_SCALES, MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_lists_bf16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_OPERANDS(uint16_t), MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_lists_f16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_OPERANDS(uint16_t), MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_lists_paged_bf16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint16_t),
+                                                    MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_lists_paged_f16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint16_t),
+                                                   MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_lists_fp8_bf16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_OPERANDS(uint8_t), MI_TREE_DECODE_SCALES,
+                                                  MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_lists_fp8_f16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_OPERANDS(uint8_t), MI_TREE_DECODE_SCALES,
+                                                 MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_lists_paged_fp8_bf16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint8_t),
+                                                        MI_TREE_DECODE_SCALES, MI_TREE_DECODE_OUT);
+int mi_block_attention_tree_decode_lists_paged_fp8_f16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint8_t),
+                                                       MI_TREE_DECODE_SCALES, MI_TREE_DECODE_OUT);
+
+/* ------------------------------------------------------------------------ *
+ * Compaction after a speculative step: mi_kv_compact{,_paged} move the accepted path's k / v rows to the front
+ * of the window of the T ≤ 64 drafted slots, in place, in one launch for k and v.  The cache is that of mi_kv_append_* (items,
+ * heads, Smax, D, the strides IN ELEMENTS, block_table, table_ld, pages, page as there); elem_bytes is 2 (bfloat16 / float16) or 1
+ * (e4m3fn): rows are bit copies.
+ *   k_lens         [lens_count], lens_count 1 or items / heads: the lengths that STILL COUNT the T drafted slots; not clamped, not written
+ *   accept         int32 [items / heads][T]: offsets into the window;   accept_counts  int32 [items / heads]
+ * With base = k_len − T and n = clamp(accept_counts[b], 0, T): for i < n, row base + i of every k / v head of batch item b becomes
+ * the OLD row base + accept[b][i] — every source row of an (item, head) is read before any is written.  A row whose offset lies
+ * outside [0, T), whose source or destination row lies outside [0, Smax), or (paged) behind a table entry outside [0, pages) is
+ * left unwritten; rows at or beyond n and everything else keep their bytes.  No atomics, no read-back: graph-capturable.
+ * MI_EINVAL before any HIP call: elem_bytes, T > 64, what mi_kv_append_* refuses about sizes and the cache, a null or misaligned
+ * k_lens, accept or accept_counts.  MI_OK for items == 0 or T == 0.
+ * ------------------------------------------------------------------------ */
+#define MI_KV_COMPACT_OPERANDS                                                                                                 \
+  int32_t D, int32_t elem_bytes, void *k, int64_t ldk, int64_t headK, int64_t batchK, void *v, int64_t ldv, int64_t headV,     \
+      int64_t batchV, const int32_t *k_lens, int32_t lens_count, const int32_t *accept, const int32_t *accept_counts, mi_stream_t stream
+int mi_kv_compact(int32_t items, int32_t heads, int32_t T, int32_t Smax, MI_KV_COMPACT_OPERANDS);int mi_kv_compact_paged(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table, int64_t table_ld,
+                        int32_t pages, int32_t page, MI_KV_COMPACT_OPERANDS);
+
+/* ------------------------------------------------------------------------ *
+ * The fused rotary embedding + KV-cache append with EXPLICIT POSITIONS: the eight mi_rope_kv_append_* entries
+ * as mi_rope_pos_kv_append{,_paged}{,_fp8}_T, with one parameter after new_lens:
+ *   positions  int32 [items / heads][T] on the device, 4-byte aligned, read by the kernel and never read back
+ * Slot t of batch item b is rotated — its k row and its q rows alike — with row positions[b][t] of cos / sin in the place of row
+ * pos = k_len − T + t, and is still written where the parent writes it: q_out's and k_out's row t, the cache row pos.  A tree
+ * node is so rotated by prefix length + depth while it is stored in slot t.  The slot holds a token iff the parent's conditions
+ * hold (t ≥ T − n, 0 ≤ pos < table_rows) AND 0 ≤ positions[b][t] < table_rows; otherwise zero rows and nothing into the cache,
+ * as there.  The arithmetic is the parent's: two products, one sum, no fma, one rounding; positions[b][t] = pos gives its bits.
+ * MI_EINVAL before any HIP call: what the parent refuses, a null or misaligned positions.  (`pos` stands before `kv_append` in
+ * the name: the entries `mi_rope_kv_append…` are a closed family.)
+ * ------------------------------------------------------------------------ */
+int mi_rope_pos_kv_append_bf16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint16_t),
+                               const int32_t* positions, mi_stream_t stream);
+int mi_rope_pos_kv_append_f16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint16_t),
+                              const int32_t* positions, mi_stream_t stream);
+int mi_rope_pos_kv_append_paged_bf16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                     int64_t table_ld, int32_t pages, int32_t page, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint16_t),
+                                     const int32_t* positions, mi_stream_t stream);
+int mi_rope_pos_kv_append_paged_f16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                    int64_t table_ld, int32_t pages, int32_t page, int32_t D, MI_ROPE_KV_APPEND_OPERANDS(uint16_t),
+                                    const int32_t* positions, mi_stream_t stream);
+int mi_rope_pos_kv_append_fp8_bf16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D,
+                                   MI_ROPE_KV_APPEND_OPERANDS(uint8_t), const int32_t* positions, const float* k_scale,
+                                   int32_t k_scale_count, const float* v_scale, int32_t v_scale_count, mi_stream_t stream);
+int mi_rope_pos_kv_append_fp8_f16(int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D,
+                                  MI_ROPE_KV_APPEND_OPERANDS(uint8_t), const int32_t* positions, const float* k_scale,
+                                  int32_t k_scale_count, const float* v_scale, int32_t v_scale_count, mi_stream_t stream);
+int mi_rope_pos_kv_append_paged_fp8_bf16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                         int64_t table_ld, int32_t pages, int32_t page, int32_t D,
+                                         MI_ROPE_KV_APPEND_OPERANDS(uint8_t), const int32_t* positions, const float* k_scale,
+                                         int32_t k_scale_count, const float* v_scale, int32_t v_scale_count, mi_stream_t stream);
+int mi_rope_pos_kv_append_paged_fp8_f16(int32_t items, int32_t heads, int32_t T, int32_t Smax, const int32_t* block_table,
+                                        int64_t table_ld, int32_t pages, int32_t page, int32_t D,
+                                        MI_ROPE_KV_APPEND_OPERANDS(uint8_t), const int32_t* positions, const float* k_scale,
+                                        int32_t k_scale_count, const float* v_scale, int32_t v_scale_count, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * Key-block selection per POSITION TILE for chunked prefill: mi_block_select_tiles_T scores every 64-key
  * block against the queries of a whole 64-position tile of the chunk on the matrix cores and lists the K best per tile.
  * q, bounds, k_lens, group, K, sink, local and the limits are mi_block_select_T's; new_lens, new_lens_count the prefill

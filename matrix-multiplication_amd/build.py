@@ -58,9 +58,9 @@ def _run(cmd, verbose):
 # Units whose kernels sit at the edge of the register file: compiled with the compiler's resource-usage remarks, which are
 # kept as build/<unit>.resources.txt (one line per kernel instantiation); a vector-register spill fails the build.
 RESOURCE_REPORTS = ("block_attention", "block_attention_decode", "block_attention_prefill", "kv_block_bounds", "block_select",
-                    "block_select_tiles")
+                    "block_select_tiles", "kv_compact")
 # … of which these have room to spare: any scratch memory fails their build too
-NO_SCRATCH = ("kv_block_bounds", "block_select", "block_select_tiles")
+NO_SCRATCH = ("kv_block_bounds", "block_select", "block_select_tiles", "kv_compact")
 _RESOURCE_FIELDS = ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "VGPRs Spill", "SGPRs Spill", "LDS Size [bytes/block]",
                     "Occupancy [waves/SIMD]")
 

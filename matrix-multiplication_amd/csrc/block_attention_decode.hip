@@ -41,6 +41,12 @@
 //    block_select.hip writes —, the chunks are counted over the K list positions, and everything after the list's two bounds is
 //    the same statements: the bits of the layout row that lists the same blocks in the same order.
 //
+//  * Tree masks (mi_block_attention_tree_decode{,_lists}{,_paged}{,_fp8}_{bf16,f16}): the T new tokens are the nodes
+//    of a drafted tree in the window [base, base + T), base = clamp(k_len, 0, Smax) − T; token t sees key j iff the rule above
+//    holds and (j < base, or j == pos, or bit j − base of its int64 word tree_mask[b][t] is set).  A compile-time form of the
+//    kernel's first parameter — Tree<…> around either list source: a hidden key is treated like a key beyond pos (never loaded,
+//    staged as zeros, its score −inf), everything else is the same statements, so the word (2 << t) − 1 gives the plain call's bits.
+//
 // Kernel: grid (chunks, items, T), 256 threads.  No workgroup barrier inside the walk.  A wave loads the k tile of an
 // entry as 16-byte global loads straight into MFMA A fragments (lane (li, lg): row 16f + li, columns 32s + 8lg … + 7), the v
 // tile into registers and from there into a wave-private transposed LDS image [D][64 + 8] (a wave-level fence between its
@@ -68,11 +74,23 @@ template <class TS>
 struct Source {
   typedef TS cache;
   static constexpr bool lists = false;
+  static constexpr bool tree = false;
 };
 template <class TC>
 struct Source<Listed<TC>> {
   typedef TC cache;
   static constexpr bool lists = true;
+  static constexpr bool tree = false;
+};
+// … and the tree form wraps either: Tree<TC> or Tree<Listed<TC>> — the kernels of the tree_decode entries, whose
+// new tokens see the draft keys that their word of tree_mask names; the names of the plain kernels stay as they were
+template <class TS>
+struct Tree {};
+template <class TS>
+struct Source<Tree<TS>> {
+  typedef typename Source<TS>::cache cache;
+  static constexpr bool lists = Source<TS>::lists;
+  static constexpr bool tree = true;
 };
 
 struct Args {
@@ -109,7 +127,17 @@ struct Args {
   // item c its first clamp(counts[c · T + t], 0, list_k) entries; rowptr, nnz and layouts are not looked at
   const int32_t* counts;
   int list_k;
+  // the tree form of the tree_decode entries: word (b, t) of tree_mask [mask_rows][T] — mask_rows 1: one row for the
+  // batch — names the keys of the window [k_len − T, k_len) that token t sees beside itself: bit i < t is key k_len − T + i
+  const int64_t* tree_mask;
+  int mask_rows;
 };
+
+// The hide word of a tile (tree form): bit r is set iff row r of the tile is a draft key that the token does not see.  `hide`
+// is 0 in every plain kernel — a constant, so the tests on it fold away there.  A lane looks at its own rows through one
+// shift by its lane coordinate; the row's number inside the lane is a constant.
+typedef unsigned long long HideWord;
+__device__ __forceinline__ bool hidden(HideWord mine, int row) { return (mine >> row) & 1ull; }
 
 __device__ __forceinline__ void fence_wave() {  // LDS writes of this wave before, its reads after
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -120,12 +148,13 @@ __device__ __forceinline__ void fence_wave() {  // LDS writes of this wave befor
 // The k tile of a block as A fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of row 16f + li; rows at or beyond
 // `limit` (keys beyond pos) are zero fragments, whatever memory holds
 template <int D, class F, class E>
-__device__ __forceinline__ void load_k(F (&kf)[4][D / 32], const E* src, long ld, int li, int lg, int limit) {
+__device__ __forceinline__ void load_k(F (&kf)[4][D / 32], const E* src, long ld, int li, int lg, int limit, HideWord hide) {
+  const HideWord mine = hide >> li;  // row 16f + li at bit 16f
 #pragma unroll
   for (int f = 0; f < 4; ++f)
 #pragma unroll
     for (int s = 0; s < D / 32; ++s) {
-      if (16 * f + li < limit)
+      if (16 * f + li < limit && !hidden(mine, 16 * f))
         kf[f][s] = *reinterpret_cast<const F*>(src + (long)(16 * f + li) * ld + 32 * s + 8 * lg);
       else
         kf[f][s] = zero_frag<F>();
@@ -134,12 +163,13 @@ __device__ __forceinline__ void load_k(F (&kf)[4][D / 32], const E* src, long ld
 
 // The v tile of a block in one wave's registers: lane (li, lg) holds rows 4li … + 3, columns 8(lg + 4i) … + 7
 template <int D, class F, class E>
-__device__ __forceinline__ void load_v(F (&vr)[D / 32][4], const E* src, long ld, int li, int lg, int limit) {
+__device__ __forceinline__ void load_v(F (&vr)[D / 32][4], const E* src, long ld, int li, int lg, int limit, HideWord hide) {
+  const HideWord mine = hide >> (4 * li);  // row 4li + r at bit r
 #pragma unroll
   for (int i = 0; i < D / 32; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      if (4 * li + r < limit)
+      if (4 * li + r < limit && !hidden(mine, r))
         vr[i][r] = *reinterpret_cast<const F*>(src + (long)(4 * li + r) * ld + 8 * (lg + 4 * i));
       else
         vr[i][r] = zero_frag<F>();
@@ -150,11 +180,12 @@ __device__ __forceinline__ void load_v(F (&vr)[D / 32][4], const E* src, long ld
 // own page e[f]; a fragment of an invalid page is zero, whatever its entry holds
 template <int D, class F, class E>
 __device__ __forceinline__ void load_k_pages(F (&kf)[4][D / 32], const E* pool, long ld, long pageStride, const int (&e)[4],
-                                             unsigned ok, int in_page, int li, int lg, int limit) {
+                                             unsigned ok, int in_page, int li, int lg, int limit, HideWord hide) {
+  const HideWord mine = hide >> li;
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
     const E* src = pool + (long)e[f] * pageStride + (long)(((16 * f) & in_page) + li) * ld + 8 * lg;
-    const bool take = ((ok >> f) & 1u) && 16 * f + li < limit;
+    const bool take = ((ok >> f) & 1u) && 16 * f + li < limit && !hidden(mine, 16 * f);
 #pragma unroll
     for (int s = 0; s < D / 32; ++s) {
       if (take)
@@ -168,7 +199,8 @@ __device__ __forceinline__ void load_k_pages(F (&kf)[4][D / 32], const E* pool, 
 // load_v over pages of 16 or 32 keys: the lane's rows 4li … 4li + 3 lie in fragment li / 4, so in one page (4 divides 16)
 template <int D, class F, class E>
 __device__ __forceinline__ void load_v_pages(F (&vr)[D / 32][4], const E* pool, long ld, long pageStride, const int (&e)[4],
-                                             unsigned ok, int in_page, int li, int lg, int limit) {
+                                             unsigned ok, int in_page, int li, int lg, int limit, HideWord hide) {
+  const HideWord own = hide >> (4 * li);
   const int f = li >> 2;
   const int mine = f == 0 ? e[0] : f == 1 ? e[1] : f == 2 ? e[2] : e[3];
   const E* src = pool + (long)mine * pageStride + (long)((4 * li) & in_page) * ld + 8 * lg;
@@ -177,7 +209,7 @@ __device__ __forceinline__ void load_v_pages(F (&vr)[D / 32][4], const E* pool, 
   for (int i = 0; i < D / 32; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      if (valid && 4 * li + r < limit)
+      if (valid && 4 * li + r < limit && !hidden(own, r))
         vr[i][r] = *reinterpret_cast<const F*>(src + (long)r * ld + 32 * i);
       else
         vr[i][r] = zero_frag<F>();
@@ -266,6 +298,7 @@ template <class TS, int D, int FORM>
 __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   typedef typename Source<TS>::cache TC;
   constexpr bool LISTS = Source<TS>::lists;
+  constexpr bool TREE = Source<TS>::tree;
   typedef typename Operand<TC>::type T;
   constexpr bool FP8 = Operand<TC>::fp8;
   typedef typename Cache<FP8>::elem E;
@@ -276,7 +309,8 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lg = lane >> 4;
   // the paged forms say that the wave's number is uniform: list positions, columns and table entries stay in scalar
   // registers, and the page bases cost the vector file nothing
-  const int w = FORM == kContiguous ? tid >> 6 : __builtin_amdgcn_readfirstlane(tid >> 6);
+  // (so does the tree form: the tile's column and with it the hide word stay scalar)
+  const int w = FORM == kContiguous && !TREE ? tid >> 6 : __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ch = blockIdx.x, c = blockIdx.y, t = blockIdx.z;
   const int G = a.group;
   int klen = a.k_lens[c / a.lens_div];
@@ -317,6 +351,25 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   const E* K = static_cast<const E*>(a.k) + (FORM == kContiguous ? (long)(c / a.heads) * a.batchK : 0L) + (long)(c % a.heads) * a.headK;
   const E* V = static_cast<const E*>(a.v) + (FORM == kContiguous ? (long)(c / a.heads) * a.batchV : 0L) + (long)(c % a.heads) * a.headV;
   unsigned short* Vw = Vt[w];
+  // The tree form: token t sees key j iff the plain rule holds and (j < base, or j == pos, or bit j − base of its word is set).
+  // H: the hidden keys in window coordinates (bit i: key base + i), of the bits below t only — the token sees itself, and the
+  // keys beyond pos are the plain rule's.  Read once per workgroup through a uniform address, shifted per tile in scalar
+  // registers; a hidden key is treated like a key beyond pos: never loaded, staged as zeros, its score −inf.
+  [[maybe_unused]] HideWord H = 0;
+  [[maybe_unused]] int base = 0;
+  if constexpr (TREE) {
+    base = klen - a.T;
+    const HideWord mask = (HideWord)a.tree_mask[(long)(a.mask_rows == 1 ? 0 : c / a.heads) * a.T + t];
+    H = ~mask & ((1ull << t) - 1ull);  // (t < T ≤ 64)
+  }
+  auto hide_of = [&](int J) -> HideWord {  // the hide word of tile J: H moved by off = base − 64 J, 0 unless −64 < off < 64
+    if constexpr (TREE) {
+      const int off = base - J * kB;
+      return off <= -kB || off >= kB ? 0ull : off >= 0 ? H << off : H >> -off;
+    } else {
+      return 0ull;
+    }
+  };
   // what multiplies a score: scale, or in the fp8 forms scale · k_scale[h] — one fp32 product per workgroup
   const float sc = FP8 ? a.scale * head_scale(a.k_scale, a.k_scale_count, c % a.heads) : a.scale;
   // … and the stored element (only a one-chunk walk stores): read here, long before it is used
@@ -347,13 +400,14 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   const int in_page = FORM == kContiguous ? 0 : (1 << a.page_shift) - 1;
   auto issue = [&]() {  // the loads of tile J of the pool; an invalid page loads nothing and stages zeros
     const int limit = pos + 1 - J * kB;
+    const HideWord hide = hide_of(J);
     if constexpr (FORM == kPaged) {
       const long row = (J * kB) & in_page;
-      load_k<D>(kf, K + (long)e[0] * a.pageK + row * a.ldk, a.ldk, li, lg, ok ? limit : 0);
-      load_v<D>(vr, V + (long)e[0] * a.pageV + row * a.ldv, a.ldv, li, lg, ok ? limit : 0);
+      load_k<D>(kf, K + (long)e[0] * a.pageK + row * a.ldk, a.ldk, li, lg, ok ? limit : 0, hide);
+      load_v<D>(vr, V + (long)e[0] * a.pageV + row * a.ldv, a.ldv, li, lg, ok ? limit : 0, hide);
     } else {
-      load_k_pages<D>(kf, K, a.ldk, a.pageK, e, ok, in_page, li, lg, limit);
-      load_v_pages<D>(vr, V, a.ldv, a.pageV, e, ok, in_page, li, lg, limit);
+      load_k_pages<D>(kf, K, a.ldk, a.pageK, e, ok, in_page, li, lg, limit, hide);
+      load_v_pages<D>(vr, V, a.ldv, a.pageV, e, ok, in_page, li, lg, limit, hide);
     }
   };
   auto look_ahead = [&](int from) {  // the next computed entry at or after `from`, its column and its table entries
@@ -366,8 +420,8 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   if constexpr (FORM == kContiguous) {
     if (p < end) {
       const int J = a.col[p];
-      load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB);
-      load_v<D>(vr, V + (long)J * kB * a.ldv, a.ldv, li, lg, pos + 1 - J * kB);
+      load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB, hide_of(J));
+      load_v<D>(vr, V + (long)J * kB * a.ldv, a.ldv, li, lg, pos + 1 - J * kB, hide_of(J));
     }
   } else {
     trow = a.table + (long)(c / a.heads) * a.table_ld;
@@ -382,6 +436,8 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   while (p < end) {
     // keys of this block the token sees (≥ 1; 64 or more: all)
     const int visible = pos + 1 - (FORM == kContiguous ? a.col[p] : J) * kB;
+    // … and the draft keys among them that it does not (tree form): element 16f + 4lg + r at bit 16f + r
+    [[maybe_unused]] const HideWord unseen = hide_of(FORM == kContiguous ? a.col[p] : J) >> (4 * lg);
     const unsigned seen = ok;  // … and the fragments of it that lie in a page (paged forms)
     fence_wave();  // the previous entry's reads of the image are done
     store_transposed<T, D>(Vw, vr, li, lg);
@@ -392,8 +448,8 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
       p = next_entry(a.col, p + kWaves, end, pos, a.blocks);
       if (p < end) {  // the next entry's loads are in flight while this one is computed
         const int J = a.col[p];
-        load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB);
-        load_v<D>(vr, V + (long)J * kB * a.ldv, a.ldv, li, lg, pos + 1 - J * kB);
+        load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB, hide_of(J));
+        load_v<D>(vr, V + (long)J * kB * a.ldv, a.ldv, li, lg, pos + 1 - J * kB, hide_of(J));
       }
     } else {
       p = pn;
@@ -413,6 +469,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
       for (int r = 0; r < 4; ++r) {
         float x = s[f][r] * sc;
         if (16 * f + 4 * lg + r >= visible) x = -INFINITY;
+        if (TREE && hidden(unseen, 16 * f + r)) x = -INFINITY;  // a hidden draft key
         if (FORM != kContiguous && !((seen >> f) & 1u)) x = -INFINITY;  // a key of an invalid page
         s[f][r] = x;
         mt = fmaxf(mt, x);
@@ -514,27 +571,36 @@ int finish_launch(const Args& a, int items, int D, hipStream_t s) {
   return mi::check_launch();
 }
 
-template <class T, int D, bool FP8>
+template <class T, int D, bool FP8, bool TREE>
 int launch(const Args& a, int items, hipStream_t s) {
   const dim3 grid((unsigned)a.chunks, (unsigned)items, (unsigned)a.T);
   typedef std::conditional_t<FP8, Fp8<T>, T> TC;  // the cache element type is part of the kernel's first parameter
+  typedef std::conditional_t<TREE, Tree<TC>, TC> OfLayout;  // … and so is the tree form, around either list source
+  typedef std::conditional_t<TREE, Tree<Listed<TC>>, Listed<TC>> OfLists;
   with_form(a, [&](auto form) {
     constexpr int FORM = decltype(form)::value;
     if (a.counts) {  // the list source
-      hipLaunchKernelGGL((block_attention_decode_kernel<Listed<TC>, D, FORM>), grid, dim3(256), 0, s, a);
+      hipLaunchKernelGGL((block_attention_decode_kernel<OfLists, D, FORM>), grid, dim3(256), 0, s, a);
       return 0;
     }
-    hipLaunchKernelGGL((block_attention_decode_kernel<TC, D, FORM>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((block_attention_decode_kernel<OfLayout, D, FORM>), grid, dim3(256), 0, s, a);
     return 0;
   });
   return finish_launch<T>(a, items, D, s);
 }
 
+// the tree mask of the tree_decode entries: [rows][T] words, rows 1 (one row for the batch) or the batch size
+struct TreeMask {
+  const int64_t* mask = nullptr;
+  int32_t rows = 0;
+};
+constexpr int kMaxTree = 64;  // the T of a tree call: a token's word names the window's keys
+
 // Every check comes before the first HIP call.  `r`: what every reading entry takes (block_attention_cache_device.h), FP8 its
-// cache type; q, chunk and the workspace are this entry's own.
-template <class T, bool FP8 = false>
+// cache type, TREE that it is a tree_decode entry (`tree` is looked at); q, chunk and the workspace are this entry's own.
+template <class T, bool FP8 = false, bool TREE = false>
 int decode_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t strideQ, int32_t chunk, void* workspace,
-                 size_t workspace_bytes, hipStream_t s, const Lists& lists = Lists()) {
+                 size_t workspace_bytes, hipStream_t s, const Lists& lists = Lists(), const TreeMask& tree = TreeMask()) {
   // the list source: `col` is block_ids, nnz its items · T · K entries; a list has at most K entries, so the chunks — and
   // the workspace — are those of a cache of K blocks
   const bool listed = lists.K != 0 || lists.counts;
@@ -543,9 +609,12 @@ int decode_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t stri
   if (r.group > kMaxGroup || chunk < 1) return MI_EINVAL;
   if (const int st = read_sizes_status(FP8, r)) return st;
   if (r.items > 65535 || r.T > 65535) return MI_EINVAL;  // the grid's y and z: no item loop
+  if (TREE && r.T > kMaxTree) return MI_EINVAL;
   if (read_is_empty(r)) return MI_OK;
   if (!q || !mi::aligned16(q) || ldq < r.D || !stride_ok(ldq) || !stride_ok(strideQ)) return MI_EINVAL;
   if (!read_operands_ok(FP8, r, listed)) return MI_EINVAL;
+  if (TREE && (!tree.mask || reinterpret_cast<uintptr_t>(tree.mask) % 8 != 0 || (tree.rows != 1 && tree.rows != r.items / r.heads)))
+    return MI_EINVAL;
   const int chunks = chunks_of(span, chunk);
   if (chunks > 1) {
     if (!workspace || !mi::aligned16(workspace)) return MI_EINVAL;
@@ -557,7 +626,8 @@ int decode_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t stri
   a.q = q, a.ldq = ldq, a.strideQ = strideQ;
   a.ws = static_cast<float*>(workspace);
   if (listed) a.counts = lists.counts, a.list_k = lists.K;
-  return with_width(r.D, [&](auto d) { return launch<T, decltype(d)::value, FP8>(a, r.items, s); });
+  if (TREE) a.tree_mask = tree.mask, a.mask_rows = tree.rows;
+  return with_width(r.D, [&](auto d) { return launch<T, decltype(d)::value, FP8, TREE>(a, r.items, s); });
 }
 
 }  // namespace
@@ -655,6 +725,80 @@ int mi_block_attention_lists_decode_paged_fp8_bf16(MI_DECODE_LISTS_LIST, MI_DECO
 int mi_block_attention_lists_decode_paged_fp8_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
                                                   MI_DECODE_SCALES, MI_DECODE_OUT) {
   return page < 16 ? MI_EINVAL : decode_entry<F16, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LISTS_OWN);
+}
+
+// The tree forms: every entry above as mi_block_attention_tree_decode{,_lists}{,_paged}{,_fp8}_T, with
+// `tree_mask, mask_rows` between its operands and its outputs — int64 words [mask_rows][T], mask_rows 1 (one row for the batch) or
+// the batch size items / heads; T ≤ 64.
+#define MI_DECODE_TREE const int64_t *tree_mask, int32_t mask_rows
+#define MI_DECODE_TREE_OWN TreeMask{tree_mask, mask_rows}
+#define MI_DECODE_LAYOUT_TREE_OWN MI_DECODE_OWN, Lists(), MI_DECODE_TREE_OWN
+
+int mi_block_attention_tree_decode_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_TREE, MI_DECODE_OUT) {
+  return decode_entry<Bf16, false, true>(MI_DECODE_CALL(), MI_DECODE_LAYOUT_TREE_OWN);
+}
+int mi_block_attention_tree_decode_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_TREE, MI_DECODE_OUT) {
+  return decode_entry<F16, false, true>(MI_DECODE_CALL(), MI_DECODE_LAYOUT_TREE_OWN);
+}
+int mi_block_attention_tree_decode_paged_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
+                                              MI_DECODE_TREE, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16, false, true>(MI_DECODE_CALL(MI_READ_PAGED), MI_DECODE_LAYOUT_TREE_OWN);
+}
+int mi_block_attention_tree_decode_paged_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
+                                             MI_DECODE_TREE, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16, false, true>(MI_DECODE_CALL(MI_READ_PAGED), MI_DECODE_LAYOUT_TREE_OWN);
+}
+int mi_block_attention_tree_decode_fp8_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
+                                            MI_DECODE_TREE, MI_DECODE_OUT) {
+  return decode_entry<Bf16, true, true>(MI_DECODE_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LAYOUT_TREE_OWN);
+}
+int mi_block_attention_tree_decode_fp8_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
+                                           MI_DECODE_TREE, MI_DECODE_OUT) {
+  return decode_entry<F16, true, true>(MI_DECODE_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LAYOUT_TREE_OWN);
+}
+int mi_block_attention_tree_decode_paged_fp8_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
+                                                  MI_DECODE_SCALES, MI_DECODE_TREE, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16, true, true>(MI_DECODE_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LAYOUT_TREE_OWN);
+}
+int mi_block_attention_tree_decode_paged_fp8_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
+                                                 MI_DECODE_SCALES, MI_DECODE_TREE, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16, true, true>(MI_DECODE_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LAYOUT_TREE_OWN);
+}
+
+// … over the caller's lists
+#define MI_DECODE_LISTS_TREE_OWN MI_DECODE_OWN, Lists{block_counts, K < 1 ? -1 : K}, MI_DECODE_TREE_OWN
+
+int mi_block_attention_tree_decode_lists_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_TREE,
+                                              MI_DECODE_OUT) {
+  return decode_entry<Bf16, false, true>(MI_DECODE_LISTS_CALL(), MI_DECODE_LISTS_TREE_OWN);
+}
+int mi_block_attention_tree_decode_lists_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_TREE,
+                                             MI_DECODE_OUT) {
+  return decode_entry<F16, false, true>(MI_DECODE_LISTS_CALL(), MI_DECODE_LISTS_TREE_OWN);
+}
+int mi_block_attention_tree_decode_lists_paged_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
+                                                    MI_DECODE_TREE, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16, false, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_TREE_OWN);
+}
+int mi_block_attention_tree_decode_lists_paged_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
+                                                   MI_DECODE_TREE, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16, false, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_TREE_OWN);
+}
+int mi_block_attention_tree_decode_lists_fp8_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
+                                                  MI_DECODE_TREE, MI_DECODE_OUT) {
+  return decode_entry<Bf16, true, true>(MI_DECODE_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LISTS_TREE_OWN);
+}
+int mi_block_attention_tree_decode_lists_fp8_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
+                                                 MI_DECODE_TREE, MI_DECODE_OUT) {
+  return decode_entry<F16, true, true>(MI_DECODE_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LISTS_TREE_OWN);
+}
+int mi_block_attention_tree_decode_lists_paged_fp8_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
+                                                        MI_DECODE_SCALES, MI_DECODE_TREE, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<Bf16, true, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LISTS_TREE_OWN);
+}
+int mi_block_attention_tree_decode_lists_paged_fp8_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
+                                                       MI_DECODE_SCALES, MI_DECODE_TREE, MI_DECODE_OUT) {
+  return page < 16 ? MI_EINVAL : decode_entry<F16, true, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LISTS_TREE_OWN);
 }
 
 }  // extern "C"

@@ -53,6 +53,7 @@ namespace {
 #include "custom_mm_block_attention_decode.inc"
 #include "custom_mm_block_attention_prefill.inc"
 #include "custom_mm_kv_append.inc"
+#include "custom_mm_kv_compact.inc"
 #include "custom_mm_rope_kv_append.inc"
 #include "custom_mm_kv_block_bounds.inc"
 #include "custom_mm_block_select.inc"
@@ -249,6 +250,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_append_paged", &kv_append_paged,
         "(k_new, v_new, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, k_scale, v_scale): kv_append into a "
         "pool of pages; a token whose table entry lies outside [0, P) is dropped");
+  m.def("kv_compact", &kv_compact,
+        "(k, v [B, Hkv, Smax, D] bfloat16 / float16 / float8_e4m3fn through their own strides, k_lens int32 [B] or [1] — still "
+        "counting the T drafted slots —, accept int32 [B, T], accept_counts int32 [B], T <= 64): row k_lens[b] - T + i becomes the old "
+        "row k_lens[b] - T + accept[b, i] for i < accept_counts[b], every source row read before any is written; one launch for k and v");
+  m.def("kv_compact_paged", &kv_compact_paged,
+        "(k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, accept, accept_counts, T): kv_compact over a pool of "
+        "pages; a row behind an entry outside [0, P) is neither read nor written");
   m.def("rope_kv_append", &rope_kv_append,
         "(q [B, Hq, T, D], k_new, v_new [B, Hkv, T, D] bfloat16 / float16 through their own strides, cos, sin float32 [Pmax, R/2], "
         "k, v [B, Hkv, Smax, D] of that dtype or float8_e4m3fn, k_lens int32 [B] or [1] — the lengths AFTER the append —, new_lens "
@@ -258,6 +266,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_kv_append_paged", &rope_kv_append_paged,
         "(q, k_new, v_new, cos, sin, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, new_lens, q_out, k_out, "
         "rotary_dim, interleaved, k_scale, v_scale): rope_kv_append into a pool of pages");
+  m.def("rope_kv_append_pos", &rope_kv_append_pos,
+        "(rope_kv_append's arguments, positions int32 [B, T]): slot t of item b is rotated by table row positions[b, t] and still "
+        "written to row k_lens[b] - T + t; a slot whose position lies outside [0, Pmax) holds no token");
+  m.def("rope_kv_append_paged_pos", &rope_kv_append_paged_pos,
+        "(rope_kv_append_paged's arguments, positions int32 [B, T]): rope_kv_append_pos into a pool of pages");
   m.def("kv_block_bounds", &kv_block_bounds,
         "(k [B, Hkv, Smax, D] bfloat16 / float16 through its own strides, k_lens int32 [B] or [1], last, bounds [B, Hkv, Smax/64, 2, D]): "
         "the minimum and maximum of the seen keys of every 64-key block, in place; last = 0 every block that holds a key, n >= 1 "
@@ -280,6 +293,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("block_attention_decode_lists_paged", &block_attention_decode_lists_paged,
         "(block_ids, block_counts, q, k_pages, v_pages [P, Hkv, page, D], block_table int32 [B, W], k_lens, scale, chunk, out, lse): "
         "block_attention_decode_lists over a pool of pages");
+  m.def("block_attention_tree_decode", &block_attention_tree_decode,
+        "(block_attention_decode's arguments with tree_mask int64 [B, T] or [T], T <= 64, before chunk): token t sees the draft key "
+        "k_len - T + i, i < t, iff bit i of its word is set; the cached prefix and itself always");
+  m.def("block_attention_tree_decode_paged", &block_attention_tree_decode_paged,
+        "(block_attention_decode_paged's arguments with tree_mask before chunk): block_attention_tree_decode over a pool of pages");
+  m.def("block_attention_tree_decode_fp8", &block_attention_tree_decode_fp8,
+        "(block_attention_decode_fp8's arguments with tree_mask before chunk): block_attention_tree_decode over an fp8 cache");
+  m.def("block_attention_tree_decode_paged_fp8", &block_attention_tree_decode_paged_fp8,
+        "(block_attention_decode_paged_fp8's arguments with tree_mask before chunk): block_attention_tree_decode over an fp8 pool");
+  m.def("block_attention_tree_decode_lists", &block_attention_tree_decode_lists,
+        "(block_attention_decode_lists' arguments with tree_mask int64 [B, T] or [T], T <= 64, before chunk): the tree rule over the "
+        "caller's lists");
+  m.def("block_attention_tree_decode_lists_paged", &block_attention_tree_decode_lists_paged,
+        "(block_attention_decode_lists_paged's arguments with tree_mask before chunk)");
+  m.def("block_attention_tree_lists_decode_fp8", &block_attention_tree_lists_decode_fp8,
+        "(block_attention_lists_decode_fp8's arguments with tree_mask before chunk)");
+  m.def("block_attention_tree_lists_decode_paged_fp8", &block_attention_tree_lists_decode_paged_fp8,
+        "(block_attention_lists_decode_paged_fp8's arguments with tree_mask before chunk)");
   m.def("kv_block_bounds_fp8", &kv_block_bounds_fp8,
         "(k [B, Hkv, Smax, D] float8_e4m3fn through its own strides (multiples of 16 bytes), k_lens, last, bounds [B, Hkv, Smax/64, 2, D] "
         "bfloat16 / float16): kv_block_bounds over an fp8 cache — the bits of kv_block_bounds on the cache widened to bounds' dtype");

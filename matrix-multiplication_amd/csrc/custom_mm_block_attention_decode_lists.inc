@@ -14,7 +14,7 @@ torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kn
                                                 const torch::Tensor& k, const torch::Tensor& v, const torch::Tensor* table,
                                                 const torch::Tensor& k_lens, double scale, const c10::optional<torch::Tensor>& k_scale,
                                                 const c10::optional<torch::Tensor>& v_scale, int64_t chunk, torch::Tensor out,
-                                                const torch::Tensor& lse) {
+                                                const torch::Tensor& lse, const torch::Tensor* tree = nullptr) {
   const ReadShape s = read_shape(what, kname, vname, fp8, q, k, v, table, out);
   TORCH_CHECK(chunk >= 1 && chunk <= INT32_MAX, what, ": chunk must be a positive int32, got ", chunk);
   const int64_t Smax = read_smax(what, k, table, s.B);
@@ -32,6 +32,8 @@ torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kn
   check_read_operands(what, q.device(), true, q, table, k_lens, out, lse, s);
   const ReadCache r = read_cache(what, kname, vname, fp8, q, k, v, table, k_scale, v_scale, s);
   check_sizes(what, {64 * K, s.B * s.Hkv * s.T * K});
+  std::pair<const int64_t*, int32_t> tm = {nullptr, 0};
+  if (tree) tm = tree_mask_operand(what, *tree, s.B, s.T, q.device());
   if (out.numel() == 0) return out;
   c10::hip::HIPGuard guard(out.device().index());
   // a list has at most K entries: the chunks' partials are those of a cache of K blocks
@@ -41,8 +43,19 @@ torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kn
 #define MI_LISTS_HEAD block_ids.data_ptr<int32_t>(), block_counts.data_ptr<int32_t>(), (int32_t)K, MI_READ_SIZES
 #define MI_LISTS_OPERANDS(CT) (int32_t) s.D, bits16(q), s.D, s.T* s.D, MI_READ_CACHE(CT), (int32_t)s.group, (int32_t)chunk, (float)scale
 #define MI_LISTS_OUT MI_READ_OUT, ws.data_ptr(), ws_bytes, stream_of(out)
+#define MI_LISTS_TREE tm.first, tm.second
   int st;
-  if (fp8)
+  if (tree && fp8)
+    st = table ? (s.bf ? mi_block_attention_tree_decode_lists_paged_fp8_bf16 : mi_block_attention_tree_decode_lists_paged_fp8_f16)(
+                     MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_TREE, MI_LISTS_OUT)
+               : (s.bf ? mi_block_attention_tree_decode_lists_fp8_bf16 : mi_block_attention_tree_decode_lists_fp8_f16)(
+                     MI_LISTS_HEAD, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_TREE, MI_LISTS_OUT);
+  else if (tree)
+    st = table ? (s.bf ? mi_block_attention_tree_decode_lists_paged_bf16 : mi_block_attention_tree_decode_lists_paged_f16)(
+                     MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint16_t), MI_LISTS_TREE, MI_LISTS_OUT)
+               : (s.bf ? mi_block_attention_tree_decode_lists_bf16 : mi_block_attention_tree_decode_lists_f16)(
+                     MI_LISTS_HEAD, MI_LISTS_OPERANDS(uint16_t), MI_LISTS_TREE, MI_LISTS_OUT);
+  else if (fp8)
     st = table ? (s.bf ? mi_block_attention_lists_decode_paged_fp8_bf16 : mi_block_attention_lists_decode_paged_fp8_f16)(
                      MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_OUT)
                : (s.bf ? mi_block_attention_lists_decode_fp8_bf16 : mi_block_attention_lists_decode_fp8_f16)(
@@ -55,6 +68,7 @@ torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kn
 #undef MI_LISTS_HEAD
 #undef MI_LISTS_OPERANDS
 #undef MI_LISTS_OUT
+#undef MI_LISTS_TREE
   check_status(st, what);
   return out;
 }
@@ -89,4 +103,39 @@ torch::Tensor block_attention_lists_decode_paged_fp8(torch::Tensor block_ids, to
                                                      torch::Tensor lse) {
   return block_attention_decode_lists_impl("block_attention_lists_decode_paged_fp8", "k_pages", "v_pages", true, block_ids, block_counts,
                                            q, k_pages, v_pages, &block_table, k_lens, scale, k_scale, v_scale, chunk, out, lse);
+}
+
+// … with a tree mask (DESIGN.md §3.34): the four bindings above with `tree_mask` int64 [B, T] or [T] before chunk
+torch::Tensor block_attention_tree_decode_lists(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q, torch::Tensor k,
+                                                torch::Tensor v, torch::Tensor k_lens, double scale, torch::Tensor tree_mask,
+                                                int64_t chunk, torch::Tensor out, torch::Tensor lse) {
+  return block_attention_decode_lists_impl("block_attention_tree_decode_lists", "k", "v", false, block_ids, block_counts, q, k, v,
+                                           nullptr, k_lens, scale, c10::nullopt, c10::nullopt, chunk, out, lse, &tree_mask);
+}
+
+torch::Tensor block_attention_tree_decode_lists_paged(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q,
+                                                      torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table,
+                                                      torch::Tensor k_lens, double scale, torch::Tensor tree_mask, int64_t chunk,
+                                                      torch::Tensor out, torch::Tensor lse) {
+  return block_attention_decode_lists_impl("block_attention_tree_decode_lists_paged", "k_pages", "v_pages", false, block_ids,
+                                           block_counts, q, k_pages, v_pages, &block_table, k_lens, scale, c10::nullopt, c10::nullopt,
+                                           chunk, out, lse, &tree_mask);
+}
+
+torch::Tensor block_attention_tree_lists_decode_fp8(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q, torch::Tensor k,
+                                                    torch::Tensor v, torch::Tensor k_lens, double scale,
+                                                    c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale,
+                                                    torch::Tensor tree_mask, int64_t chunk, torch::Tensor out, torch::Tensor lse) {
+  return block_attention_decode_lists_impl("block_attention_tree_lists_decode_fp8", "k", "v", true, block_ids, block_counts, q, k, v,
+                                           nullptr, k_lens, scale, k_scale, v_scale, chunk, out, lse, &tree_mask);
+}
+
+torch::Tensor block_attention_tree_lists_decode_paged_fp8(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q,
+                                                          torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table,
+                                                          torch::Tensor k_lens, double scale, c10::optional<torch::Tensor> k_scale,
+                                                          c10::optional<torch::Tensor> v_scale, torch::Tensor tree_mask, int64_t chunk,
+                                                          torch::Tensor out, torch::Tensor lse) {
+  return block_attention_decode_lists_impl("block_attention_tree_lists_decode_paged_fp8", "k_pages", "v_pages", true, block_ids,
+                                           block_counts, q, k_pages, v_pages, &block_table, k_lens, scale, k_scale, v_scale, chunk, out,
+                                           lse, &tree_mask);
 }

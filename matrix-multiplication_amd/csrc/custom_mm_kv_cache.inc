@@ -187,6 +187,20 @@ uint16_t* bits16(const torch::Tensor& t) { return static_cast<uint16_t*>(t.data_
 #define MI_READ_SCALES r.ks.first, r.ks.second, r.vs.first, r.vs.second
 #define MI_READ_OUT bits16(out), s.D, s.T* s.D, lse.data_ptr<float>()
 
+// The tree mask of the block_attention_tree_… bindings (DESIGN.md §3.34) as the C ABI takes it: (pointer, rows) — contiguous int64 words [B, T], or
+// [T] for the whole batch, on `dev`, T <= 64; handed over as it is and never read back
+std::pair<const int64_t*, int32_t> tree_mask_operand(const char* what, const torch::Tensor& mask, int64_t B, int64_t T,
+                                                     const torch::Device& dev) {
+  TORCH_CHECK(mask.is_cuda(), "tree_mask must be a device (HIP) tensor; custom_mm has no CPU path");
+  TORCH_CHECK(mask.scalar_type() == torch::kInt64, "tree_mask must be int64, got ", mask.scalar_type());
+  check_same_device(what, dev, {&mask});
+  const bool shared = mask.dim() == 1;
+  TORCH_CHECK(mask.is_contiguous() && ((shared && mask.size(0) == T) || (mask.dim() == 2 && mask.size(0) == B && mask.size(1) == T)),
+              what, ": tree_mask must be a contiguous [B, T] = [", B, ", ", T, "] or [T] tensor");
+  TORCH_CHECK(T <= 64, what, ": a tree mask needs T <= 64, got T = ", T);
+  return {mask.data_ptr<int64_t>(), shared ? 1 : (int32_t)B};
+}
+
 // the writing calls' cache: of the source's dtype `dt` (a bit copy) or float8_e4m3fn; returns whether it is fp8
 bool written_cache_is_fp8(const char* what, const char* kname, const char* vname, torch::ScalarType dt, const torch::Tensor& k,
                           const torch::Tensor& v, const c10::optional<torch::Tensor>& k_scale,

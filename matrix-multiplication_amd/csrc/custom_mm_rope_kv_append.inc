@@ -14,7 +14,8 @@ torch::Tensor rope_kv_append_impl(const char* what, const char* kname, const cha
                                   const torch::Tensor& sin, const torch::Tensor& k, const torch::Tensor& v, const torch::Tensor* table,
                                   const torch::Tensor& k_lens, const c10::optional<torch::Tensor>& new_lens, torch::Tensor q_out,
                                   const c10::optional<torch::Tensor>& k_out, int64_t R, bool interleaved,
-                                  const c10::optional<torch::Tensor>& k_scale, const c10::optional<torch::Tensor>& v_scale) {
+                                  const c10::optional<torch::Tensor>& k_scale, const c10::optional<torch::Tensor>& v_scale,
+                                  const torch::Tensor* positions = nullptr) {
   const torch::ScalarType dt = value_dtype(what, {{"q", &q}, {"k_new", &k_new}, {"v_new", &v_new}, {"q_out", &q_out}}, true);
   TORCH_CHECK(is_lowp(dt), what, ": q must be bfloat16 or float16, got ", dt);
   TORCH_CHECK(!k_out.has_value() || k_out->scalar_type() == dt, what, ": k_out must have q's dtype ", dt, ", got ",
@@ -52,6 +53,12 @@ torch::Tensor rope_kv_append_impl(const char* what, const char* kname, const cha
     TORCH_CHECK(new_lens->is_contiguous() && new_lens->dim() == 1 && new_lens->numel() == B, what,
                 ": new_lens must be a contiguous int32 tensor of B = ", B, " entries");
   }
+  if (positions) {  // the *_pos bindings (DESIGN.md §3.34): the table row of every slot's rotation, handed over as it is
+    check_same_device(what, q.device(), {positions});
+    check_device_i32(*positions, "positions");
+    TORCH_CHECK(positions->is_contiguous() && positions->dim() == 2 && positions->size(0) == B && positions->size(1) == T, what,
+                ": positions must be a contiguous int32 [B, T] = [", B, ", ", T, "] tensor");
+  }
   check_source_strides(what, "q", q);
   check_source_strides(what, "k_new", k_new);
   check_source_strides(what, "v_new", v_new);
@@ -87,7 +94,22 @@ torch::Tensor rope_kv_append_impl(const char* what, const char* kname, const cha
   (int32_t) Hq, src(q), sq[0], sq[1], sq[2], dst16(q_out), sqo[0], sqo[1], sqo[2], src(k_new), skn[0], skn[1], skn[2], src(v_new),  \
       svn[0], svn[1], svn[2], ko, sko[0], sko[1], sko[2], cp, sp, (int32_t)Pmax, ld, (int32_t)R, (int32_t)interleaved,              \
       static_cast<CT*>(c.k), c.ldk, c.headK, c.outerK, static_cast<CT*>(c.v), c.ldv, c.headV, c.outerV, lens, lens_count, nl
-  if (!fp8) {
+  if (positions) {
+    const int32_t* pp = positions->data_ptr<int32_t>();
+    if (!fp8)
+      st = table ? (bf ? mi_rope_pos_kv_append_paged_bf16 : mi_rope_pos_kv_append_paged_f16)(
+                       items, (int32_t)Hkv, (int32_t)T, (int32_t)c.Smax, c.table, c.table_ld, (int32_t)c.P, (int32_t)c.page, (int32_t)D,
+                       MI_ROPE_CALL_OPERANDS(uint16_t), pp, stream)
+                 : (bf ? mi_rope_pos_kv_append_bf16 : mi_rope_pos_kv_append_f16)(items, (int32_t)Hkv, (int32_t)T, (int32_t)c.Smax,
+                                                                                 (int32_t)D, MI_ROPE_CALL_OPERANDS(uint16_t), pp, stream);
+    else
+      st = table ? (bf ? mi_rope_pos_kv_append_paged_fp8_bf16 : mi_rope_pos_kv_append_paged_fp8_f16)(
+                       items, (int32_t)Hkv, (int32_t)T, (int32_t)c.Smax, c.table, c.table_ld, (int32_t)c.P, (int32_t)c.page, (int32_t)D,
+                       MI_ROPE_CALL_OPERANDS(uint8_t), pp, ks.first, ks.second, vs.first, vs.second, stream)
+                 : (bf ? mi_rope_pos_kv_append_fp8_bf16 : mi_rope_pos_kv_append_fp8_f16)(
+                       items, (int32_t)Hkv, (int32_t)T, (int32_t)c.Smax, (int32_t)D, MI_ROPE_CALL_OPERANDS(uint8_t), pp, ks.first,
+                       ks.second, vs.first, vs.second, stream);
+  } else if (!fp8) {
     st = table ? (bf ? mi_rope_kv_append_paged_bf16 : mi_rope_kv_append_paged_f16)(
                      items, (int32_t)Hkv, (int32_t)T, (int32_t)c.Smax, c.table, c.table_ld, (int32_t)c.P, (int32_t)c.page, (int32_t)D,
                      MI_ROPE_CALL_OPERANDS(uint16_t), stream)
@@ -121,4 +143,22 @@ torch::Tensor rope_kv_append_paged(torch::Tensor q, torch::Tensor k_new, torch::
                                    c10::optional<torch::Tensor> v_scale) {
   return rope_kv_append_impl("rope_kv_append_paged", "k_pages", "v_pages", "page", q, k_new, v_new, cos, sin, k_pages, v_pages,
                              &block_table, k_lens, new_lens, q_out, k_out, rotary_dim, interleaved, k_scale, v_scale);
+}
+
+// … with explicit positions (DESIGN.md §3.34): `positions` int32 [B, T] after v_scale
+torch::Tensor rope_kv_append_pos(torch::Tensor q, torch::Tensor k_new, torch::Tensor v_new, torch::Tensor cos, torch::Tensor sin,
+                                 torch::Tensor k, torch::Tensor v, torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens,
+                                 torch::Tensor q_out, c10::optional<torch::Tensor> k_out, int64_t rotary_dim, bool interleaved,
+                                 c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale, torch::Tensor positions) {
+  return rope_kv_append_impl("rope_kv_append_pos", "k", "v", "batch", q, k_new, v_new, cos, sin, k, v, nullptr, k_lens, new_lens, q_out,
+                             k_out, rotary_dim, interleaved, k_scale, v_scale, &positions);
+}
+
+torch::Tensor rope_kv_append_paged_pos(torch::Tensor q, torch::Tensor k_new, torch::Tensor v_new, torch::Tensor cos, torch::Tensor sin,
+                                       torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table, torch::Tensor k_lens,
+                                       c10::optional<torch::Tensor> new_lens, torch::Tensor q_out, c10::optional<torch::Tensor> k_out,
+                                       int64_t rotary_dim, bool interleaved, c10::optional<torch::Tensor> k_scale,
+                                       c10::optional<torch::Tensor> v_scale, torch::Tensor positions) {
+  return rope_kv_append_impl("rope_kv_append_paged_pos", "k_pages", "v_pages", "page", q, k_new, v_new, cos, sin, k_pages, v_pages,
+                             &block_table, k_lens, new_lens, q_out, k_out, rotary_dim, interleaved, k_scale, v_scale, &positions);
 }

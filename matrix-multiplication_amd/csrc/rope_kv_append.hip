@@ -10,6 +10,10 @@
 //  * A token: its q rows and its k row are rotated by table row pos; q goes to q_out, k to k_out if given; k and v go into the
 //    cache iff 0 ≤ pos < Smax and, paged, the table entry lies in [0, pages) — kv_append.hip's condition — and are dropped
 //    otherwise.  Everything the rule does not write keeps its bytes.
+//  * Explicit positions (mi_rope_pos_kv_append_* — DESIGN.md §3.34): with `positions` int32 [B][T] the ROTATION of slot t takes table
+//    row positions[b][t] in the place of pos — a tree node is rotated by prefix length + depth while it is stored in slot t —,
+//    and the slot holds a token iff the conditions above hold AND 0 ≤ positions[b][t] < table_rows.  Where the rows go — q_out's
+//    and k_out's row t, the cache row pos — does not change; positions[b][t] = pos is the call without them, bit for bit.
 //  * Bits: for pair index i < R/2 the pair (a, b) is (x[i], x[i + R/2]) — the NeoX halves — or, interleaved, (x[2i], x[2i + 1]);
 //    with c = cos[pos, i], s = sin[pos, i] and the elements widened exactly:
 //        a' = fl32(fl32(a·c) − fl32(b·s))      b' = fl32(fl32(b·c) + fl32(a·s))
@@ -58,6 +62,7 @@ struct Args {
   int pages, page_shift;
   const float *k_scale, *v_scale;  // the fp8 forms: null is 1, a count of 1 one scale for all heads, else one per k / v head
   int k_scale_count, v_scale_count;
+  const int32_t* positions;  // null, or [B][T]: the table row slot t is rotated by, in the place of pos
 };
 
 // ---- the rotation -------------------------------------------------------------------------------------------------------------
@@ -122,7 +127,12 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(Args a) {
   const long pos = (long)a.k_lens[a.lens_each ? b : 0] - a.T + t;
   int n_new = a.T;
   if (a.new_lens) n_new = min(max(a.new_lens[b], 0), a.T);
-  const bool token = t >= a.T - n_new && pos >= 0 && pos < a.table_rows;
+  bool token = t >= a.T - n_new && pos >= 0 && pos < a.table_rows;
+  long turn = pos;  // the table row of the rotation
+  if (a.positions) {
+    turn = a.positions[(long)b * a.T + t];
+    token = token && turn >= 0 && turn < a.table_rows;
+  }
 
   if (!token) {  // zeros into q_out and k_out; nothing into the cache
     if (v_head) return;
@@ -156,11 +166,11 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(Args a) {
   uint4 x = *reinterpret_cast<const uint4*>(sp), y = make_uint4(0u, 0u, 0u, 0u);
   if (rotated) {
     if constexpr (INTER) {
-      const long at = pos * a.ld + (d >> 1);
+      const long at = turn * a.ld + (d >> 1);
       rotate_pairs<T>(x, *reinterpret_cast<const float4*>(a.cos + at), *reinterpret_cast<const float4*>(a.sin + at));
     } else {
       y = *reinterpret_cast<const uint4*>(sp + half);
-      const long at = pos * a.ld + d;
+      const long at = turn * a.ld + d;
       const float4 c[2] = {*reinterpret_cast<const float4*>(a.cos + at), *reinterpret_cast<const float4*>(a.cos + at + 4)};
       const float4 s[2] = {*reinterpret_cast<const float4*>(a.sin + at), *reinterpret_cast<const float4*>(a.sin + at + 4)};
       rotate_halves<T>(x, y, c, s);
@@ -214,6 +224,8 @@ struct Rope {  // what the entries take beyond the append's arguments
   int64_t ld;
   int32_t rotary_dim, interleaved;
   const int32_t* new_lens;
+  const int32_t* positions = nullptr;  // the *_pos entries: [B][T], and …
+  bool with_positions = false;         // … that the entry takes them: a null pointer is refused there
 };
 
 // Every check comes before the first HIP call.  page == 0: the contiguous cache; page > 0: a pool, as in kv_append.hip.
@@ -233,6 +245,7 @@ int rope_entry(int32_t items, int32_t heads, int32_t T_, int32_t Smax, int32_t D
   const int32_t B = items / heads;
   if (lens_count != 1 && lens_count != B) return MI_EINVAL;  // (q has no k / v head: one length per batch item, or one for all)
   if (!k_lens || !aligned4(k_lens) || !aligned4(ro.new_lens)) return MI_EINVAL;
+  if (ro.with_positions && (!ro.positions || !aligned4(ro.positions))) return MI_EINVAL;
   if (!operand_ok(ro.q.p, ro.q.ld, ro.q.head, ro.q.batch) || !operand_ok(ro.q_out.p, ro.q_out.ld, ro.q_out.head, ro.q_out.batch))
     return MI_EINVAL;
   if (!operand_ok(k_new.p, k_new.ld, k_new.head, k_new.batch) || !operand_ok(v_new.p, v_new.ld, v_new.head, v_new.batch)) return MI_EINVAL;
@@ -249,7 +262,7 @@ int rope_entry(int32_t items, int32_t heads, int32_t T_, int32_t Smax, int32_t D
   a.q = ro.q, a.k_new = k_new, a.v_new = v_new, a.q_out = ro.q_out, a.k_out = ro.k_out;
   a.cos = ro.cos, a.sin = ro.sin, a.ld = ro.ld;
   a.k = k, a.ldk = ldk, a.headK = headK, a.outerK = outerK, a.v = v, a.ldv = ldv, a.headV = headV, a.outerV = outerV;
-  a.k_lens = k_lens, a.lens_each = lens_count == 1 ? 0 : 1, a.new_lens = ro.new_lens;
+  a.k_lens = k_lens, a.lens_each = lens_count == 1 ? 0 : 1, a.new_lens = ro.new_lens, a.positions = ro.positions;
   if (paged && written) a.table = table, a.table_ld = table_ld, a.pages = pages, a.page_shift = __builtin_ctz((unsigned)page);
   if (FP8) a.k_scale = scales.k, a.k_scale_count = scales.k_count, a.v_scale = scales.v, a.v_scale_count = scales.v_count;
   return launch<T, FP8>(a, ro.interleaved != 0, s);
@@ -266,12 +279,15 @@ extern "C" {
       const float *sin, int32_t table_rows, int64_t ld, int32_t rotary_dim, int32_t interleaved, CT *k, int64_t ldk,              \
       int64_t headK, int64_t batchK, CT *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, \
       const int32_t *new_lens
-#define MI_ROPE_PASS                                                                                                            \
+// (the variadic tail: what the *_pos entries add to the Rope record)
+#define MI_ROPE_PASS_WITH(...)                                                                                                   \
   items, heads, T, Smax, D,                                                                                                     \
       Rope{q_heads,   Src{q, ldq, headQ, batchQ}, Dst{q_out, ldqo, headQo, batchQo}, Dst{k_out, ldko, headKo, batchKo}, cos, sin, \
-           table_rows, ld, rotary_dim, interleaved, new_lens},                                                                   \
+           table_rows, ld, rotary_dim, interleaved, new_lens __VA_ARGS__},                                                       \
       Src{k_new, ldkn, headKn, batchKn}, Src{v_new, ldvn, headVn, batchVn}, k, ldk, headK, batchK, v, ldv, headV, batchV, k_lens, \
       lens_count, static_cast<hipStream_t>(stream)
+#define MI_ROPE_PASS MI_ROPE_PASS_WITH()
+#define MI_ROPE_POS_PASS MI_ROPE_PASS_WITH(, positions, true)
 #define MI_ROPE_SIZES int32_t items, int32_t heads, int32_t T, int32_t Smax, int32_t D
 // (k, batchK and v, batchV stand for k_pages, pageK and v_pages, pageV of the header)  A page of 0 rows would name the
 // contiguous form: it is refused here like every page that is no power of two ≥ 16.
@@ -300,6 +316,34 @@ int mi_rope_kv_append_paged_fp8_bf16(MI_ROPE_PAGED_SIZES, MI_ROPE_ARGS(uint8_t),
 }
 int mi_rope_kv_append_paged_fp8_f16(MI_ROPE_PAGED_SIZES, MI_ROPE_ARGS(uint8_t), MI_ROPE_SCALE_ARGS, mi_stream_t stream) {
   return page < 16 ? MI_EINVAL : rope_entry<F16, true>(MI_ROPE_PASS, MI_ROPE_TABLE, MI_ROPE_SCALES);
+}
+
+// … with explicit positions: the eight entries above with `positions` int32 [B][T] after new_lens.  (`pos`
+// stands before `kv_append` in the name: the entries `mi_rope_kv_append…` are a closed family.)
+#define MI_ROPE_POS const int32_t *positions
+int mi_rope_pos_kv_append_bf16(MI_ROPE_SIZES, MI_ROPE_ARGS(uint16_t), MI_ROPE_POS, mi_stream_t stream) {
+  return rope_entry<Bf16, false>(MI_ROPE_POS_PASS);
+}
+int mi_rope_pos_kv_append_f16(MI_ROPE_SIZES, MI_ROPE_ARGS(uint16_t), MI_ROPE_POS, mi_stream_t stream) {
+  return rope_entry<F16, false>(MI_ROPE_POS_PASS);
+}
+int mi_rope_pos_kv_append_paged_bf16(MI_ROPE_PAGED_SIZES, MI_ROPE_ARGS(uint16_t), MI_ROPE_POS, mi_stream_t stream) {
+  return page < 16 ? MI_EINVAL : rope_entry<Bf16, false>(MI_ROPE_POS_PASS, MI_ROPE_TABLE);
+}
+int mi_rope_pos_kv_append_paged_f16(MI_ROPE_PAGED_SIZES, MI_ROPE_ARGS(uint16_t), MI_ROPE_POS, mi_stream_t stream) {
+  return page < 16 ? MI_EINVAL : rope_entry<F16, false>(MI_ROPE_POS_PASS, MI_ROPE_TABLE);
+}
+int mi_rope_pos_kv_append_fp8_bf16(MI_ROPE_SIZES, MI_ROPE_ARGS(uint8_t), MI_ROPE_POS, MI_ROPE_SCALE_ARGS, mi_stream_t stream) {
+  return rope_entry<Bf16, true>(MI_ROPE_POS_PASS, nullptr, 0, 0, 0, MI_ROPE_SCALES);
+}
+int mi_rope_pos_kv_append_fp8_f16(MI_ROPE_SIZES, MI_ROPE_ARGS(uint8_t), MI_ROPE_POS, MI_ROPE_SCALE_ARGS, mi_stream_t stream) {
+  return rope_entry<F16, true>(MI_ROPE_POS_PASS, nullptr, 0, 0, 0, MI_ROPE_SCALES);
+}
+int mi_rope_pos_kv_append_paged_fp8_bf16(MI_ROPE_PAGED_SIZES, MI_ROPE_ARGS(uint8_t), MI_ROPE_POS, MI_ROPE_SCALE_ARGS, mi_stream_t stream) {
+  return page < 16 ? MI_EINVAL : rope_entry<Bf16, true>(MI_ROPE_POS_PASS, MI_ROPE_TABLE, MI_ROPE_SCALES);
+}
+int mi_rope_pos_kv_append_paged_fp8_f16(MI_ROPE_PAGED_SIZES, MI_ROPE_ARGS(uint8_t), MI_ROPE_POS, MI_ROPE_SCALE_ARGS, mi_stream_t stream) {
+  return page < 16 ? MI_EINVAL : rope_entry<F16, true>(MI_ROPE_POS_PASS, MI_ROPE_TABLE, MI_ROPE_SCALES);
 }
 
 }  // extern "C"

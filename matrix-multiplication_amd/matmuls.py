@@ -1976,9 +1976,75 @@ def _check_cache_shape(what, names, q, k, v, block_table, base_text=_DECODE_SIZE
     return Smax
 
 
+_TREE_MAX_T = 64         # tokens of a tree-masked decode call: token t's int64 word names the draft keys it sees
+
+
+def _tree_binding(name: str) -> str:
+    '''The binding of a decode call with a tree mask: block_attention_tree_… for block_attention_… (the mask stands ahead of chunk).'''
+    return 'block_attention_tree_' + name[len('block_attention_'):]
+
+
+def _check_tree_mask(what, tree_mask, B, T, q):
+    '''The tree_mask operand of the eight decode calls: a contiguous int64 tensor [B, T], or [T] for the whole
+    batch, T ≤ 64 — ValueError for what it is, RuntimeError for another device than q's.  Returns it by name for
+    _check_on_device, which refuses host tensors; None: nothing.'''
+    if tree_mask is None:
+        return {}
+    if not isinstance(tree_mask, torch.Tensor) or tree_mask.layout != torch.strided:
+        raise ValueError(f'{what}: tree_mask must be None or a dense int64 tensor, got {type(tree_mask).__name__}')
+    if tree_mask.dtype != torch.int64:
+        raise ValueError(f'{what}: tree_mask must be int64 (one word of draft keys per token), got {tree_mask.dtype}')
+    if tuple(tree_mask.shape) not in ((B, T), (T,)):
+        raise ValueError(f'{what}: tree_mask must be [B, T] = [{B}, {T}] or [T] = [{T}], got {tuple(tree_mask.shape)}')
+    if T > _TREE_MAX_T:
+        raise ValueError(f'{what}: a tree mask needs T <= {_TREE_MAX_T} (a token\'s word has 64 bits), got T = {T}')
+    if not tree_mask.is_contiguous():
+        raise ValueError(f'{what}: tree_mask must be contiguous (it is handed to the kernel as it is), got strides '
+                         f'{tuple(tree_mask.stride())}')
+    if tree_mask.device != q.device:
+        raise RuntimeError(f'{what}: tree_mask is on {tree_mask.device} but q is on {q.device}: the mask is read by the kernel, on '
+                           f'q\'s device')
+    return {'tree_mask': tree_mask}
+
+
+def tree_attention_mask(parents: torch.Tensor):
+    '''The tree_mask of the decode calls from the parents of a drafted tree: `parents` is an int tensor [B, T] or [T], T ≤ 64, with
+    parents[t] ∈ [−1, t) — node t's parent among the drafted tokens, −1 for a child of the last cached token; nodes come in an
+    order in which every parent precedes its children.  Returns (mask, depth) on parents' device: mask int64 of parents' shape,
+    bit i of mask[…, t] set iff i is t or an ancestor of t — what tree_mask= takes as it is —, and depth int32, the number of
+    t's ancestors among the drafted tokens (a child of the cached prefix has depth 0), so that the rope position of node t is
+    (k_lens − T)[:, None] + depth.
+
+    torch operators only and no read-back: the call can be captured in a graph.  The precondition is checked on a HOST tensor
+    (ValueError); on a device tensor it is the caller's: an entry outside [−1, t) is read as −1 there.'''
+    what = 'tree_attention_mask'
+    if (not isinstance(parents, torch.Tensor) or parents.layout != torch.strided or parents.dtype.is_floating_point
+            or parents.dtype.is_complex or parents.dtype == torch.bool or parents.dim() not in (1, 2)):
+        raise ValueError(f'{what}: parents must be a dense integer tensor [B, T] or [T]')
+    T = parents.shape[-1]
+    if T > _TREE_MAX_T:
+        raise ValueError(f'{what}: T = {T} must be at most {_TREE_MAX_T}')
+    with torch.no_grad():
+        par = parents.detach().to(torch.int64)
+        steps = torch.arange(T, device=parents.device, dtype=torch.int64)
+        if parents.device.type == 'cpu' and bool(((par < -1) | (par >= steps)).any()):
+            raise ValueError(f'{what}: parents[t] must lie in [-1, t): a parent precedes its children, -1 is the cached prefix')
+        mask = torch.zeros(par.shape, device=parents.device, dtype=torch.int64)
+        depth = torch.zeros(par.shape, device=parents.device, dtype=torch.int32)
+        for t in range(T):  # T ≤ 64 steps of whole-batch operators: node t's word is its parent's with bit t
+            p = par[..., t]
+            has = (p >= 0) & (p < t)
+            at = p.clamp(0, max(t - 1, 0)).unsqueeze(-1)
+            up = torch.where(has, mask.gather(-1, at).squeeze(-1), torch.zeros_like(p))
+            bit = 1 << t if t < 63 else -(1 << 63)  # (bit 63 is the int64's sign)
+            mask[..., t] = up | bit
+            depth[..., t] = torch.where(has, depth.gather(-1, at).squeeze(-1) + 1, torch.zeros_like(depth[..., t]))
+    return mask, depth
+
+
 def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8=False, scales=(),
                                            block_table=None, *, sizes_text=None, max_group=_DECODE_MAX_GROUP,
-                                           max_grid=_DECODE_MAX_GRID, q_strided=False, new_lens=None, split=None):
+                                           max_grid=_DECODE_MAX_GRID, q_strided=False, new_lens=None, split=None, tree_mask=None):
     '''Every refusal of the four decode calls, before the first device call, split as _check_block_attention_operands splits
     them: ValueError for what an operand is, RuntimeError for operands that do not go together (mixed dtypes, host tensors /
     devices).  The cache-shape half is _check_cache_shape's (`names` as there), the layout half _check_decode_layout's.  fp8,
@@ -2014,6 +2080,7 @@ def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens,
         operands['new_lens'] = new_lens
     if fp8:
         operands.update(_check_fp8_scales(what, scales, Hkv, q))
+    operands.update(_check_tree_mask(what, tree_mask, B, T, q))
     _check_on_device(what, **operands)
     return Smax
 
@@ -2022,13 +2089,15 @@ _DECODE_BINDINGS = (('block_attention_decode', 'block_attention_decode_fp8'),  #
                     ('block_attention_decode_paged', 'block_attention_decode_paged_fp8'))
 
 
-def _decode(what, names, q, k, v, block_table, layout, k_lens, block, scale, chunk, k_scale, v_scale, fp8, return_lse):
+def _decode(what, names, q, k, v, block_table, layout, k_lens, block, scale, chunk, k_scale, v_scale, fp8, return_lse, tree_mask=None):
     '''The one body of the four decode calls: the checks, the defaults, the operands as the binding takes them, one binding
     call.  `names` as in _check_block_attention_decode_operands; block_table, k_scale and v_scale are looked at by the paged
-    and the fp8 forms only.'''
+    and the fp8 forms only.  tree_mask: None — the binding and the arguments of the call without it — or the mask, which goes
+    to the binding's block_attention_tree_… form (_tree_binding) ahead of chunk.'''
     paged = names[0] == 'k_pages'
     scales = (('k_scale', k_scale), ('v_scale', v_scale)) if fp8 else ()
-    Smax = _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8, scales, block_table)
+    Smax = _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8, scales, block_table,
+                                                  tree_mask=tree_mask)
     B, Hq, T, D = q.shape
     if scale is None:
         scale = 1.0 / float(D) ** 0.5
@@ -2043,14 +2112,16 @@ def _decode(what, names, q, k, v, block_table, layout, k_lens, block, scale, chu
         out = torch.empty_like(qc)
         lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
         if out.numel() > 0:
-            binding = getattr(custom_mm, _DECODE_BINDINGS[paged][fp8])
+            tree = () if tree_mask is None else (tree_mask.detach(),)
+            binding = getattr(custom_mm, _tree_binding(_DECODE_BINDINGS[paged][fp8]) if tree else _DECODE_BINDINGS[paged][fp8])
             fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
-            binding(offsets, columns, nnz, qc, k.detach(), v.detach(), *table, lens, float(scale), *fp8_scales, int(chunk), out, lse)
+            binding(offsets, columns, nnz, qc, k.detach(), v.detach(), *table, lens, float(scale), *fp8_scales, *tree, int(chunk), out,
+                    lse)
     return (out, lse) if return_lse else out
 
 
 def block_sparse_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
-                                  block: int = 64, scale=None, *, chunk=None, return_lse: bool = False):
+                                  block: int = 64, scale=None, *, chunk=None, return_lse: bool = False, tree_mask=None):
     '''Block-sparse attention of the T ≥ 1 newest tokens of every item against its key / value cache, on the matrix cores:
     q [B, Hq, T, D] (contiguous or made so: it is small), k and v [B, Hkv, Smax, D] — the cache, with the new tokens' keys
     and values already written —, all bfloat16 or all float16, Hq = G · Hkv with 1 ≤ G ≤ 16 (query head h reads k / v head
@@ -2083,9 +2154,20 @@ def block_sparse_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Ten
 
     Returns out [B, Hq, T, D] in q's dtype, or with return_lse=True (out, lse) with lse float32 [B, Hq, T].  There is NO
     autograd: the result does not require grad whatever the operands do.  scale defaults to 1/√D.  For T beyond a few
-    tokens — a prompt, or a chunk of one — use block_sparse_attention_prefill, whose tokens share their walks.'''
+    tokens — a prompt, or a chunk of one — use block_sparse_attention_prefill, whose tokens share their walks.
+
+    tree_mask (keyword only): None, or a contiguous int64 device tensor [B, T] — or [T] for the whole batch —
+    with T ≤ 64, for verifying a drafted TREE: the T new tokens are its nodes, stored in the window [base, base + T) of the
+    cache, base = clamp(k_lens[b], 0, Smax) − T.  Token t still stands at pos = base + t and sees key j iff the rule above
+    holds AND (j < base, or j == pos, or bit j − base of tree_mask[b, t] is set): the cached prefix, itself, and the draft keys
+    its word names — tree_attention_mask makes the words from the tree's parents.  Bits at or above t are never looked at; the
+    word (2 << t) − 1, or all ones, gives the bits of the call without a mask.  A hidden key is treated like a key beyond pos:
+    never loaded, its score −inf — NaN or inf in a hidden draft slot reaches no output.  Chunks, the deal to the waves, the
+    order of the merges, out and lse are unchanged.  The mask is handed over as it is and never read back: a captured graph
+    follows in-place updates.  ValueError for another dtype or shape, T > 64 or a non-contiguous mask, RuntimeError for a host
+    tensor or another device — before the first device call.'''
     return _decode('block_sparse_attention_decode', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, chunk, None, None, False,
-                   return_lse)
+                   return_lse, tree_mask=tree_mask)
 
 
 # --------------------------------------------------------------------------- #
@@ -2101,7 +2183,7 @@ def block_attention_decode_paged_takes(dtype, D: int, block: int, group: int, pa
 
 def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
                                         layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *, chunk=None,
-                                        return_lse: bool = False):
+                                        return_lse: bool = False, tree_mask=None):
     '''block_sparse_attention_decode over a PAGED cache: k_pages and v_pages [P, Hkv, page, D] are one pool of pages of
     `page` keys (a power of two ≥ 16, taken from the pool's shape) and block_table [B, W] maps the logical pages of every
     item to pool pages: key j of batch item b, k / v head h, is row j % page of head h of pool page block_table[b, j // page].
@@ -2122,9 +2204,9 @@ def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, 
     block_sparse_attention_decode with the same chunk on the cache gathered to [B, Hkv, Smax, D] — so they do not depend
     on P, on where the pages lie, or on `page`.  No atomics, no read-back: graph-capturable, and one captured graph keeps
     serving while k_lens, the pool and the block table are updated in place.  NO autograd.  For T beyond a few tokens use
-    block_sparse_attention_prefill_paged.'''
+    block_sparse_attention_prefill_paged.  tree_mask: as in block_sparse_attention_decode.'''
     return _decode('block_sparse_attention_decode_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens, block,
-                   scale, chunk, None, None, False, return_lse)
+                   scale, chunk, None, None, False, return_lse, tree_mask=tree_mask)
 
 
 # --------------------------------------------------------------------------- #
@@ -2219,7 +2301,7 @@ def kv_to_fp8(x: torch.Tensor, scale=None):
 
 def block_sparse_attention_decode_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
                                       block: int = 64, scale=None, *, k_scale=None, v_scale=None, chunk=None,
-                                      return_lse: bool = False):
+                                      return_lse: bool = False, tree_mask=None):
     '''block_sparse_attention_decode over an FP8 cache: q [B, Hq, T, D] bfloat16 or float16, k and v [B, Hkv, Smax, D]
     torch.float8_e4m3fn — the OCP encoding, gfx950's native one; float8_e4m3fnuz, float8_e5m2 and uint8 raise ValueError —
     with the real key k8 · k_scale[h] and the real value v8 · v_scale[h].  Everything else — the visibility rule, the
@@ -2241,14 +2323,14 @@ def block_sparse_attention_decode_fp8(q: torch.Tensor, k: torch.Tensor, v: torch
     and lse are bit for bit those of block_sparse_attention_decode on k.to(q.dtype), v.to(q.dtype) with the same chunk;
     with k_scale = s for all heads and v_scale = 2^n, out is that call\'s result at scale\' = float32(scale) · float32(s)
     times 2^n, and lse that call\'s.  Nothing beyond pos, in an unlisted block or between the rows is loaded: a NaN byte
-    there reaches no output.  For T beyond a few tokens use block_sparse_attention_prefill_fp8.'''
+    there reaches no output.  For T beyond a few tokens use block_sparse_attention_prefill_fp8.  tree_mask: as in block_sparse_attention_decode.'''
     return _decode('block_sparse_attention_decode_fp8', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, chunk, k_scale, v_scale,
-                   True, return_lse)
+                   True, return_lse, tree_mask=tree_mask)
 
 
 def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
                                             layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *,
-                                            k_scale=None, v_scale=None, chunk=None, return_lse: bool = False):
+                                            k_scale=None, v_scale=None, chunk=None, return_lse: bool = False, tree_mask=None):
     '''block_sparse_attention_decode_paged over an FP8 pool: k_pages and v_pages [P, Hkv, page, D] torch.float8_e4m3fn
     with k_scale / v_scale as in block_sparse_attention_decode_fp8, everything else — the table, the pages (a power of two
     ≥ 16 keys), entries outside [0, P) hiding their page, the refusals — as in block_sparse_attention_decode_paged
@@ -2258,9 +2340,9 @@ def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tens
     Bits: for in-range tables, out and lse are bit for bit those of block_sparse_attention_decode_fp8 with the same chunk
     and scales on the gathered cache; with both scales None, those of block_sparse_attention_decode_paged on the pool
     widened to q\'s type.  Nothing in an invalid page is loaded.  Graph-capturable while k_lens, the pool, the table and
-    the scale tensors are updated in place.  For T beyond a few tokens use block_sparse_attention_prefill_paged_fp8.'''
+    the scale tensors are updated in place.  For T beyond a few tokens use block_sparse_attention_prefill_paged_fp8.  tree_mask: as in block_sparse_attention_decode.'''
     return _decode('block_sparse_attention_decode_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens,
-                   block, scale, chunk, k_scale, v_scale, True, return_lse)
+                   block, scale, chunk, k_scale, v_scale, True, return_lse, tree_mask=tree_mask)
 
 
 # --------------------------------------------------------------------------- #
@@ -2619,6 +2701,109 @@ def kv_cache_append_paged(k_new: torch.Tensor, v_new: torch.Tensor, k_pages: tor
 
 
 # --------------------------------------------------------------------------- #
+# compaction after a speculative step: the accepted path's rows to the front of the drafted window
+# --------------------------------------------------------------------------- #
+
+_COMPACT_DTYPES = (torch.bfloat16, torch.float16, torch.float8_e4m3fn)
+
+
+def _check_kv_compact_operands(what, names, k, v, k_lens, accept, accept_counts, T, block_table=None):
+    '''Every refusal of kv_cache_compact and kv_cache_compact_paged before the first device call: ValueError for what an
+    operand is, RuntimeError for operands that do not go together.  The cache operands' checks are kv_cache_append's.'''
+    kn, vn = names
+    paged = kn == 'k_pages'
+    for name, t in ((kn, k), (vn, v)):
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided:
+            raise ValueError(f'{what}: {name} must be a dense tensor')
+    fp8 = k.dtype.itemsize == 1 or v.dtype.itemsize == 1
+    if fp8:
+        _check_fp8_cache(what, ((kn, k), (vn, v)))
+    else:
+        if k.dtype not in _LOWP:
+            raise ValueError(f'{what}: {kn} must be bfloat16, float16 or float8_e4m3fn, got {k.dtype}')
+        if v.dtype != k.dtype:
+            raise RuntimeError(f'{what}: {kn} is {k.dtype} but {vn} is {v.dtype}: the cache must have one dtype')
+    if not _is_int(T) or T < 1 or T > _TREE_MAX_T:
+        raise ValueError(f'{what}: T must be an int in [1, {_TREE_MAX_T}] — the drafted slots of the step —, got {T!r}')
+    for name, t in (('accept', accept), ('accept_counts', accept_counts)):
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided or t.dtype != torch.int32:
+            raise ValueError(f'{what}: {name} must be a dense int32 tensor (it is handed over as it is)')
+    if k.dim() != 4 or v.dim() != 4:
+        raise ValueError(f'{what}: {kn} and {vn} must be {"[P, Hkv, page, D]" if paged else "[B, Hkv, Smax, D]"}, got {k.dim()}-d and '
+                         f'{v.dim()}-d')
+    if accept.dim() != 2 or accept.shape[1] != T or not accept.is_contiguous():
+        raise ValueError(f'{what}: accept must be a contiguous [B, T] = [B, {T}] tensor, got {tuple(accept.shape)}')
+    B = accept.shape[0]
+    Hkv, D = k.shape[1], k.shape[3]
+    if tuple(accept_counts.shape) != (B,) or not accept_counts.is_contiguous():
+        raise ValueError(f'{what}: accept_counts must be a contiguous [B] = [{B}] tensor, got {tuple(accept_counts.shape)}')
+    if D not in _BLOCK_HEAD_SIZES:
+        raise ValueError(f'{what}: head size D must be 32, 64, 96 or 128, got {D}')
+    if not paged and k.shape[0] != B:
+        raise ValueError(f'{what}: accept of shape {tuple(accept.shape)} needs {kn} ({B}, "Hkv", "Smax", "D"), got {tuple(k.shape)}')
+    if tuple(v.shape) != tuple(k.shape):
+        raise ValueError(f'{what}: {vn} must be a dense tensor with {kn}\'s shape {tuple(k.shape)}, got {tuple(v.shape)}')
+    tensors = {}
+    if paged:
+        page = k.shape[2]
+        if not _page_ok(page):
+            raise ValueError(f'{what}: the pool\'s pages must hold a power of two >= {_DECODE_MIN_PAGE} rows, got page = {page}')
+        Smax = _check_block_table(what, block_table, B) * page
+        tensors['block_table'] = block_table
+    else:
+        Smax = k.shape[2]
+    if B * Hkv > _DECODE_MAX_GRID or Smax >= 2 ** 31:
+        raise ValueError(f'{what}: B·Hkv = {B * Hkv} must be at most {_DECODE_MAX_GRID} and Smax = {Smax} fit an int32')
+    _check_k_lens(what, k_lens, B)
+    outer = 'page' if paged else 'batch'
+    _check_cache_strides(what, kn, k, D, outer, 16 if fp8 else 8)
+    _check_cache_strides(what, vn, v, D, outer, 16 if fp8 else 8)
+    _check_on_device(what, **{kn: k, vn: v}, **tensors, k_lens=k_lens, accept=accept, accept_counts=accept_counts)
+
+
+def kv_cache_compact(k: torch.Tensor, v: torch.Tensor, k_lens: torch.Tensor, accept: torch.Tensor, accept_counts: torch.Tensor,
+                     T: int) -> None:
+    '''After a speculative step: moves the accepted path's key / value rows to the front of the window of the T drafted slots,
+    IN PLACE and in one launch for k and v.  k and v [B, Hkv, Smax, D] are the cache of kv_cache_append with its rules —
+    bfloat16, float16 or torch.float8_e4m3fn, read and written through their own strides, never copied —, D ∈ {32, 64, 96, 128},
+    1 ≤ T ≤ 64.  k_lens (int32 / int64 device tensor [B] or 0-d, never read back) STILL COUNTS the T drafted slots; accept is an
+    int32 device tensor [B, T] of offsets into the window, accept_counts int32 [B], both contiguous and handed over as they are.
+
+    With base = k_lens[b] − T and n = clamp(accept_counts[b], 0, T): for i < n, row base + i of every k / v head of item b
+    becomes the OLD row base + accept[b, i] — gather semantics: every source row is read before any is written, so the path
+    [1, 2, 3] moves rows 1, 2, 3 to 0, 1, 2.  A row whose offset lies outside [0, T), or whose source or destination row lies
+    outside [0, Smax), is left unwritten; rows at or beyond n, and everything else, keep their bytes.  Rows are bit copies (an
+    fp8 cache keeps its scales).  k_lens is NOT written: shrink it on the device, lens −= T − n; key_block_bounds(…, last=T)
+    after the shrink refreshes the bounds of the blocks that were touched.
+
+    No atomics, no read-back: `lens += T; rope_kv_cache_append(positions=…); decode(tree_mask=…); kv_cache_compact(…);
+    lens −= rejected` can be captured in one graph.  Returns None.  NO autograd.'''
+    what = 'kv_cache_compact'
+    _check_kv_compact_operands(what, ('k', 'v'), k, v, k_lens, accept, accept_counts, T)
+    if k.numel() == 0:
+        return None
+    with torch.no_grad():
+        custom_mm.kv_compact(k.detach(), v.detach(), _lens_i32(k_lens), accept, accept_counts, int(T))
+    return None
+
+
+def kv_cache_compact_paged(k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor, k_lens: torch.Tensor,
+                           accept: torch.Tensor, accept_counts: torch.Tensor, T: int) -> None:
+    '''kv_cache_compact over a PAGED cache: k_pages, v_pages [P, Hkv, page, D] and block_table [B, W] are the operands of
+    kv_cache_append_paged with its rules (Smax = W · page).  Row j of item b is row j % page of pool page
+    block_table[b, j // page]; a row behind an entry outside [0, P) is neither read nor written.  Items that share a page they
+    both write are the caller's business.  Everything else is kv_cache_compact's.'''
+    what = 'kv_cache_compact_paged'
+    _check_kv_compact_operands(what, ('k_pages', 'v_pages'), k_pages, v_pages, k_lens, accept, accept_counts, T, block_table)
+    if k_pages.numel() == 0 or block_table.numel() == 0:
+        return None
+    with torch.no_grad():
+        custom_mm.kv_compact_paged(k_pages.detach(), v_pages.detach(), _table_i32(block_table), _lens_i32(k_lens), accept,
+                                   accept_counts, int(T))
+    return None
+
+
+# --------------------------------------------------------------------------- #
 # the fused rotary embedding + KV-cache append: the step in front of the append, in its launch (DESIGN.md §3.22)
 # --------------------------------------------------------------------------- #
 
@@ -2702,9 +2887,25 @@ def _check_rope_operands(what, q, k_new, cos, sin, rotary_dim, new_lens, q_out, 
     return R, tensors
 
 
+def _check_rope_positions(what, positions, q):
+    '''The positions operand of the rope calls: an int32 / int64 tensor [B, T] — ValueError for what it is,
+    RuntimeError for another device than q's.  Returns it by name for _check_on_device; None: nothing.'''
+    if positions is None:
+        return {}
+    if not isinstance(positions, torch.Tensor) or positions.layout != torch.strided or positions.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'{what}: positions must be None or a dense int32 / int64 tensor')
+    if q.dim() == 4 and tuple(positions.shape) != (q.shape[0], q.shape[2]):
+        raise ValueError(f'{what}: positions must be [B, T] = [{q.shape[0]}, {q.shape[2]}], got {tuple(positions.shape)}')
+    if positions.device != q.device:
+        raise RuntimeError(f'{what}: positions is on {positions.device} but q is on {q.device}: the positions are read by the '
+                           f'kernel, on q\'s device')
+    return {'positions': positions}
+
+
 def _rope_kv_cache_append(what, names, q, k_new, v_new, cos, sin, k, v, block_table, k_lens, interleaved, rotary_dim, new_lens,
-                          q_out, k_out, k_scale, v_scale):
-    '''Both forms of the fused call: the checks, then the one binding call.'''
+                          q_out, k_out, k_scale, v_scale, positions=None):
+    '''Both forms of the fused call: the checks, then the one binding call — with positions the *_pos binding, which takes them
+    as an int32 [B, T] tensor after the arguments of the call without them.'''
     paged = block_table is not None or names[0] == 'k_pages'
     _check_lowp_operands(what, (('q', q), ('k_new', k_new), ('v_new', v_new)), _ROPE_SIZES_TEXT)
     if not isinstance(interleaved, bool):
@@ -2713,6 +2914,7 @@ def _rope_kv_cache_append(what, names, q, k_new, v_new, cos, sin, k, v, block_ta
     R, tensors = None, {}
     if k_new.dim() == 4 and k_new.shape[3] in _BLOCK_HEAD_SIZES and k_new.shape[2] >= 1 and k_new.shape[1] >= 1:
         R, tensors = _check_rope_operands(what, q, k_new, cos, sin, rotary_dim, new_lens, q_out, k_out)
+    tensors.update(_check_rope_positions(what, positions, q))  # (what it is: ahead of the cache's device check)
     fp8 = _check_kv_append_operands(what, names, k_new, v_new, k, v, k_lens, scales, block_table)
     _check_on_device(what, k_new=k_new, q=q, **tensors)
     if q.numel() == 0:
@@ -2724,16 +2926,20 @@ def _rope_kv_cache_append(what, names, q, k_new, v_new, cos, sin, k, v, block_ta
         ks, vs = (_fp8_scale(k_scale, k_new.device), _fp8_scale(v_scale, k_new.device)) if fp8 else (None, None)
         head = (q.detach(), k_new.detach(), v_new.detach(), cos.detach(), sin.detach(), k.detach(), v.detach())
         tail = (lens, news, out.detach(), None if k_out is None else k_out.detach(), R, interleaved, ks, vs)
+        if positions is not None:  # (an int32 tensor is handed over as it is, an int64 one narrowed on the device)
+            tail += (positions.detach().to(torch.int32).contiguous(),)
         if paged:
-            custom_mm.rope_kv_append_paged(*head, _table_i32(block_table), *tail)
+            binding = custom_mm.rope_kv_append_paged if positions is None else custom_mm.rope_kv_append_paged_pos
+            binding(*head, _table_i32(block_table), *tail)
         else:
-            custom_mm.rope_kv_append(*head, *tail)
+            binding = custom_mm.rope_kv_append if positions is None else custom_mm.rope_kv_append_pos
+            binding(*head, *tail)
     return out
 
 
 def rope_kv_cache_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
                          k: torch.Tensor, v: torch.Tensor, k_lens: torch.Tensor, *, interleaved: bool = False, rotary_dim=None,
-                         new_lens=None, q_out=None, k_out=None, k_scale=None, v_scale=None) -> torch.Tensor:
+                         new_lens=None, q_out=None, k_out=None, k_scale=None, v_scale=None, positions=None) -> torch.Tensor:
     '''The rotary embedding (RoPE) of q and of the new keys FUSED INTO kv_cache_append: in ONE launch q [B, Hq, T, D] and
     k_new [B, Hkv, T, D] are rotated by position, the rotated keys and v_new [B, Hkv, T, D] are written into the cache k, v
     [B, Hkv, Smax, D] — copied, or quantised into a float8_e4m3fn cache — and the rotated q is returned.  q, k_new, v_new:
@@ -2773,22 +2979,29 @@ def rope_kv_cache_append(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tens
     round-to-nearest-even to the source dtype: operation for operation what torch gives ON THE CPU for
     (a.float() * c − b.float() * s).to(dtype).  A NaN result is a NaN of unspecified payload.  Elements d ≥ R of q and k, and
     all of v, are bit copies.  An fp8 cache receives kv_cache_append\'s bytes of the rotated k after its rounding to the
-    source dtype: every cache form is byte for byte what kv_cache_append(k_rot, v_new, …) leaves.'''
+    source dtype: every cache form is byte for byte what kv_cache_append(k_rot, v_new, …) leaves.
+
+    positions (keyword only): None, or an int32 / int64 device tensor [B, T] (int32 contiguous: handed over as it
+    is; never read back).  Slot t of item b is then ROTATED — its k row and its q rows — with row positions[b, t] of cos / sin
+    in the place of row pos, and still WRITTEN where the call without positions writes it: q_out\'s and k_out\'s row t, the
+    cache row pos.  The slot holds a token iff the conditions above hold and 0 ≤ positions[b, t] < Pmax; otherwise zero rows
+    and nothing into the cache, as above.  The arithmetic is unchanged; positions[b, t] = pos gives the bits of the call
+    without them.  For a drafted tree: positions = (k_lens − T)[:, None] + depth, depth from tree_attention_mask.'''
     return _rope_kv_cache_append('rope_kv_cache_append', ('k', 'v'), q, k_new, v_new, cos, sin, k, v, None, k_lens, interleaved,
-                                 rotary_dim, new_lens, q_out, k_out, k_scale, v_scale)
+                                 rotary_dim, new_lens, q_out, k_out, k_scale, v_scale, positions)
 
 
 def rope_kv_cache_append_paged(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
                                k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor, k_lens: torch.Tensor, *,
                                interleaved: bool = False, rotary_dim=None, new_lens=None, q_out=None, k_out=None, k_scale=None,
-                               v_scale=None) -> torch.Tensor:
+                               v_scale=None, positions=None) -> torch.Tensor:
     '''rope_kv_cache_append into a PAGED cache: k_pages, v_pages [P, Hkv, page, D] and block_table [B, W] are the operands of
     kv_cache_append_paged with its checks (rope_kv_cache_append_paged_takes).  A token\'s rotated k and its v are written to
     row pos % page of pool page block_table[b, pos // page] iff 0 ≤ pos < W · page and that entry lies in [0, P); otherwise
-    they are dropped — q is still rotated.  Everything else — the tables, new_lens, q_out, k_out, the bits — is
+    they are dropped — q is still rotated.  Everything else — the tables, new_lens, positions, q_out, k_out, the bits — is
     rope_kv_cache_append\'s: bit for bit the flat call on the gathered cache.'''
     return _rope_kv_cache_append('rope_kv_cache_append_paged', ('k_pages', 'v_pages'), q, k_new, v_new, cos, sin, k_pages, v_pages,
-                                 block_table, k_lens, interleaved, rotary_dim, new_lens, q_out, k_out, k_scale, v_scale)
+                                 block_table, k_lens, interleaved, rotary_dim, new_lens, q_out, k_out, k_scale, v_scale, positions)
 
 
 # --------------------------------------------------------------------------- #
@@ -3011,7 +3224,7 @@ def select_key_blocks(q: torch.Tensor, bounds: torch.Tensor, k_lens: torch.Tenso
 
 
 def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse, k_scale=None,
-                     v_scale=None, fp8=False):
+                     v_scale=None, fp8=False, tree_mask=None):
     '''The one body of the four list-source decode calls: _decode's checks minus the layout ones, the lists' own, one binding
     call with the caller's lists as they are.  fp8: a float8_e4m3fn cache with the scale operands of _decode(…, fp8=True).'''
     kn, vn = names
@@ -3054,6 +3267,7 @@ def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts,
     operands.update(block_ids=block_ids, block_counts=block_counts, k_lens=k_lens)
     if fp8:
         operands.update(_check_fp8_scales(what, (('k_scale', k_scale), ('v_scale', v_scale)), Hkv, q))
+    operands.update(_check_tree_mask(what, tree_mask, B, T, q))
     _check_on_device(what, **operands)
     if scale is None:
         scale = 1.0 / float(D) ** 0.5
@@ -3066,16 +3280,17 @@ def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts,
         out = torch.empty_like(qc)
         lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
         if out.numel() > 0:
-            binding = getattr(custom_mm, _SELECTED_BINDINGS[paged][fp8])
+            tree = () if tree_mask is None else (tree_mask.detach(),)
+            binding = getattr(custom_mm, _tree_binding(_SELECTED_BINDINGS[paged][fp8]) if tree else _SELECTED_BINDINGS[paged][fp8])
             fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
             binding(block_ids.detach(), block_counts.detach(), qc, k.detach(), v.detach(), *table, lens, float(scale), *fp8_scales,
-                    int(chunk), out, lse)
+                    *tree, int(chunk), out, lse)
     return (out, lse) if return_lse else out
 
 
 def block_sparse_attention_decode_selected(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
                                            block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, chunk=None,
-                                           return_lse: bool = False):
+                                           return_lse: bool = False, tree_mask=None):
     '''block_sparse_attention_decode with the blocks of every token given as a LIST — the output of select_key_blocks — in the
     place of a CSR layout: q [B, Hq, T, D], k and v [B, Hkv, Smax, D] and k_lens as in that call (64-key blocks, Smax a
     multiple of 64, the cache read through its own strides and never copied), block_ids int32 [B, Hkv, T, K] and
@@ -3092,20 +3307,21 @@ def block_sparse_attention_decode_selected(q: torch.Tensor, k: torch.Tensor, v: 
     Bits: for token t, out and lse are bit for bit those of block_sparse_attention_decode with T = 1, k_lens = pos + 1, the
     same chunk and a (B, Hkv) layout whose row pos // 64 lists the same blocks in the same order — a row's bits depend on
     its list, pos and chunk only.  Returns out [B, Hq, T, D], or (out, lse) with return_lse=True.  No atomics, no read-back:
-    graph-capturable.  NO autograd.  An fp8 cache is block_sparse_attention_decode_selected_fp8's.'''
+    graph-capturable.  NO autograd.  An fp8 cache is block_sparse_attention_decode_selected_fp8's.  tree_mask: as in block_sparse_attention_decode, over the lists.'''
     return _decode_selected('block_sparse_attention_decode_selected', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens, scale,
-                            chunk, return_lse)
+                            chunk, return_lse, tree_mask=tree_mask)
 
 
 def block_sparse_attention_decode_selected_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
                                                  block_table: torch.Tensor, block_ids: torch.Tensor, block_counts: torch.Tensor,
-                                                 k_lens: torch.Tensor, scale=None, *, chunk=None, return_lse: bool = False):
+                                                 k_lens: torch.Tensor, scale=None, *, chunk=None, return_lse: bool = False,
+                                                 tree_mask=None):
     '''block_sparse_attention_decode_selected over a PAGED cache: k_pages, v_pages [P, Hkv, page, D] and block_table [B, W]
     are the operands of block_sparse_attention_decode_paged with its rules (Smax = W · page; an entry outside [0, P) hides
     its page's keys); the lists are indexed by logical 64-key blocks, whatever `page` is.  Bit for bit the contiguous call
-    on the gathered cache (block_attention_decode_selected_paged_takes).'''
+    on the gathered cache (block_attention_decode_selected_paged_takes).  tree_mask: as in block_sparse_attention_decode, over the lists.'''
     return _decode_selected('block_sparse_attention_decode_selected_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
-                            block_ids, block_counts, k_lens, scale, chunk, return_lse)
+                            block_ids, block_counts, k_lens, scale, chunk, return_lse, tree_mask=tree_mask)
 
 
 # --------------------------------------------------------------------------- #
@@ -3164,7 +3380,7 @@ def key_block_bounds_paged_fp8(k_pages: torch.Tensor, block_table: torch.Tensor,
 
 def block_sparse_attention_decode_selected_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
                                                block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, k_scale=None,
-                                               v_scale=None, chunk=None, return_lse: bool = False):
+                                               v_scale=None, chunk=None, return_lse: bool = False, tree_mask=None):
     '''block_sparse_attention_decode_selected over an FP8 cache: q [B, Hq, T, D] bfloat16 or float16, k and v
     [B, Hkv, Smax, D] torch.float8_e4m3fn with k_scale / v_scale as in block_sparse_attention_decode_fp8 — None (= 1), a
     float, or a float32 device tensor of shape (), (1,) or (Hkv,), read by the kernel from device memory, so a captured
@@ -3178,20 +3394,20 @@ def block_sparse_attention_decode_selected_fp8(q: torch.Tensor, k: torch.Tensor,
 
     With lists from select_key_blocks over key_block_bounds_fp8: the selection ranks by the unscaled widened keys, which
     for positive per-head k scales is the ranking of the real keys (see key_block_bounds_fp8).  No atomics, no read-back:
-    graph-capturable.  NO autograd.'''
+    graph-capturable.  NO autograd.  tree_mask: as in block_sparse_attention_decode, over the lists.'''
     return _decode_selected('block_sparse_attention_decode_selected_fp8', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens,
-                            scale, chunk, return_lse, k_scale, v_scale, True)
+                            scale, chunk, return_lse, k_scale, v_scale, True, tree_mask=tree_mask)
 
 
 def block_sparse_attention_decode_selected_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
                                                      block_table: torch.Tensor, block_ids: torch.Tensor, block_counts: torch.Tensor,
                                                      k_lens: torch.Tensor, scale=None, *, k_scale=None, v_scale=None, chunk=None,
-                                                     return_lse: bool = False):
+                                                     return_lse: bool = False, tree_mask=None):
     '''block_sparse_attention_decode_selected_fp8 over a PAGED cache: k_pages, v_pages [P, Hkv, page, D] torch.float8_e4m3fn
     and block_table [B, W] as in block_sparse_attention_decode_paged_fp8; the lists are indexed by logical 64-key blocks.
-    Bit for bit the contiguous fp8 call on the gathered bytes (block_attention_decode_selected_paged_fp8_takes).'''
+    Bit for bit the contiguous fp8 call on the gathered bytes (block_attention_decode_selected_paged_fp8_takes).  tree_mask: as in block_sparse_attention_decode, over the lists.'''
     return _decode_selected('block_sparse_attention_decode_selected_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages,
-                            block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse, k_scale, v_scale, True)
+                            block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse, k_scale, v_scale, True, tree_mask=tree_mask)
 
 
 # --------------------------------------------------------------------------- #
