@@ -1609,6 +1609,54 @@ int mi_block_attention_tree_decode_lists_paged_fp8_f16(MI_TREE_DECODE_LISTS, MI_
                                                        MI_TREE_DECODE_SCALES, MI_TREE_DECODE_OUT);
 
 /* ------------------------------------------------------------------------ *
+ * Sliding windows and sink keys for decode: the sixteen plain decode entries — the layout entries
+ * mi_block_attention_decode{,_paged}{,_fp8}_T and the list entries mi_block_attention_decode_lists{,_paged}_T,
+ * mi_block_attention_lists_decode{,_paged}_fp8_T — as mi_block_attention_window_decode{,_lists}{,_paged}{,_fp8}_T, with two
+ * parameters between `scale` (or the four scale parameters) and `out`:
+ *   window  W ≥ 1: the token sees its last W keys, ITSELF INCLUDED (HF's sliding_window, FlashAttention's window_size = (W − 1, 0))
+ *   sink    S ≥ 0: … and the first S keys of the cache (StreamingLLM's sink tokens)
+ * Token t stands at pos = clamp(k_len, 0, Smax) − T + t, as in the parents, and sees key j iff the parent's rule holds (j ≤ pos,
+ * its list names block j / 64, its page is valid) AND (j > pos − W or j < S).  A hidden key is treated like a key beyond pos:
+ * never loaded, staged as zeros, its score −inf — a NaN in a hidden slot reaches no output.  A listed block J with 64 J ≥ S and
+ * 64 J + 63 ≤ pos − W is wholly hidden and is skipped like a block beyond pos: it keeps its list position, so chunks, the deal to
+ * the waves, the order of the merges, the workspace, out and lse are the parent's.  W = 2³¹ − 1, or S ≥ Smax, gives the parent
+ * entry's bits.  A token that sees nothing has a zero row and lse −inf.
+ * Validation before any HIP call: window < 1 or sink < 0 — MI_EINVAL, before anything else; then what the parent refuses.
+ * (`window` stands before `decode` in the name: the entries `mi_block_attention_decode…` are a closed family.)
+ * ------------------------------------------------------------------------ */
+#define MI_WINDOW_DECODE_OUT                                                                                                    \
+  int32_t window, int32_t sink, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes, \
+      mi_stream_t stream
+int mi_block_attention_window_decode_bf16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_OPERANDS(uint16_t), MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_f16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_OPERANDS(uint16_t), MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_paged_bf16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint16_t),
+                                                MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_paged_f16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint16_t),
+                                               MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_fp8_bf16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_OPERANDS(uint8_t), MI_TREE_DECODE_SCALES,
+                                              MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_fp8_f16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_OPERANDS(uint8_t), MI_TREE_DECODE_SCALES,
+                                             MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_paged_fp8_bf16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint8_t),
+                                                    MI_TREE_DECODE_SCALES, MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_paged_fp8_f16(MI_TREE_DECODE_LAYOUT, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint8_t),
+                                                   MI_TREE_DECODE_SCALES, MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_lists_bf16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_OPERANDS(uint16_t), MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_lists_f16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_OPERANDS(uint16_t), MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_lists_paged_bf16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint16_t),
+                                                      MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_lists_paged_f16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint16_t),
+                                                     MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_lists_fp8_bf16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_OPERANDS(uint8_t), MI_TREE_DECODE_SCALES,
+                                                    MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_lists_fp8_f16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_OPERANDS(uint8_t), MI_TREE_DECODE_SCALES,
+                                                   MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_lists_paged_fp8_bf16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint8_t),
+                                                          MI_TREE_DECODE_SCALES, MI_WINDOW_DECODE_OUT);
+int mi_block_attention_window_decode_lists_paged_fp8_f16(MI_TREE_DECODE_LISTS, MI_TREE_DECODE_TABLE, MI_TREE_DECODE_OPERANDS(uint8_t),
+                                                         MI_TREE_DECODE_SCALES, MI_WINDOW_DECODE_OUT);
+
+/* ------------------------------------------------------------------------ *
  * Compaction after a speculative step: mi_kv_compact{,_paged} move the accepted path's k / v rows to the front
  * of the window of the T ≤ 64 drafted slots, in place, in one launch for k and v.  The cache is that of mi_kv_append_* (items,
  * heads, Smax, D, the strides IN ELEMENTS, block_table, table_ld, pages, page as there); elem_bytes is 2 (bfloat16 / float16) or 1
@@ -1735,6 +1783,58 @@ int mi_block_attention_lists_prefill_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_L
 int mi_block_attention_lists_prefill_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE,
                                                    int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
                                                    MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT);
+
+/* ------------------------------------------------------------------------ *
+ * Sliding windows and sink keys for prefill: the sixteen UNSPLIT prefill entries — the layout entries
+ * mi_block_attention_prefill{,_paged}{,_fp8}_T and the list entries mi_block_attention_lists_prefill{,_paged}{,_fp8}_T — as
+ * mi_block_attention_window_prefill{,_lists}{,_paged}{,_fp8}_T, with `window, sink` (as above) between `scale` (or the four scale
+ * parameters) and `out`.  The own row at pos — the tile geometry of the parents — sees key j iff the parent's rule holds AND
+ * (j > pos − window or j < sink): a test per element beside the diagonal's.  A listed block J with 64 J ≥ sink and
+ * 64 J + 63 ≤ 64 r − window, r the tile's layout row, is hidden from every position the tile can hold and is never loaded; a block
+ * that some row of the tile sees is loaded as in the parents.  Everything else — the order of summation, new_lens, the zero rows
+ * and lse −inf of slots without a token and of rows that see nothing — is the parent's; window = 2³¹ − 1, or sink ≥ Smax, gives
+ * the parent entry's bits.  There is no split form: a windowed row's list is short.
+ * Validation before any HIP call: window < 1 or sink < 0 — MI_EINVAL, before anything else; then what the parent refuses.
+ * ------------------------------------------------------------------------ */
+#define MI_WINDOW_PREFILL_OUT int32_t window, int32_t sink, uint16_t *out, int64_t ldo, int64_t strideO, float *lse, mi_stream_t stream
+int mi_block_attention_window_prefill_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                           MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+                                          MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                 MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                               MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                              MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                     MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                                     MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                    MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                                    MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_lists_bf16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, int32_t D,
+                                                 MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_lists_f16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, int32_t D,
+                                                MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_lists_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                       MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_lists_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
+                                                      MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_lists_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, int32_t D,
+                                                     MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                                     MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_lists_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, int32_t D,
+                                                    MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+                                                    MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_lists_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE,
+                                                           int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                                           MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_WINDOW_PREFILL_OUT);
+int mi_block_attention_window_prefill_lists_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE,
+                                                          int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
+                                                          MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_WINDOW_PREFILL_OUT);
 
 /* ------------------------------------------------------------------------ *
  * Block-sparse (BSR) × dense products on the matrix cores — NEW relative to the reference: C[b] = op(A) · B[b] in

@@ -47,6 +47,14 @@
 //    kernel's first parameter — Tree<…> around either list source: a hidden key is treated like a key beyond pos (never loaded,
 //    staged as zeros, its score −inf), everything else is the same statements, so the word (2 << t) − 1 gives the plain call's bits.
 //
+//  * Sliding windows and sink keys (mi_block_attention_window_decode{,_lists}{,_paged}{,_fp8}_{bf16,f16}): with a window
+//    W ≥ 1 and S ≥ 0 sink keys the token at pos sees key j iff the rule above holds and (j > pos − W or j < S) — W counts the token
+//    itself.  The hide word's second source: in tile J the bits [max(S − 64 J, 0), min(pos − W + 1 − 64 J, 64)), made in scalar
+//    registers, are OR-ed to the tree word, so a hidden key is again never loaded, staged as zeros, its score −inf; a listed block
+//    that lies wholly in [S, pos − W] is skipped by next_entry like a block beyond pos and keeps its list position.  The entries run
+//    on the Tree<…> kernels with a null mask ("no tree": H = 0, T not bound to 64); the tree entries pass W = 2³¹ − 1, S = 0, whose
+//    range is empty.  No new instantiation.
+//
 // Kernel: grid (chunks, items, T), 256 threads.  No workgroup barrier inside the walk.  A wave loads the k tile of an
 // entry as 16-byte global loads straight into MFMA A fragments (lane (li, lg): row 16f + li, columns 32s + 8lg … + 7), the v
 // tile into registers and from there into a wave-private transposed LDS image [D][64 + 8] (a wave-level fence between its
@@ -131,6 +139,9 @@ struct Args {
   // batch — names the keys of the window [k_len − T, k_len) that token t sees beside itself: bit i < t is key k_len − T + i
   const int64_t* tree_mask;
   int mask_rows;
+  // the window of the window_decode entries, looked at by the Tree<…> kernels only: beside its other rules the
+  // token at pos sees key j iff j > pos − window or j < sink.  The tree_decode entries pass 2³¹ − 1 and 0: nothing is hidden
+  int window, sink;
 };
 
 // The hide word of a tile (tree form): bit r is set iff row r of the tile is a draft key that the token does not see.  `hide`
@@ -253,11 +264,15 @@ __device__ __forceinline__ void score(f32x4 (&acc)[4], const F (&kf)[4][D / 32],
 }
 
 // the next entry of this wave at or after p (in steps of the workgroup's waves) that is computed: inside the grid and
-// not wholly beyond pos
-__device__ __forceinline__ int next_entry(const int32_t* col, int p, int end, int pos, int blocks) {
+// not wholly beyond pos — nor (WINDOW: the Tree<…> kernels) wholly behind the window: a block of keys
+// [64j, 64j + 64) ⊂ [sink, edge), edge = pos − window + 1 the first key the window shows.  A skipped entry keeps its list position.
+template <bool WINDOW>
+__device__ __forceinline__ int next_entry(const int32_t* col, int p, int end, int pos, int blocks, int edge, int sink) {
   for (; p < end; p += kWaves) {
     const int j = col[p];
     if ((unsigned)j >= (unsigned)blocks || (long)j * kB > pos) continue;
+    if constexpr (WINDOW)
+      if ((long)j * kB >= sink && (long)j * kB + kB <= edge) continue;
     break;
   }
   return p;
@@ -355,17 +370,27 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   // H: the hidden keys in window coordinates (bit i: key base + i), of the bits below t only — the token sees itself, and the
   // keys beyond pos are the plain rule's.  Read once per workgroup through a uniform address, shifted per tile in scalar
   // registers; a hidden key is treated like a key beyond pos: never loaded, staged as zeros, its score −inf.
+  // The window is the word's second source: the keys [sink, edge), edge = pos − window + 1, are hidden — in
+  // tile J the bits [max(sink − 64 J, 0), min(edge − 64 J, 64)), made in scalar registers.  edge and sink are clamped to
+  // [0, pos + 1] and [0, Smax] once, so the differences below stay int32s; a null tree_mask is "no tree": H = 0, T unbound.
   [[maybe_unused]] HideWord H = 0;
-  [[maybe_unused]] int base = 0;
+  [[maybe_unused]] int base = 0, edge = 0, sink = 0;
   if constexpr (TREE) {
     base = klen - a.T;
-    const HideWord mask = (HideWord)a.tree_mask[(long)(a.mask_rows == 1 ? 0 : c / a.heads) * a.T + t];
-    H = ~mask & ((1ull << t) - 1ull);  // (t < T ≤ 64)
+    if (a.tree_mask) {
+      const HideWord mask = (HideWord)a.tree_mask[(long)(a.mask_rows == 1 ? 0 : c / a.heads) * a.T + t];
+      H = ~mask & ((1ull << t) - 1ull);  // (t < T ≤ 64)
+    }
+    edge = pos - a.window + 1 < 0 ? 0 : pos - a.window + 1;  // (pos ≥ 0 here, window ≥ 1: no overflow)
+    sink = a.sink > a.smax ? (int)a.smax : a.sink;
   }
   auto hide_of = [&](int J) -> HideWord {  // the hide word of tile J: H moved by off = base − 64 J, 0 unless −64 < off < 64
     if constexpr (TREE) {
       const int off = base - J * kB;
-      return off <= -kB || off >= kB ? 0ull : off >= 0 ? H << off : H >> -off;
+      HideWord h = off <= -kB || off >= kB ? 0ull : off >= 0 ? H << off : H >> -off;
+      const int lo = sink - J * kB < 0 ? 0 : sink - J * kB, hi = edge - J * kB > kB ? kB : edge - J * kB;
+      if (lo < hi) h |= (hi == kB ? ~0ull : (1ull << hi) - 1ull) & ~((1ull << lo) - 1ull);  // (lo < hi ≤ 64: a shift by 64 is none)
+      return h;
     } else {
       return 0ull;
     }
@@ -378,7 +403,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
   uint4 qf[D / 32];  // the own rows as B fragments: lane (li, lg) holds columns 32s + 8lg … + 7 of query head li
 #pragma unroll
   for (int s = 0; s < D / 32; ++s) qf[s] = uint4{0u, 0u, 0u, 0u};
-  int p = next_entry(a.col, beg + w, end, pos, a.blocks);
+  int p = next_entry<TREE>(a.col, beg + w, end, pos, a.blocks, edge, sink);
   if (li < G && p < end) {
     const uint16_t* row = a.q + ((long)c * G + li) * a.strideQ + (long)t * a.ldq;
 #pragma unroll
@@ -411,7 +436,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
     }
   };
   auto look_ahead = [&](int from) {  // the next computed entry at or after `from`, its column and its table entries
-    pn = next_entry(a.col, from, end, pos, a.blocks);
+    pn = next_entry<TREE>(a.col, from, end, pos, a.blocks, edge, sink);
     if (pn < end) {
       Jn = a.col[pn];
       read_pages<FORM>(en, trow, Jn, a.page_shift);
@@ -445,7 +470,7 @@ __global__ __launch_bounds__(256) void block_attention_decode_kernel(Args a) {
     f32x4 s[4];
     score<T, D>(s, kf, qf);
     if constexpr (FORM == kContiguous) {
-      p = next_entry(a.col, p + kWaves, end, pos, a.blocks);
+      p = next_entry<TREE>(a.col, p + kWaves, end, pos, a.blocks, edge, sink);
       if (p < end) {  // the next entry's loads are in flight while this one is computed
         const int J = a.col[p];
         load_k<D>(kf, K + (long)J * kB * a.ldk, a.ldk, li, lg, pos + 1 - J * kB, hide_of(J));
@@ -596,11 +621,20 @@ struct TreeMask {
 };
 constexpr int kMaxTree = 64;  // the T of a tree call: a token's word names the window's keys
 
+// the window of the window_decode entries; what the other entries pass hides nothing
+struct Window {
+  int32_t window = 0x7fffffff, sink = 0;
+};
+
 // Every check comes before the first HIP call.  `r`: what every reading entry takes (block_attention_cache_device.h), FP8 its
-// cache type, TREE that it is a tree_decode entry (`tree` is looked at); q, chunk and the workspace are this entry's own.
-template <class T, bool FP8 = false, bool TREE = false>
+// cache type, TREE that it is a tree_decode entry (`tree` is looked at), WINDOW that it is a window_decode entry (`win` is; it
+// runs on the Tree<…> kernels with no mask); q, chunk and the workspace are this entry's own.
+template <class T, bool FP8 = false, bool TREE = false, bool WINDOW = false>
 int decode_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t strideQ, int32_t chunk, void* workspace,
-                 size_t workspace_bytes, hipStream_t s, const Lists& lists = Lists(), const TreeMask& tree = TreeMask()) {
+                 size_t workspace_bytes, hipStream_t s, const Lists& lists = Lists(), const TreeMask& tree = TreeMask(),
+                 const Window& win = Window()) {
+  static_assert(!(TREE && WINDOW), "a window's lower edge is the slot's: no windows over tree masks");
+  if (WINDOW && (win.window < 1 || win.sink < 0)) return MI_EINVAL;
   // the list source: `col` is block_ids, nnz its items · T · K entries; a list has at most K entries, so the chunks — and
   // the workspace — are those of a cache of K blocks
   const bool listed = lists.K != 0 || lists.counts;
@@ -627,7 +661,8 @@ int decode_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t stri
   a.ws = static_cast<float*>(workspace);
   if (listed) a.counts = lists.counts, a.list_k = lists.K;
   if (TREE) a.tree_mask = tree.mask, a.mask_rows = tree.rows;
-  return with_width(r.D, [&](auto d) { return launch<T, decltype(d)::value, FP8, TREE>(a, r.items, s); });
+  a.window = win.window, a.sink = win.sink;
+  return with_width(r.D, [&](auto d) { return launch<T, decltype(d)::value, FP8, TREE || WINDOW>(a, r.items, s); });
 }
 
 }  // namespace
@@ -800,5 +835,47 @@ int mi_block_attention_tree_decode_lists_paged_fp8_f16(MI_DECODE_LISTS_LIST, MI_
                                                        MI_DECODE_SCALES, MI_DECODE_TREE, MI_DECODE_OUT) {
   return page < 16 ? MI_EINVAL : decode_entry<F16, true, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LISTS_TREE_OWN);
 }
+
+// The window forms: the sixteen plain entries as mi_block_attention_window_decode{,_lists}{,_paged}{,_fp8}_T, with
+// `window, sink` between their operands and their outputs — window ≥ 1, sink ≥ 0.  They run on the Tree<…> kernels with no mask.
+#define MI_DECODE_WINDOW int32_t window, int32_t sink
+#define MI_DECODE_WINDOW_OWN TreeMask(), Window{window, sink}
+#define MI_DECODE_LAYOUT_WINDOW_OWN MI_DECODE_OWN, Lists(), MI_DECODE_WINDOW_OWN
+#define MI_DECODE_LISTS_WINDOW_OWN MI_DECODE_OWN, Lists{block_counts, K < 1 ? -1 : K}, MI_DECODE_WINDOW_OWN
+// two entries, one per type: the name's suffix, the head of the list (a layout or the lists), the cache form, what decode_entry
+// takes, then the operands [and the scales]
+#define MI_WINDOW_DECODE(NAME, HEAD, FP8, CALL, OWN, ...)                                                                      \
+  int mi_block_attention_window_decode##NAME##_bf16(HEAD, MI_DECODE_SIZES, __VA_ARGS__ MI_DECODE_WINDOW, MI_DECODE_OUT) {          \
+    return decode_entry<Bf16, FP8, false, true>(CALL, OWN);                                                                        \
+  }                                                                                                                                \
+  int mi_block_attention_window_decode##NAME##_f16(HEAD, MI_DECODE_SIZES, __VA_ARGS__ MI_DECODE_WINDOW, MI_DECODE_OUT) {           \
+    return decode_entry<F16, FP8, false, true>(CALL, OWN);                                                                         \
+  }
+#define MI_WINDOW_DECODE_PAGED(NAME, HEAD, FP8, CALL, OWN, ...)                                                                \
+  int mi_block_attention_window_decode##NAME##_bf16(HEAD, MI_DECODE_SIZES, MI_DECODE_TABLE, __VA_ARGS__ MI_DECODE_WINDOW,          \
+                                                    MI_DECODE_OUT) {                                                               \
+    return page < 16 ? MI_EINVAL : decode_entry<Bf16, FP8, false, true>(CALL, OWN);                                                \
+  }                                                                                                                                \
+  int mi_block_attention_window_decode##NAME##_f16(HEAD, MI_DECODE_SIZES, MI_DECODE_TABLE, __VA_ARGS__ MI_DECODE_WINDOW,           \
+                                                   MI_DECODE_OUT) {                                                                \
+    return page < 16 ? MI_EINVAL : decode_entry<F16, FP8, false, true>(CALL, OWN);                                                 \
+  }
+// clang-format off
+MI_WINDOW_DECODE(, MI_DECODE_LIST, false, MI_DECODE_CALL(), MI_DECODE_LAYOUT_WINDOW_OWN, MI_DECODE_OPERANDS(uint16_t),)
+MI_WINDOW_DECODE_PAGED(_paged, MI_DECODE_LIST, false, MI_DECODE_CALL(MI_READ_PAGED), MI_DECODE_LAYOUT_WINDOW_OWN,
+                       MI_DECODE_OPERANDS(uint16_t),)
+MI_WINDOW_DECODE(_fp8, MI_DECODE_LIST, true, MI_DECODE_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LAYOUT_WINDOW_OWN,
+                 MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,)
+MI_WINDOW_DECODE_PAGED(_paged_fp8, MI_DECODE_LIST, true, MI_DECODE_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LAYOUT_WINDOW_OWN,
+                       MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,)
+MI_WINDOW_DECODE(_lists, MI_DECODE_LISTS_LIST, false, MI_DECODE_LISTS_CALL(), MI_DECODE_LISTS_WINDOW_OWN,
+                 MI_DECODE_OPERANDS(uint16_t),)
+MI_WINDOW_DECODE_PAGED(_lists_paged, MI_DECODE_LISTS_LIST, false, MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_WINDOW_OWN,
+                       MI_DECODE_OPERANDS(uint16_t),)
+MI_WINDOW_DECODE(_lists_fp8, MI_DECODE_LISTS_LIST, true, MI_DECODE_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8),
+                 MI_DECODE_LISTS_WINDOW_OWN, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,)
+MI_WINDOW_DECODE_PAGED(_lists_paged_fp8, MI_DECODE_LISTS_LIST, true, MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8),
+                       MI_DECODE_LISTS_WINDOW_OWN, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,)
+// clang-format on
 
 }  // extern "C"

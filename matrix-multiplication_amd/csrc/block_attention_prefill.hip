@@ -54,6 +54,15 @@
 // list_range() stands, every statement after the two bounds of the list is shared, so a list has the bits of the layout row that
 // lists the same blocks in the same order.  block_attention_prefill_lists_kernel is the third shell; what it adds to Args
 // travels beside it (ListArgs).  Unsplit only: a list has K entries.
+//
+// Sliding windows and sink keys (mi_block_attention_window_prefill{,_lists}{,_paged}{,_fp8}_* — DESIGN.md §3.35): with a window W ≥ 1 and
+// S ≥ 0 sink keys the own row at pos sees key j iff the rule above holds and (j > pos − W or j < S).  prefill_walk<…, WINDOW> is the same
+// walk with two additions: a test per element behind the diagonal's — the rows of a tile have different edges; under a uniform branch,
+// in the blocks that reach behind the window of the tile's last position — and next_block_window,
+// which skips a listed block that lies wholly in [S, 64 r − W], hidden from every position the tile can hold: never loaded.
+// block_attention_prefill_window_kernel<…, LISTS> is the fourth shell, over either list source, reading new_lens at run time as the
+// lists kernel does (so NEWLENS does not double it); what it adds to Args travels beside it (WindowArgs).  Unsplit only.  The walks
+// without a window keep their statements — next_block is untouched — and with them their registers.
 #include <type_traits>
 
 #include "block_attention_cache_device.h"
@@ -196,6 +205,19 @@ __device__ __forceinline__ int next_block(const int32_t* col, int p, int end, in
   }
   return p;
 }
+// … under a window: nor wholly behind the window of every position the tile can hold — the keys
+// [64j, 64j + 64) ⊂ [sink, edge), edge = 64 · own_block − window + 1 the first key that the window of the tile's first position
+// shows.  (A function of its own: the walks without a window keep their statements, and with them their registers.)
+__device__ __forceinline__ int next_block_window(const int32_t* col, int p, int end, int own_block, int walk_blocks, int edge, int sink) {
+  for (; p < end; ++p) {
+    const int j = col[p];
+    if ((unsigned)j >= (unsigned)walk_blocks) continue;
+    if (j > own_block) continue;
+    if ((long)j * kB >= sink && (long)j * kB + kB <= edge) continue;
+    break;
+  }
+  return p;
+}
 
 // What the split launches add to Args.  The unsplit kernel's argument stays as it was.
 struct SplitArgs {
@@ -297,9 +319,13 @@ __device__ __forceinline__ void store_row(const Args& a, const Geom& gm, long it
 // combine launch writes those rows —, and the epilogue stores the partial (o, m, l) of the 64 own rows into `ws`.
 // LISTS (unsplit only): the list is the caller's, row (c, x) of block_ids, where the layout gives row r of its CSR lists —
 // the two bounds of the list are all that differs; a.new_lens is looked at when it is there, whatever NEWLENS says.
-template <class TC, int D, int FORM, bool NEWLENS, bool SPLIT, bool LISTS = false>
+// WINDOW (unsplit only): the own row at pos sees key j iff the rule above holds and (j > pos − window or
+// j < sink) — a test per element beside the diagonal's, the rows of a tile having different edges —, and a listed block that
+// no position of the tile can see is skipped by next_block and never loaded.  new_lens is looked at as LISTS looks at it.
+template <class TC, int D, int FORM, bool NEWLENS, bool SPLIT, bool LISTS = false, bool WINDOW = false>
 __device__ __forceinline__ void prefill_walk(const Args& a, int split, int parts, float* ws, const int32_t* counts = nullptr,
-                                             int list_k = 0) {
+                                             int list_k = 0, [[maybe_unused]] int window = 0x7fffffff, [[maybe_unused]] int sink = 0) {
+  static_assert(!(WINDOW && SPLIT), "a windowed row's list is short: no split walks");
   typedef typename Operand<TC>::type T;
   constexpr bool FP8 = Operand<TC>::fp8;
   typedef typename Cache<FP8>::elem E;
@@ -320,7 +346,7 @@ __device__ __forceinline__ void prefill_walk(const Args& a, int split, int parts
     const int g = (int)((u / kSpreadHeads) % G);
     const int c = (int)(slot / a.tiles), x = (int)(slot - (long)c * a.tiles);
     const int bi = c / a.heads, h = c - bi * a.heads;
-    const Geom gm = geometry(a, LISTS ? a.new_lens != nullptr : NEWLENS, c, bi, x, w, li);
+    const Geom gm = geometry(a, LISTS || WINDOW ? a.new_lens != nullptr : NEWLENS, c, bi, x, w, li);
     const int klen = gm.klen, r = gm.r;
     const long item = (long)c * G + g;
     if (!gm.any) {  // nothing to walk: the zero rows of the slots it owns, if any
@@ -375,13 +401,20 @@ __device__ __forceinline__ void prefill_walk(const Args& a, int split, int parts
       tv.load(V, a.ldv, a.pageV, J, e, ok, in_page, tid, klen - J * kB);
     };
     auto look_ahead = [&](int from) {
-      pn = next_block(a.col, from, pend, r, kblocks);
+      if constexpr (WINDOW)  // (the tile skips the blocks inside [sink, 64r − window]; r ≥ 0, window ≥ 1: an int32)
+        pn = next_block_window(a.col, from, pend, r, kblocks, r * kB - window + 1, sink);
+      else
+        pn = next_block(a.col, from, pend, r, kblocks);
       if (pn < pend) {
         Jn = a.col[pn];
         if constexpr (FORM != kContiguous) read_pages<FORM>(en, trow, Jn, a.page_shift);
       }
     };
-    int p = next_block(a.col, (int)ls.beg, pend, r, kblocks);
+    int p;
+    if constexpr (WINDOW)
+      p = next_block_window(a.col, (int)ls.beg, pend, r, kblocks, r * kB - window + 1, sink);
+    else
+      p = next_block(a.col, (int)ls.beg, pend, r, kblocks);
     if (p < pend) {
       J = a.col[p];
       if constexpr (FORM != kContiguous) {
@@ -421,6 +454,20 @@ __device__ __forceinline__ void prefill_walk(const Args& a, int split, int parts
           if (16 * f + 4 * lg + rr >= kleft) x = -INFINITY;
           s[f][rr] = x;
         }
+      if constexpr (WINDOW) {
+        // keys behind the own row's window that are no sink keys: j ≥ sink and j ≤ pos − window (pos ≥ 0, window ≥ 1: int32s).  A
+        // uniform branch: only a block that reaches behind the window of the tile's LAST position, and is not all sink keys, holds
+        // one — of a banded list the oldest block or two
+        if (Jc * kB <= r * kB + (kB - 1) - window && Jc * kB + (kB - 1) >= sink) {
+#pragma unroll
+          for (int f = 0; f < 4; ++f)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const int j = Jc * kB + 16 * f + 4 * lg + rr;
+              if (j >= sink && j <= gm.pos - window) s[f][rr] = -INFINITY;
+            }
+        }
+      }
       if (FORM != kContiguous && seen != 0xfu) {  // keys of a page outside the pool (a uniform branch: tables are in range as a rule)
 #pragma unroll
         for (int f = 0; f < 4; ++f)
@@ -488,6 +535,25 @@ template <class TC, int D, int FORM>
 __global__ __launch_bounds__(256) void block_attention_prefill_lists_kernel(ListArgs la) {
   prefill_walk<TC, D, FORM, true, false, true>(la.a, 0, 1, nullptr, la.counts, la.list_k);
 }
+
+// What the window entries add to Args, for either list source: counts null — the layout —, or the caller's lists
+// as in ListArgs.  The other kernels' arguments stay as they were.
+struct WindowArgs {
+  Args a;
+  const int32_t* counts;
+  int list_k;
+  int window, sink;
+};
+template <class TC, int D, int FORM, bool LISTS>
+__global__ __launch_bounds__(256) void block_attention_prefill_window_kernel(WindowArgs wa) {
+  prefill_walk<TC, D, FORM, true, false, LISTS, true>(wa.a, 0, 1, nullptr, wa.counts, wa.list_k, wa.window, wa.sink);
+}
+
+// the window of the window_prefill entries
+struct Window {
+  bool on = false;
+  int32_t window = 0x7fffffff, sink = 0;
+};
 
 // The second launch of a split call: one workgroup per (query item, tile), thread (w, li, lg) on own row 16w + li as in the
 // walk.  The tile's rows, its list and its number of parts are recomputed as the walk computes them; the partials of parts
@@ -558,7 +624,16 @@ __global__ __launch_bounds__(256) void block_attention_prefill_combine_kernel(Sp
 }
 
 template <class TC, int D, int FORM>
-int launch_form(const Args& a, const SplitArgs& sp, const ListArgs& li, hipStream_t s) {
+int launch_form(const Args& a, const SplitArgs& sp, const ListArgs& li, const Window& win, hipStream_t s) {
+  if (win.on) {  // a window: one launch over either list source, never split
+    const WindowArgs wa = {a, li.counts, li.list_k, win.window, win.sink};
+    const dim3 grid((unsigned)(a.units < kMaxGrid ? a.units : kMaxGrid));
+    if (li.counts)
+      hipLaunchKernelGGL((block_attention_prefill_window_kernel<TC, D, FORM, true>), grid, dim3(256), 0, s, wa);
+    else
+      hipLaunchKernelGGL((block_attention_prefill_window_kernel<TC, D, FORM, false>), grid, dim3(256), 0, s, wa);
+    return mi::check_launch();
+  }
   if (li.counts) {  // the list source: one launch, never split
     const ListArgs la = {a, li.counts, li.list_k};
     hipLaunchKernelGGL((block_attention_prefill_lists_kernel<TC, D, FORM>), dim3((unsigned)(a.units < kMaxGrid ? a.units : kMaxGrid)),
@@ -588,9 +663,9 @@ int launch_form(const Args& a, const SplitArgs& sp, const ListArgs& li, hipStrea
 }
 
 template <class T, int D, bool FP8>
-int launch(const Args& a, const SplitArgs& sp, const ListArgs& li, hipStream_t s) {
+int launch(const Args& a, const SplitArgs& sp, const ListArgs& li, const Window& win, hipStream_t s) {
   typedef std::conditional_t<FP8, Fp8<T>, T> TC;  // the cache element type is part of the kernel's first parameter
-  return with_form(a, [&](auto form) { return launch_form<TC, D, decltype(form)::value>(a, sp, li, s); });
+  return with_form(a, [&](auto form) { return launch_form<TC, D, decltype(form)::value>(a, sp, li, win, s); });
 }
 
 // What the split entries add: the list entries of a part, and the workspace of the partials.
@@ -612,10 +687,13 @@ inline int parts_of(int32_t Smax, int32_t split) { return (int)(((long)Smax / kB
 
 // Every check comes before the first HIP call.  `r`: what every reading entry takes (block_attention_cache_device.h), FP8 its
 // cache type; q, new_lens and `split` — the split entries' cut and workspace; with one part the call is the unsplit launch —
-// are this entry's own, and `lists`: the list source (never with split) — `col` is block_ids, nnz its items · tiles · K entries.
+// are this entry's own, and `lists`: the list source (never with split) — `col` is block_ids, nnz its items · tiles · K entries;
+// `win`: the window of the window_prefill entries (never with split), over either list source.
 template <class T, bool FP8 = false>
 int prefill_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t headQ, int64_t batchQ, const int32_t* new_lens,
-                  int32_t new_lens_count, hipStream_t s, const Split& split = Split(), const Lists& lists = Lists()) {
+                  int32_t new_lens_count, hipStream_t s, const Split& split = Split(), const Lists& lists = Lists(),
+                  const Window& win = Window()) {
+  if (win.on && (win.window < 1 || win.sink < 0 || split.on)) return MI_EINVAL;
   const bool listed = lists.K != 0 || lists.counts;
   if (listed && (split.on || lists.K < 1 || !lists.counts || !aligned4(lists.counts) || !aligned4(r.col))) return MI_EINVAL;
   if (split.on && split.entries < 1) return MI_EINVAL;
@@ -642,7 +720,7 @@ int prefill_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t hea
   a.units = (a.slots + kSpreadHeads - 1) / kSpreadHeads * kSpreadHeads * r.group;
   a.q = q, a.ldq = ldq, a.headQ = headQ, a.batchQ = batchQ;
   a.new_lens = new_lens, a.new_lens_one = new_lens_count == 1;
-  return with_width(r.D, [&](auto d) { return launch<T, decltype(d)::value, FP8>(a, sp, li, s); });
+  return with_width(r.D, [&](auto d) { return launch<T, decltype(d)::value, FP8>(a, sp, li, win, s); });
 }
 
 }  // namespace
@@ -781,5 +859,37 @@ int mi_block_attention_lists_prefill_paged_fp8_f16(MI_PREFILL_LISTS_HEAD, MI_BLO
                                                    MI_BLOCK_ATTENTION_PREFILL_OUT) {
   return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_LISTS_OWN);
 }
+
+// The window forms: the sixteen unsplit entries as mi_block_attention_window_prefill{,_lists}{,_paged}{,_fp8}_T, with
+// `window, sink` between their operands and their outputs — window ≥ 1, sink ≥ 0.
+#define MI_PREFILL_WINDOW int32_t window, int32_t sink
+#define MI_PREFILL_WINDOW_OWN MI_PREFILL_OWN, Split(), Lists(), Window{true, window, sink}
+#define MI_PREFILL_LISTS_WINDOW_OWN MI_PREFILL_OWN, Split(), Lists{block_counts, K < 1 ? -1 : K}, Window{true, window, sink}
+// two entries, one per type: the name's suffix, the head of the list (a layout or the lists) [and the table], the cache form, what
+// prefill_entry takes, then the operands [and the scales]
+#define MI_WINDOW_PREFILL(NAME, HEAD, FP8, GUARD, CALL, OWN, ...)                                                                  \
+  int mi_block_attention_window_prefill##NAME##_bf16(HEAD, int32_t D, __VA_ARGS__ MI_PREFILL_WINDOW, MI_BLOCK_ATTENTION_PREFILL_OUT) { \
+    return GUARD ? MI_EINVAL : prefill_entry<Bf16, FP8>(CALL, OWN);                                                                \
+  }                                                                                                                                \
+  int mi_block_attention_window_prefill##NAME##_f16(HEAD, int32_t D, __VA_ARGS__ MI_PREFILL_WINDOW, MI_BLOCK_ATTENTION_PREFILL_OUT) {  \
+    return GUARD ? MI_EINVAL : prefill_entry<F16, FP8>(CALL, OWN);                                                                 \
+  }
+#define MI_LAYOUT_PAGED MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE
+#define MI_LISTS_PAGED MI_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE
+#define MI_OPS16 MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
+#define MI_OPS8 MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+// clang-format off
+MI_WINDOW_PREFILL(, MI_BLOCK_ATTENTION_PREFILL_LIST, false, false, MI_PREFILL_CALL(), MI_PREFILL_WINDOW_OWN, MI_OPS16)
+MI_WINDOW_PREFILL(_paged, MI_LAYOUT_PAGED, false, page < 16, MI_PREFILL_CALL(MI_READ_PAGED), MI_PREFILL_WINDOW_OWN, MI_OPS16)
+MI_WINDOW_PREFILL(_fp8, MI_BLOCK_ATTENTION_PREFILL_LIST, true, false, MI_PREFILL_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_WINDOW_OWN,
+                  MI_OPS8)
+MI_WINDOW_PREFILL(_paged_fp8, MI_LAYOUT_PAGED, true, page < 16, MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_WINDOW_OWN, MI_OPS8)
+MI_WINDOW_PREFILL(_lists, MI_PREFILL_LISTS_HEAD, false, false, MI_PREFILL_LISTS_CALL(), MI_PREFILL_LISTS_WINDOW_OWN, MI_OPS16)
+MI_WINDOW_PREFILL(_lists_paged, MI_LISTS_PAGED, false, page < 16, MI_PREFILL_LISTS_CALL(MI_READ_PAGED), MI_PREFILL_LISTS_WINDOW_OWN, MI_OPS16)
+MI_WINDOW_PREFILL(_lists_fp8, MI_PREFILL_LISTS_HEAD, true, false, MI_PREFILL_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8),
+                  MI_PREFILL_LISTS_WINDOW_OWN, MI_OPS8)
+MI_WINDOW_PREFILL(_lists_paged_fp8, MI_LISTS_PAGED, true, page < 16, MI_PREFILL_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8),
+                  MI_PREFILL_LISTS_WINDOW_OWN, MI_OPS8)
+// clang-format on
 
 }  // extern "C"

@@ -311,6 +311,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(block_attention_lists_decode_fp8's arguments with tree_mask before chunk)");
   m.def("block_attention_tree_lists_decode_paged_fp8", &block_attention_tree_lists_decode_paged_fp8,
         "(block_attention_lists_decode_paged_fp8's arguments with tree_mask before chunk)");
+  m.def("block_attention_window_decode", &block_attention_window_decode,
+        "(block_attention_decode's arguments with window >= 1 and sink >= 0, ints, before chunk): the token at pos sees key j iff the "
+        "plain rule holds and (j > pos - window or j < sink); the window counts the token itself");
+  m.def("block_attention_window_decode_paged", &block_attention_window_decode_paged,
+        "(block_attention_decode_paged's arguments with window, sink before chunk): block_attention_window_decode over a pool of pages");
+  m.def("block_attention_window_decode_fp8", &block_attention_window_decode_fp8,
+        "(block_attention_decode_fp8's arguments with window, sink before chunk): block_attention_window_decode over an fp8 cache");
+  m.def("block_attention_window_decode_paged_fp8", &block_attention_window_decode_paged_fp8,
+        "(block_attention_decode_paged_fp8's arguments with window, sink before chunk): block_attention_window_decode over an fp8 pool");
+  m.def("block_attention_window_decode_lists", &block_attention_window_decode_lists,
+        "(block_attention_decode_lists' arguments with window, sink before chunk): the window rule over the caller's lists");
+  m.def("block_attention_window_decode_lists_paged", &block_attention_window_decode_lists_paged,
+        "(block_attention_decode_lists_paged's arguments with window, sink before chunk)");
+  m.def("block_attention_window_lists_decode_fp8", &block_attention_window_lists_decode_fp8,
+        "(block_attention_lists_decode_fp8's arguments with window, sink before chunk)");
+  m.def("block_attention_window_lists_decode_paged_fp8", &block_attention_window_lists_decode_paged_fp8,
+        "(block_attention_lists_decode_paged_fp8's arguments with window, sink before chunk)");
   m.def("kv_block_bounds_fp8", &kv_block_bounds_fp8,
         "(k [B, Hkv, Smax, D] float8_e4m3fn through its own strides (multiples of 16 bytes), k_lens, last, bounds [B, Hkv, Smax/64, 2, D] "
         "bfloat16 / float16): kv_block_bounds over an fp8 cache — the bits of kv_block_bounds on the cache widened to bounds' dtype");
@@ -336,6 +353,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("block_attention_lists_prefill_paged_fp8", &block_attention_prefill_lists_paged_fp8,
         "(block_ids, block_counts, q, k_pages, v_pages [P, Hkv, page, D] float8_e4m3fn, block_table int32 [B, W], k_lens, new_lens, scale, "
         "k_scale, v_scale, out, lse): block_attention_lists_prefill_fp8 over a pool of pages");
+  m.def("block_attention_window_prefill", &block_attention_window_prefill,
+        "(block_attention_prefill's arguments with window >= 1 and sink >= 0, ints, before out): the token at pos sees key j iff the "
+        "plain rule holds and (j > pos - window or j < sink); the window counts the token itself");
+  m.def("block_attention_window_prefill_paged", &block_attention_window_prefill_paged,
+        "(block_attention_prefill_paged's arguments with window, sink before out)");
+  m.def("block_attention_window_prefill_fp8", &block_attention_window_prefill_fp8,
+        "(block_attention_prefill_fp8's arguments with window, sink before out)");
+  m.def("block_attention_window_prefill_paged_fp8", &block_attention_window_prefill_paged_fp8,
+        "(block_attention_prefill_paged_fp8's arguments with window, sink before out)");
+  m.def("block_attention_window_lists_prefill", &block_attention_window_prefill_lists,
+        "(block_attention_lists_prefill's arguments with window, sink before out): the window rule over the caller's lists");
+  m.def("block_attention_window_lists_prefill_paged", &block_attention_window_prefill_lists_paged,
+        "(block_attention_lists_prefill_paged's arguments with window, sink before out)");
+  m.def("block_attention_window_lists_prefill_fp8", &block_attention_window_prefill_lists_fp8,
+        "(block_attention_lists_prefill_fp8's arguments with window, sink before out)");
+  m.def("block_attention_window_lists_prefill_paged_fp8", &block_attention_window_prefill_lists_paged_fp8,
+        "(block_attention_lists_prefill_paged_fp8's arguments with window, sink before out)");
   m.def("bsr_mm", &bsr_mm,
         "(offsets [rows/64+1], columns, entry_ids or None, nnz, values [n, 64, 64], B [batch, inner, N], C [batch, rows, N], trans_a): "
         "C = op(A) B with A in 64 x 64 blocks on the matrix cores, bfloat16 / float16");

@@ -14,7 +14,9 @@ torch::Tensor block_attention_decode_impl(const char* what, const char* kname, c
                                           const torch::Tensor& v, const torch::Tensor* table, const torch::Tensor& k_lens, double scale,
                                           const c10::optional<torch::Tensor>& k_scale, const c10::optional<torch::Tensor>& v_scale,
                                           int64_t chunk, torch::Tensor out, const torch::Tensor& lse,
-                                          const torch::Tensor* tree = nullptr) {
+                                          const torch::Tensor* tree = nullptr, const WindowOperand* win = nullptr) {
+  TORCH_CHECK(!(tree && win), what, ": a tree mask and a window do not go together");
+  if (win) check_window(what, *win);
   const ReadShape s = read_shape(what, kname, vname, fp8, q, k, v, table, out);
   TORCH_CHECK(chunk >= 1 && chunk <= INT32_MAX, what, ": chunk must be a positive int32, got ", chunk);
   const int64_t Smax = read_smax(what, k, table, s.B);
@@ -34,8 +36,19 @@ torch::Tensor block_attention_decode_impl(const char* what, const char* kname, c
 #define MI_DECODE_OPERANDS(CT) (int32_t) s.D, bits16(q), s.D, s.T* s.D, MI_READ_CACHE(CT), (int32_t)s.group, (int32_t)chunk, (float)scale
 #define MI_DECODE_OUT MI_READ_OUT, ws.data_ptr(), ws_bytes, stream_of(out)
 #define MI_DECODE_TREE tm.first, tm.second
+#define MI_DECODE_WINDOW (int32_t) win->window, (int32_t)win->sink
   int st;
-  if (tree && !fp8)
+  if (win && !fp8)
+    st = table ? (s.bf ? mi_block_attention_window_decode_paged_bf16 : mi_block_attention_window_decode_paged_f16)(
+                     MI_DECODE_LIST, MI_READ_TABLE, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_WINDOW, MI_DECODE_OUT)
+               : (s.bf ? mi_block_attention_window_decode_bf16 : mi_block_attention_window_decode_f16)(
+                     MI_DECODE_LIST, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_WINDOW, MI_DECODE_OUT);
+  else if (win)
+    st = table ? (s.bf ? mi_block_attention_window_decode_paged_fp8_bf16 : mi_block_attention_window_decode_paged_fp8_f16)(
+                     MI_DECODE_LIST, MI_READ_TABLE, MI_DECODE_OPERANDS(uint8_t), MI_READ_SCALES, MI_DECODE_WINDOW, MI_DECODE_OUT)
+               : (s.bf ? mi_block_attention_window_decode_fp8_bf16 : mi_block_attention_window_decode_fp8_f16)(
+                     MI_DECODE_LIST, MI_DECODE_OPERANDS(uint8_t), MI_READ_SCALES, MI_DECODE_WINDOW, MI_DECODE_OUT);
+  else if (tree && !fp8)
     st = table ? (s.bf ? mi_block_attention_tree_decode_paged_bf16 : mi_block_attention_tree_decode_paged_f16)(
                      MI_DECODE_LIST, MI_READ_TABLE, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_TREE, MI_DECODE_OUT)
                : (s.bf ? mi_block_attention_tree_decode_bf16 : mi_block_attention_tree_decode_f16)(
@@ -59,6 +72,7 @@ torch::Tensor block_attention_decode_impl(const char* what, const char* kname, c
 #undef MI_DECODE_OPERANDS
 #undef MI_DECODE_OUT
 #undef MI_DECODE_TREE
+#undef MI_DECODE_WINDOW
   check_status(st, what);
   return out;
 }
@@ -124,4 +138,42 @@ torch::Tensor block_attention_tree_decode_paged_fp8(torch::Tensor offsets, torch
                                                     torch::Tensor out, torch::Tensor lse) {
   return block_attention_decode_impl("block_attention_tree_decode_paged_fp8", "k_pages", "v_pages", true, offsets, columns, nnz, q,
                                      k_pages, v_pages, &block_table, k_lens, scale, k_scale, v_scale, chunk, out, lse, &tree_mask);
+}
+
+// … with a window (DESIGN.md §3.35): the four plain bindings with `window, sink` (ints, 1 ≤ window, 0 ≤ sink, both int32) before chunk
+torch::Tensor block_attention_window_decode(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q, torch::Tensor k,
+                                            torch::Tensor v, torch::Tensor k_lens, double scale, int64_t window, int64_t sink,
+                                            int64_t chunk, torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_decode_impl("block_attention_window_decode", "k", "v", false, offsets, columns, nnz, q, k, v, nullptr, k_lens,
+                                     scale, c10::nullopt, c10::nullopt, chunk, out, lse, nullptr, &win);
+}
+
+torch::Tensor block_attention_window_decode_paged(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q,
+                                                  torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table,
+                                                  torch::Tensor k_lens, double scale, int64_t window, int64_t sink, int64_t chunk,
+                                                  torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_decode_impl("block_attention_window_decode_paged", "k_pages", "v_pages", false, offsets, columns, nnz, q,
+                                     k_pages, v_pages, &block_table, k_lens, scale, c10::nullopt, c10::nullopt, chunk, out, lse, nullptr,
+                                     &win);
+}
+
+torch::Tensor block_attention_window_decode_fp8(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q,
+                                                torch::Tensor k, torch::Tensor v, torch::Tensor k_lens, double scale,
+                                                c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale,
+                                                int64_t window, int64_t sink, int64_t chunk, torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_decode_impl("block_attention_window_decode_fp8", "k", "v", true, offsets, columns, nnz, q, k, v, nullptr,
+                                     k_lens, scale, k_scale, v_scale, chunk, out, lse, nullptr, &win);
+}
+
+torch::Tensor block_attention_window_decode_paged_fp8(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q,
+                                                      torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table,
+                                                      torch::Tensor k_lens, double scale, c10::optional<torch::Tensor> k_scale,
+                                                      c10::optional<torch::Tensor> v_scale, int64_t window, int64_t sink,
+                                                      int64_t chunk, torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_decode_impl("block_attention_window_decode_paged_fp8", "k_pages", "v_pages", true, offsets, columns, nnz, q,
+                                     k_pages, v_pages, &block_table, k_lens, scale, k_scale, v_scale, chunk, out, lse, nullptr, &win);
 }

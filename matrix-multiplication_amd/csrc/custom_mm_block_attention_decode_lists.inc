@@ -14,7 +14,10 @@ torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kn
                                                 const torch::Tensor& k, const torch::Tensor& v, const torch::Tensor* table,
                                                 const torch::Tensor& k_lens, double scale, const c10::optional<torch::Tensor>& k_scale,
                                                 const c10::optional<torch::Tensor>& v_scale, int64_t chunk, torch::Tensor out,
-                                                const torch::Tensor& lse, const torch::Tensor* tree = nullptr) {
+                                                const torch::Tensor& lse, const torch::Tensor* tree = nullptr,
+                                                const WindowOperand* win = nullptr) {
+  TORCH_CHECK(!(tree && win), what, ": a tree mask and a window do not go together");
+  if (win) check_window(what, *win);
   const ReadShape s = read_shape(what, kname, vname, fp8, q, k, v, table, out);
   TORCH_CHECK(chunk >= 1 && chunk <= INT32_MAX, what, ": chunk must be a positive int32, got ", chunk);
   const int64_t Smax = read_smax(what, k, table, s.B);
@@ -44,8 +47,19 @@ torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kn
 #define MI_LISTS_OPERANDS(CT) (int32_t) s.D, bits16(q), s.D, s.T* s.D, MI_READ_CACHE(CT), (int32_t)s.group, (int32_t)chunk, (float)scale
 #define MI_LISTS_OUT MI_READ_OUT, ws.data_ptr(), ws_bytes, stream_of(out)
 #define MI_LISTS_TREE tm.first, tm.second
+#define MI_LISTS_WINDOW (int32_t) win->window, (int32_t)win->sink
   int st;
-  if (tree && fp8)
+  if (win && fp8)
+    st = table ? (s.bf ? mi_block_attention_window_decode_lists_paged_fp8_bf16 : mi_block_attention_window_decode_lists_paged_fp8_f16)(
+                     MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_WINDOW, MI_LISTS_OUT)
+               : (s.bf ? mi_block_attention_window_decode_lists_fp8_bf16 : mi_block_attention_window_decode_lists_fp8_f16)(
+                     MI_LISTS_HEAD, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_WINDOW, MI_LISTS_OUT);
+  else if (win)
+    st = table ? (s.bf ? mi_block_attention_window_decode_lists_paged_bf16 : mi_block_attention_window_decode_lists_paged_f16)(
+                     MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint16_t), MI_LISTS_WINDOW, MI_LISTS_OUT)
+               : (s.bf ? mi_block_attention_window_decode_lists_bf16 : mi_block_attention_window_decode_lists_f16)(
+                     MI_LISTS_HEAD, MI_LISTS_OPERANDS(uint16_t), MI_LISTS_WINDOW, MI_LISTS_OUT);
+  else if (tree && fp8)
     st = table ? (s.bf ? mi_block_attention_tree_decode_lists_paged_fp8_bf16 : mi_block_attention_tree_decode_lists_paged_fp8_f16)(
                      MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_TREE, MI_LISTS_OUT)
                : (s.bf ? mi_block_attention_tree_decode_lists_fp8_bf16 : mi_block_attention_tree_decode_lists_fp8_f16)(
@@ -69,6 +83,7 @@ torch::Tensor block_attention_decode_lists_impl(const char* what, const char* kn
 #undef MI_LISTS_OPERANDS
 #undef MI_LISTS_OUT
 #undef MI_LISTS_TREE
+#undef MI_LISTS_WINDOW
   check_status(st, what);
   return out;
 }
@@ -138,4 +153,44 @@ torch::Tensor block_attention_tree_lists_decode_paged_fp8(torch::Tensor block_id
   return block_attention_decode_lists_impl("block_attention_tree_lists_decode_paged_fp8", "k_pages", "v_pages", true, block_ids,
                                            block_counts, q, k_pages, v_pages, &block_table, k_lens, scale, k_scale, v_scale, chunk, out,
                                            lse, &tree_mask);
+}
+
+// … with a window (DESIGN.md §3.35): the four plain bindings with `window, sink` before chunk
+torch::Tensor block_attention_window_decode_lists(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q, torch::Tensor k,
+                                                  torch::Tensor v, torch::Tensor k_lens, double scale, int64_t window, int64_t sink,
+                                                  int64_t chunk, torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_decode_lists_impl("block_attention_window_decode_lists", "k", "v", false, block_ids, block_counts, q, k, v,
+                                           nullptr, k_lens, scale, c10::nullopt, c10::nullopt, chunk, out, lse, nullptr, &win);
+}
+
+torch::Tensor block_attention_window_decode_lists_paged(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q,
+                                                        torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table,
+                                                        torch::Tensor k_lens, double scale, int64_t window, int64_t sink, int64_t chunk,
+                                                        torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_decode_lists_impl("block_attention_window_decode_lists_paged", "k_pages", "v_pages", false, block_ids,
+                                           block_counts, q, k_pages, v_pages, &block_table, k_lens, scale, c10::nullopt, c10::nullopt,
+                                           chunk, out, lse, nullptr, &win);
+}
+
+torch::Tensor block_attention_window_lists_decode_fp8(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q,
+                                                      torch::Tensor k, torch::Tensor v, torch::Tensor k_lens, double scale,
+                                                      c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale,
+                                                      int64_t window, int64_t sink, int64_t chunk, torch::Tensor out,
+                                                      torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_decode_lists_impl("block_attention_window_lists_decode_fp8", "k", "v", true, block_ids, block_counts, q, k, v,
+                                           nullptr, k_lens, scale, k_scale, v_scale, chunk, out, lse, nullptr, &win);
+}
+
+torch::Tensor block_attention_window_lists_decode_paged_fp8(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q,
+                                                            torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table,
+                                                            torch::Tensor k_lens, double scale, c10::optional<torch::Tensor> k_scale,
+                                                            c10::optional<torch::Tensor> v_scale, int64_t window, int64_t sink,
+                                                            int64_t chunk, torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_decode_lists_impl("block_attention_window_lists_decode_paged_fp8", "k_pages", "v_pages", true, block_ids,
+                                           block_counts, q, k_pages, v_pages, &block_table, k_lens, scale, k_scale, v_scale, chunk, out,
+                                           lse, nullptr, &win);
 }

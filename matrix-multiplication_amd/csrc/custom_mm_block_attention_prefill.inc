@@ -17,7 +17,10 @@ torch::Tensor block_attention_prefill_impl(const char* what, const char* kname, 
                                            const torch::Tensor& v, const torch::Tensor* table, const torch::Tensor& k_lens,
                                            const c10::optional<torch::Tensor>& new_lens, double scale,
                                            const c10::optional<torch::Tensor>& k_scale, const c10::optional<torch::Tensor>& v_scale,
-                                           torch::Tensor out, const torch::Tensor& lse, int64_t split = 0) {
+                                           torch::Tensor out, const torch::Tensor& lse, int64_t split = 0,
+                                           const WindowOperand* win = nullptr) {
+  TORCH_CHECK(!(split != 0 && win), what, ": split and a window do not go together");
+  if (win) check_window(what, *win);
   const ReadShape s = read_shape(what, kname, vname, fp8, q, k, v, table, out);
   const int64_t Smax = read_smax(what, k, table, s.B);
   const BlockLayout lay = block_layout(what, offsets, columns, nnz, Smax, Smax);
@@ -51,8 +54,19 @@ torch::Tensor block_attention_prefill_impl(const char* what, const char* kname, 
       (int32_t)s.group, (float)scale
 #define MI_PREFILL_OUT MI_READ_OUT, stream_of(out)
 #define MI_PREFILL_SPLIT_OUT MI_READ_OUT, (int32_t)split, ws.data_ptr(), (size_t)ws_bytes, stream_of(out)
+#define MI_PREFILL_WINDOW_OUT (int32_t) win->window, (int32_t)win->sink, MI_PREFILL_OUT
   int st;
-  if (split != 0 && !fp8)
+  if (win && !fp8)
+    st = table ? (s.bf ? mi_block_attention_window_prefill_paged_bf16 : mi_block_attention_window_prefill_paged_f16)(
+                     MI_PREFILL_LIST, MI_READ_TABLE, MI_PREFILL_OPERANDS(uint16_t), MI_PREFILL_WINDOW_OUT)
+               : (s.bf ? mi_block_attention_window_prefill_bf16 : mi_block_attention_window_prefill_f16)(
+                     MI_PREFILL_LIST, MI_PREFILL_OPERANDS(uint16_t), MI_PREFILL_WINDOW_OUT);
+  else if (win)
+    st = table ? (s.bf ? mi_block_attention_window_prefill_paged_fp8_bf16 : mi_block_attention_window_prefill_paged_fp8_f16)(
+                     MI_PREFILL_LIST, MI_READ_TABLE, MI_PREFILL_OPERANDS(uint8_t), MI_READ_SCALES, MI_PREFILL_WINDOW_OUT)
+               : (s.bf ? mi_block_attention_window_prefill_fp8_bf16 : mi_block_attention_window_prefill_fp8_f16)(
+                     MI_PREFILL_LIST, MI_PREFILL_OPERANDS(uint8_t), MI_READ_SCALES, MI_PREFILL_WINDOW_OUT);
+  else if (split != 0 && !fp8)
     st = table ? (s.bf ? mi_block_attention_prefill_split_paged_bf16 : mi_block_attention_prefill_split_paged_f16)(
                      MI_PREFILL_LIST, MI_READ_TABLE, MI_PREFILL_OPERANDS(uint16_t), MI_PREFILL_SPLIT_OUT)
                : (s.bf ? mi_block_attention_prefill_split_bf16 : mi_block_attention_prefill_split_f16)(
@@ -76,6 +90,7 @@ torch::Tensor block_attention_prefill_impl(const char* what, const char* kname, 
 #undef MI_PREFILL_OPERANDS
 #undef MI_PREFILL_OUT
 #undef MI_PREFILL_SPLIT_OUT
+#undef MI_PREFILL_WINDOW_OUT
   check_status(st, what);
   return out;
 }
@@ -153,4 +168,39 @@ torch::Tensor block_attention_prefill_split_paged_fp8(torch::Tensor offsets, tor
   check_split("block_attention_prefill_split_paged_fp8", split);
   return block_attention_prefill_impl("block_attention_prefill_split_paged_fp8", "k_pages", "v_pages", true, offsets, columns, nnz, q,
                                       k_pages, v_pages, &block_table, k_lens, new_lens, scale, k_scale, v_scale, out, lse, split);
+}
+
+// … with a window (DESIGN.md §3.35): the four unsplit bindings with `window, sink` (ints, 1 ≤ window, 0 ≤ sink, both int32) before out
+torch::Tensor block_attention_window_prefill(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens, double scale, int64_t window, int64_t sink,
+    torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_prefill_impl("block_attention_window_prefill", "k", "v", false, offsets, columns, nnz, q, k, v, nullptr, k_lens,
+      new_lens, scale, c10::nullopt, c10::nullopt, out, lse, 0, &win);
+}
+
+torch::Tensor block_attention_window_prefill_fp8(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q,
+    torch::Tensor k, torch::Tensor v, torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens, double scale,
+    c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale, int64_t window, int64_t sink,
+    torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_prefill_impl("block_attention_window_prefill_fp8", "k", "v", true, offsets, columns, nnz, q, k, v, nullptr,
+      k_lens, new_lens, scale, k_scale, v_scale, out, lse, 0, &win);
+}
+
+torch::Tensor block_attention_window_prefill_paged(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q,
+    torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table, torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens,
+    double scale, int64_t window, int64_t sink, torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_prefill_impl("block_attention_window_prefill_paged", "k_pages", "v_pages", false, offsets, columns, nnz, q,
+      k_pages, v_pages, &block_table, k_lens, new_lens, scale, c10::nullopt, c10::nullopt, out, lse, 0, &win);
+}
+
+torch::Tensor block_attention_window_prefill_paged_fp8(torch::Tensor offsets, torch::Tensor columns, int64_t nnz, torch::Tensor q,
+    torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table, torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens,
+    double scale, c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale, int64_t window, int64_t sink,
+    torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_prefill_impl("block_attention_window_prefill_paged_fp8", "k_pages", "v_pages", true, offsets, columns, nnz, q,
+      k_pages, v_pages, &block_table, k_lens, new_lens, scale, k_scale, v_scale, out, lse, 0, &win);
 }

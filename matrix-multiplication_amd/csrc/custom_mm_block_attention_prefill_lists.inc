@@ -17,7 +17,8 @@ torch::Tensor block_attention_prefill_lists_impl(const char* what, const char* k
                                                  const torch::Tensor& k, const torch::Tensor& v, const torch::Tensor* table,
                                                  const torch::Tensor& k_lens, const c10::optional<torch::Tensor>& new_lens, double scale,
                                                  const c10::optional<torch::Tensor>& k_scale, const c10::optional<torch::Tensor>& v_scale,
-                                                 torch::Tensor out, const torch::Tensor& lse) {
+                                                 torch::Tensor out, const torch::Tensor& lse, const WindowOperand* win = nullptr) {
+  if (win) check_window(what, *win);
   const ReadShape s = read_shape(what, kname, vname, fp8, q, k, v, table, out);
   const int64_t Smax = read_smax(what, k, table, s.B);
   TORCH_CHECK(Smax % 64 == 0, what, ": Smax = ", Smax, " must be a multiple of 64");
@@ -52,8 +53,19 @@ torch::Tensor block_attention_prefill_lists_impl(const char* what, const char* k
   (int32_t) s.D, bits16(q), cache_stride(q, 2, s.D), cache_stride(q, 1, 0), cache_stride(q, 0, 0), MI_READ_CACHE(CT), nl, nl_count, \
       (int32_t)s.group, (float)scale
 #define MI_LISTS_OUT MI_READ_OUT, stream_of(out)
+#define MI_LISTS_WINDOW_OUT (int32_t) win->window, (int32_t)win->sink, MI_LISTS_OUT
   int st;
-  if (fp8)
+  if (win && fp8)
+    st = table ? (s.bf ? mi_block_attention_window_prefill_lists_paged_fp8_bf16 : mi_block_attention_window_prefill_lists_paged_fp8_f16)(
+                     MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_WINDOW_OUT)
+               : (s.bf ? mi_block_attention_window_prefill_lists_fp8_bf16 : mi_block_attention_window_prefill_lists_fp8_f16)(
+                     MI_LISTS_HEAD, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_WINDOW_OUT);
+  else if (win)
+    st = table ? (s.bf ? mi_block_attention_window_prefill_lists_paged_bf16 : mi_block_attention_window_prefill_lists_paged_f16)(
+                     MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint16_t), MI_LISTS_WINDOW_OUT)
+               : (s.bf ? mi_block_attention_window_prefill_lists_bf16 : mi_block_attention_window_prefill_lists_f16)(
+                     MI_LISTS_HEAD, MI_LISTS_OPERANDS(uint16_t), MI_LISTS_WINDOW_OUT);
+  else if (fp8)
     st = table ? (s.bf ? mi_block_attention_lists_prefill_paged_fp8_bf16 : mi_block_attention_lists_prefill_paged_fp8_f16)(
                      MI_LISTS_HEAD, MI_READ_TABLE, MI_LISTS_OPERANDS(uint8_t), MI_READ_SCALES, MI_LISTS_OUT)
                : (s.bf ? mi_block_attention_lists_prefill_fp8_bf16 : mi_block_attention_lists_prefill_fp8_f16)(
@@ -66,6 +78,7 @@ torch::Tensor block_attention_prefill_lists_impl(const char* what, const char* k
 #undef MI_LISTS_HEAD
 #undef MI_LISTS_OPERANDS
 #undef MI_LISTS_OUT
+#undef MI_LISTS_WINDOW_OUT
   check_status(st, what);
   return out;
 }
@@ -102,4 +115,39 @@ torch::Tensor block_attention_prefill_lists_paged_fp8(torch::Tensor block_ids, t
   return block_attention_prefill_lists_impl("block_attention_lists_prefill_paged_fp8", "k_pages", "v_pages", true, block_ids,
                                             block_counts, q, k_pages, v_pages, &block_table, k_lens, new_lens, scale, k_scale, v_scale,
                                             out, lse);
+}
+
+// … with a window (DESIGN.md §3.35): the four bindings with `window, sink` before out, named block_attention_window_lists_prefill…
+torch::Tensor block_attention_window_prefill_lists(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens, double scale, int64_t window, int64_t sink,
+    torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_prefill_lists_impl("block_attention_window_lists_prefill", "k", "v", false, block_ids, block_counts, q, k, v,
+      nullptr, k_lens, new_lens, scale, c10::nullopt, c10::nullopt, out, lse, &win);
+}
+
+torch::Tensor block_attention_window_prefill_lists_fp8(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q,
+    torch::Tensor k, torch::Tensor v, torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens, double scale,
+    c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale, int64_t window, int64_t sink,
+    torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_prefill_lists_impl("block_attention_window_lists_prefill_fp8", "k", "v", true, block_ids, block_counts, q, k, v,
+      nullptr, k_lens, new_lens, scale, k_scale, v_scale, out, lse, &win);
+}
+
+torch::Tensor block_attention_window_prefill_lists_paged(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q,
+    torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table, torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens,
+    double scale, int64_t window, int64_t sink, torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_prefill_lists_impl("block_attention_window_lists_prefill_paged", "k_pages", "v_pages", false, block_ids,
+      block_counts, q, k_pages, v_pages, &block_table, k_lens, new_lens, scale, c10::nullopt, c10::nullopt, out, lse, &win);
+}
+
+torch::Tensor block_attention_window_prefill_lists_paged_fp8(torch::Tensor block_ids, torch::Tensor block_counts, torch::Tensor q,
+    torch::Tensor k_pages, torch::Tensor v_pages, torch::Tensor block_table, torch::Tensor k_lens, c10::optional<torch::Tensor> new_lens,
+    double scale, c10::optional<torch::Tensor> k_scale, c10::optional<torch::Tensor> v_scale, int64_t window, int64_t sink,
+    torch::Tensor out, torch::Tensor lse) {
+  const WindowOperand win = {window, sink};
+  return block_attention_prefill_lists_impl("block_attention_window_lists_prefill_paged_fp8", "k_pages", "v_pages", true, block_ids,
+      block_counts, q, k_pages, v_pages, &block_table, k_lens, new_lens, scale, k_scale, v_scale, out, lse, &win);
 }

@@ -201,6 +201,16 @@ std::pair<const int64_t*, int32_t> tree_mask_operand(const char* what, const tor
   return {mask.data_ptr<int64_t>(), shared ? 1 : (int32_t)B};
 }
 
+// The window of the block_attention_window_… bindings (DESIGN.md §3.35): the token sees its last `window` keys, itself included, and
+// the first `sink` keys of the cache — two int32s, 1 <= window, 0 <= sink
+struct WindowOperand {
+  int64_t window, sink;
+};
+void check_window(const char* what, const WindowOperand& w) {
+  TORCH_CHECK(w.window >= 1 && w.window <= INT32_MAX, what, ": window must be a positive int32, got ", w.window);
+  TORCH_CHECK(w.sink >= 0 && w.sink <= INT32_MAX, what, ": sink must be an int32 >= 0, got ", w.sink);
+}
+
 // the writing calls' cache: of the source's dtype `dt` (a bit copy) or float8_e4m3fn; returns whether it is fp8
 bool written_cache_is_fp8(const char* what, const char* kname, const char* vname, torch::ScalarType dt, const torch::Tensor& k,
                           const torch::Tensor& v, const c10::optional<torch::Tensor>& k_scale,

@@ -1984,6 +1984,56 @@ def _tree_binding(name: str) -> str:
     return 'block_attention_tree_' + name[len('block_attention_'):]
 
 
+def _window_binding(name: str) -> str:
+    '''The binding of a reading call with a window: block_attention_window_… for block_attention_… (window and sink stand
+    ahead of chunk in the decode bindings, ahead of out in the prefill bindings).'''
+    return 'block_attention_window_' + name[len('block_attention_'):]
+
+
+def _check_window(what, window, sink, tree_mask=None, split=None):
+    '''The window= and sink= operands of the sixteen reading calls: window None or a Python int in
+    [1, 2³¹ − 1], sink a Python int in [0, 2³¹ − 1] and 0 without a window; no tree mask (the decode calls) and no split (the
+    prefill calls) beside a window.  ValueError naming the operand.  Returns the two ints as the binding takes them — () for
+    window=None, the call without them.'''
+    for name, x, lo in (('window', window, 1), ('sink', sink, 0)):
+        if name == 'window' and x is None:
+            continue
+        if not _is_int(x) or isinstance(x, bool) or x < lo or x >= 2 ** 31:
+            raise ValueError(f'{what}: {name} must be {"None or " if lo else ""}a Python int in [{lo}, 2^31 - 1], got {x!r}')
+    if window is None:
+        if sink != 0:
+            raise ValueError(f'{what}: sink = {sink} needs a window: sink keys are what a window keeps of the keys behind it')
+        return ()
+    if tree_mask is not None:
+        raise ValueError(f'{what}: window and tree_mask do not go together: in a tree the window\'s edge belongs to prefix + depth, '
+                         f'not to the slot')
+    if split is not None:
+        raise ValueError(f'{what}: window and split do not go together: a windowed row\'s list is short, and the split exists for '
+                         f'long lists')
+    return (int(window), int(sink))
+
+
+def sliding_window_layout(Smax: int, window: int, sink: int = 0, block: int = 64, device=None) -> torch.Tensor:
+    '''The smallest causal block layout that covers the rule of window= and sink=: a dense bool tensor
+    [Smax/block, Smax/block] on `device` whose block (r, c) is kept iff c ≤ r and SOME position pos of block row r sees SOME
+    key j of block column c under j ≤ pos and (j > pos − window or j < sink) — the diagonal, the columns that the window of
+    the row's first position still reaches (window ≥ (r − c − 1) · block + 2), and the columns that hold a sink key
+    (c · block < sink).  layout.to_sparse_csr() is what the decode and prefill calls take: with it a token's walk reads about
+    window / block + 1 blocks, not its whole prefix; the window itself is cut to the key by the calls' window= and sink=.
+    Smax a positive multiple of block, block a positive multiple of 64, window ≥ 1, sink ≥ 0: Python ints (ValueError).
+    torch operators only and no read-back: the call can be captured in a graph.'''
+    what = 'sliding_window_layout'
+    for name, x, lo in (('Smax', Smax, 1), ('window', window, 1), ('sink', sink, 0), ('block', block, 1)):
+        if not _is_int(x) or x < lo or x >= 2 ** 31:
+            raise ValueError(f'{what}: {name} must be a Python int in [{lo}, 2^31 - 1], got {x!r}')
+    if block % _BLOCK_TILE != 0 or Smax % block != 0:
+        raise ValueError(f'{what}: block = {block} must be a multiple of 64 and Smax = {Smax} a multiple of block')
+    n = Smax // block
+    r = torch.arange(n, device=device, dtype=torch.int64)[:, None]
+    c = torch.arange(n, device=device, dtype=torch.int64)[None, :]
+    return (c <= r) & ((c == r) | (c * block < sink) | ((r - c - 1) * block + 2 <= window))
+
+
 def _check_tree_mask(what, tree_mask, B, T, q):
     '''The tree_mask operand of the eight decode calls: a contiguous int64 tensor [B, T], or [T] for the whole
     batch, T ≤ 64 — ValueError for what it is, RuntimeError for another device than q's.  Returns it by name for
@@ -2089,12 +2139,15 @@ _DECODE_BINDINGS = (('block_attention_decode', 'block_attention_decode_fp8'),  #
                     ('block_attention_decode_paged', 'block_attention_decode_paged_fp8'))
 
 
-def _decode(what, names, q, k, v, block_table, layout, k_lens, block, scale, chunk, k_scale, v_scale, fp8, return_lse, tree_mask=None):
+def _decode(what, names, q, k, v, block_table, layout, k_lens, block, scale, chunk, k_scale, v_scale, fp8, return_lse, tree_mask=None,
+            window=None, sink=0):
     '''The one body of the four decode calls: the checks, the defaults, the operands as the binding takes them, one binding
     call.  `names` as in _check_block_attention_decode_operands; block_table, k_scale and v_scale are looked at by the paged
     and the fp8 forms only.  tree_mask: None — the binding and the arguments of the call without it — or the mask, which goes
-    to the binding's block_attention_tree_… form (_tree_binding) ahead of chunk.'''
+    to the binding's block_attention_tree_… form (_tree_binding) ahead of chunk.  window, sink: likewise — None and 0: the call
+    without them; else two ints to the block_attention_window_… form (_window_binding) ahead of chunk.'''
     paged = names[0] == 'k_pages'
+    win = _check_window(what, window, sink, tree_mask)
     scales = (('k_scale', k_scale), ('v_scale', v_scale)) if fp8 else ()
     Smax = _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8, scales, block_table,
                                                   tree_mask=tree_mask)
@@ -2113,15 +2166,17 @@ def _decode(what, names, q, k, v, block_table, layout, k_lens, block, scale, chu
         lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
         if out.numel() > 0:
             tree = () if tree_mask is None else (tree_mask.detach(),)
-            binding = getattr(custom_mm, _tree_binding(_DECODE_BINDINGS[paged][fp8]) if tree else _DECODE_BINDINGS[paged][fp8])
+            name = _DECODE_BINDINGS[paged][fp8]
+            binding = getattr(custom_mm, _tree_binding(name) if tree else _window_binding(name) if win else name)
             fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
-            binding(offsets, columns, nnz, qc, k.detach(), v.detach(), *table, lens, float(scale), *fp8_scales, *tree, int(chunk), out,
-                    lse)
+            binding(offsets, columns, nnz, qc, k.detach(), v.detach(), *table, lens, float(scale), *fp8_scales, *tree, *win, int(chunk),
+                    out, lse)
     return (out, lse) if return_lse else out
 
 
 def block_sparse_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
-                                  block: int = 64, scale=None, *, chunk=None, return_lse: bool = False, tree_mask=None):
+                                  block: int = 64, scale=None, *, chunk=None, return_lse: bool = False, tree_mask=None,
+                                  window=None, sink: int = 0):
     '''Block-sparse attention of the T ≥ 1 newest tokens of every item against its key / value cache, on the matrix cores:
     q [B, Hq, T, D] (contiguous or made so: it is small), k and v [B, Hkv, Smax, D] — the cache, with the new tokens' keys
     and values already written —, all bfloat16 or all float16, Hq = G · Hkv with 1 ≤ G ≤ 16 (query head h reads k / v head
@@ -2165,9 +2220,23 @@ def block_sparse_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Ten
     never loaded, its score −inf — NaN or inf in a hidden draft slot reaches no output.  Chunks, the deal to the waves, the
     order of the merges, out and lse are unchanged.  The mask is handed over as it is and never read back: a captured graph
     follows in-place updates.  ValueError for another dtype or shape, T > 64 or a non-contiguous mask, RuntimeError for a host
-    tensor or another device — before the first device call.'''
+    tensor or another device — before the first device call.
+
+    window, sink (keyword only): a SLIDING WINDOW with sink keys.  window=None (the default) is the call
+    without one; else a Python int 1 ≤ window ≤ 2³¹ − 1, and sink a Python int 0 ≤ sink ≤ 2³¹ − 1 (0 without a window).
+    The token at pos sees key j iff the rule above holds AND (j > pos − window or j < sink): its last `window` keys, ITSELF
+    INCLUDED, and the first `sink` keys of the cache.  This is Hugging Face's sliding_window and FlashAttention's
+    window_size = (window − 1, 0); window=1 sees the token itself and the sinks.  The window is exact to the key, whatever
+    pos % 64 is; the layout still says which blocks are walked, so pair it with sliding_window_layout(Smax, window, sink),
+    the smallest layout that covers the rule: about window / 64 + 1 blocks per token.  A hidden key is treated like a key
+    beyond pos: never loaded, its score −inf — NaN or inf there reaches no output; a listed block that the window hides
+    wholly is skipped in its list position, so chunks, the deal to the waves and the order of the merges do not move, and
+    window = 2³¹ − 1 or sink ≥ Smax gives the bits of the call without a window.  A token that sees nothing has a zero row
+    and lse −inf.  Both values are Python ints, baked into a captured graph.  ValueError for a bool, a tensor or a value
+    out of range, for sink without window, and for window together with tree_mask (a tree's window edge belongs to
+    prefix + depth, not to the slot) — before the first device call.'''
     return _decode('block_sparse_attention_decode', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, chunk, None, None, False,
-                   return_lse, tree_mask=tree_mask)
+                   return_lse, tree_mask=tree_mask, window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -2183,7 +2252,8 @@ def block_attention_decode_paged_takes(dtype, D: int, block: int, group: int, pa
 
 def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
                                         layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *, chunk=None,
-                                        return_lse: bool = False, tree_mask=None):
+                                        return_lse: bool = False, tree_mask=None,
+                                        window=None, sink: int = 0):
     '''block_sparse_attention_decode over a PAGED cache: k_pages and v_pages [P, Hkv, page, D] are one pool of pages of
     `page` keys (a power of two ≥ 16, taken from the pool's shape) and block_table [B, W] maps the logical pages of every
     item to pool pages: key j of batch item b, k / v head h, is row j % page of head h of pool page block_table[b, j // page].
@@ -2204,9 +2274,11 @@ def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, 
     block_sparse_attention_decode with the same chunk on the cache gathered to [B, Hkv, Smax, D] — so they do not depend
     on P, on where the pages lie, or on `page`.  No atomics, no read-back: graph-capturable, and one captured graph keeps
     serving while k_lens, the pool and the block table are updated in place.  NO autograd.  For T beyond a few tokens use
-    block_sparse_attention_prefill_paged.  tree_mask: as in block_sparse_attention_decode.'''
+    block_sparse_attention_prefill_paged.  tree_mask: as in block_sparse_attention_decode.
+    window, sink (keyword only): as in block_sparse_attention_decode — the token sees its last `window` keys,
+    itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys.'''
     return _decode('block_sparse_attention_decode_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens, block,
-                   scale, chunk, None, None, False, return_lse, tree_mask=tree_mask)
+                   scale, chunk, None, None, False, return_lse, tree_mask=tree_mask, window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -2301,7 +2373,8 @@ def kv_to_fp8(x: torch.Tensor, scale=None):
 
 def block_sparse_attention_decode_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
                                       block: int = 64, scale=None, *, k_scale=None, v_scale=None, chunk=None,
-                                      return_lse: bool = False, tree_mask=None):
+                                      return_lse: bool = False, tree_mask=None,
+                                      window=None, sink: int = 0):
     '''block_sparse_attention_decode over an FP8 cache: q [B, Hq, T, D] bfloat16 or float16, k and v [B, Hkv, Smax, D]
     torch.float8_e4m3fn — the OCP encoding, gfx950's native one; float8_e4m3fnuz, float8_e5m2 and uint8 raise ValueError —
     with the real key k8 · k_scale[h] and the real value v8 · v_scale[h].  Everything else — the visibility rule, the
@@ -2323,14 +2396,17 @@ def block_sparse_attention_decode_fp8(q: torch.Tensor, k: torch.Tensor, v: torch
     and lse are bit for bit those of block_sparse_attention_decode on k.to(q.dtype), v.to(q.dtype) with the same chunk;
     with k_scale = s for all heads and v_scale = 2^n, out is that call\'s result at scale\' = float32(scale) · float32(s)
     times 2^n, and lse that call\'s.  Nothing beyond pos, in an unlisted block or between the rows is loaded: a NaN byte
-    there reaches no output.  For T beyond a few tokens use block_sparse_attention_prefill_fp8.  tree_mask: as in block_sparse_attention_decode.'''
+    there reaches no output.  For T beyond a few tokens use block_sparse_attention_prefill_fp8.  tree_mask: as in block_sparse_attention_decode.
+    window, sink (keyword only): as in block_sparse_attention_decode — the token sees its last `window` keys,
+    itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys.'''
     return _decode('block_sparse_attention_decode_fp8', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, chunk, k_scale, v_scale,
-                   True, return_lse, tree_mask=tree_mask)
+                   True, return_lse, tree_mask=tree_mask, window=window, sink=sink)
 
 
 def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
                                             layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *,
-                                            k_scale=None, v_scale=None, chunk=None, return_lse: bool = False, tree_mask=None):
+                                            k_scale=None, v_scale=None, chunk=None, return_lse: bool = False, tree_mask=None,
+                                            window=None, sink: int = 0):
     '''block_sparse_attention_decode_paged over an FP8 pool: k_pages and v_pages [P, Hkv, page, D] torch.float8_e4m3fn
     with k_scale / v_scale as in block_sparse_attention_decode_fp8, everything else — the table, the pages (a power of two
     ≥ 16 keys), entries outside [0, P) hiding their page, the refusals — as in block_sparse_attention_decode_paged
@@ -2340,9 +2416,11 @@ def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tens
     Bits: for in-range tables, out and lse are bit for bit those of block_sparse_attention_decode_fp8 with the same chunk
     and scales on the gathered cache; with both scales None, those of block_sparse_attention_decode_paged on the pool
     widened to q\'s type.  Nothing in an invalid page is loaded.  Graph-capturable while k_lens, the pool, the table and
-    the scale tensors are updated in place.  For T beyond a few tokens use block_sparse_attention_prefill_paged_fp8.  tree_mask: as in block_sparse_attention_decode.'''
+    the scale tensors are updated in place.  For T beyond a few tokens use block_sparse_attention_prefill_paged_fp8.  tree_mask: as in block_sparse_attention_decode.
+    window, sink (keyword only): as in block_sparse_attention_decode — the token sees its last `window` keys,
+    itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys.'''
     return _decode('block_sparse_attention_decode_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens,
-                   block, scale, chunk, k_scale, v_scale, True, return_lse, tree_mask=tree_mask)
+                   block, scale, chunk, k_scale, v_scale, True, return_lse, tree_mask=tree_mask, window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -2406,11 +2484,14 @@ def block_attention_prefill_split(B: int, Hq: int, T: int, Smax: int, D: int):
     return max(16, 1 << (per_part.bit_length() - 1))
 
 
-def _prefill(what, names, q, k, v, block_table, layout, k_lens, block, scale, new_lens, k_scale, v_scale, fp8, return_lse, split=None):
+def _prefill(what, names, q, k, v, block_table, layout, k_lens, block, scale, new_lens, k_scale, v_scale, fp8, return_lse, split=None,
+             window=None, sink=0):
     '''The one body of the four prefill calls, beside _decode: the decode calls' checks with what differs given as
     parameters, the defaults, the operands as the binding takes them — q AS IT IS, through its own strides —, one binding
-    call: split None the unsplit binding with its own argument list, an int the split binding with that int behind it.'''
+    call: split None the unsplit binding with its own argument list, an int the split binding with that int behind it;
+    window None likewise, an int the block_attention_window_… binding (_window_binding) with window and sink ahead of out.'''
     paged = names[0] == 'k_pages'
+    win = _check_window(what, window, sink, split=split)
     scales = (('k_scale', k_scale), ('v_scale', v_scale)) if fp8 else ()
     _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, None, fp8, scales, block_table,
                                            sizes_text=_PREFILL_FP8_SIZES_TEXT if fp8 else _PREFILL_SIZES_TEXT, max_group=None,
@@ -2427,15 +2508,17 @@ def _prefill(what, names, q, k, v, block_table, layout, k_lens, block, scale, ne
         out = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
         lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
         if out.numel() > 0:
-            binding = getattr(custom_mm, (_PREFILL_BINDINGS if split is None else _PREFILL_SPLIT_BINDINGS)[paged][fp8])
+            name = (_PREFILL_BINDINGS if split is None else _PREFILL_SPLIT_BINDINGS)[paged][fp8]
+            binding = getattr(custom_mm, _window_binding(name) if win else name)
             fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
-            binding(offsets, columns, nnz, q.detach(), k.detach(), v.detach(), *table, lens, news, float(scale), *fp8_scales, out, lse,
-                    *(() if split is None else (int(split),)))
+            binding(offsets, columns, nnz, q.detach(), k.detach(), v.detach(), *table, lens, news, float(scale), *fp8_scales, *win, out,
+                    lse, *(() if split is None else (int(split),)))
     return (out, lse) if return_lse else out
 
 
 def block_sparse_attention_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
-                                   block: int = 64, scale=None, *, new_lens=None, return_lse: bool = False, split=None):
+                                   block: int = 64, scale=None, *, new_lens=None, return_lse: bool = False, split=None,
+                                   window=None, sink: int = 0):
     '''Block-sparse attention of the T ≥ 1 newest tokens of every item — a whole prompt, or one CHUNK of it behind a prefix
     that is already cached — against its key / value cache, on the matrix cores: the read side of `lens += new;
     rope_kv_cache_append(…, new_lens)`.  q [B, Hq, T, D] bfloat16 or float16; k, v [B, Hkv, Smax, D] — the cache of
@@ -2488,14 +2571,25 @@ def block_sparse_attention_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Te
     Returns a fresh contiguous out [B, Hq, T, D] in q's dtype, every row written exactly once by ONE launch (split: by the
     second of two), or with return_lse=True (out, lse) with lse float32 [B, Hq, T].  NO autograd, no atomics, no
     read-back, no workspace without split: the call can be captured in a graph and replayed while k_lens, new_lens and
-    the cache change in place.  scale defaults to 1/√D.'''
+    the cache change in place.  scale defaults to 1/√D.
+
+    window, sink (keyword only): block_sparse_attention_decode's, word for word — window=None the call without
+    one, else Python ints 1 ≤ window ≤ 2³¹ − 1 and 0 ≤ sink ≤ 2³¹ − 1: the token at pos sees key j iff the rule above holds
+    AND (j > pos − window or j < sink), its last `window` keys ITSELF INCLUDED plus the first `sink` keys — Hugging Face's
+    sliding_window, FlashAttention's window_size = (window − 1, 0).  The rows of a tile have different edges, so the test is
+    made per element beside the diagonal's; a listed block J with 64 J ≥ sink and 64 J + 63 ≤ 64 r − window, r the tile's
+    layout row, is hidden from every position of the tile and is never loaded.  Pair it with sliding_window_layout(Smax,
+    window, sink).  Everything else is unchanged: 100 tokens equal chunks of 60 and 40, window = 2³¹ − 1 or sink ≥ Smax gives
+    the bits of the call without a window.  ValueError for a bool, a tensor or a value out of range, for sink without window,
+    and for window together with split (a windowed row's list is short; the split exists for long lists).'''
     return _prefill('block_sparse_attention_prefill', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, new_lens, None, None,
-                    False, return_lse, split)
+                    False, return_lse, split, window, sink)
 
 
 def block_sparse_attention_prefill_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
                                          layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *, new_lens=None,
-                                         return_lse: bool = False, split=None):
+                                         return_lse: bool = False, split=None,
+                                         window=None, sink: int = 0):
     '''block_sparse_attention_prefill over a PAGED cache: the pool k_pages, v_pages [P, Hkv, page, D] and block_table
     [B, W] of block_sparse_attention_decode_paged, with that call's operand rules and refusals (Smax = W · page, pages of a
     power of two ≥ 16 keys; block_attention_prefill_paged_takes).  A table entry outside [0, P) hides its page's keys:
@@ -2503,14 +2597,17 @@ def block_sparse_attention_prefill_paged(q: torch.Tensor, k_pages: torch.Tensor,
     k_lens[b], are never consulted.  Bits: for a pool and a table whose seen entries are in range, out and lse are bit for
     bit those of block_sparse_attention_prefill on the cache gathered to [B, Hkv, Smax, D] — independent of P, of where the
     pages lie and of `page`.  Graph-capturable while k_lens, new_lens, the pool and the table change in place.  split: as in
-    block_sparse_attention_prefill, whose split call on the gathered cache has this one's bits.'''
+    block_sparse_attention_prefill, whose split call on the gathered cache has this one's bits.
+    window, sink (keyword only): as in block_sparse_attention_prefill — the token sees its last `window` keys,
+    itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys; not with split.'''
     return _prefill('block_sparse_attention_prefill_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens,
-                    block, scale, new_lens, None, None, False, return_lse, split)
+                    block, scale, new_lens, None, None, False, return_lse, split, window, sink)
 
 
 def block_sparse_attention_prefill_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
                                        block: int = 64, scale=None, *, k_scale=None, v_scale=None, new_lens=None,
-                                       return_lse: bool = False, split=None):
+                                       return_lse: bool = False, split=None,
+                                       window=None, sink: int = 0):
     '''block_sparse_attention_prefill over an FP8 cache: k, v [B, Hkv, Smax, D] torch.float8_e4m3fn with k_scale / v_scale
     as in block_sparse_attention_decode_fp8, whose operand rules and refusals these are (strides multiples of 16 bytes;
     block_attention_prefill_fp8_takes).  Every byte is widened to q's type on its way into LDS, which is exact, and
@@ -2518,21 +2615,26 @@ def block_sparse_attention_prefill_fp8(q: torch.Tensor, k: torch.Tensor, v: torc
     and with a v_scale the stored element is round(float32((O / L) · v_scale[h])).  With both scales None, out and lse are
     bit for bit those of block_sparse_attention_prefill on k.to(q.dtype), v.to(q.dtype).  (A v_scale TENSOR equal to 1 is
     the scaled statement: in float16 it rounds O / L to float32 first and may differ from v_scale=None in a last bit.)  split:
-    as in block_sparse_attention_prefill; the merged O takes the same two stores.'''
+    as in block_sparse_attention_prefill; the merged O takes the same two stores.
+    window, sink (keyword only): as in block_sparse_attention_prefill — the token sees its last `window` keys,
+    itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys; not with split.'''
     return _prefill('block_sparse_attention_prefill_fp8', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, new_lens, k_scale,
-                    v_scale, True, return_lse, split)
+                    v_scale, True, return_lse, split, window, sink)
 
 
 def block_sparse_attention_prefill_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
                                              layout: torch.Tensor, k_lens: torch.Tensor, block: int = 64, scale=None, *,
-                                             k_scale=None, v_scale=None, new_lens=None, return_lse: bool = False, split=None):
+                                             k_scale=None, v_scale=None, new_lens=None, return_lse: bool = False, split=None,
+                                             window=None, sink: int = 0):
     '''block_sparse_attention_prefill_paged over an FP8 pool: k_pages, v_pages [P, Hkv, page, D] torch.float8_e4m3fn with
     the scales of block_sparse_attention_prefill_fp8 (block_attention_prefill_paged_fp8_takes).  Bits: for in-range
     tables those of block_sparse_attention_prefill_fp8 with the same scales on the gathered cache; with both scales None
     those of block_sparse_attention_prefill_paged on the pool widened to q's type.  split: as in
-    block_sparse_attention_prefill, with the same equalities at the same split.'''
+    block_sparse_attention_prefill, with the same equalities at the same split.
+    window, sink (keyword only): as in block_sparse_attention_prefill — the token sees its last `window` keys,
+    itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys; not with split.'''
     return _prefill('block_sparse_attention_prefill_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout,
-                    k_lens, block, scale, new_lens, k_scale, v_scale, True, return_lse, split)
+                    k_lens, block, scale, new_lens, k_scale, v_scale, True, return_lse, split, window, sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -3224,10 +3326,12 @@ def select_key_blocks(q: torch.Tensor, bounds: torch.Tensor, k_lens: torch.Tenso
 
 
 def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse, k_scale=None,
-                     v_scale=None, fp8=False, tree_mask=None):
+                     v_scale=None, fp8=False, tree_mask=None, window=None, sink=0):
     '''The one body of the four list-source decode calls: _decode's checks minus the layout ones, the lists' own, one binding
-    call with the caller's lists as they are.  fp8: a float8_e4m3fn cache with the scale operands of _decode(…, fp8=True).'''
+    call with the caller's lists as they are.  fp8: a float8_e4m3fn cache with the scale operands of _decode(…, fp8=True).
+    tree_mask, window, sink: as in _decode.'''
     kn, vn = names
+    win = _check_window(what, window, sink, tree_mask)
     paged = kn == 'k_pages'
     base_text = _DECODE_FP8_SIZES_TEXT if fp8 else _DECODE_SIZES_TEXT
     sizes_text = base_text + (_PAGED_SIZES_SUFFIX if paged else '')
@@ -3281,16 +3385,18 @@ def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts,
         lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
         if out.numel() > 0:
             tree = () if tree_mask is None else (tree_mask.detach(),)
-            binding = getattr(custom_mm, _tree_binding(_SELECTED_BINDINGS[paged][fp8]) if tree else _SELECTED_BINDINGS[paged][fp8])
+            name = _SELECTED_BINDINGS[paged][fp8]
+            binding = getattr(custom_mm, _tree_binding(name) if tree else _window_binding(name) if win else name)
             fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
             binding(block_ids.detach(), block_counts.detach(), qc, k.detach(), v.detach(), *table, lens, float(scale), *fp8_scales,
-                    *tree, int(chunk), out, lse)
+                    *tree, *win, int(chunk), out, lse)
     return (out, lse) if return_lse else out
 
 
 def block_sparse_attention_decode_selected(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
                                            block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, chunk=None,
-                                           return_lse: bool = False, tree_mask=None):
+                                           return_lse: bool = False, tree_mask=None,
+                                           window=None, sink: int = 0):
     '''block_sparse_attention_decode with the blocks of every token given as a LIST — the output of select_key_blocks — in the
     place of a CSR layout: q [B, Hq, T, D], k and v [B, Hkv, Smax, D] and k_lens as in that call (64-key blocks, Smax a
     multiple of 64, the cache read through its own strides and never copied), block_ids int32 [B, Hkv, T, K] and
@@ -3307,21 +3413,28 @@ def block_sparse_attention_decode_selected(q: torch.Tensor, k: torch.Tensor, v: 
     Bits: for token t, out and lse are bit for bit those of block_sparse_attention_decode with T = 1, k_lens = pos + 1, the
     same chunk and a (B, Hkv) layout whose row pos // 64 lists the same blocks in the same order — a row's bits depend on
     its list, pos and chunk only.  Returns out [B, Hq, T, D], or (out, lse) with return_lse=True.  No atomics, no read-back:
-    graph-capturable.  NO autograd.  An fp8 cache is block_sparse_attention_decode_selected_fp8's.  tree_mask: as in block_sparse_attention_decode, over the lists.'''
+    graph-capturable.  NO autograd.  An fp8 cache is block_sparse_attention_decode_selected_fp8's.  tree_mask: as in block_sparse_attention_decode, over the lists.
+    window, sink (keyword only): as in block_sparse_attention_decode, over the lists — the token sees its last
+    `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
+    keys; a listed block that the window hides wholly is skipped in its list position.'''
     return _decode_selected('block_sparse_attention_decode_selected', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens, scale,
-                            chunk, return_lse, tree_mask=tree_mask)
+                            chunk, return_lse, tree_mask=tree_mask, window=window, sink=sink)
 
 
 def block_sparse_attention_decode_selected_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
                                                  block_table: torch.Tensor, block_ids: torch.Tensor, block_counts: torch.Tensor,
                                                  k_lens: torch.Tensor, scale=None, *, chunk=None, return_lse: bool = False,
-                                                 tree_mask=None):
+                                                 tree_mask=None,
+                                                 window=None, sink: int = 0):
     '''block_sparse_attention_decode_selected over a PAGED cache: k_pages, v_pages [P, Hkv, page, D] and block_table [B, W]
     are the operands of block_sparse_attention_decode_paged with its rules (Smax = W · page; an entry outside [0, P) hides
     its page's keys); the lists are indexed by logical 64-key blocks, whatever `page` is.  Bit for bit the contiguous call
-    on the gathered cache (block_attention_decode_selected_paged_takes).  tree_mask: as in block_sparse_attention_decode, over the lists.'''
+    on the gathered cache (block_attention_decode_selected_paged_takes).  tree_mask: as in block_sparse_attention_decode, over the lists.
+    window, sink (keyword only): as in block_sparse_attention_decode, over the lists — the token sees its last
+    `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
+    keys; a listed block that the window hides wholly is skipped in its list position.'''
     return _decode_selected('block_sparse_attention_decode_selected_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
-                            block_ids, block_counts, k_lens, scale, chunk, return_lse, tree_mask=tree_mask)
+                            block_ids, block_counts, k_lens, scale, chunk, return_lse, tree_mask=tree_mask, window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -3380,7 +3493,8 @@ def key_block_bounds_paged_fp8(k_pages: torch.Tensor, block_table: torch.Tensor,
 
 def block_sparse_attention_decode_selected_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
                                                block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, k_scale=None,
-                                               v_scale=None, chunk=None, return_lse: bool = False, tree_mask=None):
+                                               v_scale=None, chunk=None, return_lse: bool = False, tree_mask=None,
+                                               window=None, sink: int = 0):
     '''block_sparse_attention_decode_selected over an FP8 cache: q [B, Hq, T, D] bfloat16 or float16, k and v
     [B, Hkv, Smax, D] torch.float8_e4m3fn with k_scale / v_scale as in block_sparse_attention_decode_fp8 — None (= 1), a
     float, or a float32 device tensor of shape (), (1,) or (Hkv,), read by the kernel from device memory, so a captured
@@ -3394,20 +3508,28 @@ def block_sparse_attention_decode_selected_fp8(q: torch.Tensor, k: torch.Tensor,
 
     With lists from select_key_blocks over key_block_bounds_fp8: the selection ranks by the unscaled widened keys, which
     for positive per-head k scales is the ranking of the real keys (see key_block_bounds_fp8).  No atomics, no read-back:
-    graph-capturable.  NO autograd.  tree_mask: as in block_sparse_attention_decode, over the lists.'''
+    graph-capturable.  NO autograd.  tree_mask: as in block_sparse_attention_decode, over the lists.
+    window, sink (keyword only): as in block_sparse_attention_decode, over the lists — the token sees its last
+    `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
+    keys; a listed block that the window hides wholly is skipped in its list position.'''
     return _decode_selected('block_sparse_attention_decode_selected_fp8', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens,
-                            scale, chunk, return_lse, k_scale, v_scale, True, tree_mask=tree_mask)
+                            scale, chunk, return_lse, k_scale, v_scale, True, tree_mask=tree_mask, window=window, sink=sink)
 
 
 def block_sparse_attention_decode_selected_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
                                                      block_table: torch.Tensor, block_ids: torch.Tensor, block_counts: torch.Tensor,
                                                      k_lens: torch.Tensor, scale=None, *, k_scale=None, v_scale=None, chunk=None,
-                                                     return_lse: bool = False, tree_mask=None):
+                                                     return_lse: bool = False, tree_mask=None,
+                                                     window=None, sink: int = 0):
     '''block_sparse_attention_decode_selected_fp8 over a PAGED cache: k_pages, v_pages [P, Hkv, page, D] torch.float8_e4m3fn
     and block_table [B, W] as in block_sparse_attention_decode_paged_fp8; the lists are indexed by logical 64-key blocks.
-    Bit for bit the contiguous fp8 call on the gathered bytes (block_attention_decode_selected_paged_fp8_takes).  tree_mask: as in block_sparse_attention_decode, over the lists.'''
+    Bit for bit the contiguous fp8 call on the gathered bytes (block_attention_decode_selected_paged_fp8_takes).  tree_mask: as in block_sparse_attention_decode, over the lists.
+    window, sink (keyword only): as in block_sparse_attention_decode, over the lists — the token sees its last
+    `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
+    keys; a listed block that the window hides wholly is skipped in its list position.'''
     return _decode_selected('block_sparse_attention_decode_selected_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages,
-                            block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse, k_scale, v_scale, True, tree_mask=tree_mask)
+                            block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse, k_scale, v_scale, True, tree_mask=tree_mask,
+                            window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -3539,11 +3661,12 @@ _PREFILL_SELECTED_BINDINGS = (('block_attention_lists_prefill', 'block_attention
 
 
 def _prefill_selected(what, names, q, k, v, block_table, block_ids, block_counts, k_lens, scale, new_lens, return_lse, k_scale=None,
-                      v_scale=None, fp8=False):
+                      v_scale=None, fp8=False, window=None, sink=0):
     '''The one body of the four list-source prefill calls, beside _decode_selected: _prefill's checks minus the layout ones —
     no bound on the group, on B·Hkv or on T, q through its own strides, new_lens —, the lists' own with X = ⌈T / 64⌉ + 1 in
-    the place of T, one binding call with the caller's lists as they are.'''
+    the place of T, one binding call with the caller's lists as they are.  window, sink: as in _prefill.'''
     kn, vn = names
+    win = _check_window(what, window, sink)
     paged = kn == 'k_pages'
     base_text = _PREFILL_FP8_SIZES_TEXT if fp8 else _PREFILL_SIZES_TEXT
     sizes_text = base_text + (_PAGED_SIZES_SUFFIX if paged else '')
@@ -3596,16 +3719,18 @@ def _prefill_selected(what, names, q, k, v, block_table, block_ids, block_counts
         out = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
         lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
         if out.numel() > 0:
-            binding = getattr(custom_mm, _PREFILL_SELECTED_BINDINGS[paged][fp8])
+            name = _PREFILL_SELECTED_BINDINGS[paged][fp8]
+            binding = getattr(custom_mm, _window_binding(name) if win else name)
             fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
             binding(block_ids.detach(), block_counts.detach(), q.detach(), k.detach(), v.detach(), *table, lens, news, float(scale),
-                    *fp8_scales, out, lse)
+                    *fp8_scales, *win, out, lse)
     return (out, lse) if return_lse else out
 
 
 def block_sparse_attention_prefill_selected(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
                                             block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, new_lens=None,
-                                            return_lse: bool = False):
+                                            return_lse: bool = False,
+                                            window=None, sink: int = 0):
     '''block_sparse_attention_prefill with the blocks of every POSITION TILE given as a LIST in the place of a CSR layout: a
     chunk of a prompt behind a long cached prefix reads the listed blocks only.  q [B, Hq, T, D], k and v [B, Hkv, Smax, D],
     k_lens and new_lens as in that call (64-key blocks, Smax a multiple of 64, q and the cache read through their own strides
@@ -3627,44 +3752,60 @@ def block_sparse_attention_prefill_selected(q: torch.Tensor, k: torch.Tensor, v:
     shared rows agree.  Every refusal is that call's but for the layout, plus the lists' own (ValueError: not int32, not
     contiguous, a shape other than [B, Hkv, X, K ≥ 1] / [B, Hkv, X], B·Hkv·X·K beyond int32).  There is no `split`: a list
     has K entries.  Returns a fresh out [B, Hq, T, D], every row written exactly once by ONE launch, or (out, lse) with
-    return_lse=True.  No atomics, no workspace, no read-back: graph-capturable.  NO autograd.'''
+    return_lse=True.  No atomics, no workspace, no read-back: graph-capturable.  NO autograd.
+    window, sink (keyword only): as in block_sparse_attention_prefill, over the lists — the token sees its last
+    `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
+    keys; a listed block that the window hides from every position of the tile is skipped and never loaded.'''
     return _prefill_selected('block_sparse_attention_prefill_selected', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens,
-                             scale, new_lens, return_lse)
+                             scale, new_lens, return_lse, window=window, sink=sink)
 
 
 def block_sparse_attention_prefill_selected_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
                                                   block_table: torch.Tensor, block_ids: torch.Tensor, block_counts: torch.Tensor,
-                                                  k_lens: torch.Tensor, scale=None, *, new_lens=None, return_lse: bool = False):
+                                                  k_lens: torch.Tensor, scale=None, *, new_lens=None, return_lse: bool = False,
+                                                  window=None, sink: int = 0):
     '''block_sparse_attention_prefill_selected over a PAGED cache: k_pages, v_pages [P, Hkv, page, D] and block_table [B, W]
     are the operands of block_sparse_attention_prefill_paged with its rules (Smax = W · page; an entry outside [0, P) hides
     its page's keys); the lists are indexed by logical 64-key blocks, whatever `page` is.  Bit for bit the contiguous call
-    on the gathered cache (block_attention_prefill_selected_paged_takes).'''
+    on the gathered cache (block_attention_prefill_selected_paged_takes).
+    window, sink (keyword only): as in block_sparse_attention_prefill, over the lists — the token sees its last
+    `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
+    keys; a listed block that the window hides from every position of the tile is skipped and never loaded.'''
     return _prefill_selected('block_sparse_attention_prefill_selected_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
-                             block_ids, block_counts, k_lens, scale, new_lens, return_lse)
+                             block_ids, block_counts, k_lens, scale, new_lens, return_lse, window=window, sink=sink)
 
 
 def block_sparse_attention_prefill_selected_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
                                                 block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, k_scale=None,
-                                                v_scale=None, new_lens=None, return_lse: bool = False):
+                                                v_scale=None, new_lens=None, return_lse: bool = False,
+                                                window=None, sink: int = 0):
     '''block_sparse_attention_prefill_selected over an FP8 cache: k, v [B, Hkv, Smax, D] torch.float8_e4m3fn with k_scale /
     v_scale as in block_sparse_attention_prefill_fp8, whose cache rules and statements these are
     (block_attention_prefill_selected_fp8_takes).  Bits: those of block_sparse_attention_prefill_fp8 with the same scales and
     a layout that lists the same blocks in the same order; with both scales None those of
-    block_sparse_attention_prefill_selected on k.to(q.dtype), v.to(q.dtype).'''
+    block_sparse_attention_prefill_selected on k.to(q.dtype), v.to(q.dtype).
+    window, sink (keyword only): as in block_sparse_attention_prefill, over the lists — the token sees its last
+    `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
+    keys; a listed block that the window hides from every position of the tile is skipped and never loaded.'''
     return _prefill_selected('block_sparse_attention_prefill_selected_fp8', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens,
-                             scale, new_lens, return_lse, k_scale, v_scale, True)
+                             scale, new_lens, return_lse, k_scale, v_scale, True, window=window, sink=sink)
 
 
 def block_sparse_attention_prefill_selected_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
                                                       block_table: torch.Tensor, block_ids: torch.Tensor, block_counts: torch.Tensor,
                                                       k_lens: torch.Tensor, scale=None, *, k_scale=None, v_scale=None,
-                                                      new_lens=None, return_lse: bool = False):
+                                                      new_lens=None, return_lse: bool = False,
+                                                      window=None, sink: int = 0):
     '''block_sparse_attention_prefill_selected_fp8 over a PAGED cache: k_pages, v_pages [P, Hkv, page, D]
     torch.float8_e4m3fn and block_table [B, W] as in block_sparse_attention_prefill_paged_fp8; the lists are indexed by
     logical 64-key blocks.  Bit for bit the contiguous fp8 call on the gathered bytes
-    (block_attention_prefill_selected_paged_fp8_takes).'''
+    (block_attention_prefill_selected_paged_fp8_takes).
+    window, sink (keyword only): as in block_sparse_attention_prefill, over the lists — the token sees its last
+    `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
+    keys; a listed block that the window hides from every position of the tile is skipped and never loaded.'''
     return _prefill_selected('block_sparse_attention_prefill_selected_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages,
-                             block_table, block_ids, block_counts, k_lens, scale, new_lens, return_lse, k_scale, v_scale, True)
+                             block_table, block_ids, block_counts, k_lens, scale, new_lens, return_lse, k_scale, v_scale, True, window=window,
+                             sink=sink)
 
 
 # --------------------------------------------------------------------------- #
