@@ -134,6 +134,17 @@ struct ReadCall {
            group, scale, out, ldo, strideO, lse, __VA_ARGS__}
 #define MI_READ_PAGED block_table, table_ld, pages, page
 #define MI_READ_FP8 Scales{k_scale, k_scale_count, v_scale, v_scale_count}
+// … and by token, for the entry tables of the decode and the prefill unit, whose lines say FLAT or PAGED and FP8 false or true:
+// what MI_READ_CALL takes behind the list, the cache's element type, and the paged entries' guard — a page of 0 keys would
+// name the contiguous form, so it is refused here like every page that is no power of two ≥ 16.
+#define MI_READ_TABLE_FLAT nullptr, 0, 0, 0
+#define MI_READ_TABLE_PAGED MI_READ_PAGED
+#define MI_READ_GUARD_FLAT
+#define MI_READ_GUARD_PAGED page < 16 ? MI_EINVAL:
+#define MI_READ_SCALES_false Scales()
+#define MI_READ_SCALES_true MI_READ_FP8
+#define MI_READ_CACHE_false uint16_t
+#define MI_READ_CACHE_true uint8_t
 
 // The checks come in two halves, as the cache's own do, because every entry answers MI_OK for an empty call between them —
 // and refuses sizes of its own (the decode grid's items and T) there.  The sizes: MI_EINVAL, MI_ERANGE for a layout beyond

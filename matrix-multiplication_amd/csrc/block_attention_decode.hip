@@ -676,206 +676,80 @@ size_t mi_block_attention_decode_workspace_bytes(int32_t items, int32_t T, int32
   return (size_t)items * (size_t)T * (size_t)chunks * (size_t)group * (size_t)(D + 2) * sizeof(float);
 }
 
-// the header's parameter lists in pieces: [table] and [scales] are what the paged and the fp8 entries add
-#define MI_DECODE_LIST const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts
-#define MI_DECODE_LISTS_LIST const int32_t *block_ids, const int32_t *block_counts, int32_t K
+// The 48 entries of the header, two per line of the table below (bf16, f16).  The header's parameter lists in pieces: the
+// list — a LAYOUT's, or the caller's LISTS —, the sizes, [the table] of a PAGED entry, the operands, [the
+// scales] of an fp8 entry (§3.20, §3.32), [what the entry's form adds], the outputs …
+#define MI_DECODE_HEAD_LAYOUT const int32_t *rowptr, const int32_t *col, int64_t nnz, int32_t layouts
+#define MI_DECODE_HEAD_LISTS const int32_t *block_ids, const int32_t *block_counts, int32_t K
 #define MI_DECODE_SIZES int32_t items, int32_t heads, int32_t T, int32_t Smax
-#define MI_DECODE_TABLE const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page
+#define MI_DECODE_TABLE_FLAT
+#define MI_DECODE_TABLE_PAGED const int32_t *block_table, int64_t table_ld, int32_t pages, int32_t page,
 #define MI_DECODE_OPERANDS(CT)                                                                                                  \
   int32_t D, const uint16_t *q, int64_t ldq, int64_t strideQ, const CT *k, int64_t ldk, int64_t headK, int64_t batchK,          \
       const CT *v, int64_t ldv, int64_t headV, int64_t batchV, const int32_t *k_lens, int32_t lens_count, int32_t group,        \
       int32_t chunk, float scale
-#define MI_DECODE_SCALES const float *k_scale, int32_t k_scale_count, const float *v_scale, int32_t v_scale_count
+#define MI_DECODE_SCALES_false
+#define MI_DECODE_SCALES_true const float *k_scale, int32_t k_scale_count, const float *v_scale, int32_t v_scale_count,
 #define MI_DECODE_OUT \
   uint16_t *out, int64_t ldo, int64_t strideO, float *lse, void *workspace, size_t workspace_bytes, mi_stream_t stream
-// … and what the entries pass on: the reading call, then their own.  A page of 0 keys would name the contiguous form: it is
-// refused here like every page that is no power of two ≥ 16.
-#define MI_DECODE_CALL(...) MI_READ_CALL(rowptr, col, nnz, layouts, __VA_ARGS__)
+// … and what an entry passes on: the reading call, then its own.  The list source hands block_ids over as col, its
+// items · T · K entries as nnz, no rowptr and one layout.  (A K that is no positive int32 is refused inside, before the
+// product is looked at.)
+#define MI_DECODE_CALL_LAYOUT(...) MI_READ_CALL(rowptr, col, nnz, layouts, __VA_ARGS__)
+#define MI_DECODE_CALL_LISTS(...) MI_READ_CALL(nullptr, block_ids, K < 1 ? 0 : (int64_t)items * T * K, 1, __VA_ARGS__)
+#define MI_DECODE_LISTS_LAYOUT Lists()
+#define MI_DECODE_LISTS_LISTS Lists{block_counts, K < 1 ? -1 : K}
 #define MI_DECODE_OWN q, ldq, strideQ, chunk, workspace, workspace_bytes, static_cast<hipStream_t>(stream)
+// The forms, by the token a line ends in — its parameters between the operands and the outputs, and what is passed for them:
+// PLAIN; TREE (§3.34): int64 words [mask_rows][T], mask_rows 1 (one row for the batch) or the batch size items / heads, T ≤ 64;
+// WINDOW (§3.35): window ≥ 1, sink ≥ 0 — these entries run on the Tree<…> kernels with no mask.
+#define MI_DECODE_ADDS_PLAIN
+#define MI_DECODE_ADDS_TREE const int64_t *tree_mask, int32_t mask_rows,
+#define MI_DECODE_ADDS_WINDOW int32_t window, int32_t sink,
+#define MI_DECODE_PASS_PLAIN TreeMask()
+#define MI_DECODE_PASS_TREE TreeMask{tree_mask, mask_rows}
+#define MI_DECODE_PASS_WINDOW TreeMask(), Window{window, sink}
 
-int mi_block_attention_decode_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
-  return decode_entry<Bf16>(MI_DECODE_CALL(), MI_DECODE_OWN);
-}
-int mi_block_attention_decode_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
-  return decode_entry<F16>(MI_DECODE_CALL(), MI_DECODE_OWN);
-}
-int mi_block_attention_decode_paged_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16>(MI_DECODE_CALL(MI_READ_PAGED), MI_DECODE_OWN);
-}
-int mi_block_attention_decode_paged_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16>(MI_DECODE_CALL(MI_READ_PAGED), MI_DECODE_OWN);
-}
-
-// the fp8 caches: the parents' lists with byte caches and the two scales
-int mi_block_attention_decode_fp8_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES, MI_DECODE_OUT) {
-  return decode_entry<Bf16, true>(MI_DECODE_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_OWN);
-}
-int mi_block_attention_decode_fp8_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES, MI_DECODE_OUT) {
-  return decode_entry<F16, true>(MI_DECODE_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_OWN);
-}
-int mi_block_attention_decode_paged_fp8_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
-                                             MI_DECODE_SCALES, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16, true>(MI_DECODE_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_OWN);
-}
-int mi_block_attention_decode_paged_fp8_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
-                                            MI_DECODE_SCALES, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16, true>(MI_DECODE_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_OWN);
-}
-
-// the list source: the caller's block_ids / block_counts in the place of the layout — no rowptr, block_ids as
-// col, its items · T · K entries as nnz, one layout.  (A K that is no positive int32 is refused inside, before the product is
-// looked at.)
-#define MI_DECODE_LISTS_CALL(...) MI_READ_CALL(nullptr, block_ids, K < 1 ? 0 : (int64_t)items * T * K, 1, __VA_ARGS__)
-#define MI_DECODE_LISTS_OWN MI_DECODE_OWN, Lists{block_counts, K < 1 ? -1 : K}
-
-int mi_block_attention_decode_lists_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
-  return decode_entry<Bf16>(MI_DECODE_LISTS_CALL(), MI_DECODE_LISTS_OWN);
-}
-int mi_block_attention_decode_lists_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_OUT) {
-  return decode_entry<F16>(MI_DECODE_LISTS_CALL(), MI_DECODE_LISTS_OWN);
-}
-int mi_block_attention_decode_lists_paged_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
-                                               MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16>(MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_OWN);
-}
-int mi_block_attention_decode_lists_paged_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
-                                              MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16>(MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_OWN);
-}
-
-// … over an fp8 cache: byte caches and the two scales after `scale`, as the fp8 layout entries place them.  (The
-// names put `lists` first: `mi_block_attention_decode…` is the closed family of the entries above.)
-int mi_block_attention_lists_decode_fp8_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
-                                             MI_DECODE_OUT) {
-  return decode_entry<Bf16, true>(MI_DECODE_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LISTS_OWN);
-}
-int mi_block_attention_lists_decode_fp8_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
-                                            MI_DECODE_OUT) {
-  return decode_entry<F16, true>(MI_DECODE_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LISTS_OWN);
-}
-int mi_block_attention_lists_decode_paged_fp8_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
-                                                   MI_DECODE_SCALES, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LISTS_OWN);
-}
-int mi_block_attention_lists_decode_paged_fp8_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
-                                                  MI_DECODE_SCALES, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LISTS_OWN);
-}
-
-// The tree forms: every entry above as mi_block_attention_tree_decode{,_lists}{,_paged}{,_fp8}_T, with
-// `tree_mask, mask_rows` between its operands and its outputs — int64 words [mask_rows][T], mask_rows 1 (one row for the batch) or
-// the batch size items / heads; T ≤ 64.
-#define MI_DECODE_TREE const int64_t *tree_mask, int32_t mask_rows
-#define MI_DECODE_TREE_OWN TreeMask{tree_mask, mask_rows}
-#define MI_DECODE_LAYOUT_TREE_OWN MI_DECODE_OWN, Lists(), MI_DECODE_TREE_OWN
-
-int mi_block_attention_tree_decode_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_TREE, MI_DECODE_OUT) {
-  return decode_entry<Bf16, false, true>(MI_DECODE_CALL(), MI_DECODE_LAYOUT_TREE_OWN);
-}
-int mi_block_attention_tree_decode_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_TREE, MI_DECODE_OUT) {
-  return decode_entry<F16, false, true>(MI_DECODE_CALL(), MI_DECODE_LAYOUT_TREE_OWN);
-}
-int mi_block_attention_tree_decode_paged_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
-                                              MI_DECODE_TREE, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16, false, true>(MI_DECODE_CALL(MI_READ_PAGED), MI_DECODE_LAYOUT_TREE_OWN);
-}
-int mi_block_attention_tree_decode_paged_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
-                                             MI_DECODE_TREE, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16, false, true>(MI_DECODE_CALL(MI_READ_PAGED), MI_DECODE_LAYOUT_TREE_OWN);
-}
-int mi_block_attention_tree_decode_fp8_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
-                                            MI_DECODE_TREE, MI_DECODE_OUT) {
-  return decode_entry<Bf16, true, true>(MI_DECODE_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LAYOUT_TREE_OWN);
-}
-int mi_block_attention_tree_decode_fp8_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
-                                           MI_DECODE_TREE, MI_DECODE_OUT) {
-  return decode_entry<F16, true, true>(MI_DECODE_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LAYOUT_TREE_OWN);
-}
-int mi_block_attention_tree_decode_paged_fp8_bf16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
-                                                  MI_DECODE_SCALES, MI_DECODE_TREE, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16, true, true>(MI_DECODE_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LAYOUT_TREE_OWN);
-}
-int mi_block_attention_tree_decode_paged_fp8_f16(MI_DECODE_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
-                                                 MI_DECODE_SCALES, MI_DECODE_TREE, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16, true, true>(MI_DECODE_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LAYOUT_TREE_OWN);
-}
-
-// … over the caller's lists
-#define MI_DECODE_LISTS_TREE_OWN MI_DECODE_OWN, Lists{block_counts, K < 1 ? -1 : K}, MI_DECODE_TREE_OWN
-
-int mi_block_attention_tree_decode_lists_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_TREE,
-                                              MI_DECODE_OUT) {
-  return decode_entry<Bf16, false, true>(MI_DECODE_LISTS_CALL(), MI_DECODE_LISTS_TREE_OWN);
-}
-int mi_block_attention_tree_decode_lists_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint16_t), MI_DECODE_TREE,
-                                             MI_DECODE_OUT) {
-  return decode_entry<F16, false, true>(MI_DECODE_LISTS_CALL(), MI_DECODE_LISTS_TREE_OWN);
-}
-int mi_block_attention_tree_decode_lists_paged_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
-                                                    MI_DECODE_TREE, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16, false, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_TREE_OWN);
-}
-int mi_block_attention_tree_decode_lists_paged_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint16_t),
-                                                   MI_DECODE_TREE, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16, false, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_TREE_OWN);
-}
-int mi_block_attention_tree_decode_lists_fp8_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
-                                                  MI_DECODE_TREE, MI_DECODE_OUT) {
-  return decode_entry<Bf16, true, true>(MI_DECODE_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LISTS_TREE_OWN);
-}
-int mi_block_attention_tree_decode_lists_fp8_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,
-                                                 MI_DECODE_TREE, MI_DECODE_OUT) {
-  return decode_entry<F16, true, true>(MI_DECODE_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LISTS_TREE_OWN);
-}
-int mi_block_attention_tree_decode_lists_paged_fp8_bf16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
-                                                        MI_DECODE_SCALES, MI_DECODE_TREE, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<Bf16, true, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LISTS_TREE_OWN);
-}
-int mi_block_attention_tree_decode_lists_paged_fp8_f16(MI_DECODE_LISTS_LIST, MI_DECODE_SIZES, MI_DECODE_TABLE, MI_DECODE_OPERANDS(uint8_t),
-                                                       MI_DECODE_SCALES, MI_DECODE_TREE, MI_DECODE_OUT) {
-  return page < 16 ? MI_EINVAL : decode_entry<F16, true, true>(MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LISTS_TREE_OWN);
-}
-
-// The window forms: the sixteen plain entries as mi_block_attention_window_decode{,_lists}{,_paged}{,_fp8}_T, with
-// `window, sink` between their operands and their outputs — window ≥ 1, sink ≥ 0.  They run on the Tree<…> kernels with no mask.
-#define MI_DECODE_WINDOW int32_t window, int32_t sink
-#define MI_DECODE_WINDOW_OWN TreeMask(), Window{window, sink}
-#define MI_DECODE_LAYOUT_WINDOW_OWN MI_DECODE_OWN, Lists(), MI_DECODE_WINDOW_OWN
-#define MI_DECODE_LISTS_WINDOW_OWN MI_DECODE_OWN, Lists{block_counts, K < 1 ? -1 : K}, MI_DECODE_WINDOW_OWN
-// two entries, one per type: the name's suffix, the head of the list (a layout or the lists), the cache form, what decode_entry
-// takes, then the operands [and the scales]
-#define MI_WINDOW_DECODE(NAME, HEAD, FP8, CALL, OWN, ...)                                                                      \
-  int mi_block_attention_window_decode##NAME##_bf16(HEAD, MI_DECODE_SIZES, __VA_ARGS__ MI_DECODE_WINDOW, MI_DECODE_OUT) {          \
-    return decode_entry<Bf16, FP8, false, true>(CALL, OWN);                                                                        \
-  }                                                                                                                                \
-  int mi_block_attention_window_decode##NAME##_f16(HEAD, MI_DECODE_SIZES, __VA_ARGS__ MI_DECODE_WINDOW, MI_DECODE_OUT) {           \
-    return decode_entry<F16, FP8, false, true>(CALL, OWN);                                                                         \
+#define MI_DECODE_ENTRY(STEM, TYPE, SUFFIX, HEAD, PAGED, FP8, TREE, WINDOW, FORM)                                               \
+  int mi_block_attention_##STEM##SUFFIX(MI_DECODE_HEAD_##HEAD, MI_DECODE_SIZES, MI_DECODE_TABLE_##PAGED                         \
+                                        MI_DECODE_OPERANDS(MI_READ_CACHE_##FP8), MI_DECODE_SCALES_##FP8 MI_DECODE_ADDS_##FORM   \
+                                        MI_DECODE_OUT) {                                                                        \
+    return MI_READ_GUARD_##PAGED decode_entry<TYPE, FP8, TREE, WINDOW>(                                                         \
+        MI_DECODE_CALL_##HEAD(MI_READ_TABLE_##PAGED, MI_READ_SCALES_##FP8), MI_DECODE_OWN, MI_DECODE_LISTS_##HEAD,              \
+        MI_DECODE_PASS_##FORM);                                                                                                 \
   }
-#define MI_WINDOW_DECODE_PAGED(NAME, HEAD, FP8, CALL, OWN, ...)                                                                \
-  int mi_block_attention_window_decode##NAME##_bf16(HEAD, MI_DECODE_SIZES, MI_DECODE_TABLE, __VA_ARGS__ MI_DECODE_WINDOW,          \
-                                                    MI_DECODE_OUT) {                                                               \
-    return page < 16 ? MI_EINVAL : decode_entry<Bf16, FP8, false, true>(CALL, OWN);                                                \
-  }                                                                                                                                \
-  int mi_block_attention_window_decode##NAME##_f16(HEAD, MI_DECODE_SIZES, MI_DECODE_TABLE, __VA_ARGS__ MI_DECODE_WINDOW,           \
-                                                   MI_DECODE_OUT) {                                                                \
-    return page < 16 ? MI_EINVAL : decode_entry<F16, FP8, false, true>(CALL, OWN);                                                 \
-  }
+// one line of the table: the entry's name stem as the header spells it, the list, the cache's storage, FP8, the TREE and WINDOW
+// of decode_entry, the form
+#define MI_DECODE_ENTRIES(STEM, HEAD, PAGED, FP8, TREE, WINDOW, FORM)          \
+  MI_DECODE_ENTRY(STEM, Bf16, _bf16, HEAD, PAGED, FP8, TREE, WINDOW, FORM)     \
+  MI_DECODE_ENTRY(STEM, F16, _f16, HEAD, PAGED, FP8, TREE, WINDOW, FORM)
+
 // clang-format off
-MI_WINDOW_DECODE(, MI_DECODE_LIST, false, MI_DECODE_CALL(), MI_DECODE_LAYOUT_WINDOW_OWN, MI_DECODE_OPERANDS(uint16_t),)
-MI_WINDOW_DECODE_PAGED(_paged, MI_DECODE_LIST, false, MI_DECODE_CALL(MI_READ_PAGED), MI_DECODE_LAYOUT_WINDOW_OWN,
-                       MI_DECODE_OPERANDS(uint16_t),)
-MI_WINDOW_DECODE(_fp8, MI_DECODE_LIST, true, MI_DECODE_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_DECODE_LAYOUT_WINDOW_OWN,
-                 MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,)
-MI_WINDOW_DECODE_PAGED(_paged_fp8, MI_DECODE_LIST, true, MI_DECODE_CALL(MI_READ_PAGED, MI_READ_FP8), MI_DECODE_LAYOUT_WINDOW_OWN,
-                       MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,)
-MI_WINDOW_DECODE(_lists, MI_DECODE_LISTS_LIST, false, MI_DECODE_LISTS_CALL(), MI_DECODE_LISTS_WINDOW_OWN,
-                 MI_DECODE_OPERANDS(uint16_t),)
-MI_WINDOW_DECODE_PAGED(_lists_paged, MI_DECODE_LISTS_LIST, false, MI_DECODE_LISTS_CALL(MI_READ_PAGED), MI_DECODE_LISTS_WINDOW_OWN,
-                       MI_DECODE_OPERANDS(uint16_t),)
-MI_WINDOW_DECODE(_lists_fp8, MI_DECODE_LISTS_LIST, true, MI_DECODE_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8),
-                 MI_DECODE_LISTS_WINDOW_OWN, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,)
-MI_WINDOW_DECODE_PAGED(_lists_paged_fp8, MI_DECODE_LISTS_LIST, true, MI_DECODE_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8),
-                       MI_DECODE_LISTS_WINDOW_OWN, MI_DECODE_OPERANDS(uint8_t), MI_DECODE_SCALES,)
+MI_DECODE_ENTRIES(decode,                            LAYOUT, FLAT,  false, false, false, PLAIN)
+MI_DECODE_ENTRIES(decode_paged,                      LAYOUT, PAGED, false, false, false, PLAIN)
+MI_DECODE_ENTRIES(decode_fp8,                        LAYOUT, FLAT,  true,  false, false, PLAIN)
+MI_DECODE_ENTRIES(decode_paged_fp8,                  LAYOUT, PAGED, true,  false, false, PLAIN)
+MI_DECODE_ENTRIES(decode_lists,                      LISTS,  FLAT,  false, false, false, PLAIN)
+MI_DECODE_ENTRIES(decode_lists_paged,                LISTS,  PAGED, false, false, false, PLAIN)
+// (over an fp8 cache the names put `lists` first: `mi_block_attention_decode…` was a closed family when these came)
+MI_DECODE_ENTRIES(lists_decode_fp8,                  LISTS,  FLAT,  true,  false, false, PLAIN)
+MI_DECODE_ENTRIES(lists_decode_paged_fp8,            LISTS,  PAGED, true,  false, false, PLAIN)
+MI_DECODE_ENTRIES(tree_decode,                       LAYOUT, FLAT,  false, true,  false, TREE)
+MI_DECODE_ENTRIES(tree_decode_paged,                 LAYOUT, PAGED, false, true,  false, TREE)
+MI_DECODE_ENTRIES(tree_decode_fp8,                   LAYOUT, FLAT,  true,  true,  false, TREE)
+MI_DECODE_ENTRIES(tree_decode_paged_fp8,             LAYOUT, PAGED, true,  true,  false, TREE)
+MI_DECODE_ENTRIES(tree_decode_lists,                 LISTS,  FLAT,  false, true,  false, TREE)
+MI_DECODE_ENTRIES(tree_decode_lists_paged,           LISTS,  PAGED, false, true,  false, TREE)
+MI_DECODE_ENTRIES(tree_decode_lists_fp8,             LISTS,  FLAT,  true,  true,  false, TREE)
+MI_DECODE_ENTRIES(tree_decode_lists_paged_fp8,       LISTS,  PAGED, true,  true,  false, TREE)
+MI_DECODE_ENTRIES(window_decode,                     LAYOUT, FLAT,  false, false, true,  WINDOW)
+MI_DECODE_ENTRIES(window_decode_paged,               LAYOUT, PAGED, false, false, true,  WINDOW)
+MI_DECODE_ENTRIES(window_decode_fp8,                 LAYOUT, FLAT,  true,  false, true,  WINDOW)
+MI_DECODE_ENTRIES(window_decode_paged_fp8,           LAYOUT, PAGED, true,  false, true,  WINDOW)
+MI_DECODE_ENTRIES(window_decode_lists,               LISTS,  FLAT,  false, false, true,  WINDOW)
+MI_DECODE_ENTRIES(window_decode_lists_paged,         LISTS,  PAGED, false, false, true,  WINDOW)
+MI_DECODE_ENTRIES(window_decode_lists_fp8,           LISTS,  FLAT,  true,  false, true,  WINDOW)
+MI_DECODE_ENTRIES(window_decode_lists_paged_fp8,     LISTS,  PAGED, true,  false, true,  WINDOW)
 // clang-format on
 
 }  // extern "C"

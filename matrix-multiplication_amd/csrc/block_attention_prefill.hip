@@ -727,46 +727,6 @@ int prefill_entry(const ReadCall& r, const uint16_t* q, int64_t ldq, int64_t hea
 
 extern "C" {
 
-// what the entries pass on: the reading call, then their own.  A page of 0 keys would name the contiguous form: it is refused
-// here like every page that is no power of two ≥ 16.
-#define MI_PREFILL_CALL(...) MI_READ_CALL(rowptr, col, nnz, layouts, __VA_ARGS__)
-#define MI_PREFILL_OWN q, ldq, headQ, batchQ, new_lens, new_lens_count, static_cast<hipStream_t>(stream)
-
-int mi_block_attention_prefill_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
-                                    MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<Bf16>(MI_PREFILL_CALL(), MI_PREFILL_OWN);
-}
-int mi_block_attention_prefill_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
-                                   MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<F16>(MI_PREFILL_CALL(), MI_PREFILL_OWN);
-}
-int mi_block_attention_prefill_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                          MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<Bf16>(MI_PREFILL_CALL(MI_READ_PAGED), MI_PREFILL_OWN);
-}
-int mi_block_attention_prefill_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                         MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<F16>(MI_PREFILL_CALL(MI_READ_PAGED), MI_PREFILL_OWN);
-}
-int mi_block_attention_prefill_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
-                                        MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<Bf16, true>(MI_PREFILL_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_OWN);
-}
-int mi_block_attention_prefill_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
-                                       MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<F16, true>(MI_PREFILL_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_OWN);
-}
-int mi_block_attention_prefill_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                              MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
-                                              MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<Bf16, true>(MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_OWN);
-}
-int mi_block_attention_prefill_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                             MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
-                                             MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_OWN);
-}
-
 int64_t mi_block_attention_prefill_split_workspace_bytes(int32_t items, int32_t group, int32_t T, int32_t D, int32_t Smax,
                                                          int32_t split) {
   if (items < 0 || group < 1 || T < 0 || !takes_width(D) || Smax < 0 || Smax % kB != 0 || split < 1) return MI_EINVAL;
@@ -779,117 +739,67 @@ int64_t mi_block_attention_prefill_split_workspace_bytes(int32_t items, int32_t 
   return n;
 }
 
-#define MI_PREFILL_SPLIT Split{true, split, workspace, workspace_bytes}
-#define MI_PREFILL_SPLIT_OUT MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT
-
-int mi_block_attention_prefill_split_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
-                                          MI_PREFILL_SPLIT_OUT) {
-  return prefill_entry<Bf16>(MI_PREFILL_CALL(), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
-}
-int mi_block_attention_prefill_split_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
-                                         MI_PREFILL_SPLIT_OUT) {
-  return prefill_entry<F16>(MI_PREFILL_CALL(), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
-}
-int mi_block_attention_prefill_split_paged_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                                MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_PREFILL_SPLIT_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<Bf16>(MI_PREFILL_CALL(MI_READ_PAGED), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
-}
-int mi_block_attention_prefill_split_paged_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                               MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_PREFILL_SPLIT_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<F16>(MI_PREFILL_CALL(MI_READ_PAGED), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
-}
-int mi_block_attention_prefill_split_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
-                                              MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_PREFILL_SPLIT_OUT) {
-  return prefill_entry<Bf16, true>(MI_PREFILL_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
-}
-int mi_block_attention_prefill_split_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
-                                             MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_PREFILL_SPLIT_OUT) {
-  return prefill_entry<F16, true>(MI_PREFILL_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
-}
-int mi_block_attention_prefill_split_paged_fp8_bf16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                                    MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
-                                                    MI_PREFILL_SPLIT_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<Bf16, true>(MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
-}
-int mi_block_attention_prefill_split_paged_fp8_f16(MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                                   MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
-                                                   MI_PREFILL_SPLIT_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_OWN, MI_PREFILL_SPLIT);
-}
-
-// the list source: the caller's block_ids / block_counts in the place of the layout — no rowptr, block_ids as
-// col, its items · (⌈T / 64⌉ + 1) · K entries as nnz, one layout.  (A K that is no positive int32 is refused inside, before the
-// product is looked at; T < 0 likewise by the sizes' check.)
-#define MI_PREFILL_LISTS_CALL(...) \
+// The 48 entries of the header, two per line of the table below (bf16, f16).  Their parameter lists are the header's pieces:
+// the list with the sizes — a LAYOUT's, or the caller's LISTS —, [the table] of a PAGED entry, D, the operands,
+// [the scales] of an fp8 entry, and the tail of the entry's form.  What an entry passes on: the reading call, then its own.  The
+// list source hands block_ids over as col, its items · (⌈T / 64⌉ + 1) · K entries as nnz, no rowptr and one layout.  (A K that
+// is no positive int32 is refused inside, before the product is looked at; T < 0 likewise by the sizes' check.)
+#define MI_PREFILL_HEAD_LAYOUT MI_BLOCK_ATTENTION_PREFILL_LIST
+#define MI_PREFILL_HEAD_LISTS MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD
+#define MI_PREFILL_TABLE_FLAT
+#define MI_PREFILL_TABLE_PAGED MI_BLOCK_ATTENTION_PREFILL_TABLE,
+#define MI_PREFILL_SCALES_false
+#define MI_PREFILL_SCALES_true MI_BLOCK_ATTENTION_PREFILL_SCALES,
+#define MI_PREFILL_CALL_LAYOUT(...) MI_READ_CALL(rowptr, col, nnz, layouts, __VA_ARGS__)
+#define MI_PREFILL_CALL_LISTS(...) \
   MI_READ_CALL(nullptr, block_ids, (K < 1 || T < 0) ? 0 : (int64_t)items * (((int64_t)T + kB - 1) / kB + 1) * K, 1, __VA_ARGS__)
-#define MI_PREFILL_LISTS_OWN MI_PREFILL_OWN, Split(), Lists{block_counts, K < 1 ? -1 : K}
-#define MI_PREFILL_LISTS_HEAD MI_BLOCK_ATTENTION_PREFILL_LISTS_HEAD
+#define MI_PREFILL_LISTS_LAYOUT Lists()
+#define MI_PREFILL_LISTS_LISTS Lists{block_counts, K < 1 ? -1 : K}
+#define MI_PREFILL_OWN q, ldq, headQ, batchQ, new_lens, new_lens_count, static_cast<hipStream_t>(stream)
+// The forms, by the token a line ends in — the tail of the parameter list, and what is passed behind the entry's own (LISTS: the
+// entry's Lists): PLAIN; SPLIT (§3.28): the cut and the workspace, behind the outputs; WINDOW (§3.35): window ≥ 1 and sink ≥ 0,
+// ahead of them.  prefill_entry refuses a split over lists or beside a window.
+#define MI_PREFILL_TAIL_PLAIN MI_BLOCK_ATTENTION_PREFILL_OUT
+#define MI_PREFILL_TAIL_SPLIT MI_BLOCK_ATTENTION_PREFILL_SPLIT_OUT
+#define MI_PREFILL_TAIL_WINDOW int32_t window, int32_t sink, MI_BLOCK_ATTENTION_PREFILL_OUT
+#define MI_PREFILL_PASS_PLAIN(LISTS) Split(), LISTS
+#define MI_PREFILL_PASS_SPLIT(LISTS) Split{true, split, workspace, workspace_bytes}, LISTS
+#define MI_PREFILL_PASS_WINDOW(LISTS) Split(), LISTS, Window{true, window, sink}
 
-int mi_block_attention_lists_prefill_bf16(MI_PREFILL_LISTS_HEAD, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
-                                          MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<Bf16>(MI_PREFILL_LISTS_CALL(), MI_PREFILL_LISTS_OWN);
-}
-int mi_block_attention_lists_prefill_f16(MI_PREFILL_LISTS_HEAD, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
-                                         MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<F16>(MI_PREFILL_LISTS_CALL(), MI_PREFILL_LISTS_OWN);
-}
-int mi_block_attention_lists_prefill_paged_bf16(MI_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                                MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<Bf16>(MI_PREFILL_LISTS_CALL(MI_READ_PAGED), MI_PREFILL_LISTS_OWN);
-}
-int mi_block_attention_lists_prefill_paged_f16(MI_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                               MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t), MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<F16>(MI_PREFILL_LISTS_CALL(MI_READ_PAGED), MI_PREFILL_LISTS_OWN);
-}
-int mi_block_attention_lists_prefill_fp8_bf16(MI_PREFILL_LISTS_HEAD, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
-                                              MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<Bf16, true>(MI_PREFILL_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_LISTS_OWN);
-}
-int mi_block_attention_lists_prefill_fp8_f16(MI_PREFILL_LISTS_HEAD, int32_t D, MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t),
-                                             MI_BLOCK_ATTENTION_PREFILL_SCALES, MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return prefill_entry<F16, true>(MI_PREFILL_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_LISTS_OWN);
-}
-int mi_block_attention_lists_prefill_paged_fp8_bf16(MI_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                                    MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
-                                                    MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<Bf16, true>(MI_PREFILL_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_LISTS_OWN);
-}
-int mi_block_attention_lists_prefill_paged_fp8_f16(MI_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE, int32_t D,
-                                                   MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
-                                                   MI_BLOCK_ATTENTION_PREFILL_OUT) {
-  return page < 16 ? MI_EINVAL : prefill_entry<F16, true>(MI_PREFILL_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_LISTS_OWN);
-}
-
-// The window forms: the sixteen unsplit entries as mi_block_attention_window_prefill{,_lists}{,_paged}{,_fp8}_T, with
-// `window, sink` between their operands and their outputs — window ≥ 1, sink ≥ 0.
-#define MI_PREFILL_WINDOW int32_t window, int32_t sink
-#define MI_PREFILL_WINDOW_OWN MI_PREFILL_OWN, Split(), Lists(), Window{true, window, sink}
-#define MI_PREFILL_LISTS_WINDOW_OWN MI_PREFILL_OWN, Split(), Lists{block_counts, K < 1 ? -1 : K}, Window{true, window, sink}
-// two entries, one per type: the name's suffix, the head of the list (a layout or the lists) [and the table], the cache form, what
-// prefill_entry takes, then the operands [and the scales]
-#define MI_WINDOW_PREFILL(NAME, HEAD, FP8, GUARD, CALL, OWN, ...)                                                                  \
-  int mi_block_attention_window_prefill##NAME##_bf16(HEAD, int32_t D, __VA_ARGS__ MI_PREFILL_WINDOW, MI_BLOCK_ATTENTION_PREFILL_OUT) { \
-    return GUARD ? MI_EINVAL : prefill_entry<Bf16, FP8>(CALL, OWN);                                                                \
-  }                                                                                                                                \
-  int mi_block_attention_window_prefill##NAME##_f16(HEAD, int32_t D, __VA_ARGS__ MI_PREFILL_WINDOW, MI_BLOCK_ATTENTION_PREFILL_OUT) {  \
-    return GUARD ? MI_EINVAL : prefill_entry<F16, FP8>(CALL, OWN);                                                                 \
+#define MI_PREFILL_ENTRY(STEM, TYPE, SUFFIX, HEAD, PAGED, FP8, FORM)                                                            \
+  int mi_block_attention_##STEM##SUFFIX(MI_PREFILL_HEAD_##HEAD, MI_PREFILL_TABLE_##PAGED int32_t D,                             \
+                                        MI_BLOCK_ATTENTION_PREFILL_OPERANDS(MI_READ_CACHE_##FP8),                               \
+                                        MI_PREFILL_SCALES_##FP8 MI_PREFILL_TAIL_##FORM) {                                       \
+    return MI_READ_GUARD_##PAGED prefill_entry<TYPE, FP8>(MI_PREFILL_CALL_##HEAD(MI_READ_TABLE_##PAGED, MI_READ_SCALES_##FP8),  \
+                                                          MI_PREFILL_OWN, MI_PREFILL_PASS_##FORM(MI_PREFILL_LISTS_##HEAD));     \
   }
-#define MI_LAYOUT_PAGED MI_BLOCK_ATTENTION_PREFILL_LIST, MI_BLOCK_ATTENTION_PREFILL_TABLE
-#define MI_LISTS_PAGED MI_PREFILL_LISTS_HEAD, MI_BLOCK_ATTENTION_PREFILL_TABLE
-#define MI_OPS16 MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint16_t),
-#define MI_OPS8 MI_BLOCK_ATTENTION_PREFILL_OPERANDS(uint8_t), MI_BLOCK_ATTENTION_PREFILL_SCALES,
+// one line of the table: the entry's name stem as the header spells it, the list, the cache's storage, FP8, the form
+#define MI_PREFILL_ENTRIES(STEM, HEAD, PAGED, FP8, FORM)       \
+  MI_PREFILL_ENTRY(STEM, Bf16, _bf16, HEAD, PAGED, FP8, FORM)  \
+  MI_PREFILL_ENTRY(STEM, F16, _f16, HEAD, PAGED, FP8, FORM)
+
 // clang-format off
-MI_WINDOW_PREFILL(, MI_BLOCK_ATTENTION_PREFILL_LIST, false, false, MI_PREFILL_CALL(), MI_PREFILL_WINDOW_OWN, MI_OPS16)
-MI_WINDOW_PREFILL(_paged, MI_LAYOUT_PAGED, false, page < 16, MI_PREFILL_CALL(MI_READ_PAGED), MI_PREFILL_WINDOW_OWN, MI_OPS16)
-MI_WINDOW_PREFILL(_fp8, MI_BLOCK_ATTENTION_PREFILL_LIST, true, false, MI_PREFILL_CALL(nullptr, 0, 0, 0, MI_READ_FP8), MI_PREFILL_WINDOW_OWN,
-                  MI_OPS8)
-MI_WINDOW_PREFILL(_paged_fp8, MI_LAYOUT_PAGED, true, page < 16, MI_PREFILL_CALL(MI_READ_PAGED, MI_READ_FP8), MI_PREFILL_WINDOW_OWN, MI_OPS8)
-MI_WINDOW_PREFILL(_lists, MI_PREFILL_LISTS_HEAD, false, false, MI_PREFILL_LISTS_CALL(), MI_PREFILL_LISTS_WINDOW_OWN, MI_OPS16)
-MI_WINDOW_PREFILL(_lists_paged, MI_LISTS_PAGED, false, page < 16, MI_PREFILL_LISTS_CALL(MI_READ_PAGED), MI_PREFILL_LISTS_WINDOW_OWN, MI_OPS16)
-MI_WINDOW_PREFILL(_lists_fp8, MI_PREFILL_LISTS_HEAD, true, false, MI_PREFILL_LISTS_CALL(nullptr, 0, 0, 0, MI_READ_FP8),
-                  MI_PREFILL_LISTS_WINDOW_OWN, MI_OPS8)
-MI_WINDOW_PREFILL(_lists_paged_fp8, MI_LISTS_PAGED, true, page < 16, MI_PREFILL_LISTS_CALL(MI_READ_PAGED, MI_READ_FP8),
-                  MI_PREFILL_LISTS_WINDOW_OWN, MI_OPS8)
+MI_PREFILL_ENTRIES(prefill,                          LAYOUT, FLAT,  false, PLAIN)
+MI_PREFILL_ENTRIES(prefill_paged,                    LAYOUT, PAGED, false, PLAIN)
+MI_PREFILL_ENTRIES(prefill_fp8,                      LAYOUT, FLAT,  true,  PLAIN)
+MI_PREFILL_ENTRIES(prefill_paged_fp8,                LAYOUT, PAGED, true,  PLAIN)
+MI_PREFILL_ENTRIES(prefill_split,                    LAYOUT, FLAT,  false, SPLIT)
+MI_PREFILL_ENTRIES(prefill_split_paged,              LAYOUT, PAGED, false, SPLIT)
+MI_PREFILL_ENTRIES(prefill_split_fp8,                LAYOUT, FLAT,  true,  SPLIT)
+MI_PREFILL_ENTRIES(prefill_split_paged_fp8,          LAYOUT, PAGED, true,  SPLIT)
+// (the names put `lists` first: `mi_block_attention_prefill…` was a closed family when these came)
+MI_PREFILL_ENTRIES(lists_prefill,                    LISTS,  FLAT,  false, PLAIN)
+MI_PREFILL_ENTRIES(lists_prefill_paged,              LISTS,  PAGED, false, PLAIN)
+MI_PREFILL_ENTRIES(lists_prefill_fp8,                LISTS,  FLAT,  true,  PLAIN)
+MI_PREFILL_ENTRIES(lists_prefill_paged_fp8,          LISTS,  PAGED, true,  PLAIN)
+MI_PREFILL_ENTRIES(window_prefill,                   LAYOUT, FLAT,  false, WINDOW)
+MI_PREFILL_ENTRIES(window_prefill_paged,             LAYOUT, PAGED, false, WINDOW)
+MI_PREFILL_ENTRIES(window_prefill_fp8,               LAYOUT, FLAT,  true,  WINDOW)
+MI_PREFILL_ENTRIES(window_prefill_paged_fp8,         LAYOUT, PAGED, true,  WINDOW)
+MI_PREFILL_ENTRIES(window_prefill_lists,             LISTS,  FLAT,  false, WINDOW)
+MI_PREFILL_ENTRIES(window_prefill_lists_paged,       LISTS,  PAGED, false, WINDOW)
+MI_PREFILL_ENTRIES(window_prefill_lists_fp8,         LISTS,  FLAT,  true,  WINDOW)
+MI_PREFILL_ENTRIES(window_prefill_lists_paged_fp8,   LISTS,  PAGED, true,  WINDOW)
 // clang-format on
 
 }  // extern "C"

@@ -23,9 +23,11 @@ math = `torch.matmul` and its autograd (SURVEY.md §8a "known defects"):
     Python recursion with one to_sparse_csr() per slice (reference :289-297).
 '''
 
+import functools
 import math
 import os
 import weakref
+from typing import NamedTuple
 
 import torch
 from torch.autograd.function import InplaceFunction
@@ -1798,6 +1800,10 @@ _DECODE_CHUNK = 16       # list entries per workgroup when chunk=None: a constan
 #                          fitted over (Smax, D) by tools/bench_block_attention_decode.py; not measured yet
 _DECODE_SIZES_TEXT = ('bfloat16 or float16 operands, head size D in {32, 64, 96, 128}, block a multiple of 64, Smax a multiple '
                       'of block, 1 to 16 query heads per k / v head')
+# … as the fp8 calls and the prefill calls (§3.27) word them
+_DECODE_FP8_SIZES_TEXT = _DECODE_SIZES_TEXT.replace('bfloat16 or float16 operands', 'bfloat16 or float16 q, a float8_e4m3fn cache')
+_PREFILL_SIZES_TEXT = _DECODE_SIZES_TEXT.replace('1 to 16 query heads per k / v head', 'Hq a multiple of Hkv')
+_PREFILL_FP8_SIZES_TEXT = _PREFILL_SIZES_TEXT.replace('bfloat16 or float16 operands', 'bfloat16 or float16 q, a float8_e4m3fn cache')
 
 
 def block_attention_decode_takes(dtype, D: int, block: int, group: int) -> bool:
@@ -1979,17 +1985,6 @@ def _check_cache_shape(what, names, q, k, v, block_table, base_text=_DECODE_SIZE
 _TREE_MAX_T = 64         # tokens of a tree-masked decode call: token t's int64 word names the draft keys it sees
 
 
-def _tree_binding(name: str) -> str:
-    '''The binding of a decode call with a tree mask: block_attention_tree_… for block_attention_… (the mask stands ahead of chunk).'''
-    return 'block_attention_tree_' + name[len('block_attention_'):]
-
-
-def _window_binding(name: str) -> str:
-    '''The binding of a reading call with a window: block_attention_window_… for block_attention_… (window and sink stand
-    ahead of chunk in the decode bindings, ahead of out in the prefill bindings).'''
-    return 'block_attention_window_' + name[len('block_attention_'):]
-
-
 def _check_window(what, window, sink, tree_mask=None, split=None):
     '''The window= and sink= operands of the sixteen reading calls: window None or a Python int in
     [1, 2³¹ − 1], sink a Python int in [0, 2³¹ − 1] and 0 without a window; no tree mask (the decode calls) and no split (the
@@ -2092,85 +2087,177 @@ def tree_attention_mask(parents: torch.Tensor):
     return mask, depth
 
 
-def _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8=False, scales=(),
-                                           block_table=None, *, sizes_text=None, max_group=_DECODE_MAX_GROUP,
-                                           max_grid=_DECODE_MAX_GRID, q_strided=False, new_lens=None, split=None, tree_mask=None):
-    '''Every refusal of the four decode calls, before the first device call, split as _check_block_attention_operands splits
-    them: ValueError for what an operand is, RuntimeError for operands that do not go together (mixed dtypes, host tensors /
-    devices).  The cache-shape half is _check_cache_shape's (`names` as there), the layout half _check_decode_layout's.  fp8,
-    scales: the fp8 calls' cache type and their (name, scale) pairs (_check_fp8_scales).  The keyword parameters are what the
-    prefill calls say differently (_prefill): the accepted sizes in the messages, no bound on the group (max_group None), none
-    on B·Hkv and T (max_grid None), q read through its own strides (q_strided: _check_source_strides), new_lens
-    (_check_new_lens) and split.'''
-    kn, vn = names
-    paged = kn == 'k_pages'
-    base_text = sizes_text or _DECODE_SIZES_TEXT
-    _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8, base_text, split)
-    Smax = _check_cache_shape(what, names, q, k, v, block_table, base_text, max_group)
-    B, Hq, T, D = q.shape
+# --------------------------------------------------------------------------- #
+# the one body of the sixteen reading calls
+# --------------------------------------------------------------------------- #
+
+class _ReadKind(NamedTuple):
+    '''What one KIND of reading call — decode or prefill, over a layout or over the caller's lists — says differently from the
+    others; paged and fp8, which every kind has, are arguments of _read_call.  `decode` also says which operand the call has
+    behind k_lens: chunk (decode) or new_lens (prefill).  Which optional pieces a call takes is its signature's business:
+    tree_mask the decode calls, split the prefill calls over a layout, window and sink all sixteen.'''
+    decode: bool
+    listed: bool      # the caller's lists in the place of a layout
+    sizes: tuple      # the accepted sizes the messages name, [fp8]
+    max_group: object  # query heads per k / v head: the decode kernel's own rows; None: any group >= 1
+    max_grid: object  # B·Hkv and T are grid dimensions of the decode kernel; None: B·Hq, T and Smax fit an int32
+    q_strided: bool   # q is read through its own strides, as it is; else it is made contiguous (a decode call's q is small)
+
+
+_DECODE_LAYOUT = _ReadKind(True, False, (_DECODE_SIZES_TEXT, _DECODE_SIZES_TEXT), _DECODE_MAX_GROUP, _DECODE_MAX_GRID, False)
+_DECODE_LISTS = _ReadKind(True, True, (_DECODE_SIZES_TEXT, _DECODE_FP8_SIZES_TEXT), _DECODE_MAX_GROUP, _DECODE_MAX_GRID, False)
+_PREFILL_LAYOUT = _ReadKind(False, False, (_PREFILL_SIZES_TEXT, _PREFILL_FP8_SIZES_TEXT), None, None, True)
+_PREFILL_LISTS = _ReadKind(False, True, (_PREFILL_SIZES_TEXT, _PREFILL_FP8_SIZES_TEXT), None, None, True)
+
+
+def _check_read_grid(what, kind, B, Hq, Hkv, T, Smax):
+    '''The bound of a kind on the sizes its launch is made of.'''
+    if kind.max_grid is None:
+        if max(B * Hq, T, Smax) >= 2 ** 31:
+            raise ValueError(f'{what}: B·Hq = {B * Hq}, T = {T} and Smax = {Smax} must each fit an int32')
+    elif B * Hkv > kind.max_grid or T > kind.max_grid:
+        raise ValueError(f'{what}: B·Hkv = {B * Hkv} and T = {T} must each be at most {kind.max_grid} (they are grid dimensions)')
+
+
+# The two list sources.  Each holds the refusals of a reading call from the operands' kinds to k_lens — the part in which the
+# sources order their checks differently: the cache-shape half (_check_cache_shape) stands between the source's first checks and
+# its shape checks, and the layout calls look at k_lens between the decode kinds' bound and the prefill kinds' —, and returns
+# (Smax, the operands it names for _check_on_device ahead of q and those behind the cache, head): head() is the head of the
+# binding's argument list, made after the last check.  `source`: the call's own two operands.
+
+def _layout_source(what, kind, names, q, k, v, block_table, fp8, source, chunk, split, k_lens):
+    '''The layout of block_sparse_attention, (layout, block): its expansion into 64-blocks is the record the call keeps on it.'''
+    layout, block = source
+    sizes = kind.sizes[fp8]
+    _check_decode_call(what, names, q, k, v, layout, block, chunk, fp8, sizes, split)
+    Smax = _check_cache_shape(what, names, q, k, v, block_table, sizes, kind.max_group)
+    B, Hq, T, _ = q.shape
     Hkv = k.shape[1]
     values = torch.Tensor.values(layout)  # (taken once: a new tensor every time)
-    operands = {'layout': values, 'q': q, kn: k, vn: v}  # in the order the device check names them
-    if paged:
-        operands['block_table'] = block_table
-    _check_decode_layout(what, B, Hkv, Smax, layout, values.numel(), block, base_text)
-    if max_grid is not None and (B * Hkv > _DECODE_MAX_GRID or T > _DECODE_MAX_GRID):
-        raise ValueError(f'{what}: B·Hkv = {B * Hkv} and T = {T} must each be at most {_DECODE_MAX_GRID} (they are grid dimensions)')
+    _check_decode_layout(what, B, Hkv, Smax, layout, values.numel(), block, sizes)
+    if kind.decode:
+        _check_read_grid(what, kind, B, Hq, Hkv, T, Smax)
     _check_k_lens(what, k_lens, B)
-    if max_grid is None and max(B * Hq, T, Smax) >= 2 ** 31:
-        raise ValueError(f'{what}: B·Hq = {B * Hq}, T = {T} and Smax = {Smax} must each fit an int32')
+    if not kind.decode:
+        _check_read_grid(what, kind, B, Hq, Hkv, T, Smax)
+    return Smax, {'layout': values}, {}, lambda: _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))['fwd'][:3]
+
+
+def _lists_source(what, kind, names, q, k, v, block_table, fp8, source, chunk, split, k_lens):
+    '''The caller's lists, (block_ids, block_counts), handed over as they are: a list per token (decode: select_key_blocks'
+    output) or per 64-position tile (prefill: select_key_blocks_tiles').'''
+    block_ids, block_counts = source
+    kn, vn = names
+    sizes = kind.sizes[fp8]
+    if fp8:
+        _check_lowp_operands(what, (('q', q),), sizes)
+        _check_fp8_cache(what, ((kn, k), (vn, v)), sizes)
+    else:
+        _check_lowp_operands(what, (('q', q), (kn, k), (vn, v)), sizes)
+    maker = 'select_key_blocks' if kind.decode else 'select_key_blocks_tiles'
+    for name, t in (('block_ids', block_ids), ('block_counts', block_counts)):
+        if not isinstance(t, torch.Tensor) or t.layout != torch.strided or t.dtype != torch.int32:
+            raise ValueError(f'{what}: {name} must be a dense int32 tensor ({maker}\' output is handed over as it is)')
+    if chunk is not None and (not _is_int(chunk) or chunk < 1 or chunk >= 2 ** 31):
+        raise ValueError(f'{what}: chunk must be None or a positive int, got {chunk!r}')
+    Smax = _check_cache_shape(what, names, q, k, v, block_table, sizes, kind.max_group, pool_owner="k_pages's")
+    B, Hq, T, _ = q.shape
+    Hkv = k.shape[1]
+    rows, rows_text = (T, 'T') if kind.decode else (block_attention_prefill_tiles(T), 'ceil(T/64) + 1')
+    if Smax % _BLOCK_TILE != 0:
+        raise ValueError(f'{what}: Smax = {Smax} must be a multiple of 64 (accepted: '
+                         f'{sizes + (_PAGED_SIZES_SUFFIX if kn == "k_pages" else "")})')
+    if block_ids.dim() != 4 or tuple(block_ids.shape[:3]) != (B, Hkv, rows) or block_ids.shape[3] < 1 or not block_ids.is_contiguous():
+        raise ValueError(f'{what}: block_ids must be a contiguous [B, Hkv, {rows_text}, K] = [{B}, {Hkv}, {rows}, K >= 1] tensor, got '
+                         f'{tuple(block_ids.shape)}')
+    if tuple(block_counts.shape) != (B, Hkv, rows) or not block_counts.is_contiguous():
+        raise ValueError(f'{what}: block_counts must be a contiguous [B, Hkv, {rows_text}] = [{B}, {Hkv}, {rows}] tensor, got '
+                         f'{tuple(block_counts.shape)}')
+    K = block_ids.shape[3]
+    _check_read_grid(what, kind, B, Hq, Hkv, T, Smax)
+    if kind.decode:
+        if B * Hkv * T * K >= 2 ** 31 or K * _BLOCK_TILE >= 2 ** 31:
+            raise ValueError(f'{what}: B·Hkv·T·K = {B * Hkv * T * K} and 64·K must fit int32 indices')
+    elif B * Hkv * rows * K >= 2 ** 31:
+        raise ValueError(f'{what}: B·Hkv·(ceil(T/64) + 1)·K = {B * Hkv * rows * K} must fit int32 indices')
+    _check_k_lens(what, k_lens, B)
+    return Smax, {}, {'block_ids': block_ids, 'block_counts': block_counts}, lambda: (block_ids.detach(), block_counts.detach())
+
+
+@functools.lru_cache(maxsize=None)
+def _read_binding(decode: bool, listed: bool, paged: bool, fp8: bool, modifier: str = '') -> str:
+    '''The binding of a reading call, block_attention_[tree_|window_]STEM[_split][_paged][_fp8] — the one place that knows how
+    the stems are spelled: decode and prefill over a layout, decode_lists over the lists of a 2-byte cache, and lists_decode
+    (over an fp8 cache) and lists_prefill, which put `lists` first because block_attention_decode… and
+    block_attention_prefill… were closed families when they came.  modifier: '', 'tree' (decode), 'window', or 'split'
+    (prefill over a layout).'''
+    stem = 'decode' if decode else 'prefill'
+    if listed:
+        stem = 'decode_lists' if decode and not fp8 else 'lists_' + stem
+    return ('block_attention_' + (modifier + '_' if modifier in ('tree', 'window') else '') + stem
+            + ('_split' if modifier == 'split' else '') + ('_paged' if paged else '') + ('_fp8' if fp8 else ''))
+
+
+def _read_call(what, kind, names, q, k, v, block_table, source, k_lens, scale, return_lse, *, chunk=None, new_lens=None, fp8=False,
+               k_scale=None, v_scale=None, tree_mask=None, split=None, window=None, sink=0):
+    '''The one body of the sixteen reading calls: every refusal before the first device call — ValueError for what an operand
+    is, RuntimeError for operands that do not go together (mixed dtypes, host tensors / devices) —, the defaults, the operands
+    as the binding takes them, one binding call.  kind: what the call's kind says differently (_ReadKind); `names`: the cache
+    operands' names in the messages — ('k_pages', 'v_pages') is the paged form, the only one to look at block_table; `source`:
+    the call's list source, (layout, block) or (block_ids, block_counts).  fp8: a float8_e4m3fn cache with k_scale and v_scale.
+    chunk (decode) and new_lens (prefill) are what the kinds have behind k_lens.  tree_mask, split, window and sink: None
+    (sink 0) is the binding and the argument list of the call without the piece; else the piece chooses the binding's form
+    (_read_binding) and takes its place in the argument list.
+
+    A new optional piece gets its check here, a form in _read_binding, a place in the argument list below, and a keyword in
+    the signatures of the calls that take it.'''
+    kn, vn = names
+    paged = kn == 'k_pages'
+    win = _check_window(what, window, sink, tree_mask, split)
+    check_source = _lists_source if kind.listed else _layout_source
+    Smax, ahead, behind, head = check_source(what, kind, names, q, k, v, block_table, fp8, source, chunk, split, k_lens)
+    B, Hq, T, D = q.shape
     _check_new_lens(what, new_lens, B)
-    if q_strided:
+    if kind.q_strided:
         _check_source_strides(what, 'q', q)
     outer, unit = ('page' if paged else 'batch'), (16 if fp8 else 8)
     _check_cache_strides(what, kn, k, D, outer, unit)
     _check_cache_strides(what, vn, v, D, outer, unit)
-    operands['k_lens'] = k_lens
+    operands = {**ahead, 'q': q, kn: k, vn: v}  # in the order the device check names them
+    if paged:
+        operands['block_table'] = block_table
+    operands.update(behind, k_lens=k_lens)
     if new_lens is not None:
         operands['new_lens'] = new_lens
     if fp8:
-        operands.update(_check_fp8_scales(what, scales, Hkv, q))
+        operands.update(_check_fp8_scales(what, (('k_scale', k_scale), ('v_scale', v_scale)), k.shape[1], q))
     operands.update(_check_tree_mask(what, tree_mask, B, T, q))
     _check_on_device(what, **operands)
-    return Smax
-
-
-_DECODE_BINDINGS = (('block_attention_decode', 'block_attention_decode_fp8'),  # [paged][fp8]
-                    ('block_attention_decode_paged', 'block_attention_decode_paged_fp8'))
-
-
-def _decode(what, names, q, k, v, block_table, layout, k_lens, block, scale, chunk, k_scale, v_scale, fp8, return_lse, tree_mask=None,
-            window=None, sink=0):
-    '''The one body of the four decode calls: the checks, the defaults, the operands as the binding takes them, one binding
-    call.  `names` as in _check_block_attention_decode_operands; block_table, k_scale and v_scale are looked at by the paged
-    and the fp8 forms only.  tree_mask: None — the binding and the arguments of the call without it — or the mask, which goes
-    to the binding's block_attention_tree_… form (_tree_binding) ahead of chunk.  window, sink: likewise — None and 0: the call
-    without them; else two ints to the block_attention_window_… form (_window_binding) ahead of chunk.'''
-    paged = names[0] == 'k_pages'
-    win = _check_window(what, window, sink, tree_mask)
-    scales = (('k_scale', k_scale), ('v_scale', v_scale)) if fp8 else ()
-    Smax = _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, chunk, fp8, scales, block_table,
-                                                  tree_mask=tree_mask)
-    B, Hq, T, D = q.shape
     if scale is None:
         scale = 1.0 / float(D) ** 0.5
-    if chunk is None:
+    if kind.decode and chunk is None:
         chunk = _decode_chunk(Smax, D)
     with torch.no_grad():
-        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
-        offsets, columns, nnz, _ = rec['fwd']
+        head = head()
         lens = _lens_i32(k_lens)
+        news = () if kind.decode else (None if new_lens is None else new_lens.detach().to(torch.int32).contiguous(),)
         table = (_table_i32(block_table),) if paged else ()
-        qc = q.detach().contiguous()
-        out = torch.empty_like(qc)
+        if kind.q_strided:
+            qx = q.detach()
+            out = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
+        else:
+            qx = q.detach().contiguous()
+            out = torch.empty_like(qx)
         lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
         if out.numel() > 0:
-            tree = () if tree_mask is None else (tree_mask.detach(),)
-            name = _DECODE_BINDINGS[paged][fp8]
-            binding = getattr(custom_mm, _tree_binding(name) if tree else _window_binding(name) if win else name)
+            modifier = 'tree' if tree_mask is not None else 'window' if win else 'split' if split is not None else ''
+            binding = getattr(custom_mm, _read_binding(kind.decode, kind.listed, paged, fp8, modifier))
             fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
-            binding(offsets, columns, nnz, qc, k.detach(), v.detach(), *table, lens, float(scale), *fp8_scales, *tree, *win, int(chunk),
-                    out, lse)
+            tree = () if tree_mask is None else (tree_mask.detach(),)
+            chunks = (int(chunk),) if kind.decode else ()
+            splits = () if split is None else (int(split),)
+            binding(*head, qx, k.detach(), v.detach(), *table, lens, *news, float(scale), *fp8_scales, *tree, *win, *chunks, out, lse,
+                    *splits)
     return (out, lse) if return_lse else out
 
 
@@ -2235,8 +2322,8 @@ def block_sparse_attention_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Ten
     and lse −inf.  Both values are Python ints, baked into a captured graph.  ValueError for a bool, a tensor or a value
     out of range, for sink without window, and for window together with tree_mask (a tree's window edge belongs to
     prefix + depth, not to the slot) — before the first device call.'''
-    return _decode('block_sparse_attention_decode', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, chunk, None, None, False,
-                   return_lse, tree_mask=tree_mask, window=window, sink=sink)
+    return _read_call('block_sparse_attention_decode', _DECODE_LAYOUT, ('k', 'v'), q, k, v, None, (layout, block), k_lens, scale,
+                      return_lse, chunk=chunk, tree_mask=tree_mask, window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -2277,8 +2364,8 @@ def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, 
     block_sparse_attention_prefill_paged.  tree_mask: as in block_sparse_attention_decode.
     window, sink (keyword only): as in block_sparse_attention_decode — the token sees its last `window` keys,
     itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys.'''
-    return _decode('block_sparse_attention_decode_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens, block,
-                   scale, chunk, None, None, False, return_lse, tree_mask=tree_mask, window=window, sink=sink)
+    return _read_call('block_sparse_attention_decode_paged', _DECODE_LAYOUT, ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
+                      (layout, block), k_lens, scale, return_lse, chunk=chunk, tree_mask=tree_mask, window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -2286,7 +2373,6 @@ def block_sparse_attention_decode_paged(q: torch.Tensor, k_pages: torch.Tensor, 
 # --------------------------------------------------------------------------- #
 
 _FP8_MAX = 448.0                     # the largest finite e4m3fn value
-_DECODE_FP8_SIZES_TEXT = _DECODE_SIZES_TEXT.replace('bfloat16 or float16 operands', 'bfloat16 or float16 q, a float8_e4m3fn cache')
 
 
 def _check_fp8_cache(what, operands, sizes_text=None):
@@ -2399,8 +2485,8 @@ def block_sparse_attention_decode_fp8(q: torch.Tensor, k: torch.Tensor, v: torch
     there reaches no output.  For T beyond a few tokens use block_sparse_attention_prefill_fp8.  tree_mask: as in block_sparse_attention_decode.
     window, sink (keyword only): as in block_sparse_attention_decode — the token sees its last `window` keys,
     itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys.'''
-    return _decode('block_sparse_attention_decode_fp8', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, chunk, k_scale, v_scale,
-                   True, return_lse, tree_mask=tree_mask, window=window, sink=sink)
+    return _read_call('block_sparse_attention_decode_fp8', _DECODE_LAYOUT, ('k', 'v'), q, k, v, None, (layout, block), k_lens, scale,
+                      return_lse, chunk=chunk, fp8=True, k_scale=k_scale, v_scale=v_scale, tree_mask=tree_mask, window=window, sink=sink)
 
 
 def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
@@ -2419,16 +2505,15 @@ def block_sparse_attention_decode_paged_fp8(q: torch.Tensor, k_pages: torch.Tens
     the scale tensors are updated in place.  For T beyond a few tokens use block_sparse_attention_prefill_paged_fp8.  tree_mask: as in block_sparse_attention_decode.
     window, sink (keyword only): as in block_sparse_attention_decode — the token sees its last `window` keys,
     itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys.'''
-    return _decode('block_sparse_attention_decode_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens,
-                   block, scale, chunk, k_scale, v_scale, True, return_lse, tree_mask=tree_mask, window=window, sink=sink)
+    return _read_call('block_sparse_attention_decode_paged_fp8', _DECODE_LAYOUT, ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
+                      (layout, block), k_lens, scale, return_lse, chunk=chunk, fp8=True, k_scale=k_scale, v_scale=v_scale,
+                      tree_mask=tree_mask, window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
 # block-sparse prefill attention over the KV cache: chunked prompts in 64-row position tiles (DESIGN.md §3.27)
 # --------------------------------------------------------------------------- #
 
-_PREFILL_SIZES_TEXT = _DECODE_SIZES_TEXT.replace('1 to 16 query heads per k / v head', 'Hq a multiple of Hkv')
-_PREFILL_FP8_SIZES_TEXT = _PREFILL_SIZES_TEXT.replace('bfloat16 or float16 operands', 'bfloat16 or float16 q, a float8_e4m3fn cache')
 
 
 def block_attention_prefill_takes(dtype, D: int, block: int) -> bool:
@@ -2450,12 +2535,6 @@ def block_attention_prefill_fp8_takes(dtype, D: int, block: int) -> bool:
 def block_attention_prefill_paged_fp8_takes(dtype, D: int, block: int, page: int) -> bool:
     '''… and of block_sparse_attention_prefill_paged_fp8: exactly block_attention_prefill_paged_takes.'''
     return block_attention_prefill_paged_takes(dtype, D, block, page)
-
-
-_PREFILL_BINDINGS = (('block_attention_prefill', 'block_attention_prefill_fp8'),  # [paged][fp8]
-                     ('block_attention_prefill_paged', 'block_attention_prefill_paged_fp8'))
-_PREFILL_SPLIT_BINDINGS = (('block_attention_prefill_split', 'block_attention_prefill_split_fp8'),  # [paged][fp8]
-                           ('block_attention_prefill_split_paged', 'block_attention_prefill_split_paged_fp8'))
 
 
 def block_attention_prefill_split(B: int, Hq: int, T: int, Smax: int, D: int):
@@ -2482,38 +2561,6 @@ def block_attention_prefill_split(B: int, Hq: int, T: int, Smax: int, D: int):
         return None
     per_part = (Smax // _BLOCK_TILE) // 32
     return max(16, 1 << (per_part.bit_length() - 1))
-
-
-def _prefill(what, names, q, k, v, block_table, layout, k_lens, block, scale, new_lens, k_scale, v_scale, fp8, return_lse, split=None,
-             window=None, sink=0):
-    '''The one body of the four prefill calls, beside _decode: the decode calls' checks with what differs given as
-    parameters, the defaults, the operands as the binding takes them — q AS IT IS, through its own strides —, one binding
-    call: split None the unsplit binding with its own argument list, an int the split binding with that int behind it;
-    window None likewise, an int the block_attention_window_… binding (_window_binding) with window and sink ahead of out.'''
-    paged = names[0] == 'k_pages'
-    win = _check_window(what, window, sink, split=split)
-    scales = (('k_scale', k_scale), ('v_scale', v_scale)) if fp8 else ()
-    _check_block_attention_decode_operands(what, names, q, k, v, layout, k_lens, block, None, fp8, scales, block_table,
-                                           sizes_text=_PREFILL_FP8_SIZES_TEXT if fp8 else _PREFILL_SIZES_TEXT, max_group=None,
-                                           max_grid=None, q_strided=True, new_lens=new_lens, split=split)
-    B, Hq, T, D = q.shape
-    if scale is None:
-        scale = 1.0 / float(D) ** 0.5
-    with torch.no_grad():
-        rec = _block_layout(layout, q.device, block // _BLOCK_TILE, _csr_state(layout))
-        offsets, columns, nnz, _ = rec['fwd']
-        lens = _lens_i32(k_lens)
-        news = None if new_lens is None else new_lens.detach().to(torch.int32).contiguous()
-        table = (_table_i32(block_table),) if paged else ()
-        out = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
-        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
-        if out.numel() > 0:
-            name = (_PREFILL_BINDINGS if split is None else _PREFILL_SPLIT_BINDINGS)[paged][fp8]
-            binding = getattr(custom_mm, _window_binding(name) if win else name)
-            fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
-            binding(offsets, columns, nnz, q.detach(), k.detach(), v.detach(), *table, lens, news, float(scale), *fp8_scales, *win, out,
-                    lse, *(() if split is None else (int(split),)))
-    return (out, lse) if return_lse else out
 
 
 def block_sparse_attention_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
@@ -2582,8 +2629,8 @@ def block_sparse_attention_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Te
     window, sink).  Everything else is unchanged: 100 tokens equal chunks of 60 and 40, window = 2³¹ − 1 or sink ≥ Smax gives
     the bits of the call without a window.  ValueError for a bool, a tensor or a value out of range, for sink without window,
     and for window together with split (a windowed row's list is short; the split exists for long lists).'''
-    return _prefill('block_sparse_attention_prefill', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, new_lens, None, None,
-                    False, return_lse, split, window, sink)
+    return _read_call('block_sparse_attention_prefill', _PREFILL_LAYOUT, ('k', 'v'), q, k, v, None, (layout, block), k_lens, scale,
+                      return_lse, new_lens=new_lens, split=split, window=window, sink=sink)
 
 
 def block_sparse_attention_prefill_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
@@ -2600,8 +2647,8 @@ def block_sparse_attention_prefill_paged(q: torch.Tensor, k_pages: torch.Tensor,
     block_sparse_attention_prefill, whose split call on the gathered cache has this one's bits.
     window, sink (keyword only): as in block_sparse_attention_prefill — the token sees its last `window` keys,
     itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys; not with split.'''
-    return _prefill('block_sparse_attention_prefill_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout, k_lens,
-                    block, scale, new_lens, None, None, False, return_lse, split, window, sink)
+    return _read_call('block_sparse_attention_prefill_paged', _PREFILL_LAYOUT, ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
+                      (layout, block), k_lens, scale, return_lse, new_lens=new_lens, split=split, window=window, sink=sink)
 
 
 def block_sparse_attention_prefill_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, layout: torch.Tensor, k_lens: torch.Tensor,
@@ -2618,8 +2665,8 @@ def block_sparse_attention_prefill_fp8(q: torch.Tensor, k: torch.Tensor, v: torc
     as in block_sparse_attention_prefill; the merged O takes the same two stores.
     window, sink (keyword only): as in block_sparse_attention_prefill — the token sees its last `window` keys,
     itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys; not with split.'''
-    return _prefill('block_sparse_attention_prefill_fp8', ('k', 'v'), q, k, v, None, layout, k_lens, block, scale, new_lens, k_scale,
-                    v_scale, True, return_lse, split, window, sink)
+    return _read_call('block_sparse_attention_prefill_fp8', _PREFILL_LAYOUT, ('k', 'v'), q, k, v, None, (layout, block), k_lens, scale,
+                      return_lse, new_lens=new_lens, fp8=True, k_scale=k_scale, v_scale=v_scale, split=split, window=window, sink=sink)
 
 
 def block_sparse_attention_prefill_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor, block_table: torch.Tensor,
@@ -2633,8 +2680,9 @@ def block_sparse_attention_prefill_paged_fp8(q: torch.Tensor, k_pages: torch.Ten
     block_sparse_attention_prefill, with the same equalities at the same split.
     window, sink (keyword only): as in block_sparse_attention_prefill — the token sees its last `window` keys,
     itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink` keys; not with split.'''
-    return _prefill('block_sparse_attention_prefill_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table, layout,
-                    k_lens, block, scale, new_lens, k_scale, v_scale, True, return_lse, split, window, sink)
+    return _read_call('block_sparse_attention_prefill_paged_fp8', _PREFILL_LAYOUT, ('k_pages', 'v_pages'), q, k_pages, v_pages,
+                      block_table, (layout, block), k_lens, scale, return_lse, new_lens=new_lens, fp8=True, k_scale=k_scale,
+                      v_scale=v_scale, split=split, window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -3145,8 +3193,6 @@ def block_attention_decode_selected_paged_takes(dtype, D: int, group: int, page:
 
 _BOUNDS_BINDINGS = (('kv_block_bounds', 'kv_block_bounds_fp8'),  # [paged][fp8]
                     ('kv_block_bounds_paged', 'kv_block_bounds_paged_fp8'))
-_SELECTED_BINDINGS = (('block_attention_decode_lists', 'block_attention_lists_decode_fp8'),  # [paged][fp8]
-                      ('block_attention_decode_lists_paged', 'block_attention_lists_decode_paged_fp8'))
 _SELECT_FP8_SIZES_TEXT = 'a float8_e4m3fn cache, bfloat16 or float16 bounds, head size D in {32, 64, 96, 128}, Smax a multiple of 64'
 
 
@@ -3325,74 +3371,6 @@ def select_key_blocks(q: torch.Tensor, bounds: torch.Tensor, k_lens: torch.Tenso
     return (ids, counts, scores) if return_scores else (ids, counts)
 
 
-def _decode_selected(what, names, q, k, v, block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse, k_scale=None,
-                     v_scale=None, fp8=False, tree_mask=None, window=None, sink=0):
-    '''The one body of the four list-source decode calls: _decode's checks minus the layout ones, the lists' own, one binding
-    call with the caller's lists as they are.  fp8: a float8_e4m3fn cache with the scale operands of _decode(…, fp8=True).
-    tree_mask, window, sink: as in _decode.'''
-    kn, vn = names
-    win = _check_window(what, window, sink, tree_mask)
-    paged = kn == 'k_pages'
-    base_text = _DECODE_FP8_SIZES_TEXT if fp8 else _DECODE_SIZES_TEXT
-    sizes_text = base_text + (_PAGED_SIZES_SUFFIX if paged else '')
-    if fp8:
-        _check_lowp_operands(what, (('q', q),), base_text)
-        _check_fp8_cache(what, ((kn, k), (vn, v)), base_text)
-    else:
-        _check_lowp_operands(what, (('q', q), (kn, k), (vn, v)), _DECODE_SIZES_TEXT)
-    for name, t in (('block_ids', block_ids), ('block_counts', block_counts)):
-        if not isinstance(t, torch.Tensor) or t.layout != torch.strided or t.dtype != torch.int32:
-            raise ValueError(f'{what}: {name} must be a dense int32 tensor (select_key_blocks\' output is handed over as it is)')
-    if chunk is not None and (not _is_int(chunk) or chunk < 1 or chunk >= 2 ** 31):
-        raise ValueError(f'{what}: chunk must be None or a positive int, got {chunk!r}')
-    Smax = _check_cache_shape(what, names, q, k, v, block_table, base_text, pool_owner="k_pages's")
-    B, Hq, T, D = q.shape
-    Hkv = k.shape[1]
-    if Smax % _BLOCK_TILE != 0:
-        raise ValueError(f'{what}: Smax = {Smax} must be a multiple of 64 (accepted: {sizes_text})')
-    if block_ids.dim() != 4 or tuple(block_ids.shape[:3]) != (B, Hkv, T) or block_ids.shape[3] < 1 or not block_ids.is_contiguous():
-        raise ValueError(f'{what}: block_ids must be a contiguous [B, Hkv, T, K] = [{B}, {Hkv}, {T}, K >= 1] tensor, got '
-                         f'{tuple(block_ids.shape)}')
-    if tuple(block_counts.shape) != (B, Hkv, T) or not block_counts.is_contiguous():
-        raise ValueError(f'{what}: block_counts must be a contiguous [B, Hkv, T] = [{B}, {Hkv}, {T}] tensor, got '
-                         f'{tuple(block_counts.shape)}')
-    K = block_ids.shape[3]
-    if B * Hkv > _DECODE_MAX_GRID or T > _DECODE_MAX_GRID:
-        raise ValueError(f'{what}: B·Hkv = {B * Hkv} and T = {T} must each be at most {_DECODE_MAX_GRID} (they are grid dimensions)')
-    if B * Hkv * T * K >= 2 ** 31 or K * _BLOCK_TILE >= 2 ** 31:
-        raise ValueError(f'{what}: B·Hkv·T·K = {B * Hkv * T * K} and 64·K must fit int32 indices')
-    _check_k_lens(what, k_lens, B)
-    outer, unit = ('page' if paged else 'batch'), (16 if fp8 else 8)
-    _check_cache_strides(what, kn, k, D, outer, unit)
-    _check_cache_strides(what, vn, v, D, outer, unit)
-    operands = {'q': q, kn: k, vn: v}  # in the order the device check names them
-    if paged:
-        operands['block_table'] = block_table
-    operands.update(block_ids=block_ids, block_counts=block_counts, k_lens=k_lens)
-    if fp8:
-        operands.update(_check_fp8_scales(what, (('k_scale', k_scale), ('v_scale', v_scale)), Hkv, q))
-    operands.update(_check_tree_mask(what, tree_mask, B, T, q))
-    _check_on_device(what, **operands)
-    if scale is None:
-        scale = 1.0 / float(D) ** 0.5
-    if chunk is None:
-        chunk = _decode_chunk(Smax, D)
-    with torch.no_grad():
-        lens = _lens_i32(k_lens)
-        table = (_table_i32(block_table),) if paged else ()
-        qc = q.detach().contiguous()
-        out = torch.empty_like(qc)
-        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
-        if out.numel() > 0:
-            tree = () if tree_mask is None else (tree_mask.detach(),)
-            name = _SELECTED_BINDINGS[paged][fp8]
-            binding = getattr(custom_mm, _tree_binding(name) if tree else _window_binding(name) if win else name)
-            fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
-            binding(block_ids.detach(), block_counts.detach(), qc, k.detach(), v.detach(), *table, lens, float(scale), *fp8_scales,
-                    *tree, *win, int(chunk), out, lse)
-    return (out, lse) if return_lse else out
-
-
 def block_sparse_attention_decode_selected(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
                                            block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, chunk=None,
                                            return_lse: bool = False, tree_mask=None,
@@ -3417,8 +3395,8 @@ def block_sparse_attention_decode_selected(q: torch.Tensor, k: torch.Tensor, v: 
     window, sink (keyword only): as in block_sparse_attention_decode, over the lists — the token sees its last
     `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
     keys; a listed block that the window hides wholly is skipped in its list position.'''
-    return _decode_selected('block_sparse_attention_decode_selected', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens, scale,
-                            chunk, return_lse, tree_mask=tree_mask, window=window, sink=sink)
+    return _read_call('block_sparse_attention_decode_selected', _DECODE_LISTS, ('k', 'v'), q, k, v, None, (block_ids, block_counts),
+                      k_lens, scale, return_lse, chunk=chunk, tree_mask=tree_mask, window=window, sink=sink)
 
 
 def block_sparse_attention_decode_selected_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
@@ -3433,8 +3411,9 @@ def block_sparse_attention_decode_selected_paged(q: torch.Tensor, k_pages: torch
     window, sink (keyword only): as in block_sparse_attention_decode, over the lists — the token sees its last
     `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
     keys; a listed block that the window hides wholly is skipped in its list position.'''
-    return _decode_selected('block_sparse_attention_decode_selected_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
-                            block_ids, block_counts, k_lens, scale, chunk, return_lse, tree_mask=tree_mask, window=window, sink=sink)
+    return _read_call('block_sparse_attention_decode_selected_paged', _DECODE_LISTS, ('k_pages', 'v_pages'), q, k_pages, v_pages,
+                      block_table, (block_ids, block_counts), k_lens, scale, return_lse, chunk=chunk, tree_mask=tree_mask, window=window,
+                      sink=sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -3512,8 +3491,9 @@ def block_sparse_attention_decode_selected_fp8(q: torch.Tensor, k: torch.Tensor,
     window, sink (keyword only): as in block_sparse_attention_decode, over the lists — the token sees its last
     `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
     keys; a listed block that the window hides wholly is skipped in its list position.'''
-    return _decode_selected('block_sparse_attention_decode_selected_fp8', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens,
-                            scale, chunk, return_lse, k_scale, v_scale, True, tree_mask=tree_mask, window=window, sink=sink)
+    return _read_call('block_sparse_attention_decode_selected_fp8', _DECODE_LISTS, ('k', 'v'), q, k, v, None, (block_ids, block_counts),
+                      k_lens, scale, return_lse, chunk=chunk, fp8=True, k_scale=k_scale, v_scale=v_scale, tree_mask=tree_mask,
+                      window=window, sink=sink)
 
 
 def block_sparse_attention_decode_selected_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
@@ -3527,9 +3507,9 @@ def block_sparse_attention_decode_selected_paged_fp8(q: torch.Tensor, k_pages: t
     window, sink (keyword only): as in block_sparse_attention_decode, over the lists — the token sees its last
     `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
     keys; a listed block that the window hides wholly is skipped in its list position.'''
-    return _decode_selected('block_sparse_attention_decode_selected_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages,
-                            block_table, block_ids, block_counts, k_lens, scale, chunk, return_lse, k_scale, v_scale, True, tree_mask=tree_mask,
-                            window=window, sink=sink)
+    return _read_call('block_sparse_attention_decode_selected_paged_fp8', _DECODE_LISTS, ('k_pages', 'v_pages'), q, k_pages, v_pages,
+                      block_table, (block_ids, block_counts), k_lens, scale, return_lse, chunk=chunk, fp8=True, k_scale=k_scale,
+                      v_scale=v_scale, tree_mask=tree_mask, window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
@@ -3656,77 +3636,6 @@ def block_attention_prefill_selected_paged_fp8_takes(dtype, D: int, page: int) -
     return block_attention_prefill_selected_paged_takes(dtype, D, page)
 
 
-_PREFILL_SELECTED_BINDINGS = (('block_attention_lists_prefill', 'block_attention_lists_prefill_fp8'),  # [paged][fp8]
-                              ('block_attention_lists_prefill_paged', 'block_attention_lists_prefill_paged_fp8'))
-
-
-def _prefill_selected(what, names, q, k, v, block_table, block_ids, block_counts, k_lens, scale, new_lens, return_lse, k_scale=None,
-                      v_scale=None, fp8=False, window=None, sink=0):
-    '''The one body of the four list-source prefill calls, beside _decode_selected: _prefill's checks minus the layout ones —
-    no bound on the group, on B·Hkv or on T, q through its own strides, new_lens —, the lists' own with X = ⌈T / 64⌉ + 1 in
-    the place of T, one binding call with the caller's lists as they are.  window, sink: as in _prefill.'''
-    kn, vn = names
-    win = _check_window(what, window, sink)
-    paged = kn == 'k_pages'
-    base_text = _PREFILL_FP8_SIZES_TEXT if fp8 else _PREFILL_SIZES_TEXT
-    sizes_text = base_text + (_PAGED_SIZES_SUFFIX if paged else '')
-    if fp8:
-        _check_lowp_operands(what, (('q', q),), base_text)
-        _check_fp8_cache(what, ((kn, k), (vn, v)), base_text)
-    else:
-        _check_lowp_operands(what, (('q', q), (kn, k), (vn, v)), base_text)
-    for name, t in (('block_ids', block_ids), ('block_counts', block_counts)):
-        if not isinstance(t, torch.Tensor) or t.layout != torch.strided or t.dtype != torch.int32:
-            raise ValueError(f'{what}: {name} must be a dense int32 tensor (select_key_blocks_tiles\' output is handed over as it is)')
-    Smax = _check_cache_shape(what, names, q, k, v, block_table, base_text, None, pool_owner="k_pages's")
-    B, Hq, T, D = q.shape
-    Hkv = k.shape[1]
-    X = block_attention_prefill_tiles(T)
-    if Smax % _BLOCK_TILE != 0:
-        raise ValueError(f'{what}: Smax = {Smax} must be a multiple of 64 (accepted: {sizes_text})')
-    if block_ids.dim() != 4 or tuple(block_ids.shape[:3]) != (B, Hkv, X) or block_ids.shape[3] < 1 or not block_ids.is_contiguous():
-        raise ValueError(f'{what}: block_ids must be a contiguous [B, Hkv, ceil(T/64) + 1, K] = [{B}, {Hkv}, {X}, K >= 1] tensor, got '
-                         f'{tuple(block_ids.shape)}')
-    if tuple(block_counts.shape) != (B, Hkv, X) or not block_counts.is_contiguous():
-        raise ValueError(f'{what}: block_counts must be a contiguous [B, Hkv, ceil(T/64) + 1] = [{B}, {Hkv}, {X}] tensor, got '
-                         f'{tuple(block_counts.shape)}')
-    K = block_ids.shape[3]
-    if max(B * Hq, T, Smax) >= 2 ** 31:
-        raise ValueError(f'{what}: B·Hq = {B * Hq}, T = {T} and Smax = {Smax} must each fit an int32')
-    if B * Hkv * X * K >= 2 ** 31:
-        raise ValueError(f'{what}: B·Hkv·(ceil(T/64) + 1)·K = {B * Hkv * X * K} must fit int32 indices')
-    _check_k_lens(what, k_lens, B)
-    _check_new_lens(what, new_lens, B)
-    _check_source_strides(what, 'q', q)
-    outer, unit = ('page' if paged else 'batch'), (16 if fp8 else 8)
-    _check_cache_strides(what, kn, k, D, outer, unit)
-    _check_cache_strides(what, vn, v, D, outer, unit)
-    operands = {'q': q, kn: k, vn: v}  # in the order the device check names them
-    if paged:
-        operands['block_table'] = block_table
-    operands.update(block_ids=block_ids, block_counts=block_counts, k_lens=k_lens)
-    if new_lens is not None:
-        operands['new_lens'] = new_lens
-    if fp8:
-        operands.update(_check_fp8_scales(what, (('k_scale', k_scale), ('v_scale', v_scale)), Hkv, q))
-    _check_on_device(what, **operands)
-    if scale is None:
-        scale = 1.0 / float(D) ** 0.5
-    with torch.no_grad():
-        lens = _lens_i32(k_lens)
-        news = None if new_lens is None else new_lens.detach().to(torch.int32).contiguous()
-        table = (_table_i32(block_table),) if paged else ()
-        out = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
-        lse = torch.empty((B, Hq, T), device=q.device, dtype=torch.float32)
-        if out.numel() > 0:
-            name = _PREFILL_SELECTED_BINDINGS[paged][fp8]
-            binding = getattr(custom_mm, _window_binding(name) if win else name)
-            fp8_scales = (_fp8_scale(k_scale, q.device), _fp8_scale(v_scale, q.device)) if fp8 else ()
-            binding(block_ids.detach(), block_counts.detach(), q.detach(), k.detach(), v.detach(), *table, lens, news, float(scale),
-                    *fp8_scales, *win, out, lse)
-    return (out, lse) if return_lse else out
-
-
 def block_sparse_attention_prefill_selected(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
                                             block_counts: torch.Tensor, k_lens: torch.Tensor, scale=None, *, new_lens=None,
                                             return_lse: bool = False,
@@ -3756,8 +3665,8 @@ def block_sparse_attention_prefill_selected(q: torch.Tensor, k: torch.Tensor, v:
     window, sink (keyword only): as in block_sparse_attention_prefill, over the lists — the token sees its last
     `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
     keys; a listed block that the window hides from every position of the tile is skipped and never loaded.'''
-    return _prefill_selected('block_sparse_attention_prefill_selected', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens,
-                             scale, new_lens, return_lse, window=window, sink=sink)
+    return _read_call('block_sparse_attention_prefill_selected', _PREFILL_LISTS, ('k', 'v'), q, k, v, None, (block_ids, block_counts),
+                      k_lens, scale, return_lse, new_lens=new_lens, window=window, sink=sink)
 
 
 def block_sparse_attention_prefill_selected_paged(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
@@ -3771,8 +3680,8 @@ def block_sparse_attention_prefill_selected_paged(q: torch.Tensor, k_pages: torc
     window, sink (keyword only): as in block_sparse_attention_prefill, over the lists — the token sees its last
     `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
     keys; a listed block that the window hides from every position of the tile is skipped and never loaded.'''
-    return _prefill_selected('block_sparse_attention_prefill_selected_paged', ('k_pages', 'v_pages'), q, k_pages, v_pages, block_table,
-                             block_ids, block_counts, k_lens, scale, new_lens, return_lse, window=window, sink=sink)
+    return _read_call('block_sparse_attention_prefill_selected_paged', _PREFILL_LISTS, ('k_pages', 'v_pages'), q, k_pages, v_pages,
+                      block_table, (block_ids, block_counts), k_lens, scale, return_lse, new_lens=new_lens, window=window, sink=sink)
 
 
 def block_sparse_attention_prefill_selected_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, block_ids: torch.Tensor,
@@ -3787,8 +3696,8 @@ def block_sparse_attention_prefill_selected_fp8(q: torch.Tensor, k: torch.Tensor
     window, sink (keyword only): as in block_sparse_attention_prefill, over the lists — the token sees its last
     `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
     keys; a listed block that the window hides from every position of the tile is skipped and never loaded.'''
-    return _prefill_selected('block_sparse_attention_prefill_selected_fp8', ('k', 'v'), q, k, v, None, block_ids, block_counts, k_lens,
-                             scale, new_lens, return_lse, k_scale, v_scale, True, window=window, sink=sink)
+    return _read_call('block_sparse_attention_prefill_selected_fp8', _PREFILL_LISTS, ('k', 'v'), q, k, v, None, (block_ids, block_counts),
+                      k_lens, scale, return_lse, new_lens=new_lens, fp8=True, k_scale=k_scale, v_scale=v_scale, window=window, sink=sink)
 
 
 def block_sparse_attention_prefill_selected_paged_fp8(q: torch.Tensor, k_pages: torch.Tensor, v_pages: torch.Tensor,
@@ -3803,9 +3712,9 @@ def block_sparse_attention_prefill_selected_paged_fp8(q: torch.Tensor, k_pages: 
     window, sink (keyword only): as in block_sparse_attention_prefill, over the lists — the token sees its last
     `window` keys, itself included (HF's sliding_window, FlashAttention's window_size = (window − 1, 0)), and the first `sink`
     keys; a listed block that the window hides from every position of the tile is skipped and never loaded.'''
-    return _prefill_selected('block_sparse_attention_prefill_selected_paged_fp8', ('k_pages', 'v_pages'), q, k_pages, v_pages,
-                             block_table, block_ids, block_counts, k_lens, scale, new_lens, return_lse, k_scale, v_scale, True, window=window,
-                             sink=sink)
+    return _read_call('block_sparse_attention_prefill_selected_paged_fp8', _PREFILL_LISTS, ('k_pages', 'v_pages'), q, k_pages, v_pages,
+                      block_table, (block_ids, block_counts), k_lens, scale, return_lse, new_lens=new_lens, fp8=True, k_scale=k_scale,
+                      v_scale=v_scale, window=window, sink=sink)
 
 
 # --------------------------------------------------------------------------- #
